@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: clips/s (15 s @ 22.05 kHz) through HIP CQT + PitchClassNet forward.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path (``ake_pipeline_forward_f32``: CQT -> seq_length fill ->
 network) over B = 256 synthetic sine-mix clips that are already resident in HBM (BASELINE.json
@@ -28,6 +28,13 @@ Extra objects on the line (tier contract):
 `--gpus N` without a launcher (WORLD_SIZE unset) starts N fresh rank processes itself
 (torch.distributed.run, one per GPU, RCCL) BEFORE this process touches the GPU and relays their
 output; a world size that differs from --gpus is a hard error.
+
+`--dump-outputs DIR`: after the timed steps rank 0 writes what the LAST timed step returned as
+DIR/<name>.npy (float32), so that two builds can be compared output for output on the same seeded
+inputs.  Inference: key.npy, tonic.npy, genre.npy, the rows of every rank's clips in rank order.
+--train: the step's loss and metrics (loss.npy, train_<metric>.npy), and the state the step left:
+state.npy (every float state_dict entry after the optimizer step, flattened in state_dict order)
+and grads.npy (the all-reduced parameter gradients, flattened in parameters() order).
 """
 from __future__ import annotations
 
@@ -58,6 +65,7 @@ PEAK_BF16_TFLOPS = 2500.0
 NET_MACS_PER_CLIP = 277_395_712
 PEAK_FP32_TFLOPS = 157.3
 PEAK_HBM_GBS = 8000.0
+DUMP_MAX_BYTES = 64 << 20
 
 
 def kernel_set_hash():
@@ -92,6 +100,23 @@ def pmc_traffic():
         print("bench.py: PMC traffic " + why, file=sys.stderr)
         return name, {}, why
     return name, d["kernels"], None
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: {name: array} -> out_dir/<name>.npy as float32 (float64 stays float64), at most `max_bytes` in all.  Over the
+    limit every array keeps a fixed, seeded sample of its rows (seed 0: arrays with the same number of rows keep the same rows, and
+    the same arguments keep the same rows from run to run)."""
+    arrays = {k: np.asarray(v, np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > max_bytes:
+        for k, a in arrays.items():
+            if a.ndim and a.shape[0] > 1:
+                keep = max(1, int(a.shape[0] * max_bytes / total))
+                arrays[k] = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    print(f"bench.py: wrote {len(arrays)} arrays ({sum(a.nbytes for a in arrays.values())} bytes) to {out_dir}", file=sys.stderr)
 
 
 def load_fixture_weights():
@@ -231,9 +256,11 @@ def train_main(args):
 
     def step(i):
         optim.zero_grad()
-        net.training_step(batch, i)["loss"].backward()
+        d = net.training_step(batch, i)
+        d["loss"].backward()
         optim.grad_scale = D.all_reduce_gradients(net)
         optim.step()
+        return d
 
     # device / host spin-up as in the inference line (--spinup-seconds; untimed, not part of W): the first ~50 steps of a fresh process run
     # 20-60 % slower than the steady state (measured: 20 timed steps after 5 warm-up steps 11.0-15.1 ms, 150 after 30: 9.12 +- 0.01 ms)
@@ -247,10 +274,16 @@ def train_main(args):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(i)
+        d = step(i)
     torch.cuda.synchronize()
     D.barrier()
     dt = D.max_over_ranks(time.perf_counter() - t0, dev)
+    if args.dump_outputs and rank == 0:                                 # before the profiled pass below moves the weights on
+        with torch.no_grad():
+            dumped = {k: v.detach().float().reshape(-1).cpu() for k, v in d.items() if torch.is_tensor(v)}
+            dumped["state"] = torch.cat([v.detach().float().reshape(-1) for v in net.state_dict().values() if v.is_floating_point()]).cpu()
+            dumped["grads"] = torch.cat([p.grad.detach().float().reshape(-1) for p in net.parameters()]).cpu()
+        dump_outputs(args.dump_outputs, {k: v.numpy() for k, v in dumped.items()})
     ake_amd._lib.prof_enable("", True)
     for i in range(args.steps):
         step(i)
@@ -382,7 +415,11 @@ def main():
     ap.add_argument("--no-parity", action="store_true", help="skip the oracle comparison of the last step's rows (profiler runs)")
     ap.add_argument("--train", action="store_true",
                     help="BASELINE configs[3] instead of the headline: one fwd + bwd + gradient all-reduce + fused Adam step per GPU batch")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args.gpus)                                         # never returns; nothing here has touched the GPU yet
     if args.train:
@@ -496,6 +533,9 @@ def main():
     if rank != 0:
         return
     assert rows.shape == (B * world, 35) and bool(torch.isfinite(rows).all())
+    if args.dump_outputs:
+        r = rows.float().cpu().numpy()
+        dump_outputs(args.dump_outputs, {"key": r[:, :12], "tonic": r[:, 12:24], "genre": r[:, 24:35]})
     parity = mirex = None
     if not args.no_parity:
         parity, mirex = parity_and_mirex(rows, batches[last_j], lambda r: first_clip(r, last_j), world, B)

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import REPO
@@ -37,6 +38,32 @@ def test_gpus_n_without_launcher_spawns_n_ranks():
     assert "2-rank launch failed" in out.stderr
     assert out.stderr.count("bench.py needs a GPU") >= 2 or ("rank: 1" in out.stderr or "local_rank: 1" in out.stderr)
     assert not [l for l in out.stdout.splitlines() if l.startswith("{")]
+
+
+def test_steps_must_be_positive():
+    out = subprocess.run([sys.executable, BENCH, "--steps", "0"], env=_env(), capture_output=True, text=True, timeout=300)
+    assert out.returncode != 0 and "--steps must be at least 1" in out.stderr
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    """--dump-outputs: float32 (float64 kept) .npy files; over the byte limit every array keeps the same seeded sample of rows."""
+    sys.path.insert(0, REPO)
+    import bench
+    rng = np.random.default_rng(1)
+    small = {"key": rng.normal(size=(8, 12)).astype(np.float32), "loss": np.float32(0.5), "x64": rng.normal(size=3)}
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    for k, v in small.items():
+        got = np.load(tmp_path / "a" / f"{k}.npy")
+        assert got.dtype == np.asarray(v).dtype and np.array_equal(got, v)
+    big = {"key": rng.normal(size=(1000, 12)).astype(np.float32), "tonic": rng.normal(size=(1000, 12)).astype(np.float32)}
+    bench.dump_outputs(str(tmp_path / "b"), big, max_bytes=10_000)
+    bench.dump_outputs(str(tmp_path / "c"), big, max_bytes=10_000)
+    got = {k: np.load(tmp_path / "b" / f"{k}.npy") for k in big}
+    assert 0 < sum(a.nbytes for a in got.values()) <= 10_000
+    rows = [int(np.flatnonzero((big["key"] == r).all(1))[0]) for r in got["key"]]
+    assert rows == sorted(set(rows)) and np.array_equal(got["tonic"], big["tonic"][rows])
+    for k in big:
+        assert np.array_equal(got[k], np.load(tmp_path / "c" / f"{k}.npy"))
 
 
 def test_pmc_traffic_is_refused_when_stale(tmp_path, monkeypatch):

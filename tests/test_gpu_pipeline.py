@@ -221,6 +221,24 @@ def test_pipeline_at_the_bench_batch(net, gold_default):
     assert torch.equal(torch.cat(est(audio[perm2].contiguous()), 1), out[perm2])
 
 
+def test_bench_dump_outputs_are_the_last_timed_step(net, tmp_path):
+    """`bench.py --dump-outputs DIR` writes the rows the LAST timed step returned: with 3 steps over 2 rotating batches that is batch 0
+    (clips 0..15, not the step before it, clips 16..31), which the estimator of this process reproduces."""
+    import os, subprocess, sys
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "16", "--rotate", "2",
+           "--sustained-seconds", "0", "--pipelined-streams", "0", "--spinup-seconds", "0", "--no-cpu-baseline", "--no-parity",
+           "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+    est = ake_amd.KeyEstimator(net, 22050, 5)
+    audio, _ = synthetic.make_batch_device(range(16), torch.device(DEV))
+    for name, want in zip(("key", "tonic", "genre"), est(audio)):
+        got = np.load(tmp_path / f"{name}.npy")
+        assert got.dtype == np.float32 and got.shape == tuple(want.shape)
+        assert rel_err(got, want) < 1e-5, name
+
+
 def test_bench_starts_its_own_ranks():
     """`python3 bench.py --gpus 2` with NO launcher must start two rank processes itself and print an n_gpus: 2 line (both ranks on
     this GPU, gloo collectives: AKE_REHEARSE_ONE_GPU); a world size that differs from --gpus is a hard error."""

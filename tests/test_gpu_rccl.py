@@ -112,7 +112,17 @@ def test_bench_train_line_through_a_one_rank_rccl_group(tmp_path):
     env = dict(os.environ, AKE_FORCE_PROCESS_GROUP="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--train", "--batch", "16", "--steps", "3", "--warmup", "1",
-                        "--spinup-seconds", "0"], env=env, capture_output=True, text=True, timeout=900)
+                        "--spinup-seconds", "0", "--dump-outputs", str(tmp_path / "dump")], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["collective_backend"] == "nccl" and line["parity"]["max_rel_err"] < 2e-4
+    # --dump-outputs: the last timed step's loss and the weights / gradients it left
+    import numpy as np
+    from argparse import Namespace
+    import ake_amd
+    dump = {n: np.load(tmp_path / "dump" / f"{n}.npy") for n in ("loss", "train_accuracy", "state", "grads")}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in dump.values())
+    assert dump["loss"].shape == (1,) and dump["loss"][0] > 0 and np.abs(dump["grads"]).max() > 0
+    cpu_net = ake_amd.PitchClassNet(288, 12, 2, 7, Namespace(genre=True))
+    assert dump["state"].size == sum(v.numel() for v in cpu_net.state_dict().values() if v.is_floating_point())
+    assert dump["grads"].size == sum(p.numel() for p in cpu_net.parameters())
