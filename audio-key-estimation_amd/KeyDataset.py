@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import synthetic
-from .cqt import get_plan, hop_for
+from .cqt import WHOLE_SONG_FRAMES, get_any_hop_plan, get_plan, hop_for, hop_for_window, whole_song_frames
 
 SIGNATURE = [n + " minor" for n in ("C", "Db", "D", "Eb", "E", "F", "Gb", "G", "Ab", "A", "Bb", "B")] + \
             [n + " major" for n in ("C", "Db", "D", "Eb", "E", "F", "Gb", "G", "Ab", "A", "Bb", "B")]   # KeyDataset.py:524-527
@@ -128,15 +128,35 @@ class WaveformLoader(DatasetLoader):
 
 def cqt_features(waveforms: torch.Tensor, rate: int, opt, lengths=None) -> torch.Tensor:
     """(B, n) waveforms -> log-CQT (B, 36*octaves, T) float32 on the GPU (KeyDataset.py:485-499); ``lengths``: samples per row of
-    a ragged batch (clip i then has ``1 + lengths[i] // hop`` frames, zeros after them)."""
+    a ragged batch (clip i then has ``1 + lengths[i] // hop`` frames, zeros after them).
+
+    ``opt.frames == 0`` (whole songs, KeyDataset.py:485-503, 212-215): clip i gets its own hop ``n_i // opt.window_size + 1``, hence
+    ``T_i = 1 + n_i // hop_i <= window_size`` frames, cropped to ``window_size`` and zero-padded to 592; the result has
+    ``F = max(min(window_size, max T_i), 592)`` frames, clip i's first T_i of them its own, zeros after them."""
     frames = getattr(opt, "frames", 5)
-    if frames <= 0:
-        raise NotImplementedError("opt.frames == 0 (fixed 592-frame windows, KeyDataset.py:490,501-503) is not built")
     if getattr(opt, "only_semitones", False) or getattr(opt, "multi_scale", False):
         raise NotImplementedError("--only_semitones / --multi_scale CQTs are not built (SURVEY.md section 2.1)")
     # opt.cqt_q_mode (not a reference option): 1 selects librosa <= 0.9's filter Q, see ake_amd.cqt.get_plan
-    plan = get_plan(rate, hop_for(rate, frames), 36 * getattr(opt, "octaves", 8), 36, q_mode=int(getattr(opt, "cqt_q_mode", 0)))
+    q_mode, n_bins = int(getattr(opt, "cqt_q_mode", 0)), 36 * getattr(opt, "octaves", 8)
+    if frames <= 0:
+        return whole_song_cqt(waveforms, rate, n_bins, getattr(opt, "window_size", WHOLE_SONG_FRAMES), lengths, q_mode)
+    plan = get_plan(rate, hop_for(rate, frames), n_bins, 36, q_mode=q_mode)
     return plan.logmag(waveforms, lengths=lengths)
+
+
+def whole_song_cqt(waveforms: torch.Tensor, rate: int, n_bins: int = 288, window_size: int = WHOLE_SONG_FRAMES, lengths=None,
+                   q_mode: int = 0) -> torch.Tensor:
+    """--frames 0 front end (see cqt_features): one ragged launch with a hop per clip."""
+    if waveforms.dim() == 1:
+        waveforms = waveforms[None]
+    B, n = waveforms.shape
+    lens_host = torch.full((B,), n, dtype=torch.int64) if lengths is None else torch.as_tensor(lengths).reshape(-1).to("cpu", torch.int64)
+    T_max = int((1 + lens_host // hop_for_window(lens_host, window_size)).max())
+    F = max(min(window_size, T_max), WHOLE_SONG_FRAMES)      # (every T_i <= window_size: the crop of KeyDataset.py:501-503 never cuts)
+    plan = get_any_hop_plan(rate, n_bins, 36, q_mode=q_mode)
+    lens = (lens_host if lengths is None else torch.as_tensor(lengths).reshape(-1)).to(plan.device, torch.int64)
+    hops = hop_for_window(lens, window_size).to(torch.int32)                      # computed on the device
+    return plan.logmag_hops(waveforms, hops, lens if lengths is not None else None, out_frames=F)
 
 
 class KeyDataset:
@@ -188,9 +208,12 @@ class KeyDataset:
             wav, sr = self.datasets[dname].get_waveform(f)
             waves[idx] = torch.as_tensor(wav, dtype=torch.float32).reshape(-1)
             groups[sr].append(idx)
+        frames = getattr(self.opt, "frames", 5)
+        window = getattr(self.opt, "window_size", WHOLE_SONG_FRAMES)
         for sr, idxs in groups.items():
             idxs = sorted(idxs, key=lambda i: waves[i].numel())
-            hop = hop_for(sr, getattr(self.opt, "frames", 5))
+            # frames kept per clip: 1 + n // hop; --frames 0: max(T_i, 592) (KeyDataset.py:212-215)
+            keep = (lambda n: whole_song_frames(n, window)) if frames <= 0 else (lambda n, hop=hop_for(sr, frames): 1 + n // hop)
             for s in range(0, len(idxs), self.cqt_batch):
                 part = idxs[s:s + self.cqt_batch]
                 lens = [waves[i].numel() for i in part]
@@ -203,7 +226,7 @@ class KeyDataset:
                     mel = cqt_features(batch, sr, self.opt, lengths=torch.tensor(lens, dtype=torch.int64))
                 mel = mel.double().cpu()                                               # .double(): KeyDataset.py:509
                 for j, i in enumerate(part):
-                    self.mel[str(i)] = mel[j:j + 1, :, :1 + lens[j] // hop].clone()    # (1, bins, T_i)
+                    self.mel[str(i)] = mel[j:j + 1, :, :keep(lens[j])].clone()          # (1, bins, T_i)
                     self.mel2[str(i)] = None
         for idx, (f, dname, _) in enumerate(self.filenames):
             ld = self.datasets[dname]
@@ -219,6 +242,9 @@ class KeyDataset:
 
     def __getitem__(self, idx):
         mel = self.mel[str(idx)]
+        if getattr(self.opt, "frames", 5) <= 0:                                          # KeyDataset.py:257-262: no seq_length, no padding
+            return {"mel": mel, "key_labels": self.key_labels[str(idx)], "tonic_labels": self.tonic_labels[str(idx)],
+                    "key_signature_id": self.key_signature_id[str(idx)], "genre": self.genre_labels[str(idx)]}
         seq_length = mel.shape[2]
         pad = self.seq_length_max - seq_length
         padded = torch.cat((mel, torch.zeros([mel.shape[0], mel.shape[1], pad], dtype=mel.dtype)), dim=2)   # KeyDataset.py:243-245

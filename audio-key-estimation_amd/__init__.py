@@ -6,7 +6,7 @@ root aliases it).  Reference-shaped modules: ``models`` (PitchClassNet), ``KeyDa
 """
 from . import _lib  # noqa: F401
 from .audio import Resampler, get_resampler, prepare as prepare_audio  # noqa: F401
-from .cqt import CQTPlan, cqt_logmag, get_plan, hop_for  # noqa: F401
+from .cqt import CQTPlan, cqt_logmag, get_any_hop_plan, get_plan, hop_for, hop_for_window  # noqa: F401
 from .KeyDataset import DatasetLoader, KeyDataset, SyntheticSineMixLoader, WaveformLoader  # noqa: F401
 from .metrics import KEY_SIGNATURE_MAP, mirex_score  # noqa: F401
 from .models import PitchClassNet  # noqa: F401

@@ -46,6 +46,8 @@ SYMBOLS = {
     "ake_cqt_workspace_bytes": (_SZ, [_P, _I, _I64]),
     "ake_cqt_logmag_f32": (_I, [_P, _P, _I, _I64, _I64, _P, _I64, _P, _SZ, _P]),
     "ake_cqt_logmag_ragged_f32": (_I, [_P, _P, _I, _I64, _I64, _P, _P, _I64, _P, _SZ, _P]),
+    "ake_cqt_workspace_bytes_hops": (_SZ, [_P, _I, _I64, _I64]),
+    "ake_cqt_logmag_hops_f32": (_I, [_P, _P, _I, _I64, _I64, _P, _P, _P, _I64, _P, _SZ, _P]),
     "ake_cqt_frames_major_supported": (_I, [_P]),
     "ake_cqt_logmag_frames_major_f32": (_I, [_P, _P, _I, _I64, _I64, _P, _P, _SZ, _P]),
     "ake_pcnet_default_config": (_I, [C.POINTER(PcnetConfig), _I, _I]),

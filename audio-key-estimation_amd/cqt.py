@@ -23,6 +23,22 @@ def hop_for(sample_rate: int, frames: int) -> int:
     return int(round(sample_rate / (frames if frames > 0 else 1)))
 
 
+WHOLE_SONG_FRAMES = 592          # --frames 0: the time axis is zero-padded to 592 frames (KeyDataset.py:212-215, hard-coded there)
+
+
+def hop_for_window(n_samples, window_size: int = WHOLE_SONG_FRAMES):
+    """--frames 0 (KeyDataset.py:485,490): ``w_length // opt.window_size + 1``, the whole clip in at most ``window_size`` frames.
+    Works on ints and on integer tensors alike."""
+    return n_samples // window_size + 1
+
+
+def whole_song_frames(n_samples: int, window_size: int = WHOLE_SONG_FRAMES) -> int:
+    """Frames a --frames 0 item has: ``T = 1 + n // hop`` (never more than ``window_size``), cropped to ``window_size``
+    (KeyDataset.py:501-503) and zero-padded to 592 (KeyDataset.py:212-215)."""
+    T = 1 + n_samples // hop_for_window(n_samples, window_size)
+    return max(min(T, window_size), WHOLE_SONG_FRAMES)
+
+
 class CQTPlan:
     """Filter tables for one (sample rate, hop, bins) on one device; reusable across calls."""
 
@@ -91,6 +107,41 @@ class CQTPlan:
                                                        out_frames, ws.data_ptr(), ws.numel(), stream), "ake_cqt_logmag_ragged_f32")
         return out[0] if squeeze else out
 
+    def workspace_bytes_hops(self, batch: int, n_max: int, out_frames: int) -> int:
+        return int(_lib.lib().ake_cqt_workspace_bytes_hops(self._h, int(batch), int(n_max), int(out_frames)))
+
+    def logmag_hops(self, audio: torch.Tensor, hops: torch.Tensor, lengths: torch.Tensor | None = None, *, out_frames: int,
+                    out: torch.Tensor | None = None, workspace: torch.Tensor | None = None) -> torch.Tensor:
+        """Every clip with its own hop (``ake_cqt_logmag_hops_f32``; a plan with an odd hop, see ``get_any_hop_plan``).
+
+        audio (B, n) -> float32 (B, n_bins, out_frames): clip i is transformed at hop ``hops[i]`` (int32 on the device, >= 1) and has
+        ``T_i = 1 + lengths[i] // hops[i]`` frames (``lengths`` (B,) int64: samples of each row; None: every row has n); the output holds
+        its first ``min(T_i, out_frames)`` frames, then zeros.  Nothing waits for the device.  ``workspace``: a uint8 device tensor of at
+        least ``workspace_bytes_hops(B, n, out_frames)`` bytes to use instead of the plan's own (one per stream)."""
+        audio = audio.to(device=self.device, dtype=torch.float32)
+        if audio.stride(-1) != 1:
+            audio = audio.contiguous()
+        B, n = audio.shape
+        out_frames = int(out_frames)
+        hops = torch.as_tensor(hops).to(device=self.device, dtype=torch.int32).contiguous()
+        assert hops.shape == (B,)
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths).to(device=self.device, dtype=torch.int64).contiguous()
+            assert lengths.shape == (B,)
+        if out is None:
+            out = torch.empty((B, self.n_bins, out_frames), dtype=torch.float32, device=self.device)
+        assert out.is_contiguous() and out.shape == (B, self.n_bins, out_frames) and out.dtype == torch.float32
+        L = _lib.lib()
+        nbytes = self.workspace_bytes_hops(B, n, out_frames)
+        ws = self._workspace(nbytes) if workspace is None else workspace
+        assert ws.numel() >= nbytes
+        with torch.cuda.device(self.device):
+            _lib.check(L.ake_cqt_logmag_hops_f32(self._h, audio.data_ptr(), B, n, audio.stride(0),
+                                                 lengths.data_ptr() if lengths is not None else None, hops.data_ptr(), out.data_ptr(),
+                                                 out_frames, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
+                       "ake_cqt_logmag_hops_f32")
+        return out
+
 
 _plans = {}
 
@@ -105,6 +156,12 @@ def get_plan(sr, hop_length, n_bins=288, bins_per_octave=36, device=None, q_mode
     if key not in _plans:
         _plans[key] = CQTPlan(sr, hop_length, n_bins, bins_per_octave, q_mode=q_mode, device=dev)
     return _plans[key]
+
+
+def get_any_hop_plan(sr, n_bins=288, bins_per_octave=36, device=None, q_mode: int = 0) -> CQTPlan:
+    """Cached plan for per-clip hops (``CQTPlan.logmag_hops``): hop_length 1 makes it hold a phase table for every phase of every
+    octave (255 for 8 octaves, about twice a hop-4410 plan's tables).  ``q_mode`` as in get_plan."""
+    return get_plan(sr, 1, n_bins, bins_per_octave, device, q_mode)
 
 
 def cqt_logmag(y, sr=22050, hop_length=512, n_bins=84, bins_per_octave=12, device=None, q_mode: int = 0) -> torch.Tensor:

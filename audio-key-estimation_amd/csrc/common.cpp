@@ -79,7 +79,7 @@ using namespace ake;
 
 extern "C" {
 
-int ake_version(void) { return 101; }
+int ake_version(void) { return 102; }
 int ake_build_has_diag(void) {
 #ifdef AKE_DIAG
     return 1;

@@ -241,6 +241,8 @@ struct CascArgs {
     int ticks_total, ticks_per_seg, warm;
     DecimTaps taps;
     unsigned long long* stamps;   // diagnostic build: [4 waves][16] cycle sums per phase of a tick
+    const int* hops;           // per-clip hops (cqt_cascade_kernel<..., HOPS = true>): clip c's frame centres are multiples of hops[c], and
+                               // need[] holds the plain distances -- each clip applies `2 * need >= hop -> everywhere` itself
 };
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -271,8 +273,8 @@ struct CascLayout {
     static constexpr int total = 2 * (C - (C >> kCascMax)) + 2 * kCascMax * kCascHist;
 };
 
-template <int NODD, int C, int NT, int L, bool SPLIT>
-__device__ __forceinline__ void cascade_level(const CascArgs& a, float* lds, int tid, int clip, int k, bool owned) {
+template <int NODD, int C, int NT, int L, bool SPLIT, bool HOPS>
+__device__ __forceinline__ void cascade_level(const CascArgs& a, float* lds, int tid, int clip, int k, bool owned, int hop_c) {
     using Lay = CascLayout<C>;
     constexpr int chunk_out = C >> (L + 1);                          // outputs of level L+1 per tick
     constexpr int lag_in = L == 0 ? 0 : (L == 1 ? 16 : 24), lag_out = L == 0 ? 16 : 24;   // kLag[L], kLag[L+1]
@@ -281,8 +283,8 @@ __device__ __forceinline__ void cascade_level(const CascArgs& a, float* lds, int
     const float* od = lds + Lay::od(L);
     const int f_prev = ((a.g0 + k * C) >> (L + 1)) - lag_out;        // first sample of level L+1 produced this tick
     float* yrow = a.y[L + 1] ? a.y[L + 1] + clip * a.y_stride[L + 1] + a.pad : nullptr;
-    const int need = a.need[L + 1];
-    const float hopf = static_cast<float>(a.hop), inv_hop = 1.f / hopf;
+    const int need = HOPS && 2 * a.need[L + 1] >= hop_c ? -1 : a.need[L + 1];
+    const float hopf = static_cast<float>(HOPS ? hop_c : a.hop), inv_hop = 1.f / hopf;
 #pragma unroll
     for (int j0 = 0; j0 < chunk_out / 4; j0 += NT) {
         const int j = j0 + tid;
@@ -340,8 +342,9 @@ __device__ __forceinline__ unsigned long long casc_stamp() {
     return t;
 }
 
-// STAMP: diagnostic build (AKE_CQT_CASC_STAMP): s_memtime stamps around the phases of a tick, workgroup (0, 0); never timed
-template <int NODD, int C, int NT, bool SPLIT, bool STAMP = false>
+// STAMP: diagnostic build (AKE_CQT_CASC_STAMP): s_memtime stamps around the phases of a tick, workgroup (0, 0); never timed.
+// HOPS: every clip has its own hop (a.hops[clip]); only the "store near frame centres" predicate depends on it, never a stored value.
+template <int NODD, int C, int NT, bool SPLIT, bool STAMP = false, bool HOPS = false>
 __global__ __launch_bounds__(NT) void cqt_cascade_kernel(CascArgs a) {
     static_assert(C % 512 == 0 && C >= 1024 && (C / 4) % NT == 0, "chunk");
     using Lay = CascLayout<C>;
@@ -385,7 +388,9 @@ __global__ __launch_bounds__(NT) void cqt_cascade_kernel(CascArgs a) {
             if (last) for (int i = hi_beg + a.ppad + 4 * tid; i < a.p_count[l]; i += 4 * NT) *reinterpret_cast<uint4*>(h + i) = make_uint4(0, 0, 0, 0);
         }
     }
-    const float hopf0 = static_cast<float>(a.hop), inv_hop0 = 1.f / hopf0;
+    const int hop_c = HOPS ? max(__builtin_amdgcn_readfirstlane(a.hops[clip]), 1) : a.hop;   // workgroup-uniform: one clip per workgroup
+    const int need0 = HOPS && 2 * a.need[0] >= hop_c ? -1 : a.need[0];                       // (HOPS only)
+    const float hopf0 = static_cast<float>(HOPS ? hop_c : a.hop), inv_hop0 = 1.f / hopf0;
     __syncthreads();
     unsigned long long sm[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ts[10];
     for (int k = k_start; k < k_end; ++k) {
@@ -413,9 +418,9 @@ __global__ __launch_bounds__(NT) void cqt_cascade_kernel(CascArgs a) {
                     const int i0 = a.g0 + k * C + 4 * (tid + NT * g);
                     if (i0 >= 0 && i0 < a.n) {
                         bool store = true;
-                        if (a.need[0] >= 0) {
+                        if ((HOPS ? need0 : a.need[0]) >= 0) {
                             const float pos = static_cast<float>(i0);
-                            store = fabsf(pos - rintf(pos * inv_hop0) * hopf0) <= static_cast<float>(a.need[0]);
+                            store = fabsf(pos - rintf(pos * inv_hop0) * hopf0) <= static_cast<float>(HOPS ? need0 : a.need[0]);
                         }
                         if (store) store_split4(a.ph[0], clip * a.p_stride[0] + i0 + a.ppad, pre[g][0], pre[g][1], pre[g][2], pre[g][3]);
                     }
@@ -439,20 +444,20 @@ __global__ __launch_bounds__(NT) void cqt_cascade_kernel(CascArgs a) {
         if (k + 1 < k_end) fetch(k + 1);                              // next chunk in flight during the whole tick
         __syncthreads();
         if (STAMP) ts[1] = casc_stamp();
-        cascade_level<NODD, C, NT, 0, SPLIT>(a, lds, tid, clip, k, owned);
+        cascade_level<NODD, C, NT, 0, SPLIT, HOPS>(a, lds, tid, clip, k, owned, hop_c);
         __syncthreads();
         if (STAMP) ts[2] = casc_stamp();
-        if (S > 1) { cascade_level<NODD, C, NT, 1, SPLIT>(a, lds, tid, clip, k, owned); __syncthreads(); }
+        if (S > 1) { cascade_level<NODD, C, NT, 1, SPLIT, HOPS>(a, lds, tid, clip, k, owned, hop_c); __syncthreads(); }
         if (STAMP) ts[3] = casc_stamp();
-        if (S > 2) { cascade_level<NODD, C, NT, 2, SPLIT>(a, lds, tid, clip, k, owned); __syncthreads(); }
+        if (S > 2) { cascade_level<NODD, C, NT, 2, SPLIT, HOPS>(a, lds, tid, clip, k, owned, hop_c); __syncthreads(); }
         if (STAMP) ts[4] = casc_stamp();
-        if (S > 3) { cascade_level<NODD, C, NT, 3, SPLIT>(a, lds, tid, clip, k, owned); __syncthreads(); }
+        if (S > 3) { cascade_level<NODD, C, NT, 3, SPLIT, HOPS>(a, lds, tid, clip, k, owned, hop_c); __syncthreads(); }
         if (STAMP) ts[5] = casc_stamp();
-        if (S > 4) { cascade_level<NODD, C, NT, 4, SPLIT>(a, lds, tid, clip, k, owned); __syncthreads(); }
+        if (S > 4) { cascade_level<NODD, C, NT, 4, SPLIT, HOPS>(a, lds, tid, clip, k, owned, hop_c); __syncthreads(); }
         if (STAMP) ts[6] = casc_stamp();
-        if (S > 5) { cascade_level<NODD, C, NT, 5, SPLIT>(a, lds, tid, clip, k, owned); __syncthreads(); }
+        if (S > 5) { cascade_level<NODD, C, NT, 5, SPLIT, HOPS>(a, lds, tid, clip, k, owned, hop_c); __syncthreads(); }
         if (STAMP) ts[7] = casc_stamp();
-        if (S > 6) { cascade_level<NODD, C, NT, 6, SPLIT>(a, lds, tid, clip, k, owned); __syncthreads(); }
+        if (S > 6) { cascade_level<NODD, C, NT, 6, SPLIT, HOPS>(a, lds, tid, clip, k, owned, hop_c); __syncthreads(); }
         if (STAMP) {
             ts[8] = casc_stamp();
 #pragma unroll
@@ -566,6 +571,51 @@ typedef unsigned int u32x4u __attribute__((ext_vector_type(4), aligned(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4b __attribute__((ext_vector_type(4)));
 
+// One 32-tap block of the split product for every N-tile of the octave: de-interleave the lane's 8 (hi << 16 | lo) words into the
+// hi and the lo operand (v_perm_b32: bytes 0-3 index the 2nd source, 4-7 the 1st), then acc += xh*wh + xl*wh + xh*wl.  The same
+// operations in the same order as cqt_bank_bf16_kernel's inner loop (kept written out there: as a call its schedule changed), so a
+// row's result does not depend on which bank computed it.
+__device__ __forceinline__ void bank2_block(f32x4b (&acc)[kMaxTiles], const OctDesc2& g, int blk, int bi, const u32x4u va, const u32x4u vb,
+                                            const uint4* ldsW, int lane) {
+    const u32x4u hv = {__builtin_amdgcn_perm(va[1], va[0], 0x07060302), __builtin_amdgcn_perm(va[3], va[2], 0x07060302),
+                       __builtin_amdgcn_perm(vb[1], vb[0], 0x07060302), __builtin_amdgcn_perm(vb[3], vb[2], 0x07060302)};
+    const u32x4u lv = {__builtin_amdgcn_perm(va[1], va[0], 0x05040100), __builtin_amdgcn_perm(va[3], va[2], 0x05040100),
+                       __builtin_amdgcn_perm(vb[1], vb[0], 0x05040100), __builtin_amdgcn_perm(vb[3], vb[2], 0x05040100)};
+    const bf16x8 ch = __builtin_bit_cast(bf16x8, hv), cl = __builtin_bit_cast(bf16x8, lv);
+#pragma unroll
+    for (int j = 0; j < kMaxTiles; ++j) {
+        if (j < g.n_tiles && blk >= g.blk_lo[j] && blk <= g.blk_hi[j]) {
+            const bf16x8 bh = __builtin_bit_cast(bf16x8, ldsW[((bi * kMaxTiles + j) * 2 + 0) * 64 + lane]);
+            const bf16x8 bl = __builtin_bit_cast(bf16x8, ldsW[((bi * kMaxTiles + j) * 2 + 1) * 64 + lane]);
+            acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ch, bh, acc[j], 0, 0, 0);
+            acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cl, bh, acc[j], 0, 0, 0);
+            acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ch, bl, acc[j], 0, 0, 0);
+        }
+    }
+}
+
+// Stage blocks [b0, b0 + nbc) of one phase table into the LDS with LDS-DMA (global_load_lds_dwordx4): the pieces go straight to the LDS,
+// all in flight at once and without registers.  As a loop of load -> LDS store per iteration this was a chain of up to four dependent
+// memory round trips per chunk behind the A fragments' one (0.070 -> 0.066 ms per 256 clips).  Ends with this wave's vmcnt(0); the
+// caller's barrier then publishes the chunk.  (cqt_bank_bf16_kernel has the same staging written out.)
+__device__ __forceinline__ void bank2_stage(const uint4* w, int b0, int nbc, uint4* ldsW, int wave, int lane) {
+    const uint4* src = w + static_cast<long long>(b0) * (kMaxTiles * 2 * 64);
+    const int total = nbc * kMaxTiles * 2 * 64;                      // a multiple of 64: a wave's piece is whole or absent
+    constexpr int kU = (kBank2Chunk * kMaxTiles * 2 * 64 + kBankThreads - 1) / kBankThreads;
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+        const int i0 = wave * 64 + kBankThreads * u;
+        if (i0 < total) {
+            const uint4* sp = src + i0 + lane;
+            const unsigned int lds_dst = static_cast<unsigned int>(reinterpret_cast<unsigned long long>(ldsW + i0));   // LDS aperture: low 32 bits = byte address
+            unsigned int keep;
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                         : "=&s"(keep) : "v"(sp), "s"(lds_dst) : "memory");
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);                              // vmcnt(0): this wave's pieces (and its A fragments) have landed
+}
+
 __global__ __launch_bounds__(kBankThreads) void cqt_bank_bf16_kernel(
     BankCall2 call, const OctDesc2* __restrict__ octs, const uint4* __restrict__ table,
     int batch, int hop, int hop_twos, float* __restrict__ out, long long out_clip_stride, int n_bins_total, int n_frames, int o_first) {
@@ -668,14 +718,191 @@ __global__ __launch_bounds__(kBankThreads) void cqt_bank_bf16_kernel(
     }
 }
 
+// ---- per-clip hops (ake_cqt_logmag_hops_f32) ------------------------------------------------------------------------
+// With a hop per clip the clips of one frame index t sit at different phases, so they cannot share a staged phase table as in
+// cqt_bank_bf16_kernel.  The work is bucketed by (octave o, phase p) instead: a row (clip, t), t < min(T_clip, out_frames), has phase
+// (t * hop_clip) mod 2^o at octave o.  cqt_rows_count_kernel and cqt_rows_scatter_kernel counting-sort the rows of each octave by phase in
+// the workspace and deal every bucket into chunks of <= kBankClips rows; cqt_bank_rows_bf16_kernel stages a chunk's phase table once and
+// gives each lane its own row's tap window.  Row r = clip * out_frames + t, which is also its frame's offset (in bins) in the
+// [clip][out_frames][bin] scratch.  The sort runs over (kRowsPerGroup rows, octave) workgroups, so its time does not grow with the batch.
+constexpr int kRowsThreads = 256;
+constexpr int kRowsPerThread = 4;
+constexpr int kRowsPerGroup = kRowsThreads * kRowsPerThread;
+constexpr int kMaxPhases = 1 << kCascMax;   // phases of engine 3's deepest octave (<= 8 octaves)
+
+// Adds the lane's row (key = its phase, < 0: none) to bucket counter ctr[key]; RANK: returns the row's slot among the bucket's adds.
+// With few buckets a wave's lanes pile onto one LDS address, so those adds go as one atomic per (wave, bucket).  Call with the whole wave.
+template <bool RANK>
+__device__ __forceinline__ int bucket_add(int* ctr, int key, int np, int lane) {
+    if (np > 8) return key >= 0 ? atomicAdd(&ctr[key], 1) : 0;
+    int slot = 0;
+    for (int p = 0; p < np; ++p) {
+        const unsigned long long m = __ballot(key == p);
+        if (!m) continue;
+        const int leader = __ffsll(static_cast<unsigned long long>(m)) - 1;
+        int base = 0;
+        if (lane == leader) base = atomicAdd(&ctr[p], __popcll(m));
+        if (RANK) {
+            base = __shfl(base, leader);
+            if (key == p) slot = base + static_cast<int>(__builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(m >> 32),
+                                                                                      __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(m), 0u)));
+        }
+    }
+    return slot;
+}
+
+// phase of row r at octave o (np = 2^o phases), or -1 when the row is past its clip's frames (or past the batch)
+__device__ __forceinline__ int row_phase(const long long* __restrict__ n_clip, const int* __restrict__ hops, int n_max, int out_frames, int total,
+                                         int np, int r) {
+    if (r >= total) return -1;
+    const int clip = r / out_frames, t = r - clip * out_frames;
+    int n = n_max;
+    if (n_clip) {                                                      // (a negative length has no frames, as in cqt_transpose_kernel)
+        const long long nc = n_clip[clip];
+        if (nc < 0) return -1;
+        n = nc < n_max ? static_cast<int>(nc) : n_max;
+    }
+    const int h = max(hops[clip], 1);
+    if (t > n / h) return -1;                                          // frames t < T = 1 + n / hop, so t * hop <= n
+    return static_cast<int>((static_cast<long long>(t) * h) & (np - 1));
+}
+
+// grid (ceil(rows / kRowsPerGroup), octaves): counts[o][p] += rows of this workgroup's range at phase p (counts zeroed by the caller)
+__global__ __launch_bounds__(kRowsThreads) void cqt_rows_count_kernel(
+    const long long* __restrict__ n_clip, const int* __restrict__ hops, int batch, int n_max, int out_frames, int* __restrict__ counts) {
+    __shared__ int cnt[kMaxPhases];
+    const int o = blockIdx.y, np = 1 << o, tid = threadIdx.x, lane = tid & 63;
+    for (int p = tid; p < np; p += kRowsThreads) cnt[p] = 0;
+    __syncthreads();
+    const int total = batch * out_frames, r0 = blockIdx.x * kRowsPerGroup;
+#pragma unroll
+    for (int k = 0; k < kRowsPerThread; ++k)
+        bucket_add<false>(cnt, row_phase(n_clip, hops, n_max, out_frames, total, np, r0 + k * kRowsThreads + tid), np, lane);
+    __syncthreads();
+    for (int p = tid; p < np; p += kRowsThreads)
+        if (cnt[p]) atomicAdd(&counts[o * kMaxPhases + p], cnt[p]);
+}
+
+// Same grid.  rows[o][...] = the octave's rows grouped by phase; workgroup (0, o) also writes chunks[o][k] = {phase, first row, rows
+// (<= kBankClips), 0} and n_chunks[o] = chunks used (<= 2^o + ceil(batch * out_frames / kBankClips)).  A workgroup claims a range of each of
+// its buckets with one device atomic on cursors[o][p] (zeroed by the caller).  The order of the rows inside a bucket depends on the
+// atomics; every row is computed on its own, so the result does not.
+__global__ __launch_bounds__(kRowsThreads) void cqt_rows_scatter_kernel(
+    const long long* __restrict__ n_clip, const int* __restrict__ hops, int batch, int n_max, int out_frames, const int* __restrict__ counts,
+    int* __restrict__ cursors, int* __restrict__ rows, long long rows_stride, int4* __restrict__ chunks, int chunks_stride,
+    int* __restrict__ n_chunks) {
+    __shared__ int cnt[kMaxPhases], off[kMaxPhases], tot[kMaxPhases];
+    const int o = blockIdx.y, np = 1 << o, tid = threadIdx.x, lane = tid & 63;
+    for (int p = tid; p < np; p += kRowsThreads) { cnt[p] = 0; tot[p] = counts[o * kMaxPhases + p]; }
+    __syncthreads();
+    for (int p = tid; p < np; p += kRowsThreads) {
+        int s = 0, cs = 0;                                             // exclusive prefix sums of the octave's rows and chunks
+        for (int q = 0; q < p; ++q) { s += tot[q]; cs += (tot[q] + kBankClips - 1) / kBankClips; }
+        off[p] = s;
+        if (blockIdx.x == 0) {                                         // this bucket's chunks
+            const int c = tot[p], nch = (c + kBankClips - 1) / kBankClips;
+            for (int k = 0; k < nch; ++k)
+                chunks[static_cast<long long>(o) * chunks_stride + cs + k] = make_int4(p, s + k * kBankClips, min(kBankClips, c - k * kBankClips), 0);
+            if (p == np - 1) n_chunks[o] = cs + nch;
+        }
+    }
+    __syncthreads();
+    const int total = batch * out_frames, r0 = blockIdx.x * kRowsPerGroup;
+    int key[kRowsPerThread];
+#pragma unroll
+    for (int k = 0; k < kRowsPerThread; ++k) {
+        key[k] = row_phase(n_clip, hops, n_max, out_frames, total, np, r0 + k * kRowsThreads + tid);
+        bucket_add<false>(cnt, key[k], np, lane);
+    }
+    __syncthreads();
+    for (int p = tid; p < np; p += kRowsThreads) {                     // this workgroup's range of bucket p; cnt becomes its local cursor
+        if (cnt[p]) off[p] += atomicAdd(&cursors[o * kMaxPhases + p], cnt[p]);
+        cnt[p] = 0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kRowsPerThread; ++k) {
+        const int slot = bucket_add<true>(cnt, key[k], np, lane);
+        if (key[k] >= 0) rows[o * rows_stride + off[key[k]] + slot] = r0 + k * kRowsThreads + tid;
+    }
+}
+
+// Workgroup = one chunk of one (octave, phase) bucket: cqt_bank_bf16_kernel with the clip and the frame per LANE (its A operand loads were
+// per-lane addressed already) and the phase per workgroup.  grid = (upper bound of any octave's chunks, octaves); the surplus exits.
+__global__ __launch_bounds__(kBankThreads) void cqt_bank_rows_bf16_kernel(
+    BankCall2 call, const OctDesc2* __restrict__ octs, const uint4* __restrict__ table, const int* __restrict__ hops,
+    const int* __restrict__ rows, long long rows_stride, const int4* __restrict__ chunks, int chunks_stride, const int* __restrict__ n_chunks,
+    int out_frames, float* __restrict__ out, int n_bins_total) {
+    extern __shared__ __attribute__((aligned(16))) uint4 ldsW[];
+    const int o = blockIdx.y;
+    if (static_cast<int>(blockIdx.x) >= n_chunks[o]) return;
+    const int4 chk = chunks[static_cast<long long>(o) * chunks_stride + blockIdx.x];
+    const int ph = chk.x, cnt = chk.z;
+    const int* __restrict__ rw = rows + o * rows_stride + chk.y;
+    const OctDesc2 g = octs[o];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int r16 = lane & 15, q = lane >> 4;
+    const int i = wave * 16 + r16;
+    const int r = rw[i < cnt ? i : cnt - 1];                          // idle rows redo the chunk's last row (never stored)
+    const int clip = r / out_frames, t = r - clip * out_frames;
+    const long long c = static_cast<long long>(t) * max(hops[clip], 1);
+    const int c_int = static_cast<int>(c >> o);
+    const uint4* __restrict__ w = table + g.table_off + static_cast<long long>(ph) * g.phase_stride;   // (hop_twos == 0: a table per phase)
+    const long long base = clip * call.stride[o] + (c_int - g.uh + call.pad) + 8 * q;
+    const unsigned int* __restrict__ xw = call.xw[o] + base;
+    f32x4b acc[kMaxTiles];
+#pragma unroll
+    for (int j = 0; j < kMaxTiles; ++j) acc[j] = f32x4b{0.f, 0.f, 0.f, 0.f};
+    const bool idle = wave * 16 >= cnt;                               // whole M-tile beyond the chunk: only helps staging
+#pragma unroll 1
+    for (int b0 = 0; b0 < g.n_blk; b0 += kBank2Chunk) {
+        const int nbc = g.n_blk - b0 < kBank2Chunk ? g.n_blk - b0 : kBank2Chunk;
+        u32x4u xa[kBank2Chunk], xb[kBank2Chunk];
+#pragma unroll
+        for (int bi = 0; bi < kBank2Chunk; ++bi) {
+            const int blk = b0 + (bi < nbc ? bi : nbc - 1);
+            xa[bi] = *reinterpret_cast<const u32x4u*>(xw + 32 * blk);
+            xb[bi] = *reinterpret_cast<const u32x4u*>(xw + 32 * blk + 4);
+        }
+        if (b0) __syncthreads();
+        bank2_stage(w, b0, nbc, ldsW, wave, lane);
+        __syncthreads();
+        if (idle) continue;
+#pragma unroll
+        for (int bi = 0; bi < kBank2Chunk; ++bi)
+            if (bi < nbc) bank2_block(acc, g, b0 + bi, bi, xa[bi], xb[bi], ldsW, lane);
+    }
+    if (idle) return;
+#pragma unroll
+    for (int j = 0; j < kMaxTiles; ++j) {
+        const int b = kTileBins * j + (r16 >> 1);
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const float v2 = acc[j][reg] * acc[j][reg];
+            const float m2 = v2 + __shfl_xor(v2, 1);
+            const int i2 = wave * 16 + 4 * q + reg;
+            if ((r16 & 1) == 0 && j < g.n_tiles && b < g.n_bins && i2 < cnt)
+                out[static_cast<long long>(rw[i2]) * n_bins_total + g.k0 + b] = __logf(1.f + __builtin_amdgcn_sqrtf(m2));
+        }
+    }
+}
+
 // [clip][frame][bin] scratch -> [clip][bin][out_frames] (the reference layout), zero-filling frames >= T
-// (KeyDataset.py:245 padding).  32x32 LDS tile transpose: coalesced on both sides.
+// (KeyDataset.py:245 padding).  32x32 LDS tile transpose: coalesced on both sides.  Per-clip hops (hops != null): clip c has
+// 1 + n_c / hops[c] frames (n_c = n_clip[c], or n_max without n_clip), cropped at T.
 __global__ __launch_bounds__(256) void cqt_transpose_kernel(const float* __restrict__ src, float* __restrict__ dst, int T,
-                                                            int n_bins, int out_frames, const long long* __restrict__ n_clip, int hop) {
+                                                            int n_bins, int out_frames, const long long* __restrict__ n_clip, int hop,
+                                                            const int* __restrict__ hops, long long n_max) {
     __shared__ float tile[32][33];
     const int clip = blockIdx.z;
     int Tc = T;                                                        // ragged batches: frames of THIS clip; the rest is zero padding
-    if (n_clip) { const long long nc = n_clip[clip]; const long long tc = nc < 0 ? 0 : 1 + nc / hop; Tc = tc < T ? static_cast<int>(tc) : T; }
+    if (n_clip || hops) {
+        const long long nc = n_clip ? min(n_clip[clip], n_max) : n_max;
+        const long long h = hops ? max(hops[clip], 1) : hop;
+        const long long tc = nc < 0 ? 0 : 1 + nc / h;
+        Tc = tc < T ? static_cast<int>(tc) : T;
+    }
     const int k0 = blockIdx.x * 32, t0 = blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;           // 32 x 8
     const float* s = src + static_cast<long long>(clip) * T * n_bins;
@@ -739,6 +966,34 @@ int next_len(int64_t n) { return (static_cast<int>((n + 15) / 16) + 2 * kNextPad
 int plane_len(const ake_cqt_plan* p, int l, int64_t n) {   // split words per clip of level l (multiple of 8)
     const int64_t ln = (n + (1ll << l) - 1) >> l;
     return (static_cast<int>(ln) + 2 * pad_of(p) + 2 * p->ppad + 8 + 7) / 8 * 8;
+}
+
+// per-clip hops (engine 3): chunk slots per octave = the bank's grid width, an upper bound of any octave's 2^o + ceil(rows / kBankClips)
+int hops_chunk_slots(const ake_cqt_plan* p, int batch, int64_t out_frames) {
+    return (1 << (p->n_oct - 1)) + static_cast<int>((batch * out_frames + kBankClips - 1) / kBankClips);
+}
+
+struct HopsWork {
+    unsigned int* plane[kMaxOct];
+    float* scratch;           // [clip][out_frames][bin]
+    int* rows;                // [octave][batch * out_frames]
+    int4* chunks;             // [octave][hops_chunk_slots]
+    int* n_chunks;            // [octave]
+    int* counts;              // [2][octave][kMaxPhases]: rows per bucket, then the scatter's cursors (zeroed per call)
+};
+
+// The workspace of ake_cqt_logmag_hops_f32, sized by out_frames (the frame count of a clip is only known on the device).
+HopsWork carve_hops(const ake_cqt_plan* p, ake::Carver& c, int batch, int64_t n_max, int64_t out_frames) {
+    HopsWork w;
+    std::memset(&w, 0, sizeof(w));
+    for (int l = 0; l < p->n_oct; ++l) w.plane[l] = c.take<unsigned int>(static_cast<size_t>(batch) * plane_len(p, l, n_max));
+    const size_t rows = static_cast<size_t>(batch) * out_frames;
+    w.scratch = c.take<float>(rows * p->cfg.n_bins);
+    w.rows = c.take<int>(rows * p->n_oct);
+    w.chunks = c.take<int4>(static_cast<size_t>(hops_chunk_slots(p, batch, out_frames)) * p->n_oct);
+    w.n_chunks = c.take<int>(p->n_oct);
+    w.counts = c.take<int>(static_cast<size_t>(2) * p->n_oct * kMaxPhases);
+    return w;
 }
 
 }  // namespace
@@ -972,6 +1227,9 @@ int ake_cqt_plan_create(const ake_cqt_config* cfg_in, ake_cqt_plan** out) {
             what = "hipFuncSetAttribute(max dynamic LDS)";
             e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(cqt_bank_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      static_cast<int>(p->bank2_lds));
+            if (e2 == hipSuccess && p->engine == 3 && p->hop_twos == 0)      // a plan that can take per-clip hops
+                e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(cqt_bank_rows_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         static_cast<int>(p->bank2_lds));
         }
         if (e2 != hipSuccess) {
             ake::set_error("cqt plan (bf16 tables, %zu B of LDS per workgroup): %s failed: %s", p->bank2_lds, what, hipGetErrorString(e2));
@@ -1019,11 +1277,19 @@ size_t ake_cqt_workspace_bytes(const ake_cqt_plan* p, int batch, int64_t n_sampl
     return ake::align_up(c.off, 256);
 }
 
+size_t ake_cqt_workspace_bytes_hops(const ake_cqt_plan* p, int batch, int64_t n_max, int64_t out_frames) {
+    if (!p || p->engine != 3 || batch <= 0 || n_max <= 0 || out_frames <= 0) return 0;
+    ake::Carver c(nullptr, 0);
+    carve_hops(p, c, batch, n_max, out_frames);
+    return ake::align_up(c.off, 256);
+}
+
 }  // extern "C"
 
 namespace {
 int cqt_logmag_impl(const ake_cqt_plan* p, const float* audio, int batch, int64_t n, int64_t audio_stride, const int64_t* n_clip,
-                    float* out, int64_t out_frames, void* workspace, size_t ws_bytes, ake_stream_t stream_, bool frames_major = false);
+                    float* out, int64_t out_frames, void* workspace, size_t ws_bytes, ake_stream_t stream_, bool frames_major = false,
+                    const int32_t* hops = nullptr);
 }
 
 extern "C" {
@@ -1049,20 +1315,36 @@ int ake_cqt_logmag_ragged_f32(const ake_cqt_plan* p, const float* audio, int bat
     return cqt_logmag_impl(p, audio, batch, n_max, audio_stride, n_samples_dev, out, out_frames, workspace, ws_bytes, stream_);
 }
 
+int ake_cqt_logmag_hops_f32(const ake_cqt_plan* p, const float* audio, int batch, int64_t n_max, int64_t audio_stride, const int64_t* n_clip_dev,
+                            const int32_t* hop_dev, float* out, int64_t out_frames, void* workspace, size_t ws_bytes, ake_stream_t stream_) {
+    AKE_REQUIRE(p, AKE_ERR_INVALID, "ake_cqt_logmag_hops_f32: null plan");
+    AKE_REQUIRE(p->engine == 3, AKE_ERR_UNSUPPORTED, "cqt: per-clip hops need engine 3 (this plan runs engine %d)", p->engine);
+    AKE_REQUIRE(p->hop_twos == 0, AKE_ERR_INVALID, "cqt: per-clip hops need a plan with an odd hop_length (a phase table for every "
+                                                   "phase; create it with hop_length = 1), this one has %d", p->cfg.hop_length);
+    AKE_REQUIRE(hop_dev, AKE_ERR_INVALID, "ake_cqt_logmag_hops_f32: null hop_dev");
+    AKE_REQUIRE(out_frames > 0 && batch > 0 && static_cast<int64_t>(batch) * out_frames <= (1ll << 30), AKE_ERR_INVALID,
+                "cqt: bad batch (%d) / out_frames (%lld)", batch, static_cast<long long>(out_frames));
+    return cqt_logmag_impl(p, audio, batch, n_max, audio_stride, n_clip_dev, out, out_frames, workspace, ws_bytes, stream_, false, hop_dev);
+}
+
 }  // extern "C"
 
 namespace {
 
 int cqt_logmag_impl(const ake_cqt_plan* p, const float* audio, int batch, int64_t n, int64_t audio_stride, const int64_t* n_clip,
-                    float* out, int64_t out_frames, void* workspace, size_t ws_bytes, ake_stream_t stream_, bool frames_major) {
+                    float* out, int64_t out_frames, void* workspace, size_t ws_bytes, ake_stream_t stream_, bool frames_major,
+                    const int32_t* hops) {
     AKE_REQUIRE(p && audio && out, AKE_ERR_INVALID, "ake_cqt_logmag_f32: null argument");
     // frames_major: leave the result as the filter bank writes it, [clip][frame][bin] (no transpose pass); engine 3, equal-length clips
     AKE_REQUIRE(!frames_major || ((p->engine == 3 || p->engine == 5) && !n_clip), AKE_ERR_UNSUPPORTED, "cqt: the frames-major output needs engine 3 or 5 and equal-length clips");
     AKE_REQUIRE(batch > 0 && n > 0 && audio_stride >= n, AKE_ERR_INVALID, "cqt: bad batch/n_samples/stride");
     AKE_REQUIRE(n < (1ll << 30), AKE_ERR_INVALID, "cqt: clip too long (%lld samples)", static_cast<long long>(n));
-    const int64_t T = ake_cqt_num_frames(p, n);
+    // frames per clip the bank computes and the scratch holds: the plan's hop gives every clip T; per-clip hops (engine 3) give clip i
+    // min(1 + n_i / hop_i, out_frames), a count known on the device only, so the scratch has out_frames per clip
+    const int64_t T = hops ? out_frames : ake_cqt_num_frames(p, n);
     AKE_REQUIRE(out_frames >= T, AKE_ERR_INVALID, "cqt: out_frames %lld < %lld frames", static_cast<long long>(out_frames), static_cast<long long>(T));
-    AKE_REQUIRE(ws_bytes >= ake_cqt_workspace_bytes(p, batch, n) && (workspace || p->n_oct == 1), AKE_ERR_WORKSPACE, "cqt: workspace too small");
+    const size_t ws_need = hops ? ake_cqt_workspace_bytes_hops(p, batch, n, out_frames) : ake_cqt_workspace_bytes(p, batch, n);
+    AKE_REQUIRE(ws_bytes >= ws_need && (workspace || p->n_oct == 1), AKE_ERR_WORKSPACE, "cqt: workspace too small");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
 
     ake::Carver c(workspace, ws_bytes);
@@ -1087,7 +1369,9 @@ int cqt_logmag_impl(const ake_cqt_plan* p, const float* audio, int batch, int64_
         dim3 grid((a.ticks_total + a.ticks_per_seg - 1) / a.ticks_per_seg, batch);
         ake::ProfScope ps("cqt_cascade_kernel", stream);
         const bool split = a.ph[0] != nullptr;
-        if (p->half_len == 15 && split) hipLaunchKernelGGL((cqt_cascade_kernel<8, C, NT, true>), grid, dim3(NT), 0, stream, a);
+        if (a.hops && p->half_len == 15) hipLaunchKernelGGL((cqt_cascade_kernel<8, C, NT, true, false, true>), grid, dim3(NT), 0, stream, a);
+        else if (a.hops) hipLaunchKernelGGL((cqt_cascade_kernel<12, C, NT, true, false, true>), grid, dim3(NT), 0, stream, a);
+        else if (p->half_len == 15 && split) hipLaunchKernelGGL((cqt_cascade_kernel<8, C, NT, true>), grid, dim3(NT), 0, stream, a);
         else if (p->half_len == 15) hipLaunchKernelGGL((cqt_cascade_kernel<8, C, NT, false>), grid, dim3(NT), 0, stream, a);
         else if (split) {
             static const bool stamp_env = ake::diag_env("AKE_CQT_CASC_STAMP") != nullptr;
@@ -1176,23 +1460,50 @@ int cqt_logmag_impl(const ake_cqt_plan* p, const float* audio, int batch, int64_
         // second took 0.025 ms whatever its segment count -- a latency chain over 6 ticks -- so the pair gained nothing and was removed.)
         fill_cascade(a, p->n_oct - 1);
         a.ppad = p->ppad;
+        a.hops = hops;
         call2.pad = p->ppad;
+        HopsWork hw{};
+        if (hops) hw = carve_hops(p, c, batch, n, out_frames);
         for (int l = 0; l < p->n_oct; ++l) {
             const int pl = plane_len(p, l, n);
-            a.ph[l] = c.take<unsigned int>(static_cast<size_t>(batch) * pl);
+            a.ph[l] = hops ? hw.plane[l] : c.take<unsigned int>(static_cast<size_t>(batch) * pl);
             a.p_stride[l] = pl; a.p_count[l] = pl;
             call2.xw[l] = a.ph[l]; call2.stride[l] = pl;
-            // taps [c - uh, c - uh + 32 * n_blk) of level l around every frame centre c
+            // taps [c - uh, c - uh + 32 * n_blk) of level l around every frame centre c (per-clip hops: each clip decides "everywhere")
             const OctDesc2& g = p->octs2[l];
             const long long need = static_cast<long long>(std::max(g.uh, 32 * g.n_blk - g.uh) + 8) << l;
-            a.need[l] = 2 * need >= a.hop ? -1 : static_cast<int>(need);
+            a.need[l] = !hops && 2 * need >= a.hop ? -1 : static_cast<int>(need);
         }
         launch_cascade(a);
-        scratch = frames_major ? out : c.take<float>(static_cast<size_t>(batch) * T * p->cfg.n_bins);
-        dim3 grid(static_cast<unsigned>((T + 7) / 8 * 8), p->n_oct, (batch + kBankClips - 1) / kBankClips);
-        ake::ProfScope ps("cqt_bank_bf16_kernel", stream);
-        hipLaunchKernelGGL(cqt_bank_bf16_kernel, grid, dim3(kBankThreads), p->bank2_lds, stream, call2, p->octs2_dev, p->table2_dev, batch,
-                           p->cfg.hop_length, p->hop_twos, scratch, static_cast<long long>(T) * p->cfg.n_bins, p->cfg.n_bins, static_cast<int>(T), 0);
+        if (hops) {
+            scratch = hw.scratch;
+            const long long rows_stride = static_cast<long long>(batch) * out_frames;
+            const int slots = hops_chunk_slots(p, batch, out_frames);
+            {
+                const size_t nc = static_cast<size_t>(p->n_oct) * kMaxPhases;
+                AKE_HIP_CHECK(hipMemsetAsync(hw.counts, 0, 2 * nc * sizeof(int), stream));
+                const dim3 grid_r(static_cast<unsigned>((rows_stride + kRowsPerGroup - 1) / kRowsPerGroup), p->n_oct);
+                const long long* nc_dev = reinterpret_cast<const long long*>(n_clip);
+                {
+                    ake::ProfScope ps("cqt_rows_count_kernel", stream);
+                    hipLaunchKernelGGL(cqt_rows_count_kernel, grid_r, dim3(kRowsThreads), 0, stream, nc_dev, hops, batch, static_cast<int>(n),
+                                       static_cast<int>(out_frames), hw.counts);
+                }
+                ake::ProfScope ps("cqt_rows_scatter_kernel", stream);
+                hipLaunchKernelGGL(cqt_rows_scatter_kernel, grid_r, dim3(kRowsThreads), 0, stream, nc_dev, hops, batch, static_cast<int>(n),
+                                   static_cast<int>(out_frames), hw.counts, hw.counts + nc, hw.rows, rows_stride, hw.chunks, slots, hw.n_chunks);
+            }
+            ake::ProfScope ps("cqt_bank_rows_bf16_kernel", stream);
+            hipLaunchKernelGGL(cqt_bank_rows_bf16_kernel, dim3(slots, p->n_oct), dim3(kBankThreads), p->bank2_lds, stream, call2, p->octs2_dev,
+                               p->table2_dev, hops, hw.rows, rows_stride, hw.chunks, slots, hw.n_chunks, static_cast<int>(out_frames), scratch,
+                               p->cfg.n_bins);
+        } else {
+            scratch = frames_major ? out : c.take<float>(static_cast<size_t>(batch) * T * p->cfg.n_bins);
+            dim3 grid(static_cast<unsigned>((T + 7) / 8 * 8), p->n_oct, (batch + kBankClips - 1) / kBankClips);
+            ake::ProfScope ps("cqt_bank_bf16_kernel", stream);
+            hipLaunchKernelGGL(cqt_bank_bf16_kernel, grid, dim3(kBankThreads), p->bank2_lds, stream, call2, p->octs2_dev, p->table2_dev, batch,
+                               p->cfg.hop_length, p->hop_twos, scratch, static_cast<long long>(T) * p->cfg.n_bins, p->cfg.n_bins, static_cast<int>(T), 0);
+        }
     } else {
         BankCall call;
         std::memset(&call, 0, sizeof(call));
@@ -1248,7 +1559,7 @@ int cqt_logmag_impl(const ake_cqt_plan* p, const float* audio, int batch, int64_
         dim3 grid((p->cfg.n_bins + 31) / 32, static_cast<unsigned>((out_frames + 31) / 32), batch);
         ake::ProfScope ps("cqt_transpose_kernel", stream);
         hipLaunchKernelGGL(cqt_transpose_kernel, grid, dim3(256), 0, stream, scratch, out, static_cast<int>(T), p->cfg.n_bins,
-                           static_cast<int>(out_frames), reinterpret_cast<const long long*>(n_clip), p->cfg.hop_length);
+                           static_cast<int>(out_frames), reinterpret_cast<const long long*>(n_clip), p->cfg.hop_length, hops, static_cast<long long>(n));
     }
     AKE_HIP_CHECK(hipGetLastError());
     return AKE_OK;

@@ -830,6 +830,10 @@ int run_pc_bf16(const ake_pcnet* n, const PackedConv& pc, const unsigned short* 
     return AKE_OK;
 }
 
+// LDS of run_pc_f16x3_full's patch + weight ring for T_dz gradient frames (T_out = T_dz + 6, Tp = T_out + 8)
+size_t pc_f16x3_full_lds(int T_dz) { return (static_cast<size_t>(2) * 12 * (T_dz + 14) * 2 + 2 * 4 * 2 * 64) * sizeof(uint4); }
+bool pc_f16x3_full_ok(int T_dz) { return pc_f16x3_full_lds(T_dz) <= 150 * 1024; }
+
 // f16 x 3 data gradient of a "valid" head convolution (32 -> 16 channels seen from the gradient): full correlation (pad 6 on both sides,
 // T_out = T_dz + 6) of 16 gradient channels (planes) with one half of the transposed + flipped weights; dst [clip][16][12][T_out] (+)=.
 int run_pc_f16x3_full(const ake_pcnet* n, long long frag_off, int kh, const unsigned short* planes, int batch, int T_dz, float* dst, bool accumulate,
@@ -844,8 +848,8 @@ int run_pc_f16x3_full(const ake_pcnet* n, long long frag_off, int kh, const unsi
     AKE_REQUIRE(kh == 12 || kh == 1, AKE_ERR_STATE, "conv %s: kernel rows %d", name, kh);
     a.dst = dst; a.dst_clip_stride = static_cast<long long>(16) * 12 * a.T_out; a.cl_stride = 16;
     a.accumulate = accumulate ? 1 : 0; a.in_amax = in_amax;
-    const size_t lds = (static_cast<size_t>(2) * 12 * a.Tp * 2 + 2 * 4 * 2 * 64) * sizeof(uint4);
-    AKE_REQUIRE(lds <= 150 * 1024, AKE_ERR_UNSUPPORTED, "conv %s: %d frames do not fit the kernel's LDS patch", name, T_dz);
+    const size_t lds = pc_f16x3_full_lds(T_dz);
+    AKE_REQUIRE(pc_f16x3_full_ok(T_dz), AKE_ERR_UNSUPPORTED, "conv %s: %d frames do not fit the kernel's LDS patch", name, T_dz);
     static ake::DeviceOnce attr_set;
     if (attr_set.need()) {
         AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_pc_bf16_kernel<1, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));

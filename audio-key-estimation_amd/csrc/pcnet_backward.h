@@ -229,9 +229,10 @@ struct Bwd {
                                nullptr, 0, amax_for(dz));
         }
         // the heads' first convolutions (16 features -> 32 channels, "valid" in time): 32 gradient channels as two 16-channel halves on the same
-        // kernel, full correlation, the second half (and every head after the first) adding to the feature gradient
+        // kernel, full correlation, the second half (and every head after the first) adding to the feature gradient.  Maps longer than its LDS
+        // patch holds (whole songs: 290 frames at T = 592) take the generic kernel below, as the other head geometries do.
         if (kind == 1 && !same_time && planes_scratch && pd.bf_off >= 0 && pd.bf_off2 >= 0 && pd.cin == 32 && pd.cout == 16 && dst_coff == 0 &&
-            dst_ctot == 16 && T_in == T_dz + 6 && H == 12) {
+            dst_ctot == 16 && T_in == T_dz + 6 && H == 12 && pc_f16x3_full_ok(T_dz)) {
             const long long half = static_cast<long long>(B) * 12 * T_dz * 16 * 2;       // one set of hi + lo planes
             int rc2;
             for (int hf = 0; hf < 2; ++hf) {
@@ -676,9 +677,14 @@ struct Bwd {
         bn_block_backward(m + "pool_semi_b", g, b.semi_raw[layer], b.aff_semi[layer], C, 0, (P / 3) * Tn);
         {
             ake::ProfScope ps("semi_bwd_weight_kernel", s);
-            const size_t lds = std::max<size_t>(static_cast<size_t>(4) * (C * Tn + 3 * C * (Tn + 2)), 4 * 9 * 64) * sizeof(float);
             const size_t cap = 160 * 1024;          // one workgroup per CU beyond 64 KB (--local clips: no time pooling, more frames)
-            AKE_REQUIRE(lds <= cap, AKE_ERR_UNSUPPORTED, "backward: pool_semi weight gradient stages %zu B of LDS per workgroup (got %zu: too many channels x frames)", cap, lds);
+            // frames staged at a time: the whole clip where it fits (one tile), else the most that fit (whole songs: 318 of 592 at 8 channels)
+            auto lds_of = [&](int tc) { return std::max<size_t>(static_cast<size_t>(4) * (C * tc + 3 * C * (tc + 2)), 4 * 9 * 64) * sizeof(float); };
+            int tile = Tn;
+            if (lds_of(tile) > cap) tile = static_cast<int>((cap / (4 * sizeof(float)) / C - 6) / 4);
+            AKE_REQUIRE(tile >= 1 && 3 * C * (std::min(tile, Tn) + 2) < (1 << 16), AKE_ERR_UNSUPPORTED,
+                        "backward: pool_semi weight gradient: %d channels do not fit its LDS slices", C);
+            const size_t lds = lds_of(std::min(tile, Tn));
             static ake::DeviceOnce semi_attr;
             if (lds > kLdsBudget && semi_attr.need()) {
                 AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(semi_bwd_weight_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(cap)));
@@ -689,7 +695,7 @@ struct Bwd {
             const int want = (std::max(tiling_cus(2), 1) + B * pair_groups - 1) / (B * pair_groups);     // workgroups per clip that fill the chip
             const int rows = std::min(kSemiRows, std::max(4, (S + want - 1) / want));
             hipLaunchKernelGGL(semi_bwd_weight_kernel, dim3((S + rows - 1) / rows, B, pair_groups), dim3(256), lds, s, g, x, x_aff,
-                               grad_of(m + "pool_semi.weight"), static_cast<long long>(n->grad_floats), C, P, Tn, rows);
+                               grad_of(m + "pool_semi.weight"), static_cast<long long>(n->grad_floats), C, P, Tn, rows, tile);
         }
         if (ga_x) {
             const long long total = static_cast<long long>(B) * P * Tn;

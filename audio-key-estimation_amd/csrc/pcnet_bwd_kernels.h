@@ -482,21 +482,21 @@ __global__ __launch_bounds__(256) void semi_bwd_data_kernel(const float* __restr
 // Workgroup = (clip, group of rows_per_wg <= kSemiRows output rows: fewer per workgroup at small batches, so that the chip fills), 256 threads = 4 waves; wave w takes rows w, w+4, ...: it stages the
 // dz row of every output channel and the three activated input rows of every input channel in its own LDS slice (with
 // the circular time halo), then lane (co, ci) accumulates its 9 taps over the frames.  One atomic per weight and workgroup.
+// Clips longer than an LDS slice holds (whole songs: 592 frames) are staged in time tiles of `tile` frames, each with its own halo; the
+// tiles run in frame order, so every accumulator receives its products in the same order as with one tile (tile >= T: the untiled pass).
 constexpr int kSemiRows = 48;
 
 __global__ __launch_bounds__(256) void semi_bwd_weight_kernel(const float* __restrict__ dz, const float* __restrict__ x,
                                                               const float* __restrict__ x_aff, gfx_t* __restrict__ dW, long long slot_stride, int C,
-                                                              int H, int T, int rows_per_wg) {
+                                                              int H, int T, int rows_per_wg, int tile) {
     extern __shared__ float semi_lds[];
     const int clip = blockIdx.y;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int S = H / 3;
-    const int Tp = T + 2;
-    float* ldz = semi_lds + wave * (C * T + 3 * C * Tp);      // [co][T]
-    float* lx = ldz + C * T;                                  // [ci][3][T + 2]   (index 0 <-> frame -1)
-    const unsigned int magicT = 0xFFFFFFFFu / static_cast<unsigned int>(T) + 1u;        // floor(i / T) = umulhi(i, magic) for i < 2^16
-    const unsigned int magicTp = 0xFFFFFFFFu / static_cast<unsigned int>(Tp) + 1u;
+    const int TC = tile < T ? tile : T;                       // frames per tile
+    float* ldz = semi_lds + wave * (C * TC + 3 * C * (TC + 2));   // [co][tc]
+    float* lx = ldz + C * TC;                                 // [ci][3][tc + 2]   (index 0 <-> frame t0 - 1)
     const int pairs = C * C;
     const int pair = blockIdx.z * 64 + lane;                  // wider layers (C > 8): blockIdx.z walks the (co, ci) pairs 64 at a time
     const int co = pair / C, ci = pair - co * C;
@@ -505,22 +505,26 @@ __global__ __launch_bounds__(256) void semi_bwd_weight_kernel(const float* __res
     for (int k = 0; k < 9; ++k) acc[k] = 0.f;
     const int s_end = min(S, static_cast<int>(blockIdx.x + 1) * rows_per_wg);
     for (int srow = blockIdx.x * rows_per_wg + wave; srow < s_end; srow += 4) {
+      for (int t0 = 0; t0 < T; t0 += TC) {
+        const int tc = T - t0 < TC ? T - t0 : TC, Tp = tc + 2;
+        const unsigned int magicT = 0xFFFFFFFFu / static_cast<unsigned int>(tc) + 1u;        // floor(i / tc) = umulhi(i, magic) for i < 2^16
+        const unsigned int magicTp = 0xFFFFFFFFu / static_cast<unsigned int>(Tp) + 1u;
         // (index splits by multiply-high with precomputed reciprocals: two integer divisions per staged value were a third of the kernel)
         // Eight loads in flight per lane (round 3): with one load per loop iteration every value waited out a full memory round trip before its
         // LDS store -- 40 dependent round trips per row and wave were this launch's 0.41 ms per step (its arithmetic is a tenth of that).  The
         // loads are branch-free (clamped index), only the stores are guarded.
         constexpr int kU = 8;
-        for (int i0 = lane; i0 < C * T; i0 += 64 * kU) {
+        for (int i0 = lane; i0 < C * tc; i0 += 64 * kU) {
             float v[kU];
 #pragma unroll
             for (int u = 0; u < kU; ++u) {
-                const int i = min(i0 + 64 * u, C * T - 1);
-                const int c = static_cast<int>(__umulhi(static_cast<unsigned int>(i), magicT)), t = i - c * T;
-                v[u] = dz[((static_cast<long long>(clip) * C + c) * S + srow) * T + t];
+                const int i = min(i0 + 64 * u, C * tc - 1);
+                const int c = static_cast<int>(__umulhi(static_cast<unsigned int>(i), magicT)), t = i - c * tc;
+                v[u] = dz[((static_cast<long long>(clip) * C + c) * S + srow) * T + t0 + t];
             }
 #pragma unroll
             for (int u = 0; u < kU; ++u)
-                if (i0 + 64 * u < C * T) ldz[i0 + 64 * u] = v[u];
+                if (i0 + 64 * u < C * tc) ldz[i0 + 64 * u] = v[u];
         }
         for (int i0 = lane; i0 < 3 * C * Tp; i0 += 64 * kU) {
             float v[kU];
@@ -530,7 +534,7 @@ __global__ __launch_bounds__(256) void semi_bwd_weight_kernel(const float* __res
                 const int i = min(i0 + 64 * u, 3 * C * Tp - 1);
                 const int cr = static_cast<int>(__umulhi(static_cast<unsigned int>(i), magicTp));      // (c, r) = i / Tp
                 const int c = static_cast<int>(__umulhi(static_cast<unsigned int>(cr), 0x55555556u)), r = cr - 3 * c, tj = i - cr * Tp;
-                int t = tj - 1;
+                int t = t0 + tj - 1;
                 t += t < 0 ? T : 0;
                 t -= t >= T ? T : 0;
                 cs[u] = c;
@@ -542,7 +546,7 @@ __global__ __launch_bounds__(256) void semi_bwd_weight_kernel(const float* __res
         }
         // a wave's LDS slice is private: no workgroup barrier, the waitcnt the compiler inserts for the reads is enough
         if (pair < pairs) {
-            const float* dr = ldz + co * T;
+            const float* dr = ldz + co * tc;
             const float* xr = lx + ci * 3 * Tp;
             // sliding window over the frames: the three taps of a row share two of their three values with the previous frame (4 LDS reads per
             // frame instead of 10; every accumulator still receives its products in frame order: bit-identical sums)
@@ -550,7 +554,7 @@ __global__ __launch_bounds__(256) void semi_bwd_weight_kernel(const float* __res
 #pragma unroll
             for (int dy = 0; dy < 3; ++dy) { x0[dy] = xr[dy * Tp]; x1[dy] = xr[dy * Tp + 1]; }
 #pragma unroll 4
-            for (int t = 0; t < T; ++t) {                          // (unrolled: the 16 LDS reads of four frames are requested together)
+            for (int t = 0; t < tc; ++t) {                         // (unrolled: the 16 LDS reads of four frames are requested together)
                 const float d = dr[t];
 #pragma unroll
                 for (int dy = 0; dy < 3; ++dy) {
@@ -562,6 +566,7 @@ __global__ __launch_bounds__(256) void semi_bwd_weight_kernel(const float* __res
                 }
             }
         }
+      }
     }
     // one atomic per weight and WORKGROUP: 4096 adders on the 18 cache lines of dW serialise in L2 (measured 1.6 ms when
     // every wave added its own partial sums)

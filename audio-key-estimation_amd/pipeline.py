@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from .audio import get_resampler
-from .cqt import CQTPlan, hop_for
+from .cqt import WHOLE_SONG_FRAMES, CQTPlan, get_any_hop_plan, hop_for, hop_for_window
 from .models import PitchClassNet
 
 
@@ -25,16 +25,28 @@ class KeyEstimator:
     longest clip (the reference pads to the longest clip of the whole dataset, KeyDataset.py:243-245), so a shorter clip's last
     frames wrap into padding and its outputs depend on what it was batched with.  ``"dataset_max"`` (default) is that
     behaviour, bit for bit.  ``"true_end"`` (opt-in) wraps every clip at its OWN last frame: clips are
-    grouped by frame count and each group runs unpadded, so a clip's outputs are those of the clip alone."""
+    grouped by frame count and each group runs unpadded, so a clip's outputs are those of the clip alone.
+
+    ``frames=0``: the reference's whole-song mode (``--frames 0 --window_size W``, KeyDataset.py:485-503, 212-215, models.py:842-847).
+    Clip i is transformed at its own hop ``n_i // W + 1`` (``n_i`` = ``lengths[i]``, or n), which gives ``T_i <= W`` frames, zero-padded
+    to F = 592 frames (the reference's item width; for W > 592, ``F = max(min(W, max T_i), 592)``, which reads the lengths on the host).
+    The net then runs on (B, 1, n_bins, F) with ``seq_length=None``: its pooling covers all F frames, the zero tail included, as the
+    reference's does.  ``wrap_mode`` has no meaning here ("true_end" is refused)."""
 
     def __init__(self, net: PitchClassNet, sample_rate: int = 22050, frames: int = 5, streams: int = 1, wrap_mode: str = "dataset_max",
-                 q_mode: int = 0):
+                 q_mode: int = 0, window_size: int = WHOLE_SONG_FRAMES):
         if wrap_mode not in ("dataset_max", "true_end"):
             raise ValueError("wrap_mode must be 'dataset_max' or 'true_end'")
+        if frames <= 0 and wrap_mode == "true_end":
+            raise ValueError("wrap_mode 'true_end' has no meaning with frames=0 (every clip is zero-padded to the same width)")
         self.net = net.eval()
         self.device = net._device()
         self.sample_rate, self.wrap_mode = int(sample_rate), wrap_mode
-        self.plan = CQTPlan(sample_rate, hop_for(sample_rate, frames), net.pitches, 36, q_mode=q_mode, device=self.device)   # q_mode: ake_amd.cqt.get_plan
+        self.frames, self.window_size = int(frames), int(window_size)
+        if self.frames <= 0:
+            self.plan = get_any_hop_plan(sample_rate, net.pitches, 36, device=self.device, q_mode=q_mode)
+        else:
+            self.plan = CQTPlan(sample_rate, hop_for(sample_rate, frames), net.pitches, 36, q_mode=q_mode, device=self.device)   # q_mode: ake_amd.cqt.get_plan
         self.streams = max(1, int(streams))
         self._slots = [{"ws": None, "stream": None} for _ in range(self.streams)]
         self._turn = 0
@@ -55,7 +67,7 @@ class KeyEstimator:
         ``lengths`` (B,) int64: ragged batch, row i holds ``lengths[i] <= n`` samples; every clip is pooled over its own frames
         (``seq_length`` = ``1 + lengths[i] // hop``), as a ``KeyDataset`` batch of unequal clips is (KeyDataset.py:245-256).
         ``rate``: sample rate of ``audio`` when it is not the estimator's -- it is resampled on the device first
-        (``scipy.signal.resample_poly``'s filter); ``channel``: which channel of (B, C, n) audio to take (0 = the reference's
+        (``scipy.signal.resample_poly``'s filter; with ``frames=0`` each clip's hop is then taken from its resampled length); ``channel``: which channel of (B, C, n) audio to take (0 = the reference's
         ``waveform[0]``, KeyDataset.py:480) or -1 for the mean of all."""
         self.net._sync_weights(self.device, for_eval=True)
         if audio.dim() == 3 or (rate is not None and int(rate) != self.sample_rate):
@@ -83,6 +95,8 @@ class KeyEstimator:
 
     def _run_wrapped(self, slot, audio, lengths):
         """wrap_mode "true_end": one unpadded call per distinct frame count (the clips of a group share T, so no frame is padding)."""
+        if self.frames <= 0:
+            return self._run_whole_song(slot, audio, lengths)
         if self.wrap_mode != "true_end" or lengths is None:
             return self._run(slot, audio, lengths)
         lengths = torch.as_tensor(lengths).to(device=self.device, dtype=torch.int64)
@@ -128,4 +142,37 @@ class KeyEstimator:
                                                              key.data_ptr(), tonic.data_ptr(), genre.data_ptr() if genre is not None else None,
                                                              ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
                            "ake_pipeline_forward_ragged_f32")
+        return (key, tonic, genre) if net.genre else (key, tonic)
+
+    def _run_whole_song(self, slot, audio, lengths):
+        """frames=0: per-clip-hop CQT, then the net at (B, 1, n_bins, F) with no seq_length; one stream, no host synchronisation
+        (W <= 592, or host lengths)."""
+        net, L = self.net, _lib.lib()
+        audio = audio.to(device=self.device, dtype=torch.float32)
+        if audio.stride(-1) != 1:
+            audio = audio.contiguous()
+        B, n = audio.shape
+        W = self.window_size
+        if W <= WHOLE_SONG_FRAMES:
+            F = WHOLE_SONG_FRAMES                                    # T_i <= W <= 592
+        else:                                                        # (the width depends on the longest clip's frame count)
+            lens_host = torch.full((B,), n, dtype=torch.int64) if lengths is None else torch.as_tensor(lengths).cpu().to(torch.int64)
+            F = max(min(W, int((1 + lens_host // hop_for_window(lens_host, W)).max())), WHOLE_SONG_FRAMES)
+        if lengths is None:
+            hops = torch.full((B,), hop_for_window(n, W), dtype=torch.int32, device=self.device)
+        else:
+            lengths = torch.as_tensor(lengths).to(device=self.device, dtype=torch.int64).contiguous()
+            hops = hop_for_window(lengths, W).to(torch.int32)
+        nbytes = max(self.plan.workspace_bytes_hops(B, n, F), int(L.ake_pcnet_workspace_bytes(net.handle, B, F)))
+        if slot["ws"] is None or slot["ws"].numel() < nbytes:
+            slot["ws"] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=self.device)
+        ws = slot["ws"]                                              # the CQT's, then (same stream, after it) the net's
+        mel = self.plan.logmag_hops(audio, hops, lengths, out_frames=F, workspace=ws)
+        key = torch.empty((B, 12), dtype=torch.float32, device=self.device)
+        tonic = torch.empty((B, 12), dtype=torch.float32, device=self.device)
+        genre = torch.empty((B, 11), dtype=torch.float32, device=self.device) if net.genre else None
+        with torch.cuda.device(self.device):
+            _lib.check(L.ake_pcnet_forward_f32(net.handle, mel.data_ptr(), B, F, None, key.data_ptr(), tonic.data_ptr(),
+                                               genre.data_ptr() if genre is not None else None, ws.data_ptr(), ws.numel(),
+                                               torch.cuda.current_stream().cuda_stream), "ake_pcnet_forward_f32")
         return (key, tonic, genre) if net.genre else (key, tonic)

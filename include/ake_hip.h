@@ -96,6 +96,18 @@ int ake_cqt_logmag_ragged_f32(const ake_cqt_plan* plan, const float* audio_dev, 
                               int64_t audio_stride, const int64_t* n_samples_dev, float* out_dev, int64_t out_frames,
                               void* workspace, size_t workspace_bytes, ake_stream_t stream);
 
+/* Per-clip hops (the reference's whole-song mode, --frames 0: hop_i = n_i / window_size + 1, KeyDataset.py:485-490).  Clip i has
+ * n_i = n_clip_dev[i] samples (int64; null: every clip has n_max), hop hop_dev[i] (int32, device) and T_i = 1 + n_i / hop_i frames.
+ * out_dev = [batch][n_bins][out_frames]: clip i's first min(T_i, out_frames) frames, then zeros.  The plan must be engine 3 with an odd
+ * hop_length (hop_twos == 0: it holds a phase table for every phase; create it with hop_length = 1) -- engines 1, 2 and 5 give
+ * AKE_ERR_UNSUPPORTED, an even hop AKE_ERR_INVALID.  Hops < 1 are the caller's contract: the results for such a clip are unspecified
+ * (the kernels read them as 1 and stay in bounds).  Workspace from ake_cqt_workspace_bytes_hops, sized by out_frames (the frame counts
+ * are only known on the device); no host synchronisation. */
+size_t ake_cqt_workspace_bytes_hops(const ake_cqt_plan* plan, int batch, int64_t n_max, int64_t out_frames);
+int ake_cqt_logmag_hops_f32(const ake_cqt_plan* plan, const float* audio_dev, int batch, int64_t n_max, int64_t audio_stride,
+                            const int64_t* n_clip_dev, const int32_t* hop_dev, float* out_dev, int64_t out_frames, void* workspace,
+                            size_t workspace_bytes, ake_stream_t stream);
+
 /* Frames-major output: the same transform left as the filter bank writes it, out_dev = [batch][num_frames][n_bins] -- no transpose
  * pass (a 48 MB round trip per 256 clips).  For consumers that can read that order: ake_pcnet_forward_frames_major_f32, and
  * ake_pipeline_forward_f32 uses the pair internally.  Engine 3, equal-length clips (ake_cqt_frames_major_supported). */
