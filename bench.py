@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: clips/s (15 s @ 22.05 kHz) through HIP CQT + PitchClassNet forward.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (``ake_pipeline_forward_f32``: CQT -> seq_length fill ->
 network) over B = 256 synthetic sine-mix clips that are already resident in HBM (BASELINE.json
@@ -9,21 +9,29 @@ configs[1]).  For N > 1 the driver launches this file under ``torch.distributed.
 owns 256 clips of its own (weak scaling, clips are independent, no data-path collective) and the
 step time is the max over ranks.  Rank 0 prints ONE JSON line.
 
-Extra objects on the line (tier contract):
+A plain run does only what the headline needs: set-up, spin-up, the W warm-up steps, the K timed
+steps, the --dump-outputs files and the line.  Its extra object:
   roofline      dominant kernel (conv_p2p_f16_kernel: the 7x7 circular pitch convolutions, 65 % of
                 the MACs): algorithmic FLOPs (2 x MACs) of its launches / their hipEvent-measured
                 duration, vs the 2.5 PFLOP/s dense f16 / bf16 MFMA peak of MI355X; the kernel multiplies
                 f16 activations with f16 weights, one MFMA product per MAC.
-  roofline_cqt  the CQT stage against the 8 TB/s HBM peak (1 410 552 algorithmic bytes per clip).
+
+`--full` adds everything that takes passes or host work of its own (tier contract); without it these
+objects are null and cpu_baseline is absent:
+  roofline.single_stream, roofline_cqt, kernel_ms_per_step
+                a second, untimed pass with every kernel bracketed; roofline_cqt is the CQT stage
+                against the 8 TB/s HBM peak (1 410 552 algorithmic bytes per clip).
   cpu_baseline  the CPU oracle (direct-form CQT as BLAS matmuls + the oracle network) timed on this
                 box's host cores on a bounded sample: BASELINE.md section 3's cases (fp32 / fp64, B = 1 /
                 B = 32, CQT and network separately, best of several thread counts); `value` = the
                 float64 (reference dtype) B = 1 (eval.py's batch size) whole-path rate.
   parity        max relative error of four clips of the LAST timed step against the CPU oracle
                 (outside the timed region) and a MIREX sanity score of the whole batch.
+  pipelined     the same K steps again, with --pipelined-streams steps in flight.
   sustained     >= 2 s of steps rotating over >= 4 distinct resident batches (> 256 MiB of audio, so
                 no step is served from the Infinity Cache), with its own ms_per_step and the dominant
                 kernel's mean launch duration at that steady state.
+With --train, --full adds the per-kernel pass (kernel_ms_per_step); the step-0 parity runs either way.
 
 `--gpus N` without a launcher (WORLD_SIZE unset) starts N fresh rank processes itself
 (torch.distributed.run, one per GPU, RCCL) BEFORE this process touches the GPU and relays their
@@ -251,8 +259,10 @@ def train_main(args):
     net.train()
     net.trainer = ake_amd.Trainer(accumulate_grad_batches=1)
     parity = None
+    # step 0, outside the timed region (weights untouched: no optimizer step); not behind --full: its train-mode passes move the
+    # BatchNorm running statistics that --dump-outputs writes to state.npy
     if not args.no_parity:
-        parity = train_parity(net, sd, batch, rank)                     # step 0, outside the timed region (weights untouched: no optimizer step)
+        parity = train_parity(net, sd, batch, rank)
 
     def step(i):
         optim.zero_grad()
@@ -284,16 +294,18 @@ def train_main(args):
             dumped["state"] = torch.cat([v.detach().float().reshape(-1) for v in net.state_dict().values() if v.is_floating_point()]).cpu()
             dumped["grads"] = torch.cat([p.grad.detach().float().reshape(-1) for p in net.parameters()]).cpu()
         dump_outputs(args.dump_outputs, {k: v.numpy() for k, v in dumped.items()})
-    ake_amd._lib.prof_enable("", True)
-    for i in range(args.steps):
-        step(i)
-    torch.cuda.synchronize()
-    prof_all = ake_amd._lib.prof_results()
-    ake_amd._lib.prof_enable("", False)
+    kernel_ms = None
+    if args.full:
+        ake_amd._lib.prof_enable("", True)
+        for i in range(args.steps):
+            step(i)
+        torch.cuda.synchronize()
+        prof_all = ake_amd._lib.prof_results()
+        ake_amd._lib.prof_enable("", False)
+        kernel_ms = {k: round(v[0] / args.steps, 4) for k, v in sorted(prof_all.items(), key=lambda kv: -kv[1][0])}
     if rank != 0:
         return
     value = B * world * args.steps / dt
-    kernel_ms = {k: round(v[0] / args.steps, 4) for k, v in sorted(prof_all.items(), key=lambda kv: -kv[1][0])}
     print(json.dumps({
         "metric": "clips/s, PitchClassNet training step (fwd + bwd + grad all-reduce + Adam)", "value": round(value, 1), "unit": "clips/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
@@ -302,7 +314,7 @@ def train_main(args):
                  "dropped), their weight gradient as split bf16 x 3, everything else f32 MFMA", "data": "synthetic",
         "config": {"workload": f"BASELINE configs[3]: {B} clips per GPU (288x76 log-CQT resident), default PitchClassNet, local BatchNorm, "
                                f"one all-reduce of the flat gradient buffer per step, fused Adam lr 3e-4",
-                   "clips_per_gpu": B, "parallelism": f"data-parallel x{world}", "spinup_steps": n_spin},
+                   "clips_per_gpu": B, "parallelism": f"data-parallel x{world}", "spinup_steps": n_spin, "full": args.full},
         # fwd + data gradient + weight gradient = 3 x the forward's MACs, algorithmic, against the dense f16 / bf16 MFMA peak the kernels
         # multiply on (NOT the 157 TF f32 peak: VERDICT r2 item 7); every algorithmic MAC costs 3 MFMA products in these kernel families
         # (f16 hi + lo x 3, split bf16 x 3), so the matrix pipe's own ceiling for this formulation is a third of the peak
@@ -417,6 +429,9 @@ def main():
                     help="BASELINE configs[3] instead of the headline: one fwd + bwd + gradient all-reduce + fused Adam step per GPU batch")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the all-kernel pass (roofline_cqt, kernel_ms_per_step), the pipelined and "
+                         "sustained passes, the oracle parity and the CPU baseline (--train: the all-kernel pass); off: those objects are null")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -477,19 +492,22 @@ def main():
     D.barrier()
     dt = time.perf_counter() - t0
     prof = ake_amd._lib.prof_results()
+    ake_amd._lib.prof_enable("", False)
     last_j = (args.steps - 1) % R
     # second, untimed pass, one step after the other on one stream with every kernel bracketed: per-kernel breakdown, the CQT stage's
     # roofline, and the dominant kernel's duration when nothing else shares the GPU with it
-    ake_amd._lib.prof_enable("", True)
-    for i in range(args.steps):
-        est1(batches[i % R])
-    torch.cuda.synchronize()
-    prof_all = ake_amd._lib.prof_results()
-    ake_amd._lib.prof_enable("", False)
+    prof_all = None
+    if args.full:
+        ake_amd._lib.prof_enable("", True)
+        for i in range(args.steps):
+            est1(batches[i % R])
+        torch.cuda.synchronize()
+        prof_all = ake_amd._lib.prof_results()
+        ake_amd._lib.prof_enable("", False)
     dt = D.max_over_ranks(dt, dev)
     # third pass (timers off): the same steps with several in flight -- the throughput a serving loop over independent batches gets
     dt_pipe = None
-    if args.pipelined_streams > 1 and args.streams == 1:
+    if args.full and args.pipelined_streams > 1 and args.streams == 1:
         estp = ake_amd.KeyEstimator(net, SR, FRAMES, streams=args.pipelined_streams)
         for i in range(2 * args.pipelined_streams):
             estp(batches[i % R])
@@ -506,7 +524,7 @@ def main():
     # sustained pass: the timed region's steps again, for >= --sustained-seconds (the step count is fixed from the timed region's
     # rate so that every rank runs the same number), dominant kernel bracketed as in the timed region
     sustained = None
-    if args.sustained_seconds > 0:
+    if args.full and args.sustained_seconds > 0:
         n_sus = max(args.steps, int(args.sustained_seconds / (dt / args.steps) * 1.1) + 1)
         ake_amd._lib.lib().ake_prof_reset()
         ake_amd._lib.prof_enable(DOM, True)
@@ -537,7 +555,7 @@ def main():
         r = rows.float().cpu().numpy()
         dump_outputs(args.dump_outputs, {"key": r[:, :12], "tonic": r[:, 12:24], "genre": r[:, 24:35]})
     parity = mirex = None
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         parity, mirex = parity_and_mirex(rows, batches[last_j], lambda r: first_clip(r, last_j), world, B)
         assert parity["max_rel_err"] < 1e-3, f"parity vs the oracle: {parity}"
 
@@ -548,17 +566,27 @@ def main():
     launches_per_step = p2p_n / args.steps if args.steps else 0
     p2p_flops = 2.0 * P2P_MACS_PER_CLIP * B * args.steps              # algorithmic: (5*8 + 8*8 + 8*8) * 49 MACs per position
     achieved = p2p_flops / (p2p_ms * 1e-3) / 1e12 if p2p_ms > 0 else None
-    cqt_ms = sum(prof_all.get(k, (0.0, 0))[0] for k in prof_all if k.startswith("cqt_"))
-    cqt_gbs = CQT_BYTES_PER_CLIP * B * args.steps / (cqt_ms * 1e-3) / 1e9 if cqt_ms > 0 else None
-    kernel_ms = {k: round(v[0] / args.steps, 4) for k, v in sorted(prof_all.items(), key=lambda kv: -kv[1][0])}
-    p2p1_ms, p2p1_n = prof_all.get(DOM, (0.0, 0))
-    achieved1 = p2p_flops / (p2p1_ms * 1e-3) / 1e12 if p2p1_ms > 0 else None
     traffic_src, traffic, traffic_stale = pmc_traffic()
     p2p_traffic = cqt_traffic = None
     if B == 256 and traffic:
         bf_rows = [v for k, v in traffic.items() if k.startswith("conv_p2p_f16")]
         p2p_traffic = round(sum(v["hbm_bytes"] * v["dispatches"] for v in bf_rows) / max(1, sum(v["dispatches"] for v in bf_rows))) if bf_rows else None
         cqt_traffic = sum(v["hbm_bytes"] for k, v in traffic.items() if k.startswith("cqt_")) or None
+    single_stream = roofline_cqt = kernel_ms = None
+    if prof_all is not None:                                            # --full: the second, all-kernel pass
+        cqt_ms = sum(prof_all.get(k, (0.0, 0))[0] for k in prof_all if k.startswith("cqt_"))
+        cqt_gbs = CQT_BYTES_PER_CLIP * B * args.steps / (cqt_ms * 1e-3) / 1e9 if cqt_ms > 0 else None
+        kernel_ms = {k: round(v[0] / args.steps, 4) for k, v in sorted(prof_all.items(), key=lambda kv: -kv[1][0])}
+        p2p1_ms, p2p1_n = prof_all.get(DOM, (0.0, 0))
+        achieved1 = p2p_flops / (p2p1_ms * 1e-3) / 1e12 if p2p1_ms > 0 else None
+        single_stream = {"achieved": round(achieved1, 2) if achieved1 else None,
+                         "frac": round(achieved1 / DOM_PEAK, 4) if achieved1 else None,
+                         "avg_launch_ms": round(p2p1_ms / p2p1_n, 4) if p2p1_n else None,
+                         "note": "same launches in the second, untimed pass: one step after the other on one stream"}
+        roofline_cqt = {"bound": "hbm", "kernels": " + ".join(sorted(k for k in prof_all if k.startswith("cqt_"))), "achieved": round(cqt_gbs, 1) if cqt_gbs else None,
+                        "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(cqt_gbs / PEAK_HBM_GBS, 4) if cqt_gbs else None,
+                        "traffic": cqt_traffic, "algorithmic_bytes_per_step": CQT_BYTES_PER_CLIP * B, "algorithmic_bytes_per_clip": CQT_BYTES_PER_CLIP,
+                        "stage_ms_per_step": round(cqt_ms / args.steps, 4)}
     line = {
         "metric": "clips/s (15 s @ 22.05 kHz), HIP CQT + PitchClassNet forward",
         "value": round(value, 1), "unit": "clips/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -570,7 +598,7 @@ def main():
                    "clips_per_gpu": B, "n_samples": N_SAMPLES, "frames": T_FRAMES, "weights": "tests/golden/pcnet_default.npz (seeded)",
                    "distinct_batches": R, "resident_audio_bytes_per_gpu": R * B * N_SAMPLES * 4, "spinup_seconds": args.spinup_seconds,
                    "parallelism": f"clip-sharded x{world}, no data-path collective",
-                   "streams": args.streams,
+                   "streams": args.streams, "full": args.full,
                    "steps_in_flight": f"{args.streams}: every step is the whole path over one batch; consecutive steps go round-robin to "
                                       f"{args.streams} streams with a workspace each (KeyEstimator(streams=...))" if args.streams > 1 else "1"},
         "roofline": {"bound": "mfma",
@@ -590,20 +618,14 @@ def main():
                      "algorithmic_bytes_per_launch": B * T_FRAMES * ((4 * (P + 4 * 36) + 2 * 8 * P) + (2 * 8 * P + 2 * 8 * P) + (2 * 8 * P + 4 * 8 * 12)) // 3,
                      "avg_launch_ms": round(p2p_ms / p2p_n, 4) if p2p_n else None, "launches_per_step": launches_per_step,
                      "note": "measured in the timed region: with streams > 1 another step's kernels share the GPU with these launches" if args.streams > 1 else None,
-                     "single_stream": {"achieved": round(achieved1, 2) if achieved1 else None,
-                                       "frac": round(achieved1 / DOM_PEAK, 4) if achieved1 else None,
-                                       "avg_launch_ms": round(p2p1_ms / p2p1_n, 4) if p2p1_n else None,
-                                       "note": "same launches in the second, untimed pass: one step after the other on one stream"},
+                     "single_stream": single_stream,
                      "algorithmic_flops_per_clip": 2 * P2P_MACS_PER_CLIP,
                      # `peak` is the data-sheet figure the contract asks for.  What a pure v_mfma_f32_16x16x32_f16 stream (4 waves per SIMD, nothing
                      # else issued) sustains on this part, measured by tools/micro/mfma_data_power.hip: 1 365 TFLOP/s with zero operands, 1 185 with
                      # random ones, whether the launch lasts 0.25 ms or 180 ms (profiles/r03_b_mfma_data_power.txt)
                      "measured_mfma_stream_tflops": {"zero_operands": 1365.0, "random_operands": 1185.0, "source": "profiles/r03_b_mfma_data_power.txt",
                                                      "frac_of_random": round(achieved / 1185.0, 4) if achieved else None}},
-        "roofline_cqt": {"bound": "hbm", "kernels": " + ".join(sorted(k for k in prof_all if k.startswith("cqt_"))), "achieved": round(cqt_gbs, 1) if cqt_gbs else None,
-                         "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(cqt_gbs / PEAK_HBM_GBS, 4) if cqt_gbs else None,
-                         "traffic": cqt_traffic, "algorithmic_bytes_per_step": CQT_BYTES_PER_CLIP * B, "algorithmic_bytes_per_clip": CQT_BYTES_PER_CLIP,
-                         "stage_ms_per_step": round(cqt_ms / args.steps, 4)},
+        "roofline_cqt": roofline_cqt,
         "kernel_ms_per_step": kernel_ms,
         "pipelined": {"streams": args.pipelined_streams, "value": round(clips / dt_pipe, 1), "unit": "clips/s",
                       "ms_per_step": round(dt_pipe / args.steps * 1e3, 4),
@@ -613,7 +635,7 @@ def main():
         "net_algorithmic_tflops": round(2.0 * NET_MACS_PER_CLIP * value / world / 1e12, 2),
         "sustained": sustained, "parity": parity, "max_rel_err": parity["max_rel_err"] if parity else None, "mirex": mirex,
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(sd)
     print(json.dumps(line))
 

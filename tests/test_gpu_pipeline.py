@@ -239,6 +239,25 @@ def test_bench_dump_outputs_are_the_last_timed_step(net, tmp_path):
         assert rel_err(got, want) < 1e-5, name
 
 
+def test_bench_plain_run_prints_the_headline_only():
+    """A run without --full times its steps and prints the headline with the roofline of the timed region's launches; the passes and
+    host work behind --full (all-kernel pass, pipelined, sustained, oracle parity, CPU baseline) do not run: their objects are null."""
+    import json, os, subprocess, sys
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "16", "--rotate", "2"]
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == 1 and line["steps"] == 3 and line["warmup"] == 1 and line["config"]["full"] is False
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "clips/s" and line["higher_is_better"] is True
+    assert line["roofline"]["launches_per_step"] == 3 and line["roofline"]["achieved"] > 0
+    assert line["roofline"]["single_stream"] is None and "cpu_baseline" not in line
+    for k in ("roofline_cqt", "kernel_ms_per_step", "pipelined", "sustained", "parity", "max_rel_err", "mirex"):
+        assert line[k] is None, k
+
+
 def test_bench_starts_its_own_ranks():
     """`python3 bench.py --gpus 2` with NO launcher must start two rank processes itself and print an n_gpus: 2 line (both ranks on
     this GPU, gloo collectives: AKE_REHEARSE_ONE_GPU); a world size that differs from --gpus is a hard error."""
@@ -246,7 +265,7 @@ def test_bench_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["AKE_REHEARSE_ONE_GPU"] = "1"
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "32", "--rotate", "2",
-           "--sustained-seconds", "0.2", "--pipelined-streams", "0", "--no-cpu-baseline"]
+           "--sustained-seconds", "0.2", "--pipelined-streams", "0", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -254,6 +273,7 @@ def test_bench_starts_its_own_ranks():
     line = json.loads(lines[0])
     assert line["n_gpus"] == 2 and line["config"]["clips_per_gpu"] == 32 and line["max_rel_err"] < 1e-3
     assert line["mirex"]["clips"] == 64 and line["sustained"]["steps"] >= 3
+    assert line["roofline_cqt"]["achieved"] > 0 and line["kernel_ms_per_step"] and line["roofline"]["single_stream"]["avg_launch_ms"] > 0
     # world size != --gpus: refused, no line
     env2 = dict(env, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     bad = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--no-cpu-baseline"], env=env2,

@@ -8,7 +8,7 @@ mkdir -p $out
 export TMPDIR=/tmp
 timeout -k 10 900 python -m pytest tests -x -q -m gpu > $out/gpu_tests.log 2>&1; echo "gpu tests rc=$?" | tee -a $out/gpu_tests.log
 tail -3 $out/gpu_tests.log
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-parity --sustained-seconds 0 --pipelined-streams 0 --spinup-seconds 0 > $out/stats_bench.log 2>&1; echo "stats rc=$?"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-parity --sustained-seconds 0 --pipelined-streams 0 --spinup-seconds 0 > $out/stats_bench.log 2>&1; echo "stats rc=$?"
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-parity --sustained-seconds 0 --pipelined-streams 0 --spinup-seconds 0 > $out/pmc_fetch.log 2>&1; echo "pmc fetch rc=$?"
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/pmc_write -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-parity --sustained-seconds 0 --pipelined-streams 0 --spinup-seconds 0 > $out/pmc_write.log 2>&1; echo "pmc write rc=$?"
 find $out -name "*.csv" | head -20
@@ -28,7 +28,7 @@ timeout -k 10 300 rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_AN
 # the bench lines last: the PMC summary of THIS build sits in profiles/ (box-local copy; copy it to the repo's profiles/ afterwards), so
 # the line's roofline.traffic is filled from counters taken with the same kernel sources
 [ -f $out/pmc_traffic.json ] && cp $out/pmc_traffic.json profiles/${tag}_pmc_traffic.json
-timeout -k 10 300 python3 bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
-timeout -k 10 300 python3 bench.py --train > $out/train_bench.json 2> $out/train_bench.err; echo "train bench rc=$?"
-timeout -k 10 300 python3 bench.py --precision f32x3 --no-cpu-baseline --sustained-seconds 0 --pipelined-streams 0 > $out/bench_f32x3.json 2> $out/bench_f32x3.err; echo "f32x3 bench rc=$?"
+timeout -k 10 300 python3 bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
+timeout -k 10 300 python3 bench.py --train --full > $out/train_bench.json 2> $out/train_bench.err; echo "train bench rc=$?"
+timeout -k 10 300 python3 bench.py --full --precision f32x3 --no-cpu-baseline --sustained-seconds 0 --pipelined-streams 0 > $out/bench_f32x3.json 2> $out/bench_f32x3.err; echo "f32x3 bench rc=$?"
 echo "collect_round done"

@@ -18,7 +18,7 @@ def main(stats_csv, bench_log, out_md, spin=100, warm=5, steps=20):
     lib = [r for r in rows if r[4]]
     with open(out_md, "w") as f:
         f.write(f"# rocprofv3 --kernel-trace --stats summary of the training bench ({stats_csv.split('/')[-1]})\n\n")
-        f.write(f"Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --train --steps {steps} --warmup {warm} --no-cpu-baseline`\n")
+        f.write(f"Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --train --full --steps {steps} --warmup {warm} --no-cpu-baseline`\n")
         f.write(f"({total_steps} training steps in the process: {spin} spin-up + {warm} warm-up + {steps} timed + {steps} with the in-bench event timers; per-step = total / {total_steps})\n\n")
         f.write("| kernel | calls | total ms | avg us | ms per step |\n|---|---|---|---|---|\n")
         for r in sorted(lib, key=lambda r: -r[2])[:45]:
