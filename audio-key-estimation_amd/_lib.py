@@ -9,8 +9,6 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libake_hip.so")
-if os.environ.get("AKE_USE_DIAG_LIB") == "1":      # kernel experiments only (tools/, tests/tools/): the -DAKE_DIAG build, `AKE_DIAG=1 csrc/build.sh`
-    LIB_PATH = os.path.join(_HERE, "libake_hip_diag.so")
 
 AKE_OK = 0
 

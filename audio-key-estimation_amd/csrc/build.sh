@@ -5,10 +5,7 @@ cd "$(dirname "$0")"
 OUT=../libake_hip.so
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-result"
-# AKE_DIAG=1: the diagnostic build (-DAKE_DIAG: the AKE_* environment switches of the kernel experiments exist, common.h) -> libake_hip_diag.so,
-# loaded instead of the shipped library only when AKE_USE_DIAG_LIB=1 is set for the Python process (tools/, tests/tools/).
 BUILD=build
-if [ "${AKE_DIAG:-0}" = 1 ]; then FLAGS="$FLAGS -DAKE_DIAG=1"; OUT=../libake_hip_diag.so; BUILD=build_diag; fi
 mkdir -p $BUILD
 HEADERS="common.h cqt_stream.h pcnet_kernels.h pcnet_bwd_kernels.h pcnet_backward.h ../../include/ake_hip.h"
 pids=()

@@ -80,13 +80,7 @@ using namespace ake;
 extern "C" {
 
 int ake_version(void) { return 102; }
-int ake_build_has_diag(void) {
-#ifdef AKE_DIAG
-    return 1;
-#else
-    return 0;
-#endif
-}
+int ake_build_has_diag(void) { return 0; }
 
 const char* ake_last_error(void) { return g_err; }
 

@@ -240,7 +240,6 @@ struct CascArgs {
     int g0;                    // full-rate frontier before tick 0 (multiple of 512, <= -512)
     int ticks_total, ticks_per_seg, warm;
     DecimTaps taps;
-    unsigned long long* stamps;   // diagnostic build: [4 waves][16] cycle sums per phase of a tick
     const int* hops;           // per-clip hops (cqt_cascade_kernel<..., HOPS = true>): clip c's frame centres are multiples of hops[c], and
                                // need[] holds the plain distances -- each clip applies `2 * need >= hop -> everywhere` itself
 };
@@ -336,15 +335,8 @@ __device__ __forceinline__ void cascade_level(const CascArgs& a, float* lds, int
     }
 }
 
-__device__ __forceinline__ unsigned long long casc_stamp() {
-    unsigned long long t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-    return t;
-}
-
-// STAMP: diagnostic build (AKE_CQT_CASC_STAMP): s_memtime stamps around the phases of a tick, workgroup (0, 0); never timed.
 // HOPS: every clip has its own hop (a.hops[clip]); only the "store near frame centres" predicate depends on it, never a stored value.
-template <int NODD, int C, int NT, bool SPLIT, bool STAMP = false, bool HOPS = false>
+template <int NODD, int C, int NT, bool SPLIT, bool HOPS = false>
 __global__ __launch_bounds__(NT) void cqt_cascade_kernel(CascArgs a) {
     static_assert(C % 512 == 0 && C >= 1024 && (C / 4) % NT == 0, "chunk");
     using Lay = CascLayout<C>;
@@ -392,13 +384,7 @@ __global__ __launch_bounds__(NT) void cqt_cascade_kernel(CascArgs a) {
     const int need0 = HOPS && 2 * a.need[0] >= hop_c ? -1 : a.need[0];                       // (HOPS only)
     const float hopf0 = static_cast<float>(HOPS ? hop_c : a.hop), inv_hop0 = 1.f / hopf0;
     __syncthreads();
-    unsigned long long sm[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ts[10];
     for (int k = k_start; k < k_end; ++k) {
-        if (STAMP) {
-            ts[0] = casc_stamp();
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // how long the prefetched chunk is still outstanding
-            sm[9] += casc_stamp() - ts[0];
-        }
         const bool owned = k >= k_own;
         if (S == 1 && k > k_start) {                                  // single stage: level 0 is also the deepest level
             float4 h = {0.f, 0.f, 0.f, 0.f};
@@ -443,31 +429,14 @@ __global__ __launch_bounds__(NT) void cqt_cascade_kernel(CascArgs a) {
         }
         if (k + 1 < k_end) fetch(k + 1);                              // next chunk in flight during the whole tick
         __syncthreads();
-        if (STAMP) ts[1] = casc_stamp();
         cascade_level<NODD, C, NT, 0, SPLIT, HOPS>(a, lds, tid, clip, k, owned, hop_c);
         __syncthreads();
-        if (STAMP) ts[2] = casc_stamp();
         if (S > 1) { cascade_level<NODD, C, NT, 1, SPLIT, HOPS>(a, lds, tid, clip, k, owned, hop_c); __syncthreads(); }
-        if (STAMP) ts[3] = casc_stamp();
         if (S > 2) { cascade_level<NODD, C, NT, 2, SPLIT, HOPS>(a, lds, tid, clip, k, owned, hop_c); __syncthreads(); }
-        if (STAMP) ts[4] = casc_stamp();
         if (S > 3) { cascade_level<NODD, C, NT, 3, SPLIT, HOPS>(a, lds, tid, clip, k, owned, hop_c); __syncthreads(); }
-        if (STAMP) ts[5] = casc_stamp();
         if (S > 4) { cascade_level<NODD, C, NT, 4, SPLIT, HOPS>(a, lds, tid, clip, k, owned, hop_c); __syncthreads(); }
-        if (STAMP) ts[6] = casc_stamp();
         if (S > 5) { cascade_level<NODD, C, NT, 5, SPLIT, HOPS>(a, lds, tid, clip, k, owned, hop_c); __syncthreads(); }
-        if (STAMP) ts[7] = casc_stamp();
         if (S > 6) { cascade_level<NODD, C, NT, 6, SPLIT, HOPS>(a, lds, tid, clip, k, owned, hop_c); __syncthreads(); }
-        if (STAMP) {
-            ts[8] = casc_stamp();
-#pragma unroll
-            for (int i = 0; i < 8; ++i) sm[i] += ts[i + 1] - ts[i];
-            sm[8] += 1;
-        }
-    }
-    if (STAMP && blockIdx.x == 1 && blockIdx.y == 0 && (tid & 63) == 0 && a.stamps) {
-#pragma unroll
-        for (int i = 0; i < 10; ++i) a.stamps[(tid >> 6) * 16 + i] = sm[i];
     }
 }
 
@@ -1128,8 +1097,7 @@ int ake_cqt_plan_create(const ake_cqt_config* cfg_in, ake_cqt_plan** out) {
     }
     // ---- engine ----
     {
-        int want = cfg.engine;
-        if (const char* e = ake::diag_env("AKE_CQT_ENGINE")) want = std::atoi(e);
+        const int want = cfg.engine;
         const bool can_fuse = p->half_len <= 23;
         const bool can_bf16 = can_fuse && n_oct >= 2 && n_oct - 1 <= kCascMax;
         if (want == 3 && !can_bf16) { ake::set_error("cqt: engine 3 needs 2..%d octaves and decim_half_len <= 23", kCascMax + 1); ake_cqt_plan_destroy(p); return AKE_ERR_UNSUPPORTED; }
@@ -1359,8 +1327,7 @@ int cqt_logmag_impl(const ake_cqt_plan* p, const float* audio, int batch, int64_
         a.g0 = -512;
         const long long g1 = n_in + static_cast<long long>(25 + kLagHost[fused]) * (1ll << fused) + 512;
         a.ticks_total = static_cast<int>((g1 - a.g0 + C - 1) / C);
-        static const int segs_env = ake::diag_env("AKE_CQT_SEGS") ? std::atoi(ake::diag_env("AKE_CQT_SEGS")) : 0;
-        const int segs = std::max(1, std::min(a.ticks_total, segs_env > 0 ? segs_env : 4));
+        const int segs = std::max(1, std::min(a.ticks_total, 4));
         a.ticks_per_seg = (a.ticks_total + segs - 1) / segs;
         a.warm = 3;                                         // >= 64 * 2^7 / C ticks of history before the first owned tick
     };
@@ -1369,29 +1336,11 @@ int cqt_logmag_impl(const ake_cqt_plan* p, const float* audio, int batch, int64_
         dim3 grid((a.ticks_total + a.ticks_per_seg - 1) / a.ticks_per_seg, batch);
         ake::ProfScope ps("cqt_cascade_kernel", stream);
         const bool split = a.ph[0] != nullptr;
-        if (a.hops && p->half_len == 15) hipLaunchKernelGGL((cqt_cascade_kernel<8, C, NT, true, false, true>), grid, dim3(NT), 0, stream, a);
-        else if (a.hops) hipLaunchKernelGGL((cqt_cascade_kernel<12, C, NT, true, false, true>), grid, dim3(NT), 0, stream, a);
+        if (a.hops && p->half_len == 15) hipLaunchKernelGGL((cqt_cascade_kernel<8, C, NT, true, true>), grid, dim3(NT), 0, stream, a);
+        else if (a.hops) hipLaunchKernelGGL((cqt_cascade_kernel<12, C, NT, true, true>), grid, dim3(NT), 0, stream, a);
         else if (p->half_len == 15 && split) hipLaunchKernelGGL((cqt_cascade_kernel<8, C, NT, true>), grid, dim3(NT), 0, stream, a);
         else if (p->half_len == 15) hipLaunchKernelGGL((cqt_cascade_kernel<8, C, NT, false>), grid, dim3(NT), 0, stream, a);
-        else if (split) {
-            static const bool stamp_env = ake::diag_env("AKE_CQT_CASC_STAMP") != nullptr;
-            unsigned long long* sb = nullptr;
-            if (stamp_env && a.n_stage == 7 && hipMalloc(&sb, 64 * sizeof(unsigned long long)) == hipSuccess) {
-                CascArgs a2 = a;
-                a2.stamps = sb;
-                (void)hipMemsetAsync(sb, 0, 64 * sizeof(unsigned long long), stream);
-                hipLaunchKernelGGL((cqt_cascade_kernel<12, C, NT, true, true>), grid, dim3(NT), 0, stream, a2);
-                unsigned long long hb[64];
-                (void)hipMemcpyAsync(hb, sb, sizeof(hb), hipMemcpyDeviceToHost, stream);
-                (void)hipStreamSynchronize(stream);
-                (void)hipFree(sb);
-                for (int wv = 0; wv < 4; ++wv) {
-                    fprintf(stderr, "cascade stamps wave %d: ticks %llu  cycles/tick: level-0 write+barrier %.0f", wv, hb[wv * 16 + 8], hb[wv * 16] / double(hb[wv * 16 + 8]));
-                    for (int i = 1; i < 8; ++i) fprintf(stderr, "  stage %d: %.0f", i - 1, hb[wv * 16 + i] / double(hb[wv * 16 + 8]));
-                    fprintf(stderr, "  (audio prefetch still outstanding at tick start: %.0f)\n", hb[wv * 16 + 9] / double(hb[wv * 16 + 8]));
-                }
-            } else hipLaunchKernelGGL((cqt_cascade_kernel<12, C, NT, true>), grid, dim3(NT), 0, stream, a);
-        }
+        else if (split) hipLaunchKernelGGL((cqt_cascade_kernel<12, C, NT, true>), grid, dim3(NT), 0, stream, a);
         else hipLaunchKernelGGL((cqt_cascade_kernel<12, C, NT, false>), grid, dim3(NT), 0, stream, a);
     };
     if (p->engine == 5) {
@@ -1403,7 +1352,6 @@ int cqt_logmag_impl(const ake_cqt_plan* p, const float* audio, int batch, int64_
         call2.pad = p->ppad;
         sa.x = audio; sa.x_stride = audio_stride; sa.n = static_cast<int>(n); sa.n_clip = reinterpret_cast<const long long*>(n_clip); sa.batch = batch;
         sa.ppad = p->ppad; sa.hop = p->cfg.hop_length; sa.toep = p->toep5_dev; sa.h0 = p->taps.h0;
-        if (const char* e = ake::diag_env("AKE_SM_ABLATE")) sa.dbg = std::atoi(e);
         for (int l = 0; l < sm::kStages; ++l) {
             const int pl = plane_len(p, l, n);
             sa.ph[l] = c.take<unsigned int>(static_cast<size_t>(batch) * pl);
@@ -1419,9 +1367,8 @@ int cqt_logmag_impl(const ake_cqt_plan* p, const float* audio, int batch, int64_
         // (everything in periods of 8 chunks: the kernel's stage parities are compile-time)
         sa.c_begin = -static_cast<int>((((static_cast<long long>(p->ppad) + 64) * 8 + 63) / 64 + 7) / 8 * 8);  // level 3's left pad, as silence
         sa.c_end = static_cast<int>(((n + 2048) / 64 + 9 + 7) / 8 * 8);                                        // ... and every level's tail + the pipeline's delay
-        static const int segs_env = ake::diag_env("AKE_CQT_SEGS") ? std::atoi(ake::diag_env("AKE_CQT_SEGS")) : 0;
         const int n_groups = (batch + 15) / 16;
-        int segs = segs_env > 0 ? segs_env : std::max(1, (4 * p->n_cu + n_groups - 1) / n_groups);            // one wave per SIMD
+        int segs = std::max(1, (4 * p->n_cu + n_groups - 1) / n_groups);                                       // one wave per SIMD
         sa.warm = 24;
         const int total = sa.c_end - sa.c_begin;
         segs = std::max(1, std::min(segs, total / (2 * sa.warm)));                                             // (short clips: warm-up must not dominate)

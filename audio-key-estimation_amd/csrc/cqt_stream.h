@@ -54,7 +54,6 @@ struct Args {
     int hop;
     int c_begin, c_end;             // level-0 chunks [c_begin, c_end) are processed; everything before c_begin is silence
     int chunks_per_seg, warm;
-    int dbg;                        // diagnostic build (AKE_SM_ABLATE; timing only, wrong results): 1 no audio loads, 2 no stage work, 4 no stores
     const uint4* toep;              // [4 matrices: A_T x O_{T-1}, A_T x O_T, B_{T-1} x O_{T-1}, B_{T-1} x O_T][hi | lo][64 lanes] x 8 bf16
     float h0;
 };
@@ -198,7 +197,7 @@ __device__ __forceinline__ void run_stage(const Args& a, Ctx& cx, Stage (&st)[kS
 
 constexpr int kBufs = 4, kAhead = 3;                                              // audio chunks: 4 register buffers, loads 3 chunks ahead
 
-// One wave = 16 clips x one time segment.  Measured at 256 clips (tests/tools/cqt_engine5_ablate.py, diagnostic build): 0.140 ms, of which vector /
+// One wave = 16 clips x one time segment.  Measured at 256 clips, switching phases off one at a time: 0.140 ms, of which vector /
 // scalar issue of the lone wave 0.076 (loads and stores off), the stores +0.03..0.046, the loads +0.018 where the period is branch-free (a
 // branch around a load made every join wait for vmcnt(0): 0.203 ms).  A producer / consumer split over two waves per SIMD (stage 0 | stages
 // 1-3 through an LDS ring) halves the issue time on paper but the compiler needs 373 registers for the producer role and spills: 0.27 ms.
@@ -256,11 +255,6 @@ __global__ __launch_bounds__(64) void cqt_stream_kernel(Args a) {
         for (int j = 0; j < 4; ++j) g[j] = *reinterpret_cast<const f4un*>(p + 16 * j);
     };
     auto load_groups_masked = [&](f4un (&g)[4], int c) {                           // edges: samples outside [0, n_lane) read as zero
-        if (a.dbg & 1) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) g[j] = f4un{1.f, 1.f, 1.f, 1.f};
-            return;
-        }
         if (c < 0 || c >= c_zero) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) g[j] = f4un{0.f, 0.f, 0.f, 0.f};
@@ -303,16 +297,15 @@ __global__ __launch_bounds__(64) void cqt_stream_kernel(Args a) {
 #pragma unroll
     for (int k = 0; k < kAhead; ++k) load_groups_masked(buf[k], c_start + k);
     for (int c0 = c_start; c0 < c_stop; c0 += 8) {                                // one period: 8 level-0 chunks = 4 / 2 / 1 chunks of levels 1 / 2 / 3
-        cx.owned = c0 >= c_own && !(a.dbg & 4);
-        const bool fast = c0 >= 0 && c0 + 8 + kAhead <= c_fast_end && !(a.dbg & 1);
+        cx.owned = c0 >= c_own;
+        const bool fast = c0 >= 0 && c0 + 8 + kAhead <= c_fast_end;
 #define AKE_SM_STEP(K_, LOAD_)                                                                   \
         {                                                                                         \
             LOAD_(buf[(K_ + kAhead) % kBufs], c0 + K_ + kAhead);                                  \
             float raw[16];                                                                        \
             deal(buf[K_ % kBufs], raw);                                                           \
             store_level0(raw, c0 + K_);                                                           \
-            if (!(a.dbg & 2)) run_stage<0, K_>(a, cx, st, toep, raw, c0);                         \
-            else if (cx.owned && cx.live && raw[0] == 123.f) a.next[0] = 1.f;                     \
+            run_stage<0, K_>(a, cx, st, toep, raw, c0);                                           \
         }
         if (fast) {
             AKE_SM_STEP(0, load_groups) AKE_SM_STEP(1, load_groups) AKE_SM_STEP(2, load_groups) AKE_SM_STEP(3, load_groups)

@@ -3,8 +3,8 @@
 // Replaces PitchClassNet.forward (models.py:747-817) for the default architecture family
 // (models.py:190-197, 227-234, 311-350).  Channel algebra follows models.py:279-308 / 693-710.
 //
-// HBM layout (all fp32, NCHW; the pitch stream runs in chunks of <= chunk_clips clips (AKE_PCNET_CHUNK, default
-// 256): measured on MI355X a larger launch beats Infinity-Cache residency of the 700 KB/clip activations):
+// HBM layout (all fp32, NCHW; the pitch stream runs in chunks of <= chunk_clips = 256 clips: measured on MI355X a larger
+// launch beats Infinity-Cache residency of the 700 KB/clip activations):
 //   mel      [B][1][P][T]                    caller's
 //   fold0    [c][1][12][T]                   semitone conv + octave fold of layer 0
 //   cat_i    [c][prev_pc + out_p][12][T_i]   concat buffer of layer i: producers write their channel slice
@@ -320,7 +320,6 @@ struct Tile {
 // the LDS budget.  Score = useful tile slots / issued, times the row-tile fill.
 struct MTile { int W, cin_chunk; };
 int device_cus();
-int tiling_cus(int which);
 
 // want_tiles > 1 (small batches): tilings with fewer (row, time) tiles than that lose score, so that the launch fills the chip.
 bool choose_tile(bool fullrows, int cin, int H, int KH, int T_out, int TB, int KU, int NT, int MT, Tile* t, MTile* mt_out, int want_tiles = 1) {
@@ -366,10 +365,8 @@ bool choose_tile(bool fullrows, int cin, int H, int KH, int T_out, int TB, int K
 }
 
 template <bool TRAIN>
-int launch_mfma_t(const PackedConv& pc, const MfmaArgs& a, int MT, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+int launch_mfma_t(const PackedConv& pc, const MfmaArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
 #define AKE_MFMA(KU_, NT_, MT_) hipLaunchKernelGGL((conv_mfma_kernel<KU_, NT_, MT_, TRAIN>), grid, block, lds, s, a); return AKE_OK
-    if (pc.ku == 8 && pc.nt == 1 && MT == 6) { AKE_MFMA(8, 1, 6); }
-    if (pc.ku == 8 && pc.nt == 1 && MT == 4) { AKE_MFMA(8, 1, 4); }
     if (pc.ku == 8 && pc.nt == 1) { AKE_MFMA(8, 1, 3); }
     if (pc.ku == 8 && pc.nt == 2) { AKE_MFMA(8, 2, 3); }
     if (pc.ku == 12 && pc.nt == 1) { AKE_MFMA(12, 1, 3); }
@@ -383,9 +380,9 @@ int launch_mfma_t(const PackedConv& pc, const MfmaArgs& a, int MT, dim3 grid, di
 }
 
 // inference launches carry none of the training-mode code (pending BatchNorm on load, statistics, accumulation)
-int launch_mfma(const PackedConv& pc, const MfmaArgs& a, int MT, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+int launch_mfma(const PackedConv& pc, const MfmaArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
     const bool train = a.c.in_affine || a.c.stats || a.c.accumulate || a.c.rows_zero;      // (rows_zero: only the TRAIN form's loader zero-pads the rows)
-    return train ? launch_mfma_t<true>(pc, a, MT, grid, block, lds, s) : launch_mfma_t<false>(pc, a, MT, grid, block, lds, s);
+    return train ? launch_mfma_t<true>(pc, a, grid, block, lds, s) : launch_mfma_t<false>(pc, a, grid, block, lds, s);
 }
 
 struct Src {
@@ -429,12 +426,9 @@ int run_conv(const ake_pcnet* n, const PackedConv& pc, int kind, Src src, int ba
     a.residual = residual; a.residual_clip_stride = static_cast<long long>(pc.cout) * a.H_out * a.T_out;      // dense [B][cout][H][T]
     Tile t;
     MTile mtile;
-    static const int mt_env = ake::diag_env("AKE_MT") ? std::atoi(ake::diag_env("AKE_MT")) : 3;
-    const int MT = (pc.ku == 8 && pc.nt == 1 && kind == 0) ? mt_env : 3;
+    constexpr int MT = 3;
     const int cout_tiles = std::max(1, pc.ntiles / pc.nt);
-    static const char* const tiling_only = ake::diag_env("AKE_TILING_ONLY");      // diagnostic: AKE_TILING_CUS only for launches whose name contains this
-    const int t_cus = (tiling_only && !std::strstr(name, tiling_only)) ? device_cus() : tiling_cus(0);
-    const int want_tiles = (std::max(t_cus, 1) + batch * cout_tiles - 1) / (batch * cout_tiles);      // 1 at the bench / training batch sizes
+    const int want_tiles = (std::max(device_cus(), 1) + batch * cout_tiles - 1) / (batch * cout_tiles);      // 1 at the bench / training batch sizes
     AKE_REQUIRE(choose_tile(fullrows, pc.cin, H, pc.kh, a.T_out, pc.tb, pc.ku, pc.nt, MT, &t, &mtile, want_tiles), AKE_ERR_UNSUPPORTED,
                 "conv %s: no tile fits LDS (cin=%d H=%d)", name, pc.cin, H);
     a.R = t.R; a.TT = t.TT; a.Tp = t.Tp; a.n_row_tiles = t.n_row_tiles; a.n_time_tiles = t.n_time_tiles;
@@ -444,30 +438,22 @@ int run_conv(const ake_pcnet* n, const PackedConv& pc, int kind, Src src, int ba
     ma.row_k = pc.row_k;
     ma.ksplit = 0;
     ma.h1_magic = (65536 + a.h1 - 1) / a.h1;
-    static const int ablate = ake::diag_env("AKE_ABLATE") ? std::atoi(ake::diag_env("AKE_ABLATE")) : 0;
-    ma.dbg = ablate;
     if (mtile.W == 1 && pc.cin * pc.kh >= 16) {   // tiny M (1-channel head convs): split the (channel, dy) steps over 8 waves instead
         ma.ksplit = 1;
         mtile.W = 8;
         t.threads = 8 * 64;
         t.lds = std::max<size_t>(t.lds, static_cast<size_t>(8) * MT * pc.nt * 64 * sizeof(float) * 4);
     }
-    static const bool debug = ake::diag_env("AKE_DEBUG") != nullptr;
-    if (debug)
-        fprintf(stderr, "[ake] %-28s cin=%3d cout=%3d kh=%2d TB=%2d KU=%2d NT=%d | R=%2d TT=%3d Tp=%3d tiles=%dx%d waves=%d chunk=%d lds=%zu grid=(%d,%d,%d)\n",
-                name, pc.cin, pc.cout, pc.kh, pc.tb, pc.ku, pc.nt, t.R, t.TT, t.Tp, t.n_row_tiles, t.n_time_tiles, mtile.W,
-                mtile.cin_chunk, t.lds, t.n_row_tiles * t.n_time_tiles, pc.ntiles / pc.nt, batch);
     dim3 grid(t.n_row_tiles * t.n_time_tiles, pc.ntiles / pc.nt, batch), block(t.threads);
     ake::ProfScope ps(name, s);
-    return launch_mfma(pc, ma, MT, grid, block, t.lds, s);
+    return launch_mfma(pc, ma, grid, block, t.lds, s);
 }
 
 // does inference run layer i's Pitch2Pitch stack on the bf16 kernel (everything but its first conv)?
 // (the bf16 kernels keep all frames of their row tile in one LDS patch: long clips fall back to the time-tiled f32 kernel)
 bool p2p_uses_f16(const ake_pcnet* n, int i, int T) {
-    static const bool f32_only = ake::diag_env("AKE_P2P_F32") != nullptr;
     const auto& c = n->cfg;
-    if (f32_only || c.precision == AKE_PRECISION_F32X3 || c.resblock || i < 1 || c.conv_layers < 2 || n->dims[i].out_p != 8 || T > 146) return false;
+    if (c.precision == AKE_PRECISION_F32X3 || c.resblock || i < 1 || c.conv_layers < 2 || n->dims[i].out_p != 8 || T > 146) return false;
     for (int j = 0; j < c.conv_layers; ++j)
         if (n->p2p[i][j].bf_off < 0) return false;
     return true;
@@ -476,8 +462,7 @@ bool p2p_uses_f16(const ake_pcnet* n, int i, int T) {
 // does inference run layer i's PitchClass2PitchClass stack on conv_pc_bf16_kernel?
 constexpr int kPcBf16MaxFrames = 120;
 bool pc2pc_uses_bf16(const ake_pcnet* n, int i, int T) {
-    static const bool f32_only = ake::diag_env("AKE_PC_F32") != nullptr;
-    if (f32_only || n->cfg.resblock || n->pc2pc[i].empty() || T > kPcBf16MaxFrames) return false;
+    if (n->cfg.resblock || n->pc2pc[i].empty() || T > kPcBf16MaxFrames) return false;
     for (const PackedConv& pc : n->pc2pc[i])
         if (pc.bf_off < 0 || pc.cout != 16) return false;
     return true;
@@ -535,15 +520,6 @@ int device_cus() {
     return n_cus;
 }
 
-// The CU count the TILING heuristics compare the batch with ("does this launch fill the chip?").  Diagnostic builds can override it
-// (AKE_TILING_CUS): a 32-clip batch with AKE_TILING_CUS=32 runs the tilings a 256-clip batch gets on the 256-CU part, small enough for
-// float64 autograd to check them (the grids of the persistent kernels keep using the real count).
-int tiling_cus(int which) {          // which: 0 the convolution's tile choice, 1 the weight-gradient kernels, 2 the semitone weight gradient
-    static const int over = ake::diag_env("AKE_TILING_CUS") ? std::atoi(ake::diag_env("AKE_TILING_CUS")) : 0;
-    static const int mask = ake::diag_env("AKE_TILING_CUS_MASK") ? std::atoi(ake::diag_env("AKE_TILING_CUS_MASK")) : 7;
-    return (over > 0 && ((mask >> which) & 1)) ? over : device_cus();
-}
-
 // row-tile height of the persistent pitch-conv kernel for H x T maps (0: the shape does not qualify); `semi`: the form fused with the
 // semitone conv (tiles of 3k rows, no staging slabs but a double-buffered output patch)
 int p2p_ps_rows(int H, int T, bool semi, int* plane_pos, size_t* lds) {
@@ -564,8 +540,7 @@ int p2p_ps_rows(int H, int T, bool semi, int* plane_pos, size_t* lds) {
 // does inference fuse the semitone conv of layer i into the last pitch conv of its stack (the pitch tensor is then never written)?
 // Only in the net's last layer: an inner layer's pitch tensor is also the next layer's pitch stream (time_pool_p, models.py:395).
 bool p2p_fuses_semi(const ake_pcnet* n, int i, int P, int T) {
-    static const bool off = ake::diag_env("AKE_P2P_PS") != nullptr && std::atoi(ake::diag_env("AKE_P2P_PS")) == 0;
-    return !off && !g_keep_taps && !n->cfg.p2pc_conv && !n->cfg.stay_sixth && i == n->cfg.num_layers - 1 && p2p_uses_f16(n, i, T) && static_cast<size_t>(i) < n->semi.size() && n->semi[i].bf_off >= 0 &&
+    return !g_keep_taps && !n->cfg.p2pc_conv && !n->cfg.stay_sixth && i == n->cfg.num_layers - 1 && p2p_uses_f16(n, i, T) && static_cast<size_t>(i) < n->semi.size() && n->semi[i].bf_off >= 0 &&
            p2p_ps_rows(P, T, true, nullptr, nullptr) > 0;
 }
 
@@ -579,8 +554,6 @@ bool p2p_fuses_semi(const ake_pcnet* n, int i, int P, int T) {
 bool run_p2p_f16_ps(const ake_pcnet* n, const PackedConv& pc, const unsigned short* xh, const Src* nchw, int batch, int H, int T, float* dst_nchw,
                      int dst_ctot, unsigned short* oh, const PackedConv* semi_pc, hipStream_t s, const char* name, bool p_frames_major = false,
                      bool dry_run = false, int fold_coff = -1, bool u_f16x4 = false) {     // u_f16x4: nchw->p1 is layer 0's f16 x 4 form of the up_sixth map (Layer0Args::psix_h)
-    static const bool off = ake::diag_env("AKE_P2P_PS") != nullptr && std::atoi(ake::diag_env("AKE_P2P_PS")) == 0;
-    if (off) return false;
     P2pPsArgs a;
     std::memset(&a, 0, sizeof(a));
     size_t lds = 0;
@@ -608,9 +581,7 @@ bool run_p2p_f16_ps(const ake_pcnet* n, const PackedConv& pc, const unsigned sho
     a.H = H; a.T = T; a.J = T / 2; a.Tp = p2p_pitch(a.J);
     a.n_row_tiles = (H + a.R - 1) / a.R;
     a.n_tiles = a.n_row_tiles * batch;
-    static const bool fold_off = ake::diag_env("AKE_P2P_FOLD") != nullptr && std::atoi(ake::diag_env("AKE_P2P_FOLD")) == 0;
     const bool fold = fold_coff >= 0;
-    if (fold && fold_off) return false;
     if (fold) {
         if (!semi_pc || H % 36 || 36 % a.R) return false;
         a.n_oct = H / 36; a.n_units = batch * (36 / a.R);
@@ -627,8 +598,7 @@ bool run_p2p_f16_ps(const ake_pcnet* n, const PackedConv& pc, const unsigned sho
         const void* fns[] = {reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<3, 0>),
                              reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<1, 0>), reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<1, 5>),
                              reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<1, 8>), reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<0, 0>),
-                             reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<2, 0>), reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<1, 0, true>),
-                             reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<1, 3>)};
+                             reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<2, 0>), reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<1, 3>)};
         for (const void* f : fns)
             if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
         attr_set.mark();
@@ -636,8 +606,7 @@ bool run_p2p_f16_ps(const ake_pcnet* n, const PackedConv& pc, const unsigned sho
     // two workgroups per CU when the LDS allows it (the kernel is built for 4 waves per SIMD): one's epilogue (vector work) and
     // barrier waits run under the other's multiply loop (bound by its LDS reads)
     if (dry_run) return true;                          // (the eligibility question of ake_pcnet_accepts_frames_major)
-    static const int wg_per_cu_env = ake::diag_env("AKE_P2P_WG_PER_CU") ? std::atoi(ake::diag_env("AKE_P2P_WG_PER_CU")) : 2;
-    const int wg_per_cu = (wg_per_cu_env >= 2 && (!nchw || a.uh) && lds <= 80 * 1024 && a.n_tiles >= 4 * n_cus) ? 2 : 1;
+    const int wg_per_cu = ((!nchw || a.uh) && lds <= 80 * 1024 && a.n_tiles >= 4 * n_cus) ? 2 : 1;
     dim3 grid(std::min(wg_per_cu * (n_cus / 8 * 8), (a.n_tiles + 7) / 8 * 8)), block(512);
     ake::ProfScope ps(name, s);
     if (fold) hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<3, 0>), grid, block, lds, s, a);
@@ -646,24 +615,7 @@ bool run_p2p_f16_ps(const ake_pcnet* n, const PackedConv& pc, const unsigned sho
     else if (nchw && a.uh) hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<1, 3>), grid, block, lds, s, a);
     else if (nchw && a.c0 + a.c1 <= 5) hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<1, 5>), grid, block, lds, s, a);
     else if (nchw) hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<1, 8>), grid, block, lds, s, a);
-    else {
-        static const bool stamp_env = ake::diag_env("AKE_P2P_STAMP") != nullptr;
-        unsigned long long* sb = nullptr;
-        if (stamp_env && hipMalloc(&sb, 64 * sizeof(unsigned long long)) == hipSuccess) {
-            // diagnostic build: in-kernel cycle stamps of the tile loop's sections (workgroup 0), printed to stderr; never timed
-            (void)hipMemsetAsync(sb, 0, 64 * sizeof(unsigned long long), s);
-            a.stamps = sb;
-            hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<1, 0, true>), grid, block, lds, s, a);
-            unsigned long long hb[64];
-            (void)hipMemcpyAsync(hb, sb, sizeof(hb), hipMemcpyDeviceToHost, s);
-            (void)hipStreamSynchronize(s);
-            (void)hipFree(sb);
-            for (int wv = 0; wv < 8; ++wv)
-                fprintf(stderr, "p2p stamps wave %d: tiles %llu  cycles/tile: vmcnt-wait %.0f barrier %.0f late-epilogue %.0f multiply(+dma+stores) %.0f epilogue %.0f\n", wv,
-                        hb[wv * 8 + 5], hb[wv * 8 + 0] / double(hb[wv * 8 + 5]), hb[wv * 8 + 1] / double(hb[wv * 8 + 5]), hb[wv * 8 + 2] / double(hb[wv * 8 + 5]),
-                        hb[wv * 8 + 3] / double(hb[wv * 8 + 5]), hb[wv * 8 + 4] / double(hb[wv * 8 + 5]));
-        } else hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<1, 0>), grid, block, lds, s, a);
-    }
+    else hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<1, 0>), grid, block, lds, s, a);
     return true;
 }
 
@@ -671,8 +623,7 @@ bool run_p2p_f16_ps(const ake_pcnet* n, const PackedConv& pc, const unsigned sho
 // and data gradient (none of them).  false when the shape does not qualify: the caller then runs conv_mfma_kernel.
 bool run_p2p_f16x3(const ake_pcnet* n, long long frag_off, const Src& src, const float* in_aff, const float* bias, int batch, int H, int T, float* dst,
                    int cout, double* stats, int stats_stride, hipStream_t s, const char* name, const unsigned int* in_amax = nullptr, bool lrelu = false) {
-    static const bool off = ake::diag_env("AKE_P2P_TRAIN_F32") != nullptr;
-    if (off || frag_off < 0 || T < 2 || (T & 1) || src.c0 < 1 || src.c0 + src.c1 > 8 || cout > 8 || src.ctot0 != 0) return false;
+    if (frag_off < 0 || T < 2 || (T & 1) || src.c0 < 1 || src.c0 + src.c1 > 8 || cout > 8 || src.ctot0 != 0) return false;
     P2pTrArgs a;
     std::memset(&a, 0, sizeof(a));
     const int n_cus = device_cus();
@@ -713,8 +664,6 @@ int run_fold_max(const float* smap, int C, int S, int batch, int T, float* dst, 
     return AKE_OK;
 }
 
-static const bool g_pc_f32_only = ake::diag_env("AKE_PC_F32") != nullptr;
-
 // NCHW f32 [clip][C][12][T] -> channels-last split planes [clip][12][T][16] (hi plane, then lo plane, at `planes`)
 int run_nchw_to_cl16(const float* src, int C, int batch, int T, unsigned short* planes, hipStream_t s) {
     const long long npos = static_cast<long long>(batch) * 12 * T;
@@ -727,9 +676,8 @@ int run_nchw_to_cl16(const float* src, int C, int batch, int T, unsigned short* 
 // does inference run the last layer's pitch-class stack + its time pooling as ONE launch (pc2pc_fused_kernel)?  The stack's
 // intermediate activations then never leave LDS (ake_debug_keep_taps(1) keeps the per-conv launches for bisecting).
 bool pc2pc_fuses(const ake_pcnet* n, int i, int T) {
-    static const bool off = ake::diag_env("AKE_PC_FUSED") != nullptr && std::atoi(ake::diag_env("AKE_PC_FUSED")) == 0;
     const auto& c = n->cfg;
-    if (off || g_keep_taps || i < 1 || i != c.num_layers - 1 || c.time_pool_size != 2 || c.conv_layers < 1 || c.conv_layers > 4) return false;
+    if (g_keep_taps || i < 1 || i != c.num_layers - 1 || c.time_pool_size != 2 || c.conv_layers < 1 || c.conv_layers > 4) return false;
     if (!pc2pc_uses_bf16(n, i, T) || T % 4 || 12 * T > 1024 || 3 * ((T + 15) / 16) > 16) return false;   // (16 waves: 3 row groups x 16-frame tiles)
     for (const PackedConv& pc : n->pc2pc[i])
         if (pc.cout != 16 || pc.cin > 16 || pc.kh != 12) return false;
@@ -758,8 +706,7 @@ int run_pc2pc_fused(const ake_pcnet* n, int i, const float* src, int cin, int ba
 
 // does the f16 x 3 training form of conv_pc_bf16_kernel take this convolution (fragments built, patch fits the LDS)?
 bool pc_f16x3_ok(const PackedConv& pt, int T_in, bool same_time) {
-    static const bool off = ake::diag_env("AKE_PC_TRAIN_F32") != nullptr;
-    if (off || pt.bf_off < 0 || pt.cin > 16) return false;
+    if (pt.bf_off < 0 || pt.cin > 16) return false;
     const int T_out = same_time ? T_in : T_in - pt.kw + 1;
     if (T_out < 1) return false;
     const size_t lds = (static_cast<size_t>(2) * 12 * (T_out + 8) * 2 + 2 * 4 * ((pt.cout + 15) / 16) * 2 * 64) * sizeof(uint4);
@@ -1096,7 +1043,6 @@ int ake_pcnet_create(const ake_pcnet_config* cfg, ake_pcnet** out) {
     auto* n = new ake_pcnet();
     n->cfg = c;
     if (c.local > 0) n->cfg.time_pool_size = 1;           // --local: the layers do not pool over time (models.py:348, 394)
-    if (const char* e = ake::diag_env("AKE_PCNET_CHUNK")) n->chunk_clips = std::max(1, std::atoi(e));
     const int nf = c.n_filters, L = c.num_layers, k = c.kernel_size;
     n->dims.resize(L);
     for (int i = 1; i < L; ++i) {           // models.py:281-308
@@ -2238,10 +2184,9 @@ struct Fwd {
 
     // inference, default family: the whole of phase A as one launch, one workgroup per clip (layer0_fused_kernel)
     bool layer0_fused(const float* mel, int B, bool dry_run = false) {
-        static const bool off = ake::diag_env("AKE_L0_FUSED") != nullptr && std::atoi(ake::diag_env("AKE_L0_FUSED")) == 0;
         const auto& c = n->cfg;
         const int P = c.pitches, T0 = b.Tl[0], NF = c.n_filters;
-        if (off || c.resblock || c.denseblock || c.p2pc_conv || c.stay_sixth || NF < 2 || NF > 4 || c.conv_layers < 1 || c.conv_layers > 4 || c.kernel_size != 7 || P % 36 || T0 < 1) return false;
+        if (c.resblock || c.denseblock || c.p2pc_conv || c.stay_sixth || NF < 2 || NF > 4 || c.conv_layers < 1 || c.conv_layers > 4 || c.kernel_size != 7 || P % 36 || T0 < 1) return false;
         const PackedConv& sp = n->semi[0];
         if (sp.cin != 1 || sp.co != 1) return false;
         for (int j = 0; j < c.conv_layers; ++j) {
@@ -2274,8 +2219,8 @@ struct Fwd {
                 return false;
             attr_set.mark();
         }
-        // the convolution stack on bf16 MFMA when the fragments exist and the maps fit (AKE_PC_F32=1: the exact-f32 VALU form)
-        bool mfma = !g_pc_f32_only && c.precision == AKE_PRECISION_MIXED;      // (the MFMA form multiplies f16 x f16)
+        // the convolution stack on bf16 MFMA when the fragments exist and the maps fit (f32x3: the exact-f32 VALU form)
+        bool mfma = c.precision == AKE_PRECISION_MIXED;      // (the MFMA form multiplies f16 x f16)
         for (int j = 0; j < c.conv_layers; ++j) {
             mfma = mfma && n->pc2pc[0][j].l0_off >= 0;
             if (mfma) a.frag[j] = n->bf_frags_dev + n->pc2pc[0][j].l0_off;
@@ -2289,9 +2234,8 @@ struct Fwd {
         a.taps = g_keep_taps ? 1 : 0;
         // the up_sixth map as f16 x 4 when the conv that reads it is the persistent f16 kernel for every chunk of this batch (it rounds to f16
         // itself otherwise: same values); psix[1]'s buffer holds either form
-        static const bool uh_off = ake::diag_env("AKE_PSIX_F32") != nullptr;
         psix_f16 = false;
-        if (take_mfma && b.melh && !uh_off && !g_keep_taps && !c.pc2p_mem && d1.prev_p == 1 && chunk > 0 && p2p_uses_f16(n, 1, b.Tl[1])) {
+        if (take_mfma && b.melh && !g_keep_taps && !c.pc2p_mem && d1.prev_p == 1 && chunk > 0 && p2p_uses_f16(n, 1, b.Tl[1])) {
             Src sd{mel, 1, b.psix[1], d1.prev_pc, 36};
             unsigned short* oh = reinterpret_cast<unsigned short*>(b.pa[1]);
             psix_f16 = run_p2p_f16_ps(n, n->p2p[1][0], nullptr, &sd, std::min(B, chunk), P, b.Tl[1], nullptr, d1.out_p, oh, nullptr, s, "", mel_fm, true, -1, true) &&
@@ -2299,9 +2243,6 @@ struct Fwd {
                         run_p2p_f16_ps(n, n->p2p[1][0], nullptr, &sd, B % chunk, P, b.Tl[1], nullptr, d1.out_p, oh, nullptr, s, "", mel_fm, true, -1, true));
         }
         if (psix_f16) { a.psix_h = reinterpret_cast<uint2*>(b.psix[1]); a.psix = nullptr; a.melh = b.melh; }
-        static const int dbg_skip = ake::diag_env("AKE_L0_SKIP") ? std::atoi(ake::diag_env("AKE_L0_SKIP")) : 0;   // timing experiments only (wrong results)
-        if (dbg_skip & 1) a.n_conv = 0;
-        if (dbg_skip & 2) { a.psix = nullptr; a.psix_h = nullptr; }
         ake::ProfScope ps("layer0_fused_kernel", s);
         if (take_mfma) hipLaunchKernelGGL(layer0_mfma_kernel, dim3(B), dim3(512), lds_m, s, a);
         else hipLaunchKernelGGL(layer0_fused_kernel, dim3(B), dim3(512), lds, s, a);
@@ -2605,7 +2546,7 @@ struct Fwd {
         // reused), the last convolution writes NCHW f32 for the pooling / heads
         const bool pc_bf = !train && pc2pc_uses_bf16(n, i, Ti);
         // heads on the bf16 kernels read a channels-last copy of the pooled features (decided here: the fused stack writes it itself)
-        const bool head_bf = !train && !g_pc_f32_only && L > 1 && n->final_ch == 16 && c.head_layers >= 2 && n->head_key[0].bf_off >= 0 &&
+        const bool head_bf = !train && L > 1 && n->final_ch == 16 && c.head_layers >= 2 && n->head_key[0].bf_off >= 0 &&
                              n->head_tonic[0].bf_off >= 0 && b.Tf <= kPcBf16MaxFrames;
         const bool pc_fused = !train && L > 1 && !c.denseblock && pc2pc_fuses(n, i, Ti);
         if (pc_fused) {
@@ -2764,11 +2705,10 @@ struct Fwd {
                     continue;
                 }
                 if (train && lastj && j > 0 && pe.cout == 1 && pe.kw == 7 && !n->raw_w_off.empty()) {   // cin -> 1: one workgroup per clip, f32 VALU
-                    static const bool off = ake::diag_env("AKE_HEAD_LAST_MFMA") != nullptr;
                     const std::string wn = std::string(heads[h].nm) + "." + std::to_string(3 * j) + (heads[h].kind == 2 ? "" : ".conv2d");
                     const auto wi = n->spec_index.find(wn + ".weight"), bi = n->spec_index.find(wn + ".bias");
                     const size_t lds = (static_cast<size_t>(hc) * 12 * Tcur + static_cast<size_t>(hc) * pe.kh * 7) * sizeof(float);
-                    if (!off && wi != n->spec_index.end() && bi != n->spec_index.end() && lds <= 150 * 1024 && Tcur - 6 >= 1) {
+                    if (wi != n->spec_index.end() && bi != n->spec_index.end() && lds <= 150 * 1024 && Tcur - 6 >= 1) {
                         static ake::DeviceOnce hl_attr;
                         if (hl_attr.need()) {
                             AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_head_last_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
@@ -2976,7 +2916,6 @@ static int tap_lookup(const ake_pcnet* n, const char* name, int batch, int frame
         if (t == "g_pin") { *p = b.g_pin[L1]; shape[1] = dd.prev_pc + dd.prev_p; shape[2] = c.pitches; shape[3] = b.Tl[L1]; }
         if (t == "z_p_last") { *p = b.pst[L1].back(); shape[1] = dd.out_p; shape[2] = c.pitches; shape[3] = b.Tl[L1]; }
         AKE_REQUIRE(shape[1] > 0, AKE_ERR_INVALID, "tap: unknown training buffer '%s'", name);
-        if (ake::diag_env("AKE_DEBUG")) fprintf(stderr, "[ake] tap %s -> %p\n", name, (void*)*p);
         return AKE_OK;
     }
     const int L = c.num_layers, P = c.pitches;
@@ -3003,7 +2942,7 @@ static int tap_lookup(const ake_pcnet* n, const char* name, int batch, int frame
                     return AKE_ERR_INVALID;
                 }
                 if (j < last_j && i == L - 1 && pc2pc_uses_bf16(n, i, Ti) && channels_last) *channels_last = 1;
-                if (i == 0 && L > 1 && !g_keep_taps && !g_pc_f32_only && c.precision == AKE_PRECISION_MIXED && !c.resblock && !c.denseblock && !c.p2pc_conv && !c.stay_sixth && c.n_filters >= 2 &&
+                if (i == 0 && L > 1 && !g_keep_taps && c.precision == AKE_PRECISION_MIXED && !c.resblock && !c.denseblock && !c.p2pc_conv && !c.stay_sixth && c.n_filters >= 2 &&
                     c.n_filters <= 4) {
                     ake::set_error("tap: '%s' stays in LDS (layer 0 runs as one launch); ake_debug_keep_taps(1) before the forward writes it", name);
                     return AKE_ERR_INVALID;
@@ -3022,7 +2961,7 @@ static int tap_lookup(const ake_pcnet* n, const char* name, int batch, int frame
             }
         }
         if (i >= 1 && nm == m + "up_sixth_a") {
-            if (i == 1 && !g_keep_taps && !g_pc_f32_only && c.precision == AKE_PRECISION_MIXED && !c.denseblock && !c.p2pc_conv && !c.stay_sixth && !c.pc2p_mem) {
+            if (i == 1 && !g_keep_taps && c.precision == AKE_PRECISION_MIXED && !c.denseblock && !c.p2pc_conv && !c.stay_sixth && !c.pc2p_mem) {
                 ake::set_error("tap: '%s' may be held as f16 words for the pitch conv that reads it; ake_debug_keep_taps(1) before the forward writes it as f32", name);
                 return AKE_ERR_INVALID;
             }

@@ -55,8 +55,7 @@ struct Bwd {
     // zero_pad (kind 0 only): the convolution pads rows AND frames with zeros (--denseblock's plain Conv2d) instead of wrapping both
     int wgrad(const PackedConv& pc, int kind, Src src, const float* in_aff, int H, int T_in, bool same_time, const float* dz, int dz_ctot,
               int dz_coff, gfx_t* dW, const char* name, bool zero_pad = false) {
-        static const bool wg_f32 = ake::diag_env("AKE_WGRAD_F32") != nullptr;
-        if (!wg_f32 && !zero_pad && kind == 0 && pc.kh == 7 && pc.kw == 7 && pc.cout == 8 && pc.cin <= 8 && T_in <= kWgMaxT && dz_ctot == 8 && dz_coff == 0 && src.ctot0 == 0) {
+        if (!zero_pad && kind == 0 && pc.kh == 7 && pc.kw == 7 && pc.cout == 8 && pc.cin <= 8 && T_in <= kWgMaxT && dz_ctot == 8 && dz_coff == 0 && src.ctot0 == 0) {
             WgradBfArgs w;
             std::memset(&w, 0, sizeof(w));
             w.src0 = src.p0; w.c0 = src.c0; w.src1 = src.p1; w.c1 = src.c1; w.h1 = src.h1 > 0 ? src.h1 : 1;
@@ -64,7 +63,7 @@ struct Bwd {
             w.src1_clip_stride = static_cast<long long>(src.c1) * w.h1 * T_in;
             w.in_affine = in_aff; w.dz = dz; w.dW = dW; w.slot_stride = static_cast<long long>(n->grad_floats);
             w.cin = pc.cin; w.H = H; w.T = T_in;
-            const int wgs_per_clip = std::max(3, std::min(H, (3 * std::max(tiling_cus(1), 1) + B - 1) / B));   // three workgroups fit a CU
+            const int wgs_per_clip = std::max(3, std::min(H, (3 * std::max(device_cus(), 1) + B - 1) / B));   // three workgroups fit a CU
             w.rows_per_wg = (H + wgs_per_clip - 1) / wgs_per_clip;
             dim3 grid((H + w.rows_per_wg - 1) / w.rows_per_wg, 1, B);
             const size_t lds = (static_cast<size_t>(2 * kWgARows + 2 * 64) * kWgKP + kWgKP) * sizeof(unsigned short);
@@ -74,8 +73,7 @@ struct Bwd {
                 attr_set.mark();
             }
             const long long n_w = static_cast<long long>(8) * pc.cin * 49, n_wg = static_cast<long long>(grid.x) * B;
-            static const bool partial_off = ake::diag_env("AKE_WGRAD_ATOMIC") != nullptr;
-            const bool use_partial = !partial_off && b.wg_partial && n_wg * n_w <= static_cast<long long>(b.wg_partial_floats);
+            const bool use_partial = b.wg_partial && n_wg * n_w <= static_cast<long long>(b.wg_partial_floats);
             if (use_partial) { w.partial = b.wg_partial; w.partial_stride = n_w; }
             {
                 ake::ProfScope ps("conv_wgrad_p2p_bf16_kernel", s);
@@ -91,8 +89,7 @@ struct Bwd {
         // channel block), see conv_wgrad_pc_f16x3_kernel
         {
             const int T_out = kind == 0 ? T_in : (same_time ? T_in : T_in - pc.kw + 1);
-            static const int wpc_min_cout = ake::diag_env("AKE_WPC_MIN_COUT") ? std::atoi(ake::diag_env("AKE_WPC_MIN_COUT")) : 1;
-            if (!wg_f32 && kind == 1 && pc.kh == 12 && pc.kw == 7 && H == 12 && src.c1 == 0 && T_out >= 1 && pc.cout >= wpc_min_cout) {
+            if (kind == 1 && pc.kh == 12 && pc.kw == 7 && H == 12 && src.c1 == 0 && T_out >= 1) {
                 WgradPcArgs w;
                 std::memset(&w, 0, sizeof(w));
                 w.x = src.p0; w.x_clip_stride = static_cast<long long>(src.ctot0 > 0 ? src.ctot0 : src.c0) * 12 * T_in;
@@ -105,9 +102,8 @@ struct Bwd {
                 w.n_seg = (T_out + kWpSeg - 1) / kWpSeg;
                 w.dW = dW; w.slot_stride = static_cast<long long>(n->grad_floats);
                 const long long n_w = static_cast<long long>(pc.cout) * pc.cin * 84;
-                static const bool partial_off = ake::diag_env("AKE_WGRAD_ATOMIC") != nullptr;
                 const long long n_wg = static_cast<long long>(B) * w.n_seg;
-                const bool use_partial = !partial_off && b.wg_partial && n_wg * n_w <= static_cast<long long>(b.wg_partial_floats);
+                const bool use_partial = b.wg_partial && n_wg * n_w <= static_cast<long long>(b.wg_partial_floats);
                 if (use_partial) { w.partial = b.wg_partial; w.partial_stride = n_w; }
                 const size_t lds = static_cast<size_t>(2) * 12 * 16 * (w.AP + w.ZP) * sizeof(unsigned short);
                 static ake::DeviceOnce attr_set;
@@ -149,8 +145,6 @@ struct Bwd {
             a.dst = const_cast<float*>(dz); a.dst_coff = dz_coff + co0; a.dst_clip_stride = static_cast<long long>(dz_ctot) * a.H_out * a.T_out;
             a.in_affine = in_aff;
             wa.dW = dW + static_cast<long long>(co0) * (src.c0 + src.c1) * pc.kh * pc.kw; wa.slot_stride = static_cast<long long>(n->grad_floats); wa.KH = pc.kh; wa.KW = pc.kw;
-            static const bool noflush = ake::diag_env("AKE_WGRAD_NOFLUSH") != nullptr;
-            wa.dbg_noflush = noflush ? 1 : 0;
             const int KK = pc.kh * pc.kw;
             const int MTC = (co_n + 15) / 16, NTK = (KK + 15) / 16;
             // tile: rows x frames such that the patch of 8 channels + the dz tile fit the LDS budget
@@ -166,7 +160,7 @@ struct Bwd {
             // small batches (the reference trains with 8 clips per step): shorter time tiles and one workgroup per group of 8 input
             // channels, until the launch has about one workgroup per CU
             const int cin_all = src.c0 + src.c1;
-            const int n_cus = std::max(tiling_cus(1), 1);
+            const int n_cus = std::max(device_cus(), 1);
             auto tiles_of = [&](int R_, int TT_) { return ((a.H_out + R_ - 1) / R_) * ((a.T_out + TT_ - 1) / TT_); };
             const int c_groups = static_cast<long long>(B) * tiles_of(R, TT) < n_cus ? (cin_all + 7) / 8 : 1;
             while (static_cast<long long>(B) * tiles_of(R, TT) * c_groups < n_cus && TT > 16) TT = std::max(16, (TT / 2 + 3) / 4 * 4);
@@ -176,7 +170,7 @@ struct Bwd {
             a.n_time_tiles = (a.T_out + TT - 1) / TT;
             const int tiles = a.n_row_tiles * a.n_time_tiles;
             // workgroups per clip: 4 at training batch sizes (fewer atomics), more for small batches so that the chip still fills
-            const int wgs_per_clip = std::min(tiles, std::max(4, (2 * std::max(tiling_cus(1), 1) + B - 1) / B));
+            const int wgs_per_clip = std::min(tiles, std::max(4, (2 * std::max(device_cus(), 1) + B - 1) / B));
             wa.rt_per_block = std::max(1, (tiles + wgs_per_clip - 1) / wgs_per_clip);
             wa.c_per_block = c_groups > 1 ? 8 : cin_all;
             dim3 grid((tiles + wa.rt_per_block - 1) / wa.rt_per_block, c_groups, B), block(512);
@@ -184,8 +178,7 @@ struct Bwd {
             // partial sums per workgroup + an ordered reduction when the scratch buffer holds them (see WgradArgs::partial)
             const long long n_w = static_cast<long long>(co_n) * (src.c0 + src.c1) * KK;
             const long long n_wg = static_cast<long long>(grid.x) * B;
-            static const bool partial_off = ake::diag_env("AKE_WGRAD_ATOMIC") != nullptr;
-            const bool use_partial = !partial_off && b.wg_partial && n_wg * n_w <= static_cast<long long>(b.wg_partial_floats);
+            const bool use_partial = b.wg_partial && n_wg * n_w <= static_cast<long long>(b.wg_partial_floats);
             if (use_partial) { wa.partial = b.wg_partial; wa.partial_stride = n_w; }
             bool launched = false;
             {
@@ -692,7 +685,7 @@ struct Bwd {
             }
             // rows per workgroup: kSemiRows at training batch sizes (few atomics), down to one row per wave when the batch is small
             const int S = P / 3, pair_groups = (C * C + 63) / 64;
-            const int want = (std::max(tiling_cus(2), 1) + B * pair_groups - 1) / (B * pair_groups);     // workgroups per clip that fill the chip
+            const int want = (std::max(device_cus(), 1) + B * pair_groups - 1) / (B * pair_groups);     // workgroups per clip that fill the chip
             const int rows = std::min(kSemiRows, std::max(4, (S + want - 1) / want));
             hipLaunchKernelGGL(semi_bwd_weight_kernel, dim3((S + rows - 1) / rows, B, pair_groups), dim3(256), lds, s, g, x, x_aff,
                                grad_of(m + "pool_semi.weight"), static_cast<long long>(n->grad_floats), C, P, Tn, rows, tile);

@@ -636,7 +636,6 @@ struct WgradArgs {
     int KH, KW;
     int rt_per_block;         // row tiles per workgroup
     int c_per_block;          // input channels per workgroup (cin: gridDim.y == 1; waves per workgroup: blockIdx.y walks the channel groups)
-    int dbg_noflush;          // timing experiments only (AKE_WGRAD_NOFLUSH): skip the atomics
     // nullable: every workgroup stores its partial dW as plain floats at partial[(blockIdx.z * gridDim.x + blockIdx.x) * partial_stride + ...]
     // and wgrad_partial_reduce_kernel adds them up in workgroup order (deterministic; one atomic per weight instead of one per weight
     // and workgroup: 6.3 M 64-bit atomics per pitch-class convolution and step cost 0.3 of its 1.1 ms)
@@ -841,7 +840,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_kernel(WgradArgs wa) {
 #pragma unroll
                     for (int reg = 0; reg < 4; ++reg) {
                         const int co = 16 * m + 4 * q + reg;
-                        if (co < a.cout && kk < KK && !wa.dbg_noflush) {
+                        if (co < a.cout && kk < KK) {
                             const long long idx = (static_cast<long long>(co) * cin + ci) * KK + kk;
                             if (wa.partial) wa.partial[(static_cast<long long>(blockIdx.z) * gridDim.x + blockIdx.x) * wa.partial_stride + idx] = acc[m][nt][reg];
                             else grad_add(dWs + idx, acc[m][nt][reg]);

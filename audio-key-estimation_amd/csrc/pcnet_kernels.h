@@ -361,7 +361,6 @@ struct MfmaArgs {
     int ntiles_total;     // N-tiles of the whole layer (fragment stride)
     int cin_chunk;        // input channels staged in LDS at a time
     int h1_magic;         // ceil(2^16 / h1): (row * h1_magic) >> 16 == row / h1 for the row counts used here
-    int dbg;              // ablation (AKE_ABLATE): 1 = skip the MFMA steps, 2 = skip the staging loads (results wrong, timing only)
     int row_k;            // 1: 1-wide kernels over KH = 4 * (steps per channel) circular rows (--denseblock's 12 x 1 bottleneck): the four k
                           //    of a step are four consecutive ROWS of one frame instead of four taps of one row; `KH` counts steps
     int ksplit;           // 1: the layer has <= MT M-tiles per workgroup (1-channel head convs): all waves share them and
@@ -457,7 +456,7 @@ __global__ __launch_bounds__(512) void conv_mfma_kernel(MfmaArgs ma) {
         // ---- stage channels [c_lo, c_lo+cc): rows and frames with both halos resolved.  One wave per patch row (row
         //      arithmetic is wave-uniform), lanes walk consecutive frames (coalesced); 4 rows x <=3 column blocks of
         //      loads are in flight before the first LDS write.
-        if (ma.dbg != 2) {
+        {
             const int nrows = cc * R_in;
             constexpr int UR = 4;
             // (cl, rj) of patch row `wave`, advanced by nw rows per step without any division
@@ -533,7 +532,7 @@ __global__ __launch_bounds__(512) void conv_mfma_kernel(MfmaArgs ma) {
             }
         }
         __syncthreads();
-        if (!active || ma.dbg == 1) continue;
+        if (!active) continue;
         // ---- this wave's steps of the chunk: step index -> (channel cl, row dy); fragments are fetched one step ahead.
         //      The cursor is wave-uniform and advanced with adds only: a_off / b_off are LDS float offsets. ----
         constexpr int GF = KS * NT * 64;
@@ -882,14 +881,7 @@ struct P2pPsArgs {
     const float* sbias;
     int H, T, R, J, Tp, n_row_tiles, n_tiles, plane_pos;   // plane_pos: (R + 6) * Tp rounded up to 64 positions
     int n_oct, n_units;           // OUT == 3: octaves (H / 36) and work units (clip, group of R rows within an octave) = batch * 36 / R
-    unsigned long long* stamps;   // diagnostic build (AKE_P2P_STAMP): [8 waves][8] cycle sums of the tile loop's sections, workgroup 0
 };
-
-__device__ __forceinline__ unsigned long long p2p_stamp() {
-    unsigned long long t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-    return t;
-}
 
 constexpr int kP2pPieces = 3;        // 1 KB pieces of the patch a wave requests per tile (8 waves: planes of up to 24 pieces)
 constexpr int kP2pPsStage = 80;      // uint4 per M-tile of a wave's staging slab (NCHW form: 8 channels x 36 floats, padded)
@@ -908,8 +900,7 @@ constexpr int kP2pPsStage = 80;      // uint4 per M-tile of a wave's staging sla
 //   (P2pPsArgs::uh): two loads, three registers and six bit operations per patch position instead of five loads, five registers and the
 //   conversions, which lets this form run two workgroups per CU like its plane-fed siblings (<1, 5>: 133 VGPRs, one workgroup per CU, 83 us
 //   against their 46; the f32 log-CQT handed over frames-major also cost it a cache line per LANE in the texture addresser)
-// STAMP: diagnostic build with s_memtime stamps around the tile loop's sections (tools/p2p_stamp.py; shares, never timed)
-template <int OUT, int NIN, bool STAMP = false>
+template <int OUT, int NIN>
 __global__ __launch_bounds__(512, ((NIN > 0 && NIN != 3) ? 2 : 4)) void conv_p2p_f16_ps_kernel(P2pPsArgs a) {   // (the assembling loader's 15 input registers do not fit 128)
     constexpr bool OUT_CL = OUT == 1, OUT_SEMI = OUT == 2 || OUT == 3, OUT_FOLD = OUT == 3;
     constexpr bool IN_NCHW = NIN > 0;
@@ -1174,7 +1165,6 @@ __global__ __launch_bounds__(512, ((NIN > 0 && NIN != 3) ? 2 : 4)) void conv_p2p
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) { acc[mt] = f32x4c{0.f, 0.f, 0.f, 0.f}; accl[mt] = f32x4c{0.f, 0.f, 0.f, 0.f}; }
     int cur = 0;
-    unsigned long long sm[6] = {0, 0, 0, 0, 0, 0}, ts[6];
     int unit = first, oct = 0, prev_oct = 0;
     for (int tile = tile0; tile >= 0; cur ^= 1) {
         int next, n_unit = unit, n_oct_i = oct;
@@ -1182,20 +1172,16 @@ __global__ __launch_bounds__(512, ((NIN > 0 && NIN != 3) ? 2 : 4)) void conv_p2p
             if (++n_oct_i == a.n_oct) { n_oct_i = 0; n_unit += nwg; }
             next = n_unit < a.n_units ? fold_tile(n_unit, n_oct_i) : -1;
         } else next = tile + nwg < a.n_tiles ? tile + nwg : -1;
-        if (STAMP) ts[0] = p2p_stamp();
         // this wave's share of the tile's patch has landed (and its stores have left).  The builtin, not asm: hipcc then knows that
         // nothing of its own is pending at the loop top and places no vmcnt wait inside the loop that would also drain the LDS-DMA
         __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
-        if (STAMP) ts[1] = p2p_stamp();
         __syncthreads();              // ... every wave's; and every wave is done with the other half
-        if (STAMP) ts[2] = p2p_stamp();
         const bool more = next >= 0;
         if (has_prev) {
             if (OUT_SEMI) semi_stage(cur ^ 1, prev_base, prev_mblk, prev_oct);
             else if (late) epilogue(acc, accl, 0);
         }
         const uint4* const pH = lds4 + cur * a.plane_pos;
-        if (STAMP) ts[3] = p2p_stamp();
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) { acc[mt] = f32x4c{0.f, 0.f, 0.f, 0.f}; accl[mt] = f32x4c{0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll
@@ -1219,7 +1205,6 @@ __global__ __launch_bounds__(512, ((NIN > 0 && NIN != 3) ? 2 : 4)) void conv_p2p
             for (int mt = 0; mt < MT; ++mt)
                 if (kP2pProducts == 2) accl[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[mt], bl, accl[mt], 0, 0, 0);
         }
-        if (STAMP) ts[4] = p2p_stamp();
         if (!late) epilogue(acc, accl, cur);
         if (IN_NCHW && more) write_lds(cur ^ 1);
         {
@@ -1235,16 +1220,6 @@ __global__ __launch_bounds__(512, ((NIN > 0 && NIN != 3) ? 2 : 4)) void conv_p2p
         }
         has_prev = true;
         tile = next; unit = n_unit; oct = n_oct_i;
-        if (STAMP) {
-            ts[5] = p2p_stamp();
-#pragma unroll
-            for (int i = 0; i < 5; ++i) sm[i] += ts[i + 1] - ts[i];
-            sm[5] += 1;
-        }
-    }
-    if (STAMP && blockIdx.x == 0 && lane == 0 && a.stamps) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) a.stamps[wave * 8 + i] = sm[i];
     }
     if (has_prev) {
         if (OUT_SEMI) {

@@ -38,9 +38,8 @@ typedef void* ake_stream_t; /* hipStream_t */
 
 int ake_version(void);
 const char* ake_last_error(void);
-/* 1 if the library was built with -DAKE_DIAG (`AKE_DIAG=1 csrc/build.sh`): only then are the AKE_* environment switches of the kernel
- * experiments (A/B kernel selection, phase ablation, in-kernel cycle stamps) read at all.  The shipped build returns 0 and never looks at
- * the environment: nothing a process inherits can change results or precision. */
+/* Always 0: there is one build, and it never looks at the environment, so nothing a process inherits can change results or precision.
+ * (Kept for ABI compatibility: it once told a diagnostic build apart.) */
 int ake_build_has_diag(void);
 
 /* ------------------------------------------------------------------------------------------

@@ -155,15 +155,20 @@ def test_workspace_queries_need_no_gpu():
 
 
 def test_shipped_library_reads_no_environment_switch():
-    """the shipped build has no switch an inherited environment variable could flip -- the AKE_* knobs of the kernel
-    experiments exist only under -DAKE_DIAG (`AKE_DIAG=1 csrc/build.sh` -> libake_hip_diag.so).  The library does not even import getenv."""
+    """there is one build, and no switch an inherited environment variable could flip -- neither in the library (it
+    does not even import getenv) nor in the binding that picks the library to load."""
     import subprocess
+    import sys
     lib = _lib.lib()
     assert lib.ake_build_has_diag() == 0
     assert os.path.basename(_lib.LIB_PATH) == "libake_hip.so"
     syms = subprocess.run(["nm", "-D", "--undefined-only", _lib.LIB_PATH], capture_output=True, text=True)
     if syms.returncode == 0:                                        # (binutils present on the build and the GPU image)
         assert "getenv" not in syms.stdout
+    child = subprocess.run([sys.executable, "-c", "import ake_amd; print(ake_amd._lib.LIB_PATH)"], cwd=REPO, capture_output=True, text=True,
+                           env=dict(os.environ, AKE_USE_DIAG_LIB="1"), timeout=300)
+    assert child.returncode == 0, child.stderr
+    assert os.path.basename(child.stdout.strip().splitlines()[-1]) == "libake_hip.so"
 
 
 def test_precision_is_part_of_the_config():

@@ -446,8 +446,9 @@ def test_mixed_precision_inference_on_trained_weights():
 
     Measured (round 3): 'f32x3' 1e-6 .. 6e-6; 'mixed' 4e-4 .. 8e-4 -- INSIDE the 1e-3 budget but 30x the 2e-5 it shows on seeded-random
     weights: trained filters difference nearly equal inputs, so the unbiased 2^-12 operand roundings of the f16 single-product kernels no
-    longer average out against the output.  Diagnostic build, same trained net: pitch convolutions on exact f32 (AKE_P2P_F32) 6.7e-4, layer 0 +
-    pitch-class kernels on exact f32 (AKE_PC_F32) 4.2e-4, both 1e-6: layer 0's f16 stack contributes ~6.7e-4, the pitch stack ~4.2e-4.
+    longer average out against the output.  Measured in round 3 with the diagnostic build's kernel switches (since removed), same trained
+    net: pitch convolutions on exact f32 6.7e-4, layer 0 + pitch-class kernels on exact f32 4.2e-4, both 1e-6: layer 0's f16 stack
+    contributes ~6.7e-4, the pitch stack ~4.2e-4.
     So: 'mixed' is asserted against the BUDGET (1e-3) here, and who needs margin on a trained net asks for opt.precision = 'f32x3'."""
     opt = Namespace(conv_layers=3, n_filters=4, head_layers=2, time_pool_size=2, genre=True, max_pool=False, frames=5, octaves=8, lr=1e-3,
                     gamma=0.96, acc_grad=2, reg=0, key_weight=1.0, tonic_weight=1.0, genre_weight=0.1, use_cos=False, no_ckpt=True, local=False,

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Per-tensor gradient errors of the default net at a large batch against float64 autograd through the oracle (the statement of
-tests/test_gpu_train_scale.py, every row printed).  Environment switches of the library (AKE_P2P_TRAIN_F32=1, AKE_PC_TRAIN_F32=1,
-AKE_WGRAD_F32=1) select the f32 kernels for bisecting.      python3 tests/tools/big_grad_rows.py [batch=32] [seed=1] [frames=76]"""
+tests/test_gpu_train_scale.py, every row printed).      python3 tests/tools/big_grad_rows.py [batch=32] [seed=1] [frames=76]"""
 import os, sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE))); sys.path.insert(0, os.path.dirname(HERE))

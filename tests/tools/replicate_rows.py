@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-tensor difference between the gradients of 8 shuffled copies of a 32-clip batch and those of the 32-clip batch itself (both on
-the device; tests/test_gpu_train_scale.py).  AKE_USE_DIAG_LIB=1 + AKE_WGRAD_F32=1 / AKE_P2P_TRAIN_F32=1 / AKE_PC_TRAIN_F32=1 bisect."""
+the device; tests/test_gpu_train_scale.py)."""
 import os, sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE))); sys.path.insert(0, os.path.dirname(HERE))
