@@ -5,6 +5,12 @@ Keeps the reference's dataset surface (KeyDataset.py:32-264): ``KeyDataset(genre
 same keys, dtypes and zero padding to ``seq_length_max``; loaders expose ``name``,
 ``get_filenames()`` and ``get_all(file, pitch_shift, genre, opt, multi_scale)``.
 
+With ``opt.local`` (per-frame key tracking) every label tensor of a clip with T CQT frames is its
+row repeated ``T - (loc_window_size * frames - 1)`` times (KeyDataset.py:345-348, 457-465: the
+non-Winterreise path), and ``ds[i]`` zero-pads the mel and every label tensor to
+``seq_length_max`` rows with ``seq_length = T`` (KeyDataset.py:225-241).  Winterreise's local-key
+segment annotations are not built (annotation parsing is out of scope, see below).
+
 What differs, on purpose: the reference computes one CQT per file on a CPU thread inside
 ``get_all`` (KeyDataset.py:488-495) and caches it on disk.  Here loaders hand over *waveforms*
 and ``import_data`` batches clips of equal length through ``ake_cqt_logmag_f32``; nothing is
@@ -47,6 +53,23 @@ def labels_for_signature(sig: int, genre_id: int | None, genre_flag: bool):
     else:
         genre = torch.zeros(8)
     return key_labels, key_signature_id, genre, tonic
+
+
+def local_labels(labels, n_frames: int, opt, clip=None):
+    """--local per-frame labels (KeyDataset.py:345-348, 457-465): each (C,) label tensor of ``labels`` -> its row repeated over the
+    clip's ``time_length = n_frames - (loc_window_size * frames - 1)`` rows, (time_length, C).  A clip shorter than one local window
+    (time_length < 1) is refused: the reference gives it an empty label tensor and a NaN loss."""
+    span = getattr(opt, "loc_window_size", 10) * getattr(opt, "frames", 5)
+    rows = n_frames - (span - 1)
+    if rows < 1:
+        raise ValueError(f"--local: clip {clip!r} has {n_frames} CQT frames, fewer than the {span} of one local window "
+                         f"(loc_window_size * frames): it has no frame to label")
+    return tuple(t.reshape(1, -1).repeat(rows, 1) for t in labels)
+
+
+def pad_rows(t: torch.Tensor, rows: int) -> torch.Tensor:
+    """(r, C) -> (rows, C), zeros after the first r rows (KeyDataset.py:228-233)."""
+    return torch.cat((t, torch.zeros([rows - t.shape[0], t.shape[1]], dtype=t.dtype)), dim=0)
 
 
 class DatasetLoader:
@@ -170,9 +193,10 @@ class KeyDataset:
         self.opt = opt
         self.seq_length_max = 0
         self.cqt_batch = cqt_batch
-        if getattr(opt, "local", False):
-            raise NotImplementedError("--local datasets (per-frame labels, KeyDataset.py:443-454) are not built; PitchClassNet(opt.local) "
-                                      "inference is (SURVEY.md section 8f)")
+        self.local = bool(getattr(opt, "local", False))
+        if self.local and getattr(opt, "frames", 5) <= 0:
+            raise ValueError("--local needs --frames > 0: its per-frame labels are counted in local windows of loc_window_size * frames "
+                             "CQT frames")
 
     def __len__(self):
         return len(self.filenames)
@@ -228,12 +252,19 @@ class KeyDataset:
                 for j, i in enumerate(part):
                     self.mel[str(i)] = mel[j:j + 1, :, :keep(lens[j])].clone()          # (1, bins, T_i)
                     self.mel2[str(i)] = None
+        self.store_labels()
+        print("done", flush=True)
+
+    def store_labels(self):
+        """Labels of every clip (KeyDataset.py:441-467); with --local per frame of its stored mel (local_labels)."""
         for idx, (f, dname, _) in enumerate(self.filenames):
             ld = self.datasets[dname]
-            kl, ks, g, t = labels_for_signature(ld.get_key_signature_id(f), ld.get_genre_id(f), self.genre)
+            labels = labels_for_signature(ld.get_key_signature_id(f), ld.get_genre_id(f), self.genre)
+            if self.local:
+                labels = local_labels(labels, self.mel[str(idx)].shape[2], self.opt, clip=f"{dname}/{f}")
+            kl, ks, g, t = labels
             self.key_labels[str(idx)], self.key_signature_id[str(idx)] = kl, ks
             self.genre_labels[str(idx)], self.tonic_labels[str(idx)] = g, t
-        print("done", flush=True)
 
     def find_longest_seq(self):
         for i in range(len(self.mel)):                                                # KeyDataset.py:113-119
@@ -242,6 +273,13 @@ class KeyDataset:
 
     def __getitem__(self, idx):
         mel = self.mel[str(idx)]
+        if self.local:                                                                  # KeyDataset.py:224-241
+            rows = self.seq_length_max
+            padded = torch.cat((mel, torch.zeros([mel.shape[0], mel.shape[1], rows - mel.shape[2]], dtype=mel.dtype)), dim=2)
+            return {"mel": padded, "key_labels": pad_rows(self.key_labels[str(idx)], rows),
+                    "tonic_labels": pad_rows(self.tonic_labels[str(idx)], rows),
+                    "key_signature_id": pad_rows(self.key_signature_id[str(idx)], rows),
+                    "genre": pad_rows(self.genre_labels[str(idx)], rows), "seq_length": mel.shape[2]}
         if getattr(self.opt, "frames", 5) <= 0:                                          # KeyDataset.py:257-262: no seq_length, no padding
             return {"mel": mel, "key_labels": self.key_labels[str(idx)], "tonic_labels": self.tonic_labels[str(idx)],
                     "key_signature_id": self.key_signature_id[str(idx)], "genre": self.genre_labels[str(idx)]}

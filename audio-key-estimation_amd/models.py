@@ -256,6 +256,14 @@ class _TrainStep(torch.autograd.Function):
         return (None, None, None) + tuple(grads)
 
 
+def _onehot_labels(t, dev):
+    """One-hot label tensor as the loss kernels take it: on ``dev``, float32 or int64, contiguous; -> (tensor, is_int64)."""
+    t = t.to(dev)
+    if t.dtype not in (torch.float32, torch.int64):
+        t = t.long() if not t.is_floating_point() else t.float()
+    return t.contiguous(), int(t.dtype == torch.int64)
+
+
 class _FusedGeneralStep(torch.autograd.Function):
     """general_step's loss, its gradient w.r.t. the network outputs and the nine metrics in ONE launch (ake_general_step_f32) instead of
     ~110 torch kernels forward and ~50 in autograd's backward (models.py:826-905, 1065-1116).  Returns a float32 tensor of 10 scalars in
@@ -265,13 +273,7 @@ class _FusedGeneralStep(torch.autograd.Function):
     def forward(ctx, key_out, tonic_out, genre_out, key_labels, tonic_labels, genre_labels, key_signature_id, weights, use_cos):
         dev = key_out.device
         B = key_out.shape[0]
-
-        def onehot(t):
-            t = t.to(dev)
-            if t.dtype not in (torch.float32, torch.int64):
-                t = t.long() if not t.is_floating_point() else t.float()
-            return t.contiguous(), int(t.dtype == torch.int64)
-
+        onehot = lambda t: _onehot_labels(t, dev)
         # (float64 outputs -- the reference's dtype, train_model.py:106 -- are the kernels' float32 values cast up: the cast back is exact)
         key, tonic = key_out.detach().float().contiguous(), tonic_out.detach().float().contiguous()
         genre = genre_out.detach().float().contiguous() if genre_out is not None else None
@@ -302,6 +304,45 @@ class _FusedGeneralStep(torch.autograd.Function):
         d_tonic = scaled[B * 12:B * 24].view(B, 12)
         d_genre = scaled[B * 24:B * 35].view(B, 11) if ctx.has_genre else None
         return d_key, d_tonic, d_genre, None, None, None, None, None, None
+
+
+class _FusedGeneralStepLocal(torch.autograd.Function):
+    """general_step's --local loss (models.py:861-876, 898-909), its gradient w.r.t. the per-frame outputs and the nine metrics in two
+    launches (ake_general_step_local_f32) instead of a Python loop over the clips (BCE, cross entropy, the batched MIREX and the tonic
+    accuracy per clip, and autograd's backward of every slice).  ``valid``: n_i per clip (host ints, already checked against the
+    extents).  Returns a float32 tensor of 10 scalars in general_step's order; only element 0 (the loss) carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, key_out, tonic_out, key_labels, tonic_labels, key_signature_id, valid, weights):
+        dev = key_out.device
+        B, T = key_out.shape[0], key_out.shape[1]
+        key, tonic = key_out.detach().float().contiguous(), tonic_out.detach().float().contiguous()
+        kl = key_labels.to(device=dev, dtype=torch.float32).contiguous()
+        tl, tl64 = _onehot_labels(tonic_labels, dev)
+        sl, sl64 = _onehot_labels(key_signature_id, dev)
+        R = kl.shape[1]
+        if kl.shape != (B, R, 12) or tl.shape != (B, R, 12) or sl.shape != (B, R, 24):
+            raise ValueError(f"--local labels must be (B, R, 12 | 12 | 24) with B = {B}: got key_labels {tuple(kl.shape)}, "
+                             f"tonic_labels {tuple(tl.shape)}, key_signature_id {tuple(sl.shape)}")
+        n_dev = torch.tensor(valid, dtype=torch.int32).to(dev)          # the one upload (the global path uploads seq_length in forward)
+        L = _lib.lib()
+        ws = torch.empty(L.ake_general_step_local_workspace_bytes(B, T), dtype=torch.uint8, device=dev)
+        need_grad = any(ctx.needs_input_grad[:2])
+        scal = torch.empty(10, dtype=torch.float32, device=dev)
+        grads = torch.empty((2, B, T, 12), dtype=torch.float32, device=dev) if need_grad else None
+        with torch.cuda.device(dev):
+            _lib.check(L.ake_general_step_local_f32(
+                key.data_ptr(), tonic.data_ptr(), kl.data_ptr(), tl.data_ptr(), tl64, sl.data_ptr(), sl64, n_dev.data_ptr(), B, T, R,
+                weights[0], weights[1], scal.data_ptr(), grads[0].data_ptr() if need_grad else None,
+                grads[1].data_ptr() if need_grad else None, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
+                "ake_general_step_local_f32")
+        ctx.grads, ctx.out_dtype = grads, key_out.dtype
+        return scal
+
+    @staticmethod
+    def backward(ctx, g):
+        scaled = (ctx.grads * g[0]).to(ctx.out_dtype)                   # one multiply (+ one cast) for both gradients
+        return scaled[0], scaled[1], None, None, None, None, None
 
 
 def _opt_get(opt, name, default):
@@ -810,7 +851,8 @@ class PitchClassNet(LightningModule):
     def _general_step_local(self, batch):
         """--local branch of general_step (models.py:861-876, 898-909): per-frame labels (B, T', 12); for every clip the losses and
         scores cover its first ``seq_length - loc_window_size * frames + 1`` frames and are averaged over the batch.  The tonic accuracy
-        covers two frames fewer (the reference's ``seq_length - (loc_window_size * frames + 1)``, :906 -- kept).  The reference's
+        covers two frames fewer (the reference's ``seq_length - (loc_window_size * frames + 1)``, :906 -- kept).  On the device this
+        is _FusedGeneralStepLocal (two launches); the per-clip loop below is the fused_loss = False path and the fallback.  The reference's
         --local --genre lines (:866-873, :907-911) index a (B, 11) "mask" into per-frame tensors and re-mask inside the clip loop;
         they cannot run for any batch, so that combination is refused here rather than invented."""
         opt = self.opt
@@ -818,16 +860,31 @@ class PitchClassNet(LightningModule):
             raise NotImplementedError("general_step with --local and --genre: the reference's lines (models.py:866-873) do not run; "
                                       "forward / backward of such a net are available, the loss is the caller's")
         mel = batch["mel"]
+        span = _opt_get(opt, "loc_window_size", 10) * _opt_get(opt, "frames", 5)
+        seq = [int(v) for v in torch.as_tensor(batch["seq_length"]).reshape(-1).tolist()]        # read before the forward is queued
         out = self.forward(mel, None)
         key_out, tonic_out = out[0], out[1]
         dev = key_out.device
+        B = mel.shape[0]
+        valid = [s - span + 1 for s in seq]
+        use_cos = _opt_get(opt, "use_cos", False)
+        # the device path on the global path's condition; the loop below keeps use_cos (its per-frame cosine_similarity(dim=1) only runs
+        # when the label rows equal T') and clips with n < 3 (the reference's slicing of n - 2 <= 0 rows)
+        if (key_out.is_cuda and key_out.dtype in (torch.float32, torch.float64) and type(self).mirex_score is PitchClassNet.mirex_score
+                and self.fused_loss and not use_cos and len(valid) == B and min(valid) >= 3):
+            T, R = key_out.shape[1], batch["key_labels"].shape[1]
+            bad = [(i, n) for i, n in enumerate(valid) if n > T or n > R]
+            if bad:
+                raise ValueError(f"--local general_step: clip(s) {bad} score n = seq_length - {span} + 1 frames, more than the "
+                                 f"{T} output frames or the {R} label rows")
+            weights = (float(_opt_get(opt, "key_weight", 1.0)), float(_opt_get(opt, "tonic_weight", 1.0)))
+            vals = _FusedGeneralStepLocal.apply(key_out, tonic_out, batch["key_labels"], batch["tonic_labels"], batch["key_signature_id"],
+                                                valid, weights)
+            return tuple(vals.unbind(0))
         key_labels = batch["key_labels"].to(device=dev, dtype=key_out.dtype)
         tonic_labels = batch["tonic_labels"].long().to(dev)
         tonic_idx = torch.argmax(tonic_labels, dim=2)
         key_signature_id = batch["key_signature_id"].to(dev)
-        span = _opt_get(opt, "loc_window_size", 10) * _opt_get(opt, "frames", 5)
-        seq = [int(v) for v in torch.as_tensor(batch["seq_length"]).reshape(-1).tolist()]
-        B = mel.shape[0]
         bce = tonic_loss = 0
         sums = [0.0] * 7
         acc_tonic = 0.0
@@ -841,7 +898,7 @@ class PitchClassNet(LightningModule):
                 m = seq[i] - (span + 1)
                 acc_tonic = acc_tonic + (torch.argmax(tonic_out[i, :m], dim=1) == tonic_idx[i, :m]).float().mean()
         loss = _opt_get(opt, "key_weight", 1.0) * bce / B + _opt_get(opt, "tonic_weight", 1.0) * tonic_loss / B
-        if _opt_get(opt, "use_cos", False):
+        if use_cos:
             loss = loss + (1 - F.cosine_similarity(key_out, key_labels, dim=1).sum() / key_out.shape[0])
         mirex, correct, fifths, relative, parallel, other, accuracy = [torch.as_tensor(v / B).clone().float() for v in sums]
         return (loss, accuracy, mirex, correct, fifths, relative, parallel, other, torch.as_tensor(acc_tonic / B).float(),

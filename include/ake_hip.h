@@ -281,6 +281,25 @@ int ake_general_step_f32(const float* key_out_dev, const float* tonic_out_dev, c
                          float genre_weight, int use_cos, float* scalars_out_dev, float* d_key_dev, float* d_tonic_dev, float* d_genre_dev,
                          ake_stream_t stream);
 
+/* general_step of a --local net (models.py:861-876, 898-909): per-frame outputs key_out (after the sigmoid) and tonic_out (logits),
+ * [batch][out_frames][12] as the forward returns them; labels with their own row count, key_labels [batch][label_frames][12] float32,
+ * tonic_labels [batch][label_frames][12] and key_signature_id [batch][label_frames][24] one-hot, float32 or int64 (the *_i64 flags;
+ * float tonic labels are truncated as .long() does, key-signature labels are not).  valid_frames_dev[batch] (int32, on the device):
+ * n_i = seq_length_i - loc_window_size * frames + 1, the rows of clip i that are scored; the contract is 3 <= n_i <= min(out_frames,
+ * label_frames), and values outside [0, min(out_frames, label_frames)] are read clamped to it (results unspecified, reads in bounds).
+ * scalars_out_dev[10], general_step's order: loss = key_weight * mean_i BCE_i + tonic_weight * mean_i CE_i (BCE_i over the clip's
+ * n_i * 12 elements, CE_i over its n_i frames); accuracy, mirex_score, correct, fifths, relative, parallel, other: each clip's MIREX
+ * categories over its n_i frames / n_i (the table match of ake_general_step_f32), mean over the clips; accuracy_tonic: per clip over
+ * its first n_i - 2 frames (the reference's seq_length - (span + 1)), mean over the clips (a clip with n_i <= 2 adds 0); 0.
+ * d_key_dev / d_tonic_dev (both or none) [batch][out_frames][12]: dloss/d(key_out | tonic_out), rows t >= n_i exact zeros.
+ * Two launches (per-chunk partial sums in the workspace, then a fixed-order reduction): bit-reproducible.  Workspace from
+ * ake_general_step_local_workspace_bytes(batch, out_frames) (0 for batch < 1 or out_frames < 1). */
+size_t ake_general_step_local_workspace_bytes(int batch, int out_frames);
+int ake_general_step_local_f32(const float* key_out_dev, const float* tonic_out_dev, const float* key_labels_dev, const void* tonic_labels_dev,
+                               int tonic_labels_i64, const void* key_signature_id_dev, int key_signature_i64, const int* valid_frames_dev,
+                               int batch, int out_frames, int label_frames, float key_weight, float tonic_weight, float* scalars_out_dev,
+                               float* d_key_dev, float* d_tonic_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream);
+
 /* Debug tap: copy an intermediate activation of the LAST forward call out of the workspace.
  * name is the reference module path whose output it is (e.g. "model.1.p2p.layer.8"). */
 int ake_pcnet_tap_info(const ake_pcnet* net, const char* name, int batch, int frames, int64_t shape[4]);
