@@ -136,9 +136,12 @@ __device__ __forceinline__ void store_level(const Args& a, Ctx& cx, const float 
     constexpr int P = LV < kStages ? LV : 0;
     if (LV < kStages) {
         if (!near_frame(cx.fc[P], gs * (1 << LV), (gs + 32) * (1 << LV), a.need[P], a.hop)) return;
-        const int g0 = gs + a.ppad;                                               // the whole group inside the row (its pads are wider than any window)
-        if (g0 < 0 || g0 + 32 > a.p_count[P]) return;
-        if (cx.live) store_words8(a.ph[P], static_cast<long long>(cx.clip) * a.p_stride[P] + g0 + 8 * cx.q, c);
+        // A group that straddles an end of the row keeps the lanes whose 8 words lie inside it.  (Dropping the whole group left up to 28
+        // words at the row's start unwritten -- groups start at 32 T - kOff[LV] + ppad -- while a window starts ppad - uh >= 8 words in:
+        // with 12 bins per octave frame 0 of octaves 2 and 3 read 1 to 5 words of whatever the workspace held.  Now at most 4 stay unwritten.)
+        const int w0 = gs + a.ppad + 8 * cx.q;
+        if (w0 < 0 || w0 + 8 > a.p_count[P]) return;
+        if (cx.live) store_words8(a.ph[P], static_cast<long long>(cx.clip) * a.p_stride[P] + w0, c);
     } else {
         if (!cx.live) return;
         float* row = a.next + static_cast<long long>(cx.clip) * a.next_stride;
@@ -284,12 +287,12 @@ __global__ __launch_bounds__(64) void cqt_stream_kernel(Args a) {
         for (int h = 0; h < 2; ++h) {
             const int g = 64 * c + 32 * h;
             if (!near_frame(cx.fc[0], g, g + 32, a.need[0], a.hop)) continue;
-            const int g0 = g + a.ppad;
-            if (g0 < 0 || g0 + 32 > a.p_count[0] || !cx.live) continue;
+            const int w0 = g + a.ppad + 8 * cx.q;                                  // per lane, as in store_level
+            if (w0 < 0 || w0 + 8 > a.p_count[0] || !cx.live) continue;
             float cc[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) cc[i] = r[8 * h + i];
-            store_words8(a.ph[0], static_cast<long long>(cx.clip) * a.p_stride[0] + g0 + 8 * cx.q, cc);
+            store_words8(a.ph[0], static_cast<long long>(cx.clip) * a.p_stride[0] + w0, cc);
         }
     };
 

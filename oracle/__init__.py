@@ -23,4 +23,8 @@ Pinning status (see DESIGN.md section "Oracle"):
     ``cqt_oracle`` restates librosa's *published definition* (direct-form
     constant-Q transform) in float64; it is the
     build's own specification of that stage.
+  * ``cqt_multirate_oracle`` -- float64 model of the *algorithm* the HIP CQT
+    evaluates (half-band decimators, per-phase filter banks), checked against
+    ``cqt_oracle`` on the CPU; the kernels are held to it to rounding error.
+    Also holds the probe signals and the per-bin error measure of those tests.
 """

@@ -2,7 +2,8 @@
 
 The CQT oracle is the build's own specification (parity with librosa is UNPINNED, oracle/cqt_oracle.py).
 Tolerance: 1e-3 of the tensor's peak (north_star); the multirate evaluation's own error is ~1.5e-4
-(tests/tools/cqt_multirate_proto.py), so we assert 5e-4.
+(tests/tools/cqt_multirate_proto.py), so we assert 5e-4.  The tight comparison (kernels against the float64 model of their own algorithm,
+per element, tolerances of 1e-6 .. 1e-5 of full scale) is tests/test_gpu_cqt_model.py.
 """
 import numpy as np
 import pytest

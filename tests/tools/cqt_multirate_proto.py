@@ -2,9 +2,12 @@
 """Design study for the device CQT: octave-decimated (multirate) evaluation vs the
 direct-form specification in ``oracle/cqt_oracle.py``.
 
-Not shipped, not imported by the product: a numpy model of the algorithm the HIP
+Not shipped, not imported by the product: the per-bin loop form of the algorithm the HIP
 kernels implement (``csrc/cqt.hip``), used to choose the decimator length / Kaiser
-beta and to size the error budget recorded in DESIGN.md.
+beta and to size the error budget recorded in DESIGN.md.  The vectorised model the tests
+use is ``oracle/cqt_multirate_oracle.py``; this loop is the slow, obviously-right statement
+of the same arithmetic and takes the decimator, its taps and the cascade gain from there
+(``tests/test_oracle_cqt.py`` holds the two to 1e-12 of full scale).
 
     python3 tests/tools/cqt_multirate_proto.py
 """
@@ -20,29 +23,10 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, REPO)
 from oracle import cqt_oracle as O  # noqa: E402
+from oracle import cqt_multirate_oracle as M  # noqa: E402  (the decimator, its float32-rounded taps and the cascade gain: one copy)
+from oracle.cqt_multirate_oracle import kaiser_halfband  # noqa: E402,F401
 
 synthetic = importlib.import_module("audio-key-estimation_amd.synthetic")
-
-
-def kaiser_halfband(half_len, beta):
-    j = np.arange(-half_len, half_len + 1, dtype=np.float64)
-    h = 0.5 * np.sinc(j / 2.0) * np.kaiser(2 * half_len + 1, beta)
-    return h / h.sum()
-
-
-def decimate(y, y_lo, h):
-    """y holds samples m = y_lo .. y_lo+len-1 (zero outside). Returns (y2, y2_lo) on the half-rate grid:
-    y2[m] = sum_j h[j] y[2m + j], stored for m in [-Hh, ceil(n/2)+Hh)."""
-    Hh = (len(h) - 1) // 2
-    n_live = len(y) + y_lo * 2 if False else None  # unused
-    hi = y_lo + len(y)                      # exclusive end of stored input
-    m_lo = math.floor((y_lo - Hh) / 2)
-    m_hi = math.ceil((hi + Hh) / 2)
-    ypad = np.concatenate([np.zeros(2 * Hh + 4), y, np.zeros(2 * Hh + 4)])
-    off = 2 * Hh + 4 - y_lo                  # index of sample 0 in ypad
-    ms = np.arange(m_lo, m_hi)
-    idx = (2 * ms + off)[:, None] + np.arange(-Hh, Hh + 1)[None, :]
-    return ypad[idx] @ h, m_lo
 
 
 def multirate_cqt(y, sr, hop, n_bins=288, bpo=36, half_len=31, beta=10.0, dtype=np.float64, gain_fix=True):
@@ -52,7 +36,7 @@ def multirate_cqt(y, sr, hop, n_bins=288, bpo=36, half_len=31, beta=10.0, dtype=
     freqs = O.cqt_frequencies(n_bins, bpo)
     lengths = O.cqt_lengths(sr, n_bins, bpo)
     n_oct = math.ceil(n_bins / bpo)
-    h = kaiser_halfband(half_len, beta)
+    h0, hodd = M.decim_taps(half_len, beta)                      # as the kernels hold them: float32 values, even taps dropped
     out = np.zeros((n_bins, T), dtype=np.complex128)
     yo, yo_lo = y.astype(np.float64), 0
     for o in range(n_oct):
@@ -78,14 +62,10 @@ def multirate_cqt(y, sr, hop, n_bins=288, bpo=36, half_len=31, beta=10.0, dtype=
                 g = (dec * math.sqrt(lengths[k]) / (L / 2.0)) * w * np.exp(-2j * np.pi * freqs[k] * pos / sr)
                 if gain_fix and o > 0:
                     # undo the decimator cascade's passband droop at this bin's centre frequency
-                    gain = 1.0
-                    for s in range(o):
-                        wn = 2 * np.pi * freqs[k] / (sr / 2 ** s)
-                        gain *= abs(np.sum(h * np.exp(-1j * wn * np.arange(-half_len, half_len + 1))))
-                    g = g / gain
+                    g = g / M.cascade_gain(freqs[k], o, sr, h0, hodd)
                 out[k, t] = np.dot(seg.astype(dtype), g.real.astype(dtype)) + 1j * np.dot(seg.astype(dtype), g.imag.astype(dtype))
         if o + 1 < n_oct:
-            yo, yo_lo = decimate(yo, yo_lo, h)
+            yo, yo_lo = M.decimate(yo, yo_lo, h0, hodd)
     return out
 
 
