@@ -2631,7 +2631,59 @@ struct Fwd {
                               (12 * ((T2 + 15) / 16) + 15) / 16 <= kHead1MT;
         const bool genre_bf = head1_bf && c.genre && n->head_genre.size() == 2 && n->head_genre[0].bf_off >= 0 && n->head_genre[1].bf_off >= 0 &&
                               n->head_genre[0].kh == 1 && n->head_genre[1].kh == 2;
-        if (head1_bf) {
+        // ... and when the stack above ran as one launch (inference at the shapes pc2pc_fuses admits) both convolutions of a head run
+        // as ONE launch too (heads_fused_kernel): the 32 hidden channels stay in LDS.  ake_debug_keep_taps(1), training, other head
+        // depths and shapes whose patches do not fit keep the two launches below.
+        constexpr bool kHeadsGenreOwnLaunch = false;
+        const int TpB = 16 * ((T2 + 15) / 16 - 1) + 22;
+        const size_t hf_lds = std::max({(static_cast<size_t>(2) * 12 * (T1 + 8) * 2 + 2 * 4 * 2 * 2 * 64) * sizeof(uint4),      // phase A: patch + weight ring
+                                        static_cast<size_t>(2) * 12 * TpB * 4 * sizeof(uint4),                                  // phase B: patch,
+                                        static_cast<size_t>(8) * kHead1MT * 4 * 64 * sizeof(float)}) +                          // then the partial tiles
+                              static_cast<size_t>(12) * T2 * sizeof(float);                                                     // the finished map
+        const bool heads_fused = head1_bf && pc_fused && !g_keep_taps && c.local == 0 && n->head_key[0].cout == 32 && n->head_tonic[0].cout == 32 &&
+                                 n->head_key[0].kh == 12 && n->head_tonic[0].kh == 12 && n->head_key[1].kh == 12 && n->head_tonic[1].kh == 12 &&
+                                 (!genre_bf || n->head_genre[0].cout == 32) && (12 * T1 + 15) / 16 <= 32 && hf_lds <= 150 * 1024;
+        if (heads_fused) {
+            HeadsFusedArgs ha;
+            std::memset(&ha, 0, sizeof(ha));
+            float* maps[3] = {b.map_k, b.map_t, b.map_g};
+            float* outs[3] = {key_out, tonic_out, genre_out};
+            const std::vector<PackedConv>* hc[3] = {&n->head_key, &n->head_tonic, &n->head_genre};
+            ha.xh = feat_cl; ha.xl = feat_cl + static_cast<long long>(B) * 12 * Tf * 16;
+            for (int h = 0; h < (genre_bf ? 3 : 2); ++h) {
+                const PackedConv& p0 = (*hc[h])[0];
+                const PackedConv& p1 = (*hc[h])[1];
+                ha.bfragA[h] = n->bf_frags_dev + p0.bf_off; ha.biasA[h] = n->blob_dev + p0.b_off; ha.KHA[h] = p0.kh;
+                ha.bfragB[h] = n->bf_frags_dev + p1.bf_off; ha.biasB[h] = n->blob_dev + p1.b_off; ha.KHB[h] = p1.kh;
+                ha.dst[h] = maps[h];
+                ha.pout[h] = outs[h];
+            }
+            ha.batch = B; ha.T_in = Tf; ha.T1 = T1; ha.T2 = T2; ha.TpA = T1 + 8; ha.TpB = TpB; ha.JB = (T2 + 15) / 16;
+            ha.fin_off = static_cast<int>(hf_lds / sizeof(float)) - 12 * T2;
+            ha.seq = reinterpret_cast<const long long*>(seq);
+            ha.n_pool_layers = L - 1; ha.tp = tp; ha.shrink = (c.kernel_size - 1) * c.head_layers; ha.max_pool = c.max_pool; ha.clip0 = 0;
+            static ake::DeviceOnce hf_attr;
+            if (hf_attr.need()) {
+                AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(heads_fused_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+                AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(heads_fused_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+                hf_attr.mark();
+            }
+            // phase A's M-tiles over the 8 waves: three each where 24 cover the hidden map (12 x 32 positions and fewer), else four
+            const bool mt3 = (12 * T1 + 15) / 16 <= 24;
+            auto launch = [&](int h0, int h1, int h2, int nseg, const char* name) {
+                ha.hs[0] = h0; ha.hs[1] = h1; ha.hs[2] = h2;
+                ake::ProfScope ps(name, s);
+                if (mt3) hipLaunchKernelGGL(heads_fused_kernel<3>, dim3(nseg * B), dim3(512), hf_lds, s, ha);
+                else hipLaunchKernelGGL(heads_fused_kernel<4>, dim3(nseg * B), dim3(512), hf_lds, s, ha);
+            };
+            if (!genre_bf) launch(0, 1, 1, 2, "heads_fused_kernel");
+            else if (kHeadsGenreOwnLaunch) {
+                launch(0, 1, 1, 2, "heads_fused_kernel");
+                launch(2, 2, 2, 1, "heads_fused_kernel/genre");
+            } else launch(2, 0, 1, 3, "heads_fused_kernel");     // the short genre workgroups first: they hand their slots on early
+            pooled_heads = genre_bf ? 3 : 2;
+            Tm = T2;
+        } else if (head1_bf) {
             Head1BfArgs ha;
             std::memset(&ha, 0, sizeof(ha));
             float* maps[3] = {b.map_k, b.map_t, b.map_g};

@@ -1998,6 +1998,287 @@ __global__ __launch_bounds__(512) void conv_head1_bf16_kernel(Head1BfArgs a) {
     }
 }
 
+// ==========================================================================================
+// Both convolutions of a two-conv head (16 -> 32 channels, then 32 -> one map) + the masked pooling in ONE launch: one workgroup of
+// 8 waves per (clip, head).  Phase A is conv_pc_bf16_kernel<2, true> over the whole clip (the same k-steps and products in the same
+// order per tile), phase B is conv_head1_bf16_kernel from its first barrier on.  Between them the 32 hidden channels do not leave
+// the LDS: phase A's epilogue writes its split-bf16 values straight into phase B's patch [12][TpB][4 groups of 8 channels], which
+// overlays phase A's own patch and weight ring (dead by then).  Values are bit for bit those of the two launches.
+// ==========================================================================================
+struct HeadsFusedArgs {
+    const unsigned short* xh;     // pooled features, channels-last planes [clip][12][T_in][16]
+    const unsigned short* xl;
+    const uint4* bfragA[3];       // per head (key, tonic, genre): first conv, [KHA * 4 k-steps][2 N-tiles][hi|lo][64 lanes]
+    const float* biasA[3];        // [32]
+    const uint4* bfragB[3];       // second conv, [KHB * 22 k-steps][hi|lo][64 lanes]
+    const float* biasB[3];
+    float* dst[3];                // finished maps [clip][H_out][T2]
+    float* pout[3];               // masked temporal mean (+ sigmoid) of each finished map [clip][H_out]
+    int KHA[3], KHB[3];           // kernel rows: 12 = circular over the pitch classes (key / tonic); genre 1 then 2, valid
+    int hs[3];                    // head of the workgroups [i * batch, (i + 1) * batch) of the grid
+    int batch;
+    int T_in, T1, T2;             // frames: features, hidden map (T_in - 6), finished map (T1 - 6)
+    int TpA, TpB, JB;             // patch widths of the two phases (T1 + 8; 16 (JB - 1) + 22), 16-frame blocks of the finished map
+    const long long* seq;
+    int n_pool_layers, tp, shrink, max_pool, clip0;
+    int fin_off;                  // float offset of the finished map's LDS copy [H_out][T2] (behind everything else)
+};
+
+// MT M-tiles per wave in phase A: 8 x MT x 16 >= 12 * T1 positions (which tiles a wave owns changes no value)
+template <int MT>
+__global__ __launch_bounds__(512, 4) void heads_fused_kernel(HeadsFusedArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint4 lds4[];
+    // (members of the argument arrays are picked with selects: a run-time index sends the whole struct through scratch)
+#define AKE_HSEL(f) (head == 0 ? a.f[0] : head == 1 ? a.f[1] : a.f[2])
+    const int bid = __builtin_amdgcn_readfirstlane(blockIdx.x);
+    const int seg = (bid >= a.batch ? 1 : 0) + (bid >= 2 * a.batch ? 1 : 0);
+    const int clip = bid - seg * a.batch;
+    const int head = seg == 0 ? a.hs[0] : seg == 1 ? a.hs[1] : a.hs[2];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int r16 = lane & 15, q = lane >> 4;
+    typedef float f32x4c __attribute__((ext_vector_type(4)));
+    constexpr int NT = 2;
+    const int TpB = a.TpB;
+    uint4* const pHB = lds4;                                 // phase B's patch [12][TpB][4 groups of 8 channels]
+    uint4* const pLB = lds4 + 12 * TpB * 4;
+    const uint4* __restrict__ bg = AKE_HSEL(bfragB) + lane;
+    const int KHB = AKE_HSEL(KHB);
+    const int nks = KHB * 22;
+    constexpr int PF = 3;
+    uint4 nbh[PF], nbl[PF];
+    {   // ---- phase A: conv_pc_bf16_kernel<2, true>, valid in time, the whole clip in this workgroup ----
+        const int Tp = a.TpA;
+        const int KH = AKE_HSEL(KHA);
+        const int Mtot = 12 * a.T1;                          // (12 output rows in both forms: 12 circular kernel rows, or one)
+        uint4* const pH = lds4;                              // [12][Tp][2 halves of 8 channels]
+        uint4* const pL = lds4 + 12 * Tp * 2;
+        uint4* const wring = lds4 + 2 * 12 * Tp * 2;         // one kernel row of weight fragments, double-buffered (conv_pc_bf16_kernel)
+        constexpr int kRow = 4 * NT * 2 * 64;
+        const uint4* const bfr = AKE_HSEL(bfragA);
+        auto fetch_row = [&](int dyn) {
+            for (int pc = wave; pc < kRow / 64; pc += 8) {
+                const uint4* src = bfr + dyn * kRow + pc * 64 + lane;
+                const unsigned int lds_dst = static_cast<unsigned int>(reinterpret_cast<unsigned long long>(wring + (dyn & 1) * kRow + pc * 64));
+                unsigned int keep;
+                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                             : "=&s"(keep) : "v"(src), "s"(lds_dst) : "memory");
+            }
+        };
+        fetch_row(0);
+        {
+            const long long cbase = static_cast<long long>(clip) * 12 * a.T_in * 2;
+            const uint4* gh = reinterpret_cast<const uint4*>(a.xh) + cbase;
+            const uint4* gl = reinterpret_cast<const uint4*>(a.xl) + cbase;
+            const int n16 = 12 * Tp * 2;
+            for (int i = threadIdx.x; i < n16; i += 512) {
+                const int half = i & 1, pos = i >> 1;
+                const int row = pos / Tp, f = pos - row * Tp;
+                uint4 vh = make_uint4(0, 0, 0, 0), vl = make_uint4(0, 0, 0, 0);
+                if (f < a.T_in) {
+                    const long long g = (static_cast<long long>(row) * a.T_in + f) * 2 + half;
+                    vh = gh[g]; vl = gl[g];
+                }
+                pH[i] = vh; pL[i] = vl;
+            }
+        }
+        __builtin_amdgcn_s_waitcnt(0x0F70);                   // vmcnt(0): this wave's share of row 0 has landed
+        __syncthreads();
+        const int tile0 = wave * MT;
+        const bool active = tile0 * 16 < Mtot;                // (idle waves still fetch and meet the barriers)
+        int ay[MT], at[MT];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            int m = (tile0 + mt) * 16 + r16;
+            if (m >= Mtot) m = Mtot - 1;
+            ay[mt] = m / a.T1;
+            at[mt] = m - ay[mt] * a.T1;
+        }
+        f32x4c acc[MT][NT];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4c{0.f, 0.f, 0.f, 0.f};
+        const int dxq = q >> 1, half = q & 1;
+        const bool pair = !(KH & 1);
+        for (int dy = 0; dy < KH; ++dy) {
+            if (dy + 1 < KH) fetch_row(dy + 1);
+            const uint4* const wr = wring + (dy & 1) * kRow + lane;
+            if (active) {
+                int rowoff[MT], rowoff3[MT];
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) {
+                    int row = ay[mt] + dy;
+                    row -= row >= 12 ? 12 : 0;
+                    rowoff[mt] = ((row * Tp + at[mt] + dxq) << 1) + half;
+                    int row3 = ay[mt] + dy + dxq;             // the paired seventh taps of kernel rows dy, dy + 1 (conv_pc_bf16_kernel)
+                    row3 -= row3 >= 12 ? 12 : 0;
+                    rowoff3[mt] = pair ? ((row3 * Tp + at[mt] + 6) << 1) + half : rowoff[mt] + 12;
+                }
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    if (p == 3 && pair && (dy & 1)) break;
+                    uint4 bhu[NT], blu[NT], ahu[MT], alu[MT];
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) {
+                        bhu[nt] = wr[((p * NT + nt) * 2 + 0) * 64];
+                        blu[nt] = wr[((p * NT + nt) * 2 + 1) * 64];
+                    }
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt) {
+                        ahu[mt] = pH[p == 3 ? rowoff3[mt] : rowoff[mt] + 4 * p];
+                        alu[mt] = pL[p == 3 ? rowoff3[mt] : rowoff[mt] + 4 * p];
+                    }
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) {
+                        const bf16x8c bh = __builtin_bit_cast(bf16x8c, bhu[nt]), bl = __builtin_bit_cast(bf16x8c, blu[nt]);
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8c, ahu[mt]), bh, acc[mt][nt], 0, 0, 0);
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8c, alu[mt]), bh, acc[mt][nt], 0, 0, 0);
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8c, ahu[mt]), bl, acc[mt][nt], 0, 0, 0);
+                    }
+                }
+            }
+            if (dy + 1 < KH) {
+                __builtin_amdgcn_s_waitcnt(0x0F70);           // this wave's share of the next row has landed ...
+                __syncthreads();                              // ... everybody's; and everybody is done with this row's half
+            }
+        }
+        // phase B's first weight fragments (from L2): their latency hides under the epilogue
+#pragma unroll
+        for (int i = 0; i < PF; ++i) {
+            const int kn = wave + 8 * i < nks ? wave + 8 * i : wave;
+            nbh[i] = bg[(2 * kn + 0) * 64]; nbl[i] = bg[(2 * kn + 1) * 64];
+        }
+        __syncthreads();                                      // every wave is done with phase A's patch and ring
+        // ---- hand-over: bias, LeakyReLU, hi / lo split (the OUT_CL epilogue of conv_pc_bf16_kernel) into phase B's patch; the
+        // frames f >= T1 of that patch are zeros ----
+        unsigned short* const sH = reinterpret_cast<unsigned short*>(pHB);
+        unsigned short* const sL = reinterpret_cast<unsigned short*>(pLB);
+        {
+            const int nz = TpB - a.T1, n16 = 12 * nz * 4;
+            for (int i = threadIdx.x; i < n16; i += 512) {
+                const int grp = i & 3, pos = i >> 2;
+                const int row = pos / nz, f = a.T1 + pos - row * nz;
+                pHB[((row * TpB + f) << 2) + grp] = make_uint4(0, 0, 0, 0);
+                pLB[((row * TpB + f) << 2) + grp] = make_uint4(0, 0, 0, 0);
+            }
+        }
+        if (active) {
+            const float* const bptr = AKE_HSEL(biasA);
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const int co = nt * 16 + r16;
+                const float bias = bptr[co];
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) {
+                    const int m0 = (tile0 + mt) * 16 + 4 * q;
+                    int y = m0 / a.T1, t = m0 - y * a.T1;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        if (m0 + i < Mtot) {
+                            float v = acc[mt][nt][i] + bias;
+                            v = v > 0.f ? v : v * kSlope;
+                            const int idx = (y * TpB + t) * 32 + co;
+                            const unsigned int hb = bf16_bits(v);
+                            sH[idx] = static_cast<unsigned short>(hb);
+                            sL[idx] = static_cast<unsigned short>(bf16_bits(v - __uint_as_float(hb << 16)));
+                        }
+                        if (++t == a.T1) { t = 0; ++y; }
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // ---- phase B: conv_head1_bf16_kernel ----
+    float* const red = reinterpret_cast<float*>(lds4);       // [8 waves][kHead1MT][4][64]: reuses the patch's bytes after the multiply loop
+    const int circ = KHB == 12 ? 1 : 0;
+    const int HO = circ ? 12 : 12 - KHB + 1;
+    const int Mtot = HO * a.JB;
+    const int mtiles = (Mtot + 15) / 16;
+    int ay[kHead1MT], af[kHead1MT];
+#pragma unroll
+    for (int mt = 0; mt < kHead1MT; ++mt) {
+        int m = mt * 16 + r16;
+        if (m >= Mtot) m = Mtot - 1;
+        const int jb = m / HO;
+        ay[mt] = m - jb * HO;
+        af[mt] = 16 * jb;
+    }
+    f32x4c acc[kHead1MT];
+#pragma unroll
+    for (int mt = 0; mt < kHead1MT; ++mt) acc[mt] = f32x4c{0.f, 0.f, 0.f, 0.f};
+    for (int ks = wave; ks < nks; ks += 8) {
+        const int dy = ks / 22, dxe = ks - dy * 22;
+        const bf16x8c bh = __builtin_bit_cast(bf16x8c, nbh[0]);
+        const bf16x8c bl = __builtin_bit_cast(bf16x8c, nbl[0]);
+#pragma unroll
+        for (int i = 0; i + 1 < PF; ++i) { nbh[i] = nbh[i + 1]; nbl[i] = nbl[i + 1]; }
+        {
+            const int kn = ks + 8 * PF < nks ? ks + 8 * PF : ks;
+            nbh[PF - 1] = bg[(2 * kn + 0) * 64]; nbl[PF - 1] = bg[(2 * kn + 1) * 64];
+        }
+#pragma unroll
+        for (int mt = 0; mt < kHead1MT; ++mt) {
+            if (mt < mtiles) {
+                int row = ay[mt] + dy;
+                row -= (circ && row >= 12) ? 12 : 0;
+                const int ad = ((row * TpB + af[mt] + dxe) << 2) + q;
+                const bf16x8c ah = __builtin_bit_cast(bf16x8c, pHB[ad]);
+                const bf16x8c al = __builtin_bit_cast(bf16x8c, pLB[ad]);
+                acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc[mt], 0, 0, 0);
+                acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, acc[mt], 0, 0, 0);
+                acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, acc[mt], 0, 0, 0);
+            }
+        }
+    }
+    __syncthreads();                                         // every wave is done with the patch
+#pragma unroll
+    for (int mt = 0; mt < kHead1MT; ++mt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) red[((wave * kHead1MT + mt) * 4 + i) * 64 + lane] = acc[mt][i];
+    __syncthreads();
+    // wave w finishes M-tile w: D[row m = 4q + i][col tau]
+    if (wave < mtiles) {
+        const float bias = AKE_HSEL(biasB)[0];
+        float* const dst = AKE_HSEL(dst);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float v = bias;
+#pragma unroll
+            for (int w = 0; w < 8; ++w) v += red[((w * kHead1MT + wave) * 4 + i) * 64 + lane];
+            const int m = wave * 16 + 4 * q + i;
+            const int jb = m / HO, y = m - jb * HO;
+            const int t = 16 * jb + r16;
+            if (m < Mtot && t < a.T2) {
+                dst[(static_cast<long long>(clip) * HO + y) * a.T2 + t] = v;
+                reinterpret_cast<float*>(lds4)[a.fin_off + y * a.T2 + t] = v;
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < HO) {                                   // one lane per output row, as head_pool_kernel
+        bool use_max = a.max_pool != 0;
+        const int L = pool_frames(a.seq, clip, a.T2, a.n_pool_layers, a.tp, a.shrink, a.clip0, &use_max);
+        const float* m = reinterpret_cast<const float*>(lds4) + a.fin_off + threadIdx.x * a.T2;
+        float v;
+        if (use_max) {
+            v = -INFINITY;
+            for (int t = 0; t < L; ++t) v = fmaxf(v, m[t]);
+        } else {
+            float sum = 0.f;
+            for (int t = 0; t < L; ++t) sum += m[t];
+            v = sum / static_cast<float>(L > 0 ? L : 0);              // empty slice -> NaN, as torch.mean
+        }
+        if (head == 0) v = 1.f / (1.f + expf(-v));                    // self.sig(key_out), models.py:802
+        AKE_HSEL(pout)[clip * HO + threadIdx.x] = v;
+    }
+#undef AKE_HSEL
+}
+
 // weight fragments of conv_head1_bf16_kernel from the VALU-layout eval pack [ci][12][7] (cout == 1): one thread per (k-step, lane)
 __global__ void pack_head1_bf16_kernel(const float* __restrict__ w, uint4* __restrict__ out, int cin, int KH) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
