@@ -55,6 +55,16 @@ struct DeviceOnce {
     void mark() { done.fetch_or(1ull << dev(), std::memory_order_release); }
 };
 
+// LDS-DMA: every lane's 16 bytes at `src` go straight to the LDS, lane i's to byte address lds_dst + 16 i (wave-uniform; of an LDS
+// pointer the low 32 bits are the LDS byte address), without passing through registers.  Nothing waits here: the caller places
+// vmcnt(0) and its barrier.  Inline asm because hipcc orders every later LDS access behind a builtin LDS-DMA with vmcnt(0) (it cannot
+// tell the halves of a double buffer apart), which would serialise load and multiply.  m0 is saved and restored around the request.
+__device__ __forceinline__ void lds_dma_16(const uint4* src, unsigned int lds_dst) {
+    unsigned int keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(src), "s"(lds_dst) : "memory");
+}
+
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // Bump allocator over the caller's workspace.

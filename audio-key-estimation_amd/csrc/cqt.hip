@@ -575,11 +575,7 @@ __device__ __forceinline__ void bank2_stage(const uint4* w, int b0, int nbc, uin
     for (int u = 0; u < kU; ++u) {
         const int i0 = wave * 64 + kBankThreads * u;
         if (i0 < total) {
-            const uint4* sp = src + i0 + lane;
-            const unsigned int lds_dst = static_cast<unsigned int>(reinterpret_cast<unsigned long long>(ldsW + i0));   // LDS aperture: low 32 bits = byte address
-            unsigned int keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(sp), "s"(lds_dst) : "memory");
+            ake::lds_dma_16(src + i0 + lane, static_cast<unsigned int>(reinterpret_cast<unsigned long long>(ldsW + i0)));
         }
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);                              // vmcnt(0): this wave's pieces (and its A fragments) have landed
@@ -636,11 +632,7 @@ __global__ __launch_bounds__(kBankThreads) void cqt_bank_bf16_kernel(
             for (int u = 0; u < kU; ++u) {
                 const int i0 = wave * 64 + kBankThreads * u;
                 if (i0 < total) {
-                    const uint4* sp = src + i0 + lane;
-                    const unsigned int lds_dst = static_cast<unsigned int>(reinterpret_cast<unsigned long long>(ldsW + i0));   // LDS aperture: low 32 bits = byte address
-                    unsigned int keep;
-                    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                                 : "=&s"(keep) : "v"(sp), "s"(lds_dst) : "memory");
+                    ake::lds_dma_16(src + i0 + lane, static_cast<unsigned int>(reinterpret_cast<unsigned long long>(ldsW + i0)));
                 }
             }
             __builtin_amdgcn_s_waitcnt(0x0F70);                              // vmcnt(0): this wave's pieces (and its A fragments) have landed

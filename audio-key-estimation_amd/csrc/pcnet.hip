@@ -2035,9 +2035,25 @@ struct Fwd {
         return AKE_OK;
     }
 
+    // one launch of semi_conv_stats_kernel over [B][pc.cin][P][ta.s.T]: thread = (semitone row, strip of frames), CO channels per thread
+    int launch_semi_conv(const PackedConv& pc, const SemiTrainArgs& ta, int P, int B) {
+        const int per_clip = (P / 3) * ta.s.n_strips;
+        const int threads = per_clip >= 256 ? 256 : (per_clip + 63) / 64 * 64;
+        dim3 grid((per_clip + threads - 1) / threads, pc.groups, B), block(threads);
+        ake::ProfScope ps("semi_conv_stats_kernel", s);
+        switch (pc.co) {
+            case 8: hipLaunchKernelGGL((semi_conv_stats_kernel<8>), grid, block, 0, s, ta); break;
+            case 4: hipLaunchKernelGGL((semi_conv_stats_kernel<4>), grid, block, 0, s, ta); break;
+            case 1: hipLaunchKernelGGL((semi_conv_stats_kernel<1>), grid, block, 0, s, ta); break;
+            default: ake::set_error("semi: bad CO"); return AKE_ERR_UNSUPPORTED;
+        }
+        return AKE_OK;
+    }
+
     // pool_semi (+BN+LReLU) + octave fold of `src` [B][C][P][T] into channels [coff, coff+C) of dst [B][ctot][12][T]
     int semi(int layer, const float* src, const float* in_aff, int B, int P, int Tn, float* dst, int ctot, int coff, float* aff_cat_rows) {
         const char* nm = layer == 0 ? "semi_fold_kernel/L0" : "semi_fold_kernel/L1+";
+        int rc;
         if (!train && n->cfg.p2pc_conv) {   // semitone conv (raw, BatchNorm folded) -> octave-fold convolution (LeakyReLU applied on load)
             const PackedConv& pc = n->semi[layer];
             SemiTrainArgs ta;
@@ -2047,18 +2063,7 @@ struct Fwd {
             a.src_clip_stride = static_cast<long long>(pc.cin) * P * Tn;
             a.w = n->blob_dev + pc.w_off; a.bias = n->blob_dev + pc.b_off;
             a.dst = b.smap; a.n_strips = (Tn + TW - 1) / TW;
-            const int per_clip = (P / 3) * a.n_strips;
-            const int threads = per_clip >= 256 ? 256 : (per_clip + 63) / 64 * 64;
-            dim3 grid((per_clip + threads - 1) / threads, pc.groups, B), block(threads);
-            {
-                ake::ProfScope ps("semi_conv_stats_kernel", s);
-                switch (pc.co) {
-                    case 8: hipLaunchKernelGGL((semi_conv_stats_kernel<8>), grid, block, 0, s, ta); break;
-                    case 4: hipLaunchKernelGGL((semi_conv_stats_kernel<4>), grid, block, 0, s, ta); break;
-                    case 1: hipLaunchKernelGGL((semi_conv_stats_kernel<1>), grid, block, 0, s, ta); break;
-                    default: ake::set_error("semi: bad CO"); return AKE_ERR_UNSUPPORTED;
-                }
-            }
+            if ((rc = launch_semi_conv(pc, ta, P, B))) return rc;
             const PackedConv& fc = n->foldc[layer];
             const long long total = static_cast<long long>(B) * pc.cin * 12 * Tn;
             ake::ProfScope ps("fold_conv_kernel", s);
@@ -2078,18 +2083,7 @@ struct Fwd {
         a.dst = b.semi_raw[layer]; a.dst_coff = 0; a.dst_clip_stride = 0;
         a.n_strips = (Tn + TW - 1) / TW;
         ta.in_affine = in_aff; ta.stats = b.stats + 2 * n->bns[bn].ch_off; ta.stats_stride = 2 * n->bn_channels;
-        const int per_clip = (P / 3) * a.n_strips;            // thread = (semitone row, strip of frames)
-        const int threads = per_clip >= 256 ? 256 : (per_clip + 63) / 64 * 64;
-        dim3 grid((per_clip + threads - 1) / threads, pc.groups, B), block(threads);
-        {
-            ake::ProfScope ps("semi_conv_stats_kernel", s);
-            switch (pc.co) {
-                case 8: hipLaunchKernelGGL((semi_conv_stats_kernel<8>), grid, block, 0, s, ta); break;
-                case 4: hipLaunchKernelGGL((semi_conv_stats_kernel<4>), grid, block, 0, s, ta); break;
-                case 1: hipLaunchKernelGGL((semi_conv_stats_kernel<1>), grid, block, 0, s, ta); break;
-                default: ake::set_error("semi: bad CO"); return AKE_ERR_UNSUPPORTED;
-            }
-        }
+        if ((rc = launch_semi_conv(pc, ta, P, B))) return rc;
         finalize_bn(bn, static_cast<double>(B) * (P / 3) * Tn, b.aff_semi[layer]);
         const long long total = static_cast<long long>(B) * pc.cin * 12 * Tn;
         if (n->cfg.p2pc_conv) {   // models.py:108-133: the fold is a learned convolution over the octaves + BatchNorm (batch statistics) + LeakyReLU
@@ -2158,17 +2152,7 @@ struct Fwd {
         a.w = n->blob_dev + pc.w_off; a.bias = n->blob_dev + pc.b_off;
         a.dst = dst; a.n_strips = (Tn + TW - 1) / TW;
         ta.out_lrelu = raw ? 0 : 1;
-        const int per_clip = (P / 3) * a.n_strips;
-        const int threads = per_clip >= 256 ? 256 : (per_clip + 63) / 64 * 64;
-        dim3 grid((per_clip + threads - 1) / threads, pc.groups, B), block(threads);
-        ake::ProfScope ps("semi_conv_stats_kernel", s);
-        switch (pc.co) {
-            case 8: hipLaunchKernelGGL((semi_conv_stats_kernel<8>), grid, block, 0, s, ta); break;
-            case 4: hipLaunchKernelGGL((semi_conv_stats_kernel<4>), grid, block, 0, s, ta); break;
-            case 1: hipLaunchKernelGGL((semi_conv_stats_kernel<1>), grid, block, 0, s, ta); break;
-            default: ake::set_error("semi: bad CO"); return AKE_ERR_UNSUPPORTED;
-        }
-        return AKE_OK;
+        return launch_semi_conv(pc, ta, P, B);
     }
 
     // the octave fold of ready maps [B][C][S][T] into channels [coff, coff + C) of dst: max (models.py:95-106) or --p2pc_conv's convolution
@@ -2634,7 +2618,6 @@ struct Fwd {
         // ... and when the stack above ran as one launch (inference at the shapes pc2pc_fuses admits) both convolutions of a head run
         // as ONE launch too (heads_fused_kernel): the 32 hidden channels stay in LDS.  ake_debug_keep_taps(1), training, other head
         // depths and shapes whose patches do not fit keep the two launches below.
-        constexpr bool kHeadsGenreOwnLaunch = false;
         const int TpB = 16 * ((T2 + 15) / 16 - 1) + 22;
         const size_t hf_lds = std::max({(static_cast<size_t>(2) * 12 * (T1 + 8) * 2 + 2 * 4 * 2 * 2 * 64) * sizeof(uint4),      // phase A: patch + weight ring
                                         static_cast<size_t>(2) * 12 * TpB * 4 * sizeof(uint4),                                  // phase B: patch,
@@ -2643,25 +2626,32 @@ struct Fwd {
         const bool heads_fused = head1_bf && pc_fused && !g_keep_taps && c.local == 0 && n->head_key[0].cout == 32 && n->head_tonic[0].cout == 32 &&
                                  n->head_key[0].kh == 12 && n->head_tonic[0].kh == 12 && n->head_key[1].kh == 12 && n->head_tonic[1].kh == 12 &&
                                  (!genre_bf || n->head_genre[0].cout == 32) && (12 * T1 + 15) / 16 <= 32 && hf_lds <= 150 * 1024;
+        // per-head tables of the two bf16 paths (key, tonic, genre), and the pooling of a finished map
+        const int nh_bf = genre_bf ? 3 : 2;
+        float* const maps[3] = {b.map_k, b.map_t, b.map_g};
+        float* const outs[3] = {key_out, tonic_out, genre_out};
+        const std::vector<PackedConv>* const hconv[3] = {&n->head_key, &n->head_tonic, &n->head_genre};
+        PoolArgs pool;
+        pool.seq = reinterpret_cast<const long long*>(seq);
+        pool.n_pool_layers = L - 1; pool.tp = tp; pool.shrink = (c.kernel_size - 1) * c.head_layers; pool.max_pool = c.max_pool; pool.clip0 = 0;
         if (heads_fused) {
             HeadsFusedArgs ha;
             std::memset(&ha, 0, sizeof(ha));
-            float* maps[3] = {b.map_k, b.map_t, b.map_g};
-            float* outs[3] = {key_out, tonic_out, genre_out};
-            const std::vector<PackedConv>* hc[3] = {&n->head_key, &n->head_tonic, &n->head_genre};
             ha.xh = feat_cl; ha.xl = feat_cl + static_cast<long long>(B) * 12 * Tf * 16;
-            for (int h = 0; h < (genre_bf ? 3 : 2); ++h) {
-                const PackedConv& p0 = (*hc[h])[0];
-                const PackedConv& p1 = (*hc[h])[1];
+            for (int h = 0; h < nh_bf; ++h) {
+                const PackedConv& p0 = (*hconv[h])[0];
+                const PackedConv& p1 = (*hconv[h])[1];
                 ha.bfragA[h] = n->bf_frags_dev + p0.bf_off; ha.biasA[h] = n->blob_dev + p0.b_off; ha.KHA[h] = p0.kh;
                 ha.bfragB[h] = n->bf_frags_dev + p1.bf_off; ha.biasB[h] = n->blob_dev + p1.b_off; ha.KHB[h] = p1.kh;
                 ha.dst[h] = maps[h];
                 ha.pout[h] = outs[h];
             }
+            // workgroups [i * B, (i + 1) * B) run head hs[i]; with a genre head its short workgroups come first: they hand their slots on early
+            if (genre_bf) { ha.hs[0] = 2; ha.hs[1] = 0; ha.hs[2] = 1; }
+            else { ha.hs[0] = 0; ha.hs[1] = 1; ha.hs[2] = 1; }
             ha.batch = B; ha.T_in = Tf; ha.T1 = T1; ha.T2 = T2; ha.TpA = T1 + 8; ha.TpB = TpB; ha.JB = (T2 + 15) / 16;
             ha.fin_off = static_cast<int>(hf_lds / sizeof(float)) - 12 * T2;
-            ha.seq = reinterpret_cast<const long long*>(seq);
-            ha.n_pool_layers = L - 1; ha.tp = tp; ha.shrink = (c.kernel_size - 1) * c.head_layers; ha.max_pool = c.max_pool; ha.clip0 = 0;
+            ha.pool = pool;
             static ake::DeviceOnce hf_attr;
             if (hf_attr.need()) {
                 AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(heads_fused_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
@@ -2670,50 +2660,38 @@ struct Fwd {
             }
             // phase A's M-tiles over the 8 waves: three each where 24 cover the hidden map (12 x 32 positions and fewer), else four
             const bool mt3 = (12 * T1 + 15) / 16 <= 24;
-            auto launch = [&](int h0, int h1, int h2, int nseg, const char* name) {
-                ha.hs[0] = h0; ha.hs[1] = h1; ha.hs[2] = h2;
-                ake::ProfScope ps(name, s);
-                if (mt3) hipLaunchKernelGGL(heads_fused_kernel<3>, dim3(nseg * B), dim3(512), hf_lds, s, ha);
-                else hipLaunchKernelGGL(heads_fused_kernel<4>, dim3(nseg * B), dim3(512), hf_lds, s, ha);
-            };
-            if (!genre_bf) launch(0, 1, 1, 2, "heads_fused_kernel");
-            else if (kHeadsGenreOwnLaunch) {
-                launch(0, 1, 1, 2, "heads_fused_kernel");
-                launch(2, 2, 2, 1, "heads_fused_kernel/genre");
-            } else launch(2, 0, 1, 3, "heads_fused_kernel");     // the short genre workgroups first: they hand their slots on early
-            pooled_heads = genre_bf ? 3 : 2;
+            ake::ProfScope ps("heads_fused_kernel", s);
+            if (mt3) hipLaunchKernelGGL(heads_fused_kernel<3>, dim3(nh_bf * B), dim3(512), hf_lds, s, ha);
+            else hipLaunchKernelGGL(heads_fused_kernel<4>, dim3(nh_bf * B), dim3(512), hf_lds, s, ha);
+            pooled_heads = nh_bf;
             Tm = T2;
         } else if (head1_bf) {
             Head1BfArgs ha;
             std::memset(&ha, 0, sizeof(ha));
-            float* maps[3] = {b.map_k, b.map_t, b.map_g};
             float* hids[3] = {b.hid_k, b.hid_t, b.hid_g};
-            const PackedConv* c0[3] = {&n->head_key[0], &n->head_tonic[0], genre_bf ? &n->head_genre[0] : nullptr};
-            const PackedConv* c1[3] = {&n->head_key[1], &n->head_tonic[1], genre_bf ? &n->head_genre[1] : nullptr};
-            const int nh = genre_bf ? 3 : 2;
-            for (int h = 0; h < nh; ++h) {
+            for (int h = 0; h < nh_bf; ++h) {
+                const PackedConv& p0 = (*hconv[h])[0];
+                const PackedConv& p1 = (*hconv[h])[1];
                 unsigned short* planes = reinterpret_cast<unsigned short*>(hids[h]);
                 // the key and the tonic head read the same features with the same geometry: one launch, blockIdx.y picks the head
-                if (h == 0 && (rc = run_pc_bf16(n, *c0[0], feat_cl, B, Tf, false, true, nullptr, planes, s, "conv_pc_bf16_kernel/head", c0[1],
+                if (h == 0 && (rc = run_pc_bf16(n, p0, feat_cl, B, Tf, false, true, nullptr, planes, s, "conv_pc_bf16_kernel/head", &(*hconv[1])[0],
                                                 reinterpret_cast<unsigned short*>(hids[1]))))
                     return rc;
-                if (h == 2 && (rc = run_pc_bf16(n, *c0[h], feat_cl, B, Tf, false, true, nullptr, planes, s, "conv_pc_bf16_kernel/genre_head")))
+                if (h == 2 && (rc = run_pc_bf16(n, p0, feat_cl, B, Tf, false, true, nullptr, planes, s, "conv_pc_bf16_kernel/genre_head")))
                     return rc;
                 ha.xh[h] = planes; ha.xl[h] = planes + static_cast<long long>(B) * 12 * T1 * 32;
-                ha.bfrag[h] = n->bf_frags_dev + c1[h]->bf_off; ha.bias[h] = n->blob_dev + c1[h]->b_off; ha.dst[h] = maps[h];
-                ha.KH[h] = c1[h]->kh; ha.circular[h] = c1[h]->kh == 12 ? 1 : 0; ha.H_out[h] = ha.circular[h] ? 12 : 12 - c1[h]->kh + 1;
+                ha.bfrag[h] = n->bf_frags_dev + p1.bf_off; ha.bias[h] = n->blob_dev + p1.b_off; ha.dst[h] = maps[h];
+                ha.KH[h] = p1.kh; ha.circular[h] = p1.kh == 12 ? 1 : 0; ha.H_out[h] = ha.circular[h] ? 12 : 12 - p1.kh + 1;
             }
-            ha.T_in = T1; ha.T_out = T2; ha.JB = (T2 + 15) / 16; ha.Tp = 16 * (ha.JB - 1) + 22;
+            ha.T_in = T1; ha.T_out = T2; ha.JB = (T2 + 15) / 16; ha.Tp = TpB;
             // the patch, and after the multiply loop the partial tiles of the 8 waves in the same bytes (two workgroups per CU fit)
             size_t lds = std::max(static_cast<size_t>(2) * 12 * ha.Tp * 4 * sizeof(uint4), static_cast<size_t>(8) * kHead1MT * 4 * 64 * sizeof(float));
             if (c.local == 0) {   // the masked mean + sigmoid of each finished map in the same launch (its LDS copy sits behind the patch / partial tiles)
                 ha.fin_off = static_cast<int>(lds / sizeof(float));
                 lds += static_cast<size_t>(12) * T2 * sizeof(float);
-                float* outs[3] = {key_out, tonic_out, genre_out};
-                for (int h = 0; h < nh; ++h) ha.pout[h] = outs[h];
-                ha.seq = reinterpret_cast<const long long*>(seq);
-                ha.n_pool_layers = L - 1; ha.tp = tp; ha.shrink = (c.kernel_size - 1) * c.head_layers; ha.max_pool = c.max_pool; ha.clip0 = 0;
-                pooled_heads = nh;
+                for (int h = 0; h < nh_bf; ++h) ha.pout[h] = outs[h];
+                ha.pool = pool;
+                pooled_heads = nh_bf;
             }
             static ake::DeviceOnce h1_attr;
             if (h1_attr.need()) {
@@ -2722,10 +2700,10 @@ struct Fwd {
             }
             AKE_REQUIRE(lds <= 150 * 1024, AKE_ERR_UNSUPPORTED, "heads: %d frames do not fit conv_head1_bf16_kernel", T1);
             ake::ProfScope ps("conv_head1_bf16_kernel", s);
-            hipLaunchKernelGGL(conv_head1_bf16_kernel, dim3(B, nh), dim3(512), lds, s, ha);
+            hipLaunchKernelGGL(conv_head1_bf16_kernel, dim3(B, nh_bf), dim3(512), lds, s, ha);
             Tm = T2;
         }
-        for (int h = head1_bf ? (genre_bf ? 3 : 2) : 0; h < (c.genre ? 3 : 2); ++h) {
+        for (int h = head1_bf ? nh_bf : 0; h < (c.genre ? 3 : 2); ++h) {
             const float* src = feat;
             const float* src_aff = feat_aff;
             int hc = n->final_ch, Tcur = Tf;
@@ -2801,9 +2779,7 @@ struct Fwd {
         if (!pa.maps[0] && !pa.maps[1] && !pa.maps[2]) return AKE_OK;
         pa.outs[0] = key_out; pa.outs[1] = tonic_out; pa.outs[2] = genre_out;
         pa.rows[0] = 12; pa.rows[1] = 12; pa.rows[2] = 11;
-        pa.Tm = Tm; pa.seq = reinterpret_cast<const long long*>(seq);
-        pa.n_pool_layers = L - 1; pa.tp = tp; pa.shrink = (c.kernel_size - 1) * c.head_layers;
-        pa.max_pool = c.max_pool; pa.batch = B; pa.clip0 = 0;
+        pa.Tm = Tm; pa.batch = B; pa.pool = pool;
         {
             ake::ProfScope ps("head_pool_kernel", s);
             hipLaunchKernelGGL(head_pool_kernel, dim3((B * 12 + 63) / 64, 3), dim3(64), 0, s, pa);

@@ -21,6 +21,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "common.h"
+
 namespace ake_k {
 
 constexpr int TW = 4;              // frames per thread
@@ -253,44 +255,38 @@ __global__ void time_pool_kernel(const float* __restrict__ src, float* __restric
 // Masked temporal mean over the head maps + sigmoid on key (models.py:754-804).
 // maps: [B][rows][Tm]; one thread per (clip, row).
 // ------------------------------------------------------------------------------------------
-struct PoolHeadArgs {
-    const float* maps[3];     // key, tonic, genre (genre may be null)
-    float* outs[3];
-    int rows[3];              // 12, 12, 11
-    int Tm;                   // frames of the maps
+// what the pooling of a finished head map needs besides the map (Fwd::tail fills it once for every kernel that pools)
+struct PoolArgs {
     const long long* seq;     // [B] or null
     int n_pool_layers;        // num_layers - 1
     int tp;                   // time_pool_size
     int shrink;               // (kernel_size - 1) * head_layers
     int max_pool;
-    int batch;
     int clip0;                // global index of the first clip of this chunk (for the max_pool sample-0 quirk)
 };
 
-// frames pooled for `clip` (models.py:754-785) and whether the maximum is taken instead of the mean
-__device__ __forceinline__ int pool_frames(const long long* seq, int clip, int Tm, int n_pool_layers, int tp, int shrink, int clip0, bool* use_max) {
+struct PoolHeadArgs {
+    const float* maps[3];     // key, tonic, genre (genre may be null)
+    float* outs[3];
+    int rows[3];              // 12, 12, 11
+    int Tm;                   // frames of the maps
+    int batch;
+    PoolArgs pool;
+};
+
+// One row `m` of `clip`'s finished map of Tm frames (global memory or its LDS copy) -> the masked mean, or the maximum, over the frames
+// pooled for the clip (models.py:754-785); sigmoid on the key head (`head` == 0)
+__device__ __forceinline__ float pool_row(const PoolArgs& p, const float* m, int clip, int Tm, int head) {
     int L = Tm;
-    if (seq) {
-        long long l = seq[clip];
-        for (int k = 0; k < n_pool_layers; ++k) l = l / tp;          // floor (models.py:759)
-        L = static_cast<int>(l) - shrink;                             // models.py:760
+    bool use_max = p.max_pool != 0;
+    if (p.seq) {
+        long long l = p.seq[clip];
+        for (int k = 0; k < p.n_pool_layers; ++k) l = l / p.tp;      // floor (models.py:759)
+        L = static_cast<int>(l) - p.shrink;                           // models.py:760
         if (L > Tm) L = Tm;                                           // x[..., :L] clamps at the end ...
         if (L < 0) L = Tm + L > 0 ? Tm + L : 0;                       // ... and counts from the end when negative
-        *use_max = *use_max && (clip0 + clip == 0);                   // models.py:764-785 quirk
+        use_max = use_max && (p.clip0 + clip == 0);                   // models.py:764-785 quirk
     }
-    return L;
-}
-
-__global__ void head_pool_kernel(PoolHeadArgs a) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int which = blockIdx.y;
-    if (a.maps[which] == nullptr) return;
-    const int rows = a.rows[which];
-    if (i >= a.batch * rows) return;
-    const int clip = i / rows;
-    bool use_max = a.max_pool != 0;
-    const int L = pool_frames(a.seq, clip, a.Tm, a.n_pool_layers, a.tp, a.shrink, a.clip0, &use_max);
-    const float* m = a.maps[which] + static_cast<long long>(i) * a.Tm;
     float v;
     if (use_max) {
         v = -INFINITY;
@@ -300,8 +296,17 @@ __global__ void head_pool_kernel(PoolHeadArgs a) {
         for (int t = 0; t < L; ++t) sum += m[t];
         v = sum / static_cast<float>(L > 0 ? L : 0);                  // empty slice -> NaN, as torch.mean
     }
-    if (which == 0) v = 1.f / (1.f + expf(-v));                       // self.sig(key_out), models.py:802
-    a.outs[which][i] = v;
+    if (head == 0) v = 1.f / (1.f + expf(-v));                        // self.sig(key_out), models.py:802
+    return v;
+}
+
+__global__ void head_pool_kernel(PoolHeadArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int which = blockIdx.y;
+    if (a.maps[which] == nullptr) return;
+    const int rows = a.rows[which];
+    if (i >= a.batch * rows) return;
+    a.outs[which][i] = pool_row(a.pool, a.maps[which] + static_cast<long long>(i) * a.Tm, i / rows, a.Tm, which);
 }
 
 
@@ -690,6 +695,7 @@ struct P2pBfArgs {
 };
 
 typedef __bf16 bf16x8c __attribute__((ext_vector_type(8)));
+typedef float f32x4c __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8c __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2c __attribute__((ext_vector_type(2)));
 constexpr int kP2pProducts = 1;                                      // 1: f16 weights;  2: f16 hi + f16 lo weights (see above)
@@ -788,7 +794,6 @@ __global__ __launch_bounds__(512) void conv_p2p_f16_kernel(P2pBfArgs a) {
         const int r = m / J, j = m - r * J;
         abase[mt] = r * Tp + 2 * j + q;
     }
-    typedef float f32x4c __attribute__((ext_vector_type(4)));
     f32x4c acc[MT], accl[MT];       // products with the hi / the (scaled) lo weight plane
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) { acc[mt] = f32x4c{0.f, 0.f, 0.f, 0.f}; accl[mt] = f32x4c{0.f, 0.f, 0.f, 0.f}; }
@@ -941,12 +946,8 @@ __global__ __launch_bounds__(512, ((NIN > 0 && NIN != 3) ? 2 : 4)) void conv_p2p
                 row -= row >= a.H ? a.H : 0;
                 const uint4* src = reinterpret_cast<const uint4*>(a.xh) + cbase + static_cast<long long>(row) * T + (pk[k] & 0xffff);
                 uint4* dstl = lds4 + buf * a.plane_pos + c * 64;
-                // inline asm: hipcc orders every later LDS access behind a builtin LDS-DMA with vmcnt(0) (it cannot tell the two buffer
-                // halves apart), which would serialise load and multiply; the wait is placed by hand before the barrier instead
-                const unsigned int lds_dst = static_cast<unsigned int>(reinterpret_cast<unsigned long long>(dstl));   // LDS aperture: low 32 bits = LDS byte address
-                unsigned int keep;
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(src), "s"(lds_dst) : "memory");
+                // (lds_dma_16 waits for nothing: the wait is placed by hand before the barrier)
+                ake::lds_dma_16(src, static_cast<unsigned int>(reinterpret_cast<unsigned long long>(dstl)));
             }
         }
     };
@@ -1085,7 +1086,6 @@ __global__ __launch_bounds__(512, ((NIN > 0 && NIN != 3) ? 2 : 4)) void conv_p2p
         }
     };
     // bias + LeakyReLU, transposed into the wave's staging slab
-    typedef float f32x4c __attribute__((ext_vector_type(4)));
     auto epilogue = [&](const f32x4c (&acc)[MT], const f32x4c (&accl)[MT], int obuf) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
@@ -1351,7 +1351,6 @@ __global__ __launch_bounds__(512) void conv_p2p_f16x3_kernel(P2pTrArgs a) {
     const float bias = (a.bias && co < a.cout) ? a.bias[co] : 0.f;
     const float iscale = reinterpret_cast<const float*>(a.bfrag + kP2pFragScale)[co] / in_mul;
     uint4* const stage = lds4 + 4 * a.plane_pos + wave * (MT * kP2pPsStage);
-    typedef float f32x4c __attribute__((ext_vector_type(4)));
     long long prev_base = 0;
     int prev_mblk = 0;
     bool has_prev = false;
@@ -1470,23 +1469,20 @@ struct PcBfArgs {
     const unsigned int* in_amax;  // F16X3 data gradients: the input planes hold value * f16_weight_scale(*in_amax) (nchw_to_cl16_f16x2_kernel); or null
 };
 
-// F16X3 (training mode; forward with BatchNorm-on-load planes and the data gradients): the planes and fragments hold f16 hi and
-// f16 lo * 2^11 instead of bf16 hi / lo, the products are xh*wh and (xl'*wh + xh*wl') in an accumulator of their own folded in with 2^-11
-// (2^-22 of a product dropped: f32-equivalent, the gradient tests hold 2e-5), every output channel's weights are scaled by a power of
-// two (inverse scales behind the fragments), and the raw output's per-channel sums go to the BatchNorm statistics.
-template <int NT, bool OUT_CL, bool F16X3 = false>
-__global__ __launch_bounds__(512) void conv_pc_bf16_kernel(PcBfArgs a) {
-    extern __shared__ __attribute__((aligned(16))) uint4 lds4[];
-    const int clip = blockIdx.z;
+// The multiply loop of that convolution for one clip, shared by conv_pc_bf16_kernel (all forms) and phase A of heads_fused_kernel: the
+// workgroup's `nw` waves stage the clip and the weight rows in `lds4`, and this wave accumulates its MT M-tiles from `tile0` on (NT
+// N-tiles each) into acc / accl.  Ends after the last kernel row's MFMAs with no barrier: a caller that reuses the LDS places its own.
+// Which M-tiles a wave owns changes no value: per tile the k-steps and products come in one fixed order.
+template <int NT, int MT, bool F16X3>
+__device__ __forceinline__ void pc_bf16_multiply(const unsigned short* xh, const unsigned short* xl, const uint4* bfr, uint4* lds4, int clip, int T_in,
+                                                 int T_out, int pad_l, int Tp, int KH, int nw, int tile0, int Mtot, f32x4c (&acc_out)[MT][NT],
+                                                 f32x4c (&accl_out)[F16X3 ? MT : 1][F16X3 ? NT : 1]) {
+    // (the sums are kept in arrays of this function's own and handed over at the end: accumulated through the references, the two-N-tile
+    //  bf16 forms of conv_pc_bf16_kernel came out at 131 VGPRs instead of 115, 3 waves per SIMD instead of 4)
+    f32x4c acc[MT][NT], accl[F16X3 ? MT : 1][F16X3 ? NT : 1];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const float in_mul = (F16X3 && a.in_amax) ? f16_weight_scale(amax_load(a.in_amax)) : 1.f;      // data gradients: the planes hold dz * in_mul
-    const int nw = blockDim.x >> 6;
     const int r16 = lane & 15, q = lane >> 4;
-    const int Tp = a.Tp;
-    constexpr int MT = 4;
-    const int H_out = a.circular ? 12 : 12 - a.KH + 1;
-    const int Mtot = H_out * a.T_out;
     uint4* const pH = lds4;                                  // [12][Tp][2 halves of 8 channels]
     uint4* const pL = lds4 + 12 * Tp * 2;
     // weight fragments of one kernel row (4 k-steps x NT x (hi | lo) x 64 lanes), double-buffered: fetched ONCE per workgroup by LDS-DMA,
@@ -1494,30 +1490,24 @@ __global__ __launch_bounds__(512) void conv_pc_bf16_kernel(PcBfArgs a) {
     // pc2pc_fused_kernel)
     uint4* const wring = lds4 + 2 * 12 * Tp * 2;
     constexpr int kRow = 4 * NT * 2 * 64;                    // uint4 per kernel row
-    const bool second = blockIdx.y == 1;
-    const uint4* const bfr = second ? a.bfrag2 : a.bfrag;
     auto fetch_row = [&](int dyn) {                          // pieces of 64 lanes x 16 bytes, dealt to the waves
-        for (int pc = wave; pc < kRow / 64; pc += nw) {
-            const uint4* src = bfr + dyn * kRow + pc * 64 + lane;
-            const unsigned int lds_dst = static_cast<unsigned int>(reinterpret_cast<unsigned long long>(wring + (dyn & 1) * kRow + pc * 64));
-            unsigned int keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(src), "s"(lds_dst) : "memory");
-        }
+        for (int pc = wave; pc < kRow / 64; pc += nw)
+            ake::lds_dma_16(bfr + dyn * kRow + pc * 64 + lane,
+                            static_cast<unsigned int>(reinterpret_cast<unsigned long long>(wring + (dyn & 1) * kRow + pc * 64)));
     };
     fetch_row(0);
     {   // patch frame f <-> input frame f - pad_l, zeros outside [0, T_in)
-        const long long cbase = static_cast<long long>(clip) * 12 * a.T_in * 2;
-        const uint4* gh = reinterpret_cast<const uint4*>(a.xh) + cbase;
-        const uint4* gl = reinterpret_cast<const uint4*>(a.xl) + cbase;
+        const long long cbase = static_cast<long long>(clip) * 12 * T_in * 2;
+        const uint4* gh = reinterpret_cast<const uint4*>(xh) + cbase;
+        const uint4* gl = reinterpret_cast<const uint4*>(xl) + cbase;
         const int n16 = 12 * Tp * 2;
-        for (int i = threadIdx.x; i < n16; i += blockDim.x) {
+        for (int i = threadIdx.x; i < n16; i += nw * 64) {
             const int half = i & 1, pos = i >> 1;
             const int row = pos / Tp, f = pos - row * Tp;
-            const int t = f - a.pad_l;
+            const int t = f - pad_l;
             uint4 vh = make_uint4(0, 0, 0, 0), vl = make_uint4(0, 0, 0, 0);
-            if (t >= 0 && t < a.T_in) {
-                const long long g = (static_cast<long long>(row) * a.T_in + t) * 2 + half;
+            if (t >= 0 && t < T_in) {
+                const long long g = (static_cast<long long>(row) * T_in + t) * 2 + half;
                 vh = gh[g]; vl = gl[g];
             }
             pH[i] = vh; pL[i] = vl;
@@ -1525,18 +1515,15 @@ __global__ __launch_bounds__(512) void conv_pc_bf16_kernel(PcBfArgs a) {
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);                       // vmcnt(0): this wave's share of row 0 has landed
     __syncthreads();
-    const int tile0 = (blockIdx.x * nw + wave) * MT;          // first M-tile of this wave
     const bool active = tile0 * 16 < Mtot;                    // (idle waves still fetch and meet the barriers)
     int ay[MT], at[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
         int m = (tile0 + mt) * 16 + r16;
         if (m >= Mtot) m = Mtot - 1;
-        ay[mt] = m / a.T_out;
-        at[mt] = m - ay[mt] * a.T_out;
+        ay[mt] = m / T_out;
+        at[mt] = m - ay[mt] * T_out;
     }
-    typedef float f32x4c __attribute__((ext_vector_type(4)));
-    f32x4c acc[MT][NT], accl[F16X3 ? MT : 1][F16X3 ? NT : 1];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -1545,9 +1532,9 @@ __global__ __launch_bounds__(512) void conv_pc_bf16_kernel(PcBfArgs a) {
             if (F16X3) accl[mt][nt] = f32x4c{0.f, 0.f, 0.f, 0.f};
         }
     const int dxq = q >> 1, half = q & 1;
-    const bool pair = !(a.KH & 1);
-    for (int dy = 0; dy < a.KH; ++dy) {
-        if (dy + 1 < a.KH) fetch_row(dy + 1);                 // lands in the other half during this row's MFMAs
+    const bool pair = !(KH & 1);
+    for (int dy = 0; dy < KH; ++dy) {
+        if (dy + 1 < KH) fetch_row(dy + 1);                   // lands in the other half during this row's MFMAs
         const uint4* const wr = wring + (dy & 1) * kRow + lane;
         if (active) {
         int rowoff[MT], rowoff3[MT];
@@ -1599,12 +1586,42 @@ __global__ __launch_bounds__(512) void conv_pc_bf16_kernel(PcBfArgs a) {
             }
         }
         }
-        if (dy + 1 < a.KH) {
+        if (dy + 1 < KH) {
             __builtin_amdgcn_s_waitcnt(0x0F70);               // this wave's share of the next row has landed ...
             __syncthreads();                                  // ... everybody's; and everybody is done with this row's half
         }
     }
-    if (!active) return;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            acc_out[mt][nt] = acc[mt][nt];
+            if (F16X3) accl_out[mt][nt] = accl[mt][nt];
+        }
+}
+
+// F16X3 (training mode; forward with BatchNorm-on-load planes and the data gradients): the planes and fragments hold f16 hi and
+// f16 lo * 2^11 instead of bf16 hi / lo, the products are xh*wh and (xl'*wh + xh*wl') in an accumulator of their own folded in with 2^-11
+// (2^-22 of a product dropped: f32-equivalent, the gradient tests hold 2e-5), every output channel's weights are scaled by a power of
+// two (inverse scales behind the fragments), and the raw output's per-channel sums go to the BatchNorm statistics.
+template <int NT, bool OUT_CL, bool F16X3 = false>
+__global__ __launch_bounds__(512) void conv_pc_bf16_kernel(PcBfArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint4 lds4[];
+    const int clip = blockIdx.z;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const float in_mul = (F16X3 && a.in_amax) ? f16_weight_scale(amax_load(a.in_amax)) : 1.f;      // data gradients: the planes hold dz * in_mul
+    const int nw = blockDim.x >> 6;
+    const int r16 = lane & 15, q = lane >> 4;
+    constexpr int MT = 4;
+    const int H_out = a.circular ? 12 : 12 - a.KH + 1;
+    const int Mtot = H_out * a.T_out;
+    const bool second = blockIdx.y == 1;
+    const uint4* const bfr = second ? a.bfrag2 : a.bfrag;
+    const int tile0 = (blockIdx.x * nw + wave) * MT;          // first M-tile of this wave
+    f32x4c acc[MT][NT], accl[F16X3 ? MT : 1][F16X3 ? NT : 1];
+    pc_bf16_multiply<NT, MT, F16X3>(a.xh, a.xl, bfr, lds4, clip, a.T_in, a.T_out, a.pad_l, a.Tp, a.KH, nw, tile0, Mtot, acc, accl);
+    if (tile0 * 16 >= Mtot) return;
     // ---- epilogue: D[row m = 4q + i][col = co within the N-tile] ----
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
@@ -1658,8 +1675,8 @@ __global__ __launch_bounds__(512) void conv_pc_bf16_kernel(PcBfArgs a) {
 // The last layer's PitchClass2PitchClass stack (cin <= 16 -> 16 -> 16 -> 16 channels on a 12 x T map) + the time pooling that
 // follows it (models.py:393, 396) in ONE launch: one workgroup of 16 waves per clip keeps the maps in LDS as channels-last
 // split planes (two ping-pong maps of 12 x (T + 8) x 16 channels), converts the NCHW f32 input while loading, runs the convs with
-// the MFMA loop of conv_pc_bf16_kernel<1, *> (same arithmetic in the same order), and the last epilogue takes the max over frame
-// pairs in registers and writes the pooled features twice: NCHW f32 (taps, f32 heads) and channels-last planes (bf16 heads).
+// an MFMA loop of its own (the k-steps and products of pc_bf16_multiply<1, 4, false> on another schedule: rotating A fragments, the
+// k-step pair as the outer loop; it shares no code with it), and the last epilogue takes the max over frame pairs in registers and writes the pooled features twice: NCHW f32 (taps, f32 heads) and channels-last planes (bf16 heads).
 // Measured on the per-conv launches (phases switched off one at a time): 13 us of launch + epilogue and 4 us of patch load per
 // 21 us of MFMA loop, three times, plus the conversion and pooling passes.
 // ==========================================================================================
@@ -1727,7 +1744,6 @@ __global__ __launch_bounds__(1024) void pc2pc_fused_kernel(Pc2pcFusedArgs a) {
     const bool active = wave < 3 * n_tt;
     const int tt = wave / 3, y0 = 4 * (wave - 3 * tt);
     const int t0 = 16 * tt;
-    typedef float f32x4c __attribute__((ext_vector_type(4)));
     const int dxq = q >> 1, half = q & 1;
     const int lane_off = ((t0 + r16 + dxq) << 1) + half;      // (frames past the row's end read the next row: those output rows are never stored)
     const int lane_off3 = ((t0 + r16 + 6) << 1) + half;
@@ -1872,42 +1888,37 @@ struct Head1BfArgs {
     int T_in, T_out, Tp, JB;
     // masked temporal mean + sigmoid of the finished map (models.py:754-804) in the same launch: pout[head] = [clip][H_out] or null
     float* pout[3];
-    const long long* seq;
-    int n_pool_layers, tp, shrink, max_pool, clip0;
+    PoolArgs pool;
     int fin_off;                  // float offset of the finished map's LDS copy [H_out][T_out] (behind the reduction buffer)
 };
 
 constexpr int kHead1MT = 4;       // M-tiles (12 * JB positions / 16): T_out <= 80
+constexpr int kHead1PF = 3;       // weight fragments in flight per wave (they come from L2: fetched at their use, every k-step paid a full round trip)
 
-__global__ __launch_bounds__(512) void conv_head1_bf16_kernel(Head1BfArgs a) {
-    extern __shared__ __attribute__((aligned(16))) uint4 lds4[];
-    const int clip = blockIdx.x, head = blockIdx.y;
+// The body of that convolution, shared by conv_head1_bf16_kernel and phase B of heads_fused_kernel, in two calls so that a caller can
+// issue the first loads before its patch is ready.  bg = the head's fragments + lane, nks = KH * 22 k-steps, wave w takes w, w + 8, ...
+__device__ __forceinline__ void head1_prefetch(const uint4* __restrict__ bg, int nks, int wave, uint4 (&nbh)[kHead1PF], uint4 (&nbl)[kHead1PF]) {
+#pragma unroll
+    for (int i = 0; i < kHead1PF; ++i) {
+        const int kn = wave + 8 * i < nks ? wave + 8 * i : wave;
+        nbh[i] = bg[(2 * kn + 0) * 64]; nbl[i] = bg[(2 * kn + 1) * 64];
+    }
+}
+
+// ... and the k-step loop over the patch [12][Tp][4 groups of 8 channels] at the start of `lds4` (hi plane, then lo), the reduction of
+// the eight waves' partial tiles through LDS, the bias and the store of the finished map [HO][T_out] to dst and, with `keep`, to its LDS
+// copy at float offset fin_off.  A caller that reads the copy places a barrier first.
+__device__ __forceinline__ void head1_multiply_store(const uint4* __restrict__ bg, int nks, uint4 (&nbh)[kHead1PF], uint4 (&nbl)[kHead1PF], uint4* lds4,
+                                                     int Tp, int HO, int circ, int JB, int T_out, int clip, const float* bias_p, float* dst,
+                                                     bool keep, int fin_off) {
+    constexpr int PF = kHead1PF;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r16 = lane & 15, q = lane >> 4;
-    const int Tp = a.Tp;
-    uint4* const pH = lds4;                                  // [12][Tp][4 groups of 8 channels]
-    uint4* const pL = lds4 + 12 * Tp * 4;
+    const uint4* const pH = lds4;
+    const uint4* const pL = lds4 + 12 * Tp * 4;
     float* const red = reinterpret_cast<float*>(lds4);       // [8 waves][kHead1MT][4][64]: reuses the patch's bytes after the multiply loop
-    {
-        const long long cbase = static_cast<long long>(clip) * 12 * a.T_in * 4;
-        const uint4* gh = reinterpret_cast<const uint4*>(a.xh[head]) + cbase;
-        const uint4* gl = reinterpret_cast<const uint4*>(a.xl[head]) + cbase;
-        const int n16 = 12 * Tp * 4;
-        for (int i = threadIdx.x; i < n16; i += blockDim.x) {
-            const int grp = i & 3, pos = i >> 2;
-            const int row = pos / Tp, f = pos - row * Tp;
-            uint4 vh = make_uint4(0, 0, 0, 0), vl = make_uint4(0, 0, 0, 0);
-            if (f < a.T_in) {
-                const long long g = (static_cast<long long>(row) * a.T_in + f) * 4 + grp;
-                vh = gh[g]; vl = gl[g];
-            }
-            pH[i] = vh; pL[i] = vl;
-        }
-    }
-    __syncthreads();
-    const int HO = a.H_out[head], circ = a.circular[head], nks = a.KH[head] * 22;
-    const int Mtot = HO * a.JB;
+    const int Mtot = HO * JB;
     const int mtiles = (Mtot + 15) / 16;
     int ay[kHead1MT], af[kHead1MT];
 #pragma unroll
@@ -1918,19 +1929,9 @@ __global__ __launch_bounds__(512) void conv_head1_bf16_kernel(Head1BfArgs a) {
         ay[mt] = m - jb * HO;
         af[mt] = 16 * jb;
     }
-    typedef float f32x4c __attribute__((ext_vector_type(4)));
     f32x4c acc[kHead1MT];
 #pragma unroll
     for (int mt = 0; mt < kHead1MT; ++mt) acc[mt] = f32x4c{0.f, 0.f, 0.f, 0.f};
-    const uint4* __restrict__ bg = a.bfrag[head] + lane;
-    // weight fragments three k-steps ahead (they come from L2: fetched at their use, every k-step paid a full round trip)
-    constexpr int PF = 3;
-    uint4 nbh[PF], nbl[PF];
-#pragma unroll
-    for (int i = 0; i < PF; ++i) {
-        const int kn = wave + 8 * i < nks ? wave + 8 * i : wave;
-        nbh[i] = bg[(2 * kn + 0) * 64]; nbl[i] = bg[(2 * kn + 1) * 64];
-    }
     for (int ks = wave; ks < nks; ks += 8) {
         const int dy = ks / 22, dxe = ks - dy * 22;
         const bf16x8c bh = __builtin_bit_cast(bf16x8c, nbh[0]);
@@ -1963,7 +1964,7 @@ __global__ __launch_bounds__(512) void conv_head1_bf16_kernel(Head1BfArgs a) {
     __syncthreads();
     // wave w finishes M-tile w: D[row m = 4q + i][col tau]
     if (wave < mtiles) {
-        const float bias = a.bias[head][0];
+        const float bias = bias_p[0];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             float v = bias;
@@ -1972,38 +1973,59 @@ __global__ __launch_bounds__(512) void conv_head1_bf16_kernel(Head1BfArgs a) {
             const int m = wave * 16 + 4 * q + i;
             const int jb = m / HO, y = m - jb * HO;
             const int t = 16 * jb + r16;
-            if (m < Mtot && t < a.T_out) {
-                a.dst[head][(static_cast<long long>(clip) * HO + y) * a.T_out + t] = v;
-                if (a.pout[head]) reinterpret_cast<float*>(lds4)[a.fin_off + y * a.T_out + t] = v;
+            if (m < Mtot && t < T_out) {
+                dst[(static_cast<long long>(clip) * HO + y) * T_out + t] = v;
+                if (keep) red[fin_off + y * T_out + t] = v;
             }
         }
     }
+}
+
+__global__ __launch_bounds__(512) void conv_head1_bf16_kernel(Head1BfArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint4 lds4[];
+    const int clip = blockIdx.x, head = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int Tp = a.Tp;
+    uint4* const pH = lds4;                                  // [12][Tp][4 groups of 8 channels]
+    uint4* const pL = lds4 + 12 * Tp * 4;
+    {
+        const long long cbase = static_cast<long long>(clip) * 12 * a.T_in * 4;
+        const uint4* gh = reinterpret_cast<const uint4*>(a.xh[head]) + cbase;
+        const uint4* gl = reinterpret_cast<const uint4*>(a.xl[head]) + cbase;
+        const int n16 = 12 * Tp * 4;
+        for (int i = threadIdx.x; i < n16; i += blockDim.x) {
+            const int grp = i & 3, pos = i >> 2;
+            const int row = pos / Tp, f = pos - row * Tp;
+            uint4 vh = make_uint4(0, 0, 0, 0), vl = make_uint4(0, 0, 0, 0);
+            if (f < a.T_in) {
+                const long long g = (static_cast<long long>(row) * a.T_in + f) * 4 + grp;
+                vh = gh[g]; vl = gl[g];
+            }
+            pH[i] = vh; pL[i] = vl;
+        }
+    }
+    __syncthreads();
+    const int HO = a.H_out[head], nks = a.KH[head] * 22;
+    const uint4* __restrict__ bg = a.bfrag[head] + lane;
+    uint4 nbh[kHead1PF], nbl[kHead1PF];
+    head1_prefetch(bg, nks, wave, nbh, nbl);
+    head1_multiply_store(bg, nks, nbh, nbl, lds4, Tp, HO, a.circular[head], a.JB, a.T_out, clip, a.bias[head], a.dst[head], a.pout[head] != nullptr,
+                         a.fin_off);
     if (a.pout[head] == nullptr) return;
     __syncthreads();
-    if (threadIdx.x < HO) {                                   // one lane per output row, as head_pool_kernel
-        bool use_max = a.max_pool != 0;
-        const int L = pool_frames(a.seq, clip, a.T_out, a.n_pool_layers, a.tp, a.shrink, a.clip0, &use_max);
-        const float* m = reinterpret_cast<const float*>(lds4) + a.fin_off + threadIdx.x * a.T_out;
-        float v;
-        if (use_max) {
-            v = -INFINITY;
-            for (int t = 0; t < L; ++t) v = fmaxf(v, m[t]);
-        } else {
-            float sum = 0.f;
-            for (int t = 0; t < L; ++t) sum += m[t];
-            v = sum / static_cast<float>(L > 0 ? L : 0);              // empty slice -> NaN, as torch.mean
-        }
-        if (head == 0) v = 1.f / (1.f + expf(-v));                    // self.sig(key_out), models.py:802
-        a.pout[head][clip * HO + threadIdx.x] = v;
-    }
+    if (threadIdx.x < HO)                                     // one lane per output row, as head_pool_kernel
+        a.pout[head][clip * HO + threadIdx.x] =
+            pool_row(a.pool, reinterpret_cast<const float*>(lds4) + a.fin_off + threadIdx.x * a.T_out, clip, a.T_out, head);
 }
 
 // ==========================================================================================
 // Both convolutions of a two-conv head (16 -> 32 channels, then 32 -> one map) + the masked pooling in ONE launch: one workgroup of
-// 8 waves per (clip, head).  Phase A is conv_pc_bf16_kernel<2, true> over the whole clip (the same k-steps and products in the same
-// order per tile), phase B is conv_head1_bf16_kernel from its first barrier on.  Between them the 32 hidden channels do not leave
-// the LDS: phase A's epilogue writes its split-bf16 values straight into phase B's patch [12][TpB][4 groups of 8 channels], which
-// overlays phase A's own patch and weight ring (dead by then).  Values are bit for bit those of the two launches.
+// 8 waves per (clip, head).  Phase A is pc_bf16_multiply, the multiply loop of conv_pc_bf16_kernel<2, true>, over the whole clip;
+// phase B is head1_prefetch + head1_multiply_store, all of conv_head1_bf16_kernel behind its patch load.  Between them the 32 hidden
+// channels do not leave the LDS: phase A's epilogue writes its split-bf16 values straight into phase B's patch [12][TpB][4 groups of
+// 8 channels], which overlays phase A's own patch and weight ring (dead by then).  Values are bit for bit those of the two launches:
+// both paths run the same functions.
 // ==========================================================================================
 struct HeadsFusedArgs {
     const unsigned short* xh;     // pooled features, channels-last planes [clip][12][T_in][16]
@@ -2019,8 +2041,7 @@ struct HeadsFusedArgs {
     int batch;
     int T_in, T1, T2;             // frames: features, hidden map (T_in - 6), finished map (T1 - 6)
     int TpA, TpB, JB;             // patch widths of the two phases (T1 + 8; 16 (JB - 1) + 22), 16-frame blocks of the finished map
-    const long long* seq;
-    int n_pool_layers, tp, shrink, max_pool, clip0;
+    PoolArgs pool;
     int fin_off;                  // float offset of the finished map's LDS copy [H_out][T2] (behind everything else)
 };
 
@@ -2037,7 +2058,6 @@ __global__ __launch_bounds__(512, 4) void heads_fused_kernel(HeadsFusedArgs a) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r16 = lane & 15, q = lane >> 4;
-    typedef float f32x4c __attribute__((ext_vector_type(4)));
     constexpr int NT = 2;
     const int TpB = a.TpB;
     uint4* const pHB = lds4;                                 // phase B's patch [12][TpB][4 groups of 8 channels]
@@ -2045,113 +2065,15 @@ __global__ __launch_bounds__(512, 4) void heads_fused_kernel(HeadsFusedArgs a) {
     const uint4* __restrict__ bg = AKE_HSEL(bfragB) + lane;
     const int KHB = AKE_HSEL(KHB);
     const int nks = KHB * 22;
-    constexpr int PF = 3;
-    uint4 nbh[PF], nbl[PF];
-    {   // ---- phase A: conv_pc_bf16_kernel<2, true>, valid in time, the whole clip in this workgroup ----
-        const int Tp = a.TpA;
-        const int KH = AKE_HSEL(KHA);
+    uint4 nbh[kHead1PF], nbl[kHead1PF];
+    {   // ---- phase A: pc_bf16_multiply<2, MT, false>, valid in time, the whole clip in this workgroup ----
         const int Mtot = 12 * a.T1;                          // (12 output rows in both forms: 12 circular kernel rows, or one)
-        uint4* const pH = lds4;                              // [12][Tp][2 halves of 8 channels]
-        uint4* const pL = lds4 + 12 * Tp * 2;
-        uint4* const wring = lds4 + 2 * 12 * Tp * 2;         // one kernel row of weight fragments, double-buffered (conv_pc_bf16_kernel)
-        constexpr int kRow = 4 * NT * 2 * 64;
-        const uint4* const bfr = AKE_HSEL(bfragA);
-        auto fetch_row = [&](int dyn) {
-            for (int pc = wave; pc < kRow / 64; pc += 8) {
-                const uint4* src = bfr + dyn * kRow + pc * 64 + lane;
-                const unsigned int lds_dst = static_cast<unsigned int>(reinterpret_cast<unsigned long long>(wring + (dyn & 1) * kRow + pc * 64));
-                unsigned int keep;
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(src), "s"(lds_dst) : "memory");
-            }
-        };
-        fetch_row(0);
-        {
-            const long long cbase = static_cast<long long>(clip) * 12 * a.T_in * 2;
-            const uint4* gh = reinterpret_cast<const uint4*>(a.xh) + cbase;
-            const uint4* gl = reinterpret_cast<const uint4*>(a.xl) + cbase;
-            const int n16 = 12 * Tp * 2;
-            for (int i = threadIdx.x; i < n16; i += 512) {
-                const int half = i & 1, pos = i >> 1;
-                const int row = pos / Tp, f = pos - row * Tp;
-                uint4 vh = make_uint4(0, 0, 0, 0), vl = make_uint4(0, 0, 0, 0);
-                if (f < a.T_in) {
-                    const long long g = (static_cast<long long>(row) * a.T_in + f) * 2 + half;
-                    vh = gh[g]; vl = gl[g];
-                }
-                pH[i] = vh; pL[i] = vl;
-            }
-        }
-        __builtin_amdgcn_s_waitcnt(0x0F70);                   // vmcnt(0): this wave's share of row 0 has landed
-        __syncthreads();
         const int tile0 = wave * MT;
-        const bool active = tile0 * 16 < Mtot;                // (idle waves still fetch and meet the barriers)
-        int ay[MT], at[MT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            int m = (tile0 + mt) * 16 + r16;
-            if (m >= Mtot) m = Mtot - 1;
-            ay[mt] = m / a.T1;
-            at[mt] = m - ay[mt] * a.T1;
-        }
-        f32x4c acc[MT][NT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4c{0.f, 0.f, 0.f, 0.f};
-        const int dxq = q >> 1, half = q & 1;
-        const bool pair = !(KH & 1);
-        for (int dy = 0; dy < KH; ++dy) {
-            if (dy + 1 < KH) fetch_row(dy + 1);
-            const uint4* const wr = wring + (dy & 1) * kRow + lane;
-            if (active) {
-                int rowoff[MT], rowoff3[MT];
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) {
-                    int row = ay[mt] + dy;
-                    row -= row >= 12 ? 12 : 0;
-                    rowoff[mt] = ((row * Tp + at[mt] + dxq) << 1) + half;
-                    int row3 = ay[mt] + dy + dxq;             // the paired seventh taps of kernel rows dy, dy + 1 (conv_pc_bf16_kernel)
-                    row3 -= row3 >= 12 ? 12 : 0;
-                    rowoff3[mt] = pair ? ((row3 * Tp + at[mt] + 6) << 1) + half : rowoff[mt] + 12;
-                }
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    if (p == 3 && pair && (dy & 1)) break;
-                    uint4 bhu[NT], blu[NT], ahu[MT], alu[MT];
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) {
-                        bhu[nt] = wr[((p * NT + nt) * 2 + 0) * 64];
-                        blu[nt] = wr[((p * NT + nt) * 2 + 1) * 64];
-                    }
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) {
-                        ahu[mt] = pH[p == 3 ? rowoff3[mt] : rowoff[mt] + 4 * p];
-                        alu[mt] = pL[p == 3 ? rowoff3[mt] : rowoff[mt] + 4 * p];
-                    }
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) {
-                        const bf16x8c bh = __builtin_bit_cast(bf16x8c, bhu[nt]), bl = __builtin_bit_cast(bf16x8c, blu[nt]);
-#pragma unroll
-                        for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8c, ahu[mt]), bh, acc[mt][nt], 0, 0, 0);
-#pragma unroll
-                        for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8c, alu[mt]), bh, acc[mt][nt], 0, 0, 0);
-#pragma unroll
-                        for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8c, ahu[mt]), bl, acc[mt][nt], 0, 0, 0);
-                    }
-                }
-            }
-            if (dy + 1 < KH) {
-                __builtin_amdgcn_s_waitcnt(0x0F70);           // this wave's share of the next row has landed ...
-                __syncthreads();                              // ... everybody's; and everybody is done with this row's half
-            }
-        }
+        const bool active = tile0 * 16 < Mtot;
+        f32x4c acc[MT][NT], accl[1][1];
+        pc_bf16_multiply<NT, MT, false>(a.xh, a.xl, AKE_HSEL(bfragA), lds4, clip, a.T_in, a.T1, 0, a.TpA, AKE_HSEL(KHA), 8, tile0, Mtot, acc, accl);
         // phase B's first weight fragments (from L2): their latency hides under the epilogue
-#pragma unroll
-        for (int i = 0; i < PF; ++i) {
-            const int kn = wave + 8 * i < nks ? wave + 8 * i : wave;
-            nbh[i] = bg[(2 * kn + 0) * 64]; nbl[i] = bg[(2 * kn + 1) * 64];
-        }
+        head1_prefetch(bg, nks, wave, nbh, nbl);
         __syncthreads();                                      // every wave is done with phase A's patch and ring
         // ---- hand-over: bias, LeakyReLU, hi / lo split (the OUT_CL epilogue of conv_pc_bf16_kernel) into phase B's patch; the
         // frames f >= T1 of that patch are zeros ----
@@ -2193,89 +2115,13 @@ __global__ __launch_bounds__(512, 4) void heads_fused_kernel(HeadsFusedArgs a) {
         }
     }
     __syncthreads();
-    // ---- phase B: conv_head1_bf16_kernel ----
-    float* const red = reinterpret_cast<float*>(lds4);       // [8 waves][kHead1MT][4][64]: reuses the patch's bytes after the multiply loop
+    // ---- phase B: head1_multiply_store on the patch just written ----
     const int circ = KHB == 12 ? 1 : 0;
     const int HO = circ ? 12 : 12 - KHB + 1;
-    const int Mtot = HO * a.JB;
-    const int mtiles = (Mtot + 15) / 16;
-    int ay[kHead1MT], af[kHead1MT];
-#pragma unroll
-    for (int mt = 0; mt < kHead1MT; ++mt) {
-        int m = mt * 16 + r16;
-        if (m >= Mtot) m = Mtot - 1;
-        const int jb = m / HO;
-        ay[mt] = m - jb * HO;
-        af[mt] = 16 * jb;
-    }
-    f32x4c acc[kHead1MT];
-#pragma unroll
-    for (int mt = 0; mt < kHead1MT; ++mt) acc[mt] = f32x4c{0.f, 0.f, 0.f, 0.f};
-    for (int ks = wave; ks < nks; ks += 8) {
-        const int dy = ks / 22, dxe = ks - dy * 22;
-        const bf16x8c bh = __builtin_bit_cast(bf16x8c, nbh[0]);
-        const bf16x8c bl = __builtin_bit_cast(bf16x8c, nbl[0]);
-#pragma unroll
-        for (int i = 0; i + 1 < PF; ++i) { nbh[i] = nbh[i + 1]; nbl[i] = nbl[i + 1]; }
-        {
-            const int kn = ks + 8 * PF < nks ? ks + 8 * PF : ks;
-            nbh[PF - 1] = bg[(2 * kn + 0) * 64]; nbl[PF - 1] = bg[(2 * kn + 1) * 64];
-        }
-#pragma unroll
-        for (int mt = 0; mt < kHead1MT; ++mt) {
-            if (mt < mtiles) {
-                int row = ay[mt] + dy;
-                row -= (circ && row >= 12) ? 12 : 0;
-                const int ad = ((row * TpB + af[mt] + dxe) << 2) + q;
-                const bf16x8c ah = __builtin_bit_cast(bf16x8c, pHB[ad]);
-                const bf16x8c al = __builtin_bit_cast(bf16x8c, pLB[ad]);
-                acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc[mt], 0, 0, 0);
-                acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, acc[mt], 0, 0, 0);
-                acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, acc[mt], 0, 0, 0);
-            }
-        }
-    }
-    __syncthreads();                                         // every wave is done with the patch
-#pragma unroll
-    for (int mt = 0; mt < kHead1MT; ++mt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) red[((wave * kHead1MT + mt) * 4 + i) * 64 + lane] = acc[mt][i];
+    head1_multiply_store(bg, nks, nbh, nbl, lds4, TpB, HO, circ, a.JB, a.T2, clip, AKE_HSEL(biasB), AKE_HSEL(dst), true, a.fin_off);
     __syncthreads();
-    // wave w finishes M-tile w: D[row m = 4q + i][col tau]
-    if (wave < mtiles) {
-        const float bias = AKE_HSEL(biasB)[0];
-        float* const dst = AKE_HSEL(dst);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float v = bias;
-#pragma unroll
-            for (int w = 0; w < 8; ++w) v += red[((w * kHead1MT + wave) * 4 + i) * 64 + lane];
-            const int m = wave * 16 + 4 * q + i;
-            const int jb = m / HO, y = m - jb * HO;
-            const int t = 16 * jb + r16;
-            if (m < Mtot && t < a.T2) {
-                dst[(static_cast<long long>(clip) * HO + y) * a.T2 + t] = v;
-                reinterpret_cast<float*>(lds4)[a.fin_off + y * a.T2 + t] = v;
-            }
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < HO) {                                   // one lane per output row, as head_pool_kernel
-        bool use_max = a.max_pool != 0;
-        const int L = pool_frames(a.seq, clip, a.T2, a.n_pool_layers, a.tp, a.shrink, a.clip0, &use_max);
-        const float* m = reinterpret_cast<const float*>(lds4) + a.fin_off + threadIdx.x * a.T2;
-        float v;
-        if (use_max) {
-            v = -INFINITY;
-            for (int t = 0; t < L; ++t) v = fmaxf(v, m[t]);
-        } else {
-            float sum = 0.f;
-            for (int t = 0; t < L; ++t) sum += m[t];
-            v = sum / static_cast<float>(L > 0 ? L : 0);              // empty slice -> NaN, as torch.mean
-        }
-        if (head == 0) v = 1.f / (1.f + expf(-v));                    // self.sig(key_out), models.py:802
-        AKE_HSEL(pout)[clip * HO + threadIdx.x] = v;
-    }
+    if (threadIdx.x < HO)                                     // one lane per output row, as head_pool_kernel
+        AKE_HSEL(pout)[clip * HO + threadIdx.x] = pool_row(a.pool, reinterpret_cast<const float*>(lds4) + a.fin_off + threadIdx.x * a.T2, clip, a.T2, head);
 #undef AKE_HSEL
 }
 
@@ -2917,7 +2763,6 @@ __global__ __launch_bounds__(512) void layer0_mfma_kernel(Layer0Args a) {
     }
     __syncthreads();
     // ---- the convolution stack on MFMA ----
-    typedef float f32x4c __attribute__((ext_vector_type(4)));
     const int J = (T + 1) / 2, M = 12 * J, n_tiles = (M + 15) / 16;
     const int tau = (r16 >> 2) & 1, co = r16 & 3;
     const unsigned short* in = mapA;
