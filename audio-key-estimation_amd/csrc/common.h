@@ -65,6 +65,9 @@ __device__ __forceinline__ void lds_dma_16(const uint4* src, unsigned int lds_ds
                  : "=&s"(keep) : "v"(src), "s"(lds_dst) : "memory");
 }
 
+// cfg.local of a handle: the --local pooling window, 0 for a clip-level net (pcnet.hip)
+int pcnet_local_window(const ake_pcnet* net);
+
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // Bump allocator over the caller's workspace.

@@ -1319,7 +1319,13 @@ int cqt_logmag_impl(const ake_cqt_plan* p, const float* audio, int batch, int64_
         a.g0 = -512;
         const long long g1 = n_in + static_cast<long long>(25 + kLagHost[fused]) * (1ll << fused) + 512;
         a.ticks_total = static_cast<int>((g1 - a.g0 + C - 1) / C);
-        const int segs = std::max(1, std::min(a.ticks_total, 4));
+        // Segments per clip: 4 (the benchmarked shape: 256 clips x 82 ticks = 1 024 workgroups), or -- when the batch alone does not fill
+        // the GPU and the clips are long (key tracking: 8 recordings x 1 616 ticks were 32 workgroups, 1.41 ms for the samples that 160
+        // clips stream in 0.12 ms) -- enough to reach that many workgroups from the clips' length, at >= 20 ticks per segment (each
+        // segment recomputes `warm` ticks of history).  The segments are tick-aligned and every output sees its full history either way,
+        // so the split never changes a value.
+        const int by_batch = (1024 + batch - 1) / batch, by_length = a.ticks_total / 20;
+        const int segs = std::max(1, std::min(a.ticks_total, std::max(4, std::min(by_batch, by_length))));
         a.ticks_per_seg = (a.ticks_total + segs - 1) / segs;
         a.warm = 3;                                         // >= 64 * 2^7 / C ticks of history before the first owned tick
     };

@@ -1007,6 +1007,9 @@ int plan_buffers(const ake_pcnet* n, int batch, int chunk, int frames, void* ws,
 
 }  // namespace
 
+// (for the other translation units of the library: the handle's layout is private to this one)
+int ake::pcnet_local_window(const ake_pcnet* n) { return n ? n->cfg.local : 0; }
+
 extern "C" {
 
 int ake_pcnet_precision(const ake_pcnet* n) { return n ? n->cfg.precision : AKE_ERR_INVALID; }

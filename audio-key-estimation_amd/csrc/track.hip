@@ -1,0 +1,324 @@
+// Key tracking over long recordings: ONE CQT per recording, then the clip-level net on sliding windows of its frames, then a decode of
+// every window's (key, tonic) outputs to a key label -- all on one stream, no host round trip.
+//
+// Semantics (also include/ake_hip.h and INTEGRATION.md):
+//   - a recording of n samples is transformed once at the plan's hop: T = 1 + n / hop frames (ake_cqt_num_frames);
+//   - window w of a recording is frames [w * stride_frames, w * stride_frames + window_frames) of the recording's OWN transform; the net
+//     runs on it exactly as on a clip of window_frames frames with seq_length = window_frames (time-circular convolutions wrap at the
+//     window's ends).  A frame near a window edge therefore sees the recording's real neighbouring audio where a separately transformed
+//     clip sees zero padding: the one intended difference from clip-wise results;
+//   - recording i has count_i = (T_i - window_frames) / stride_frames + 1 windows (0 if T_i < window_frames);
+//   - decode per window: sig = first-maximum cosine match of the key output over the 21-row key-signature table (the arithmetic and tie
+//     rule of metrics.mirex_score / models.py:1065-1083, eps 1e-8), tonic = first maximum of the tonic logits, confidence = that cosine,
+//     key_id in the project's 24-way label order (0-11 minor, 12-23 major, tonic = id mod 12; KeyDataset.py:524-527): 12 + tonic if tonic
+//     is the table row's major tonic, tonic if it is that tonic + 9 (the relative minor), -1 otherwise (signature and tonic disagree).
+//
+// The windows reach the net through window_gather_kernel, which copies them out of either CQT layout into the [B][1][P][window_frames]
+// tensor ake_pcnet_forward_f32 takes, a chunk of kTrackChunk windows at a time (the chunk bounds the workspace and is the net's own
+// pitch-stream chunk, so nothing is chunked twice).
+#include "common.h"
+
+#include <algorithm>
+
+namespace {
+
+constexpr int kTrackChunk = 256;      // windows per forward call = ake_pcnet's pitch-stream chunk
+constexpr int kTile = 32;
+
+struct GatherArgs {
+    const float* src;          // FM: [recording][total_frames][P]; else [recording][P][total_frames]
+    float* dst;                // [clip][P][window_frames]
+    int P, total_frames, window_frames, stride_frames;
+    int windows;               // per recording
+    int clip0;                 // global window index of dst's clip 0
+};
+
+// One 32 x 32 tile of one window per block of 32 x 8 threads.  FM source: the loads run along the bins (the source's fast axis), the
+// stores along the frames (the destination's), a padded LDS tile turns the one into the other.  Row-major source: both fast axes are
+// the frames, a straight copy.
+template <bool FM>
+__global__ __launch_bounds__(256) void window_gather_kernel(GatherArgs a) {
+    __shared__ float tile[kTile][kTile + 1];
+    const int g = a.clip0 + blockIdx.z;
+    const int rec = g / a.windows, t0 = (g - rec * a.windows) * a.stride_frames;      // t0 + window_frames <= total_frames (host-checked)
+    const int p0 = blockIdx.x * kTile, f0 = blockIdx.y * kTile;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const float* const src = a.src + static_cast<long long>(rec) * a.P * a.total_frames;
+    float* const dst = a.dst + static_cast<long long>(blockIdx.z) * a.P * a.window_frames;
+    if (FM) {
+        for (int j = ty; j < kTile; j += 8) {
+            const int f = f0 + j, p = p0 + tx;
+            if (f < a.window_frames && p < a.P) tile[j][tx] = src[static_cast<long long>(t0 + f) * a.P + p];
+        }
+        __syncthreads();
+        for (int j = ty; j < kTile; j += 8) {
+            const int p = p0 + j, f = f0 + tx;
+            if (p < a.P && f < a.window_frames) dst[p * a.window_frames + f] = tile[tx][j];
+        }
+    } else {
+        for (int j = ty; j < kTile; j += 8) {
+            const int p = p0 + j, f = f0 + tx;
+            if (p < a.P && f < a.window_frames) dst[p * a.window_frames + f] = src[static_cast<long long>(p) * a.total_frames + t0 + f];
+        }
+    }
+}
+
+__global__ void fill_i64_kernel(long long* dst, long long v, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = v;
+}
+
+// counts of the track: recording i has T_i = min(1 + n_i / hop, total_frames) frames (n_clip null: every recording has total_frames)
+__global__ void track_counts_kernel(int* counts, const long long* __restrict__ n_clip, int hop, int total_frames, int window_frames,
+                                    int stride_frames, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    long long t = total_frames;
+    if (n_clip) {
+        const long long nc = n_clip[i];
+        t = nc < 0 ? 0 : 1 + nc / hop;                                   // librosa center=True framing, as ake_cqt_num_frames
+        t = t < total_frames ? t : total_frames;
+    }
+    counts[i] = t < window_frames ? 0 : static_cast<int>((t - window_frames) / stride_frames + 1);
+}
+
+// The key-signature table (utils/key_signatures.py:19-42, metrics.KEY_SIGNATURE_MAP): circle of fifths Cb .. C# (15 rows), then six
+// enharmonic duplicates; major_tonic[k] is the pitch class of row k's major scale.
+struct KeyTable {
+    float row[21][12];
+    int major_tonic[21];
+};
+constexpr KeyTable make_key_table() {
+    KeyTable t{};
+    const int dup[6] = {9, 11, 10, 4, 3, 5};
+    for (int k = 0; k < 21; ++k) {
+        const int i = k < 15 ? k : dup[k - 15];
+        const int tonic = ((7 * (i - 7)) % 12 + 12) % 12;
+        t.major_tonic[k] = tonic;
+        for (int pc = 0; pc < 12; ++pc) {
+            const int d = ((pc - tonic) % 12 + 12) % 12;
+            t.row[k][pc] = (d == 0 || d == 2 || d == 4 || d == 5 || d == 7 || d == 9 || d == 11) ? 1.f : 0.f;
+        }
+    }
+    return t;
+}
+__constant__ const KeyTable kKeyTable = make_key_table();
+
+struct DecodeArgs {
+    const float* key;          // [rows][12]
+    const float* tonic;        // [rows][12]
+    const int* counts;         // [rows / windows] valid windows per recording, nullable (all valid)
+    int rows, windows;
+    int* key_id;
+    int* sig;
+    int* tonic_id;
+    float* confidence;
+};
+
+// One thread per row (a row is 24 floats in, 4 words out).
+__global__ __launch_bounds__(256) void decode_keys_kernel(DecodeArgs a) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.rows) return;
+    if (a.counts) {
+        const int rec = r / a.windows;
+        if (r - rec * a.windows >= a.counts[rec]) {
+            a.key_id[r] = -1; a.sig[r] = -1; a.tonic_id[r] = -1; a.confidence[r] = 0.f;
+            return;
+        }
+    }
+    float p[12], pp = 0.f;
+    for (int j = 0; j < 12; ++j) { p[j] = a.key[r * 12 + j]; pp += p[j] * p[j]; }
+    const float pn = fmaxf(sqrtf(pp), 1e-8f), tn = fmaxf(sqrtf(7.f), 1e-8f);
+    int sig = 0;
+    float best = -INFINITY;
+    for (int k = 0; k < 21; ++k) {
+        float dot = 0.f;
+        for (int j = 0; j < 12; ++j) dot += p[j] * kKeyTable.row[k][j];
+        const float sim = dot / (pn * tn);
+        if (sim > best) { best = sim; sig = k; }                          // strict: the first maximum
+    }
+    int tonic = 0;
+    float tb = a.tonic[r * 12];
+    for (int j = 1; j < 12; ++j) {
+        const float v = a.tonic[r * 12 + j];
+        if (v > tb) { tb = v; tonic = j; }
+    }
+    const int maj = kKeyTable.major_tonic[sig];
+    a.key_id[r] = tonic == maj ? 12 + tonic : tonic == (maj + 9) % 12 ? tonic : -1;
+    a.sig[r] = sig;
+    a.tonic_id[r] = tonic;
+    a.confidence[r] = best;
+}
+
+struct WinCarve {
+    float* mel;                // [chunk][P][window_frames]
+    long long* seq;            // [chunk]
+    void* net_ws;
+    size_t net_bytes;
+    size_t total;
+    int chunk;
+    long long windows;         // per recording
+};
+
+int carve_windows(const ake_pcnet* net, int recordings, int total_frames, int window_frames, int stride_frames, void* ws, WinCarve* wc) {
+    AKE_REQUIRE(net, AKE_ERR_INVALID, "forward_windows: null net");
+    AKE_REQUIRE(ake::pcnet_local_window(net) == 0, AKE_ERR_UNSUPPORTED,
+                "forward_windows: a --local net is not tracked (it has its own per-frame forward, ake_pcnet_forward_local_f32, and its rows are not time frames)");
+    AKE_REQUIRE(recordings > 0 && window_frames > 0 && stride_frames > 0 && total_frames >= window_frames, AKE_ERR_INVALID,
+                "forward_windows: bad shape (%d recordings, %d frames, window %d, stride %d)", recordings, total_frames, window_frames, stride_frames);
+    wc->windows = (total_frames - window_frames) / stride_frames + 1;
+    const long long total = wc->windows * recordings;
+    AKE_REQUIRE(total <= (1ll << 30), AKE_ERR_INVALID, "forward_windows: %lld windows", total);
+    wc->chunk = static_cast<int>(std::min<long long>(total, kTrackChunk));
+    const int P = ake_pcnet_pitches(net);
+    ake::Carver c(ws, 0);
+    wc->mel = c.take<float>(static_cast<size_t>(wc->chunk) * P * window_frames);
+    wc->seq = c.take<long long>(wc->chunk);
+    wc->net_bytes = ake_pcnet_workspace_bytes(net, wc->chunk, window_frames);
+    AKE_REQUIRE(wc->net_bytes > 0, AKE_ERR_INVALID, "forward_windows: the net has no workspace for %d x %d frames", wc->chunk, window_frames);
+    wc->net_ws = c.take<char>(wc->net_bytes);
+    wc->total = ake::align_up(c.off, 256);
+    return AKE_OK;
+}
+
+struct TrackCarve {
+    float* mel;
+    void* cqt_ws;
+    size_t cqt_bytes;
+    void* win_ws;
+    size_t win_bytes;
+    size_t total;
+    int T;
+};
+
+int carve_track(const ake_cqt_plan* plan, const ake_pcnet* net, int recordings, int64_t n, int window_frames, int stride_frames, void* ws,
+                TrackCarve* tc) {
+    AKE_REQUIRE(plan && net, AKE_ERR_INVALID, "track: null argument");
+    AKE_REQUIRE(recordings > 0 && n > 0, AKE_ERR_INVALID, "track: bad recordings / n_samples");
+    const int64_t T = ake_cqt_num_frames(plan, n);
+    AKE_REQUIRE(T > 0 && T < (1ll << 30), AKE_ERR_INVALID, "track: bad n_samples");
+    const int n_bins = ake_cqt_plan_n_bins(plan);
+    AKE_REQUIRE(n_bins == ake_pcnet_pitches(net), AKE_ERR_INVALID, "track: CQT has %d bins but the net expects %d pitches", n_bins,
+                ake_pcnet_pitches(net));
+    tc->T = static_cast<int>(T);
+    WinCarve wc;
+    int rc = carve_windows(net, recordings, tc->T, window_frames, stride_frames, nullptr, &wc);
+    if (rc) return rc;
+    ake::Carver c(ws, 0);
+    tc->mel = c.take<float>(static_cast<size_t>(recordings) * n_bins * T);
+    tc->cqt_bytes = ake_cqt_workspace_bytes(plan, recordings, n);
+    tc->cqt_ws = c.take<char>(tc->cqt_bytes);
+    tc->win_bytes = wc.total;
+    tc->win_ws = c.take<char>(tc->win_bytes);
+    tc->total = ake::align_up(c.off, 256);
+    return AKE_OK;
+}
+
+int track_impl(const ake_cqt_plan* plan, const ake_pcnet* net, const float* audio_dev, int recordings, int64_t n_samples,
+               int64_t audio_stride, const int64_t* n_clip_dev, int window_frames, int stride_frames, float* key_out, float* tonic_out,
+               float* genre_out, int32_t* key_id, int32_t* sig, int32_t* tonic_id, float* confidence, int32_t* counts, void* ws,
+               size_t ws_bytes, ake_stream_t stream) {
+    AKE_REQUIRE(audio_dev && key_out && tonic_out && key_id && sig && tonic_id && confidence && counts, AKE_ERR_INVALID, "track: null argument");
+    TrackCarve tc;
+    int rc = carve_track(plan, net, recordings, n_samples, window_frames, stride_frames, ws, &tc);
+    if (rc) return rc;
+    AKE_REQUIRE(ws && ws_bytes >= tc.total, AKE_ERR_WORKSPACE, "track: workspace %zu < %zu bytes", ws_bytes, tc.total);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // equal-length recordings: the CQT stays in the filter bank's own [recording][frame][bin] order (no transpose pass; the gather
+    // transposes the windows it copies anyway).  Ragged recordings: [recording][bin][frame], frames behind a recording's end are zeros.
+    const bool fm = !n_clip_dev && ake_cqt_frames_major_supported(plan);
+    rc = n_clip_dev ? ake_cqt_logmag_ragged_f32(plan, audio_dev, recordings, n_samples, audio_stride, n_clip_dev, tc.mel, tc.T, tc.cqt_ws, tc.cqt_bytes, stream)
+         : fm       ? ake_cqt_logmag_frames_major_f32(plan, audio_dev, recordings, n_samples, audio_stride, tc.mel, tc.cqt_ws, tc.cqt_bytes, stream)
+                    : ake_cqt_logmag_f32(plan, audio_dev, recordings, n_samples, audio_stride, tc.mel, tc.T, tc.cqt_ws, tc.cqt_bytes, stream);
+    if (rc) return rc;
+    rc = ake_pcnet_forward_windows_f32(net, tc.mel, fm ? 1 : 0, recordings, tc.T, window_frames, stride_frames, key_out, tonic_out, genre_out,
+                                       tc.win_ws, tc.win_bytes, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(track_counts_kernel, dim3((recordings + 255) / 256), dim3(256), 0, s, counts, reinterpret_cast<const long long*>(n_clip_dev),
+                       ake_cqt_plan_hop(plan), tc.T, window_frames, stride_frames, recordings);
+    AKE_HIP_CHECK(hipGetLastError());
+    const int windows = (tc.T - window_frames) / stride_frames + 1;
+    return ake_decode_keys_f32(key_out, tonic_out, recordings * windows, n_clip_dev ? counts : nullptr, windows, key_id, sig, tonic_id, confidence,
+                               stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t ake_pcnet_forward_windows_workspace_bytes(const ake_pcnet* net, int recordings, int total_frames, int window_frames, int stride_frames) {
+    WinCarve wc;
+    if (carve_windows(net, recordings, total_frames, window_frames, stride_frames, nullptr, &wc) != AKE_OK) return 0;
+    return wc.total;
+}
+
+int ake_pcnet_forward_windows_f32(const ake_pcnet* net, const float* mel_dev, int frames_major, int recordings, int total_frames,
+                                  int window_frames, int stride_frames, float* key_out_dev, float* tonic_out_dev, float* genre_out_dev,
+                                  void* workspace, size_t workspace_bytes, ake_stream_t stream) {
+    AKE_REQUIRE(mel_dev && key_out_dev && tonic_out_dev, AKE_ERR_INVALID, "forward_windows: null argument");
+    WinCarve wc;
+    int rc = carve_windows(net, recordings, total_frames, window_frames, stride_frames, workspace, &wc);
+    if (rc) return rc;
+    AKE_REQUIRE(workspace && workspace_bytes >= wc.total, AKE_ERR_WORKSPACE, "forward_windows: workspace %zu < %zu bytes", workspace_bytes, wc.total);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int P = ake_pcnet_pitches(net);
+    const long long total = wc.windows * recordings;
+    hipLaunchKernelGGL(fill_i64_kernel, dim3((wc.chunk + 255) / 256), dim3(256), 0, s, wc.seq, static_cast<long long>(window_frames), wc.chunk);
+    for (long long c0 = 0; c0 < total; c0 += wc.chunk) {
+        const int B = static_cast<int>(std::min<long long>(wc.chunk, total - c0));
+        GatherArgs ga{mel_dev, wc.mel, P, total_frames, window_frames, stride_frames, static_cast<int>(wc.windows), static_cast<int>(c0)};
+        const dim3 grid((P + kTile - 1) / kTile, (window_frames + kTile - 1) / kTile, B);
+        {
+            ake::ProfScope ps("window_gather_kernel", s);
+            if (frames_major) hipLaunchKernelGGL(window_gather_kernel<true>, grid, dim3(256), 0, s, ga);
+            else hipLaunchKernelGGL(window_gather_kernel<false>, grid, dim3(256), 0, s, ga);
+        }
+        AKE_HIP_CHECK(hipGetLastError());
+        rc = ake_pcnet_forward_f32(net, wc.mel, B, window_frames, reinterpret_cast<const int64_t*>(wc.seq), key_out_dev + c0 * 12, tonic_out_dev + c0 * 12,
+                                   genre_out_dev ? genre_out_dev + c0 * 11 : nullptr, wc.net_ws, wc.net_bytes, stream);
+        if (rc) return rc;
+    }
+    return AKE_OK;
+}
+
+int ake_decode_keys_f32(const float* key_dev, const float* tonic_dev, int rows, const int32_t* counts_dev, int windows_per_recording,
+                        int32_t* key_id_dev, int32_t* sig_dev, int32_t* tonic_id_dev, float* confidence_dev, ake_stream_t stream) {
+    AKE_REQUIRE(key_dev && tonic_dev && key_id_dev && sig_dev && tonic_id_dev && confidence_dev, AKE_ERR_INVALID, "decode_keys: null argument");
+    AKE_REQUIRE(rows >= 0 && (!counts_dev || (windows_per_recording > 0 && rows % windows_per_recording == 0)), AKE_ERR_INVALID,
+                "decode_keys: %d rows do not divide into recordings of %d windows", rows, windows_per_recording);
+    if (rows == 0) return AKE_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DecodeArgs a{key_dev, tonic_dev, counts_dev, rows, counts_dev ? windows_per_recording : 1, key_id_dev, sig_dev, tonic_id_dev, confidence_dev};
+    {
+        ake::ProfScope ps("decode_keys_kernel", s);
+        hipLaunchKernelGGL(decode_keys_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, a);
+    }
+    AKE_HIP_CHECK(hipGetLastError());
+    return AKE_OK;
+}
+
+size_t ake_pipeline_track_workspace_bytes(const ake_cqt_plan* plan, const ake_pcnet* net, int recordings, int64_t n_samples, int window_frames,
+                                          int stride_frames) {
+    TrackCarve tc;
+    if (carve_track(plan, net, recordings, n_samples, window_frames, stride_frames, nullptr, &tc) != AKE_OK) return 0;
+    return tc.total;
+}
+
+int ake_pipeline_track_f32(const ake_cqt_plan* plan, const ake_pcnet* net, const float* audio_dev, int recordings, int64_t n_samples,
+                           int64_t audio_stride, int window_frames, int stride_frames, float* key_out_dev, float* tonic_out_dev,
+                           float* genre_out_dev, int32_t* key_id_dev, int32_t* sig_dev, int32_t* tonic_id_dev, float* confidence_dev,
+                           int32_t* counts_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream) {
+    return track_impl(plan, net, audio_dev, recordings, n_samples, audio_stride, nullptr, window_frames, stride_frames, key_out_dev, tonic_out_dev,
+                      genre_out_dev, key_id_dev, sig_dev, tonic_id_dev, confidence_dev, counts_dev, workspace, workspace_bytes, stream);
+}
+
+int ake_pipeline_track_ragged_f32(const ake_cqt_plan* plan, const ake_pcnet* net, const float* audio_dev, int recordings, int64_t n_max,
+                                  int64_t audio_stride, const int64_t* n_samples_dev, int window_frames, int stride_frames, float* key_out_dev,
+                                  float* tonic_out_dev, float* genre_out_dev, int32_t* key_id_dev, int32_t* sig_dev, int32_t* tonic_id_dev,
+                                  float* confidence_dev, int32_t* counts_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream) {
+    AKE_REQUIRE(n_samples_dev, AKE_ERR_INVALID, "ake_pipeline_track_ragged_f32: null n_samples_dev");
+    return track_impl(plan, net, audio_dev, recordings, n_max, audio_stride, n_samples_dev, window_frames, stride_frames, key_out_dev, tonic_out_dev,
+                      genre_out_dev, key_id_dev, sig_dev, tonic_id_dev, confidence_dev, counts_dev, workspace, workspace_bytes, stream);
+}
+
+}  // extern "C"

@@ -34,6 +34,44 @@ def _device_table(dev, dtype):
     return _tables[key]
 
 
+# major tonic (pitch class) of every table row: the circle of fifths, then the duplicates' own rows
+MAJOR_TONIC = torch.tensor([(7 * (i - 7)) % 12 for i in list(range(15)) + [9, 11, 10, 4, 3, 5]], dtype=torch.int64)
+
+_PITCH_NAMES = ("C", "Db", "D", "Eb", "E", "F", "Gb", "G", "Ab", "A", "Bb", "B")
+# the project's 24-way key labels: 0-11 minor, 12-23 major, tonic = id mod 12 (KeyDataset.py:524-527; the same list as KeyDataset.SIGNATURE)
+KEY_NAMES = tuple(f"{n} minor" for n in _PITCH_NAMES) + tuple(f"{n} major" for n in _PITCH_NAMES)
+
+
+def decode_keys(key, tonic):
+    """(..., 12) key outputs (sigmoid) and (..., 12) tonic logits -> (key_id, sig, tonic_id, confidence), shaped like the leading dims.
+
+    The decode of ``ake_decode_keys_f32`` in torch ops, on whatever device the tensors live on: ``sig`` (0..20) is the first-maximum
+    cosine match over ``KEY_SIGNATURE_MAP`` with ``mirex_score``'s arithmetic and tie rule, ``confidence`` that cosine, ``tonic_id``
+    (0..11) the first maximum of the tonic logits, and ``key_id`` the 24-way label (``KEY_NAMES``): ``12 + tonic_id`` if the tonic is the
+    major tonic of row ``sig``, ``tonic_id`` if it is that tonic + 9 mod 12 (the relative minor), -1 if signature and tonic disagree.
+    ``key_id``, ``sig`` and ``tonic_id`` are int32."""
+    lead = key.shape[:-1]
+    k2, t2 = key.reshape(-1, 12), tonic.reshape(-1, 12)
+    # the cosines as sums over the 12 pitch classes in one order for every table row, so that the duplicate rows (0/12, 1/13, ...) get
+    # bit-identical values and the first of them wins (a matmul may block the 21 columns differently and break such ties either way)
+    table = _device_table(k2.device, k2.dtype)
+    eps = 1e-8
+    pn = k2.norm(dim=1, keepdim=True).clamp_min(eps)
+    tn = table.norm(dim=1, keepdim=True).clamp_min(eps)
+    sims = (k2[:, None, :] * table[None, :, :]).sum(dim=2) / (pn * tn.T)     # (B, 21)
+    conf = sims.max(dim=1).values
+    idx21 = torch.arange(table.shape[0], device=k2.device)[None, :].expand_as(sims)
+    sig = torch.where(sims == conf[:, None], idx21, torch.full_like(idx21, table.shape[0])).min(dim=1).values
+    # first maximum of the logits (torch.argmax does not promise which of equal maxima it returns)
+    is_max = t2 == t2.max(dim=1, keepdim=True).values
+    idx = torch.arange(12, device=t2.device)[None, :].expand_as(t2)
+    tonic_id = torch.where(is_max, idx, torch.full_like(idx, 12)).min(dim=1).values
+    maj = MAJOR_TONIC.to(sig.device)[sig]
+    key_id = torch.where(tonic_id == maj, 12 + tonic_id, torch.where(tonic_id == (maj + 9) % 12, tonic_id, torch.full_like(tonic_id, -1)))
+    return (key_id.to(torch.int32).reshape(lead), sig.to(torch.int32).reshape(lead), tonic_id.to(torch.int32).reshape(lead),
+            conf.reshape(lead))
+
+
 def mirex_score(key_labels, key_preds, tonic_labels, tonic_preds, key_signature_id):
     """-> (mirex, correct, fifths, relative, parallel, other, accuracy), float32 scalars.
 

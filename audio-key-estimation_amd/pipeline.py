@@ -7,12 +7,74 @@ to back on one stream with no host round trip (what ``DatasetLoader.get_all`` ->
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
+
 import torch
 
-from . import _lib
+from . import _lib, metrics
 from .audio import get_resampler
 from .cqt import WHOLE_SONG_FRAMES, CQTPlan, get_any_hop_plan, hop_for, hop_for_window
 from .models import PitchClassNet
+
+
+def track_window_frames(window_samples: int, hop: int) -> int:
+    """Frames of one tracking window: the framing of a clip of that many samples (``ake_cqt_num_frames``)."""
+    return 1 + int(window_samples) // int(hop)
+
+
+def track_stride_frames(stride_seconds: float, frames: int) -> int:
+    """Frames between the starts of consecutive windows (``frames`` = the estimator's frames per second)."""
+    return max(1, int(round(float(stride_seconds) * frames)))
+
+
+def track_counts(total_frames, window_frames: int, stride_frames: int):
+    """Windows of a recording of ``total_frames`` frames (int or integer tensor): 0 if it is shorter than one window."""
+    if isinstance(total_frames, torch.Tensor):
+        n = torch.div(total_frames - window_frames, stride_frames, rounding_mode="floor") + 1
+        return torch.where(total_frames < window_frames, torch.zeros_like(n), n)
+    return 0 if total_frames < window_frames else (int(total_frames) - window_frames) // stride_frames + 1
+
+
+@dataclass
+class KeyTrack:
+    """The key of R recordings over time (``KeyEstimator.track``), W windows each; everything but ``times`` lives on the device.
+
+    ``key`` (R, W, 12) sigmoid pitch-class membership, ``tonic`` (R, W, 12) logits, ``genre`` (R, W, 11) or None: the net's outputs per
+    window.  ``key_id``, ``sig``, ``tonic_id`` int32 (R, W) and ``confidence`` (R, W): the decode of ``metrics.decode_keys``.  ``counts``
+    int32 (R,): windows of each recording; windows at index >= its count hold -1.  ``times`` (W,) float64 on the host: window centres
+    in seconds."""
+    key: torch.Tensor
+    tonic: torch.Tensor
+    genre: torch.Tensor | None
+    key_id: torch.Tensor
+    sig: torch.Tensor
+    tonic_id: torch.Tensor
+    confidence: torch.Tensor
+    counts: torch.Tensor
+    times: torch.Tensor
+    window_seconds: float = 0.0
+    stride_seconds: float = 0.0
+
+    def _tensors(self):
+        return (self.key, self.tonic, self.genre, self.key_id, self.sig, self.tonic_id, self.confidence, self.counts)
+
+    def segments(self, recording: int):
+        """Run-length encoding of ``key_id[recording]`` on the host -> list of ``(start_s, end_s, key_id, name)``.  A window stands for
+        the stride around its centre; the first segment starts at 0 and the last ends with the last window.  ``name`` is
+        ``metrics.KEY_NAMES[key_id]`` ("A minor"), or "unknown" where signature and tonic disagree (-1)."""
+        n = int(self.counts[recording])
+        ids = self.key_id[recording, :n].cpu().tolist()
+        times = self.times[:n].tolist()
+        half_w, half_s = self.window_seconds / 2, self.stride_seconds / 2
+        out, a = [], 0
+        for b in range(n):
+            if b + 1 < n and ids[b + 1] == ids[a]:
+                continue
+            start = 0.0 if a == 0 else times[a] - half_s
+            end = times[b] + (half_w if b == n - 1 else half_s)
+            out.append((start, end, ids[a], metrics.KEY_NAMES[ids[a]] if ids[a] >= 0 else "unknown"))
+            a = b + 1
+        return out
 
 
 class KeyEstimator:
@@ -74,9 +136,13 @@ class KeyEstimator:
             rs = get_resampler(self.sample_rate if rate is None else int(rate), self.sample_rate, self.device)
             audio, len_out = rs(audio, channel=channel, lengths=lengths)
             lengths = len_out if lengths is not None else None
+        return self._issue(self._run_wrapped, audio, lengths)
+
+    def _issue(self, run, audio, lengths):
+        """``run(slot, audio, lengths)`` on the caller's stream (``streams`` == 1) or on the next side stream in turn."""
         slot = self._slots[self._turn]
         if self.streams == 1:
-            return self._run_wrapped(slot, audio, lengths)
+            return run(slot, audio, lengths)
         self._turn = (self._turn + 1) % self.streams
         with torch.cuda.device(self.device):
             if slot["stream"] is None:
@@ -84,14 +150,82 @@ class KeyEstimator:
             slot["stream"].wait_stream(torch.cuda.current_stream(self.device))      # the inputs were produced on the caller's stream
             cur = torch.cuda.current_stream(self.device)
             with torch.cuda.stream(slot["stream"]):
-                out = self._run_wrapped(slot, audio, lengths)
+                out = run(slot, audio, lengths)
             # the outputs were allocated on the side stream and will be read on the caller's: tell the allocator now (nothing to
             # remember until join(), nothing to drop when a caller never joins)
-            for t in out:
+            for t in (out._tensors() if isinstance(out, KeyTrack) else out):
                 if t is not None:
                     t.record_stream(cur)
             audio.record_stream(slot["stream"])
         return out
+
+    @torch.no_grad()
+    def track(self, audio: torch.Tensor, lengths: torch.Tensor | None = None, rate: int | None = None, channel: int = 0,
+              window_seconds: float = 15.0, stride_seconds: float = 5.0) -> KeyTrack:
+        """The key of long recordings over time: audio (R, n) or (R, C, n) float32 on the GPU -> ``KeyTrack``.
+
+        Every recording is transformed ONCE at the estimator's hop (``T = 1 + n // hop`` frames); the net then runs on sliding windows
+        of those frames -- ``window_frames = 1 + round(window_seconds * sample_rate) // hop`` frames each (76 for 15 s at 22.05 kHz and 5
+        frames per second), ``stride_frames = max(1, round(stride_seconds * frames))`` apart -- exactly as on a clip of that many frames
+        with ``seq_length = window_frames``, and every window's outputs are decoded to a key label on the device
+        (``metrics.decode_keys``).  Recording i has ``(T_i - window_frames) // stride_frames + 1`` windows (0 if it is shorter than one).
+        The one difference from cutting the audio into clips and calling the estimator on them: a frame near a window edge sees the
+        recording's real neighbouring audio, where a separately transformed clip sees zero padding.
+
+        ``lengths``, ``rate``, ``channel``, ``streams`` > 1 and ``join()`` behave as in ``__call__``.  Refused with a ``ValueError``:
+        ``frames=0`` estimators (one hop per song: there are no frames to slide over), ``wrap_mode="true_end"`` (a window has no padding
+        to wrap into) and ``--local`` nets (their own per-frame forward; its rows are not time frames)."""
+        if self.frames <= 0:
+            raise ValueError("track() needs a fixed frame rate: this estimator was built with frames=0 (whole-song mode)")
+        if self.wrap_mode == "true_end":
+            raise ValueError("track() runs every window unpadded; wrap_mode 'true_end' has no meaning here: build the estimator with 'dataset_max'")
+        if getattr(self.net, "local", False):
+            raise ValueError("track() slides a clip-level net over the recording: a --local net is not tracked "
+                             "(it has its own per-frame forward, and its rows are not time frames)")
+        self.net._sync_weights(self.device, for_eval=True)
+        if audio.dim() == 3 or (rate is not None and int(rate) != self.sample_rate):
+            rs = get_resampler(self.sample_rate if rate is None else int(rate), self.sample_rate, self.device)
+            audio, len_out = rs(audio, channel=channel, lengths=lengths)
+            lengths = len_out if lengths is not None else None
+        wf = track_window_frames(int(round(window_seconds * self.sample_rate)), self.plan.hop_length)
+        sf = track_stride_frames(stride_seconds, self.frames)
+        return self._issue(lambda slot, a, l: self._run_track(slot, a, l, wf, sf), audio, lengths)
+
+    def _run_track(self, slot, audio, lengths, wf, sf):
+        net, L, dev = self.net, _lib.lib(), self.device
+        audio = audio.to(device=dev, dtype=torch.float32)
+        if audio.stride(-1) != 1:
+            audio = audio.contiguous()
+        R, n = audio.shape
+        hop = self.plan.hop_length
+        W = track_counts(1 + n // hop, wf, sf)
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        key, tonic, genre = f32(R, W, 12), f32(R, W, 12), f32(R, W, 11) if net.genre else None
+        key_id, sig, tonic_id, conf, counts = i32(R, W), i32(R, W), i32(R, W), f32(R, W), i32(R)
+        times = (torch.arange(W, dtype=torch.float64) * sf + (wf - 1) / 2) * hop / self.sample_rate
+        track = KeyTrack(key, tonic, genre, key_id, sig, tonic_id, conf, counts, times, wf * hop / self.sample_rate, sf * hop / self.sample_rate)
+        if W == 0:                                                   # every recording is shorter than one window
+            counts.zero_()
+            return track
+        nbytes = L.ake_pipeline_track_workspace_bytes(self.plan.handle, net.handle, R, n, wf, sf)
+        if nbytes == 0:
+            _lib.check(-1, "ake_pipeline_track_workspace_bytes")
+        if slot["ws"] is None or slot["ws"].numel() < nbytes:
+            slot["ws"] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+        ws = slot["ws"]
+        with torch.cuda.device(dev):
+            outs = (key.data_ptr(), tonic.data_ptr(), genre.data_ptr() if genre is not None else None, key_id.data_ptr(), sig.data_ptr(),
+                    tonic_id.data_ptr(), conf.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+            if lengths is None:
+                _lib.check(L.ake_pipeline_track_f32(self.plan.handle, net.handle, audio.data_ptr(), R, n, audio.stride(0), wf, sf, *outs),
+                           "ake_pipeline_track_f32")
+            else:
+                lengths = torch.as_tensor(lengths).to(device=dev, dtype=torch.int64).contiguous()
+                assert lengths.shape == (R,)
+                _lib.check(L.ake_pipeline_track_ragged_f32(self.plan.handle, net.handle, audio.data_ptr(), R, n, audio.stride(0),
+                                                           lengths.data_ptr(), wf, sf, *outs), "ake_pipeline_track_ragged_f32")
+        return track
 
     def _run_wrapped(self, slot, audio, lengths):
         """wrap_mode "true_end": one unpadded call per distinct frame count (the clips of a group share T, so no frame is padding)."""

@@ -344,6 +344,55 @@ int ake_pipeline_forward_ragged_f32(const ake_cqt_plan* plan, const ake_pcnet* n
                                     ake_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Key tracking over a long recording (not in the reference, whose --local nets return rows that are not time frames, models.py:806-807):
+ * ONE CQT per recording, the clip-level net on sliding windows of its frames, and a decode of every window to a key label.
+ *   - A recording of n samples is transformed once at the plan's hop: T = 1 + n / hop frames (ake_cqt_num_frames).
+ *   - Window w is frames [w * stride_frames, w * stride_frames + window_frames) of the recording's own transform.  The net runs on it
+ *     exactly as on a clip of window_frames frames with seq_length = window_frames; time-circular convolutions wrap at the window's ends.
+ *   - Recording i has count_i = (T_i - window_frames) / stride_frames + 1 windows, 0 if T_i < window_frames.
+ *   - The one difference from cutting the audio into clips and transforming each: a frame near a window edge sees the recording's real
+ *     neighbouring audio where a separately transformed clip sees zero padding.  Intended.
+ * A --local net is refused (AKE_ERR_UNSUPPORTED): it has its own per-frame forward, and its rows are not time frames.
+ * ---------------------------------------------------------------------------------------- */
+/* The net on every window of `recordings` equally long transforms.  mel_dev: [recordings][total_frames][pitches] (frames_major != 0, as
+ * ake_cqt_logmag_frames_major_f32 leaves it) or [recordings][pitches][total_frames].  Outputs [recordings][windows][12 | 12 | 11] with
+ * windows = (total_frames - window_frames) / stride_frames + 1 (total_frames >= window_frames).  The windows are gathered into the
+ * [B][1][pitches][window_frames] tensor of ake_pcnet_forward_f32 and run 256 at a time, which is what the workspace query sizes: any
+ * architecture variant and precision runs, with the results of ake_pcnet_forward_f32 on the materialised windows, bit for bit. */
+size_t ake_pcnet_forward_windows_workspace_bytes(const ake_pcnet* net, int recordings, int total_frames, int window_frames, int stride_frames);
+int ake_pcnet_forward_windows_f32(const ake_pcnet* net, const float* mel_dev, int frames_major, int recordings, int total_frames,
+                                  int window_frames, int stride_frames, float* key_out_dev, float* tonic_out_dev, float* genre_out_dev,
+                                  void* workspace, size_t workspace_bytes, ake_stream_t stream);
+/* (key, tonic) rows -> key labels, one launch.  key_dev [rows][12] sigmoid outputs, tonic_dev [rows][12] logits.  Per row:
+ *   sig_dev        0..20: first-maximum cosine match of the key row over the 21-row key-signature table (utils/key_signatures.py:19-42),
+ *                  the arithmetic and tie rule of PitchClassNet.mirex_score (models.py:1065-1083; norms clamped at 1e-8), in float32;
+ *   tonic_id_dev   0..11: first maximum of the tonic logits;
+ *   confidence_dev that maximum cosine;
+ *   key_id_dev     the project's 24-way label (0-11 minor, 12-23 major, tonic = id mod 12; KeyDataset.py:524-527): 12 + tonic if tonic
+ *                  is the major tonic of table row sig, tonic if it is that tonic + 9 mod 12 (the relative minor), else -1
+ *                  (signature and tonic disagree).
+ * counts_dev (nullable, int32 [rows / windows_per_recording]): row r is window r % windows_per_recording of recording
+ * r / windows_per_recording; windows at index >= the recording's count get key_id = sig = tonic_id = -1 and confidence 0. */
+int ake_decode_keys_f32(const float* key_dev, const float* tonic_dev, int rows, const int32_t* counts_dev, int windows_per_recording,
+                        int32_t* key_id_dev, int32_t* sig_dev, int32_t* tonic_id_dev, float* confidence_dev, ake_stream_t stream);
+/* Waveforms -> track, on one stream with no host round trip: the CQT of the whole recordings (frames-major where the plan can), the
+ * windows forward, the decode.  With W = (T - window_frames) / stride_frames + 1 and T = ake_cqt_num_frames(n_samples) >= window_frames:
+ * key / tonic / genre outputs [recordings][W][12 | 12 | 11], key_id / sig / tonic_id (int32) and confidence [recordings][W],
+ * counts_dev (int32) [recordings].  The ragged form takes row i's length n_samples_dev[i] <= n_max (int64, device) as
+ * ake_pipeline_forward_ragged_f32 does and derives count_i on the device; windows at index >= count_i decode to -1 (their key / tonic
+ * / genre rows are the net's outputs on frames that are partly the zero padding behind the recording's end). */
+size_t ake_pipeline_track_workspace_bytes(const ake_cqt_plan* plan, const ake_pcnet* net, int recordings, int64_t n_samples, int window_frames,
+                                          int stride_frames);
+int ake_pipeline_track_f32(const ake_cqt_plan* plan, const ake_pcnet* net, const float* audio_dev, int recordings, int64_t n_samples,
+                           int64_t audio_stride, int window_frames, int stride_frames, float* key_out_dev, float* tonic_out_dev,
+                           float* genre_out_dev, int32_t* key_id_dev, int32_t* sig_dev, int32_t* tonic_id_dev, float* confidence_dev,
+                           int32_t* counts_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream);
+int ake_pipeline_track_ragged_f32(const ake_cqt_plan* plan, const ake_pcnet* net, const float* audio_dev, int recordings, int64_t n_max,
+                                  int64_t audio_stride, const int64_t* n_samples_dev, int window_frames, int stride_frames, float* key_out_dev,
+                                  float* tonic_out_dev, float* genre_out_dev, int32_t* key_id_dev, int32_t* sig_dev, int32_t* tonic_id_dev,
+                                  float* confidence_dev, int32_t* counts_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel timing with hipEvents recorded on the launch stream (bench.py roofline leg).
  * ---------------------------------------------------------------------------------------- */
 int ake_prof_enable(const char* name_filter /* substring, NULL or "" = all */, int on);

@@ -1,0 +1,103 @@
+"""Key tracking over long recordings: KeyEstimator.track against the clip-wise route -> one JSON line.
+
+  workload : 8 recordings x 5 min at 22.05 kHz (white noise: neither side's cost depends on the content), 15 s windows,
+             strides of 15 s, 5 s and 1 s
+  A        : est.track(audio, stride_seconds=s) -- one CQT per recording, the net on gathered windows of its frames, the decode kernel
+  B        : the clip-wise route: the overlapping windows cut with unfold(...).contiguous() on the device (timed), KeyEstimator.__call__
+             on them in batches of 256 clips (the benchmarked shape, which takes the frames-major path), metrics.decode_keys
+
+Both sides run in this process, hipEvent-timed (torch.cuda.Event), warm, median of --reps runs each; per-kernel times from one run of each
+under the library's kernel timer.  max_abs_diff is for information: A and B differ at window edges by design (A's edge frames see the
+recording's neighbouring audio, B's see zero padding).  Usage: python tools/track_bench.py [--reps 30]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+from argparse import Namespace
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import ake_amd  # noqa: E402
+from ake_amd import metrics  # noqa: E402
+
+SR, DEV = 22050, "cuda:0"
+
+
+def timed(fn, reps, warmup=3):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return statistics.median(ms)
+
+
+def kernels(fn):
+    ake_amd._lib.prof_enable("", True)
+    fn()
+    res = {k: round(v[0], 4) for k, v in ake_amd._lib.prof_results().items()}
+    ake_amd._lib.prof_enable("", False)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--recordings", type=int, default=8)
+    ap.add_argument("--minutes", type=float, default=5.0)
+    ap.add_argument("--strides", type=float, nargs="+", default=[15.0, 5.0, 1.0])
+    args = ap.parse_args()
+    torch.manual_seed(0)
+    gold = np.load(os.path.join(REPO, "tests", "golden", "pcnet_default.npz"))
+    sd = {k[3:]: torch.from_numpy(gold[k]) for k in gold.files if k.startswith("sd/")}
+    net = ake_amd.PitchClassNet(288, 12, 2, 7, Namespace(genre=True))
+    net.load_state_dict(sd, strict=True)
+    net = net.to(DEV).eval()
+    est = ake_amd.KeyEstimator(net, SR, 5)
+    R, n = args.recordings, int(SR * 60 * args.minutes)
+    audio = torch.randn((R, n), device=DEV) * 0.3
+    win = 15 * SR
+    rows = []
+    for stride in args.strides:
+        step = int(round(stride * 5)) * est.plan.hop_length          # the stride track() uses, in samples
+
+        def clipwise():
+            clips = audio.unfold(1, win, step).reshape(-1, win).contiguous()
+            outs = [est(clips[c:c + 256]) for c in range(0, clips.shape[0], 256)]
+            key, tonic = torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
+            return key, tonic, metrics.decode_keys(key, tonic)
+
+        track = lambda: est.track(audio, stride_seconds=stride)     # noqa: E731
+        a_ms, b_ms = timed(track, args.reps), timed(clipwise, args.reps)
+        a_k, b_k = kernels(track), kernels(clipwise)
+        tr = track()
+        key_b, tonic_b, (key_id_b, _, _, _) = clipwise()
+        W = tr.key.shape[1]
+        assert key_b.shape[0] == R * W, (key_b.shape, R, W)
+        agree = float((tr.key_id.reshape(-1) == key_id_b).float().mean())
+        rows.append({"stride_s": stride, "windows": R * W, "track_ms": round(a_ms, 4), "clipwise_ms": round(b_ms, 4),
+                     "track_over_clipwise": round(a_ms / b_ms, 3),
+                     "max_abs_diff": {"key": float((tr.key.reshape(-1, 12) - key_b).abs().max()),
+                                      "tonic": float((tr.tonic.reshape(-1, 12) - tonic_b).abs().max())},
+                     "key_id_agreement": round(agree, 4), "track_kernels_ms": a_k, "clipwise_kernels_ms": b_k})
+        del tr, key_b, tonic_b
+        torch.cuda.empty_cache()
+    torch.cuda.synchronize()
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "reps": args.reps, "recordings": R, "minutes": args.minutes,
+                      "window_s": 15, "strides": rows}))
+
+
+if __name__ == "__main__":
+    main()
