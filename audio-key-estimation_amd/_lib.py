@@ -89,6 +89,10 @@ SYMBOLS = {
     "ake_pipeline_track_workspace_bytes": (_SZ, [_P, _P, _I, _I64, _I, _I]),
     "ake_pipeline_track_f32": (_I, [_P, _P, _P, _I, _I64, _I64, _I, _I] + [_P] * 9 + [_SZ, _P]),
     "ake_pipeline_track_ragged_f32": (_I, [_P, _P, _P, _I, _I64, _I64, _P, _I, _I] + [_P] * 9 + [_SZ, _P]),
+    "ake_key_emissions_f32": (_I, [_P, _P, _I, _P, _I, C.c_float, _P, _P]),
+    "ake_viterbi_keys_workspace_bytes": (_SZ, [_I, _I]),
+    "ake_viterbi_chunk_windows": (_I, []),
+    "ake_viterbi_keys_f32": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
     "ake_resampler_create": (_I, [_I, _I, C.POINTER(_P)]),
     "ake_resampler_destroy": (None, [_P]),
     "ake_resampler_out_len": (_I64, [_P, _I64]),

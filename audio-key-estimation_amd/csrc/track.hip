@@ -16,9 +16,15 @@
 // The windows reach the net through window_gather_kernel, which copies them out of either CQT layout into the [B][1][P][window_frames]
 // tensor ake_pcnet_forward_f32 takes, a chunk of kTrackChunk windows at a time (the chunk bounds the workspace and is the net's own
 // pitch-stream chunk, so nothing is chunked twice).
+//
+// A smooth track is two more launches on the track's outputs: key_emissions_kernel (every window's log-score of the 24 keys) and
+// viterbi_keys_kernel (the most likely path through them); further down, semantics in include/ake_hip.h.
 #include "common.h"
 
 #include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdint>
 
 namespace {
 
@@ -148,6 +154,200 @@ __global__ __launch_bounds__(256) void decode_keys_kernel(DecodeArgs a) {
     a.sig[r] = sig;
     a.tonic_id[r] = tonic;
     a.confidence[r] = best;
+}
+
+// ---- a smooth track: key emissions and a Viterbi decode over them (semantics: include/ake_hip.h; host restatement: metrics.py) ----
+constexpr int kKeys = 24;             // the 24-way label order: 0-11 minor, 12-23 major, tonic = id mod 12
+constexpr unsigned kMajorScale = 0xAB5;   // bit d set: d semitones above the major tonic is in the scale {0,2,4,5,7,9,11}
+constexpr int kVitBatch = 8;          // emission rows in flight ahead of the recurrence (a multiple of 4: one back-pointer word is 4 steps)
+constexpr int kVitChunk = 256;        // windows of back-pointers the backtrace stages into LDS at a time (a multiple of 4)
+
+struct EmisArgs {
+    const float* key;          // [rows][12]
+    const float* tonic;        // [rows][12]
+    const int* counts;         // nullable, as DecodeArgs
+    int rows, windows;
+    float scale;               // signature_weight / 12
+    float* emis;               // [rows][24]
+};
+
+// One thread per row, as decode_keys_kernel.  A row is 96 bytes in and 96 out, moved as float4s.  Only 12 distinct signature sums exist
+// (key k's scale is that of its relative major), so 12 are computed and the 24 outputs index them.
+__global__ __launch_bounds__(256) void key_emissions_kernel(EmisArgs a) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.rows) return;
+    float4* const out = reinterpret_cast<float4*>(a.emis + static_cast<size_t>(r) * kKeys);
+    if (a.counts) {
+        const int rec = r / a.windows;
+        if (r - rec * a.windows >= a.counts[rec]) {
+            for (int q = 0; q < 6; ++q) out[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+            return;
+        }
+    }
+    float p[12], t[12];
+    for (int q = 0; q < 3; ++q) {
+        const float4 pv = reinterpret_cast<const float4*>(a.key + static_cast<size_t>(r) * 12)[q];
+        const float4 tv = reinterpret_cast<const float4*>(a.tonic + static_cast<size_t>(r) * 12)[q];
+        p[4 * q] = pv.x; p[4 * q + 1] = pv.y; p[4 * q + 2] = pv.z; p[4 * q + 3] = pv.w;
+        t[4 * q] = tv.x; t[4 * q + 1] = tv.y; t[4 * q + 2] = tv.z; t[4 * q + 3] = tv.w;
+    }
+    float in[12], outside[12];                                           // the two Bernoulli terms, clamped as nn.BCELoss clamps them
+    for (int j = 0; j < 12; ++j) {
+        in[j] = fmaxf(logf(p[j]), -100.f);
+        outside[j] = fmaxf(log1pf(-p[j]), -100.f);
+    }
+    float tmax = t[0];
+    for (int j = 1; j < 12; ++j) tmax = fmaxf(tmax, t[j]);
+    float se = 0.f;
+    for (int j = 0; j < 12; ++j) se += expf(t[j] - tmax);
+    const float lse = tmax + logf(se);
+    float sig[12];                                                       // by major tonic
+    for (int m = 0; m < 12; ++m) {
+        float s = 0.f;
+        for (int j = 0; j < 12; ++j) s += (kMajorScale >> ((j - m + 12) % 12)) & 1 ? in[j] : outside[j];
+        sig[m] = s;
+    }
+    float e[kKeys];
+    for (int k = 0; k < kKeys; ++k) e[k] = (t[k % 12] - lse) + a.scale * sig[k >= 12 ? k - 12 : (k + 3) % 12];
+    for (int q = 0; q < 6; ++q) out[q] = make_float4(e[4 * q], e[4 * q + 1], e[4 * q + 2], e[4 * q + 3]);
+}
+
+struct VitArgs {
+    const float* emis;         // [recordings][windows][24]
+    const int* counts;         // nullable
+    const float* trans;        // [24][24], from i (row) to j
+    const float* prior;        // [24], nullable = zeros
+    int* path;                 // [recordings][windows]
+    unsigned* bp;              // [recordings][groups][24] words: byte b of word [g][j] = bp_{4g+b}[j]
+    int windows, groups;       // groups = ceil(windows / 4)
+};
+
+// f32 bits <-> a signed integer with the same order (its own inverse): the normalising maximum runs on these, because an integer
+// maximum folds into its DPP operand (v_max_i32_dpp) where a float one costs a move and a canonicalisation beside it.
+__device__ __forceinline__ int order_key(int bits) { return bits ^ ((bits >> 31) & 0x7fffffff); }
+
+template <int kCtrl>
+__device__ __forceinline__ int dpp_max(int x) {
+    const int y = __builtin_amdgcn_update_dpp(0, x, kCtrl, 0xf, 0xf, true);
+    return x > y ? x : y;
+}
+
+// max over the states of a wave whose 64 lanes are all active; `valid` marks the lanes that hold one (lanes 0..23 must).  Four
+// in-register butterfly steps inside each row of 16 lanes (xor 1, xor 2, half-row mirror, row mirror), then the two rows that hold
+// states meet through two v_readlane and scalar arithmetic: no LDS round trip.
+__device__ __forceinline__ float states_max(float x, bool valid) {
+    int k = valid ? order_key(__float_as_int(x)) : INT_MIN;
+    k = dpp_max<0xB1>(k);      // quad_perm [1,0,3,2]
+    k = dpp_max<0x4E>(k);      // quad_perm [2,3,0,1]
+    k = dpp_max<0x141>(k);     // row_half_mirror
+    k = dpp_max<0x140>(k);     // row_mirror
+    const int k0 = __builtin_amdgcn_readlane(k, 0), k1 = __builtin_amdgcn_readlane(k, 16);
+    return __int_as_float(order_key(k0 > k1 ? k0 : k1));
+}
+
+// One wave per recording.  A step is a latency chain on one wave, so what counts is its number of instructions:
+//   - lanes j and 32 + j (j < 24) share state j: the first takes the predecessors i = 0..11, the second i = 12..23, each with its half
+//     of column j of A in registers, so a lane adds, maximises (v_max3) and compare-selects over 12 candidates, not 24; the halves meet
+//     through two v_permlane32_swap (a tie goes to the lower half: the smallest i);
+//   - the step's 24 scores reach the lanes through a 96-byte LDS row, 48 bytes of it per lane as three 16-byte broadcast reads;
+//   - the normalising maximum is the butterfly above;
+//   - nothing else on the chain touches memory: emission rows are loaded kVitBatch steps ahead, and the back-pointers leave as one word
+//     per state every 4 steps.
+// The backtrace then walks the back-pointers in LDS, kVitChunk windows at a time, staged in and written out by all lanes.
+__global__ __launch_bounds__(64) void viterbi_keys_kernel(VitArgs a) {
+    __shared__ uint4 bp_lds[kVitChunk / 4 * kKeys / 4];
+    __shared__ int path_lds[kVitChunk];
+    __shared__ float4 d_lds[kKeys / 4];
+    const int r = blockIdx.x, lane = threadIdx.x, W = a.windows;
+    int n = a.counts ? a.counts[r] : W;
+    n = n < 0 ? 0 : n > W ? W : n;
+    constexpr int kHalf = kKeys / 2;
+    const int half = lane >> 5;
+    const bool own = (lane & 31) < kKeys, writer = lane < kKeys;
+    const int j = own ? lane & 31 : 0;                                   // (the other lanes run along on column 0; their scores are never read)
+    float A[kHalf];
+#pragma unroll
+    for (int i = 0; i < kHalf; ++i) A[i] = a.trans[(half * kHalf + i) * kKeys + j];
+    const float4* const dsrc = d_lds + half * (kHalf / 4);
+    const float* const e = a.emis + static_cast<size_t>(r) * W * kKeys + j;
+    unsigned* const bp = a.bp + static_cast<size_t>(r) * a.groups * kKeys + j;
+    float d = a.prior ? a.prior[j] : 0.f;
+    const int wl = n > 0 ? n - 1 : 0;                                    // the last row that is read (W >= 1)
+    float eb[kVitBatch];
+#pragma unroll
+    for (int k = 0; k < kVitBatch; ++k) eb[k] = e[static_cast<size_t>(k < wl ? k : wl) * kKeys];
+    unsigned word = 0;
+    for (int w0 = 0; w0 < n; w0 += kVitBatch) {
+        float en[kVitBatch];                                             // the next batch: in flight while this one is consumed
+#pragma unroll
+        for (int k = 0; k < kVitBatch; ++k) {
+            const int w = w0 + kVitBatch + k;                            // (clamped, not branched around: the loads stay one straight batch)
+            en[k] = e[static_cast<size_t>(w < wl ? w : wl) * kKeys];
+        }
+#pragma unroll
+        for (int k = 0; k < kVitBatch; ++k) {
+            const int w = w0 + k;
+            if (w >= n) break;                                           // wave-uniform: all 64 lanes stay active for the cross-lane steps
+            float m = d;                                                 // w == 0: the prior
+            unsigned arg = 0;
+            if (w > 0) {
+                if (writer) reinterpret_cast<float*>(d_lds)[lane] = d;
+                __syncthreads();                                         // (one wave: the wait for the LDS write, no more)
+                const float4 q0 = dsrc[0], q1 = dsrc[1], q2 = dsrc[2];
+                const float c[kHalf] = {q0.x + A[0], q0.y + A[1], q0.z + A[2],  q0.w + A[3],  q1.x + A[4], q1.y + A[5],
+                                        q1.z + A[6], q1.w + A[7], q2.x + A[8], q2.y + A[9], q2.z + A[10], q2.w + A[11]};
+                const float mh = fmaxf(fmaxf(fmaxf(fmaxf(c[0], c[1]), c[2]), fmaxf(fmaxf(c[3], c[4]), c[5])),
+                                       fmaxf(fmaxf(fmaxf(c[6], c[7]), c[8]), fmaxf(fmaxf(c[9], c[10]), c[11])));
+                unsigned ah = 0;
+#pragma unroll
+                for (int i = kHalf - 1; i >= 0; --i) ah = c[i] == mh ? static_cast<unsigned>(i) : ah;        // ends on the smallest i
+                // v_permlane32_swap(x, x): the lower half's x in every lane of the first result, the upper half's in the second
+                const auto ms = __builtin_amdgcn_permlane32_swap(__float_as_uint(mh), __float_as_uint(mh), false, false);
+                const auto as = __builtin_amdgcn_permlane32_swap(ah, ah, false, false);
+                const float m_lo = __uint_as_float(ms[0]), m_hi = __uint_as_float(ms[1]);
+                const bool upper = m_hi > m_lo;                          // strict: a tie goes to the smaller i
+                m = upper ? m_hi : m_lo;
+                arg = upper ? as[1] + kHalf : as[0];
+            }
+            const float raw = m + eb[k];
+            d = raw - states_max(raw, own);
+            word |= arg << (8 * (k & 3));                                // (w0 is a multiple of 4, so w & 3 == k & 3)
+            if ((k & 3) == 3) {
+                if (writer) bp[static_cast<size_t>(w >> 2) * kKeys] = word;
+                word = 0;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kVitBatch; ++k) eb[k] = en[k];
+    }
+    if ((n & 3) && writer) bp[static_cast<size_t>((n - 1) >> 2) * kKeys] = word;  // the last, partial word
+    __syncthreads();                                                     // the wave's own stores, before other lanes load them
+
+    // the last state: the smallest j attaining the maximum (0 after the normalisation, found the same way all the same)
+    int cur = 0;
+    if (n > 0) {
+        const float mx = states_max(d, own);
+        cur = __ffsll(static_cast<unsigned long long>(__ballot(writer && d == mx))) - 1;
+    }
+    int* const path = a.path + static_cast<size_t>(r) * W;
+    const unsigned char* const bytes = reinterpret_cast<const unsigned char*>(bp_lds);
+    for (int c0 = (W - 1) / kVitChunk * kVitChunk; c0 >= 0; c0 -= kVitChunk) {
+        const int len = W - c0 < kVitChunk ? W - c0 : kVitChunk;         // windows of this chunk
+        const int nv = n - c0 < len ? n - c0 : len;                      // of which decoded (<= 0: none)
+        if (nv > 0) {
+            const uint4* const src = reinterpret_cast<const uint4*>(a.bp + (static_cast<size_t>(r) * a.groups + c0 / 4) * kKeys);
+            const int quads = (nv + 3) / 4 * (kKeys / 4);                // 16-byte pieces: 6 per group of 4 windows
+            for (int x = lane; x < quads; x += 64) bp_lds[x] = src[x];
+            __syncthreads();
+            for (int w = nv - 1; w >= 0; --w) {                          // a chain of LDS reads, one per window; cur is wave-uniform
+                path_lds[w] = cur;
+                cur = bytes[(w >> 2) * (4 * kKeys) + cur * 4 + (w & 3)];
+            }
+            __syncthreads();
+        }
+        for (int x = lane; x < len; x += 64) path[c0 + x] = x < nv ? path_lds[x] : -1;
+        __syncthreads();                                                 // path_lds and bp_lds are reused by the chunk before
+    }
 }
 
 struct WinCarve {
@@ -292,6 +492,49 @@ int ake_decode_keys_f32(const float* key_dev, const float* tonic_dev, int rows, 
     {
         ake::ProfScope ps("decode_keys_kernel", s);
         hipLaunchKernelGGL(decode_keys_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, a);
+    }
+    AKE_HIP_CHECK(hipGetLastError());
+    return AKE_OK;
+}
+
+int ake_key_emissions_f32(const float* key_dev, const float* tonic_dev, int rows, const int32_t* counts_dev, int windows_per_recording,
+                          float signature_weight, float* emis_dev, ake_stream_t stream) {
+    AKE_REQUIRE(key_dev && tonic_dev && emis_dev, AKE_ERR_INVALID, "key_emissions: null argument");
+    AKE_REQUIRE(rows >= 0 && (!counts_dev || (windows_per_recording > 0 && rows % windows_per_recording == 0)), AKE_ERR_INVALID,
+                "key_emissions: %d rows do not divide into recordings of %d windows", rows, windows_per_recording);
+    AKE_REQUIRE(((reinterpret_cast<uintptr_t>(key_dev) | reinterpret_cast<uintptr_t>(tonic_dev) | reinterpret_cast<uintptr_t>(emis_dev)) & 15) == 0,
+                AKE_ERR_INVALID, "key_emissions: the buffers must be 16-byte aligned");
+    AKE_REQUIRE(std::isfinite(signature_weight), AKE_ERR_INVALID, "key_emissions: signature_weight is not finite");
+    if (rows == 0) return AKE_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    EmisArgs a{key_dev, tonic_dev, counts_dev, rows, counts_dev ? windows_per_recording : 1, signature_weight / 12.f, emis_dev};
+    {
+        ake::ProfScope ps("key_emissions_kernel", s);
+        hipLaunchKernelGGL(key_emissions_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, a);
+    }
+    AKE_HIP_CHECK(hipGetLastError());
+    return AKE_OK;
+}
+
+int ake_viterbi_chunk_windows(void) { return kVitChunk; }
+
+size_t ake_viterbi_keys_workspace_bytes(int recordings, int windows) {
+    if (recordings <= 0 || windows <= 0 || static_cast<long long>(recordings) * windows > (1ll << 30)) return 0;
+    return ake::align_up(static_cast<size_t>(recordings) * ((windows + 3) / 4) * kKeys * sizeof(unsigned), 256);
+}
+
+int ake_viterbi_keys_f32(const float* emis_dev, int recordings, int windows, const int32_t* counts_dev, const float* log_trans_dev,
+                         const float* log_prior_dev, int32_t* path_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream) {
+    AKE_REQUIRE(emis_dev && log_trans_dev && path_dev, AKE_ERR_INVALID, "viterbi_keys: null argument");
+    const size_t need = ake_viterbi_keys_workspace_bytes(recordings, windows);
+    AKE_REQUIRE(need > 0, AKE_ERR_INVALID, "viterbi_keys: bad shape (%d recordings, %d windows)", recordings, windows);
+    AKE_REQUIRE(workspace && workspace_bytes >= need, AKE_ERR_WORKSPACE, "viterbi_keys: workspace %zu < %zu bytes", workspace_bytes, need);
+    AKE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, AKE_ERR_INVALID, "viterbi_keys: the workspace must be 16-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    VitArgs a{emis_dev, counts_dev, log_trans_dev, log_prior_dev, path_dev, static_cast<unsigned*>(workspace), windows, (windows + 3) / 4};
+    {
+        ake::ProfScope ps("viterbi_keys_kernel", s);
+        hipLaunchKernelGGL(viterbi_keys_kernel, dim3(recordings), dim3(64), 0, s, a);
     }
     AKE_HIP_CHECK(hipGetLastError());
     return AKE_OK;

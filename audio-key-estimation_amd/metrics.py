@@ -107,3 +107,127 @@ def mirex_score(key_labels, key_preds, tonic_labels, tonic_preds, key_signature_
     f = lambda m: (m.sum().float() / n).float()
     mirex = (1.0 * correct.sum() + 0.5 * fifths.sum() + 0.3 * relative.sum() + 0.2 * parallel.sum()).float() / n
     return mirex.float(), f(correct), f(fifths), f(relative), f(parallel), f(other), f(full)
+
+
+# ---- a smooth key track: per-window log-scores of the 24 keys and a first-order Viterbi decode (ake_key_emissions_f32 / ake_viterbi_keys_f32) ----
+
+_MAJOR_SCALE = (0, 2, 4, 5, 7, 9, 11)
+# the major tonic whose scale key k uses (k in KEY_NAMES order): its own for a major key, tonic + 3 for a minor one
+KEY_MAJOR_TONIC = tuple(k - 12 if k >= 12 else (k + 3) % 12 for k in range(24))
+# S_k: (24, 12), 1 where pitch class j belongs to key k's scale
+KEY_SCALES = torch.tensor([[1.0 if (j - m) % 12 in _MAJOR_SCALE else 0.0 for j in range(12)] for m in KEY_MAJOR_TONIC], dtype=torch.float64)
+
+
+def _behind_count(counts, R, W, device):
+    """(R, W) bool: window w of recording r lies at or behind counts[r]."""
+    counts = torch.as_tensor(counts, device=device).to(torch.int64).reshape(R)
+    return torch.arange(W, device=device)[None, :] >= counts[:, None]
+
+
+def key_emissions(key, tonic, signature_weight=1.0, counts=None):
+    """(..., 12) key outputs (sigmoid memberships) and (..., 12) tonic logits -> (..., 24) log-scores of the 24 keys (``KEY_NAMES`` order).
+
+    The arithmetic of ``ake_key_emissions_f32`` in torch ops, in the tensors' dtype (float64 inputs give the test model).  The key head is
+    trained with BCE and the tonic head with cross-entropy, so with p = key and S_k the scale of key k (``KEY_SCALES``)::
+
+        e[k] = log_softmax(tonic)[k mod 12] + signature_weight / 12 * sum_j (S_k[j] * max(log p_j, -100) + (1 - S_k[j]) * max(log1p(-p_j), -100))
+
+    (-100 is ``nn.BCELoss``'s clamp).  ``counts`` (R,) with inputs shaped (R, W, 12): windows at index >= ``counts[r]`` get zeros."""
+    inside = torch.log(key).clamp_min(-100.0)
+    outside = torch.log1p(-key).clamp_min(-100.0)
+    S = KEY_SCALES.to(device=key.device, dtype=key.dtype)
+    sig = (S * inside[..., None, :] + (1.0 - S) * outside[..., None, :]).sum(dim=-1)          # (..., 24)
+    ls = torch.log_softmax(tonic, dim=-1)
+    e = torch.cat([ls, ls], dim=-1) + (float(signature_weight) / 12.0) * sig
+    if counts is not None:
+        if key.dim() != 3:
+            raise ValueError("key_emissions: counts needs inputs shaped (R, W, 12)")
+        e = torch.where(_behind_count(counts, key.shape[0], key.shape[1], key.device)[..., None], torch.zeros_like(e), e)
+    return e
+
+
+def _check_finite(name, t):
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError(f"{name} must be finite: write a forbidden transition as a large negative number (say -1e4), not as -inf "
+                         "(the recurrence subtracts each step's maximum, and max - max of infinities is NaN)")
+
+
+def viterbi_keys(emissions, log_trans, log_prior=None, counts=None):
+    """The most likely key path through (R, W, 24) or (W, 24) ``emissions`` -> int32 (R, W) or (W,).
+
+    ``log_trans`` (24, 24): log-probability of moving from key i (row) to key j; ``log_prior`` (24,), default zeros; ``counts`` (R,):
+    recording r has ``counts[r]`` windows (clamped to 0..W), the path holds -1 behind them.  The recurrence of ``ake_viterbi_keys_f32``,
+    operation for operation, in the emissions' dtype -- additions, subtractions and comparisons only, so the float32 run on the host is
+    bit-identical to the kernel's::
+
+        d_0[j] = prior[j] + e[0][j]
+        m[j]   = max_i (d_{w-1}[i] + A[i][j]),  bp_w[j] = the smallest i that attains it,  d_w[j] = m[j] + e[w][j]
+        d_w[j] -= max_j d_w[j]                  (every step, w = 0 included)
+
+    The last state is the smallest j attaining max d; the path follows bp backwards."""
+    single = emissions.dim() == 2
+    e = emissions[None] if single else emissions
+    if e.dim() != 3 or e.shape[2] != 24:
+        raise ValueError(f"viterbi_keys: emissions must be (R, W, 24) or (W, 24), got {tuple(emissions.shape)}")
+    R, W, K = e.shape
+    dev = e.device
+    A = torch.as_tensor(log_trans).to(device=dev, dtype=e.dtype)
+    if A.shape != (K, K):
+        raise ValueError(f"viterbi_keys: log_trans must be (24, 24), got {tuple(A.shape)}")
+    prior = torch.zeros(K, device=dev, dtype=e.dtype) if log_prior is None else torch.as_tensor(log_prior).to(device=dev, dtype=e.dtype).reshape(K)
+    _check_finite("log_trans", A)
+    _check_finite("log_prior", prior)
+    n = torch.full((R,), W, device=dev, dtype=torch.int64) if counts is None else \
+        torch.as_tensor(counts, device=dev).to(torch.int64).reshape(R).clamp(0, W)
+    path = torch.full((R, W), -1, device=dev, dtype=torch.int64)
+    idx = torch.arange(K, device=dev)
+    none = torch.full((), K, device=dev, dtype=torch.int64)
+    d = torch.zeros((R, K), device=dev, dtype=e.dtype)
+    last = torch.zeros((R,), device=dev, dtype=torch.int64)
+    bps = torch.zeros((W, R, K), device=dev, dtype=torch.int64)
+    for w in range(W):
+        if w == 0:
+            raw = prior[None, :] + e[:, 0]
+        else:
+            cand = d[:, :, None] + A[None, :, :]                                    # (R, from i, to j)
+            m = cand.max(dim=1).values
+            bps[w] = torch.where(cand == m[:, None, :], idx[None, :, None], none).min(dim=1).values
+            raw = m + e[:, w]
+        mx = raw.max(dim=1, keepdim=True).values
+        dn = raw - mx
+        d = torch.where((w < n)[:, None], dn, d)
+        first = torch.where(dn == dn.max(dim=1, keepdim=True).values, idx[None, :], none).min(dim=1).values
+        last = torch.where(n == w + 1, first, last)
+    cur = last
+    for w in range(W - 1, -1, -1):
+        live = w < n
+        path[:, w] = torch.where(live, cur, torch.full_like(cur, -1))
+        if w > 0:
+            cur = torch.where(live, bps[w].gather(1, cur[:, None])[:, 0], cur)
+    path = path.to(torch.int32)
+    return path[0] if single else path
+
+
+def key_transition_log(stay, fifth=0.5, relative=0.3, parallel=0.2, other=0.02):
+    """(24, 24) float64 log transition matrix between the 24 keys (``KEY_NAMES`` order), from key i (row) to key j.
+
+    The diagonal is ``stay``.  The off-diagonal weights of a row are the MIREX weights ``mirex_score`` uses -- ``fifth``: same mode, tonic
+    +-7; ``relative``: major t <-> minor t + 9; ``parallel``: same tonic, other mode; ``other``: every other key -- normalised to
+    ``1 - stay``, so every row sums to 1 before the logarithm.  The matrix is symmetric."""
+    stay = float(stay)
+    if not 0.0 < stay < 1.0:
+        raise ValueError(f"key_transition_log: stay must lie strictly between 0 and 1, got {stay}")
+    if min(fifth, relative, parallel, other) <= 0.0:
+        raise ValueError("key_transition_log: the weights must be positive (a zero weight is a forbidden transition, whose logarithm is "
+                         "-inf: use a small positive weight instead)")
+    Wt = torch.full((24, 24), float(other), dtype=torch.float64)
+    for i in range(24):
+        major, t = divmod(i, 12)
+        Wt[i, 12 * major + (t + 7) % 12] = Wt[i, 12 * major + (t + 5) % 12] = float(fifth)
+        Wt[i, (t + 9) % 12 if major else 12 + (t + 3) % 12] = float(relative)
+        Wt[i, 12 * (1 - major) + t] = float(parallel)
+        Wt[i, i] = 0.0
+    # every row holds the same weights (2 fifths, 1 relative, 1 parallel, 19 others): one scale for all, so P is symmetric to the bit
+    P = Wt * ((1.0 - stay) / (2.0 * float(fifth) + float(relative) + float(parallel) + 19.0 * float(other)))
+    P[torch.arange(24), torch.arange(24)] = stay
+    return torch.log(P)

@@ -9,6 +9,8 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 
+import math
+
 import torch
 
 from . import _lib, metrics
@@ -42,7 +44,11 @@ class KeyTrack:
     ``key`` (R, W, 12) sigmoid pitch-class membership, ``tonic`` (R, W, 12) logits, ``genre`` (R, W, 11) or None: the net's outputs per
     window.  ``key_id``, ``sig``, ``tonic_id`` int32 (R, W) and ``confidence`` (R, W): the decode of ``metrics.decode_keys``.  ``counts``
     int32 (R,): windows of each recording; windows at index >= its count hold -1.  ``times`` (W,) float64 on the host: window centres
-    in seconds."""
+    in seconds.
+
+    ``track(smooth=True)`` adds ``emissions`` (R, W, 24), every window's log-score of the 24 keys (``metrics.key_emissions``; zeros behind
+    a recording's count), and ``smooth_key_id`` int32 (R, W), the Viterbi path through them (``metrics.viterbi_keys``): always a key
+    0..23 below the count, -1 behind it.  Both are None otherwise."""
     key: torch.Tensor
     tonic: torch.Tensor
     genre: torch.Tensor | None
@@ -54,16 +60,28 @@ class KeyTrack:
     times: torch.Tensor
     window_seconds: float = 0.0
     stride_seconds: float = 0.0
+    emissions: torch.Tensor | None = None
+    smooth_key_id: torch.Tensor | None = None
 
     def _tensors(self):
-        return (self.key, self.tonic, self.genre, self.key_id, self.sig, self.tonic_id, self.confidence, self.counts)
+        """Every device tensor of the track; the two of a smooth track only when it is one (a plain track lists what it always did)."""
+        plain = (self.key, self.tonic, self.genre, self.key_id, self.sig, self.tonic_id, self.confidence, self.counts)
+        if self.emissions is None and self.smooth_key_id is None:
+            return plain
+        return plain + (self.emissions, self.smooth_key_id)
 
-    def segments(self, recording: int):
-        """Run-length encoding of ``key_id[recording]`` on the host -> list of ``(start_s, end_s, key_id, name)``.  A window stands for
-        the stride around its centre; the first segment starts at 0 and the last ends with the last window.  ``name`` is
-        ``metrics.KEY_NAMES[key_id]`` ("A minor"), or "unknown" where signature and tonic disagree (-1)."""
+    def segments(self, recording: int, smoothed: bool | None = None):
+        """Run-length encoding of one recording's key labels on the host -> list of ``(start_s, end_s, key_id, name)``.  A window stands
+        for the stride around its centre; the first segment starts at 0 and the last ends with the last window.  ``name`` is
+        ``metrics.KEY_NAMES[key_id]`` ("A minor"), or "unknown" where signature and tonic disagree (-1).
+
+        ``smoothed``: True reads ``smooth_key_id`` (``ValueError`` if the track has none), False ``key_id``; None (default) the smoothed
+        path when the track has one, ``key_id`` otherwise."""
+        if smoothed and self.smooth_key_id is None:
+            raise ValueError("segments(smoothed=True): this track has no smoothed path; make it with track(..., smooth=True)")
+        source = self.smooth_key_id if (smoothed or (smoothed is None and self.smooth_key_id is not None)) else self.key_id
         n = int(self.counts[recording])
-        ids = self.key_id[recording, :n].cpu().tolist()
+        ids = source[recording, :n].cpu().tolist()
         times = self.times[:n].tolist()
         half_w, half_s = self.window_seconds / 2, self.stride_seconds / 2
         out, a = [], 0
@@ -112,6 +130,7 @@ class KeyEstimator:
         self.streams = max(1, int(streams))
         self._slots = [{"ws": None, "stream": None} for _ in range(self.streams)]
         self._turn = 0
+        self._transitions = {}                                       # track(smooth=True): log transition matrices on the device
 
     def join(self):
         """Make the caller's current stream wait for every call issued so far (``streams`` > 1; a no-op otherwise)."""
@@ -161,7 +180,8 @@ class KeyEstimator:
 
     @torch.no_grad()
     def track(self, audio: torch.Tensor, lengths: torch.Tensor | None = None, rate: int | None = None, channel: int = 0,
-              window_seconds: float = 15.0, stride_seconds: float = 5.0) -> KeyTrack:
+              window_seconds: float = 15.0, stride_seconds: float = 5.0, smooth: bool = False, mean_key_seconds: float = 60.0,
+              transition: torch.Tensor | None = None, signature_weight: float = 1.0) -> KeyTrack:
         """The key of long recordings over time: audio (R, n) or (R, C, n) float32 on the GPU -> ``KeyTrack``.
 
         Every recording is transformed ONCE at the estimator's hop (``T = 1 + n // hop`` frames); the net then runs on sliding windows
@@ -174,7 +194,17 @@ class KeyEstimator:
 
         ``lengths``, ``rate``, ``channel``, ``streams`` > 1 and ``join()`` behave as in ``__call__``.  Refused with a ``ValueError``:
         ``frames=0`` estimators (one hop per song: there are no frames to slide over), ``wrap_mode="true_end"`` (a window has no padding
-        to wrap into) and ``--local`` nets (their own per-frame forward; its rows are not time frames)."""
+        to wrap into) and ``--local`` nets (their own per-frame forward; its rows are not time frames).
+
+        ``smooth=True`` appends two launches on the same stream and fills ``KeyTrack.emissions`` and ``KeyTrack.smooth_key_id``: every
+        window's log-score of the 24 keys from the two heads (``metrics.key_emissions``: the tonic head's log-softmax plus
+        ``signature_weight`` times the key head's mean Bernoulli log-likelihood of the key's scale), then a first-order Viterbi decode
+        (``metrics.viterbi_keys``).  The path always names a key: a tonic that does not fit the signature scores low instead of decoding
+        to -1.  ``transition``: a (24, 24) log matrix, from key i (row) to key j, all finite (write a forbidden transition as a large
+        negative number).  Default: ``metrics.key_transition_log(stay=exp(-stride / mean_key_seconds))`` with ``stride`` the track's
+        actual stride in seconds, so the amount of smoothing does not depend on the stride chosen.  The default of 60 s is a starting
+        value and nothing more: no recordings labelled with modulations exist here, so no accuracy claim is made for it.  Nothing else
+        of the track changes with ``smooth``."""
         if self.frames <= 0:
             raise ValueError("track() needs a fixed frame rate: this estimator was built with frames=0 (whole-song mode)")
         if self.wrap_mode == "true_end":
@@ -189,9 +219,32 @@ class KeyEstimator:
             lengths = len_out if lengths is not None else None
         wf = track_window_frames(int(round(window_seconds * self.sample_rate)), self.plan.hop_length)
         sf = track_stride_frames(stride_seconds, self.frames)
-        return self._issue(lambda slot, a, l: self._run_track(slot, a, l, wf, sf), audio, lengths)
+        # (made on the caller's stream, which every side stream waits for before it runs the call)
+        smoothing = (self._transition(sf, mean_key_seconds, transition), float(signature_weight)) if smooth else None
+        return self._issue(lambda slot, a, l: self._run_track(slot, a, l, wf, sf, smoothing), audio, lengths)
 
-    def _run_track(self, slot, audio, lengths, wf, sf):
+    def _transition(self, sf, mean_key_seconds, transition):
+        """The (24, 24) float32 log transition matrix on the device: built and validated once per (stride, mean_key_seconds) or per
+        user tensor (by identity and version; the entry keeps the tensor alive), not per call."""
+        cache = self.__dict__.setdefault("_transitions", {})
+        if transition is None:
+            mean_key_seconds = float(mean_key_seconds)
+            if not mean_key_seconds > 0.0:
+                raise ValueError("track(smooth=True): mean_key_seconds must be positive")
+            key = (sf, mean_key_seconds)
+            if key not in cache:
+                stride = sf * self.plan.hop_length / self.sample_rate
+                cache[key] = (None, metrics.key_transition_log(stay=math.exp(-stride / mean_key_seconds)).to(device=self.device, dtype=torch.float32))
+            return cache[key][1]
+        if not isinstance(transition, torch.Tensor) or tuple(transition.shape) != (24, 24):
+            raise ValueError("track(smooth=True): transition must be a (24, 24) tensor of log-probabilities, from key i (row) to key j")
+        key = (id(transition), transition._version)
+        if key not in cache:
+            metrics._check_finite("transition", transition)
+            cache[key] = (transition, transition.detach().to(device=self.device, dtype=torch.float32).contiguous())
+        return cache[key][1]
+
+    def _run_track(self, slot, audio, lengths, wf, sf, smoothing=None):
         net, L, dev = self.net, _lib.lib(), self.device
         audio = audio.to(device=dev, dtype=torch.float32)
         if audio.stride(-1) != 1:
@@ -205,12 +258,19 @@ class KeyEstimator:
         key_id, sig, tonic_id, conf, counts = i32(R, W), i32(R, W), i32(R, W), f32(R, W), i32(R)
         times = (torch.arange(W, dtype=torch.float64) * sf + (wf - 1) / 2) * hop / self.sample_rate
         track = KeyTrack(key, tonic, genre, key_id, sig, tonic_id, conf, counts, times, wf * hop / self.sample_rate, sf * hop / self.sample_rate)
+        if smoothing is not None:
+            track.emissions, track.smooth_key_id = f32(R, W, 24), i32(R, W)
         if W == 0:                                                   # every recording is shorter than one window
             counts.zero_()
             return track
         nbytes = L.ake_pipeline_track_workspace_bytes(self.plan.handle, net.handle, R, n, wf, sf)
         if nbytes == 0:
             _lib.check(-1, "ake_pipeline_track_workspace_bytes")
+        if smoothing is not None:                                    # the back-pointers: after the track on the same stream, so in its workspace
+            vbytes = L.ake_viterbi_keys_workspace_bytes(R, W)
+            if vbytes == 0:
+                _lib.check(-1, "ake_viterbi_keys_workspace_bytes")
+            nbytes = max(int(nbytes), int(vbytes))
         if slot["ws"] is None or slot["ws"].numel() < nbytes:
             slot["ws"] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
         ws = slot["ws"]
@@ -225,6 +285,13 @@ class KeyEstimator:
                 assert lengths.shape == (R,)
                 _lib.check(L.ake_pipeline_track_ragged_f32(self.plan.handle, net.handle, audio.data_ptr(), R, n, audio.stride(0),
                                                            lengths.data_ptr(), wf, sf, *outs), "ake_pipeline_track_ragged_f32")
+            if smoothing is not None:
+                trans, weight = smoothing
+                stream = torch.cuda.current_stream().cuda_stream
+                _lib.check(L.ake_key_emissions_f32(key.data_ptr(), tonic.data_ptr(), R * W, counts.data_ptr(), W, weight,
+                                                   track.emissions.data_ptr(), stream), "ake_key_emissions_f32")
+                _lib.check(L.ake_viterbi_keys_f32(track.emissions.data_ptr(), R, W, counts.data_ptr(), trans.data_ptr(), None,
+                                                  track.smooth_key_id.data_ptr(), ws.data_ptr(), ws.numel(), stream), "ake_viterbi_keys_f32")
         return track
 
     def _run_wrapped(self, slot, audio, lengths):

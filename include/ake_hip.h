@@ -393,6 +393,36 @@ int ake_pipeline_track_ragged_f32(const ake_cqt_plan* plan, const ake_pcnet* net
                                   float* confidence_dev, int32_t* counts_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A smooth key track: per-window log-scores of the 24 keys from the two heads, then a first-order Viterbi decode over them.  Both run on
+ * the outputs of ake_pipeline_track*_f32 (same stream, right after it), which keep their signatures and results.  Every decoded window
+ * holds a key 0..23: a tonic that does not fit the signature scores low instead of decoding to -1.
+ * ---------------------------------------------------------------------------------------- */
+/* emis_dev [rows][24] in the 24-way label order (0-11 minor, 12-23 major, tonic t_k = k mod 12).  With p = key_dev[row] (the sigmoid
+ * memberships, trained with BCE) and tonic_dev[row] the logits (trained with cross-entropy):
+ *   maj(k) = k - 12 if k >= 12, else (k + 3) mod 12;   S_k[j] = 1 if (j - maj(k)) mod 12 is in {0,2,4,5,7,9,11}, else 0
+ *   e[row][k] = log_softmax(tonic)[t_k] + signature_weight / 12 * sum_j ( S_k[j] * max(log p_j, -100) + (1 - S_k[j]) * max(log1p(-p_j), -100) )
+ * (the -100 clamp is nn.BCELoss's).  counts_dev / windows_per_recording as in ake_decode_keys_f32: rows behind a recording's count are
+ * written as 0.  The three buffers are 16-byte aligned (rows move as 16-byte pieces). */
+int ake_key_emissions_f32(const float* key_dev, const float* tonic_dev, int rows, const int32_t* counts_dev, int windows_per_recording,
+                          float signature_weight, float* emis_dev, ake_stream_t stream);
+/* Viterbi over emis_dev [recordings][windows][24], one wave per recording.  log_trans_dev [24][24]: log-probability of moving from key i
+ * (row) to key j; log_prior_dev [24], NULL = zeros; counts_dev (int32 [recordings], NULL = every recording has `windows`), clamped to
+ * 0..windows.  In float32, additions, subtractions and comparisons only (no product, so nothing to contract), so that a host
+ * restatement (metrics.viterbi_keys) is bit-identical:
+ *   d_0[j] = prior[j] + e[0][j]
+ *   m[j]   = max_i ( d_{w-1}[i] + A[i][j] ),  bp_w[j] = the smallest i that attains it,   d_w[j] = m[j] + e[w][j]
+ *   then d_w[j] -= max_j d_w[j]   at every step, w = 0 included (the scores stay bounded for any number of windows)
+ * The last state is the smallest j attaining max d; the path follows bp backwards.  path_dev (int32 [recordings][windows]) holds -1 at
+ * w >= count; a recording of count 0 holds only -1.  All of A, the prior and the emissions must be finite: write a forbidden
+ * transition as a large negative number, not as -infinity (max - max would be NaN).
+ * The workspace holds the back-pointers, one byte per state and window.  The backtrace stages them through LDS
+ * ake_viterbi_chunk_windows() windows at a time. */
+size_t ake_viterbi_keys_workspace_bytes(int recordings, int windows);
+int ake_viterbi_chunk_windows(void);
+int ake_viterbi_keys_f32(const float* emis_dev, int recordings, int windows, const int32_t* counts_dev, const float* log_trans_dev,
+                         const float* log_prior_dev, int32_t* path_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel timing with hipEvents recorded on the launch stream (bench.py roofline leg).
  * ---------------------------------------------------------------------------------------- */
 int ake_prof_enable(const char* name_filter /* substring, NULL or "" = all */, int on);

@@ -8,13 +8,27 @@
 
 Both sides run in this process, hipEvent-timed (torch.cuda.Event), warm, median of --reps runs each; per-kernel times from one run of each
 under the library's kernel timer.  max_abs_diff is for information: A and B differ at window edges by design (A's edge frames see the
-recording's neighbouring audio, B's see zero padding).  Usage: python tools/track_bench.py [--reps 30]
+recording's neighbouring audio, B's see zero padding).  Usage: python tools/track_bench.py [--reps 30] [--smooth]
+
+  --smooth : also, at every stride, what a smooth track costs ("smooth" in each row):
+             track_smooth_ms      est.track(audio, stride_seconds=s, smooth=True), timed as A is
+             smooth_adds_ms       that minus A
+             kernels_ms           key_emissions_kernel and viterbi_keys_kernel under the library's kernel timer
+             viterbi_us_per_window  the Viterbi kernel's time over the W windows of a recording (one wave per recording walks them in turn)
+             host_route_ms        what a user writes without the kernels: key / tonic / counts of a finished track copied to the CPU, then
+                                  metrics.key_emissions and metrics.viterbi_keys there (float32); wall clock from a synchronised device,
+                                  copies included, median of min(--reps, 10) runs
+             path_agreement       share of windows where the device path equals the host route's (the host route takes its logarithms
+                                  with torch on the CPU, so its emissions differ from the kernel's in the last bits; white noise through
+                                  seeded weights scores the keys that close)
+             viterbi_exact        the device path equals metrics.viterbi_keys on the device's own emissions (what the tests assert)
 """
 import argparse
 import json
 import os
 import statistics
 import sys
+import time
 from argparse import Namespace
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -52,12 +66,41 @@ def kernels(fn):
     return res
 
 
+def smooth_row(est, audio, stride, track_ms, reps):
+    smooth = lambda: est.track(audio, stride_seconds=stride, smooth=True)     # noqa: E731
+    s_ms = timed(smooth, reps)
+    k = kernels(smooth)
+    tr = smooth()
+    W = tr.key.shape[1]
+    trans = metrics.key_transition_log(stay=float(np.exp(-tr.stride_seconds / 60.0))).float()
+    torch.cuda.synchronize()
+
+    def host():
+        key, tonic, counts = tr.key.cpu(), tr.tonic.cpu(), tr.counts.cpu()
+        return metrics.viterbi_keys(metrics.key_emissions(key, tonic, counts=counts), trans, counts=counts)
+
+    ms = []
+    for _ in range(max(1, min(reps, 10))):
+        t0 = time.perf_counter()
+        path = host()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    h_ms = statistics.median(ms)
+    vit = k.get("viterbi_keys_kernel", float("nan"))
+    return {"windows_per_recording": W, "track_smooth_ms": round(s_ms, 4), "smooth_adds_ms": round(s_ms - track_ms, 4),
+            "kernels_ms": {n: k.get(n) for n in ("key_emissions_kernel", "viterbi_keys_kernel")},
+            "viterbi_us_per_window": round(1e3 * vit / W, 4), "host_route_ms": round(h_ms, 4),
+            "host_over_smooth_adds": round(h_ms / max(s_ms - track_ms, 1e-6), 1),
+            "path_agreement": round(float((path == tr.smooth_key_id.cpu()).float().mean()), 4),
+            "viterbi_exact": bool(torch.equal(metrics.viterbi_keys(tr.emissions.cpu(), trans, counts=tr.counts.cpu()), tr.smooth_key_id.cpu()))}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--recordings", type=int, default=8)
     ap.add_argument("--minutes", type=float, default=5.0)
     ap.add_argument("--strides", type=float, nargs="+", default=[15.0, 5.0, 1.0])
+    ap.add_argument("--smooth", action="store_true", help="also measure track(smooth=True) and the host route it replaces")
     args = ap.parse_args()
     torch.manual_seed(0)
     gold = np.load(os.path.join(REPO, "tests", "golden", "pcnet_default.npz"))
@@ -92,6 +135,8 @@ def main():
                      "max_abs_diff": {"key": float((tr.key.reshape(-1, 12) - key_b).abs().max()),
                                       "tonic": float((tr.tonic.reshape(-1, 12) - tonic_b).abs().max())},
                      "key_id_agreement": round(agree, 4), "track_kernels_ms": a_k, "clipwise_kernels_ms": b_k})
+        if args.smooth:
+            rows[-1]["smooth"] = smooth_row(est, audio, stride, a_ms, args.reps)
         del tr, key_b, tonic_b
         torch.cuda.empty_cache()
     torch.cuda.synchronize()
