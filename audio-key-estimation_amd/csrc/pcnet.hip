@@ -2925,9 +2925,56 @@ int ake_pcnet_forward_train_f32(const ake_pcnet* n, const float* mel, int batch,
 }
 
 // ---- debug taps ---------------------------------------------------------------------------
+// train:raw/<bn prefix> and train:aff/<bn prefix> (default architecture family): the raw convolution output z that the BatchNorm
+// normalises, [B][C][H][T], and its [C][3] = (scale, shift, negative slope) table as the forward left it -- exactly the (z, aff) pair that
+// Bwd::run hands to affine_act for that site, so a caller can restate every LeakyReLU sign / max-pool winner the backward pass re-derives.
+// *clip_stride (floats) differs from C * H * T where the tensor is a channel slice of a wider buffer.
+static int train_site_lookup(const ake_pcnet* n, const Buffers& b, const std::string& t, int batch, float** p, int64_t shape[4], long long* clip_stride) {
+    const auto& c = n->cfg;
+    const bool want_aff = t.compare(0, 4, "aff/") == 0;
+    std::string site = t.substr(4);
+    if (!site.empty() && site.back() == '.') site.pop_back();
+    AKE_REQUIRE(!c.resblock && !c.denseblock && !c.p2pc_conv && !c.stay_sixth && !c.pc2p_mem && c.local == 0, AKE_ERR_INVALID,
+                "tap: 'train:%s': the raw / table taps cover the default architecture family only", t.c_str());
+    const int L = c.num_layers, P = c.pitches;
+    float *z = nullptr, *aff = nullptr;
+    int64_t C = 0, H = 0, Tn = 0;
+    long long stride = 0;
+    bool hit = false;            // (the pointers are null in the dry run of ake_pcnet_tap_info)
+    auto found = [&](float* z_, float* aff_, int64_t C_, int64_t H_, int64_t T_, long long stride_ = 0) { z = z_; aff = aff_; C = C_; H = H_; Tn = T_; stride = stride_; hit = true; };
+    for (int i = 0; i < L && !hit; ++i) {
+        const std::string m = "model." + std::to_string(i) + ".";
+        const LayerDims& d = n->dims[i];
+        const int Ti = b.Tl[i];
+        if (site == m + "pool_semi_b") found(b.semi_raw[i], b.aff_semi[i], i == 0 ? 1 : d.out_p, P / 3, Ti);
+        if (i >= 1 && site == m + "up_sixth_b") found(b.psix[i], b.aff_p2pin[i] ? b.aff_p2pin[i] + 3 * d.prev_p : nullptr, d.prev_pc, 36, Ti);
+        for (int j = 0; j < c.conv_layers && !hit; ++j) {
+            const std::string bn = "layer." + std::to_string(3 * j + 1);
+            if (i >= 1 && site == m + "p2p." + bn) found(b.pst[i][j], b.aff_pst[i][j], d.out_p, P, Ti);
+            if (site == m + "pc2pc." + bn) {
+                // layer 0's last convolution of a deeper net writes channels [0, n_filters) of layer 1's concat buffer (table: aff_cat[1])
+                if (i == 0 && L > 1 && j == c.conv_layers - 1) {
+                    found(b.cat[1], b.aff_cat[1], c.n_filters, 12, Ti, static_cast<long long>(n->dims[1].prev_pc + n->dims[1].out_p) * 12 * Ti);
+                } else found(b.pcst[i][j], b.aff_pcst[i][j], i == 0 ? c.n_filters : d.out_pc, 12, Ti);
+            }
+        }
+    }
+    const std::vector<PackedConv>* head_t[3] = {&n->head_key_t, &n->head_tonic_t, &n->head_genre_t};
+    const char* head_nm[3] = {"key_classifier", "tonic_classifier", "genre_classifier"};
+    for (int h = 0; h < (c.genre ? 3 : 2) && !hit; ++h)
+        for (int j = 0; j + 1 < c.head_layers; ++j)
+            if (site == std::string(head_nm[h]) + "." + std::to_string(3 * j + 1))
+                found(b.hst[h][j], b.aff_hst[h][j], (*head_t[h])[j].cout, 12, b.Tf - (j + 1) * (c.kernel_size - 1));
+    AKE_REQUIRE(hit && Tn >= 1, AKE_ERR_INVALID, "tap: 'train:%s' names no BatchNorm of this net", t.c_str());
+    if (want_aff) { *p = aff; shape[0] = C; shape[1] = 3; shape[2] = 1; shape[3] = 1; }
+    else { *p = z; shape[0] = batch; shape[1] = C; shape[2] = H; shape[3] = Tn; if (clip_stride) *clip_stride = stride; }
+    return AKE_OK;
+}
+
 static int tap_lookup(const ake_pcnet* n, const char* name, int batch, int frames, const void* ws, float** p, int64_t shape[4],
-                      int* channels_last = nullptr) {
+                      int* channels_last = nullptr, long long* clip_stride = nullptr) {
     if (channels_last) *channels_last = 0;
+    if (clip_stride) *clip_stride = 0;
     AKE_REQUIRE(n && name, AKE_ERR_INVALID, "tap: null argument");
     AKE_REQUIRE(batch <= n->chunk_clips, AKE_ERR_INVALID, "tap: batch %d exceeds the chunk size %d", batch, n->chunk_clips);
     Buffers b;
@@ -2937,6 +2984,7 @@ static int tap_lookup(const ake_pcnet* n, const char* name, int batch, int frame
     const auto& c = n->cfg;
     if (tr) {
         const std::string t = name + 6;
+        if (t.compare(0, 4, "raw/") == 0 || t.compare(0, 4, "aff/") == 0) return train_site_lookup(n, b, t, batch, p, shape, clip_stride);
         const int L1 = c.num_layers - 1;
         const LayerDims& dd = n->dims[L1];
         *p = nullptr;
@@ -3026,8 +3074,14 @@ int ake_pcnet_tap_copy(const ake_pcnet* n, const char* name, int batch, int fram
     float* p = nullptr;
     int64_t shape[4];
     int cl = 0;
-    int rc = tap_lookup(n, name, batch, frames, workspace, &p, shape, &cl);
+    long long clip_stride = 0;
+    int rc = tap_lookup(n, name, batch, frames, workspace, &p, shape, &cl, &clip_stride);
     if (rc) return rc;
+    if (clip_stride) {   // a channel slice of a wider buffer: one row per clip
+        const size_t row = sizeof(float) * shape[1] * shape[2] * shape[3];
+        AKE_HIP_CHECK(hipMemcpy2DAsync(out_dev, row, p, sizeof(float) * clip_stride, row, shape[0], hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+        return AKE_OK;
+    }
     if (cl) {
         const long long total = shape[0] * shape[1] * shape[2] * shape[3];
         const unsigned short* h = reinterpret_cast<const unsigned short*>(p);

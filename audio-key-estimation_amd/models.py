@@ -836,7 +836,16 @@ class PitchClassNet(LightningModule):
         return bool(_lib.lib().ake_debug_keep_taps(1 if on else 0))
 
     def tap(self, name):
-        """Intermediate activation of the last forward (debug / bisecting): reference module path -> tensor."""
+        """Intermediate activation of the last forward (debug / bisecting): reference module path -> tensor.
+
+        After a TRAIN-mode forward (and before its backward, which hands the workspace on) the ``train:`` family names buffers of the training
+        workspace: ``train:g_p`` / ``g_semi`` / ``g_cat`` / ``g_pin`` (gradient buffers of the last layer, valid after a backward on the
+        same workspace), ``train:z_p_last``, and for every BatchNorm of the default architecture family, by its state_dict prefix,
+          ``train:raw/<bn prefix>``   the raw convolution output that BatchNorm normalises, (B, C, H, T) float32;
+          ``train:aff/<bn prefix>``   its (C, 3) table of (scale, shift, negative slope) as the forward left it
+        -- exactly the pair the backward kernels re-derive their decisions from: the activation is ``y = fmaf(z, scale, shift)``,
+        ``a = y if y > 0 else y * slope``, a LeakyReLU's sign is ``y > 0`` and the octave fold / time pools route the gradient to the
+        first maximum of ``a`` (tests/device_decisions.py restates this on the host).  Architecture variants and --local raise."""
         B, Tn = self._last_shape
         L = _lib.lib()
         shape = (C.c_int64 * 4)()
@@ -845,7 +854,7 @@ class PitchClassNet(LightningModule):
         with torch.cuda.device(self._h_device):
             _lib.check(L.ake_pcnet_tap_copy(self._h, name.encode(), B, Tn, self._ws_last.data_ptr(), out.data_ptr(),
                                             torch.cuda.current_stream().cuda_stream), "ake_pcnet_tap_copy")
-        return out
+        return out.reshape(out.shape[0], 3) if name.startswith("train:aff/") else out
 
     # ------------------------------------------------------------------ steps (models.py:819-1027)
     def _general_step_local(self, batch):

@@ -301,7 +301,11 @@ int ake_general_step_local_f32(const float* key_out_dev, const float* tonic_out_
                                float* d_key_dev, float* d_tonic_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream);
 
 /* Debug tap: copy an intermediate activation of the LAST forward call out of the workspace.
- * name is the reference module path whose output it is (e.g. "model.1.p2p.layer.8"). */
+ * name is the reference module path whose output it is (e.g. "model.1.p2p.layer.8").
+ * After ake_pcnet_forward_train_f32 (and before the backward pass) "train:<buffer>" names buffers of the training workspace; for every
+ * BatchNorm of the default architecture family, by state_dict prefix: "train:raw/<bn prefix>" = the raw convolution output it normalises,
+ * [batch][C][H][T], and "train:aff/<bn prefix>" = its [C][3] (scale, shift, negative slope) table, shape {C, 3, 1, 1} -- the pair the
+ * backward kernels re-derive every LeakyReLU sign and max-pool winner from.  Other architectures: AKE_ERR_INVALID. */
 int ake_pcnet_tap_info(const ake_pcnet* net, const char* name, int batch, int frames, int64_t shape[4]);
 /* Inference fuses the semitone conv into the last pitch conv of a stack and runs the last layer's pitch-class stack as one
  * launch, so "model.i.p2p.layer.8" and the last layer's "pc2pc.layer.{2,5,8}" are never written (tap_info says so).

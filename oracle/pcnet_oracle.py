@@ -76,8 +76,104 @@ def _bn(x, sd, prefix, training=False, stats=None):
     return (x - mean[None, :, None, None]) * scale[None, :, None, None] + b[None, :, None, None]
 
 
-def _lrelu(x):
-    return F.leaky_relu(x, LRELU_SLOPE)
+_DECISIONS = None    # set by forced_decisions(): the active context
+
+
+class forced_decisions:
+    """Context manager: take every DECISION of the forward -- the sign of each LeakyReLU pre-activation, the winning octave of each
+    Pitch2PitchClassPool, the winning frame of each time-pool window -- from ``provider`` instead of from the oracle's own values.  With
+    the decisions fixed the forward is a smooth (piecewise-linear pieces glued by the BatchNorm statistics) function of the weights, so
+    a float64 run that is told the decisions of a float32 run has that run's gradients to rounding, whereas a free float64 run differs
+    by 1e-3 .. 3e-2 wherever one pre-activation within 1e-6 of zero goes the other way.
+
+    Sites are named by reference module path, as ``taps``:
+      * ``<bn prefix>`` (e.g. ``model.1.p2p.layer.4.``) for every LeakyReLU(BatchNorm(.)): a boolean tensor of the activation's shape,
+        True where the positive branch is taken, ``y = where(mask, z, slope * z)``;
+      * ``model.i.pool``: the octave index (int64) per (clip, channel, pitch class, frame);
+      * ``model.i.time_pool_p`` / ``model.i.time_pool_pc``: the index inside each window (int64) per (clip, channel, row, pooled frame).
+    ``provider`` is a mapping or a callable ``site -> tensor``; a site it does not know (KeyError / None) keeps the oracle's own
+    decision.  ``provider=None`` forces nothing and only records.  After the forward ``own[site]`` holds the oracle's own decision (the
+    first maximum for the pools, as ``nn.MaxPool2d``), ``flips[site]`` the number of forced decisions that differ from it and
+    ``counts[site]`` the number of decisions; ``keep_own=False`` keeps the counts only.  ``observe(site, x)`` (optional) is called with
+    the detached tensor each decision is taken on -- the BatchNorm output in front of a LeakyReLU, the windows of a pool -- before the
+    provider is asked, so that a caller can compare the forward per site.
+
+    Default family only (num_layers, n_filters, conv_layers, kernel_size, head_layers, genre, mean head pooling): the architecture
+    variants, --local and max_pool raise NotImplementedError under the context.  Without the context nothing changes."""
+
+    def __init__(self, provider=None, keep_own=True, observe=None):
+        self.provider, self.keep_own, self.observe = provider, keep_own, observe
+        self.own, self.flips, self.counts = {}, {}, {}
+
+    def __enter__(self):
+        global _DECISIONS
+        assert _DECISIONS is None, "forced_decisions does not nest"
+        _DECISIONS = self
+        return self
+
+    def __exit__(self, *exc):
+        global _DECISIONS
+        _DECISIONS = None
+
+    def decide(self, site, own, x):
+        """The decision to apply at ``site`` given the oracle's own (taken on ``x``); records both."""
+        assert site not in self.counts, f"decision site {site!r} visited twice"
+        if self.observe is not None:
+            self.observe(site, x)
+        forced = None
+        if self.provider is not None:
+            try:
+                forced = self.provider(site) if callable(self.provider) else self.provider[site]
+            except KeyError:
+                forced = None
+        self.counts[site] = own.numel()
+        if forced is None:
+            self.flips[site] = 0
+        else:
+            forced = forced.to(device=own.device, dtype=own.dtype)
+            if forced.shape != own.shape:
+                raise ValueError(f"forced_decisions: {site!r} wants shape {tuple(own.shape)}, the provider gave {tuple(forced.shape)}")
+            self.flips[site] = int((forced != own).sum())
+        if self.keep_own:
+            self.own[site] = own
+        return own if forced is None else forced
+
+    @property
+    def total_flips(self):
+        return sum(self.flips.values())
+
+    @property
+    def total_decisions(self):
+        return sum(self.counts.values())
+
+
+def _no_forcing(what):
+    if _DECISIONS is not None:
+        raise NotImplementedError(f"forced_decisions covers the default architecture family only: {what} is not supported")
+
+
+def _lrelu(x, site=None):
+    """LeakyReLU behind the BatchNorm ``site`` (its state_dict prefix): the one place where a sign decision is taken."""
+    if _DECISIONS is None:
+        return F.leaky_relu(x, LRELU_SLOPE)
+    if site is None:
+        _no_forcing("an activation without a site name")
+    mask = _DECISIONS.decide(site, (x > 0).detach(), x.detach())
+    return torch.where(mask, x, LRELU_SLOPE * x)
+
+
+def _act_bn(x, sd, prefix, training):
+    return _lrelu(_bn(x, sd, prefix, training), prefix)
+
+
+def _time_pool(x, size, site):
+    """F.max_pool2d(x, (1, size)) (models.py:395-396); under forced_decisions the winner of each window comes from the provider."""
+    if _DECISIONS is None:
+        return F.max_pool2d(x, (1, size))
+    B, C, H, T = x.shape
+    w = x[..., :T // size * size].reshape(B, C, H, T // size, size)
+    idx = _DECISIONS.decide(site, w.detach().argmax(dim=-1), w.detach())
+    return w.gather(-1, idx.unsqueeze(-1)).squeeze(-1)
 
 
 def equiv_pc_conv(x, weight, bias, same: bool):
@@ -93,7 +189,7 @@ def equiv_pc_conv(x, weight, bias, same: bool):
     return F.conv2d(x_wrap, weight, bias, padding=(0, kd // 2 if same else 0))
 
 
-def pitch2pitchclass_pool(x, pitch_classes: int = 12):
+def pitch2pitchclass_pool(x, pitch_classes: int = 12, site=None):
     """Pitch2PitchClassPool.forward, models.py:95-106 (ctor :84-92).
 
     Dilated max-pool over octaves; -inf rows are appended only when the row
@@ -105,18 +201,25 @@ def pitch2pitchclass_pool(x, pitch_classes: int = 12):
     if pad:
         filler = torch.full((x.shape[0], x.shape[1], pad, x.shape[3]), float("-inf"), dtype=x.dtype)
         x = torch.cat([x, filler], dim=2)
+    if _DECISIONS is not None:      # row = octave * 12 + pitch class: the window of pitch class p is x[:, :, p::12]
+        if site is None:
+            _no_forcing("an octave pool without a site name")
+        o = x.reshape(x.shape[0], x.shape[1], ks, pitch_classes, x.shape[3])
+        idx = _DECISIONS.decide(site, o.detach().argmax(dim=2), o.detach())
+        return o.gather(2, idx.unsqueeze(2)).squeeze(2)
     return F.max_pool2d(x, (ks, 1), (1, 1), dilation=(pitch_classes, 1))
 
 
 def pitch2pitchclass_conv(x, sd, prefix, training=False):
     """Pitch2PitchClassConv.forward, models.py:108-133 (--p2pc_conv): the octave fold as a learned convolution -- kernel
     (ceil(pitches_in / 12), 1) with dilation (12, 1) over the channels, then BatchNorm + LeakyReLU -- instead of the max."""
+    _no_forcing("--p2pc_conv")
     w = sd[prefix + "conv.weight"]
     pad = w.shape[2] * 12 - x.shape[2]                       # rows of padding_value appended (:130-131); 0 for whole octaves
     if pad:
         x = torch.cat([x, torch.full((x.shape[0], x.shape[1], pad, x.shape[3]), float("-inf"), dtype=x.dtype)], dim=2)
     y = F.conv2d(x, w, sd[prefix + "conv.bias"], dilation=(12, 1))
-    return _lrelu(_bn(y, sd, prefix + "bn.", training))
+    return _act_bn(y, sd, prefix + "bn.", training)
 
 
 def pitchclass2pitch(x, target_rows: int):
@@ -144,10 +247,11 @@ def _res_blocks(x, sd, prefix, conv, training, taps):
     """--resblock (models.py:181-187 / :218-224): after the first conv + BN + LeakyReLU the Sequential holds ``conv_layers`` blocks
     at indices 3, 4, ...; a block is x -> act2(x + b2(conv2(act1(b1(conv1(x)))))) (ResBlock / ResBlockEquivariant, models.py:402-454).
     ``conv(x, block_prefix + "conv1")`` applies the stack's convolution type."""
+    _no_forcing("--resblock")
     idx = 3
     while f"{prefix}layer.{idx}.b1.weight" in sd:
         bp = f"{prefix}layer.{idx}."
-        h = _lrelu(_bn(conv(x, bp + "conv1"), sd, bp + "b1.", training))
+        h = _act_bn(conv(x, bp + "conv1"), sd, bp + "b1.", training)
         x = _lrelu(x + _bn(conv(h, bp + "conv2"), sd, bp + "b2.", training))
         if taps is not None:
             taps[f"{prefix}layer.{idx}"] = x
@@ -162,12 +266,13 @@ def _dense_block(x, sd, prefix, conv, training, taps):
     (pre-activation BatchNorm; relu1 is a LeakyReLU, relu2 a plain ReLU; conv1 is the 1-wide bottleneck), and the block returns the
     concatenation of everything (:614 / :647).  drop_rate is 0.0 at both call sites (:189, 226).  ``conv(x, key_prefix, same)``
     applies the stack's convolution type."""
+    _no_forcing("--denseblock")
     feats = [x]
     j = 1
     while f"{prefix}denselayer{j}.norm1.weight" in sd:
         lp = f"{prefix}denselayer{j}."
         cat = torch.cat(feats, dim=1)
-        h = conv(_lrelu(_bn(cat, sd, lp + "norm1.", training)), lp + "conv1")
+        h = conv(_act_bn(cat, sd, lp + "norm1.", training), lp + "conv1")
         new = conv(F.relu(_bn(h, sd, lp + "norm2.", training)), lp + "conv2")
         feats.append(new)
         if taps is not None:
@@ -184,13 +289,13 @@ def pc2pc_stack(pc, sd, prefix, training=False, taps=None):
                             training, taps)
     if f"{prefix}layer.3.b1.weight" in sd:
         pc = equiv_pc_conv(pc, sd[prefix + "layer.0.conv2d.weight"], sd[prefix + "layer.0.conv2d.bias"], same=True)
-        pc = _lrelu(_bn(pc, sd, prefix + "layer.1.", training))
+        pc = _act_bn(pc, sd, prefix + "layer.1.", training)
         return _res_blocks(pc, sd, prefix, lambda x, q: equiv_pc_conv(x, sd[q + ".conv2d.weight"], sd[q + ".conv2d.bias"], same=True),
                            training, taps)
     n = _count(sd, prefix + "layer.", ".conv2d.weight")
     for i in range(n):
         pc = equiv_pc_conv(pc, sd[f"{prefix}layer.{3*i}.conv2d.weight"], sd[f"{prefix}layer.{3*i}.conv2d.bias"], same=True)
-        pc = _lrelu(_bn(pc, sd, f"{prefix}layer.{3*i+1}.", training))
+        pc = _act_bn(pc, sd, f"{prefix}layer.{3*i+1}.", training)
         if taps is not None:
             taps[f"{prefix}layer.{3*i+2}"] = pc
     return pc
@@ -204,14 +309,14 @@ def p2p_stack(p, sd, prefix, training=False, taps=None):
                             training, taps)
     if f"{prefix}layer.3.b1.weight" in sd:
         circ = lambda x, q: _circular_conv(x, sd[q + ".weight"], sd[q + ".bias"], (1, 1), (sd[q + ".weight"].shape[2] // 2,) * 2)
-        p = _lrelu(_bn(circ(p, prefix + "layer.0"), sd, prefix + "layer.1.", training))
+        p = _act_bn(circ(p, prefix + "layer.0"), sd, prefix + "layer.1.", training)
         return _res_blocks(p, sd, prefix, circ, training, taps)
     n = _count(sd, prefix + "layer.", ".weight")
     for i in range(n):
         w = sd[f"{prefix}layer.{3*i}.weight"]
         k = w.shape[2]
         p = _circular_conv(p, w, sd[f"{prefix}layer.{3*i}.bias"], (1, 1), (k // 2, k // 2))
-        p = _lrelu(_bn(p, sd, f"{prefix}layer.{3*i+1}.", training))
+        p = _act_bn(p, sd, f"{prefix}layer.{3*i+1}.", training)
         if taps is not None:
             taps[f"{prefix}layer.{3*i+2}"] = p
     return p
@@ -224,7 +329,7 @@ def semitone_pool(p, sd, prefix, training=False):
     one semitone, time wraps.
     """
     x = _circular_conv(p, sd[prefix + "pool_semi.weight"], sd[prefix + "pool_semi.bias"], (3, 1), (0, 1))
-    return _lrelu(_bn(x, sd, prefix + "pool_semi_b.", training))
+    return _act_bn(x, sd, prefix + "pool_semi_b.", training)
 
 
 def pitchclass2pitch_memory(p, p_sixth):
@@ -232,6 +337,7 @@ def pitchclass2pitch_memory(p, p_sixth):
     map, ADD it to the pitch stream -- after summing groups of its channels down to the stream's channel count.  The reference
     reshapes the P pitch rows to (36, P / 36), so row r receives third-semitone index r // (P / 36) (eight CONSECUTIVE rows share
     one), not r % 36 as the repeat of the default path does; kept as it is."""
+    _no_forcing("--pc2p_mem")
     B, C, P, T = p.shape
     s = p_sixth.reshape(B, C, p_sixth.shape[1] // C, p_sixth.shape[2], T).sum(dim=2)          # (B, C, 36, T)
     k = s.shape[2]
@@ -257,11 +363,12 @@ def forward_features(sd, mel, time_pool_size=2, training=False, taps=None):
             if stay:
                 p = p_semi                                          # :366-367
             pc = (pitch2pitchclass_conv(p_semi, sd, pre + "pool.", training) if pre + "pool.conv.weight" in sd
-                  else pitch2pitchclass_pool(p_semi))               # :368 (p stays raw, :366-367)
+                  else pitch2pitchclass_pool(p_semi, site=pre + "pool"))   # :368 (p stays raw, :366-367)
             if taps is not None:
                 taps[pre + "pool"] = pc
             pc = pc2pc_stack(pc, sd, pre + "pc2pc.", training, taps)  # :369
         elif stay:
+            _no_forcing("--stay_sixth")
             p = torch.cat([p, pitchclass2pitch(pc, p.shape[2])], dim=1)   # :379-383 with up = PitchClass2Pitch(pitches // 3)
             p = p2p_stack(p, sd, pre + "p2p.", training, taps)      # :384
             pc2 = (pitch2pitchclass_conv(p, sd, pre + "pool.", training) if pre + "pool.conv.weight" in sd
@@ -276,7 +383,7 @@ def forward_features(sd, mel, time_pool_size=2, training=False, taps=None):
                 taps[pre + "time_pool_pc"] = pc
         else:
             p_sixth = F.conv_transpose2d(pc, sd[pre + "up_sixth.weight"], sd[pre + "up_sixth.bias"], stride=(3, 1))  # :372
-            p_sixth = _lrelu(_bn(p_sixth, sd, pre + "up_sixth_b.", training))     # :373-374
+            p_sixth = _act_bn(p_sixth, sd, pre + "up_sixth_b.", training)         # :373-374
             if taps is not None:
                 taps[pre + "up_sixth_a"] = p_sixth
             if pre + "p2p.layer.0.weight" in sd and sd[pre + "p2p.layer.0.weight"].shape[1] == p.shape[1]:       # --pc2p_mem: :376-377, no concat (:382)
@@ -287,13 +394,13 @@ def forward_features(sd, mel, time_pool_size=2, training=False, taps=None):
             p = p2p_stack(p, sd, pre + "p2p.", training, taps)      # :384
             pc2 = semitone_pool(p, sd, pre, training)               # :386-388
             pc2 = (pitch2pitchclass_conv(pc2, sd, pre + "pool.", training) if pre + "pool.conv.weight" in sd
-                   else pitch2pitchclass_pool(pc2))                 # :389
+                   else pitch2pitchclass_pool(pc2, site=pre + "pool"))   # :389
             if taps is not None:
                 taps[pre + "pool"] = pc2
             pc = torch.cat([pc, pc2], dim=1)                        # :392
             pc = pc2pc_stack(pc, sd, pre + "pc2pc.", training, taps)  # :393
-            p = F.max_pool2d(p, (1, time_pool_size))                # :395
-            pc = F.max_pool2d(pc, (1, time_pool_size))              # :396
+            p = _time_pool(p, time_pool_size, pre + "time_pool_p")      # :395
+            pc = _time_pool(pc, time_pool_size, pre + "time_pool_pc")   # :396
             if taps is not None:
                 taps[pre + "time_pool_pc"] = pc
     return p, pc, num_layers
@@ -308,7 +415,7 @@ def _equiv_head(pc, sd, name, training=False):
     while f"{name}.{idx}.conv2d.weight" in sd:
         x = equiv_pc_conv(x, sd[f"{name}.{idx}.conv2d.weight"], sd[f"{name}.{idx}.conv2d.bias"], same=False)
         if f"{name}.{idx+1}.weight" in sd:       # BN follows -> hidden block
-            x = _lrelu(_bn(x, sd, f"{name}.{idx+1}.", training))
+            x = _act_bn(x, sd, f"{name}.{idx+1}.", training)
             idx += 3
         else:
             break
@@ -322,7 +429,7 @@ def _genre_head(pc, sd, training=False):
     while f"genre_classifier.{idx}.weight" in sd and sd[f"genre_classifier.{idx}.weight"].dim() == 4:
         x = F.conv2d(x, sd[f"genre_classifier.{idx}.weight"], sd[f"genre_classifier.{idx}.bias"])
         if f"genre_classifier.{idx+1}.running_mean" in sd:
-            x = _lrelu(_bn(x, sd, f"genre_classifier.{idx+1}.", training))
+            x = _act_bn(x, sd, f"genre_classifier.{idx+1}.", training)
             idx += 3
         else:
             break
@@ -344,7 +451,10 @@ def pcnet_forward(sd: Dict[str, torch.Tensor], mel: torch.Tensor, seq_length: Op
     """
     if genre is None:
         genre = "genre_classifier.0.weight" in sd
+    if max_pool:
+        _no_forcing("max_pool")
     if local_window is not None:
+        _no_forcing("--local")
         time_pool_size = 1                                                           # :348, :394 -- no time pooling with --local
     p, pc, num_layers = forward_features(sd, mel, time_pool_size, training, taps)   # :749
     tonic = _equiv_head(pc, sd, "tonic_classifier", training)                        # :750

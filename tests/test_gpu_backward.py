@@ -11,7 +11,9 @@ tests/tools/grad_seed_scan.py scans (shape, seed) cases.  So:
     proves each kernel of the chain (a systematic error fails every seed);
   * KINKED cases only bound the damage (5e-2) and require the median tensor to stay tight.
 If a change of summation order moves a flip into a tight case, re-pick its seed with tests/tools/grad_seed_scan.py;
-test_default_net_gradients_without_curated_seeds makes the same statement over eight seeds per shape without any picking."""
+test_default_net_gradients_without_curated_seeds makes the same statement over eight seeds per shape without any picking.
+The flip-free statement -- the same cases, kinked ones and all eight seeds included, tight against a float64 run that takes the
+device's own decisions -- is tests/test_gpu_backward_decisions.py."""
 import json
 from argparse import Namespace
 

@@ -110,7 +110,8 @@ def test_gradients_at_32_clips(gold_default):
     batches, against the same float64 gradients: worst tensor 4.6e-3 .. 3.0e-2, MEDIAN tensor 1.0e-3 .. 3.6e-3 on each of seeds 0-3
     (256 clips: 5.2e-3 / 2.1e-3).  So against float64 the statement is: every seed inside that band; the tensors no flip can reach tight
     on every seed; and a seed whose flips sit low in the net (seed 0: median 5e-6) shows most tensors tight.  The flip-free statements at
-    these sizes are the replication identities below."""
+    these sizes are the replication identities below (device against device) and tests/test_gpu_backward_decisions.py (these four batches
+    against float64 autograd at the device's own decisions, every tensor to 2e-5)."""
     net, sd32 = fresh_net(gold_default)
     medians = []
     for seed in range(4):
@@ -193,11 +194,13 @@ def test_512_clips_equal_the_replicated_256(gold_default):
 def test_gradients_at_the_bench_shard(gold_default):
     """256 clips x 76 frames of DISTINCT data -- the per-rank batch of `bench.py --train` and of BASELINE configs[3] -- against float64
     autograd of the whole batch (about a minute on the host).  Inside the float32 band (float32 PyTorch on the CPU, this batch: worst
-    5.2e-3, median 2.1e-3 against the same float64 gradients); the tensors nothing can flip above -- the heads' last convolutions -- tight."""
-    net, sd32 = fresh_net(gold_default)
-    x, seq, labels = big_case(256, 76, 7)
+    5.2e-3, median 2.1e-3 against the same float64 gradients); the tensors nothing can flip above -- the heads' last convolutions -- tight.
+    The flip-free statement about this very step is tests/test_gpu_backward_decisions.py::test_the_bench_shard_is_tight: the same device
+    gradients against float64 at the device's own decisions, every tensor to 2e-5."""
+    import device_decisions
+    run = device_decisions.bench_shard_run(gold_default)      # the device step, shared with tests/test_gpu_backward_decisions.py
+    sd32, x, seq, labels, loss, got = (run[k] for k in ("sd32", "x", "seq", "labels", "loss", "got"))
     loss_ref, ref = oracle_grads(sd32, x, seq, labels)
-    loss, got = device_grads(net, x, seq, labels)
     assert abs(loss - loss_ref) < 2e-5 * max(1.0, abs(loss_ref)), (loss, loss_ref)
     rows = error_rows(got, ref)
     report("256 clips", rows)

@@ -219,3 +219,181 @@ def test_denseblock_training_step_against_reference_fixture():
     for k in names:
         ref = gold["grad/" + k]
         assert np.abs(sd[k].grad.numpy() - ref).max() <= 1e-6 * max(float(np.abs(ref).max()), 1e-9 * gmax), k
+
+
+# ---- forced decisions (oracle.pcnet_oracle.forced_decisions): the float64 oracle told which way every LeakyReLU / max-pool goes ----
+
+def _small_case(batch, frames, seed):
+    """tests/test_gpu_backward.py's make_case (kept in step with it: the GPU tests run the same batches)."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.rand((batch, 1, 288, frames), generator=g) * 2.5
+    seq = torch.tensor([frames, frames - 6, frames - 13, frames][:batch])
+    key_labels = (torch.rand((batch, 12), generator=g) > 0.5).float()
+    tonic_idx = torch.randint(0, 12, (batch,), generator=g)
+    genre_idx = torch.randint(0, 11, (batch,), generator=g)
+    genre_mask = torch.tensor([True, False, True, True][:batch])
+    return x, seq, (key_labels, tonic_idx, genre_idx, genre_mask)
+
+
+def _loss(out, labels):
+    import torch.nn.functional as F
+    key_labels, tonic_idx, genre_idx, genre_mask = labels
+    return (F.binary_cross_entropy(out[0], key_labels.to(out[0].dtype)) + F.cross_entropy(out[1], tonic_idx)
+            + 0.1 * F.cross_entropy(out[2][genre_mask], genre_idx[genre_mask]))
+
+
+def _train_step(sd32, x, seq, labels, dtype, provider="free", perturb=None):
+    """(outputs, loss, {name: grad}, context or None) of one train-mode step of the oracle in `dtype`; `provider` = "free" runs without the
+    context, anything else (None: record only) under forced_decisions(provider)."""
+    sd = {k: (v.to(dtype).clone().requires_grad_(True) if v.is_floating_point() and "running" not in k else v.to(dtype) if v.is_floating_point() else v)
+          for k, v in sd32.items()}
+    ctx = None
+    if isinstance(provider, str):
+        out = pcnet_oracle.pcnet_forward(sd, x.to(dtype), seq, training=True)
+    else:
+        with pcnet_oracle.forced_decisions(provider) as ctx:
+            out = pcnet_oracle.pcnet_forward(sd, x.to(dtype), seq, training=True)
+    loss = _loss(out, labels)
+    loss.backward()
+    return [o.detach() for o in out], float(loss.detach()), {k: v.grad for k, v in sd.items() if torch.is_tensor(v) and v.requires_grad}, ctx
+
+
+def test_forcing_the_oracles_own_decisions_changes_nothing(gold_default):
+    """forced_decisions with the float64 run's OWN recorded decisions is the free run: outputs bit for bit (where(mask, z, slope z) and the
+    gathered maximum are the values leaky_relu and max_pool2d return), gradients to 1e-12 of the largest; no flip is counted; and every
+    decision site of the default net is visited exactly once under its reference module path."""
+    sd32 = golden_state_dict(gold_default)
+    x, seq, labels = _small_case(3, 40, 0)
+    out_f, loss_f, g_f, _ = _train_step(sd32, x, seq, labels, torch.float64)
+    _, _, _, rec = _train_step(sd32, x, seq, labels, torch.float64, provider=None)
+    assert rec.total_flips == 0
+    sites = set(rec.own)
+    bns = {k[:-len("running_mean")] for k in sd32 if k.endswith("running_mean")}
+    assert sites == bns | {"model.0.pool", "model.1.pool", "model.1.time_pool_p", "model.1.time_pool_pc"}, sites ^ bns
+    assert rec.own["model.1.p2p.layer.7."].dtype == torch.bool and rec.own["model.1.p2p.layer.7."].shape == (3, 8, 288, 40)
+    assert rec.own["model.1.pool"].shape == (3, 8, 12, 40) and int(rec.own["model.1.pool"].max()) == 7
+    assert rec.own["model.1.time_pool_pc"].shape == (3, 16, 12, 20) and rec.own["model.1.time_pool_p"].shape == (3, 8, 288, 20)
+    assert rec.total_decisions == sum(v.numel() for v in rec.own.values())
+    out_o, loss_o, g_o, ctx = _train_step(sd32, x, seq, labels, torch.float64, provider=rec.own)
+    assert ctx.total_flips == 0 and ctx.counts == rec.counts
+    for a, b in zip(out_o, out_f):
+        assert torch.equal(a, b)
+    assert loss_o == loss_f
+    gmax = max(float(v.abs().max()) for v in g_f.values())
+    for k in g_f:
+        assert float((g_o[k] - g_f[k]).abs().max()) <= 1e-12 * gmax, k
+    # a callable provider, and one that knows only some sites (the others keep the oracle's own decision)
+    out_c, _, _, ctx = _train_step(sd32, x, seq, labels, torch.float64, provider=lambda s: rec.own[s] if s.startswith("model.1.") else None)
+    assert ctx.total_flips == 0 and all(torch.equal(a, b) for a, b in zip(out_c, out_f))
+    with pytest.raises(ValueError, match="wants shape"):
+        _train_step(sd32, x, seq, labels, torch.float64, provider={"model.0.pool": rec.own["model.1.pool"]})
+
+
+@pytest.mark.parametrize("site", ["model.1.p2p.layer.4.", "model.0.pc2pc.layer.7.", "tonic_classifier.1."])
+def test_one_forced_flip_moves_that_batchnorms_dbeta_by_its_gradient(gold_default, site):
+    """The hook is wired to the right site and element: with one LeakyReLU decision of BatchNorm `site` forced the other way, the
+    activation there becomes slope z instead of z (or the reverse), so d a / d beta at that element changes by -+(1 - slope) and nothing
+    else that multiplies ga in dbeta changes -- IF ga, the gradient arriving at the activation, is held.  It is held by making the loss
+    LINEAR in that activation: loss = sum(w * a) for a fixed random w, read through `taps` (the tap of a stack's conv + BN + LReLU block)."""
+    sd32 = golden_state_dict(gold_default)
+    x, seq, _ = _small_case(2, 40, 1)
+    tap_name = {"model.1.p2p.layer.4.": "model.1.p2p.layer.5", "model.0.pc2pc.layer.7.": "model.0.pc2pc.layer.8"}.get(site)
+    slope = pcnet_oracle.LRELU_SLOPE
+
+    def dbeta(provider, w=None):
+        sd = {k: (v.double().clone().requires_grad_(True) if k == site + "bias" else v.double() if v.is_floating_point() else v) for k, v in sd32.items()}
+        taps = {}
+        if tap_name is None:      # a head's hidden block has no tap: catch the activation on its way out of _lrelu
+            orig = pcnet_oracle._lrelu
+            def spy(z, s=None):
+                a = orig(z, s)
+                if s == site:
+                    taps["a"] = a
+                return a
+            pcnet_oracle._lrelu = spy
+        try:
+            with pcnet_oracle.forced_decisions(provider) as ctx:
+                pcnet_oracle.pcnet_forward(sd, x.double(), seq, training=True, taps=taps)
+        finally:
+            if tap_name is None:
+                pcnet_oracle._lrelu = orig
+        a = taps[tap_name or "a"]
+        if w is None:
+            w = torch.randn(a.shape, generator=torch.Generator().manual_seed(5), dtype=torch.float64)
+        (w * a).sum().backward()
+        return sd[site + "bias"].grad.clone(), ctx, w
+
+    g0, rec, w = dbeta(None)
+    own = rec.own[site]
+    c = 1 if own.shape[1] > 1 else 0
+    for want in (True, False):           # flip one element that went up, one that went down
+        ix = tuple(torch.nonzero(own[:, c] == want)[7].tolist())
+        ix = (ix[0], c) + ix[1:]
+        forced = own.clone()
+        forced[ix] = not want
+        g1, ctx, _ = dbeta({site: forced}, w)
+        assert ctx.total_flips == 1 and ctx.flips[site] == 1
+        delta = g1 - g0
+        sign = -1.0 if want else 1.0     # z -> slope z loses (1 - slope) of the element's d a / d beta = 1
+        assert abs(float(delta[c]) - sign * (1 - slope) * float(w[ix])) <= 1e-12 * max(1.0, abs(float(w[ix])))
+        others = torch.cat([delta[:c], delta[c + 1:]])
+        assert others.numel() == 0 or float(others.abs().max()) == 0.0
+
+
+# tests/test_gpu_backward.py's list: dgamma of the first BatchNorm is a heavily cancelling sum
+ILL_CONDITIONED = {"model.0.pool_semi_b.weight": 2e-3}
+
+
+def _grad_rows(got, ref):
+    rows = []
+    gmax = max(float(r.abs().max()) for r in ref.values())
+    for k, r in ref.items():
+        m = float(r.abs().max())
+        if k.endswith(".bias") and m < 1e-9:
+            # a convolution bias in front of a BatchNorm: exactly zero.  Autograd in float32 still SUMS its ~1e4 .. 1e6 cancelling terms (the
+            # device writes no such sum), so the stand-in is held to the rule of test_gpu_backward.cancelling_ok: 1e-5 of the largest gradient
+            assert float(got[k].abs().max()) < 1e-5 * gmax, k
+            continue
+        rows.append((float((got[k].double() - r).abs().max()) / max(m, 1e-7), k))
+    rows.sort(reverse=True)
+    return rows
+
+
+def test_forcing_a_float32_runs_decisions_makes_float64_its_reference(gold_default):
+    """The method of tests/test_gpu_backward_decisions.py, on the CPU with float32 torch in the device's place: record the decisions of a
+    float32 oracle step at 4 x 52, seeds 0-2, force them into the float64 step.  Against THAT reference every float32 gradient tensor is
+    within 2e-5 of its maximum (measured 1.3e-5 worst; the ill-conditioned first dgamma within its listed 2e-3), whereas against the free
+    float64 run at least one seed is off by more than 1e-3 (measured 5.4e-3 and 4.2e-3) -- a handful of the 2.2e6 decisions go the other
+    way -- so it is the forcing that makes the comparison tight."""
+    sd32 = golden_state_dict(gold_default)
+    worst_free = []
+    for seed in range(3):
+        x, seq, labels = _small_case(4, 52, seed)
+        _, loss32, g32, rec = _train_step(sd32, x, seq, labels, torch.float32, provider=None)
+        _, loss_forced, g_forced, ctx = _train_step(sd32, x, seq, labels, torch.float64, provider=rec.own)
+        _, _, g_free, _ = _train_step(sd32, x, seq, labels, torch.float64)
+        rows = _grad_rows(g32, g_forced)
+        free = _grad_rows(g32, g_free)
+        print(f"\n4 x 52 seed {seed}: float32 against forced float64 worst {rows[0][0]:.2e} ({rows[0][1]}), against free float64 {free[0][0]:.2e}; "
+              f"{ctx.total_flips} of {ctx.total_decisions} decisions forced the other way")
+        assert abs(loss32 - loss_forced) < 2e-5 * max(1.0, abs(loss_forced))
+        assert ctx.total_decisions == rec.total_decisions and ctx.total_flips <= 1e-5 * ctx.total_decisions
+        bad = [(e, n) for e, n in rows if e > ILL_CONDITIONED.get(n, 2e-5)]
+        assert not bad, (seed, bad[:5])
+        worst_free.append(max(e for e, n in free if n not in ILL_CONDITIONED))
+    assert max(worst_free) > 1e-3, worst_free
+
+
+def test_forced_decisions_refuses_what_it_does_not_cover(gold_default, gold_resblock, gold_pc2pmem, gold_p2pcconv, gold_staysixth, gold_denseblock):
+    """Default family only: the architecture variants, --local and max_pool raise under the context (and run as before without it)."""
+    sd = golden_state_dict(gold_default, torch.float64)
+    x = torch.from_numpy(gold_default["x"]).double()
+    for kw, flag in (({"max_pool": True}, "max_pool"), ({"local_window": 5}, "--local")):
+        with pcnet_oracle.forced_decisions(None), pytest.raises(NotImplementedError, match=flag):
+            pcnet_oracle.pcnet_forward(sd, x, None, **kw)
+    for gold, flag in ((gold_resblock, "--resblock"), (gold_pc2pmem, "--pc2p_mem"), (gold_p2pcconv, "--p2pc_conv"), (gold_staysixth, "--stay_sixth"),
+                       (gold_denseblock, "--denseblock")):
+        with pcnet_oracle.forced_decisions(None), pytest.raises(NotImplementedError, match=flag):
+            pcnet_oracle.pcnet_forward(golden_state_dict(gold, torch.float64), torch.from_numpy(gold["x"]).double(), None)
+    assert pcnet_oracle._DECISIONS is None              # the context is closed again after an error
+    pcnet_oracle.pcnet_forward(sd, x, None, max_pool=True)

@@ -1,7 +1,6 @@
 """Count LeakyReLU kink flips between the device's f32 training forward and the f64 oracle at the last pitch-stream
 BatchNorm of the default net, and list per-parameter gradient errors (see tests/test_gpu_backward.py for why these
 two are linked).  Usage on a GPU box: DBG_B=4 DBG_T=52 DBG_SEED=4 python tests/tools/debug_bwd.py"""
-import ctypes as C
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -24,22 +23,13 @@ for v in taps.values():
     if v.requires_grad: v.retain_grad()
 tb.loss_fn(out[0], out[1], out[2], *labels).backward()
 o = net(x.cuda(), seq.cuda())
-tb.loss_fn(o[0], o[1], o[2], *(t.cuda() for t in labels)).backward()
 
 
-def tap(name):
-    L = ake_amd._lib.lib(); shape = (C.c_int64 * 4)()
-    ake_amd._lib.check(L.ake_pcnet_tap_info(net._h, name.encode(), B, T, shape), "tap_info")
-    t = torch.empty(tuple(shape), dtype=torch.float32, device="cuda")
-    ake_amd._lib.check(L.ake_pcnet_tap_copy(net._h, name.encode(), B, T, net._ws_last.data_ptr(), t.data_ptr(), torch.cuda.current_stream().cuda_stream), "tap_copy")
-    return t.cpu().double()
-
-
-z = tap("train:z_p_last")                       # raw output of the last pitch conv (device)
 bnp = "model.1.p2p.layer.7"
-gamma, beta = sd32[bnp + ".weight"].double(), sd32[bnp + ".bias"].double()
-mu = z.mean(dim=(0, 2, 3), keepdim=True); var = z.var(dim=(0, 2, 3), unbiased=False, keepdim=True)
-pre = (z - mu) / torch.sqrt(var + 1e-5) * gamma.view(1, -1, 1, 1) + beta.view(1, -1, 1, 1)
+# the pair the backward kernels read for this BatchNorm (tests/device_decisions.py): raw output of the last pitch conv + its (scale, shift, slope) table
+z, aff = net.tap("train:raw/" + bnp + ".").cpu().double(), net.tap("train:aff/" + bnp + ".").cpu().double()
+pre = (z * aff[:, 0].view(1, -1, 1, 1) + aff[:, 1].view(1, -1, 1, 1)).float().double()       # fmaf(z, scale, shift)
+tb.loss_fn(o[0], o[1], o[2], *(t.cuda() for t in labels)).backward()
 a_ref = taps["model.1.p2p.layer.8"].detach(); ga = taps["model.1.p2p.layer.8"].grad
 flip = (pre > 0) != (a_ref > 0)
 print("kink flips at", bnp, ":", int(flip.sum()), "of", flip.numel())
