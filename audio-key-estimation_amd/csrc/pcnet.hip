@@ -544,54 +544,108 @@ bool p2p_fuses_semi(const ake_pcnet* n, int i, int P, int T) {
            p2p_ps_rows(P, T, true, nullptr, nullptr) > 0;
 }
 
-// the same convolution as a persistent launch (conv_p2p_f16_ps_kernel): one workgroup per CU walks the row tiles.  Taken for even
-// frame counts and enough tiles to give every CU at least two (always when `semi_pc` asks for the fused semitone conv: `dst` then
-// receives the semitone maps [clip][8][H / 3][T]); returns false when the shape does not qualify (the caller then launches
-// conv_p2p_f16_kernel)
-// p_frames_major: the one pitch-stream channel of `nchw` is stored [clip][T][H] (ake_pcnet_forward_frames_major_f32)
-// fold_coff >= 0 (with semi_pc): the fused semitone launch also takes the maximum over the octaves and writes channels
-// [fold_coff, fold_coff + 8) of the concat buffer dst_nchw [clip][dst_ctot][12][T] (OUT = 3); false when the shape does not allow it
-bool run_p2p_f16_ps(const ake_pcnet* n, const PackedConv& pc, const unsigned short* xh, const Src* nchw, int batch, int H, int T, float* dst_nchw,
-                     int dst_ctot, unsigned short* oh, const PackedConv* semi_pc, hipStream_t s, const char* name, bool p_frames_major = false,
-                     bool dry_run = false, int fold_coff = -1, bool u_f16x4 = false) {     // u_f16x4: nchw->p1 is layer 0's f16 x 4 form of the up_sixth map (Layer0Args::psix_h)
+// ---- the persistent pitch conv (conv_p2p_f16_ps_kernel): one workgroup per CU walks the row tiles ----
+// What one launch reads and writes.  The forms decide the kernel instance and whether a shape qualifies (p2p_ps_plan); the pointers
+// only matter to the launch.
+enum class P2pIn : unsigned char {
+    Planes,           // the channels-last f16 plane the conv before it wrote
+    Src,              // NCHW f32: the pitch stream (c0 channels) | the up_sixth map (c1 channels of h1 rows), assembled by the kernel's loader
+    SrcFramesMajor,   // ... with the one pitch-stream channel stored [clip][T][H] (ake_pcnet_forward_frames_major_f32)
+    SrcF16x4,         // ... both as layer 0 left them: the CQT as f16 hi | lo words (Buffers::melh), the map as f16 x 4 words (Layer0Args::psix_h)
+};
+enum class P2pOut : unsigned char {
+    Plane,            // a channels-last f16 plane for the next conv
+    Nchw,             // the pitch tensor [clip][8][H][T] f32
+    Semi,             // fused with the semitone conv: the semitone maps [clip][8][H / 3][T] (the pitch tensor is never written)
+    SemiFold,         // ... and with the maximum over the octaves: channels [fold_coff, fold_coff + 8) of the concat buffer [clip][dst_ctot][12][T]
+};
+struct P2pPsIo {
+    P2pIn in = P2pIn::Planes;
+    const unsigned short* planes = nullptr;       // in == Planes
+    Src src{};                                    // every other input form
+    P2pOut out = P2pOut::Plane;
+    unsigned short* plane = nullptr;              // out == Plane
+    float* dst = nullptr;                         // every other output form
+    int dst_ctot = 0;                             // channels of the tensor `dst` points into
+    int fold_coff = 0;                            // out == SemiFold
+    const PackedConv* semi = nullptr;             // out == Semi / SemiFold: the semitone conv
+};
+
+// Launch geometry of one such conv for `batch` clips of H x T maps; ok == false: the shape does not qualify and the tiled
+// conv_p2p_f16_kernel runs instead.  Taken for even frame counts and enough tiles to give every CU at least two (always for the forms
+// fused with the semitone conv; the folding form wants four units per CU: a unit is n_oct tiles in a row, small batches keep the
+// tile-parallel form).  ws16: the workspace (hence every buffer carved from it) is 16-byte aligned.  Launches nothing.
+struct P2pPsPlan {
+    bool ok = false;
+    P2pIn in = P2pIn::Planes;
+    P2pOut out = P2pOut::Plane;
+    int R = 0, plane_pos = 0, n_row_tiles = 0, n_tiles = 0, n_oct = 0, n_units = 0, grid = 0;
+    size_t lds = 0;
+};
+P2pPsPlan p2p_ps_plan(P2pIn in, int c0, int c1, P2pOut out, int dst_ctot, bool semi_frags, int batch, int H, int T, bool ws16) {
+    P2pPsPlan g;
+    g.in = in; g.out = out;
+    const bool semi = out == P2pOut::Semi || out == P2pOut::SemiFold;
+    g.R = p2p_ps_rows(H, T, semi, &g.plane_pos, &g.lds);
+    if (g.R <= 0 || batch < 1) return g;
+    const int n_cus = device_cus();
+    if (in != P2pIn::Planes) {
+        if (out != P2pOut::Plane || c0 < 1 || c0 + c1 > 8) return g;
+        if (in != P2pIn::Src && c0 != 1) return g;
+        if (in == P2pIn::SrcF16x4 && (c1 < 1 || c1 > 4)) return g;
+    }
+    if (semi && !semi_frags) return g;
+    g.n_row_tiles = (H + g.R - 1) / g.R;
+    g.n_tiles = g.n_row_tiles * batch;
+    if (out == P2pOut::SemiFold) {
+        if (H % 36 || 36 % g.R) return g;
+        g.n_oct = H / 36; g.n_units = batch * (36 / g.R);
+        if (g.n_units < 4 * n_cus) return g;
+    }
+    if (!semi && g.n_tiles < 2 * n_cus) return g;
+    if (out == P2pOut::Nchw &&      // 16-byte stores of 4 consecutive frames
+        ((g.R * T) % 4 || (static_cast<long long>(H) * T) % 4 || (static_cast<long long>(dst_ctot) * H * T) % 4 || !ws16))
+        return g;
+    // two workgroups per CU when the LDS allows it (the kernel is built for 4 waves per SIMD): one's epilogue (vector work) and
+    // barrier waits run under the other's multiply loop (bound by its LDS reads)
+    const int wg_per_cu = ((in == P2pIn::Planes || in == P2pIn::SrcF16x4) && g.lds <= 80 * 1024 && g.n_tiles >= 4 * n_cus) ? 2 : 1;
+    g.grid = std::min(wg_per_cu * (n_cus / 8 * 8), (g.n_tiles + 7) / 8 * 8);
+    g.ok = true;
+    return g;
+}
+
+// the launch of a planned conv; a plan that does not cover the call is a broken promise of the route, not a fall-back
+int run_p2p_f16_ps(const ake_pcnet* n, const PackedConv& pc, const P2pPsPlan& g, const P2pPsIo& io, int batch, int H, int T, hipStream_t s, const char* name) {
+    AKE_REQUIRE(g.ok, AKE_ERR_STATE, "conv %s: the route sent a shape to the persistent kernel that does not qualify for it", name);
+    AKE_REQUIRE(g.in == io.in && g.out == io.out, AKE_ERR_STATE, "conv %s: the route planned the persistent kernel for another input / output form", name);
+    AKE_REQUIRE(g.n_tiles == g.n_row_tiles * batch, AKE_ERR_STATE, "conv %s: the route planned the persistent kernel for another chunk than these %d clips", name, batch);
+    const bool semi = io.out == P2pOut::Semi || io.out == P2pOut::SemiFold;
+    AKE_REQUIRE((io.in == P2pIn::Planes ? io.planes != nullptr : io.src.p0 != nullptr) && (io.out == P2pOut::Plane ? io.plane != nullptr : io.dst != nullptr) &&
+                    (!semi || (io.semi && io.semi->bf_off >= 0)) && (io.in != P2pIn::SrcF16x4 || io.src.p1),
+                AKE_ERR_STATE, "conv %s: the persistent kernel's planned form lacks a buffer", name);
+    AKE_REQUIRE(io.out != P2pOut::Nchw || !(reinterpret_cast<uintptr_t>(io.dst) & 15), AKE_ERR_STATE, "conv %s: the route planned 16-byte stores to an unaligned tensor", name);
     P2pPsArgs a;
     std::memset(&a, 0, sizeof(a));
-    size_t lds = 0;
-    a.R = p2p_ps_rows(H, T, semi_pc != nullptr, &a.plane_pos, &lds);
-    if (a.R <= 0) return false;
-    const int n_cus = device_cus();
-    a.xh = xh; a.bfrag = n->bf_frags_dev + pc.bf_off; a.bias = n->blob_dev + pc.b_off;
-    if (nchw) {
-        if (dst_nchw || nchw->c0 < 1 || nchw->c0 + nchw->c1 > 8) return false;
-        a.p = nchw->p0; a.c0 = nchw->c0; a.u = nchw->p1 ? nchw->p1 : nchw->p0; a.c1 = nchw->p1 ? nchw->c1 : 0; a.h1 = nchw->h1 > 0 ? nchw->h1 : 1;
-        if (p_frames_major && nchw->c0 != 1) return false;
-        a.p_fm = p_frames_major ? 1 : 0;
-        if (u_f16x4) {
-            if (nchw->c0 != 1 || !nchw->p1 || nchw->c1 > 4) return false;
-            a.uh = reinterpret_cast<const uint2*>(nchw->p1);
-            a.ph = reinterpret_cast<const unsigned int*>(nchw->p0);
-            a.p_fm = 0;
+    a.R = g.R; a.plane_pos = g.plane_pos;
+    a.bfrag = n->bf_frags_dev + pc.bf_off; a.bias = n->blob_dev + pc.b_off;
+    if (io.in == P2pIn::Planes) a.xh = io.planes;
+    else {
+        const Src& x = io.src;
+        a.p = x.p0; a.c0 = x.c0; a.u = x.p1 ? x.p1 : x.p0; a.c1 = x.p1 ? x.c1 : 0; a.h1 = x.h1 > 0 ? x.h1 : 1;
+        a.p_fm = io.in == P2pIn::SrcFramesMajor ? 1 : 0;
+        if (io.in == P2pIn::SrcF16x4) {
+            a.uh = reinterpret_cast<const uint2*>(x.p1);
+            a.ph = reinterpret_cast<const unsigned int*>(x.p0);
         }
-    } else if (p_frames_major || u_f16x4) return false;
-    a.dst = dst_nchw; a.dst_clip_stride = static_cast<long long>(dst_ctot) * (semi_pc ? H / 3 : H) * T; a.oh = oh;
-    if (semi_pc) {
-        if (!dst_nchw || semi_pc->bf_off < 0) return false;
-        a.sfrag = n->bf_frags_dev + semi_pc->bf_off; a.sbias = n->blob_dev + semi_pc->b_off;
     }
+    a.dst = io.dst; a.dst_clip_stride = static_cast<long long>(io.dst_ctot) * (semi ? H / 3 : H) * T; a.oh = io.plane;
+    if (semi) { a.sfrag = n->bf_frags_dev + io.semi->bf_off; a.sbias = n->blob_dev + io.semi->b_off; }
     a.H = H; a.T = T; a.J = T / 2; a.Tp = p2p_pitch(a.J);
-    a.n_row_tiles = (H + a.R - 1) / a.R;
-    a.n_tiles = a.n_row_tiles * batch;
-    const bool fold = fold_coff >= 0;
-    if (fold) {
-        if (!semi_pc || H % 36 || 36 % a.R) return false;
-        a.n_oct = H / 36; a.n_units = batch * (36 / a.R);
-        if (a.n_units < 4 * n_cus) return false;                      // a unit is n_oct tiles in a row: small batches keep the tile-parallel form
-        a.dst = dst_nchw + static_cast<long long>(fold_coff) * 12 * T;
-        a.dst_clip_stride = static_cast<long long>(dst_ctot) * 12 * T;
-    }
-    if (!semi_pc && a.n_tiles < 2 * n_cus) return false;
-    if (dst_nchw && !semi_pc) {   // 16-byte stores of 4 consecutive frames
-        if ((a.R * T) % 4 || (static_cast<long long>(H) * T) % 4 || a.dst_clip_stride % 4 || (reinterpret_cast<uintptr_t>(dst_nchw) & 15)) return false;
+    a.n_row_tiles = g.n_row_tiles; a.n_tiles = g.n_tiles;
+    if (io.out == P2pOut::SemiFold) {
+        a.n_oct = g.n_oct; a.n_units = g.n_units;
+        a.dst = io.dst + static_cast<long long>(io.fold_coff) * 12 * T;
+        a.dst_clip_stride = static_cast<long long>(io.dst_ctot) * 12 * T;
     }
     static ake::DeviceOnce attr_set;
     if (attr_set.need()) {
@@ -599,60 +653,78 @@ bool run_p2p_f16_ps(const ake_pcnet* n, const PackedConv& pc, const unsigned sho
                              reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<1, 0>), reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<1, 5>),
                              reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<1, 8>), reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<0, 0>),
                              reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<2, 0>), reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<1, 3>)};
-        for (const void* f : fns)
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
+        for (const void* f : fns) AKE_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set.mark();
     }
-    // two workgroups per CU when the LDS allows it (the kernel is built for 4 waves per SIMD): one's epilogue (vector work) and
-    // barrier waits run under the other's multiply loop (bound by its LDS reads)
-    if (dry_run) return true;                          // (the eligibility question of ake_pcnet_accepts_frames_major)
-    const int wg_per_cu = ((!nchw || a.uh) && lds <= 80 * 1024 && a.n_tiles >= 4 * n_cus) ? 2 : 1;
-    dim3 grid(std::min(wg_per_cu * (n_cus / 8 * 8), (a.n_tiles + 7) / 8 * 8)), block(512);
+    dim3 grid(g.grid), block(512);
     ake::ProfScope ps(name, s);
-    if (fold) hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<3, 0>), grid, block, lds, s, a);
-    else if (semi_pc) hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<2, 0>), grid, block, lds, s, a);
-    else if (dst_nchw) hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<0, 0>), grid, block, lds, s, a);
-    else if (nchw && a.uh) hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<1, 3>), grid, block, lds, s, a);
-    else if (nchw && a.c0 + a.c1 <= 5) hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<1, 5>), grid, block, lds, s, a);
-    else if (nchw) hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<1, 8>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<1, 0>), grid, block, lds, s, a);
-    return true;
+    switch (io.out) {
+        case P2pOut::SemiFold: hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<3, 0>), grid, block, g.lds, s, a); break;
+        case P2pOut::Semi: hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<2, 0>), grid, block, g.lds, s, a); break;
+        case P2pOut::Nchw: hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<0, 0>), grid, block, g.lds, s, a); break;
+        case P2pOut::Plane:
+            if (io.in == P2pIn::Planes) hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<1, 0>), grid, block, g.lds, s, a);
+            else if (io.in == P2pIn::SrcF16x4) hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<1, 3>), grid, block, g.lds, s, a);
+            else if (a.c0 + a.c1 <= 5) hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<1, 5>), grid, block, g.lds, s, a);
+            else hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<1, 8>), grid, block, g.lds, s, a);
+            break;
+    }
+    return AKE_OK;
 }
 
-// 7 x 7 circular pitch convolution with f32-equivalent products (conv_p2p_f16x3_kernel): train-mode forward (in_aff, bias, statistics)
-// and data gradient (none of them).  false when the shape does not qualify: the caller then runs conv_mfma_kernel.
-bool run_p2p_f16x3(const ake_pcnet* n, long long frag_off, const Src& src, const float* in_aff, const float* bias, int batch, int H, int T, float* dst,
-                   int cout, double* stats, int stats_stride, hipStream_t s, const char* name, const unsigned int* in_amax = nullptr, bool lrelu = false) {
-    if (frag_off < 0 || T < 2 || (T & 1) || src.c0 < 1 || src.c0 + src.c1 > 8 || cout > 8 || src.ctot0 != 0) return false;
+// ---- 7 x 7 circular pitch convolution with f32-equivalent products (conv_p2p_f16x3_kernel, persistent): train-mode forward (in_aff,
+// bias, statistics), f32x3 inference (bias, LeakyReLU) and data gradient (none of them) ----
+// Launch geometry for c0 + c1 input and cout output channels; ok == false: the shape does not qualify (conv_mfma_kernel runs it).
+// dst16: the output tensor is 16-byte aligned.  Launches nothing; a convolution also needs its f16 x 3 fragments (PackedConv::bf_off).
+struct P2pX3Plan {
+    bool ok = false;
+    int R = 0, plane_pos = 0, n_row_tiles = 0, n_tiles = 0, grid = 0;
+    size_t lds = 0;
+};
+P2pX3Plan p2p_f16x3_plan(int c0, int c1, int cout, int batch, int H, int T, bool dst16) {
+    P2pX3Plan g;
+    if (T < 2 || (T & 1) || c0 < 1 || c0 + c1 > 8 || cout > 8 || batch < 1) return g;
+    const int n_cus = device_cus();
+    if (n_cus < 8) return g;
+    const int Tp = p2p_pitch(T / 2);
+    auto plane_of = [&](int R) { return ((R + 6) * Tp + 63) / 64 * 64; };
+    auto lds_of = [&](int R) { return (static_cast<size_t>(4) * plane_of(R) + 8 * kP2pMT * kP2pPsStage) * sizeof(uint4); };
+    int R = std::max(1, std::min(H, 8 * kP2pMT * 16 / (T / 2)));
+    while (R >= 1 && (lds_of(R) > 156 * 1024 || plane_of(R) > 3 * 512)) --R;         // (the loader: three positions per thread)
+    if (R < 1 || H < R + 6) return g;
+    if ((R * T) % 4 || (static_cast<long long>(H) * T) % 4 || (static_cast<long long>(cout) * H * T) % 4 || !dst16) return g;
+    g.R = R; g.plane_pos = plane_of(R); g.lds = lds_of(R);
+    g.n_row_tiles = (H + R - 1) / R;
+    g.n_tiles = g.n_row_tiles * batch;
+    g.grid = std::min(n_cus / 8 * 8, (g.n_tiles + 7) / 8 * 8);
+    g.ok = true;
+    return g;
+}
+
+int run_p2p_f16x3(const ake_pcnet* n, const P2pX3Plan& g, long long frag_off, const Src& src, const float* in_aff, const float* bias, int batch, int H, int T,
+                  float* dst, int cout, double* stats, int stats_stride, hipStream_t s, const char* name, const unsigned int* in_amax = nullptr, bool lrelu = false) {
+    AKE_REQUIRE(g.ok && frag_off >= 0 && src.ctot0 == 0, AKE_ERR_STATE, "conv %s: a convolution that does not qualify was sent to the f16 x 3 persistent kernel", name);
+    AKE_REQUIRE(g.n_tiles == g.n_row_tiles * batch, AKE_ERR_STATE, "conv %s: the f16 x 3 persistent kernel was planned for another batch than these %d clips", name, batch);
+    AKE_REQUIRE(!(reinterpret_cast<uintptr_t>(dst) & 15), AKE_ERR_STATE, "conv %s: the f16 x 3 persistent kernel was planned for 16-byte stores to an unaligned tensor", name);
     P2pTrArgs a;
     std::memset(&a, 0, sizeof(a));
-    const int n_cus = device_cus();
-    if (n_cus < 8) return false;
     a.J = T / 2; a.Tp = p2p_pitch(a.J);
-    auto plane_of = [&](int R) { return ((R + 6) * a.Tp + 63) / 64 * 64; };
-    auto lds_of = [&](int R) { return (static_cast<size_t>(4) * plane_of(R) + 8 * kP2pMT * kP2pPsStage) * sizeof(uint4); };
-    int R = std::max(1, std::min(H, 8 * kP2pMT * 16 / a.J));
-    while (R >= 1 && (lds_of(R) > 156 * 1024 || plane_of(R) > 3 * 512)) --R;         // (the loader: three positions per thread)
-    if (R < 1 || H < R + 6) return false;
-    a.R = R; a.plane_pos = plane_of(R);
+    a.R = g.R; a.plane_pos = g.plane_pos;
     a.H = H; a.T = T;
-    a.n_row_tiles = (H + R - 1) / R;
-    a.n_tiles = a.n_row_tiles * batch;
-    const long long clip_stride = static_cast<long long>(cout) * H * T;
-    if ((R * T) % 4 || (static_cast<long long>(H) * T) % 4 || clip_stride % 4 || (reinterpret_cast<uintptr_t>(dst) & 15)) return false;
+    a.n_row_tiles = g.n_row_tiles; a.n_tiles = g.n_tiles;
     a.p = src.p0; a.c0 = src.c0; a.u = src.p1 ? src.p1 : src.p0; a.c1 = src.p1 ? src.c1 : 0; a.h1 = src.h1 > 0 ? src.h1 : 1;
     a.in_aff = in_aff; a.bfrag = n->bf_frags_dev + frag_off; a.bias = bias;
-    a.dst = dst; a.dst_clip_stride = clip_stride; a.cout = cout;
+    a.dst = dst; a.dst_clip_stride = static_cast<long long>(cout) * H * T; a.cout = cout;
     a.stats = stats; a.stats_stride = stats_stride; a.in_amax = in_amax; a.lrelu = lrelu ? 1 : 0;
     static ake::DeviceOnce attr_set;
     if (attr_set.need()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_p2p_f16x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
+        AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_p2p_f16x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set.mark();
     }
-    dim3 grid(std::min(n_cus / 8 * 8, (a.n_tiles + 7) / 8 * 8)), block(512);
+    dim3 grid(g.grid), block(512);
     ake::ProfScope ps(name, s);
-    hipLaunchKernelGGL(conv_p2p_f16x3_kernel, grid, block, lds_of(R), s, a);
-    return true;
+    hipLaunchKernelGGL(conv_p2p_f16x3_kernel, grid, block, g.lds, s, a);
+    return AKE_OK;
 }
 
 // semitone maps [clip][C][S][T] -> channels [coff, coff + C) of the concat buffer [clip][ctot][12][T]: max over the octaves
@@ -1003,6 +1075,179 @@ int plan_buffers(const ake_pcnet* n, int batch, int chunk, int frames, void* ws,
     }
     b->bytes = ake::align_up(cv.off, 256);
     return AKE_OK;
+}
+
+// ---- the route: which kernel form every stage of one forward call launches -------------------------------------------------------
+// Decided once per call by build_route() from the handle, the mode, the shape, the two alignments that are conditions and
+// ake_debug_keep_taps; plain data, no allocation.  Fwd launches what it says, ake_pcnet_accepts_frames_major returns its flag and the
+// debug taps answer from it, so none of them can disagree about what was written where.  It does not touch the workspace layout
+// (plan_buffers knows nothing of it).
+enum class L0Form : unsigned char { Generic, FusedValu, FusedMfma };       // layer 0 + layer 1's up_sixth: per-stage kernels | layer0_fused_kernel | layer0_mfma_kernel
+enum class PStack : unsigned char { Generic, F16x3, F16 };                 // a layer's pitch convs: conv_mfma_kernel | conv_p2p_f16x3_kernel where `x3_convs` says | the f16 kernels
+enum class PcStack : unsigned char { Generic, F16x3, Bf16, Fused };        // the last pitch-class stack: conv_mfma_kernel | conv_pc_f16x3 where `pc_x3_convs` says | conv_pc_bf16_kernel | pc2pc_fused_kernel
+enum class HeadForm : unsigned char { Generic, Bf16First, Head1, Fused };  // key / tonic heads: conv_mfma_kernel | bf16 first conv | + conv_head1_bf16_kernel | heads_fused_kernel
+
+struct Layer0Plan {
+    L0Form form = L0Form::Generic;
+    int RP = 0, RPp = 0;
+    size_t lds = 0;
+};
+
+struct Route {
+    bool frames_major = false;       // the call was asked to read mel frames-major and every reader of mel takes it
+    Layer0Plan l0;
+    bool psix_f16 = false;           // layer 0 leaves layer 1's up_sixth map as f16 x 4 words in psix[1] (and the CQT in melh) for conv_p2p_f16_ps_kernel<1, 3>
+    int chunk_clips[2] = {0, 0};     // clips of a full pitch_chunk call and of the remainder call (0: none); `k` below indexes them
+    struct Pitch {                   // layers >= 1
+        PStack stack = PStack::Generic;
+        unsigned x3_convs = 0;       // F16x3: bit j = conv j runs on conv_p2p_f16x3_kernel
+        struct PerChunk {
+            P2pPsPlan first, mid, last;   // F16: the persistent form of the first / an inner / the last conv (!ok: the tiled conv_p2p_f16_kernel);
+                                          // last.out: plain (Nchw), semitone conv fused (Semi), semitone conv and fold fused (SemiFold)
+            P2pX3Plan x3[2];              // F16x3: geometry of conv 0 and of the later convs
+        } k[2];
+    } p[4];
+    PcStack pc = PcStack::Generic;
+    unsigned pc_x3_convs = 0;
+    HeadForm heads = HeadForm::Generic;
+    bool genre_bf = false;           // Head1 / Fused: the genre head rides in the same launches
+    bool heads_pool = false;         // Head1 / Fused: the masked mean + sigmoid ride in the launch
+    int heads_mt = 0;                // Fused: M-tiles per wave of phase A (heads_fused_kernel<MT>)
+    int T1 = 0, T2 = 0, TpB = 0;     // Head1 / Fused: frames after each head conv, phase B's patch pitch
+    size_t hf_lds = 0;               // Fused
+
+    int chunk_kind(int B) const { return B == chunk_clips[0] ? 0 : 1; }
+};
+
+// layer 0 as one launch per clip (default family, inference): which form fits, and its LDS geometry
+Layer0Plan layer0_plan(const ake_pcnet* n, int T0, bool mel16, bool mel_fm) {
+    const auto& c = n->cfg;
+    const int P = c.pitches, NF = c.n_filters;
+    Layer0Plan g;
+    if (c.num_layers < 2 || c.resblock || c.denseblock || c.p2pc_conv || c.stay_sixth || NF < 2 || NF > 4 || c.conv_layers < 1 || c.conv_layers > 4 || c.kernel_size != 7 || P % 36 || T0 < 1) return g;
+    const PackedConv& sp = n->semi[0];
+    if (sp.cin != 1 || sp.co != 1) return g;
+    bool mfma = c.precision == AKE_PRECISION_MIXED;      // (the MFMA form multiplies f16 x f16; f32x3: the exact-f32 VALU form)
+    for (int j = 0; j < c.conv_layers; ++j) {
+        const PackedConv& pc = n->pc2pc[0][j];
+        if (pc.co != 4 || pc.groups != 1 || pc.kh != 12 || pc.kw != 7 || pc.cout != NF || pc.cin != (j == 0 ? 1 : NF)) return g;
+        mfma = mfma && pc.l0_off >= 0;
+    }
+    if (n->dims[1].prev_pc != NF) return g;
+    g.RP = 4 * ((T0 + 3) / 4) + 8;
+    g.RPp = (T0 + 8 + 1) / 2 * 2;
+    const size_t lds_v = (static_cast<size_t>(9) * 12 * g.RP + static_cast<size_t>(P) * T0) * sizeof(float);   // maps + the clip's CQT
+    if (lds_v > 150 * 1024 || (static_cast<long long>(P) * T0) % 4 || !mel16) return g;
+    const size_t lds_m = (static_cast<size_t>(4) * 12 * g.RP + static_cast<size_t>(2) * 12 * g.RPp * 4 + static_cast<size_t>(P) * T0) * sizeof(float);
+    const bool take_mfma = mfma && lds_m <= 150 * 1024;
+    if (mel_fm && (!take_mfma || P % 4)) return g;        // only the MFMA form's loader transposes
+    g.form = take_mfma ? L0Form::FusedMfma : L0Form::FusedValu;
+    g.lds = take_mfma ? lds_m : lds_v;
+    return g;
+}
+
+// mel, ws: only their 16-byte alignment is read (null counts as aligned).  chunk: clips per pitch_chunk call.
+Route build_route(const ake_pcnet* n, bool train, int batch, int chunk, int frames, const float* mel, const void* ws, bool mel_fm) {
+    Route r;
+    const auto& c = n->cfg;
+    const int L = c.num_layers;
+    const bool ws16 = !(reinterpret_cast<uintptr_t>(ws) & 15);
+    int Tl[4];
+    for (int i = 0; i < L; ++i) Tl[i] = i < 2 ? frames : Tl[i - 1] / c.time_pool_size;
+    const int Tf = L > 1 ? Tl[L - 1] / c.time_pool_size : frames;
+    if (batch < 1 || chunk < 1 || Tf < 1) return r;
+    r.chunk_clips[0] = std::min(batch, chunk);
+    r.chunk_clips[1] = batch > chunk ? batch % chunk : 0;
+
+    // ---- layer 0 ----
+    if (!train && L > 1) r.l0 = layer0_plan(n, Tl[0], !(reinterpret_cast<uintptr_t>(mel) & 15), mel_fm);
+    // the up_sixth map as f16 x 4 when the conv that reads it is the persistent f16 kernel for every chunk of this batch (it rounds to f16
+    // itself otherwise: same values); psix[1]'s buffer holds either form
+    if (r.l0.form == L0Form::FusedMfma && !g_keep_taps && !c.pc2p_mem && n->dims[1].prev_p == 1 && p2p_uses_f16(n, 1, Tl[1])) {
+        r.psix_f16 = true;
+        for (int k = 0; k < 2 && r.psix_f16; ++k)
+            if (r.chunk_clips[k])
+                r.psix_f16 = p2p_ps_plan(P2pIn::SrcF16x4, 1, n->dims[1].prev_pc, P2pOut::Plane, n->dims[1].out_p, false, r.chunk_clips[k], c.pitches, Tl[1], ws16).ok;
+    }
+
+    // ---- pitch stacks of the layers >= 1 (--denseblock runs its own blocks, --resblock the f32 MFMA kernel) ----
+    const int P = c.stay_sixth ? c.pitches / 3 : c.pitches;
+    int cp = 1;
+    for (int i = 1; i < L && !c.denseblock && !c.resblock; ++i) {
+        const LayerDims& d = n->dims[i];
+        Route::Pitch& rp = r.p[i];
+        const int Ti = Tl[i], c0 = cp, c1 = c.pc2p_mem ? 0 : d.prev_pc;     // (--pc2p_mem: the summed map was added to the pitch stream)
+        if (!train && p2p_uses_f16(n, i, Ti)) {
+            rp.stack = PStack::F16;
+            const bool semi = p2p_fuses_semi(n, i, P, Ti);
+            for (int k = 0; k < 2; ++k) {
+                const int B = r.chunk_clips[k];
+                if (!B) continue;
+                const P2pIn in0 = (i == 1 && r.psix_f16) ? P2pIn::SrcF16x4 : ((mel_fm && i == 1) ? P2pIn::SrcFramesMajor : P2pIn::Src);
+                rp.k[k].first = p2p_ps_plan(in0, c0, c1, P2pOut::Plane, d.out_p, false, B, P, Ti, ws16);
+                rp.k[k].mid = p2p_ps_plan(P2pIn::Planes, 0, 0, P2pOut::Plane, d.out_p, false, B, P, Ti, ws16);
+                P2pPsPlan& last = rp.k[k].last;
+                if (semi) last = p2p_ps_plan(P2pIn::Planes, 0, 0, P2pOut::SemiFold, d.prev_pc + d.out_p, true, B, P, Ti, ws16);
+                if (semi && !last.ok) last = p2p_ps_plan(P2pIn::Planes, 0, 0, P2pOut::Semi, d.out_p, true, B, P, Ti, ws16);
+                if (!last.ok) last = p2p_ps_plan(P2pIn::Planes, 0, 0, P2pOut::Nchw, d.out_p, false, B, P, Ti, ws16);
+            }
+        } else if (!c.pc2p_mem && !c.stay_sixth && (train || (c.precision == AKE_PRECISION_F32X3 && !g_keep_taps))) {
+            // training: f16 x 3 on the persistent form (f32-equivalent products).  Inference in the f32x3 precision mode: the same kernel with
+            // the EVAL fragments (BatchNorm folded; three products: f32-equivalent to 2^-22) and LeakyReLU in its epilogue
+            for (int k = 0; k < 2; ++k) {
+                const int B = r.chunk_clips[k];
+                if (!B) continue;
+                rp.k[k].x3[0] = p2p_f16x3_plan(c0, c1, d.out_p, B, P, Ti, ws16);
+                rp.k[k].x3[1] = p2p_f16x3_plan(d.out_p, 0, d.out_p, B, P, Ti, ws16);
+            }
+            for (int j = 0; j < c.conv_layers && j < 32; ++j)          // (eligibility does not depend on the clip count)
+                if ((train ? n->p2p_t[i][j] : n->p2p[i][j]).bf_off >= 0 && rp.k[0].x3[j > 0].ok) rp.x3_convs |= 1u << j;
+            if (rp.x3_convs) rp.stack = PStack::F16x3;
+        }
+        cp = d.out_p;
+    }
+    r.frames_major = mel_fm && !train && L == 2 && !c.resblock && !c.denseblock && !c.pc2p_mem && !c.p2pc_conv && !c.stay_sixth && !c.local &&
+                     batch <= chunk && r.l0.form == L0Form::FusedMfma && r.p[1].stack == PStack::F16 && r.p[1].k[0].first.ok;
+
+    // ---- the last layer's pitch-class stack ----
+    const int i = L - 1, Ti = Tl[i];
+    if (!train && L > 1 && !c.denseblock && pc2pc_fuses(n, i, Ti)) r.pc = PcStack::Fused;
+    else if (!train && pc2pc_uses_bf16(n, i, Ti)) r.pc = PcStack::Bf16;
+    else if (train && L > 1 && !c.resblock && !c.denseblock) {
+        for (int j = 0; j < c.conv_layers && j < 32; ++j)
+            if (pc_f16x3_ok(n->pc2pc_t[i][j], Ti, true)) r.pc_x3_convs |= 1u << j;
+        if (r.pc_x3_convs) r.pc = PcStack::F16x3;
+    }
+
+    // ---- heads (training keeps its own per-conv choices in Fwd::tail) ----
+    // key / tonic heads: the first convolution (16 -> 32 channels, most of a head's work) on the bf16 kernel
+    const bool head_bf = !train && L > 1 && n->final_ch == 16 && c.head_layers >= 2 && n->head_key[0].bf_off >= 0 && n->head_tonic[0].bf_off >= 0 &&
+                         Tf <= kPcBf16MaxFrames;
+    if (!head_bf) return r;
+    r.heads = HeadForm::Bf16First;
+    // two-conv heads: conv0 leaves its 32 channels as channels-last planes and ONE launch of conv_head1_bf16_kernel finishes both maps
+    r.T1 = Tf - (c.kernel_size - 1); r.T2 = r.T1 - (c.kernel_size - 1);
+    const int T1 = r.T1, T2 = r.T2;
+    if (!(c.head_layers == 2 && n->head_key[1].bf_off >= 0 && n->head_tonic[1].bf_off >= 0 && T2 > 0 && (12 * ((T2 + 15) / 16) + 15) / 16 <= kHead1MT)) return r;
+    r.heads = HeadForm::Head1;
+    r.genre_bf = c.genre && n->head_genre.size() == 2 && n->head_genre[0].bf_off >= 0 && n->head_genre[1].bf_off >= 0 && n->head_genre[0].kh == 1 &&
+                 n->head_genre[1].kh == 2;
+    r.heads_pool = c.local == 0;
+    // ... and when the stack above ran as one launch both convolutions of a head run as ONE launch too (heads_fused_kernel): the 32 hidden
+    // channels stay in LDS.  ake_debug_keep_taps(1), other head depths and shapes whose patches do not fit keep the two launches.
+    r.TpB = 16 * ((T2 + 15) / 16 - 1) + 22;
+    r.hf_lds = std::max({(static_cast<size_t>(2) * 12 * (T1 + 8) * 2 + 2 * 4 * 2 * 2 * 64) * sizeof(uint4),      // phase A: patch + weight ring
+                         static_cast<size_t>(2) * 12 * r.TpB * 4 * sizeof(uint4),                                // phase B: patch,
+                         static_cast<size_t>(8) * kHead1MT * 4 * 64 * sizeof(float)}) +                          // then the partial tiles
+               static_cast<size_t>(12) * T2 * sizeof(float);                                                     // the finished map
+    if (r.pc == PcStack::Fused && !g_keep_taps && c.local == 0 && n->head_key[0].cout == 32 && n->head_tonic[0].cout == 32 && n->head_key[0].kh == 12 &&
+        n->head_tonic[0].kh == 12 && n->head_key[1].kh == 12 && n->head_tonic[1].kh == 12 && (!r.genre_bf || n->head_genre[0].cout == 32) &&
+        (12 * T1 + 15) / 16 <= 32 && r.hf_lds <= 150 * 1024) {
+        r.heads = HeadForm::Fused;
+        // phase A's M-tiles over the 8 waves: three each where 24 cover the hidden map (12 x 32 positions and fewer), else four
+        r.heads_mt = (12 * T1 + 15) / 16 <= 24 ? 3 : 4;
+    }
+    return r;
 }
 
 }  // namespace
@@ -1880,9 +2125,7 @@ struct Fwd {
     Buffers& b;
     hipStream_t s;
     bool train;
-    bool mel_fm = false;             // mel is frames-major [clip][T][P] (ake_pcnet_forward_frames_major_f32): only the fused default path can read it
-    int chunk = 0;                   // clips per pitch_chunk call (the last one may be shorter)
-    bool psix_f16 = false;           // layer 0's launch left layer 1's up_sixth map as f16 x 4 words in psix[1] (Layer0Args::psix_h), for conv_p2p_f16_ps_kernel<1, 3>
+    const Route& r;                  // what this call launches (build_route)
 
     int bn_of(const std::string& name) const { return n->bn_index.at(name); }
 
@@ -2169,30 +2412,27 @@ struct Fwd {
         return AKE_OK;
     }
 
-    // inference, default family: the whole of phase A as one launch, one workgroup per clip (layer0_fused_kernel)
-    bool layer0_fused(const float* mel, int B, bool dry_run = false) {
+    // inference, default family: the whole of phase A as one launch, one workgroup per clip (the form and geometry are the route's)
+    int layer0_fused(const float* mel, int B) {
         const auto& c = n->cfg;
         const int P = c.pitches, T0 = b.Tl[0], NF = c.n_filters;
-        if (c.resblock || c.denseblock || c.p2pc_conv || c.stay_sixth || NF < 2 || NF > 4 || c.conv_layers < 1 || c.conv_layers > 4 || c.kernel_size != 7 || P % 36 || T0 < 1) return false;
+        const bool take_mfma = r.l0.form == L0Form::FusedMfma;
+        AKE_REQUIRE(r.l0.form != L0Form::Generic && r.l0.lds > 0 && !(reinterpret_cast<uintptr_t>(mel) & 15), AKE_ERR_STATE,
+                    "pcnet: the route sent layer 0 to its one-launch form, which this call does not qualify for");
+        AKE_REQUIRE(!r.frames_major || take_mfma, AKE_ERR_STATE, "pcnet: the route promised the frames-major input to a layer-0 form that cannot read it");
+        AKE_REQUIRE(!r.psix_f16 || (take_mfma && b.melh), AKE_ERR_STATE, "pcnet: the route promised the f16 up_sixth map to a layer-0 form that does not write it");
         const PackedConv& sp = n->semi[0];
-        if (sp.cin != 1 || sp.co != 1) return false;
-        for (int j = 0; j < c.conv_layers; ++j) {
-            const PackedConv& pc = n->pc2pc[0][j];
-            if (pc.co != 4 || pc.groups != 1 || pc.kh != 12 || pc.kw != 7 || pc.cout != NF || pc.cin != (j == 0 ? 1 : NF)) return false;
-        }
         const LayerDims& d1 = n->dims[1];
-        if (d1.prev_pc != NF) return false;
         Layer0Args a;
         std::memset(&a, 0, sizeof(a));
-        a.RP = 4 * ((T0 + 3) / 4) + 8;
-        const size_t lds = (static_cast<size_t>(9) * 12 * a.RP + static_cast<size_t>(P) * T0) * sizeof(float);   // maps + the clip's CQT
-        if (lds > 150 * 1024 || (static_cast<long long>(P) * T0) % 4 || (reinterpret_cast<uintptr_t>(mel) & 15)) return false;
+        a.RP = r.l0.RP; a.RPp = r.l0.RPp;
         a.mel = mel; a.sw = n->blob_dev + sp.w_off; a.sb = n->blob_dev + sp.b_off;
         const int ctot1 = d1.prev_pc + d1.out_p;
         for (int j = 0; j < c.conv_layers; ++j) {
             const PackedConv& pc = n->pc2pc[0][j];
             const bool lastj = j == c.conv_layers - 1;
             a.w[j] = n->blob_dev + pc.w_off; a.b[j] = n->blob_dev + pc.b_off;
+            if (take_mfma) a.frag[j] = n->bf_frags_dev + pc.l0_off;
             a.dst[j] = lastj ? b.cat[1] : ((j & 1) ? b.pcb[0] : b.pca[0]);
             a.dst_clip_stride[j] = static_cast<long long>(lastj ? ctot1 : NF) * 12 * T0;
         }
@@ -2201,39 +2441,17 @@ struct Fwd {
         a.H = P; a.T = T0; a.NF = NF; a.n_conv = c.conv_layers;
         static ake::DeviceOnce attr_set;
         if (attr_set.need()) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(layer0_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(layer0_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
-                return false;
+            AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(layer0_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+            AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(layer0_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
             attr_set.mark();
         }
-        // the convolution stack on bf16 MFMA when the fragments exist and the maps fit (f32x3: the exact-f32 VALU form)
-        bool mfma = c.precision == AKE_PRECISION_MIXED;      // (the MFMA form multiplies f16 x f16)
-        for (int j = 0; j < c.conv_layers; ++j) {
-            mfma = mfma && n->pc2pc[0][j].l0_off >= 0;
-            if (mfma) a.frag[j] = n->bf_frags_dev + n->pc2pc[0][j].l0_off;
-        }
-        a.RPp = (T0 + 8 + 1) / 2 * 2;
-        const size_t lds_m = (static_cast<size_t>(4) * 12 * a.RP + static_cast<size_t>(2) * 12 * a.RPp * 4 + static_cast<size_t>(P) * T0) * sizeof(float);
-        const bool take_mfma = mfma && lds_m <= 150 * 1024;
-        if (mel_fm && (!take_mfma || P % 4)) return false;        // only the MFMA form's loader transposes
-        if (dry_run) return true;
-        a.mel_fm = mel_fm ? 1 : 0;
+        a.mel_fm = r.frames_major ? 1 : 0;
         a.taps = g_keep_taps ? 1 : 0;
-        // the up_sixth map as f16 x 4 when the conv that reads it is the persistent f16 kernel for every chunk of this batch (it rounds to f16
-        // itself otherwise: same values); psix[1]'s buffer holds either form
-        psix_f16 = false;
-        if (take_mfma && b.melh && !g_keep_taps && !c.pc2p_mem && d1.prev_p == 1 && chunk > 0 && p2p_uses_f16(n, 1, b.Tl[1])) {
-            Src sd{mel, 1, b.psix[1], d1.prev_pc, 36};
-            unsigned short* oh = reinterpret_cast<unsigned short*>(b.pa[1]);
-            psix_f16 = run_p2p_f16_ps(n, n->p2p[1][0], nullptr, &sd, std::min(B, chunk), P, b.Tl[1], nullptr, d1.out_p, oh, nullptr, s, "", mel_fm, true, -1, true) &&
-                       (B <= chunk || B % chunk == 0 ||
-                        run_p2p_f16_ps(n, n->p2p[1][0], nullptr, &sd, B % chunk, P, b.Tl[1], nullptr, d1.out_p, oh, nullptr, s, "", mel_fm, true, -1, true));
-        }
-        if (psix_f16) { a.psix_h = reinterpret_cast<uint2*>(b.psix[1]); a.psix = nullptr; a.melh = b.melh; }
+        if (r.psix_f16) { a.psix_h = reinterpret_cast<uint2*>(b.psix[1]); a.psix = nullptr; a.melh = b.melh; }
         ake::ProfScope ps("layer0_fused_kernel", s);
-        if (take_mfma) hipLaunchKernelGGL(layer0_mfma_kernel, dim3(B), dim3(512), lds_m, s, a);
-        else hipLaunchKernelGGL(layer0_fused_kernel, dim3(B), dim3(512), lds, s, a);
-        return true;
+        if (take_mfma) hipLaunchKernelGGL(layer0_mfma_kernel, dim3(B), dim3(512), r.l0.lds, s, a);
+        else hipLaunchKernelGGL(layer0_fused_kernel, dim3(B), dim3(512), r.l0.lds, s, a);
+        return AKE_OK;
     }
 
     // Phase A, whole batch: layer 0 (models.py:361-369) and layer 1's up_sixth (models.py:372-374).
@@ -2241,8 +2459,7 @@ struct Fwd {
         const auto& c = n->cfg;
         const int L = c.num_layers, P = c.pitches, T0 = b.Tl[0];
         int rc;
-        if (!train && L > 1 && layer0_fused(mel, B)) return AKE_OK;
-        AKE_REQUIRE(!mel_fm, AKE_ERR_UNSUPPORTED, "pcnet: this configuration does not take the frames-major input (ake_pcnet_accepts_frames_major)");
+        if (r.l0.form != L0Form::Generic) return layer0_fused(mel, B);
         if (c.stay_sixth && L > 1 && train) {   // training: the RAW semitone map (semi_raw[0]) + its pending table are the pitch stream
             if ((rc = semi(0, mel, nullptr, B, P, T0, b.fold0, 1, 0, nullptr))) return rc;
         } else if (c.stay_sixth && L > 1) {   // models.py:366-367: the activated semitone map is the pitch stream from here on; its fold feeds pc2pc
@@ -2386,10 +2603,9 @@ struct Fwd {
             float* out_aff = nullptr;
             // inference: the stack runs on f16 MFMA (f16 activations x hi + lo f16 weights, see conv_p2p_f16_kernel); the activations
             // between its convs are ONE channels-last f16 plane (16 B per position) in the same ping-pong buffers
-            const bool bf = !train && p2p_uses_f16(n, i, Ti);
-            AKE_REQUIRE(!mel_fm || (bf && i == 1 && L == 2 && !c.resblock && !c.pc2p_mem && !c.stay_sixth), AKE_ERR_UNSUPPORTED,
-                        "pcnet: this configuration does not take the frames-major input (ake_pcnet_accepts_frames_major)");
-            bool fused_semi = false, fused_fold = false;
+            const Route::Pitch& rp = r.p[i];
+            const Route::Pitch::PerChunk& rk = rp.k[r.chunk_kind(B)];
+            P2pOut last_out = P2pOut::Nchw;       // what the stack's last launch left: the pitch tensor, the semitone maps, or the folded maps in `cat`
             if (c.resblock && train) {
                 if ((rc = res_stack_train(n->p2p_t[i], m + "p2p.layer.", 0, sdesc, in_aff, B, P, Ti, b.pst[i], b.aff_pst[i], nullptr, 0, "conv_mfma_kernel/p2p")))
                     return rc;
@@ -2401,60 +2617,41 @@ struct Fwd {
             for (int j = 0; j < c.conv_layers && !c.resblock; ++j) {
                 out = train ? b.pst[i][j] : ((j & 1) ? b.pb[i] : b.pa[i]);
                 out_aff = !train ? nullptr : b.aff_pst[i][j];
-                if (bf) {
-                    unsigned short* oh = reinterpret_cast<unsigned short*>(out);
+                if (rp.stack == PStack::F16) {
                     const bool last_conv = j == c.conv_layers - 1;
-                    if (j == 0) {   // the stack's input (pitch stream | repeated up_sixth output) is assembled by the kernel's own loader
-                        if (i == 1 && psix_f16) {   // layer 0 left the up_sixth map as f16 x 4 words (8 bytes per position, clip stride 36 T words)
-                            Src sh{reinterpret_cast<const float*>(b.melh + static_cast<size_t>(c0) * P * Ti), 1,
-                                   reinterpret_cast<const float*>(reinterpret_cast<const uint2*>(b.psix[1]) + static_cast<size_t>(c0) * 36 * Ti), d.prev_pc, 36};
-                            AKE_REQUIRE(run_p2p_f16_ps(n, n->p2p[i][0], nullptr, &sh, B, P, Ti, nullptr, d.out_p, oh, nullptr, s, "conv_p2p_f16_kernel", false, false, -1, true),
-                                        AKE_ERR_STATE, "pcnet: the f16 up_sixth map has no reader for this chunk (%d clips)", B);
-                            continue;
-                        }
-                        if (run_p2p_f16_ps(n, n->p2p[i][0], nullptr, &sdesc, B, P, Ti, nullptr, d.out_p, oh, nullptr, s, "conv_p2p_f16_kernel", mel_fm && i == 1)) continue;
-                        AKE_REQUIRE(!mel_fm, AKE_ERR_UNSUPPORTED, "pcnet: this shape does not take the frames-major input (ake_pcnet_accepts_frames_major)");
-                        if ((rc = run_p2p_f16(n, n->p2p[i][0], nullptr, &sdesc, B, P, Ti, nullptr, d.out_p, oh, s, "conv_p2p_f16_kernel")))
-                            return rc;
-                    } else {
-                        const unsigned short* xh = reinterpret_cast<const unsigned short*>(((j - 1) & 1) ? b.pb[i] : b.pa[i]);
-                        if (last_conv && p2p_fuses_semi(n, i, P, Ti) &&
-                            run_p2p_f16_ps(n, n->p2p[i][j], xh, nullptr, B, P, Ti, cat, ctot, nullptr, &n->semi[i], s, "conv_p2p_f16_kernel", false, false,
-                                           d.prev_pc)) {
-                            fused_semi = fused_fold = true;    // semitone conv AND octave fold inside the launch: the folded maps are in `cat`
-                            continue;
-                        }
-                        if (last_conv && p2p_fuses_semi(n, i, P, Ti) &&
-                            run_p2p_f16_ps(n, n->p2p[i][j], xh, nullptr, B, P, Ti, out, d.out_p, nullptr, &n->semi[i], s, "conv_p2p_f16_kernel")) {
-                            fused_semi = true;    // `out` holds the semitone maps [clip][8][P / 3][T], not the pitch tensor
-                            continue;
-                        }
-                        if (run_p2p_f16_ps(n, n->p2p[i][j], xh, nullptr, B, P, Ti, last_conv ? out : nullptr, d.out_p, last_conv ? nullptr : oh, nullptr, s,
-                                            "conv_p2p_f16_kernel"))
-                            continue;
-                        if ((rc = run_p2p_f16(n, n->p2p[i][j], xh, nullptr, B, P, Ti, last_conv ? out : nullptr, d.out_p, last_conv ? nullptr : oh, s,
-                                               "conv_p2p_f16_kernel")))
-                            return rc;
+                    const P2pPsPlan& g = j == 0 ? rk.first : (last_conv ? rk.last : rk.mid);
+                    P2pPsIo io;
+                    io.in = g.in; io.out = g.out;
+                    io.dst_ctot = d.out_p;
+                    if (j > 0) io.planes = reinterpret_cast<const unsigned short*>(((j - 1) & 1) ? b.pb[i] : b.pa[i]);
+                    else if (g.in == P2pIn::SrcF16x4)   // layer 0 left the CQT and the up_sixth map as f16 words (8 bytes per position of the map, clip stride 36 T words)
+                        io.src = Src{reinterpret_cast<const float*>(b.melh + static_cast<size_t>(c0) * P * Ti), 1,
+                                     reinterpret_cast<const float*>(reinterpret_cast<const uint2*>(b.psix[1]) + static_cast<size_t>(c0) * 36 * Ti), d.prev_pc, 36};
+                    else io.src = sdesc;              // the stack's input (pitch stream | repeated up_sixth output) is assembled by the kernel's own loader
+                    switch (g.out) {
+                        case P2pOut::Plane: io.plane = reinterpret_cast<unsigned short*>(out); break;
+                        case P2pOut::Nchw: io.dst = out; break;
+                        case P2pOut::Semi: io.dst = out; io.semi = &n->semi[i]; break;       // `out` receives the semitone maps [clip][8][P / 3][T]
+                        case P2pOut::SemiFold: io.dst = cat; io.dst_ctot = ctot; io.fold_coff = d.prev_pc; io.semi = &n->semi[i]; break;
                     }
+                    if (last_conv) last_out = g.out;
+                    AKE_REQUIRE(g.ok || g.in == P2pIn::Planes || g.in == P2pIn::Src, AKE_ERR_STATE,
+                                "pcnet: the route promised an input form only the persistent pitch conv reads, for a chunk (%d clips) it does not take", B);
+                    if (g.ok) rc = run_p2p_f16_ps(n, n->p2p[i][j], g, io, B, P, Ti, s, "conv_p2p_f16_kernel");
+                    else rc = run_p2p_f16(n, n->p2p[i][j], io.planes, j == 0 ? &io.src : nullptr, B, P, Ti, io.dst, d.out_p, io.plane, s, "conv_p2p_f16_kernel");
+                    if (rc) return rc;
                     continue;
                 }
-                if (train && !c.pc2p_mem && !c.stay_sixth) {   // f16 x 3 on the persistent form (f32-equivalent products); else the f32 MFMA kernel
-                    const PackedConv& pt = n->p2p_t[i][j];
-                    const int bn = bn_of(m + "p2p.layer." + std::to_string(3 * j + 1));
-                    if (run_p2p_f16x3(n, pt.bf_off, sdesc, in_aff, n->blob_dev + pt.b_off, B, P, Ti, out, d.out_p, b.stats + 2 * n->bns[bn].ch_off,
-                                      2 * n->bn_channels, s, "conv_p2p_f16x3_kernel/p2p")) {
-                        finalize_bn(bn, static_cast<double>(B) * P * Ti, out_aff);
-                        sdesc = Src{out, d.out_p, nullptr, 0, 0};
-                        in_aff = out_aff;
-                        continue;
-                    }
-                }
-                // inference in the f32x3 precision mode: the same persistent kernel with the EVAL fragments (BatchNorm folded; f16 hi + lo operands,
-                // three products: f32-equivalent to 2^-22) and LeakyReLU in its epilogue, instead of the f32-MFMA kernel at the vector rate
-                if (!train && c.precision == AKE_PRECISION_F32X3 && !c.pc2p_mem && !c.stay_sixth && !g_keep_taps && n->p2p[i][j].bf_off >= 0 &&
-                    run_p2p_f16x3(n, n->p2p[i][j].bf_off, sdesc, nullptr, n->blob_dev + n->p2p[i][j].b_off, B, P, Ti, out, d.out_p, nullptr, 0, s,
-                                  "conv_p2p_f16x3_kernel/p2p", nullptr, true)) {
+                if (rp.x3_convs >> j & 1) {   // f16 x 3 on the persistent form; else the f32 MFMA kernel
+                    const PackedConv& px = train ? n->p2p_t[i][j] : n->p2p[i][j];
+                    const int bn = train ? bn_of(m + "p2p.layer." + std::to_string(3 * j + 1)) : -1;
+                    if ((rc = run_p2p_f16x3(n, rk.x3[j > 0], px.bf_off, sdesc, in_aff, n->blob_dev + px.b_off, B, P, Ti, out, d.out_p,
+                                            train ? b.stats + 2 * n->bns[bn].ch_off : nullptr, train ? 2 * n->bn_channels : 0, s, "conv_p2p_f16x3_kernel/p2p", nullptr,
+                                            !train)))
+                        return rc;
+                    if (train) finalize_bn(bn, static_cast<double>(B) * P * Ti, out_aff);
                     sdesc = Src{out, d.out_p, nullptr, 0, 0};
+                    in_aff = out_aff;
                     continue;
                 }
                 if ((rc = conv(n->p2p[i][j], train ? n->p2p_t[i][j] : n->p2p[i][j], m + "p2p.layer." + std::to_string(3 * j + 1), 0, sdesc,
@@ -2464,8 +2661,8 @@ struct Fwd {
                 in_aff = out_aff;
             }
             // models.py:386-392  pool_semi -> fold, written next to pc in the concat buffer
-            if (fused_fold) {
-            } else if (fused_semi) {
+            if (last_out == P2pOut::SemiFold) {
+            } else if (last_out == P2pOut::Semi) {
                 if ((rc = run_fold_max(out, d.out_p, P / 3, B, Ti, cat, ctot, d.prev_pc, s))) return rc;
             } else if (c.stay_sixth && train) {   // ... through the last conv's pending BatchNorm + LeakyReLU
                 const long long total = static_cast<long long>(B) * d.out_p * 12 * Ti;
@@ -2531,11 +2728,9 @@ struct Fwd {
         // inference, 16-channel stacks: bf16 MFMA with split operands; the stack's input is converted to channels-last planes once,
         // the intermediate activations stay in that format (same 64 B per position as 16 f32 channels: the ping-pong buffers are
         // reused), the last convolution writes NCHW f32 for the pooling / heads
-        const bool pc_bf = !train && pc2pc_uses_bf16(n, i, Ti);
-        // heads on the bf16 kernels read a channels-last copy of the pooled features (decided here: the fused stack writes it itself)
-        const bool head_bf = !train && L > 1 && n->final_ch == 16 && c.head_layers >= 2 && n->head_key[0].bf_off >= 0 &&
-                             n->head_tonic[0].bf_off >= 0 && b.Tf <= kPcBf16MaxFrames;
-        const bool pc_fused = !train && L > 1 && !c.denseblock && pc2pc_fuses(n, i, Ti);
+        const bool pc_bf = r.pc == PcStack::Bf16, pc_fused = r.pc == PcStack::Fused;
+        // heads on the bf16 kernels read a channels-last copy of the pooled features (the fused stack writes it itself)
+        const bool head_bf = r.heads != HeadForm::Generic;
         if (pc_fused) {
             if ((rc = run_pc2pc_fused(n, i, psrc, cin, B, Ti, b.pcf, head_bf ? b.feat_cl : nullptr, s))) return rc;
         } else if (pc_bf) run_nchw_to_cl16(psrc, cin, B, Ti, reinterpret_cast<unsigned short*>(b.pcb[i]), s);
@@ -2572,7 +2767,7 @@ struct Fwd {
                     return rc;
                 continue;
             }
-            if (train && L > 1 && pc_f16x3_ok(n->pc2pc_t[i][j], Ti, true)) {   // f16 x 3 MFMA (f32-equivalent products) instead of the f32 MFMA kernel
+            if (r.pc_x3_convs >> j & 1) {   // f16 x 3 MFMA (f32-equivalent products) instead of the f32 MFMA kernel
                 const PackedConv& pt = n->pc2pc_t[i][j];
                 unsigned short* planes = reinterpret_cast<unsigned short*>(b.pcb[i]);       // (the inference ping-pong buffer: idle in training)
                 run_nchw_to_cl16_f16x2(psrc, cin, B, Ti, psrc_aff, planes, s);
@@ -2611,24 +2806,8 @@ struct Fwd {
         // channels-last copy of the features
         unsigned short* feat_cl = b.feat_cl;
         if (head_bf && !pc_fused) run_nchw_to_cl16(feat, n->final_ch, B, Tf, feat_cl, s);
-        // two-conv heads: conv0 leaves its 32 channels as channels-last planes and ONE launch of conv_head1_bf16_kernel finishes
-        // both the key and the tonic map
-        const int T1 = Tf - (c.kernel_size - 1), T2 = T1 - (c.kernel_size - 1);
-        const bool head1_bf = head_bf && c.head_layers == 2 && n->head_key[1].bf_off >= 0 && n->head_tonic[1].bf_off >= 0 && T2 > 0 &&
-                              (12 * ((T2 + 15) / 16) + 15) / 16 <= kHead1MT;
-        const bool genre_bf = head1_bf && c.genre && n->head_genre.size() == 2 && n->head_genre[0].bf_off >= 0 && n->head_genre[1].bf_off >= 0 &&
-                              n->head_genre[0].kh == 1 && n->head_genre[1].kh == 2;
-        // ... and when the stack above ran as one launch (inference at the shapes pc2pc_fuses admits) both convolutions of a head run
-        // as ONE launch too (heads_fused_kernel): the 32 hidden channels stay in LDS.  ake_debug_keep_taps(1), training, other head
-        // depths and shapes whose patches do not fit keep the two launches below.
-        const int TpB = 16 * ((T2 + 15) / 16 - 1) + 22;
-        const size_t hf_lds = std::max({(static_cast<size_t>(2) * 12 * (T1 + 8) * 2 + 2 * 4 * 2 * 2 * 64) * sizeof(uint4),      // phase A: patch + weight ring
-                                        static_cast<size_t>(2) * 12 * TpB * 4 * sizeof(uint4),                                  // phase B: patch,
-                                        static_cast<size_t>(8) * kHead1MT * 4 * 64 * sizeof(float)}) +                          // then the partial tiles
-                              static_cast<size_t>(12) * T2 * sizeof(float);                                                     // the finished map
-        const bool heads_fused = head1_bf && pc_fused && !g_keep_taps && c.local == 0 && n->head_key[0].cout == 32 && n->head_tonic[0].cout == 32 &&
-                                 n->head_key[0].kh == 12 && n->head_tonic[0].kh == 12 && n->head_key[1].kh == 12 && n->head_tonic[1].kh == 12 &&
-                                 (!genre_bf || n->head_genre[0].cout == 32) && (12 * T1 + 15) / 16 <= 32 && hf_lds <= 150 * 1024;
+        const bool head1_bf = r.heads == HeadForm::Head1 || r.heads == HeadForm::Fused, genre_bf = r.genre_bf;
+        const int T1 = r.T1, T2 = r.T2, TpB = r.TpB;
         // per-head tables of the two bf16 paths (key, tonic, genre), and the pooling of a finished map
         const int nh_bf = genre_bf ? 3 : 2;
         float* const maps[3] = {b.map_k, b.map_t, b.map_g};
@@ -2637,7 +2816,8 @@ struct Fwd {
         PoolArgs pool;
         pool.seq = reinterpret_cast<const long long*>(seq);
         pool.n_pool_layers = L - 1; pool.tp = tp; pool.shrink = (c.kernel_size - 1) * c.head_layers; pool.max_pool = c.max_pool; pool.clip0 = 0;
-        if (heads_fused) {
+        if (r.heads == HeadForm::Fused) {
+            const size_t hf_lds = r.hf_lds;
             HeadsFusedArgs ha;
             std::memset(&ha, 0, sizeof(ha));
             ha.xh = feat_cl; ha.xl = feat_cl + static_cast<long long>(B) * 12 * Tf * 16;
@@ -2661,10 +2841,8 @@ struct Fwd {
                 AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(heads_fused_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
                 hf_attr.mark();
             }
-            // phase A's M-tiles over the 8 waves: three each where 24 cover the hidden map (12 x 32 positions and fewer), else four
-            const bool mt3 = (12 * T1 + 15) / 16 <= 24;
             ake::ProfScope ps("heads_fused_kernel", s);
-            if (mt3) hipLaunchKernelGGL(heads_fused_kernel<3>, dim3(nh_bf * B), dim3(512), hf_lds, s, ha);
+            if (r.heads_mt == 3) hipLaunchKernelGGL(heads_fused_kernel<3>, dim3(nh_bf * B), dim3(512), hf_lds, s, ha);
             else hipLaunchKernelGGL(heads_fused_kernel<4>, dim3(nh_bf * B), dim3(512), hf_lds, s, ha);
             pooled_heads = nh_bf;
             Tm = T2;
@@ -2689,7 +2867,7 @@ struct Fwd {
             ha.T_in = T1; ha.T_out = T2; ha.JB = (T2 + 15) / 16; ha.Tp = TpB;
             // the patch, and after the multiply loop the partial tiles of the 8 waves in the same bytes (two workgroups per CU fit)
             size_t lds = std::max(static_cast<size_t>(2) * 12 * ha.Tp * 4 * sizeof(uint4), static_cast<size_t>(8) * kHead1MT * 4 * 64 * sizeof(float));
-            if (c.local == 0) {   // the masked mean + sigmoid of each finished map in the same launch (its LDS copy sits behind the patch / partial tiles)
+            if (r.heads_pool) {   // the masked mean + sigmoid of each finished map in the same launch (its LDS copy sits behind the patch / partial tiles)
                 ha.fin_off = static_cast<int>(lds / sizeof(float));
                 lds += static_cast<size_t>(12) * T2 * sizeof(float);
                 for (int h = 0; h < nh_bf; ++h) ha.pout[h] = outs[h];
@@ -2794,7 +2972,7 @@ struct Fwd {
 
 int forward_impl(const ake_pcnet* n, bool train, const float* mel, int batch, int frames, const int64_t* seq_length, float* key_out,
                  float* tonic_out, float* genre_out, float* bn_stats_out, void* workspace, size_t ws_bytes, ake_stream_t stream,
-                 bool mel_frames_major = false, bool dry_run = false) {
+                 bool mel_frames_major = false) {
     AKE_REQUIRE(n && mel && key_out && tonic_out, AKE_ERR_INVALID, "pcnet forward: null argument");
     AKE_REQUIRE(n->finalized, AKE_ERR_STATE, "pcnet: ake_pcnet_finalize has not been called");
     AKE_REQUIRE(train || !n->eval_frags_stale, AKE_ERR_STATE,
@@ -2807,21 +2985,11 @@ int forward_impl(const ake_pcnet* n, bool train, const float* mel, int batch, in
     if (rc) return rc;
     AKE_REQUIRE(workspace && ws_bytes >= b.bytes, AKE_ERR_WORKSPACE, "pcnet: workspace %zu < %zu bytes", ws_bytes, b.bytes);
     hipStream_t s = static_cast<hipStream_t>(stream);
+    const Route route = build_route(n, train, batch, chunk, frames, mel, workspace, mel_frames_major);
+    AKE_REQUIRE(!mel_frames_major || route.frames_major, AKE_ERR_UNSUPPORTED,
+                "pcnet: this configuration does not take the frames-major input (ake_pcnet_accepts_frames_major)");
     if (train) AKE_HIP_CHECK(hipMemsetAsync(b.stats, 0, sizeof(double) * 2 * n->bn_channels * kStatSlots, s));
-    Fwd f{n, b, s, train};
-    f.mel_fm = mel_frames_major;
-    f.chunk = chunk;
-    if (dry_run) {   // ake_pcnet_accepts_frames_major: would the two readers of mel take that layout for this shape?  (no launch)
-        const auto& c = n->cfg;
-        if (train || c.num_layers != 2 || c.resblock || c.denseblock || c.pc2p_mem || c.p2pc_conv || c.stay_sixth || c.local ||
-            batch > chunk || !p2p_uses_f16(n, 1, b.Tl[1]))
-            return AKE_ERR_UNSUPPORTED;
-        if (!f.layer0_fused(mel, batch, true)) return AKE_ERR_UNSUPPORTED;
-        const LayerDims& d = n->dims[1];
-        Src sdesc{mel, 1, b.psix[1], d.prev_pc, 36};
-        return run_p2p_f16_ps(n, n->p2p[1][0], nullptr, &sdesc, batch, c.pitches, b.Tl[1], nullptr, d.out_p, reinterpret_cast<unsigned short*>(b.pa[1]), nullptr, s,
-                              "conv_p2p_f16_kernel", true, true) ? AKE_OK : AKE_ERR_UNSUPPORTED;
-    }
+    Fwd f{n, b, s, train, route};
     if ((rc = f.entry(mel, batch))) return rc;
     for (int c0 = 0; c0 < batch && n->cfg.num_layers > 1; c0 += chunk) {
         const int B = std::min(chunk, batch - c0);
@@ -2902,12 +3070,7 @@ int ake_pcnet_forward_f32(const ake_pcnet* n, const float* mel, int batch, int f
 // inference path only: ask ake_pcnet_accepts_frames_major first (other configurations return AKE_ERR_UNSUPPORTED).
 int ake_pcnet_accepts_frames_major(const ake_pcnet* n, int batch, int frames) {
     if (!n || !n->finalized || batch <= 0 || frames <= 0) return 0;
-    float dummy = 0.f;           // never dereferenced: the dry run stops before any launch
-    Buffers b;
-    if (plan_buffers(n, batch, std::min(batch, n->chunk_clips), frames, nullptr, &b, false) != AKE_OK) return 0;
-    const int rc = forward_impl(n, false, reinterpret_cast<const float*>(16), batch, frames, nullptr, &dummy, &dummy, &dummy, nullptr,
-                                reinterpret_cast<void*>(16), b.bytes, nullptr, true, true);
-    return rc == AKE_OK ? 1 : 0;
+    return build_route(n, false, batch, std::min(batch, n->chunk_clips), frames, nullptr, nullptr, true).frames_major ? 1 : 0;
 }
 
 int ake_pcnet_forward_frames_major_f32(const ake_pcnet* n, const float* mel_fm, int batch, int frames, const int64_t* seq_length,
@@ -2999,6 +3162,8 @@ static int tap_lookup(const ake_pcnet* n, const char* name, int batch, int frame
     }
     const int L = c.num_layers, P = c.pitches;
     const std::string nm = name;
+    // what a forward of this shape launches under the current ake_debug_keep_taps setting: which activations exist, and in which layout
+    const Route r = build_route(n, false, batch, batch, frames, nullptr, ws, false);
     auto set = [&](float* ptr, int64_t C, int64_t H, int64_t Tn) { *p = ptr; shape[0] = batch; shape[1] = C; shape[2] = H; shape[3] = Tn; return AKE_OK; };
     if (nm == "model.0.pool") return set(b.fold0, 1, 12, frames);
     if (c.resblock && (std::strstr(name, "pc2pc.layer.") || std::strstr(name, "p2p.layer."))) {
@@ -3016,13 +3181,12 @@ static int tap_lookup(const ake_pcnet* n, const char* name, int batch, int frame
                 const bool to_cat = i == 0 && L > 1;             // layer 0's last conv writes into cat[1]
                 if (to_cat && j == last_j) break;                // strided inside the concat buffer: use "model.1.cat"
                 if (j < last_j - (to_cat ? 2 : 1)) break;
-                if (i == L - 1 && pc2pc_fuses(n, i, Ti)) {
+                if (i == L - 1 && r.pc == PcStack::Fused) {
                     ake::set_error("tap: '%s' stays in LDS (the stack runs as one launch); ake_debug_keep_taps(1) before the forward keeps it", name);
                     return AKE_ERR_INVALID;
                 }
-                if (j < last_j && i == L - 1 && pc2pc_uses_bf16(n, i, Ti) && channels_last) *channels_last = 1;
-                if (i == 0 && L > 1 && !g_keep_taps && c.precision == AKE_PRECISION_MIXED && !c.resblock && !c.denseblock && !c.p2pc_conv && !c.stay_sixth && c.n_filters >= 2 &&
-                    c.n_filters <= 4) {
+                if (j < last_j && i == L - 1 && r.pc == PcStack::Bf16 && channels_last) *channels_last = 1;
+                if (i == 0 && r.l0.form == L0Form::FusedMfma && !g_keep_taps) {      // (the VALU form writes every conv's output)
                     ake::set_error("tap: '%s' stays in LDS (layer 0 runs as one launch); ake_debug_keep_taps(1) before the forward writes it", name);
                     return AKE_ERR_INVALID;
                 }
@@ -3030,18 +3194,18 @@ static int tap_lookup(const ake_pcnet* n, const char* name, int batch, int frame
             }
             if (i >= 1 && nm == m + "p2p.layer." + std::to_string(3 * j + 2)) {
                 if (j < last_j - 1) break;
-                if (j == last_j && p2p_fuses_semi(n, i, P, Ti)) {
+                if (j == last_j && r.p[i].stack == PStack::F16 && r.p[i].k[0].last.out != P2pOut::Nchw) {
                     ake::set_error("tap: '%s' is fused with the semitone conv that follows it (never written); ake_debug_keep_taps(1) before the forward keeps it", name);
                     return AKE_ERR_INVALID;
                 }
                 // inference keeps the stack's intermediate activations as channels-last split-bf16 planes (conv_p2p_f16_kernel)
-                if (j < last_j && p2p_uses_f16(n, i, Ti) && channels_last) *channels_last = 2;      // one f16 plane
+                if (j < last_j && r.p[i].stack == PStack::F16 && channels_last) *channels_last = 2;      // one f16 plane
                 return set((j & 1) ? b.pb[i] : b.pa[i], d.out_p, P, Ti);
             }
         }
         if (i >= 1 && nm == m + "up_sixth_a") {
-            if (i == 1 && !g_keep_taps && c.precision == AKE_PRECISION_MIXED && !c.denseblock && !c.p2pc_conv && !c.stay_sixth && !c.pc2p_mem) {
-                ake::set_error("tap: '%s' may be held as f16 words for the pitch conv that reads it; ake_debug_keep_taps(1) before the forward writes it as f32", name);
+            if (i == 1 && r.psix_f16) {
+                ake::set_error("tap: '%s' is held as f16 words for the pitch conv that reads it; ake_debug_keep_taps(1) before the forward writes it as f32", name);
                 return AKE_ERR_INVALID;
             }
             return set(b.psix[i], d.prev_pc, 36, Ti);

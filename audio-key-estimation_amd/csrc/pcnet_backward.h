@@ -209,10 +209,12 @@ struct Bwd {
         g.pad_l = fwd.kw - 1 - pad_fwd;
         g.T_out = T_in;
         g.H_out = H;
-        if (kind == 0 && !accumulate && dst_coff == 0 && dst_ctot == pd.cout && T_dz == T_in &&
-            run_p2p_f16x3(n, pd.bf_off, Src{dz, pd.cin, nullptr, 0, 0}, nullptr, nullptr, B, H, T_dz, dst, pd.cout, nullptr, 0, s, "conv_p2p_f16x3_kernel/p2p_dgrad",
-                          amax_for(dz)))
-            return AKE_OK;
+        if (kind == 0 && !accumulate && dst_coff == 0 && dst_ctot == pd.cout && T_dz == T_in && pd.bf_off >= 0) {
+            const P2pX3Plan x3 = p2p_f16x3_plan(pd.cin, 0, pd.cout, B, H, T_dz, !(reinterpret_cast<uintptr_t>(dst) & 15));
+            if (x3.ok)
+                return run_p2p_f16x3(n, x3, pd.bf_off, Src{dz, pd.cin, nullptr, 0, 0}, nullptr, nullptr, B, H, T_dz, dst, pd.cout, nullptr, 0, s,
+                                     "conv_p2p_f16x3_kernel/p2p_dgrad", amax_for(dz));
+        }
         // pitch-class stacks of layers >= 1 (same-size 12 x 7 convolutions, 16 gradient channels): the f16 x 3 form of conv_pc_bf16_kernel with
         // the transposed + flipped weights (f32-equivalent products; the f32 MFMA kernel took 0.17 ms per convolution and 256 clips)
         if (kind == 1 && same_time && planes_scratch && !accumulate && dst_coff == 0 && dst_ctot == pd.cout && T_dz == T_in && H == 12 &&

@@ -2240,7 +2240,7 @@ __global__ void nchw_to_cl16_f16x2_kernel(const float* __restrict__ src, long lo
 // starts AT the output row (py = 0) starts 11 rows before it, i.e. (mod 12) one row after: rotating the rows by 11 lets the same
 // py = 0 kernel compute it.
 // Inverse power-of-two scale of every output channel of a pack [group][ci][dy][dx][CO] (f16_weight_scale of its largest |w|), written
-// behind the fragments pack_pc_f16x3_kernel fills afterwards.  One workgroup per output channel.
+// behind the fragments pack_pc_f16x3_jobs_kernel fills afterwards.  One workgroup per output channel.
 // Several packs per launch (round 3: a training step re-packs ~14 convolutions after every optimizer step, two tiny launches each -- 28 dependent
 // launches, 0.39 ms of a 7 ms step, were launch latency): blockIdx.y picks the job, the jobs travel in the kernel argument.
 struct PcPackJob { const float* w; uint4* out; int cin, cout, CO, NT, KH, dy_rot, ci_off; };      // (the inverse scales live behind the fragments: out + KH * 4 * NT * 2 * 64)
@@ -2298,10 +2298,6 @@ __device__ __forceinline__ void pack_pc_f16x3_body(const float* __restrict__ w, 
     }
     out[((ks * NT + nt) * 2 + 0) * 64 + lane] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
     out[((ks * NT + nt) * 2 + 1) * 64 + lane] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
-}
-__global__ void pack_pc_f16x3_kernel(const float* __restrict__ w, uint4* __restrict__ out, int cin, int cout, int CO, int NT, int KH, int dy_rot,
-                                     int ci_off) {
-    pack_pc_f16x3_body(w, out, cin, cout, CO, NT, KH, dy_rot, ci_off, blockIdx.x);
 }
 __global__ void pack_pc_f16x3_jobs_kernel(PcPackJobs js) {
     const PcPackJob& J = js.j[blockIdx.y];
@@ -2442,9 +2438,6 @@ __device__ __forceinline__ void pack_p2p_f16_raw_body(const float* __restrict__ 
     }
     out[(2 * ks + 0) * 64 + lane] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
     out[(2 * ks + 1) * 64 + lane] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
-}
-__global__ void pack_p2p_f16_raw_kernel(const float* __restrict__ w, uint4* __restrict__ out, int cin_fwd, int cout_fwd, int transpose_flip) {
-    pack_p2p_f16_raw_body(w, out, cin_fwd, cout_fwd, transpose_flip, blockIdx.x);
 }
 __global__ void pack_p2p_f16_raw_jobs_kernel(P2pRawJobs js) {
     const P2pRawJob& J = js.j[blockIdx.y];
