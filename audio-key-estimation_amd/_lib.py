@@ -93,6 +93,9 @@ SYMBOLS = {
     "ake_viterbi_keys_workspace_bytes": (_SZ, [_I, _I]),
     "ake_viterbi_chunk_windows": (_I, []),
     "ake_viterbi_keys_f32": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
+    "ake_key_posteriors_workspace_bytes": (_SZ, [_I, _I]),
+    "ake_key_posteriors_chunk_windows": (_I, []),
+    "ake_key_posteriors_f32": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "ake_resampler_create": (_I, [_I, _I, C.POINTER(_P)]),
     "ake_resampler_destroy": (None, [_P]),
     "ake_resampler_out_len": (_I64, [_P, _I64]),

@@ -18,7 +18,9 @@
 // pitch-stream chunk, so nothing is chunked twice).
 //
 // A smooth track is two more launches on the track's outputs: key_emissions_kernel (every window's log-score of the 24 keys) and
-// viterbi_keys_kernel (the most likely path through them); further down, semantics in include/ake_hip.h.
+// viterbi_keys_kernel (the most likely path through them); further down, semantics in include/ake_hip.h.  Posterior key probabilities
+// are a forward-backward pass over the same emissions: key_forward_backward_kernel (the two serial chains, side by side) and
+// key_posteriors_kernel (everything per window), below the Viterbi kernel.
 #include "common.h"
 
 #include <algorithm>
@@ -245,6 +247,17 @@ __device__ __forceinline__ float states_max(float x, bool valid) {
     return __int_as_float(order_key(k0 > k1 ? k0 : k1));
 }
 
+// A lane's 12 candidates of a step, c[i] = score[i] + A[i] for its half of the predecessors (the scores: three 16-byte broadcast reads
+// of the LDS row), and their maximum.  Shared by the Viterbi step and the forward-backward step.
+__device__ __forceinline__ float half_candidates(const float4* dsrc, const float (&A)[12], float (&c)[12]) {
+    const float4 q0 = dsrc[0], q1 = dsrc[1], q2 = dsrc[2];
+    c[0] = q0.x + A[0]; c[1] = q0.y + A[1]; c[2] = q0.z + A[2];  c[3] = q0.w + A[3];
+    c[4] = q1.x + A[4]; c[5] = q1.y + A[5]; c[6] = q1.z + A[6];  c[7] = q1.w + A[7];
+    c[8] = q2.x + A[8]; c[9] = q2.y + A[9]; c[10] = q2.z + A[10]; c[11] = q2.w + A[11];
+    return fmaxf(fmaxf(fmaxf(fmaxf(c[0], c[1]), c[2]), fmaxf(fmaxf(c[3], c[4]), c[5])),
+                 fmaxf(fmaxf(fmaxf(c[6], c[7]), c[8]), fmaxf(fmaxf(c[9], c[10]), c[11])));
+}
+
 // One wave per recording.  A step is a latency chain on one wave, so what counts is its number of instructions:
 //   - lanes j and 32 + j (j < 24) share state j: the first takes the predecessors i = 0..11, the second i = 12..23, each with its half
 //     of column j of A in registers, so a lane adds, maximises (v_max3) and compare-selects over 12 candidates, not 24; the halves meet
@@ -293,11 +306,8 @@ __global__ __launch_bounds__(64) void viterbi_keys_kernel(VitArgs a) {
             if (w > 0) {
                 if (writer) reinterpret_cast<float*>(d_lds)[lane] = d;
                 __syncthreads();                                         // (one wave: the wait for the LDS write, no more)
-                const float4 q0 = dsrc[0], q1 = dsrc[1], q2 = dsrc[2];
-                const float c[kHalf] = {q0.x + A[0], q0.y + A[1], q0.z + A[2],  q0.w + A[3],  q1.x + A[4], q1.y + A[5],
-                                        q1.z + A[6], q1.w + A[7], q2.x + A[8], q2.y + A[9], q2.z + A[10], q2.w + A[11]};
-                const float mh = fmaxf(fmaxf(fmaxf(fmaxf(c[0], c[1]), c[2]), fmaxf(fmaxf(c[3], c[4]), c[5])),
-                                       fmaxf(fmaxf(fmaxf(c[6], c[7]), c[8]), fmaxf(fmaxf(c[9], c[10]), c[11])));
+                float c[kHalf];
+                const float mh = half_candidates(dsrc, A, c);
                 unsigned ah = 0;
 #pragma unroll
                 for (int i = kHalf - 1; i >= 0; --i) ah = c[i] == mh ? static_cast<unsigned>(i) : ah;        // ends on the smallest i
@@ -348,6 +358,257 @@ __global__ __launch_bounds__(64) void viterbi_keys_kernel(VitArgs a) {
         for (int x = lane; x < len; x += 64) path[c0 + x] = x < nv ? path_lds[x] : -1;
         __syncthreads();                                                 // path_lds and bp_lds are reused by the chunk before
     }
+}
+
+// ---- posterior key probabilities: forward-backward over the same emissions (semantics: include/ake_hip.h; host model: metrics.key_posteriors) ----
+constexpr int kPostChunk = 64;        // windows per block of key_posteriors_kernel: 16 per wave for the transition sums (a multiple of 4)
+constexpr int kCells = kKeys * kKeys; // 576 = 9 per lane of a wave
+
+struct FbArgs {
+    const float* emis;         // [recordings][windows][24]
+    const int* counts;         // nullable
+    const float* trans;        // [24][24], from i (row) to j
+    const float* prior;        // [24], nullable = zeros
+    float* a;                  // [recordings][windows][24] normalised forward scores (rows behind the count are not written)
+    float* b;                  // the same, backward
+    float* loglik;             // [recordings]
+    int windows;
+};
+
+template <int kCtrl>
+__device__ __forceinline__ float dpp_add(float x) {
+    return x + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), kCtrl, 0xf, 0xf, true));
+}
+
+// sum over the states, laid out and joined as states_max: every stage adds a lane's value and its partner's, which is the same sum in
+// both (x + y == y + x), so all 16 lanes of a row end on the same bits, and the order is fixed.
+__device__ __forceinline__ float states_sum(float x, bool valid) {
+    float s = valid ? x : 0.f;
+    s = dpp_add<0xB1>(s);
+    s = dpp_add<0x4E>(s);
+    s = dpp_add<0x141>(s);
+    s = dpp_add<0x140>(s);
+    const int bits = __float_as_int(s);                                  // (v_readlane is typed int: the bits, not the value)
+    return __int_as_float(__builtin_amdgcn_readlane(bits, 0)) + __int_as_float(__builtin_amdgcn_readlane(bits, 16));
+}
+
+// One direction of one recording on one wave, the Viterbi step's layout with log-sum-exp in the place of max: lanes j and 32 + j share
+// state j with 12 of the 24 terms each, the step's 24 scores travel through the 96-byte LDS row, v_permlane32_swap joins the halves (the
+// two partial sums meet at their common maximum), emission rows are loaded kVitBatch steps ahead with clamped indices.
+//   forward  (kBack = false), step t = window t:         the row holds a_{t-1},               the lane a column half of A, raw = e[t] + LSE
+//   backward (kBack = true),  step t = window n - 1 - t: the row holds b_{w+1} + e[w+1],      the lane a row half of A,    raw = LSE
+// Every exponential's argument is <= 0 and the largest is 0, so a sum lies in [1, 24]: the fast v_exp_f32 / v_log_f32 forms are exact
+// to an ulp of the sum (a term's error is |x| e^x 2^-24 <= 0.37 * 2^-24), and no range handling is needed.  loglik adds the c_w in a
+// double beside the chain: a float32 running sum would lose sqrt(n) ulps.
+template <bool kBack>
+__device__ __forceinline__ void forward_backward_chain(const FbArgs& a, float4* d_lds) {
+    const int r = blockIdx.x, lane = threadIdx.x, W = a.windows;
+    int n = a.counts ? a.counts[r] : W;
+    n = n < 0 ? 0 : n > W ? W : n;
+    constexpr int kHalf = kKeys / 2;
+    const int half = lane >> 5;
+    const bool own = (lane & 31) < kKeys, writer = lane < kKeys;
+    const int j = own ? lane & 31 : 0;
+    float A[kHalf];
+#pragma unroll
+    for (int i = 0; i < kHalf; ++i) A[i] = kBack ? a.trans[j * kKeys + half * kHalf + i] : a.trans[(half * kHalf + i) * kKeys + j];
+    const float4* const dsrc = d_lds + half * (kHalf / 4);
+    const float* const e = a.emis + static_cast<size_t>(r) * W * kKeys + j;
+    float* const out = (kBack ? a.b : a.a) + static_cast<size_t>(r) * W * kKeys + j;
+    const int wl = n > 0 ? n - 1 : 0;                                    // the last row that is read (W >= 1)
+    // the emission row of step t: window t forward, window n - t backward (step 0 reads none there), clamped into 0..wl
+    auto row = [&](int t) { const int w = kBack ? n - t : t; return static_cast<size_t>(w < 0 ? 0 : w < wl ? w : wl) * kKeys; };
+    float d = kBack ? 0.f : (a.prior ? a.prior[j] : 0.f);
+    double ll = 0.0;
+    float eb[kVitBatch];
+#pragma unroll
+    for (int k = 0; k < kVitBatch; ++k) eb[k] = e[row(k)];
+    for (int t0 = 0; t0 < n; t0 += kVitBatch) {
+        float en[kVitBatch];
+#pragma unroll
+        for (int k = 0; k < kVitBatch; ++k) en[k] = e[row(t0 + kVitBatch + k)];
+#pragma unroll
+        for (int k = 0; k < kVitBatch; ++k) {
+            const int t = t0 + k;
+            if (t >= n) break;                                           // wave-uniform
+            float raw = kBack ? 0.f : d + eb[k];                         // t == 0: b_{n-1} = 0, a_0 = prior + e[0]
+            if (t > 0) {
+                if (writer) reinterpret_cast<float*>(d_lds)[lane] = kBack ? d + eb[k] : d;
+                __syncthreads();                                         // (one wave: the wait for the LDS write, no more)
+                float c[kHalf];
+                const float mh = half_candidates(dsrc, A, c);
+                float sh = 0.f;
+#pragma unroll
+                for (int i = 0; i < kHalf; ++i) sh += __expf(c[i] - mh);
+                const auto ms = __builtin_amdgcn_permlane32_swap(__float_as_uint(mh), __float_as_uint(mh), false, false);
+                const auto ss = __builtin_amdgcn_permlane32_swap(__float_as_uint(sh), __float_as_uint(sh), false, false);
+                const float m_lo = __uint_as_float(ms[0]), m_hi = __uint_as_float(ms[1]);
+                const float m = fmaxf(m_lo, m_hi);
+                const float s = __uint_as_float(ss[0]) * __expf(m_lo - m) + __uint_as_float(ss[1]) * __expf(m_hi - m);
+                const float lse = m + __logf(s);
+                raw = kBack ? lse : lse + eb[k];
+            }
+            if (!kBack || t > 0) {                                       // b_{n-1} stays 0, unnormalised
+                const float mx = states_max(raw, own);
+                const float cw = mx + __logf(states_sum(__expf(raw - mx), own));
+                d = raw - cw;
+                ll += static_cast<double>(cw);
+            } else {
+                d = raw;
+            }
+            if (writer) out[static_cast<size_t>(kBack ? n - 1 - t : t) * kKeys] = d;
+        }
+#pragma unroll
+        for (int k = 0; k < kVitBatch; ++k) eb[k] = en[k];
+    }
+    if (!kBack && lane == 0) a.loglik[r] = static_cast<float>(ll);
+}
+
+// grid (recordings, 2): blockIdx.y picks the direction, so the two chains of a recording run at the same time on two CUs.
+__global__ __launch_bounds__(64) void key_forward_backward_kernel(FbArgs a) {
+    __shared__ float4 d_lds[kKeys / 4];
+    if (blockIdx.y == 0) forward_backward_chain<false>(a, d_lds);
+    else forward_backward_chain<true>(a, d_lds);
+}
+
+struct PostArgs {
+    const float* emis;         // [recordings][windows][24]
+    const int* counts;         // nullable
+    const float* trans;        // [24][24]
+    const int* path;           // [recordings][windows], nullable
+    const float* a;            // [recordings][windows][24]
+    const float* b;
+    float* post;               // [recordings][windows][24]
+    float* path_post;          // [recordings][windows], nullable
+    float* xi_part;            // [recordings][chunks][576], nullable: no transition sums
+    int windows, chunks;       // chunks = ceil(windows / kPostChunk)
+};
+
+__device__ __forceinline__ float wave_max(float x) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) x = fmaxf(x, __shfl_xor(x, m));
+    return x;
+}
+__device__ __forceinline__ float wave_sum(float x) {                     // (x + y == y + x: every lane ends on the same bits)
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
+    return x;
+}
+
+// One block of 4 waves per (recording, chunk of kPostChunk windows).
+//   - post / path_post: one thread per window (a row is 2 x 96 bytes in and 96 out, moved as float4s, as key_emissions_kernel's);
+//   - the transition sums: wave v takes windows c0 + v, c0 + v + 4, ... of the chunk in turn, a lane 9 of the 576 cells of each (a
+//     softmax over the wave: one maximum, one sum), and keeps its cells' running sums in registers.  The four waves' sums meet in LDS
+//     and leave as one partial per chunk, added in wave order; key_xi_reduce_kernel adds the chunks in chunk order.  No atomics: the
+//     order of every addition is fixed by the shape alone.
+__global__ __launch_bounds__(256) void key_posteriors_kernel(PostArgs p) {
+    __shared__ float part[4][kCells];
+    const int r = blockIdx.x / p.chunks, chunk = blockIdx.x - r * p.chunks, c0 = chunk * kPostChunk;
+    const int W = p.windows, tid = threadIdx.x;
+    int n = p.counts ? p.counts[r] : W;
+    n = n < 0 ? 0 : n > W ? W : n;
+    const size_t row0 = static_cast<size_t>(r) * W;
+    if (tid < kPostChunk && c0 + tid < W) {
+        const int w = c0 + tid;
+        float4* const out = reinterpret_cast<float4*>(p.post + (row0 + w) * kKeys);
+        float pp = 0.f;
+        if (w < n) {
+            const float4* const av = reinterpret_cast<const float4*>(p.a + (row0 + w) * kKeys);
+            const float4* const bv = reinterpret_cast<const float4*>(p.b + (row0 + w) * kKeys);
+            float s[kKeys];
+#pragma unroll
+            for (int q = 0; q < 6; ++q) {
+                const float4 x = av[q], y = bv[q];
+                s[4 * q] = x.x + y.x; s[4 * q + 1] = x.y + y.y; s[4 * q + 2] = x.z + y.z; s[4 * q + 3] = x.w + y.w;
+            }
+            float mx = s[0];
+#pragma unroll
+            for (int k = 1; k < kKeys; ++k) mx = fmaxf(mx, s[k]);
+            float z = 0.f;
+#pragma unroll
+            for (int k = 0; k < kKeys; ++k) { s[k] = __expf(s[k] - mx); z += s[k]; }
+#pragma unroll
+            for (int k = 0; k < kKeys; ++k) s[k] = s[k] / z;
+#pragma unroll
+            for (int q = 0; q < 6; ++q) out[q] = make_float4(s[4 * q], s[4 * q + 1], s[4 * q + 2], s[4 * q + 3]);
+            if (p.path_post) {
+                const int k0 = p.path[row0 + w];
+#pragma unroll
+                for (int k = 0; k < kKeys; ++k) pp = k == k0 ? s[k] : pp;   // (selects, not an indexed register array; -1 matches none)
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 6; ++q) out[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        if (p.path_post) p.path_post[row0 + w] = pp;
+    }
+    if (!p.xi_part) return;
+    const int wave = tid >> 6, lane = tid & 63;
+    constexpr int kPer = kCells / 64;
+    float A[kPer], acc[kPer];
+    int ci[kPer], cj[kPer];
+#pragma unroll
+    for (int q = 0; q < kPer; ++q) {
+        const int cell = lane + 64 * q;
+        ci[q] = cell / kKeys; cj[q] = cell - ci[q] * kKeys;
+        A[q] = p.trans[cell];
+        acc[q] = 0.f;
+    }
+    for (int k = 0; k < kPostChunk / 4; ++k) {
+        const int w = c0 + wave + 4 * k;
+        if (w < 1 || w >= n) continue;                                   // wave-uniform
+        const float* const ap = p.a + (row0 + w - 1) * kKeys;
+        const float* const bw = p.b + (row0 + w) * kKeys;
+        const float* const ew = p.emis + (row0 + w) * kKeys;
+        float x[kPer];
+#pragma unroll
+        for (int q = 0; q < kPer; ++q) x[q] = ((ap[ci[q]] + A[q]) + ew[cj[q]]) + bw[cj[q]];
+        float mx = x[0];
+#pragma unroll
+        for (int q = 1; q < kPer; ++q) mx = fmaxf(mx, x[q]);
+        mx = wave_max(mx);
+        float z = 0.f;
+#pragma unroll
+        for (int q = 0; q < kPer; ++q) { x[q] = __expf(x[q] - mx); z += x[q]; }
+        z = wave_sum(z);
+#pragma unroll
+        for (int q = 0; q < kPer; ++q) acc[q] += x[q] / z;
+    }
+#pragma unroll
+    for (int q = 0; q < kPer; ++q) part[wave][lane + 64 * q] = acc[q];
+    __syncthreads();
+    float* const dst = p.xi_part + static_cast<size_t>(blockIdx.x) * kCells;
+    for (int cell = tid; cell < kCells; cell += 256) dst[cell] = ((part[0][cell] + part[1][cell]) + part[2][cell]) + part[3][cell];
+}
+
+// xi_sum[r] = the chunks' partial sums, added in chunk order.
+__global__ __launch_bounds__(192) void key_xi_reduce_kernel(const float* __restrict__ part, float* __restrict__ xi, int chunks) {
+    const int r = blockIdx.x;
+    for (int cell = threadIdx.x; cell < kCells; cell += 192) {
+        float s = 0.f;
+        for (int c = 0; c < chunks; ++c) s += part[(static_cast<size_t>(r) * chunks + c) * kCells + cell];
+        xi[static_cast<size_t>(r) * kCells + cell] = s;
+    }
+}
+
+struct PostCarve {
+    float* a;
+    float* b;
+    float* part;
+    size_t total;
+    int chunks;
+};
+
+bool carve_posteriors(int recordings, int windows, void* ws, PostCarve* pc) {
+    if (recordings <= 0 || windows <= 0 || static_cast<long long>(recordings) * windows > (1ll << 30)) return false;
+    pc->chunks = (windows + kPostChunk - 1) / kPostChunk;
+    const size_t rows = static_cast<size_t>(recordings) * windows;
+    ake::Carver c(ws, 0);
+    pc->a = c.take<float>(rows * kKeys);
+    pc->b = c.take<float>(rows * kKeys);
+    pc->part = c.take<float>(static_cast<size_t>(recordings) * pc->chunks * kCells);
+    pc->total = ake::align_up(c.off, 256);
+    return true;
 }
 
 struct WinCarve {
@@ -535,6 +796,46 @@ int ake_viterbi_keys_f32(const float* emis_dev, int recordings, int windows, con
     {
         ake::ProfScope ps("viterbi_keys_kernel", s);
         hipLaunchKernelGGL(viterbi_keys_kernel, dim3(recordings), dim3(64), 0, s, a);
+    }
+    AKE_HIP_CHECK(hipGetLastError());
+    return AKE_OK;
+}
+
+int ake_key_posteriors_chunk_windows(void) { return kPostChunk; }
+
+size_t ake_key_posteriors_workspace_bytes(int recordings, int windows) {
+    PostCarve pc;
+    return carve_posteriors(recordings, windows, nullptr, &pc) ? pc.total : 0;
+}
+
+int ake_key_posteriors_f32(const float* emis_dev, int recordings, int windows, const int32_t* counts_dev, const float* log_trans_dev,
+                           const float* log_prior_dev, const int32_t* path_dev, float* post_dev, float* loglik_dev, float* xi_sum_dev,
+                           float* path_post_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream) {
+    AKE_REQUIRE(emis_dev && log_trans_dev && post_dev && loglik_dev, AKE_ERR_INVALID, "key_posteriors: null argument");
+    AKE_REQUIRE(!path_post_dev || path_dev, AKE_ERR_INVALID, "key_posteriors: path_post_dev needs the path it reads (path_dev)");
+    PostCarve pc;
+    AKE_REQUIRE(carve_posteriors(recordings, windows, workspace, &pc), AKE_ERR_INVALID, "key_posteriors: bad shape (%d recordings, %d windows)",
+                recordings, windows);
+    AKE_REQUIRE(workspace && workspace_bytes >= pc.total, AKE_ERR_WORKSPACE, "key_posteriors: workspace %zu < %zu bytes", workspace_bytes, pc.total);
+    AKE_REQUIRE(((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(post_dev)) & 15) == 0, AKE_ERR_INVALID,
+                "key_posteriors: the workspace and post_dev must be 16-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    FbArgs fa{emis_dev, counts_dev, log_trans_dev, log_prior_dev, pc.a, pc.b, loglik_dev, windows};
+    {
+        ake::ProfScope ps("key_forward_backward_kernel", s);
+        hipLaunchKernelGGL(key_forward_backward_kernel, dim3(recordings, 2), dim3(64), 0, s, fa);
+    }
+    AKE_HIP_CHECK(hipGetLastError());
+    PostArgs pa{emis_dev, counts_dev, log_trans_dev, path_post_dev ? path_dev : nullptr, pc.a, pc.b, post_dev, path_post_dev,
+                xi_sum_dev ? pc.part : nullptr, windows, pc.chunks};
+    {
+        ake::ProfScope ps("key_posteriors_kernel", s);
+        hipLaunchKernelGGL(key_posteriors_kernel, dim3(recordings * pc.chunks), dim3(256), 0, s, pa);
+    }
+    AKE_HIP_CHECK(hipGetLastError());
+    if (xi_sum_dev) {
+        ake::ProfScope ps("key_xi_reduce_kernel", s);
+        hipLaunchKernelGGL(key_xi_reduce_kernel, dim3(recordings), dim3(192), 0, s, pc.part, xi_sum_dev, pc.chunks);
     }
     AKE_HIP_CHECK(hipGetLastError());
     return AKE_OK;

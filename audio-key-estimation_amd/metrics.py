@@ -231,3 +231,141 @@ def key_transition_log(stay, fifth=0.5, relative=0.3, parallel=0.2, other=0.02):
     P = Wt * ((1.0 - stay) / (2.0 * float(fifth) + float(relative) + float(parallel) + 19.0 * float(other)))
     P[torch.arange(24), torch.arange(24)] = stay
     return torch.log(P)
+
+
+# ---- posterior key probabilities and a fitted transition: forward-backward over the emissions (ake_key_posteriors_f32) and EM on top ----
+
+def key_posteriors(emissions, log_trans, log_prior=None, counts=None, transitions=False):
+    """Posterior marginals of the 24 keys at every window of (R, W, 24) or (W, 24) ``emissions`` -> ``(post, loglik)``, or
+    ``(post, loglik, xi_sum)`` with ``transitions=True``.
+
+    ``log_trans``, ``log_prior`` and ``counts`` as in ``viterbi_keys``, all finite.  The recurrence of ``ake_key_posteriors_f32`` in torch
+    ops, in the emissions' dtype (float64 inputs give the test model), for a recording of n = count windows, LSE = log-sum-exp::
+
+        a_0[j] = prior[j] + e[0][j]
+        a_w[j] = e[w][j] + LSE_i (a_{w-1}[i] + A[i][j])
+        c_w = LSE_j a_w[j];  a_w[j] -= c_w                                  (every step, w = 0 included)
+        b_{n-1}[i] = 0
+        b_w[i] = LSE_j (A[i][j] + e[w+1][j] + b_{w+1}[j]);  b_w[i] -= LSE_i b_w[i]
+        post_w[j]  = softmax_j (a_w[j] + b_w[j])
+        xi_w[i][j] = softmax over all 576 (i, j) of (a_{w-1}[i] + A[i][j] + e[w][j] + b_w[j])      w = 1..n-1
+
+    ``post`` (R, W, 24): every row below the count sums to 1, rows at or behind it are zeros.  ``loglik`` (R,) = sum_w c_w, 0 for a count
+    of 0.  The emissions are log-scores, not normalised likelihoods, so ``loglik`` is a log-score of the recording under ``log_trans``:
+    the quantity ``fit_key_transition`` raises, and no more than that.  ``xi_sum`` (R, 24, 24) = sum_w xi_w: the expected number of
+    moves from key i to key j, n - 1 in all, zeros for counts 0 and 1."""
+    single = emissions.dim() == 2
+    e = emissions[None] if single else emissions
+    if e.dim() != 3 or e.shape[2] != 24:
+        raise ValueError(f"key_posteriors: emissions must be (R, W, 24) or (W, 24), got {tuple(emissions.shape)}")
+    R, W, K = e.shape
+    dev = e.device
+    A = torch.as_tensor(log_trans).to(device=dev, dtype=e.dtype)
+    if A.shape != (K, K):
+        raise ValueError(f"key_posteriors: log_trans must be (24, 24), got {tuple(A.shape)}")
+    prior = torch.zeros(K, device=dev, dtype=e.dtype) if log_prior is None else torch.as_tensor(log_prior).to(device=dev, dtype=e.dtype).reshape(K)
+    _check_finite("log_trans", A)
+    _check_finite("log_prior", prior)
+    _check_finite("emissions", e)
+    n = torch.full((R,), W, device=dev, dtype=torch.int64) if counts is None else \
+        torch.as_tensor(counts, device=dev).to(torch.int64).reshape(R).clamp(0, W)
+    a, b, c = e.new_zeros((R, W, K)), e.new_zeros((R, W, K)), e.new_zeros((R, W))
+    for w in range(W):
+        raw = prior[None, :] + e[:, 0] if w == 0 else e[:, w] + torch.logsumexp(a[:, w - 1, :, None] + A[None, :, :], dim=1)
+        c[:, w] = torch.logsumexp(raw, dim=1)
+        a[:, w] = raw - c[:, w, None]
+    for w in range(W - 2, -1, -1):                                                  # (b stays 0 at w >= n - 1)
+        raw = torch.logsumexp(A[None, :, :] + (e[:, w + 1] + b[:, w + 1])[:, None, :], dim=2)
+        raw = raw - torch.logsumexp(raw, dim=1, keepdim=True)
+        b[:, w] = torch.where((w < n - 1)[:, None], raw, torch.zeros_like(raw))
+    live = torch.arange(W, device=dev)[None, :] < n[:, None]                        # (R, W)
+    post = torch.where(live[..., None], torch.softmax(a + b, dim=2), torch.zeros_like(a))
+    loglik = torch.where(live, c, torch.zeros_like(c)).sum(dim=1)
+    if single:
+        post, loglik = post[0], loglik[0]
+    if not transitions:
+        return post, loglik
+    xi_sum = e.new_zeros((R, K, K))
+    for w0 in range(1, W, 256):                                                     # (a chunk of windows at a time bounds the memory)
+        w1 = min(w0 + 256, W)
+        x = a[:, w0 - 1:w1 - 1, :, None] + A[None, None, :, :] + e[:, w0:w1, None, :] + b[:, w0:w1, None, :]
+        xi = torch.softmax(x.reshape(R, w1 - w0, K * K), dim=2).reshape(R, w1 - w0, K, K)
+        xi_sum += torch.where(live[:, w0:w1, None, None], xi, torch.zeros_like(xi)).sum(dim=1)
+    return post, loglik, (xi_sum[0] if single else xi_sum)
+
+
+def _transposition_classes():
+    """(24, 24) int64: the class 0..47 of cell (i, j) under transposition -- (mode of i, mode of j, (t_j - t_i) mod 12); 12 cells each."""
+    k = torch.arange(24)
+    mode, t = k // 12, k % 12
+    return (mode[:, None] * 2 + mode[None, :]) * 12 + (t[None, :] - t[:, None]) % 12
+
+
+def transition_m_step(xi_sum, init_log, tied=True, pseudo_count=1.0):
+    """The M-step of the transition fit: expected transition counts -> float64 (24, 24) log matrix, from key i (row) to key j.
+
+    ``C`` = ``xi_sum`` ((24, 24), or (R, 24, 24) summed over the recordings) + ``pseudo_count * exp(init_log)``: ``pseudo_count``
+    pseudo-transitions per row, spread as ``init``, so ``C`` stays positive and the result finite.  ``tied``: every cell of ``C`` is
+    replaced by the mean over its transposition class -- the cells (i', j') with the modes of i and j and the same tonic interval
+    ``(t_j - t_i) mod 12``: 48 classes of 12 cells -- so the matrix depends on the interval moved, not on the key left.  The result is
+    ``log(C / rowsum(C))``."""
+    xi = torch.as_tensor(xi_sum).detach().to(device="cpu", dtype=torch.float64)
+    if xi.dim() == 3:
+        xi = xi.sum(dim=0)
+    init = torch.as_tensor(init_log).detach().to(device="cpu", dtype=torch.float64)
+    if xi.shape != (24, 24) or init.shape != (24, 24):
+        raise ValueError(f"transition_m_step: xi_sum must be (24, 24) or (R, 24, 24) and init_log (24, 24), got {tuple(xi.shape)} and {tuple(init.shape)}")
+    _check_finite("xi_sum", xi)
+    _check_finite("init_log", init)
+    if float(pseudo_count) < 0.0:
+        raise ValueError("transition_m_step: pseudo_count must not be negative")
+    C = xi + float(pseudo_count) * torch.exp(init)
+    if tied:
+        cls = _transposition_classes().reshape(-1)
+        mean = torch.zeros(48, dtype=torch.float64).index_add_(0, cls, C.reshape(-1)) / 12.0
+        C = mean[cls].reshape(24, 24)
+    return torch.log(C / C.sum(dim=1, keepdim=True))
+
+
+def fit_key_transition(emissions, counts=None, init=None, iterations=10, tied=True, pseudo_count=1.0, log_prior=None, e_step=None):
+    """Fit the transition matrix to recordings' own emissions by EM (Baum-Welch with the emissions held fixed) ->
+    ``(log_trans, log_likelihoods)``.
+
+    ``emissions``: one (R, W, 24) or (W, 24) tensor or a list of them, ``counts`` matching (one per tensor, or None).  ``init``: the
+    (24, 24) log matrix to start from, default ``key_transition_log(stay=0.9)``; it also spreads the M-step's pseudo-counts
+    (``transition_m_step``).  Every iteration runs ``e_step(emissions_k, log_trans, log_prior, counts_k)`` -> ``(loglik, xi_sum)`` on
+    every tensor -- default: ``key_posteriors`` -- and then one M-step.  ``log_trans`` is float64 (24, 24); ``log_likelihoods`` holds one
+    float per iteration: the summed score of all recordings under the matrix that ENTERED that iteration, which EM does not lower.
+    No accuracy claim goes with the fitted matrix: it is the matrix under which these emissions score highest, and no more."""
+    batches = list(emissions) if isinstance(emissions, (list, tuple)) else [emissions]
+    if not batches:
+        raise ValueError("fit_key_transition: no emissions")
+    if counts is None:
+        cnts = [None] * len(batches)
+    elif isinstance(emissions, (list, tuple)):
+        cnts = list(counts)
+        if len(cnts) != len(batches):
+            raise ValueError(f"fit_key_transition: {len(batches)} emission tensors but {len(cnts)} counts")
+    else:
+        cnts = [counts]
+    if int(iterations) < 1:
+        raise ValueError("fit_key_transition: iterations must be at least 1")
+    init = key_transition_log(stay=0.9) if init is None else torch.as_tensor(init).detach().to(device="cpu", dtype=torch.float64)
+    if init.shape != (24, 24):
+        raise ValueError(f"fit_key_transition: init must be (24, 24), got {tuple(init.shape)}")
+    _check_finite("init", init)
+    if e_step is None:
+        def e_step(e, log_trans, prior, cnt):
+            _, ll, xi = key_posteriors(e, log_trans, log_prior=prior, counts=cnt, transitions=True)
+            return ll, xi
+    log_trans, scores = init.clone(), []
+    for _ in range(int(iterations)):
+        xi_total, score = torch.zeros((24, 24), dtype=torch.float64), 0.0
+        for e, cnt in zip(batches, cnts):
+            ll, xi = e_step(e, log_trans, log_prior, cnt)
+            xi = xi.detach().to(device="cpu", dtype=torch.float64)
+            xi_total += xi.sum(dim=0) if xi.dim() == 3 else xi
+            score += float(ll.detach().to(device="cpu", dtype=torch.float64).sum())
+        scores.append(score)
+        log_trans = transition_m_step(xi_total, init, tied=tied, pseudo_count=pseudo_count)
+    return log_trans, scores

@@ -48,7 +48,13 @@ class KeyTrack:
 
     ``track(smooth=True)`` adds ``emissions`` (R, W, 24), every window's log-score of the 24 keys (``metrics.key_emissions``; zeros behind
     a recording's count), and ``smooth_key_id`` int32 (R, W), the Viterbi path through them (``metrics.viterbi_keys``): always a key
-    0..23 below the count, -1 behind it.  Both are None otherwise."""
+    0..23 below the count, -1 behind it.  Both are None otherwise.
+
+    ``track(smooth=True, posteriors=True)`` adds the forward-backward pass over the same emissions and transition
+    (``metrics.key_posteriors``): ``posteriors`` (R, W, 24), the posterior probability of every key at every window (rows below the
+    count sum to 1, rows behind it are zeros); ``smooth_confidence`` (R, W), the posterior of the key ``smooth_key_id`` names (0 behind
+    the count); ``log_likelihood`` (R,), the recording's log-score under the transition (the emissions are log-scores, not normalised
+    likelihoods: it compares transitions on the same recording and means nothing else).  All three are None otherwise."""
     key: torch.Tensor
     tonic: torch.Tensor
     genre: torch.Tensor | None
@@ -62,27 +68,39 @@ class KeyTrack:
     stride_seconds: float = 0.0
     emissions: torch.Tensor | None = None
     smooth_key_id: torch.Tensor | None = None
+    posteriors: torch.Tensor | None = None
+    smooth_confidence: torch.Tensor | None = None
+    log_likelihood: torch.Tensor | None = None
 
     def _tensors(self):
-        """Every device tensor of the track; the two of a smooth track only when it is one (a plain track lists what it always did)."""
+        """Every device tensor of the track; the two of a smooth track and the three of its posteriors only when it has them (a plain
+        track lists what it always did)."""
         plain = (self.key, self.tonic, self.genre, self.key_id, self.sig, self.tonic_id, self.confidence, self.counts)
         if self.emissions is None and self.smooth_key_id is None:
             return plain
-        return plain + (self.emissions, self.smooth_key_id)
+        if self.posteriors is None:
+            return plain + (self.emissions, self.smooth_key_id)
+        return plain + (self.emissions, self.smooth_key_id, self.posteriors, self.smooth_confidence, self.log_likelihood)
 
-    def segments(self, recording: int, smoothed: bool | None = None):
+    def segments(self, recording: int, smoothed: bool | None = None, confidence: bool = False):
         """Run-length encoding of one recording's key labels on the host -> list of ``(start_s, end_s, key_id, name)``.  A window stands
         for the stride around its centre; the first segment starts at 0 and the last ends with the last window.  ``name`` is
         ``metrics.KEY_NAMES[key_id]`` ("A minor"), or "unknown" where signature and tonic disagree (-1).
 
         ``smoothed``: True reads ``smooth_key_id`` (``ValueError`` if the track has none), False ``key_id``; None (default) the smoothed
-        path when the track has one, ``key_id`` otherwise."""
+        path when the track has one, ``key_id`` otherwise.
+
+        ``confidence=True``: every tuple gets a fifth item, the mean of ``smooth_confidence`` over the segment's windows: how sure the
+        smoother is of the key it names there (``ValueError`` on a track without posteriors)."""
+        if confidence and self.smooth_confidence is None:
+            raise ValueError("segments(confidence=True): this track has no posteriors; make it with track(..., smooth=True, posteriors=True)")
         if smoothed and self.smooth_key_id is None:
             raise ValueError("segments(smoothed=True): this track has no smoothed path; make it with track(..., smooth=True)")
         source = self.smooth_key_id if (smoothed or (smoothed is None and self.smooth_key_id is not None)) else self.key_id
         n = int(self.counts[recording])
         ids = source[recording, :n].cpu().tolist()
         times = self.times[:n].tolist()
+        conf = self.smooth_confidence[recording, :n].cpu().tolist() if confidence else None
         half_w, half_s = self.window_seconds / 2, self.stride_seconds / 2
         out, a = [], 0
         for b in range(n):
@@ -90,7 +108,8 @@ class KeyTrack:
                 continue
             start = 0.0 if a == 0 else times[a] - half_s
             end = times[b] + (half_w if b == n - 1 else half_s)
-            out.append((start, end, ids[a], metrics.KEY_NAMES[ids[a]] if ids[a] >= 0 else "unknown"))
+            seg = (start, end, ids[a], metrics.KEY_NAMES[ids[a]] if ids[a] >= 0 else "unknown")
+            out.append(seg + (sum(conf[a:b + 1]) / (b + 1 - a),) if confidence else seg)
             a = b + 1
         return out
 
@@ -181,7 +200,7 @@ class KeyEstimator:
     @torch.no_grad()
     def track(self, audio: torch.Tensor, lengths: torch.Tensor | None = None, rate: int | None = None, channel: int = 0,
               window_seconds: float = 15.0, stride_seconds: float = 5.0, smooth: bool = False, mean_key_seconds: float = 60.0,
-              transition: torch.Tensor | None = None, signature_weight: float = 1.0) -> KeyTrack:
+              transition: torch.Tensor | None = None, signature_weight: float = 1.0, posteriors: bool = False) -> KeyTrack:
         """The key of long recordings over time: audio (R, n) or (R, C, n) float32 on the GPU -> ``KeyTrack``.
 
         Every recording is transformed ONCE at the estimator's hop (``T = 1 + n // hop`` frames); the net then runs on sliding windows
@@ -204,7 +223,15 @@ class KeyEstimator:
         negative number).  Default: ``metrics.key_transition_log(stay=exp(-stride / mean_key_seconds))`` with ``stride`` the track's
         actual stride in seconds, so the amount of smoothing does not depend on the stride chosen.  The default of 60 s is a starting
         value and nothing more: no recordings labelled with modulations exist here, so no accuracy claim is made for it.  Nothing else
-        of the track changes with ``smooth``."""
+        of the track changes with ``smooth``.
+
+        ``posteriors=True`` (with ``smooth=True``; a ``ValueError`` without it) appends the forward-backward pass over the same
+        emissions and transition, two more launches on the same stream, and fills ``KeyTrack.posteriors``, ``smooth_confidence`` and
+        ``log_likelihood`` (``metrics.key_posteriors``).  Nothing else of the track changes with it.  ``ake_amd.fit_key_transition``
+        fits a ``transition`` to smooth tracks' own emissions; the same caveat holds for it: no labelled modulations, no accuracy
+        claim."""
+        if posteriors and not smooth:
+            raise ValueError("track(posteriors=True) needs smooth=True: the posteriors belong to the smoothed track's emissions and transition")
         if self.frames <= 0:
             raise ValueError("track() needs a fixed frame rate: this estimator was built with frames=0 (whole-song mode)")
         if self.wrap_mode == "true_end":
@@ -220,7 +247,7 @@ class KeyEstimator:
         wf = track_window_frames(int(round(window_seconds * self.sample_rate)), self.plan.hop_length)
         sf = track_stride_frames(stride_seconds, self.frames)
         # (made on the caller's stream, which every side stream waits for before it runs the call)
-        smoothing = (self._transition(sf, mean_key_seconds, transition), float(signature_weight)) if smooth else None
+        smoothing = (self._transition(sf, mean_key_seconds, transition), float(signature_weight), bool(posteriors)) if smooth else None
         return self._issue(lambda slot, a, l: self._run_track(slot, a, l, wf, sf, smoothing), audio, lengths)
 
     def _transition(self, sf, mean_key_seconds, transition):
@@ -260,8 +287,12 @@ class KeyEstimator:
         track = KeyTrack(key, tonic, genre, key_id, sig, tonic_id, conf, counts, times, wf * hop / self.sample_rate, sf * hop / self.sample_rate)
         if smoothing is not None:
             track.emissions, track.smooth_key_id = f32(R, W, 24), i32(R, W)
+            if smoothing[2]:
+                track.posteriors, track.smooth_confidence, track.log_likelihood = f32(R, W, 24), f32(R, W), f32(R)
         if W == 0:                                                   # every recording is shorter than one window
             counts.zero_()
+            if track.log_likelihood is not None:
+                track.log_likelihood.zero_()
             return track
         nbytes = L.ake_pipeline_track_workspace_bytes(self.plan.handle, net.handle, R, n, wf, sf)
         if nbytes == 0:
@@ -271,6 +302,11 @@ class KeyEstimator:
             if vbytes == 0:
                 _lib.check(-1, "ake_viterbi_keys_workspace_bytes")
             nbytes = max(int(nbytes), int(vbytes))
+            if smoothing[2]:                                         # a, b of the forward-backward pass: after the Viterbi, in the same place
+                pbytes = L.ake_key_posteriors_workspace_bytes(R, W)
+                if pbytes == 0:
+                    _lib.check(-1, "ake_key_posteriors_workspace_bytes")
+                nbytes = max(nbytes, int(pbytes))
         if slot["ws"] is None or slot["ws"].numel() < nbytes:
             slot["ws"] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
         ws = slot["ws"]
@@ -286,12 +322,17 @@ class KeyEstimator:
                 _lib.check(L.ake_pipeline_track_ragged_f32(self.plan.handle, net.handle, audio.data_ptr(), R, n, audio.stride(0),
                                                            lengths.data_ptr(), wf, sf, *outs), "ake_pipeline_track_ragged_f32")
             if smoothing is not None:
-                trans, weight = smoothing
+                trans, weight, with_posteriors = smoothing
                 stream = torch.cuda.current_stream().cuda_stream
                 _lib.check(L.ake_key_emissions_f32(key.data_ptr(), tonic.data_ptr(), R * W, counts.data_ptr(), W, weight,
                                                    track.emissions.data_ptr(), stream), "ake_key_emissions_f32")
                 _lib.check(L.ake_viterbi_keys_f32(track.emissions.data_ptr(), R, W, counts.data_ptr(), trans.data_ptr(), None,
                                                   track.smooth_key_id.data_ptr(), ws.data_ptr(), ws.numel(), stream), "ake_viterbi_keys_f32")
+                if with_posteriors:
+                    _lib.check(L.ake_key_posteriors_f32(track.emissions.data_ptr(), R, W, counts.data_ptr(), trans.data_ptr(), None,
+                                                        track.smooth_key_id.data_ptr(), track.posteriors.data_ptr(),
+                                                        track.log_likelihood.data_ptr(), None, track.smooth_confidence.data_ptr(),
+                                                        ws.data_ptr(), ws.numel(), stream), "ake_key_posteriors_f32")
         return track
 
     def _run_wrapped(self, slot, audio, lengths):
@@ -377,3 +418,42 @@ class KeyEstimator:
                                                genre.data_ptr() if genre is not None else None, ws.data_ptr(), ws.numel(),
                                                torch.cuda.current_stream().cuda_stream), "ake_pcnet_forward_f32")
         return (key, tonic, genre) if net.genre else (key, tonic)
+
+
+def _device_e_step(emissions, log_trans, log_prior, counts):
+    """The E-step of ``fit_key_transition`` on float32 (R, W, 24) ``emissions`` that live on the GPU: ``ake_key_posteriors_f32`` ->
+    ``(loglik, xi_sum)``.  Runs on the current stream, in a workspace of its own."""
+    L, dev = _lib.lib(), emissions.device
+    R, W, _ = emissions.shape
+    e = emissions.to(torch.float32).contiguous()
+    A = torch.as_tensor(log_trans).to(device=dev, dtype=torch.float32).contiguous()
+    prior = None if log_prior is None else torch.as_tensor(log_prior).to(device=dev, dtype=torch.float32).reshape(24).contiguous()
+    cnt = None if counts is None else torch.as_tensor(counts).to(device=dev, dtype=torch.int32).reshape(R).contiguous()
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    post, loglik, xi = f32(R, W, 24), f32(R), f32(R, 24, 24)
+    nbytes = L.ake_key_posteriors_workspace_bytes(R, W)
+    if nbytes == 0:
+        _lib.check(-1, "ake_key_posteriors_workspace_bytes")
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        _lib.check(L.ake_key_posteriors_f32(e.data_ptr(), R, W, ptr(cnt), A.data_ptr(), ptr(prior), None, post.data_ptr(), loglik.data_ptr(),
+                                            xi.data_ptr(), None, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
+                   "ake_key_posteriors_f32")
+    return loglik, xi
+
+
+def fit_key_transition(tracks, init=None, iterations=10, tied=True, pseudo_count=1.0):
+    """Fit a transition matrix to smooth tracks' own emissions by EM -> ``(log_trans, log_likelihoods)`` as ``metrics.fit_key_transition``,
+    whose loop this is: the E-step (``ake_key_posteriors_f32``) runs on every track's device emissions and counts, the M-step on its 576
+    numbers is ordinary torch (``metrics.transition_m_step``).  ``tracks``: one ``KeyTrack`` of ``track(smooth=True)`` or a list of
+    them.  ``log_trans`` (float64, on the host) goes straight into ``track(transition=...)``.  It is the matrix under which these
+    emissions score highest; no labelled modulations exist here, so no accuracy claim is made for it."""
+    tracks = list(tracks) if isinstance(tracks, (list, tuple)) else [tracks]
+    if not tracks or any(not isinstance(t, KeyTrack) or t.emissions is None for t in tracks):
+        raise ValueError("fit_key_transition: needs smooth tracks (KeyTrack.emissions); make them with track(..., smooth=True)")
+    tracks = [t for t in tracks if t.emissions.shape[1] > 0]
+    if not tracks:
+        raise ValueError("fit_key_transition: every recording is shorter than one window")
+    return metrics.fit_key_transition([t.emissions for t in tracks], counts=[t.counts for t in tracks], init=init, iterations=iterations,
+                                      tied=tied, pseudo_count=pseudo_count, e_step=_device_e_step)

@@ -426,6 +426,33 @@ int ake_viterbi_chunk_windows(void);
 int ake_viterbi_keys_f32(const float* emis_dev, int recordings, int windows, const int32_t* counts_dev, const float* log_trans_dev,
                          const float* log_prior_dev, int32_t* path_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream);
 
+/* Posterior key probabilities: the forward-backward pass over the same emis_dev [recordings][windows][24], with log_trans_dev,
+ * log_prior_dev and counts_dev as ake_viterbi_keys_f32 takes them (all finite; counts clamped to 0..windows).  For a recording of
+ * n = count windows, in float32 and the log domain (LSE = log-sum-exp, taken about its largest term):
+ *   a_0[j] = prior[j] + e[0][j]
+ *   a_w[j] = e[w][j] + LSE_i ( a_{w-1}[i] + A[i][j] )                     w = 1..n-1
+ *   c_w = LSE_j a_w[j];  a_w[j] -= c_w                                    every step, w = 0 included
+ *   b_{n-1}[i] = 0
+ *   b_w[i] = LSE_j ( A[i][j] + e[w+1][j] + b_{w+1}[j] );  then b_w[i] -= LSE_i b_w[i]
+ *   post_w[j]  = softmax_j ( a_w[j] + b_w[j] )                                                   w = 0..n-1
+ *   xi_w[i][j] = softmax over all 576 (i, j) of ( a_{w-1}[i] + A[i][j] + e[w][j] + b_w[j] )      w = 1..n-1
+ *   loglik = sum_w c_w;   xi_sum[i][j] = sum_{w=1..n-1} xi_w[i][j]   (expected transition counts; they add up to n - 1)
+ * The log domain stays finite for everything the Viterbi kernel accepts (forbidden transitions written as -1e4, emissions near -240).
+ * Outputs: post_dev [recordings][windows][24], probabilities: every row below the count sums to 1, rows at or behind it are zeros;
+ * loglik_dev [recordings], 0 for a count of 0; xi_sum_dev [recordings][24][24], nullable, zeros for counts 0 and 1; path_post_dev
+ * [recordings][windows], nullable: post[r][w][path_dev[r][w]] for path_dev (int32 [recordings][windows], the Viterbi path), 0 where the
+ * path holds -1 -- path_post_dev without path_dev is AKE_ERR_INVALID.  The emissions are log-scores, not normalised likelihoods, so
+ * loglik is a log-score of the recording under A (the quantity an EM fit of A raises), not a likelihood of the audio.
+ * Launches: the two serial chains side by side (one wave per recording and direction), then one kernel over (recording, window); with
+ * xi_sum_dev a third adds the per-chunk transition sums (ake_key_posteriors_chunk_windows() windows each) in chunk order.  No atomics:
+ * two runs on the same inputs are bit-identical.  The workspace holds a, b and the per-chunk sums; it and post_dev are 16-byte
+ * aligned. */
+size_t ake_key_posteriors_workspace_bytes(int recordings, int windows);
+int ake_key_posteriors_chunk_windows(void);
+int ake_key_posteriors_f32(const float* emis_dev, int recordings, int windows, const int32_t* counts_dev, const float* log_trans_dev,
+                           const float* log_prior_dev, const int32_t* path_dev, float* post_dev, float* loglik_dev, float* xi_sum_dev,
+                           float* path_post_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Per-kernel timing with hipEvents recorded on the launch stream (bench.py roofline leg).
  * ---------------------------------------------------------------------------------------- */

@@ -8,7 +8,7 @@
 
 Both sides run in this process, hipEvent-timed (torch.cuda.Event), warm, median of --reps runs each; per-kernel times from one run of each
 under the library's kernel timer.  max_abs_diff is for information: A and B differ at window edges by design (A's edge frames see the
-recording's neighbouring audio, B's see zero padding).  Usage: python tools/track_bench.py [--reps 30] [--smooth]
+recording's neighbouring audio, B's see zero padding).  Usage: python tools/track_bench.py [--reps 30] [--smooth] [--posteriors]
 
   --smooth : also, at every stride, what a smooth track costs ("smooth" in each row):
              track_smooth_ms      est.track(audio, stride_seconds=s, smooth=True), timed as A is
@@ -22,6 +22,19 @@ recording's neighbouring audio, B's see zero padding).  Usage: python tools/trac
                                   with torch on the CPU, so its emissions differ from the kernel's in the last bits; white noise through
                                   seeded weights scores the keys that close)
              viterbi_exact        the device path equals metrics.viterbi_keys on the device's own emissions (what the tests assert)
+
+  --posteriors : also, at every stride, what the posteriors of a smooth track cost ("posteriors" in each row):
+             track_posteriors_ms / track_smooth_ms   est.track(..., smooth=True, posteriors=True) and est.track(..., smooth=True), timed in
+                                  turn (one of each per repetition), medians
+             posteriors_add_ms    their difference
+             kernels_ms           key_forward_backward_kernel, key_posteriors_kernel and viterbi_keys_kernel under the library's kernel timer
+             chain_us_per_window / viterbi_us_per_window   the chain kernel's and the Viterbi kernel's time over the W windows of a recording
+             host_route_ms        emissions and counts of a finished smooth track copied to the CPU, metrics.key_posteriors there (float32);
+                                  wall clock from a synchronised device, copies included, median of min(--reps, 10) runs
+             fit_device_ms / fit_host_ms   one ake_amd.fit_key_transition of 10 iterations on the track (E-step on the device, the three
+                                  launches, M-step on the host) against metrics.fit_key_transition on the copied emissions (float32, copies
+                                  included); wall clock, median of 3 runs of each
+             max_abs_diff         device posteriors against the host route's, fitted probabilities device against host (for information)
 """
 import argparse
 import json
@@ -66,6 +79,57 @@ def kernels(fn):
     return res
 
 
+def timed_in_turn(f, g, reps, warmup=3):
+    """Medians of f and of g, one of each per repetition."""
+    for _ in range(warmup):
+        f()
+        g()
+    torch.cuda.synchronize()
+    ms = ([], [])
+    for _ in range(reps):
+        for fn, out in ((f, ms[0]), (g, ms[1])):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            out.append(a.elapsed_time(b))
+    return statistics.median(ms[0]), statistics.median(ms[1])
+
+
+def wall(fn, runs):
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(runs):
+        t0 = time.perf_counter()
+        out = fn()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(ms), out
+
+
+def posteriors_row(est, audio, stride, reps):
+    smooth = lambda: est.track(audio, stride_seconds=stride, smooth=True)                      # noqa: E731
+    both = lambda: est.track(audio, stride_seconds=stride, smooth=True, posteriors=True)      # noqa: E731
+    p_ms, s_ms = timed_in_turn(both, smooth, reps)
+    k = kernels(both)
+    tr = both()
+    W = tr.key.shape[1]
+    trans = metrics.key_transition_log(stay=float(np.exp(-tr.stride_seconds / 60.0))).float()
+    torch.cuda.synchronize()
+    h_ms, (post, _) = wall(lambda: metrics.key_posteriors(tr.emissions.cpu(), trans, counts=tr.counts.cpu()), max(1, min(reps, 10)))
+    fd_ms, (A_dev, _) = wall(lambda: ake_amd.fit_key_transition(tr, iterations=10), 3)
+    fh_ms, (A_host, _) = wall(lambda: metrics.fit_key_transition(tr.emissions.cpu(), counts=tr.counts.cpu(), iterations=10), 3)
+    names = ("key_forward_backward_kernel", "key_posteriors_kernel", "viterbi_keys_kernel")
+    return {"windows_per_recording": W, "track_posteriors_ms": round(p_ms, 4), "track_smooth_ms": round(s_ms, 4),
+            "posteriors_add_ms": round(p_ms - s_ms, 4), "kernels_ms": {n: k.get(n) for n in names},
+            "chain_us_per_window": round(1e3 * k.get(names[0], float("nan")) / W, 4),
+            "viterbi_us_per_window": round(1e3 * k.get(names[2], float("nan")) / W, 4),
+            "host_route_ms": round(h_ms, 4), "host_over_posteriors_add": round(h_ms / max(p_ms - s_ms, 1e-6), 1),
+            "fit_device_ms": round(fd_ms, 3), "fit_host_ms": round(fh_ms, 3), "fit_host_over_device": round(fh_ms / fd_ms, 1),
+            "max_abs_diff": {"posteriors": float((tr.posteriors.cpu() - post).abs().max()),
+                             "fitted_probabilities": float((torch.exp(A_dev) - torch.exp(A_host)).abs().max())}}
+
+
 def smooth_row(est, audio, stride, track_ms, reps):
     smooth = lambda: est.track(audio, stride_seconds=stride, smooth=True)     # noqa: E731
     s_ms = timed(smooth, reps)
@@ -101,6 +165,7 @@ def main():
     ap.add_argument("--minutes", type=float, default=5.0)
     ap.add_argument("--strides", type=float, nargs="+", default=[15.0, 5.0, 1.0])
     ap.add_argument("--smooth", action="store_true", help="also measure track(smooth=True) and the host route it replaces")
+    ap.add_argument("--posteriors", action="store_true", help="also measure track(smooth=True, posteriors=True), the host route and the EM fit")
     args = ap.parse_args()
     torch.manual_seed(0)
     gold = np.load(os.path.join(REPO, "tests", "golden", "pcnet_default.npz"))
@@ -137,6 +202,8 @@ def main():
                      "key_id_agreement": round(agree, 4), "track_kernels_ms": a_k, "clipwise_kernels_ms": b_k})
         if args.smooth:
             rows[-1]["smooth"] = smooth_row(est, audio, stride, a_ms, args.reps)
+        if args.posteriors:
+            rows[-1]["posteriors"] = posteriors_row(est, audio, stride, args.reps)
         del tr, key_b, tonic_b
         torch.cuda.empty_cache()
     torch.cuda.synchronize()
