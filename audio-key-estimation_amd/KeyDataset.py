@@ -87,7 +87,7 @@ class DatasetLoader:
         return self.size
 
     def get_waveform(self, file_id):
-        """-> (waveform float32 (n,), sample_rate)"""
+        """-> (waveform float32 (n,), sample_rate); an int16 array is 16-bit PCM (sample / 32768, ``ake_amd.pcm16_to_float``)"""
         raise NotImplementedError
 
     def get_key_signature_id(self, file_id) -> int:
@@ -139,7 +139,10 @@ class WaveformLoader(DatasetLoader):
         return list(range(self.size))
 
     def get_waveform(self, file_id):
-        return np.asarray(self.waveforms[file_id], dtype=np.float32), self.sample_rate
+        wav = np.asarray(self.waveforms[file_id])
+        if wav.dtype == np.int16:                                    # 16-bit PCM stays PCM: import_data runs the PCM CQT on it
+            return wav, self.sample_rate
+        return wav.astype(np.float32, copy=False), self.sample_rate
 
     def get_key_signature_id(self, file_id):
         k = self.keys[file_id]
@@ -230,11 +233,13 @@ class KeyDataset:
         waves = {}
         for idx, (f, dname, _) in enumerate(self.filenames):
             wav, sr = self.datasets[dname].get_waveform(f)
-            waves[idx] = torch.as_tensor(wav, dtype=torch.float32).reshape(-1)
-            groups[sr].append(idx)
+            wav = torch.as_tensor(wav)
+            pcm = wav.dtype == torch.int16                           # 16-bit PCM clips batch among themselves, through the PCM CQT
+            waves[idx] = (wav if pcm else wav.to(torch.float32)).reshape(-1)
+            groups[(sr, pcm)].append(idx)
         frames = getattr(self.opt, "frames", 5)
         window = getattr(self.opt, "window_size", WHOLE_SONG_FRAMES)
-        for sr, idxs in groups.items():
+        for (sr, pcm), idxs in groups.items():
             idxs = sorted(idxs, key=lambda i: waves[i].numel())
             # frames kept per clip: 1 + n // hop; --frames 0: max(T_i, 592) (KeyDataset.py:212-215)
             keep = (lambda n: whole_song_frames(n, window)) if frames <= 0 else (lambda n, hop=hop_for(sr, frames): 1 + n // hop)
@@ -244,7 +249,7 @@ class KeyDataset:
                 if min(lens) == max(lens):
                     mel = cqt_features(torch.stack([waves[i] for i in part]), sr, self.opt)
                 else:
-                    batch = torch.zeros((len(part), max(lens)), dtype=torch.float32)
+                    batch = torch.zeros((len(part), max(lens)), dtype=torch.int16 if pcm else torch.float32)
                     for j, i in enumerate(part):
                         batch[j, :lens[j]] = waves[i]
                     mel = cqt_features(batch, sr, self.opt, lengths=torch.tensor(lens, dtype=torch.int64))

@@ -48,6 +48,7 @@ SYMBOLS = {
     "ake_cqt_logmag_hops_f32": (_I, [_P, _P, _I, _I64, _I64, _P, _P, _P, _I64, _P, _SZ, _P]),
     "ake_cqt_frames_major_supported": (_I, [_P]),
     "ake_cqt_logmag_frames_major_f32": (_I, [_P, _P, _I, _I64, _I64, _P, _P, _SZ, _P]),
+    "ake_cqt_logmag_pcm16_f32": (_I, [_P, _P, _I, _I64, _I64, _P, _P, _P, _I64, _I, _P, _SZ, _P]),
     "ake_pcnet_default_config": (_I, [C.POINTER(PcnetConfig), _I, _I]),
     "ake_pcnet_create": (_I, [C.POINTER(PcnetConfig), C.POINTER(_P)]),
     "ake_pcnet_destroy": (None, [_P]),
@@ -83,12 +84,14 @@ SYMBOLS = {
     "ake_pipeline_workspace_bytes": (_SZ, [_P, _P, _I, _I64]),
     "ake_pipeline_forward_f32": (_I, [_P, _P, _P, _I, _I64, _I64, _P, _P, _P, _P, _SZ, _P]),
     "ake_pipeline_forward_ragged_f32": (_I, [_P, _P, _P, _I, _I64, _I64, _P, _P, _P, _P, _P, _SZ, _P]),
+    "ake_pipeline_forward_pcm16_f32": (_I, [_P, _P, _P, _I, _I64, _I64, _P, _P, _P, _P, _P, _SZ, _P]),
     "ake_pcnet_forward_windows_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I]),
     "ake_pcnet_forward_windows_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "ake_decode_keys_f32": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
     "ake_pipeline_track_workspace_bytes": (_SZ, [_P, _P, _I, _I64, _I, _I]),
     "ake_pipeline_track_f32": (_I, [_P, _P, _P, _I, _I64, _I64, _I, _I] + [_P] * 9 + [_SZ, _P]),
     "ake_pipeline_track_ragged_f32": (_I, [_P, _P, _P, _I, _I64, _I64, _P, _I, _I] + [_P] * 9 + [_SZ, _P]),
+    "ake_pipeline_track_pcm16_f32": (_I, [_P, _P, _P, _I, _I64, _I64, _P, _I, _I] + [_P] * 9 + [_SZ, _P]),
     "ake_key_emissions_f32": (_I, [_P, _P, _I, _P, _I, C.c_float, _P, _P]),
     "ake_viterbi_keys_workspace_bytes": (_SZ, [_I, _I]),
     "ake_viterbi_chunk_windows": (_I, []),
@@ -100,6 +103,7 @@ SYMBOLS = {
     "ake_resampler_destroy": (None, [_P]),
     "ake_resampler_out_len": (_I64, [_P, _I64]),
     "ake_resample_f32": (_I, [_P, _P, _I, _I, _I64, _I64, _I64, _I, _P, _P, _I64, _P, _P]),
+    "ake_resample_pcm16_f32": (_I, [_P, _P, _I, _I, _I64, _I64, _I64, _I64, _I, _P, _P, _I64, _P, _P]),
     "ake_prof_enable": (_I, [C.c_char_p, _I]),
     "ake_prof_collect": (_I, []),
     "ake_prof_reset": (_I, []),

@@ -16,6 +16,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from .audio import pcm16_rows
 
 
 def hop_for(sample_rate: int, frames: int) -> int:
@@ -81,13 +82,20 @@ class CQTPlan:
         """audio (B, n) or (n,) -> log(1+|CQT|) float32 (B, n_bins, out_frames); frames past the clip are zero.
 
         ``lengths`` (B,) int64: ragged batch -- row i holds ``lengths[i] <= n`` samples (the rest of the row is ignored); clip i
-        gets ``1 + lengths[i] // hop`` frames and zeros after them, as ``KeyDataset.__getitem__`` pads (KeyDataset.py:245)."""
+        gets ``1 + lengths[i] // hop`` frames and zeros after them, as ``KeyDataset.__getitem__`` pads (KeyDataset.py:245).
+
+        int16 audio is 16-bit PCM (``pcm16_to_float``), transformed by ``ake_cqt_logmag_pcm16_f32`` without a float32 copy of it: the
+        float32 route's result on the converted audio, bit for bit (engine 3)."""
         squeeze = audio.dim() == 1
         if squeeze:
             audio = audio[None]
-        audio = audio.to(device=self.device, dtype=torch.float32)
-        if audio.stride(-1) != 1:
-            audio = audio.contiguous()
+        pcm = audio.dtype == torch.int16
+        if pcm:
+            audio, row_stride = pcm16_rows(audio, self.device)
+        else:
+            audio = audio.to(device=self.device, dtype=torch.float32)
+            if audio.stride(-1) != 1:
+                audio = audio.contiguous()
         B, n = audio.shape
         T = self.num_frames(n)
         out_frames = T if out_frames is None else int(out_frames)
@@ -99,7 +107,14 @@ class CQTPlan:
         ws = self._workspace(nbytes)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream().cuda_stream
-            if lengths is None:
+            if pcm:
+                if lengths is not None:
+                    lengths = torch.as_tensor(lengths).to(device=self.device, dtype=torch.int64).contiguous()
+                    assert lengths.shape == (B,)
+                _lib.check(L.ake_cqt_logmag_pcm16_f32(self._h, audio.data_ptr(), B, n, row_stride, lengths.data_ptr() if lengths is not None else None,
+                                                      None, out.data_ptr(), out_frames, 0, ws.data_ptr(), ws.numel(), stream),
+                           "ake_cqt_logmag_pcm16_f32")
+            elif lengths is None:
                 _lib.check(L.ake_cqt_logmag_f32(self._h, audio.data_ptr(), B, n, audio.stride(0), out.data_ptr(), out_frames,
                                                 ws.data_ptr(), ws.numel(), stream), "ake_cqt_logmag_f32")
             else:
@@ -119,10 +134,15 @@ class CQTPlan:
         audio (B, n) -> float32 (B, n_bins, out_frames): clip i is transformed at hop ``hops[i]`` (int32 on the device, >= 1) and has
         ``T_i = 1 + lengths[i] // hops[i]`` frames (``lengths`` (B,) int64: samples of each row; None: every row has n); the output holds
         its first ``min(T_i, out_frames)`` frames, then zeros.  Nothing waits for the device.  ``workspace``: a uint8 device tensor of at
-        least ``workspace_bytes_hops(B, n, out_frames)`` bytes to use instead of the plan's own (one per stream)."""
-        audio = audio.to(device=self.device, dtype=torch.float32)
-        if audio.stride(-1) != 1:
-            audio = audio.contiguous()
+        least ``workspace_bytes_hops(B, n, out_frames)`` bytes to use instead of the plan's own (one per stream).  int16 audio is 16-bit
+        PCM, as in ``logmag``."""
+        pcm = audio.dtype == torch.int16
+        if pcm:
+            audio, row_stride = pcm16_rows(audio, self.device)
+        else:
+            audio = audio.to(device=self.device, dtype=torch.float32)
+            if audio.stride(-1) != 1:
+                audio = audio.contiguous()
         B, n = audio.shape
         out_frames = int(out_frames)
         hops = torch.as_tensor(hops).to(device=self.device, dtype=torch.int32).contiguous()
@@ -137,6 +157,12 @@ class CQTPlan:
         nbytes = self.workspace_bytes_hops(B, n, out_frames)
         ws = self._workspace(nbytes) if workspace is None else workspace
         assert ws.numel() >= nbytes
+        if pcm:
+            with torch.cuda.device(self.device):
+                _lib.check(L.ake_cqt_logmag_pcm16_f32(self._h, audio.data_ptr(), B, n, row_stride, lengths.data_ptr() if lengths is not None else None,
+                                                      hops.data_ptr(), out.data_ptr(), out_frames, 0, ws.data_ptr(), ws.numel(),
+                                                      torch.cuda.current_stream().cuda_stream), "ake_cqt_logmag_pcm16_f32")
+            return out
         with torch.cuda.device(self.device):
             _lib.check(L.ake_cqt_logmag_hops_f32(self._h, audio.data_ptr(), B, n, audio.stride(0),
                                                  lengths.data_ptr() if lengths is not None else None, hops.data_ptr(), out.data_ptr(),

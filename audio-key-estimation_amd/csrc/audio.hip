@@ -81,6 +81,56 @@ __global__ __launch_bounds__(256) void resample_kernel(ResampleArgs a) {
     *o = acc * scale;
 }
 
+// 16-bit PCM in place: sample s stands for float(s) * 2^-15 (exact), read at x[c * channel_stride + i * sample_stride] -- planar
+// (B, C, n) and interleaved (B, n, C) storage alike.  Same order of additions and the same fmaf chain as resample_kernel, so the output
+// is bit-identical to resample_kernel on the converted planar tensor.
+struct ResamplePcmArgs {
+    const short* in;
+    long long clip_stride, channel_stride, sample_stride;
+    int channels, channel;
+    long long n_in;
+    const long long* n_in_clip;
+    float* out;
+    long long out_stride, n_out_max;
+    long long* n_out_clip;
+    const float* h;
+    int up, down, half;
+};
+
+__global__ __launch_bounds__(256) void resample_pcm16_kernel(ResamplePcmArgs a) {
+    constexpr float kScale = 1.f / 32768.f;
+    const int clip = blockIdx.y;
+    long long n = a.n_in;
+    if (a.n_in_clip) { const long long nc = a.n_in_clip[clip]; n = nc < 0 ? 0 : (nc < n ? nc : n); }
+    const long long n_out = (n * a.up + a.down - 1) / a.down;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && a.n_out_clip) a.n_out_clip[clip] = n_out;
+    const long long k = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (k >= a.n_out_max) return;
+    float* o = a.out + clip * a.out_stride + k;
+    if (k >= n_out) { *o = 0.f; return; }                         // zero padding behind a shorter clip
+    const short* x = a.in + clip * a.clip_stride;
+    const int nch = a.channel >= 0 ? 1 : a.channels;
+    const long long c0 = a.channel >= 0 ? a.channel : 0;
+    const float scale = a.channel >= 0 ? 1.f : 1.f / a.channels;
+    float acc = 0.f;
+    if (a.up == a.down) {                                         // same rate: channel selection / mix only
+        for (int c = 0; c < nch; ++c) acc += static_cast<float>(x[(c0 + c) * a.channel_stride + k * a.sample_stride]) * kScale;
+        *o = acc * scale;
+        return;
+    }
+    const long long t = k * a.down;
+    long long i_lo = t - a.half <= 0 ? 0 : (t - a.half + a.up - 1) / a.up;
+    long long i_hi = (t + a.half) / a.up;
+    i_hi = i_hi < n - 1 ? i_hi : n - 1;
+    int j = static_cast<int>(t - i_lo * a.up + a.half);           // tap of input sample i_lo; the next sample's is up less
+    for (long long i = i_lo; i <= i_hi; ++i, j -= a.up) {
+        float v = 0.f;
+        for (int c = 0; c < nch; ++c) v += static_cast<float>(x[(c0 + c) * a.channel_stride + i * a.sample_stride]) * kScale;
+        acc = fmaf(v, a.h[j], acc);
+    }
+    *o = acc * scale;
+}
+
 }  // namespace
 
 extern "C" {
@@ -146,6 +196,27 @@ int ake_resample_f32(const ake_resampler* r, const float* in_dev, int batch, int
     hipStream_t s = static_cast<hipStream_t>(stream);
     ake::ProfScope ps("resample_kernel", s);
     hipLaunchKernelGGL(resample_kernel, dim3(static_cast<unsigned>((n_out + 255) / 256), batch), dim3(256), 0, s, a);
+    AKE_HIP_CHECK(hipGetLastError());
+    return AKE_OK;
+}
+
+int ake_resample_pcm16_f32(const ake_resampler* r, const int16_t* in_dev, int batch, int channels, int64_t n_in, int64_t clip_stride,
+                           int64_t channel_stride, int64_t sample_stride, int channel, const int64_t* n_in_clip_dev, float* out_dev,
+                           int64_t out_stride, int64_t* n_out_clip_dev, ake_stream_t stream) {
+    AKE_REQUIRE(r && in_dev && out_dev, AKE_ERR_INVALID, "ake_resample_pcm16_f32: null argument");
+    AKE_REQUIRE(batch > 0 && channels > 0 && n_in > 0 && channel >= -1 && channel < channels, AKE_ERR_INVALID, "resample: bad batch / channels / channel");
+    AKE_REQUIRE(clip_stride >= 0 && channel_stride >= 0 && sample_stride >= 1, AKE_ERR_INVALID, "resample: bad strides (%lld, %lld, %lld)",
+                static_cast<long long>(clip_stride), static_cast<long long>(channel_stride), static_cast<long long>(sample_stride));
+    const int64_t n_out = ake_resampler_out_len(r, n_in);
+    AKE_REQUIRE(out_stride >= n_out, AKE_ERR_INVALID, "resample: out_stride %lld < %lld output samples", static_cast<long long>(out_stride), static_cast<long long>(n_out));
+    ResamplePcmArgs a;
+    a.in = in_dev; a.clip_stride = clip_stride; a.channel_stride = channel_stride; a.sample_stride = sample_stride; a.channels = channels;
+    a.channel = channel; a.n_in = n_in; a.n_in_clip = reinterpret_cast<const long long*>(n_in_clip_dev);
+    a.out = out_dev; a.out_stride = out_stride; a.n_out_max = n_out; a.n_out_clip = reinterpret_cast<long long*>(n_out_clip_dev);
+    a.h = r->h_dev; a.up = r->up; a.down = r->down; a.half = r->half;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ake::ProfScope ps("resample_pcm16_kernel", s);
+    hipLaunchKernelGGL(resample_pcm16_kernel, dim3(static_cast<unsigned>((n_out + 255) / 256), batch), dim3(256), 0, s, a);
     AKE_HIP_CHECK(hipGetLastError());
     return AKE_OK;
 }

@@ -79,7 +79,7 @@ using namespace ake;
 
 extern "C" {
 
-int ake_version(void) { return 104; }
+int ake_version(void) { return 105; }
 int ake_build_has_diag(void) { return 0; }
 
 const char* ake_last_error(void) { return g_err; }

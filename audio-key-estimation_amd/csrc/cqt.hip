@@ -219,7 +219,7 @@ constexpr int kCascHist = 32;                                          // ring h
 constexpr int kLagHost[kCascMax + 1] = {0, 16, 24, 24, 24, 24, 24, 24};
 
 struct CascArgs {
-    const float* x;            // [batch][x_stride] audio
+    const float* x;            // [batch][x_stride] audio (the PCM instantiation reads the same pointer as int16 samples, x_stride in samples)
     long long x_stride;
     int n;                     // samples per clip (ragged batches: of the longest clip)
     const long long* n_clip;   // ragged batches: samples of each clip (<= n), or null; the rest of a row reads as zero
@@ -336,7 +336,9 @@ __device__ __forceinline__ void cascade_level(const CascArgs& a, float* lds, int
 }
 
 // HOPS: every clip has its own hop (a.hops[clip]); only the "store near frame centres" predicate depends on it, never a stored value.
-template <int NODD, int C, int NT, bool SPLIT, bool HOPS = false>
+// SAMPLE: float, or short = 16-bit PCM, sample s standing for float(s) * 2^-15 (exact for every int16).  Only `fetch` knows the
+// difference: the LDS image, the split copy of level 0 and the `need` predicate see the floats the float kernel sees on the converted audio.
+template <int NODD, int C, int NT, bool SPLIT, bool HOPS = false, typename SAMPLE = float>
 __global__ __launch_bounds__(NT) void cqt_cascade_kernel(CascArgs a) {
     static_assert(C % 512 == 0 && C >= 1024 && (C / 4) % NT == 0, "chunk");
     using Lay = CascLayout<C>;
@@ -349,23 +351,39 @@ __global__ __launch_bounds__(NT) void cqt_cascade_kernel(CascArgs a) {
     const int k_start = k_own - a.warm > 0 ? k_own - a.warm : 0;
     if (k_own >= a.ticks_total) return;
     for (int i = tid; i < Lay::total; i += NT) lds[i] = 0.f;
-    const float* xs = a.x + clip * a.x_stride;
+    constexpr bool PCM = sizeof(SAMPLE) == 2;
+    const SAMPLE* xs = reinterpret_cast<const SAMPLE*>(a.x) + clip * a.x_stride;
 
     constexpr int G = C / 4 / NT;                                     // float4 groups of the audio chunk per thread
     // Audio through a buffer resource: hardware range checking returns 0 for every dword outside [0, n) -- the zero padding
     // of the transform's definition -- so the prefetch is branch-free and all G loads are in flight together.
     int n_here = a.n;
     if (a.n_clip) { const long long nc = a.n_clip[clip]; n_here = nc < 0 ? 0 : (nc < a.n ? static_cast<int>(nc) : a.n); }
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xs), 0, n_here * 4, 0x00020000);
+    // PCM: the range is checked per dword and a dword holds two samples, so it ends with the dword of the row's last sample (rows are
+    // 4-byte aligned: base and stride are checked by the entry point).  For an odd n_here that dword's high half is not the clip's: it is
+    // zeroed in the register.  Nothing behind that dword is read.
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<SAMPLE*>(xs), 0, PCM ? (n_here + 1) / 2 * 4 : n_here * 4, 0x00020000);
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
     f4u pre[G];
     auto fetch = [&](int k) {                                          // audio samples [F0(k-1), F0(k))
         const int s0 = a.g0 + k * C;
 #pragma unroll
         for (int g = 0; g < G; ++g) {
             const int i0 = s0 + 4 * (tid + NT * g);                   // negative -> huge unsigned offset -> out of range -> 0
-            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, i0 * 4, 0, 0);
-            pre[g] = __builtin_bit_cast(f4u, v);
+            if constexpr (PCM) {
+                const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, i0 * 2, 0, 0);
+                constexpr float kScale = 1.f / 32768.f;
+                const int w0 = static_cast<int>(v[0]), w1 = static_cast<int>(v[1]);
+                // i0 is a multiple of 4: only the odd samples can lie in a dword that the range check lets through but the clip does not own
+                pre[g][0] = static_cast<float>(static_cast<short>(w0)) * kScale;
+                pre[g][1] = i0 + 1 < n_here ? static_cast<float>(w0 >> 16) * kScale : 0.f;
+                pre[g][2] = static_cast<float>(static_cast<short>(w1)) * kScale;
+                pre[g][3] = i0 + 3 < n_here ? static_cast<float>(w1 >> 16) * kScale : 0.f;
+            } else {
+                const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, i0 * 4, 0, 0);
+                pre[g] = __builtin_bit_cast(f4u, v);
+            }
         }
     };
     fetch(k_start);
@@ -1249,7 +1267,7 @@ size_t ake_cqt_workspace_bytes_hops(const ake_cqt_plan* p, int batch, int64_t n_
 namespace {
 int cqt_logmag_impl(const ake_cqt_plan* p, const float* audio, int batch, int64_t n, int64_t audio_stride, const int64_t* n_clip,
                     float* out, int64_t out_frames, void* workspace, size_t ws_bytes, ake_stream_t stream_, bool frames_major = false,
-                    const int32_t* hops = nullptr);
+                    const int32_t* hops = nullptr, bool pcm = false);
 }
 
 extern "C" {
@@ -1287,14 +1305,41 @@ int ake_cqt_logmag_hops_f32(const ake_cqt_plan* p, const float* audio, int batch
     return cqt_logmag_impl(p, audio, batch, n_max, audio_stride, n_clip_dev, out, out_frames, workspace, ws_bytes, stream_, false, hop_dev);
 }
 
+int ake_cqt_logmag_pcm16_f32(const ake_cqt_plan* p, const int16_t* audio, int batch, int64_t n_max, int64_t audio_stride, const int64_t* n_clip_dev,
+                             const int32_t* hop_dev, float* out, int64_t out_frames, int frames_major, void* workspace, size_t ws_bytes,
+                             ake_stream_t stream_) {
+    AKE_REQUIRE(p, AKE_ERR_INVALID, "ake_cqt_logmag_pcm16_f32: null plan");
+    AKE_REQUIRE(p->engine == 3, AKE_ERR_UNSUPPORTED, "cqt: 16-bit PCM input needs engine 3 (this plan runs engine %d)", p->engine);
+    // the loader reads whole dwords: every row must start on one
+    AKE_REQUIRE((reinterpret_cast<uintptr_t>(audio) & 3) == 0 && (audio_stride & 1) == 0, AKE_ERR_INVALID,
+                "cqt: 16-bit PCM rows must be 4-byte aligned (base %p, audio_stride %lld samples: the stride must be even)",
+                static_cast<const void*>(audio), static_cast<long long>(audio_stride));
+    const float* as_f32 = reinterpret_cast<const float*>(audio);     // cqt_logmag_impl(pcm = true) hands it to the int16 cascade untouched
+    if (hop_dev) {
+        AKE_REQUIRE(!frames_major, AKE_ERR_UNSUPPORTED, "cqt: per-clip hops have no frames-major output");
+        AKE_REQUIRE(p->hop_twos == 0, AKE_ERR_INVALID, "cqt: per-clip hops need a plan with an odd hop_length (a phase table for every "
+                                                       "phase; create it with hop_length = 1), this one has %d", p->cfg.hop_length);
+        AKE_REQUIRE(out_frames > 0 && batch > 0 && static_cast<int64_t>(batch) * out_frames <= (1ll << 30), AKE_ERR_INVALID,
+                    "cqt: bad batch (%d) / out_frames (%lld)", batch, static_cast<long long>(out_frames));
+        return cqt_logmag_impl(p, as_f32, batch, n_max, audio_stride, n_clip_dev, out, out_frames, workspace, ws_bytes, stream_, false, hop_dev, true);
+    }
+    // frames-major: [batch][num_frames][n_bins] has no padded frames to write
+    AKE_REQUIRE(!frames_major || out_frames == ake_cqt_num_frames(p, n_max), AKE_ERR_INVALID,
+                "cqt: the frames-major output has exactly num_frames frames, out_frames is %lld", static_cast<long long>(out_frames));
+    return cqt_logmag_impl(p, as_f32, batch, n_max, audio_stride, n_clip_dev, out, out_frames, workspace, ws_bytes, stream_, frames_major != 0, nullptr,
+                           true);
+}
+
 }  // extern "C"
 
 namespace {
 
 int cqt_logmag_impl(const ake_cqt_plan* p, const float* audio, int batch, int64_t n, int64_t audio_stride, const int64_t* n_clip,
                     float* out, int64_t out_frames, void* workspace, size_t ws_bytes, ake_stream_t stream_, bool frames_major,
-                    const int32_t* hops) {
+                    const int32_t* hops, bool pcm) {
+    // pcm: `audio` points at int16 samples (strides in samples); only engine 3's cascade has that instantiation
     AKE_REQUIRE(p && audio && out, AKE_ERR_INVALID, "ake_cqt_logmag_f32: null argument");
+    AKE_REQUIRE(!pcm || p->engine == 3, AKE_ERR_UNSUPPORTED, "cqt: 16-bit PCM input needs engine 3 (this plan runs engine %d)", p->engine);
     // frames_major: leave the result as the filter bank writes it, [clip][frame][bin] (no transpose pass); engine 3, equal-length clips
     AKE_REQUIRE(!frames_major || ((p->engine == 3 || p->engine == 5) && !n_clip), AKE_ERR_UNSUPPORTED, "cqt: the frames-major output needs engine 3 or 5 and equal-length clips");
     AKE_REQUIRE(batch > 0 && n > 0 && audio_stride >= n, AKE_ERR_INVALID, "cqt: bad batch/n_samples/stride");
@@ -1334,7 +1379,13 @@ int cqt_logmag_impl(const ake_cqt_plan* p, const float* audio, int batch, int64_
         dim3 grid((a.ticks_total + a.ticks_per_seg - 1) / a.ticks_per_seg, batch);
         ake::ProfScope ps("cqt_cascade_kernel", stream);
         const bool split = a.ph[0] != nullptr;
-        if (a.hops && p->half_len == 15) hipLaunchKernelGGL((cqt_cascade_kernel<8, C, NT, true, true>), grid, dim3(NT), 0, stream, a);
+        if (pcm) {                                                    // engine 3 only: always split
+            if (a.hops && p->half_len == 15) hipLaunchKernelGGL((cqt_cascade_kernel<8, C, NT, true, true, short>), grid, dim3(NT), 0, stream, a);
+            else if (a.hops) hipLaunchKernelGGL((cqt_cascade_kernel<12, C, NT, true, true, short>), grid, dim3(NT), 0, stream, a);
+            else if (p->half_len == 15) hipLaunchKernelGGL((cqt_cascade_kernel<8, C, NT, true, false, short>), grid, dim3(NT), 0, stream, a);
+            else hipLaunchKernelGGL((cqt_cascade_kernel<12, C, NT, true, false, short>), grid, dim3(NT), 0, stream, a);
+        }
+        else if (a.hops && p->half_len == 15) hipLaunchKernelGGL((cqt_cascade_kernel<8, C, NT, true, true>), grid, dim3(NT), 0, stream, a);
         else if (a.hops) hipLaunchKernelGGL((cqt_cascade_kernel<12, C, NT, true, true>), grid, dim3(NT), 0, stream, a);
         else if (p->half_len == 15 && split) hipLaunchKernelGGL((cqt_cascade_kernel<8, C, NT, true>), grid, dim3(NT), 0, stream, a);
         else if (p->half_len == 15) hipLaunchKernelGGL((cqt_cascade_kernel<8, C, NT, false>), grid, dim3(NT), 0, stream, a);

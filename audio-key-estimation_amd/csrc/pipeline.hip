@@ -54,9 +54,10 @@ size_t ake_pipeline_workspace_bytes(const ake_cqt_plan* plan, const ake_pcnet* n
     return pc.total;
 }
 
+// pcm16_dev != null: the audio is 16-bit PCM (ake_cqt_logmag_pcm16_f32) and audio_dev is ignored; everything behind the CQT is shared
 static int pipeline_impl(const ake_cqt_plan* plan, const ake_pcnet* net, const float* audio_dev, int batch, int64_t n_samples,
                          int64_t audio_stride, const int64_t* n_clip_dev, int hop, float* key_out_dev, float* tonic_out_dev,
-                         float* genre_out_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream);
+                         float* genre_out_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream, const int16_t* pcm16_dev = nullptr);
 
 int ake_pipeline_forward_f32(const ake_cqt_plan* plan, const ake_pcnet* net, const float* audio_dev, int batch,
                              int64_t n_samples, int64_t audio_stride, float* key_out_dev, float* tonic_out_dev,
@@ -75,10 +76,18 @@ int ake_pipeline_forward_ragged_f32(const ake_cqt_plan* plan, const ake_pcnet* n
                          genre_out_dev, workspace, workspace_bytes, stream);
 }
 
+int ake_pipeline_forward_pcm16_f32(const ake_cqt_plan* plan, const ake_pcnet* net, const int16_t* audio_dev, int batch, int64_t n_max,
+                                   int64_t audio_stride, const int64_t* n_samples_dev, float* key_out_dev, float* tonic_out_dev,
+                                   float* genre_out_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream) {
+    AKE_REQUIRE(plan && n_max > 0, AKE_ERR_INVALID, "ake_pipeline_forward_pcm16_f32: bad argument");
+    return pipeline_impl(plan, net, nullptr, batch, n_max, audio_stride, n_samples_dev, ake_cqt_plan_hop(plan), key_out_dev, tonic_out_dev,
+                         genre_out_dev, workspace, workspace_bytes, stream, audio_dev);
+}
+
 static int pipeline_impl(const ake_cqt_plan* plan, const ake_pcnet* net, const float* audio_dev, int batch, int64_t n_samples,
                          int64_t audio_stride, const int64_t* n_clip_dev, int hop, float* key_out_dev, float* tonic_out_dev,
-                         float* genre_out_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream) {
-    AKE_REQUIRE(plan && net && audio_dev, AKE_ERR_INVALID, "ake_pipeline_forward_f32: null argument");
+                         float* genre_out_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream, const int16_t* pcm16_dev) {
+    AKE_REQUIRE(plan && net && (audio_dev || pcm16_dev), AKE_ERR_INVALID, "ake_pipeline_forward_f32: null argument");
     const int n_bins = ake_cqt_plan_n_bins(plan);
     AKE_REQUIRE(n_bins == ake_pcnet_pitches(net), AKE_ERR_INVALID, "pipeline: CQT has %d bins but the net expects %d pitches",
                 n_bins, ake_pcnet_pitches(net));
@@ -91,7 +100,8 @@ static int pipeline_impl(const ake_cqt_plan* plan, const ake_pcnet* net, const f
     // equal-length clips through the default net: the CQT stays in the filter bank's own [clip][frame][bin] order and the net's two
     // readers transpose while they stage it -- no transpose pass, same results bit for bit
     const bool fm = !n_clip_dev && ake_cqt_frames_major_supported(plan) && ake_pcnet_accepts_frames_major(net, batch, static_cast<int>(T));
-    rc = n_clip_dev ? ake_cqt_logmag_ragged_f32(plan, audio_dev, batch, n_samples, audio_stride, n_clip_dev, pc.mel, T, pc.cqt_ws, pc.cqt_bytes, stream)
+    rc = pcm16_dev  ? ake_cqt_logmag_pcm16_f32(plan, pcm16_dev, batch, n_samples, audio_stride, n_clip_dev, nullptr, pc.mel, T, fm ? 1 : 0, pc.cqt_ws, pc.cqt_bytes, stream)
+         : n_clip_dev ? ake_cqt_logmag_ragged_f32(plan, audio_dev, batch, n_samples, audio_stride, n_clip_dev, pc.mel, T, pc.cqt_ws, pc.cqt_bytes, stream)
          : fm       ? ake_cqt_logmag_frames_major_f32(plan, audio_dev, batch, n_samples, audio_stride, pc.mel, pc.cqt_ws, pc.cqt_bytes, stream)
                     : ake_cqt_logmag_f32(plan, audio_dev, batch, n_samples, audio_stride, pc.mel, T, pc.cqt_ws, pc.cqt_bytes, stream);
     if (rc) return rc;

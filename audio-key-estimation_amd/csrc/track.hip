@@ -678,8 +678,9 @@ int carve_track(const ake_cqt_plan* plan, const ake_pcnet* net, int recordings, 
 int track_impl(const ake_cqt_plan* plan, const ake_pcnet* net, const float* audio_dev, int recordings, int64_t n_samples,
                int64_t audio_stride, const int64_t* n_clip_dev, int window_frames, int stride_frames, float* key_out, float* tonic_out,
                float* genre_out, int32_t* key_id, int32_t* sig, int32_t* tonic_id, float* confidence, int32_t* counts, void* ws,
-               size_t ws_bytes, ake_stream_t stream) {
-    AKE_REQUIRE(audio_dev && key_out && tonic_out && key_id && sig && tonic_id && confidence && counts, AKE_ERR_INVALID, "track: null argument");
+               size_t ws_bytes, ake_stream_t stream, const int16_t* pcm16_dev = nullptr) {
+    // pcm16_dev != null: the audio is 16-bit PCM (ake_cqt_logmag_pcm16_f32) and audio_dev is ignored
+    AKE_REQUIRE((audio_dev || pcm16_dev) && key_out && tonic_out && key_id && sig && tonic_id && confidence && counts, AKE_ERR_INVALID, "track: null argument");
     TrackCarve tc;
     int rc = carve_track(plan, net, recordings, n_samples, window_frames, stride_frames, ws, &tc);
     if (rc) return rc;
@@ -688,7 +689,8 @@ int track_impl(const ake_cqt_plan* plan, const ake_pcnet* net, const float* audi
     // equal-length recordings: the CQT stays in the filter bank's own [recording][frame][bin] order (no transpose pass; the gather
     // transposes the windows it copies anyway).  Ragged recordings: [recording][bin][frame], frames behind a recording's end are zeros.
     const bool fm = !n_clip_dev && ake_cqt_frames_major_supported(plan);
-    rc = n_clip_dev ? ake_cqt_logmag_ragged_f32(plan, audio_dev, recordings, n_samples, audio_stride, n_clip_dev, tc.mel, tc.T, tc.cqt_ws, tc.cqt_bytes, stream)
+    rc = pcm16_dev  ? ake_cqt_logmag_pcm16_f32(plan, pcm16_dev, recordings, n_samples, audio_stride, n_clip_dev, nullptr, tc.mel, tc.T, fm ? 1 : 0, tc.cqt_ws, tc.cqt_bytes, stream)
+         : n_clip_dev ? ake_cqt_logmag_ragged_f32(plan, audio_dev, recordings, n_samples, audio_stride, n_clip_dev, tc.mel, tc.T, tc.cqt_ws, tc.cqt_bytes, stream)
          : fm       ? ake_cqt_logmag_frames_major_f32(plan, audio_dev, recordings, n_samples, audio_stride, tc.mel, tc.cqt_ws, tc.cqt_bytes, stream)
                     : ake_cqt_logmag_f32(plan, audio_dev, recordings, n_samples, audio_stride, tc.mel, tc.T, tc.cqt_ws, tc.cqt_bytes, stream);
     if (rc) return rc;
@@ -863,6 +865,14 @@ int ake_pipeline_track_ragged_f32(const ake_cqt_plan* plan, const ake_pcnet* net
     AKE_REQUIRE(n_samples_dev, AKE_ERR_INVALID, "ake_pipeline_track_ragged_f32: null n_samples_dev");
     return track_impl(plan, net, audio_dev, recordings, n_max, audio_stride, n_samples_dev, window_frames, stride_frames, key_out_dev, tonic_out_dev,
                       genre_out_dev, key_id_dev, sig_dev, tonic_id_dev, confidence_dev, counts_dev, workspace, workspace_bytes, stream);
+}
+
+int ake_pipeline_track_pcm16_f32(const ake_cqt_plan* plan, const ake_pcnet* net, const int16_t* audio_dev, int recordings, int64_t n_max,
+                                 int64_t audio_stride, const int64_t* lengths_dev, int window_frames, int stride_frames, float* key_out_dev,
+                                 float* tonic_out_dev, float* genre_out_dev, int32_t* key_id_dev, int32_t* sig_dev, int32_t* tonic_id_dev,
+                                 float* confidence_dev, int32_t* counts_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream) {
+    return track_impl(plan, net, nullptr, recordings, n_max, audio_stride, lengths_dev, window_frames, stride_frames, key_out_dev, tonic_out_dev,
+                      genre_out_dev, key_id_dev, sig_dev, tonic_id_dev, confidence_dev, counts_dev, workspace, workspace_bytes, stream, audio_dev);
 }
 
 }  // extern "C"

@@ -14,7 +14,7 @@ import math
 import torch
 
 from . import _lib, metrics
-from .audio import get_resampler
+from .audio import get_resampler, pcm16_rows
 from .cqt import WHOLE_SONG_FRAMES, CQTPlan, get_any_hop_plan, hop_for, hop_for_window
 from .models import PitchClassNet
 
@@ -164,6 +164,11 @@ class KeyEstimator:
     def __call__(self, audio: torch.Tensor, lengths: torch.Tensor | None = None, rate: int | None = None, channel: int = 0):
         """audio (B, n) or (B, C, n) float32 on the GPU -> tuple of (B,12), (B,12)[, (B,11)] float32 tensors.
 
+        int16 audio is 16-bit PCM, sample / 32768 (``ake_amd.pcm16_to_float``): mono at the estimator's rate goes straight to the PCM
+        pipeline entry, (B, C, n) audio of any strides (interleaved storage as ``buf.transpose(1, 2)``) or another ``rate`` through the PCM
+        resampler first.  No float32 copy of the audio is written, and the results are those of the float32 route on the converted
+        audio, bit for bit.  Every other dtype is converted with ``.to(float32)``, unscaled.
+
         ``lengths`` (B,) int64: ragged batch, row i holds ``lengths[i] <= n`` samples; every clip is pooled over its own frames
         (``seq_length`` = ``1 + lengths[i] // hop``), as a ``KeyDataset`` batch of unequal clips is (KeyDataset.py:245-256).
         ``rate``: sample rate of ``audio`` when it is not the estimator's -- it is resampled on the device first
@@ -201,7 +206,8 @@ class KeyEstimator:
     def track(self, audio: torch.Tensor, lengths: torch.Tensor | None = None, rate: int | None = None, channel: int = 0,
               window_seconds: float = 15.0, stride_seconds: float = 5.0, smooth: bool = False, mean_key_seconds: float = 60.0,
               transition: torch.Tensor | None = None, signature_weight: float = 1.0, posteriors: bool = False) -> KeyTrack:
-        """The key of long recordings over time: audio (R, n) or (R, C, n) float32 on the GPU -> ``KeyTrack``.
+        """The key of long recordings over time: audio (R, n) or (R, C, n) float32 on the GPU -> ``KeyTrack``.  int16 audio is 16-bit
+        PCM, as in ``__call__``.
 
         Every recording is transformed ONCE at the estimator's hop (``T = 1 + n // hop`` frames); the net then runs on sliding windows
         of those frames -- ``window_frames = 1 + round(window_seconds * sample_rate) // hop`` frames each (76 for 15 s at 22.05 kHz and 5
@@ -273,9 +279,13 @@ class KeyEstimator:
 
     def _run_track(self, slot, audio, lengths, wf, sf, smoothing=None):
         net, L, dev = self.net, _lib.lib(), self.device
-        audio = audio.to(device=dev, dtype=torch.float32)
-        if audio.stride(-1) != 1:
-            audio = audio.contiguous()
+        pcm = audio.dtype == torch.int16
+        if pcm:
+            audio, row_stride = pcm16_rows(audio, dev)
+        else:
+            audio = audio.to(device=dev, dtype=torch.float32)
+            if audio.stride(-1) != 1:
+                audio = audio.contiguous()
         R, n = audio.shape
         hop = self.plan.hop_length
         W = track_counts(1 + n // hop, wf, sf)
@@ -313,7 +323,14 @@ class KeyEstimator:
         with torch.cuda.device(dev):
             outs = (key.data_ptr(), tonic.data_ptr(), genre.data_ptr() if genre is not None else None, key_id.data_ptr(), sig.data_ptr(),
                     tonic_id.data_ptr(), conf.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
-            if lengths is None:
+            if pcm:
+                if lengths is not None:
+                    lengths = torch.as_tensor(lengths).to(device=dev, dtype=torch.int64).contiguous()
+                    assert lengths.shape == (R,)
+                _lib.check(L.ake_pipeline_track_pcm16_f32(self.plan.handle, net.handle, audio.data_ptr(), R, n, row_stride,
+                                                          lengths.data_ptr() if lengths is not None else None, wf, sf, *outs),
+                           "ake_pipeline_track_pcm16_f32")
+            elif lengths is None:
                 _lib.check(L.ake_pipeline_track_f32(self.plan.handle, net.handle, audio.data_ptr(), R, n, audio.stride(0), wf, sf, *outs),
                            "ake_pipeline_track_f32")
             else:
@@ -360,9 +377,13 @@ class KeyEstimator:
 
     def _run(self, slot, audio, lengths):
         net, L = self.net, _lib.lib()
-        audio = audio.to(device=self.device, dtype=torch.float32)
-        if audio.stride(-1) != 1:
-            audio = audio.contiguous()
+        pcm = audio.dtype == torch.int16
+        if pcm:
+            audio, row_stride = pcm16_rows(audio, self.device)
+        else:
+            audio = audio.to(device=self.device, dtype=torch.float32)
+            if audio.stride(-1) != 1:
+                audio = audio.contiguous()
         B, n = audio.shape
         nbytes = L.ake_pipeline_workspace_bytes(self.plan.handle, net.handle, B, n)
         if slot["ws"] is None or slot["ws"].numel() < nbytes:
@@ -372,7 +393,16 @@ class KeyEstimator:
         tonic = torch.empty((B, 12), dtype=torch.float32, device=self.device)
         genre = torch.empty((B, 11), dtype=torch.float32, device=self.device) if net.genre else None
         with torch.cuda.device(self.device):
-            if lengths is None:
+            if pcm:
+                if lengths is not None:
+                    lengths = torch.as_tensor(lengths).to(device=self.device, dtype=torch.int64).contiguous()
+                    assert lengths.shape == (B,)
+                _lib.check(L.ake_pipeline_forward_pcm16_f32(self.plan.handle, net.handle, audio.data_ptr(), B, n, row_stride,
+                                                            lengths.data_ptr() if lengths is not None else None,
+                                                            key.data_ptr(), tonic.data_ptr(), genre.data_ptr() if genre is not None else None,
+                                                            ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
+                           "ake_pipeline_forward_pcm16_f32")
+            elif lengths is None:
                 _lib.check(L.ake_pipeline_forward_f32(self.plan.handle, net.handle, audio.data_ptr(), B, n, audio.stride(0),
                                                       key.data_ptr(), tonic.data_ptr(), genre.data_ptr() if genre is not None else None,
                                                       ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
@@ -390,9 +420,12 @@ class KeyEstimator:
         """frames=0: per-clip-hop CQT, then the net at (B, 1, n_bins, F) with no seq_length; one stream, no host synchronisation
         (W <= 592, or host lengths)."""
         net, L = self.net, _lib.lib()
-        audio = audio.to(device=self.device, dtype=torch.float32)
-        if audio.stride(-1) != 1:
-            audio = audio.contiguous()
+        if audio.dtype == torch.int16:                               # 16-bit PCM: logmag_hops reads it in place
+            audio = audio.to(device=self.device)
+        else:
+            audio = audio.to(device=self.device, dtype=torch.float32)
+            if audio.stride(-1) != 1:
+                audio = audio.contiguous()
         B, n = audio.shape
         W = self.window_size
         if W <= WHOLE_SONG_FRAMES:

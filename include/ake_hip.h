@@ -15,7 +15,8 @@
  *     they are safe to capture into a hipGraph;
  *   - one handle may be used from one stream at a time (the workspace is the
  *     per-call state; handles are immutable after creation / finalize);
- *   - all tensors are dense row-major float32, NCHW as in the reference.
+ *   - all tensors are dense row-major float32, NCHW as in the reference; the *_pcm16_f32 entries take their AUDIO as 16-bit PCM
+ *     (int16, sample s = s / 32768) and are float32 everywhere else.
  */
 #ifndef AKE_HIP_H
 #define AKE_HIP_H
@@ -114,6 +115,22 @@ int ake_cqt_frames_major_supported(const ake_cqt_plan* plan);
 int ake_cqt_logmag_frames_major_f32(const ake_cqt_plan* plan, const float* audio_dev, int batch, int64_t n_samples,
                                     int64_t audio_stride, float* out_dev, void* workspace, size_t workspace_bytes,
                                     ake_stream_t stream);
+
+/* 16-bit PCM audio (what decoders and WAV files deliver): sample s stands for float(s) * 2^-15, which is exact, so this entry gives the
+ * results of the four float entries above on the converted audio, bit for bit, without a float32 copy of the audio being written.  One
+ * entry for all four forms:
+ *   n_clip_dev   null: every row holds n_max samples; else row i holds n_clip_dev[i] <= n_max (int64, device)  -- the ragged form
+ *   hop_dev      null: the plan's hop; else per-clip hops (int32, device) as ake_cqt_logmag_hops_f32, same requirements on the plan
+ *   frames_major != 0: out_dev = [batch][out_frames][n_bins] as ake_cqt_logmag_frames_major_f32 (n_clip_dev and hop_dev null, and
+ *                out_frames == ake_cqt_num_frames); 0: out_dev = [batch][n_bins][out_frames], out_frames the padded frame count
+ * Engine 3 only: engines 1, 2 and 5 give AKE_ERR_UNSUPPORTED.  audio_dev must be 4-byte aligned and audio_stride (in samples) even,
+ * AKE_ERR_INVALID otherwise: the kernel loads whole 4-byte words.  Sample i < n_i of a row contributes its value and sample i >= n_i
+ * exactly zero, whatever lies there; the kernel may read up to the end of the 4-byte word that holds a row's last sample (one sample
+ * behind an odd n_i, inside the row's own stride), and no further.  Workspace: ake_cqt_workspace_bytes, or
+ * ake_cqt_workspace_bytes_hops with hop_dev -- the existing *_workspace_bytes functions serve every PCM entry unchanged. */
+int ake_cqt_logmag_pcm16_f32(const ake_cqt_plan* plan, const int16_t* audio_dev, int batch, int64_t n_max, int64_t audio_stride,
+                             const int64_t* n_clip_dev, const int32_t* hop_dev, float* out_dev, int64_t out_frames, int frames_major,
+                             void* workspace, size_t workspace_bytes, ake_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * PitchClassNet forward (inference: eval-mode BatchNorm folded into the convolutions).
@@ -330,6 +347,12 @@ int64_t ake_resampler_out_len(const ake_resampler* r, int64_t n_in);
 int ake_resample_f32(const ake_resampler* r, const float* in_dev, int batch, int channels, int64_t n_in, int64_t clip_stride,
                      int64_t channel_stride, int channel, const int64_t* n_in_clip_dev, float* out_dev, int64_t out_stride,
                      int64_t* n_out_clip_dev, ake_stream_t stream);
+/* The same from 16-bit PCM (sample s = s / 32768), read in place at in_dev[clip * clip_stride + c * channel_stride + i * sample_stride]
+ * (strides in samples): planar (B, C, n) storage has sample_stride 1, interleaved (B, n, C) storage -- what decoders hand over -- has
+ * channel_stride 1 and sample_stride C.  Output float32 mono, bit-identical to ake_resample_f32 on the converted planar audio. */
+int ake_resample_pcm16_f32(const ake_resampler* r, const int16_t* in_dev, int batch, int channels, int64_t n_in, int64_t clip_stride,
+                           int64_t channel_stride, int64_t sample_stride, int channel, const int64_t* n_in_clip_dev, float* out_dev,
+                           int64_t out_stride, int64_t* n_out_clip_dev, ake_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Whole hot path for a batch of equal-length clips: CQT then forward
@@ -346,6 +369,12 @@ int ake_pipeline_forward_ragged_f32(const ake_cqt_plan* plan, const ake_pcnet* n
                                     int64_t n_max, int64_t audio_stride, const int64_t* n_samples_dev, float* key_out_dev,
                                     float* tonic_out_dev, float* genre_out_dev, void* workspace, size_t workspace_bytes,
                                     ake_stream_t stream);
+/* Both of the above from 16-bit PCM audio (ake_cqt_logmag_pcm16_f32: alignment, engine 3): n_samples_dev null = equal-length clips of
+ * n_max samples.  The frames-major route is chosen exactly where ake_pipeline_forward_f32 chooses it; same outputs as the float entries on
+ * the converted audio, bit for bit.  Workspace: ake_pipeline_workspace_bytes(plan, net, batch, n_max). */
+int ake_pipeline_forward_pcm16_f32(const ake_cqt_plan* plan, const ake_pcnet* net, const int16_t* audio_dev, int batch, int64_t n_max,
+                                   int64_t audio_stride, const int64_t* n_samples_dev, float* key_out_dev, float* tonic_out_dev,
+                                   float* genre_out_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Key tracking over a long recording (not in the reference, whose --local nets return rows that are not time frames, models.py:806-807):
@@ -395,6 +424,12 @@ int ake_pipeline_track_ragged_f32(const ake_cqt_plan* plan, const ake_pcnet* net
                                   int64_t audio_stride, const int64_t* n_samples_dev, int window_frames, int stride_frames, float* key_out_dev,
                                   float* tonic_out_dev, float* genre_out_dev, int32_t* key_id_dev, int32_t* sig_dev, int32_t* tonic_id_dev,
                                   float* confidence_dev, int32_t* counts_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream);
+/* Both from 16-bit PCM recordings (ake_cqt_logmag_pcm16_f32: alignment, engine 3): lengths_dev null = ake_pipeline_track_f32, else
+ * ake_pipeline_track_ragged_f32; same route, same outputs.  Workspace: ake_pipeline_track_workspace_bytes. */
+int ake_pipeline_track_pcm16_f32(const ake_cqt_plan* plan, const ake_pcnet* net, const int16_t* audio_dev, int recordings, int64_t n_max,
+                                 int64_t audio_stride, const int64_t* lengths_dev, int window_frames, int stride_frames, float* key_out_dev,
+                                 float* tonic_out_dev, float* genre_out_dev, int32_t* key_id_dev, int32_t* sig_dev, int32_t* tonic_id_dev,
+                                 float* confidence_dev, int32_t* counts_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * A smooth key track: per-window log-scores of the 24 keys from the two heads, then a first-order Viterbi decode over them.  Both run on
