@@ -99,6 +99,10 @@ SYMBOLS = {
     "ake_key_posteriors_workspace_bytes": (_SZ, [_I, _I]),
     "ake_key_posteriors_chunk_windows": (_I, []),
     "ake_key_posteriors_f32": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "ake_track_score_i32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "ake_synth_partials_workspace_bytes": (_SZ, [_I]),
+    "ake_synth_batch_partials": (_I, []),
+    "ake_synth_partials_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _I64, _I64, C.c_float, _P, C.c_float, _P, _P, _SZ, _P]),
     "ake_resampler_create": (_I, [_I, _I, C.POINTER(_P)]),
     "ake_resampler_destroy": (None, [_P]),
     "ake_resampler_out_len": (_I64, [_P, _I64]),

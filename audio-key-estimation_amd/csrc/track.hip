@@ -21,6 +21,8 @@
 // viterbi_keys_kernel (the most likely path through them); further down, semantics in include/ake_hip.h.  Posterior key probabilities
 // are a forward-backward pass over the same emissions: key_forward_backward_kernel (the two serial chains, side by side) and
 // key_posteriors_kernel (everything per window), below the Viterbi kernel.
+//
+// A track is scored against key annotations by track_score_kernel (one launch, integers only), below the posterior kernels.
 #include "common.h"
 
 #include <algorithm>
@@ -591,6 +593,91 @@ __global__ __launch_bounds__(192) void key_xi_reduce_kernel(const float* __restr
     }
 }
 
+// ---- a track against key annotations (semantics: include/ake_hip.h; host restatement: metrics.window_truth / metrics.track_score) ----
+struct ScoreArgs {
+    const int* pred;           // [recordings][windows], -1..23
+    const int* counts;         // nullable
+    const long long* seg_start;   // [recordings][max_segments], ascending below seg_count
+    const int* seg_key;        // [recordings][max_segments], -1 = unlabelled
+    const int* seg_count;      // [recordings]
+    int* truth;                // [recordings][windows], nullable
+    int* category;             // [recordings][windows], nullable
+    int* tally;                // [recordings][2][6]
+    int* changes;              // [recordings][2]
+    int windows, max_segments;
+    long long hop;
+    int window_frames, stride_frames;
+};
+
+// the relation of a decoded key to the true one: 0 correct, 1 fifth, 2 relative, 3 parallel, 4 other, 5 undecoded (truth in 0..23)
+__device__ __forceinline__ int key_relation(int pred, int truth) {
+    if (pred < 0) return 5;
+    if (pred == truth) return 0;
+    if (pred >= kKeys) return 4;
+    const int pm = pred >= 12, tm = truth >= 12, pt = pred - 12 * pm, tt = truth - 12 * tm;
+    if (pm == tm) {
+        const int d = (pt - tt + 12) % 12;
+        return d == 5 || d == 7 ? 1 : 4;
+    }
+    const int pmaj = pm ? pt : (pt + 3) % 12, tmaj = tm ? tt : (tt + 3) % 12;      // the major tonic of the key's scale
+    return pmaj == tmaj ? 2 : pt == tt ? 3 : 4;
+}
+
+// truth and purity of window w: the key of the last segment that starts at or before the centre sample; pure when every segment that
+// overlaps the window's samples [lo, hi] carries that key.  A linear walk over the recording's segments (a handful per recording).
+__device__ __forceinline__ int window_truth(const ScoreArgs& a, const long long* start, const int* key, int ns, int w, bool* pure) {
+    const long long f0 = static_cast<long long>(w) * a.stride_frames;
+    const long long lo = f0 * a.hop, hi = (f0 + a.window_frames - 1) * a.hop, centre = (2 * f0 + a.window_frames - 1) * a.hop / 2;
+    int truth = -1;
+    for (int s = 0; s < ns; ++s) truth = start[s] <= centre ? key[s] : truth;
+    bool all = truth >= 0;
+    for (int s = 0; s < ns; ++s) {
+        const bool overlaps = start[s] <= hi && (s + 1 >= ns || start[s + 1] > lo);
+        all = all && (!overlaps || key[s] == truth);
+    }
+    *pure = all;
+    return truth;
+}
+
+// One block per recording, a thread per window in turn.  Integers only: the tallies meet in LDS through integer atomics, whose result
+// does not depend on the order, so every run gives the same bits.
+__global__ __launch_bounds__(256) void track_score_kernel(ScoreArgs a) {
+    __shared__ int s_tally[14];                                          // [2][6], then the two change counts
+    const int r = blockIdx.x, W = a.windows;
+    if (threadIdx.x < 14) s_tally[threadIdx.x] = 0;
+    __syncthreads();
+    int n = a.counts ? a.counts[r] : W;
+    n = n < 0 ? 0 : n > W ? W : n;
+    int ns = a.seg_count[r];
+    ns = ns < 0 ? 0 : ns > a.max_segments ? a.max_segments : ns;
+    const long long* const start = a.seg_start + static_cast<size_t>(r) * a.max_segments;
+    const int* const key = a.seg_key + static_cast<size_t>(r) * a.max_segments;
+    const int* const pred = a.pred + static_cast<size_t>(r) * W;
+    for (int w = threadIdx.x; w < W; w += blockDim.x) {
+        int truth = -1, cat = -1;
+        if (w < n && ns > 0) {
+            bool pure;
+            truth = window_truth(a, start, key, ns, w, &pure);
+            const int p = pred[w];
+            if (truth >= 0) {
+                cat = key_relation(p, truth);
+                atomicAdd(&s_tally[cat], 1);
+                if (pure) atomicAdd(&s_tally[6 + cat], 1);
+            }
+            if (w > 0) {
+                bool unused;
+                if (p != pred[w - 1]) atomicAdd(&s_tally[12], 1);
+                if (truth != window_truth(a, start, key, ns, w - 1, &unused)) atomicAdd(&s_tally[13], 1);
+            }
+        }
+        if (a.truth) a.truth[static_cast<size_t>(r) * W + w] = truth;
+        if (a.category) a.category[static_cast<size_t>(r) * W + w] = cat;
+    }
+    __syncthreads();
+    if (threadIdx.x < 12) a.tally[r * 12 + threadIdx.x] = s_tally[threadIdx.x];
+    else if (threadIdx.x < 14) a.changes[r * 2 + threadIdx.x - 12] = s_tally[threadIdx.x];
+}
+
 struct PostCarve {
     float* a;
     float* b;
@@ -873,6 +960,26 @@ int ake_pipeline_track_pcm16_f32(const ake_cqt_plan* plan, const ake_pcnet* net,
                                  float* confidence_dev, int32_t* counts_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream) {
     return track_impl(plan, net, nullptr, recordings, n_max, audio_stride, lengths_dev, window_frames, stride_frames, key_out_dev, tonic_out_dev,
                       genre_out_dev, key_id_dev, sig_dev, tonic_id_dev, confidence_dev, counts_dev, workspace, workspace_bytes, stream, audio_dev);
+}
+
+int ake_track_score_i32(const int32_t* pred_dev, const int32_t* counts_dev, const int64_t* seg_start_dev, const int32_t* seg_key_dev,
+                        const int32_t* seg_count_dev, int recordings, int windows, int max_segments, int hop, int window_frames,
+                        int stride_frames, int32_t* truth_dev, int32_t* category_dev, int32_t* tally_dev, int32_t* changes_dev,
+                        ake_stream_t stream) {
+    AKE_REQUIRE(pred_dev && seg_start_dev && seg_key_dev && seg_count_dev && tally_dev && changes_dev, AKE_ERR_INVALID, "track_score: null argument");
+    AKE_REQUIRE(recordings > 0 && windows > 0 && max_segments > 0 && static_cast<long long>(recordings) * windows <= (1ll << 30), AKE_ERR_INVALID,
+                "track_score: bad shape (%d recordings, %d windows, %d segments)", recordings, windows, max_segments);
+    AKE_REQUIRE(hop > 0 && window_frames > 0 && stride_frames > 0, AKE_ERR_INVALID, "track_score: bad geometry (hop %d, window %d, stride %d)", hop,
+                window_frames, stride_frames);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ScoreArgs a{pred_dev, counts_dev, reinterpret_cast<const long long*>(seg_start_dev), seg_key_dev, seg_count_dev, truth_dev, category_dev,
+                tally_dev, changes_dev, windows, max_segments, hop, window_frames, stride_frames};
+    {
+        ake::ProfScope ps("track_score_kernel", s);
+        hipLaunchKernelGGL(track_score_kernel, dim3(recordings), dim3(256), 0, s, a);
+    }
+    AKE_HIP_CHECK(hipGetLastError());
+    return AKE_OK;
 }
 
 }  // extern "C"

@@ -369,3 +369,112 @@ def fit_key_transition(emissions, counts=None, init=None, iterations=10, tied=Tr
         scores.append(score)
         log_trans = transition_m_step(xi_total, init, tied=tied, pseudo_count=pseudo_count)
     return log_trans, scores
+
+
+# ---- a key track against key annotations (ake_track_score_i32) and a transition counted from labels ----
+
+# category codes of track_score: the relations key_transition_log uses, and their MIREX weights
+SCORE_CATEGORIES = ("correct", "fifth", "relative", "parallel", "other", "undecoded")
+SCORE_WEIGHTS = (1.0, 0.5, 0.3, 0.2, 0.0, 0.0)
+_I64_MAX = 2 ** 63 - 1
+
+
+def _window_spans(W, hop, window_frames, stride_frames, device):
+    """(lo, hi, centre) int64 (W,): the first, last and centre sample of every window (frame f is centred on sample f * hop)."""
+    f0 = torch.arange(W, device=device, dtype=torch.int64) * int(stride_frames)
+    hop, wf = int(hop), int(window_frames)
+    return f0 * hop, (f0 + wf - 1) * hop, torch.div((2 * f0 + wf - 1) * hop, 2, rounding_mode="floor")
+
+
+def window_truth(seg_start, seg_key, seg_count, windows, hop, window_frames, stride_frames, counts=None):
+    """The annotated key of every window -> ``(truth, pure)``: int32 (R, W) and bool (R, W), on the annotations' device.
+
+    ``seg_start`` int64 (R, S) in samples, ``seg_key`` int32 (R, S) (-1 = unlabelled), ``seg_count`` (R,): the arrays of
+    ``KeyAnnotations``.  Window w covers the samples ``w * stride_frames * hop .. (w * stride_frames + window_frames - 1) * hop``
+    inclusive; its centre sample is ``(2 * w * stride_frames + window_frames - 1) * hop // 2`` (``KeyTrack.times`` in samples).
+    ``truth`` is the key of the last segment that starts at or before the centre sample: -1 for windows at or behind ``counts[r]``, in an
+    unlabelled segment, or in a recording without segments.  ``pure``: the truth is a key and every segment that overlaps the window's
+    samples carries it.  Integer torch ops, exact: the restatement of ``ake_track_score_i32``'s geometry."""
+    dev = seg_start.device
+    R, S = seg_start.shape
+    W = int(windows)
+    start = seg_start.to(torch.int64)
+    key = seg_key.to(device=dev, dtype=torch.int64)
+    ns = torch.as_tensor(seg_count, device=dev).to(torch.int64).reshape(R).clamp(0, S)
+    lo, hi, centre = _window_spans(W, hop, window_frames, stride_frames, dev)
+    s_idx = torch.arange(S, device=dev)
+    valid = s_idx[None, :] < ns[:, None]                                                            # (R, S)
+    holds = valid[:, None, :] & (start[:, None, :] <= centre[None, :, None])                        # (R, W, S)
+    last = (holds * (s_idx + 1)[None, None, :]).amax(dim=2) - 1 if S > 0 else torch.full((R, W), -1, device=dev, dtype=torch.int64)
+    truth = torch.where(last >= 0, key.gather(1, last.clamp_min(0)), torch.full_like(last, -1))
+    n = torch.full((R,), W, device=dev, dtype=torch.int64) if counts is None else \
+        torch.as_tensor(counts, device=dev).to(torch.int64).reshape(R).clamp(0, W)
+    truth = torch.where(torch.arange(W, device=dev)[None, :] < n[:, None], truth, torch.full_like(truth, -1))
+    nxt = torch.cat([start[:, 1:], torch.full((R, 1), _I64_MAX, device=dev, dtype=torch.int64)], dim=1)
+    nxt = torch.where(s_idx[None, :] + 1 < ns[:, None], nxt, torch.full_like(nxt, _I64_MAX))         # the last segment has no end
+    overlaps = valid[:, None, :] & (start[:, None, :] <= hi[None, :, None]) & (nxt[:, None, :] > lo[None, :, None])
+    pure = (truth >= 0) & (~overlaps | (key[:, None, :] == truth[:, :, None])).all(dim=2)
+    return truth.to(torch.int32), pure
+
+
+def key_category(pred, truth):
+    """Category 0..5 (``SCORE_CATEGORIES``) of decoded keys ``pred`` (-1..23) against true keys ``truth`` (0..23), -1 where ``truth``
+    is -1; integer tensors of one shape -> int32."""
+    p, t = pred.to(torch.int64), truth.to(torch.int64)
+    tc = t.clamp(0, 23)
+    pc = p.clamp(0, 23)
+    maj = torch.tensor(KEY_MAJOR_TONIC, device=p.device, dtype=torch.int64)
+    same_mode = (pc >= 12) == (tc >= 12)
+    d = (pc % 12 - tc % 12) % 12
+    cat = torch.full_like(p, 4)
+    cat = torch.where(~same_mode & (pc % 12 == tc % 12), torch.full_like(p, 3), cat)
+    cat = torch.where(~same_mode & (maj[pc] == maj[tc]), torch.full_like(p, 2), cat)
+    cat = torch.where(same_mode & ((d == 5) | (d == 7)), torch.full_like(p, 1), cat)
+    cat = torch.where(p > 23, torch.full_like(p, 4), cat)
+    cat = torch.where(p == t, torch.zeros_like(p), cat)
+    cat = torch.where(p < 0, torch.full_like(p, 5), cat)
+    return torch.where(t < 0, torch.full_like(p, -1), cat).to(torch.int32)
+
+
+def track_score(pred, counts, seg_start, seg_key, seg_count, hop, window_frames, stride_frames):
+    """Score decoded keys against annotations -> ``(truth, category, tally, changes)``: ``ake_track_score_i32`` in integer torch ops,
+    exact, on the device of ``pred``.
+
+    ``pred`` int32 (R, W), -1..23 (``KeyTrack.key_id`` or ``smooth_key_id``); ``counts`` (R,) or None.  ``truth`` as ``window_truth``;
+    ``category`` int32 (R, W): -1 where the truth is -1, else 0 correct, 1 fifth, 2 relative, 3 parallel, 4 other, 5 undecoded
+    (``SCORE_CATEGORIES``, weighted by ``SCORE_WEIGHTS``).  ``tally`` int32 (R, 2, 6): the category counts over all scored windows and
+    over the pure ones.  ``changes`` int32 (R, 2): the number of w in 1..count-1 with ``pred[w] != pred[w-1]``, and the same for
+    ``truth``.  A recording with count 0 or no segments gets zeros in both."""
+    dev = pred.device
+    R, W = pred.shape
+    seg_start, seg_key = seg_start.to(dev), seg_key.to(dev)
+    ns = torch.as_tensor(seg_count, device=dev).to(torch.int64).reshape(R).clamp(0, seg_start.shape[1])
+    n = torch.full((R,), W, device=dev, dtype=torch.int64) if counts is None else \
+        torch.as_tensor(counts, device=dev).to(torch.int64).reshape(R).clamp(0, W)
+    truth, pure = window_truth(seg_start, seg_key, ns, W, hop, window_frames, stride_frames, counts=n)
+    category = key_category(pred, truth)
+    onehot = category[:, :, None] == torch.arange(6, device=dev, dtype=torch.int32)[None, None, :]     # (R, W, 6); -1 matches none
+    tally = torch.stack([onehot.sum(dim=1), (onehot & pure[:, :, None]).sum(dim=1)], dim=1).to(torch.int32)
+    live = (torch.arange(1, W, device=dev)[None, :] < n[:, None]) & (ns > 0)[:, None]                  # (R, W - 1): w = 1..count-1
+    changes = torch.stack([((pred[:, 1:] != pred[:, :-1]) & live).sum(dim=1), ((truth[:, 1:] != truth[:, :-1]) & live).sum(dim=1)],
+                          dim=1).to(torch.int32)
+    return truth, category, tally, changes
+
+
+def transition_from_labels(truth, counts=None, tied=True, pseudo_count=1.0, init=None):
+    """A transition matrix counted from key labels -> float64 (24, 24) log matrix that ``track(transition=...)`` accepts.
+
+    ``truth`` integer (R, W) or (W,) labels per window (``window_truth`` / ``TrackScore.truth``; -1 = none), ``counts`` (R,) or None.
+    Every pair of consecutive windows below the count with both labels >= 0 is one move (i -> j); the (24, 24) count matrix goes through
+    ``transition_m_step`` as expected counts would: ``pseudo_count`` pseudo-moves per row spread as ``init`` (default
+    ``key_transition_log(stay=0.9)``), and ``tied`` averages over the transposition classes."""
+    t = torch.as_tensor(truth).detach().to(device="cpu", dtype=torch.int64)
+    if t.dim() == 1:
+        t = t[None]
+    R, W = t.shape
+    n = torch.full((R,), W, dtype=torch.int64) if counts is None else torch.as_tensor(counts).detach().to(device="cpu", dtype=torch.int64).reshape(R).clamp(0, W)
+    a, b = t[:, :-1], t[:, 1:]
+    ok = (torch.arange(1, W)[None, :] < n[:, None]) & (a >= 0) & (b >= 0)
+    C = torch.zeros(576, dtype=torch.float64).index_add_(0, (a * 24 + b)[ok], torch.ones(int(ok.sum()), dtype=torch.float64)).reshape(24, 24)
+    init = key_transition_log(stay=0.9) if init is None else init
+    return transition_m_step(C, init, tied=tied, pseudo_count=pseudo_count)

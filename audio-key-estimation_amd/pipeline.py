@@ -38,6 +38,88 @@ def track_counts(total_frames, window_frames: int, stride_frames: int):
 
 
 @dataclass
+class KeyAnnotations:
+    """Key labels of R recordings over time, on the device: what ``KeyTrack.score`` scores a track against.
+
+    ``seg_start`` int64 (R, S): the segments' first samples, ascending, segment 0 at sample 0; ``seg_key`` int32 (R, S): their keys in
+    ``metrics.KEY_NAMES`` order, -1 for an unlabelled stretch; ``seg_count`` int32 (R,).  Behind a recording's count the starts hold
+    INT64_MAX and the keys -1.  A segment lasts until the next one starts, the last one to the end of the recording."""
+    seg_start: torch.Tensor
+    seg_key: torch.Tensor
+    seg_count: torch.Tensor
+    sample_rate: int = 0
+
+    @classmethod
+    def from_segments(cls, segments, sample_rate, device="cpu"):
+        """``segments``: for every recording a list of ``(start_seconds, key)``, ``key`` an id 0..23, -1 (unlabelled) or a name of
+        ``metrics.KEY_NAMES`` ("A minor").  Starts become samples as ``round(start_seconds * sample_rate)``.  ``ValueError`` unless
+        segment 0 starts at 0 and the starts are strictly ascending (in samples); a recording may have no segments at all."""
+        rows = []
+        for r, segs in enumerate(segments):
+            starts, keys = [], []
+            for start_s, key in segs:
+                if isinstance(key, str):
+                    if key not in metrics.KEY_NAMES:
+                        raise ValueError(f"KeyAnnotations: recording {r}: unknown key name {key!r} (metrics.KEY_NAMES: 'C minor' .. 'B major')")
+                    key = metrics.KEY_NAMES.index(key)
+                key = int(key)
+                if not -1 <= key < 24:
+                    raise ValueError(f"KeyAnnotations: recording {r}: key id {key} is outside -1..23")
+                starts.append(int(round(float(start_s) * sample_rate)))
+                keys.append(key)
+            if starts and starts[0] != 0:
+                raise ValueError(f"KeyAnnotations: recording {r}: segment 0 must start at 0, not at sample {starts[0]}")
+            if any(b <= a for a, b in zip(starts, starts[1:])):
+                raise ValueError(f"KeyAnnotations: recording {r}: segment starts must be strictly ascending")
+            rows.append((starts, keys))
+        R, S = len(rows), max([len(st) for st, _ in rows] + [1])
+        seg_start = torch.full((R, S), metrics._I64_MAX, dtype=torch.int64)
+        seg_key = torch.full((R, S), -1, dtype=torch.int32)
+        for r, (starts, keys) in enumerate(rows):
+            seg_start[r, :len(starts)] = torch.tensor(starts, dtype=torch.int64)
+            seg_key[r, :len(keys)] = torch.tensor(keys, dtype=torch.int32)
+        seg_count = torch.tensor([len(st) for st, _ in rows], dtype=torch.int32)
+        return cls(seg_start.to(device), seg_key.to(device), seg_count.to(device), int(sample_rate))
+
+
+@dataclass
+class TrackScore:
+    """A track against annotations (``KeyTrack.score``); the four tensors live on the device.
+
+    ``truth`` int32 (R, W): the annotated key of every window (-1: none); ``category`` int32 (R, W): -1 where the truth is -1, else
+    0 correct, 1 fifth, 2 relative, 3 parallel, 4 other, 5 undecoded (``metrics.SCORE_CATEGORIES``); ``tally`` int32 (R, 2, 6): the
+    category counts over all scored windows and over the pure ones (every annotated segment under the window carries one key);
+    ``changes`` int32 (R, 2): how often the track's key changes from one window to the next, and how often the truth does."""
+    truth: torch.Tensor
+    category: torch.Tensor
+    tally: torch.Tensor
+    changes: torch.Tensor
+
+    def _tally(self, pure):
+        return self.tally[:, 1 if pure else 0].cpu().to(torch.float64)                          # (R, 6)
+
+    def fractions(self, pure: bool = False):
+        """Share of every category among the scored windows -> ``(per_recording (R, 6), pooled (6,))`` float64 on the host; NaN where
+        nothing was scored.  ``pure``: over the pure windows only."""
+        t = self._tally(pure)
+        return t / t.sum(dim=1, keepdim=True), t.sum(dim=0) / t.sum()
+
+    def weighted(self, pure: bool = False):
+        """The MIREX-weighted score (correct 1, fifth 0.5, relative 0.3, parallel 0.2; ``metrics.SCORE_WEIGHTS``) ->
+        ``(per_recording (R,), pooled float)``."""
+        per, pooled = self.fractions(pure)
+        w = torch.tensor(metrics.SCORE_WEIGHTS, dtype=torch.float64)
+        return per @ w, float(pooled @ w)
+
+    def flicker(self):
+        """Key changes of the track per key change of the truth -> ``(per_recording (R,), pooled float)``; 1 is a track that moves as
+        often as the key does (NaN or inf where the truth never moves)."""
+        c = self.changes.cpu().to(torch.float64)
+        tot = c.sum(dim=0)
+        return c[:, 0] / c[:, 1], float(tot[0] / tot[1])
+
+
+@dataclass
 class KeyTrack:
     """The key of R recordings over time (``KeyEstimator.track``), W windows each; everything but ``times`` lives on the device.
 
@@ -54,7 +136,10 @@ class KeyTrack:
     (``metrics.key_posteriors``): ``posteriors`` (R, W, 24), the posterior probability of every key at every window (rows below the
     count sum to 1, rows behind it are zeros); ``smooth_confidence`` (R, W), the posterior of the key ``smooth_key_id`` names (0 behind
     the count); ``log_likelihood`` (R,), the recording's log-score under the transition (the emissions are log-scores, not normalised
-    likelihoods: it compares transitions on the same recording and means nothing else).  All three are None otherwise."""
+    likelihoods: it compares transitions on the same recording and means nothing else).  All three are None otherwise.
+
+    ``hop``, ``window_frames``, ``stride_frames`` and ``sample_rate`` are the track's geometry in samples and frames (0 on a track
+    built by hand): ``score`` needs them to place the windows on the annotations."""
     key: torch.Tensor
     tonic: torch.Tensor
     genre: torch.Tensor | None
@@ -71,6 +156,10 @@ class KeyTrack:
     posteriors: torch.Tensor | None = None
     smooth_confidence: torch.Tensor | None = None
     log_likelihood: torch.Tensor | None = None
+    hop: int = 0
+    window_frames: int = 0
+    stride_frames: int = 0
+    sample_rate: int = 0
 
     def _tensors(self):
         """Every device tensor of the track; the two of a smooth track and the three of its posteriors only when it has them (a plain
@@ -112,6 +201,39 @@ class KeyTrack:
             out.append(seg + (sum(conf[a:b + 1]) / (b + 1 - a),) if confidence else seg)
             a = b + 1
         return out
+
+
+    def score(self, annotations: KeyAnnotations, smoothed: bool | None = None) -> TrackScore:
+        """Score the track against ``annotations`` on the device (``ake_track_score_i32``, one launch; ``metrics.track_score`` is its
+        restatement) -> ``TrackScore``.  ``smoothed`` picks the source as in ``segments``: True ``smooth_key_id`` (``ValueError`` if the
+        track has none), False ``key_id``, None the smoothed path when there is one.  The annotations are in samples at the track's
+        sample rate.  ``ValueError`` on a track without its geometry (``hop``, ``window_frames``, ``stride_frames``)."""
+        if smoothed and self.smooth_key_id is None:
+            raise ValueError("score(smoothed=True): this track has no smoothed path; make it with track(..., smooth=True)")
+        if self.hop <= 0 or self.window_frames <= 0 or self.stride_frames <= 0:
+            raise ValueError("score: this track does not know its geometry (hop, window_frames, stride_frames); KeyEstimator.track fills it in")
+        if annotations.sample_rate and self.sample_rate and annotations.sample_rate != self.sample_rate:
+            raise ValueError(f"score: the annotations are in samples at {annotations.sample_rate} Hz, the track at {self.sample_rate} Hz")
+        pred = self.smooth_key_id if (smoothed or (smoothed is None and self.smooth_key_id is not None)) else self.key_id
+        dev = pred.device
+        R, W = pred.shape
+        if annotations.seg_start.shape[0] != R:
+            raise ValueError(f"score: the track has {R} recordings, the annotations {annotations.seg_start.shape[0]}")
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        truth, category, tally, changes = i32(R, W), i32(R, W), i32(R, 2, 6), i32(R, 2)
+        if W == 0:
+            tally.zero_(); changes.zero_()
+            return TrackScore(truth, category, tally, changes)
+        start = annotations.seg_start.to(device=dev, dtype=torch.int64).contiguous()
+        key = annotations.seg_key.to(device=dev, dtype=torch.int32).contiguous()
+        count = annotations.seg_count.to(device=dev, dtype=torch.int32).contiguous()
+        pred, counts = pred.contiguous(), self.counts.to(torch.int32).contiguous()
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().ake_track_score_i32(pred.data_ptr(), counts.data_ptr(), start.data_ptr(), key.data_ptr(), count.data_ptr(), R, W,
+                                                      start.shape[1], self.hop, self.window_frames, self.stride_frames, truth.data_ptr(),
+                                                      category.data_ptr(), tally.data_ptr(), changes.data_ptr(),
+                                                      torch.cuda.current_stream().cuda_stream), "ake_track_score_i32")
+        return TrackScore(truth, category, tally, changes)
 
 
 class KeyEstimator:
@@ -228,14 +350,13 @@ class KeyEstimator:
         to -1.  ``transition``: a (24, 24) log matrix, from key i (row) to key j, all finite (write a forbidden transition as a large
         negative number).  Default: ``metrics.key_transition_log(stay=exp(-stride / mean_key_seconds))`` with ``stride`` the track's
         actual stride in seconds, so the amount of smoothing does not depend on the stride chosen.  The default of 60 s is a starting
-        value and nothing more: no recordings labelled with modulations exist here, so no accuracy claim is made for it.  Nothing else
-        of the track changes with ``smooth``.
+        value; how it and its neighbours score against ground truth on synthesised modulating recordings is in
+        ``profiles/track_accuracy.md`` (``KeyTrack.score``).  Nothing else of the track changes with ``smooth``.
 
         ``posteriors=True`` (with ``smooth=True``; a ``ValueError`` without it) appends the forward-backward pass over the same
         emissions and transition, two more launches on the same stream, and fills ``KeyTrack.posteriors``, ``smooth_confidence`` and
         ``log_likelihood`` (``metrics.key_posteriors``).  Nothing else of the track changes with it.  ``ake_amd.fit_key_transition``
-        fits a ``transition`` to smooth tracks' own emissions; the same caveat holds for it: no labelled modulations, no accuracy
-        claim."""
+        fits a ``transition`` to smooth tracks' own emissions; the same table scores it."""
         if posteriors and not smooth:
             raise ValueError("track(posteriors=True) needs smooth=True: the posteriors belong to the smoothed track's emissions and transition")
         if self.frames <= 0:
@@ -295,6 +416,7 @@ class KeyEstimator:
         key_id, sig, tonic_id, conf, counts = i32(R, W), i32(R, W), i32(R, W), f32(R, W), i32(R)
         times = (torch.arange(W, dtype=torch.float64) * sf + (wf - 1) / 2) * hop / self.sample_rate
         track = KeyTrack(key, tonic, genre, key_id, sig, tonic_id, conf, counts, times, wf * hop / self.sample_rate, sf * hop / self.sample_rate)
+        track.hop, track.window_frames, track.stride_frames, track.sample_rate = int(hop), int(wf), int(sf), self.sample_rate
         if smoothing is not None:
             track.emissions, track.smooth_key_id = f32(R, W, 24), i32(R, W)
             if smoothing[2]:
@@ -481,7 +603,7 @@ def fit_key_transition(tracks, init=None, iterations=10, tied=True, pseudo_count
     whose loop this is: the E-step (``ake_key_posteriors_f32``) runs on every track's device emissions and counts, the M-step on its 576
     numbers is ordinary torch (``metrics.transition_m_step``).  ``tracks``: one ``KeyTrack`` of ``track(smooth=True)`` or a list of
     them.  ``log_trans`` (float64, on the host) goes straight into ``track(transition=...)``.  It is the matrix under which these
-    emissions score highest; no labelled modulations exist here, so no accuracy claim is made for it."""
+    emissions score highest; ``profiles/track_accuracy.md`` scores tracks under it against ground truth on synthesised recordings."""
     tracks = list(tracks) if isinstance(tracks, (list, tuple)) else [tracks]
     if not tracks or any(not isinstance(t, KeyTrack) or t.emissions is None for t in tracks):
         raise ValueError("fit_key_transition: needs smooth tracks (KeyTrack.emissions); make them with track(..., smooth=True)")

@@ -489,6 +489,64 @@ int ake_key_posteriors_f32(const float* emis_dev, int recordings, int windows, c
                            float* path_post_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A track against key annotations, one launch, integers only: two runs on the same inputs are bit-identical.
+ * ---------------------------------------------------------------------------------------- */
+/* pred_dev (int32 [recordings][windows], -1..23: key_id or the Viterbi path) against the annotations of every recording:
+ * seg_start_dev (int64 [recordings][max_segments], in samples), seg_key_dev (int32, 0..23, -1 = an unlabelled stretch) and seg_count_dev
+ * (int32 [recordings], clamped to 0..max_segments).  Segment s < count runs from its start to the next segment's start, the last one without
+ * end; the starts ascend and segment 0 starts at 0 (entries at or behind the count are not read).  counts_dev (int32 [recordings], NULL =
+ * every recording has `windows`), clamped to 0..windows.  Frame f is centred on sample f * hop, so with f0 = w * stride_frames window w
+ * covers the samples lo = f0 * hop .. hi = (f0 + window_frames - 1) * hop inclusive, and its centre sample is
+ * (2 * f0 + window_frames - 1) * hop / 2 (integer division), in int64.
+ *   truth[r][w]    the key of the last segment that starts at or before the centre sample; -1 for w >= count, for an unlabelled segment
+ *                  and for a recording without segments
+ *   pure           truth >= 0 and every segment that overlaps lo..hi (start <= hi and next start > lo) carries truth's key
+ *   category[r][w] -1 where truth is -1, else: 0 correct (pred == truth), 1 fifth (same mode, tonic difference mod 12 in {5, 7}),
+ *                  2 relative (other mode, the same scale), 3 parallel (other mode, the same tonic), 4 other (any other decoded key),
+ *                  5 undecoded (pred < 0): the relations and MIREX weights 1 / 0.5 / 0.3 / 0.2 / 0 / 0 of the transition matrix
+ *   tally[r][0][c] windows of category c; tally[r][1][c] the pure ones among them
+ *   changes[r][0]  the number of w in 1..count-1 with pred[w] != pred[w-1];  changes[r][1] the same for truth
+ * truth_dev and category_dev (int32 [recordings][windows]) are nullable; tally_dev is int32 [recordings][2][6], changes_dev int32
+ * [recordings][2].  A recording with count 0 or seg_count 0 gets zeros in both (and -1 in truth and category).
+ * One block per recording, the counts meet through integer LDS atomics (order-independent). */
+int ake_track_score_i32(const int32_t* pred_dev, const int32_t* counts_dev, const int64_t* seg_start_dev, const int32_t* seg_key_dev,
+                        const int32_t* seg_count_dev, int recordings, int windows, int max_segments, int hop, int window_frames,
+                        int stride_frames, int32_t* truth_dev, int32_t* category_dev, int32_t* tally_dev, int32_t* changes_dev,
+                        ake_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Additive synthesiser: recordings from lists of enveloped sinusoidal partials plus Gaussian noise, peak-normalised, float32, ragged.
+ * It makes test audio whose key changes are known (synthetic.make_modulating_batch_device); host model: synthetic.synth_partials_reference.
+ * ---------------------------------------------------------------------------------------- */
+/* Structure of arrays, all on the device.  offsets_dev (int32 [recordings + 1]): recording r owns the partials offsets[r] .. offsets[r+1]
+ * - 1 (an empty range is legal).  Per partial: cps_dev (float64, cycles per sample = f / sample rate, 0 < cps < 0.5), phase_dev (float64,
+ * turns, in [0, 1)), amp_dev (float32), start_dev / end_dev (int64): the partial sounds on the samples start <= t < end, which may be
+ * negative or reach beyond the recording (it is clipped).  fade >= 0 samples, one value per call.  n_dev (int64 [recordings]) samples of
+ * every row, at most n_max; stride (floats between rows) a multiple of 4 and >= n_max; out_dev 16-byte aligned.  For t < n_r:
+ *   y[t]  = sum over the partials p of r with start_p <= t < end_p of  amp_p * g_in * g_out * sin(2 pi frac(cps_p * t + phase_p))
+ *           + noise_sigma * z_r[t]
+ *   g_in  = 1 if fade == 0 or t - start >= fade,        else 0.5 - 0.5 cos(pi (t - start + 0.5) / fade)
+ *   g_out = 1 if fade == 0 or m = end - 1 - t >= fade,  else 0.5 - 0.5 cos(pi (m + 0.5) / fade)
+ * so a partial that ends at E and one that starts at E - fade cross-fade with envelopes that sum to 1.  Samples n_r <= t < stride are
+ * written as 0.  cps * t + phase is one float64 fma and its fraction (minus its floor) is taken in float64; only the fraction is rounded
+ * to float32, so the phase error does not grow with t.  Sine, cosine and logarithm are the accurate library forms.
+ * Noise: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85), key (seed_dev[r] low 32 bits, high 32
+ * bits), counter (b low, b high, r, 0) with b = t >> 2.  Its words x_0..x_3 give u_k = ((x_k >> 9) + 0.5) * 2^-23 (exact, never 0) and the
+ * samples 4b .. 4b+3 get R(u_0) cos(2 pi u_1), R(u_0) sin(2 pi u_1), R(u_2) cos(2 pi u_3), R(u_2) sin(2 pi u_3), R(u) = sqrt(-2 ln u).
+ * With noise_sigma == 0 nothing is drawn and seed_dev may be NULL.
+ * peak > 0: a second pass scales every recording so that max |y| over t < n_r is peak (an all-zero recording stays zero); peak == 0: no
+ * normalisation, and no workspace is needed.  The maximum is an integer atomicMax on the float's bit pattern, one per block, so two runs
+ * are bit-identical; the workspace (ake_synth_partials_workspace_bytes) holds it.
+ * A thread makes 4 consecutive samples (one 16-byte store), a block 1024 samples of one recording: it compacts the partials that
+ * overlap its tile into LDS, ake_synth_batch_partials() candidates at a time and in their own order, so any number of partials runs. */
+size_t ake_synth_partials_workspace_bytes(int recordings);
+int ake_synth_batch_partials(void);
+int ake_synth_partials_f32(const int32_t* offsets_dev, const double* cps_dev, const double* phase_dev, const float* amp_dev,
+                           const int64_t* start_dev, const int64_t* end_dev, int fade, int recordings, const int64_t* n_dev, int64_t n_max,
+                           int64_t stride, float noise_sigma, const int64_t* seed_dev, float peak, float* out_dev, void* workspace,
+                           size_t workspace_bytes, ake_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel timing with hipEvents recorded on the launch stream (bench.py roofline leg).
  * ---------------------------------------------------------------------------------------- */
 int ake_prof_enable(const char* name_filter /* substring, NULL or "" = all */, int on);
