@@ -521,15 +521,16 @@ int device_cus() {
 }
 
 // row-tile height of the persistent pitch-conv kernel for H x T maps (0: the shape does not qualify); `semi`: the form fused with the
-// semitone conv (tiles of 3k rows, no staging slabs but a double-buffered output patch)
-int p2p_ps_rows(int H, int T, bool semi, int* plane_pos, size_t* lds) {
+// semitone conv (tiles of 3k rows, no staging slabs but a double-buffered output patch).  nw: waves of the workgroup (8; 16: a phase of
+// p2p_stack_kernel, whose semitone form always folds: its tile height also divides the octave's 36 rows)
+int p2p_ps_rows(int H, int T, bool semi, int* plane_pos, size_t* lds, int nw = 8) {
     if (T < 2 || (T & 1) || device_cus() < 8) return 0;
     const int J = T / 2, Tp = p2p_pitch(J);
     auto plane_of = [&](int R) { return ((R + 6) * Tp + 63) / 64 * 64; };
-    auto lds_of = [&](int R) { return (static_cast<size_t>(2) * plane_of(R) + (semi ? 2 * 8 * kP2pMT * 16 * 2 : 8 * kP2pMT * kP2pPsStage)) * sizeof(uint4); };
-    int R = std::max(1, std::min(H, 8 * kP2pMT * 16 / J));
+    auto lds_of = [&](int R) { return (static_cast<size_t>(2) * plane_of(R) + (semi ? 2 * nw * kP2pMT * 16 * 2 : nw * kP2pMT * kP2pPsStage)) * sizeof(uint4); };
+    int R = std::max(1, std::min(H, nw * kP2pMT * 16 / J));
     if (semi) R = R / 3 * 3;
-    while (R >= (semi ? 3 : 1) && (lds_of(R) > 156 * 1024 || plane_of(R) / 64 > 8 * kP2pPieces)) R -= semi ? 3 : 1;     // the loader: 8 waves x kP2pPieces pieces
+    while (R >= (semi ? 3 : 1) && (lds_of(R) > 156 * 1024 || plane_of(R) / 64 > nw * kP2pPieces || (semi && nw == 16 && 36 % R))) R -= semi ? 3 : 1;     // the loader: nw waves x kP2pPieces pieces
     if (R < (semi ? 3 : 1) || H < R + 6) return 0;
     if (semi && (H % 3 || (H / 3) % 12)) return 0;
     if (plane_pos) *plane_pos = plane_of(R);
@@ -669,6 +670,72 @@ int run_p2p_f16_ps(const ake_pcnet* n, const PackedConv& pc, const P2pPsPlan& g,
             else hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<1, 8>), grid, block, g.lds, s, a);
             break;
     }
+    return AKE_OK;
+}
+
+// ---- a layer's whole pitch stack as one launch (p2p_stack_kernel): one workgroup of 16 waves per clip walks conv after conv ----
+// Geometry of the phases (first conv fed by layer 0's f16 words | inner convs | last conv + semitone conv + octave fold); ok == false:
+// the stack runs as one launch per conv.  Taken when the chunk fills the machine with one clip per workgroup -- no more clips than
+// CUs, and at most one CU in sixteen left idle.  Launches nothing.
+struct P2pStackPlan {
+    bool ok = false;
+    int n = 0;                              // phases = convs of the stack
+    int R[2] = {0, 0}, plane_pos[2] = {0, 0}, n_row_tiles[2] = {0, 0};     // [0]: the plane-writing phases, [1]: the folding phase
+    int n_oct = 0;
+    size_t lds = 0;
+};
+P2pStackPlan p2p_stack_plan(int convs, int c0, int c1, bool semi_frags, int batch, int H, int T) {
+    P2pStackPlan g;
+    const int n_cus = device_cus();
+    if (convs < 2 || convs > kP2pStackMax || c0 != 1 || c1 < 1 || c1 > 4 || !semi_frags || batch < 1 || batch > n_cus || 16 * (n_cus - batch) > n_cus) return g;
+    size_t lds[2] = {0, 0};
+    for (int f = 0; f < 2; ++f) {
+        g.R[f] = p2p_ps_rows(H, T, f == 1, &g.plane_pos[f], &lds[f], 16);
+        if (g.R[f] <= 0) return g;
+        g.n_row_tiles[f] = (H + g.R[f] - 1) / g.R[f];
+    }
+    if (H % 36 || 36 % g.R[1]) return g;
+    g.n_oct = H / 36;
+    g.lds = std::max(lds[0], lds[1]);
+    g.n = convs;
+    g.ok = true;
+    return g;
+}
+
+// the launch of a planned stack (the same contract as run_p2p_f16_ps: it cannot decline).  planes[j]: where conv j < n - 1 leaves its plane
+int run_p2p_stack(const ake_pcnet* n, const std::vector<PackedConv>& convs, const PackedConv& semi, const P2pStackPlan& g, const unsigned int* melh, const uint2* psix_h,
+                  int c1, unsigned short* const planes[], float* cat, int cat_ctot, int fold_coff, int batch, int H, int T, hipStream_t s, const char* name) {
+    AKE_REQUIRE(g.ok && g.n == static_cast<int>(convs.size()) && batch <= device_cus(), AKE_ERR_STATE,
+                "conv %s: the route sent a stack to the one-launch kernel that does not qualify for it", name);
+    AKE_REQUIRE(melh && psix_h && cat && semi.bf_off >= 0, AKE_ERR_STATE, "conv %s: the one-launch stack lacks a buffer", name);
+    P2pStackArgs sa;
+    std::memset(&sa, 0, sizeof(sa));
+    sa.n = g.n;
+    for (int j = 0; j < g.n; ++j) {
+        const bool fold = j == g.n - 1;
+        P2pPsArgs& a = sa.ph[j];
+        AKE_REQUIRE(fold || planes[j], AKE_ERR_STATE, "conv %s: the one-launch stack lacks a plane", name);
+        a.R = g.R[fold]; a.plane_pos = g.plane_pos[fold]; a.n_row_tiles = g.n_row_tiles[fold]; a.n_tiles = a.n_row_tiles * batch;
+        a.bfrag = n->bf_frags_dev + convs[j].bf_off; a.bias = n->blob_dev + convs[j].b_off;
+        a.H = H; a.T = T; a.J = T / 2; a.Tp = p2p_pitch(a.J);
+        if (j == 0) { a.ph = melh; a.uh = psix_h; a.c0 = 1; a.c1 = c1; a.h1 = 36; }
+        else a.xh = planes[j - 1];
+        if (!fold) a.oh = planes[j];
+        else {
+            a.sfrag = n->bf_frags_dev + semi.bf_off; a.sbias = n->blob_dev + semi.b_off;
+            a.n_oct = g.n_oct; a.n_units = batch * (36 / a.R);
+            a.dst = cat + static_cast<long long>(fold_coff) * 12 * T;
+            a.dst_clip_stride = static_cast<long long>(cat_ctot) * 12 * T;
+        }
+    }
+    static ake::DeviceOnce attr_set;
+    if (attr_set.need()) {
+        AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(p2p_stack_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_set.mark();
+    }
+    dim3 grid(batch), block(1024);
+    ake::ProfScope ps(name, s);
+    hipLaunchKernelGGL(p2p_stack_kernel, grid, block, g.lds, s, sa);
     return AKE_OK;
 }
 
@@ -1104,6 +1171,7 @@ struct Route {
         struct PerChunk {
             P2pPsPlan first, mid, last;   // F16: the persistent form of the first / an inner / the last conv (!ok: the tiled conv_p2p_f16_kernel);
                                           // last.out: plain (Nchw), semitone conv fused (Semi), semitone conv and fold fused (SemiFold)
+            P2pStackPlan stack;           // F16, ok: the whole stack is ONE launch of p2p_stack_kernel, and first / mid / last launch nothing
             P2pX3Plan x3[2];              // F16x3: geometry of conv 0 and of the later convs
         } k[2];
     } p[4];
@@ -1190,6 +1258,9 @@ Route build_route(const ake_pcnet* n, bool train, int batch, int chunk, int fram
                 if (semi) last = p2p_ps_plan(P2pIn::Planes, 0, 0, P2pOut::SemiFold, d.prev_pc + d.out_p, true, B, P, Ti, ws16);
                 if (semi && !last.ok) last = p2p_ps_plan(P2pIn::Planes, 0, 0, P2pOut::Semi, d.out_p, true, B, P, Ti, ws16);
                 if (!last.ok) last = p2p_ps_plan(P2pIn::Planes, 0, 0, P2pOut::Nchw, d.out_p, false, B, P, Ti, ws16);
+                // one launch for the stack: fed by layer 0's f16 words, its last conv fused with the semitone conv (what was written where
+                // stays as the taps know it: planes in the ping-pong buffers, the folded maps in `cat`)
+                if (in0 == P2pIn::SrcF16x4 && semi) rp.k[k].stack = p2p_stack_plan(c.conv_layers, c0, c1, true, B, P, Ti);
             }
         } else if (!c.pc2p_mem && !c.stay_sixth && (train || (c.precision == AKE_PRECISION_F32X3 && !g_keep_taps))) {
             // training: f16 x 3 on the persistent form (f32-equivalent products).  Inference in the f32x3 precision mode: the same kernel with
@@ -2614,7 +2685,18 @@ struct Fwd {
                 if ((rc = res_stack(n->p2p[i], 0, sdesc, B, P, Ti, b.pa[i], b.pb[i], nullptr, 0, "conv_mfma_kernel/p2p"))) return rc;
                 out = b.pa[i];
             }
-            for (int j = 0; j < c.conv_layers && !c.resblock; ++j) {
+            const bool one_launch = rp.stack == PStack::F16 && rk.stack.ok;
+            if (one_launch) {      // the whole stack, semitone conv and fold as one launch
+                unsigned short* planes[kP2pStackMax];
+                for (int j = 0; j < kP2pStackMax; ++j) planes[j] = reinterpret_cast<unsigned short*>((j & 1) ? b.pb[i] : b.pa[i]);
+                if ((rc = run_p2p_stack(n, n->p2p[i], n->semi[i], rk.stack, b.melh + static_cast<size_t>(c0) * P * Ti,
+                                        reinterpret_cast<const uint2*>(b.psix[1]) + static_cast<size_t>(c0) * 36 * Ti, d.prev_pc, planes, cat, ctot, d.prev_pc, B, P, Ti, s,
+                                        "conv_p2p_f16_kernel")))
+                    return rc;
+                out = ((c.conv_layers - 1) & 1) ? b.pb[i] : b.pa[i];
+                last_out = P2pOut::SemiFold;
+            }
+            for (int j = 0; j < c.conv_layers && !c.resblock && !one_launch; ++j) {
                 out = train ? b.pst[i][j] : ((j & 1) ? b.pb[i] : b.pa[i]);
                 out_aff = !train ? nullptr : b.aff_pst[i][j];
                 if (rp.stack == PStack::F16) {

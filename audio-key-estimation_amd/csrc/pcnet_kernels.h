@@ -905,8 +905,18 @@ constexpr int kP2pPsStage = 80;      // uint4 per M-tile of a wave's staging sla
 //   (P2pPsArgs::uh): two loads, three registers and six bit operations per patch position instead of five loads, five registers and the
 //   conversions, which lets this form run two workgroups per CU like its plane-fed siblings (<1, 5>: 133 VGPRs, one workgroup per CU, 83 us
 //   against their 46; the f32 log-CQT handed over frames-major also cost it a cache line per LANE in the texture addresser)
-template <int OUT, int NIN>
-__global__ __launch_bounds__(512, ((NIN > 0 && NIN != 3) ? 2 : 4)) void conv_p2p_f16_ps_kernel(P2pPsArgs a) {   // (the assembling loader's 15 input registers do not fit 128)
+// The body, for a workgroup of NW waves (8: conv_p2p_f16_ps_kernel; 16: p2p_stack_kernel) that walks the tiles first, first + step, ... below
+// `limit` (OUT 3: units).  CHAIN: the workgroup itself wrote this conv's input a moment ago (p2p_stack_kernel), so the first patch is
+// requested only behind p2p_phase_sync() -- the weight fragments, which depend on nothing, are requested in front of it.
+__device__ __forceinline__ void p2p_phase_sync() {
+    __builtin_amdgcn_s_waitcnt(0x0F70);                      // vmcnt(0): this wave's own plane stores have left (and its fragments are here)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();                                         // producer and consumer are waves of ONE workgroup on one CU: workgroup scope
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+template <int OUT, int NIN, int NW, bool CHAIN>
+__device__ __forceinline__ void p2p_ps_tiles(const P2pPsArgs& a, const int first, const int step, const int limit) {
     constexpr bool OUT_CL = OUT == 1, OUT_SEMI = OUT == 2 || OUT == 3, OUT_FOLD = OUT == 3;
     constexpr bool IN_NCHW = NIN > 0;
     constexpr bool IN_UH = NIN == 3;
@@ -920,14 +930,11 @@ __global__ __launch_bounds__(512, ((NIN > 0 && NIN != 3) ? 2 : 4)) void conv_p2p
     f16_saturate_mode();
     const int nchunk = a.plane_pos >> 6;                        // 1 KB pieces per plane
     const int npos = (a.R + 6) * Tp;
-    // tiles of this workgroup: first, first + gridDim.x, ...; workgroups of one XCD take neighbouring tiles
-    const int nwg = gridDim.x, per_xcd = nwg >> 3;
-    const int first = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    // ---- loader: the pieces c = wave, wave + 8, ... of the plane; lane -> patch position -> (row offset, frame) ----
+    // ---- loader: the pieces c = wave, wave + NW, ... of the plane; lane -> patch position -> (row offset, frame) ----
     int pk[kP2pPieces];
 #pragma unroll
     for (int k = 0; k < kP2pPieces; ++k) {
-        const int c = wave + 8 * k;
+        const int c = wave + NW * k;
         int i = c * 64 + lane;
         i = i < npos ? i : npos - 1;
         const int rj = i / Tp, f = i - rj * Tp;
@@ -939,7 +946,7 @@ __global__ __launch_bounds__(512, ((NIN > 0 && NIN != 3) ? 2 : 4)) void conv_p2p
         const long long cbase = static_cast<long long>(clip) * a.H * T;
 #pragma unroll
         for (int k = 0; k < kP2pPieces; ++k) {
-            const int c = wave + 8 * k;
+            const int c = wave + NW * k;
             if (c < nchunk) {
                 int row = y0 - 3 + (pk[k] >> 16);
                 row += row < 0 ? a.H : 0;
@@ -952,7 +959,7 @@ __global__ __launch_bounds__(512, ((NIN > 0 && NIN != 3) ? 2 : 4)) void conv_p2p
         }
     };
     // IN_NCHW: f32 planes -> registers (requested before the multiply loop) -> f16 channels-last patch (written after it);
-    // thread -> the patch positions threadIdx.x, + 512, + 1024
+    // thread -> the patch positions threadIdx.x, + 64 NW, + 128 NW
     float vin[3][NV];
     uint2 vuh[3];
     unsigned int vw[3];
@@ -960,7 +967,7 @@ __global__ __launch_bounds__(512, ((NIN > 0 && NIN != 3) ? 2 : 4)) void conv_p2p
     if (IN_NCHW) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const int i = threadIdx.x + 512 * k;
+            const int i = threadIdx.x + 64 * NW * k;
             const int ic = i < npos ? i : npos - 1;
             const int rj = ic / Tp, f = ic - rj * Tp;
             pn[k] = (rj << 16) | wrap(f - 3, T);
@@ -1013,7 +1020,7 @@ __global__ __launch_bounds__(512, ((NIN > 0 && NIN != 3) ? 2 : 4)) void conv_p2p
                 hi[1] = (vuh[k].x >> 16) | (vuh[k].y << 16);
                 hi[2] = (vuh[k].y >> 16) | (vw[k] & 0xffff0000u);
                 hi[3] = hb;
-                const int i = threadIdx.x + 512 * k;
+                const int i = threadIdx.x + 64 * NW * k;
                 if (i < npos) wH[i] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
                 continue;
             }
@@ -1027,18 +1034,21 @@ __global__ __launch_bounds__(512, ((NIN > 0 && NIN != 3) ? 2 : 4)) void conv_p2p
                 hi[2] = (hi[2] & 0xffffu) | (f16_bits(vin[k][0] - static_cast<float>(h0)) << 16);
                 hi[3] = static_cast<unsigned int>(__builtin_bit_cast(unsigned short, h0));
             }
-            const int i = threadIdx.x + 512 * k;
+            const int i = threadIdx.x + 64 * NW * k;
             if (i < npos) wH[i] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
         }
     };
-    // tile sequence: first, first + nwg, ...; OUT 3: units first, first + nwg, ..., each the n_oct tiles (clip, octave o, group g)
+    // tile sequence: first, first + step, ...; OUT 3: units first, first + step, ..., each the n_oct tiles (clip, octave o, group g)
     const int G = OUT_FOLD ? a.n_row_tiles / a.n_oct : 1;
     auto fold_tile = [&](int u, int o) { const int clip = u / G; return clip * a.n_row_tiles + o * G + (u - clip * G); };
-    const int tile0 = OUT_FOLD ? (first < a.n_units ? fold_tile(first, 0) : -1) : (first < a.n_tiles ? first : -1);
-    if (tile0 >= 0) {
-        if (IN_NCHW) { load_regs(tile0); write_lds(0); }
-        else issue_loads(tile0, 0);
-    }
+    const int tile0 = first < limit ? (OUT_FOLD ? fold_tile(first, 0) : first) : -1;
+    auto first_patch = [&]() {
+        if (tile0 >= 0) {
+            if (IN_NCHW) { load_regs(tile0); write_lds(0); }
+            else issue_loads(tile0, 0);
+        }
+    };
+    if (!CHAIN) first_patch();
     // ---- weight fragments: registers, for the whole launch ----
     uint4 breg[28];                  // (kP2pProducts == 1: the lo halves are never used and never loaded)
 #pragma unroll
@@ -1056,7 +1066,7 @@ __global__ __launch_bounds__(512, ((NIN > 0 && NIN != 3) ? 2 : 4)) void conv_p2p
     const float iscale = reinterpret_cast<const float*>(a.bfrag + kP2pFragScale)[co];
     uint4* const stage = lds4 + 2 * a.plane_pos + wave * (MT * kP2pPsStage);          // OUT 0 / 1: wave-private slabs
     uint4* const opatch = lds4 + 2 * a.plane_pos;                                      // OUT 2: [2 buffers][384 m][2 tau] positions
-    constexpr int kOP = 8 * MT * 16 * 2;                                               // positions of one output patch
+    constexpr int kOP = NW * MT * 16 * 2;                                               // positions of one output patch
     typedef float f32x2e __attribute__((ext_vector_type(2)));
     long long prev_base = 0;          // element offset of the pending tile's first position (channels-last: position index)
     int prev_mblk = 0;
@@ -1157,10 +1167,11 @@ __global__ __launch_bounds__(512, ((NIN > 0 && NIN != 3) ? 2 : 4)) void conv_p2p
             }
         }
     };
-    // The waves 4..7 run their epilogue one barrier late (the accumulators wait in registers): each SIMD holds one wave of either
-    // half, so one half's epilogue, loads and stores issue under the other half's MFMAs instead of all eight waves leaving the
-    // matrix pipe idle together
-    const bool late = !OUT_SEMI && wave >= 4;
+    if (CHAIN) { p2p_phase_sync(); first_patch(); }
+    // The upper half of the waves runs its epilogue one barrier late (the accumulators wait in registers): each SIMD holds as many
+    // waves of either half, so one half's epilogue, loads and stores issue under the other half's MFMAs instead of all waves
+    // leaving the matrix pipe idle together
+    const bool late = !OUT_SEMI && wave >= NW / 2;
     f32x4c acc[MT], accl[MT];       // products with the hi / the (scaled) lo weight plane
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) { acc[mt] = f32x4c{0.f, 0.f, 0.f, 0.f}; accl[mt] = f32x4c{0.f, 0.f, 0.f, 0.f}; }
@@ -1169,9 +1180,9 @@ __global__ __launch_bounds__(512, ((NIN > 0 && NIN != 3) ? 2 : 4)) void conv_p2p
     for (int tile = tile0; tile >= 0; cur ^= 1) {
         int next, n_unit = unit, n_oct_i = oct;
         if (OUT_FOLD) {
-            if (++n_oct_i == a.n_oct) { n_oct_i = 0; n_unit += nwg; }
-            next = n_unit < a.n_units ? fold_tile(n_unit, n_oct_i) : -1;
-        } else next = tile + nwg < a.n_tiles ? tile + nwg : -1;
+            if (++n_oct_i == a.n_oct) { n_oct_i = 0; n_unit += step; }
+            next = n_unit < limit ? fold_tile(n_unit, n_oct_i) : -1;
+        } else next = tile + step < limit ? tile + step : -1;
         // this wave's share of the tile's patch has landed (and its stores have left).  The builtin, not asm: hipcc then knows that
         // nothing of its own is pending at the loop top and places no vmcnt wait inside the loop that would also drain the LDS-DMA
         __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
@@ -1230,6 +1241,46 @@ __global__ __launch_bounds__(512, ((NIN > 0 && NIN != 3) ? 2 : 4)) void conv_p2p
             store_pending();
         }
     }
+}
+
+template <int OUT, int NIN>
+__global__ __launch_bounds__(512, ((NIN > 0 && NIN != 3) ? 2 : 4)) void conv_p2p_f16_ps_kernel(P2pPsArgs a) {   // (the assembling loader's 15 input registers do not fit 128)
+    // tiles of this workgroup: first, first + gridDim.x, ...; workgroups of one XCD take neighbouring tiles
+    const int nwg = gridDim.x, per_xcd = nwg >> 3;
+    const int first = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    p2p_ps_tiles<OUT, NIN, 8, false>(a, first, nwg, OUT == 3 ? a.n_units : a.n_tiles);
+}
+
+// ==========================================================================================
+// The pitch convs of a stack as ONE launch: a workgroup of 16 waves owns a clip and walks the first conv's row tiles, then the next
+// conv's, and so on.  The convs are circular in pitch, so a tile's halo rows belong to the same clip and everything a conv reads was
+// written by the same workgroup: between two convs stands p2p_phase_sync(), a workgroup barrier with workgroup-scope fences, and no
+// workgroup ever waits for another.  Against one launch per conv this drops the inner launches' starts and drains and the tail of a
+// tile count that does not divide by the grid (every workgroup has the same tiles).  The planes between the convs go through memory
+// where the separate launches put them, in the same format; every product and rounding is p2p_ps_tiles's, only the tile height differs.
+//   ph[0]: the first conv <1, 3>; ph[1 .. n - 2]: the inner convs <1, 0>; ph[n - 1]: the last conv with the semitone conv and the
+//   octave fold <3, 0>
+// ==========================================================================================
+constexpr int kP2pStackMax = 4;
+struct P2pStackArgs {
+    P2pPsArgs ph[kP2pStackMax];
+    int n;
+};
+
+__global__ __launch_bounds__(1024) void p2p_stack_kernel(P2pStackArgs s) {
+    const int clip = blockIdx.x;
+    {
+        const int first = clip * s.ph[0].n_row_tiles;
+        p2p_ps_tiles<1, 3, 16, false>(s.ph[0], first, 1, first + s.ph[0].n_row_tiles);
+    }
+    for (int j = 1; j < s.n - 1; ++j) {
+        const P2pPsArgs& a = s.ph[j];
+        const int first = clip * a.n_row_tiles;
+        p2p_ps_tiles<1, 0, 16, true>(a, first, 1, first + a.n_row_tiles);
+    }
+    const P2pPsArgs& a = s.ph[s.n - 1];
+    const int G = a.n_row_tiles / a.n_oct;
+    p2p_ps_tiles<3, 0, 16, true>(a, clip * G, 1, clip * G + G);
 }
 
 // ==========================================================================================
