@@ -76,6 +76,7 @@ SYMBOLS = {
     "ake_pcnet_update_recomputed_running_stats_f32": (_I, [_P, _P, _P, C.c_float, _P, _P]),
     "ake_adam_step_f32": (_I, [_P, _P, _P, _P, _P, _SZ] + [C.c_float] * 5 + [_I, C.c_float, _P]),
     "ake_general_step_f32": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _I] + [C.c_float] * 3 + [_I, _P, _P, _P, _P, _P]),
+    "ake_general_step_weighted_f32": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _I] + [C.c_float] * 3 + [_I, _P, _P, _P, _P, _P, _P]),
     "ake_general_step_local_workspace_bytes": (_SZ, [_I, _I]),
     "ake_general_step_local_f32": (_I, [_P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I] + [C.c_float] * 2 + [_P, _P, _P, _P, _SZ, _P]),
     "ake_pcnet_tap_info": (_I, [_P, C.c_char_p, _I, _I, C.POINTER(_I64)]),
@@ -100,6 +101,8 @@ SYMBOLS = {
     "ake_key_posteriors_chunk_windows": (_I, []),
     "ake_key_posteriors_f32": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "ake_track_score_i32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "ake_draw_windows_i32": (_I, [_P, _I, C.c_uint64, C.c_uint32, _I64, _I, _P, _P, _P]),
+    "ake_window_batch_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, C.c_float, _I, _P, _P, _P, _P, _P, _P, _P]),
     "ake_synth_partials_workspace_bytes": (_SZ, [_I]),
     "ake_synth_batch_partials": (_I, []),
     "ake_synth_partials_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _I64, _I64, C.c_float, _P, C.c_float, _P, _P, _SZ, _P]),

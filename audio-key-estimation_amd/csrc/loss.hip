@@ -23,6 +23,7 @@ struct StepLossArgs {
     int B;
     float key_w, tonic_w, genre_w;
     int use_cos;
+    const float* weight;       // [B] sample weights >= 0, nullable (ake_general_step_weighted_f32)
     float* scalars;            // [10]: loss, accuracy, mirex, correct, fifths, relative, parallel, other, accuracy_tonic, accuracy_genre
     float* d_key;              // nullable (all three or none)
     float* d_tonic;
@@ -90,13 +91,36 @@ __device__ __forceinline__ void mirex_row(const double* p, const double* y, doub
 
 constexpr int kNS = 12;        // per-thread sums: bce, ce_tonic, ce_genre (masked), genre count, genre correct, cos, tonic ok, full, correct, fifths, relative, parallel
 
+// kWeighted: row r counts w_r = sample_weight[r] times in every sum, and the means divide by Wsum = sum_r w_r (a thirteenth sum)
+// instead of B; the genre term by sum_r w_r m_r.  A row's terms are collected on their own and enter the sums as w_r * term; a row with
+// w_r = 0 is not read at all.  The gradients are written as w_r * (the row's derivative) and scaled by 1 / Wsum (the genre's by its own
+// denominator) after the reduction, the way the unweighted genre gradient always was.  !kWeighted is the arithmetic it always was.
+template <bool kWeighted>
 __global__ __launch_bounds__(256) void general_step_kernel(StepLossArgs a) {
-    __shared__ double red[kNS][256];
+    constexpr int NS = kWeighted ? kNS + 1 : kNS;
+    __shared__ double red[NS][256];
     const int B = a.B;
-    double sum[kNS];
+    double sum[NS];
 #pragma unroll
-    for (int k = 0; k < kNS; ++k) sum[k] = 0.0;
+    for (int k = 0; k < NS; ++k) sum[k] = 0.0;
     for (int r = threadIdx.x; r < B; r += blockDim.x) {
+        double row[NS];
+        double* const acc = kWeighted ? row : sum;                                 // where this row's terms are added
+        double w = 1.0;
+        if (kWeighted) {
+            w = static_cast<double>(a.weight[r]);
+            if (!(w > 0.0)) {                                                      // exact zeros, whatever the row holds
+                if (a.d_key)
+                    for (int j = 0; j < 12; ++j) { a.d_key[r * 12 + j] = 0.0f; a.d_tonic[r * 12 + j] = 0.0f; }
+                if (a.genre && a.d_genre)
+                    for (int j = 0; j < 11; ++j) a.d_genre[r * 11 + j] = 0.0f;
+                continue;
+            }
+#pragma unroll
+            for (int k = 0; k < NS; ++k) row[k] = 0.0;
+            row[kNS] = 1.0;
+        }
+        const double rows = kWeighted ? 1.0 / w : static_cast<double>(B);          // a gradient's divisor before the reduction
         // ---- key: BCE (log clamped at -100 as torch does), models.py:855, 878 ----
         double p[12], y[12];
         double pp = 0.0, yy = 0.0, py = 0.0;
@@ -104,15 +128,15 @@ __global__ __launch_bounds__(256) void general_step_kernel(StepLossArgs a) {
             p[j] = static_cast<double>(a.key[r * 12 + j]);
             y[j] = static_cast<double>(a.key_labels[r * 12 + j]);
             const double lp = fmax(log(p[j]), -100.0), l1p = fmax(log1p(-p[j]), -100.0);
-            sum[0] -= y[j] * lp + (1.0 - y[j]) * l1p;
+            acc[0] -= y[j] * lp + (1.0 - y[j]) * l1p;
             pp += p[j] * p[j]; yy += y[j] * y[j]; py += p[j] * y[j];
         }
         const double pn = fmax(sqrt(pp), 1e-8), yn = fmax(sqrt(yy), 1e-8);
-        if (a.use_cos) sum[5] += py / (pn * yn);                                   // models.py:885-887
+        if (a.use_cos) acc[5] += py / (pn * yn);                                   // models.py:885-887
         if (a.d_key) {
             for (int j = 0; j < 12; ++j) {
-                double g = a.key_w * (p[j] - y[j]) / fmax((1.0 - p[j]) * p[j], 1e-12) / (12.0 * B);      // torch's binary_cross_entropy_backward
-                if (a.use_cos) g -= (y[j] / (pn * yn) - py * p[j] / (pn * pn * pn * yn)) / B;
+                double g = a.key_w * (p[j] - y[j]) / fmax((1.0 - p[j]) * p[j], 1e-12) / (12.0 * rows);      // torch's binary_cross_entropy_backward
+                if (a.use_cos) g -= (y[j] / (pn * yn) - py * p[j] / (pn * pn * pn * yn)) / rows;
                 a.d_key[r * 12 + j] = static_cast<float>(g);
             }
         }
@@ -128,11 +152,11 @@ __global__ __launch_bounds__(256) void general_step_kernel(StepLossArgs a) {
             }
             double se = 0.0;
             for (int j = 0; j < 12; ++j) se += exp(z[j] - zmax);
-            sum[1] -= z[t_idx] - zmax - log(se);
+            acc[1] -= z[t_idx] - zmax - log(se);
             if (a.d_tonic)
-                for (int j = 0; j < 12; ++j) a.d_tonic[r * 12 + j] = static_cast<float>(a.tonic_w * (exp(z[j] - zmax) / se - (j == t_idx ? 1.0 : 0.0)) / B);
+                for (int j = 0; j < 12; ++j) a.d_tonic[r * 12 + j] = static_cast<float>(a.tonic_w * (exp(z[j] - zmax) / se - (j == t_idx ? 1.0 : 0.0)) / rows);
             tok = zarg == t_idx;
-            sum[6] += tok ? 1.0 : 0.0;
+            acc[6] += tok ? 1.0 : 0.0;
         }
         // ---- genre: cross entropy over the rows that carry a label, models.py:839-840, 881-883, 892-893 ----
         if (a.genre) {
@@ -148,34 +172,50 @@ __global__ __launch_bounds__(256) void general_step_kernel(StepLossArgs a) {
             }
             double se = 0.0;
             for (int j = 0; j < 11; ++j) se += exp(z[j] - zmax);
-            sum[2] -= m * (z[g_idx] - zmax - log(se));
-            sum[3] += m;
-            sum[4] += m * (zarg == g_idx ? 1.0 : 0.0);
+            acc[2] -= m * (z[g_idx] - zmax - log(se));
+            acc[3] += m;
+            acc[4] += m * (zarg == g_idx ? 1.0 : 0.0);
             if (a.d_genre)   // scaled by 1 / (number of labelled rows) after the reduction
-                for (int j = 0; j < 11; ++j) a.d_genre[r * 11 + j] = static_cast<float>(a.genre_w * m * (exp(z[j] - zmax) / se - (j == g_idx ? 1.0 : 0.0)));
+                for (int j = 0; j < 11; ++j)
+                    a.d_genre[r * 11 + j] = static_cast<float>(a.genre_w * (kWeighted ? w * m : m) * (exp(z[j] - zmax) / se - (j == g_idx ? 1.0 : 0.0)));
         }
         // ---- MIREX categories, models.py:1065-1116 ----
-        mirex_row(p, y, pn, tok, lab_argmax(a.sig_lab, a.sig_i64, static_cast<long long>(r) * 24, 24, false), sum + 7);   // (models.py:1090: no .long())
+        mirex_row(p, y, pn, tok, lab_argmax(a.sig_lab, a.sig_i64, static_cast<long long>(r) * 24, 24, false), acc + 7);   // (models.py:1090: no .long())
+        if (kWeighted) {
+#pragma unroll
+            for (int k = 0; k < NS; ++k) sum[k] += w * row[k];
+        }
     }
 #pragma unroll
-    for (int k = 0; k < kNS; ++k) red[k][threadIdx.x] = sum[k];
+    for (int k = 0; k < NS; ++k) red[k][threadIdx.x] = sum[k];
     __syncthreads();
     for (int w = 128; w > 0; w >>= 1) {
         if (static_cast<int>(threadIdx.x) < w)
 #pragma unroll
-            for (int k = 0; k < kNS; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + w];
+            for (int k = 0; k < NS; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + w];
         __syncthreads();
     }
     const double cnt = red[3][0];
-    const double inv_cnt = 1.0 / fmax(cnt, 1.0);
+    const double inv_cnt = kWeighted ? (cnt > 0.0 ? 1.0 / cnt : 0.0) : 1.0 / fmax(cnt, 1.0);
+    const double n = kWeighted ? red[NS - 1][0] : static_cast<double>(B);          // Wsum, or the batch
+    const double inv_n = kWeighted ? (n > 0.0 ? 1.0 / n : 0.0) : 0.0;
     if (a.genre && a.d_genre)
         for (int r = threadIdx.x; r < B; r += blockDim.x)          // the rows this thread wrote above
             for (int j = 0; j < 11; ++j) a.d_genre[r * 11 + j] = static_cast<float>(static_cast<double>(a.d_genre[r * 11 + j]) * inv_cnt);
+    if (kWeighted && a.d_key)
+        for (int r = threadIdx.x; r < B; r += blockDim.x)
+            for (int j = 0; j < 12; ++j) {
+                a.d_key[r * 12 + j] = static_cast<float>(static_cast<double>(a.d_key[r * 12 + j]) * inv_n);
+                a.d_tonic[r * 12 + j] = static_cast<float>(static_cast<double>(a.d_tonic[r * 12 + j]) * inv_n);
+            }
     if (threadIdx.x == 0) {
-        double loss = a.key_w * red[0][0] / (12.0 * B) + a.tonic_w * red[1][0] / B;                 // models.py:889
+        if (kWeighted && !(n > 0.0)) {                                                              // no row counts: zeros
+            for (int k = 0; k < 10; ++k) a.scalars[k] = 0.0f;
+            return;
+        }
+        double loss = a.key_w * red[0][0] / (12.0 * n) + a.tonic_w * red[1][0] / n;                 // models.py:889
         if (a.genre) loss += a.genre_w * red[2][0] * inv_cnt;                                       // an exact zero when no row carries a label (:892)
-        if (a.use_cos) loss += 1.0 - red[5][0] / B;
-        const double n = B;
+        if (a.use_cos) loss += 1.0 - red[5][0] / n;
         const double correct = red[8][0], fifths = red[9][0], relative = red[10][0], parallel = red[11][0];
         a.scalars[0] = static_cast<float>(loss);
         a.scalars[1] = static_cast<float>(red[7][0] / n);                                           // accuracy = all 12 key bits right
@@ -328,11 +368,12 @@ __global__ __launch_bounds__(kLocFinish) void general_step_local_finish_kernel(S
 
 }  // namespace
 
-extern "C" int ake_general_step_f32(const float* key_out, const float* tonic_out, const float* genre_out, const float* key_labels,
-                                    const void* tonic_labels, int tonic_labels_i64, const void* genre_labels, int genre_labels_i64,
-                                    const void* key_signature_id, int key_signature_i64, int batch, float key_weight, float tonic_weight,
-                                    float genre_weight, int use_cos, float* scalars_out, float* d_key, float* d_tonic, float* d_genre,
-                                    ake_stream_t stream) {
+namespace {
+
+int general_step_launch(const float* key_out, const float* tonic_out, const float* genre_out, const float* key_labels, const void* tonic_labels,
+                        int tonic_labels_i64, const void* genre_labels, int genre_labels_i64, const void* key_signature_id, int key_signature_i64,
+                        int batch, float key_weight, float tonic_weight, float genre_weight, int use_cos, const float* sample_weight,
+                        float* scalars_out, float* d_key, float* d_tonic, float* d_genre, ake_stream_t stream) {
     AKE_REQUIRE(key_out && tonic_out && key_labels && tonic_labels && key_signature_id && scalars_out, AKE_ERR_INVALID, "general_step: null argument");
     AKE_REQUIRE(batch >= 1, AKE_ERR_INVALID, "general_step: batch %d", batch);
     AKE_REQUIRE(!genre_out || genre_labels, AKE_ERR_INVALID, "general_step: genre outputs without genre labels");
@@ -342,13 +383,36 @@ extern "C" int ake_general_step_f32(const float* key_out, const float* tonic_out
     a.key = key_out; a.tonic = tonic_out; a.genre = genre_out; a.key_labels = key_labels;
     a.tonic_lab = tonic_labels; a.genre_lab = genre_labels; a.sig_lab = key_signature_id;
     a.tonic_i64 = tonic_labels_i64; a.genre_i64 = genre_labels_i64; a.sig_i64 = key_signature_i64;
-    a.B = batch; a.key_w = key_weight; a.tonic_w = tonic_weight; a.genre_w = genre_weight; a.use_cos = use_cos;
+    a.B = batch; a.key_w = key_weight; a.tonic_w = tonic_weight; a.genre_w = genre_weight; a.use_cos = use_cos; a.weight = sample_weight;
     a.scalars = scalars_out; a.d_key = d_key; a.d_tonic = d_tonic; a.d_genre = genre_out ? d_genre : nullptr;
     hipStream_t s = static_cast<hipStream_t>(stream);
     ake::ProfScope ps("general_step_kernel", s);
-    hipLaunchKernelGGL(general_step_kernel, dim3(1), dim3(256), 0, s, a);
+    if (sample_weight) hipLaunchKernelGGL(general_step_kernel<true>, dim3(1), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(general_step_kernel<false>, dim3(1), dim3(256), 0, s, a);
     AKE_HIP_CHECK(hipGetLastError());
     return AKE_OK;
+}
+
+}  // namespace
+
+extern "C" int ake_general_step_f32(const float* key_out, const float* tonic_out, const float* genre_out, const float* key_labels,
+                                    const void* tonic_labels, int tonic_labels_i64, const void* genre_labels, int genre_labels_i64,
+                                    const void* key_signature_id, int key_signature_i64, int batch, float key_weight, float tonic_weight,
+                                    float genre_weight, int use_cos, float* scalars_out, float* d_key, float* d_tonic, float* d_genre,
+                                    ake_stream_t stream) {
+    return general_step_launch(key_out, tonic_out, genre_out, key_labels, tonic_labels, tonic_labels_i64, genre_labels, genre_labels_i64,
+                               key_signature_id, key_signature_i64, batch, key_weight, tonic_weight, genre_weight, use_cos, nullptr, scalars_out,
+                               d_key, d_tonic, d_genre, stream);
+}
+
+extern "C" int ake_general_step_weighted_f32(const float* key_out, const float* tonic_out, const float* genre_out, const float* key_labels,
+                                             const void* tonic_labels, int tonic_labels_i64, const void* genre_labels, int genre_labels_i64,
+                                             const void* key_signature_id, int key_signature_i64, int batch, float key_weight,
+                                             float tonic_weight, float genre_weight, int use_cos, const float* sample_weight_dev,
+                                             float* scalars_out, float* d_key, float* d_tonic, float* d_genre, ake_stream_t stream) {
+    return general_step_launch(key_out, tonic_out, genre_out, key_labels, tonic_labels, tonic_labels_i64, genre_labels, genre_labels_i64,
+                               key_signature_id, key_signature_i64, batch, key_weight, tonic_weight, genre_weight, use_cos, sample_weight_dev,
+                               scalars_out, d_key, d_tonic, d_genre, stream);
 }
 
 extern "C" size_t ake_general_step_local_workspace_bytes(int batch, int out_frames) {

@@ -12,6 +12,7 @@
 // The block's max |y| goes through a wave butterfly and LDS into one integer atomicMax on the float's bit pattern per block (the maximum
 // does not depend on the order).  synth_scale_kernel is the second pass: y *= peak / max.
 #include "common.h"
+#include "philox.h"
 
 #include <algorithm>
 #include <cmath>
@@ -39,22 +40,6 @@ struct SynthArgs {
     int fade;
     float sigma;
 };
-
-__device__ __forceinline__ void philox_round(unsigned (&c)[4], unsigned k0, unsigned k1) {
-    const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
-    const unsigned n0 = static_cast<unsigned>(p1 >> 32) ^ c[1] ^ k0, n2 = static_cast<unsigned>(p0 >> 32) ^ c[3] ^ k1;
-    c[1] = static_cast<unsigned>(p1); c[3] = static_cast<unsigned>(p0);
-    c[0] = n0; c[2] = n2;
-}
-
-// Philox4x32-10 (Salmon et al., SC 2011): 10 rounds, the key bumped by the Weyl constants between them
-__device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        philox_round(c, k0, k1);
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
 
 // ((x >> 9) + 0.5) 2^-23: an odd multiple of 2^-24 in (0, 1), exact in float32
 __device__ __forceinline__ float philox_uniform(unsigned x) { return (static_cast<float>(x >> 9) + 0.5f) * 0x1p-23f; }
@@ -129,7 +114,7 @@ __global__ __launch_bounds__(kSynthBlock) void synth_kernel(SynthArgs a) {
     if (a.sigma != 0.f) {
         const unsigned long long b = static_cast<unsigned long long>(t0) >> 2, sd = static_cast<unsigned long long>(a.seed[r]);
         unsigned c[4] = {static_cast<unsigned>(b), static_cast<unsigned>(b >> 32), static_cast<unsigned>(r), 0u};
-        philox4x32_10(c, static_cast<unsigned>(sd), static_cast<unsigned>(sd >> 32));
+        ake::philox4x32_10(c, static_cast<unsigned>(sd), static_cast<unsigned>(sd >> 32));
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const float rad = a.sigma * sqrtf(-2.0f * logf(philox_uniform(c[2 * h])));

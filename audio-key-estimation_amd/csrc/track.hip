@@ -23,7 +23,11 @@
 // key_posteriors_kernel (everything per window), below the Viterbi kernel.
 //
 // A track is scored against key annotations by track_score_kernel (one launch, integers only), below the posterior kernels.
+//
+// Training on annotated recordings assembles its batches from the same cached transform: draw_windows_kernel (window positions from a
+// counter-based generator) and window_batch_kernel (the gather, from a list in device memory, with every window's labels and weight).
 #include "common.h"
+#include "philox.h"
 
 #include <algorithm>
 #include <climits>
@@ -43,34 +47,40 @@ struct GatherArgs {
     int clip0;                 // global window index of dst's clip 0
 };
 
-// One 32 x 32 tile of one window per block of 32 x 8 threads.  FM source: the loads run along the bins (the source's fast axis), the
-// stores along the frames (the destination's), a padded LDS tile turns the one into the other.  Row-major source: both fast axes are
-// the frames, a straight copy.
+// One 32 x 32 tile of one window per block of 32 x 8 threads: frames [t0, t0 + window_frames) of `src` (one recording's transform) to
+// `dst` ([P][window_frames]).  FM source: the loads run along the bins (the source's fast axis), the stores along the frames (the
+// destination's), a padded LDS tile turns the one into the other.  Row-major source: both fast axes are the frames, a straight copy.
+template <bool FM>
+__device__ __forceinline__ void gather_tile(const float* src, float* dst, int P, int total_frames, int window_frames, int t0,
+                                            float (&tile)[kTile][kTile + 1]) {
+    const int p0 = blockIdx.x * kTile, f0 = blockIdx.y * kTile;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    if (FM) {
+        for (int j = ty; j < kTile; j += 8) {
+            const int f = f0 + j, p = p0 + tx;
+            if (f < window_frames && p < P) tile[j][tx] = src[static_cast<long long>(t0 + f) * P + p];
+        }
+        __syncthreads();
+        for (int j = ty; j < kTile; j += 8) {
+            const int p = p0 + j, f = f0 + tx;
+            if (p < P && f < window_frames) dst[p * window_frames + f] = tile[tx][j];
+        }
+    } else {
+        for (int j = ty; j < kTile; j += 8) {
+            const int p = p0 + j, f = f0 + tx;
+            if (p < P && f < window_frames) dst[p * window_frames + f] = src[static_cast<long long>(p) * total_frames + t0 + f];
+        }
+    }
+}
+
+// Windows at a fixed stride: global window g is window g % windows of recording g / windows.
 template <bool FM>
 __global__ __launch_bounds__(256) void window_gather_kernel(GatherArgs a) {
     __shared__ float tile[kTile][kTile + 1];
     const int g = a.clip0 + blockIdx.z;
     const int rec = g / a.windows, t0 = (g - rec * a.windows) * a.stride_frames;      // t0 + window_frames <= total_frames (host-checked)
-    const int p0 = blockIdx.x * kTile, f0 = blockIdx.y * kTile;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const float* const src = a.src + static_cast<long long>(rec) * a.P * a.total_frames;
-    float* const dst = a.dst + static_cast<long long>(blockIdx.z) * a.P * a.window_frames;
-    if (FM) {
-        for (int j = ty; j < kTile; j += 8) {
-            const int f = f0 + j, p = p0 + tx;
-            if (f < a.window_frames && p < a.P) tile[j][tx] = src[static_cast<long long>(t0 + f) * a.P + p];
-        }
-        __syncthreads();
-        for (int j = ty; j < kTile; j += 8) {
-            const int p = p0 + j, f = f0 + tx;
-            if (p < a.P && f < a.window_frames) dst[p * a.window_frames + f] = tile[tx][j];
-        }
-    } else {
-        for (int j = ty; j < kTile; j += 8) {
-            const int p = p0 + j, f = f0 + tx;
-            if (p < a.P && f < a.window_frames) dst[p * a.window_frames + f] = src[static_cast<long long>(p) * a.total_frames + t0 + f];
-        }
-    }
+    gather_tile<FM>(a.src + static_cast<long long>(rec) * a.P * a.total_frames, a.dst + static_cast<long long>(blockIdx.z) * a.P * a.window_frames,
+                    a.P, a.total_frames, a.window_frames, t0, tile);
 }
 
 __global__ void fill_i64_kernel(long long* dst, long long v, int n) {
@@ -678,6 +688,105 @@ __global__ __launch_bounds__(256) void track_score_kernel(ScoreArgs a) {
     else if (threadIdx.x < 14) a.changes[r * 2 + threadIdx.x - 12] = s_tally[threadIdx.x];
 }
 
+// ---- training windows: positions drawn on the device, gathered from the cached transform, labelled from the annotations ----
+// (semantics: include/ake_hip.h; host models: metrics.draw_windows / metrics.window_labels)
+struct DrawArgs {
+    const long long* prefix;   // [R + 1] exclusive sums of the recordings' start counts; N = prefix[R]
+    int recordings;
+    unsigned key0, key1, epoch;
+    unsigned long long first_slot;
+    int batch;
+    int* recording;            // [batch]
+    int* start;                // [batch]
+};
+
+// One thread per slot: one Philox block -> a 64-bit word x -> index = floor(x * N / 2^64) -> (recording, start) by binary search over
+// the prefix.  Integers only.  N <= 0 (the entry's contract excludes it, and the host cannot see it): -1 in both outputs.
+__global__ __launch_bounds__(256) void draw_windows_kernel(DrawArgs a) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.batch) return;
+    const unsigned long long j = a.first_slot + static_cast<unsigned long long>(b);
+    unsigned c[4] = {static_cast<unsigned>(j), static_cast<unsigned>(j >> 32), a.epoch, 0x57494E44u};
+    ake::philox4x32_10(c, a.key0, a.key1);
+    const unsigned long long x = static_cast<unsigned long long>(c[0]) | static_cast<unsigned long long>(c[1]) << 32;
+    const long long N = a.prefix[a.recordings];
+    if (N <= 0) { a.recording[b] = -1; a.start[b] = -1; return; }
+    const long long index = static_cast<long long>(__umul64hi(x, static_cast<unsigned long long>(N)));
+    int lo = 0, hi = a.recordings - 1;                                   // the last i in 0..R-1 with prefix[i] <= index (prefix[0] = 0)
+    while (lo < hi) {
+        const int mid = lo + (hi - lo + 1) / 2;
+        if (a.prefix[mid] <= index) lo = mid; else hi = mid - 1;
+    }
+    a.recording[b] = lo;
+    a.start[b] = static_cast<int>(index - a.prefix[lo]);
+}
+
+struct BatchArgs {
+    const float* src;          // as GatherArgs
+    float* dst;                // [batch][P][window_frames], nullable: labels only
+    int P, recordings, total_frames, window_frames;
+    long long hop;
+    const int* recording;      // [batch], in device memory: read clamped to 0..recordings-1
+    const int* start;          // [batch], read clamped to 0..total_frames-window_frames
+    const long long* seg_start;   // as ScoreArgs; null: no labels
+    const int* seg_key;
+    const int* seg_count;
+    int max_segments;
+    float min_purity;
+    int uniform;
+    float* key_labels;         // [batch][12]
+    float* tonic_labels;       // [batch][12]
+    float* sig;                // [batch][24]
+    long long* seq;            // [batch]
+    float* weight;             // [batch]
+};
+
+// grid (P tiles, frame tiles, batch) with a gather, (1, 1, batch) without: every block copies its tile of window blockIdx.z, and block
+// (0, 0, z) also writes that window's 50 label words.  Its first 64 threads each walk the recording's segments (the same handful of
+// broadcast loads; integers until the one division) and then write one word each.
+template <bool FM>
+__global__ __launch_bounds__(256) void window_batch_kernel(BatchArgs a) {
+    __shared__ float tile[kTile][kTile + 1];
+    const int b = blockIdx.z;
+    int rec = a.recording[b], t0 = a.start[b];
+    rec = rec < 0 ? 0 : rec >= a.recordings ? a.recordings - 1 : rec;
+    t0 = t0 < 0 ? 0 : t0 > a.total_frames - a.window_frames ? a.total_frames - a.window_frames : t0;     // (>= 0: host-checked)
+    if (a.dst)
+        gather_tile<FM>(a.src + static_cast<long long>(rec) * a.P * a.total_frames, a.dst + static_cast<long long>(b) * a.P * a.window_frames, a.P,
+                        a.total_frames, a.window_frames, t0, tile);
+    const int t = threadIdx.x;
+    if (!a.seg_start || blockIdx.x != 0 || blockIdx.y != 0 || t >= 50) return;
+    int ns = a.seg_count[rec];
+    ns = ns < 0 ? 0 : ns > a.max_segments ? a.max_segments : ns;
+    const long long* const start = a.seg_start + static_cast<size_t>(rec) * a.max_segments;
+    const int* const key = a.seg_key + static_cast<size_t>(rec) * a.max_segments;
+    const long long lo = t0 * a.hop, hi = (static_cast<long long>(t0) + a.window_frames - 1) * a.hop;
+    const long long centre = (2ll * t0 + a.window_frames - 1) * a.hop / 2;
+    int truth = -1;
+    for (int s = 0; s < ns; ++s) truth = start[s] <= centre ? key[s] : truth;
+    long long c = 0;                                                     // samples of lo..hi inside segments that carry truth
+    for (int s = 0; s < ns; ++s) {
+        const long long s0 = start[s] > lo ? start[s] : lo;
+        const long long last = s + 1 < ns ? start[s + 1] - 1 : LLONG_MAX;
+        const long long s1 = last < hi ? last : hi;
+        if (key[s] == truth && s1 >= s0) c += s1 - s0 + 1;
+    }
+    const float purity = static_cast<float>(static_cast<double>(c) / static_cast<double>(hi - lo + 1));
+    const bool keep = truth >= 0 && !(purity < a.min_purity);
+    if (t < 12) {
+        const int major = truth >= 12 ? truth - 12 : (truth + 3) % 12;
+        a.key_labels[b * 12 + t] = truth >= 0 && ((kMajorScale >> ((t - major + 12) % 12)) & 1) ? 1.f : 0.f;
+    } else if (t < 24) {
+        a.tonic_labels[b * 12 + t - 12] = truth >= 0 && t - 12 == truth % 12 ? 1.f : 0.f;
+    } else if (t < 48) {
+        a.sig[b * 24 + t - 24] = t - 24 == truth ? 1.f : 0.f;
+    } else if (t == 48) {
+        a.seq[b] = a.window_frames;
+    } else {
+        a.weight[b] = keep ? (a.uniform ? 1.f : purity) : 0.f;
+    }
+}
+
 struct PostCarve {
     float* a;
     float* b;
@@ -977,6 +1086,54 @@ int ake_track_score_i32(const int32_t* pred_dev, const int32_t* counts_dev, cons
     {
         ake::ProfScope ps("track_score_kernel", s);
         hipLaunchKernelGGL(track_score_kernel, dim3(recordings), dim3(256), 0, s, a);
+    }
+    AKE_HIP_CHECK(hipGetLastError());
+    return AKE_OK;
+}
+
+int ake_draw_windows_i32(const int64_t* prefix_dev, int recordings, uint64_t seed, uint32_t epoch, int64_t first_slot, int batch,
+                         int32_t* recording_out_dev, int32_t* start_out_dev, ake_stream_t stream) {
+    AKE_REQUIRE(prefix_dev && recording_out_dev && start_out_dev, AKE_ERR_INVALID, "draw_windows: null argument");
+    AKE_REQUIRE(recordings > 0 && batch >= 0 && first_slot >= 0, AKE_ERR_INVALID, "draw_windows: bad shape (%d recordings, batch %d, first slot %lld)",
+                recordings, batch, static_cast<long long>(first_slot));
+    if (batch == 0) return AKE_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DrawArgs a{reinterpret_cast<const long long*>(prefix_dev), recordings, static_cast<unsigned>(seed), static_cast<unsigned>(seed >> 32), epoch,
+               static_cast<unsigned long long>(first_slot), batch, recording_out_dev, start_out_dev};
+    {
+        ake::ProfScope ps("draw_windows_kernel", s);
+        hipLaunchKernelGGL(draw_windows_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, a);
+    }
+    AKE_HIP_CHECK(hipGetLastError());
+    return AKE_OK;
+}
+
+int ake_window_batch_f32(const float* mel_dev, int frames_major, int recordings, int total_frames, int pitches, int window_frames, int hop,
+                         const int32_t* recording_dev, const int32_t* start_dev, int batch, const int64_t* seg_start_dev,
+                         const int32_t* seg_key_dev, const int32_t* seg_count_dev, int max_segments, float min_purity, int uniform,
+                         float* mel_out_dev, float* key_labels_dev, float* tonic_labels_dev, float* key_signature_id_dev,
+                         int64_t* seq_length_dev, float* weight_dev, ake_stream_t stream) {
+    AKE_REQUIRE(recording_dev && start_dev, AKE_ERR_INVALID, "window_batch: null window list");
+    const int given = !!seg_start_dev + !!seg_key_dev + !!seg_count_dev + !!key_labels_dev + !!tonic_labels_dev + !!key_signature_id_dev +
+                      !!seq_length_dev + !!weight_dev;
+    AKE_REQUIRE(given == 0 || given == 8, AKE_ERR_INVALID, "window_batch: pass the annotations and every label output, or none of them");
+    AKE_REQUIRE(!mel_out_dev || mel_dev, AKE_ERR_INVALID, "window_batch: mel_out_dev without mel_dev");
+    AKE_REQUIRE(mel_out_dev || given, AKE_ERR_INVALID, "window_batch: nothing to write");
+    AKE_REQUIRE(recordings > 0 && pitches > 0 && window_frames > 0 && total_frames >= window_frames && total_frames < (1 << 30) && hop > 0, AKE_ERR_INVALID,
+                "window_batch: bad shape (%d recordings, %d frames, %d pitches, window %d, hop %d)", recordings, total_frames, pitches, window_frames, hop);
+    AKE_REQUIRE(batch >= 0 && batch <= 65535, AKE_ERR_INVALID, "window_batch: batch %d (at most 65535)", batch);                  // (grid z)
+    AKE_REQUIRE(!given || max_segments > 0, AKE_ERR_INVALID, "window_batch: max_segments %d", max_segments);
+    AKE_REQUIRE(!(min_purity != min_purity), AKE_ERR_INVALID, "window_batch: min_purity is NaN");
+    if (batch == 0) return AKE_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    BatchArgs a{mel_dev, mel_out_dev, pitches, recordings, total_frames, window_frames, hop, recording_dev, start_dev,
+                reinterpret_cast<const long long*>(seg_start_dev), seg_key_dev, seg_count_dev, max_segments, min_purity, uniform,
+                key_labels_dev, tonic_labels_dev, key_signature_id_dev, reinterpret_cast<long long*>(seq_length_dev), weight_dev};
+    const dim3 grid(mel_out_dev ? (pitches + kTile - 1) / kTile : 1, mel_out_dev ? (window_frames + kTile - 1) / kTile : 1, batch);
+    {
+        ake::ProfScope ps("window_batch_kernel", s);
+        if (frames_major) hipLaunchKernelGGL(window_batch_kernel<true>, grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(window_batch_kernel<false>, grid, dim3(256), 0, s, a);
     }
     AKE_HIP_CHECK(hipGetLastError());
     return AKE_OK;

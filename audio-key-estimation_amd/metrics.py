@@ -72,8 +72,9 @@ def decode_keys(key, tonic):
             conf.reshape(lead))
 
 
-def mirex_score(key_labels, key_preds, tonic_labels, tonic_preds, key_signature_id):
-    """-> (mirex, correct, fifths, relative, parallel, other, accuracy), float32 scalars.
+def mirex_categories(key_labels, key_preds, tonic_labels, tonic_preds, key_signature_id):
+    """-> (correct, fifths, relative, parallel, other, full): bool (B,) each, every prediction's MIREX category (at most one of the first
+    five) and whether all 12 key bits are right.
 
     Category logic and its quirks follow models.py:1084-1114 exactly: the predicted key is the
     first-maximum cosine match over the 21-row table, ``diff`` compares that row index with the
@@ -103,6 +104,13 @@ def mirex_score(key_labels, key_preds, tonic_labels, tonic_preds, key_signature_
     relative = full & ~tonic_ok & ~fifths
     parallel = tonic_ok & ~full & ~fifths
     other = ~(fifths | correct | relative | parallel)
+    return correct, fifths, relative, parallel, other, full
+
+
+def mirex_score(key_labels, key_preds, tonic_labels, tonic_preds, key_signature_id):
+    """-> (mirex, correct, fifths, relative, parallel, other, accuracy), float32 scalars: the shares of ``mirex_categories`` over the
+    batch and their MIREX-weighted sum."""
+    correct, fifths, relative, parallel, other, full = mirex_categories(key_labels, key_preds, tonic_labels, tonic_preds, key_signature_id)
     n = float(key_preds.shape[0])
     f = lambda m: (m.sum().float() / n).float()
     mirex = (1.0 * correct.sum() + 0.5 * fifths.sum() + 0.3 * relative.sum() + 0.2 * parallel.sum()).float() / n
@@ -478,3 +486,156 @@ def transition_from_labels(truth, counts=None, tied=True, pseudo_count=1.0, init
     C = torch.zeros(576, dtype=torch.float64).index_add_(0, (a * 24 + b)[ok], torch.ones(int(ok.sum()), dtype=torch.float64)).reshape(24, 24)
     init = key_transition_log(stay=0.9) if init is None else init
     return transition_m_step(C, init, tied=tied, pseudo_count=pseudo_count)
+
+
+# ---- training windows of annotated recordings: host models of ake_draw_windows_i32, ake_window_batch_f32's labels and the weighted loss ----
+
+DRAW_DOMAIN = 0x57494E44             # "WIND": the fourth counter word of the window draw (the synthesiser's noise uses 0 there)
+
+
+def window_prefix(frames, window_frames):
+    """``[0, c_0, c_0 + c_1, ...]`` (Python ints, R + 1 entries) with ``c_i = max(0, T_i - window_frames + 1)``: the number of window
+    starts of every recording, summed exclusively -- the population ``draw_windows`` draws from."""
+    prefix = [0]
+    for t in frames:
+        prefix.append(prefix[-1] + max(0, int(t) - int(window_frames) + 1))
+    return prefix
+
+
+def draw_windows(prefix, seed, epoch, first_slot, batch):
+    """``batch`` window positions -> ``(recording, start, index)``, lists of Python ints: ``ake_draw_windows_i32`` restated in
+    Python-int arithmetic on ``synthetic.philox4x32_10``.
+
+    ``prefix`` (R + 1 ints, ``window_prefix``; a prefix alone describes the population, no recording needs to exist), ``N = prefix[R]``.
+    Slot ``j = first_slot + b`` takes one Philox block with counter ``(j low 32, j high 32, epoch, DRAW_DOMAIN)`` and key
+    ``(seed low 32, seed high 32)``; ``x = word0 | word1 << 32``, ``index = (x * N) >> 64``, ``recording`` = the last i < R with
+    ``prefix[i] <= index``, ``start = index - prefix[recording]``.  ``ValueError`` for N <= 0."""
+    import bisect
+    import numpy as np
+    from .synthetic import philox4x32_10
+    prefix = [int(v) for v in prefix]
+    R, N = len(prefix) - 1, prefix[-1]
+    if R < 1 or N <= 0:
+        raise ValueError("draw_windows: no recording is as long as one window (N = 0)")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    j = [int(first_slot) + b for b in range(int(batch))]
+    counter = np.array([[v & 0xFFFFFFFF, (v >> 32) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, DRAW_DOMAIN] for v in j], dtype=np.uint64).reshape(-1, 4)
+    words = philox4x32_10(counter, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64))
+    recording, start, index = [], [], []
+    for w in words:
+        x = int(w[0]) | int(w[1]) << 32
+        idx = (x * N) >> 64
+        r = bisect.bisect_right(prefix, idx, 0, R) - 1
+        recording.append(r); start.append(idx - prefix[r]); index.append(idx)
+    return recording, start, index
+
+
+def window_labels(seg_start, seg_key, seg_count, recording, start, hop, window_frames, min_purity=0.0, uniform=False):
+    """Labels and weights of the windows ``(recording[b], start[b])`` -> dict of ``truth`` int32 (B,), ``purity`` float32 (B,),
+    ``key_labels`` (B, 12), ``tonic_labels`` (B, 12), ``key_signature_id`` (B, 24), ``sample_weight`` (B,) float32 and ``seq_length``
+    int64 (B,): ``ake_window_batch_f32``'s labels in integer torch ops, on the annotations' device.
+
+    The geometry is ``window_truth``'s at the window's own start frame: ``lo = start * hop``, ``hi = (start + window_frames - 1) * hop``,
+    ``centre = (2 * start + window_frames - 1) * hop // 2``; ``truth`` = the key of the last segment that starts at or before ``centre``;
+    ``purity = float32(float64(c) / float64(hi - lo + 1))`` with ``c`` the samples of ``lo..hi`` inside segments that carry ``truth``
+    (``window_truth``'s ``pure`` is ``purity == 1``); the weight is 0 where ``truth < 0`` or ``purity < min_purity``, else 1
+    (``uniform``) or ``purity``.  The labels of key k are ``synthetic.key_pitch_classes(k)``, one-hot ``k % 12`` and one-hot ``k``; zeros
+    for ``truth < 0``."""
+    dev = seg_start.device
+    R, S = seg_start.shape
+    rec = torch.as_tensor(recording, device=dev).to(torch.int64).reshape(-1)
+    st = torch.as_tensor(start, device=dev).to(torch.int64).reshape(-1)
+    hop, wf = int(hop), int(window_frames)
+    begin = seg_start.to(torch.int64)[rec]                                                          # (B, S)
+    key = seg_key.to(device=dev, dtype=torch.int64)[rec]
+    ns = torch.as_tensor(seg_count, device=dev).to(torch.int64).reshape(R).clamp(0, S)[rec]
+    lo, hi, centre = st * hop, (st + wf - 1) * hop, torch.div((2 * st + wf - 1) * hop, 2, rounding_mode="floor")
+    s_idx = torch.arange(S, device=dev)
+    valid = s_idx[None, :] < ns[:, None]
+    holds = valid & (begin <= centre[:, None])
+    last = (holds * (s_idx + 1)[None, :]).amax(dim=1) - 1
+    truth = torch.where(last >= 0, key.gather(1, last.clamp_min(0)[:, None])[:, 0], torch.full_like(last, -1))
+    nxt = torch.cat([begin[:, 1:], torch.full((len(rec), 1), _I64_MAX, device=dev, dtype=torch.int64)], dim=1)
+    end = torch.where(s_idx[None, :] + 1 < ns[:, None], nxt - 1, torch.full_like(nxt, _I64_MAX))      # a segment's last sample
+    a, b = torch.maximum(begin, lo[:, None]), torch.minimum(end, hi[:, None])
+    c = torch.where(valid & (key == truth[:, None]) & (truth >= 0)[:, None] & (b >= a), b - a + 1, torch.zeros_like(a)).sum(dim=1)
+    purity = (c.to(torch.float64) / (hi - lo + 1).to(torch.float64)).to(torch.float32)
+    keep = (truth >= 0) & ~(purity < torch.tensor(float(min_purity), dtype=torch.float32, device=dev))
+    weight = torch.where(keep, torch.ones_like(purity) if uniform else purity, torch.zeros_like(purity))
+    k = truth.clamp_min(0)
+    labelled = (truth >= 0)[:, None]
+    scales = KEY_SCALES.to(device=dev, dtype=torch.float32)
+    eye = lambda n, i: (torch.arange(n, device=dev)[None, :] == i[:, None]) & labelled
+    return {"truth": truth.to(torch.int32), "purity": purity,
+            "key_labels": torch.where(labelled, scales[k], torch.zeros((), device=dev)),
+            "tonic_labels": eye(12, k % 12).to(torch.float32), "key_signature_id": eye(24, k).to(torch.float32),
+            "sample_weight": weight, "seq_length": torch.full((len(rec),), wf, dtype=torch.int64, device=dev)}
+
+
+def weighted_general_step(key_out, tonic_out, genre_out, key_labels, tonic_labels, genre_labels, key_signature_id, sample_weight,
+                          weights=(1.0, 1.0, 0.1), use_cos=False, grads=False):
+    """``general_step``'s loss and nine metrics with a weight per row -> the 10 scalars in ``general_step``'s order, and with
+    ``grads=True`` also ``(d_key, d_tonic, d_genre)``, the loss's derivatives written out: the formulas of
+    ``ake_general_step_weighted_f32`` in torch ops, in the outputs' dtype (float64 inputs give the test model; the loss is
+    differentiable, which is what ``PitchClassNet.general_step`` uses off the fused path).
+
+    With ``w_i >= 0`` the weights, ``Wsum`` their sum and ``m_i`` the genre mask (the row's one-hot label sums to 1)::
+
+        loss = key_w * sum_i w_i sum_j BCE_ij / (12 Wsum) + tonic_w * sum_i w_i CE_i / Wsum
+               + genre_w * sum_i w_i m_i CE_i / sum_i w_i m_i        (0 when that denominator is 0)
+               [+ 1 - sum_i w_i cos_i / Wsum]                        (use_cos)
+
+    The metrics are the same weighted means; ``other`` is 1 minus the four categories.  Rows with ``w_i = 0`` contribute exact zeros
+    whatever they hold (NaN included); ``Wsum = 0`` gives zeros everywhere.  ``genre_out`` None: no genre term, accuracy_genre 0."""
+    import torch.nn.functional as F
+    dt, dev = key_out.dtype, key_out.device
+    w = torch.as_tensor(sample_weight, device=dev).to(dt).reshape(-1)
+    live = w > 0
+    w = torch.where(live, w, torch.zeros_like(w))
+    row = live[:, None]
+    # rows that do not count are replaced by harmless values before anything is computed: whatever they hold stays out of every sum
+    key = torch.where(row, key_out, torch.full_like(key_out, 0.5))
+    tonic = torch.where(row, tonic_out, torch.zeros_like(tonic_out))
+    y = torch.where(row, key_labels.to(device=dev, dtype=dt), torch.zeros((), dtype=dt, device=dev))
+    tl = torch.where(row, tonic_labels.to(dev).long(), torch.zeros((), dtype=torch.int64, device=dev))
+    sig = torch.where(row, key_signature_id.to(dev), torch.zeros((), dtype=key_signature_id.dtype, device=dev))
+    t_idx = torch.argmax(tl, dim=1)
+    wsum = w.sum()
+    inv = torch.where(wsum > 0, 1.0 / wsum.clamp_min(torch.finfo(dt).tiny), torch.zeros_like(wsum))
+    bce = F.binary_cross_entropy(key, y, reduction="none").sum(dim=1)
+    ce = F.cross_entropy(tonic, t_idx, reduction="none")
+    kw, tw, gw = (float(v) for v in weights)
+    loss = kw * (w * bce).sum() * inv / 12.0 + tw * (w * ce).sum() * inv
+    acc_genre = torch.zeros((), dtype=dt, device=dev)
+    if genre_out is not None:
+        genre = torch.where(row, genre_out, torch.zeros_like(genre_out))
+        gl = torch.where(row, genre_labels.to(dev).long(), torch.zeros((), dtype=torch.int64, device=dev))
+        g_idx = torch.argmax(gl, dim=1)
+        wm = w * (gl.sum(dim=1) == 1).to(dt)
+        cnt = wm.sum()
+        inv_g = torch.where(cnt > 0, 1.0 / cnt.clamp_min(torch.finfo(dt).tiny), torch.zeros_like(cnt))
+        ce_g = F.cross_entropy(genre, g_idx, reduction="none")
+        loss = loss + gw * (wm * ce_g).sum() * inv_g
+        acc_genre = (wm * (torch.argmax(genre, dim=1) == g_idx).to(dt)).sum() * inv_g
+    if use_cos:
+        cos = F.cosine_similarity(key, y, dim=1)
+        loss = loss + torch.where(wsum > 0, 1.0 - (w * cos).sum() * inv, torch.zeros_like(wsum))
+    with torch.no_grad():
+        correct, fifths, relative, parallel, _, full = mirex_categories(y, key, tl, tonic, sig)
+        mean = lambda m: (w * m.to(dt)).sum() * inv
+        c, f, r, p = mean(correct), mean(fifths), mean(relative), mean(parallel)
+        other = torch.where(wsum > 0, 1.0 - c - f - r - p, torch.zeros_like(wsum))
+        tonic_ok = mean(torch.argmax(tonic, dim=1) == t_idx)
+        scalars = (loss, mean(full), 1.0 * c + 0.5 * f + 0.3 * r + 0.2 * p, c, f, r, p, other, tonic_ok, acc_genre)
+        if not grads:
+            return scalars
+        d_key = kw * (w * inv)[:, None] * (key - y) / ((1.0 - key) * key).clamp_min(1e-12) / 12.0       # torch's binary_cross_entropy_backward
+        if use_cos:
+            pn, yn = key.norm(dim=1, keepdim=True).clamp_min(1e-8), y.norm(dim=1, keepdim=True).clamp_min(1e-8)
+            py = (key * y).sum(dim=1, keepdim=True)
+            d_key = d_key - (w * inv)[:, None] * (y / (pn * yn) - py * key / (pn ** 3 * yn))
+        d_tonic = tw * (w * inv)[:, None] * (torch.softmax(tonic, dim=1) - F.one_hot(t_idx, 12).to(dt))
+        d_genre = None
+        if genre_out is not None:
+            d_genre = gw * (wm * inv_g)[:, None] * (torch.softmax(genre, dim=1) - F.one_hot(g_idx, genre.shape[1]).to(dt))
+        return scalars, (d_key, d_tonic, d_genre)

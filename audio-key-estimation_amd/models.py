@@ -21,7 +21,7 @@ from torch import nn
 
 from . import _lib
 from .lightning_shim import LightningModule
-from .metrics import mirex_score as _mirex_score
+from .metrics import mirex_score as _mirex_score, weighted_general_step
 
 _VARIANT_FLAGS = ("only_semitones",)
 # opt.precision -> ake_pcnet_config::precision (include/ake_hip.h: AKE_PRECISION_MIXED / AKE_PRECISION_F32X3)
@@ -270,7 +270,8 @@ class _FusedGeneralStep(torch.autograd.Function):
     general_step's order; only element 0 (the loss) carries a gradient."""
 
     @staticmethod
-    def forward(ctx, key_out, tonic_out, genre_out, key_labels, tonic_labels, genre_labels, key_signature_id, weights, use_cos):
+    def forward(ctx, key_out, tonic_out, genre_out, key_labels, tonic_labels, genre_labels, key_signature_id, weights, use_cos,
+                sample_weight=None):
         dev = key_out.device
         B = key_out.shape[0]
         onehot = lambda t: _onehot_labels(t, dev)
@@ -285,13 +286,22 @@ class _FusedGeneralStep(torch.autograd.Function):
         scal = torch.empty(10, dtype=torch.float32, device=dev)
         grads = torch.empty((B, 35), dtype=torch.float32, device=dev) if need_grad else None
         ptr = lambda t: t.data_ptr() if t is not None else None
+        outs = (scal.data_ptr(), grads.data_ptr() if need_grad else None, grads.data_ptr() + 4 * B * 12 if need_grad else None,
+                grads.data_ptr() + 4 * B * 24 if need_grad and genre is not None else None)
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().ake_general_step_f32(
-                key.data_ptr(), tonic.data_ptr(), ptr(genre), kl.data_ptr(), tl.data_ptr(), tl64, ptr(gl), gl64, sl.data_ptr(), sl64, B,
-                weights[0], weights[1], weights[2], int(bool(use_cos)), scal.data_ptr(),
-                grads.data_ptr() if need_grad else None, grads.data_ptr() + 4 * B * 12 if need_grad else None,
-                grads.data_ptr() + 4 * B * 24 if need_grad and genre is not None else None, torch.cuda.current_stream().cuda_stream),
-                "ake_general_step_f32")
+            if sample_weight is None:
+                _lib.check(_lib.lib().ake_general_step_f32(
+                    key.data_ptr(), tonic.data_ptr(), ptr(genre), kl.data_ptr(), tl.data_ptr(), tl64, ptr(gl), gl64, sl.data_ptr(), sl64, B,
+                    weights[0], weights[1], weights[2], int(bool(use_cos)), *outs, torch.cuda.current_stream().cuda_stream),
+                    "ake_general_step_f32")
+            else:                                                        # a weight per row (TrackWindows batches)
+                sw = sample_weight.detach().to(device=dev, dtype=torch.float32).contiguous()
+                if sw.shape != (B,):
+                    raise ValueError(f"sample_weight must be ({B},), got {tuple(sw.shape)}")
+                _lib.check(_lib.lib().ake_general_step_weighted_f32(
+                    key.data_ptr(), tonic.data_ptr(), ptr(genre), kl.data_ptr(), tl.data_ptr(), tl64, ptr(gl), gl64, sl.data_ptr(), sl64, B,
+                    weights[0], weights[1], weights[2], int(bool(use_cos)), sw.data_ptr(), *outs, torch.cuda.current_stream().cuda_stream),
+                    "ake_general_step_weighted_f32")
         ctx.grads, ctx.B, ctx.has_genre, ctx.out_dtype = grads, B, genre is not None, key_out.dtype
         return scal
 
@@ -303,7 +313,7 @@ class _FusedGeneralStep(torch.autograd.Function):
         d_key = scaled[:B * 12].view(B, 12)
         d_tonic = scaled[B * 12:B * 24].view(B, 12)
         d_genre = scaled[B * 24:B * 35].view(B, 11) if ctx.has_genre else None
-        return d_key, d_tonic, d_genre, None, None, None, None, None, None
+        return d_key, d_tonic, d_genre, None, None, None, None, None, None, None
 
 
 class _FusedGeneralStepLocal(torch.autograd.Function):
@@ -927,8 +937,16 @@ class PitchClassNet(LightningModule):
             # the device path: one launch for the loss, its gradient and the metrics (a subclass that overrides mirex_score keeps the torch ops)
             weights = (float(_opt_get(opt, "key_weight", 1.0)), float(_opt_get(opt, "tonic_weight", 1.0)), float(_opt_get(opt, "genre_weight", 0.1)))
             vals = _FusedGeneralStep.apply(key_out, tonic_out, out[2] if self.genre else None, batch["key_labels"], batch["tonic_labels"],
-                                           batch["genre"] if self.genre else None, key_signature_id, weights, _opt_get(opt, "use_cos", False))
+                                           batch["genre"] if self.genre else None, key_signature_id, weights, _opt_get(opt, "use_cos", False),
+                                           batch.get("sample_weight"))
             return tuple(vals.unbind(0))
+        if batch.get("sample_weight") is not None:
+            # a weight per row off the device path: the formulas of ake_general_step_weighted_f32 in torch ops (metrics.weighted_general_step)
+            weights = (_opt_get(opt, "key_weight", 1.0), _opt_get(opt, "tonic_weight", 1.0), _opt_get(opt, "genre_weight", 0.1))
+            vals = weighted_general_step(key_out, tonic_out, out[2] if self.genre else None, batch["key_labels"], batch["tonic_labels"],
+                                         batch["genre"] if self.genre else None, key_signature_id, batch["sample_weight"], weights,
+                                         _opt_get(opt, "use_cos", False))
+            return (vals[0],) + tuple(v.float() for v in vals[1:])
         key_labels = batch["key_labels"].to(mel.dtype if mel.is_floating_point() else torch.float32)
         tonic_labels = batch["tonic_labels"].long()
         tonic_idx = torch.argmax(tonic_labels, dim=1)

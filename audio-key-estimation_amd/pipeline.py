@@ -359,13 +359,7 @@ class KeyEstimator:
         fits a ``transition`` to smooth tracks' own emissions; the same table scores it."""
         if posteriors and not smooth:
             raise ValueError("track(posteriors=True) needs smooth=True: the posteriors belong to the smoothed track's emissions and transition")
-        if self.frames <= 0:
-            raise ValueError("track() needs a fixed frame rate: this estimator was built with frames=0 (whole-song mode)")
-        if self.wrap_mode == "true_end":
-            raise ValueError("track() runs every window unpadded; wrap_mode 'true_end' has no meaning here: build the estimator with 'dataset_max'")
-        if getattr(self.net, "local", False):
-            raise ValueError("track() slides a clip-level net over the recording: a --local net is not tracked "
-                             "(it has its own per-frame forward, and its rows are not time frames)")
+        self._refuse_untrackable()
         self.net._sync_weights(self.device, for_eval=True)
         if audio.dim() == 3 or (rate is not None and int(rate) != self.sample_rate):
             rs = get_resampler(self.sample_rate if rate is None else int(rate), self.sample_rate, self.device)
@@ -376,6 +370,55 @@ class KeyEstimator:
         # (made on the caller's stream, which every side stream waits for before it runs the call)
         smoothing = (self._transition(sf, mean_key_seconds, transition), float(signature_weight), bool(posteriors)) if smooth else None
         return self._issue(lambda slot, a, l: self._run_track(slot, a, l, wf, sf, smoothing), audio, lengths)
+
+    def _refuse_untrackable(self):
+        """What ``track`` and ``training_windows`` cannot slide windows over."""
+        if self.frames <= 0:
+            raise ValueError("track() needs a fixed frame rate: this estimator was built with frames=0 (whole-song mode)")
+        if self.wrap_mode == "true_end":
+            raise ValueError("track() runs every window unpadded; wrap_mode 'true_end' has no meaning here: build the estimator with 'dataset_max'")
+        if getattr(self.net, "local", False):
+            raise ValueError("track() slides a clip-level net over the recording: a --local net is not tracked "
+                             "(it has its own per-frame forward, and its rows are not time frames)")
+
+    @torch.no_grad()
+    def training_windows(self, audio: torch.Tensor, annotations: KeyAnnotations, lengths: torch.Tensor | None = None, rate: int | None = None,
+                         channel: int = 0, window_seconds: float = 15.0, batch_size: int = 8, batches_per_epoch: int | None = None,
+                         stride_seconds: float | None = None, seed: int = 0, weighting: str = "purity", min_purity: float = 0.0):
+        """Training batches cut from annotated recordings on the device -> ``ake_amd.TrackWindows``, which
+        ``Trainer.fit(net, train_dataloaders=...)`` takes as it takes a ``DataLoader``.
+
+        ``audio``, ``lengths``, ``rate`` and ``channel`` mean what they mean in ``track`` (int16 is 16-bit PCM), and the windows are
+        ``track``'s: every recording is transformed ONCE at the estimator's hop, here and now, and the transform stays on the device
+        (``T_i = 1 + lengths[i] // hop`` frames); a window is ``1 + round(window_seconds * sample_rate) // hop`` consecutive frames of
+        it, so its edge frames have seen the neighbouring audio, as the windows ``track`` feeds the net have.  ``annotations``
+        (``KeyAnnotations``, in samples at the estimator's rate) give every window its labels and its weight.
+
+        ``stride_seconds=None``: every epoch draws ``batches_per_epoch`` batches of ``batch_size`` windows at random start frames, from
+        ``seed`` and the epoch.  ``stride_seconds`` given: ``track``'s own windows at that stride, in order (for validation).
+        ``weighting`` and ``min_purity``: see ``TrackWindows``.  Refused with a ``ValueError``: what ``track`` refuses, annotations of
+        another number of recordings or another sample rate, and recordings none of which holds one window.  The lengths are read on
+        the host once, here; iterating the result waits for nothing."""
+        from .windows import TrackWindows
+        self._refuse_untrackable()
+        if annotations.sample_rate and annotations.sample_rate != self.sample_rate:
+            raise ValueError(f"training_windows: the annotations are in samples at {annotations.sample_rate} Hz, the estimator runs at {self.sample_rate} Hz")
+        if annotations.seg_start.shape[0] != audio.shape[0]:
+            raise ValueError(f"training_windows: {audio.shape[0]} recordings, but annotations of {annotations.seg_start.shape[0]}")
+        if audio.dim() == 3 or (rate is not None and int(rate) != self.sample_rate):
+            rs = get_resampler(self.sample_rate if rate is None else int(rate), self.sample_rate, self.device)
+            audio, len_out = rs(audio, channel=channel, lengths=lengths)
+            lengths = len_out if lengths is not None else None
+        hop = self.plan.hop_length
+        mel = self.plan.logmag(audio, lengths=lengths)                                       # (R, P, T), zeros behind a recording's end
+        T = mel.shape[2]
+        frames = [T] * mel.shape[0] if lengths is None else [min(1 + int(n) // hop, T) for n in torch.as_tensor(lengths).reshape(-1).tolist()]
+        wf = track_window_frames(int(round(window_seconds * self.sample_rate)), hop)
+        if T < wf:
+            raise ValueError("training_windows: no recording is as long as one window")
+        sf = None if stride_seconds is None else track_stride_frames(stride_seconds, self.frames)
+        return TrackWindows(mel, frames, annotations, hop, wf, batch_size=batch_size, batches_per_epoch=batches_per_epoch, stride_frames=sf,
+                            seed=seed, weighting=weighting, min_purity=min_purity, genre_classes=11 if self.net.genre else 8)
 
     def _transition(self, sf, mean_key_seconds, transition):
         """The (24, 24) float32 log transition matrix on the device: built and validated once per (stride, mean_key_seconds) or per

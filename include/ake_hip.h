@@ -297,6 +297,20 @@ int ake_general_step_f32(const float* key_out_dev, const float* tonic_out_dev, c
                          const void* key_signature_id_dev, int key_signature_i64, int batch, float key_weight, float tonic_weight,
                          float genre_weight, int use_cos, float* scalars_out_dev, float* d_key_dev, float* d_tonic_dev, float* d_genre_dev,
                          ake_stream_t stream);
+/* The same with a weight per row: sample_weight_dev [batch] float32, values >= 0 (anything else counts as 0), nullable.  NULL runs
+ * ake_general_step_f32's arithmetic, bit for bit.  Otherwise, with w_i the weights, Wsum = sum_i w_i and m_i the genre mask:
+ *   loss = key_weight * sum_i w_i sum_j BCE_ij / (12 Wsum) + tonic_weight * sum_i w_i CE_i / Wsum
+ *          + genre_weight * sum_i w_i m_i CE_i / sum_i w_i m_i   (an exact 0 when that denominator is 0)
+ *          [+ 1 - sum_i w_i cos_i / Wsum with use_cos]
+ * the nine metrics are the same weighted means (`other` = 1 - the four categories; accuracy_genre over sum_i w_i m_i), and d_*_dev the
+ * derivatives of exactly this loss.  A row with w_i = 0 is not read: it contributes exact zeros to the loss, the metrics and its own
+ * gradient rows, whatever its outputs and labels hold.  Wsum = 0: all ten scalars and all gradients are exact zeros.  One launch, double
+ * sums in a fixed-order tree, no atomics: bit-reproducible.  Under data-parallel training every rank normalises by its own Wsum. */
+int ake_general_step_weighted_f32(const float* key_out_dev, const float* tonic_out_dev, const float* genre_out_dev, const float* key_labels_dev,
+                                  const void* tonic_labels_dev, int tonic_labels_i64, const void* genre_labels_dev, int genre_labels_i64,
+                                  const void* key_signature_id_dev, int key_signature_i64, int batch, float key_weight, float tonic_weight,
+                                  float genre_weight, int use_cos, const float* sample_weight_dev, float* scalars_out_dev, float* d_key_dev,
+                                  float* d_tonic_dev, float* d_genre_dev, ake_stream_t stream);
 
 /* general_step of a --local net (models.py:861-876, 898-909): per-frame outputs key_out (after the sigmoid) and tonic_out (logits),
  * [batch][out_frames][12] as the forward returns them; labels with their own row count, key_labels [batch][label_frames][12] float32,
@@ -513,6 +527,41 @@ int ake_track_score_i32(const int32_t* pred_dev, const int32_t* counts_dev, cons
                         const int32_t* seg_count_dev, int recordings, int windows, int max_segments, int hop, int window_frames,
                         int stride_frames, int32_t* truth_dev, int32_t* category_dev, int32_t* tally_dev, int32_t* changes_dev,
                         ake_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Training batches from annotated recordings, assembled on the device: window positions from a counter-based generator, the windows
+ * gathered from the recordings' cached transforms (one CQT per recording, as the track makes it), their labels and a weight per window
+ * from the annotations.  Two launches per batch, no host round trip.  Host models: metrics.draw_windows / metrics.window_labels.
+ * ---------------------------------------------------------------------------------------- */
+/* `batch` window positions, one launch, one thread per slot, integers only (identical to a Python-int restatement).  The population:
+ * every start frame of every recording that is long enough, prefix_dev[i] (int64 [recordings + 1], device) = the exclusive sum of
+ * max(0, T_i - window_frames + 1), N = prefix_dev[recordings].  Slot j = first_slot + b takes one Philox4x32-10 block (the synthesiser's
+ * generator) with counter (j low 32, j high 32, epoch, 0x57494E44) and key (seed low, seed high); x = word0 | word1 << 32,
+ * index = (x * N) >> 64, recording_out_dev[b] = the last i < recordings with prefix[i] <= index, start_out_dev[b] = index - prefix[i].
+ * So a slot's draw depends on (seed, epoch, j) alone, not on how the slots are split into calls.  N > 0 is the caller's contract: N lives
+ * in device memory, where this entry cannot see it without waiting for the stream (ake_amd checks it where the lengths are known, on the
+ * host); with N <= 0 both outputs get -1.  AKE_ERR_INVALID for recordings < 1, batch < 0 or first_slot < 0. */
+int ake_draw_windows_i32(const int64_t* prefix_dev, int recordings, uint64_t seed, uint32_t epoch, int64_t first_slot, int batch,
+                         int32_t* recording_out_dev, int32_t* start_out_dev, ake_stream_t stream);
+/* One launch: window b = frames [start_dev[b], start_dev[b] + window_frames) of recording recording_dev[b] (both int32 [batch], device),
+ * copied out of mel_dev -- [recordings][total_frames][pitches] (frames_major != 0) or [recordings][pitches][total_frames] -- into
+ * mel_out_dev [batch][1][pitches][window_frames], with the window's labels.  The host cannot see the list: entries are read clamped
+ * (recording to 0..recordings-1, start to 0..total_frames-window_frames), so every load stays inside mel_dev and the annotations whatever
+ * the list holds; results for out-of-range entries are unspecified.  batch <= 65535.
+ * Labels, from the annotations of ake_track_score_i32 (seg_start_dev, seg_key_dev, seg_count_dev, max_segments) with its geometry at the
+ * window's own start: lo = start * hop, hi = (start + window_frames - 1) * hop, centre = (2 * start + window_frames - 1) * hop / 2;
+ *   truth      the key of the last segment that starts at or before centre (-1: none, or unlabelled)
+ *   purity     float32(double(c) / double(hi - lo + 1)), c = the samples of lo..hi inside segments that carry truth
+ *   weight     0 if truth < 0 or purity < min_purity, else 1 (uniform != 0) or purity
+ *   key_labels_dev [batch][12] the scale of key truth, tonic_labels_dev [batch][12] one-hot at truth mod 12, key_signature_id_dev
+ *   [batch][24] one-hot at truth (all three zeros for truth < 0), seq_length_dev [batch] int64 = window_frames, weight_dev [batch].
+ * The three annotation pointers and the five label outputs are passed all together or all NULL (gather only); mel_out_dev NULL: labels
+ * only (mel_dev is then not read). */
+int ake_window_batch_f32(const float* mel_dev, int frames_major, int recordings, int total_frames, int pitches, int window_frames, int hop,
+                         const int32_t* recording_dev, const int32_t* start_dev, int batch, const int64_t* seg_start_dev,
+                         const int32_t* seg_key_dev, const int32_t* seg_count_dev, int max_segments, float min_purity, int uniform,
+                         float* mel_out_dev, float* key_labels_dev, float* tonic_labels_dev, float* key_signature_id_dev,
+                         int64_t* seq_length_dev, float* weight_dev, ake_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Additive synthesiser: recordings from lists of enveloped sinusoidal partials plus Gaussian noise, peak-normalised, float32, ragged.
