@@ -394,12 +394,27 @@ struct ConvGeom {            // explicit geometry for the data-gradient convolut
     int py, pad_l, T_out, H_out, time_circ;
 };
 
+// One thread per element: `total` items in workgroups of 256 threads, timed under `label`.
+template <class... P, class... A>
+void launch_flat(const char* label, void (*kernel)(P...), hipStream_t s, long long total, A... args) {
+    ake::ProfScope ps(label, s);
+    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, static_cast<P>(args)...);
+}
+
+// What only some callers of run_conv set (the defaults are the inference forward's)
+struct ConvOpts {
+    const float* in_affine = nullptr;   // training: the input's pending [cin][3] table, applied on load
+    double* stats = nullptr;            // training: the raw output's per-channel statistics land here
+    const ConvGeom* geom = nullptr;     // padding and output size given outright instead of derived from `kind`
+    bool accumulate = false;            // dst += instead of dst =
+    const float* residual = nullptr;    // dense [B][cout][H_out][T_out], added before the LeakyReLU
+    bool rows_zero = false;             // rows beyond the map are zeros, not wrapped
+};
+
 // One convolution of the net.  `kind`: 0 pitch conv (7x7 circular both axes), 1 equivariant pitch-class
 // conv (12 x k, rows circular), 2 genre conv (kh in {1,2}, rows valid).
 int run_conv(const ake_pcnet* n, const PackedConv& pc, int kind, Src src, int batch, int H, int T_in, bool same_time,
-             bool lrelu, float* dst, int dst_ctot, int dst_coff, hipStream_t s, const char* name,
-             const float* in_affine = nullptr, double* stats = nullptr, const ConvGeom* geom = nullptr, bool accumulate = false,
-             const float* residual = nullptr, bool rows_zero = false) {
+             bool lrelu, float* dst, int dst_ctot, int dst_coff, hipStream_t s, const char* name, const ConvOpts& o = {}) {
     ConvArgs a;
     std::memset(&a, 0, sizeof(a));
     AKE_REQUIRE(pc.kw == 7 || pc.kw == 5 || pc.kw == 3 || pc.row_k, AKE_ERR_UNSUPPORTED, "conv: kernel width %d not built (3, 5, 7)", pc.kw);
@@ -407,7 +422,7 @@ int run_conv(const ake_pcnet* n, const PackedConv& pc, int kind, Src src, int ba
     a.src0 = src.p0; a.c0 = src.c0; a.src1 = src.p1; a.c1 = src.c1; a.h1 = src.h1 > 0 ? src.h1 : 1;
     a.H = H; a.T_in = T_in;
     a.src0_clip_stride = static_cast<long long>(src.ctot0 > 0 ? src.ctot0 : src.c0) * H * T_in;
-    a.rows_zero = rows_zero ? 1 : 0;
+    a.rows_zero = o.rows_zero ? 1 : 0;
     a.src1_clip_stride = static_cast<long long>(src.c1) * a.h1 * T_in;
     const bool fullrows = kind != 0;
     if (kind == 0) { a.py = pc.kh / 2; a.pad_l = pc.kw / 2; a.time_circ = 1; a.T_out = T_in; a.H_out = H; }
@@ -417,13 +432,13 @@ int run_conv(const ake_pcnet* n, const PackedConv& pc, int kind, Src src, int ba
         a.T_out = same_time ? T_in : T_in - pc.kw + 1;
         a.H_out = kind == 1 ? H : H - pc.kh + 1;
     }
-    if (geom) { a.py = geom->py; a.pad_l = geom->pad_l; a.T_out = geom->T_out; a.H_out = geom->H_out; a.time_circ = geom->time_circ; }
+    if (o.geom) { a.py = o.geom->py; a.pad_l = o.geom->pad_l; a.T_out = o.geom->T_out; a.H_out = o.geom->H_out; a.time_circ = o.geom->time_circ; }
     AKE_REQUIRE(a.T_out > 0, AKE_ERR_INVALID, "conv %s: %d frames is too short for the valid head convolutions", name, T_in);
     a.w = n->blob_dev + pc.w_off; a.bias = n->blob_dev + pc.b_off; a.cout = pc.cout;
     a.dst = dst; a.dst_coff = dst_coff; a.dst_clip_stride = static_cast<long long>(dst_ctot) * a.H_out * a.T_out;
     a.lrelu = lrelu ? 1 : 0;
-    a.in_affine = in_affine; a.stats = stats; a.stats_stride = 2 * n->bn_channels; a.accumulate = accumulate ? 1 : 0;
-    a.residual = residual; a.residual_clip_stride = static_cast<long long>(pc.cout) * a.H_out * a.T_out;      // dense [B][cout][H][T]
+    a.in_affine = o.in_affine; a.stats = o.stats; a.stats_stride = 2 * n->bn_channels; a.accumulate = o.accumulate ? 1 : 0;
+    a.residual = o.residual; a.residual_clip_stride = static_cast<long long>(pc.cout) * a.H_out * a.T_out;      // dense [B][cout][H][T]
     Tile t;
     MTile mtile;
     constexpr int MT = 3;
@@ -768,8 +783,13 @@ P2pX3Plan p2p_f16x3_plan(int c0, int c1, int cout, int batch, int H, int T, bool
     return g;
 }
 
+struct P2pX3Opts {
+    const unsigned int* in_amax = nullptr;   // data gradients: the bits of the input's largest |value| (see run_nchw_to_cl16_f16x2)
+    bool lrelu = false;                      // f32x3 inference: LeakyReLU on the output
+};
+
 int run_p2p_f16x3(const ake_pcnet* n, const P2pX3Plan& g, long long frag_off, const Src& src, const float* in_aff, const float* bias, int batch, int H, int T,
-                  float* dst, int cout, double* stats, int stats_stride, hipStream_t s, const char* name, const unsigned int* in_amax = nullptr, bool lrelu = false) {
+                  float* dst, int cout, double* stats, int stats_stride, hipStream_t s, const char* name, const P2pX3Opts& o = {}) {
     AKE_REQUIRE(g.ok && frag_off >= 0 && src.ctot0 == 0, AKE_ERR_STATE, "conv %s: a convolution that does not qualify was sent to the f16 x 3 persistent kernel", name);
     AKE_REQUIRE(g.n_tiles == g.n_row_tiles * batch, AKE_ERR_STATE, "conv %s: the f16 x 3 persistent kernel was planned for another batch than these %d clips", name, batch);
     AKE_REQUIRE(!(reinterpret_cast<uintptr_t>(dst) & 15), AKE_ERR_STATE, "conv %s: the f16 x 3 persistent kernel was planned for 16-byte stores to an unaligned tensor", name);
@@ -782,7 +802,7 @@ int run_p2p_f16x3(const ake_pcnet* n, const P2pX3Plan& g, long long frag_off, co
     a.p = src.p0; a.c0 = src.c0; a.u = src.p1 ? src.p1 : src.p0; a.c1 = src.p1 ? src.c1 : 0; a.h1 = src.h1 > 0 ? src.h1 : 1;
     a.in_aff = in_aff; a.bfrag = n->bf_frags_dev + frag_off; a.bias = bias;
     a.dst = dst; a.dst_clip_stride = static_cast<long long>(cout) * H * T; a.cout = cout;
-    a.stats = stats; a.stats_stride = stats_stride; a.in_amax = in_amax; a.lrelu = lrelu ? 1 : 0;
+    a.stats = stats; a.stats_stride = stats_stride; a.in_amax = o.in_amax; a.lrelu = o.lrelu ? 1 : 0;
     static ake::DeviceOnce attr_set;
     if (attr_set.need()) {
         AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_p2p_f16x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -794,21 +814,18 @@ int run_p2p_f16x3(const ake_pcnet* n, const P2pX3Plan& g, long long frag_off, co
     return AKE_OK;
 }
 
-// semitone maps [clip][C][S][T] -> channels [coff, coff + C) of the concat buffer [clip][ctot][12][T]: max over the octaves
-int run_fold_max(const float* smap, int C, int S, int batch, int T, float* dst, int dst_ctot, int dst_coff, hipStream_t s) {
+// semitone maps [clip][C][S][T] (aff: raw, with their pending table) -> channels [coff, coff + C) of the concat buffer
+// [clip][ctot][12][T]: max over the octaves
+int run_fold_max(const char* label, const float* smap, const float* aff, int C, int S, int batch, int T, float* dst, int dst_ctot, int dst_coff, hipStream_t s) {
     const long long total = static_cast<long long>(batch) * C * 12 * T;
-    ake::ProfScope ps("fold_max_kernel", s);
-    hipLaunchKernelGGL(fold_max_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, smap, C, S, T, dst,
-                       static_cast<long long>(dst_ctot) * 12 * T, dst_coff, total);
+    launch_flat(label, fold_max_kernel, s, total, smap, aff, C, S, T, dst, static_cast<long long>(dst_ctot) * 12 * T, dst_coff, total);
     return AKE_OK;
 }
 
 // NCHW f32 [clip][C][12][T] -> channels-last split planes [clip][12][T][16] (hi plane, then lo plane, at `planes`)
 int run_nchw_to_cl16(const float* src, int C, int batch, int T, unsigned short* planes, hipStream_t s) {
     const long long npos = static_cast<long long>(batch) * 12 * T;
-    ake::ProfScope ps("nchw_to_cl16_kernel", s);
-    hipLaunchKernelGGL(nchw_to_cl16_kernel, dim3(static_cast<unsigned>((npos + 255) / 256)), dim3(256), 0, s, src, static_cast<long long>(C) * 12 * T, C, T,
-                       planes, planes + npos * 16, npos);
+    launch_flat("nchw_to_cl16_kernel", nchw_to_cl16_kernel, s, npos, src, static_cast<long long>(C) * 12 * T, C, T, planes, planes + npos * 16, npos);
     return AKE_OK;
 }
 
@@ -859,16 +876,22 @@ bool pc_f16x3_ok(const PackedConv& pt, int T_in, bool same_time) {
 void run_nchw_to_cl16_f16x2(const float* src, int C, int batch, int T, const float* aff, unsigned short* planes, hipStream_t s, int src_ctot = 0,
                             const unsigned int* amax = nullptr) {
     const long long npos = static_cast<long long>(batch) * 12 * T;
-    ake::ProfScope ps("nchw_to_cl16_f16x2_kernel", s);
-    hipLaunchKernelGGL(nchw_to_cl16_f16x2_kernel, dim3(static_cast<unsigned>((npos + 255) / 256)), dim3(256), 0, s, src, static_cast<long long>(src_ctot > 0 ? src_ctot : C) * 12 * T, C, T,
-                       aff, planes, planes + npos * 16, npos, amax);
+    launch_flat("nchw_to_cl16_f16x2_kernel", nchw_to_cl16_f16x2_kernel, s, npos, src, static_cast<long long>(src_ctot > 0 ? src_ctot : C) * 12 * T, C, T, aff, planes,
+                planes + npos * 16, npos, amax);
 }
+
+struct PcBf16Opts {
+    const PackedConv* pc2 = nullptr;         // a second convolution of the same geometry over the same input, written to planes_out2
+    unsigned short* planes_out2 = nullptr;
+    bool f16x3 = false;                      // training / data gradients: f16 hi / lo planes in, f32-equivalent products, NCHW f32 out
+    double* stats = nullptr;                 // f16x3: the raw output's per-channel statistics
+    int stats_stride = 0;
+    const unsigned int* in_amax = nullptr;   // f16x3 data gradients: the bits of the input's largest |value| (see run_nchw_to_cl16_f16x2)
+};
 
 // pitch-class convolution on bf16 MFMA (conv_pc_bf16_kernel): channels-last planes in; planes (cout == 16) or NCHW f32 out
 int run_pc_bf16(const ake_pcnet* n, const PackedConv& pc, const unsigned short* planes_in, int batch, int T_in, bool same_time, bool lrelu,
-                float* dst_nchw, unsigned short* planes_out, hipStream_t s, const char* name, const PackedConv* pc2 = nullptr,
-                unsigned short* planes_out2 = nullptr, bool f16x3 = false, double* stats = nullptr, int stats_stride = 0,
-                const unsigned int* in_amax = nullptr) {
+                float* dst_nchw, unsigned short* planes_out, hipStream_t s, const char* name, const PcBf16Opts& o = {}) {
     PcBfArgs a;
     std::memset(&a, 0, sizeof(a));
     const long long npos_in = static_cast<long long>(batch) * 12 * T_in;
@@ -883,14 +906,14 @@ int run_pc_bf16(const ake_pcnet* n, const PackedConv& pc, const unsigned short* 
     a.dst = dst_nchw; a.dst_clip_stride = static_cast<long long>(pc.cout) * H_out * a.T_out;
     a.cl_stride = pc.cout;
     if (planes_out) { a.oh = planes_out; a.ol = planes_out + static_cast<long long>(batch) * H_out * a.T_out * pc.cout; }
-    if (pc2) {   // a second convolution of the same geometry over the same input, as blockIdx.y == 1 (planes out only)
-        AKE_REQUIRE(planes_out && planes_out2 && pc2->cout == pc.cout && pc2->kh == pc.kh && pc2->kw == pc.kw && pc2->cin == pc.cin && pc2->bf_off >= 0,
+    if (o.pc2) {   // a second convolution of the same geometry over the same input, as blockIdx.y == 1 (planes out only)
+        AKE_REQUIRE(planes_out && o.planes_out2 && o.pc2->cout == pc.cout && o.pc2->kh == pc.kh && o.pc2->kw == pc.kw && o.pc2->cin == pc.cin && o.pc2->bf_off >= 0,
                     AKE_ERR_STATE, "conv %s: the paired convolution differs in shape", name);
-        a.bfrag2 = n->bf_frags_dev + pc2->bf_off; a.bias2 = n->blob_dev + pc2->b_off;
-        a.oh2 = planes_out2; a.ol2 = planes_out2 + static_cast<long long>(batch) * H_out * a.T_out * pc.cout;
+        a.bfrag2 = n->bf_frags_dev + o.pc2->bf_off; a.bias2 = n->blob_dev + o.pc2->b_off;
+        a.oh2 = o.planes_out2; a.ol2 = o.planes_out2 + static_cast<long long>(batch) * H_out * a.T_out * pc.cout;
     }
-    a.stats = stats; a.stats_stride = stats_stride; a.in_amax = in_amax;
-    AKE_REQUIRE(!f16x3 || (dst_nchw && !planes_out && !pc2), AKE_ERR_STATE, "conv %s: the f16 x 3 form writes NCHW f32", name);
+    a.stats = o.stats; a.stats_stride = o.stats_stride; a.in_amax = o.in_amax;
+    AKE_REQUIRE(!o.f16x3 || (dst_nchw && !planes_out && !o.pc2), AKE_ERR_STATE, "conv %s: the f16 x 3 form writes NCHW f32", name);
     const size_t lds = (static_cast<size_t>(2) * 12 * a.Tp * 2 + 2 * 4 * ((pc.cout + 15) / 16) * 2 * 64) * sizeof(uint4);   // patch + weight ring
     AKE_REQUIRE(lds <= 150 * 1024, AKE_ERR_UNSUPPORTED, "conv %s: %d frames do not fit the bf16 kernel's LDS patch", name, T_in);
     static ake::DeviceOnce attr_set;
@@ -905,10 +928,10 @@ int run_pc_bf16(const ake_pcnet* n, const PackedConv& pc, const unsigned short* 
     }
     const int tiles = (H_out * a.T_out + 15) / 16;
     const int waves = std::min(8, (tiles + 3) / 4);
-    dim3 grid((tiles + waves * 4 - 1) / (waves * 4), pc2 ? 2 : 1, batch), block(waves * 64);
+    dim3 grid((tiles + waves * 4 - 1) / (waves * 4), o.pc2 ? 2 : 1, batch), block(waves * 64);
     ake::ProfScope ps(name, s);
-    if (f16x3 && pc.cout <= 16) hipLaunchKernelGGL((conv_pc_bf16_kernel<1, false, true>), grid, block, lds, s, a);
-    else if (f16x3) hipLaunchKernelGGL((conv_pc_bf16_kernel<2, false, true>), grid, block, lds, s, a);
+    if (o.f16x3 && pc.cout <= 16) hipLaunchKernelGGL((conv_pc_bf16_kernel<1, false, true>), grid, block, lds, s, a);
+    else if (o.f16x3) hipLaunchKernelGGL((conv_pc_bf16_kernel<2, false, true>), grid, block, lds, s, a);
     else if (pc.cout == 16 && planes_out) hipLaunchKernelGGL((conv_pc_bf16_kernel<1, true>), grid, block, lds, s, a);
     else if (pc.cout == 16) hipLaunchKernelGGL((conv_pc_bf16_kernel<1, false>), grid, block, lds, s, a);
     else if (planes_out) hipLaunchKernelGGL((conv_pc_bf16_kernel<2, true>), grid, block, lds, s, a);
@@ -949,14 +972,22 @@ int run_pc_f16x3_full(const ake_pcnet* n, long long frag_off, int kh, const unsi
     return AKE_OK;
 }
 
+// the semitone kernels' arguments: src [B][pc.cin][P][T]; dst: channels [coff, ..) of [B][ctot][12][T] (semi_fold_kernel) or the dense
+// semitone maps (semi_conv_stats_kernel, which reads neither ctot nor coff)
+SemiArgs semi_args(const ake_pcnet* n, const PackedConv& pc, const float* src, int P, int T, float* dst, int dst_ctot = 0, int dst_coff = 0) {
+    SemiArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.src = src; a.C = pc.cin; a.H = P; a.T = T;
+    a.src_clip_stride = static_cast<long long>(pc.cin) * P * T;
+    a.w = n->blob_dev + pc.w_off; a.bias = n->blob_dev + pc.b_off;
+    a.dst = dst; a.dst_coff = dst_coff; a.dst_clip_stride = static_cast<long long>(dst_ctot) * 12 * T;
+    a.n_strips = (T + TW - 1) / TW;
+    return a;
+}
+
 int run_semi(const ake_pcnet* n, const PackedConv& pc, const float* src, int batch, int H, int Tn, float* dst,
              int dst_ctot, int dst_coff, hipStream_t s, const char* name) {
-    SemiArgs a;
-    a.src = src; a.C = pc.cin; a.H = H; a.T = Tn;
-    a.src_clip_stride = static_cast<long long>(pc.cin) * H * Tn;
-    a.w = n->blob_dev + pc.w_off; a.bias = n->blob_dev + pc.b_off;
-    a.dst = dst; a.dst_coff = dst_coff; a.dst_clip_stride = static_cast<long long>(dst_ctot) * 12 * Tn;
-    a.n_strips = (Tn + TW - 1) / TW;
+    const SemiArgs a = semi_args(n, pc, src, H, Tn, dst, dst_ctot, dst_coff);
     const int per_clip = 12 * a.n_strips;
     const int threads = per_clip >= 256 ? 256 : (per_clip + 63) / 64 * 64;
     dim3 grid((per_clip + threads - 1) / threads, pc.groups, batch), block(threads);
@@ -970,6 +1001,12 @@ int run_semi(const ake_pcnet* n, const PackedConv& pc, const float* src, int bat
     return AKE_OK;
 }
 
+// A tensor and the pending BatchNorm + LeakyReLU table its readers apply while loading (null: the tensor is final), see Fwd
+struct Slot {
+    float* p = nullptr;
+    float* aff = nullptr;
+};
+
 struct Buffers {           // workspace carve
     // per chunk (pitch stream): everything up to the last layer's semitone fold
     float* fold0 = nullptr;
@@ -981,6 +1018,7 @@ struct Buffers {           // workspace carve
     // whole batch (pitch-class tail): last layer's concat buffer, its pc stack, pooled features, heads
     float *pcf = nullptr, *hid_k = nullptr, *hid_t = nullptr, *hid_g = nullptr;
     float *map_k = nullptr, *map_t = nullptr, *map_g = nullptr;
+    size_t hid_half = 0;    // floats of one of the two maps a head's hid_* buffer holds
     std::vector<int> Tl;    // frames at layer i
     int Tf = 0;             // frames after the last layer
     size_t bytes = 0;
@@ -1008,6 +1046,22 @@ struct Buffers {           // workspace carve
     // buffer of the widest bottleneck per block kind
     std::vector<std::vector<float*>> dn_bott_pc, dn_aff1_pc, dn_aff2_pc, dn_bott_p, dn_aff1_p, dn_aff2_p;
     float *dn_gbott_pc = nullptr, *dn_gbott_p = nullptr;
+
+    // Where conv j of a stack writes: training keeps every raw output next to its table (the backward pass reads all of them), inference
+    // ping-pongs between two buffers of final activations.  p_out: layer i's pitch stack, pc_out: its pitch-class stack, head_out: head
+    // h (key, tonic, genre), whose last conv writes the head's map (no BatchNorm); cat_slot: layer i's concat buffer.
+    Slot p_out(bool train, int i, int j) const { return train ? Slot{pst[i][j], aff_pst[i][j]} : Slot{(j & 1) ? pb[i] : pa[i], nullptr}; }
+    Slot pc_out(bool train, int i, int j) const { return train ? Slot{pcst[i][j], aff_pcst[i][j]} : Slot{(j & 1) ? pcb[i] : pca[i], nullptr}; }
+    Slot head_out(bool train, int h, int j, bool last) const {
+        float* const hid[3] = {hid_k, hid_t, hid_g};
+        float* const map[3] = {map_k, map_t, map_g};
+        if (last) return Slot{map[h], nullptr};
+        return train ? Slot{hst[h][j], aff_hst[h][j]} : Slot{hid[h] + (j & 1) * hid_half, nullptr};
+    }
+    Slot cat_slot(bool train, int i) const { return Slot{cat[i], train ? aff_cat[i] : nullptr}; }
+    // training: what layer i's pitch / pitch-class stack leaves (the last conv's raw output, or a --resblock stack's last block output)
+    Slot p_last(int i) const { return Slot{pst[i].back(), aff_pst[i].back()}; }
+    Slot pc_last(int i) const { return Slot{pcst[i].back(), aff_pcst[i].back()}; }
 };
 
 // chunk = clips per pitch-stream pass, batch = clips of the call (tail buffers)
@@ -1054,6 +1108,7 @@ int plan_buffers(const ake_pcnet* n, int batch, int chunk, int frames, void* ws,
     }
     b->pcf = cv.take<float>(B * n->final_ch * 12 * b->Tf);
     const size_t hid = B * 2 * n->final_ch * 12 * b->Tf;
+    b->hid_half = hid;
     b->hid_k = cv.take<float>(2 * hid); b->hid_t = cv.take<float>(2 * hid);
     b->feat_cl = cv.take<unsigned short>(B * 12 * b->Tf * 16 * 2);     // channels-last split copy of the head input (bf16 head convs)
     b->map_k = cv.take<float>(B * 12 * b->Tf); b->map_t = cv.take<float>(B * 12 * b->Tf);
@@ -2190,7 +2245,7 @@ namespace {
 
 // One forward pass.  In eval mode BatchNorm is folded into the convolutions and every tensor is final.  In training
 // mode a convolution followed by BatchNorm leaves its RAW output plus a pending (scale, shift, slope) table that the
-// next reader applies while loading: `aff` travels next to every tensor pointer below (null = nothing pending).
+// next reader applies while loading: the two travel together as a Slot (aff null = nothing pending), handed out by Buffers.
 struct Fwd {
     const ake_pcnet* n;
     Buffers& b;
@@ -2199,6 +2254,8 @@ struct Fwd {
     const Route& r;                  // what this call launches (build_route)
 
     int bn_of(const std::string& name) const { return n->bn_index.at(name); }
+    // training: the rows of layer i's pitch-stack input table that belong to the up_sixth map (they follow the pitch stream's prev_p rows)
+    float* p2pin_up(int i) const { return train ? b.aff_p2pin[i] + 3 * n->dims[i].prev_p : nullptr; }
 
     // launch BatchNorm finalisation of layer `bn` (count values per channel) into the affine table `aff_out`
     void finalize_bn(int bn, double count, float* aff_out, float slope = kSlope) {
@@ -2215,11 +2272,16 @@ struct Fwd {
     // conv (+BatchNorm `bn_name` + LeakyReLU unless bn_name is empty).  Returns via *aff_out_used whether dst is raw.
     int conv(const PackedConv& pe, const PackedConv& pt, const std::string& bn_name, int kind, Src src, const float* in_aff,
              int B, int H, int T_in, bool same, float* dst, int ctot, int coff, float* aff_dst, const char* name, const float* residual = nullptr) {
-        if (!train) return run_conv(n, pe, kind, src, B, H, T_in, same, !bn_name.empty(), dst, ctot, coff, s, name, nullptr, nullptr, nullptr, false, residual);
+        ConvOpts o;
+        if (!train) {
+            o.residual = residual;
+            return run_conv(n, pe, kind, src, B, H, T_in, same, !bn_name.empty(), dst, ctot, coff, s, name, o);
+        }
         const bool has_bn = !bn_name.empty();
         const int bn = has_bn ? bn_of(bn_name) : -1;
-        int rc = run_conv(n, pt, kind, src, B, H, T_in, same, false, dst, ctot, coff, s, name, in_aff,
-                          has_bn ? b.stats + 2 * n->bns[bn].ch_off : nullptr);
+        o.in_affine = in_aff;
+        if (has_bn) o.stats = b.stats + 2 * n->bns[bn].ch_off;
+        int rc = run_conv(n, pt, kind, src, B, H, T_in, same, false, dst, ctot, coff, s, name, o);
         if (rc) return rc;
         if (has_bn) {
             const int T_out = same ? T_in : T_in - pt.kw + 1;
@@ -2229,41 +2291,25 @@ struct Fwd {
         return AKE_OK;
     }
 
-    // --denseblock (models.py:584-648), inference: one block IN PLACE on feat [B][ctot][H][T] whose channels [0, cin) are filled; layer j
-    // reads channels [0, cin + j*nf) through its norm1 table, writes the bottleneck map to `bott`, and its k-wide convolution (input
-    // through the norm2 table, ReLU) appends nf channels at cin + j*nf.  kind 0: plain Conv2d -- 1 x 1, then k x k ZERO-padded on both
-    // axes; kind 1: equivariant 12 x 1 and 12 x k (rows circular, frames zero-padded).
-    int dense_stack(const std::vector<DensePack>& packs, int kind, float* feat, int ctot, int cin, int B, int H, int T, float* bott, const char* label) {
-        const int nf = n->cfg.n_filters, k = n->cfg.kernel_size;
-        int rc;
-        for (size_t j = 0; j < packs.size(); ++j) {
-            const DensePack& dp = packs[j];
-            const int cj = cin + static_cast<int>(j) * nf;
-            AKE_REQUIRE(dp.c1.cin == cj && cj + nf <= ctot, AKE_ERR_STATE, "dense %s: channel bookkeeping", label);
-            Src s1{feat, cj, nullptr, 0, 0, ctot};
-            const ConvGeom g1{0, 3, T, H, 0};                  // the single tap sits at offset 3 of the 7 stored
-            if ((rc = run_conv(n, dp.c1, kind, s1, B, H, T, true, false, bott, dp.c1.cout, 0, s, label, n->dense_aff_dev + dp.aff1, nullptr,
-                               kind == 0 ? &g1 : nullptr)))
-                return rc;
-            const ConvGeom g2{k / 2, k / 2, T, H, 0};
-            if ((rc = run_conv(n, dp.c2, kind, Src{bott, dp.c1.cout, nullptr, 0, 0}, B, H, T, true, false, feat, ctot, cj, s, label,
-                               n->dense_aff_dev + dp.aff2, nullptr, kind == 0 ? &g2 : nullptr, false, nullptr, kind == 0)))
-                return rc;
-        }
-        return AKE_OK;
-    }
-
-    // ... in TRAINING mode (batch statistics).  BatchNorm sits in FRONT of both convolutions here, so every norm1 needs the statistics of
-    // features other kernels produced: the block input's are taken by channel_stats_kernel, a layer's new features leave theirs in the NEXT
-    // layer's norm1 cells (conv2's statistics epilogue) and every later norm1 copies the prefix it shares (stats_copy_kernel).  The
-    // bottleneck maps and both tables of every layer stay in the workspace for the backward pass.
-    int dense_stack_train(const std::vector<DensePack>& packs, int kind, float* feat, int ctot, int cin, int B, int H, int T,
-                          const std::vector<float*>& botts, const std::vector<float*>& aff1s, const std::vector<float*>& aff2s, const char* label) {
+    // --denseblock (models.py:584-648): layer i's pitch block (kind 0) or pitch-class block (kind 1) IN PLACE on feat [B][ctot][H][T] whose
+    // channels [0, cin) are filled; dense layer j reads channels [0, cin + j*nf) through its norm1 table, writes the bottleneck map, and its
+    // k-wide convolution (input through the norm2 table, ReLU) appends nf channels at cin + j*nf.  kind 0: plain Conv2d -- 1 x 1, then
+    // k x k ZERO-padded on both axes; kind 1: equivariant 12 x 1 and 12 x k (rows circular, frames zero-padded).
+    // Inference: the tables are the folded ones of n->dense_aff_dev and every layer's bottleneck map goes to `bott`.
+    // Training (batch statistics): BatchNorm sits in FRONT of both convolutions here, so every norm1 needs the statistics of features other
+    // kernels produced: the block input's are taken by channel_stats_kernel, a layer's new features leave theirs in the NEXT layer's norm1
+    // cells (conv2's statistics epilogue) and every later norm1 copies the prefix it shares (stats_copy_kernel).  The bottleneck maps and
+    // both tables of every layer stay in the workspace (dn_*) for the backward pass.
+    int dense_stack(int i, int kind, float* feat, int ctot, int cin, int B, int H, int T, float* bott, const char* label) {
+        const std::vector<DensePack>& packs = kind == 0 ? n->dense_p[i] : n->dense_pc[i];
+        const auto& botts = kind == 0 ? b.dn_bott_p : b.dn_bott_pc;
+        const auto& aff1s = kind == 0 ? b.dn_aff1_p : b.dn_aff1_pc;
+        const auto& aff2s = kind == 0 ? b.dn_aff2_p : b.dn_aff2_pc;
         const int nf = n->cfg.n_filters, k = n->cfg.kernel_size;
         const double count = static_cast<double>(B) * H * T;
         const int sstride = 2 * n->bn_channels;
         int rc;
-        {
+        if (train) {
             ake::ProfScope ps("channel_stats_kernel", s);
             hipLaunchKernelGGL(channel_stats_kernel, dim3(cin, 1, B), dim3(256), 0, s, feat, static_cast<long long>(ctot) * H * T, static_cast<long long>(H) * T,
                                b.stats + 2 * n->bns[packs[0].bn1].ch_off, sstride);
@@ -2271,25 +2317,26 @@ struct Fwd {
         for (size_t j = 0; j < packs.size(); ++j) {
             const DensePack& dp = packs[j];
             const int cj = cin + static_cast<int>(j) * nf;
-            AKE_REQUIRE(dp.c1.cin == cj && cj + nf <= ctot && dp.bn1 >= 0 && dp.bn2 >= 0, AKE_ERR_STATE, "dense %s: channel bookkeeping (training)", label);
-            if (j > 0) {   // the statistics of channels [0, cj - nf): the previous norm1 has them (its own copy or the block input's)
+            AKE_REQUIRE(dp.c1.cin == cj && cj + nf <= ctot && (!train || (dp.bn1 >= 0 && dp.bn2 >= 0)), AKE_ERR_STATE, "dense %s: channel bookkeeping", label);
+            if (train && j > 0) {   // the statistics of channels [0, cj - nf): the previous norm1 has them (its own copy or the block input's)
                 const int C = cj - nf;
-                ake::ProfScope ps("stats_copy_kernel", s);
-                hipLaunchKernelGGL(stats_copy_kernel, dim3((kStatSlots * 2 * C + 255) / 256), dim3(256), 0, s, b.stats, sstride,
-                                   n->bns[packs[j - 1].bn1].ch_off, n->bns[dp.bn1].ch_off, C);
+                launch_flat("stats_copy_kernel", stats_copy_kernel, s, kStatSlots * 2 * C, b.stats, sstride, n->bns[packs[j - 1].bn1].ch_off, n->bns[dp.bn1].ch_off, C);
             }
-            finalize_bn(dp.bn1, count, aff1s[j], kSlope);                              // relu1 = nn.LeakyReLU
-            Src s1{feat, cj, nullptr, 0, 0, ctot};
-            const ConvGeom g1{0, 3, T, H, 0};
-            if ((rc = run_conv(n, dp.c1, kind, s1, B, H, T, true, false, botts[j], dp.c1.cout, 0, s, label, aff1s[j], b.stats + 2 * n->bns[dp.bn2].ch_off,
-                               kind == 0 ? &g1 : nullptr)))
-                return rc;
-            finalize_bn(dp.bn2, count, aff2s[j], 0.f);                                 // relu2 = nn.ReLU
+            if (train) finalize_bn(dp.bn1, count, aff1s[i][j], kSlope);                 // relu1 = nn.LeakyReLU
+            float* const bott_j = train ? botts[i][j] : bott;
+            const ConvGeom g1{0, 3, T, H, 0};                  // the single tap sits at offset 3 of the 7 stored
+            ConvOpts o1;
+            o1.in_affine = train ? aff1s[i][j] : n->dense_aff_dev + dp.aff1;
+            if (train) o1.stats = b.stats + 2 * n->bns[dp.bn2].ch_off;
+            if (kind == 0) o1.geom = &g1;
+            if ((rc = run_conv(n, dp.c1, kind, Src{feat, cj, nullptr, 0, 0, ctot}, B, H, T, true, false, bott_j, dp.c1.cout, 0, s, label, o1))) return rc;
+            if (train) finalize_bn(dp.bn2, count, aff2s[i][j], 0.f);                    // relu2 = nn.ReLU
             const ConvGeom g2{k / 2, k / 2, T, H, 0};
-            double* next_stats = j + 1 < packs.size() ? b.stats + 2 * (n->bns[packs[j + 1].bn1].ch_off + cj) : nullptr;
-            if ((rc = run_conv(n, dp.c2, kind, Src{botts[j], dp.c1.cout, nullptr, 0, 0}, B, H, T, true, false, feat, ctot, cj, s, label, aff2s[j], next_stats,
-                               kind == 0 ? &g2 : nullptr, false, nullptr, kind == 0)))
-                return rc;
+            ConvOpts o2;
+            o2.in_affine = train ? aff2s[i][j] : n->dense_aff_dev + dp.aff2;
+            if (train && j + 1 < packs.size()) o2.stats = b.stats + 2 * (n->bns[packs[j + 1].bn1].ch_off + cj);
+            if (kind == 0) { o2.geom = &g2; o2.rows_zero = true; }
+            if ((rc = run_conv(n, dp.c2, kind, Src{bott_j, dp.c1.cout, nullptr, 0, 0}, B, H, T, true, false, feat, ctot, cj, s, label, o2))) return rc;
         }
         return AKE_OK;
     }
@@ -2334,18 +2381,15 @@ struct Fwd {
             if ((rc = conv(st[1 + 2 * r], st[1 + 2 * r], bp + "b1", kind, Src{x, C, nullptr, 0, 0}, x_aff, B, H, T, true, z1, 2 * C, 0, aff[1 + 3 * r], label)))
                 return rc;
             const int bn2 = bn_of(bp + "b2");
-            if ((rc = run_conv(n, st[2 + 2 * r], kind, Src{z1, 2 * C, nullptr, 0, 0}, B, H, T, true, false, z2, C, 0, s, label, aff[1 + 3 * r],
-                               b.stats + 2 * n->bns[bn2].ch_off)))
-                return rc;
+            ConvOpts o2;
+            o2.in_affine = aff[1 + 3 * r];
+            o2.stats = b.stats + 2 * n->bns[bn2].ch_off;
+            if ((rc = run_conv(n, st[2 + 2 * r], kind, Src{z1, 2 * C, nullptr, 0, 0}, B, H, T, true, false, z2, C, 0, s, label, o2))) return rc;
             finalize_bn(bn2, count, aff[2 + 3 * r], 1.f);
             const bool to_final = r == nb - 1 && final_dst;
             float* xo = to_final ? final_dst : z[3 + 3 * r];
-            {
-                const long long total = static_cast<long long>(B) * C * H * T;
-                ake::ProfScope ps("res_add_act_kernel", s);
-                hipLaunchKernelGGL(res_add_act_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, z2, aff[2 + 3 * r], x, x_aff, xo, C,
-                                   H * T, to_final ? final_ctot : C, total);
-            }
+            const long long total = static_cast<long long>(B) * C * H * T;
+            launch_flat("res_add_act_kernel", res_add_act_kernel, s, total, z2, aff[2 + 3 * r], x, x_aff, xo, C, H * T, to_final ? final_ctot : C, total);
             identity(aff[3 + 3 * r], C);
             x = xo; x_aff = aff[3 + 3 * r];
         }
@@ -2375,17 +2419,12 @@ struct Fwd {
             const PackedConv& pc = n->semi[layer];
             SemiTrainArgs ta;
             std::memset(&ta, 0, sizeof(ta));
-            SemiArgs& a = ta.s;
-            a.src = src; a.C = pc.cin; a.H = P; a.T = Tn;
-            a.src_clip_stride = static_cast<long long>(pc.cin) * P * Tn;
-            a.w = n->blob_dev + pc.w_off; a.bias = n->blob_dev + pc.b_off;
-            a.dst = b.smap; a.n_strips = (Tn + TW - 1) / TW;
+            ta.s = semi_args(n, pc, src, P, Tn, b.smap);
             if ((rc = launch_semi_conv(pc, ta, P, B))) return rc;
             const PackedConv& fc = n->foldc[layer];
             const long long total = static_cast<long long>(B) * pc.cin * 12 * Tn;
-            ake::ProfScope ps("fold_conv_kernel", s);
-            hipLaunchKernelGGL(fold_conv_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, b.smap, n->blob_dev + fc.w_off,
-                               n->blob_dev + fc.b_off, dst, pc.cin, P / 36, Tn, 1, static_cast<long long>(ctot) * 12 * Tn, coff, total);
+            launch_flat("fold_conv_kernel", fold_conv_kernel, s, total, b.smap, n->blob_dev + fc.w_off, n->blob_dev + fc.b_off, dst, pc.cin, P / 36, Tn, 1,
+                        static_cast<long long>(ctot) * 12 * Tn, coff, total);
             return AKE_OK;
         }
         if (!train) return run_semi(n, n->semi[layer], src, B, P, Tn, dst, ctot, coff, s, nm);
@@ -2393,12 +2432,7 @@ struct Fwd {
         const int bn = bn_of("model." + std::to_string(layer) + ".pool_semi_b");
         SemiTrainArgs ta;
         std::memset(&ta, 0, sizeof(ta));
-        SemiArgs& a = ta.s;
-        a.src = src; a.C = pc.cin; a.H = P; a.T = Tn;
-        a.src_clip_stride = static_cast<long long>(pc.cin) * P * Tn;
-        a.w = n->blob_dev + pc.w_off; a.bias = n->blob_dev + pc.b_off;
-        a.dst = b.semi_raw[layer]; a.dst_coff = 0; a.dst_clip_stride = 0;
-        a.n_strips = (Tn + TW - 1) / TW;
+        ta.s = semi_args(n, pc, src, P, Tn, b.semi_raw[layer]);
         ta.in_affine = in_aff; ta.stats = b.stats + 2 * n->bns[bn].ch_off; ta.stats_stride = 2 * n->bn_channels;
         if ((rc = launch_semi_conv(pc, ta, P, B))) return rc;
         finalize_bn(bn, static_cast<double>(B) * (P / 3) * Tn, b.aff_semi[layer]);
@@ -2407,55 +2441,36 @@ struct Fwd {
             const PackedConv& fc = n->foldc_t[layer];
             const int bnf = bn_of("model." + std::to_string(layer) + ".pool.bn");
             AKE_REQUIRE(pc.cin <= 64, AKE_ERR_UNSUPPORTED, "p2pc_conv training: %d channels", pc.cin);
-            {
-                ake::ProfScope ps("fold_conv_kernel", s);
-                hipLaunchKernelGGL(fold_conv_train_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, b.semi_raw[layer],
-                                   b.aff_semi[layer], n->blob_dev + fc.w_off, n->blob_dev + fc.b_off, b.foldc_raw[layer],
-                                   b.stats + 2 * n->bns[bnf].ch_off, 2 * n->bn_channels, pc.cin, P / 36, Tn, total);
-            }
+            launch_flat("fold_conv_kernel", fold_conv_train_kernel, s, total, b.semi_raw[layer], b.aff_semi[layer], n->blob_dev + fc.w_off, n->blob_dev + fc.b_off,
+                        b.foldc_raw[layer], b.stats + 2 * n->bns[bnf].ch_off, 2 * n->bn_channels, pc.cin, P / 36, Tn, total);
             finalize_bn(bnf, static_cast<double>(B) * 12 * Tn, b.aff_foldc[layer]);
-            {   // the folded channels are materialised as final activations: every reader of the concat buffer takes them as they are
-                ake::ProfScope ps("apply_affine_kernel", s);
-                hipLaunchKernelGGL(apply_affine_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, b.foldc_raw[layer],
-                                   b.aff_foldc[layer], dst, pc.cin, static_cast<long long>(12) * Tn, ctot, coff, total);
-            }
-        } else {
-            ake::ProfScope ps("fold_affine_kernel", s);
-            hipLaunchKernelGGL(fold_affine_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, b.semi_raw[layer],
-                               b.aff_semi[layer], dst, pc.cin, P / 36, Tn, ctot, coff, total);
-        }
+            // the folded channels are materialised as final activations: every reader of the concat buffer takes them as they are
+            launch_flat("apply_affine_kernel", apply_affine_kernel, s, total, b.foldc_raw[layer], b.aff_foldc[layer], dst, pc.cin, static_cast<long long>(12) * Tn, ctot,
+                        coff, total);
+        } else if ((rc = run_fold_max("fold_affine_kernel", b.semi_raw[layer], b.aff_semi[layer], pc.cin, P / 3, B, Tn, dst, ctot, coff, s))) return rc;
         if (aff_cat_rows) identity(aff_cat_rows, pc.cin);     // the folded channels are final activations
         return AKE_OK;
     }
 
-    void up_sixth(int layer, const float* src, long long src_clip_stride, const float* in_aff, int B, int C, int Tn, float* dst, float* aff_dst) {
+    int up_sixth(int layer, const float* src, long long src_clip_stride, const float* in_aff, int B, int C, int Tn, float* dst, float* aff_dst) {
         const long long total = static_cast<long long>(B) * C * 36 * Tn;
         if (!train) {
-            ake::ProfScope ps("up_sixth_kernel", s);
-            hipLaunchKernelGGL(up_sixth_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, src, src_clip_stride,
-                               n->blob_dev + n->up[layer].w_off, n->blob_dev + n->up[layer].b_off, dst, C, Tn, total);
-            return;
+            launch_flat("up_sixth_kernel", up_sixth_kernel<false>, s, total, src, src_clip_stride, nullptr, n->blob_dev + n->up[layer].w_off,
+                        n->blob_dev + n->up[layer].b_off, dst, nullptr, 0, C, Tn, total);
+            return AKE_OK;
         }
         const int bn = bn_of("model." + std::to_string(layer) + ".up_sixth_b");
-        {
-            ake::ProfScope ps("up_sixth_train_kernel", s);
-            hipLaunchKernelGGL(up_sixth_train_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, src, src_clip_stride,
-                               in_aff, n->blob_dev + n->up_t[layer].w_off, n->blob_dev + n->up_t[layer].b_off, dst,
-                               b.stats + 2 * n->bns[bn].ch_off, 2 * n->bn_channels, C, Tn, total);
-        }
+        AKE_REQUIRE(C <= kBlockStatCh, AKE_ERR_UNSUPPORTED, "up_sixth training: %d channels", C);
+        launch_flat("up_sixth_train_kernel", up_sixth_kernel<true>, s, total, src, src_clip_stride, in_aff, n->blob_dev + n->up_t[layer].w_off,
+                    n->blob_dev + n->up_t[layer].b_off, dst, b.stats + 2 * n->bns[bn].ch_off, 2 * n->bn_channels, C, Tn, total);
         finalize_bn(bn, static_cast<double>(B) * 36 * Tn, aff_dst);
+        return AKE_OK;
     }
 
     void time_pool(const float* src, const float* in_aff, int B, int C, int H, int Tn, float* dst, int ctot, int coff) {
         const int tp = n->cfg.time_pool_size;
         const long long total = static_cast<long long>(B) * C * H * (Tn / tp);
-        ake::ProfScope ps("time_pool_kernel", s);
-        if (train && in_aff)
-            hipLaunchKernelGGL(time_pool_affine_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, src, in_aff, dst, C, H,
-                               Tn, tp, ctot, coff, total);
-        else
-            hipLaunchKernelGGL(time_pool_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, src, dst, C, H, Tn, tp, ctot,
-                               coff, total);
+        launch_flat("time_pool_kernel", time_pool_kernel, s, total, src, in_aff, dst, C, H, Tn, tp, ctot, coff, total);
     }
 
     // inference: semitone conv + BN + LeakyReLU of `src` [B][C][P][T] as a map of its own [B][C][P / 3][T] (raw = before the LeakyReLU)
@@ -2463,23 +2478,18 @@ struct Fwd {
         const PackedConv& pc = n->semi[layer];
         SemiTrainArgs ta;
         std::memset(&ta, 0, sizeof(ta));
-        SemiArgs& a = ta.s;
-        a.src = src; a.C = pc.cin; a.H = P; a.T = Tn;
-        a.src_clip_stride = static_cast<long long>(pc.cin) * P * Tn;
-        a.w = n->blob_dev + pc.w_off; a.bias = n->blob_dev + pc.b_off;
-        a.dst = dst; a.n_strips = (Tn + TW - 1) / TW;
+        ta.s = semi_args(n, pc, src, P, Tn, dst);
         ta.out_lrelu = raw ? 0 : 1;
         return launch_semi_conv(pc, ta, P, B);
     }
 
     // the octave fold of ready maps [B][C][S][T] into channels [coff, coff + C) of dst: max (models.py:95-106) or --p2pc_conv's convolution
     int fold_maps(int layer, const float* maps, int C, int S, int B, int Tn, float* dst, int ctot, int coff) {
-        if (!n->cfg.p2pc_conv) return run_fold_max(maps, C, S, B, Tn, dst, ctot, coff, s);
+        if (!n->cfg.p2pc_conv) return run_fold_max("fold_max_kernel", maps, nullptr, C, S, B, Tn, dst, ctot, coff, s);
         const PackedConv& fc = n->foldc[layer];
         const long long total = static_cast<long long>(B) * C * 12 * Tn;
-        ake::ProfScope ps("fold_conv_kernel", s);
-        hipLaunchKernelGGL(fold_conv_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, maps, n->blob_dev + fc.w_off,
-                           n->blob_dev + fc.b_off, dst, C, S / 12, Tn, 0, static_cast<long long>(ctot) * 12 * Tn, coff, total);
+        launch_flat("fold_conv_kernel", fold_conv_kernel, s, total, maps, n->blob_dev + fc.w_off, n->blob_dev + fc.b_off, dst, C, S / 12, Tn, 0,
+                    static_cast<long long>(ctot) * 12 * Tn, coff, total);
         return AKE_OK;
     }
 
@@ -2504,7 +2514,7 @@ struct Fwd {
             const bool lastj = j == c.conv_layers - 1;
             a.w[j] = n->blob_dev + pc.w_off; a.b[j] = n->blob_dev + pc.b_off;
             if (take_mfma) a.frag[j] = n->bf_frags_dev + pc.l0_off;
-            a.dst[j] = lastj ? b.cat[1] : ((j & 1) ? b.pcb[0] : b.pca[0]);
+            a.dst[j] = lastj ? b.cat[1] : b.pc_out(false, 0, j).p;
             a.dst_clip_stride[j] = static_cast<long long>(lastj ? ctot1 : NF) * 12 * T0;
         }
         a.uw = n->blob_dev + n->up[1].w_off; a.ub = n->blob_dev + n->up[1].b_off;
@@ -2542,22 +2552,15 @@ struct Fwd {
             float* feat = L == 1 ? b.fold0 : b.cat[1];
             if ((rc = semi(0, mel, nullptr, B, P, T0, feat, ctot1, 0, nullptr))) return rc;
             if (L == 1) return AKE_OK;                           // its block runs in the tail
-            if (train) {
-                if ((rc = dense_stack_train(n->dense_pc[0], 1, feat, ctot1, 1, B, 12, T0, b.dn_bott_pc[0], b.dn_aff1_pc[0], b.dn_aff2_pc[0], "conv_mfma_kernel/pc2pc0")))
-                    return rc;
-                // the raw up_sixth map + its table (rows [prev_p, ..) of the pitch block's input table, as in the default net)
-                up_sixth(1, feat, static_cast<long long>(ctot1) * 12 * T0, nullptr, B, n->dims[1].prev_pc, T0, b.psix[1], b.aff_p2pin[1] + 3 * n->dims[1].prev_p);
-                return AKE_OK;
-            }
-            if ((rc = dense_stack(n->dense_pc[0], 1, feat, ctot1, 1, B, 12, T0, b.pca[0], "conv_mfma_kernel/pc2pc0"))) return rc;
-            up_sixth(1, feat, static_cast<long long>(ctot1) * 12 * T0, nullptr, B, n->dims[1].prev_pc, T0, b.psix[1], nullptr);
+            if ((rc = dense_stack(0, 1, feat, ctot1, 1, B, 12, T0, b.pca[0], "conv_mfma_kernel/pc2pc0"))) return rc;
+            // training: the raw up_sixth map + its table (rows [prev_p, ..) of the pitch block's input table, as in the default net)
+            if ((rc = up_sixth(1, feat, static_cast<long long>(ctot1) * 12 * T0, nullptr, B, n->dims[1].prev_pc, T0, b.psix[1], p2pin_up(1)))) return rc;
             return AKE_OK;
         } else if ((rc = semi(0, mel, nullptr, B, P, T0, b.fold0, 1, 0, nullptr))) return rc;
         if (L == 1) return AKE_OK;                               // its pc2pc runs in the tail
         const LayerDims& d1 = n->dims[1];
         const int ctot1 = d1.prev_pc + d1.out_p;
-        const float* src = b.fold0;
-        const float* src_aff = nullptr;
+        Slot src{b.fold0, nullptr};
         int cin = 1;
         const std::string m = "model.0.pc2pc.layer.";
         if (c.resblock && train) {   // the last block's output = channels [0, nf) of layer 1's concat buffer, final (identity table)
@@ -2570,19 +2573,17 @@ struct Fwd {
         }
         for (int j = 0; j < c.conv_layers && !c.resblock; ++j) {
             const bool lastj = j == c.conv_layers - 1;           // the last conv writes channels [0, nf) of layer 1's concat buffer
-            float* dst = lastj ? b.cat[1] : (train ? b.pcst[0][j] : ((j & 1) ? b.pcb[0] : b.pca[0]));
-            float* aff = !train ? nullptr : (lastj ? b.aff_cat[1] : b.aff_pcst[0][j]);
+            const Slot dst = lastj ? b.cat_slot(train, 1) : b.pc_out(train, 0, j);
             if ((rc = conv(n->pc2pc[0][j], train ? n->pc2pc_t[0][j] : n->pc2pc[0][j], m + std::to_string(3 * j + 1), 1,
-                           Src{src, cin, nullptr, 0, 0}, src_aff, B, 12, T0, true, dst, lastj ? ctot1 : c.n_filters, 0, aff,
+                           Src{src.p, cin, nullptr, 0, 0}, src.aff, B, 12, T0, true, dst.p, lastj ? ctot1 : c.n_filters, 0, dst.aff,
                            "conv_mfma_kernel/pc2pc0")))
                 return rc;
-            src = dst; src_aff = aff; cin = c.n_filters;
+            src = dst; cin = c.n_filters;
         }
         if (c.stay_sixth) return AKE_OK;                         // no up_sixth: the pitch classes are repeated as they are
         // psix's BatchNorm lands in rows [prev_p, ..) of the pitch-conv input table (row 0.. = the pitch stream itself)
         if (train) identity(b.aff_p2pin[1], d1.prev_p);
-        up_sixth(1, b.cat[1], static_cast<long long>(ctot1) * 12 * T0, train ? b.aff_cat[1] : nullptr, B, d1.prev_pc, T0, b.psix[1],
-                 train ? b.aff_p2pin[1] + 3 * d1.prev_p : nullptr);
+        if ((rc = up_sixth(1, b.cat[1], static_cast<long long>(ctot1) * 12 * T0, b.cat_slot(train, 1).aff, B, d1.prev_pc, T0, b.psix[1], p2pin_up(1)))) return rc;
         return AKE_OK;
     }
 
@@ -2606,25 +2607,14 @@ struct Fwd {
                 const int ctd = d.prev_pc + d.out_p + g;                             // = d.out_pc
                 float* catd = b.cat[i] + (last || i == 1 ? static_cast<size_t>(c0) * ctd * 12 * Ti : 0);
                 float* psixd = b.psix[i] + (i == 1 ? static_cast<size_t>(c0) * d.prev_pc * 36 * Ti : 0);
-                if (i > 1) up_sixth(i, pc_cur, static_cast<long long>(ctd) * 12 * Ti, nullptr, B, d.prev_pc, Ti, psixd, train ? b.aff_p2pin[i] + 3 * d.prev_p : nullptr);
+                if (i > 1 && (rc = up_sixth(i, pc_cur, static_cast<long long>(ctd) * 12 * Ti, nullptr, B, d.prev_pc, Ti, psixd, p2pin_up(i)))) return rc;
                 float* fp = b.pa[i];                                                  // [B][out_p][P][Ti]
-                {
-                    const long long total = static_cast<long long>(B) * (cp + d.prev_pc) * P * Ti;
-                    ake::ProfScope ps("concat_repeat_kernel", s);
-                    hipLaunchKernelGGL(concat_repeat_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, p_cur, cp, psixd, d.prev_pc, 36,
-                                       fp, d.out_p, P, Ti, total, train ? b.aff_p2pin[i] + 3 * d.prev_p : nullptr);
-                }
-                if (train) {
-                    if ((rc = dense_stack_train(n->dense_p[i], 0, fp, d.out_p, cp + d.prev_pc, B, P, Ti, b.dn_bott_p[i], b.dn_aff1_p[i], b.dn_aff2_p[i], "conv_mfma_kernel/p2p")))
-                        return rc;
-                } else if ((rc = dense_stack(n->dense_p[i], 0, fp, d.out_p, cp + d.prev_pc, B, P, Ti, b.pb[i], "conv_mfma_kernel/p2p"))) return rc;
+                const long long total = static_cast<long long>(B) * (cp + d.prev_pc) * P * Ti;
+                launch_flat("concat_repeat_kernel", concat_repeat_kernel, s, total, p_cur, cp, psixd, d.prev_pc, 36, fp, d.out_p, P, Ti, total, p2pin_up(i));
+                if ((rc = dense_stack(i, 0, fp, d.out_p, cp + d.prev_pc, B, P, Ti, b.pb[i], "conv_mfma_kernel/p2p"))) return rc;
                 if ((rc = semi(i, fp, nullptr, B, P, Ti, catd, ctd, d.prev_pc, nullptr))) return rc;
                 if (last) return AKE_OK;                                              // its pitch-class block + pooling + heads run batch-wide
-                if (train) {
-                    if ((rc = dense_stack_train(n->dense_pc[i], 1, catd, ctd, d.prev_pc + d.out_p, B, 12, Ti, b.dn_bott_pc[i], b.dn_aff1_pc[i], b.dn_aff2_pc[i],
-                                                "conv_mfma_kernel/pc2pc")))
-                        return rc;
-                } else if ((rc = dense_stack(n->dense_pc[i], 1, catd, ctd, d.prev_pc + d.out_p, B, 12, Ti, b.pca[i], "conv_mfma_kernel/pc2pc"))) return rc;
+                if ((rc = dense_stack(i, 1, catd, ctd, d.prev_pc + d.out_p, B, 12, Ti, b.pca[i], "conv_mfma_kernel/pc2pc"))) return rc;
                 const LayerDims& dn = n->dims[i + 1];
                 const int ctn = dn.prev_pc + dn.out_p + g;
                 const int Tn = Ti / tp;
@@ -2640,8 +2630,7 @@ struct Fwd {
             float* psix = b.psix[i] + (i == 1 ? static_cast<size_t>(c0) * d.prev_pc * 36 * Ti : 0);
             if (i > 1 && !c.stay_sixth) {   // layer 1's up_sixth ran batch-wide in entry(); pc_cur = pooled (final) features here
                 if (train) identity(b.aff_p2pin[i], d.prev_p);
-                up_sixth(i, pc_cur, static_cast<long long>(ctot) * 12 * Ti, nullptr, B, d.prev_pc, Ti, psix,
-                         train ? b.aff_p2pin[i] + 3 * d.prev_p : nullptr);
+                if ((rc = up_sixth(i, pc_cur, static_cast<long long>(ctot) * 12 * Ti, nullptr, B, d.prev_pc, Ti, psix, p2pin_up(i)))) return rc;
             }
             // models.py:378-384  repeat + concat (never materialised) + pitch convs
             Src sdesc{p_cur, cp, psix, d.prev_pc, 36};
@@ -2649,11 +2638,7 @@ struct Fwd {
                                   // in channels [0, prev_pc) of a concat buffer)
                 const float* pcs = i == 1 ? b.cat[1] + static_cast<size_t>(c0) * ctot * 12 * Ti : pc_cur;
                 const long long per_clip = static_cast<long long>(d.prev_pc) * 12 * Ti, total = per_clip * B;
-                {
-                    ake::ProfScope ps("slice_channels_kernel", s);
-                    hipLaunchKernelGGL(slice_channels_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, pcs,
-                                       static_cast<long long>(ctot) * 12 * Ti, b.pcd[i], per_clip, total);
-                }
+                launch_flat("slice_channels_kernel", slice_channels_kernel, s, total, pcs, static_cast<long long>(ctot) * 12 * Ti, b.pcd[i], per_clip, total);
                 sdesc = Src{p_cur, cp, b.pcd[i], d.prev_pc, 12};
                 if (train) {   // the stack's input table: the pitch stream's rows, then the pitch classes' (they were copied raw)
                     if (i == 1) AKE_HIP_CHECK(hipMemcpyAsync(b.aff_p2pin[i], b.aff_semi[0], sizeof(float) * 3 * cp, hipMemcpyDeviceToDevice, s));
@@ -2663,15 +2648,12 @@ struct Fwd {
             }
             if (c.pc2p_mem) {   // models.py:376-377: no concat, the summed up_sixth map is added to the pitch stream
                 const long long total = static_cast<long long>(B) * cp * P * Ti;
-                ake::ProfScope ps("pc2p_mem_kernel", s);
                 // (training: psix is raw, its up_sixth_b table sits behind the pitch stream's identity rows; the sum itself is final)
-                hipLaunchKernelGGL(pc2p_mem_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, p_cur, psix, b.pin[i], cp,
-                                   d.prev_pc / cp, P, Ti, total, train ? b.aff_p2pin[i] + 3 * d.prev_p : nullptr);
+                launch_flat("pc2p_mem_kernel", pc2p_mem_kernel, s, total, p_cur, psix, b.pin[i], cp, d.prev_pc / cp, P, Ti, total, p2pin_up(i));
                 sdesc = Src{b.pin[i], cp, nullptr, 0, 0};
             }
             const float* in_aff = train ? b.aff_p2pin[i] : nullptr;
-            float* out = nullptr;
-            float* out_aff = nullptr;
+            Slot out;                             // the stack's last output
             // inference: the stack runs on f16 MFMA (f16 activations x hi + lo f16 weights, see conv_p2p_f16_kernel); the activations
             // between its convs are ONE channels-last f16 plane (16 B per position) in the same ping-pong buffers
             const Route::Pitch& rp = r.p[i];
@@ -2680,40 +2662,39 @@ struct Fwd {
             if (c.resblock && train) {
                 if ((rc = res_stack_train(n->p2p_t[i], m + "p2p.layer.", 0, sdesc, in_aff, B, P, Ti, b.pst[i], b.aff_pst[i], nullptr, 0, "conv_mfma_kernel/p2p")))
                     return rc;
-                out = b.pst[i].back(); out_aff = b.aff_pst[i].back();
+                out = b.p_last(i);
             } else if (c.resblock) {
                 if ((rc = res_stack(n->p2p[i], 0, sdesc, B, P, Ti, b.pa[i], b.pb[i], nullptr, 0, "conv_mfma_kernel/p2p"))) return rc;
-                out = b.pa[i];
+                out = Slot{b.pa[i], nullptr};
             }
             const bool one_launch = rp.stack == PStack::F16 && rk.stack.ok;
             if (one_launch) {      // the whole stack, semitone conv and fold as one launch
                 unsigned short* planes[kP2pStackMax];
-                for (int j = 0; j < kP2pStackMax; ++j) planes[j] = reinterpret_cast<unsigned short*>((j & 1) ? b.pb[i] : b.pa[i]);
+                for (int j = 0; j < kP2pStackMax; ++j) planes[j] = reinterpret_cast<unsigned short*>(b.p_out(false, i, j).p);
                 if ((rc = run_p2p_stack(n, n->p2p[i], n->semi[i], rk.stack, b.melh + static_cast<size_t>(c0) * P * Ti,
                                         reinterpret_cast<const uint2*>(b.psix[1]) + static_cast<size_t>(c0) * 36 * Ti, d.prev_pc, planes, cat, ctot, d.prev_pc, B, P, Ti, s,
                                         "conv_p2p_f16_kernel")))
                     return rc;
-                out = ((c.conv_layers - 1) & 1) ? b.pb[i] : b.pa[i];
+                out = b.p_out(false, i, c.conv_layers - 1);
                 last_out = P2pOut::SemiFold;
             }
             for (int j = 0; j < c.conv_layers && !c.resblock && !one_launch; ++j) {
-                out = train ? b.pst[i][j] : ((j & 1) ? b.pb[i] : b.pa[i]);
-                out_aff = !train ? nullptr : b.aff_pst[i][j];
+                out = b.p_out(train, i, j);
                 if (rp.stack == PStack::F16) {
                     const bool last_conv = j == c.conv_layers - 1;
                     const P2pPsPlan& g = j == 0 ? rk.first : (last_conv ? rk.last : rk.mid);
                     P2pPsIo io;
                     io.in = g.in; io.out = g.out;
                     io.dst_ctot = d.out_p;
-                    if (j > 0) io.planes = reinterpret_cast<const unsigned short*>(((j - 1) & 1) ? b.pb[i] : b.pa[i]);
+                    if (j > 0) io.planes = reinterpret_cast<const unsigned short*>(b.p_out(false, i, j - 1).p);
                     else if (g.in == P2pIn::SrcF16x4)   // layer 0 left the CQT and the up_sixth map as f16 words (8 bytes per position of the map, clip stride 36 T words)
                         io.src = Src{reinterpret_cast<const float*>(b.melh + static_cast<size_t>(c0) * P * Ti), 1,
                                      reinterpret_cast<const float*>(reinterpret_cast<const uint2*>(b.psix[1]) + static_cast<size_t>(c0) * 36 * Ti), d.prev_pc, 36};
                     else io.src = sdesc;              // the stack's input (pitch stream | repeated up_sixth output) is assembled by the kernel's own loader
                     switch (g.out) {
-                        case P2pOut::Plane: io.plane = reinterpret_cast<unsigned short*>(out); break;
-                        case P2pOut::Nchw: io.dst = out; break;
-                        case P2pOut::Semi: io.dst = out; io.semi = &n->semi[i]; break;       // `out` receives the semitone maps [clip][8][P / 3][T]
+                        case P2pOut::Plane: io.plane = reinterpret_cast<unsigned short*>(out.p); break;
+                        case P2pOut::Nchw: io.dst = out.p; break;
+                        case P2pOut::Semi: io.dst = out.p; io.semi = &n->semi[i]; break;       // `out` receives the semitone maps [clip][8][P / 3][T]
                         case P2pOut::SemiFold: io.dst = cat; io.dst_ctot = ctot; io.fold_coff = d.prev_pc; io.semi = &n->semi[i]; break;
                     }
                     if (last_conv) last_out = g.out;
@@ -2727,65 +2708,56 @@ struct Fwd {
                 if (rp.x3_convs >> j & 1) {   // f16 x 3 on the persistent form; else the f32 MFMA kernel
                     const PackedConv& px = train ? n->p2p_t[i][j] : n->p2p[i][j];
                     const int bn = train ? bn_of(m + "p2p.layer." + std::to_string(3 * j + 1)) : -1;
-                    if ((rc = run_p2p_f16x3(n, rk.x3[j > 0], px.bf_off, sdesc, in_aff, n->blob_dev + px.b_off, B, P, Ti, out, d.out_p,
-                                            train ? b.stats + 2 * n->bns[bn].ch_off : nullptr, train ? 2 * n->bn_channels : 0, s, "conv_p2p_f16x3_kernel/p2p", nullptr,
-                                            !train)))
+                    P2pX3Opts ox;
+                    ox.lrelu = !train;             // (training: the BatchNorm finalised below comes first)
+                    if ((rc = run_p2p_f16x3(n, rk.x3[j > 0], px.bf_off, sdesc, in_aff, n->blob_dev + px.b_off, B, P, Ti, out.p, d.out_p,
+                                            train ? b.stats + 2 * n->bns[bn].ch_off : nullptr, train ? 2 * n->bn_channels : 0, s, "conv_p2p_f16x3_kernel/p2p", ox)))
                         return rc;
-                    if (train) finalize_bn(bn, static_cast<double>(B) * P * Ti, out_aff);
-                    sdesc = Src{out, d.out_p, nullptr, 0, 0};
-                    in_aff = out_aff;
-                    continue;
-                }
-                if ((rc = conv(n->p2p[i][j], train ? n->p2p_t[i][j] : n->p2p[i][j], m + "p2p.layer." + std::to_string(3 * j + 1), 0, sdesc,
-                               in_aff, B, P, Ti, true, out, d.out_p, 0, out_aff, "conv_mfma_kernel/p2p")))
+                    if (train) finalize_bn(bn, static_cast<double>(B) * P * Ti, out.aff);
+                } else if ((rc = conv(n->p2p[i][j], train ? n->p2p_t[i][j] : n->p2p[i][j], m + "p2p.layer." + std::to_string(3 * j + 1), 0, sdesc,
+                                      in_aff, B, P, Ti, true, out.p, d.out_p, 0, out.aff, "conv_mfma_kernel/p2p")))
                     return rc;
-                sdesc = Src{out, d.out_p, nullptr, 0, 0};
-                in_aff = out_aff;
+                sdesc = Src{out.p, d.out_p, nullptr, 0, 0};
+                in_aff = out.aff;
             }
             // models.py:386-392  pool_semi -> fold, written next to pc in the concat buffer
             if (last_out == P2pOut::SemiFold) {
             } else if (last_out == P2pOut::Semi) {
-                if ((rc = run_fold_max(out, d.out_p, P / 3, B, Ti, cat, ctot, d.prev_pc, s))) return rc;
+                if ((rc = run_fold_max("fold_max_kernel", out.p, nullptr, d.out_p, P / 3, B, Ti, cat, ctot, d.prev_pc, s))) return rc;
             } else if (c.stay_sixth && train) {   // ... through the last conv's pending BatchNorm + LeakyReLU
-                const long long total = static_cast<long long>(B) * d.out_p * 12 * Ti;
-                ake::ProfScope ps("fold_affine_kernel", s);
-                hipLaunchKernelGGL(fold_affine_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, out, out_aff, cat, d.out_p, P / 12, Ti,
-                                   ctot, d.prev_pc, total);
+                if ((rc = run_fold_max("fold_affine_kernel", out.p, out.aff, d.out_p, P, B, Ti, cat, ctot, d.prev_pc, s))) return rc;
                 identity(b.aff_cat[i] + 3 * d.prev_pc, d.out_p);
             } else if (c.stay_sixth) {   // models.py:391: the stack's output is folded as it is (no semitone conv)
-                if ((rc = fold_maps(i, out, d.out_p, P, B, Ti, cat, ctot, d.prev_pc))) return rc;
-            } else if ((rc = semi(i, out, out_aff, B, P, Ti, cat, ctot, d.prev_pc, train ? b.aff_cat[i] + 3 * d.prev_pc : nullptr))) return rc;
+                if ((rc = fold_maps(i, out.p, d.out_p, P, B, Ti, cat, ctot, d.prev_pc))) return rc;
+            } else if ((rc = semi(i, out.p, out.aff, B, P, Ti, cat, ctot, d.prev_pc, train ? b.aff_cat[i] + 3 * d.prev_pc : nullptr))) return rc;
             if (last) return AKE_OK;                             // pc2pc + pooling + heads run batch-wide
             // inner layers of deeper nets: pc2pc, then both time pools (models.py:393-396)
-            const float* psrc = cat;
-            const float* psrc_aff = train ? b.aff_cat[i] : nullptr;
+            Slot psrc{cat, b.cat_slot(train, i).aff};
             int cin = ctot;
-            float* pdst = nullptr;
-            float* pdst_aff = nullptr;
+            Slot pdst;
             if (c.resblock && train) {
-                if ((rc = res_stack_train(n->pc2pc_t[i], m + "pc2pc.layer.", 1, Src{psrc, cin, nullptr, 0, 0}, psrc_aff, B, 12, Ti, b.pcst[i], b.aff_pcst[i],
+                if ((rc = res_stack_train(n->pc2pc_t[i], m + "pc2pc.layer.", 1, Src{psrc.p, cin, nullptr, 0, 0}, psrc.aff, B, 12, Ti, b.pcst[i], b.aff_pcst[i],
                                           nullptr, 0, "conv_mfma_kernel/pc2pc")))
                     return rc;
-                pdst = b.pcst[i].back(); pdst_aff = b.aff_pcst[i].back();
+                pdst = b.pc_last(i);
             } else if (c.resblock) {
-                if ((rc = res_stack(n->pc2pc[i], 1, Src{psrc, cin, nullptr, 0, 0}, B, 12, Ti, b.pca[i], b.pcb[i], nullptr, 0, "conv_mfma_kernel/pc2pc"))) return rc;
-                pdst = b.pca[i];
+                if ((rc = res_stack(n->pc2pc[i], 1, Src{psrc.p, cin, nullptr, 0, 0}, B, 12, Ti, b.pca[i], b.pcb[i], nullptr, 0, "conv_mfma_kernel/pc2pc"))) return rc;
+                pdst = Slot{b.pca[i], nullptr};
             }
             for (int j = 0; j < c.conv_layers && !c.resblock; ++j) {
-                pdst = train ? b.pcst[i][j] : ((j & 1) ? b.pcb[i] : b.pca[i]);
-                pdst_aff = !train ? nullptr : b.aff_pcst[i][j];
+                pdst = b.pc_out(train, i, j);
                 if ((rc = conv(n->pc2pc[i][j], train ? n->pc2pc_t[i][j] : n->pc2pc[i][j], m + "pc2pc.layer." + std::to_string(3 * j + 1), 1,
-                               Src{psrc, cin, nullptr, 0, 0}, psrc_aff, B, 12, Ti, true, pdst, d.out_pc, 0, pdst_aff, "conv_mfma_kernel/pc2pc")))
+                               Src{psrc.p, cin, nullptr, 0, 0}, psrc.aff, B, 12, Ti, true, pdst.p, d.out_pc, 0, pdst.aff, "conv_mfma_kernel/pc2pc")))
                     return rc;
-                psrc = pdst; psrc_aff = pdst_aff; cin = d.out_pc;
+                psrc = pdst; cin = d.out_pc;
             }
             const LayerDims& dn = n->dims[i + 1];
             const int ctn = dn.prev_pc + dn.out_p;
             const int Tn = Ti / tp;
             float* catn = b.cat[i + 1] + (i + 1 == L - 1 ? static_cast<size_t>(c0) * ctn * 12 * Tn : 0);
-            time_pool(pdst, pdst_aff, B, d.out_pc, 12, Ti, catn, ctn, 0);
+            time_pool(pdst.p, pdst.aff, B, d.out_pc, 12, Ti, catn, ctn, 0);
             if (train) identity(b.aff_cat[i + 1], d.out_pc);
-            time_pool(out, out_aff, B, d.out_p, P, Ti, b.ppool[i], d.out_p, 0);
+            time_pool(out.p, out.aff, B, d.out_p, P, Ti, b.ppool[i], d.out_p, 0);
             pc_cur = catn; p_cur = b.ppool[i]; cp = d.out_p;
         }
         return AKE_OK;
@@ -2799,14 +2771,12 @@ struct Fwd {
         const int Ti = b.Tl[i];
         const LayerDims& d = n->dims[i];
         int rc;
-        const float* psrc = L == 1 ? b.fold0 : b.cat[i];
-        const float* psrc_aff = (train && L > 1) ? b.aff_cat[i] : nullptr;
+        Slot psrc = L == 1 ? Slot{b.fold0, nullptr} : b.cat_slot(train, i);
         int cin = L == 1 ? 1 : d.prev_pc + d.out_p;
         const int cout_default = L == 1 ? c.n_filters : d.out_pc;
         const int cout = cout_default;
         const std::string m = "model." + std::to_string(i) + ".pc2pc.layer.";
-        float* pdst = nullptr;
-        float* pdst_aff = nullptr;
+        Slot pdst;
         // inference, 16-channel stacks: bf16 MFMA with split operands; the stack's input is converted to channels-last planes once,
         // the intermediate activations stay in that format (same 64 B per position as 16 f32 channels: the ping-pong buffers are
         // reused), the last convolution writes NCHW f32 for the pooling / heads
@@ -2814,80 +2784,65 @@ struct Fwd {
         // heads on the bf16 kernels read a channels-last copy of the pooled features (the fused stack writes it itself)
         const bool head_bf = r.heads != HeadForm::Generic;
         if (pc_fused) {
-            if ((rc = run_pc2pc_fused(n, i, psrc, cin, B, Ti, b.pcf, head_bf ? b.feat_cl : nullptr, s))) return rc;
-        } else if (pc_bf) run_nchw_to_cl16(psrc, cin, B, Ti, reinterpret_cast<unsigned short*>(b.pcb[i]), s);
+            if ((rc = run_pc2pc_fused(n, i, psrc.p, cin, B, Ti, b.pcf, head_bf ? b.feat_cl : nullptr, s))) return rc;
+        } else if (pc_bf) run_nchw_to_cl16(psrc.p, cin, B, Ti, reinterpret_cast<unsigned short*>(b.pcb[i]), s);
+        const char* const pc_label = L == 1 ? "conv_mfma_kernel/pc2pc0" : "conv_mfma_kernel/pc2pc";
         if (c.resblock && train) {
-            if ((rc = res_stack_train(n->pc2pc_t[i], m, 1, Src{psrc, cin, nullptr, 0, 0}, psrc_aff, B, 12, Ti, b.pcst[i], b.aff_pcst[i], nullptr, 0,
-                                      L == 1 ? "conv_mfma_kernel/pc2pc0" : "conv_mfma_kernel/pc2pc")))
+            if ((rc = res_stack_train(n->pc2pc_t[i], m, 1, Src{psrc.p, cin, nullptr, 0, 0}, psrc.aff, B, 12, Ti, b.pcst[i], b.aff_pcst[i], nullptr, 0, pc_label)))
                 return rc;
-            pdst = b.pcst[i].back(); pdst_aff = b.aff_pcst[i].back();
+            pdst = b.pc_last(i);
         } else if (c.resblock) {
-            if ((rc = res_stack(n->pc2pc[i], 1, Src{psrc, cin, nullptr, 0, 0}, B, 12, Ti, b.pca[i], b.pcb[i], nullptr, 0,
-                                L == 1 ? "conv_mfma_kernel/pc2pc0" : "conv_mfma_kernel/pc2pc")))
-                return rc;
-            pdst = b.pca[i];
+            if ((rc = res_stack(n->pc2pc[i], 1, Src{psrc.p, cin, nullptr, 0, 0}, B, 12, Ti, b.pca[i], b.pcb[i], nullptr, 0, pc_label))) return rc;
+            pdst = Slot{b.pca[i], nullptr};
         }
         if (c.denseblock) {   // the last layer's pitch-class block, in place on its concat buffer: the features are the buffer itself
-            float* feat_buf = L == 1 ? b.fold0 : b.cat[i];
-            if (train) {
-                if ((rc = dense_stack_train(n->dense_pc[i], 1, feat_buf, n->final_ch, cin, B, 12, Ti, b.dn_bott_pc[i], b.dn_aff1_pc[i], b.dn_aff2_pc[i],
-                                            L == 1 ? "conv_mfma_kernel/pc2pc0" : "conv_mfma_kernel/pc2pc")))
-                    return rc;
-            } else if ((rc = dense_stack(n->dense_pc[i], 1, feat_buf, n->final_ch, cin, B, 12, Ti, b.pca[i],
-                                         L == 1 ? "conv_mfma_kernel/pc2pc0" : "conv_mfma_kernel/pc2pc")))
-                return rc;
-            pdst = feat_buf; pdst_aff = nullptr;
+            if ((rc = dense_stack(i, 1, psrc.p, n->final_ch, cin, B, 12, Ti, b.pca[i], pc_label))) return rc;
+            pdst = Slot{psrc.p, nullptr};
         }
         for (int j = 0; j < c.conv_layers && !pc_fused && !c.resblock && !c.denseblock; ++j) {
-            pdst = train ? b.pcst[i][j] : ((j & 1) ? b.pcb[i] : b.pca[i]);
-            pdst_aff = !train ? nullptr : b.aff_pcst[i][j];
+            pdst = b.pc_out(train, i, j);
             if (pc_bf) {
                 const bool last_conv = j == c.conv_layers - 1;
-                const unsigned short* in = reinterpret_cast<const unsigned short*>((j & 1) ? b.pca[i] : b.pcb[i]);
-                if ((rc = run_pc_bf16(n, n->pc2pc[i][j], in, B, Ti, true, true, last_conv ? pdst : nullptr,
-                                      last_conv ? nullptr : reinterpret_cast<unsigned short*>(pdst), s, "conv_pc_bf16_kernel/pc2pc")))
+                const unsigned short* in = reinterpret_cast<const unsigned short*>(j == 0 ? b.pcb[i] : b.pc_out(false, i, j - 1).p);   // (the stack's input planes: pcb)
+                if ((rc = run_pc_bf16(n, n->pc2pc[i][j], in, B, Ti, true, true, last_conv ? pdst.p : nullptr,
+                                      last_conv ? nullptr : reinterpret_cast<unsigned short*>(pdst.p), s, "conv_pc_bf16_kernel/pc2pc")))
                     return rc;
                 continue;
             }
             if (r.pc_x3_convs >> j & 1) {   // f16 x 3 MFMA (f32-equivalent products) instead of the f32 MFMA kernel
                 const PackedConv& pt = n->pc2pc_t[i][j];
                 unsigned short* planes = reinterpret_cast<unsigned short*>(b.pcb[i]);       // (the inference ping-pong buffer: idle in training)
-                run_nchw_to_cl16_f16x2(psrc, cin, B, Ti, psrc_aff, planes, s);
+                run_nchw_to_cl16_f16x2(psrc.p, cin, B, Ti, psrc.aff, planes, s);
                 const int bn = bn_of(m + std::to_string(3 * j + 1));
-                if ((rc = run_pc_bf16(n, pt, planes, B, Ti, true, false, pdst, nullptr, s, "conv_pc_f16x3_kernel/pc2pc", nullptr, nullptr, true,
-                                      b.stats + 2 * n->bns[bn].ch_off, 2 * n->bn_channels)))
-                    return rc;
-                finalize_bn(bn, static_cast<double>(B) * 12 * Ti, pdst_aff);
-                psrc = pdst; psrc_aff = pdst_aff; cin = cout;
-                continue;
-            }
-            if ((rc = conv(n->pc2pc[i][j], train ? n->pc2pc_t[i][j] : n->pc2pc[i][j], m + std::to_string(3 * j + 1), 1,
-                           Src{psrc, cin, nullptr, 0, 0}, psrc_aff, B, 12, Ti, true, pdst, cout, 0, pdst_aff,
-                           L == 1 ? "conv_mfma_kernel/pc2pc0" : "conv_mfma_kernel/pc2pc")))
+                PcBf16Opts o;
+                o.f16x3 = true; o.stats = b.stats + 2 * n->bns[bn].ch_off; o.stats_stride = 2 * n->bn_channels;
+                if ((rc = run_pc_bf16(n, pt, planes, B, Ti, true, false, pdst.p, nullptr, s, "conv_pc_f16x3_kernel/pc2pc", o))) return rc;
+                finalize_bn(bn, static_cast<double>(B) * 12 * Ti, pdst.aff);
+            } else if ((rc = conv(n->pc2pc[i][j], train ? n->pc2pc_t[i][j] : n->pc2pc[i][j], m + std::to_string(3 * j + 1), 1,
+                                  Src{psrc.p, cin, nullptr, 0, 0}, psrc.aff, B, 12, Ti, true, pdst.p, cout, 0, pdst.aff, pc_label)))
                 return rc;
-            psrc = pdst; psrc_aff = pdst_aff; cin = cout;
+            psrc = pdst; cin = cout;
         }
-        const float* feat = pdst;                 // features feeding the heads
-        const float* feat_aff = pdst_aff;
-        if (pc_fused) { feat = b.pcf; feat_aff = nullptr; }
+        Slot feat = pdst;                         // features feeding the heads
+        if (pc_fused) feat = Slot{b.pcf, nullptr};
         else if (L > 1) {   // models.py:396  (the pitch stream of the last layer feeds nothing: its pool is skipped)
             const int cout = c.denseblock ? n->final_ch : cout_default;
-            time_pool(pdst, pdst_aff, B, cout, 12, Ti, b.pcf, cout, 0);
-            feat = b.pcf; feat_aff = nullptr;
+            time_pool(pdst.p, pdst.aff, B, cout, 12, Ti, b.pcf, cout, 0);
+            feat = Slot{b.pcf, nullptr};
         }
         // ---- heads (models.py:750-753) ----
         const int Tf = b.Tf;
-        struct HeadRun { const std::vector<PackedConv>* ce; const std::vector<PackedConv>* ct; float* hid; float* map; int kind; const char* nm; };
-        HeadRun heads[3] = {{&n->head_key, &n->head_key_t, b.hid_k, b.map_k, 1, "key_classifier"},
-                            {&n->head_tonic, &n->head_tonic_t, b.hid_t, b.map_t, 1, "tonic_classifier"},
-                            {&n->head_genre, &n->head_genre_t, b.hid_g, b.map_g, 2, "genre_classifier"}};
+        struct HeadRun { const std::vector<PackedConv>* ce; const std::vector<PackedConv>* ct; int kind; const char* nm; };
+        HeadRun heads[3] = {{&n->head_key, &n->head_key_t, 1, "key_classifier"},
+                            {&n->head_tonic, &n->head_tonic_t, 1, "tonic_classifier"},
+                            {&n->head_genre, &n->head_genre_t, 2, "genre_classifier"}};
         int Tm = Tf;
         bool head_planes_ready = false;           // training: the f16 hi / lo planes of the pooled features (b.feat_cl) exist
         int pooled_heads = 0;                     // heads whose outputs conv_head1_bf16_kernel already wrote
         // key / tonic heads: the first convolution (16 -> 32 channels, most of a head's work) on the bf16 kernel; both read the same
         // channels-last copy of the features
         unsigned short* feat_cl = b.feat_cl;
-        if (head_bf && !pc_fused) run_nchw_to_cl16(feat, n->final_ch, B, Tf, feat_cl, s);
+        if (head_bf && !pc_fused) run_nchw_to_cl16(feat.p, n->final_ch, B, Tf, feat_cl, s);
         const bool head1_bf = r.heads == HeadForm::Head1 || r.heads == HeadForm::Fused, genre_bf = r.genre_bf;
         const int T1 = r.T1, T2 = r.T2, TpB = r.TpB;
         // per-head tables of the two bf16 paths (key, tonic, genre), and the pooling of a finished map
@@ -2931,15 +2886,15 @@ struct Fwd {
         } else if (head1_bf) {
             Head1BfArgs ha;
             std::memset(&ha, 0, sizeof(ha));
-            float* hids[3] = {b.hid_k, b.hid_t, b.hid_g};
             for (int h = 0; h < nh_bf; ++h) {
                 const PackedConv& p0 = (*hconv[h])[0];
                 const PackedConv& p1 = (*hconv[h])[1];
-                unsigned short* planes = reinterpret_cast<unsigned short*>(hids[h]);
-                // the key and the tonic head read the same features with the same geometry: one launch, blockIdx.y picks the head
-                if (h == 0 && (rc = run_pc_bf16(n, p0, feat_cl, B, Tf, false, true, nullptr, planes, s, "conv_pc_bf16_kernel/head", &(*hconv[1])[0],
-                                                reinterpret_cast<unsigned short*>(hids[1]))))
-                    return rc;
+                unsigned short* planes = reinterpret_cast<unsigned short*>(b.head_out(false, h, 0, false).p);
+                if (h == 0) {   // the key and the tonic head read the same features with the same geometry: one launch, blockIdx.y picks the head
+                    PcBf16Opts tonic;
+                    tonic.pc2 = &(*hconv[1])[0]; tonic.planes_out2 = reinterpret_cast<unsigned short*>(b.head_out(false, 1, 0, false).p);
+                    if ((rc = run_pc_bf16(n, p0, feat_cl, B, Tf, false, true, nullptr, planes, s, "conv_pc_bf16_kernel/head", tonic))) return rc;
+                }
                 if (h == 2 && (rc = run_pc_bf16(n, p0, feat_cl, B, Tf, false, true, nullptr, planes, s, "conv_pc_bf16_kernel/genre_head")))
                     return rc;
                 ha.xh[h] = planes; ha.xl[h] = planes + static_cast<long long>(B) * 12 * T1 * 32;
@@ -2967,34 +2922,31 @@ struct Fwd {
             Tm = T2;
         }
         for (int h = head1_bf ? nh_bf : 0; h < (c.genre ? 3 : 2); ++h) {
-            const float* src = feat;
-            const float* src_aff = feat_aff;
-            int hc = n->final_ch, Tcur = Tf;
-            const size_t hid_half = static_cast<size_t>(B) * 2 * n->final_ch * 12 * Tf;
             for (int j = 0; j < c.head_layers; ++j) {
                 const PackedConv& pe = (*heads[h].ce)[j];
                 const bool lastj = j == c.head_layers - 1;
-                float* dst = lastj ? heads[h].map : (train ? b.hst[h][j] : heads[h].hid + (j & 1) * hid_half);
-                float* aff = (!train || lastj) ? nullptr : b.aff_hst[h][j];
+                // conv j reads the features or conv j - 1's output, hc channels of Tcur frames
+                const Slot src = j == 0 ? feat : b.head_out(train, h, j - 1, false);
+                const int hc = j == 0 ? n->final_ch : (*heads[h].ce)[j - 1].cout, Tcur = Tf - j * (c.kernel_size - 1);
+                const Slot dst = b.head_out(train, h, j, lastj);
                 if (head_bf && h < 2 && j == 0) {
-                    if ((rc = run_pc_bf16(n, pe, feat_cl, B, Tcur, false, true, dst, nullptr, s, "conv_pc_bf16_kernel/head"))) return rc;
-                    src = dst; src_aff = aff; hc = pe.cout; Tcur -= c.kernel_size - 1;
+                    if ((rc = run_pc_bf16(n, pe, feat_cl, B, Tcur, false, true, dst.p, nullptr, s, "conv_pc_bf16_kernel/head"))) return rc;
                     continue;
                 }
                 if (train && j == 0 && !lastj && pc_f16x3_ok((*heads[h].ct)[0], Tcur, false)) {   // the heads' first convs: f16 x 3 MFMA
                     const PackedConv& pt = (*heads[h].ct)[0];
                     if (!head_planes_ready) {               // one conversion of the pooled features serves the three heads
-                        run_nchw_to_cl16_f16x2(src, hc, B, Tcur, src_aff, b.feat_cl, s);
+                        run_nchw_to_cl16_f16x2(src.p, hc, B, Tcur, src.aff, b.feat_cl, s);
                         head_planes_ready = true;
                     }
                     const int bn = bn_of(std::string(heads[h].nm) + ".1");
-                    if ((rc = run_pc_bf16(n, pt, b.feat_cl, B, Tcur, false, false, dst, nullptr, s,
-                                          h == 2 ? "conv_pc_f16x3_kernel/genre_head" : "conv_pc_f16x3_kernel/head", nullptr, nullptr, true,
-                                          b.stats + 2 * n->bns[bn].ch_off, 2 * n->bn_channels)))
+                    PcBf16Opts o;
+                    o.f16x3 = true; o.stats = b.stats + 2 * n->bns[bn].ch_off; o.stats_stride = 2 * n->bn_channels;
+                    if ((rc = run_pc_bf16(n, pt, b.feat_cl, B, Tcur, false, false, dst.p, nullptr, s,
+                                          h == 2 ? "conv_pc_f16x3_kernel/genre_head" : "conv_pc_f16x3_kernel/head", o)))
                         return rc;
                     const int H_out = heads[h].kind == 2 ? 12 - pt.kh + 1 : 12;
-                    finalize_bn(bn, static_cast<double>(B) * H_out * (Tcur - pt.kw + 1), aff);
-                    src = dst; src_aff = aff; hc = pe.cout; Tcur -= c.kernel_size - 1;
+                    finalize_bn(bn, static_cast<double>(B) * H_out * (Tcur - pt.kw + 1), dst.aff);
                     continue;
                 }
                 if (train && lastj && j > 0 && pe.cout == 1 && pe.kw == 7 && !n->raw_w_off.empty()) {   // cin -> 1: one workgroup per clip, f32 VALU
@@ -3008,19 +2960,17 @@ struct Fwd {
                             hl_attr.mark();
                         }
                         ake::ProfScope ps(h == 2 ? "conv_head_last_kernel/genre" : "conv_head_last_kernel", s);
-                        hipLaunchKernelGGL(conv_head_last_kernel, dim3(B), dim3(384), lds, s, src, src_aff, n->blob_dev + n->raw_w_off[wi->second],
-                                           n->blob_dev + n->raw_w_off[bi->second], dst, hc, pe.kh, heads[h].kind == 2 ? 0 : 1, Tcur, Tcur - 6);
-                        src = dst; src_aff = aff; hc = pe.cout; Tcur -= c.kernel_size - 1;
+                        hipLaunchKernelGGL(conv_head_last_kernel, dim3(B), dim3(384), lds, s, src.p, src.aff, n->blob_dev + n->raw_w_off[wi->second],
+                                           n->blob_dev + n->raw_w_off[bi->second], dst.p, hc, pe.kh, heads[h].kind == 2 ? 0 : 1, Tcur, Tcur - 6);
                         continue;
                     }
                 }
                 if ((rc = conv(pe, train ? (*heads[h].ct)[j] : pe, lastj ? "" : std::string(heads[h].nm) + "." + std::to_string(3 * j + 1),
-                               heads[h].kind, Src{src, hc, nullptr, 0, 0}, src_aff, B, 12, Tcur, false, dst, pe.cout, 0, aff,
+                               heads[h].kind, Src{src.p, hc, nullptr, 0, 0}, src.aff, B, 12, Tcur, false, dst.p, pe.cout, 0, dst.aff,
                                h == 2 ? "conv_mfma_kernel/genre_head" : "conv_mfma_kernel/head")))
                     return rc;
-                src = dst; src_aff = aff; hc = pe.cout; Tcur -= c.kernel_size - 1;
             }
-            Tm = Tcur;
+            Tm = Tf - c.head_layers * (c.kernel_size - 1);
         }
         if (c.local > 0) {   // ---- --local: sliding-window max over the maps, per-frame outputs (models.py:720-722, 805-810) ----
             AKE_REQUIRE(Tm >= c.local, AKE_ERR_INVALID, "pcnet --local: %d map frames are fewer than the pooling window %d", Tm, c.local);
@@ -3114,11 +3064,7 @@ int ake_pcnet_backward_f32(const ake_pcnet* n, const float* mel, int batch, int 
     Bwd bw{n, b, s, b.gslots, batch};
     rc = bw.run(mel, seq_length, d_key, d_tonic, d_genre, key_out);
     if (rc) return rc;
-    {
-        ake::ProfScope ps("grad_reduce_kernel", s);
-        hipLaunchKernelGGL(grad_reduce_kernel, dim3(static_cast<unsigned>((n->grad_floats + 255) / 256)), dim3(256), 0, s, b.gslots, grads_out,
-                           static_cast<long long>(n->grad_floats), accumulate ? 1 : 0);
-    }
+    launch_flat("grad_reduce_kernel", grad_reduce_kernel, s, n->grad_floats, b.gslots, grads_out, static_cast<long long>(n->grad_floats), accumulate ? 1 : 0);
     AKE_HIP_CHECK(hipGetLastError());
     return AKE_OK;
 }
@@ -3186,21 +3132,21 @@ static int train_site_lookup(const ake_pcnet* n, const Buffers& b, const std::st
     int64_t C = 0, H = 0, Tn = 0;
     long long stride = 0;
     bool hit = false;            // (the pointers are null in the dry run of ake_pcnet_tap_info)
-    auto found = [&](float* z_, float* aff_, int64_t C_, int64_t H_, int64_t T_, long long stride_ = 0) { z = z_; aff = aff_; C = C_; H = H_; Tn = T_; stride = stride_; hit = true; };
+    auto found = [&](Slot t_, int64_t C_, int64_t H_, int64_t T_, long long stride_ = 0) { z = t_.p; aff = t_.aff; C = C_; H = H_; Tn = T_; stride = stride_; hit = true; };
     for (int i = 0; i < L && !hit; ++i) {
         const std::string m = "model." + std::to_string(i) + ".";
         const LayerDims& d = n->dims[i];
         const int Ti = b.Tl[i];
-        if (site == m + "pool_semi_b") found(b.semi_raw[i], b.aff_semi[i], i == 0 ? 1 : d.out_p, P / 3, Ti);
-        if (i >= 1 && site == m + "up_sixth_b") found(b.psix[i], b.aff_p2pin[i] ? b.aff_p2pin[i] + 3 * d.prev_p : nullptr, d.prev_pc, 36, Ti);
+        if (site == m + "pool_semi_b") found(Slot{b.semi_raw[i], b.aff_semi[i]}, i == 0 ? 1 : d.out_p, P / 3, Ti);
+        if (i >= 1 && site == m + "up_sixth_b") found(Slot{b.psix[i], b.aff_p2pin[i] ? b.aff_p2pin[i] + 3 * d.prev_p : nullptr}, d.prev_pc, 36, Ti);
         for (int j = 0; j < c.conv_layers && !hit; ++j) {
             const std::string bn = "layer." + std::to_string(3 * j + 1);
-            if (i >= 1 && site == m + "p2p." + bn) found(b.pst[i][j], b.aff_pst[i][j], d.out_p, P, Ti);
+            if (i >= 1 && site == m + "p2p." + bn) found(b.p_out(true, i, j), d.out_p, P, Ti);
             if (site == m + "pc2pc." + bn) {
                 // layer 0's last convolution of a deeper net writes channels [0, n_filters) of layer 1's concat buffer (table: aff_cat[1])
                 if (i == 0 && L > 1 && j == c.conv_layers - 1) {
-                    found(b.cat[1], b.aff_cat[1], c.n_filters, 12, Ti, static_cast<long long>(n->dims[1].prev_pc + n->dims[1].out_p) * 12 * Ti);
-                } else found(b.pcst[i][j], b.aff_pcst[i][j], i == 0 ? c.n_filters : d.out_pc, 12, Ti);
+                    found(b.cat_slot(true, 1), c.n_filters, 12, Ti, static_cast<long long>(n->dims[1].prev_pc + n->dims[1].out_p) * 12 * Ti);
+                } else found(b.pc_out(true, i, j), i == 0 ? c.n_filters : d.out_pc, 12, Ti);
             }
         }
     }
@@ -3209,7 +3155,7 @@ static int train_site_lookup(const ake_pcnet* n, const Buffers& b, const std::st
     for (int h = 0; h < (c.genre ? 3 : 2) && !hit; ++h)
         for (int j = 0; j + 1 < c.head_layers; ++j)
             if (site == std::string(head_nm[h]) + "." + std::to_string(3 * j + 1))
-                found(b.hst[h][j], b.aff_hst[h][j], (*head_t[h])[j].cout, 12, b.Tf - (j + 1) * (c.kernel_size - 1));
+                found(b.head_out(true, h, j, false), (*head_t[h])[j].cout, 12, b.Tf - (j + 1) * (c.kernel_size - 1));
     AKE_REQUIRE(hit && Tn >= 1, AKE_ERR_INVALID, "tap: 'train:%s' names no BatchNorm of this net", t.c_str());
     if (want_aff) { *p = aff; shape[0] = C; shape[1] = 3; shape[2] = 1; shape[3] = 1; }
     else { *p = z; shape[0] = batch; shape[1] = C; shape[2] = H; shape[3] = Tn; if (clip_stride) *clip_stride = stride; }
@@ -3272,7 +3218,7 @@ static int tap_lookup(const ake_pcnet* n, const char* name, int batch, int frame
                     ake::set_error("tap: '%s' stays in LDS (layer 0 runs as one launch); ake_debug_keep_taps(1) before the forward writes it", name);
                     return AKE_ERR_INVALID;
                 }
-                return set((j & 1) ? b.pcb[i] : b.pca[i], i == 0 ? c.n_filters : d.out_pc, 12, Ti);
+                return set(b.pc_out(false, i, j).p, i == 0 ? c.n_filters : d.out_pc, 12, Ti);
             }
             if (i >= 1 && nm == m + "p2p.layer." + std::to_string(3 * j + 2)) {
                 if (j < last_j - 1) break;
@@ -3282,7 +3228,7 @@ static int tap_lookup(const ake_pcnet* n, const char* name, int batch, int frame
                 }
                 // inference keeps the stack's intermediate activations as channels-last split-bf16 planes (conv_p2p_f16_kernel)
                 if (j < last_j && r.p[i].stack == PStack::F16 && channels_last) *channels_last = 2;      // one f16 plane
-                return set((j & 1) ? b.pb[i] : b.pa[i], d.out_p, P, Ti);
+                return set(b.p_out(false, i, j).p, d.out_p, P, Ti);
             }
         }
         if (i >= 1 && nm == m + "up_sixth_a") {

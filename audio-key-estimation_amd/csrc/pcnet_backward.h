@@ -51,6 +51,19 @@ struct Bwd {
         amax_of = g; amax_cell = cell;
     }
 
+    // A weight-gradient kernel of n_wg workgroups and n_w weights leaves every workgroup's own sums in b.wg_partial where that buffer holds
+    // n_wg * n_w floats (see WgradArgs::partial), else it adds to dW itself.  use_partial decides and, where it says yes, points the
+    // kernel's two arguments at the buffer; reduce_partial, after the kernel, adds the partial sums to dW in workgroup order.
+    bool use_partial(long long n_wg, long long n_w, float*& partial, long long& partial_stride) const {
+        if (!b.wg_partial || n_wg * n_w > static_cast<long long>(b.wg_partial_floats)) return false;
+        partial = b.wg_partial; partial_stride = n_w;
+        return true;
+    }
+    void reduce_partial(long long n_wg, long long n_w, gfx_t* dW) {
+        ake::ProfScope ps("wgrad_partial_reduce_kernel", s);
+        hipLaunchKernelGGL(wgrad_partial_reduce_kernel, dim3(static_cast<unsigned>((n_w + 63) / 64)), dim3(1024), 0, s, b.wg_partial, static_cast<int>(n_wg), n_w, dW);
+    }
+
     // weight gradient of one convolution: dW += corr(act(input), dz)
     // zero_pad (kind 0 only): the convolution pads rows AND frames with zeros (--denseblock's plain Conv2d) instead of wrapping both
     int wgrad(const PackedConv& pc, int kind, Src src, const float* in_aff, int H, int T_in, bool same_time, const float* dz, int dz_ctot,
@@ -73,16 +86,12 @@ struct Bwd {
                 attr_set.mark();
             }
             const long long n_w = static_cast<long long>(8) * pc.cin * 49, n_wg = static_cast<long long>(grid.x) * B;
-            const bool use_partial = b.wg_partial && n_wg * n_w <= static_cast<long long>(b.wg_partial_floats);
-            if (use_partial) { w.partial = b.wg_partial; w.partial_stride = n_w; }
+            const bool partial = use_partial(n_wg, n_w, w.partial, w.partial_stride);
             {
                 ake::ProfScope ps("conv_wgrad_p2p_bf16_kernel", s);
                 hipLaunchKernelGGL(conv_wgrad_p2p_bf16_kernel, grid, dim3(256), lds, s, w);
             }
-            if (use_partial) {
-                ake::ProfScope ps("wgrad_partial_reduce_kernel", s);
-                hipLaunchKernelGGL(wgrad_partial_reduce_kernel, dim3(static_cast<unsigned>((n_w + 63) / 64)), dim3(1024), 0, s, b.wg_partial, static_cast<int>(n_wg), n_w, dW);
-            }
+            if (partial) reduce_partial(n_wg, n_w, dW);
             return AKE_OK;
         }
         // 12 x 7 pitch-class convolutions (the pitch-class stacks, the heads' first convs): split-bf16 MFMA, one workgroup per (clip, 16 x 16
@@ -101,26 +110,21 @@ struct Bwd {
                 w.n_co_blocks = (pc.cout + 15) / 16;
                 w.n_seg = (T_out + kWpSeg - 1) / kWpSeg;
                 w.dW = dW; w.slot_stride = static_cast<long long>(n->grad_floats);
-                const long long n_w = static_cast<long long>(pc.cout) * pc.cin * 84;
-                const long long n_wg = static_cast<long long>(B) * w.n_seg;
-                const bool use_partial = b.wg_partial && n_wg * n_w <= static_cast<long long>(b.wg_partial_floats);
-                if (use_partial) { w.partial = b.wg_partial; w.partial_stride = n_w; }
                 const size_t lds = static_cast<size_t>(2) * 12 * 16 * (w.AP + w.ZP) * sizeof(unsigned short);
                 static ake::DeviceOnce attr_set;
                 if (attr_set.need()) {
                     AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_pc_f16x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
                     attr_set.mark();
                 }
+                const long long n_w = static_cast<long long>(pc.cout) * pc.cin * 84, n_wg = static_cast<long long>(B) * w.n_seg;
+                const bool partial = use_partial(n_wg, n_w, w.partial, w.partial_stride);
                 {
                     const char* slash = std::strrchr(name, '/');
                     const std::string pname = std::string("conv_wgrad_pc_f16x3_kernel") + (slash ? slash : "");
                     ake::ProfScope ps(pname.c_str(), s);
                     hipLaunchKernelGGL(conv_wgrad_pc_f16x3_kernel, dim3(w.n_seg * w.n_co_blocks, (pc.cin + 15) / 16, B), dim3(512), lds, s, w);
                 }
-                if (use_partial) {
-                    ake::ProfScope ps("wgrad_partial_reduce_kernel", s);
-                    hipLaunchKernelGGL(wgrad_partial_reduce_kernel, dim3(static_cast<unsigned>((n_w + 63) / 64)), dim3(1024), 0, s, b.wg_partial, static_cast<int>(n_wg), n_w, dW);
-                }
+                if (partial) reduce_partial(n_wg, n_w, dW);
                 return AKE_OK;
             }
         }
@@ -176,10 +180,8 @@ struct Bwd {
             dim3 grid((tiles + wa.rt_per_block - 1) / wa.rt_per_block, c_groups, B), block(512);
             const size_t lds = lds_of(R, TT);
             // partial sums per workgroup + an ordered reduction when the scratch buffer holds them (see WgradArgs::partial)
-            const long long n_w = static_cast<long long>(co_n) * (src.c0 + src.c1) * KK;
-            const long long n_wg = static_cast<long long>(grid.x) * B;
-            const bool use_partial = b.wg_partial && n_wg * n_w <= static_cast<long long>(b.wg_partial_floats);
-            if (use_partial) { wa.partial = b.wg_partial; wa.partial_stride = n_w; }
+            const long long n_w = static_cast<long long>(co_n) * (src.c0 + src.c1) * KK, n_wg = static_cast<long long>(grid.x) * B;
+            const bool partial = use_partial(n_wg, n_w, wa.partial, wa.partial_stride);
             bool launched = false;
             {
                 ake::ProfScope ps(name, s);
@@ -191,10 +193,7 @@ struct Bwd {
                 ake::set_error("wgrad %s: no kernel for cout=%d taps=%d", name, co_n, KK);
                 return AKE_ERR_UNSUPPORTED;
             }
-            if (use_partial) {
-                ake::ProfScope ps("wgrad_partial_reduce_kernel", s);
-                hipLaunchKernelGGL(wgrad_partial_reduce_kernel, dim3(static_cast<unsigned>((n_w + 63) / 64)), dim3(1024), 0, s, b.wg_partial, static_cast<int>(n_wg), n_w, wa.dW);
-            }
+            if (partial) reduce_partial(n_wg, n_w, wa.dW);
         }
         return AKE_OK;
     }
@@ -211,17 +210,21 @@ struct Bwd {
         g.H_out = H;
         if (kind == 0 && !accumulate && dst_coff == 0 && dst_ctot == pd.cout && T_dz == T_in && pd.bf_off >= 0) {
             const P2pX3Plan x3 = p2p_f16x3_plan(pd.cin, 0, pd.cout, B, H, T_dz, !(reinterpret_cast<uintptr_t>(dst) & 15));
-            if (x3.ok)
+            if (x3.ok) {
+                P2pX3Opts o;
+                o.in_amax = amax_for(dz);
                 return run_p2p_f16x3(n, x3, pd.bf_off, Src{dz, pd.cin, nullptr, 0, 0}, nullptr, nullptr, B, H, T_dz, dst, pd.cout, nullptr, 0, s,
-                                     "conv_p2p_f16x3_kernel/p2p_dgrad", amax_for(dz));
+                                     "conv_p2p_f16x3_kernel/p2p_dgrad", o);
+            }
         }
         // pitch-class stacks of layers >= 1 (same-size 12 x 7 convolutions, 16 gradient channels): the f16 x 3 form of conv_pc_bf16_kernel with
         // the transposed + flipped weights (f32-equivalent products; the f32 MFMA kernel took 0.17 ms per convolution and 256 clips)
         if (kind == 1 && same_time && planes_scratch && !accumulate && dst_coff == 0 && dst_ctot == pd.cout && T_dz == T_in && H == 12 &&
             pc_f16x3_ok(pd, T_dz, true)) {
             run_nchw_to_cl16_f16x2(dz, pd.cin, B, T_dz, nullptr, planes_scratch, s, 0, amax_for(dz));
-            return run_pc_bf16(n, pd, planes_scratch, B, T_dz, true, false, dst, nullptr, s, "conv_pc_f16x3_kernel/pc2pc_dgrad", nullptr, nullptr, true,
-                               nullptr, 0, amax_for(dz));
+            PcBf16Opts o;
+            o.f16x3 = true; o.in_amax = amax_for(dz);
+            return run_pc_bf16(n, pd, planes_scratch, B, T_dz, true, false, dst, nullptr, s, "conv_pc_f16x3_kernel/pc2pc_dgrad", o);
         }
         // the heads' first convolutions (16 features -> 32 channels, "valid" in time): 32 gradient channels as two 16-channel halves on the same
         // kernel, full correlation, the second half (and every head after the first) adding to the feature gradient.  Maps longer than its LDS
@@ -239,8 +242,9 @@ struct Bwd {
             }
             return AKE_OK;
         }
-        return run_conv(n, pd, kind == 0 ? 0 : 1, Src{dz, pd.cin, nullptr, 0, 0}, B, H, T_dz, true, false, dst, dst_ctot, dst_coff, s, name,
-                        nullptr, nullptr, &g, accumulate);
+        ConvOpts o;
+        o.geom = &g; o.accumulate = accumulate;
+        return run_conv(n, pd, kind == 0 ? 0 : 1, Src{dz, pd.cin, nullptr, 0, 0}, B, H, T_dz, true, false, dst, dst_ctot, dst_coff, s, name, o);
     }
 
     // --denseblock (models.py:456-648): one block backwards, in place on g_feat [B][ctot][H][T] = dL/d(features), complete for the channels the
@@ -264,8 +268,10 @@ struct Bwd {
             if (!dp.b2.empty()) bias_grad(g_feat, ctot, cj, nf, static_cast<int>(HT), grad_of(dp.b2));
             {
                 const ConvGeom g2 = kind == 0 ? ConvGeom{k - 1 - k / 2, k - 1 - k / 2, T, H, 0} : ConvGeom{11, k - 1 - k / 2, T, H, 0};
+                ConvOpts o;
+                o.geom = &g2; o.rows_zero = kind == 0;
                 if ((rc = run_conv(n, dp.d2, kind, Src{g_feat + static_cast<long long>(cj) * HT, nf, nullptr, 0, 0, ctot}, B, H, T, true, false, g_bott, bott, 0, s,
-                                   dname, nullptr, nullptr, &g2, false, nullptr, kind == 0)))
+                                   dname, o)))
                     return rc;
             }
             bn_block_backward(dp.norm2, g_bott, botts[j], aff2s[j], bott, 0, static_cast<int>(HT));
@@ -275,15 +281,14 @@ struct Bwd {
             if ((rc = wgrad(t1, kind, Src{feat, cj, nullptr, 0, 0, ctot}, aff1s[j], H, T, true, g_bott, bott, 0, grad_of(dp.w1), wname, kind == 0))) return rc;
             {
                 const ConvGeom g1 = kind == 0 ? ConvGeom{0, 3, T, H, 0} : ConvGeom{11, 0, T, H, 0};   // (1 x 1: the centre of the 7 stored taps; 12 x 1: the row-k form, no frame extent)
-                if ((rc = run_conv(n, dp.d1, kind, Src{g_bott, bott, nullptr, 0, 0}, B, H, T, true, false, g_scr, ctot, 0, s, dname, nullptr, nullptr,
-                                   &g1, false, nullptr, kind == 0)))
-                    return rc;
+                ConvOpts o;
+                o.geom = &g1; o.rows_zero = kind == 0;
+                if ((rc = run_conv(n, dp.d1, kind, Src{g_bott, bott, nullptr, 0, 0}, B, H, T, true, false, g_scr, ctot, 0, s, dname, o))) return rc;
             }
             bn_block_backward(dp.norm1, g_scr, feat, aff1s[j], ctot, 0, static_cast<int>(HT));
             {
                 const long long total = static_cast<long long>(B) * cj * HT;
-                ake::ProfScope ps("add_channels_kernel", s);
-                hipLaunchKernelGGL(add_channels_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, g_feat, ctot, g_scr, ctot, cj, HT, total);
+                launch_flat("add_channels_kernel", add_channels_kernel, s, total, g_feat, ctot, g_scr, ctot, cj, HT, total);
             }
         }
         return AKE_OK;
@@ -304,9 +309,8 @@ struct Bwd {
                 const long long total = static_cast<long long>(B) * ctd * 12 * ((Tl / tp) + (Tl % tp ? 1 : 0));
                 const bool last = li == L - 1;
                 const int up_ctot = last ? ctd : n->dims[li + 1].prev_pc + n->dims[li + 1].out_p + g;
-                ake::ProfScope ps("time_pool_bwd_kernel", s);
-                hipLaunchKernelGGL(time_pool_bwd_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, last ? b.g_pcf : b.g_cat[li + 1], b.cat[li],
-                                   static_cast<const float*>(nullptr), b.g_cat[li], ctd, 12, Tl, tp, up_ctot, 0, total, 0);
+                launch_flat("time_pool_bwd_kernel", time_pool_bwd_kernel, s, total, last ? b.g_pcf : b.g_cat[li + 1], b.cat[li], nullptr, b.g_cat[li], ctd, 12, Tl, tp,
+                            up_ctot, 0, total, 0);
             }
             float* scr_pc = b.g_pc[li];                      // [B][ctd][12][Tl] scratch (g_pc[li] holds two of them)
             if ((rc = dense_block_backward(n->dense_pc[li], 1, b.cat[li], ctd, d.prev_pc + d.out_p, 12, Tl, b.g_cat[li], b.dn_gbott_pc, scr_pc, b.dn_bott_pc[li],
@@ -318,17 +322,15 @@ struct Bwd {
             if ((rc = semi_backward(li, b.pa[li], nullptr, b.g_cat[li], ctd, d.prev_pc, g_p))) return rc;
             if (li < L - 1) {   // second consumer of an inner layer's pitch features: their time-pooled copy is the next pitch block's input (channels [0, out_p))
                 const long long total = static_cast<long long>(B) * d.out_p * P * ((Tl / tp) + (Tl % tp ? 1 : 0));
-                ake::ProfScope ps("time_pool_bwd_kernel", s);
-                hipLaunchKernelGGL(time_pool_bwd_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, b.g_p[li + 1], b.pa[li], static_cast<const float*>(nullptr),
-                                   g_p, d.out_p, P, Tl, tp, n->dims[li + 1].out_p, 0, total, 1);
+                launch_flat("time_pool_bwd_kernel", time_pool_bwd_kernel, s, total, b.g_p[li + 1], b.pa[li], nullptr, g_p, d.out_p, P, Tl, tp, n->dims[li + 1].out_p, 0,
+                            total, 1);
             }
             if ((rc = dense_block_backward(n->dense_p[li], 0, b.pa[li], d.out_p, d.prev_p + d.prev_pc, P, Tl, g_p, b.dn_gbott_p, scr_p, b.dn_bott_p[li], b.dn_aff1_p[li],
                                            b.dn_aff2_p[li], "conv_wgrad_kernel/p2p", "conv_mfma_kernel/p2p_dgrad")))
                 return rc;
             {   // repeat (x P / 36) backward: channels [prev_p, prev_p + prev_pc) of the pitch block's input gradient -> the up_sixth map
                 const long long total = static_cast<long long>(B) * d.prev_pc * 36 * Tl;
-                ake::ProfScope ps("repeat_sum_kernel", s);
-                hipLaunchKernelGGL(repeat_sum_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, g_p, b.g_psix[li], d.out_p, d.prev_p, d.prev_pc, P, Tl, total);
+                launch_flat("repeat_sum_kernel", repeat_sum_kernel, s, total, g_p, b.g_psix[li], d.out_p, d.prev_p, d.prev_pc, P, Tl, total);
             }
             bn_block_backward(m + "up_sixth_b", b.g_psix[li], b.psix[li], b.aff_p2pin[li] + 3 * d.prev_p, d.prev_pc, 0, 36 * Tl);
             {
@@ -338,9 +340,8 @@ struct Bwd {
             }
             {
                 const long long total = static_cast<long long>(B) * d.prev_pc * 12 * Tl;
-                ake::ProfScope ps("up_sixth_bwd_data_kernel", s);
-                hipLaunchKernelGGL(up_sixth_bwd_data_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, b.g_psix[li], raw_of(m + "up_sixth.weight"),
-                                   b.g_cat[li], ctd, d.prev_pc, Tl, total);
+                launch_flat("up_sixth_bwd_data_kernel", up_sixth_bwd_data_kernel, s, total, b.g_psix[li], raw_of(m + "up_sixth.weight"), b.g_cat[li], ctd, d.prev_pc, Tl,
+                            total);
             }
         }
         // layer 0's block: channels [0, 1 + g) of layer 1's buffer, input = the fold (channel 0)
@@ -400,8 +401,7 @@ struct Bwd {
             const std::string bp = prefix + std::to_string(3 + r) + ".";
             {
                 const long long total = static_cast<long long>(B) * C * H * Tn;
-                ake::ProfScope ps("res_act_bwd_kernel", s);
-                hipLaunchKernelGGL(res_act_bwd_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, g, z[3 + 3 * r], gs, total);
+                launch_flat("res_act_bwd_kernel", res_act_bwd_kernel, s, total, g, z[3 + 3 * r], gs, total);
             }
             // b2 has no activation of its own: its table carries slope 1, so the generic block applies LeakyReLU' = 1
             bn_block_backward(bp + "b2", g, z[2 + 3 * r], aff[2 + 3 * r], C, 0, H * Tn);
@@ -458,8 +458,9 @@ struct Bwd {
             hipLaunchKernelGGL(head_pool_bwd_kernel, dim3((B * 12 + 63) / 64, 3), dim3(64), 0, s, pa);
         }
         // features feeding the heads: pcf (final) for L > 1, the raw last pc2pc output (+affine) for L == 1
-        const float* feat = L > 1 ? b.pcf : (c.denseblock ? b.fold0 : b.pcst[0].back());      // (--denseblock, one layer: the block's feature buffer itself)
-        const float* feat_aff = (L > 1 || c.denseblock) ? nullptr : b.aff_pcst[0].back();
+        const Slot feat_s = L > 1 ? Slot{b.pcf, nullptr} : (c.denseblock ? Slot{b.fold0, nullptr} : b.pc_last(0));      // (--denseblock, one layer: the block's feature buffer itself)
+        const float* feat = feat_s.p;
+        const float* feat_aff = feat_s.aff;
         float* g_feat = L > 1 ? b.g_pcf : b.g_pc[0];          // gradient w.r.t. the head input activation
         AKE_HIP_CHECK(hipMemsetAsync(g_feat, 0, sizeof(float) * B * fin * 12 * Tf, s));
 
@@ -484,10 +485,11 @@ struct Bwd {
                 const std::string cname = std::string(heads[h].nm) + "." + std::to_string(3 * j) + (heads[h].conv2d ? ".conv2d" : "");
                 const int T_in = Tcur + c.kernel_size - 1;
                 const int H_out = heads[h].kind == 2 ? 12 - pc.kh + 1 : 12;
-                if (j < nl - 1) bn_block_backward(std::string(heads[h].nm) + "." + std::to_string(3 * j + 1), g, b.hst[h][j], b.aff_hst[h][j], pc.cout, 0, 12 * Tcur);
+                const Slot z = b.head_out(true, h, j, j == nl - 1), zin = j == 0 ? Slot{} : b.head_out(true, h, j - 1, false);
+                if (j < nl - 1) bn_block_backward(std::string(heads[h].nm) + "." + std::to_string(3 * j + 1), g, z.p, z.aff, pc.cout, 0, 12 * Tcur);
                 else bias_grad(g, pc.cout, 0, pc.cout, 12 * Tcur, grad_of(cname + ".bias"));   // row 11 of the genre map gradient is zero
-                Src in = j == 0 ? Src{feat, fin, nullptr, 0, 0} : Src{b.hst[h][j - 1], ct[j - 1].cout, nullptr, 0, 0};
-                const float* in_aff = j == 0 ? feat_aff : b.aff_hst[h][j - 1];
+                Src in = j == 0 ? Src{feat, fin, nullptr, 0, 0} : Src{zin.p, ct[j - 1].cout, nullptr, 0, 0};
+                const float* in_aff = j == 0 ? feat_aff : zin.aff;
                 // the genre gradient maps carry 12 rows (the last one zero), so circular rows reproduce its "valid" rows exactly
                 const int kind_w = 1;
                 if ((rc = wgrad(pc, kind_w, in, in_aff, 12, T_in, false, g, pc.cout, 0, grad_of(cname + ".weight"), "conv_wgrad_kernel/head"))) return rc;
@@ -513,9 +515,8 @@ struct Bwd {
         float* g_last2 = b.g_pc[i] + static_cast<size_t>(B) * (i == 0 ? c.n_filters : d.out_pc) * 12 * Ti;
         if (L > 1) {
             const long long total = static_cast<long long>(B) * d.out_pc * 12 * ((Ti / tp) + (Ti % tp ? 1 : 0));
-            ake::ProfScope ps("time_pool_bwd_kernel", s);
-            hipLaunchKernelGGL(time_pool_bwd_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, b.g_pcf, b.pcst[i].back(),
-                               b.aff_pcst[i].back(), g_last, d.out_pc, 12, Ti, tp, d.out_pc, 0, total, 0);
+            launch_flat("time_pool_bwd_kernel", time_pool_bwd_kernel, s, total, b.g_pcf, b.pc_last(i).p, b.pc_last(i).aff, g_last, d.out_pc, 12, Ti, tp, d.out_pc,
+                        0, total, 0);
         }
         if (L == 1) {
             // single layer: pc2pc0 stack straight down to fold0
@@ -544,20 +545,19 @@ struct Bwd {
             if (rc) return rc;
             // channels [prev_pc, ctot) of g_cat: gradient of the folded semitone features -> pool_semi(li) -> pitch stream
             const std::vector<float*>& zp = b.pst[li];
+            const Slot zl = b.p_last(li);                         // the pitch stack's output
             float* g_p = b.g_p[li];
             float* g_p2 = b.g_p[li] + static_cast<size_t>(B) * dl.out_p * P * Tl;
             if (c.stay_sixth) {   // models.py:391: the stack's output (semitone resolution) was folded as it is
                 const long long total = static_cast<long long>(B) * dl.out_p * 12 * Tl;
-                ake::ProfScope ps("fold_bwd_kernel", s);
-                hipLaunchKernelGGL(fold_bwd_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, b.g_cat[li], zp.back(),
-                                   b.aff_pst[li].back(), g_p, dl.out_p, Pp / 12, Tl, ctot, dl.prev_pc, total);
-            } else if ((rc = semi_backward(li, zp.back(), b.aff_pst[li].back(), b.g_cat[li], ctot, dl.prev_pc, g_p))) return rc;
+                launch_flat("fold_bwd_kernel", fold_bwd_kernel, s, total, b.g_cat[li], zl.p, zl.aff, g_p, dl.out_p, Pp / 12, Tl, ctot, dl.prev_pc,
+                            total);
+            } else if ((rc = semi_backward(li, zl.p, zl.aff, b.g_cat[li], ctot, dl.prev_pc, g_p))) return rc;
             if (inner) {   // second consumer of an inner layer's pitch stream: its time-pooled copy is the next layer's pitch input (models.py:395)
                 const LayerDims& dn = n->dims[li + 1];
                 const long long total = static_cast<long long>(B) * dl.out_p * Pp * ((Tl / tp) + (Tl % tp ? 1 : 0));
-                ake::ProfScope ps("time_pool_bwd_kernel", s);
-                hipLaunchKernelGGL(time_pool_bwd_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, b.g_pin[li + 1], zp.back(),
-                                   b.aff_pst[li].back(), g_p, dl.out_p, Pp, Tl, tp, c.pc2p_mem ? dn.prev_p : dn.prev_p + dn.prev_pc, 0, total, 1);
+                launch_flat("time_pool_bwd_kernel", time_pool_bwd_kernel, s, total, b.g_pin[li + 1], zl.p, zl.aff, g_p, dl.out_p, Pp, Tl, tp,
+                            c.pc2p_mem ? dn.prev_p : dn.prev_p + dn.prev_pc, 0, total, 1);
             }
             // ---- pitch convs; input = (pitch stream | psix repeated) ----
             // (--pc2p_mem, models.py:145-166: the stack read the pitch stream + the summed up_sixth map, kept in b.pin by the forward)
@@ -570,19 +570,14 @@ struct Bwd {
             // ---- repeat (x P/36) backward, then up_sixth ----
             if (c.stay_sixth) {   // no up_sixth: the pitch classes were repeated as they are
                 const long long total = static_cast<long long>(B) * dl.prev_pc * 12 * Tl;
-                ake::ProfScope ps("repeat_sum_kernel", s);
-                hipLaunchKernelGGL(repeat_sum_add_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, b.g_pin[li], b.g_cat[li],
-                                   dl.prev_p + dl.prev_pc, dl.prev_p, dl.prev_pc, Pp, Tl, ctot, total);
+                launch_flat("repeat_sum_kernel", repeat_sum_add_kernel, s, total, b.g_pin[li], b.g_cat[li], dl.prev_p + dl.prev_pc, dl.prev_p, dl.prev_pc, Pp, Tl, ctot,
+                            total);
             } else if (c.pc2p_mem) {
                 const long long total = static_cast<long long>(B) * dl.prev_pc * 36 * Tl;
-                ake::ProfScope ps("pc2p_mem_bwd_kernel", s);
-                hipLaunchKernelGGL(pc2p_mem_bwd_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, b.g_pin[li], b.g_psix[li],
-                                   dl.prev_p, dl.prev_pc / dl.prev_p, P, Tl, total);
+                launch_flat("pc2p_mem_bwd_kernel", pc2p_mem_bwd_kernel, s, total, b.g_pin[li], b.g_psix[li], dl.prev_p, dl.prev_pc / dl.prev_p, P, Tl, total);
             } else {
                 const long long total = static_cast<long long>(B) * dl.prev_pc * 36 * Tl;
-                ake::ProfScope ps("repeat_sum_kernel", s);
-                hipLaunchKernelGGL(repeat_sum_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, b.g_pin[li], b.g_psix[li],
-                                   dl.prev_p + dl.prev_pc, dl.prev_p, dl.prev_pc, P, Tl, total);
+                launch_flat("repeat_sum_kernel", repeat_sum_kernel, s, total, b.g_pin[li], b.g_psix[li], dl.prev_p + dl.prev_pc, dl.prev_p, dl.prev_pc, P, Tl, total);
             }
             if (!c.stay_sixth) {
                 bn_block_backward(m + "up_sixth_b", b.g_psix[li], b.psix[li], b.aff_p2pin[li] + 3 * dl.prev_p, dl.prev_pc, 0, 36 * Tl);
@@ -594,18 +589,16 @@ struct Bwd {
                 }
                 {
                     const long long total = static_cast<long long>(B) * dl.prev_pc * 12 * Tl;
-                    ake::ProfScope ps("up_sixth_bwd_data_kernel", s);
-                    hipLaunchKernelGGL(up_sixth_bwd_data_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, b.g_psix[li],
-                                       raw_of(m + "up_sixth.weight"), b.g_cat[li], ctot, dl.prev_pc, Tl, total);
+                    launch_flat("up_sixth_bwd_data_kernel", up_sixth_bwd_data_kernel, s, total, b.g_psix[li], raw_of(m + "up_sixth.weight"), b.g_cat[li], ctot,
+                                dl.prev_pc, Tl, total);
                 }
             }
             if (li >= 2) {   // channels [0, prev_pc) of the concat buffer = the time-pooled pitch classes of the layer below (models.py:394)
                 const LayerDims& dp = n->dims[li - 1];
                 const int Tp = b.Tl[li - 1];
                 const long long total = static_cast<long long>(B) * dp.out_pc * 12 * ((Tp / tp) + (Tp % tp ? 1 : 0));
-                ake::ProfScope ps("time_pool_bwd_kernel", s);
-                hipLaunchKernelGGL(time_pool_bwd_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, b.g_cat[li], b.pcst[li - 1].back(),
-                                   b.aff_pcst[li - 1].back(), b.g_pc[li - 1], dp.out_pc, 12, Tp, tp, ctot, 0, total, 0);
+                launch_flat("time_pool_bwd_kernel", time_pool_bwd_kernel, s, total, b.g_cat[li], b.pc_last(li - 1).p, b.pc_last(li - 1).aff, b.g_pc[li - 1],
+                            dp.out_pc, 12, Tp, tp, ctot, 0, total, 0);
             }
         }
         const int ctot = n->dims[1].prev_pc + n->dims[1].out_p;
@@ -641,11 +634,9 @@ struct Bwd {
         if (n->cfg.p2pc_conv) {   // models.py:108-133: the fold is a convolution over the octaves + pool.bn + LeakyReLU
             const long long per_clip = static_cast<long long>(C) * 12 * Tn, total = per_clip * B;
             float* gf = b.g_foldc[layer];
-            {   // the slice of the concat gradient that belongs to the folded channels, dense
-                ake::ProfScope ps("slice_channels_kernel", s);
-                hipLaunchKernelGGL(slice_channels_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s,
-                                   gfold + static_cast<long long>(g_coff) * 12 * Tn, static_cast<long long>(g_ctot) * 12 * Tn, gf, per_clip, total);
-            }
+            // the slice of the concat gradient that belongs to the folded channels, dense
+            launch_flat("slice_channels_kernel", slice_channels_kernel, s, total, gfold + static_cast<long long>(g_coff) * 12 * Tn, static_cast<long long>(g_ctot) * 12 * Tn, gf,
+                        per_clip, total);
             bn_block_backward(m + "pool.bn", gf, b.foldc_raw[layer], b.aff_foldc[layer], C, 0, 12 * Tn);
             {
                 ake::ProfScope ps("fold_conv_bwd_weight_kernel", s);
@@ -654,20 +645,15 @@ struct Bwd {
             }
             {
                 const long long tot = static_cast<long long>(B) * C * (P / 3) * Tn;
-                ake::ProfScope ps("fold_conv_bwd_data_kernel", s);
-                hipLaunchKernelGGL(fold_conv_bwd_data_kernel, dim3(static_cast<unsigned>((tot + 255) / 256)), dim3(256), 0, s, gf,
-                                   raw_of(m + "pool.conv.weight"), g, C, P / 36, Tn, tot);
+                launch_flat("fold_conv_bwd_data_kernel", fold_conv_bwd_data_kernel, s, tot, gf, raw_of(m + "pool.conv.weight"), g, C, P / 36, Tn, tot);
             }
         } else {
             const long long total = static_cast<long long>(B) * C * 12 * Tn;
-            ake::ProfScope ps("fold_bwd_kernel", s);
-            hipLaunchKernelGGL(fold_bwd_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, gfold, b.semi_raw[layer],
-                               b.aff_semi[layer], g, C, P / 36, Tn, g_ctot, g_coff, total);
+            launch_flat("fold_bwd_kernel", fold_bwd_kernel, s, total, gfold, b.semi_raw[layer], b.aff_semi[layer], g, C, P / 36, Tn, g_ctot, g_coff, total);
         }
         if (extra_g) {   // a second consumer of the activated semitone map: add its gradient (channels [0, C) of a wider tensor)
             const long long HT = static_cast<long long>(P / 3) * Tn, total = static_cast<long long>(B) * C * HT;
-            ake::ProfScope ps("add_slice_kernel", s);
-            hipLaunchKernelGGL(add_slice_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, g, extra_g, C, HT, extra_ctot, total);
+            launch_flat("add_slice_kernel", add_slice_kernel, s, total, g, extra_g, C, HT, extra_ctot, total);
         }
         bn_block_backward(m + "pool_semi_b", g, b.semi_raw[layer], b.aff_semi[layer], C, 0, (P / 3) * Tn);
         {

@@ -212,29 +212,70 @@ __global__ void semi_fold_kernel(SemiArgs a) {
     }
 }
 
+// a pending BatchNorm + LeakyReLU table [C][3] = (scale, shift, negative slope) applied to channel c's raw value (null: x is final)
+__device__ __forceinline__ float affine_act(float x, const float* aff, int c) {
+    if (!aff) return x;
+    const float y = fmaf(x, aff[3 * c], aff[3 * c + 1]);
+    return y > 0.f ? y : y * aff[3 * c + 2];
+}
+
+// Per-channel (sum, sum of squares) of a one-thread-per-element kernel whose workgroups span channels: the threads add into LDS
+// cells `sh` ([C][2], C <= kBlockStatCh), in fixed point so that the order of their adds does not matter; block_stats_end then
+// sends every touched cell to one of the kStatSlots global copies.
+constexpr int kBlockStatCh = 128;
+__device__ __forceinline__ void block_stats_begin(long long* sh, int C) {
+    for (int k = threadIdx.x; k < 2 * C; k += blockDim.x) sh[k] = 0;
+    __syncthreads();
+}
+__device__ __forceinline__ void block_stats_add(long long* sh, int c, float v) {
+    fx_add(&sh[2 * c], v, kFxStat);
+    fx_add(&sh[2 * c + 1], static_cast<double>(v) * v, kFxStat);
+}
+__device__ __forceinline__ void block_stats_end(const long long* sh, int C, double* stats, int stats_stride) {
+    __syncthreads();
+    for (int k = threadIdx.x; k < 2 * C; k += blockDim.x)
+        if (sh[k] != 0) atomicAdd(reinterpret_cast<unsigned long long*>(stats + static_cast<size_t>(blockIdx.x & (kStatSlots - 1)) * stats_stride + k),
+                                  static_cast<unsigned long long>(sh[k]));
+}
+
 // ------------------------------------------------------------------------------------------
 // up_sixth: ConvTranspose2d(C, C, (3,1), stride (3,1)) + BN + LeakyReLU (models.py:325-327):
 // out[co][3p+j][t] = lrelu(b[co] + sum_ci in[ci][p][t] * w[ci][co][j])
+// Inference (TRAIN = false): BatchNorm is folded into w / bias and the LeakyReLU is applied to the output; in_aff and stats are unused.
+// Training: the input carries a pending table, the output stays raw and its per-channel statistics go to `stats`.
 // ------------------------------------------------------------------------------------------
-__global__ void up_sixth_kernel(const float* __restrict__ src, long long src_clip_stride, const float* __restrict__ w,
-                                const float* __restrict__ bias, float* __restrict__ dst, int C, int T, long long total) {
+template <bool TRAIN>
+__global__ void up_sixth_kernel(const float* __restrict__ src, long long src_clip_stride, const float* __restrict__ in_aff,
+                                const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ dst,
+                                double* __restrict__ stats, int stats_stride, int C, int T, long long total) {
+    __shared__ long long sh[TRAIN ? 2 * kBlockStatCh : 1];      // (inference never touches it: the compiler drops the array, no LDS)
+    if constexpr (TRAIN) block_stats_begin(sh, C);
     const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int t = static_cast<int>(i % T);
-    long long q = i / T;
-    const int row = static_cast<int>(q % 36);
-    q /= 36;
-    const int co = static_cast<int>(q % C);
-    const long long clip = q / C;
-    const int p = row / 3, j = row - 3 * p;
-    const float* s = src + clip * src_clip_stride + static_cast<long long>(p) * T + t;   // src may be a channel slice of a concat buffer
-    float acc = bias[co];
-    for (int ci = 0; ci < C; ++ci) acc = fmaf(s[static_cast<long long>(ci) * 12 * T], w[(ci * C + co) * 3 + j], acc);
-    dst[i] = acc > 0.f ? acc : acc * kSlope;
+    if (i < total) {
+        const int t = static_cast<int>(i % T);
+        long long q = i / T;
+        const int row = static_cast<int>(q % 36);
+        q /= 36;
+        const int co = static_cast<int>(q % C);
+        const long long clip = q / C;
+        const int p = row / 3, j = row - 3 * p;
+        const float* s = src + clip * src_clip_stride + static_cast<long long>(p) * T + t;   // src may be a channel slice of a concat buffer
+        float acc = bias[co];
+        for (int ci = 0; ci < C; ++ci) {
+            const float x = s[static_cast<long long>(ci) * 12 * T];
+            acc = fmaf(TRAIN ? affine_act(x, in_aff, ci) : x, w[(ci * C + co) * 3 + j], acc);
+        }
+        if constexpr (TRAIN) {
+            dst[i] = acc;
+            block_stats_add(sh, co, acc);
+        } else dst[i] = acc > 0.f ? acc : acc * kSlope;
+    }
+    if constexpr (TRAIN) block_stats_end(sh, C, stats, stats_stride);
 }
 
-// nn.MaxPool2d((1, tp)) (models.py:349-350): [B][C][H][T] -> [B][dst_ctot][H][T/tp] at channel dst_coff
-__global__ void time_pool_kernel(const float* __restrict__ src, float* __restrict__ dst, int C, int H, int T, int tp,
+// nn.MaxPool2d((1, tp)) (models.py:349-350): [B][C][H][T] -> [B][dst_ctot][H][T/tp] at channel dst_coff; aff (training, nullable): the
+// input is raw and its pending table is applied while loading
+__global__ void time_pool_kernel(const float* __restrict__ src, const float* __restrict__ aff, float* __restrict__ dst, int C, int H, int T, int tp,
                                  int dst_ctot, int dst_coff, long long total) {
     const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= total) return;
@@ -246,8 +287,8 @@ __global__ void time_pool_kernel(const float* __restrict__ src, float* __restric
     const int c = static_cast<int>(q % C);
     const long long clip = q / C;
     const float* s = src + ((clip * C + c) * H + y) * T + static_cast<long long>(t) * tp;
-    float m = s[0];
-    for (int j = 1; j < tp; ++j) m = fmaxf(m, s[j]);
+    float m = affine_act(s[0], aff, c);
+    for (int j = 1; j < tp; ++j) m = fmaxf(m, affine_act(s[j], aff, c));
     dst[((clip * dst_ctot + dst_coff + c) * H + y) * To + t] = m;
 }
 
@@ -2495,9 +2536,10 @@ __global__ void pack_p2p_f16_raw_jobs_kernel(P2pRawJobs js) {
     pack_p2p_f16_raw_body(J.w, J.out, J.cin_fwd, J.cout_fwd, J.transpose_flip, blockIdx.x);
 }
 
-// Pitch2PitchClassPool (models.py:95-106) of ready semitone maps [clip][C][S][T], S a multiple of 12: max over the octaves
-__global__ void fold_max_kernel(const float* __restrict__ smap, int C, int S, int T, float* __restrict__ dst, long long dst_clip_stride, int dst_coff,
-                                long long total) {
+// Pitch2PitchClassPool (models.py:95-106) of semitone maps [clip][C][S][T], S a multiple of 12: max over the octaves; aff (training,
+// nullable): the maps are raw and their pending BatchNorm + LeakyReLU table is applied while loading
+__global__ void fold_max_kernel(const float* __restrict__ smap, const float* __restrict__ aff, int C, int S, int T, float* __restrict__ dst,
+                                long long dst_clip_stride, int dst_coff, long long total) {
     const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;   // (clip, c, p, t)
     if (i >= total) return;
     const int t = static_cast<int>(i % T);
@@ -2507,7 +2549,7 @@ __global__ void fold_max_kernel(const float* __restrict__ smap, int C, int S, in
     const long long clip = r / C;
     const float* src = smap + ((clip * C + c) * S + p) * T + t;
     float best = -INFINITY;
-    for (int o = 0; o < S / 12; ++o) best = fmaxf(best, src[static_cast<long long>(12 * o) * T]);
+    for (int o = 0; o < S / 12; ++o) best = fmaxf(best, affine_act(src[static_cast<long long>(12 * o) * T], aff, c));
     dst[clip * dst_clip_stride + (static_cast<long long>(dst_coff + c) * 12 + p) * T + t] = best;
 }
 
@@ -2988,12 +3030,6 @@ __global__ void slice_channels_kernel(const float* __restrict__ src, long long s
 // Training-mode forward helpers (BatchNorm with batch statistics, nn.BatchNorm2d in train(), models.py:196 etc.)
 // ==========================================================================================
 
-__device__ __forceinline__ float affine_act(float x, const float* aff, int c) {
-    if (!aff) return x;
-    const float y = fmaf(x, aff[3 * c], aff[3 * c + 1]);
-    return y > 0.f ? y : y * aff[3 * c + 2];
-}
-
 // wave-level (sum, sumsq) -> one double atomic pair per wave
 __device__ __forceinline__ void stats_commit(double* stats, int stats_stride, int c, const ShiftStat& ss) {
     long long s1, s2;
@@ -3079,61 +3115,14 @@ __global__ void semi_conv_stats_kernel(SemiTrainArgs ta) {
     }
 }
 
-// BatchNorm + LeakyReLU (as `aff`) then Pitch2PitchClassPool (models.py:95-106): raw [B][C][12*n_oct][T] -> [B][ctot][12][T]
-__global__ void fold_affine_kernel(const float* __restrict__ src, const float* __restrict__ aff, float* __restrict__ dst, int C,
-                                   int n_oct, int T, int dst_ctot, int dst_coff, long long total) {
-    const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int t = static_cast<int>(i % T);
-    long long q = i / T;
-    const int p = static_cast<int>(q % 12);
-    q /= 12;
-    const int c = static_cast<int>(q % C);
-    const long long clip = q / C;
-    const float* s = src + ((clip * C + c) * (12 * n_oct) + p) * T + t;
-    float m = -INFINITY;
-    for (int o = 0; o < n_oct; ++o) m = fmaxf(m, affine_act(s[static_cast<long long>(o) * 12 * T], aff, c));
-    dst[((clip * dst_ctot + dst_coff + c) * 12 + p) * T + t] = m;
-}
-
-// up_sixth in training mode: raw ConvTranspose2d output + statistics; input carries a pending affine.
-__global__ void up_sixth_train_kernel(const float* __restrict__ src, long long src_clip_stride, const float* __restrict__ in_aff,
-                                      const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ dst,
-                                      double* __restrict__ stats, int stats_stride, int C, int T, long long total) {
-    __shared__ long long sh[2 * 128];                              // fixed point: the order of the threads' adds does not matter
-    for (int k = threadIdx.x; k < 2 * C; k += blockDim.x) sh[k] = 0;
-    __syncthreads();
-    const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i < total) {
-        const int t = static_cast<int>(i % T);
-        long long q = i / T;
-        const int row = static_cast<int>(q % 36);
-        q /= 36;
-        const int co = static_cast<int>(q % C);
-        const long long clip = q / C;
-        const int p = row / 3, j = row - 3 * p;
-        const float* s = src + clip * src_clip_stride + static_cast<long long>(p) * T + t;
-        float acc = bias[co];
-        for (int ci = 0; ci < C; ++ci) acc = fmaf(affine_act(s[static_cast<long long>(ci) * 12 * T], in_aff, ci), w[(ci * C + co) * 3 + j], acc);
-        dst[i] = acc;
-        fx_add(&sh[2 * co], acc, kFxStat);
-        fx_add(&sh[2 * co + 1], static_cast<double>(acc) * acc, kFxStat);
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < 2 * C; k += blockDim.x)
-        if (sh[k] != 0) atomicAdd(reinterpret_cast<unsigned long long*>(stats + static_cast<size_t>(blockIdx.x & (kStatSlots - 1)) * stats_stride + k),
-                                  static_cast<unsigned long long>(sh[k]));
-}
-
 // --p2pc_conv in training mode (Pitch2PitchClassConv, models.py:108-133): the octave-fold convolution (kernel (n_oct, 1), dilation
 // (12, 1)) over the RAW semitone maps [clip][C][12 * n_oct][T], whose pending BatchNorm + LeakyReLU is applied while loading; raw output
 // [clip][C][12][T] (dense) + the statistics of pool.bn.  w: the reference layout [co][ci][n_oct].
 __global__ void fold_conv_train_kernel(const float* __restrict__ src, const float* __restrict__ in_aff, const float* __restrict__ w,
                                        const float* __restrict__ bias, float* __restrict__ dst, double* __restrict__ stats, int stats_stride, int C,
                                        int n_oct, int T, long long total) {
-    __shared__ long long sh[2 * 128];                              // fixed point: the order of the threads' adds does not matter
-    for (int k = threadIdx.x; k < 2 * C; k += blockDim.x) sh[k] = 0;
-    __syncthreads();
+    __shared__ long long sh[2 * kBlockStatCh];
+    block_stats_begin(sh, C);
     const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;      // (clip, co, p, t)
     if (i < total) {
         const int t = static_cast<int>(i % T);
@@ -3147,13 +3136,9 @@ __global__ void fold_conv_train_kernel(const float* __restrict__ src, const floa
             for (int o = 0; o < n_oct; ++o)
                 acc = fmaf(affine_act(s[(static_cast<long long>(ci) * 12 * n_oct + 12 * o) * T], in_aff, ci), w[(co * C + ci) * n_oct + o], acc);
         dst[i] = acc;
-        fx_add(&sh[2 * co], acc, kFxStat);
-        fx_add(&sh[2 * co + 1], static_cast<double>(acc) * acc, kFxStat);
+        block_stats_add(sh, co, acc);
     }
-    __syncthreads();
-    for (int k = threadIdx.x; k < 2 * C; k += blockDim.x)
-        if (sh[k] != 0) atomicAdd(reinterpret_cast<unsigned long long*>(stats + static_cast<size_t>(blockIdx.x & (kStatSlots - 1)) * stats_stride + k),
-                                  static_cast<unsigned long long>(sh[k]));
+    block_stats_end(sh, C, stats, stats_stride);
 }
 
 // dst[clip][coff + c][ht] (of dst_ctot channels) = LeakyReLU(BatchNorm(src[clip][c][ht])) with the pending table `aff`
@@ -3199,24 +3184,6 @@ __global__ __launch_bounds__(384) void conv_head_last_kernel(const float* __rest
             }
         dst[(static_cast<long long>(clip) * H_out + y) * T_out + t] = acc;
     }
-}
-
-// time pooling with a pending affine on the input
-__global__ void time_pool_affine_kernel(const float* __restrict__ src, const float* __restrict__ aff, float* __restrict__ dst, int C,
-                                        int H, int T, int tp, int dst_ctot, int dst_coff, long long total) {
-    const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int To = T / tp;
-    const int t = static_cast<int>(i % To);
-    long long q = i / To;
-    const int y = static_cast<int>(q % H);
-    q /= H;
-    const int c = static_cast<int>(q % C);
-    const long long clip = q / C;
-    const float* s = src + ((clip * C + c) * H + y) * T + static_cast<long long>(t) * tp;
-    float m = affine_act(s[0], aff, c);
-    for (int j = 1; j < tp; ++j) m = fmaxf(m, affine_act(s[j], aff, c));
-    dst[((clip * dst_ctot + dst_coff + c) * H + y) * To + t] = m;
 }
 
 // (sum, sumsq) over `count` values per channel -> BatchNorm(train) as an affine triple, plus (batch mean, biased
