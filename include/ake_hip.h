@@ -78,6 +78,14 @@ int ake_cqt_plan_n_bins(const ake_cqt_plan* plan);
 int ake_cqt_plan_hop(const ake_cqt_plan* plan);
 /* 1 + n_samples / hop  (librosa center=True framing). */
 int64_t ake_cqt_num_frames(const ake_cqt_plan* plan, int64_t n_samples);
+/*
+ * The workspace contract, for every entry point that takes (workspace, workspace_bytes) with the size its *_workspace_bytes returns:
+ *   - the content of the workspace on entry is arbitrary (fresh memory, what a call of another shape or route left, NaN patterns): a call
+ *     writes everything it later reads, so one buffer sized for the largest request serves every shape in turn;
+ *   - a call writes nothing outside [workspace, workspace + workspace_bytes) and its documented outputs, and an output is written as exactly
+ *     its documented bytes (no store is rounded up past a [batch][11] row);
+ *   - the one exception: ake_pcnet_backward_f32 reads what ake_pcnet_forward_train_f32 left in the same workspace (documented there).
+ */
 size_t ake_cqt_workspace_bytes(const ake_cqt_plan* plan, int batch, int64_t n_samples);
 /*
  * audio_dev : [batch][audio_stride] float32, first n_samples of each row are the clip
