@@ -9,13 +9,14 @@ from .audio import Resampler, get_resampler, pcm16_to_float, prepare as prepare_
 from .cqt import CQTPlan, cqt_logmag, get_any_hop_plan, get_plan, hop_for, hop_for_window  # noqa: F401
 from .KeyDataset import DatasetLoader, KeyDataset, SyntheticSineMixLoader, WaveformLoader  # noqa: F401
 from .metrics import (KEY_NAMES, KEY_SIGNATURE_MAP, decode_keys, key_emissions, key_posteriors, key_transition_log, mirex_score,  # noqa: F401
-                      track_score, transition_from_labels, transition_m_step, viterbi_keys, weighted_general_step, window_labels,
+                      retune_reference, track_score, transition_from_labels, transition_m_step, viterbi_keys, weighted_general_step, window_labels,
                       window_truth)
 from .models import PitchClassNet  # noqa: F401
 from .optim import FusedAdam  # noqa: F401
 from .lightning_shim import Trainer  # noqa: F401
 from .pipeline import KeyAnnotations, KeyEstimator, KeyTrack, TrackScore, fit_key_transition  # noqa: F401
 from .synth import synth_partials  # noqa: F401
+from .tuning import estimate_tuning, retune, retune_out_len  # noqa: F401
 from .windows import TrackWindows, draw_windows, window_batch  # noqa: F401
 from .feeder import HostFeeder  # noqa: F401
 
@@ -23,4 +24,5 @@ __all__ = ["PitchClassNet", "KeyDataset", "DatasetLoader", "SyntheticSineMixLoad
            "cqt_logmag", "get_plan", "hop_for", "KEY_SIGNATURE_MAP", "mirex_score", "decode_keys", "key_emissions", "viterbi_keys", "key_transition_log", "key_posteriors",
            "transition_m_step", "fit_key_transition", "KEY_NAMES", "KeyEstimator", "KeyTrack", "Resampler", "get_resampler",
            "prepare_audio", "pcm16_to_float", "HostFeeder", "KeyAnnotations", "TrackScore", "track_score", "window_truth",
-           "transition_from_labels", "synth_partials", "TrackWindows", "draw_windows", "window_batch", "window_labels", "weighted_general_step"]
+           "transition_from_labels", "synth_partials", "TrackWindows", "draw_windows", "window_batch", "window_labels", "weighted_general_step",
+           "estimate_tuning", "retune", "retune_out_len", "retune_reference"]

@@ -111,6 +111,11 @@ SYMBOLS = {
     "ake_resampler_out_len": (_I64, [_P, _I64]),
     "ake_resample_f32": (_I, [_P, _P, _I, _I, _I64, _I64, _I64, _I, _P, _P, _I64, _P, _P]),
     "ake_resample_pcm16_f32": (_I, [_P, _P, _I, _I, _I64, _I64, _I64, _I64, _I, _P, _P, _I64, _P, _P]),
+    "ake_tuning_workspace_bytes": (_SZ, [_I, _I]),
+    "ake_tuning_estimate_f32": (_I, [_P, _I, _I, _I, _I, _P, C.c_float, _P, _P, _P, _SZ, _P]),
+    "ake_retune_out_len": (_I64, [_I64]),
+    "ake_retune_f32": (_I, [_P, _I, _I64, _I64, _P, _P, _P, _I64, _P, _P]),
+    "ake_retune_pcm16_f32": (_I, [_P, _I, _I64, _I64, _P, _P, _P, _I64, _P, _P]),
     "ake_prof_enable": (_I, [C.c_char_p, _I]),
     "ake_prof_collect": (_I, []),
     "ake_prof_reset": (_I, []),

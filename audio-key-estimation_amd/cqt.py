@@ -78,14 +78,15 @@ class CQTPlan:
         return self._ws
 
     def logmag(self, audio: torch.Tensor, out_frames: int | None = None, out: torch.Tensor | None = None,
-               lengths: torch.Tensor | None = None) -> torch.Tensor:
+               lengths: torch.Tensor | None = None, workspace: torch.Tensor | None = None) -> torch.Tensor:
         """audio (B, n) or (n,) -> log(1+|CQT|) float32 (B, n_bins, out_frames); frames past the clip are zero.
 
         ``lengths`` (B,) int64: ragged batch -- row i holds ``lengths[i] <= n`` samples (the rest of the row is ignored); clip i
         gets ``1 + lengths[i] // hop`` frames and zeros after them, as ``KeyDataset.__getitem__`` pads (KeyDataset.py:245).
 
         int16 audio is 16-bit PCM (``pcm16_to_float``), transformed by ``ake_cqt_logmag_pcm16_f32`` without a float32 copy of it: the
-        float32 route's result on the converted audio, bit for bit (engine 3)."""
+        float32 route's result on the converted audio, bit for bit (engine 3).  ``workspace``: a uint8 device tensor of at least
+        ``ake_cqt_workspace_bytes`` bytes to use instead of the plan's own (one per stream)."""
         squeeze = audio.dim() == 1
         if squeeze:
             audio = audio[None]
@@ -104,7 +105,8 @@ class CQTPlan:
         assert out.is_contiguous() and out.shape == (B, self.n_bins, out_frames) and out.dtype == torch.float32
         L = _lib.lib()
         nbytes = L.ake_cqt_workspace_bytes(self._h, B, n)
-        ws = self._workspace(nbytes)
+        ws = self._workspace(nbytes) if workspace is None else workspace
+        assert ws.numel() >= nbytes
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream().cuda_stream
             if pcm:

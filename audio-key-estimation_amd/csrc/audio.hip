@@ -12,6 +12,10 @@
 // k < ceil(n * up / down).  One thread per output sample: ~20 * max(up, down) / up + 1 taps (41 for 44.1 -> 22.05 kHz, 44 for
 // 48 -> 22.05 kHz), input and filter served from L1/L2 -- a streaming kernel, bound by HBM (4 B read per input sample and channel,
 // 4 B written per output sample).
+//
+// Retuning (ake_retune_f32, not in the reference either) is the same stage with a ratio per row that is no fraction of small integers:
+// rho = 2^(cents / 1200) undoes a detuning of `cents` (ake_tuning_estimate_f32 measures it).  Definition, table and order of the sums:
+// metrics.retune_reference, the float64 model of retune_kernel.
 #include "common.h"
 
 #include <cmath>
@@ -131,6 +135,141 @@ __global__ __launch_bounds__(256) void resample_pcm16_kernel(ResamplePcmArgs a) 
     *o = acc * scale;
 }
 
+// ---- retuning: varispeed resampling by a ratio per row ----
+// y[k] = sum_j x[j] h(k / rho - j), h(d) = c sinc(c d) kaiser_beta(d / Z) on |d| < Z: 2 Z = 64 taps of a contiguous input stretch per
+// output sample, and a filter phase of its own for every sample (rho is irrational), so there is no polyphase table to index.  h is
+// held one-sided at kRetuneRes entries per sample, G[q] = h(q / kRetuneRes), and blended linearly between neighbours: 32 KiB of LDS.
+// A workgroup loads it once and then makes kRetuneTiles tiles of kRetuneTile consecutive samples of one row; the input stretch of a
+// tile (at most kRetuneTile * 2^(50/1200) + 2 Z + 1 samples) is staged in LDS as float32 -- the PCM form converts there, and nowhere
+// else, so both forms run the same sums on the same values.  41 KiB per workgroup: three fit a CU.
+constexpr int kRetuneZeros = 32;
+constexpr int kRetuneRes = 256;
+constexpr int kRetuneTable = kRetuneZeros * kRetuneRes + 1;       // G[Z * res] = h(Z) is stored as 0: the taps are |d| < Z
+constexpr double kRetuneBeta = 9.0, kRetuneCutoff = 0.94, kRetuneMaxCents = 50.0;
+constexpr double kRetuneMaxRatio = 1.029302236643492;            // 2^(50/1200) as one double: metrics.RETUNE_MAX_RATIO, host and device
+constexpr int kRetuneTile = 2048, kRetuneTiles = 8, kRetuneThreads = 256;
+constexpr int kRetuneStretch = 2240;                              // >= ceil(2047 * 1.02931) + 1 + 2 Z = 2173
+static_assert(kRetuneTile % kRetuneThreads == 0 && (kRetuneRes & (kRetuneRes - 1)) == 0, "retune tiling");
+
+__device__ float g_retune_table[kRetuneTable + 1];
+ake::DeviceOnce g_retune_table_once;
+
+template <typename T> __device__ __forceinline__ float retune_sample(T v);
+template <> __device__ __forceinline__ float retune_sample<float>(float v) { return v; }
+template <> __device__ __forceinline__ float retune_sample<short>(short v) { return static_cast<float>(v) * (1.f / 32768.f); }
+
+template <typename T>
+struct RetuneArgs {
+    const T* in;                // [batch][in_stride]
+    long long in_stride, n_max;
+    const long long* n_in;      // samples of each row (clamped to 0..n_max), or null
+    const float* cents;         // [batch]
+    float* out;                 // [batch][out_stride]; columns [0, width) are written
+    long long out_stride, width;
+    long long* n_out;           // [batch], or null
+};
+
+template <typename T>
+__global__ __launch_bounds__(kRetuneThreads) void retune_kernel(RetuneArgs<T> a) {
+    __shared__ float G[kRetuneTable + 1];
+    __shared__ float X[kRetuneStretch];
+    const int row = blockIdx.y, tid = threadIdx.x;
+    long long n = a.n_max;
+    if (a.n_in) { const long long nc = a.n_in[row]; n = nc < 0 ? 0 : (nc < n ? nc : n); }
+    float cents = a.cents[row];
+    cents = cents != cents ? 0.f : fminf(fmaxf(cents, -static_cast<float>(kRetuneMaxCents)), static_cast<float>(kRetuneMaxCents));
+    const bool copy = cents == 0.f;
+    // at the clamp the ratio is the literal the buffer's width was sized with, so n_out < width whatever exp2 rounds to
+    const double rho = cents >= static_cast<float>(kRetuneMaxCents) ? kRetuneMaxRatio
+                     : cents <= -static_cast<float>(kRetuneMaxCents) ? 1.0 / kRetuneMaxRatio : exp2(static_cast<double>(cents) / 1200.0);
+    const double inv = 1.0 / rho;
+    long long n_out = copy ? n : static_cast<long long>(floor(static_cast<double>(n) * rho));
+    n_out = n_out < a.width ? n_out : a.width - 1;                // (|cents| < 50: rho < the literal by far more than an ulp; a guard all the same)
+    if (blockIdx.x == 0 && tid == 0 && a.n_out) a.n_out[row] = n_out;
+    const T* x = a.in + row * a.in_stride;
+    float* y = a.out + row * a.out_stride;
+    const long long k_first = static_cast<long long>(blockIdx.x) * (kRetuneTile * kRetuneTiles);
+    const bool filter = !copy && k_first < n_out;                 // (uniform over the workgroup)
+    if (filter)
+        for (int i = tid; i < kRetuneTable + 1; i += kRetuneThreads) G[i] = g_retune_table[i];
+    for (int tile = 0; tile < kRetuneTiles; ++tile) {
+        const long long k0 = k_first + static_cast<long long>(tile) * kRetuneTile;
+        if (k0 >= a.width) break;
+        if (copy || k0 >= n_out) {                                // a row that is not retuned, or the zeros behind a row's end
+            for (int i = tid; i < kRetuneTile; i += kRetuneThreads) {
+                const long long k = k0 + i;
+                if (k < a.width) y[k] = k < n_out ? retune_sample<T>(x[k]) : 0.f;
+            }
+            continue;
+        }
+        // the tile's input stretch: sample j of the row at X[j - j_base], zeros outside [0, n)
+        const long long j_base = static_cast<long long>(floor(static_cast<double>(k0) * inv)) - kRetuneZeros + 1;
+        __syncthreads();                                          // (the last tile's reads of X are done)
+        for (int i = tid; i < kRetuneStretch; i += kRetuneThreads) {
+            const long long j = j_base + i;
+            X[i] = (j >= 0 && j < n) ? retune_sample<T>(x[j]) : 0.f;
+        }
+        __syncthreads();
+        for (int i = tid; i < kRetuneTile; i += kRetuneThreads) {
+            const long long k = k0 + i;
+            if (k >= a.width) break;
+            if (k >= n_out) { y[k] = 0.f; continue; }
+            // the read position in double; only its fraction is rounded to float32, so the error does not grow with k
+            const double pos = static_cast<double>(k) * inv, j0d = floor(pos);
+            const float fr = static_cast<float>(pos - j0d) * kRetuneRes;
+            int r = static_cast<int>(fr);
+            r = r < kRetuneRes - 1 ? r : kRetuneRes - 1;
+            const float t = fr - static_cast<float>(r);
+            const float* xs = X + (static_cast<long long>(j0d) - j_base);     // xs[m] = x[j0 + m], m = -Z + 1 .. Z
+            float acc = 0.f;
+            int q = r + (kRetuneZeros - 1) * kRetuneRes;
+#pragma unroll 8
+            for (int m = -kRetuneZeros + 1; m <= 0; ++m, q -= kRetuneRes)    // d = fraction - m >= 0
+                acc = fmaf(xs[m], fmaf(t, G[q + 1] - G[q], G[q]), acc);
+            q = kRetuneRes - r - 1;
+#pragma unroll 8
+            for (int m = 1; m <= kRetuneZeros; ++m, q += kRetuneRes)         // d < 0: h(-d), read downwards
+                acc = fmaf(xs[m], fmaf(t, G[q] - G[q + 1], G[q + 1]), acc);
+            y[k] = acc;
+        }
+    }
+}
+
+int retune_table_upload() {
+    if (!g_retune_table_once.need()) return AKE_OK;
+    std::vector<float> h(kRetuneTable + 1, 0.f);
+    const double i0b = bessel_i0d(kRetuneBeta);
+    for (int q = 0; q < kRetuneTable - 1; ++q) {
+        const double d = static_cast<double>(q) / kRetuneRes, u = d / kRetuneZeros, a = M_PI * kRetuneCutoff * d;
+        const double sinc = q == 0 ? 1.0 : std::sin(a) / a;
+        h[q] = static_cast<float>(kRetuneCutoff * sinc * bessel_i0d(kRetuneBeta * std::sqrt(std::max(0.0, 1.0 - u * u))) / i0b);
+    }
+    AKE_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_retune_table), h.data(), h.size() * sizeof(float)));
+    g_retune_table_once.mark();
+    return AKE_OK;
+}
+
+template <typename T>
+int retune_launch(const char* name, const T* in_dev, int batch, int64_t n_max, int64_t in_stride, const int64_t* n_in_dev, const float* cents_dev,
+                  float* out_dev, int64_t out_stride, int64_t* n_out_dev, ake_stream_t stream) {
+    AKE_REQUIRE(in_dev && cents_dev && out_dev, AKE_ERR_INVALID, "%s: null argument", name);
+    AKE_REQUIRE(batch > 0 && batch <= 65535 && n_max >= 0 && n_max <= (1ll << 40), AKE_ERR_INVALID, "%s: bad batch %d / n_max %lld", name, batch,
+                static_cast<long long>(n_max));
+    const int64_t width = ake_retune_out_len(n_max);
+    AKE_REQUIRE(in_stride >= n_max && out_stride >= width, AKE_ERR_INVALID, "%s: row strides %lld, %lld < %lld input, %lld output samples", name,
+                static_cast<long long>(in_stride), static_cast<long long>(out_stride), static_cast<long long>(n_max), static_cast<long long>(width));
+    const int rc = retune_table_upload();
+    if (rc) return rc;
+    RetuneArgs<T> a{in_dev, in_stride, n_max, reinterpret_cast<const long long*>(n_in_dev), cents_dev, out_dev, out_stride, width,
+                    reinterpret_cast<long long*>(n_out_dev)};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    constexpr int per_block = kRetuneTile * kRetuneTiles;
+    ake::ProfScope ps(name, s);
+    hipLaunchKernelGGL(retune_kernel<T>, dim3(static_cast<unsigned>((width + per_block - 1) / per_block), batch), dim3(kRetuneThreads), 0, s, a);
+    AKE_HIP_CHECK(hipGetLastError());
+    return AKE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -219,6 +358,22 @@ int ake_resample_pcm16_f32(const ake_resampler* r, const int16_t* in_dev, int ba
     hipLaunchKernelGGL(resample_pcm16_kernel, dim3(static_cast<unsigned>((n_out + 255) / 256), batch), dim3(256), 0, s, a);
     AKE_HIP_CHECK(hipGetLastError());
     return AKE_OK;
+}
+
+int64_t ake_retune_out_len(int64_t n) {
+    if (n < 0 || n > (1ll << 40)) return -1;
+    return static_cast<int64_t>(std::floor(static_cast<double>(n) * kRetuneMaxRatio)) + 1;
+}
+
+int ake_retune_f32(const float* in_dev, int batch, int64_t n_max, int64_t in_stride, const int64_t* lengths_dev, const float* cents_dev,
+                   float* out_dev, int64_t out_stride, int64_t* lengths_out_dev, ake_stream_t stream) {
+    return retune_launch<float>("retune_kernel", in_dev, batch, n_max, in_stride, lengths_dev, cents_dev, out_dev, out_stride, lengths_out_dev, stream);
+}
+
+int ake_retune_pcm16_f32(const int16_t* in_dev, int batch, int64_t n_max, int64_t in_stride, const int64_t* lengths_dev, const float* cents_dev,
+                         float* out_dev, int64_t out_stride, int64_t* lengths_out_dev, ake_stream_t stream) {
+    return retune_launch<short>("retune_pcm16_kernel", reinterpret_cast<const short*>(in_dev), batch, n_max, in_stride, lengths_dev, cents_dev,
+                                out_dev, out_stride, lengths_out_dev, stream);
 }
 
 }  // extern "C"

@@ -1,0 +1,136 @@
+// Tuning estimate: how far a recording sits from A4 = 440 Hz, read off its log-CQT (not part of the reference, whose librosa 0.9.2
+// transform runs at tuning = 0.0 and whose net collapses each semitone's three bins as they come).
+//
+// The transform has 3 bins per semitone with in-tune notes on the bins k = 0 (mod 3).  With m = expm1(L) the magnitudes and P_j the sum
+// of m^2 over the bins k = j (mod 3) and a recording's frames:
+//     z = P_0 + P_1 e^{2 pi i / 3} + P_2 e^{4 pi i / 3},   cents = 100 arg(z) / (2 pi) in (-50, 50],   strength = |z| / (P_0 + P_1 + P_2)
+// (metrics.estimate_tuning is the float64 model).  Two launches: tuning_sums_kernel reduces a tile of kTuneChunk frames of one recording
+// to its three sums in double, in a fixed order; tuning_finish_kernel adds the chunks of a recording in chunk order and writes the two
+// floats.  No floating-point atomics anywhere, so two runs give the same bits.  expm1 and atan2 are the double library forms: the
+// estimate is a few million elements, and in double its rounding disappears beside the method's own error of about a cent.
+#include "common.h"
+
+#include <cmath>
+
+namespace {
+
+// 256 threads on a tile of 64 frames x all bins.  Frames-major: lanes run along the bins, so 288 bins take two passes and the second
+// keeps 32 of 256 lanes busy; pitch-major: lanes run along the frames, so a 76-frame clip's second chunk keeps 12 of 64.  Both are
+// left as they are until the two launches have been timed (tools/tuning_bench.py): the tile is 74 KB of loads against a double expm1
+// per element, and a 96-thread-multiple tiling would change the order of the sums that the tests pin.
+constexpr int kTuneChunk = 64;       // frames per block
+constexpr int kTuneThreads = 256;
+constexpr int kTuneBinsPerSemitone = 3;
+
+struct TuneArgs {
+    const float* mel;           // [batch][pitches][frames], or [batch][frames][pitches] (frames_major)
+    const int* counts;          // frames of each recording (clamped to 0..frames), or null
+    double* partial;            // [batch][chunks][3]
+    int pitches, frames, chunks;
+};
+
+template <bool kFramesMajor>
+__global__ __launch_bounds__(kTuneThreads) void tuning_sums_kernel(TuneArgs a) {
+    __shared__ double red[kTuneThreads][3];
+    const int rec = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
+    int T = a.frames;
+    if (a.counts) { const int c = a.counts[rec]; T = c < 0 ? 0 : (c < T ? c : T); }
+    const int t0 = chunk * kTuneChunk;
+    const int t1 = t0 + kTuneChunk < T ? t0 + kTuneChunk : T;
+    const float* mel = a.mel + static_cast<long long>(rec) * a.pitches * a.frames;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    if (kFramesMajor) {                                           // lanes along the bins, which are contiguous
+        for (int t = t0; t < t1; ++t)
+            for (int k = tid; k < a.pitches; k += kTuneThreads) {
+                const double m = expm1(static_cast<double>(mel[static_cast<long long>(t) * a.pitches + k])), v = m * m;
+                const int j = k % kTuneBinsPerSemitone;
+                s0 += j == 0 ? v : 0.0; s1 += j == 1 ? v : 0.0; s2 += j == 2 ? v : 0.0;
+            }
+    } else {                                                      // lanes along the frames, one wave per bin row
+        const int t = t0 + (tid & 63);
+        if (t < t1)
+            for (int k = tid >> 6; k < a.pitches; k += kTuneThreads / 64) {
+                const double m = expm1(static_cast<double>(mel[static_cast<long long>(k) * a.frames + t])), v = m * m;
+                const int j = k % kTuneBinsPerSemitone;
+                s0 += j == 0 ? v : 0.0; s1 += j == 1 ? v : 0.0; s2 += j == 2 ? v : 0.0;
+            }
+    }
+    red[tid][0] = s0; red[tid][1] = s1; red[tid][2] = s2;
+    __syncthreads();
+    for (int half = kTuneThreads / 2; half > 0; half >>= 1) {     // a fixed tree: the same order of additions every run
+        if (tid < half)
+            for (int j = 0; j < 3; ++j) red[tid][j] += red[tid + half][j];
+        __syncthreads();
+    }
+    if (tid < 3) a.partial[(static_cast<long long>(rec) * a.chunks + chunk) * 3 + tid] = red[0][tid];
+}
+
+struct TuneFinishArgs {
+    const double* partial;
+    float* cents;
+    float* strength;
+    int batch, chunks;
+    float min_strength;
+};
+
+__global__ __launch_bounds__(64) void tuning_finish_kernel(TuneFinishArgs a) {
+    const int rec = blockIdx.x * 64 + threadIdx.x;
+    if (rec >= a.batch) return;
+    double P[3] = {0.0, 0.0, 0.0};
+    for (int c = 0; c < a.chunks; ++c)                            // chunk order
+        for (int j = 0; j < 3; ++j) P[j] += a.partial[(static_cast<long long>(rec) * a.chunks + c) * 3 + j];
+    const double total = P[0] + P[1] + P[2];
+    double cents = 0.0, strength = 0.0;
+    if (total > 0.0) {
+        const double re = P[0] - 0.5 * (P[1] + P[2]), im = 0.86602540378443865 * (P[1] - P[2]);      // sqrt(3) / 2
+        cents = 100.0 * atan2(im, re) / (2.0 * M_PI);
+        strength = fmin(sqrt(re * re + im * im) / total, 1.0);
+    }
+    if (strength < static_cast<double>(a.min_strength)) cents = 0.0;
+    a.cents[rec] = static_cast<float>(cents);
+    a.strength[rec] = static_cast<float>(strength);
+}
+
+bool tune_shape_ok(int batch, int frames) { return batch > 0 && batch <= 65535 && frames > 0; }
+int tune_chunks(int frames) { return (frames + kTuneChunk - 1) / kTuneChunk; }
+
+}  // namespace
+
+extern "C" {
+
+size_t ake_tuning_workspace_bytes(int batch, int frames) {
+    if (!tune_shape_ok(batch, frames)) return 0;
+    return ake::align_up(static_cast<size_t>(batch) * tune_chunks(frames) * 3 * sizeof(double), 256);
+}
+
+int ake_tuning_estimate_f32(const float* mel_dev, int frames_major, int batch, int pitches, int frames, const int32_t* counts_dev,
+                            float min_strength, float* cents_dev, float* strength_dev, void* workspace, size_t workspace_bytes,
+                            ake_stream_t stream) {
+    AKE_REQUIRE(mel_dev && cents_dev && strength_dev, AKE_ERR_INVALID, "tuning_estimate: null argument");
+    AKE_REQUIRE(tune_shape_ok(batch, frames) && pitches > 0, AKE_ERR_INVALID, "tuning_estimate: bad shape (%d recordings, %d pitches, %d frames)",
+                batch, pitches, frames);
+    AKE_REQUIRE(pitches % kTuneBinsPerSemitone == 0, AKE_ERR_UNSUPPORTED, "tuning_estimate: %d bins are no multiple of 3 (3 bins per semitone)", pitches);
+    AKE_REQUIRE(static_cast<long long>(pitches) * frames <= (1ll << 31) - 1, AKE_ERR_INVALID, "tuning_estimate: %d x %d is too large", pitches, frames);
+    AKE_REQUIRE(min_strength == min_strength, AKE_ERR_INVALID, "tuning_estimate: min_strength is NaN");
+    const size_t need = ake_tuning_workspace_bytes(batch, frames);
+    AKE_REQUIRE(workspace && workspace_bytes >= need, AKE_ERR_WORKSPACE, "tuning_estimate: workspace %zu < %zu bytes", workspace_bytes, need);
+    AKE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, AKE_ERR_INVALID, "tuning_estimate: the workspace must be 8-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int chunks = tune_chunks(frames);
+    TuneArgs a{mel_dev, counts_dev, static_cast<double*>(workspace), pitches, frames, chunks};
+    {
+        ake::ProfScope ps("tuning_sums_kernel", s);
+        if (frames_major) hipLaunchKernelGGL(tuning_sums_kernel<true>, dim3(chunks, batch), dim3(kTuneThreads), 0, s, a);
+        else hipLaunchKernelGGL(tuning_sums_kernel<false>, dim3(chunks, batch), dim3(kTuneThreads), 0, s, a);
+    }
+    AKE_HIP_CHECK(hipGetLastError());
+    TuneFinishArgs f{static_cast<const double*>(workspace), cents_dev, strength_dev, batch, chunks, min_strength};
+    {
+        ake::ProfScope ps("tuning_finish_kernel", s);
+        hipLaunchKernelGGL(tuning_finish_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, f);
+    }
+    AKE_HIP_CHECK(hipGetLastError());
+    return AKE_OK;
+}
+
+}  // extern "C"

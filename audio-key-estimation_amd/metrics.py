@@ -444,7 +444,22 @@ def key_category(pred, truth):
     return torch.where(t < 0, torch.full_like(p, -1), cat).to(torch.int32)
 
 
-def track_score(pred, counts, seg_start, seg_key, seg_count, hop, window_frames, stride_frames):
+def tuning_ratio(cents):
+    """``rho = 2 ** (cents / 1200)`` in float64, on the device of ``cents``: what retuning by ``cents`` stretches the time axis by."""
+    return torch.exp2(torch.as_tensor(cents).to(torch.float64) / 1200.0)
+
+
+def scale_boundaries(seg_start, tuning_cents):
+    """Annotation boundaries int64 (R, S) in samples of the recording -> in samples of the recording retuned by ``tuning_cents`` (R,):
+    ``floor(float64(start) * rho_i)`` as float64 torch ops on the boundaries' device; INT64_MAX (no segment) stays."""
+    start = seg_start.to(torch.int64)
+    rho = tuning_ratio(torch.as_tensor(tuning_cents, device=start.device)).reshape(-1, 1)
+    if rho.shape[0] != start.shape[0]:
+        raise ValueError(f"scale_boundaries: {start.shape[0]} recordings but {rho.shape[0]} tunings")
+    return torch.where(start == _I64_MAX, start, torch.floor(start.to(torch.float64) * rho).to(torch.int64))
+
+
+def track_score(pred, counts, seg_start, seg_key, seg_count, hop, window_frames, stride_frames, tuning_cents=None):
     """Score decoded keys against annotations -> ``(truth, category, tally, changes)``: ``ake_track_score_i32`` in integer torch ops,
     exact, on the device of ``pred``.
 
@@ -452,10 +467,15 @@ def track_score(pred, counts, seg_start, seg_key, seg_count, hop, window_frames,
     ``category`` int32 (R, W): -1 where the truth is -1, else 0 correct, 1 fifth, 2 relative, 3 parallel, 4 other, 5 undecoded
     (``SCORE_CATEGORIES``, weighted by ``SCORE_WEIGHTS``).  ``tally`` int32 (R, 2, 6): the category counts over all scored windows and
     over the pure ones.  ``changes`` int32 (R, 2): the number of w in 1..count-1 with ``pred[w] != pred[w-1]``, and the same for
-    ``truth``.  A recording with count 0 or no segments gets zeros in both."""
+    ``truth``.  A recording with count 0 or no segments gets zeros in both.
+
+    ``tuning_cents`` (R,): the track was made from retuned audio (``KeyTrack.tuning_cents``), whose time axis is stretched by
+    ``rho_i = 2 ** (cents_i / 1200)``: the boundaries are moved with it first (``scale_boundaries``), as ``KeyTrack.score`` does."""
     dev = pred.device
     R, W = pred.shape
     seg_start, seg_key = seg_start.to(dev), seg_key.to(dev)
+    if tuning_cents is not None:
+        seg_start = scale_boundaries(seg_start, tuning_cents)
     ns = torch.as_tensor(seg_count, device=dev).to(torch.int64).reshape(R).clamp(0, seg_start.shape[1])
     n = torch.full((R,), W, device=dev, dtype=torch.int64) if counts is None else \
         torch.as_tensor(counts, device=dev).to(torch.int64).reshape(R).clamp(0, W)
@@ -639,3 +659,115 @@ def weighted_general_step(key_out, tonic_out, genre_out, key_labels, tonic_label
         if genre_out is not None:
             d_genre = gw * (wm * inv_g)[:, None] * (torch.softmax(genre, dim=1) - F.one_hot(g_idx, genre.shape[1]).to(dt))
         return scalars, (d_key, d_tonic, d_genre)
+
+
+# ---- tuning: how far a recording sits from A4 = 440 Hz, and the varispeed resampler that puts it back (ake_tuning_estimate_f32 / ake_retune_f32) ----
+
+TUNING_BINS_PER_SEMITONE = 3
+RETUNE_MAX_CENTS = 50.0
+RETUNE_MAX_RATIO = 1.029302236643492  # 2 ** (50 / 1200) as one double: the same literal in csrc/audio.hip, so every floor agrees
+RETUNE_ZEROS = 32                    # Z: zero crossings of the windowed sinc on either side
+RETUNE_BETA = 9.0                    # Kaiser beta of its window
+RETUNE_CUTOFF = 0.94                 # c: its cutoff as a share of Nyquist, below 2 ** (-50 / 1200) = 0.9715
+RETUNE_RESOLUTION = 256              # table entries per sample; the kernel interpolates linearly between them
+
+
+def estimate_tuning(logmag, counts=None, min_strength=0.0):
+    """The detuning of B recordings from their log-CQT (B, n_bins, T) -> ``(cents, strength)``, float64 (B,): the float64 model of
+    ``ake_tuning_estimate_f32``.
+
+    The transform has 3 bins per semitone with in-tune notes on bins ``k = 0 (mod 3)`` (``n_bins`` a multiple of 3, else
+    ``ValueError``).  With ``m = expm1(L)`` the magnitudes and ``P_j`` the sum of ``m ** 2`` over the bins ``k = j (mod 3)`` and the frames
+    ``t < counts[i]`` (default: all)::
+
+        z = P_0 + P_1 e^{2 pi i / 3} + P_2 e^{4 pi i / 3},    cents = 100 arg(z) / (2 pi),    strength = |z| / (P_0 + P_1 + P_2)
+
+    ``cents`` lies in (-50, 50], positive = sharp; ``strength`` in [0, 1] is 1 when all power sits on one bin position and 0 when the
+    three carry the same.  A row without power gives (0, 0).  A row with ``strength < min_strength`` reports ``cents = 0``."""
+    L = torch.as_tensor(logmag).detach().to(torch.float64)
+    if L.dim() != 3 or L.shape[1] % TUNING_BINS_PER_SEMITONE != 0:
+        raise ValueError(f"estimate_tuning: logmag must be (B, n_bins, T) with n_bins a multiple of 3, got {tuple(L.shape)}")
+    B, P, T = L.shape
+    power = torch.expm1(L) ** 2
+    if counts is not None:
+        power = torch.where(_behind_count(counts, B, T, L.device)[:, None, :], torch.zeros_like(power), power)
+    P0, P1, P2 = (power[:, j::3].sum(dim=(1, 2)) for j in range(3))
+    re, im = P0 - 0.5 * (P1 + P2), (3.0 ** 0.5 / 2.0) * (P1 - P2)
+    total = P0 + P1 + P2
+    live = total > 0
+    cents = torch.where(live, 100.0 * torch.atan2(im, re) / (2.0 * torch.pi), torch.zeros_like(total))
+    strength = torch.where(live, torch.sqrt(re * re + im * im) / torch.where(live, total, torch.ones_like(total)), torch.zeros_like(total))
+    strength = strength.clamp(max=1.0)
+    return torch.where(strength < float(min_strength), torch.zeros_like(cents), cents), strength
+
+
+def retune_out_len(n):
+    """Width of a retuned buffer for rows of ``n`` samples: ``floor(n * 2 ** (50 / 1200)) + 1``, the longest output plus one
+    (``ake_retune_out_len``)."""
+    import math
+    return int(math.floor(int(n) * RETUNE_MAX_RATIO)) + 1
+
+
+def retune_table():
+    """The retuner's filter as the kernel holds it: float32 ``h(q / RETUNE_RESOLUTION)``, ``q = 0 .. Z * RETUNE_RESOLUTION``, of
+    ``h(d) = c sinc(c d) I0(beta sqrt(1 - (d / Z) ** 2)) / I0(beta)``; the last entry (``d = Z``) is 0."""
+    import numpy as np
+    Z, R, c = RETUNE_ZEROS, RETUNE_RESOLUTION, RETUNE_CUTOFF
+    d = np.arange(Z * R + 1, dtype=np.float64) / R
+    h = c * np.sinc(c * d) * np.i0(RETUNE_BETA * np.sqrt(np.maximum(0.0, 1.0 - (d / Z) ** 2))) / np.i0(RETUNE_BETA)
+    h[-1] = 0.0
+    return h.astype(np.float32)
+
+
+def retune_reference(x, cents, lengths=None):
+    """Varispeed resampling that undoes a detuning of ``cents``: the float64 model of ``ake_retune_f32`` -> ``(y, n_out)``, numpy.
+
+    ``x`` (B, n) or (n,); ``cents`` one value or (B,), rounded to float32 as the kernel receives it, NaN read as 0 and clamped to
+    +-50; ``lengths`` (B,): row i holds ``lengths[i] <= n`` samples.  With ``rho = 2 ** (cents / 1200)``: ``n_out = floor(n_i * rho)`` and::
+
+        y[k] = sum_j x[j] h(k / rho - j)      over |k / rho - j| < Z,    x = 0 outside [0, n_i)
+
+    so a recording that is sharp (``cents > 0``) comes out longer and lower.  ``h`` is read from ``retune_table`` the way the kernel
+    reads it: ``k / rho`` in float64, its fraction rounded to float32, the two neighbouring table entries blended linearly; the 2 Z taps
+    are added in ascending j.  ``y`` is (B, ``retune_out_len(n)``), zeros behind ``n_out[i]``.  A row with ``cents == 0`` is copied."""
+    import numpy as np
+    x = np.asarray(x, dtype=np.float64)
+    single = x.ndim == 1
+    if single:
+        x = x[None]
+    B, n = x.shape
+    c32 = np.broadcast_to(np.asarray(cents, dtype=np.float32), (B,)).astype(np.float64)
+    c32 = np.clip(np.where(np.isnan(c32), 0.0, c32), -RETUNE_MAX_CENTS, RETUNE_MAX_CENTS)
+    n_in = np.full(B, n, dtype=np.int64) if lengths is None else np.clip(np.asarray(lengths, dtype=np.int64).reshape(B), 0, n)
+    Z, R = RETUNE_ZEROS, RETUNE_RESOLUTION
+    G = retune_table().astype(np.float64)
+    y = np.zeros((B, retune_out_len(n)), dtype=np.float64)
+    n_out = np.zeros(B, dtype=np.int64)
+    for b in range(B):
+        nb = int(n_in[b])
+        if c32[b] == 0.0:
+            y[b, :nb], n_out[b] = x[b, :nb], nb
+            continue
+        # (at the clamp the ratio is the literal, not a power: no rounding of exp2 can push n_out past the buffer's width)
+        rho = RETUNE_MAX_RATIO if c32[b] >= RETUNE_MAX_CENTS else 1.0 / RETUNE_MAX_RATIO if c32[b] <= -RETUNE_MAX_CENTS else 2.0 ** (c32[b] / 1200.0)
+        inv = 1.0 / rho
+        no = int(np.floor(nb * rho))
+        n_out[b] = no
+        pos = np.arange(no, dtype=np.float64) * inv
+        j0 = np.floor(pos)
+        fr = (pos - j0).astype(np.float32) * np.float32(R)                                   # exact: R is a power of two
+        r = np.minimum(fr.astype(np.int64), R - 1)
+        t = (fr - r.astype(np.float32)).astype(np.float64)
+        xp = np.concatenate([np.zeros(Z), x[b, :nb], np.zeros(Z + 1)])                      # sample j at index j + Z
+        j0 = j0.astype(np.int64)
+        acc = np.zeros(no, dtype=np.float64)
+        for m in range(-Z + 1, Z + 1):                                                      # tap j = j0 + m, at d = fraction - m
+            if m <= 0:
+                q = r - m * R
+                w = G[q] + t * (G[q + 1] - G[q])
+            else:
+                q = m * R - r - 1
+                w = G[q + 1] + t * (G[q] - G[q + 1])
+            acc += xp[j0 + m + Z] * w
+        y[b, :no] = acc
+    return (y[0], int(n_out[0])) if single else (y, n_out)

@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from . import _lib, metrics
+from . import _lib, metrics, tuning as _tuning
 from .audio import get_resampler, pcm16_rows
 from .cqt import WHOLE_SONG_FRAMES, CQTPlan, get_any_hop_plan, hop_for, hop_for_window
 from .models import PitchClassNet
@@ -139,7 +139,12 @@ class KeyTrack:
     likelihoods: it compares transitions on the same recording and means nothing else).  All three are None otherwise.
 
     ``hop``, ``window_frames``, ``stride_frames`` and ``sample_rate`` are the track's geometry in samples and frames (0 on a track
-    built by hand): ``score`` needs them to place the windows on the annotations."""
+    built by hand): ``score`` needs them to place the windows on the annotations.
+
+    ``track(tuning=...)`` adds ``tuning_cents`` (R,) float32, the detuning every recording was retuned by, and with ``tuning="auto"``
+    ``tuning_strength`` (R,), how clearly it was measured (``metrics.estimate_tuning``); both are None on a plain track.  Such a track
+    was made from audio whose time axis is stretched by ``rho_i = 2 ** (cents_i / 1200)``: ``times`` and the geometry are the
+    retuned audio's, ``segments`` and ``score`` translate to and from the recording's own time."""
     key: torch.Tensor
     tonic: torch.Tensor
     genre: torch.Tensor | None
@@ -160,16 +165,18 @@ class KeyTrack:
     window_frames: int = 0
     stride_frames: int = 0
     sample_rate: int = 0
+    tuning_cents: torch.Tensor | None = None
+    tuning_strength: torch.Tensor | None = None
 
     def _tensors(self):
-        """Every device tensor of the track; the two of a smooth track and the three of its posteriors only when it has them (a plain
-        track lists what it always did)."""
-        plain = (self.key, self.tonic, self.genre, self.key_id, self.sig, self.tonic_id, self.confidence, self.counts)
-        if self.emissions is None and self.smooth_key_id is None:
-            return plain
-        if self.posteriors is None:
-            return plain + (self.emissions, self.smooth_key_id)
-        return plain + (self.emissions, self.smooth_key_id, self.posteriors, self.smooth_confidence, self.log_likelihood)
+        """Every device tensor of the track; the two of a smooth track, the three of its posteriors and the two of a retuned track only
+        when it has them (a plain track lists what it always did)."""
+        out = (self.key, self.tonic, self.genre, self.key_id, self.sig, self.tonic_id, self.confidence, self.counts)
+        if self.emissions is not None or self.smooth_key_id is not None:
+            out += (self.emissions, self.smooth_key_id)
+            if self.posteriors is not None:
+                out += (self.posteriors, self.smooth_confidence, self.log_likelihood)
+        return out + tuple(t for t in (self.tuning_cents, self.tuning_strength) if t is not None)
 
     def segments(self, recording: int, smoothed: bool | None = None, confidence: bool = False):
         """Run-length encoding of one recording's key labels on the host -> list of ``(start_s, end_s, key_id, name)``.  A window stands
@@ -180,7 +187,10 @@ class KeyTrack:
         path when the track has one, ``key_id`` otherwise.
 
         ``confidence=True``: every tuple gets a fifth item, the mean of ``smooth_confidence`` over the segment's windows: how sure the
-        smoother is of the key it names there (``ValueError`` on a track without posteriors)."""
+        smoother is of the key it names there (``ValueError`` on a track without posteriors).
+
+        On a retuned track (``tuning_cents``) the times are divided by the recording's ``rho``: they are seconds of the recording as it
+        was handed in, not of its retuned copy."""
         if confidence and self.smooth_confidence is None:
             raise ValueError("segments(confidence=True): this track has no posteriors; make it with track(..., smooth=True, posteriors=True)")
         if smoothed and self.smooth_key_id is None:
@@ -191,12 +201,13 @@ class KeyTrack:
         times = self.times[:n].tolist()
         conf = self.smooth_confidence[recording, :n].cpu().tolist() if confidence else None
         half_w, half_s = self.window_seconds / 2, self.stride_seconds / 2
+        rho = 1.0 if self.tuning_cents is None else 2.0 ** (float(self.tuning_cents[recording]) / 1200.0)
         out, a = [], 0
         for b in range(n):
             if b + 1 < n and ids[b + 1] == ids[a]:
                 continue
-            start = 0.0 if a == 0 else times[a] - half_s
-            end = times[b] + (half_w if b == n - 1 else half_s)
+            start = 0.0 if a == 0 else (times[a] - half_s) / rho
+            end = (times[b] + (half_w if b == n - 1 else half_s)) / rho
             seg = (start, end, ids[a], metrics.KEY_NAMES[ids[a]] if ids[a] >= 0 else "unknown")
             out.append(seg + (sum(conf[a:b + 1]) / (b + 1 - a),) if confidence else seg)
             a = b + 1
@@ -207,7 +218,10 @@ class KeyTrack:
         """Score the track against ``annotations`` on the device (``ake_track_score_i32``, one launch; ``metrics.track_score`` is its
         restatement) -> ``TrackScore``.  ``smoothed`` picks the source as in ``segments``: True ``smooth_key_id`` (``ValueError`` if the
         track has none), False ``key_id``, None the smoothed path when there is one.  The annotations are in samples at the track's
-        sample rate.  ``ValueError`` on a track without its geometry (``hop``, ``window_frames``, ``stride_frames``)."""
+        sample rate.  ``ValueError`` on a track without its geometry (``hop``, ``window_frames``, ``stride_frames``).
+
+        On a retuned track (``tuning_cents``) the annotation boundaries are first moved onto the retuned time axis,
+        ``floor(start * rho_i)`` in float64 torch ops on the device (``metrics.scale_boundaries``); the launch is the same."""
         if smoothed and self.smooth_key_id is None:
             raise ValueError("score(smoothed=True): this track has no smoothed path; make it with track(..., smooth=True)")
         if self.hop <= 0 or self.window_frames <= 0 or self.stride_frames <= 0:
@@ -224,7 +238,10 @@ class KeyTrack:
         if W == 0:
             tally.zero_(); changes.zero_()
             return TrackScore(truth, category, tally, changes)
-        start = annotations.seg_start.to(device=dev, dtype=torch.int64).contiguous()
+        start = annotations.seg_start.to(device=dev, dtype=torch.int64)
+        if self.tuning_cents is not None:
+            start = metrics.scale_boundaries(start, self.tuning_cents)
+        start = start.contiguous()
         key = annotations.seg_key.to(device=dev, dtype=torch.int32).contiguous()
         count = annotations.seg_count.to(device=dev, dtype=torch.int32).contiguous()
         pred, counts = pred.contiguous(), self.counts.to(torch.int32).contiguous()
@@ -252,7 +269,17 @@ class KeyEstimator:
     Clip i is transformed at its own hop ``n_i // W + 1`` (``n_i`` = ``lengths[i]``, or n), which gives ``T_i <= W`` frames, zero-padded
     to F = 592 frames (the reference's item width; for W > 592, ``F = max(min(W, max T_i), 592)``, which reads the lengths on the host).
     The net then runs on (B, 1, n_bins, F) with ``seq_length=None``: its pooling covers all F frames, the zero tail included, as the
-    reference's does.  ``wrap_mode`` has no meaning here ("true_end" is refused)."""
+    reference's does.  ``wrap_mode`` has no meaning here ("true_end" is refused).
+
+    ``tuning`` (``__call__`` and ``track``; not in the reference, which assumes A4 = 440 Hz everywhere): None (default) is the code
+    path without it, untouched -- same launches, same bits.  ``"auto"`` measures every recording's detuning from one transform at the
+    estimator's plan (``estimate_tuning``), resamples it by ``2 ** (cents / 1200)`` (``ake_amd.retune``, one launch) and then runs the
+    call on the retuned audio with the retuned lengths: that first transform is the price of the estimate, so the call transforms
+    twice.  A number or a (B,) tensor of cents skips the estimate: one transform and one extra launch.  ``min_strength``: recordings
+    whose estimate is weaker keep their audio (0 cents), decided on the device.  The retuned batch is always ragged, in a buffer of
+    ``ake_retune_out_len(n)`` columns (the widest a row can get), so nothing waits for the device; ``lengths``, ``rate``, ``channel``,
+    int16 audio, ``streams`` > 1, ``wrap_mode="true_end"`` and ``frames=0`` work as without it.  The resampler discards content above
+    0.94 of the Nyquist frequency: an estimator whose transform reaches that far refuses ``tuning`` with a ``ValueError``."""
 
     def __init__(self, net: PitchClassNet, sample_rate: int = 22050, frames: int = 5, streams: int = 1, wrap_mode: str = "dataset_max",
                  q_mode: int = 0, window_size: int = WHOLE_SONG_FRAMES):
@@ -283,7 +310,8 @@ class KeyEstimator:
                 cur.wait_stream(slot["stream"])
 
     @torch.no_grad()
-    def __call__(self, audio: torch.Tensor, lengths: torch.Tensor | None = None, rate: int | None = None, channel: int = 0):
+    def __call__(self, audio: torch.Tensor, lengths: torch.Tensor | None = None, rate: int | None = None, channel: int = 0,
+                 tuning=None, min_strength: float = 0.0):
         """audio (B, n) or (B, C, n) float32 on the GPU -> tuple of (B,12), (B,12)[, (B,11)] float32 tensors.
 
         int16 audio is 16-bit PCM, sample / 32768 (``ake_amd.pcm16_to_float``): mono at the estimator's rate goes straight to the PCM
@@ -295,13 +323,87 @@ class KeyEstimator:
         (``seq_length`` = ``1 + lengths[i] // hop``), as a ``KeyDataset`` batch of unequal clips is (KeyDataset.py:245-256).
         ``rate``: sample rate of ``audio`` when it is not the estimator's -- it is resampled on the device first
         (``scipy.signal.resample_poly``'s filter; with ``frames=0`` each clip's hop is then taken from its resampled length); ``channel``: which channel of (B, C, n) audio to take (0 = the reference's
-        ``waveform[0]``, KeyDataset.py:480) or -1 for the mean of all."""
+        ``waveform[0]``, KeyDataset.py:480) or -1 for the mean of all.  ``tuning``, ``min_strength``: see the class."""
         self.net._sync_weights(self.device, for_eval=True)
         if audio.dim() == 3 or (rate is not None and int(rate) != self.sample_rate):
             rs = get_resampler(self.sample_rate if rate is None else int(rate), self.sample_rate, self.device)
             audio, len_out = rs(audio, channel=channel, lengths=lengths)
             lengths = len_out if lengths is not None else None
-        return self._issue(self._run_wrapped, audio, lengths)
+        if tuning is None:
+            return self._issue(self._run_wrapped, audio, lengths)
+        cents = self._given_tuning(tuning, audio.shape[0])
+        return self._issue(lambda slot, a, l: self._run_wrapped(slot, *self._retuned(slot, a, l, cents, min_strength)[:2]), audio, lengths)
+
+    def _given_tuning(self, tuning, B):
+        """``tuning`` of ``__call__`` / ``track`` checked -> None for "auto", else the (B,) float32 cents on the device."""
+        top = 32.70319566257483 * 2.0 ** ((self.plan.n_bins - 1) / self.plan.bins_per_octave)           # C1, the plan's fmin
+        if top >= metrics.RETUNE_CUTOFF * self.sample_rate / 2:
+            raise ValueError(f"tuning: the retuner keeps {metrics.RETUNE_CUTOFF} of the Nyquist frequency, and this estimator's top bin "
+                             f"({top:.0f} Hz at {self.sample_rate} Hz) lies beyond it")
+        if isinstance(tuning, str):
+            if tuning != "auto":
+                raise ValueError('tuning must be None, "auto", a number of cents or a (B,) tensor of cents')
+            return None
+        if isinstance(tuning, torch.Tensor):
+            cents = tuning.detach().to(device=self.device, dtype=torch.float32).reshape(-1)
+            if cents.numel() != B:
+                raise ValueError(f"tuning: {B} recordings but {cents.numel()} tunings")
+            # what the kernel would read anyway (NaN as 0, beyond +-50 as +-50), made explicit here, on the device, so that the cents a
+            # track carries are the cents its audio was resampled by
+            return torch.nan_to_num(cents, nan=0.0).clamp(-metrics.RETUNE_MAX_CENTS, metrics.RETUNE_MAX_CENTS).contiguous()
+        if not abs(float(tuning)) <= metrics.RETUNE_MAX_CENTS:
+            raise ValueError(f"tuning: {tuning} cents; a detuning lies within +-{metrics.RETUNE_MAX_CENTS:g} cents (beyond that it is the next semitone)")
+        return torch.full((B,), float(tuning), dtype=torch.float32, device=self.device)
+
+    def _slot_ws(self, slot, nbytes):
+        if slot["ws"] is None or slot["ws"].numel() < nbytes:
+            slot["ws"] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=self.device)
+        return slot["ws"]
+
+    def _estimate(self, slot, audio, lengths, min_strength=0.0):
+        """One transform at the estimator's plan in the slot's workspace, then ``ake_tuning_estimate_f32`` in the same place (same
+        stream, behind it) -> ``(cents, strength)``.  The ragged transform writes zeros behind every row's frames: no counts needed."""
+        L = _lib.lib()
+        audio = audio.to(self.device)
+        B, n = audio.shape
+        if self.frames <= 0:                                         # whole-song mode: every clip at its own hop, as the net will see it
+            W = self.window_size
+            # T_i <= W frames per clip.  (_run_whole_song reads the lengths on the host to trim this width for W > 592; here the
+            # zero frames behind a clip add nothing to the sums, so the full W serves and nothing waits for the device)
+            F = max(W, WHOLE_SONG_FRAMES)
+            if lengths is None:
+                hops = torch.full((B,), hop_for_window(n, W), dtype=torch.int32, device=self.device)
+            else:
+                lengths = torch.as_tensor(lengths).to(device=self.device, dtype=torch.int64).contiguous()
+                hops = hop_for_window(lengths, W).to(torch.int32)
+            ws = self._slot_ws(slot, max(self.plan.workspace_bytes_hops(B, n, F), int(L.ake_tuning_workspace_bytes(B, F))))
+            mel = self.plan.logmag_hops(audio, hops, lengths, out_frames=F, workspace=ws)
+        else:
+            T = self.plan.num_frames(n)
+            ws = self._slot_ws(slot, max(int(L.ake_cqt_workspace_bytes(self.plan.handle, B, n)), int(L.ake_tuning_workspace_bytes(B, T))))
+            mel = self.plan.logmag(audio, lengths=lengths, workspace=ws)
+        return _tuning.estimate_tuning(mel, None, min_strength, workspace=ws)
+
+    def _retuned(self, slot, audio, lengths, cents, min_strength):
+        """-> ``(retuned audio, retuned lengths, cents, strength)``; ``cents`` None: estimated here (``strength`` is None otherwise)."""
+        strength = None
+        if cents is None:
+            cents, strength = self._estimate(slot, audio, lengths, min_strength)
+        audio = audio.to(self.device)
+        audio, lengths = _tuning.retune(audio, cents, lengths)
+        return audio, lengths, cents, strength
+
+    @torch.no_grad()
+    def estimate_tuning(self, audio: torch.Tensor, lengths: torch.Tensor | None = None, rate: int | None = None, channel: int = 0,
+                        min_strength: float = 0.0):
+        """How far every recording sits from A4 = 440 Hz -> ``(cents, strength)``, float32 (B,) on the device: one transform at the
+        estimator's plan, in its ragged form, then ``ake_amd.estimate_tuning`` (``metrics.estimate_tuning`` is the definition).  ``audio``,
+        ``lengths``, ``rate``, ``channel``, ``streams`` > 1 and ``join()`` as in ``__call__``."""
+        if audio.dim() == 3 or (rate is not None and int(rate) != self.sample_rate):
+            rs = get_resampler(self.sample_rate if rate is None else int(rate), self.sample_rate, self.device)
+            audio, len_out = rs(audio, channel=channel, lengths=lengths)
+            lengths = len_out if lengths is not None else None
+        return self._issue(lambda slot, a, l: self._estimate(slot, a, l, min_strength), audio, lengths)
 
     def _issue(self, run, audio, lengths):
         """``run(slot, audio, lengths)`` on the caller's stream (``streams`` == 1) or on the next side stream in turn."""
@@ -327,7 +429,8 @@ class KeyEstimator:
     @torch.no_grad()
     def track(self, audio: torch.Tensor, lengths: torch.Tensor | None = None, rate: int | None = None, channel: int = 0,
               window_seconds: float = 15.0, stride_seconds: float = 5.0, smooth: bool = False, mean_key_seconds: float = 60.0,
-              transition: torch.Tensor | None = None, signature_weight: float = 1.0, posteriors: bool = False) -> KeyTrack:
+              transition: torch.Tensor | None = None, signature_weight: float = 1.0, posteriors: bool = False,
+              tuning=None, min_strength: float = 0.0) -> KeyTrack:
         """The key of long recordings over time: audio (R, n) or (R, C, n) float32 on the GPU -> ``KeyTrack``.  int16 audio is 16-bit
         PCM, as in ``__call__``.
 
@@ -356,7 +459,11 @@ class KeyEstimator:
         ``posteriors=True`` (with ``smooth=True``; a ``ValueError`` without it) appends the forward-backward pass over the same
         emissions and transition, two more launches on the same stream, and fills ``KeyTrack.posteriors``, ``smooth_confidence`` and
         ``log_likelihood`` (``metrics.key_posteriors``).  Nothing else of the track changes with it.  ``ake_amd.fit_key_transition``
-        fits a ``transition`` to smooth tracks' own emissions; the same table scores it."""
+        fits a ``transition`` to smooth tracks' own emissions; the same table scores it.
+
+        ``tuning``, ``min_strength``: see the class.  The track is then that of the retuned audio -- its ``times`` and geometry are the
+        retuned time axis -- and carries ``tuning_cents`` (and ``tuning_strength`` with "auto"), by which ``KeyTrack.segments`` and
+        ``KeyTrack.score`` translate to and from the recording's own time."""
         if posteriors and not smooth:
             raise ValueError("track(posteriors=True) needs smooth=True: the posteriors belong to the smoothed track's emissions and transition")
         self._refuse_untrackable()
@@ -369,7 +476,16 @@ class KeyEstimator:
         sf = track_stride_frames(stride_seconds, self.frames)
         # (made on the caller's stream, which every side stream waits for before it runs the call)
         smoothing = (self._transition(sf, mean_key_seconds, transition), float(signature_weight), bool(posteriors)) if smooth else None
-        return self._issue(lambda slot, a, l: self._run_track(slot, a, l, wf, sf, smoothing), audio, lengths)
+        if tuning is None:
+            return self._issue(lambda slot, a, l: self._run_track(slot, a, l, wf, sf, smoothing), audio, lengths)
+        cents = self._given_tuning(tuning, audio.shape[0])
+
+        def run(slot, a, l):
+            a, l, used, strength = self._retuned(slot, a, l, cents, min_strength)
+            track = self._run_track(slot, a, l, wf, sf, smoothing)
+            track.tuning_cents, track.tuning_strength = used, strength
+            return track
+        return self._issue(run, audio, lengths)
 
     def _refuse_untrackable(self):
         """What ``track`` and ``training_windows`` cannot slide windows over."""

@@ -604,6 +604,48 @@ int ake_synth_partials_f32(const int32_t* offsets_dev, const double* cps_dev, co
                            size_t workspace_bytes, ake_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Tuning: how far a recording sits from A4 = 440 Hz, and the resampler that puts it back.  Not in the reference (its librosa 0.9.2
+ * transform runs at tuning = 0.0).  Opt-in: nothing else in this library calls either.  Host models: metrics.estimate_tuning and
+ * metrics.retune_reference.
+ * ---------------------------------------------------------------------------------------- */
+/* The estimate, from a log-CQT with 3 bins per semitone and in-tune notes on the bins k = 0 (mod 3) (36 bins per octave from C1):
+ * mel_dev is [batch][pitches][frames] (frames_major == 0, as ake_cqt_logmag*_f32 write it) or [batch][frames][pitches] (frames_major
+ * != 0, ake_cqt_logmag_frames_major_f32).  counts_dev (int32 [batch], nullable): recording i has counts[i] frames, clamped to
+ * 0..frames; the ragged transforms write zeros behind a recording's frames, which add nothing, so their output needs no counts.  With
+ * m = expm1(mel) and P_j the sum of m^2 over the bins k = j (mod 3) and the recording's frames:
+ *   z = P_0 + P_1 e^{2 pi i / 3} + P_2 e^{4 pi i / 3}
+ *   cents_dev[i]    = 100 arg(z) / (2 pi), in (-50, 50], positive = sharp
+ *   strength_dev[i] = |z| / (P_0 + P_1 + P_2), in [0, 1]: 1 when all the power sits on one bin position, 0 when the three carry the same
+ * A recording without power gets (0, 0), never NaN.  A recording whose strength is below min_strength gets cents 0 (the decision is
+ * made on the device, on the strength in double).  pitches that are no multiple of 3: AKE_ERR_UNSUPPORTED.
+ * Two launches: blocks of (64 frames, one recording) reduce their tile to the three sums in double (expm1 in double), then one thread
+ * per recording adds its chunks in chunk order and evaluates atan2 in double.  No floating-point atomics: two runs on the same input
+ * are bit-identical.  The workspace (8-byte aligned) holds the per-chunk sums. */
+size_t ake_tuning_workspace_bytes(int batch, int frames);
+int ake_tuning_estimate_f32(const float* mel_dev, int frames_major, int batch, int pitches, int frames, const int32_t* counts_dev,
+                            float min_strength, float* cents_dev, float* strength_dev, void* workspace, size_t workspace_bytes,
+                            ake_stream_t stream);
+/* Retuning: row i is resampled by rho_i = 2^(cents_dev[i] / 1200), which undoes a detuning of cents_dev[i] (float32 [batch]; NaN is read
+ * as 0, values beyond +-50 as +-50).  in_dev [batch][in_stride], row i holds lengths_dev[i] samples (int64, clamped to 0..n_max; NULL:
+ * n_max).  n_out_i = floor(n_i * rho_i), written to lengths_out_dev (int64 [batch], nullable), and
+ *   y[k] = sum_j x[j] h(k / rho_i - j)   over |k / rho_i - j| < Z,   x = 0 outside [0, n_i)
+ *   h(d) = c sinc(c d) I0(beta sqrt(1 - (d / Z)^2)) / I0(beta),   Z = 32, beta = 9, c = 0.94
+ * One filter for every row: c < 2^(-50/1200) = 0.9715, so nothing above the new Nyquist frequency folds back below 0.94 of it;
+ * content above 0.94 of the old Nyquist frequency is discarded.  h is held at 256 entries per sample and blended linearly between
+ * neighbours; k / rho_i is computed in double and only its fraction rounded to float32; the 64 taps are added by fmaf in ascending j.
+ * out_dev [batch][out_stride]: columns [0, ake_retune_out_len(n_max)) of every row are written, zeros at and behind n_out_i;
+ * out_stride >= ake_retune_out_len(n_max) = floor(n_max * 2^(50/1200)) + 1 (2^(50/1200) is one double literal, 1.029302236643492, for this
+ * function and for the kernel's ratio at +-50 cents, so n_out_i < the width always), the longest possible row plus one, so a caller sizes the
+ * buffer without reading a ratio back.  A row with cents == 0 is copied bit for bit.  One launch.  The PCM form reads int16 in place
+ * (any base, any stride >= n_max) and gives the float form's results on the converted audio (s / 32768), bit for bit.
+ * The first call on a device uploads the filter table (32 KiB, a synchronous copy): make it before capturing into a graph. */
+int64_t ake_retune_out_len(int64_t n);
+int ake_retune_f32(const float* in_dev, int batch, int64_t n_max, int64_t in_stride, const int64_t* lengths_dev, const float* cents_dev,
+                   float* out_dev, int64_t out_stride, int64_t* lengths_out_dev, ake_stream_t stream);
+int ake_retune_pcm16_f32(const int16_t* in_dev, int batch, int64_t n_max, int64_t in_stride, const int64_t* lengths_dev,
+                         const float* cents_dev, float* out_dev, int64_t out_stride, int64_t* lengths_out_dev, ake_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel timing with hipEvents recorded on the launch stream (bench.py roofline leg).
  * ---------------------------------------------------------------------------------------- */
 int ake_prof_enable(const char* name_filter /* substring, NULL or "" = all */, int on);
