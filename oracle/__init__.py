@@ -17,6 +17,9 @@ Pinning status (see DESIGN.md section "Oracle"):
   * ``mirex_oracle``  -- PINNED against the reference ``mirex_score`` and the
     ``mel_shifting_*`` helpers the same way.
   * ``loss_oracle``   -- PINNED against the reference ``general_step`` loss.
+  * ``fit_oracle``    -- a short ``Trainer.fit`` on top of the two (autograd +
+    ``torch.optim.Adam``); ``make_trained.py`` runs it on the CPU to produce
+    ``tests/golden/pcnet_trained.npz`` (no reference tree needed).
   * ``cqt_oracle``    -- PARITY UNPINNED.  The reference's CQT is one call into
     third-party ``librosa`` (pinned 0.9.2 in requirements.txt:250, not vendored,
     not installable here) and the reference holds no fixture at that boundary.

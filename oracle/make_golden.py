@@ -432,7 +432,11 @@ def main():
                             **sd_to_npz(sd_t))
     torch.set_grad_enabled(False)
 
-    with open(os.path.join(GOLD, "PROVENANCE.json"), "w") as f:
+    prov = os.path.join(GOLD, "PROVENANCE.json")
+    if os.path.exists(prov):                     # entries of the other recipes (oracle/make_trained.py) stay
+        with open(prov) as f:
+            report.update({k: v for k, v in json.load(f).items() if k.endswith(".npz")})
+    with open(prov, "w") as f:
         json.dump(report, f, indent=1)
     print("wrote", sorted(os.listdir(GOLD)))
 

@@ -176,7 +176,225 @@ def _time_pool(x, size, site):
     return w.gather(-1, idx.unsqueeze(-1)).squeeze(-1)
 
 
-def equiv_pc_conv(x, weight, bias, same: bool):
+_ROUNDING = None     # set by rounding_model(): the active context
+
+F16_MAX = 65504.0
+
+
+def _f16(t):
+    """Round to IEEE half and back (the device converts with saturation, MODE.FP16_OVFL: clamp first)."""
+    return t.clamp(-F16_MAX, F16_MAX).to(torch.float16).to(t.dtype)
+
+
+def _bf16(t):
+    return t.to(torch.bfloat16).to(t.dtype)
+
+
+def _split(t, fmt):
+    """(hi, lo) of the device's two-term operand split: f16 hi = rn(t), lo = rn((t - hi) * 2^11) / 2^11 (kP2pLoScale); bf16 hi = rn(t),
+    lo = rn(t - hi) (bf16_bits, round to nearest even)."""
+    if fmt == "f16":
+        hi = _f16(t)
+        return hi, _f16((t - hi) * 2048.0) / 2048.0
+    hi = _bf16(t)
+    return hi, _bf16(t - hi)
+
+
+def _weight_scale(w):
+    """f16_weight_scale per output channel: the power of two s with s * max|w| in [2^13, 2^14) (1 for an all-zero channel)."""
+    wmax = w.detach().abs().amax(dim=tuple(range(1, w.dim())), keepdim=True)
+    _, e = torch.frexp(wmax)
+    s = torch.ldexp(torch.ones_like(wmax), (14 - e).clamp(max=100))
+    return torch.where(wmax > 0, s, torch.ones_like(s))
+
+
+class rounding_model:
+    """Context manager: the float64 forward with the operand roundings of the device's ``mixed`` precision, and
+    nothing else of it -- every sum, bias, BatchNorm, activation and pool stays in the dtype of the run.  ``route`` maps the state_dict
+    key of a convolution's weight to how the device multiplies it (``mixed_route`` builds it for a net and a shape):
+      * ``"f16"``: one product of f16 operands.  The activation is rounded to f16; the weight is scaled by its output channel's power of
+        two (``f16_weight_scale``), rounded to f16 and scaled back (pack_p2p_f16_kernel, pack_semi_f16_kernel);
+      * ``"f16+split0"``: the same, but input channel 0 (the log-CQT in front of a stack's first pitch conv, kP2pSplit0) is multiplied
+        f32-equivalently: x w ~ xh wh + xl wh + xh wl;
+      * ``"f16x3"``: both operands split into f16 hi + lo (weights scaled as above), three products (layer0_mfma_kernel);
+      * ``"bf16x3"``: both operands split into bf16 hi + lo, three products (conv_pc_bf16_kernel, pc2pc_fused_kernel, the head kernels).
+    A convolution the route does not name is left alone.  The device rounds the weight AFTER folding the BatchNorm that follows into it
+    (fold_pack; "BatchNorm already folded" in the pack kernels): with ``sd`` given, the model does the same -- it rounds
+    ``w * gamma / sqrt(running_var + eps)`` per output channel and divides the factor out again, so that its weight roundings are the
+    device's own and only the activation roundings are another draw.  Without ``sd`` the weight is rounded as it stands in the
+    state_dict.  ``used`` collects the sites that were rounded.  Without the context nothing changes, to the bit."""
+
+    def __init__(self, route, sd=None):
+        self.route = dict(route)
+        for site, mode in self.route.items():
+            assert mode in ("f16", "f16+split0", "f16x3", "bf16x3"), (site, mode)
+        self.used = []
+        self.fold = {}
+        for site in (self.route if sd is not None else ()):
+            base = site[:-len(".conv2d.weight")] if site.endswith(".conv2d.weight") else site[:-len(".weight")]
+            head, _, last = base.rpartition(".")
+            bn = f"{head}.{int(last) + 1}." if last.isdigit() else base + "_b."
+            if bn + "running_var" in sd:
+                f = (sd[bn + "weight"] / torch.sqrt(sd[bn + "running_var"] + BN_EPS)).detach()
+                self.fold[site] = torch.where(f == 0, torch.ones_like(f), f)
+
+    def __enter__(self):
+        global _ROUNDING
+        assert _ROUNDING is None, "rounding_model does not nest"
+        _ROUNDING = self
+        return self
+
+    def __exit__(self, *exc):
+        global _ROUNDING
+        _ROUNDING = None
+
+
+def _conv(site, x, w, bias, fn):
+    """``fn(x, w, bias)`` -- a convolution, bilinear in (x, w) -- as the active rounding_model multiplies the site ``site``."""
+    mode = None if _ROUNDING is None else _ROUNDING.route.get(site)
+    if mode is None:
+        return fn(x, w, bias)
+    _ROUNDING.used.append(site)
+    if site in _ROUNDING.fold:         # round the weight as the device holds it: with the BatchNorm behind the convolution folded in
+        f = _ROUNDING.fold[site].to(w.dtype).reshape(-1, *([1] * (w.dim() - 1)))
+        inner = fn
+        w, fn = w * f, lambda x_, w_, b_: inner(x_, w_ / f, b_)
+    if mode == "bf16x3":
+        (xh, xl), (wh, wl) = _split(x, "bf16"), _split(w, "bf16")
+        return fn(xh, wh, bias) + fn(xl, wh, None) + fn(xh, wl, None)
+    s = _weight_scale(w)
+    if mode == "f16x3":
+        (xh, xl), (wh, wl) = _split(x, "f16"), _split(w * s, "f16")
+        return fn(xh, wh / s, bias) + fn(xl, wh / s, None) + fn(xh, wl / s, None)
+    y = fn(_f16(x), _f16(w * s) / s, bias)
+    if mode == "f16+split0":      # slot 5: channel 0's weight again, meets the activation's low half; slot 6: the weight's low half, meets the high half
+        (xh, xl), (wh, wl) = _split(x[:, :1], "f16"), _split(w[:, :1] * s, "f16")
+        only0 = lambda t, like: torch.cat([t, torch.zeros_like(like[:, 1:])], dim=1)
+        y = y + fn(only0(xl, x), only0(wh / s, w), None) + fn(only0(xh, x), only0(wl / s, w), None)
+    return y
+
+
+def _p2p_ps_rows_semi(H, T):
+    """p2p_ps_rows(H, T, semi = true) of csrc/pcnet.hip with 8 waves: the rows of a tile of the persistent pitch conv that also runs the
+    semitone conv, 0 where the shape does not qualify (odd frame counts among them)."""
+    if T < 2 or T & 1:
+        return 0
+    J = T // 2
+    Tp = 2 * J + 16                                                       # p2p_pitch
+    plane_of = lambda R: ((R + 6) * Tp + 63) // 64 * 64
+    lds_of = lambda R: (2 * plane_of(R) + 2 * 8 * 3 * 16 * 2) * 16        # kP2pMT = 3
+    R = max(1, min(H, 8 * 3 * 16 // J)) // 3 * 3
+    while R >= 3 and (lds_of(R) > 156 * 1024 or plane_of(R) // 64 > 8 * 3):   # kP2pPieces = 3
+        R -= 3
+    if R < 3 or H < R + 6 or H % 3 or (H // 3) % 12:
+        return 0
+    return R
+
+
+def mixed_route(sd, frames, kernel_size=7, head_layers=2, time_pool_size=2, local=False, keep_taps=False, pitches=None):
+    """Which convolutions the device's ``mixed`` inference forward multiplies in reduced precision for THIS net at THIS frame count, as
+    ``rounding_model`` wants them: a restatement of the arithmetic side of ``build_route()`` (csrc/pcnet.hip) and of the eligibility rules
+    of ``rebuild_bf16_frags()``.  Which launch form runs a stage (per tile, persistent, one launch, fused heads) does not change what is
+    rounded -- those forms are bit-identical to one another -- so batch size and CU count do not enter.  tests/test_gpu_sensitive.py holds
+    this restatement to the kernel timer's labels of the forward it models.
+
+    default net, 76 frames: layer 0's stack f16 x 3; the pitch convs and the semitone conv behind them one f16 product (the log-CQT
+    channel of the first f32-equivalent); the last pitch-class stack and both convs of every head bf16 x 3."""
+    route = {}
+    L = 0
+    while f"model.{L}.pc2pc.layer.0.conv2d.weight" in sd or f"model.{L}.pc2pc.layer.0.denselayer1.norm1.weight" in sd:
+        L += 1
+    dense = "model.0.pc2pc.layer.0.denselayer1.norm1.weight" in sd
+    res = "model.0.pc2pc.layer.3.b1.weight" in sd
+    p2pc_conv = "model.0.pool.conv.weight" in sd
+    stay = L > 1 and "model.1.up_sixth.weight" not in sd
+    if dense or L < 1:
+        return route                                                  # --denseblock: conv_mfma_kernel (f32) throughout, generic heads (final_ch != 16)
+    tp = 1 if local else time_pool_size
+    conv_layers = _count(sd, "model.0.pc2pc.layer.", ".conv2d.weight") if not res else None
+    NF = sd["model.0.pc2pc.layer.0.conv2d.weight"].shape[0]
+    P = pitches if pitches is not None else 288
+    Tl = [frames if i < 2 else None for i in range(L)]
+    for i in range(2, L):
+        Tl[i] = Tl[i - 1] // tp
+    Tf = Tl[L - 1] // tp if L > 1 else frames
+
+    def shape(key):
+        return tuple(sd[key].shape)
+
+    # ---- layer 0 (layer0_plan): the one-launch MFMA form multiplies its 12 x 7 stack f16 x 3; every other form is exact f32 ----
+    if L > 1 and not res and not p2pc_conv and not stay and 2 <= NF <= 4 and 1 <= conv_layers <= 4 and kernel_size == 7 and P % 36 == 0:
+        T0 = Tl[0]
+        ok = shape("model.0.pool_semi.weight")[:2] == (1, 1)
+        for j in range(conv_layers):
+            ok = ok and shape(f"model.0.pc2pc.layer.{3*j}.conv2d.weight") == (NF, 1 if j == 0 else NF, 12, 7)
+        RP, RPp = 4 * ((T0 + 3) // 4) + 8, (T0 + 9) // 2 * 2
+        lds_v = (9 * 12 * RP + P * T0) * 4
+        lds_m = (4 * 12 * RP + 2 * 12 * RPp * 4 + P * T0) * 4
+        if ok and lds_v <= 150 * 1024 and (P * T0) % 4 == 0 and lds_m <= 150 * 1024:
+            for j in range(conv_layers):
+                route[f"model.0.pc2pc.layer.{3*j}.conv2d.weight"] = "f16x3"
+
+    # ---- pitch stacks of the layers >= 1 (p2p_uses_f16, p2p_fuses_semi) ----
+    Pi = P // 3 if stay else P
+    for i in range(1, L):
+        if res:
+            break
+        keys = [f"model.{i}.p2p.layer.{3*j}.weight" for j in range(conv_layers)]
+        f16 = conv_layers >= 2 and Tl[i] <= 146 and all(k in sd and shape(k)[0] == 8 and shape(k)[1] <= 8 and shape(k)[2:] == (7, 7) for k in keys)
+        if not f16:
+            continue
+        for j, k in enumerate(keys):
+            route[k] = "f16+split0" if shape(k)[1] <= 5 else "f16"       # kP2pSplit0 (only a stack's first conv is that narrow)
+        semi = f"model.{i}.pool_semi.weight"
+        if (not keep_taps and not p2pc_conv and not stay and i == L - 1 and semi in sd and shape(semi) == (8, 8, 3, 3)
+                and _p2p_ps_rows_semi(Pi, Tl[i]) > 0):
+            route[semi] = "f16"
+
+    # ---- the last layer's pitch-class stack (pc2pc_uses_bf16; the fused form is the same arithmetic) ----
+    i = L - 1
+    if not res and L > 1:
+        keys = [f"model.{i}.pc2pc.layer.{3*j}.conv2d.weight" for j in range(conv_layers)]
+        if Tl[i] <= 120 and all(shape(k)[0] == 16 and shape(k)[1] <= 16 and shape(k)[2:] == (12, 7) for k in keys):
+            for k in keys:
+                route[k] = "bf16x3"
+    elif not res and L == 1:
+        keys = [f"model.0.pc2pc.layer.{3*j}.conv2d.weight" for j in range(conv_layers)]
+        if Tl[0] <= 120 and all(shape(k)[0] == 16 and shape(k)[1] <= 16 and shape(k)[2:] == (12, 7) for k in keys):
+            for k in keys:
+                route[k] = "bf16x3"
+
+    # ---- heads (HeadForm) ----
+    def eligible0(k):      # pc_bf16_eligible
+        return k in sd and shape(k)[2] in (12, 1) and shape(k)[3] == 7 and shape(k)[1] <= 16 and shape(k)[0] in (16, 32)
+
+    def eligible1(k):      # the 32 -> 1 last convolution of a two-conv head
+        return k in sd and shape(k)[2] in (12, 2) and shape(k)[3] == 7 and shape(k)[0] == 1 and shape(k)[1] == 32
+
+    k0, t0 = "key_classifier.0.conv2d.weight", "tonic_classifier.0.conv2d.weight"
+    final_ch = shape(k0)[1]
+    if not (L > 1 and final_ch == 16 and head_layers >= 2 and eligible0(k0) and eligible0(t0) and Tf <= 120):
+        return route
+    route[k0] = route[t0] = "bf16x3"                                  # Bf16First
+    k1, t1 = "key_classifier.3.conv2d.weight", "tonic_classifier.3.conv2d.weight"
+    T2 = Tf - 2 * (kernel_size - 1)
+    if not (head_layers == 2 and eligible1(k1) and eligible1(t1) and T2 > 0 and (12 * ((T2 + 15) // 16) + 15) // 16 <= 4):
+        return route
+    route[k1] = route[t1] = "bf16x3"                                  # Head1 / Fused
+    g0, g1 = "genre_classifier.0.weight", "genre_classifier.3.weight"
+    if eligible0(g0) and eligible1(g1) and shape(g0)[2] == 1 and shape(g1)[2] == 2:
+        route[g0] = route[g1] = "bf16x3"
+    return route
+
+
+def f32x3_route(sd, frames, **kw):
+    """The same for the ``f32x3`` precision: the last pitch-class stack and the heads keep their three-term bf16
+    split, the pitch convs run on three f16 products (f32-equivalent to 2^-22; named here wherever ``mixed`` runs them on f16, which is
+    a superset of where ``conv_p2p_f16x3_kernel`` takes them -- the others are exact f32), layer 0 and the semitone convs are exact f32."""
+    return {k: ("bf16x3" if v == "bf16x3" else "f16x3") for k, v in mixed_route(sd, frames, **kw).items() if v == "bf16x3" or ".p2p.layer." in k}
+
+
+def equiv_pc_conv(x, weight, bias, same: bool, site=None):
     """EquivariantPitchClassConvolutionSimple.forward, models.py:36-47.
 
     Wrap the first 11 pitch-class rows below the 12 (``x_wrap``, :45) and run a
@@ -186,7 +404,7 @@ def equiv_pc_conv(x, weight, bias, same: bool):
     assert x.shape[2] == pcs                                   # models.py:44
     x_wrap = torch.cat([x, x[:, :, 0:pcs - 1, :]], dim=2)      # models.py:45
     kd = weight.shape[3]
-    return F.conv2d(x_wrap, weight, bias, padding=(0, kd // 2 if same else 0))
+    return _conv(site, x_wrap, weight, bias, lambda x_, w_, b_: F.conv2d(x_, w_, b_, padding=(0, kd // 2 if same else 0)))
 
 
 def pitch2pitchclass_pool(x, pitch_classes: int = 12, site=None):
@@ -228,11 +446,11 @@ def pitchclass2pitch(x, target_rows: int):
     return x.repeat(1, 1, reps, 1)[:, :, 0:target_rows, :]
 
 
-def _circular_conv(x, weight, bias, stride, pad_hw):
+def _circular_conv(x, weight, bias, stride, pad_hw, site=None):
     """nn.Conv2d(..., padding=pad_hw, padding_mode='circular') (models.py:230,313)."""
     ph, pw = pad_hw
     x = F.pad(x, (pw, pw, ph, ph), mode="circular")
-    return F.conv2d(x, weight, bias, stride=stride)
+    return _conv(site, x, weight, bias, lambda x_, w_, b_: F.conv2d(x_, w_, b_, stride=stride))
 
 
 def _count(sd, prefix, suffix):
@@ -294,7 +512,8 @@ def pc2pc_stack(pc, sd, prefix, training=False, taps=None):
                            training, taps)
     n = _count(sd, prefix + "layer.", ".conv2d.weight")
     for i in range(n):
-        pc = equiv_pc_conv(pc, sd[f"{prefix}layer.{3*i}.conv2d.weight"], sd[f"{prefix}layer.{3*i}.conv2d.bias"], same=True)
+        pc = equiv_pc_conv(pc, sd[f"{prefix}layer.{3*i}.conv2d.weight"], sd[f"{prefix}layer.{3*i}.conv2d.bias"], same=True,
+                           site=f"{prefix}layer.{3*i}.conv2d.weight")
         pc = _act_bn(pc, sd, f"{prefix}layer.{3*i+1}.", training)
         if taps is not None:
             taps[f"{prefix}layer.{3*i+2}"] = pc
@@ -315,7 +534,7 @@ def p2p_stack(p, sd, prefix, training=False, taps=None):
     for i in range(n):
         w = sd[f"{prefix}layer.{3*i}.weight"]
         k = w.shape[2]
-        p = _circular_conv(p, w, sd[f"{prefix}layer.{3*i}.bias"], (1, 1), (k // 2, k // 2))
+        p = _circular_conv(p, w, sd[f"{prefix}layer.{3*i}.bias"], (1, 1), (k // 2, k // 2), site=f"{prefix}layer.{3*i}.weight")
         p = _act_bn(p, sd, f"{prefix}layer.{3*i+1}.", training)
         if taps is not None:
             taps[f"{prefix}layer.{3*i+2}"] = p
@@ -328,7 +547,7 @@ def semitone_pool(p, sd, prefix, training=False):
     3x3 conv, stride (3,1), circular padding (0,1): three third-semitone bins ->
     one semitone, time wraps.
     """
-    x = _circular_conv(p, sd[prefix + "pool_semi.weight"], sd[prefix + "pool_semi.bias"], (3, 1), (0, 1))
+    x = _circular_conv(p, sd[prefix + "pool_semi.weight"], sd[prefix + "pool_semi.bias"], (3, 1), (0, 1), site=prefix + "pool_semi.weight")
     return _act_bn(x, sd, prefix + "pool_semi_b.", training)
 
 
@@ -413,7 +632,7 @@ def _equiv_head(pc, sd, name, training=False):
     idx = 0
     x = pc
     while f"{name}.{idx}.conv2d.weight" in sd:
-        x = equiv_pc_conv(x, sd[f"{name}.{idx}.conv2d.weight"], sd[f"{name}.{idx}.conv2d.bias"], same=False)
+        x = equiv_pc_conv(x, sd[f"{name}.{idx}.conv2d.weight"], sd[f"{name}.{idx}.conv2d.bias"], same=False, site=f"{name}.{idx}.conv2d.weight")
         if f"{name}.{idx+1}.weight" in sd:       # BN follows -> hidden block
             x = _act_bn(x, sd, f"{name}.{idx+1}.", training)
             idx += 3
@@ -427,7 +646,7 @@ def _genre_head(pc, sd, training=False):
     idx = 0
     x = pc
     while f"genre_classifier.{idx}.weight" in sd and sd[f"genre_classifier.{idx}.weight"].dim() == 4:
-        x = F.conv2d(x, sd[f"genre_classifier.{idx}.weight"], sd[f"genre_classifier.{idx}.bias"])
+        x = _conv(f"genre_classifier.{idx}.weight", x, sd[f"genre_classifier.{idx}.weight"], sd[f"genre_classifier.{idx}.bias"], F.conv2d)
         if f"genre_classifier.{idx+1}.running_mean" in sd:
             x = _act_bn(x, sd, f"genre_classifier.{idx+1}.", training)
             idx += 3

@@ -3,6 +3,11 @@
 Tolerance: BASELINE.json states 1e-3 relative (fp32 path vs the reference's fp64 outputs); measured as
 max|a-b| / max|b| per tensor.  The kernels land around 1e-6, so we assert 1e-4 to catch
 regressions long before the stated budget.
+
+What these assertions cannot see: the weights here are seeded-random, their outputs almost constant (the default fixture's key output
+moves by 1e-4 of its maximum between its input and silence), so output parity at TOL does not resolve the input-dependent part -- a
+front-end or plumbing fault passes.  tests/test_gpu_sensitive.py holds the same routes on calibrated and trained weights
+(tests/sensitive.py, tests/test_sensitive_host.py).
 """
 import json
 from argparse import Namespace

@@ -2,7 +2,7 @@
 """BASELINE configs[2] / SURVEY 8d config 3, the parity half: the first 20 OPTIMIZER steps (batch 8, accumulate_grad_batches 8 = 160
 micro-batches = 1 280 clips of the 604-clip synthetic GiantSteps-shaped set, taken in index order and wrapping around) through
 KeyDataset -> PitchClassNet.training_step -> Trainer.fit on the GPU, per-micro-batch training loss against the float64 oracle loop
-(oracle forward in train mode + general_step loss + torch.optim.Adam, tests/test_gpu_training.py::oracle_fit) on the same batches.
+(oracle forward in train mode + general_step loss + torch.optim.Adam, oracle/fit_oracle.py::oracle_fit) on the same batches.
 
 Checker-side (imports oracle/): lives under tests/.  The timing half -- 10 epochs, seconds per epoch -- is tools/config3_train.py.
 
@@ -25,7 +25,7 @@ import torch
 
 torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))         # (a GPU box grants 16 cores, whatever os.cpu_count() says)
 import ake_amd
-from test_gpu_training import oracle_fit
+from oracle.fit_oracle import oracle_fit
 
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 n_clips = int(sys.argv[2]) if len(sys.argv) > 2 else 604
