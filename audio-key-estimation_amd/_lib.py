@@ -116,6 +116,9 @@ SYMBOLS = {
     "ake_retune_out_len": (_I64, [_I64]),
     "ake_retune_f32": (_I, [_P, _I, _I64, _I64, _P, _P, _P, _I64, _P, _P]),
     "ake_retune_pcm16_f32": (_I, [_P, _I, _I64, _I64, _P, _P, _P, _I64, _P, _P]),
+    "ake_profile_workspace_bytes": (_SZ, [_I, _I]),
+    "ake_profile_windows": (_I, [_I, _I, _I]),
+    "ake_profile_emissions_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _I, C.c_float, _P, _P, _P, _P, _P, _SZ, _P]),
     "ake_prof_enable": (_I, [C.c_char_p, _I]),
     "ake_prof_collect": (_I, []),
     "ake_prof_reset": (_I, []),

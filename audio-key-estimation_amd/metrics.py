@@ -771,3 +771,165 @@ def retune_reference(x, cents, lengths=None):
             acc += xp[j0 + m + Z] * w
         y[b, :no] = acc
     return (y[0], int(n_out[0])) if single else (y, n_out)
+
+
+# ---- key-profile emissions: a key track without a trained net (ake_profile_emissions_f32) ----
+
+# Published tone profiles, rows minor and major (the order of KEY_NAMES' two halves), tonic first.  "krumhansl": Krumhansl & Kessler
+# (1982), the probe-tone ratings; "temperley": Temperley (1999), "What's Key for Key?", the revised Krumhansl-Schmuckler profiles.
+KEY_PROFILES = {
+    "krumhansl": ((6.33, 2.68, 3.52, 5.38, 2.60, 3.53, 2.54, 4.75, 3.98, 2.69, 3.34, 3.17),
+                  (6.35, 2.23, 3.48, 2.33, 4.38, 4.09, 2.52, 5.19, 2.39, 3.66, 2.29, 2.88)),
+    "temperley": ((5.0, 2.0, 3.5, 4.5, 2.0, 4.0, 2.0, 4.5, 3.5, 2.0, 1.5, 4.0),
+                  (5.0, 2.0, 3.5, 2.0, 4.5, 4.0, 2.0, 4.5, 2.0, 3.5, 1.5, 4.0)),
+}
+PROFILE_COMPRESSIONS = ("log", "magnitude", "power")
+PROFILE_SILENCE = 1e-12                 # a window is silent when sum_j (x_j - mean)^2 <= PROFILE_SILENCE * 12 * mean^2
+
+
+def key_profile_table(profiles="krumhansl"):
+    """``profiles`` of ``profile_emissions`` checked -> (2, 12) float64 on the host, rows minor and major, tonic first.  A name of
+    ``KEY_PROFILES`` or a (2, 12) tensor; ``ValueError`` for an unknown name, another shape, a value that is not finite or a row that is
+    constant (it correlates with nothing)."""
+    if isinstance(profiles, str):
+        if profiles not in KEY_PROFILES:
+            raise ValueError(f"profiles: unknown name {profiles!r} (KEY_PROFILES has {sorted(KEY_PROFILES)})")
+        return torch.tensor(KEY_PROFILES[profiles], dtype=torch.float64)
+    p = torch.as_tensor(profiles).detach().to(device="cpu", dtype=torch.float64)
+    if tuple(p.shape) != (2, 12):
+        raise ValueError(f"profiles must be a name of KEY_PROFILES or a (2, 12) tensor (rows minor and major, tonic first), got {tuple(p.shape)}")
+    if not bool(torch.isfinite(p).all()):
+        raise ValueError("profiles must be finite")
+    if bool((p == p[:, :1]).all(dim=1).any()):
+        raise ValueError("profiles: a row is constant; it correlates with nothing")
+    return p
+
+
+def _profile_compression(compression):
+    if compression not in PROFILE_COMPRESSIONS:
+        raise ValueError(f"compression must be one of {PROFILE_COMPRESSIONS}, got {compression!r}")
+    return PROFILE_COMPRESSIONS.index(compression)
+
+
+def profile_window_counts(frame_counts, window_frames, stride_frames):
+    """Windows of recordings of ``frame_counts`` frames (integer tensor): ``pipeline.track_counts``, and in the whole-clip mode
+    (``window_frames == 0``) 1 for a recording that has frames, else 0."""
+    n = torch.as_tensor(frame_counts).to(torch.int64)
+    if int(window_frames) == 0:
+        return (n > 0).to(torch.int64)
+    w = torch.div(n - int(window_frames), int(stride_frames), rounding_mode="floor") + 1
+    return torch.where(n < int(window_frames), torch.zeros_like(w), w)
+
+
+def profile_emissions(logmag, window_frames, stride_frames, counts=None, profiles="krumhansl", compression="log", sharpness=10.0):
+    """Key emissions without a net (Krumhansl-Schmuckler): every window's chroma correlated with the 24 rotations of a minor and a major
+    key profile -> ``(chroma (R, W, 12), emissions (R, W, 24), key_id int32 (R, W), confidence (R, W))``, float64: the float64 model of
+    ``ake_profile_emissions_f32``.
+
+    ``logmag`` (R, n_bins, T): a log-CQT with 3 bins per semitone from C, in-tune notes on the bins ``k = 0 (mod 3)`` (``n_bins`` a
+    multiple of 3, else ``ValueError``).  Bin k belongs to semitone ``(k + 1) // 3`` and pitch class ``((k + 1) // 3) % 12``; semitone 0
+    lacks its flat-side bin and the top bin is the flat side of a semitone above the range: both are kept as they come.  With L the
+    log-CQT, ``v = L`` (``compression="log"``), ``expm1(L)`` (``"magnitude"``) or ``expm1(L) ** 2`` (``"power"``)::
+
+        c[r, t, j] = sum of v[r, k, t] over the bins k of pitch class j, in ascending k
+        x[r, w, j] = sum of c[r, t, j] over t = w * stride_frames .. w * stride_frames + window_frames - 1, in ascending t
+
+    ``counts`` (R,): frames of every recording, clamped to 0..T (default T); recording r has
+    ``track_counts(counts[r], window_frames, stride_frames)`` windows and W is that of T.  ``window_frames = 0`` is the whole-clip mode:
+    W = 1, one window over the recording's own ``counts[r]`` frames, none for a recording of 0 frames.
+
+    Key k (``KEY_NAMES`` order) has mode ``k // 12`` (0 minor, 1 major), tonic ``k % 12`` and the profile
+    ``q_k[j] = profiles[mode][(j - tonic) % 12]``.  With ``m = (sum_j x_j) / 12``, ``d_j = x_j - m``, ``sxx = sum_j d_j ** 2`` and the same
+    ``e``, ``see`` of a profile row (all sums in ascending j), ``r_k = (sum_j d_j * e[(j - tonic) % 12]) / sqrt(sxx * see)``, the Pearson
+    correlation, and ``emissions[k] = sharpness * r_k``.  A window with ``sxx <= 1e-12 * 12 * m ** 2`` (all-zero chroma included) is
+    silent: ``r = 0``, ``key_id = -1``, zero chroma.  Otherwise ``key_id`` is the smallest k that attains the maximum ``r_k``,
+    ``confidence`` that ``r_k`` and ``chroma = x / sum_j x_j``.  Behind a recording's window count: zeros, and -1 in ``key_id``.
+
+    ``profiles``: a name of ``KEY_PROFILES`` or a (2, 12) tensor (``key_profile_table``).  ``sharpness = 10.0`` and
+    ``compression = "log"`` are starting values that nobody has measured against annotated music; ``tools/profile_baseline.py`` scores
+    them and their neighbours on synthesised recordings (``profiles/key_profiles.md``)."""
+    L = torch.as_tensor(logmag).detach().to(device="cpu", dtype=torch.float64)
+    if L.dim() != 3 or L.shape[1] % TUNING_BINS_PER_SEMITONE != 0:
+        raise ValueError(f"profile_emissions: logmag must be (R, n_bins, T) with n_bins a multiple of 3, got {tuple(L.shape)}")
+    mode = _profile_compression(compression)
+    prof = key_profile_table(profiles)
+    sharpness = float(sharpness)
+    if not sharpness > 0.0:
+        raise ValueError("profile_emissions: sharpness must be positive")
+    wf, sf = int(window_frames), int(stride_frames)
+    if wf < 0 or sf < 1:
+        raise ValueError("profile_emissions: window_frames must be >= 0 (0: the whole clip) and stride_frames >= 1")
+    R, P, T = L.shape
+    n = torch.full((R,), T, dtype=torch.int64) if counts is None else torch.as_tensor(counts).detach().cpu().to(torch.int64).reshape(R).clamp(0, T)
+    W = int(profile_window_counts(torch.tensor(T), wf, sf))
+    n_win = profile_window_counts(n, wf, sf)
+    v = L if mode == 0 else torch.expm1(L) if mode == 1 else torch.expm1(L) ** 2
+    c = torch.zeros((R, T, 12), dtype=torch.float64)
+    for k in range(P):                                                                       # ascending k
+        c[:, :, ((k + 1) // 3) % 12] += v[:, k, :]
+    c = torch.where((torch.arange(T)[None, :] < n[:, None])[:, :, None], c, torch.zeros_like(c))
+    x = torch.zeros((R, W, 12), dtype=torch.float64)
+    if W > 0:
+        start = torch.arange(W) * sf
+        for i in range(T if wf == 0 else wf):                                                # ascending t (behind counts[r]: zeros)
+            x += c[:, start + i, :]
+    live = torch.arange(W)[None, :] < n_win[:, None]                                         # (R, W)
+    x = torch.where(live[:, :, None], x, torch.zeros_like(x))
+    seq_sum = _ascending_sum
+    m = seq_sum(x) / 12.0
+    d = x - m[..., None]
+    sxx = seq_sum(d * d)
+    silent = ~live | (sxx <= PROFILE_SILENCE * 12.0 * m * m)
+    e = prof - (seq_sum(prof) / 12.0)[:, None]                                               # (2, 12)
+    see = seq_sum(e * e)                                                                     # (2,)
+    j = torch.arange(12)
+    r = torch.zeros((R, W, 24), dtype=torch.float64)
+    for k in range(24):
+        q = e[k // 12][(j - k % 12) % 12]
+        r[:, :, k] = seq_sum(d * q) / torch.sqrt(torch.where(silent, torch.ones_like(sxx), sxx) * see[k // 12])
+    r = torch.where(silent[..., None], torch.zeros_like(r), r)
+    conf = r.max(dim=2).values
+    idx = torch.arange(24)[None, None, :].expand_as(r)
+    key_id = torch.where(r == conf[..., None], idx, torch.full_like(idx, 24)).min(dim=2).values
+    key_id = torch.where(silent, torch.full_like(key_id, -1), key_id).to(torch.int32)
+    conf = torch.where(silent, torch.zeros_like(conf), conf)
+    total = seq_sum(x)
+    chroma = torch.where(silent[..., None], torch.zeros_like(x), x / torch.where(silent, torch.ones_like(total), total)[..., None])
+    return chroma, sharpness * r, key_id, conf
+
+
+def _ascending_sum(t):
+    """Sum over the last dimension in ascending index order (``Tensor.sum`` promises no order)."""
+    s = t[..., 0].clone()
+    for j in range(1, t.shape[-1]):
+        s = s + t[..., j]
+    return s
+
+
+def fit_key_profiles(chroma, key_id, weight=None):
+    """Key profiles from labelled chroma -> (2, 12) float64, rows minor and major, tonic first, each summing to 1: what
+    ``profile_emissions(profiles=...)`` takes.
+
+    ``chroma`` (..., 12) and ``key_id`` (...) in ``KEY_NAMES`` order, ``weight`` (...) or None (all 1).  Every row is divided by its sum
+    and rolled so that its labelled tonic sits at index 0; a mode's profile is the weighted mean of its rows, divided by its sum.  Rows
+    with ``key_id < 0`` or zero weight count for nothing; a mode without rows is a ``ValueError``.  Ordinary torch ops in float64 on the
+    inputs' device (24 numbers: no kernel)."""
+    x = torch.as_tensor(chroma).detach().to(torch.float64).reshape(-1, 12)
+    k = torch.as_tensor(key_id).detach().to(device=x.device, dtype=torch.int64).reshape(-1)
+    w = torch.ones_like(k, dtype=torch.float64) if weight is None else torch.as_tensor(weight).detach().to(device=x.device, dtype=torch.float64).reshape(-1)
+    if k.shape[0] != x.shape[0] or w.shape[0] != x.shape[0]:
+        raise ValueError("fit_key_profiles: chroma (..., 12), key_id (...) and weight (...) must agree in their leading dimensions")
+    w = torch.where((k >= 0) & (k < 24), w, torch.zeros_like(w))
+    total = x.sum(dim=1)
+    counted = w != 0
+    x = torch.where(counted[:, None], x / torch.where(counted, total, torch.ones_like(total))[:, None], torch.zeros_like(x))
+    tonic = k.clamp(0, 23) % 12
+    rolled = x.gather(1, (torch.arange(12, device=x.device)[None, :] + tonic[:, None]) % 12)  # rolled[i] = x[(i + tonic) % 12]
+    out = []
+    for mode in (0, 1):
+        wm = torch.where(k.clamp(0, 23) // 12 == mode, w, torch.zeros_like(w))
+        if not bool((wm != 0).any()):
+            raise ValueError(f"fit_key_profiles: no {'major' if mode else 'minor'} row carries weight")
+        p = (rolled * wm[:, None]).sum(dim=0) / wm.sum()
+        out.append(p / p.sum())
+    return torch.stack(out)

@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from . import _lib, metrics, tuning as _tuning
+from . import _lib, keyprofile as _keyprofile, metrics, tuning as _tuning
 from .audio import get_resampler, pcm16_rows
 from .cqt import WHOLE_SONG_FRAMES, CQTPlan, get_any_hop_plan, hop_for, hop_for_window
 from .models import PitchClassNet
@@ -144,7 +144,13 @@ class KeyTrack:
     ``track(tuning=...)`` adds ``tuning_cents`` (R,) float32, the detuning every recording was retuned by, and with ``tuning="auto"``
     ``tuning_strength`` (R,), how clearly it was measured (``metrics.estimate_tuning``); both are None on a plain track.  Such a track
     was made from audio whose time axis is stretched by ``rho_i = 2 ** (cents_i / 1200)``: ``times`` and the geometry are the
-    retuned audio's, ``segments`` and ``score`` translate to and from the recording's own time."""
+    retuned audio's, ``segments`` and ``score`` translate to and from the recording's own time.
+
+    ``track(method="profile")`` fills the same fields without a net (``metrics.profile_emissions``): ``key`` is every window's
+    sum-normalised chroma, ``emissions`` (always there) ``sharpness`` times the 24 profile correlations, ``tonic[..., t]`` the larger of
+    ``emissions[..., t]`` and ``emissions[..., 12 + t]``, ``genre`` None, ``key_id`` the best-correlated key and ``confidence`` its
+    correlation, ``tonic_id = key_id % 12`` and ``sig`` the first ``KEY_SIGNATURE_MAP`` row of the key's scale; a silent window holds -1
+    in the three labels and zeros elsewhere."""
     key: torch.Tensor
     tonic: torch.Tensor
     genre: torch.Tensor | None
@@ -279,26 +285,46 @@ class KeyEstimator:
     whose estimate is weaker keep their audio (0 cents), decided on the device.  The retuned batch is always ragged, in a buffer of
     ``ake_retune_out_len(n)`` columns (the widest a row can get), so nothing waits for the device; ``lengths``, ``rate``, ``channel``,
     int16 audio, ``streams`` > 1, ``wrap_mode="true_end"`` and ``frames=0`` work as without it.  The resampler discards content above
-    0.94 of the Nyquist frequency: an estimator whose transform reaches that far refuses ``tuning`` with a ``ValueError``."""
+    0.94 of the Nyquist frequency: an estimator whose transform reaches that far refuses ``tuning`` with a ``ValueError``.
 
-    def __init__(self, net: PitchClassNet, sample_rate: int = 22050, frames: int = 5, streams: int = 1, wrap_mode: str = "dataset_max",
-                 q_mode: int = 0, window_size: int = WHOLE_SONG_FRAMES):
+    ``KeyEstimator(None, device=..., pitches=288)``: an estimator without a net, for the calls that need none --
+    ``track(method="profile")``, ``profile_key`` and ``fit_key_profiles`` (and ``estimate_tuning``).  ``__call__``,
+    ``track(method="net")`` and ``training_windows`` raise a ``ValueError`` on it.  With a net, ``device`` and ``pitches`` are the net's
+    and must be left at None."""
+
+    def __init__(self, net: PitchClassNet | None, sample_rate: int = 22050, frames: int = 5, streams: int = 1, wrap_mode: str = "dataset_max",
+                 q_mode: int = 0, window_size: int = WHOLE_SONG_FRAMES, device=None, pitches: int | None = None):
         if wrap_mode not in ("dataset_max", "true_end"):
             raise ValueError("wrap_mode must be 'dataset_max' or 'true_end'")
         if frames <= 0 and wrap_mode == "true_end":
             raise ValueError("wrap_mode 'true_end' has no meaning with frames=0 (every clip is zero-padded to the same width)")
-        self.net = net.eval()
-        self.device = net._device()
+        if net is None:
+            if not torch.cuda.is_available():
+                raise _lib.AkeError("KeyEstimator needs a HIP device; there is no CPU fallback")
+            self.net = None
+            self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+            pitches = 288 if pitches is None else int(pitches)
+        else:
+            if device is not None or pitches is not None:
+                raise ValueError("KeyEstimator: device and pitches are the net's; give them only with net=None")
+            self.net = net.eval()
+            self.device = net._device()
+            pitches = net.pitches
         self.sample_rate, self.wrap_mode = int(sample_rate), wrap_mode
         self.frames, self.window_size = int(frames), int(window_size)
         if self.frames <= 0:
-            self.plan = get_any_hop_plan(sample_rate, net.pitches, 36, device=self.device, q_mode=q_mode)
+            self.plan = get_any_hop_plan(sample_rate, pitches, 36, device=self.device, q_mode=q_mode)
         else:
-            self.plan = CQTPlan(sample_rate, hop_for(sample_rate, frames), net.pitches, 36, q_mode=q_mode, device=self.device)   # q_mode: ake_amd.cqt.get_plan
+            self.plan = CQTPlan(sample_rate, hop_for(sample_rate, frames), pitches, 36, q_mode=q_mode, device=self.device)   # q_mode: ake_amd.cqt.get_plan
         self.streams = max(1, int(streams))
         self._slots = [{"ws": None, "stream": None} for _ in range(self.streams)]
         self._turn = 0
         self._transitions = {}                                       # track(smooth=True): log transition matrices on the device
+
+    def _need_net(self, what):
+        if self.net is None:
+            raise ValueError(f"{what} runs the net, and this estimator was built without one (KeyEstimator(None, ...)): it serves "
+                             'track(method="profile"), profile_key and fit_key_profiles')
 
     def join(self):
         """Make the caller's current stream wait for every call issued so far (``streams`` > 1; a no-op otherwise)."""
@@ -324,6 +350,7 @@ class KeyEstimator:
         ``rate``: sample rate of ``audio`` when it is not the estimator's -- it is resampled on the device first
         (``scipy.signal.resample_poly``'s filter; with ``frames=0`` each clip's hop is then taken from its resampled length); ``channel``: which channel of (B, C, n) audio to take (0 = the reference's
         ``waveform[0]``, KeyDataset.py:480) or -1 for the mean of all.  ``tuning``, ``min_strength``: see the class."""
+        self._need_net("KeyEstimator.__call__")
         self.net._sync_weights(self.device, for_eval=True)
         if audio.dim() == 3 or (rate is not None and int(rate) != self.sample_rate):
             rs = get_resampler(self.sample_rate if rate is None else int(rate), self.sample_rate, self.device)
@@ -430,7 +457,8 @@ class KeyEstimator:
     def track(self, audio: torch.Tensor, lengths: torch.Tensor | None = None, rate: int | None = None, channel: int = 0,
               window_seconds: float = 15.0, stride_seconds: float = 5.0, smooth: bool = False, mean_key_seconds: float = 60.0,
               transition: torch.Tensor | None = None, signature_weight: float = 1.0, posteriors: bool = False,
-              tuning=None, min_strength: float = 0.0) -> KeyTrack:
+              tuning=None, min_strength: float = 0.0, method: str = "net", profiles="krumhansl", compression: str = "log",
+              profile_sharpness: float = 10.0) -> KeyTrack:
         """The key of long recordings over time: audio (R, n) or (R, C, n) float32 on the GPU -> ``KeyTrack``.  int16 audio is 16-bit
         PCM, as in ``__call__``.
 
@@ -463,9 +491,24 @@ class KeyEstimator:
 
         ``tuning``, ``min_strength``: see the class.  The track is then that of the retuned audio -- its ``times`` and geometry are the
         retuned time axis -- and carries ``tuning_cents`` (and ``tuning_strength`` with "auto"), by which ``KeyTrack.segments`` and
-        ``KeyTrack.score`` translate to and from the recording's own time."""
+        ``KeyTrack.score`` translate to and from the recording's own time.
+
+        ``method``: ``"net"`` (default) is all of the above.  ``"profile"`` needs no net: the same one transform per recording, then
+        ``ake_amd.profile_emissions`` on the same windows (two launches, no net launch) with ``profiles`` (a name of
+        ``metrics.KEY_PROFILES`` or a (2, 12) tensor, as ``fit_key_profiles`` returns it), ``compression`` and ``profile_sharpness``; what
+        the ``KeyTrack`` then holds is in its docstring.  ``emissions`` is always filled; ``smooth`` and ``posteriors`` append the same
+        Viterbi and forward-backward launches to it.  ``signature_weight`` has no meaning there and must be left at 1.  ``lengths``,
+        ``rate``, ``channel``, int16 audio, ``tuning`` and ``streams`` > 1 work as with the net; ``frames=0`` estimators and ``--local``
+        nets are refused.  ``profile_sharpness = 10`` and ``compression = "log"`` are unmeasured starting values
+        (``profiles/key_profiles.md``)."""
         if posteriors and not smooth:
             raise ValueError("track(posteriors=True) needs smooth=True: the posteriors belong to the smoothed track's emissions and transition")
+        if method == "profile":
+            return self._track_profile(audio, lengths, rate, channel, window_seconds, stride_seconds, smooth, mean_key_seconds, transition,
+                                       signature_weight, posteriors, tuning, min_strength, profiles, compression, profile_sharpness)
+        if method != "net":
+            raise ValueError('track: method must be "net" or "profile"')
+        self._need_net('KeyEstimator.track(method="net")')
         self._refuse_untrackable()
         self.net._sync_weights(self.device, for_eval=True)
         if audio.dim() == 3 or (rate is not None and int(rate) != self.sample_rate):
@@ -516,6 +559,7 @@ class KeyEstimator:
         another number of recordings or another sample rate, and recordings none of which holds one window.  The lengths are read on
         the host once, here; iterating the result waits for nothing."""
         from .windows import TrackWindows
+        self._need_net("KeyEstimator.training_windows")
         self._refuse_untrackable()
         if annotations.sample_rate and annotations.sample_rate != self.sample_rate:
             raise ValueError(f"training_windows: the annotations are in samples at {annotations.sample_rate} Hz, the estimator runs at {self.sample_rate} Hz")
@@ -589,15 +633,7 @@ class KeyEstimator:
         if nbytes == 0:
             _lib.check(-1, "ake_pipeline_track_workspace_bytes")
         if smoothing is not None:                                    # the back-pointers: after the track on the same stream, so in its workspace
-            vbytes = L.ake_viterbi_keys_workspace_bytes(R, W)
-            if vbytes == 0:
-                _lib.check(-1, "ake_viterbi_keys_workspace_bytes")
-            nbytes = max(int(nbytes), int(vbytes))
-            if smoothing[2]:                                         # a, b of the forward-backward pass: after the Viterbi, in the same place
-                pbytes = L.ake_key_posteriors_workspace_bytes(R, W)
-                if pbytes == 0:
-                    _lib.check(-1, "ake_key_posteriors_workspace_bytes")
-                nbytes = max(nbytes, int(pbytes))
+            nbytes = max(int(nbytes), self._smooth_workspace_bytes(R, W, smoothing[2]))
         if slot["ws"] is None or slot["ws"].numel() < nbytes:
             slot["ws"] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
         ws = slot["ws"]
@@ -624,14 +660,206 @@ class KeyEstimator:
                 stream = torch.cuda.current_stream().cuda_stream
                 _lib.check(L.ake_key_emissions_f32(key.data_ptr(), tonic.data_ptr(), R * W, counts.data_ptr(), W, weight,
                                                    track.emissions.data_ptr(), stream), "ake_key_emissions_f32")
-                _lib.check(L.ake_viterbi_keys_f32(track.emissions.data_ptr(), R, W, counts.data_ptr(), trans.data_ptr(), None,
-                                                  track.smooth_key_id.data_ptr(), ws.data_ptr(), ws.numel(), stream), "ake_viterbi_keys_f32")
-                if with_posteriors:
-                    _lib.check(L.ake_key_posteriors_f32(track.emissions.data_ptr(), R, W, counts.data_ptr(), trans.data_ptr(), None,
-                                                        track.smooth_key_id.data_ptr(), track.posteriors.data_ptr(),
-                                                        track.log_likelihood.data_ptr(), None, track.smooth_confidence.data_ptr(),
-                                                        ws.data_ptr(), ws.numel(), stream), "ake_key_posteriors_f32")
+                self._smooth(track, trans, with_posteriors, ws, stream)
         return track
+
+    @staticmethod
+    def _smooth_workspace_bytes(R, W, with_posteriors):
+        """Workspace of ``_smooth``: the Viterbi's back-pointers, then (same stream, after it, in the same place) a, b of the
+        forward-backward pass."""
+        L = _lib.lib()
+        nbytes = L.ake_viterbi_keys_workspace_bytes(R, W)
+        if nbytes == 0:
+            _lib.check(-1, "ake_viterbi_keys_workspace_bytes")
+        if with_posteriors:
+            pbytes = L.ake_key_posteriors_workspace_bytes(R, W)
+            if pbytes == 0:
+                _lib.check(-1, "ake_key_posteriors_workspace_bytes")
+            nbytes = max(int(nbytes), int(pbytes))
+        return int(nbytes)
+
+    @staticmethod
+    def _smooth(track, trans, with_posteriors, ws, stream):
+        """The Viterbi decode of ``track.emissions`` and, with ``with_posteriors``, the forward-backward pass over them, on ``stream``
+        (the current device is the track's)."""
+        L = _lib.lib()
+        R, W = track.key_id.shape
+        counts = track.counts
+        _lib.check(L.ake_viterbi_keys_f32(track.emissions.data_ptr(), R, W, counts.data_ptr(), trans.data_ptr(), None,
+                                          track.smooth_key_id.data_ptr(), ws.data_ptr(), ws.numel(), stream), "ake_viterbi_keys_f32")
+        if with_posteriors:
+            _lib.check(L.ake_key_posteriors_f32(track.emissions.data_ptr(), R, W, counts.data_ptr(), trans.data_ptr(), None,
+                                                track.smooth_key_id.data_ptr(), track.posteriors.data_ptr(),
+                                                track.log_likelihood.data_ptr(), None, track.smooth_confidence.data_ptr(),
+                                                ws.data_ptr(), ws.numel(), stream), "ake_key_posteriors_f32")
+
+    # ---- the profile method: key tracks without a net (csrc/profile.hip) ----
+
+    def _refuse_unprofilable(self, what):
+        if self.frames <= 0:
+            raise ValueError(f"{what} needs a fixed frame rate: this estimator was built with frames=0 (whole-song mode)")
+        if self.net is not None and getattr(self.net, "local", False):
+            raise ValueError(f"{what}: the profile method is not offered on an estimator of a --local net; build one with KeyEstimator(None, ...)")
+
+    def _resampled(self, audio, lengths, rate, channel):
+        if audio.dim() == 3 or (rate is not None and int(rate) != self.sample_rate):
+            rs = get_resampler(self.sample_rate if rate is None else int(rate), self.sample_rate, self.device)
+            audio, len_out = rs(audio, channel=channel, lengths=lengths)
+            lengths = len_out if lengths is not None else None
+        return audio, lengths
+
+    def _track_profile(self, audio, lengths, rate, channel, window_seconds, stride_seconds, smooth, mean_key_seconds, transition,
+                       signature_weight, posteriors, tuning, min_strength, profiles, compression, sharpness):
+        self._refuse_unprofilable('track(method="profile")')
+        if float(signature_weight) != 1.0:
+            raise ValueError('track(method="profile"): signature_weight weighs the net\'s key head, which this method does not run; leave it at 1')
+        mode = metrics._profile_compression(compression)
+        sharpness = float(sharpness)
+        if not sharpness > 0.0:
+            raise ValueError('track(method="profile"): profile_sharpness must be positive')
+        prof = _keyprofile.device_profiles(profiles, self.device)    # (made on the caller's stream, which every side stream waits for)
+        audio, lengths = self._resampled(audio, lengths, rate, channel)
+        wf = track_window_frames(int(round(window_seconds * self.sample_rate)), self.plan.hop_length)
+        sf = track_stride_frames(stride_seconds, self.frames)
+        smoothing = (self._transition(sf, mean_key_seconds, transition), bool(posteriors)) if smooth else None
+        cents = None if tuning is None else self._given_tuning(tuning, audio.shape[0])
+
+        def run(slot, a, l):
+            used = strength = None
+            if self.streams > 1:                                     # (a user's table is a fresh tensor of the caller's stream)
+                prof.record_stream(torch.cuda.current_stream(self.device))
+            if tuning is not None:
+                a, l, used, strength = self._retuned(slot, a, l, cents, min_strength)
+            track = self._run_profile_track(slot, a, l, wf, sf, smoothing, prof, mode, sharpness)
+            track.tuning_cents, track.tuning_strength = used, strength
+            return track
+        return self._issue(run, audio, lengths)
+
+    def _profile_logmag(self, slot, audio, lengths, more_bytes=0):
+        """One transform at the estimator's plan in the slot's workspace (sized for ``ake_profile_emissions_f32`` and ``more_bytes`` too:
+        they run behind it on the same stream) -> ``(mel (R, P, T), frame counts int32 (R,) or None, workspace)``."""
+        L = _lib.lib()
+        if audio.dtype != torch.int16:
+            audio = audio.to(device=self.device, dtype=torch.float32)
+        R, n = audio.shape
+        T = self.plan.num_frames(n)
+        pbytes = int(L.ake_profile_workspace_bytes(R, T))
+        if pbytes == 0:
+            _lib.check(-1, "ake_profile_workspace_bytes")
+        ws = self._slot_ws(slot, max(int(L.ake_cqt_workspace_bytes(self.plan.handle, R, n)), pbytes, int(more_bytes)))
+        frames = None
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths).to(device=self.device, dtype=torch.int64).contiguous()
+            frames = (1 + lengths.clamp(0, n) // self.plan.hop_length).clamp(max=T).to(torch.int32)
+        return self.plan.logmag(audio, lengths=lengths, workspace=ws), frames, ws
+
+    _sig_tables = {}
+
+    @classmethod
+    def _key_sig_table(cls, device):
+        """int32 (24,) on ``device``: for every key of ``KEY_NAMES`` the first ``KEY_SIGNATURE_MAP`` row that carries its scale."""
+        key = str(device)
+        if key not in cls._sig_tables:
+            rows = metrics.MAJOR_TONIC.tolist()
+            cls._sig_tables[key] = torch.tensor([rows.index(m) for m in metrics.KEY_MAJOR_TONIC], dtype=torch.int32, device=device)
+        return cls._sig_tables[key]
+
+    def _run_profile_track(self, slot, audio, lengths, wf, sf, smoothing, prof, mode, sharpness):
+        dev = self.device
+        R, n = audio.shape
+        hop = self.plan.hop_length
+        W = track_counts(1 + n // hop, wf, sf)
+        times = (torch.arange(W, dtype=torch.float64) * sf + (wf - 1) / 2) * hop / self.sample_rate
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        if W == 0:                                                   # every recording is shorter than one window
+            track = KeyTrack(f32(R, 0, 12), f32(R, 0, 12), None, i32(R, 0), i32(R, 0), i32(R, 0), f32(R, 0), i32(R).zero_(), times,
+                             wf * hop / self.sample_rate, sf * hop / self.sample_rate, emissions=f32(R, 0, 24))
+        else:
+            sbytes = 0 if smoothing is None else self._smooth_workspace_bytes(R, W, smoothing[1])
+            mel, frames, ws = self._profile_logmag(slot, audio, lengths, sbytes)
+            chroma, emissions, key_id, conf = _keyprofile._launch(mel, False, frames, wf, sf, W, prof, mode, sharpness, ws)
+            counts = torch.full((R,), W, dtype=torch.int32, device=dev) if frames is None else \
+                track_counts(frames.to(torch.int64), wf, sf).to(torch.int32)
+            tonic = torch.maximum(emissions[..., :12], emissions[..., 12:])
+            undecided = key_id < 0
+            minus = torch.full_like(key_id, -1)
+            tonic_id = torch.where(undecided, minus, key_id % 12)
+            sig = torch.where(undecided, minus, self._key_sig_table(dev)[key_id.clamp_min(0).to(torch.int64)])
+            track = KeyTrack(chroma, tonic, None, key_id, sig, tonic_id, conf, counts, times, wf * hop / self.sample_rate,
+                             sf * hop / self.sample_rate, emissions=emissions)
+        track.hop, track.window_frames, track.stride_frames, track.sample_rate = int(hop), int(wf), int(sf), self.sample_rate
+        if smoothing is not None:
+            track.smooth_key_id = i32(R, W)
+            if smoothing[1]:
+                track.posteriors, track.smooth_confidence, track.log_likelihood = f32(R, W, 24), f32(R, W), f32(R)
+            if W == 0:
+                if track.log_likelihood is not None:
+                    track.log_likelihood.zero_()
+            else:
+                with torch.cuda.device(dev):
+                    self._smooth(track, smoothing[0], smoothing[1], ws, torch.cuda.current_stream().cuda_stream)
+        return track
+
+    @torch.no_grad()
+    def profile_key(self, audio: torch.Tensor, lengths: torch.Tensor | None = None, rate: int | None = None, channel: int = 0,
+                    tuning=None, min_strength: float = 0.0, profiles="krumhansl", compression: str = "log", sharpness: float = 10.0):
+        """One key per clip without a net -> ``(key_id int32 (B,), confidence (B,), chroma (B, 12), emissions (B, 24))`` on the device:
+        one transform at the estimator's plan, then ``ake_amd.profile_emissions`` in its whole-clip mode (``window_frames=0``: every
+        clip's chroma over its own ``1 + lengths[i] // hop`` frames; ``metrics.profile_emissions`` is the definition).  ``audio``,
+        ``lengths``, ``rate``, ``channel``, ``tuning``, ``min_strength``, ``streams`` > 1 and ``join()`` as in ``__call__``; ``profiles``,
+        ``compression`` and ``sharpness`` as in ``ake_amd.profile_emissions``.  ``key_id`` is -1 for a silent clip.  Refused with a
+        ``ValueError`` on ``frames=0`` estimators."""
+        self._refuse_unprofilable("profile_key")
+        mode = metrics._profile_compression(compression)
+        sharpness = float(sharpness)
+        if not sharpness > 0.0:
+            raise ValueError("profile_key: sharpness must be positive")
+        prof = _keyprofile.device_profiles(profiles, self.device)
+        audio, lengths = self._resampled(audio, lengths, rate, channel)
+        cents = None if tuning is None else self._given_tuning(tuning, audio.shape[0])
+
+        def run(slot, a, l):
+            if self.streams > 1:
+                prof.record_stream(torch.cuda.current_stream(self.device))
+            if tuning is not None:
+                a, l = self._retuned(slot, a, l, cents, min_strength)[:2]
+            mel, frames, ws = self._profile_logmag(slot, a, l)
+            chroma, emissions, key_id, conf = _keyprofile._launch(mel, False, frames, 0, 1, 1, prof, mode, sharpness, ws)
+            return key_id[:, 0], conf[:, 0], chroma[:, 0], emissions[:, 0]
+        return self._issue(run, audio, lengths)
+
+    @torch.no_grad()
+    def fit_key_profiles(self, audio: torch.Tensor, annotations: KeyAnnotations, lengths: torch.Tensor | None = None,
+                         window_seconds: float = 15.0, stride_seconds: float = 5.0, compression: str = "log", min_purity: float = 0.0):
+        """Key profiles fitted to annotated recordings -> (2, 12) float64 on the device, rows minor and major, tonic first, which goes
+        straight into ``profiles=`` of ``track(method="profile")``, ``profile_key`` and ``ake_amd.profile_emissions``.
+
+        The windows are ``track``'s grid (``window_seconds``, ``stride_seconds``) and their chroma comes from the kernel
+        (``ake_amd.profile_emissions`` with ``compression``); every window's label and weight come from ``metrics.window_labels`` (the key
+        at its centre, weighted by its purity; 0 below ``min_purity`` and for unlabelled windows); ``metrics.fit_key_profiles`` then takes
+        the weighted mean per mode.  Silent windows count for nothing.  ``audio`` (R, n) float32 or int16 at the estimator's rate;
+        ``annotations`` in samples at that rate.  ``ValueError``: annotations of another number of recordings or another rate, no
+        recording as long as one window, or a mode without a labelled window.  Runs on the current stream."""
+        self._refuse_unprofilable("fit_key_profiles")
+        if annotations.sample_rate and annotations.sample_rate != self.sample_rate:
+            raise ValueError(f"fit_key_profiles: the annotations are in samples at {annotations.sample_rate} Hz, the estimator runs at {self.sample_rate} Hz")
+        if audio.dim() != 2 or annotations.seg_start.shape[0] != audio.shape[0]:
+            raise ValueError(f"fit_key_profiles: audio must be (R, n) with one row per annotated recording ({annotations.seg_start.shape[0]})")
+        hop = self.plan.hop_length
+        wf = track_window_frames(int(round(window_seconds * self.sample_rate)), hop)
+        sf = track_stride_frames(stride_seconds, self.frames)
+        mel, frames, ws = self._profile_logmag({"ws": None}, audio, lengths)                 # a workspace of its own: no side stream's
+        R, W = mel.shape[0], track_counts(mel.shape[2], wf, sf)
+        if W == 0:
+            raise ValueError("fit_key_profiles: no recording is as long as one window")
+        chroma, _, key_id, _ = _keyprofile.profile_emissions(mel, wf, sf, frames, compression=compression, workspace=ws)
+        dev = self.device
+        lab = metrics.window_labels(annotations.seg_start.to(dev), annotations.seg_key.to(dev), annotations.seg_count.to(dev),
+                                    torch.arange(R, device=dev).repeat_interleave(W), torch.arange(W, device=dev).repeat(R) * sf, hop, wf,
+                                    min_purity=min_purity)
+        weight = torch.where(key_id.reshape(-1) >= 0, lab["sample_weight"], torch.zeros_like(lab["sample_weight"]))
+        return metrics.fit_key_profiles(chroma.reshape(-1, 12), lab["truth"], weight)
 
     def _run_wrapped(self, slot, audio, lengths):
         """wrap_mode "true_end": one unpadded call per distinct frame count (the clips of a group share T, so no frame is padding)."""

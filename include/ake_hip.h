@@ -646,6 +646,41 @@ int ake_retune_pcm16_f32(const int16_t* in_dev, int batch, int64_t n_max, int64_
                          const float* cents_dev, float* out_dev, int64_t out_stride, int64_t* lengths_out_dev, ake_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Key-profile emissions: a key track without a trained net (Krumhansl-Schmuckler).  Not in the reference.  Opt-in: nothing else in this
+ * library calls it.  Host model: metrics.profile_emissions.
+ * ---------------------------------------------------------------------------------------- */
+/* mel_dev, frames_major and counts_dev (frames of every recording, clamped to 0..frames; nullable) as in ake_tuning_estimate_f32: a
+ * log-CQT L with 3 bins per semitone from C, in-tune notes on the bins k = 0 (mod 3).  Bin k belongs to semitone (k + 1) / 3 and pitch
+ * class ((k + 1) / 3) % 12; semitone 0 lacks its flat-side bin and the top bin is the flat side of a semitone above the range, both kept
+ * as they come.  pitches that are no multiple of 3: AKE_ERR_UNSUPPORTED.  compression: 0 v = L, 1 v = expm1(L), 2 v = expm1(L)^2;
+ * anything else AKE_ERR_INVALID.
+ *   c[r][t][j] = sum of v[r][k][t] over the bins k of pitch class j, in ascending k
+ *   x[r][w][j] = sum of c[r][t][j] over t = w * stride_frames .. w * stride_frames + window_frames - 1, in ascending t
+ * Recording r with n_r frames has (n_r - window_frames) / stride_frames + 1 windows (0 if n_r < window_frames); windows must equal
+ * ake_profile_windows(frames, window_frames, stride_frames), that count for n_r = frames (AKE_ERR_INVALID otherwise; -1 from
+ * ake_profile_windows for frames < 1, window_frames < 0 or stride_frames < 1, which the entry refuses likewise).  window_frames == 0 is
+ * the whole-clip mode: windows == 1, one window over the recording's own n_r frames, none for n_r == 0.
+ * profiles_dev is float32 [2][12], rows minor and major, tonic first, finite and not constant within a row (the caller's contract; a
+ * constant row scores 0 everywhere).  Key k (0..11 minor, 12..23 major, tonic k % 12) has the profile q_k[j] = row[(j - tonic) % 12];
+ * r_k is the Pearson correlation of x and q_k over the 12 pitch classes, in double, every sum in ascending j with the means taken
+ * first; the rows' means and centred norms are computed once per block.
+ *   emissions_out [recordings][windows][24] = sharpness * r_k   (sharpness NaN or <= 0: AKE_ERR_INVALID)
+ *   key_id_out    [recordings][windows]     = the smallest k that attains the maximum r_k, decided on the double values
+ *   confidence_out[recordings][windows]     = that r_k
+ *   chroma_out    [recordings][windows][12] = x / sum_j x_j
+ * A window with sum_j (x_j - mean)^2 <= 1e-12 * 12 * mean^2 (all-zero chroma included) is silent: zeros, and -1 in key_id_out.  Windows
+ * at or behind a recording's count get the same.  Every output element is written.
+ * Two launches: blocks of (64 frames, one recording) write c in double into the workspace (expm1 in double; zeros for frames at or
+ * behind n_r, so what the workspace held never matters), then one block per (window, recording) adds its frames and scores them.  No
+ * floating-point atomics: two runs on the same input are bit-identical.  The workspace (8-byte aligned) holds c. */
+size_t ake_profile_workspace_bytes(int recordings, int frames);
+int ake_profile_windows(int frames, int window_frames, int stride_frames);
+int ake_profile_emissions_f32(const float* mel_dev, int frames_major, int recordings, int pitches, int frames, const int32_t* counts_dev,
+                              int window_frames, int stride_frames, int windows, const float* profiles_dev /* [2][12] */, int compression,
+                              float sharpness, float* chroma_out, float* emissions_out, int32_t* key_id_out, float* confidence_out,
+                              void* workspace, size_t workspace_bytes, ake_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel timing with hipEvents recorded on the launch stream (bench.py roofline leg).
  * ---------------------------------------------------------------------------------------- */
 int ake_prof_enable(const char* name_filter /* substring, NULL or "" = all */, int on);
