@@ -19,6 +19,7 @@ from .keyprofile import fit_key_profiles, profile_emissions  # noqa: F401
 from .synth import synth_partials  # noqa: F401
 from .tuning import estimate_tuning, retune, retune_out_len  # noqa: F401
 from .windows import TrackWindows, draw_windows, window_batch  # noqa: F401
+from .sequence import key_sequence_loss  # noqa: F401
 from .feeder import HostFeeder  # noqa: F401
 
 __all__ = ["PitchClassNet", "KeyDataset", "DatasetLoader", "SyntheticSineMixLoader", "WaveformLoader", "CQTPlan",
@@ -27,4 +28,4 @@ __all__ = ["PitchClassNet", "KeyDataset", "DatasetLoader", "SyntheticSineMixLoad
            "prepare_audio", "pcm16_to_float", "HostFeeder", "KeyAnnotations", "TrackScore", "track_score", "window_truth",
            "transition_from_labels", "synth_partials", "TrackWindows", "draw_windows", "window_batch", "window_labels", "weighted_general_step",
            "estimate_tuning", "retune", "retune_out_len", "retune_reference",
-           "profile_emissions", "fit_key_profiles", "KEY_PROFILES"]
+           "profile_emissions", "fit_key_profiles", "KEY_PROFILES", "key_sequence_loss"]

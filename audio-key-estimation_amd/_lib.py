@@ -100,6 +100,8 @@ SYMBOLS = {
     "ake_key_posteriors_workspace_bytes": (_SZ, [_I, _I]),
     "ake_key_posteriors_chunk_windows": (_I, []),
     "ake_key_posteriors_f32": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "ake_key_sequence_loss_workspace_bytes": (_SZ, [_I, _I]),
+    "ake_key_sequence_loss_f32": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, C.c_float, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "ake_track_score_i32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "ake_draw_windows_i32": (_I, [_P, _I, C.c_uint64, C.c_uint32, _I64, _I, _P, _P, _P]),
     "ake_window_batch_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, C.c_float, _I, _P, _P, _P, _P, _P, _P, _P]),

@@ -26,10 +26,15 @@
 //
 // Training on annotated recordings assembles its batches from the same cached transform: draw_windows_kernel (window positions from a
 // counter-based generator) and window_batch_kernel (the gather, from a list in device memory, with every window's labels and weight).
+//
+// Training for the smoothed track adds a loss over sequences of consecutive windows (ake_key_sequence_loss_f32): the emission formula and
+// the forward-backward recurrences above, in double, run on the free and on the label-clamped scores side by side, and a gradient kernel
+// per window; below the posterior kernels.
 #include "common.h"
 #include "philox.h"
 
 #include <algorithm>
+#include <cfloat>
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -185,44 +190,55 @@ struct EmisArgs {
     float* emis;               // [rows][24]
 };
 
-// One thread per row, as decode_keys_kernel.  A row is 96 bytes in and 96 out, moved as float4s.  Only 12 distinct signature sums exist
-// (key k's scale is that of its relative major), so 12 are computed and the 24 outputs index them.
+// One row's 24 scores from its 12 memberships and 12 tonic logits (96 bytes in, moved as float4s): the arithmetic of every kernel that
+// needs the emissions, in the precision T it needs them in (float for the tracker, whose bits this is; double for the sequence loss).
+// Only 12 distinct signature sums exist (key k's scale is that of its relative major), so 12 are computed and the 24 outputs index them.
+template <typename T>
+__device__ __forceinline__ void emission_row(const float* key, const float* tonic, size_t r, T scale, T (&e)[kKeys]) {
+    T p[12], t[12];
+    for (int q = 0; q < 3; ++q) {
+        const float4 pv = reinterpret_cast<const float4*>(key + r * 12)[q];
+        const float4 tv = reinterpret_cast<const float4*>(tonic + r * 12)[q];
+        p[4 * q] = pv.x; p[4 * q + 1] = pv.y; p[4 * q + 2] = pv.z; p[4 * q + 3] = pv.w;
+        t[4 * q] = tv.x; t[4 * q + 1] = tv.y; t[4 * q + 2] = tv.z; t[4 * q + 3] = tv.w;
+    }
+    T in[12], outside[12];                                               // the two Bernoulli terms, clamped as nn.BCELoss clamps them
+    for (int j = 0; j < 12; ++j) {
+        in[j] = fmax(log(p[j]), T(-100));                                // (the overloads of T: logf, log1pf, expf, fmaxf for float)
+        outside[j] = fmax(log1p(-p[j]), T(-100));
+    }
+    T tmax = t[0];
+    for (int j = 1; j < 12; ++j) tmax = fmax(tmax, t[j]);
+    T se = T(0);
+    for (int j = 0; j < 12; ++j) se += exp(t[j] - tmax);
+    const T lse = tmax + log(se);
+    T sig[12];                                                           // by major tonic
+    for (int m = 0; m < 12; ++m) {
+        T s = T(0);
+        for (int j = 0; j < 12; ++j) s += (kMajorScale >> ((j - m + 12) % 12)) & 1 ? in[j] : outside[j];
+        sig[m] = s;
+    }
+    for (int k = 0; k < kKeys; ++k) e[k] = (t[k % 12] - lse) + scale * sig[k >= 12 ? k - 12 : (k + 3) % 12];
+}
+
+// window r of a [recordings][windows] layout lies at or behind its recording's count (counts null: never)
+__device__ __forceinline__ bool behind_count(const int* counts, int windows, int r) {
+    if (!counts) return false;
+    const int rec = r / windows;
+    return r - rec * windows >= counts[rec];
+}
+
+// One thread per row, as decode_keys_kernel: 96 bytes in and 96 out, moved as float4s.
 __global__ __launch_bounds__(256) void key_emissions_kernel(EmisArgs a) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= a.rows) return;
     float4* const out = reinterpret_cast<float4*>(a.emis + static_cast<size_t>(r) * kKeys);
-    if (a.counts) {
-        const int rec = r / a.windows;
-        if (r - rec * a.windows >= a.counts[rec]) {
-            for (int q = 0; q < 6; ++q) out[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-            return;
-        }
-    }
-    float p[12], t[12];
-    for (int q = 0; q < 3; ++q) {
-        const float4 pv = reinterpret_cast<const float4*>(a.key + static_cast<size_t>(r) * 12)[q];
-        const float4 tv = reinterpret_cast<const float4*>(a.tonic + static_cast<size_t>(r) * 12)[q];
-        p[4 * q] = pv.x; p[4 * q + 1] = pv.y; p[4 * q + 2] = pv.z; p[4 * q + 3] = pv.w;
-        t[4 * q] = tv.x; t[4 * q + 1] = tv.y; t[4 * q + 2] = tv.z; t[4 * q + 3] = tv.w;
-    }
-    float in[12], outside[12];                                           // the two Bernoulli terms, clamped as nn.BCELoss clamps them
-    for (int j = 0; j < 12; ++j) {
-        in[j] = fmaxf(logf(p[j]), -100.f);
-        outside[j] = fmaxf(log1pf(-p[j]), -100.f);
-    }
-    float tmax = t[0];
-    for (int j = 1; j < 12; ++j) tmax = fmaxf(tmax, t[j]);
-    float se = 0.f;
-    for (int j = 0; j < 12; ++j) se += expf(t[j] - tmax);
-    const float lse = tmax + logf(se);
-    float sig[12];                                                       // by major tonic
-    for (int m = 0; m < 12; ++m) {
-        float s = 0.f;
-        for (int j = 0; j < 12; ++j) s += (kMajorScale >> ((j - m + 12) % 12)) & 1 ? in[j] : outside[j];
-        sig[m] = s;
+    if (behind_count(a.counts, a.windows, r)) {
+        for (int q = 0; q < 6; ++q) out[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
     }
     float e[kKeys];
-    for (int k = 0; k < kKeys; ++k) e[k] = (t[k % 12] - lse) + a.scale * sig[k >= 12 ? k - 12 : (k + 3) % 12];
+    emission_row<float>(a.key, a.tonic, static_cast<size_t>(r), a.scale, e);
     for (int q = 0; q < 6; ++q) out[q] = make_float4(e[4 * q], e[4 * q + 1], e[4 * q + 2], e[4 * q + 3]);
 }
 
@@ -490,7 +506,7 @@ struct PostArgs {
     const int* path;           // [recordings][windows], nullable
     const float* a;            // [recordings][windows][24]
     const float* b;
-    float* post;               // [recordings][windows][24]
+    float* post;               // [recordings][windows][24], nullable: the transition sums alone
     float* path_post;          // [recordings][windows], nullable
     float* xi_part;            // [recordings][chunks][576], nullable: no transition sums
     int windows, chunks;       // chunks = ceil(windows / kPostChunk)
@@ -513,14 +529,13 @@ __device__ __forceinline__ float wave_sum(float x) {                     // (x +
 //     softmax over the wave: one maximum, one sum), and keeps its cells' running sums in registers.  The four waves' sums meet in LDS
 //     and leave as one partial per chunk, added in wave order; key_xi_reduce_kernel adds the chunks in chunk order.  No atomics: the
 //     order of every addition is fixed by the shape alone.
-__global__ __launch_bounds__(256) void key_posteriors_kernel(PostArgs p) {
-    __shared__ float part[4][kCells];
+__device__ __forceinline__ void key_posteriors_block(const PostArgs& p, float (&part)[4][kCells]) {
     const int r = blockIdx.x / p.chunks, chunk = blockIdx.x - r * p.chunks, c0 = chunk * kPostChunk;
     const int W = p.windows, tid = threadIdx.x;
     int n = p.counts ? p.counts[r] : W;
     n = n < 0 ? 0 : n > W ? W : n;
     const size_t row0 = static_cast<size_t>(r) * W;
-    if (tid < kPostChunk && c0 + tid < W) {
+    if (p.post && tid < kPostChunk && c0 + tid < W) {
         const int w = c0 + tid;
         float4* const out = reinterpret_cast<float4*>(p.post + (row0 + w) * kKeys);
         float pp = 0.f;
@@ -593,6 +608,11 @@ __global__ __launch_bounds__(256) void key_posteriors_kernel(PostArgs p) {
     for (int cell = tid; cell < kCells; cell += 256) dst[cell] = ((part[0][cell] + part[1][cell]) + part[2][cell]) + part[3][cell];
 }
 
+__global__ __launch_bounds__(256) void key_posteriors_kernel(PostArgs p) {
+    __shared__ float part[4][kCells];
+    key_posteriors_block(p, part);
+}
+
 // xi_sum[r] = the chunks' partial sums, added in chunk order.
 __global__ __launch_bounds__(192) void key_xi_reduce_kernel(const float* __restrict__ part, float* __restrict__ xi, int chunks) {
     const int r = blockIdx.x;
@@ -600,6 +620,242 @@ __global__ __launch_bounds__(192) void key_xi_reduce_kernel(const float* __restr
         float s = 0.f;
         for (int c = 0; c < chunks; ++c) s += part[(static_cast<size_t>(r) * chunks + c) * kCells + cell];
         xi[static_cast<size_t>(r) * kCells + cell] = s;
+    }
+}
+
+// ---- a sequence loss for training: the conditional log-likelihood of the labelled windows under the tracker's own chain ----
+// (semantics and formulas: include/ake_hip.h; host model: metrics.key_sequence_loss)
+// Everything exists twice, as set 0 (the free emissions e) and set 1 (the clamped ones e~), laid out [set][recordings][windows][...], so
+// that one launch covers both.  Launches: the emissions of both sets; the four chains of every recording side by side; the scalars
+// (one block); the gradient per window; with d_trans two more (the per-chunk transition sums of both sets, then their ordered
+// difference).  No float atomics and no sum whose order depends on anything but the shape.
+// The emissions, the chains and the gradient are in DOUBLE.  The gradient is a difference of two posteriors that are nearly equal
+// wherever the net is already right, and a posterior whose log-odds against its row's largest is L carries, out of float32 log-scores,
+// a relative error of |L| * 2^-24 -- 1e-6 at |L| = 16, the float32 tracker's own (profiles/track_sequence.md has what the float32
+// chains measured).  A training sequence is a handful of windows, so the slower step (48 double exponentials per lane) costs nothing
+// that shows; the transition sums take float32 copies of the same scores through key_posteriors_kernel's own code.
+constexpr double kSequenceClamp = -1e4;   // AKE_SEQUENCE_CLAMP: an off-label key of a labelled window
+
+struct SeqArgs {
+    const float* key;          // [rows][12]
+    const float* tonic;        // [rows][12]
+    const int* labels;         // [rows]; outside 0..23 = unlabelled
+    const int* counts;         // nullable
+    const float* trans;        // [24][24]
+    const float* prior;        // [24], nullable = zeros
+    int rows, windows, recordings;
+    double scale;              // signature_weight / 12
+    double* emis;              // [2][rows][24]
+    double* a;                 // [2][rows][24] (rows behind the count are not written)
+    double* b;
+    float* emis32;             // the same three rounded to float32, for the transition sums
+    float* a32;
+    float* b32;
+    double* loglik;            // [2][recordings]
+    double* inv_n;             // [1]: 1 / N, 0 for N == 0
+    float* scalars;            // [4]
+    float* d_key;              // [rows][12]
+    float* d_tonic;            // [rows][12]
+    float* d_emis;             // [rows][24], nullable
+};
+
+// One thread per row: e by key_emissions_kernel's own arithmetic (emission_row) in double, and e~ beside it.
+__global__ __launch_bounds__(256) void sequence_emissions_kernel(SeqArgs a) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.rows) return;
+    const size_t at = static_cast<size_t>(r) * kKeys, set = static_cast<size_t>(a.rows) * kKeys;
+    double e[kKeys], ec[kKeys];
+    if (behind_count(a.counts, a.windows, r)) {
+        for (int k = 0; k < kKeys; ++k) e[k] = ec[k] = 0.0;
+    } else {
+        emission_row<double>(a.key, a.tonic, static_cast<size_t>(r), a.scale, e);
+        const int label = a.labels[r];
+        const bool labelled = static_cast<unsigned>(label) < static_cast<unsigned>(kKeys);
+        for (int k = 0; k < kKeys; ++k) ec[k] = !labelled || k == label ? e[k] : kSequenceClamp;
+    }
+    for (int k = 0; k < kKeys; ++k) {
+        a.emis[at + k] = e[k]; a.emis[set + at + k] = ec[k];
+        a.emis32[at + k] = static_cast<float>(e[k]); a.emis32[set + at + k] = static_cast<float>(ec[k]);
+    }
+}
+
+// log-sum-exp of 24 doubles about their largest
+__device__ __forceinline__ double lse24(const double (&x)[kKeys]) {
+    double mx = x[0];
+    for (int k = 1; k < kKeys; ++k) mx = fmax(mx, x[k]);
+    double z = 0.0;
+    for (int k = 0; k < kKeys; ++k) z += exp(x[k] - mx);
+    return mx + log(z);
+}
+
+// grid (recordings, 4): blockIdx.y = 2 * set + direction, one wave each, so the four chains of a recording run at the same time.  The
+// recurrences of forward_backward_chain (include/ake_hip.h) in double and in the plainest layout: lane j < 24 holds state j and takes
+// all 24 terms of its log-sum-exp; a step's scores travel through two LDS rows (the scores the recurrence reads, then the raw results
+// the normaliser reads), each written, then read, between two barriers of the one wave.
+__global__ __launch_bounds__(64) void key_sequence_chains_kernel(SeqArgs a) {
+    __shared__ double row_lds[kKeys], raw_lds[kKeys];
+    const int r = blockIdx.x, lane = threadIdx.x, W = a.windows;
+    const bool back = blockIdx.y & 1, own = lane < kKeys;
+    const int j = own ? lane : 0;                                        // (the other lanes run along on state 0 and write nothing)
+    const size_t base = (static_cast<size_t>(blockIdx.y >> 1) * a.recordings + r) * W * kKeys;
+    const double* const e = a.emis + base;
+    double* const out = (back ? a.b : a.a) + base;
+    float* const out32 = (back ? a.b32 : a.a32) + base;
+    int n = a.counts ? a.counts[r] : W;
+    n = n < 0 ? 0 : n > W ? W : n;
+    double A[kKeys];                                                     // forward: column j of the transition; backward: row j
+    for (int i = 0; i < kKeys; ++i) A[i] = back ? a.trans[j * kKeys + i] : a.trans[i * kKeys + j];
+    double d = back ? 0.0 : (a.prior ? static_cast<double>(a.prior[j]) : 0.0), ll = 0.0;
+    for (int t = 0; t < n; ++t) {                                        // n is wave-uniform: every lane meets every barrier
+        const int w = back ? n - 1 - t : t;
+        double raw;
+        if (t == 0) {
+            raw = back ? 0.0 : d + e[static_cast<size_t>(w) * kKeys + j];      // b_{n-1} = 0, a_0 = prior + e[0]
+        } else {
+            if (own) row_lds[lane] = back ? d + e[static_cast<size_t>(w + 1) * kKeys + j] : d;
+            __syncthreads();
+            double x[kKeys];
+            for (int i = 0; i < kKeys; ++i) x[i] = row_lds[i] + A[i];
+            raw = lse24(x);
+            if (!back) raw += e[static_cast<size_t>(w) * kKeys + j];
+        }
+        if (!back || t > 0) {                                            // b_{n-1} stays 0, unnormalised
+            if (own) raw_lds[lane] = raw;
+            __syncthreads();
+            double x[kKeys];
+            for (int i = 0; i < kKeys; ++i) x[i] = raw_lds[i];
+            const double cw = lse24(x);
+            d = raw - cw;
+            ll += cw;
+        } else {
+            d = raw;
+        }
+        if (own) {
+            out[static_cast<size_t>(w) * kKeys + j] = d;
+            out32[static_cast<size_t>(w) * kKeys + j] = static_cast<float>(d);
+        }
+    }
+    if (!back && lane == 0) a.loglik[(blockIdx.y >> 1) * a.recordings + r] = ll;
+}
+
+// One block.  N = the labelled windows below their counts (an integer sum: any order gives the same), then thread 0 adds the chains'
+// doubles in recording order: the loss is the difference of two large, nearly equal sums, so it is taken per recording and in double.
+__global__ __launch_bounds__(256) void sequence_scalars_kernel(SeqArgs a) {
+    __shared__ int s_n;
+    if (threadIdx.x == 0) s_n = 0;
+    __syncthreads();
+    int mine = 0;
+    for (int r = threadIdx.x; r < a.rows; r += blockDim.x)
+        mine += !behind_count(a.counts, a.windows, r) && static_cast<unsigned>(a.labels[r]) < static_cast<unsigned>(kKeys);
+    atomicAdd(&s_n, mine);
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const int N = s_n;
+    double diff = 0.0, ll = 0.0, llc = 0.0;
+    for (int r = 0; r < a.recordings; ++r) {
+        const double x = a.loglik[r], y = a.loglik[a.recordings + r];
+        diff += x - y; ll += x; llc += y;
+    }
+    const double inv = N > 0 ? 1.0 / N : 0.0;
+    a.inv_n[0] = inv;
+    a.scalars[0] = static_cast<float>(diff * inv);
+    a.scalars[1] = static_cast<float>(ll * inv);
+    a.scalars[2] = static_cast<float>(llc * inv);
+    a.scalars[3] = static_cast<float>(N);
+}
+
+// softmax of a row of a + b
+__device__ __forceinline__ void posterior_row(const double* a, const double* b, double (&s)[kKeys]) {
+    for (int k = 0; k < kKeys; ++k) s[k] = a[k] + b[k];
+    double mx = s[0];
+    for (int k = 1; k < kKeys; ++k) mx = fmax(mx, s[k]);
+    double z = 0.0;
+    for (int k = 0; k < kKeys; ++k) { s[k] = exp(s[k] - mx); z += s[k]; }
+    for (int k = 0; k < kKeys; ++k) s[k] = s[k] / z;
+}
+
+// One thread per window: g = (post - post~) / N, then its way back through the emission formula to the two heads' outputs.
+__global__ __launch_bounds__(256) void sequence_grad_kernel(SeqArgs a) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.rows) return;
+    const size_t row = static_cast<size_t>(r);
+    float4* const dk = reinterpret_cast<float4*>(a.d_key + row * 12);
+    float4* const dt = reinterpret_cast<float4*>(a.d_tonic + row * 12);
+    float4* const de = a.d_emis ? reinterpret_cast<float4*>(a.d_emis + row * kKeys) : nullptr;
+    if (behind_count(a.counts, a.windows, r)) {
+        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int q = 0; q < 3; ++q) dk[q] = dt[q] = zero;
+        if (de) for (int q = 0; q < 6; ++q) de[q] = zero;
+        return;
+    }
+    const size_t set = static_cast<size_t>(a.rows) * kKeys;
+    double g[kKeys], pc[kKeys];
+    posterior_row(a.a + row * kKeys, a.b + row * kKeys, g);
+    posterior_row(a.a + set + row * kKeys, a.b + set + row * kKeys, pc);
+    const double inv = a.inv_n[0];
+    double gsum = 0.0;
+    for (int k = 0; k < kKeys; ++k) { g[k] = (g[k] - pc[k]) * inv; gsum += g[k]; }
+    if (de)
+        for (int q = 0; q < 6; ++q)
+            de[q] = make_float4(static_cast<float>(g[4 * q]), static_cast<float>(g[4 * q + 1]), static_cast<float>(g[4 * q + 2]), static_cast<float>(g[4 * q + 3]));
+    float p[12], t[12];
+    for (int q = 0; q < 3; ++q) {
+        const float4 pv = reinterpret_cast<const float4*>(a.key + row * 12)[q];
+        const float4 tv = reinterpret_cast<const float4*>(a.tonic + row * 12)[q];
+        p[4 * q] = pv.x; p[4 * q + 1] = pv.y; p[4 * q + 2] = pv.z; p[4 * q + 3] = pv.w;
+        t[4 * q] = tv.x; t[4 * q + 1] = tv.y; t[4 * q + 2] = tv.z; t[4 * q + 3] = tv.w;
+    }
+    // the tonic head: e[k] holds log_softmax(tonic)[k mod 12]
+    float tmax = t[0];
+    for (int j = 1; j < 12; ++j) tmax = fmaxf(tmax, t[j]);
+    double sm[12], se = 0.0;
+    for (int j = 0; j < 12; ++j) { sm[j] = exp(static_cast<double>(t[j]) - tmax); se += sm[j]; }
+    float out[12];
+    for (int j = 0; j < 12; ++j) out[j] = static_cast<float>((g[j] + g[j + 12]) - (sm[j] / se) * gsum);
+    for (int q = 0; q < 3; ++q) dt[q] = make_float4(out[4 * q], out[4 * q + 1], out[4 * q + 2], out[4 * q + 3]);
+    // the key head: the keys that share a scale share its sum (major m and minor m + 9); pitch class j lies inside the scales whose
+    // major tonic m has bit (j - m) mod 12 of kMajorScale, and outside the others (the two sums are taken apart: they nearly cancel).
+    // The derivative of a clamped or subnormal logarithm is 0: log p > -100 holds for every normal float32, so the comparison with
+    // FLT_MIN decides alone.
+    double G[12];
+    for (int m = 0; m < 12; ++m) G[m] = g[12 + m] + g[(m + 9) % 12];
+    for (int j = 0; j < 12; ++j) {
+        double inside = 0.0, outside = 0.0;
+        for (int m = 0; m < 12; ++m) {
+            if ((kMajorScale >> ((j - m + 12) % 12)) & 1) inside += G[m];
+            else outside += G[m];
+        }
+        const float q = 1.f - p[j];
+        const double u = p[j] >= FLT_MIN ? 1.0 / p[j] : 0.0, v = q >= FLT_MIN ? 1.0 / q : 0.0;
+        out[j] = static_cast<float>(a.scale * (inside * u - outside * v));
+    }
+    for (int q = 0; q < 3; ++q) dk[q] = make_float4(out[4 * q], out[4 * q + 1], out[4 * q + 2], out[4 * q + 3]);
+}
+
+// key_posteriors_kernel's transition sums for both sets: grid (recordings * chunks, 2), blockIdx.y = the set.
+__global__ __launch_bounds__(256) void key_sequence_xi_kernel(PostArgs p, int recordings) {
+    __shared__ float part[4][kCells];
+    const size_t set = blockIdx.y, floats = static_cast<size_t>(recordings) * p.windows * kKeys;
+    p.emis += set * floats; p.a += set * floats; p.b += set * floats;
+    p.xi_part += set * recordings * p.chunks * kCells;
+    key_posteriors_block(p, part);
+}
+
+// d_trans = sum_r (xi_sum[r] - xi~_sum[r]) / N: the chunks in chunk order, the recordings in recording order, in double.
+__global__ __launch_bounds__(192) void sequence_trans_kernel(const float* __restrict__ part, const double* __restrict__ inv_n,
+                                                             float* __restrict__ d_trans, int recordings, int chunks) {
+    const size_t set = static_cast<size_t>(recordings) * chunks * kCells;
+    for (int cell = threadIdx.x; cell < kCells; cell += 192) {
+        double s = 0.0;
+        for (int r = 0; r < recordings; ++r) {
+            double x = 0.0, y = 0.0;
+            for (int c = 0; c < chunks; ++c) {
+                const size_t at = (static_cast<size_t>(r) * chunks + c) * kCells + cell;
+                x += part[at]; y += part[set + at];
+            }
+            s += x - y;
+        }
+        d_trans[cell] = static_cast<float>(s * inv_n[0]);
     }
 }
 
@@ -804,6 +1060,38 @@ bool carve_posteriors(int recordings, int windows, void* ws, PostCarve* pc) {
     pc->b = c.take<float>(rows * kKeys);
     pc->part = c.take<float>(static_cast<size_t>(recordings) * pc->chunks * kCells);
     pc->total = ake::align_up(c.off, 256);
+    return true;
+}
+
+struct SeqCarve {
+    double* emis;              // [2][rows][24]
+    double* a;
+    double* b;
+    float* emis32;             // the same three in float32
+    float* a32;
+    float* b32;
+    double* loglik;            // [2][recordings]
+    double* inv_n;             // [1]
+    float* part;               // [2][recordings][chunks][576]
+    size_t total;
+    int chunks;
+};
+
+bool carve_sequence(int recordings, int windows, void* ws, SeqCarve* sc) {
+    if (recordings <= 0 || windows <= 0 || static_cast<long long>(recordings) * windows > (1ll << 28)) return false;
+    sc->chunks = (windows + kPostChunk - 1) / kPostChunk;
+    const size_t rows = static_cast<size_t>(recordings) * windows;
+    ake::Carver c(ws, 0);
+    sc->emis = c.take<double>(2 * rows * kKeys);
+    sc->a = c.take<double>(2 * rows * kKeys);
+    sc->b = c.take<double>(2 * rows * kKeys);
+    sc->emis32 = c.take<float>(2 * rows * kKeys);
+    sc->a32 = c.take<float>(2 * rows * kKeys);
+    sc->b32 = c.take<float>(2 * rows * kKeys);
+    sc->loglik = c.take<double>(2 * static_cast<size_t>(recordings));
+    sc->inv_n = c.take<double>(1);
+    sc->part = c.take<float>(2 * static_cast<size_t>(recordings) * sc->chunks * kCells);
+    sc->total = ake::align_up(c.off, 256);
     return true;
 }
 
@@ -1036,6 +1324,66 @@ int ake_key_posteriors_f32(const float* emis_dev, int recordings, int windows, c
         hipLaunchKernelGGL(key_xi_reduce_kernel, dim3(recordings), dim3(192), 0, s, pc.part, xi_sum_dev, pc.chunks);
     }
     AKE_HIP_CHECK(hipGetLastError());
+    return AKE_OK;
+}
+
+size_t ake_key_sequence_loss_workspace_bytes(int recordings, int windows) {
+    SeqCarve sc;
+    return carve_sequence(recordings, windows, nullptr, &sc) ? sc.total : 0;
+}
+
+int ake_key_sequence_loss_f32(const float* key_dev, const float* tonic_dev, const int32_t* labels_dev, int recordings, int windows,
+                              const int32_t* counts_dev, const float* log_trans_dev, const float* log_prior_dev, float signature_weight,
+                              float* scalars_dev, float* d_key_dev, float* d_tonic_dev, float* d_trans_dev, float* d_emis_dev, void* workspace,
+                              size_t workspace_bytes, ake_stream_t stream) {
+    AKE_REQUIRE(key_dev && tonic_dev && labels_dev && log_trans_dev && scalars_dev && d_key_dev && d_tonic_dev, AKE_ERR_INVALID,
+                "key_sequence_loss: null argument");
+    SeqCarve sc;
+    AKE_REQUIRE(carve_sequence(recordings, windows, workspace, &sc), AKE_ERR_INVALID, "key_sequence_loss: bad shape (%d recordings, %d windows)",
+                recordings, windows);
+    AKE_REQUIRE(workspace && workspace_bytes >= sc.total, AKE_ERR_WORKSPACE, "key_sequence_loss: workspace %zu < %zu bytes", workspace_bytes, sc.total);
+    AKE_REQUIRE(((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(key_dev) | reinterpret_cast<uintptr_t>(tonic_dev) |
+                  reinterpret_cast<uintptr_t>(d_key_dev) | reinterpret_cast<uintptr_t>(d_tonic_dev) | reinterpret_cast<uintptr_t>(d_emis_dev)) & 15) == 0,
+                AKE_ERR_INVALID, "key_sequence_loss: the workspace, the heads' outputs and their gradients must be 16-byte aligned");
+    AKE_REQUIRE(std::isfinite(signature_weight), AKE_ERR_INVALID, "key_sequence_loss: signature_weight is not finite");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int rows = recordings * windows;
+    SeqArgs a{key_dev, tonic_dev, labels_dev, counts_dev, log_trans_dev, log_prior_dev, rows, windows, recordings,
+              static_cast<double>(signature_weight) / 12.0, sc.emis, sc.a, sc.b, sc.emis32, sc.a32, sc.b32, sc.loglik, sc.inv_n, scalars_dev,
+              d_key_dev, d_tonic_dev, d_emis_dev};
+    {
+        ake::ProfScope ps("sequence_emissions_kernel", s);
+        hipLaunchKernelGGL(sequence_emissions_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, a);
+    }
+    AKE_HIP_CHECK(hipGetLastError());
+    {
+        ake::ProfScope ps("key_sequence_chains_kernel", s);
+        hipLaunchKernelGGL(key_sequence_chains_kernel, dim3(recordings, 4), dim3(64), 0, s, a);
+    }
+    AKE_HIP_CHECK(hipGetLastError());
+    {
+        ake::ProfScope ps("sequence_scalars_kernel", s);
+        hipLaunchKernelGGL(sequence_scalars_kernel, dim3(1), dim3(256), 0, s, a);
+    }
+    AKE_HIP_CHECK(hipGetLastError());
+    {
+        ake::ProfScope ps("sequence_grad_kernel", s);
+        hipLaunchKernelGGL(sequence_grad_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, a);
+    }
+    AKE_HIP_CHECK(hipGetLastError());
+    if (d_trans_dev) {
+        PostArgs pa{sc.emis32, counts_dev, log_trans_dev, nullptr, sc.a32, sc.b32, nullptr, nullptr, sc.part, windows, sc.chunks};
+        {
+            ake::ProfScope ps("key_sequence_xi_kernel", s);
+            hipLaunchKernelGGL(key_sequence_xi_kernel, dim3(recordings * sc.chunks, 2), dim3(256), 0, s, pa, recordings);
+        }
+        AKE_HIP_CHECK(hipGetLastError());
+        {
+            ake::ProfScope ps("sequence_trans_kernel", s);
+            hipLaunchKernelGGL(sequence_trans_kernel, dim3(1), dim3(192), 0, s, sc.part, sc.inv_n, d_trans_dev, recordings, sc.chunks);
+        }
+        AKE_HIP_CHECK(hipGetLastError());
+    }
     return AKE_OK;
 }
 

@@ -661,6 +661,77 @@ def weighted_general_step(key_out, tonic_out, genre_out, key_labels, tonic_label
         return scalars, (d_key, d_tonic, d_genre)
 
 
+# ---- a sequence loss for training: the labelled windows' conditional log-likelihood under the tracker's own chain (ake_key_sequence_loss_f32) ----
+
+SEQUENCE_CLAMP = -1e4                   # AKE_SEQUENCE_CLAMP: the score of an off-label key of a labelled window (finite; exp() of it is 0)
+_FLT_MIN = 1.1754943508222875e-38       # the smallest normal float32
+
+
+def key_sequence_loss(key, tonic, labels, log_trans, counts=None, signature_weight=1.0, log_prior=None):
+    """The sequence loss of (R, W, 12) ``key`` (sigmoid memberships) and ``tonic`` (logits) against ``labels`` (R, W) -> dict:
+    ``ake_key_sequence_loss_f32`` in torch ops, in ``key``'s dtype (float64 inputs give the test model), backward written out.
+
+    A linear-chain CRF whose unary scores are the tracker's own emissions ``e = key_emissions(key, tonic, signature_weight)`` under
+    ``log_trans``, ``log_prior`` and ``counts`` (as ``key_posteriors`` takes them).  A label outside 0..23 is an unlabelled window and is
+    marginalised; a labelled window's other keys are clamped to ``SEQUENCE_CLAMP`` in ``e~``.  With N the labelled windows below their
+    recording's count, over the whole call::
+
+        loss    = (sum_r loglik(e[r]) - sum_r loglik(e~[r])) / N                 (0, with zero gradients, when N == 0)
+        g       = (post - post~) / N                                              (d loss / d e: ``d_emis``)
+        d_trans = sum_r (xi_sum[r] - xi~_sum[r]) / N
+        d_tonic[j] = g[j] + g[j + 12] - softmax(tonic)[j] * sum_k g[k]
+        d_key[j]   = signature_weight / 12 * (sum_k S_k[j] g[k] * u(p_j) - sum_k (1 - S_k[j]) g[k] * v(p_j))
+        u(p) = 1 / p where p >= FLT_MIN and log p > -100, else 0;  v(p) = 1 / (1 - p) where 1 - p >= FLT_MIN and log1p(-p) > -100, else 0
+
+    (``key_posteriors``'s loglik, post and xi_sum; the derivative is 0 where ``nn.BCELoss``'s clamp is active and for subnormal
+    arguments, where autograd would give NaN).  Keys of the dict: ``loss``, ``loglik`` (sum_r loglik / N), ``loglik_clamped``,
+    ``labelled`` (N), ``d_key``, ``d_tonic`` (R, W, 12), ``d_trans`` (24, 24), ``d_emis`` (R, W, 24); the gradients are zeros at and
+    behind the counts.  ``log_prior`` gets no gradient."""
+    if key.dim() != 3 or key.shape[2] != 12 or tonic.shape != key.shape:
+        raise ValueError(f"key_sequence_loss: key and tonic must be (R, W, 12), got {tuple(key.shape)} and {tuple(tonic.shape)}")
+    with torch.no_grad():
+        R, W, _ = key.shape
+        dt, dev = key.dtype, key.device
+        tonic = tonic.to(dt)
+        lab = torch.as_tensor(labels, device=dev).to(torch.int64)
+        if lab.shape != (R, W):
+            raise ValueError(f"key_sequence_loss: labels must be ({R}, {W}), got {tuple(lab.shape)}")
+        live = torch.ones((R, W), dtype=torch.bool, device=dev) if counts is None else ~_behind_count(counts, R, W, dev)
+        labelled = live & (lab >= 0) & (lab < 24)
+        A = torch.as_tensor(log_trans).detach().to(device=dev, dtype=dt)
+        prior = None if log_prior is None else torch.as_tensor(log_prior).detach().to(device=dev, dtype=dt)
+        e = key_emissions(key, tonic, signature_weight, counts)
+        off_label = labelled[..., None] & (torch.arange(24, device=dev)[None, None, :] != lab[..., None])
+        ec = torch.where(off_label, torch.full_like(e, SEQUENCE_CLAMP), e)
+        post, ll, xi = key_posteriors(e, A, prior, counts, transitions=True)
+        postc, llc, xic = key_posteriors(ec, A, prior, counts, transitions=True)
+        n = labelled.sum().to(dt)
+        inv = torch.where(n > 0, 1.0 / n.clamp_min(1.0), torch.zeros_like(n))
+        g = (post - postc) * inv
+        sm = torch.softmax(tonic, dim=-1)
+        d_tonic = g[..., :12] + g[..., 12:] - sm * g.sum(dim=-1, keepdim=True)
+        S = KEY_SCALES.to(device=dev, dtype=dt)
+        zero = torch.zeros((), dtype=dt, device=dev)
+        q = 1.0 - key
+        u = torch.where((key >= _FLT_MIN) & (torch.log(key) > -100.0), 1.0 / key, zero)
+        v = torch.where((q >= _FLT_MIN) & (torch.log1p(-key) > -100.0), 1.0 / q, zero)
+        d_key = (float(signature_weight) / 12.0) * ((g @ S) * u - (g @ (1.0 - S)) * v)
+        d_key = torch.where(live[..., None], d_key, zero)
+        d_tonic = torch.where(live[..., None], d_tonic, zero)
+        return {"loss": (ll - llc).sum() * inv, "loglik": ll.sum() * inv, "loglik_clamped": llc.sum() * inv, "labelled": n,
+                "d_key": d_key, "d_tonic": d_tonic, "d_trans": (xi - xic).sum(dim=0) * inv, "d_emis": g}
+
+
+def sequence_windows(prefix, seed, epoch, first_slot, batch, sequence_windows, stride_frames):
+    """``batch`` sequences of ``sequence_windows`` consecutive windows -> ``(recording, start)``, lists of ``batch * sequence_windows``
+    Python ints ordered ``[sequence][window]``: the host model of ``TrackWindows``' sequence mode.  ``prefix`` is ``window_prefix`` over
+    the span of a whole sequence, ``window_frames + (sequence_windows - 1) * stride_frames``; slot ``first_slot + s`` of ``draw_windows``
+    is the first window of sequence ``s``, and window ``k`` starts ``k * stride_frames`` frames behind it."""
+    K, sf = int(sequence_windows), int(stride_frames)
+    rec, start, _ = draw_windows(prefix, seed, epoch, first_slot, batch)
+    return [r for r in rec for _ in range(K)], [s + k * sf for s in start for k in range(K)]
+
+
 # ---- tuning: how far a recording sits from A4 = 440 Hz, and the varispeed resampler that puts it back (ake_tuning_estimate_f32 / ake_retune_f32) ----
 
 TUNING_BINS_PER_SEMITONE = 3

@@ -924,12 +924,32 @@ class PitchClassNet(LightningModule):
                 torch.tensor(0.0))
 
     def general_step(self, batch, batch_idx, mode):
+        """The loss and the nine metrics of a batch.  A batch that carries ``sequence_shape = (S, K)`` (``TrackWindows``' sequence mode:
+        its rows are S sequences of K consecutive windows) adds ``opt.sequence_weight`` (default 1) times the sequence loss
+        (``ake_amd.key_sequence_loss``) of the two heads' outputs, viewed as (S, K, 12), against ``batch["key_id"]`` under
+        ``batch["log_trans"]`` with ``opt.signature_weight`` (default 1); the term's own value stays in ``self.last_sequence_loss``."""
         opt = self.opt
+        sequence = batch.get("sequence_shape") if isinstance(batch, dict) else None
         if self.local:
+            if sequence is not None:
+                raise ValueError("general_step: a --local net takes no sequence batches (its rows are frames of a clip, not windows of a track)")
             return self._general_step_local(batch)
+        out = self.forward(batch["mel"], batch["seq_length"] if _opt_get(opt, "frames", 5) > 0 else None)
+        vals = self._window_losses(batch, out)
+        if sequence is None:
+            return vals
+        from .sequence import key_sequence_loss
+        S, K = (int(v) for v in sequence)
+        term = key_sequence_loss(out[0].view(S, K, 12), out[1].view(S, K, 12), batch["key_id"].view(S, K), batch["log_trans"],
+                                 signature_weight=float(_opt_get(opt, "signature_weight", 1.0)))
+        self.last_sequence_loss = term.detach()
+        return (vals[0] + float(_opt_get(opt, "sequence_weight", 1.0)) * term.to(vals[0].dtype),) + tuple(vals[1:])
+
+    def _window_losses(self, batch, out):
+        """general_step's loss and metrics of every window on its own, from the forward's outputs."""
+        opt = self.opt
         mel = batch["mel"]
         key_signature_id = batch["key_signature_id"]
-        out = self.forward(mel, batch["seq_length"] if _opt_get(opt, "frames", 5) > 0 else None)
         key_out, tonic_out = out[0], out[1]
         dev = key_out.device
         if (key_out.is_cuda and key_out.dtype in (torch.float32, torch.float64) and type(self).mirex_score is PitchClassNet.mirex_score

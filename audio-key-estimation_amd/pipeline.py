@@ -543,7 +543,8 @@ class KeyEstimator:
     @torch.no_grad()
     def training_windows(self, audio: torch.Tensor, annotations: KeyAnnotations, lengths: torch.Tensor | None = None, rate: int | None = None,
                          channel: int = 0, window_seconds: float = 15.0, batch_size: int = 8, batches_per_epoch: int | None = None,
-                         stride_seconds: float | None = None, seed: int = 0, weighting: str = "purity", min_purity: float = 0.0):
+                         stride_seconds: float | None = None, seed: int = 0, weighting: str = "purity", min_purity: float = 0.0,
+                         sequence_windows: int | None = None, mean_key_seconds: float = 60.0, transition: torch.Tensor | None = None):
         """Training batches cut from annotated recordings on the device -> ``ake_amd.TrackWindows``, which
         ``Trainer.fit(net, train_dataloaders=...)`` takes as it takes a ``DataLoader``.
 
@@ -557,7 +558,14 @@ class KeyEstimator:
         ``seed`` and the epoch.  ``stride_seconds`` given: ``track``'s own windows at that stride, in order (for validation).
         ``weighting`` and ``min_purity``: see ``TrackWindows``.  Refused with a ``ValueError``: what ``track`` refuses, annotations of
         another number of recordings or another sample rate, and recordings none of which holds one window.  The lengths are read on
-        the host once, here; iterating the result waits for nothing."""
+        the host once, here; iterating the result waits for nothing.
+
+        ``sequence_windows=K`` (with ``stride_seconds``, which then is the stride inside a sequence): every batch is ``batch_size``
+        sequences of K consecutive ``track`` windows at random starts, for ``PitchClassNet.general_step``'s sequence loss
+        (``TrackWindows``' sequence mode has the batch's extra entries).  Its ``log_trans`` is the transition ``track(smooth=True)``
+        would use at this stride with ``mean_key_seconds``, or ``transition``, a (24, 24) tensor that is passed through as it is: one
+        that requires grad receives the loss's gradient and is trained by the caller's optimiser.  Refused: K < 2, a missing stride,
+        and recordings none of which holds one sequence."""
         from .windows import TrackWindows
         self._need_net("KeyEstimator.training_windows")
         self._refuse_untrackable()
@@ -577,8 +585,19 @@ class KeyEstimator:
         if T < wf:
             raise ValueError("training_windows: no recording is as long as one window")
         sf = None if stride_seconds is None else track_stride_frames(stride_seconds, self.frames)
+        log_trans = None
+        if sequence_windows is not None:
+            if sf is None:
+                raise ValueError("training_windows: sequence_windows needs stride_seconds, the stride between a sequence's windows")
+            if transition is None:
+                log_trans = self._transition(sf, mean_key_seconds, None)
+            elif not isinstance(transition, torch.Tensor) or tuple(transition.shape) != (24, 24):
+                raise ValueError("training_windows: transition must be a (24, 24) tensor of log-probabilities, from key i (row) to key j")
+            else:
+                log_trans = transition
         return TrackWindows(mel, frames, annotations, hop, wf, batch_size=batch_size, batches_per_epoch=batches_per_epoch, stride_frames=sf,
-                            seed=seed, weighting=weighting, min_purity=min_purity, genre_classes=11 if self.net.genre else 8)
+                            seed=seed, weighting=weighting, min_purity=min_purity, genre_classes=11 if self.net.genre else 8,
+                            sequence_windows=sequence_windows, log_trans=log_trans)
 
     def _transition(self, sf, mean_key_seconds, transition):
         """The (24, 24) float32 log transition matrix on the device: built and validated once per (stride, mean_key_seconds) or per

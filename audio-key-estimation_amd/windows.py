@@ -88,12 +88,20 @@ class TrackWindows:
     Grid mode (``stride_frames`` given), for validation: ``KeyEstimator.track``'s own windows at that stride, in order, recording by
     recording; the last batch may be short.
 
+    Sequence mode (``sequence_windows=K`` with ``stride_frames``), for the sequence loss (``ake_amd.key_sequence_loss``): every batch is
+    ``batch_size`` sequences of K consecutive ``track`` windows, ``stride_frames`` apart, so ``B = batch_size * K`` rows ordered
+    ``[sequence][window]``.  The sequence starts are drawn as random mode draws windows, over the recordings that hold one whole sequence
+    (``metrics.window_prefix(frames, window_frames + (K - 1) * stride_frames)``): slot ``i * batch_size + s`` of ``(seed, epoch)`` is
+    sequence s of batch i (``metrics.sequence_windows``).  The batch carries three more entries: ``sequence_shape = (batch_size, K)``,
+    ``key_id`` int32 (B,) -- the window's key where ``sample_weight > 0``, else -1, an unlabelled window to the loss -- and ``log_trans``,
+    the (24, 24) transition the sequences are scored under, the tensor given here as it is.
+
     ``weighting``: ``"purity"`` weighs a window by the share of its samples that carry its label, ``"uniform"`` by 1; either way 0 for an
     unlabelled window and for ``purity < min_purity``.  Iterating launches kernels and allocates outputs, and waits for nothing.  Under
     data-parallel training every rank's loss is normalised by the weights of its own batch."""
 
     def __init__(self, mel, frames, annotations, hop, window_frames, batch_size=8, batches_per_epoch=None, stride_frames=None, seed=0,
-                 weighting="purity", min_purity=0.0, genre_classes=11):
+                 weighting="purity", min_purity=0.0, genre_classes=11, sequence_windows=None, log_trans=None):
         if weighting not in ("purity", "uniform"):
             raise ValueError("weighting must be 'purity' or 'uniform'")
         if int(batch_size) < 1:
@@ -118,7 +126,26 @@ class TrackWindows:
         self._genre = {}
         self._genre_classes = int(genre_classes)
         count = lambda t, sf: 0 if t < wf else (t - wf) // sf + 1                                   # pipeline.track_counts
-        if self.stride_frames is None:
+        self.sequence_windows = None if sequence_windows is None else int(sequence_windows)
+        self.log_trans = log_trans
+        if self.sequence_windows is not None:
+            K = self.sequence_windows
+            if K < 2:
+                raise ValueError("sequence_windows must be at least 2 (one window is what random mode draws)")
+            if self.stride_frames is None or self.stride_frames < 1:
+                raise ValueError("sequence_windows needs a stride of at least one frame between a sequence's windows (stride_seconds)")
+            if not isinstance(log_trans, torch.Tensor) or tuple(log_trans.shape) != (24, 24):
+                raise ValueError("sequence_windows needs log_trans, a (24, 24) tensor of log-probabilities, from key i (row) to key j")
+            prefix = metrics.window_prefix(self.frames, wf + (K - 1) * self.stride_frames)
+            if prefix[-1] <= 0:
+                raise ValueError(f"training_windows: no recording is as long as one sequence of {K} windows")
+            self._prefix = torch.tensor(prefix, dtype=torch.int64, device=dev)
+            self._offsets = torch.arange(K, dtype=torch.int32, device=dev) * self.stride_frames
+            grid = sum(count(t, self.stride_frames) for t in self.frames)
+            self.batches_per_epoch = -(-grid // (self.batch_size * K)) if batches_per_epoch is None else int(batches_per_epoch)
+            if self.batches_per_epoch < 1:
+                raise ValueError("batches_per_epoch must be at least 1")
+        elif self.stride_frames is None:
             prefix = metrics.window_prefix(self.frames, wf)
             if prefix[-1] <= 0:
                 raise ValueError("training_windows: no recording is as long as one window")
@@ -154,8 +181,25 @@ class TrackWindows:
         out["genre"], out["recording"], out["start_frame"] = self._genre[B], recording, start
         return out
 
+    def _sequences(self, epoch, i):
+        """Batch i of ``epoch`` in sequence mode: the drawn starts expanded to K windows each, two torch ops on the device."""
+        B, K = self.batch_size, self.sequence_windows
+        recording, start = draw_windows(self._prefix, self.seed, epoch, i * B, B)
+        out = self._batch(recording[:, None].expand(B, K).reshape(-1), (start[:, None] + self._offsets[None, :]).reshape(-1))
+        out["sequence_shape"] = (B, K)
+        key = out["key_signature_id"].argmax(dim=1).to(torch.int32)
+        out["key_id"] = torch.where(out["sample_weight"] > 0, key, torch.full_like(key, -1))
+        out["log_trans"] = self.log_trans
+        return out
+
     def __iter__(self):
         B = self.batch_size
+        if self.sequence_windows is not None:
+            epoch = self.epoch
+            for i in range(self.batches_per_epoch):
+                yield self._sequences(epoch, i)
+            self.epoch = epoch + 1
+            return
         if self.stride_frames is not None:
             for i in range(self.batches_per_epoch):
                 yield self._batch(self._recording[i * B:(i + 1) * B], self._start[i * B:(i + 1) * B])

@@ -511,6 +511,44 @@ int ake_key_posteriors_f32(const float* emis_dev, int recordings, int windows, c
                            float* path_post_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A loss over a sequence of windows, for training the net for the smoothed track: the conditional log-likelihood of the labelled windows
+ * in a linear-chain CRF whose unary scores are ake_key_emissions_f32's and whose chain is ake_key_posteriors_f32's, with its gradient
+ * with respect to the two heads' outputs and the transition.  Host model: metrics.key_sequence_loss.
+ * ---------------------------------------------------------------------------------------- */
+/* key_dev / tonic_dev [recordings][windows][12] (sigmoid memberships, tonic logits), labels_dev int32 [recordings][windows] (a key 0..23;
+ * anything else = unlabelled), counts_dev, log_trans_dev and log_prior_dev as ake_key_posteriors_f32 takes them (all finite).  With
+ *   e[r][w][k]   = ake_key_emissions_f32's score (same formula, same clamps, same signature_weight)
+ *   e~[r][w][k]  = e[r][w][k] if label[r][w] is outside 0..23 or k == label[r][w], else -1e4 (AKE_SEQUENCE_CLAMP: finite, as the chains
+ *                  require; its exponential is 0)
+ *   loglik(x)    = ake_key_posteriors_f32's sum_w c_w over x, post / xi_sum its posteriors and transition sums (post~, xi~_sum over e~)
+ *   N            = the windows with w < count[r] and a label in 0..23, over the whole call
+ *   loss         = ( sum_r loglik(e[r]) - sum_r loglik(e~[r]) ) / N          (0, with zero gradients, when N == 0)
+ * an unlabelled window is marginalised; with every window labelled this is -(score(path) - log Z) / N.  Gradients, for w < count:
+ *   g[r][w][k]   = ( post[r][w][k] - post~[r][w][k] ) / N                                       (d loss / d e; d_emis_dev)
+ *   d_trans[i][j] = sum_r ( xi_sum[r][i][j] - xi~_sum[r][i][j] ) / N                            (log_prior gets none)
+ *   d_tonic[j]   = g[j] + g[j + 12] - softmax(tonic)[j] * sum_k g[k]
+ *   d_key[j]     = signature_weight / 12 * ( sum_k S_k[j] g[k] * u(p_j) - sum_k (1 - S_k[j]) g[k] * v(p_j) )
+ *   u(p) = 1 / p where p >= FLT_MIN and log p > -100, else 0;   v(p) = 1 / (1 - p) where 1 - p >= FLT_MIN and log1p(-p) > -100, else 0
+ * (the derivative is 0 where nn.BCELoss's clamp is active and for subnormal arguments).
+ * Outputs: scalars_dev [4] = loss, sum_r loglik / N, sum_r loglik~ / N, N; d_key_dev / d_tonic_dev [recordings][windows][12] and
+ * d_emis_dev [recordings][windows][24] (nullable), zeros at w >= count; d_trans_dev [24][24], nullable.
+ * Launches: 4 -- the emissions of both sets; the four chains of a recording (free / clamped x forward / backward) side by side, one wave
+ * each; one block for N and the scalars (the two sums are large and nearly equal: subtracted per recording and added in recording
+ * order); one thread per window for the gradients -- and 2 more with d_trans_dev: the per-chunk transition sums of both sets
+ * (key_posteriors_kernel's code on float32 copies of the scores), then their difference in chunk and recording order.  The emissions
+ * (ake_key_emissions_f32's arithmetic, instantiated in double), the chains (the recurrences of ake_key_posteriors_f32) and the gradient
+ * run in double and are rounded to float32 once, on the way out: the gradient is a difference of two nearly equal posteriors, which
+ * float32 log-scores carry only to |log-odds| * 2^-24.  No float atomics: two runs on the same inputs are bit-identical.  No
+ * device-to-host copy, no synchronisation; the only memory used is the workspace and the outputs.  The
+ * workspace, key_dev, tonic_dev, d_key_dev, d_tonic_dev and d_emis_dev are 16-byte aligned.  AKE_ERR_INVALID for recordings < 1,
+ * windows < 1 and null required pointers, AKE_ERR_WORKSPACE for a workspace below ake_key_sequence_loss_workspace_bytes. */
+size_t ake_key_sequence_loss_workspace_bytes(int recordings, int windows);
+int ake_key_sequence_loss_f32(const float* key_dev, const float* tonic_dev, const int32_t* labels_dev, int recordings, int windows,
+                              const int32_t* counts_dev, const float* log_trans_dev, const float* log_prior_dev, float signature_weight,
+                              float* scalars_dev, float* d_key_dev, float* d_tonic_dev, float* d_trans_dev, float* d_emis_dev, void* workspace,
+                              size_t workspace_bytes, ake_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * A track against key annotations, one launch, integers only: two runs on the same inputs are bit-identical.
  * ---------------------------------------------------------------------------------------- */
 /* pred_dev (int32 [recordings][windows], -1..23: key_id or the Viterbi path) against the annotations of every recording:
