@@ -1213,6 +1213,14 @@ struct Layer0Plan {
     L0Form form = L0Form::Generic;
     int RP = 0, RPp = 0;
     size_t lds = 0;
+    // FusedMfma: where float (bin r, frame t) of the clip's CQT sits in the LDS image (Layer0Args::img_*).  A frames-major clip is stored
+    // tiled, [frame quad][bin & 3][bin >> 2][frame & 3]: its loader's 16-byte stores (a thread's 4 frames of one bin, adjacent lanes 4 bins
+    // apart) then lie side by side, and a frame quad's pitch of 4 (mod 32) floats keeps the semitone phase's frame-wise reads on 32 banks
+    bool tiled = false;
+    int img_sq = 0, img_sb = 0, img_sr = 0;
+    // FusedMfma: the convs >= 1 find their weight fragments in two LDS regions laid over the dead image (else, where the maps leave no room
+    // for them -- few bins, many frames -- every conv fetches its own from global memory at its start)
+    bool frag_lds = false;
 };
 
 struct Route {
@@ -1243,6 +1251,7 @@ struct Route {
 };
 
 // layer 0 as one launch per clip (default family, inference): which form fits, and its LDS geometry
+constexpr size_t kL0MaxLds = 160 * 1024;      // layer0_mfma_kernel's dynamic LDS limit (at the rule's edge, T = 86 frames-major, it takes 152.6 KiB)
 Layer0Plan layer0_plan(const ake_pcnet* n, int T0, bool mel16, bool mel_fm) {
     const auto& c = n->cfg;
     const int P = c.pitches, NF = c.n_filters;
@@ -1266,6 +1275,21 @@ Layer0Plan layer0_plan(const ake_pcnet* n, int T0, bool mel16, bool mel_fm) {
     if (mel_fm && (!take_mfma || P % 4)) return g;        // only the MFMA form's loader transposes
     g.form = take_mfma ? L0Form::FusedMfma : L0Form::FusedValu;
     g.lds = take_mfma ? lds_m : lds_v;
+    if (take_mfma) {      // what the kernel really takes (lds_m stays the rule): the maps, then the image or the fragment regions laid over it
+        const size_t maps = lds_m - static_cast<size_t>(P) * T0 * sizeof(float);
+        const size_t frag_bytes = c.conv_layers > 1 ? static_cast<size_t>(2) * 24 * 64 * sizeof(uint4) : 0;
+        const int sq = 4 * P + ((36 - (4 * P & 31)) & 31);
+        const size_t tiled_bytes = static_cast<size_t>((T0 + 3) / 4) * sq * sizeof(float);
+        // The untiled frames-major image (every frame through the scalar stores that otherwise take the frames past the last quad) is for
+        // pitch counts far above any net that is tested as a whole clip: at 288 and 360 bins the tiled image fits at every eligible frame count.
+        g.tiled = mel_fm && maps + tiled_bytes <= kL0MaxLds;
+        g.img_sq = g.tiled ? sq : 4;
+        g.img_sb = g.tiled ? P : T0;
+        g.img_sr = g.tiled ? 4 : 4 * T0;
+        const size_t img_bytes = g.tiled ? tiled_bytes : static_cast<size_t>(P) * T0 * sizeof(float);
+        g.frag_lds = frag_bytes && maps + std::max(img_bytes, frag_bytes) <= kL0MaxLds;
+        g.lds = maps + (g.frag_lds ? std::max(img_bytes, frag_bytes) : img_bytes);       // <= kL0MaxLds either way: lds_m <= 150 KiB
+    }
     return g;
 }
 
@@ -2523,10 +2547,14 @@ struct Fwd {
         static ake::DeviceOnce attr_set;
         if (attr_set.need()) {
             AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(layer0_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-            AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(layer0_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+            AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(layer0_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kL0MaxLds)));
             attr_set.mark();
         }
         a.mel_fm = r.frames_major ? 1 : 0;
+        a.frag_lds = r.l0.frag_lds ? 1 : 0;
+        a.img_tiled = r.l0.tiled ? 1 : 0; a.img_sq = r.l0.img_sq; a.img_sb = r.l0.img_sb; a.img_sr = r.l0.img_sr;
+        AKE_REQUIRE(!r.l0.tiled || r.frames_major, AKE_ERR_STATE, "pcnet: layer 0's image was planned for a frames-major input that the route refused");
+        AKE_REQUIRE(r.l0.lds <= kL0MaxLds, AKE_ERR_STATE, "pcnet: layer 0's one-launch form does not fit the LDS at this shape");
         a.taps = g_keep_taps ? 1 : 0;
         if (r.psix_f16) { a.psix_h = reinterpret_cast<uint2*>(b.psix[1]); a.psix = nullptr; a.melh = b.melh; }
         ake::ProfScope ps("layer0_fused_kernel", s);

@@ -2582,6 +2582,9 @@ struct Layer0Args {
                                  // zero), INSTEAD of psix: what conv_p2p_f16_ps_kernel<1, 3> loads (one 8-byte load per patch position, no conversion)
     unsigned int* melh;          // (with psix_h) the log-CQT as f16 hi | f16 lo << 16 words in [clip][H][T] order, for the same reader: the transposition of
                                  // a frames-major mel is paid once, here, where the clip passes through the LDS anyway
+    int img_tiled;               // layer0_mfma_kernel: the LDS image of the clip's CQT is [frame quad][bin & 3][bin >> 2][frame & 3] (Layer0Plan), not [H][T]
+    int frag_lds;                // layer0_mfma_kernel: the convs >= 1 get their fragments by LDS-DMA over the dead image (0: each conv loads its own from global)
+    int img_sq, img_sb, img_sr;  // ... float (bin r, frame t) sits at (t >> 2) img_sq + (t & 3) + (r & 3) img_sb + (r >> 2) img_sr in either order
 };
 
 __global__ __launch_bounds__(512) void layer0_fused_kernel(Layer0Args a) {
@@ -2750,9 +2753,10 @@ __global__ void local_pool_kernel(LocalPoolArgs a) {
 //   m = (pitch class p, frame pair j)     A[m][k = (position q', ci)] = X[(p + dy) mod 12][2j + q'][ci]    (8 positions x 4 channels = 32)
 //   n = (tau, co) = 4 * tau + co < 8      B[k][n] = w[co][ci][dy][q' - tau]                                  (columns 8..15 idle)
 //   k-step = dy: 12 MFMAs per 16 x 16 tile in two independent accumulator chains, ~29 tiles per clip.
-// One A fragment = one aligned 16-byte LDS read (2 positions x 4 channels); the 12 weight fragments of a layer sit in registers and the
-// next layer's are requested before the epilogue.  (Round 1: split bf16 x 3, one chain of 36 dependent MFMAs per tile, fragments
-// fetched behind the barrier: the three convs were 24 of the kernel's 45 us.)
+// One A fragment = one aligned 16-byte LDS read (2 positions x 4 channels), requested three k-steps ahead of its MFMAs; the 12 + 12 weight
+// fragments of a conv sit in registers and the next conv's travel by LDS-DMA over the dead CQT image meanwhile.  (Round 1: split bf16 x 3,
+// one chain of 36 dependent MFMAs per tile, fragments fetched behind the barrier: the three convs were 24 of the kernel's 45 us.
+// profiles/layer0_stalls.md: the phases of this form, stamped.)
 __global__ void pack_l0_f16_kernel(const float* __restrict__ w, uint4* __restrict__ out, int cin, int cout) {
     __shared__ int smax[4];
     channel_absmax4(w, cin * 84, smax);
@@ -2779,6 +2783,57 @@ __global__ void pack_l0_f16_kernel(const float* __restrict__ w, uint4* __restric
     out[(2 * dy + 1) * 64 + lane] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
 }
 
+// (q, r) += (dq, dr) with r kept below n: a quotient and remainder walked in fixed steps instead of divided again (dr < n)
+__device__ __forceinline__ void l0_step(int& qv, int& rv, const int dq, const int dr, const int n) {
+    qv += dq;
+    rv += dr;
+    if (rv >= n) { rv -= n; ++qv; }
+}
+
+// layer 1's up_sixth + BN + LeakyReLU from the f32 map of the last conv, as f16 x 4 per position.  NFC = 4: the default width as a
+// constant, its 52 weights fetched once in front of the loop; NFC = 0: the run-time width (2, 3), channels >= NF zero.
+template <int NFC>
+__device__ __forceinline__ void l0_up_sixth_h(const Layer0Args& a, const float* fmap, uint2* ph, const int tid) {
+    typedef const float __attribute__((address_space(4))) cfloat;
+    cfloat* uw = (cfloat*)a.uw;
+    cfloat* ub = (cfloat*)a.ub;
+    const int T = a.T, RP = a.RP, NF = NFC ? NFC : a.NF;
+    float wk[NFC ? 48 : 1], bk[NFC ? 4 : 1];
+    if (NFC) {
+#pragma unroll
+        for (int i = 0; i < (NFC ? 48 : 1); ++i) wk[i] = uw[i];
+#pragma unroll
+        for (int i = 0; i < (NFC ? 4 : 1); ++i) bk[i] = ub[i];
+    }
+    for (int i = tid; i < 12 * T; i += 512) {
+        const int p = i / T, t = i - p * T;
+        float x[4];
+#pragma unroll
+        for (int ci = 0; ci < 4; ++ci) x[ci] = fmap[(ci * 12 + p) * RP + 3 + t];
+#pragma unroll
+        for (int jj = 0; jj < 3; ++jj) {
+            unsigned int h[4];
+#pragma unroll
+            for (int co2 = 0; co2 < 4; ++co2) {
+                float acc;
+                if (NFC) {
+                    acc = bk[co2];
+#pragma unroll
+                    for (int ci = 0; ci < 4; ++ci) acc = fmaf(x[ci], wk[(ci * 4 + co2) * 3 + jj], acc);
+                } else {
+                    acc = co2 < NF ? ub[co2 < NF ? co2 : 0] : 0.f;
+#pragma unroll
+                    for (int ci = 0; ci < 4; ++ci)
+                        if (ci < NF && co2 < NF) acc = fmaf(x[ci], uw[(ci * NF + co2) * 3 + jj], acc);
+                }
+                acc = acc > 0.f ? acc : acc * kSlope;
+                h[co2] = __builtin_bit_cast(unsigned short, static_cast<_Float16>(acc));
+            }
+            ph[(3 * p + jj) * T + t] = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
+        }
+    }
+}
+
 __global__ __launch_bounds__(512) void layer0_mfma_kernel(Layer0Args a) {
     extern __shared__ __attribute__((aligned(16))) float l0[];
     const int clip = blockIdx.x, tid = threadIdx.x;
@@ -2786,27 +2841,83 @@ __global__ __launch_bounds__(512) void layer0_mfma_kernel(Layer0Args a) {
     const int r16 = lane & 15, q = lane >> 4;
     const int T = a.T, RP = a.RP, RPp = a.RPp, NF = a.NF;
     f16_saturate_mode();
-    // LDS: f32 map of the latest conv output [4][12][RP] (for up_sixth) | two channels-last maps of [12][RPp] positions x 4 f16 (sized
-    // as in round 1, when each had a hi and a lo plane) | the clip's CQT [H][T] (semitone phase only)
+    // LDS: f32 map of the latest conv output [4][12][RP] (for up_sixth) | two channels-last maps of [12][RPp] positions x 4 f16, a hi and a lo
+    // plane each | the clip's CQT image (semitone phase only), then, over it, the weight fragments of the convs >= 1 in two regions of 24 KB
     float* const fmap = l0;
     unsigned short* const mapA = reinterpret_cast<unsigned short*>(l0 + 4 * 12 * RP);
     const int plane = 12 * RPp * 4;                                   // f16 elements per map
     unsigned short* const mapB = mapA + 2 * plane;
     float* const ml = reinterpret_cast<float*>(mapB + 2 * plane);
-    for (int i = tid; i < 4 * 12 * RP + 2 * plane; i += 512) l0[i] = 0.f;
+    auto frags_of = [&](int j) { return j == 0 ? a.frag[0] : j == 1 ? a.frag[1] : j == 2 ? a.frag[2] : a.frag[3]; };   // (no runtime index into the argument struct)
+    // the first conv's weight fragments (hi, lo) depend on nothing: requested here, they arrive behind the loader and the semitone phase
+    uint4 breg[12], bregl[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+        breg[i] = a.n_conv > 0 ? frags_of(0)[2 * i * 64 + lane] : make_uint4(0, 0, 0, 0);
+        bregl[i] = a.n_conv > 0 ? frags_of(0)[(2 * i + 1) * 64 + lane] : make_uint4(0, 0, 0, 0);
+    }
+    // ... and so do every conv's bias and inverse weight scale of this lane's output channel.  (Fetched inside the conv loop they would be
+    // waited for with vmcnt(0) in front of the first tile, behind the LDS-DMA requests the compiler cannot count.)
+    const int tau = (r16 >> 2) & 1, co = r16 & 3;
+    float bias_j[4], iscale_j[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        bias_j[j] = (j < a.n_conv && r16 < 8 && co < NF) ? a.b[j][co] : 0.f;
+        iscale_j[j] = j < a.n_conv ? reinterpret_cast<const float*>(a.frag[j] + 24 * 64)[co] : 0.f;
+    }
+    // the two maps are read whole (padding positions, channels no conv writes) and zeroed whole; the f32 map needs none: up_sixth uses
+    // only what the last conv wrote
+    for (int i = tid; i < plane / 2; i += 512) reinterpret_cast<uint4*>(mapA)[i] = make_uint4(0, 0, 0, 0);
     // ---- semitone conv + BN + LeakyReLU + octave fold -> channel 0 of map A ----
     {
         const float4* mel4 = reinterpret_cast<const float4*>(a.mel + static_cast<long long>(clip) * a.H * T);
         const int n4 = a.H * T / 4;
-        if (a.mel_fm) {          // [T][H] -> the [H][T] image: 16-byte reads along the bins, transposed on the way into the LDS
+        const int Sq = a.img_sq, Sb = a.img_sb, Sr = a.img_sr;
+        auto img = [&](int r, int t) { return (t >> 2) * Sq + (t & 3) + (r & 3) * Sb + (r >> 2) * Sr; };
+        if (a.mel_fm) {          // [T][H] -> the image: 16-byte reads along the bins, transposed on the way into the LDS
             const int h4 = a.H / 4;
-            for (int i = tid; i < n4; i += 512) {
+            // tiled image: a thread owns 4 bins x 4 frames.  Its four loads (lanes along the bins: coalesced) are all requested before the
+            // first store, the 4 x 4 block is transposed in registers and leaves as four 16-byte stores, which adjacent lanes (bins 4 apart)
+            // put side by side: no bank conflict
+            const int nq = a.img_tiled ? T >> 2 : 0;
+            const int nit = nq * h4;
+            const int sq_i = 512 / h4, sr_i = 512 - sq_i * h4;
+            int fq_i = tid / h4, R_i = tid - fq_i * h4;               // item i = (frame quad, bin quad), walked 512 at a time without dividing
+            for (int i0 = tid; i0 < nit; i0 += 512 * 3) {
+                float4 v[3][4];
+                int fqs[3], Rs[3];
+#pragma unroll
+                for (int u = 0; u < 3; ++u) {
+                    const bool live = i0 + 512 * u < nit;            // (past the end: item 0 again, the same floats to the same place.  With a
+                    fqs[u] = live ? fq_i : 0; Rs[u] = live ? R_i : 0;  // branch here or at the stores, an item's requests are sunk to its stores)
+                    l0_step(fq_i, R_i, sq_i, sr_i, h4);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) v[u][k] = mel4[(4 * fqs[u] + k) * h4 + Rs[u]];
+                }
+#pragma unroll
+                for (int u = 0; u < 3; ++u) {
+                    float* const d = ml + fqs[u] * Sq + Rs[u] * 4;
+                    *reinterpret_cast<float4*>(d) = make_float4(v[u][0].x, v[u][1].x, v[u][2].x, v[u][3].x);
+                    *reinterpret_cast<float4*>(d + Sb) = make_float4(v[u][0].y, v[u][1].y, v[u][2].y, v[u][3].y);
+                    *reinterpret_cast<float4*>(d + 2 * Sb) = make_float4(v[u][0].z, v[u][1].z, v[u][2].z, v[u][3].z);
+                    *reinterpret_cast<float4*>(d + 3 * Sb) = make_float4(v[u][0].w, v[u][1].w, v[u][2].w, v[u][3].w);
+                }
+            }
+            for (int i = 4 * nit + tid; i < n4; i += 512) {          // the frames past the last whole quad (untiled image: all of them)
                 const int t = i / h4, r4 = (i - t * h4) * 4;
                 const float4 v = mel4[i];
-                ml[(r4 + 0) * T + t] = v.x; ml[(r4 + 1) * T + t] = v.y; ml[(r4 + 2) * T + t] = v.z; ml[(r4 + 3) * T + t] = v.w;
+                ml[img(r4 + 0, t)] = v.x; ml[img(r4 + 1, t)] = v.y; ml[img(r4 + 2, t)] = v.z; ml[img(r4 + 3, t)] = v.w;
             }
-        } else
-            for (int i = tid; i < n4; i += 512) reinterpret_cast<float4*>(ml)[i] = mel4[i];
+        } else {                 // a straight copy, eight loads requested before the first store.  Past the end a thread copies the last piece
+                                 // again: no branch, so that the loads are not sunk back to their stores
+            for (int i0 = tid; i0 < n4; i0 += 512 * 8) {
+                float4 v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) v[u] = mel4[i0 + 512 * u < n4 ? i0 + 512 * u : n4 - 1];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) reinterpret_cast<float4*>(ml)[i0 + 512 * u < n4 ? i0 + 512 * u : n4 - 1] = v[u];
+            }
+        }
         __syncthreads();
         if (a.melh) {
             uint4* const mh = reinterpret_cast<uint4*>(a.melh + static_cast<long long>(clip) * a.H * T);
@@ -2814,9 +2925,26 @@ __global__ __launch_bounds__(512) void layer0_mfma_kernel(Layer0Args a) {
                 const _Float16 h = static_cast<_Float16>(v);
                 return static_cast<unsigned int>(__builtin_bit_cast(unsigned short, h)) | (f16_bits(v - static_cast<float>(h)) << 16);
             };
-            for (int i = tid; i < n4; i += 512) {
-                const float4 v = reinterpret_cast<const float4*>(ml)[i];
-                mh[i] = make_uint4(word(v.x), word(v.y), word(v.z), word(v.w));
+            auto words = [&](const float4 v) { return make_uint4(word(v.x), word(v.y), word(v.z), word(v.w)); };
+            if (!a.img_tiled) {
+                for (int i = tid; i < n4; i += 512) mh[i] = words(reinterpret_cast<const float4*>(ml)[i]);
+            } else if (!(T & 3)) {                                    // four words of one row: one 16-byte read of the tiled image
+                const int tq4 = T >> 2, sq_m = 512 / tq4, sr_m = 512 - sq_m * tq4;
+                int r = tid / tq4, tq = tid - r * tq4;
+                for (int i = tid; i < n4; i += 512) {
+                    mh[i] = words(*reinterpret_cast<const float4*>(ml + img(r, 4 * tq)));
+                    l0_step(r, tq, sq_m, sr_m, tq4);
+                }
+            } else {
+                for (int i = tid; i < n4; i += 512) {
+                    float e[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int r = (4 * i + k) / T;
+                        e[k] = ml[img(r, 4 * i + k - r * T)];
+                    }
+                    mh[i] = words(make_float4(e[0], e[1], e[2], e[3]));
+                }
             }
         }
         float w9[9];
@@ -2827,15 +2955,19 @@ __global__ __launch_bounds__(512) void layer0_mfma_kernel(Layer0Args a) {
         for (int i = tid; i < 12 * T; i += 512) {
             const int p = i / T, t = i - p * T;
             const int tm = t == 0 ? T - 1 : t - 1, tp = t == T - 1 ? 0 : t + 1;
+            const int fm = (tm >> 2) * Sq + (tm & 3), f0 = (t >> 2) * Sq + (t & 3), fp = (tp >> 2) * Sq + (tp & 3);
+            int ro[3];                                                // bins 3 (p + 12 o) + dy: 36 o is a multiple of 4
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy) ro[dy] = ((3 * p + dy) & 3) * Sb + ((3 * p + dy) >> 2) * Sr;
             float best = -INFINITY;
             for (int o = 0; o < n_oct; ++o) {
-                const float* r = ml + 3 * (p + 12 * o) * T;
+                const float* r = ml + 9 * o * Sr;
                 float acc = 0.f;
 #pragma unroll
                 for (int dy = 0; dy < 3; ++dy) {
-                    acc = fmaf(r[dy * T + tm], w9[dy * 3 + 0], acc);
-                    acc = fmaf(r[dy * T + t], w9[dy * 3 + 1], acc);
-                    acc = fmaf(r[dy * T + tp], w9[dy * 3 + 2], acc);
+                    acc = fmaf(r[ro[dy] + fm], w9[dy * 3 + 0], acc);
+                    acc = fmaf(r[ro[dy] + f0], w9[dy * 3 + 1], acc);
+                    acc = fmaf(r[ro[dy] + fp], w9[dy * 3 + 2], acc);
                 }
                 float v = acc + sb;
                 v = v > 0.f ? v : v * kSlope;
@@ -2850,7 +2982,7 @@ __global__ __launch_bounds__(512) void layer0_mfma_kernel(Layer0Args a) {
     __syncthreads();
     // ---- the convolution stack on MFMA ----
     const int J = (T + 1) / 2, M = 12 * J, n_tiles = (M + 15) / 16;
-    const int tau = (r16 >> 2) & 1, co = r16 & 3;
+    const int sq_t = 128 / J, sr_t = 128 - sq_t * J, rowE = RPp * 4;
     const unsigned short* in = mapA;
     unsigned short* out = mapB;
     // Round 3: f32-equivalent products again (activations AND weights as f16 hi + f16 lo x 2^11, three MFMAs: ah*wh, and al'*wh + ah*wl' in an
@@ -2858,58 +2990,81 @@ __global__ __launch_bounds__(512) void layer0_mfma_kernel(Layer0Args a) {
     // weights, but on a TRAINED net (tests/test_gpu_training.py::test_mixed_precision_inference_on_trained_weights) it was the largest single
     // contributor to the outputs' error, 6.7e-4 of a 7.9e-4 total against the 1e-3 budget.  The stack is 1 % of the network's MACs: the two
     // extra products cost microseconds.
-    uint4 breg[12], bregl[12], bnext[12], bnextl[12];                     // this conv's weight fragments (hi, lo), the next one's
-    auto frags_of = [&](int j) { return j == 0 ? a.frag[0] : j == 1 ? a.frag[1] : j == 2 ? a.frag[2] : a.frag[3]; };   // (no runtime index into the argument struct)
-#pragma unroll
-    for (int i = 0; i < 12; ++i) {
-        bnext[i] = a.n_conv > 0 ? frags_of(0)[2 * i * 64 + lane] : make_uint4(0, 0, 0, 0);
-        bnextl[i] = a.n_conv > 0 ? frags_of(0)[(2 * i + 1) * 64 + lane] : make_uint4(0, 0, 0, 0);
-    }
+    // The image is dead now.  While conv j multiplies, the fragments of conv j + 1 go over it by LDS-DMA (24 pieces of 1 KB, three per
+    // wave) into region (j + 1) & 1, and conv j + 1 starts by reading its 24 registers from there: only ONE conv's fragments are held in
+    // registers, which leaves room to keep the A reads of the next k-steps in flight.  A region is rewritten two convs after it was read.
+    uint4* const fr0 = reinterpret_cast<uint4*>(ml);
     for (int j = 0; j < a.n_conv; ++j) {
+        if (j > 0 && a.frag_lds) {
+            const uint4* fr = fr0 + (j & 1) * 24 * 64;
 #pragma unroll
-        for (int i = 0; i < 12; ++i) { breg[i] = bnext[i]; bregl[i] = bnextl[i]; }
-        const float bias = (r16 < 8 && co < NF) ? a.b[j][co] : 0.f;
-        const float iscale = reinterpret_cast<const float*>(frags_of(j) + 24 * 64)[co];
+            for (int i = 0; i < 12; ++i) { breg[i] = fr[2 * i * 64 + lane]; bregl[i] = fr[(2 * i + 1) * 64 + lane]; }
+        } else if (j > 0) {                                                // no room for the regions: the latency is paid here.  (A branch of its
+            const uint4* fr = frags_of(j);                                 // own: one pointer chosen between the two makes every read a flat load)
+#pragma unroll
+            for (int i = 0; i < 12; ++i) { breg[i] = fr[2 * i * 64 + lane]; bregl[i] = fr[(2 * i + 1) * 64 + lane]; }
+        }
+        const float bias = j == 0 ? bias_j[0] : j == 1 ? bias_j[1] : j == 2 ? bias_j[2] : bias_j[3];
+        const float iscale = j == 0 ? iscale_j[0] : j == 1 ? iscale_j[1] : j == 2 ? iscale_j[2] : iscale_j[3];
         const bool write_dst = a.taps || j == a.n_conv - 1;
         float* const g = a.dst[j] + clip * a.dst_clip_stride[j];
-        if (j + 1 < a.n_conv) {                                           // in flight during this conv's multiply loop
+        if (j + 1 < a.n_conv && a.frag_lds) {                             // in flight during this conv's multiply loop
+            const uint4* src = frags_of(j + 1);
+            uint4* const dstl = fr0 + ((j + 1) & 1) * 24 * 64;
 #pragma unroll
-            for (int i = 0; i < 12; ++i) { bnext[i] = frags_of(j + 1)[2 * i * 64 + lane]; bnextl[i] = frags_of(j + 1)[(2 * i + 1) * 64 + lane]; }
+            for (int k = 0; k < 3; ++k) {
+                const int c = wave + 8 * k;
+                ake::lds_dma_16(src + c * 64 + lane, static_cast<unsigned int>(reinterpret_cast<unsigned long long>(dstl + c * 64)));
+            }
         }
+        // row m = (pitch class, frame pair) of this lane's A fragment and of its first output, divided once: a wave's next tile is 128 rows on
+        int pa = (wave * 16 + r16) / J, ja = wave * 16 + r16 - pa * J;
+        int pe = (wave * 16 + 4 * q) / J, je = wave * 16 + 4 * q - pe * J;
         for (int tile = wave; tile < n_tiles; tile += 8) {
-            int m = tile * 16 + r16;
-            m = m < M ? m : M - 1;
-            const int p = m / J, jj = m - p * J;
+            const int p = pa < 12 ? pa : 11, jj = pa < 12 ? ja : J - 1;      // (rows past the last one read the last one)
             f32x4c acc = {0.f, 0.f, 0.f, 0.f}, accl = {0.f, 0.f, 0.f, 0.f};   // hi x hi, and the two cross terms (x 2^11)
+            // the A fragments of k-step dy + kL0Ahead are requested before the MFMAs of dy (fully unrolled: ah / al are plain registers)
+            constexpr int kL0Ahead = 3;
+            f16x8c ah[12], al[12];
+            const int e0 = (p * RPp + 2 * jj + 2 * q) * 4;               // padded position of frame 2j - 3 + 2q, row p
+            auto request = [&](int dy) {                                 // row (p + dy) mod 12
+                const int e = e0 + dy * rowE - (dy >= 12 - p ? 12 * rowE : 0);
+                ah[dy] = __builtin_bit_cast(f16x8c, *reinterpret_cast<const uint4*>(in + e));
+                al[dy] = __builtin_bit_cast(f16x8c, *reinterpret_cast<const uint4*>(in + plane + e));
+            };
 #pragma unroll
-            for (int dy = 0; dy < 12; ++dy) {
-                int row = p + dy;
-                row -= row >= 12 ? 12 : 0;
-                const int pos = row * RPp + 2 * jj + 2 * q;              // padded position of frame 2j - 3 + 2q
-                const f16x8c ah = __builtin_bit_cast(f16x8c, *reinterpret_cast<const uint4*>(in + pos * 4));
-                const f16x8c al = __builtin_bit_cast(f16x8c, *reinterpret_cast<const uint4*>(in + plane + pos * 4));
+            for (int dy = 0; dy < kL0Ahead; ++dy) request(dy);
+#pragma unroll
+            for (int dy = 0; dy < 12; ++dy) {                            // (the scheduler otherwise sinks each request to just above its use)
+                if (dy + kL0Ahead < 12) request(dy + kL0Ahead);
+                __builtin_amdgcn_sched_barrier(0);
                 const f16x8c bh = __builtin_bit_cast(f16x8c, breg[dy]), bl = __builtin_bit_cast(f16x8c, bregl[dy]);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc, 0, 0, 0);
-                accl = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, accl, 0, 0, 0);
-                accl = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, accl, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[dy], bh, acc, 0, 0, 0);
+                accl = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[dy], bh, accl, 0, 0, 0);
+                accl = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[dy], bl, accl, 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
             }
             if (r16 < 8 && co < NF) {                                    // D[m = 4q + i][n = (tau, co)]
+                int pp = pe, jm = je;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const int mm = tile * 16 + 4 * q + i;
-                    const int pp = mm / J, t = 2 * (mm - pp * J) + tau;
-                    if (mm < M && t < T) {
+                    const int t = 2 * jm + tau;
+                    if (pp < 12 && t < T) {
                         float v = fmaf(fmaf(accl[i], kP2pLoInv, acc[i]), iscale, bias);
                         v = fmaxf(v, v * kSlope);
                         const _Float16 hv = static_cast<_Float16>(v);
                         out[(pp * RPp + 3 + t) * 4 + co] = __builtin_bit_cast(unsigned short, hv);
                         out[plane + (pp * RPp + 3 + t) * 4 + co] = static_cast<unsigned short>(f16_bits((v - static_cast<float>(hv)) * kP2pLoScale));
                         fmap[(co * 12 + pp) * RP + 3 + t] = v;
-                        if (write_dst) g[(static_cast<long long>(co) * 12 + pp) * T + t] = v;
+                        if (write_dst) g[(co * 12 + pp) * T + t] = v;
                     }
+                    l0_step(pp, jm, 0, 1, J);
                 }
             }
+            l0_step(pa, ja, sq_t, sr_t, J);
+            l0_step(pe, je, sq_t, sr_t, J);
         }
+        if (j + 1 < a.n_conv && a.frag_lds) __builtin_amdgcn_s_waitcnt(0x0F70);         // vmcnt(0): this wave's pieces of the next fragments have landed
         __syncthreads();
         const unsigned short* tmp = in;
         in = out;
@@ -2917,30 +3072,9 @@ __global__ __launch_bounds__(512) void layer0_mfma_kernel(Layer0Args a) {
     }
     // ---- layer 1's up_sixth + BN + LeakyReLU from the f32 map of the last conv ----
     if (a.psix_h) {          // ... as f16 x 4 per position (the pitch conv that reads it multiplies f16 anyway: the same values, rounded here)
-        typedef const float __attribute__((address_space(4))) cfloat;
-        cfloat* uw = (cfloat*)a.uw;
-        cfloat* ub = (cfloat*)a.ub;
         uint2* ph = a.psix_h + static_cast<long long>(clip) * 36 * T;
-        for (int i = tid; i < 12 * T; i += 512) {
-            const int p = i / T, t = i - p * T;
-            float x[4];
-#pragma unroll
-            for (int ci = 0; ci < 4; ++ci) x[ci] = fmap[(ci * 12 + p) * RP + 3 + t];
-#pragma unroll
-            for (int jj = 0; jj < 3; ++jj) {
-                unsigned int h[4];
-#pragma unroll
-                for (int co2 = 0; co2 < 4; ++co2) {
-                    float acc = co2 < NF ? ub[co2 < NF ? co2 : 0] : 0.f;
-#pragma unroll
-                    for (int ci = 0; ci < 4; ++ci)
-                        if (ci < NF && co2 < NF) acc = fmaf(x[ci], uw[(ci * NF + co2) * 3 + jj], acc);
-                    acc = acc > 0.f ? acc : acc * kSlope;
-                    h[co2] = __builtin_bit_cast(unsigned short, static_cast<_Float16>(acc));
-                }
-                ph[(3 * p + jj) * T + t] = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
-            }
-        }
+        if (NF == 4) l0_up_sixth_h<4>(a, fmap, ph, tid);
+        else l0_up_sixth_h<0>(a, fmap, ph, tid);
     } else if (a.psix) {
         typedef const float __attribute__((address_space(4))) cfloat;
         cfloat* uw = (cfloat*)a.uw;
