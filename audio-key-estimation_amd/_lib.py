@@ -41,6 +41,7 @@ SYMBOLS = {
     "ake_cqt_plan_n_bins": (_I, [_P]),
     "ake_cqt_plan_hop": (_I, [_P]),
     "ake_cqt_num_frames": (_I64, [_P, _I64]),
+    "ake_cqt_plan_half_support": (_I64, [_P]),
     "ake_cqt_workspace_bytes": (_SZ, [_P, _I, _I64]),
     "ake_cqt_logmag_f32": (_I, [_P, _P, _I, _I64, _I64, _P, _I64, _P, _SZ, _P]),
     "ake_cqt_logmag_ragged_f32": (_I, [_P, _P, _I, _I64, _I64, _P, _P, _I64, _P, _SZ, _P]),
@@ -100,6 +101,11 @@ SYMBOLS = {
     "ake_key_posteriors_workspace_bytes": (_SZ, [_I, _I]),
     "ake_key_posteriors_chunk_windows": (_I, []),
     "ake_key_posteriors_f32": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "ake_key_stream_state_bytes": (_SZ, [_I, _I]),
+    "ake_key_stream_step_f32": (_I, [_P, _I, _I, _I64, _I, _I, _P, _P, _P, _SZ, _P, _P, C.POINTER(_I), _P]),
+    "ake_stream_history_f32": (_I, [_P, _I, _I64, _I64, _I64, _P, _I64, _I64, _P]),
+    "ake_stream_history_pcm16": (_I, [_P, _I, _I64, _I64, _I64, _P, _I64, _I64, _P]),
+    "ake_stream_frames_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "ake_key_sequence_loss_workspace_bytes": (_SZ, [_I, _I]),
     "ake_key_sequence_loss_f32": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, C.c_float, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "ake_track_score_i32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),

@@ -1233,6 +1233,21 @@ int ake_cqt_plan_n_bins(const ake_cqt_plan* p) { return p ? p->cfg.n_bins : 0; }
 
 int ake_cqt_plan_hop(const ake_cqt_plan* p) { return p ? p->cfg.hop_length : 0; }
 
+// Frame t's bank of level l reads the level's samples c_int + u, c_int = (t * hop) >> l; its table holds zeros outside |u| <= uh (a zero
+// coefficient times a finite sample adds nothing), and the level's sample m stands at m << l, so the taps that count lie within
+// uh << l of c_int << l, which is at most 2^l - 1 in front of the centre.  A sample of level l is l half-band stages above the audio,
+// each half_len taps wide to either side on its own input grid: half_len * (2^l - 1) samples in all.  The cascade stores a level's
+// samples either exactly or not at all ("near the frame centres" covers every tap the bank reads), so that choice adds no slack.
+int64_t ake_cqt_plan_half_support(const ake_cqt_plan* p) {
+    if (!p) return -1;
+    int64_t h = 0;
+    for (int l = 0; l < p->n_oct; ++l) {
+        const int64_t grid = (1ll << l) - 1;
+        h = std::max<int64_t>(h, (static_cast<int64_t>(p->octs[l].uh) << l) + grid + p->half_len * grid);
+    }
+    return h;
+}
+
 int64_t ake_cqt_num_frames(const ake_cqt_plan* p, int64_t n_samples) {
     if (!p || n_samples < 0) return -1;
     return 1 + n_samples / p->cfg.hop_length;

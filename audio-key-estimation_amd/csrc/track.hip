@@ -22,6 +22,11 @@
 // are a forward-backward pass over the same emissions: key_forward_backward_kernel (the two serial chains, side by side) and
 // key_posteriors_kernel (everything per window), below the Viterbi kernel.
 //
+// A stream of audio is smoothed a call at a time by key_stream_step_kernel (ake_key_stream_step_f32): the Viterbi step and the forward
+// step on every new window, with d, a and a ring of the last `lag` back-pointer rows carried in device memory between calls, and a
+// fixed-lag path out of the ring.  The steps are device functions (viterbi_step, lse_step, states_lse, first_best_state) that the
+// Viterbi and the forward-backward kernel call too.  The stream's front end is csrc/stream.hip.
+//
 // A track is scored against key annotations by track_score_kernel (one launch, integers only), below the posterior kernels.
 //
 // Training on annotated recordings assembles its batches from the same cached transform: draw_windows_kernel (window positions from a
@@ -286,6 +291,35 @@ __device__ __forceinline__ float half_candidates(const float4* dsrc, const float
                  fmaxf(fmaxf(fmaxf(c[6], c[7]), c[8]), fmaxf(fmaxf(c[9], c[10]), c[11])));
 }
 
+// The Viterbi step of one wave (layout: viterbi_keys_kernel's comment): this lane's score d of the step before goes into the LDS row,
+// the lane's half of max_i (d[i] + A[i][j]) comes back and meets the other half.  Returns the maximum, `arg` the smallest i attaining
+// it.  Shared by viterbi_keys_kernel and key_stream_step_kernel.
+__device__ __forceinline__ float viterbi_step(float d, float4* d_lds, const float4* dsrc, const float (&A)[12], bool writer, int lane,
+                                              unsigned& arg) {
+    constexpr int kHalf = 12;
+    if (writer) reinterpret_cast<float*>(d_lds)[lane] = d;
+    __syncthreads();                                                     // (one wave: the wait for the LDS write, no more)
+    float c[kHalf];
+    const float mh = half_candidates(dsrc, A, c);
+    unsigned ah = 0;
+#pragma unroll
+    for (int i = kHalf - 1; i >= 0; --i) ah = c[i] == mh ? static_cast<unsigned>(i) : ah;        // ends on the smallest i
+    // v_permlane32_swap(x, x): the lower half's x in every lane of the first result, the upper half's in the second
+    const auto ms = __builtin_amdgcn_permlane32_swap(__float_as_uint(mh), __float_as_uint(mh), false, false);
+    const auto as = __builtin_amdgcn_permlane32_swap(ah, ah, false, false);
+    const float m_lo = __uint_as_float(ms[0]), m_hi = __uint_as_float(ms[1]);
+    const bool upper = m_hi > m_lo;                                      // strict: a tie goes to the smaller i
+    const float m = upper ? m_hi : m_lo;
+    arg = upper ? as[1] + kHalf : as[0];
+    return m;
+}
+
+// the smallest state attaining the maximum of the wave's scores (wave-uniform)
+__device__ __forceinline__ int first_best_state(float d, bool own, bool writer) {
+    const float mx = states_max(d, own);
+    return __ffsll(static_cast<unsigned long long>(__ballot(writer && d == mx))) - 1;
+}
+
 // One wave per recording.  A step is a latency chain on one wave, so what counts is its number of instructions:
 //   - lanes j and 32 + j (j < 24) share state j: the first takes the predecessors i = 0..11, the second i = 12..23, each with its half
 //     of column j of A in registers, so a lane adds, maximises (v_max3) and compare-selects over 12 candidates, not 24; the halves meet
@@ -331,22 +365,7 @@ __global__ __launch_bounds__(64) void viterbi_keys_kernel(VitArgs a) {
             if (w >= n) break;                                           // wave-uniform: all 64 lanes stay active for the cross-lane steps
             float m = d;                                                 // w == 0: the prior
             unsigned arg = 0;
-            if (w > 0) {
-                if (writer) reinterpret_cast<float*>(d_lds)[lane] = d;
-                __syncthreads();                                         // (one wave: the wait for the LDS write, no more)
-                float c[kHalf];
-                const float mh = half_candidates(dsrc, A, c);
-                unsigned ah = 0;
-#pragma unroll
-                for (int i = kHalf - 1; i >= 0; --i) ah = c[i] == mh ? static_cast<unsigned>(i) : ah;        // ends on the smallest i
-                // v_permlane32_swap(x, x): the lower half's x in every lane of the first result, the upper half's in the second
-                const auto ms = __builtin_amdgcn_permlane32_swap(__float_as_uint(mh), __float_as_uint(mh), false, false);
-                const auto as = __builtin_amdgcn_permlane32_swap(ah, ah, false, false);
-                const float m_lo = __uint_as_float(ms[0]), m_hi = __uint_as_float(ms[1]);
-                const bool upper = m_hi > m_lo;                          // strict: a tie goes to the smaller i
-                m = upper ? m_hi : m_lo;
-                arg = upper ? as[1] + kHalf : as[0];
-            }
+            if (w > 0) m = viterbi_step(d, d_lds, dsrc, A, writer, lane, arg);
             const float raw = m + eb[k];
             d = raw - states_max(raw, own);
             word |= arg << (8 * (k & 3));                                // (w0 is a multiple of 4, so w & 3 == k & 3)
@@ -363,10 +382,7 @@ __global__ __launch_bounds__(64) void viterbi_keys_kernel(VitArgs a) {
 
     // the last state: the smallest j attaining the maximum (0 after the normalisation, found the same way all the same)
     int cur = 0;
-    if (n > 0) {
-        const float mx = states_max(d, own);
-        cur = __ffsll(static_cast<unsigned long long>(__ballot(writer && d == mx))) - 1;
-    }
+    if (n > 0) cur = first_best_state(d, own, writer);
     int* const path = a.path + static_cast<size_t>(r) * W;
     const unsigned char* const bytes = reinterpret_cast<const unsigned char*>(bp_lds);
     for (int c0 = (W - 1) / kVitChunk * kVitChunk; c0 >= 0; c0 -= kVitChunk) {
@@ -420,6 +436,33 @@ __device__ __forceinline__ float states_sum(float x, bool valid) {
     return __int_as_float(__builtin_amdgcn_readlane(bits, 0)) + __int_as_float(__builtin_amdgcn_readlane(bits, 16));
 }
 
+// The forward-backward step of one wave (layout: forward_backward_chain's comment): this lane's score x (kAdd: x + e) goes into the
+// LDS row, the lane's half of LSE_i (row[i] + A[i]) comes back and meets the other half at their common maximum.  Shared by the two chains and
+// key_stream_step_kernel.
+template <bool kAdd>
+__device__ __forceinline__ float lse_step(float x, float e, float4* d_lds, const float4* dsrc, const float (&A)[12], bool writer, int lane) {
+    constexpr int kHalf = 12;
+    if (writer) reinterpret_cast<float*>(d_lds)[lane] = kAdd ? x + e : x;
+    __syncthreads();                                                     // (one wave: the wait for the LDS write, no more)
+    float c[kHalf];
+    const float mh = half_candidates(dsrc, A, c);
+    float sh = 0.f;
+#pragma unroll
+    for (int i = 0; i < kHalf; ++i) sh += __expf(c[i] - mh);
+    const auto ms = __builtin_amdgcn_permlane32_swap(__float_as_uint(mh), __float_as_uint(mh), false, false);
+    const auto ss = __builtin_amdgcn_permlane32_swap(__float_as_uint(sh), __float_as_uint(sh), false, false);
+    const float m_lo = __uint_as_float(ms[0]), m_hi = __uint_as_float(ms[1]);
+    const float m = fmaxf(m_lo, m_hi);
+    const float s = __uint_as_float(ss[0]) * __expf(m_lo - m) + __uint_as_float(ss[1]) * __expf(m_hi - m);
+    return m + __logf(s);
+}
+
+// c = LSE over the states of a step's raw scores (what the step subtracts)
+__device__ __forceinline__ float states_lse(float raw, bool own) {
+    const float mx = states_max(raw, own);
+    return mx + __logf(states_sum(__expf(raw - mx), own));
+}
+
 // One direction of one recording on one wave, the Viterbi step's layout with log-sum-exp in the place of max: lanes j and 32 + j share
 // state j with 12 of the 24 terms each, the step's 24 scores travel through the 96-byte LDS row, v_permlane32_swap joins the halves (the
 // two partial sums meet at their common maximum), emission rows are loaded kVitBatch steps ahead with clamped indices.
@@ -461,24 +504,11 @@ __device__ __forceinline__ void forward_backward_chain(const FbArgs& a, float4* 
             if (t >= n) break;                                           // wave-uniform
             float raw = kBack ? 0.f : d + eb[k];                         // t == 0: b_{n-1} = 0, a_0 = prior + e[0]
             if (t > 0) {
-                if (writer) reinterpret_cast<float*>(d_lds)[lane] = kBack ? d + eb[k] : d;
-                __syncthreads();                                         // (one wave: the wait for the LDS write, no more)
-                float c[kHalf];
-                const float mh = half_candidates(dsrc, A, c);
-                float sh = 0.f;
-#pragma unroll
-                for (int i = 0; i < kHalf; ++i) sh += __expf(c[i] - mh);
-                const auto ms = __builtin_amdgcn_permlane32_swap(__float_as_uint(mh), __float_as_uint(mh), false, false);
-                const auto ss = __builtin_amdgcn_permlane32_swap(__float_as_uint(sh), __float_as_uint(sh), false, false);
-                const float m_lo = __uint_as_float(ms[0]), m_hi = __uint_as_float(ms[1]);
-                const float m = fmaxf(m_lo, m_hi);
-                const float s = __uint_as_float(ss[0]) * __expf(m_lo - m) + __uint_as_float(ss[1]) * __expf(m_hi - m);
-                const float lse = m + __logf(s);
+                const float lse = lse_step<kBack>(d, eb[k], d_lds, dsrc, A, writer, lane);
                 raw = kBack ? lse : lse + eb[k];
             }
             if (!kBack || t > 0) {                                       // b_{n-1} stays 0, unnormalised
-                const float mx = states_max(raw, own);
-                const float cw = mx + __logf(states_sum(__expf(raw - mx), own));
+                const float cw = states_lse(raw, own);
                 d = raw - cw;
                 ll += static_cast<double>(cw);
             } else {
@@ -497,6 +527,131 @@ __global__ __launch_bounds__(64) void key_forward_backward_kernel(FbArgs a) {
     __shared__ float4 d_lds[kKeys / 4];
     if (blockIdx.y == 0) forward_backward_chain<false>(a, d_lds);
     else forward_backward_chain<true>(a, d_lds);
+}
+
+// ---- the smoother with carried state: a stream's new windows, a call at a time (semantics: include/ake_hip.h; host model: metrics.key_stream) ----
+constexpr int kStreamMaxLag = 255;
+constexpr int kStreamScores = 2 * kKeys * static_cast<int>(sizeof(float));    // bytes of d[24], a[24] in front of a recording's ring
+
+// bytes of one recording's state: d[24], a[24], then the ring of the last `lag` back-pointer rows (24 bytes each), in 16-byte pieces
+constexpr size_t stream_state_stride(int lag) { return static_cast<size_t>(kStreamScores + (kKeys * lag + 15) / 16 * 16); }
+
+struct StreamStepArgs {
+    const float* emis;         // [recordings][k][24]
+    const float* trans;        // [24][24], from i (row) to j
+    const float* prior;        // [24], nullable = zeros
+    unsigned char* state;      // [recordings][stream_state_stride(lag)]
+    float* filtered;           // [recordings][k][24], nullable
+    int* path;                 // [recordings][k_out]
+    long long before;          // windows of the stream before this call
+    int k, lag, flush, k_out;
+    int slot0;                 // before % lag (0 for lag 0): the ring row of the call's first window
+};
+
+// One wave per recording, in viterbi_keys_kernel's layout, both recurrences side by side on every new window: the Viterbi step
+// (viterbi_step; its back-pointers go into a ring of `lag` rows in LDS, row w % lag for window w) and the forward step (lse_step,
+// states_lse; the normalised row is `filtered`).  After the step of window w >= lag the wave follows `lag` back-pointers from the first
+// maximum of d_w and writes the label of window w - lag; a flush writes the windows still inside the lag from the last best state.
+// d, a and the ring come from `state` once, in front of the first step (not at all on a fresh stream, before == 0), and go back once,
+// behind the last.  Emission rows are loaded kVitBatch steps ahead, with clamped indices.
+__global__ __launch_bounds__(64) void key_stream_step_kernel(StreamStepArgs a) {
+    __shared__ uint4 ring_lds[(kStreamMaxLag * kKeys + 15) / 16];
+    __shared__ float4 d_lds[kKeys / 4], f_lds[kKeys / 4];
+    const int r = blockIdx.x, lane = threadIdx.x, k = a.k, lag = a.lag;
+    constexpr int kHalf = kKeys / 2;
+    const int half = lane >> 5;
+    const bool own = (lane & 31) < kKeys, writer = lane < kKeys;
+    const int j = own ? lane & 31 : 0;
+    float A[kHalf];
+#pragma unroll
+    for (int i = 0; i < kHalf; ++i) A[i] = a.trans[(half * kHalf + i) * kKeys + j];
+    const float4* const dsrc = d_lds + half * (kHalf / 4);
+    const float4* const fsrc = f_lds + half * (kHalf / 4);
+    unsigned char* const ring = reinterpret_cast<unsigned char*>(ring_lds);
+    unsigned char* const st = a.state + static_cast<size_t>(r) * stream_state_stride(lag);
+    const int ring_quads = (kKeys * lag + 15) / 16;
+    const float prior = a.prior ? a.prior[j] : 0.f;
+    float d = prior, f = prior;                                          // window 0 adds its emissions to the prior
+    if (a.before > 0) {
+        d = reinterpret_cast<const float*>(st)[j];
+        f = reinterpret_cast<const float*>(st)[kKeys + j];
+        for (int x = lane; x < ring_quads; x += 64) ring_lds[x] = reinterpret_cast<const uint4*>(st + kStreamScores)[x];
+    } else {
+        for (int x = lane; x < ring_quads; x += 64) ring_lds[x] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    __syncthreads();
+    const long long first_out = a.before > lag ? a.before - lag : 0;    // the window path[0] belongs to
+    int* const path = a.path + static_cast<size_t>(r) * a.k_out;
+    int slot = a.slot0;                                                  // ring row of the window being stepped
+    if (k > 0) {
+        const float* const e = a.emis + static_cast<size_t>(r) * k * kKeys + j;
+        float* const out = a.filtered ? a.filtered + static_cast<size_t>(r) * k * kKeys + j : nullptr;
+        const int wl = k - 1;
+        float eb[kVitBatch];
+#pragma unroll
+        for (int q = 0; q < kVitBatch; ++q) eb[q] = e[static_cast<size_t>(q < wl ? q : wl) * kKeys];
+        for (int i0 = 0; i0 < k; i0 += kVitBatch) {
+            float en[kVitBatch];
+#pragma unroll
+            for (int q = 0; q < kVitBatch; ++q) {
+                const int i = i0 + kVitBatch + q;
+                en[q] = e[static_cast<size_t>(i < wl ? i : wl) * kKeys];
+            }
+#pragma unroll
+            for (int q = 0; q < kVitBatch; ++q) {
+                const int i = i0 + q;
+                if (i >= k) break;                                       // wave-uniform
+                const long long w = a.before + i;
+                float m = d, fr = f;
+                unsigned arg = 0;
+                if (w > 0) {
+                    m = viterbi_step(d, d_lds, dsrc, A, writer, lane, arg);
+                    fr = lse_step<false>(f, 0.f, f_lds, fsrc, A, writer, lane);
+                }
+                const float raw = m + eb[q];
+                d = raw - states_max(raw, own);
+                const float fraw = fr + eb[q];
+                f = fraw - states_lse(fraw, own);
+                if (out && writer) out[static_cast<size_t>(i) * kKeys] = f;
+                if (lag > 0 && writer) ring[slot * kKeys + lane] = static_cast<unsigned char>(arg);
+                if (w >= lag) {
+                    int cur = first_best_state(d, own, writer);
+                    if (lag > 0) {
+                        __syncthreads();                                 // the row just written, before any lane reads it
+                        int s = slot;
+                        for (int b = 0; b < lag; ++b) {                  // a chain of LDS reads; cur is wave-uniform
+                            cur = ring[s * kKeys + cur];
+                            s = s == 0 ? lag - 1 : s - 1;
+                        }
+                    }
+                    if (lane == 0) path[w - lag - first_out] = cur;
+                }
+                slot = slot + 1 == lag ? 0 : slot + 1;
+            }
+#pragma unroll
+            for (int q = 0; q < kVitBatch; ++q) eb[q] = en[q];
+        }
+    }
+    const long long total = a.before + k;
+    if (a.flush && total > 0) {                                          // the windows still inside the lag, from the last best state
+        int cur = first_best_state(d, own, writer);
+        __syncthreads();
+        const long long v_min = total > lag ? total - lag : 0;
+        int s = slot == 0 ? (lag > 0 ? lag - 1 : 0) : slot - 1;          // the ring row of window total - 1
+        for (long long v = total - 1; v >= v_min; --v) {
+            if (lane == 0) path[v - first_out] = cur;
+            if (v > v_min) {
+                cur = ring[s * kKeys + cur];
+                s = s == 0 ? lag - 1 : s - 1;
+            }
+        }
+    }
+    __syncthreads();
+    if (writer) {
+        reinterpret_cast<float*>(st)[lane] = d;
+        reinterpret_cast<float*>(st)[kKeys + lane] = f;
+    }
+    for (int x = lane; x < ring_quads; x += 64) reinterpret_cast<uint4*>(st + kStreamScores)[x] = ring_lds[x];
 }
 
 struct PostArgs {
@@ -1322,6 +1477,40 @@ int ake_key_posteriors_f32(const float* emis_dev, int recordings, int windows, c
     if (xi_sum_dev) {
         ake::ProfScope ps("key_xi_reduce_kernel", s);
         hipLaunchKernelGGL(key_xi_reduce_kernel, dim3(recordings), dim3(192), 0, s, pc.part, xi_sum_dev, pc.chunks);
+    }
+    AKE_HIP_CHECK(hipGetLastError());
+    return AKE_OK;
+}
+
+size_t ake_key_stream_state_bytes(int recordings, int lag) {
+    if (recordings <= 0 || lag < 0 || lag > kStreamMaxLag) return 0;
+    return static_cast<size_t>(recordings) * stream_state_stride(lag);
+}
+
+int ake_key_stream_step_f32(const float* emis_dev, int recordings, int k, int64_t windows_before, int lag, int flush,
+                            const float* log_trans_dev, const float* log_prior_dev, void* state_dev, size_t state_bytes, float* filtered_dev,
+                            int32_t* path_dev, int* k_out, ake_stream_t stream) {
+    AKE_REQUIRE(lag >= 0 && lag <= kStreamMaxLag, AKE_ERR_INVALID, "key_stream_step: lag %d outside 0..%d", lag, kStreamMaxLag);
+    AKE_REQUIRE(recordings > 0 && k >= 0 && windows_before >= 0 && static_cast<long long>(recordings) * k <= (1ll << 30), AKE_ERR_INVALID,
+                "key_stream_step: bad shape (%d recordings, %d windows after %lld)", recordings, k, static_cast<long long>(windows_before));
+    AKE_REQUIRE(log_trans_dev && state_dev && k_out, AKE_ERR_INVALID, "key_stream_step: null argument");
+    // the count, on the host: window v leaves the lag once window v + lag has been stepped, a flush writes every window that is left
+    const int64_t first = windows_before > lag ? windows_before - lag : 0, total = windows_before + k;
+    const int64_t n_out = (flush ? total : (total > lag ? total - lag : 0)) - first;
+    AKE_REQUIRE(n_out <= INT_MAX, AKE_ERR_INVALID, "key_stream_step: %lld windows to write", static_cast<long long>(n_out));
+    AKE_REQUIRE((k == 0 || emis_dev) && (n_out == 0 || path_dev), AKE_ERR_INVALID, "key_stream_step: null argument");
+    const size_t need = ake_key_stream_state_bytes(recordings, lag);
+    AKE_REQUIRE(state_bytes >= need, AKE_ERR_WORKSPACE, "key_stream_step: state %zu < %zu bytes", state_bytes, need);
+    AKE_REQUIRE((reinterpret_cast<uintptr_t>(state_dev) & 15) == 0, AKE_ERR_INVALID, "key_stream_step: the state must be 16-byte aligned");
+    *k_out = static_cast<int>(n_out);
+    if (k == 0 && n_out == 0) return AKE_OK;                             // nothing to step and nothing to flush
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    StreamStepArgs a{emis_dev, log_trans_dev, log_prior_dev, static_cast<unsigned char*>(state_dev), filtered_dev, path_dev,
+                     static_cast<long long>(windows_before), k, lag, flush ? 1 : 0, static_cast<int>(n_out),
+                     lag > 0 ? static_cast<int>(windows_before % lag) : 0};
+    {
+        ake::ProfScope ps("key_stream_step_kernel", s);
+        hipLaunchKernelGGL(key_stream_step_kernel, dim3(recordings), dim3(64), 0, s, a);
     }
     AKE_HIP_CHECK(hipGetLastError());
     return AKE_OK;

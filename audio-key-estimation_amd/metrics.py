@@ -42,6 +42,24 @@ _PITCH_NAMES = ("C", "Db", "D", "Eb", "E", "F", "Gb", "G", "Ab", "A", "Bb", "B")
 KEY_NAMES = tuple(f"{n} minor" for n in _PITCH_NAMES) + tuple(f"{n} major" for n in _PITCH_NAMES)
 
 
+def _fma(x, y, z):
+    """x * y + z rounded once, as a fused multiply-add rounds it.  float32: the product is exact in float64, the sum's rounding error is
+    recovered (TwoSum), and where the float64 sum sits exactly halfway between two float32 values that error decides the direction,
+    not the tie rule.  Other dtypes: x * y + z (float64 is the model's own precision)."""
+    if x.dtype != torch.float32:
+        return x * y + z
+    a, q = x.double() * y.double(), z.double()
+    s = a + q
+    bb = s - a
+    err = (a - (s - bb)) + (q - bb)
+    r = s.float()
+    other = torch.nextafter(r, torch.where(s > r.double(), torch.full_like(r, float("inf")), torch.full_like(r, float("-inf"))))
+    halfway = (s - r.double()) == (other.double() - s)
+    up, down = torch.nextafter(s, torch.full_like(s, float("inf"))), torch.nextafter(s, torch.full_like(s, float("-inf")))
+    s = torch.where(halfway & (err > 0), up, torch.where(halfway & (err < 0), down, s))
+    return s.float()
+
+
 def decode_keys(key, tonic):
     """(..., 12) key outputs (sigmoid) and (..., 12) tonic logits -> (key_id, sig, tonic_id, confidence), shaped like the leading dims.
 
@@ -49,16 +67,29 @@ def decode_keys(key, tonic):
     cosine match over ``KEY_SIGNATURE_MAP`` with ``mirex_score``'s arithmetic and tie rule, ``confidence`` that cosine, ``tonic_id``
     (0..11) the first maximum of the tonic logits, and ``key_id`` the 24-way label (``KEY_NAMES``): ``12 + tonic_id`` if the tonic is the
     major tonic of row ``sig``, ``tonic_id`` if it is that tonic + 9 mod 12 (the relative minor), -1 if signature and tonic disagree.
-    ``key_id``, ``sig`` and ``tonic_id`` are int32."""
+    ``key_id``, ``sig`` and ``tonic_id`` are int32.  On float32 inputs the sums run in the kernel's own order and every root and quotient is
+    rounded once, so ``confidence`` equals the kernel's to the bit, on the CPU and on the device alike; float64 inputs give the model."""
     lead = key.shape[:-1]
     k2, t2 = key.reshape(-1, 12), tonic.reshape(-1, 12)
     # the cosines as sums over the 12 pitch classes in one order for every table row, so that the duplicate rows (0/12, 1/13, ...) get
     # bit-identical values and the first of them wins (a matmul may block the 21 columns differently and break such ties either way)
+    # -- and in the kernel's own order, so that float32 inputs give the kernel's confidence to the bit.  Additions and products round alike
+    # everywhere; the square roots and the quotient are taken in float64 and rounded once, which is the correctly rounded float32 result
+    # (53 >= 2 * 24 + 2 bits).  |p|^2 as decode_keys_kernel's build takes it: the first two squares meet in one fused multiply-add,
+    # fma(p_0, p_0, p_1 * p_1), the other ten are rounded and added in turn; a dot product is the sum of its row's members in turn.
     table = _device_table(k2.device, k2.dtype)
     eps = 1e-8
-    pn = k2.norm(dim=1, keepdim=True).clamp_min(eps)
-    tn = table.norm(dim=1, keepdim=True).clamp_min(eps)
-    sims = (k2[:, None, :] * table[None, :, :]).sum(dim=2) / (pn * tn.T)     # (B, 21)
+    wide = torch.float64 if k2.dtype == torch.float32 else k2.dtype
+    col = lambda j: k2[:, j:j + 1]
+    pp = _fma(col(0), col(0), col(1) * col(1))
+    dot = k2.new_zeros((k2.shape[0], table.shape[0]))
+    for j in range(12):
+        if j >= 2:
+            pp = pp + col(j) * col(j)
+        dot = dot + col(j) * table[None, :, j]
+    pn = pp.to(wide).sqrt().to(k2.dtype).clamp_min(eps)
+    tn = table.to(wide).square().sum(dim=1, keepdim=True).sqrt().to(k2.dtype).clamp_min(eps)      # (sqrt(7): the sum is exact)
+    sims = (dot.to(wide) / (pn * tn.T).to(wide)).to(k2.dtype)                  # (B, 21)
     conf = sims.max(dim=1).values
     idx21 = torch.arange(table.shape[0], device=k2.device)[None, :].expand_as(sims)
     sig = torch.where(sims == conf[:, None], idx21, torch.full_like(idx21, table.shape[0])).min(dim=1).values
@@ -300,6 +331,98 @@ def key_posteriors(emissions, log_trans, log_prior=None, counts=None, transition
         xi = torch.softmax(x.reshape(R, w1 - w0, K * K), dim=2).reshape(R, w1 - w0, K, K)
         xi_sum += torch.where(live[:, w0:w1, None, None], xi, torch.zeros_like(xi)).sum(dim=1)
     return post, loglik, (xi_sum[0] if single else xi_sum)
+
+
+# ---- a smoother that carries its state: the filtered scores and a fixed-lag path, window by window (ake_key_stream_step_f32) ----
+
+def key_stream_count(windows_before, k, lag, flush):
+    """Windows whose fixed-lag label a step over ``k`` new windows writes, after ``windows_before`` earlier ones -> ``(first, k_out)``:
+    window v leaves the lag once window v + lag has been stepped, and a flush writes every window that is left."""
+    windows_before, k, lag = int(windows_before), int(k), int(lag)
+    first = max(0, windows_before - lag)
+    total = windows_before + k
+    return first, (total if flush else max(0, total - lag)) - first
+
+
+def key_stream(emissions, log_trans, log_prior=None, lag=6, state=None, flush=True, return_state=False):
+    """Filtered key scores and the fixed-lag Viterbi path of (R, W, 24) or (W, 24) ``emissions`` -> ``(filtered, path)``.
+
+    The host model of ``ake_key_stream_step_f32``, in torch ops, in the emissions' dtype.  ``log_trans`` and ``log_prior`` as in
+    ``viterbi_keys``, all finite; ``lag`` 0..255.
+
+    ``filtered[w]`` is ``key_posteriors``' normalised forward row a_w (the same recurrence, c_w subtracted at every step, w = 0 included):
+    ``exp`` of it is the probability of each key given the windows up to w.  ``path[v]`` is ``viterbi_keys(e[:v + lag + 1])[v]``: the
+    label window v gets once ``lag`` more windows have been seen -- the Viterbi step of ``viterbi_keys``, operation for operation, then
+    ``lag`` back-pointers followed from the first maximum of d_{v + lag}.  With ``flush`` (the recording ends here) the last ``lag``
+    windows get ``viterbi_keys(e)[v]``.  One forward sweep; the back-pointers of the last ``lag`` windows live in a ring.
+
+    In pieces: ``state`` is what an earlier call returned with ``return_state=True`` (the call then returns ``(filtered, path, state)``),
+    and ``flush=False`` leaves the last ``lag`` windows to a later call.  ``path`` then holds the ``key_stream_count`` windows this call
+    decides, in order, int32 (R, k_out); the results do not depend on how the windows are cut into calls, to the bit."""
+    single = emissions.dim() == 2
+    e = emissions[None] if single else emissions
+    if e.dim() != 3 or e.shape[2] != 24:
+        raise ValueError(f"key_stream: emissions must be (R, W, 24) or (W, 24), got {tuple(emissions.shape)}")
+    lag = int(lag)
+    if not 0 <= lag <= 255:
+        raise ValueError(f"key_stream: lag must lie in 0..255, got {lag}")
+    R, W, K = e.shape
+    dev = e.device
+    A = torch.as_tensor(log_trans).to(device=dev, dtype=e.dtype)
+    if A.shape != (K, K):
+        raise ValueError(f"key_stream: log_trans must be (24, 24), got {tuple(A.shape)}")
+    prior = torch.zeros(K, device=dev, dtype=e.dtype) if log_prior is None else torch.as_tensor(log_prior).to(device=dev, dtype=e.dtype).reshape(K)
+    _check_finite("log_trans", A)
+    _check_finite("log_prior", prior)
+    _check_finite("emissions", e)
+    idx = torch.arange(K, device=dev)
+    none = torch.full((), K, device=dev, dtype=torch.int64)
+    if state is None:
+        before = 0
+        d, a = e.new_zeros((R, K)), e.new_zeros((R, K))
+        ring = torch.zeros((max(lag, 1), R, K), device=dev, dtype=torch.int64)       # row w % lag: bp_w
+    else:
+        before, d, a, ring = state["windows"], state["d"].clone(), state["a"].clone(), state["ring"].clone()
+    first_out, k_out = key_stream_count(before, W, lag, flush)
+    filtered = e.new_zeros((R, W, K))
+    path = torch.full((R, k_out), -1, device=dev, dtype=torch.int64)
+
+    def first_max(x):
+        return torch.where(x == x.max(dim=1, keepdim=True).values, idx[None, :], none).min(dim=1).values
+
+    for i in range(W):
+        w = before + i
+        if w == 0:
+            raw = prior[None, :] + e[:, 0]
+            fraw = prior[None, :] + e[:, 0]
+        else:
+            cand = d[:, :, None] + A[None, :, :]                                    # (R, from i, to j)
+            m = cand.max(dim=1).values
+            if lag:
+                ring[w % lag] = torch.where(cand == m[:, None, :], idx[None, :, None], none).min(dim=1).values
+            raw = m + e[:, i]
+            fraw = e[:, i] + torch.logsumexp(a[:, :, None] + A[None, :, :], dim=1)
+        d = raw - raw.max(dim=1, keepdim=True).values
+        a = fraw - torch.logsumexp(fraw, dim=1, keepdim=True)
+        filtered[:, i] = a
+        if w >= lag:
+            cur = first_max(d)
+            for back in range(lag):
+                cur = ring[(w - back) % lag].gather(1, cur[:, None])[:, 0]
+            path[:, w - lag - first_out] = cur
+    total = before + W
+    if flush and total > 0:
+        cur = first_max(d)
+        for v in range(total - 1, max(0, total - lag) - 1, -1):
+            path[:, v - first_out] = cur
+            if v > max(0, total - lag):
+                cur = ring[v % lag].gather(1, cur[:, None])[:, 0]
+    path = path.to(torch.int32)
+    if single:
+        filtered, path = filtered[0], path[0]
+    if return_state:
+        return filtered, path, {"windows": total, "d": d, "a": a, "ring": ring}
+    return filtered, path
 
 
 def _transposition_classes():

@@ -530,6 +530,46 @@ class KeyEstimator:
             return track
         return self._issue(run, audio, lengths)
 
+    def stream(self, recordings: int, window_seconds: float = 15.0, stride_seconds: float = 5.0, smooth: bool = True, lag_windows: int = 6,
+               mean_key_seconds: float = 60.0, transition: torch.Tensor | None = None, log_prior: torch.Tensor | None = None,
+               signature_weight: float = 1.0, keep_frames: bool = False, max_chunk_samples: int | None = None, rate: int | None = None,
+               tuning=None):
+        """Track keys on audio as it arrives -> ``ake_amd.KeyStream``: ``push(chunk)`` takes the next (R, m) samples of all
+        ``recordings`` = R recordings at once (float32, or int16 = 16-bit PCM; any m >= 0, the same m for every recording) and returns
+        a ``StreamUpdate`` with the windows that chunk completed; ``finish()`` ends the recordings and returns the rest.
+
+        The windows are ``track``'s (``window_seconds``, ``stride_seconds``), each emitted exactly once, in order, as soon as all its
+        frames are final: a frame of the transform depends on ``H`` = ``ake_cqt_plan_half_support`` samples to either side, so frame
+        t is final once sample ``t*hop + H`` has arrived (just under 1 s behind the audio with the default plan), and at ``finish()``
+        all ``1 + N // hop`` frames are.  After ``finish()`` on N samples the stream has emitted the windows ``track`` gives for them.
+        New frames come from re-transforming the last ``2*H + hop`` samples and the chunk with the offline transform; they equal
+        ``track``'s frames to the transform's accuracy, not to the bit (``ake_amd.stream``).  Nothing is read back from the device and
+        a push waits for nothing; it runs on the current stream (the estimator's side streams are not used), and after the first push
+        it allocates only the tensors it returns -- everything else is sized here, for chunks of up to ``max_chunk_samples`` (default
+        10 s; a longer chunk is pushed as several pieces).
+
+        ``smooth=True`` (default) adds, per window, ``emissions`` (``metrics.key_emissions`` with ``signature_weight``), ``filtered``
+        (the normalised log forward scores: the probability of each key given the audio so far) and the fixed-lag path
+        ``smooth_key_id``: window v gets its label once ``lag_windows`` more windows have been seen -- the label
+        ``metrics.viterbi_keys`` gives it on the windows up to ``v + lag_windows`` -- and never changes afterwards; ``finish()``
+        labels the last ``lag_windows`` windows with the Viterbi path of the whole recording (``metrics.key_stream``).
+        ``lag_windows`` 0..255; 6 is an unmeasured starting value (``profiles/track_stream.md``).  ``transition`` and
+        ``mean_key_seconds`` as in ``track``; ``log_prior`` (24,), default zeros.  ``keep_frames=True`` keeps every final frame in
+        ``KeyStream.frames`` (R, P, T), for tests and debugging.
+
+        Refused with a ``ValueError``: what ``track`` refuses (``frames=0``, ``wrap_mode="true_end"``, ``--local`` nets), an estimator
+        without a net, ``rate`` other than the estimator's and multi-channel chunks (the resampler keeps no state across chunks),
+        ``tuning``, ``lag_windows`` outside 0..255; by ``push``: a chunk after ``finish()``, a chunk whose R or dtype differs from
+        the first.  ``method="profile"`` streams do not exist."""
+        from .stream import KeyStream
+        if rate is not None and int(rate) != self.sample_rate:
+            raise ValueError(f"stream: chunks must be at the estimator's rate ({self.sample_rate} Hz): the resampler keeps no state across "
+                             "chunks, so a stream does not convert rates or channels")
+        if tuning is not None:
+            raise ValueError("stream: tuning is not offered inside a stream (the estimate needs the whole recording)")
+        return KeyStream(self, recordings, window_seconds, stride_seconds, smooth, lag_windows, mean_key_seconds, transition, log_prior,
+                         signature_weight, keep_frames, max_chunk_samples)
+
     def _refuse_untrackable(self):
         """What ``track`` and ``training_windows`` cannot slide windows over."""
         if self.frames <= 0:

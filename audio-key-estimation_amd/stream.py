@@ -1,0 +1,291 @@
+"""Key tracking on audio as it arrives: ``KeyEstimator.stream`` -> ``KeyStream``.
+
+A stream takes the audio of R recordings in chunks, all R in lockstep, and emits ``KeyEstimator.track``'s windows exactly once each, as
+soon as every frame of a window is final; a smoother with carried state (``ake_key_stream_step_f32``, host model
+``metrics.key_stream``) adds the filtered key scores and a fixed-lag Viterbi path.  Every count is known on the host from the number of
+samples pushed: a push reads nothing back from the device and waits for nothing.
+
+The geometry, as pure host functions (``H`` = ``ake_cqt_plan_half_support``: frame t depends on samples ``[t*hop - H, t*hop + H]``):
+
+- ``final_frames``: with N samples received, frame t is final iff ``t*hop + H <= N - 1``; at the end all ``1 + N // hop`` frames are.
+- ``windows_ready``: ``track_counts`` of the final frames -- window w covers frames ``[w*sf, w*sf + wf)``.
+- ``transform_start``: new final frames come from re-transforming ``[s0, N)`` of a float32 audio history with the offline entry
+  points; ``s0`` is the largest multiple of ``hop`` at or below ``first_needed_frame*hop - H`` (0 at the start of the stream, whose
+  frames then see the zeros in front of sample 0 that ``track``'s see).  ``s0`` is NOT held to a multiple of ``2**(octaves - 1)``: that
+  would make the decimation grids of the streamed and the offline transform coincide, but with hop 4410 the two conditions meet only
+  every 64 hops (12.8 s), which a push would have to re-transform.  Streamed frames therefore equal offline frames to the transform's
+  own accuracy (its float64 oracle bound), not to the bit; ``profiles/track_stream.md`` has the measured difference.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import ctypes as C
+
+import torch
+
+from . import _lib, metrics
+from .pipeline import track_counts, track_stride_frames, track_window_frames
+
+
+def final_frames(n_samples: int, hop: int, half_support: int, finished: bool = False) -> int:
+    """Frames of the transform that are final after ``n_samples`` samples: frame t is final iff ``t*hop + H <= n_samples - 1``; at the
+    end of the recording (``finished``) all ``1 + n_samples // hop`` are, seeing zeros behind the end as ``track``'s frames do."""
+    n_samples, hop, half_support = int(n_samples), int(hop), int(half_support)
+    if finished:
+        return 1 + n_samples // hop
+    return 0 if n_samples - 1 - half_support < 0 else (n_samples - 1 - half_support) // hop + 1
+
+
+def windows_ready(frames: int, window_frames: int, stride_frames: int) -> int:
+    """Windows all of whose frames lie among the first ``frames`` final frames (``track_counts``)."""
+    return track_counts(int(frames), int(window_frames), int(stride_frames))
+
+
+def transform_start(first_frame: int, hop: int, half_support: int) -> int:
+    """``s0``: the sample a re-transform starts at so that frame ``first_frame`` and everything behind it see their whole support --
+    the largest multiple of ``hop`` at or below ``first_frame*hop - H``, never below 0."""
+    first_frame, hop, half_support = int(first_frame), int(hop), int(half_support)
+    return max(0, (first_frame * hop - half_support) // hop) * hop
+
+
+smooth_count = metrics.key_stream_count      # (windows_before, k, lag, flush) -> (first smoothed window, k_out)
+
+
+@dataclass
+class StreamUpdate:
+    """What one ``KeyStream.push`` (or ``finish``) emits: ``windows`` = k new windows from ``first_window`` on.
+
+    ``key`` (R, k, 12), ``tonic`` (R, k, 12), ``genre`` (R, k, 11) or None, ``key_id``, ``signature_id``, ``tonic_id`` int32 (R, k) and
+    ``confidence`` (R, k): as ``KeyTrack`` names them (``signature_id`` is ``KeyTrack.sig``).  ``times`` (k,) float64 on the host: window
+    centres in seconds, as ``KeyTrack.times``.  A smooth stream adds ``emissions`` (R, k, 24), ``filtered`` (R, k, 24) -- the normalised
+    log forward scores: ``exp`` is the probability of each key given the audio so far -- and the fixed-lag path ``smooth_key_id`` int32
+    (R, k2) for the k2 windows from ``smooth_first_window`` on that have left the lag; None on a stream without a smoother."""
+    first_window: int
+    windows: int
+    key: torch.Tensor
+    tonic: torch.Tensor
+    genre: torch.Tensor | None
+    key_id: torch.Tensor
+    signature_id: torch.Tensor
+    tonic_id: torch.Tensor
+    confidence: torch.Tensor
+    times: torch.Tensor
+    emissions: torch.Tensor | None = None
+    filtered: torch.Tensor | None = None
+    smooth_first_window: int | None = None
+    smooth_key_id: torch.Tensor | None = None
+
+    @staticmethod
+    def concat(parts):
+        """One update out of the consecutive updates of a push that was cut into pieces."""
+        if len(parts) == 1:
+            return parts[0]
+        cat = lambda name: None if getattr(parts[0], name) is None else torch.cat([getattr(p, name) for p in parts], dim=1)
+        return StreamUpdate(parts[0].first_window, sum(p.windows for p in parts), cat("key"), cat("tonic"), cat("genre"), cat("key_id"),
+                            cat("signature_id"), cat("tonic_id"), cat("confidence"), torch.cat([p.times for p in parts]), cat("emissions"),
+                            cat("filtered"), parts[0].smooth_first_window, cat("smooth_key_id"))
+
+
+class KeyStream:
+    """``KeyEstimator.stream(...)``: see there.  ``push(chunk)`` and ``finish()`` return a ``StreamUpdate``.
+
+    Everything a push needs between calls is sized here, from R, the window geometry, ``lag_windows`` and ``max_chunk_samples``: the
+    audio history (float32, ``2*H + hop + max_chunk_samples`` samples a recording), the transform's output and workspace, the two
+    halves of the frame cache, the net's workspace and the smoother's state.  After the first push a push allocates only the tensors
+    it returns (a chunk longer than ``max_chunk_samples`` is pushed as several pieces, whose updates are joined by one ``torch.cat``
+    each).  ``push`` runs on the current stream."""
+
+    def __init__(self, est, recordings, window_seconds=15.0, stride_seconds=5.0, smooth=True, lag_windows=6, mean_key_seconds=60.0,
+                 transition=None, log_prior=None, signature_weight=1.0, keep_frames=False, max_chunk_samples=None):
+        R = int(recordings)
+        if R < 1:
+            raise ValueError("stream: recordings must be at least 1")
+        lag = int(lag_windows)
+        if not 0 <= lag <= 255:
+            raise ValueError(f"stream: lag_windows must lie in 0..255, got {lag_windows}")
+        est._need_net("KeyEstimator.stream")
+        est._refuse_untrackable()
+        self.est, self.R, self.lag, self.smooth = est, R, lag, bool(smooth)
+        dev = self.device = est.device
+        L = _lib.lib()
+        plan, net = est.plan, est.net
+        net._sync_weights(dev, for_eval=True)
+        hop = self.hop = int(plan.hop_length)
+        self.wf = track_window_frames(int(round(window_seconds * est.sample_rate)), hop)
+        self.sf = track_stride_frames(stride_seconds, est.frames)
+        self.H = int(L.ake_cqt_plan_half_support(plan.handle))
+        if self.H < 0:
+            _lib.check(-1, "ake_cqt_plan_half_support")
+        self.max_chunk = 10 * est.sample_rate if max_chunk_samples is None else int(max_chunk_samples)
+        if self.max_chunk < 1:
+            raise ValueError("stream: max_chunk_samples must be at least 1")
+        self.signature_weight = float(signature_weight)
+        self.trans = est._transition(self.sf, mean_key_seconds, transition) if self.smooth else None
+        self.prior = None
+        if self.smooth and log_prior is not None:
+            prior = torch.as_tensor(log_prior).detach()
+            if tuple(prior.shape) != (24,):
+                raise ValueError("stream: log_prior must hold 24 log-probabilities")
+            metrics._check_finite("log_prior", prior)
+            self.prior = prior.to(device=dev, dtype=torch.float32).contiguous()
+        self.P = int(plan.n_bins)
+        self.fm = bool(L.ake_cqt_frames_major_supported(plan.handle))
+        # what the stream has seen: samples, final frames, emitted windows -- host integers all
+        self.N = self.F = self.W = 0
+        self.s0 = 0                                                  # the history's first sample
+        self.finished = False
+        self.dtype = None
+        # the history holds [s0, N): at most 2H + hop samples survive a push (frame F is not final, so N <= F*hop + H, and
+        # s0 > F*hop - H - hop), and a piece adds at most max_chunk
+        self.hist_cap = (2 * self.H + hop + self.max_chunk + 3) // 4 * 4
+        self.max_mel = 1 + self.hist_cap // hop                      # frames of the longest re-transform
+        self.cache_cap = self.wf + self.max_mel                      # fewer than wf frames survive a push
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        self.hist = f32(R, self.hist_cap)
+        self.mel = f32(R * self.P * self.max_mel)
+        self.cache = [f32(R * self.P * self.cache_cap), f32(R * self.P * self.cache_cap)]
+        # which half is current, the stream's frame it begins at (W * sf: ahead of F when the stride skips frames) and the frames it holds
+        self.cache_at, self.cache_start, self.cache_frames = 0, 0, 0
+        with torch.cuda.device(dev):
+            cqt_bytes = max(int(L.ake_cqt_workspace_bytes(plan.handle, R, n)) for n in (self.hist_cap, self.hist_cap // 2, hop))
+            net_bytes = max(int(L.ake_pcnet_forward_windows_workspace_bytes(net.handle, R, t, self.wf, self.sf))
+                            for t in (self.cache_cap, self.wf))
+        if cqt_bytes == 0 or net_bytes == 0:
+            _lib.check(-1, "stream: workspace query")
+        self.cqt_ws = torch.empty(cqt_bytes, dtype=torch.uint8, device=dev)
+        self.net_ws = torch.empty(net_bytes, dtype=torch.uint8, device=dev)
+        self.state = None
+        if self.smooth:
+            self.state = torch.empty(max(int(L.ake_key_stream_state_bytes(R, lag)), 16), dtype=torch.uint8, device=dev)
+        self.keep_frames = bool(keep_frames)
+        self._frames = [] if keep_frames else None
+
+    @property
+    def frames(self):
+        """``keep_frames=True``: every final frame so far, (R, P, T) float32 (for tests and debugging)."""
+        if self._frames is None:
+            raise ValueError("KeyStream.frames: the stream was opened without keep_frames=True")
+        if not self._frames:
+            return torch.empty((self.R, self.P, 0), dtype=torch.float32, device=self.device)
+        if len(self._frames) > 1:
+            self._frames = [torch.cat(self._frames, dim=2)]
+        return self._frames[0]
+
+    @torch.no_grad()
+    def push(self, chunk: torch.Tensor) -> StreamUpdate:
+        """(R, m) float32 or int16 (16-bit PCM, sample / 32768) at the estimator's rate, any m >= 0 -> ``StreamUpdate``."""
+        if self.finished:
+            raise ValueError("KeyStream.push: the stream has been finished")
+        if not isinstance(chunk, torch.Tensor) or chunk.dim() != 2 or chunk.shape[0] != self.R:
+            raise ValueError(f"KeyStream.push: a chunk is (R, m) with R = {self.R}: mono audio at the estimator's rate (a stream does not "
+                             "resample or pick channels: the resampler keeps no state across chunks)")
+        if chunk.dtype not in (torch.float32, torch.int16):
+            raise ValueError("KeyStream.push: a chunk is float32 or int16 (16-bit PCM)")
+        if self.dtype is None:
+            self.dtype = chunk.dtype
+        elif chunk.dtype != self.dtype:
+            raise ValueError(f"KeyStream.push: this stream takes {self.dtype} chunks, got {chunk.dtype}")
+        self.est.net._sync_weights(self.device, for_eval=True)
+        chunk = chunk.to(self.device)
+        if chunk.stride(1) != 1 and chunk.shape[1] > 1:
+            chunk = chunk.contiguous()
+        m = chunk.shape[1]
+        if m <= self.max_chunk:
+            return self._piece(chunk, False)
+        return StreamUpdate.concat([self._piece(chunk[:, a:a + self.max_chunk], False) for a in range(0, m, self.max_chunk)])
+
+    @torch.no_grad()
+    def finish(self) -> StreamUpdate:
+        """The recording ends here: the rest of the windows (every frame is final now, seeing zeros behind the end as ``track``'s do)
+        and the rest of the smoothed path."""
+        if self.finished:
+            raise ValueError("KeyStream.finish: the stream has been finished")
+        out = self._piece(None, True)
+        self.finished = True
+        return out
+
+    def _piece(self, chunk, finishing):
+        L, dev, R, hop, P = _lib.lib(), self.device, self.R, self.hop, self.P
+        m = 0 if chunk is None else int(chunk.shape[1])
+        # ---- the counts of this piece, all on the host ----
+        N = self.N + m
+        F = final_frames(N, hop, self.H, finishing)
+        s0 = transform_start(self.F, hop, self.H)                    # where the history must begin for frames F_old.. (>= self.s0)
+        new_frames = F - self.F
+        nw = windows_ready(F, self.wf, self.sf)
+        k = nw - self.W
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            # ---- the history: [s0, N) ----
+            drop, keep = s0 - self.s0, self.N - s0
+            hist = L.ake_stream_history_pcm16 if self.dtype == torch.int16 else L.ake_stream_history_f32
+            _lib.check(hist(self.hist.data_ptr(), R, self.hist_cap, drop, keep, chunk.data_ptr() if m else None,
+                            (chunk.stride(0) if R > 1 else m) if m else 0, m, stream), "ake_stream_history")
+            self.s0, self.N = s0, N
+            # ---- the new final frames, from a re-transform of the history ----
+            n = N - s0
+            if new_frames > 0 and n > 0:
+                T = 1 + n // hop
+                if self.fm:
+                    _lib.check(L.ake_cqt_logmag_frames_major_f32(self.est.plan.handle, self.hist.data_ptr(), R, n, self.hist_cap, self.mel.data_ptr(),
+                                                                 self.cqt_ws.data_ptr(), self.cqt_ws.numel(), stream), "ake_cqt_logmag_frames_major_f32")
+                else:
+                    _lib.check(L.ake_cqt_logmag_f32(self.est.plan.handle, self.hist.data_ptr(), R, n, self.hist_cap, self.mel.data_ptr(), T,
+                                                    self.cqt_ws.data_ptr(), self.cqt_ws.numel(), stream), "ake_cqt_logmag_f32")
+                first = self.F - s0 // hop                           # the transform's frame of the stream's frame F_old
+                assert 0 <= first and first + new_frames <= T
+                # ---- the frame cache: what it holds, then the new frames (those no window needs left out), into the other half ----
+                skip = min(new_frames, max(0, self.cache_start - self.F))
+                if new_frames > skip:
+                    assert self.cache_frames + new_frames - skip <= self.cache_cap
+                    dst, old = self.cache[1 - self.cache_at], self.cache[self.cache_at]
+                    _lib.check(L.ake_stream_frames_f32(dst.data_ptr(), old.data_ptr(), self.mel.data_ptr(), int(self.fm), R, P, self.cache_frames, 0,
+                                                       self.cache_frames, T, first + skip, new_frames - skip, stream), "ake_stream_frames_f32")
+                    self.cache_at, self.cache_frames = 1 - self.cache_at, self.cache_frames + new_frames - skip
+                if self._frames is not None:
+                    mel = self.mel[:R * P * T]
+                    mel = mel.view(R, T, P).transpose(1, 2) if self.fm else mel.view(R, P, T)
+                    self._frames.append(mel[:, :, first:first + new_frames].clone())
+            elif new_frames > 0:                                     # finish() on a stream that never got a sample: nothing to transform
+                new_frames, F, k = 0, self.F, 0
+            self.F = F
+            # ---- the newly complete windows: one call of the net over the cached frames ----
+            key, tonic, genre = f32(R, k, 12), f32(R, k, 12), f32(R, k, 11) if self.est.net.genre else None
+            key_id, sig, tonic_id, conf = i32(R, k), i32(R, k), i32(R, k), f32(R, k)
+            times = (torch.arange(self.W, self.W + k, dtype=torch.float64) * self.sf + (self.wf - 1) / 2) * hop / self.est.sample_rate
+            up = StreamUpdate(self.W, k, key, tonic, genre, key_id, sig, tonic_id, conf, times)
+            if k > 0:
+                cur = self.cache[self.cache_at]
+                assert self.cache_start == self.W * self.sf and track_counts(self.cache_frames, self.wf, self.sf) == k
+                _lib.check(L.ake_pcnet_forward_windows_f32(self.est.net.handle, cur.data_ptr(), int(self.fm), R, self.cache_frames, self.wf, self.sf,
+                                                           key.data_ptr(), tonic.data_ptr(), genre.data_ptr() if genre is not None else None,
+                                                           self.net_ws.data_ptr(), self.net_ws.numel(), stream), "ake_pcnet_forward_windows_f32")
+                _lib.check(L.ake_decode_keys_f32(key.data_ptr(), tonic.data_ptr(), R * k, None, 1, key_id.data_ptr(), sig.data_ptr(),
+                                                 tonic_id.data_ptr(), conf.data_ptr(), stream), "ake_decode_keys_f32")
+                # the tail later windows still need slides to the front (of the other half): the cache begins at frame W * sf again
+                left = max(0, self.cache_frames - k * self.sf)        # (a stride longer than a window leaves none, and skips some to come)
+                dst = self.cache[1 - self.cache_at]
+                _lib.check(L.ake_stream_frames_f32(dst.data_ptr(), cur.data_ptr(), None, int(self.fm), R, P, self.cache_frames,
+                                                   self.cache_frames - left, left, 0, 0, 0, stream), "ake_stream_frames_f32")
+                self.cache_at, self.cache_start, self.cache_frames = 1 - self.cache_at, self.cache_start + k * self.sf, left
+            # ---- the smoother ----
+            if self.smooth:
+                first_s, k2 = smooth_count(self.W, k, self.lag, finishing)
+                up.emissions, up.filtered = f32(R, k, 24), f32(R, k, 24)
+                up.smooth_first_window, up.smooth_key_id = first_s, i32(R, k2)
+                if k > 0:
+                    _lib.check(L.ake_key_emissions_f32(key.data_ptr(), tonic.data_ptr(), R * k, None, 1, self.signature_weight,
+                                                       up.emissions.data_ptr(), stream), "ake_key_emissions_f32")
+                if k > 0 or k2 > 0:
+                    k_out = C.c_int(-1)
+                    _lib.check(L.ake_key_stream_step_f32(up.emissions.data_ptr() if k else None, R, k, self.W, self.lag, int(finishing),
+                                                         self.trans.data_ptr(), self.prior.data_ptr() if self.prior is not None else None,
+                                                         self.state.data_ptr(), self.state.numel(), up.filtered.data_ptr() if k else None,
+                                                         up.smooth_key_id.data_ptr() if k2 else None, C.byref(k_out), stream),
+                               "ake_key_stream_step_f32")
+                    assert k_out.value == k2
+            self.W += k
+        return up

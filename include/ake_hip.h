@@ -78,6 +78,12 @@ int ake_cqt_plan_n_bins(const ake_cqt_plan* plan);
 int ake_cqt_plan_hop(const ake_cqt_plan* plan);
 /* 1 + n_samples / hop  (librosa center=True framing). */
 int64_t ake_cqt_num_frames(const ake_cqt_plan* plan, int64_t n_samples);
+/* The half-support H of the plan, in samples: frame t depends only on the samples [t * hop - H, t * hop + H].  A host-only query, an
+ * upper bound from the plan's own tables: per level l, the filter bank's taps around the frame centre on the level's grid (uh, the
+ * centre rounded down to the grid), through the l half-band stages below it (half_len taps to either side, each):
+ *   H = max_l ( uh_l * 2^l + (2^l - 1) + half_len * (2^l - 1) )
+ * -1 for a null plan.  A stream of audio uses it to tell which frames are final (KeyEstimator.stream). */
+int64_t ake_cqt_plan_half_support(const ake_cqt_plan* plan);
 /*
  * The workspace contract, for every entry point that takes (workspace, workspace_bytes) with the size its *_workspace_bytes returns:
  *   - the content of the workspace on entry is arbitrary (fresh memory, what a call of another shape or route left, NaN patterns): a call
@@ -509,6 +515,48 @@ int ake_key_posteriors_chunk_windows(void);
 int ake_key_posteriors_f32(const float* emis_dev, int recordings, int windows, const int32_t* counts_dev, const float* log_trans_dev,
                            const float* log_prior_dev, const int32_t* path_dev, float* post_dev, float* loglik_dev, float* xi_sum_dev,
                            float* path_post_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream);
+
+/* The smoother with carried state, for audio that arrives in pieces: the k new windows emis_dev [recordings][k][24] of a stream that has
+ * seen windows_before windows so far, one wave per recording.  log_trans_dev and log_prior_dev as ake_viterbi_keys_f32 takes them, all
+ * finite.  Every new window w runs
+ *   - ake_viterbi_keys_f32's step, operation for operation (d_w, bp_w; the same tie rules), and
+ *   - ake_key_posteriors_f32's forward step (a_w, normalised by c_w at every step, w = 0 included);
+ * filtered_dev [recordings][k][24] (nullable) = a_w: exp of it is the probability of each key given the windows up to w.
+ * The fixed-lag path: after the step of window w >= lag the kernel follows `lag` back-pointers from the smallest j attaining max d_w and
+ * writes the label of window w - lag, which is what ake_viterbi_keys_f32 on windows 0..w gives for it.  flush != 0 (the recording ends
+ * here): after the last step the windows still inside the lag, min(lag, windows_before + k) of them, are written from the last best
+ * state, so they hold the Viterbi path of the whole recording.  path_dev is int32 [recordings][*k_out], the windows from
+ * max(0, windows_before - lag) on, in order; *k_out (a host integer, required) is computed on the host:
+ *   (flush ? windows_before + k : max(0, windows_before + k - lag)) - max(0, windows_before - lag)
+ * k = 0 is allowed (with flush: flush only); a call with nothing to step and nothing to write launches nothing.
+ * state_dev holds, per recording, d[24], a[24] and a ring of the last `lag` back-pointer rows (24 bytes a window):
+ * ake_key_stream_state_bytes(recordings, lag) bytes (0 for a bad shape), 16-byte aligned.  It is read once in front of the first step and
+ * written once behind the last; with windows_before == 0 it is not read, so a fresh stream needs no initialising launch.  The device
+ * keeps no count: the host passes windows_before, and the same lag at every call of a stream.  Results do not depend on how a
+ * stream's windows are cut into calls, to the bit.
+ * AKE_ERR_INVALID: lag outside 0..255, k < 0, recordings < 1, windows_before < 0, a null required pointer (log_trans_dev, state_dev,
+ * k_out; emis_dev with k > 0; path_dev with *k_out > 0), a misaligned state.  AKE_ERR_WORKSPACE: state_bytes below the query. */
+size_t ake_key_stream_state_bytes(int recordings, int lag);
+int ake_key_stream_step_f32(const float* emis_dev, int recordings, int k, int64_t windows_before, int lag, int flush,
+                            const float* log_trans_dev, const float* log_prior_dev, void* state_dev, size_t state_bytes,
+                            float* filtered_dev, int32_t* path_dev, int* k_out, ake_stream_t stream);
+
+/* The front end of a stream of audio in lockstep (csrc/stream.hip), both in one launch each, plain loads and stores, no atomics.
+ * ake_stream_history_*: the audio history [recordings][history_stride] float32 moves `drop` samples to the front -- `keep` samples
+ * survive, history[r][i] = history[r][i + drop] for i < keep -- and the m new samples of chunk_dev [recordings][chunk_stride] follow
+ * them at history[r][keep + i]; _pcm16: the chunk is 16-bit PCM, converted as float(s) * 2^-15 (exact).  The move is ordered (a row is
+ * one workgroup's, tile by tile towards the back), so source and destination may overlap.  keep + m <= history_stride and
+ * drop + keep <= history_stride, AKE_ERR_INVALID otherwise; keep = 0 or m = 0 are allowed.
+ * ake_stream_frames_f32: the frame cache.  dst_dev receives keep frames of old_dev from frame `drop` on, then n_new frames of mel_dev
+ * (a transform's output of mel_frames frames) from frame `first` on; frames_major != 0: all three are [recordings][frames][pitches]
+ * with pitches a multiple of 4 and 16-byte aligned buffers, else [recordings][pitches][frames].  old_dev holds old_frames frames and
+ * dst_dev keep + n_new; dst_dev overlaps neither source.  AKE_ERR_INVALID for ranges outside their tensors. */
+int ake_stream_history_f32(float* history_dev, int recordings, int64_t history_stride, int64_t drop, int64_t keep, const float* chunk_dev,
+                           int64_t chunk_stride, int64_t m, ake_stream_t stream);
+int ake_stream_history_pcm16(float* history_dev, int recordings, int64_t history_stride, int64_t drop, int64_t keep,
+                             const int16_t* chunk_dev, int64_t chunk_stride, int64_t m, ake_stream_t stream);
+int ake_stream_frames_f32(float* dst_dev, const float* old_dev, const float* mel_dev, int frames_major, int recordings, int pitches,
+                          int old_frames, int drop, int keep, int mel_frames, int first, int n_new, ake_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * A loss over a sequence of windows, for training the net for the smoothed track: the conditional log-likelihood of the labelled windows

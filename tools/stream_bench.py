@@ -1,0 +1,212 @@
+"""Key tracking on audio as it arrives: what a KeyStream.push costs, against calling track again on a rolling buffer -> one JSON line.
+
+  push      : est.stream(R, stride 5 s, lag 6) fed white noise (no side's cost depends on the content) in chunks of one hop (0.2 s) and of
+              1 s, float32 and 16-bit PCM, R = 1, 16, 256.  After 30 s of warm-up every push is timed with events on the stream: median, 95th
+              percentile and maximum over --pushes pushes, and the median of the pushes that completed a window.
+  split     : the same pushes once more under the library's kernel timer, per push on average: transform (history, cascade, bank, frame
+              cache), net (gather and the net's kernels), smoother (decode, emissions, step); launch_share = 1 - kernels / mean push.
+  baseline  : the parent commit's only way -- est.track(smooth=True) on a 60 s buffer of the same R and dtype, once per push (rolling the
+              buffer is not timed); median over --baseline-reps calls.
+  smoother  : ake_key_stream_step_f32 alone, 8 recordings x 2000 windows in one call at lags 3, 12, 255, per window; and one window per
+              call (a push's shape).
+  support   : H of the default plan, and the latency it gives from audio to raw label and to smoothed label.
+  frames    : streamed against offline frames, the re-transform's start s0 on the decimation grid (a multiple of 2^(octaves-1)) and off it.
+  --accuracy: tools/track_accuracy.py's net and modulating recordings (one run on sine mixes): the fixed-lag path at lags 0, 3, 6, 12 scored
+              as KeyTrack.score scores, beside the raw labels and the offline Viterbi path, at a 5 s stride.
+
+Usage: python tools/stream_bench.py [--pushes 200] [--accuracy]"""
+import argparse
+import ctypes as C
+import importlib.util
+import json
+import os
+import statistics
+import sys
+from argparse import Namespace
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import ake_amd  # noqa: E402
+from ake_amd import _lib, metrics  # noqa: E402
+from ake_amd.pipeline import KeyTrack  # noqa: E402
+
+SR, DEV, HOP = 22050, "cuda:0", 4410
+GROUPS = {"transform": ("stream_history", "stream_frames", "cqt_", "decim", "transpose", "logmag"),
+          "smoother": ("decode_keys", "key_emissions", "key_stream_step")}
+
+
+def group_of(kernel):
+    for g, prefixes in GROUPS.items():
+        if any(kernel.startswith(p) or p in kernel for p in prefixes):
+            return g
+    return "net"
+
+
+def percentile(xs, q):
+    xs = sorted(xs)
+    return xs[min(len(xs) - 1, int(round(q * (len(xs) - 1))))]
+
+
+def push_row(est, R, chunk, dtype, pushes, baseline_reps):
+    src = torch.randn((R, chunk * 8), device=DEV) * 0.3
+    if dtype == torch.int16:
+        src = (src.clamp(-1, 1) * 32767).to(torch.int16)
+    pieces = [src[:, i * chunk:(i + 1) * chunk] for i in range(8)]
+    s = est.stream(R)
+    for i in range(30 * SR // chunk + 1):                                            # warm: windows are being emitted
+        s.push(pieces[i % 8])
+    torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(pushes)]
+    emitted = []
+    for i, (a, b) in enumerate(ev):
+        a.record()
+        u = s.push(pieces[i % 8])
+        b.record()
+        emitted.append(u.windows)
+    torch.cuda.synchronize()
+    ms = [a.elapsed_time(b) for a, b in ev]
+    _lib.prof_enable("", True)
+    for i in range(pushes):
+        s.push(pieces[i % 8])
+    split = {"transform": 0.0, "net": 0.0, "smoother": 0.0}
+    for name, (total, _) in _lib.prof_results().items():
+        split[group_of(name)] += total / pushes
+    _lib.prof_enable("", False)
+    buf = torch.randn((R, 60 * SR), device=DEV) * 0.3
+    if dtype == torch.int16:
+        buf = (buf.clamp(-1, 1) * 32767).to(torch.int16)
+    for _ in range(2):
+        est.track(buf, smooth=True)
+    torch.cuda.synchronize()
+    base = []
+    for _ in range(baseline_reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        est.track(buf, smooth=True)
+        b.record()
+        b.synchronize()
+        base.append(a.elapsed_time(b))
+    del buf, s
+    torch.cuda.empty_cache()
+    with_window = [m for m, k in zip(ms, emitted) if k]
+    mean = statistics.fmean(ms)
+    return {"recordings": R, "chunk_s": round(chunk / SR, 3), "dtype": "int16" if dtype == torch.int16 else "float32",
+            "push_ms": {"median": round(statistics.median(ms), 4), "p95": round(percentile(ms, 0.95), 4), "max": round(max(ms), 4),
+                        "mean": round(mean, 4), "median_with_window": round(statistics.median(with_window), 4) if with_window else None,
+                        "pushes_with_window": len(with_window)},
+            "kernels_ms_per_push": {k: round(v, 4) for k, v in split.items()},
+            "launch_share": round(1.0 - sum(split.values()) / mean, 3),
+            "baseline_track_60s_ms": round(statistics.median(base), 4),
+            "baseline_over_push_p95": round(statistics.median(base) / percentile(ms, 0.95), 1)}
+
+
+def smoother_rows():
+    L = _lib.lib()
+    R, K = 8, 2000
+    e = torch.randn((R, K, 24), device=DEV) * 3
+    A = metrics.key_transition_log(0.92).float().to(DEV)
+    out, path, k_out = torch.empty_like(e), torch.empty((R, K), dtype=torch.int32, device=DEV), C.c_int(0)
+    stream = torch.cuda.current_stream().cuda_stream
+    rows = []
+    for lag in (3, 12, 255):
+        state = torch.zeros(L.ake_key_stream_state_bytes(R, lag), dtype=torch.uint8, device=DEV)
+
+        def call(k, before):
+            _lib.check(L.ake_key_stream_step_f32(e.data_ptr(), R, k, before, lag, 0, A.data_ptr(), None, state.data_ptr(), state.numel(), out.data_ptr(),
+                                                 path.data_ptr(), C.byref(k_out), stream), "ake_key_stream_step_f32")
+
+        res = {}
+        for name, k, before, reps in (("all_at_once", K, 0, 10), ("one_per_call", 1, 1000, 200)):
+            call(k, before)
+            torch.cuda.synchronize()
+            ms = []
+            for _ in range(reps):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                call(k, before)
+                b.record()
+                b.synchronize()
+                ms.append(a.elapsed_time(b))
+            res[name] = statistics.median(ms)
+        rows.append({"lag": lag, "us_per_window": round(1e3 * res["all_at_once"] / K, 4), "one_window_call_us": round(1e3 * res["one_per_call"], 2)})
+    return rows
+
+
+def frame_rows(est):
+    plan = est.plan
+    H = int(_lib.lib().ake_cqt_plan_half_support(plan.handle))
+    x = torch.randn((2, 100 * HOP), device=DEV) * 0.3
+    offline = plan.logmag(x)
+    rows = []
+    for name, hops in (("off the grid", 7), ("off the grid", 33), ("on the grid (64 hops)", 64)):
+        s0 = hops * HOP
+        part = plan.logmag(x[:, s0:].contiguous())
+        skip = -(-H // HOP)                                                          # frames whose support reaches in front of s0
+        a, b = part[:, :, skip:], offline[:, :, hops + skip:]
+        rows.append({"s0_hops": hops, "s0_mod_128": s0 % 128, "grid": name, "max_abs_diff": float((a - b).abs().max()),
+                     "rel_to_peak": float((a - b).abs().max() / b.abs().max()), "equal": bool(torch.equal(a, b))})
+    return H, rows
+
+
+def accuracy_rows():
+    spec = importlib.util.spec_from_file_location("track_accuracy", os.path.join(REPO, "tools", "track_accuracy.py"))
+    ta = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ta)
+    from ake_amd import synthetic
+    net, training = ta.train_net(10, 604)
+    est = ake_amd.KeyEstimator(net, SR, 5)
+    R = 24
+    audio, ann = synthetic.make_modulating_batch_device(range(R), 300.0, DEV)
+    tr = est.track(audio, stride_seconds=5.0, smooth=True)
+    rows = [("raw key_id (track)", ta.row_of(tr.score(ann, smoothed=False))), ("offline Viterbi (track)", ta.row_of(tr.score(ann)))]
+    for lag in (0, 3, 6, 12):
+        s = est.stream(R, stride_seconds=5.0, lag_windows=lag)
+        ups = [s.push(audio[:, a:a + 10 * SR]) for a in range(0, audio.shape[1], 10 * SR)] + [s.finish()]
+        cat = lambda n: torch.cat([getattr(u, n) for u in ups], dim=1)              # noqa: E731
+        W = cat("key_id").shape[1]
+        assert W == tr.key.shape[1]
+        st = KeyTrack(cat("key"), cat("tonic"), None, cat("key_id"), cat("signature_id"), cat("tonic_id"), cat("confidence"),
+                      torch.full((R,), W, dtype=torch.int32, device=DEV), torch.cat([u.times for u in ups]), tr.window_seconds, tr.stride_seconds,
+                      cat("emissions"), cat("smooth_key_id"), hop=tr.hop, window_frames=tr.window_frames, stride_frames=tr.stride_frames,
+                      sample_rate=SR)
+        rows.append((f"fixed lag {lag} ({lag * 5} s)", ta.row_of(st.score(ann))))
+        if lag == 0:
+            rows.append(("raw key_id (stream)", ta.row_of(st.score(ann, smoothed=False))))
+    return {"training": training, "recordings": R, "minutes": 5, "stride_s": 5, "rows": rows}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pushes", type=int, default=200)
+    ap.add_argument("--baseline-reps", type=int, default=10)
+    ap.add_argument("--recordings", type=int, nargs="+", default=[1, 16, 256])
+    ap.add_argument("--accuracy", action="store_true")
+    args = ap.parse_args()
+    torch.manual_seed(0)
+    gold = np.load(os.path.join(REPO, "tests", "golden", "pcnet_default.npz"))
+    sd = {k[3:]: torch.from_numpy(gold[k]) for k in gold.files if k.startswith("sd/")}
+    net = ake_amd.PitchClassNet(288, 12, 2, 7, Namespace(genre=True))
+    net.load_state_dict(sd, strict=True)
+    est = ake_amd.KeyEstimator(net.to(DEV).eval(), SR, 5)
+    rows = [push_row(est, R, chunk, dtype, args.pushes, args.baseline_reps)
+            for R in args.recordings for chunk in (HOP, SR) for dtype in (torch.float32, torch.int16)]
+    H, frames = frame_rows(est)
+    result = {"device": torch.cuda.get_device_name(0), "pushes": args.pushes, "stride_s": 5, "lag_windows": 6, "push": rows,
+              "smoother": smoother_rows(),
+              "support": {"H_samples": H, "H_hops": round(H / HOP, 3), "H_seconds": round(H / SR, 4),
+                          "raw_label_latency_s": "H + at most one hop + the chunk: %.2f .. %.2f s behind the window's last frame centre (plus the chunk)"
+                                                 % (H / SR, (H + HOP) / SR),
+                          "smoothed_label_latency_s": "that + lag_windows x stride (6 x 5 s = 30 s at the defaults)"},
+              "frames": frames}
+    if args.accuracy:
+        result["accuracy"] = accuracy_rows()
+    torch.cuda.synchronize()
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
