@@ -2042,7 +2042,7 @@ int rebuild_bf16_frags(ake_pcnet* n, hipStream_t s, bool train_only = false) {
     if (n->head_genre.size() == 2) h1.push_back(&n->head_genre[1]);              // 2 x 7 over valid rows
     for (PackedConv* pc : h1) {
         pc->bf_off = -1;
-        if ((pc->kh == 12 || pc->kh == 2) && pc->kw == 7 && pc->cout == 1 && pc->co == 1 && pc->cin == 32) { pc->bf_off = static_cast<long long>(count); count += static_cast<size_t>(pc->kh) * 22 * 2 * 64; }
+        if ((pc->kh == 12 || pc->kh == 2) && pc->kw == 7 && pc->cout == 1 && pc->co == 1 && pc->cin == 32) { pc->bf_off = static_cast<long long>(count); count += static_cast<size_t>(head1_ksteps(pc->kh)) * 2 * 64; }
     }
     if (!n->pc2pc.empty())                                   // layer 0's pitch-class stack (<= 4 channels): layer0_mfma_kernel
         for (PackedConv& pc : n->pc2pc[0]) {
@@ -2125,7 +2125,7 @@ int rebuild_bf16_frags(ake_pcnet* n, hipStream_t s, bool train_only = false) {
     if (!train_only)
     for (const PackedConv* pc : h1)
         if (pc->bf_off >= 0)
-            hipLaunchKernelGGL(pack_head1_bf16_kernel, dim3((pc->kh * 22 * 64 + 255) / 256), dim3(256), 0, s, n->blob_dev + pc->w_off,
+            hipLaunchKernelGGL(pack_head1_bf16_kernel, dim3((head1_ksteps(pc->kh) * 64 + 255) / 256), dim3(256), 0, s, n->blob_dev + pc->w_off,
                                n->bf_frags_dev + pc->bf_off, pc->cin, pc->kh);
     AKE_HIP_CHECK(hipGetLastError());
     return AKE_OK;

@@ -1963,17 +1963,23 @@ __global__ __launch_bounds__(1024) void pc2pc_fused_kernel(Pc2pcFusedArgs a) {
 
 // ==========================================================================================
 // Last convolution of the key / tonic heads: 32 channels -> ONE map, 12 x 7 over circular pitch classes, valid in time
-// (models.py:730-731).  With a single output channel the N dimension of the MFMA is filled with 16 output FRAMES (Toeplitz in
-// time), the K dimension with the 32 input channels of one tap -- channels-last split planes [clip][12][T_in][32] again:
-//   m = (frame block jb, pitch class y)     A[m][k = ci] = X[(y + dy) mod 12][16 jb + dxe][ci]
-//   n = tau (frame within the block)        B[k][n] = w[ci][dy][dxe - tau]   (zero outside the 7 taps)
-//   k-step = (dy, dxe): 12 x 22 = 264, split over the 8 waves of the workgroup (one workgroup per clip and head); the partial
-//   tiles are reduced through LDS.  The implicit-GEMM f32 kernel needed 100 us per launch for these 0.8 M MACs per clip.
+// (models.py:730-731).  With a single output channel the N dimension of the MFMA is filled with the 12 output PITCH CLASSES (the
+// circular rows make every input row feed every output row: a dense B), the K dimension with the 32 input channels of one tap --
+// channels-last split planes [clip][12][T_in][32] again:
+//   m = tau (frame within block jb)         A[m][k = ci] = X[r][16 jb + tau + dx][ci]
+//   n = output pitch class y (12 of 16)     B[k][n] = w[ci][(r - y) mod 12][dx]
+//   k-step = (input row r, tap dx): 12 x 7 = 84, split over the 8 waves of the workgroup (one workgroup per clip and head); the
+//   partial tiles are reduced through LDS.  The implicit-GEMM f32 kernel needed 100 us per launch for these 0.8 M MACs per clip.
+// The genre head's last conv (2 rows, valid: 11 output rows) keeps the form this kernel had for every head before, 16 output FRAMES
+// as N, Toeplitz in time: there it is 2 x 22 = 44 k-steps against 84.
+//   m = (frame block jb, row y)             A[m][k = ci] = X[y + dy][16 jb + dxe][ci]
+//   n = tau (frame within the block)        B[k][n] = w[ci][dy][dxe - tau]   (zero outside the 7 taps: 15 of 22 fragments of a row)
+//   k-step = (dy, dxe): KH x 22.  For the circular heads that was 264 k-steps, 528 KB of fragments per workgroup.
 // ==========================================================================================
 struct Head1BfArgs {
     const unsigned short* xh[3];  // per head (key, tonic, genre): [clip][12][T_in][32]
     const unsigned short* xl[3];
-    const uint4* bfrag[3];        // per head: [KH * 22 k-steps][hi|lo][64 lanes]
+    const uint4* bfrag[3];        // per head: [head1_ksteps(KH)][hi|lo][64 lanes]
     const float* bias[3];
     float* dst[3];                // per head: [clip][H_out][T_out]
     int KH[3], H_out[3], circular[3];   // key / tonic: 12 rows over circular pitch classes; genre: 2 rows, valid (11 output rows)
@@ -1985,10 +1991,12 @@ struct Head1BfArgs {
 };
 
 constexpr int kHead1MT = 4;       // M-tiles (12 * JB positions / 16): T_out <= 80
+constexpr int kHead1JB = 5;       // ... which is at most 5 frame blocks, the M-tiles of the circular form
+__host__ __device__ constexpr int head1_ksteps(int KH) { return KH == 12 ? 12 * 7 : KH * 22; }   // circular form | Toeplitz form
 constexpr int kHead1PF = 3;       // weight fragments in flight per wave (they come from L2: fetched at their use, every k-step paid a full round trip)
 
 // The body of that convolution, shared by conv_head1_bf16_kernel and phase B of heads_fused_kernel, in two calls so that a caller can
-// issue the first loads before its patch is ready.  bg = the head's fragments + lane, nks = KH * 22 k-steps, wave w takes w, w + 8, ...
+// issue the first loads before its patch is ready.  bg = the head's fragments + lane, nks = head1_ksteps(KH), wave w takes w, w + 8, ...
 __device__ __forceinline__ void head1_prefetch(const uint4* __restrict__ bg, int nks, int wave, uint4 (&nbh)[kHead1PF], uint4 (&nbl)[kHead1PF]) {
 #pragma unroll
     for (int i = 0; i < kHead1PF; ++i) {
@@ -2010,6 +2018,58 @@ __device__ __forceinline__ void head1_multiply_store(const uint4* __restrict__ b
     const uint4* const pH = lds4;
     const uint4* const pL = lds4 + 12 * Tp * 4;
     float* const red = reinterpret_cast<float*>(lds4);       // [8 waves][kHead1MT][4][64]: reuses the patch's bytes after the multiply loop
+    if (circ) {
+        // ---- circular heads, output rows as N: k-step ks = (input row r, tap dx), M-tile = frame block jb ----
+        f32x4c acc[kHead1JB];
+#pragma unroll
+        for (int mt = 0; mt < kHead1JB; ++mt) acc[mt] = f32x4c{0.f, 0.f, 0.f, 0.f};
+        for (int ks = wave; ks < nks; ks += 8) {
+            const int r = ks / 7, dx = ks - r * 7;
+            const bf16x8c bh = __builtin_bit_cast(bf16x8c, nbh[0]);
+            const bf16x8c bl = __builtin_bit_cast(bf16x8c, nbl[0]);
+#pragma unroll
+            for (int i = 0; i + 1 < PF; ++i) { nbh[i] = nbh[i + 1]; nbl[i] = nbl[i + 1]; }
+            {
+                const int kn = ks + 8 * PF < nks ? ks + 8 * PF : ks;
+                nbh[PF - 1] = bg[(2 * kn + 0) * 64]; nbl[PF - 1] = bg[(2 * kn + 1) * 64];
+            }
+            const int ad0 = ((r * Tp + r16 + dx) << 2) + q;  // lane = (frame tau, 8 channels): 64 lanes read 1 KB in a row
+#pragma unroll
+            for (int mt = 0; mt < kHead1JB; ++mt) {
+                if (mt < JB) {
+                    const bf16x8c ah = __builtin_bit_cast(bf16x8c, pH[ad0 + 64 * mt]);
+                    const bf16x8c al = __builtin_bit_cast(bf16x8c, pL[ad0 + 64 * mt]);
+                    acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc[mt], 0, 0, 0);
+                    acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, acc[mt], 0, 0, 0);
+                    acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, acc[mt], 0, 0, 0);
+                }
+            }
+        }
+        __syncthreads();                                     // every wave is done with the patch
+        // partial tiles [8 waves][JB][4][64] (never more bytes than the patch of the same JB)
+#pragma unroll
+        for (int mt = 0; mt < kHead1JB; ++mt)
+            if (mt < JB)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) red[((wave * JB + mt) * 4 + i) * 64 + lane] = acc[mt][i];
+        __syncthreads();
+        // wave w finishes frame block w: D[row tau = 4q + i][col y]
+        if (wave < JB) {
+            const float bias = bias_p[0];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                float v = bias;
+#pragma unroll
+                for (int w = 0; w < 8; ++w) v += red[((w * JB + wave) * 4 + i) * 64 + lane];
+                const int t = 16 * wave + 4 * q + i;
+                if (r16 < 12 && t < T_out) {
+                    dst[(static_cast<long long>(clip) * 12 + r16) * T_out + t] = v;
+                    if (keep) red[fin_off + r16 * T_out + t] = v;
+                }
+            }
+        }
+        return;
+    }
     const int Mtot = HO * JB;
     const int mtiles = (Mtot + 15) / 16;
     int ay[kHead1MT], af[kHead1MT];
@@ -2037,9 +2097,7 @@ __device__ __forceinline__ void head1_multiply_store(const uint4* __restrict__ b
 #pragma unroll
         for (int mt = 0; mt < kHead1MT; ++mt) {
             if (mt < mtiles) {
-                int row = ay[mt] + dy;
-                row -= (circ && row >= 12) ? 12 : 0;
-                const int ad = ((row * Tp + af[mt] + dxe) << 2) + q;
+                const int ad = (((ay[mt] + dy) * Tp + af[mt] + dxe) << 2) + q;   // (valid rows: no wrap)
                 const bf16x8c ah = __builtin_bit_cast(bf16x8c, pH[ad]);
                 const bf16x8c al = __builtin_bit_cast(bf16x8c, pL[ad]);
                 acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc[mt], 0, 0, 0);
@@ -2098,7 +2156,7 @@ __global__ __launch_bounds__(512) void conv_head1_bf16_kernel(Head1BfArgs a) {
         }
     }
     __syncthreads();
-    const int HO = a.H_out[head], nks = a.KH[head] * 22;
+    const int HO = a.H_out[head], nks = head1_ksteps(a.KH[head]);
     const uint4* __restrict__ bg = a.bfrag[head] + lane;
     uint4 nbh[kHead1PF], nbl[kHead1PF];
     head1_prefetch(bg, nks, wave, nbh, nbl);
@@ -2124,7 +2182,7 @@ struct HeadsFusedArgs {
     const unsigned short* xl;
     const uint4* bfragA[3];       // per head (key, tonic, genre): first conv, [KHA * 4 k-steps][2 N-tiles][hi|lo][64 lanes]
     const float* biasA[3];        // [32]
-    const uint4* bfragB[3];       // second conv, [KHB * 22 k-steps][hi|lo][64 lanes]
+    const uint4* bfragB[3];       // second conv, [head1_ksteps(KHB)][hi|lo][64 lanes]
     const float* biasB[3];
     float* dst[3];                // finished maps [clip][H_out][T2]
     float* pout[3];               // masked temporal mean (+ sigmoid) of each finished map [clip][H_out]
@@ -2156,7 +2214,7 @@ __global__ __launch_bounds__(512, 4) void heads_fused_kernel(HeadsFusedArgs a) {
     uint4* const pLB = lds4 + 12 * TpB * 4;
     const uint4* __restrict__ bg = AKE_HSEL(bfragB) + lane;
     const int KHB = AKE_HSEL(KHB);
-    const int nks = KHB * 22;
+    const int nks = head1_ksteps(KHB);
     uint4 nbh[kHead1PF], nbl[kHead1PF];
     {   // ---- phase A: pc_bf16_multiply<2, MT, false>, valid in time, the whole clip in this workgroup ----
         const int Mtot = 12 * a.T1;                          // (12 output rows in both forms: 12 circular kernel rows, or one)
@@ -2217,14 +2275,22 @@ __global__ __launch_bounds__(512, 4) void heads_fused_kernel(HeadsFusedArgs a) {
 #undef AKE_HSEL
 }
 
-// weight fragments of conv_head1_bf16_kernel from the VALU-layout eval pack [ci][12][7] (cout == 1): one thread per (k-step, lane)
+// weight fragments of conv_head1_bf16_kernel from the VALU-layout eval pack [ci][KH][7] (cout == 1): one thread per (k-step, lane).
+// KH == 12, the circular heads: k-step (input row r, tap dx), column = output row y.  Else: k-step (dy, dxe), column = frame tau.
 __global__ void pack_head1_bf16_kernel(const float* __restrict__ w, uint4* __restrict__ out, int cin, int KH) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= KH * 22 * 64) return;
+    if (i >= head1_ksteps(KH) * 64) return;
     const int lane = i & 63, ks = i >> 6;
-    const int dy = ks / 22, dxe = ks - dy * 22;
-    const int tau = lane & 15, qq = lane >> 4;
-    const int dx = dxe - tau;
+    const int col = lane & 15, qq = lane >> 4;
+    int dy, dx;
+    if (KH == 12) {
+        const int r = ks / 7;
+        dx = col < 12 ? ks - r * 7 : -1;                       // (columns 12-15: zeros)
+        dy = r - col + (r < col ? 12 : 0);
+    } else {
+        dy = ks / 22;
+        dx = ks - dy * 22 - col;
+    }
     unsigned int hi[4] = {0, 0, 0, 0}, lo[4] = {0, 0, 0, 0};
     for (int e = 0; e < 8; ++e) {
         const int ci = 8 * qq + e;
