@@ -264,10 +264,7 @@ int retune_launch(const char* name, const T* in_dev, int batch, int64_t n_max, i
                     reinterpret_cast<long long*>(n_out_dev)};
     hipStream_t s = static_cast<hipStream_t>(stream);
     constexpr int per_block = kRetuneTile * kRetuneTiles;
-    ake::ProfScope ps(name, s);
-    hipLaunchKernelGGL(retune_kernel<T>, dim3(static_cast<unsigned>((width + per_block - 1) / per_block), batch), dim3(kRetuneThreads), 0, s, a);
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    return ake::launch(name, retune_kernel<T>, dim3(static_cast<unsigned>((width + per_block - 1) / per_block), batch), dim3(kRetuneThreads), 0, s, a);
 }
 
 }  // namespace
@@ -333,10 +330,7 @@ int ake_resample_f32(const ake_resampler* r, const float* in_dev, int batch, int
     a.out = out_dev; a.out_stride = out_stride; a.n_out_max = n_out; a.n_out_clip = reinterpret_cast<long long*>(n_out_clip_dev);
     a.h = r->h_dev; a.up = r->up; a.down = r->down; a.half = r->half;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    ake::ProfScope ps("resample_kernel", s);
-    hipLaunchKernelGGL(resample_kernel, dim3(static_cast<unsigned>((n_out + 255) / 256), batch), dim3(256), 0, s, a);
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    return ake::launch("resample_kernel", resample_kernel, dim3(static_cast<unsigned>((n_out + 255) / 256), batch), dim3(256), 0, s, a);
 }
 
 int ake_resample_pcm16_f32(const ake_resampler* r, const int16_t* in_dev, int batch, int channels, int64_t n_in, int64_t clip_stride,
@@ -354,10 +348,7 @@ int ake_resample_pcm16_f32(const ake_resampler* r, const int16_t* in_dev, int ba
     a.out = out_dev; a.out_stride = out_stride; a.n_out_max = n_out; a.n_out_clip = reinterpret_cast<long long*>(n_out_clip_dev);
     a.h = r->h_dev; a.up = r->up; a.down = r->down; a.half = r->half;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    ake::ProfScope ps("resample_pcm16_kernel", s);
-    hipLaunchKernelGGL(resample_pcm16_kernel, dim3(static_cast<unsigned>((n_out + 255) / 256), batch), dim3(256), 0, s, a);
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    return ake::launch("resample_pcm16_kernel", resample_pcm16_kernel, dim3(static_cast<unsigned>((n_out + 255) / 256), batch), dim3(256), 0, s, a);
 }
 
 int64_t ake_retune_out_len(int64_t n) {

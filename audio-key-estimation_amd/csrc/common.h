@@ -36,8 +36,8 @@ void set_error(const char* fmt, ...);
     } while (0)
 
 // ---- kernel timer -------------------------------------------------------------------------
-// When enabled, every launch site brackets its kernel with two hipEvents recorded on the
-// launch stream.  Elapsed times are summed per kernel name by collect().
+// When enabled, a ProfScope brackets what is launched while it lives with two hipEvents recorded on the
+// launch stream (ake::launch below opens one per launch).  Elapsed times are summed per kernel name by collect().
 struct ProfScope {
     ProfScope(const char* name, hipStream_t stream);
     ~ProfScope();
@@ -54,6 +54,49 @@ struct DeviceOnce {
     bool need() const { return !((done.load(std::memory_order_acquire) >> dev()) & 1); }
     void mark() { done.fetch_or(1ull << dev(), std::memory_order_release); }
 };
+
+// Set the dynamic-LDS limit of `kernels` to `bytes` on the current device ...
+template <typename... K>
+int set_lds_limit(int bytes, K... kernels) {
+    for (const void* f : {reinterpret_cast<const void*>(kernels)...})
+        AKE_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    return AKE_OK;
+}
+
+// ... and once per device, for a limit that never changes (`once` is the call site's own static).
+template <typename... K>
+int raise_lds_limit(DeviceOnce& once, int bytes, K... kernels) {
+    if (!once.need()) return AKE_OK;
+    const int rc = set_lds_limit(bytes, kernels...);
+    if (!rc) once.mark();
+    return rc;
+}
+
+// ---- kernel launch ------------------------------------------------------------------------
+// Every kernel of the library is launched through one of these.  A launch the runtime rejects is reported by the call that made it,
+// by kernel name and geometry, as AKE_ERR_HIP; the caller returns that code and launches nothing more.  Nothing synchronises.
+// launch() brackets the launch with the kernel timer under `name`; launch_untimed() uses `name` for the error text alone.
+template <typename... P, typename... A>
+int launch_untimed(const char* name, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const A&... args) {
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, static_cast<P>(args)...);
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return AKE_OK;
+    set_error("%s: launch failed: %s (grid %u x %u x %u, block %u x %u x %u, %zu B of dynamic LDS)", name, hipGetErrorString(e), grid.x, grid.y,
+              grid.z, block.x, block.y, block.z, lds);
+    return AKE_ERR_HIP;
+}
+
+template <typename... P, typename... A>
+int launch(const char* name, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const A&... args) {
+    ProfScope ps(name, s);
+    return launch_untimed(name, kernel, grid, block, lds, s, args...);
+}
+
+// one thread per element, 256 to a block
+template <typename... P, typename... A>
+int launch_flat(const char* name, void (*kernel)(P...), hipStream_t s, long long total, const A&... args) {
+    return launch(name, kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, args...);
+}
 
 // LDS-DMA: every lane's 16 bytes at `src` go straight to the LDS, lane i's to byte address lds_dst + 16 i (wave-uniform; of an LDS
 // pointer the low 32 bits are the LDS byte address), without passing through registers.  Nothing waits here: the caller places

@@ -1201,18 +1201,17 @@ int ake_cqt_plan_create(const ake_cqt_config* cfg_in, ake_cqt_plan** out) {
         if (e2 == hipSuccess) { what = "hipMalloc(octs)"; e2 = hipMalloc(&p->octs2_dev, p->octs2.size() * sizeof(OctDesc2)); }
         if (e2 == hipSuccess) { what = "hipMemcpy(table)"; e2 = hipMemcpy(p->table2_dev, t2.data(), t2.size() * sizeof(uint16_t), hipMemcpyHostToDevice); }
         if (e2 == hipSuccess) { what = "hipMemcpy(octs)"; e2 = hipMemcpy(p->octs2_dev, p->octs2.data(), p->octs2.size() * sizeof(OctDesc2), hipMemcpyHostToDevice); }
-        if (e2 == hipSuccess) {
-            what = "hipFuncSetAttribute(max dynamic LDS)";
-            e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(cqt_bank_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     static_cast<int>(p->bank2_lds));
-            if (e2 == hipSuccess && p->engine == 3 && p->hop_twos == 0)      // a plan that can take per-clip hops
-                e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(cqt_bank_rows_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         static_cast<int>(p->bank2_lds));
-        }
         if (e2 != hipSuccess) {
             ake::set_error("cqt plan (bf16 tables, %zu B of LDS per workgroup): %s failed: %s", p->bank2_lds, what, hipGetErrorString(e2));
             ake_cqt_plan_destroy(p);
             return AKE_ERR_HIP;
+        }
+        int lds_rc = ake::set_lds_limit(static_cast<int>(p->bank2_lds), cqt_bank_bf16_kernel);
+        if (!lds_rc && p->engine == 3 && p->hop_twos == 0)                   // a plan that can take per-clip hops
+            lds_rc = ake::set_lds_limit(static_cast<int>(p->bank2_lds), cqt_bank_rows_bf16_kernel);
+        if (lds_rc) {
+            ake_cqt_plan_destroy(p);
+            return lds_rc;
         }
     }
     *out = p;
@@ -1392,21 +1391,23 @@ int cqt_logmag_impl(const ake_cqt_plan* p, const float* audio, int batch, int64_
     auto fill_cascade = [&](CascArgs& a, int fused) { fill_cascade_on(a, fused, audio, audio_stride, n, n_clip); };
     auto launch_cascade = [&](const CascArgs& a) {
         dim3 grid((a.ticks_total + a.ticks_per_seg - 1) / a.ticks_per_seg, batch);
-        ake::ProfScope ps("cqt_cascade_kernel", stream);
         const bool split = a.ph[0] != nullptr;
+#define AKE_CASC(...) return ake::launch("cqt_cascade_kernel", cqt_cascade_kernel<__VA_ARGS__>, grid, dim3(NT), 0, stream, a)
         if (pcm) {                                                    // engine 3 only: always split
-            if (a.hops && p->half_len == 15) hipLaunchKernelGGL((cqt_cascade_kernel<8, C, NT, true, true, short>), grid, dim3(NT), 0, stream, a);
-            else if (a.hops) hipLaunchKernelGGL((cqt_cascade_kernel<12, C, NT, true, true, short>), grid, dim3(NT), 0, stream, a);
-            else if (p->half_len == 15) hipLaunchKernelGGL((cqt_cascade_kernel<8, C, NT, true, false, short>), grid, dim3(NT), 0, stream, a);
-            else hipLaunchKernelGGL((cqt_cascade_kernel<12, C, NT, true, false, short>), grid, dim3(NT), 0, stream, a);
+            if (a.hops && p->half_len == 15) AKE_CASC(8, C, NT, true, true, short);
+            else if (a.hops) AKE_CASC(12, C, NT, true, true, short);
+            else if (p->half_len == 15) AKE_CASC(8, C, NT, true, false, short);
+            else AKE_CASC(12, C, NT, true, false, short);
         }
-        else if (a.hops && p->half_len == 15) hipLaunchKernelGGL((cqt_cascade_kernel<8, C, NT, true, true>), grid, dim3(NT), 0, stream, a);
-        else if (a.hops) hipLaunchKernelGGL((cqt_cascade_kernel<12, C, NT, true, true>), grid, dim3(NT), 0, stream, a);
-        else if (p->half_len == 15 && split) hipLaunchKernelGGL((cqt_cascade_kernel<8, C, NT, true>), grid, dim3(NT), 0, stream, a);
-        else if (p->half_len == 15) hipLaunchKernelGGL((cqt_cascade_kernel<8, C, NT, false>), grid, dim3(NT), 0, stream, a);
-        else if (split) hipLaunchKernelGGL((cqt_cascade_kernel<12, C, NT, true>), grid, dim3(NT), 0, stream, a);
-        else hipLaunchKernelGGL((cqt_cascade_kernel<12, C, NT, false>), grid, dim3(NT), 0, stream, a);
+        else if (a.hops && p->half_len == 15) AKE_CASC(8, C, NT, true, true);
+        else if (a.hops) AKE_CASC(12, C, NT, true, true);
+        else if (p->half_len == 15 && split) AKE_CASC(8, C, NT, true);
+        else if (p->half_len == 15) AKE_CASC(8, C, NT, false);
+        else if (split) AKE_CASC(12, C, NT, true);
+        else AKE_CASC(12, C, NT, false);
+#undef AKE_CASC
     };
+    int rc;
     if (p->engine == 5) {
         // levels 0..4: cqt_stream_kernel (MFMA half-band stages in registers; split planes of levels 0..3 near the frame centres + level 4 as f32)
         sm::Args sa;
@@ -1439,8 +1440,7 @@ int cqt_logmag_impl(const ake_cqt_plan* p, const float* audio, int batch, int64_
         sa.chunks_per_seg = ((total + segs - 1) / segs + 7) / 8 * 8;
         {
             dim3 grid((total + sa.chunks_per_seg - 1) / sa.chunks_per_seg, n_groups);
-            ake::ProfScope ps("cqt_stream_kernel", stream);
-            hipLaunchKernelGGL(sm::cqt_stream_kernel, grid, dim3(64), 0, stream, sa);
+            if ((rc = ake::launch("cqt_stream_kernel", sm::cqt_stream_kernel, grid, dim3(64), 0, stream, sa))) return rc;
         }
         // levels 5..: engine 3's cascade on level 4 (as its "audio": index i <-> level-4 sample i - kNextPad, so its level l holds true
         // level 4 + l shifted by kNextPad >> l samples), which also writes level 4's own split plane
@@ -1456,12 +1456,11 @@ int cqt_logmag_impl(const ake_cqt_plan* p, const float* audio, int batch, int64_
             call2.xw[sm::kStages + l] = ca.ph[l] + (kNextPad >> l);
             call2.stride[sm::kStages + l] = pl;
         }
-        launch_cascade(ca);
+        if ((rc = launch_cascade(ca))) return rc;
         scratch = frames_major ? out : c.take<float>(static_cast<size_t>(batch) * T * p->cfg.n_bins);
         dim3 grid(static_cast<unsigned>((T + 7) / 8 * 8), p->n_oct, (batch + kBankClips - 1) / kBankClips);
-        ake::ProfScope ps("cqt_bank_bf16_kernel", stream);
-        hipLaunchKernelGGL(cqt_bank_bf16_kernel, grid, dim3(kBankThreads), p->bank2_lds, stream, call2, p->octs2_dev, p->table2_dev, batch,
-                           p->cfg.hop_length, p->hop_twos, scratch, static_cast<long long>(T) * p->cfg.n_bins, p->cfg.n_bins, static_cast<int>(T), 0);
+        rc = ake::launch("cqt_bank_bf16_kernel", cqt_bank_bf16_kernel, grid, dim3(kBankThreads), p->bank2_lds, stream, call2, p->octs2_dev, p->table2_dev,
+                         batch, p->cfg.hop_length, p->hop_twos, scratch, static_cast<long long>(T) * p->cfg.n_bins, p->cfg.n_bins, static_cast<int>(T), 0);
     } else if (p->engine == 3) {
         BankCall2 call2;
         std::memset(&call2, 0, sizeof(call2));
@@ -1485,7 +1484,7 @@ int cqt_logmag_impl(const ake_cqt_plan* p, const float* audio, int batch, int64_
             const long long need = static_cast<long long>(std::max(g.uh, 32 * g.n_blk - g.uh) + 8) << l;
             a.need[l] = !hops && 2 * need >= a.hop ? -1 : static_cast<int>(need);
         }
-        launch_cascade(a);
+        if ((rc = launch_cascade(a))) return rc;
         if (hops) {
             scratch = hw.scratch;
             const long long rows_stride = static_cast<long long>(batch) * out_frames;
@@ -1495,25 +1494,22 @@ int cqt_logmag_impl(const ake_cqt_plan* p, const float* audio, int batch, int64_
                 AKE_HIP_CHECK(hipMemsetAsync(hw.counts, 0, 2 * nc * sizeof(int), stream));
                 const dim3 grid_r(static_cast<unsigned>((rows_stride + kRowsPerGroup - 1) / kRowsPerGroup), p->n_oct);
                 const long long* nc_dev = reinterpret_cast<const long long*>(n_clip);
-                {
-                    ake::ProfScope ps("cqt_rows_count_kernel", stream);
-                    hipLaunchKernelGGL(cqt_rows_count_kernel, grid_r, dim3(kRowsThreads), 0, stream, nc_dev, hops, batch, static_cast<int>(n),
-                                       static_cast<int>(out_frames), hw.counts);
-                }
-                ake::ProfScope ps("cqt_rows_scatter_kernel", stream);
-                hipLaunchKernelGGL(cqt_rows_scatter_kernel, grid_r, dim3(kRowsThreads), 0, stream, nc_dev, hops, batch, static_cast<int>(n),
-                                   static_cast<int>(out_frames), hw.counts, hw.counts + nc, hw.rows, rows_stride, hw.chunks, slots, hw.n_chunks);
+                if ((rc = ake::launch("cqt_rows_count_kernel", cqt_rows_count_kernel, grid_r, dim3(kRowsThreads), 0, stream, nc_dev, hops, batch,
+                                      static_cast<int>(n), static_cast<int>(out_frames), hw.counts)))
+                    return rc;
+                if ((rc = ake::launch("cqt_rows_scatter_kernel", cqt_rows_scatter_kernel, grid_r, dim3(kRowsThreads), 0, stream, nc_dev, hops, batch,
+                                      static_cast<int>(n), static_cast<int>(out_frames), hw.counts, hw.counts + nc, hw.rows, rows_stride, hw.chunks, slots,
+                                      hw.n_chunks)))
+                    return rc;
             }
-            ake::ProfScope ps("cqt_bank_rows_bf16_kernel", stream);
-            hipLaunchKernelGGL(cqt_bank_rows_bf16_kernel, dim3(slots, p->n_oct), dim3(kBankThreads), p->bank2_lds, stream, call2, p->octs2_dev,
-                               p->table2_dev, hops, hw.rows, rows_stride, hw.chunks, slots, hw.n_chunks, static_cast<int>(out_frames), scratch,
-                               p->cfg.n_bins);
+            rc = ake::launch("cqt_bank_rows_bf16_kernel", cqt_bank_rows_bf16_kernel, dim3(slots, p->n_oct), dim3(kBankThreads), p->bank2_lds, stream, call2,
+                             p->octs2_dev, p->table2_dev, hops, hw.rows, rows_stride, hw.chunks, slots, hw.n_chunks, static_cast<int>(out_frames), scratch,
+                             p->cfg.n_bins);
         } else {
             scratch = frames_major ? out : c.take<float>(static_cast<size_t>(batch) * T * p->cfg.n_bins);
             dim3 grid(static_cast<unsigned>((T + 7) / 8 * 8), p->n_oct, (batch + kBankClips - 1) / kBankClips);
-            ake::ProfScope ps("cqt_bank_bf16_kernel", stream);
-            hipLaunchKernelGGL(cqt_bank_bf16_kernel, grid, dim3(kBankThreads), p->bank2_lds, stream, call2, p->octs2_dev, p->table2_dev, batch,
-                               p->cfg.hop_length, p->hop_twos, scratch, static_cast<long long>(T) * p->cfg.n_bins, p->cfg.n_bins, static_cast<int>(T), 0);
+            rc = ake::launch("cqt_bank_bf16_kernel", cqt_bank_bf16_kernel, grid, dim3(kBankThreads), p->bank2_lds, stream, call2, p->octs2_dev, p->table2_dev,
+                             batch, p->cfg.hop_length, p->hop_twos, scratch, static_cast<long long>(T) * p->cfg.n_bins, p->cfg.n_bins, static_cast<int>(T), 0);
         }
     } else {
         BankCall call;
@@ -1541,39 +1537,30 @@ int cqt_logmag_impl(const ake_cqt_plan* p, const float* audio, int batch, int64_
                 const long long need = static_cast<long long>(p->octs[l].uh + 24) << l;
                 a.need[l] = (2 * need >= a.hop || (l == fused && fused < p->n_oct - 1)) ? -1 : static_cast<int>(need);
             }
-            launch_cascade(a);
+            if ((rc = launch_cascade(a))) return rc;
         }
         for (int o = fused + 1; o < p->n_oct; ++o) {
             const int ls = call.count[o];
             float* y = const_cast<float*>(call.x[o]);
             dim3 grid((ls + kDecimOutPerBlock - 1) / kDecimOutPerBlock, batch);
-            ake::ProfScope ps("cqt_decimate_kernel", stream);
             const int in_pad = -call.lo[o - 1];
-#define AKE_DECIM(N_) hipLaunchKernelGGL((cqt_decimate_kernel<N_>), grid, dim3(kDecimThreads), 0, stream, call.x[o - 1], \
-                                         call.stride[o - 1], in_pad, call.count[o - 1], y, static_cast<long long>(ls), pad_of(p), ls, p->taps)
+#define AKE_DECIM(N_) rc = ake::launch("cqt_decimate_kernel", cqt_decimate_kernel<N_>, grid, dim3(kDecimThreads), 0, stream, call.x[o - 1], \
+                                       call.stride[o - 1], in_pad, call.count[o - 1], y, static_cast<long long>(ls), pad_of(p), ls, p->taps)
             if (p->half_len == 15) AKE_DECIM(8);
             else if (p->half_len == 23) AKE_DECIM(12);
             else AKE_DECIM(16);
 #undef AKE_DECIM
+            if (rc) return rc;
         }
         scratch = c.take<float>(static_cast<size_t>(batch) * T * p->cfg.n_bins);
         dim3 grid(static_cast<unsigned>(T), p->n_oct, (batch + 63) / 64);
-        ake::ProfScope ps("cqt_bank_kernel", stream);
-        hipLaunchKernelGGL(cqt_bank_kernel, grid, dim3(256), 0, stream, call, p->octs_dev, p->table_dev, batch,
-                           p->cfg.hop_length, p->hop_twos, scratch, static_cast<long long>(T) * p->cfg.n_bins, p->cfg.n_bins);
+        rc = ake::launch("cqt_bank_kernel", cqt_bank_kernel, grid, dim3(256), 0, stream, call, p->octs_dev, p->table_dev, batch, p->cfg.hop_length,
+                         p->hop_twos, scratch, static_cast<long long>(T) * p->cfg.n_bins, p->cfg.n_bins);
     }
-    if (frames_major) {
-        AKE_HIP_CHECK(hipGetLastError());
-        return AKE_OK;
-    }
-    {
-        dim3 grid((p->cfg.n_bins + 31) / 32, static_cast<unsigned>((out_frames + 31) / 32), batch);
-        ake::ProfScope ps("cqt_transpose_kernel", stream);
-        hipLaunchKernelGGL(cqt_transpose_kernel, grid, dim3(256), 0, stream, scratch, out, static_cast<int>(T), p->cfg.n_bins,
-                           static_cast<int>(out_frames), reinterpret_cast<const long long*>(n_clip), p->cfg.hop_length, hops, static_cast<long long>(n));
-    }
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    if (rc || frames_major) return rc;
+    dim3 grid((p->cfg.n_bins + 31) / 32, static_cast<unsigned>((out_frames + 31) / 32), batch);
+    return ake::launch("cqt_transpose_kernel", cqt_transpose_kernel, grid, dim3(256), 0, stream, scratch, out, static_cast<int>(T), p->cfg.n_bins,
+                       static_cast<int>(out_frames), reinterpret_cast<const long long*>(n_clip), p->cfg.hop_length, hops, static_cast<long long>(n));
 }
 
 }  // namespace

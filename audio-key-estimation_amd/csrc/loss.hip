@@ -386,11 +386,8 @@ int general_step_launch(const float* key_out, const float* tonic_out, const floa
     a.B = batch; a.key_w = key_weight; a.tonic_w = tonic_weight; a.genre_w = genre_weight; a.use_cos = use_cos; a.weight = sample_weight;
     a.scalars = scalars_out; a.d_key = d_key; a.d_tonic = d_tonic; a.d_genre = genre_out ? d_genre : nullptr;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    ake::ProfScope ps("general_step_kernel", s);
-    if (sample_weight) hipLaunchKernelGGL(general_step_kernel<true>, dim3(1), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(general_step_kernel<false>, dim3(1), dim3(256), 0, s, a);
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    return sample_weight ? ake::launch("general_step_kernel", general_step_kernel<true>, dim3(1), dim3(256), 0, s, a)
+                         : ake::launch("general_step_kernel", general_step_kernel<false>, dim3(1), dim3(256), 0, s, a);
 }
 
 }  // namespace
@@ -441,13 +438,7 @@ extern "C" int ake_general_step_local_f32(const float* key_out, const float* ton
     a.key_w = key_weight; a.tonic_w = tonic_weight;
     a.part = static_cast<double*>(workspace); a.scalars = scalars_out; a.d_key = d_key; a.d_tonic = d_tonic;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    {
-        ake::ProfScope ps("general_step_local_kernel", s);
-        hipLaunchKernelGGL(general_step_local_kernel, dim3(a.chunks, batch), dim3(kLocRows), 0, s, a);
-        AKE_HIP_CHECK(hipGetLastError());
-    }
-    ake::ProfScope ps("general_step_local_finish_kernel", s);
-    hipLaunchKernelGGL(general_step_local_finish_kernel, dim3(1), dim3(kLocFinish), 0, s, a);
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    const int rc = ake::launch("general_step_local_kernel", general_step_local_kernel, dim3(a.chunks, batch), dim3(kLocRows), 0, s, a);
+    if (rc) return rc;
+    return ake::launch("general_step_local_finish_kernel", general_step_local_finish_kernel, dim3(1), dim3(kLocFinish), 0, s, a);
 }

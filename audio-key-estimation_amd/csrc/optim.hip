@@ -39,10 +39,6 @@ extern "C" int ake_adam_step_f32(float* params, const float* grads, float* exp_a
     const double bc1 = 1.0 - std::pow(static_cast<double>(beta1), step);
     const double bc2 = 1.0 - std::pow(static_cast<double>(beta2), step);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    ake::ProfScope ps("adam_step_kernel", s);
-    hipLaunchKernelGGL(adam_step_kernel, dim3(static_cast<unsigned>((count + 255) / 256)), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq,
-                       trainable, count, static_cast<float>(lr / bc1), beta1, beta2, eps, weight_decay, static_cast<float>(std::sqrt(bc2)),
-                       grad_scale);
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    return ake::launch("adam_step_kernel", adam_step_kernel, dim3(static_cast<unsigned>((count + 255) / 256)), dim3(256), 0, s, params, grads,
+                       exp_avg, exp_avg_sq, trainable, count, lr / bc1, beta1, beta2, eps, weight_decay, std::sqrt(bc2), grad_scale);
 }

@@ -365,24 +365,24 @@ bool choose_tile(bool fullrows, int cin, int H, int KH, int T_out, int TB, int K
 }
 
 template <bool TRAIN>
-int launch_mfma_t(const PackedConv& pc, const MfmaArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
-#define AKE_MFMA(KU_, NT_, MT_) hipLaunchKernelGGL((conv_mfma_kernel<KU_, NT_, MT_, TRAIN>), grid, block, lds, s, a); return AKE_OK
-    if (pc.ku == 8 && pc.nt == 1) { AKE_MFMA(8, 1, 3); }
-    if (pc.ku == 8 && pc.nt == 2) { AKE_MFMA(8, 2, 3); }
-    if (pc.ku == 12 && pc.nt == 1) { AKE_MFMA(12, 1, 3); }
-    if (pc.ku == 24 && pc.nt == 1) { AKE_MFMA(24, 1, 3); }
-    if (pc.ku == 4 && pc.nt == 1) { AKE_MFMA(4, 1, 3); }
-    if (pc.ku == 4 && pc.nt == 2) { AKE_MFMA(4, 2, 3); }          // kernel_size 3: the genre head's (1, 3) conv
-    if (pc.ku == 20 && pc.nt == 1) { AKE_MFMA(20, 1, 3); }        // kernel_size 3 / 5: the heads' one-channel last convs (16 frames per column group)
+int launch_mfma_t(const char* name, const PackedConv& pc, const MfmaArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+#define AKE_MFMA(KU_, NT_, MT_) return ake::launch(name, conv_mfma_kernel<KU_, NT_, MT_, TRAIN>, grid, block, lds, s, a)
+    if (pc.ku == 8 && pc.nt == 1) AKE_MFMA(8, 1, 3);
+    if (pc.ku == 8 && pc.nt == 2) AKE_MFMA(8, 2, 3);
+    if (pc.ku == 12 && pc.nt == 1) AKE_MFMA(12, 1, 3);
+    if (pc.ku == 24 && pc.nt == 1) AKE_MFMA(24, 1, 3);
+    if (pc.ku == 4 && pc.nt == 1) AKE_MFMA(4, 1, 3);
+    if (pc.ku == 4 && pc.nt == 2) AKE_MFMA(4, 2, 3);              // kernel_size 3: the genre head's (1, 3) conv
+    if (pc.ku == 20 && pc.nt == 1) AKE_MFMA(20, 1, 3);            // kernel_size 3 / 5: the heads' one-channel last convs (16 frames per column group)
 #undef AKE_MFMA
     ake::set_error("conv: no MFMA kernel for KU=%d NT=%d", pc.ku, pc.nt);
     return AKE_ERR_UNSUPPORTED;
 }
 
 // inference launches carry none of the training-mode code (pending BatchNorm on load, statistics, accumulation)
-int launch_mfma(const PackedConv& pc, const MfmaArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+int launch_mfma(const char* name, const PackedConv& pc, const MfmaArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
     const bool train = a.c.in_affine || a.c.stats || a.c.accumulate || a.c.rows_zero;      // (rows_zero: only the TRAIN form's loader zero-pads the rows)
-    return train ? launch_mfma_t<true>(pc, a, grid, block, lds, s) : launch_mfma_t<false>(pc, a, grid, block, lds, s);
+    return train ? launch_mfma_t<true>(name, pc, a, grid, block, lds, s) : launch_mfma_t<false>(name, pc, a, grid, block, lds, s);
 }
 
 struct Src {
@@ -394,12 +394,7 @@ struct ConvGeom {            // explicit geometry for the data-gradient convolut
     int py, pad_l, T_out, H_out, time_circ;
 };
 
-// One thread per element: `total` items in workgroups of 256 threads, timed under `label`.
-template <class... P, class... A>
-void launch_flat(const char* label, void (*kernel)(P...), hipStream_t s, long long total, A... args) {
-    ake::ProfScope ps(label, s);
-    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, static_cast<P>(args)...);
-}
+using ake::launch_flat;
 
 // What only some callers of run_conv set (the defaults are the inference forward's)
 struct ConvOpts {
@@ -460,8 +455,7 @@ int run_conv(const ake_pcnet* n, const PackedConv& pc, int kind, Src src, int ba
         t.lds = std::max<size_t>(t.lds, static_cast<size_t>(8) * MT * pc.nt * 64 * sizeof(float) * 4);
     }
     dim3 grid(t.n_row_tiles * t.n_time_tiles, pc.ntiles / pc.nt, batch), block(t.threads);
-    ake::ProfScope ps(name, s);
-    return launch_mfma(pc, ma, grid, block, t.lds, s);
+    return launch_mfma(name, pc, ma, grid, block, t.lds, s);
 }
 
 // does inference run layer i's Pitch2Pitch stack on the bf16 kernel (everything but its first conv)?
@@ -508,19 +502,13 @@ int run_p2p_f16(const ake_pcnet* n, const PackedConv& pc, const unsigned short* 
     AKE_REQUIRE(lds_of(a.R) <= 150 * 1024, AKE_ERR_UNSUPPORTED, "conv %s: %d frames do not fit the bf16 kernel's LDS patch", name, T);
     a.n_row_tiles = (H + a.R - 1) / a.R;
     static ake::DeviceOnce attr_set;
-    if (attr_set.need()) {
-        AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_p2p_f16_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_p2p_f16_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_p2p_f16_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        attr_set.mark();
-    }
+    const int rc = ake::raise_lds_limit(attr_set, 150 * 1024, conv_p2p_f16_kernel<true, false>, conv_p2p_f16_kernel<false, false>, conv_p2p_f16_kernel<true, true>);
+    if (rc) return rc;
     dim3 grid(a.n_row_tiles, 1, batch), block(512);
-    ake::ProfScope ps(name, s);
     AKE_REQUIRE(!nchw || oh, AKE_ERR_STATE, "conv %s: the assembling variant writes channels-last planes", name);
-    if (nchw) hipLaunchKernelGGL((conv_p2p_f16_kernel<true, true>), grid, block, lds_of(a.R), s, a);
-    else if (oh) hipLaunchKernelGGL((conv_p2p_f16_kernel<true, false>), grid, block, lds_of(a.R), s, a);
-    else hipLaunchKernelGGL((conv_p2p_f16_kernel<false, false>), grid, block, lds_of(a.R), s, a);
-    return AKE_OK;
+    if (nchw) return ake::launch(name, conv_p2p_f16_kernel<true, true>, grid, block, lds_of(a.R), s, a);
+    if (oh) return ake::launch(name, conv_p2p_f16_kernel<true, false>, grid, block, lds_of(a.R), s, a);
+    return ake::launch(name, conv_p2p_f16_kernel<false, false>, grid, block, lds_of(a.R), s, a);
 }
 
 // debug switch (ake_debug_keep_taps): keep every activation that ake_pcnet_tap_* can name in memory, i.e. no fusion across them
@@ -664,26 +652,19 @@ int run_p2p_f16_ps(const ake_pcnet* n, const PackedConv& pc, const P2pPsPlan& g,
         a.dst_clip_stride = static_cast<long long>(io.dst_ctot) * 12 * T;
     }
     static ake::DeviceOnce attr_set;
-    if (attr_set.need()) {
-        const void* fns[] = {reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<3, 0>),
-                             reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<1, 0>), reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<1, 5>),
-                             reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<1, 8>), reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<0, 0>),
-                             reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<2, 0>), reinterpret_cast<const void*>(conv_p2p_f16_ps_kernel<1, 3>)};
-        for (const void* f : fns) AKE_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set.mark();
-    }
+    const int rc = ake::raise_lds_limit(attr_set, 160 * 1024, conv_p2p_f16_ps_kernel<3, 0>, conv_p2p_f16_ps_kernel<1, 0>, conv_p2p_f16_ps_kernel<1, 5>,
+                                        conv_p2p_f16_ps_kernel<1, 8>, conv_p2p_f16_ps_kernel<0, 0>, conv_p2p_f16_ps_kernel<2, 0>, conv_p2p_f16_ps_kernel<1, 3>);
+    if (rc) return rc;
     dim3 grid(g.grid), block(512);
-    ake::ProfScope ps(name, s);
     switch (io.out) {
-        case P2pOut::SemiFold: hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<3, 0>), grid, block, g.lds, s, a); break;
-        case P2pOut::Semi: hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<2, 0>), grid, block, g.lds, s, a); break;
-        case P2pOut::Nchw: hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<0, 0>), grid, block, g.lds, s, a); break;
+        case P2pOut::SemiFold: return ake::launch(name, conv_p2p_f16_ps_kernel<3, 0>, grid, block, g.lds, s, a);
+        case P2pOut::Semi: return ake::launch(name, conv_p2p_f16_ps_kernel<2, 0>, grid, block, g.lds, s, a);
+        case P2pOut::Nchw: return ake::launch(name, conv_p2p_f16_ps_kernel<0, 0>, grid, block, g.lds, s, a);
         case P2pOut::Plane:
-            if (io.in == P2pIn::Planes) hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<1, 0>), grid, block, g.lds, s, a);
-            else if (io.in == P2pIn::SrcF16x4) hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<1, 3>), grid, block, g.lds, s, a);
-            else if (a.c0 + a.c1 <= 5) hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<1, 5>), grid, block, g.lds, s, a);
-            else hipLaunchKernelGGL((conv_p2p_f16_ps_kernel<1, 8>), grid, block, g.lds, s, a);
-            break;
+            if (io.in == P2pIn::Planes) return ake::launch(name, conv_p2p_f16_ps_kernel<1, 0>, grid, block, g.lds, s, a);
+            if (io.in == P2pIn::SrcF16x4) return ake::launch(name, conv_p2p_f16_ps_kernel<1, 3>, grid, block, g.lds, s, a);
+            if (a.c0 + a.c1 <= 5) return ake::launch(name, conv_p2p_f16_ps_kernel<1, 5>, grid, block, g.lds, s, a);
+            return ake::launch(name, conv_p2p_f16_ps_kernel<1, 8>, grid, block, g.lds, s, a);
     }
     return AKE_OK;
 }
@@ -744,14 +725,9 @@ int run_p2p_stack(const ake_pcnet* n, const std::vector<PackedConv>& convs, cons
         }
     }
     static ake::DeviceOnce attr_set;
-    if (attr_set.need()) {
-        AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(p2p_stack_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set.mark();
-    }
-    dim3 grid(batch), block(1024);
-    ake::ProfScope ps(name, s);
-    hipLaunchKernelGGL(p2p_stack_kernel, grid, block, g.lds, s, sa);
-    return AKE_OK;
+    const int rc = ake::raise_lds_limit(attr_set, 160 * 1024, p2p_stack_kernel);
+    if (rc) return rc;
+    return ake::launch(name, p2p_stack_kernel, dim3(batch), dim3(1024), g.lds, s, sa);
 }
 
 // ---- 7 x 7 circular pitch convolution with f32-equivalent products (conv_p2p_f16x3_kernel, persistent): train-mode forward (in_aff,
@@ -804,29 +780,22 @@ int run_p2p_f16x3(const ake_pcnet* n, const P2pX3Plan& g, long long frag_off, co
     a.dst = dst; a.dst_clip_stride = static_cast<long long>(cout) * H * T; a.cout = cout;
     a.stats = stats; a.stats_stride = stats_stride; a.in_amax = o.in_amax; a.lrelu = o.lrelu ? 1 : 0;
     static ake::DeviceOnce attr_set;
-    if (attr_set.need()) {
-        AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_p2p_f16x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set.mark();
-    }
-    dim3 grid(g.grid), block(512);
-    ake::ProfScope ps(name, s);
-    hipLaunchKernelGGL(conv_p2p_f16x3_kernel, grid, block, g.lds, s, a);
-    return AKE_OK;
+    const int rc = ake::raise_lds_limit(attr_set, 160 * 1024, conv_p2p_f16x3_kernel);
+    if (rc) return rc;
+    return ake::launch(name, conv_p2p_f16x3_kernel, dim3(g.grid), dim3(512), g.lds, s, a);
 }
 
 // semitone maps [clip][C][S][T] (aff: raw, with their pending table) -> channels [coff, coff + C) of the concat buffer
 // [clip][ctot][12][T]: max over the octaves
 int run_fold_max(const char* label, const float* smap, const float* aff, int C, int S, int batch, int T, float* dst, int dst_ctot, int dst_coff, hipStream_t s) {
     const long long total = static_cast<long long>(batch) * C * 12 * T;
-    launch_flat(label, fold_max_kernel, s, total, smap, aff, C, S, T, dst, static_cast<long long>(dst_ctot) * 12 * T, dst_coff, total);
-    return AKE_OK;
+    return launch_flat(label, fold_max_kernel, s, total, smap, aff, C, S, T, dst, static_cast<long long>(dst_ctot) * 12 * T, dst_coff, total);
 }
 
 // NCHW f32 [clip][C][12][T] -> channels-last split planes [clip][12][T][16] (hi plane, then lo plane, at `planes`)
 int run_nchw_to_cl16(const float* src, int C, int batch, int T, unsigned short* planes, hipStream_t s) {
     const long long npos = static_cast<long long>(batch) * 12 * T;
-    launch_flat("nchw_to_cl16_kernel", nchw_to_cl16_kernel, s, npos, src, static_cast<long long>(C) * 12 * T, C, T, planes, planes + npos * 16, npos);
-    return AKE_OK;
+    return launch_flat("nchw_to_cl16_kernel", nchw_to_cl16_kernel, s, npos, src, static_cast<long long>(C) * 12 * T, C, T, planes, planes + npos * 16, npos);
 }
 
 // does inference run the last layer's pitch-class stack + its time pooling as ONE launch (pc2pc_fused_kernel)?  The stack's
@@ -851,13 +820,9 @@ int run_pc2pc_fused(const ake_pcnet* n, int i, const float* src, int cin, int ba
     a.T = T; a.Tp = T + 8;
     const size_t lds = (static_cast<size_t>(4) * 12 * a.Tp * 2 + 2 * 512) * sizeof(uint4);
     static ake::DeviceOnce attr_set;
-    if (attr_set.need()) {
-        AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pc2pc_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set.mark();
-    }
-    ake::ProfScope ps("pc2pc_fused_kernel", s);
-    hipLaunchKernelGGL(pc2pc_fused_kernel, dim3(batch), dim3(1024), lds, s, a);
-    return AKE_OK;
+    const int rc = ake::raise_lds_limit(attr_set, 160 * 1024, pc2pc_fused_kernel);
+    if (rc) return rc;
+    return ake::launch("pc2pc_fused_kernel", pc2pc_fused_kernel, dim3(batch), dim3(1024), lds, s, a);
 }
 
 // does the f16 x 3 training form of conv_pc_bf16_kernel take this convolution (fragments built, patch fits the LDS)?
@@ -873,10 +838,10 @@ bool pc_f16x3_ok(const PackedConv& pt, int T_in, bool same_time) {
 // (src_ctot > 0: src points at the first of C channels inside a tensor of src_ctot channels)
 // amax (data gradients): the bits of the tensor's largest |value|; the planes then hold value * f16_weight_scale(max) and the convolution
 // that reads them (PcBfArgs::in_amax) divides it out again
-void run_nchw_to_cl16_f16x2(const float* src, int C, int batch, int T, const float* aff, unsigned short* planes, hipStream_t s, int src_ctot = 0,
-                            const unsigned int* amax = nullptr) {
+int run_nchw_to_cl16_f16x2(const float* src, int C, int batch, int T, const float* aff, unsigned short* planes, hipStream_t s, int src_ctot = 0,
+                           const unsigned int* amax = nullptr) {
     const long long npos = static_cast<long long>(batch) * 12 * T;
-    launch_flat("nchw_to_cl16_f16x2_kernel", nchw_to_cl16_f16x2_kernel, s, npos, src, static_cast<long long>(src_ctot > 0 ? src_ctot : C) * 12 * T, C, T, aff, planes,
+    return launch_flat("nchw_to_cl16_f16x2_kernel", nchw_to_cl16_f16x2_kernel, s, npos, src, static_cast<long long>(src_ctot > 0 ? src_ctot : C) * 12 * T, C, T, aff, planes,
                 planes + npos * 16, npos, amax);
 }
 
@@ -917,26 +882,18 @@ int run_pc_bf16(const ake_pcnet* n, const PackedConv& pc, const unsigned short* 
     const size_t lds = (static_cast<size_t>(2) * 12 * a.Tp * 2 + 2 * 4 * ((pc.cout + 15) / 16) * 2 * 64) * sizeof(uint4);   // patch + weight ring
     AKE_REQUIRE(lds <= 150 * 1024, AKE_ERR_UNSUPPORTED, "conv %s: %d frames do not fit the bf16 kernel's LDS patch", name, T_in);
     static ake::DeviceOnce attr_set;
-    if (attr_set.need()) {
-        AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_pc_bf16_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_pc_bf16_kernel<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_pc_bf16_kernel<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_pc_bf16_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_pc_bf16_kernel<1, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_pc_bf16_kernel<2, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        attr_set.mark();
-    }
+    const int rc = ake::raise_lds_limit(attr_set, 150 * 1024, conv_pc_bf16_kernel<1, true>, conv_pc_bf16_kernel<1, false>, conv_pc_bf16_kernel<2, false>,
+                                        conv_pc_bf16_kernel<2, true>, conv_pc_bf16_kernel<1, false, true>, conv_pc_bf16_kernel<2, false, true>);
+    if (rc) return rc;
     const int tiles = (H_out * a.T_out + 15) / 16;
     const int waves = std::min(8, (tiles + 3) / 4);
     dim3 grid((tiles + waves * 4 - 1) / (waves * 4), o.pc2 ? 2 : 1, batch), block(waves * 64);
-    ake::ProfScope ps(name, s);
-    if (o.f16x3 && pc.cout <= 16) hipLaunchKernelGGL((conv_pc_bf16_kernel<1, false, true>), grid, block, lds, s, a);
-    else if (o.f16x3) hipLaunchKernelGGL((conv_pc_bf16_kernel<2, false, true>), grid, block, lds, s, a);
-    else if (pc.cout == 16 && planes_out) hipLaunchKernelGGL((conv_pc_bf16_kernel<1, true>), grid, block, lds, s, a);
-    else if (pc.cout == 16) hipLaunchKernelGGL((conv_pc_bf16_kernel<1, false>), grid, block, lds, s, a);
-    else if (planes_out) hipLaunchKernelGGL((conv_pc_bf16_kernel<2, true>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((conv_pc_bf16_kernel<2, false>), grid, block, lds, s, a);
-    return AKE_OK;
+    if (o.f16x3 && pc.cout <= 16) return ake::launch(name, conv_pc_bf16_kernel<1, false, true>, grid, block, lds, s, a);
+    if (o.f16x3) return ake::launch(name, conv_pc_bf16_kernel<2, false, true>, grid, block, lds, s, a);
+    if (pc.cout == 16 && planes_out) return ake::launch(name, conv_pc_bf16_kernel<1, true>, grid, block, lds, s, a);
+    if (pc.cout == 16) return ake::launch(name, conv_pc_bf16_kernel<1, false>, grid, block, lds, s, a);
+    if (planes_out) return ake::launch(name, conv_pc_bf16_kernel<2, true>, grid, block, lds, s, a);
+    return ake::launch(name, conv_pc_bf16_kernel<2, false>, grid, block, lds, s, a);
 }
 
 // LDS of run_pc_f16x3_full's patch + weight ring for T_dz gradient frames (T_out = T_dz + 6, Tp = T_out + 8)
@@ -960,16 +917,12 @@ int run_pc_f16x3_full(const ake_pcnet* n, long long frag_off, int kh, const unsi
     const size_t lds = pc_f16x3_full_lds(T_dz);
     AKE_REQUIRE(pc_f16x3_full_ok(T_dz), AKE_ERR_UNSUPPORTED, "conv %s: %d frames do not fit the kernel's LDS patch", name, T_dz);
     static ake::DeviceOnce attr_set;
-    if (attr_set.need()) {
-        AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_pc_bf16_kernel<1, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        attr_set.mark();
-    }
+    const int rc = ake::raise_lds_limit(attr_set, 150 * 1024, conv_pc_bf16_kernel<1, false, true>);
+    if (rc) return rc;
     const int tiles = (12 * a.T_out + 15) / 16;
     const int waves = std::min(8, (tiles + 3) / 4);
     dim3 grid((tiles + waves * 4 - 1) / (waves * 4), 1, batch), block(waves * 64);
-    ake::ProfScope ps(name, s);
-    hipLaunchKernelGGL((conv_pc_bf16_kernel<1, false, true>), grid, block, lds, s, a);
-    return AKE_OK;
+    return ake::launch(name, conv_pc_bf16_kernel<1, false, true>, grid, block, lds, s, a);
 }
 
 // the semitone kernels' arguments: src [B][pc.cin][P][T]; dst: channels [coff, ..) of [B][ctot][12][T] (semi_fold_kernel) or the dense
@@ -991,14 +944,12 @@ int run_semi(const ake_pcnet* n, const PackedConv& pc, const float* src, int bat
     const int per_clip = 12 * a.n_strips;
     const int threads = per_clip >= 256 ? 256 : (per_clip + 63) / 64 * 64;
     dim3 grid((per_clip + threads - 1) / threads, pc.groups, batch), block(threads);
-    ake::ProfScope ps(name, s);
     switch (pc.co) {
-        case 8: hipLaunchKernelGGL((semi_fold_kernel<8>), grid, block, 0, s, a); break;
-        case 4: hipLaunchKernelGGL((semi_fold_kernel<4>), grid, block, 0, s, a); break;
-        case 1: hipLaunchKernelGGL((semi_fold_kernel<1>), grid, block, 0, s, a); break;
+        case 8: return ake::launch(name, semi_fold_kernel<8>, grid, block, 0, s, a);
+        case 4: return ake::launch(name, semi_fold_kernel<4>, grid, block, 0, s, a);
+        case 1: return ake::launch(name, semi_fold_kernel<1>, grid, block, 0, s, a);
         default: ake::set_error("semi: bad CO"); return AKE_ERR_UNSUPPORTED;
     }
-    return AKE_OK;
 }
 
 // A tensor and the pending BatchNorm + LeakyReLU table its readers apply while loading (null: the tensor is final), see Fwd
@@ -1906,10 +1857,7 @@ int rebuild_dense_affine(ake_pcnet* n, const float* params_dev, hipStream_t s) {
         if (rc) return rc;
         AKE_HIP_CHECK(hipMalloc(&n->dense_aff_dev, n->dense_aff_floats * sizeof(float)));
     }
-    ake::ProfScope ps("dense_affine_kernel", s);
-    hipLaunchKernelGGL(dense_affine_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, params_dev, n->dense_aff_idx_dev, n->dense_aff_dev, rows);
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    return launch_flat("dense_affine_kernel", dense_affine_kernel, s, rows, params_dev, n->dense_aff_idx_dev, n->dense_aff_dev, rows);
 }
 
 int build_fold_tables(ake_pcnet* n) {
@@ -2064,26 +2012,30 @@ int rebuild_bf16_frags(ake_pcnet* n, hipStream_t s, bool train_only = false) {
         AKE_HIP_CHECK(hipMalloc(&n->bf_frags_dev, count * sizeof(uint4)));
         n->bf_frags_count = count;
     }
-    ake::ProfScope ps("pack_bf16_kernels", s);
+    ake::ProfScope ps("pack_bf16_kernels", s);               // one timer entry for all the packing launches of a load
+    int rc;
     // train_only (ake_pcnet_load_for_training_f32, after every optimizer step): only the fragments the training-mode forward and the backward
     // read -- the inference kernels' (20 of the 40 launches; 0.2 ms of a 7 ms step) are rebuilt by the next full load
     n->eval_frags_stale = train_only;
     if (!train_only)
     for (const auto& layer : n->p2p)
         for (const PackedConv& pc : layer)
-            if (pc.bf_off >= 0)
-                hipLaunchKernelGGL(pack_p2p_f16_kernel, dim3((14 * 64 + 255) / 256), dim3(256), 0, s, n->blob_dev + pc.w_off, n->bf_frags_dev + pc.bf_off, pc.cin);
+            if (pc.bf_off >= 0 && (rc = ake::launch_untimed("pack_p2p_f16_kernel", pack_p2p_f16_kernel, dim3((14 * 64 + 255) / 256), dim3(256), 0, s,
+                                                            n->blob_dev + pc.w_off, n->bf_frags_dev + pc.bf_off, pc.cin)))
+                return rc;
     if (!train_only)
     for (const PackedConv* pc : pcs)
         if (pc->bf_off >= 0) {
             const int NT = pc->cout / 16;
-            hipLaunchKernelGGL(pack_pc_bf16_kernel, dim3((pc->kh * 4 * NT * 64 + 255) / 256), dim3(256), 0, s, n->blob_dev + pc->w_off,
-                               n->bf_frags_dev + pc->bf_off, pc->cin, pc->cout, pc->co, NT, pc->kh);
+            if ((rc = ake::launch_untimed("pack_pc_bf16_kernel", pack_pc_bf16_kernel, dim3((pc->kh * 4 * NT * 64 + 255) / 256), dim3(256), 0, s,
+                                          n->blob_dev + pc->w_off, n->bf_frags_dev + pc->bf_off, pc->cin, pc->cout, pc->co, NT, pc->kh)))
+                return rc;
         }
     if (!train_only && !n->pc2pc.empty())
         for (const PackedConv& pc : n->pc2pc[0])
-            if (pc.l0_off >= 0)
-                hipLaunchKernelGGL(pack_l0_f16_kernel, dim3(3), dim3(256), 0, s, n->blob_dev + pc.w_off, n->bf_frags_dev + pc.l0_off, pc.cin, pc.cout);
+            if (pc.l0_off >= 0 && (rc = ake::launch_untimed("pack_l0_f16_kernel", pack_l0_f16_kernel, dim3(3), dim3(256), 0, s, n->blob_dev + pc.w_off,
+                                                            n->bf_frags_dev + pc.l0_off, pc.cin, pc.cout)))
+                return rc;
     {   // the training-mode packs (pitch-class stacks, their data gradients, the heads' data gradients; the pitch convs' raw forms): ONE launch per
         // kernel for all of them, the jobs in the kernel argument (28 dependent launches of a few microseconds of work each were 0.39 ms per step)
         std::vector<PcPackJob> jobs;
@@ -2106,8 +2058,8 @@ int rebuild_bf16_frags(ake_pcnet* n, hipStream_t s, bool train_only = false) {
                 max_cout = std::max(max_cout, js.j[k].cout);
                 max_blocks = std::max(max_blocks, (js.j[k].KH * 4 * js.j[k].NT * 64 + 255) / 256);
             }
-            hipLaunchKernelGGL(pc_weight_scale_jobs_kernel, dim3(max_cout, js.n), dim3(256), 0, s, js);
-            hipLaunchKernelGGL(pack_pc_f16x3_jobs_kernel, dim3(max_blocks, js.n), dim3(256), 0, s, js);
+            if ((rc = ake::launch_untimed("pc_weight_scale_jobs_kernel", pc_weight_scale_jobs_kernel, dim3(max_cout, js.n), dim3(256), 0, s, js))) return rc;
+            if ((rc = ake::launch_untimed("pack_pc_f16x3_jobs_kernel", pack_pc_f16x3_jobs_kernel, dim3(max_blocks, js.n), dim3(256), 0, s, js))) return rc;
         }
         for (size_t j0 = 0; j0 < tfr.size(); j0 += kMaxPackJobs) {
             P2pRawJobs js;
@@ -2116,18 +2068,19 @@ int rebuild_bf16_frags(ake_pcnet* n, hipStream_t s, bool train_only = false) {
                 const TrainFrag& t = tfr[j0 + k];
                 js.j[k] = P2pRawJob{n->blob_dev + t.raw, n->bf_frags_dev + t.pc->bf_off, t.cin, t.cout, t.flip};
             }
-            hipLaunchKernelGGL(pack_p2p_f16_raw_jobs_kernel, dim3((14 * 64 + 255) / 256, js.n), dim3(256), 0, s, js);
+            if ((rc = ake::launch_untimed("pack_p2p_f16_raw_jobs_kernel", pack_p2p_f16_raw_jobs_kernel, dim3((14 * 64 + 255) / 256, js.n), dim3(256), 0, s, js)))
+                return rc;
         }
     }
     for (size_t i = 1; !train_only && i < n->semi.size(); ++i)
-        if (n->semi[i].bf_off >= 0)
-            hipLaunchKernelGGL(pack_semi_f16_kernel, dim3(1), dim3(192), 0, s, n->blob_dev + n->semi[i].w_off, n->bf_frags_dev + n->semi[i].bf_off);
+        if (n->semi[i].bf_off >= 0 && (rc = ake::launch_untimed("pack_semi_f16_kernel", pack_semi_f16_kernel, dim3(1), dim3(192), 0, s,
+                                                                n->blob_dev + n->semi[i].w_off, n->bf_frags_dev + n->semi[i].bf_off)))
+            return rc;
     if (!train_only)
     for (const PackedConv* pc : h1)
-        if (pc->bf_off >= 0)
-            hipLaunchKernelGGL(pack_head1_bf16_kernel, dim3((head1_ksteps(pc->kh) * 64 + 255) / 256), dim3(256), 0, s, n->blob_dev + pc->w_off,
-                               n->bf_frags_dev + pc->bf_off, pc->cin, pc->kh);
-    AKE_HIP_CHECK(hipGetLastError());
+        if (pc->bf_off >= 0 && (rc = ake::launch_untimed("pack_head1_bf16_kernel", pack_head1_bf16_kernel, dim3((head1_ksteps(pc->kh) * 64 + 255) / 256),
+                                                         dim3(256), 0, s, n->blob_dev + pc->w_off, n->bf_frags_dev + pc->bf_off, pc->cin, pc->kh)))
+            return rc;
     return AKE_OK;
 }
 
@@ -2189,20 +2142,11 @@ int load_from_device_impl(ake_pcnet* n, const float* params_dev, ake_stream_t st
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int P = static_cast<int>(n->grad_floats), NB = static_cast<int>(n->map_host.size());
-    {
-        ake::ProfScope ps("fold_params_kernel", s);
-        hipLaunchKernelGGL(fold_params_kernel, dim3((P + 255) / 256), dim3(256), 0, s, params_dev, n->fold_ch_dev, n->fold_bn_dev, n->folded_dev, P);
-    }
-    {
-        ake::ProfScope ps("gather_blob_kernel", s);
-        hipLaunchKernelGGL(gather_blob_kernel, dim3((NB + 255) / 256), dim3(256), 0, s, params_dev, n->folded_dev, n->map_dev, n->blob_dev, NB);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
-    {
-        int rc2 = rebuild_bf16_frags(n, s, train_only);
-        if (!rc2) rc2 = rebuild_dense_affine(n, params_dev, s);
-        if (rc2) return rc2;
-    }
+    int rc;
+    if ((rc = launch_flat("fold_params_kernel", fold_params_kernel, s, P, params_dev, n->fold_ch_dev, n->fold_bn_dev, n->folded_dev, P))) return rc;
+    if ((rc = launch_flat("gather_blob_kernel", gather_blob_kernel, s, NB, params_dev, n->folded_dev, n->map_dev, n->blob_dev, NB))) return rc;
+    if ((rc = rebuild_bf16_frags(n, s, train_only))) return rc;
+    if ((rc = rebuild_dense_affine(n, params_dev, s))) return rc;
     n->finalized = true;
     return AKE_OK;
 }
@@ -2214,11 +2158,8 @@ int ake_pcnet_update_running_stats_f32(const ake_pcnet* n, const float* bn_stats
     AKE_REQUIRE(n && bn_stats_dev && params_dev, AKE_ERR_INVALID, "update_running_stats: null argument");
     AKE_REQUIRE(n->finalized && n->run_off_dev, AKE_ERR_STATE, "update_running_stats: the handle has no parameters yet");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    ake::ProfScope ps("running_stats_kernel", s);
-    hipLaunchKernelGGL(running_stats_kernel, dim3((n->bn_channels + 63) / 64), dim3(64), 0, s, bn_stats_dev, n->run_off_dev, params_dev, momentum,
-                       n->bn_channels);
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    return ake::launch("running_stats_kernel", running_stats_kernel, dim3((n->bn_channels + 63) / 64), dim3(64), 0, s, bn_stats_dev, n->run_off_dev,
+                       params_dev, momentum, n->bn_channels);
 }
 
 // The BatchNorm layers whose forward the reference's BACKWARD pass runs a second time (checkpointed halves: every dense layer's norm1,
@@ -2232,11 +2173,8 @@ int ake_pcnet_update_recomputed_running_stats_f32(const ake_pcnet* n, const floa
     AKE_REQUIRE(bn_stats_dev && params_dev, AKE_ERR_INVALID, "update_recomputed_running_stats: null argument");
     AKE_REQUIRE(n->finalized && n->run_off2_dev, AKE_ERR_STATE, "update_recomputed_running_stats: the handle has no parameters yet");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    ake::ProfScope ps("running_stats_kernel", s);
-    hipLaunchKernelGGL(running_stats_kernel, dim3((n->bn_channels + 63) / 64), dim3(64), 0, s, bn_stats_dev, n->run_off2_dev, params_dev, momentum,
-                       n->bn_channels);
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    return ake::launch("running_stats_kernel", running_stats_kernel, dim3((n->bn_channels + 63) / 64), dim3(64), 0, s, bn_stats_dev, n->run_off2_dev,
+                       params_dev, momentum, n->bn_channels);
 }
 
 // BatchNorm layers of the training-mode forward, in forward order (valid after ake_pcnet_create; channel counts only
@@ -2282,15 +2220,14 @@ struct Fwd {
     float* p2pin_up(int i) const { return train ? b.aff_p2pin[i] + 3 * n->dims[i].prev_p : nullptr; }
 
     // launch BatchNorm finalisation of layer `bn` (count values per channel) into the affine table `aff_out`
-    void finalize_bn(int bn, double count, float* aff_out, float slope = kSlope) {
+    int finalize_bn(int bn, double count, float* aff_out, float slope = kSlope) {
         const auto& l = n->bns[bn];
-        ake::ProfScope ps("bn_finalize_kernel", s);
-        hipLaunchKernelGGL(bn_finalize_kernel, dim3((l.C + 63) / 64), dim3(64), 0, s, b.stats + 2 * l.ch_off, 2 * n->bn_channels, count,
-                           n->blob_dev + l.gamma_off, n->blob_dev + l.beta_off, aff_out, b.bstats + 3 * l.ch_off, l.C, slope);
         // the element count rides along for the unbiased running variance (written by the host-visible copy below)
+        return ake::launch("bn_finalize_kernel", bn_finalize_kernel, dim3((l.C + 63) / 64), dim3(64), 0, s, b.stats + 2 * l.ch_off, 2 * n->bn_channels,
+                           count, n->blob_dev + l.gamma_off, n->blob_dev + l.beta_off, aff_out, b.bstats + 3 * l.ch_off, l.C, slope);
     }
-    void identity(float* aff, int C) {
-        hipLaunchKernelGGL(affine_identity_kernel, dim3((C + 63) / 64), dim3(64), 0, s, aff, C);
+    int identity(float* aff, int C) {
+        return ake::launch_untimed("affine_identity_kernel", affine_identity_kernel, dim3((C + 63) / 64), dim3(64), 0, s, aff, C);
     }
 
     // conv (+BatchNorm `bn_name` + LeakyReLU unless bn_name is empty).  Returns via *aff_out_used whether dst is raw.
@@ -2310,7 +2247,7 @@ struct Fwd {
         if (has_bn) {
             const int T_out = same ? T_in : T_in - pt.kw + 1;
             const int H_out = kind == 2 ? H - pt.kh + 1 : H;
-            finalize_bn(bn, static_cast<double>(B) * H_out * T_out, aff_dst);
+            return finalize_bn(bn, static_cast<double>(B) * H_out * T_out, aff_dst);
         }
         return AKE_OK;
     }
@@ -2333,20 +2270,20 @@ struct Fwd {
         const double count = static_cast<double>(B) * H * T;
         const int sstride = 2 * n->bn_channels;
         int rc;
-        if (train) {
-            ake::ProfScope ps("channel_stats_kernel", s);
-            hipLaunchKernelGGL(channel_stats_kernel, dim3(cin, 1, B), dim3(256), 0, s, feat, static_cast<long long>(ctot) * H * T, static_cast<long long>(H) * T,
-                               b.stats + 2 * n->bns[packs[0].bn1].ch_off, sstride);
-        }
+        if (train && (rc = ake::launch("channel_stats_kernel", channel_stats_kernel, dim3(cin, 1, B), dim3(256), 0, s, feat, static_cast<long long>(ctot) * H * T,
+                                       static_cast<long long>(H) * T, b.stats + 2 * n->bns[packs[0].bn1].ch_off, sstride)))
+            return rc;
         for (size_t j = 0; j < packs.size(); ++j) {
             const DensePack& dp = packs[j];
             const int cj = cin + static_cast<int>(j) * nf;
             AKE_REQUIRE(dp.c1.cin == cj && cj + nf <= ctot && (!train || (dp.bn1 >= 0 && dp.bn2 >= 0)), AKE_ERR_STATE, "dense %s: channel bookkeeping", label);
             if (train && j > 0) {   // the statistics of channels [0, cj - nf): the previous norm1 has them (its own copy or the block input's)
                 const int C = cj - nf;
-                launch_flat("stats_copy_kernel", stats_copy_kernel, s, kStatSlots * 2 * C, b.stats, sstride, n->bns[packs[j - 1].bn1].ch_off, n->bns[dp.bn1].ch_off, C);
+                if ((rc = launch_flat("stats_copy_kernel", stats_copy_kernel, s, kStatSlots * 2 * C, b.stats, sstride, n->bns[packs[j - 1].bn1].ch_off,
+                                      n->bns[dp.bn1].ch_off, C)))
+                    return rc;
             }
-            if (train) finalize_bn(dp.bn1, count, aff1s[i][j], kSlope);                 // relu1 = nn.LeakyReLU
+            if (train && (rc = finalize_bn(dp.bn1, count, aff1s[i][j], kSlope))) return rc;   // relu1 = nn.LeakyReLU
             float* const bott_j = train ? botts[i][j] : bott;
             const ConvGeom g1{0, 3, T, H, 0};                  // the single tap sits at offset 3 of the 7 stored
             ConvOpts o1;
@@ -2354,7 +2291,7 @@ struct Fwd {
             if (train) o1.stats = b.stats + 2 * n->bns[dp.bn2].ch_off;
             if (kind == 0) o1.geom = &g1;
             if ((rc = run_conv(n, dp.c1, kind, Src{feat, cj, nullptr, 0, 0, ctot}, B, H, T, true, false, bott_j, dp.c1.cout, 0, s, label, o1))) return rc;
-            if (train) finalize_bn(dp.bn2, count, aff2s[i][j], 0.f);                    // relu2 = nn.ReLU
+            if (train && (rc = finalize_bn(dp.bn2, count, aff2s[i][j], 0.f))) return rc;      // relu2 = nn.ReLU
             const ConvGeom g2{k / 2, k / 2, T, H, 0};
             ConvOpts o2;
             o2.in_affine = train ? aff2s[i][j] : n->dense_aff_dev + dp.aff2;
@@ -2409,12 +2346,13 @@ struct Fwd {
             o2.in_affine = aff[1 + 3 * r];
             o2.stats = b.stats + 2 * n->bns[bn2].ch_off;
             if ((rc = run_conv(n, st[2 + 2 * r], kind, Src{z1, 2 * C, nullptr, 0, 0}, B, H, T, true, false, z2, C, 0, s, label, o2))) return rc;
-            finalize_bn(bn2, count, aff[2 + 3 * r], 1.f);
+            if ((rc = finalize_bn(bn2, count, aff[2 + 3 * r], 1.f))) return rc;
             const bool to_final = r == nb - 1 && final_dst;
             float* xo = to_final ? final_dst : z[3 + 3 * r];
             const long long total = static_cast<long long>(B) * C * H * T;
-            launch_flat("res_add_act_kernel", res_add_act_kernel, s, total, z2, aff[2 + 3 * r], x, x_aff, xo, C, H * T, to_final ? final_ctot : C, total);
-            identity(aff[3 + 3 * r], C);
+            if ((rc = launch_flat("res_add_act_kernel", res_add_act_kernel, s, total, z2, aff[2 + 3 * r], x, x_aff, xo, C, H * T, to_final ? final_ctot : C, total)))
+                return rc;
+            if ((rc = identity(aff[3 + 3 * r], C))) return rc;
             x = xo; x_aff = aff[3 + 3 * r];
         }
         return AKE_OK;
@@ -2425,14 +2363,12 @@ struct Fwd {
         const int per_clip = (P / 3) * ta.s.n_strips;
         const int threads = per_clip >= 256 ? 256 : (per_clip + 63) / 64 * 64;
         dim3 grid((per_clip + threads - 1) / threads, pc.groups, B), block(threads);
-        ake::ProfScope ps("semi_conv_stats_kernel", s);
         switch (pc.co) {
-            case 8: hipLaunchKernelGGL((semi_conv_stats_kernel<8>), grid, block, 0, s, ta); break;
-            case 4: hipLaunchKernelGGL((semi_conv_stats_kernel<4>), grid, block, 0, s, ta); break;
-            case 1: hipLaunchKernelGGL((semi_conv_stats_kernel<1>), grid, block, 0, s, ta); break;
+            case 8: return ake::launch("semi_conv_stats_kernel", semi_conv_stats_kernel<8>, grid, block, 0, s, ta);
+            case 4: return ake::launch("semi_conv_stats_kernel", semi_conv_stats_kernel<4>, grid, block, 0, s, ta);
+            case 1: return ake::launch("semi_conv_stats_kernel", semi_conv_stats_kernel<1>, grid, block, 0, s, ta);
             default: ake::set_error("semi: bad CO"); return AKE_ERR_UNSUPPORTED;
         }
-        return AKE_OK;
     }
 
     // pool_semi (+BN+LReLU) + octave fold of `src` [B][C][P][T] into channels [coff, coff+C) of dst [B][ctot][12][T]
@@ -2447,9 +2383,8 @@ struct Fwd {
             if ((rc = launch_semi_conv(pc, ta, P, B))) return rc;
             const PackedConv& fc = n->foldc[layer];
             const long long total = static_cast<long long>(B) * pc.cin * 12 * Tn;
-            launch_flat("fold_conv_kernel", fold_conv_kernel, s, total, b.smap, n->blob_dev + fc.w_off, n->blob_dev + fc.b_off, dst, pc.cin, P / 36, Tn, 1,
-                        static_cast<long long>(ctot) * 12 * Tn, coff, total);
-            return AKE_OK;
+            return launch_flat("fold_conv_kernel", fold_conv_kernel, s, total, b.smap, n->blob_dev + fc.w_off, n->blob_dev + fc.b_off, dst, pc.cin, P / 36, Tn, 1,
+                               static_cast<long long>(ctot) * 12 * Tn, coff, total);
         }
         if (!train) return run_semi(n, n->semi[layer], src, B, P, Tn, dst, ctot, coff, s, nm);
         const PackedConv& pc = n->semi_t[layer];
@@ -2459,42 +2394,40 @@ struct Fwd {
         ta.s = semi_args(n, pc, src, P, Tn, b.semi_raw[layer]);
         ta.in_affine = in_aff; ta.stats = b.stats + 2 * n->bns[bn].ch_off; ta.stats_stride = 2 * n->bn_channels;
         if ((rc = launch_semi_conv(pc, ta, P, B))) return rc;
-        finalize_bn(bn, static_cast<double>(B) * (P / 3) * Tn, b.aff_semi[layer]);
+        if ((rc = finalize_bn(bn, static_cast<double>(B) * (P / 3) * Tn, b.aff_semi[layer]))) return rc;
         const long long total = static_cast<long long>(B) * pc.cin * 12 * Tn;
         if (n->cfg.p2pc_conv) {   // models.py:108-133: the fold is a learned convolution over the octaves + BatchNorm (batch statistics) + LeakyReLU
             const PackedConv& fc = n->foldc_t[layer];
             const int bnf = bn_of("model." + std::to_string(layer) + ".pool.bn");
             AKE_REQUIRE(pc.cin <= 64, AKE_ERR_UNSUPPORTED, "p2pc_conv training: %d channels", pc.cin);
-            launch_flat("fold_conv_kernel", fold_conv_train_kernel, s, total, b.semi_raw[layer], b.aff_semi[layer], n->blob_dev + fc.w_off, n->blob_dev + fc.b_off,
-                        b.foldc_raw[layer], b.stats + 2 * n->bns[bnf].ch_off, 2 * n->bn_channels, pc.cin, P / 36, Tn, total);
-            finalize_bn(bnf, static_cast<double>(B) * 12 * Tn, b.aff_foldc[layer]);
+            if ((rc = launch_flat("fold_conv_kernel", fold_conv_train_kernel, s, total, b.semi_raw[layer], b.aff_semi[layer], n->blob_dev + fc.w_off,
+                                  n->blob_dev + fc.b_off, b.foldc_raw[layer], b.stats + 2 * n->bns[bnf].ch_off, 2 * n->bn_channels, pc.cin, P / 36, Tn, total)))
+                return rc;
+            if ((rc = finalize_bn(bnf, static_cast<double>(B) * 12 * Tn, b.aff_foldc[layer]))) return rc;
             // the folded channels are materialised as final activations: every reader of the concat buffer takes them as they are
-            launch_flat("apply_affine_kernel", apply_affine_kernel, s, total, b.foldc_raw[layer], b.aff_foldc[layer], dst, pc.cin, static_cast<long long>(12) * Tn, ctot,
-                        coff, total);
+            if ((rc = launch_flat("apply_affine_kernel", apply_affine_kernel, s, total, b.foldc_raw[layer], b.aff_foldc[layer], dst, pc.cin,
+                                  static_cast<long long>(12) * Tn, ctot, coff, total)))
+                return rc;
         } else if ((rc = run_fold_max("fold_affine_kernel", b.semi_raw[layer], b.aff_semi[layer], pc.cin, P / 3, B, Tn, dst, ctot, coff, s))) return rc;
-        if (aff_cat_rows) identity(aff_cat_rows, pc.cin);     // the folded channels are final activations
-        return AKE_OK;
+        return aff_cat_rows ? identity(aff_cat_rows, pc.cin) : AKE_OK;     // the folded channels are final activations
     }
 
     int up_sixth(int layer, const float* src, long long src_clip_stride, const float* in_aff, int B, int C, int Tn, float* dst, float* aff_dst) {
         const long long total = static_cast<long long>(B) * C * 36 * Tn;
-        if (!train) {
-            launch_flat("up_sixth_kernel", up_sixth_kernel<false>, s, total, src, src_clip_stride, nullptr, n->blob_dev + n->up[layer].w_off,
-                        n->blob_dev + n->up[layer].b_off, dst, nullptr, 0, C, Tn, total);
-            return AKE_OK;
-        }
+        if (!train)
+            return launch_flat("up_sixth_kernel", up_sixth_kernel<false>, s, total, src, src_clip_stride, nullptr, n->blob_dev + n->up[layer].w_off,
+                               n->blob_dev + n->up[layer].b_off, dst, nullptr, 0, C, Tn, total);
         const int bn = bn_of("model." + std::to_string(layer) + ".up_sixth_b");
         AKE_REQUIRE(C <= kBlockStatCh, AKE_ERR_UNSUPPORTED, "up_sixth training: %d channels", C);
-        launch_flat("up_sixth_train_kernel", up_sixth_kernel<true>, s, total, src, src_clip_stride, in_aff, n->blob_dev + n->up_t[layer].w_off,
-                    n->blob_dev + n->up_t[layer].b_off, dst, b.stats + 2 * n->bns[bn].ch_off, 2 * n->bn_channels, C, Tn, total);
-        finalize_bn(bn, static_cast<double>(B) * 36 * Tn, aff_dst);
-        return AKE_OK;
+        const int rc = launch_flat("up_sixth_train_kernel", up_sixth_kernel<true>, s, total, src, src_clip_stride, in_aff, n->blob_dev + n->up_t[layer].w_off,
+                                   n->blob_dev + n->up_t[layer].b_off, dst, b.stats + 2 * n->bns[bn].ch_off, 2 * n->bn_channels, C, Tn, total);
+        return rc ? rc : finalize_bn(bn, static_cast<double>(B) * 36 * Tn, aff_dst);
     }
 
-    void time_pool(const float* src, const float* in_aff, int B, int C, int H, int Tn, float* dst, int ctot, int coff) {
+    int time_pool(const float* src, const float* in_aff, int B, int C, int H, int Tn, float* dst, int ctot, int coff) {
         const int tp = n->cfg.time_pool_size;
         const long long total = static_cast<long long>(B) * C * H * (Tn / tp);
-        launch_flat("time_pool_kernel", time_pool_kernel, s, total, src, in_aff, dst, C, H, Tn, tp, ctot, coff, total);
+        return launch_flat("time_pool_kernel", time_pool_kernel, s, total, src, in_aff, dst, C, H, Tn, tp, ctot, coff, total);
     }
 
     // inference: semitone conv + BN + LeakyReLU of `src` [B][C][P][T] as a map of its own [B][C][P / 3][T] (raw = before the LeakyReLU)
@@ -2512,9 +2445,8 @@ struct Fwd {
         if (!n->cfg.p2pc_conv) return run_fold_max("fold_max_kernel", maps, nullptr, C, S, B, Tn, dst, ctot, coff, s);
         const PackedConv& fc = n->foldc[layer];
         const long long total = static_cast<long long>(B) * C * 12 * Tn;
-        launch_flat("fold_conv_kernel", fold_conv_kernel, s, total, maps, n->blob_dev + fc.w_off, n->blob_dev + fc.b_off, dst, C, S / 12, Tn, 0,
-                    static_cast<long long>(ctot) * 12 * Tn, coff, total);
-        return AKE_OK;
+        return launch_flat("fold_conv_kernel", fold_conv_kernel, s, total, maps, n->blob_dev + fc.w_off, n->blob_dev + fc.b_off, dst, C, S / 12, Tn, 0,
+                           static_cast<long long>(ctot) * 12 * Tn, coff, total);
     }
 
     // inference, default family: the whole of phase A as one launch, one workgroup per clip (the form and geometry are the route's)
@@ -2544,12 +2476,10 @@ struct Fwd {
         a.uw = n->blob_dev + n->up[1].w_off; a.ub = n->blob_dev + n->up[1].b_off;
         a.fold0 = b.fold0; a.psix = b.psix[1];
         a.H = P; a.T = T0; a.NF = NF; a.n_conv = c.conv_layers;
-        static ake::DeviceOnce attr_set;
-        if (attr_set.need()) {
-            AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(layer0_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-            AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(layer0_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kL0MaxLds)));
-            attr_set.mark();
-        }
+        static ake::DeviceOnce fused_attr, mfma_attr;
+        int rc;
+        if ((rc = ake::raise_lds_limit(fused_attr, 150 * 1024, layer0_fused_kernel))) return rc;
+        if ((rc = ake::raise_lds_limit(mfma_attr, static_cast<int>(kL0MaxLds), layer0_mfma_kernel))) return rc;
         a.mel_fm = r.frames_major ? 1 : 0;
         a.frag_lds = r.l0.frag_lds ? 1 : 0;
         a.img_tiled = r.l0.tiled ? 1 : 0; a.img_sq = r.l0.img_sq; a.img_sb = r.l0.img_sb; a.img_sr = r.l0.img_sr;
@@ -2557,10 +2487,8 @@ struct Fwd {
         AKE_REQUIRE(r.l0.lds <= kL0MaxLds, AKE_ERR_STATE, "pcnet: layer 0's one-launch form does not fit the LDS at this shape");
         a.taps = g_keep_taps ? 1 : 0;
         if (r.psix_f16) { a.psix_h = reinterpret_cast<uint2*>(b.psix[1]); a.psix = nullptr; a.melh = b.melh; }
-        ake::ProfScope ps("layer0_fused_kernel", s);
-        if (take_mfma) hipLaunchKernelGGL(layer0_mfma_kernel, dim3(B), dim3(512), r.l0.lds, s, a);
-        else hipLaunchKernelGGL(layer0_fused_kernel, dim3(B), dim3(512), r.l0.lds, s, a);
-        return AKE_OK;
+        if (take_mfma) return ake::launch("layer0_fused_kernel", layer0_mfma_kernel, dim3(B), dim3(512), r.l0.lds, s, a);
+        return ake::launch("layer0_fused_kernel", layer0_fused_kernel, dim3(B), dim3(512), r.l0.lds, s, a);
     }
 
     // Phase A, whole batch: layer 0 (models.py:361-369) and layer 1's up_sixth (models.py:372-374).
@@ -2595,7 +2523,7 @@ struct Fwd {
             if ((rc = res_stack_train(n->pc2pc_t[0], m, 1, Src{b.fold0, 1, nullptr, 0, 0}, nullptr, B, 12, T0, b.pcst[0], b.aff_pcst[0], b.cat[1], ctot1,
                                       "conv_mfma_kernel/pc2pc0")))
                 return rc;
-            identity(b.aff_cat[1], c.n_filters);
+            if ((rc = identity(b.aff_cat[1], c.n_filters))) return rc;
         } else if (c.resblock) {
             if ((rc = res_stack(n->pc2pc[0], 1, Src{b.fold0, 1, nullptr, 0, 0}, B, 12, T0, b.pca[0], b.pcb[0], b.cat[1], ctot1, "conv_mfma_kernel/pc2pc0"))) return rc;
         }
@@ -2610,9 +2538,8 @@ struct Fwd {
         }
         if (c.stay_sixth) return AKE_OK;                         // no up_sixth: the pitch classes are repeated as they are
         // psix's BatchNorm lands in rows [prev_p, ..) of the pitch-conv input table (row 0.. = the pitch stream itself)
-        if (train) identity(b.aff_p2pin[1], d1.prev_p);
-        if ((rc = up_sixth(1, b.cat[1], static_cast<long long>(ctot1) * 12 * T0, b.cat_slot(train, 1).aff, B, d1.prev_pc, T0, b.psix[1], p2pin_up(1)))) return rc;
-        return AKE_OK;
+        if (train && (rc = identity(b.aff_p2pin[1], d1.prev_p))) return rc;
+        return up_sixth(1, b.cat[1], static_cast<long long>(ctot1) * 12 * T0, b.cat_slot(train, 1).aff, B, d1.prev_pc, T0, b.psix[1], p2pin_up(1));
     }
 
     // Phase B, per chunk of clips [c0, c0+B): pitch convs -> semitone fold for every layer >= 1 (plus pc2pc / pooling /
@@ -2638,7 +2565,8 @@ struct Fwd {
                 if (i > 1 && (rc = up_sixth(i, pc_cur, static_cast<long long>(ctd) * 12 * Ti, nullptr, B, d.prev_pc, Ti, psixd, p2pin_up(i)))) return rc;
                 float* fp = b.pa[i];                                                  // [B][out_p][P][Ti]
                 const long long total = static_cast<long long>(B) * (cp + d.prev_pc) * P * Ti;
-                launch_flat("concat_repeat_kernel", concat_repeat_kernel, s, total, p_cur, cp, psixd, d.prev_pc, 36, fp, d.out_p, P, Ti, total, p2pin_up(i));
+                if ((rc = launch_flat("concat_repeat_kernel", concat_repeat_kernel, s, total, p_cur, cp, psixd, d.prev_pc, 36, fp, d.out_p, P, Ti, total, p2pin_up(i))))
+                    return rc;
                 if ((rc = dense_stack(i, 0, fp, d.out_p, cp + d.prev_pc, B, P, Ti, b.pb[i], "conv_mfma_kernel/p2p"))) return rc;
                 if ((rc = semi(i, fp, nullptr, B, P, Ti, catd, ctd, d.prev_pc, nullptr))) return rc;
                 if (last) return AKE_OK;                                              // its pitch-class block + pooling + heads run batch-wide
@@ -2647,8 +2575,8 @@ struct Fwd {
                 const int ctn = dn.prev_pc + dn.out_p + g;
                 const int Tn = Ti / tp;
                 float* catn = b.cat[i + 1] + (i + 1 == L - 1 ? static_cast<size_t>(c0) * ctn * 12 * Tn : 0);
-                time_pool(catd, nullptr, B, ctd, 12, Ti, catn, ctn, 0);
-                time_pool(fp, nullptr, B, d.out_p, P, Ti, b.ppool[i], d.out_p, 0);
+                if ((rc = time_pool(catd, nullptr, B, ctd, 12, Ti, catn, ctn, 0))) return rc;
+                if ((rc = time_pool(fp, nullptr, B, d.out_p, P, Ti, b.ppool[i], d.out_p, 0))) return rc;
                 pc_cur = catn; p_cur = b.ppool[i]; cp = d.out_p;
                 continue;
             }
@@ -2657,7 +2585,7 @@ struct Fwd {
             float* cat = b.cat[i] + (last || i == 1 ? static_cast<size_t>(c0) * ctot * 12 * Ti : 0);
             float* psix = b.psix[i] + (i == 1 ? static_cast<size_t>(c0) * d.prev_pc * 36 * Ti : 0);
             if (i > 1 && !c.stay_sixth) {   // layer 1's up_sixth ran batch-wide in entry(); pc_cur = pooled (final) features here
-                if (train) identity(b.aff_p2pin[i], d.prev_p);
+                if (train && (rc = identity(b.aff_p2pin[i], d.prev_p))) return rc;
                 if ((rc = up_sixth(i, pc_cur, static_cast<long long>(ctot) * 12 * Ti, nullptr, B, d.prev_pc, Ti, psix, p2pin_up(i)))) return rc;
             }
             // models.py:378-384  repeat + concat (never materialised) + pitch convs
@@ -2666,18 +2594,19 @@ struct Fwd {
                                   // in channels [0, prev_pc) of a concat buffer)
                 const float* pcs = i == 1 ? b.cat[1] + static_cast<size_t>(c0) * ctot * 12 * Ti : pc_cur;
                 const long long per_clip = static_cast<long long>(d.prev_pc) * 12 * Ti, total = per_clip * B;
-                launch_flat("slice_channels_kernel", slice_channels_kernel, s, total, pcs, static_cast<long long>(ctot) * 12 * Ti, b.pcd[i], per_clip, total);
+                if ((rc = launch_flat("slice_channels_kernel", slice_channels_kernel, s, total, pcs, static_cast<long long>(ctot) * 12 * Ti, b.pcd[i], per_clip, total)))
+                    return rc;
                 sdesc = Src{p_cur, cp, b.pcd[i], d.prev_pc, 12};
                 if (train) {   // the stack's input table: the pitch stream's rows, then the pitch classes' (they were copied raw)
                     if (i == 1) AKE_HIP_CHECK(hipMemcpyAsync(b.aff_p2pin[i], b.aff_semi[0], sizeof(float) * 3 * cp, hipMemcpyDeviceToDevice, s));
-                    else identity(b.aff_p2pin[i], cp);
+                    else if ((rc = identity(b.aff_p2pin[i], cp))) return rc;
                     AKE_HIP_CHECK(hipMemcpyAsync(b.aff_p2pin[i] + 3 * cp, b.aff_cat[i], sizeof(float) * 3 * d.prev_pc, hipMemcpyDeviceToDevice, s));
                 }
             }
             if (c.pc2p_mem) {   // models.py:376-377: no concat, the summed up_sixth map is added to the pitch stream
                 const long long total = static_cast<long long>(B) * cp * P * Ti;
                 // (training: psix is raw, its up_sixth_b table sits behind the pitch stream's identity rows; the sum itself is final)
-                launch_flat("pc2p_mem_kernel", pc2p_mem_kernel, s, total, p_cur, psix, b.pin[i], cp, d.prev_pc / cp, P, Ti, total, p2pin_up(i));
+                if ((rc = launch_flat("pc2p_mem_kernel", pc2p_mem_kernel, s, total, p_cur, psix, b.pin[i], cp, d.prev_pc / cp, P, Ti, total, p2pin_up(i)))) return rc;
                 sdesc = Src{b.pin[i], cp, nullptr, 0, 0};
             }
             const float* in_aff = train ? b.aff_p2pin[i] : nullptr;
@@ -2741,7 +2670,7 @@ struct Fwd {
                     if ((rc = run_p2p_f16x3(n, rk.x3[j > 0], px.bf_off, sdesc, in_aff, n->blob_dev + px.b_off, B, P, Ti, out.p, d.out_p,
                                             train ? b.stats + 2 * n->bns[bn].ch_off : nullptr, train ? 2 * n->bn_channels : 0, s, "conv_p2p_f16x3_kernel/p2p", ox)))
                         return rc;
-                    if (train) finalize_bn(bn, static_cast<double>(B) * P * Ti, out.aff);
+                    if (train && (rc = finalize_bn(bn, static_cast<double>(B) * P * Ti, out.aff))) return rc;
                 } else if ((rc = conv(n->p2p[i][j], train ? n->p2p_t[i][j] : n->p2p[i][j], m + "p2p.layer." + std::to_string(3 * j + 1), 0, sdesc,
                                       in_aff, B, P, Ti, true, out.p, d.out_p, 0, out.aff, "conv_mfma_kernel/p2p")))
                     return rc;
@@ -2754,7 +2683,7 @@ struct Fwd {
                 if ((rc = run_fold_max("fold_max_kernel", out.p, nullptr, d.out_p, P / 3, B, Ti, cat, ctot, d.prev_pc, s))) return rc;
             } else if (c.stay_sixth && train) {   // ... through the last conv's pending BatchNorm + LeakyReLU
                 if ((rc = run_fold_max("fold_affine_kernel", out.p, out.aff, d.out_p, P, B, Ti, cat, ctot, d.prev_pc, s))) return rc;
-                identity(b.aff_cat[i] + 3 * d.prev_pc, d.out_p);
+                if ((rc = identity(b.aff_cat[i] + 3 * d.prev_pc, d.out_p))) return rc;
             } else if (c.stay_sixth) {   // models.py:391: the stack's output is folded as it is (no semitone conv)
                 if ((rc = fold_maps(i, out.p, d.out_p, P, B, Ti, cat, ctot, d.prev_pc))) return rc;
             } else if ((rc = semi(i, out.p, out.aff, B, P, Ti, cat, ctot, d.prev_pc, train ? b.aff_cat[i] + 3 * d.prev_pc : nullptr))) return rc;
@@ -2783,9 +2712,9 @@ struct Fwd {
             const int ctn = dn.prev_pc + dn.out_p;
             const int Tn = Ti / tp;
             float* catn = b.cat[i + 1] + (i + 1 == L - 1 ? static_cast<size_t>(c0) * ctn * 12 * Tn : 0);
-            time_pool(pdst.p, pdst.aff, B, d.out_pc, 12, Ti, catn, ctn, 0);
-            if (train) identity(b.aff_cat[i + 1], d.out_pc);
-            time_pool(out.p, out.aff, B, d.out_p, P, Ti, b.ppool[i], d.out_p, 0);
+            if ((rc = time_pool(pdst.p, pdst.aff, B, d.out_pc, 12, Ti, catn, ctn, 0))) return rc;
+            if (train && (rc = identity(b.aff_cat[i + 1], d.out_pc))) return rc;
+            if ((rc = time_pool(out.p, out.aff, B, d.out_p, P, Ti, b.ppool[i], d.out_p, 0))) return rc;
             pc_cur = catn; p_cur = b.ppool[i]; cp = d.out_p;
         }
         return AKE_OK;
@@ -2813,7 +2742,7 @@ struct Fwd {
         const bool head_bf = r.heads != HeadForm::Generic;
         if (pc_fused) {
             if ((rc = run_pc2pc_fused(n, i, psrc.p, cin, B, Ti, b.pcf, head_bf ? b.feat_cl : nullptr, s))) return rc;
-        } else if (pc_bf) run_nchw_to_cl16(psrc.p, cin, B, Ti, reinterpret_cast<unsigned short*>(b.pcb[i]), s);
+        } else if (pc_bf && (rc = run_nchw_to_cl16(psrc.p, cin, B, Ti, reinterpret_cast<unsigned short*>(b.pcb[i]), s))) return rc;
         const char* const pc_label = L == 1 ? "conv_mfma_kernel/pc2pc0" : "conv_mfma_kernel/pc2pc";
         if (c.resblock && train) {
             if ((rc = res_stack_train(n->pc2pc_t[i], m, 1, Src{psrc.p, cin, nullptr, 0, 0}, psrc.aff, B, 12, Ti, b.pcst[i], b.aff_pcst[i], nullptr, 0, pc_label)))
@@ -2840,12 +2769,12 @@ struct Fwd {
             if (r.pc_x3_convs >> j & 1) {   // f16 x 3 MFMA (f32-equivalent products) instead of the f32 MFMA kernel
                 const PackedConv& pt = n->pc2pc_t[i][j];
                 unsigned short* planes = reinterpret_cast<unsigned short*>(b.pcb[i]);       // (the inference ping-pong buffer: idle in training)
-                run_nchw_to_cl16_f16x2(psrc.p, cin, B, Ti, psrc.aff, planes, s);
+                if ((rc = run_nchw_to_cl16_f16x2(psrc.p, cin, B, Ti, psrc.aff, planes, s))) return rc;
                 const int bn = bn_of(m + std::to_string(3 * j + 1));
                 PcBf16Opts o;
                 o.f16x3 = true; o.stats = b.stats + 2 * n->bns[bn].ch_off; o.stats_stride = 2 * n->bn_channels;
                 if ((rc = run_pc_bf16(n, pt, planes, B, Ti, true, false, pdst.p, nullptr, s, "conv_pc_f16x3_kernel/pc2pc", o))) return rc;
-                finalize_bn(bn, static_cast<double>(B) * 12 * Ti, pdst.aff);
+                if ((rc = finalize_bn(bn, static_cast<double>(B) * 12 * Ti, pdst.aff))) return rc;
             } else if ((rc = conv(n->pc2pc[i][j], train ? n->pc2pc_t[i][j] : n->pc2pc[i][j], m + std::to_string(3 * j + 1), 1,
                                   Src{psrc.p, cin, nullptr, 0, 0}, psrc.aff, B, 12, Ti, true, pdst.p, cout, 0, pdst.aff, pc_label)))
                 return rc;
@@ -2855,7 +2784,7 @@ struct Fwd {
         if (pc_fused) feat = Slot{b.pcf, nullptr};
         else if (L > 1) {   // models.py:396  (the pitch stream of the last layer feeds nothing: its pool is skipped)
             const int cout = c.denseblock ? n->final_ch : cout_default;
-            time_pool(pdst.p, pdst.aff, B, cout, 12, Ti, b.pcf, cout, 0);
+            if ((rc = time_pool(pdst.p, pdst.aff, B, cout, 12, Ti, b.pcf, cout, 0))) return rc;
             feat = Slot{b.pcf, nullptr};
         }
         // ---- heads (models.py:750-753) ----
@@ -2870,7 +2799,7 @@ struct Fwd {
         // key / tonic heads: the first convolution (16 -> 32 channels, most of a head's work) on the bf16 kernel; both read the same
         // channels-last copy of the features
         unsigned short* feat_cl = b.feat_cl;
-        if (head_bf && !pc_fused) run_nchw_to_cl16(feat.p, n->final_ch, B, Tf, feat_cl, s);
+        if (head_bf && !pc_fused && (rc = run_nchw_to_cl16(feat.p, n->final_ch, B, Tf, feat_cl, s))) return rc;
         const bool head1_bf = r.heads == HeadForm::Head1 || r.heads == HeadForm::Fused, genre_bf = r.genre_bf;
         const int T1 = r.T1, T2 = r.T2, TpB = r.TpB;
         // per-head tables of the two bf16 paths (key, tonic, genre), and the pooling of a finished map
@@ -2901,14 +2830,10 @@ struct Fwd {
             ha.fin_off = static_cast<int>(hf_lds / sizeof(float)) - 12 * T2;
             ha.pool = pool;
             static ake::DeviceOnce hf_attr;
-            if (hf_attr.need()) {
-                AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(heads_fused_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-                AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(heads_fused_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-                hf_attr.mark();
-            }
-            ake::ProfScope ps("heads_fused_kernel", s);
-            if (r.heads_mt == 3) hipLaunchKernelGGL(heads_fused_kernel<3>, dim3(nh_bf * B), dim3(512), hf_lds, s, ha);
-            else hipLaunchKernelGGL(heads_fused_kernel<4>, dim3(nh_bf * B), dim3(512), hf_lds, s, ha);
+            if ((rc = ake::raise_lds_limit(hf_attr, 150 * 1024, heads_fused_kernel<3>, heads_fused_kernel<4>))) return rc;
+            rc = r.heads_mt == 3 ? ake::launch("heads_fused_kernel", heads_fused_kernel<3>, dim3(nh_bf * B), dim3(512), hf_lds, s, ha)
+                                 : ake::launch("heads_fused_kernel", heads_fused_kernel<4>, dim3(nh_bf * B), dim3(512), hf_lds, s, ha);
+            if (rc) return rc;
             pooled_heads = nh_bf;
             Tm = T2;
         } else if (head1_bf) {
@@ -2940,13 +2865,9 @@ struct Fwd {
                 pooled_heads = nh_bf;
             }
             static ake::DeviceOnce h1_attr;
-            if (h1_attr.need()) {
-                AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_head1_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-                h1_attr.mark();
-            }
+            if ((rc = ake::raise_lds_limit(h1_attr, 150 * 1024, conv_head1_bf16_kernel))) return rc;
             AKE_REQUIRE(lds <= 150 * 1024, AKE_ERR_UNSUPPORTED, "heads: %d frames do not fit conv_head1_bf16_kernel", T1);
-            ake::ProfScope ps("conv_head1_bf16_kernel", s);
-            hipLaunchKernelGGL(conv_head1_bf16_kernel, dim3(B, nh_bf), dim3(512), lds, s, ha);
+            if ((rc = ake::launch("conv_head1_bf16_kernel", conv_head1_bf16_kernel, dim3(B, nh_bf), dim3(512), lds, s, ha))) return rc;
             Tm = T2;
         }
         for (int h = head1_bf ? nh_bf : 0; h < (c.genre ? 3 : 2); ++h) {
@@ -2964,7 +2885,7 @@ struct Fwd {
                 if (train && j == 0 && !lastj && pc_f16x3_ok((*heads[h].ct)[0], Tcur, false)) {   // the heads' first convs: f16 x 3 MFMA
                     const PackedConv& pt = (*heads[h].ct)[0];
                     if (!head_planes_ready) {               // one conversion of the pooled features serves the three heads
-                        run_nchw_to_cl16_f16x2(src.p, hc, B, Tcur, src.aff, b.feat_cl, s);
+                        if ((rc = run_nchw_to_cl16_f16x2(src.p, hc, B, Tcur, src.aff, b.feat_cl, s))) return rc;
                         head_planes_ready = true;
                     }
                     const int bn = bn_of(std::string(heads[h].nm) + ".1");
@@ -2974,7 +2895,7 @@ struct Fwd {
                                           h == 2 ? "conv_pc_f16x3_kernel/genre_head" : "conv_pc_f16x3_kernel/head", o)))
                         return rc;
                     const int H_out = heads[h].kind == 2 ? 12 - pt.kh + 1 : 12;
-                    finalize_bn(bn, static_cast<double>(B) * H_out * (Tcur - pt.kw + 1), dst.aff);
+                    if ((rc = finalize_bn(bn, static_cast<double>(B) * H_out * (Tcur - pt.kw + 1), dst.aff))) return rc;
                     continue;
                 }
                 if (train && lastj && j > 0 && pe.cout == 1 && pe.kw == 7 && !n->raw_w_off.empty()) {   // cin -> 1: one workgroup per clip, f32 VALU
@@ -2983,13 +2904,11 @@ struct Fwd {
                     const size_t lds = (static_cast<size_t>(hc) * 12 * Tcur + static_cast<size_t>(hc) * pe.kh * 7) * sizeof(float);
                     if (wi != n->spec_index.end() && bi != n->spec_index.end() && lds <= 150 * 1024 && Tcur - 6 >= 1) {
                         static ake::DeviceOnce hl_attr;
-                        if (hl_attr.need()) {
-                            AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_head_last_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-                            hl_attr.mark();
-                        }
-                        ake::ProfScope ps(h == 2 ? "conv_head_last_kernel/genre" : "conv_head_last_kernel", s);
-                        hipLaunchKernelGGL(conv_head_last_kernel, dim3(B), dim3(384), lds, s, src.p, src.aff, n->blob_dev + n->raw_w_off[wi->second],
-                                           n->blob_dev + n->raw_w_off[bi->second], dst.p, hc, pe.kh, heads[h].kind == 2 ? 0 : 1, Tcur, Tcur - 6);
+                        if ((rc = ake::raise_lds_limit(hl_attr, 150 * 1024, conv_head_last_kernel))) return rc;
+                        if ((rc = ake::launch(h == 2 ? "conv_head_last_kernel/genre" : "conv_head_last_kernel", conv_head_last_kernel, dim3(B), dim3(384), lds, s,
+                                              src.p, src.aff, n->blob_dev + n->raw_w_off[wi->second], n->blob_dev + n->raw_w_off[bi->second], dst.p, hc, pe.kh,
+                                              heads[h].kind == 2 ? 0 : 1, Tcur, Tcur - 6)))
+                            return rc;
                         continue;
                     }
                 }
@@ -3007,10 +2926,8 @@ struct Fwd {
             la.maps[0] = b.map_k; la.maps[1] = b.map_t; la.maps[2] = c.genre ? b.map_g : nullptr;
             la.outs[0] = key_out; la.outs[1] = tonic_out; la.outs[2] = genre_out;
             la.Tm = Tm; la.Tq = Tm - c.local + 1; la.W = c.local; la.batch = B;
-            ake::ProfScope ps("local_pool_kernel", s);
-            hipLaunchKernelGGL(local_pool_kernel, dim3(static_cast<unsigned>((static_cast<long long>(B) * 12 * Tm + 255) / 256), 3), dim3(256), 0, s, la);
-            AKE_HIP_CHECK(hipGetLastError());
-            return AKE_OK;
+            return ake::launch("local_pool_kernel", local_pool_kernel, dim3(static_cast<unsigned>((static_cast<long long>(B) * 12 * Tm + 255) / 256), 3), dim3(256),
+                               0, s, la);
         }
         // ---- masked temporal mean, sigmoid (models.py:754-804) ----
         PoolHeadArgs pa;
@@ -3021,12 +2938,7 @@ struct Fwd {
         pa.outs[0] = key_out; pa.outs[1] = tonic_out; pa.outs[2] = genre_out;
         pa.rows[0] = 12; pa.rows[1] = 12; pa.rows[2] = 11;
         pa.Tm = Tm; pa.batch = B; pa.pool = pool;
-        {
-            ake::ProfScope ps("head_pool_kernel", s);
-            hipLaunchKernelGGL(head_pool_kernel, dim3((B * 12 + 63) / 64, 3), dim3(64), 0, s, pa);
-        }
-        AKE_HIP_CHECK(hipGetLastError());
-        return AKE_OK;
+        return ake::launch("head_pool_kernel", head_pool_kernel, dim3((B * 12 + 63) / 64, 3), dim3(64), 0, s, pa);
     }
 };
 
@@ -3092,9 +3004,7 @@ int ake_pcnet_backward_f32(const ake_pcnet* n, const float* mel, int batch, int 
     Bwd bw{n, b, s, b.gslots, batch};
     rc = bw.run(mel, seq_length, d_key, d_tonic, d_genre, key_out);
     if (rc) return rc;
-    launch_flat("grad_reduce_kernel", grad_reduce_kernel, s, n->grad_floats, b.gslots, grads_out, static_cast<long long>(n->grad_floats), accumulate ? 1 : 0);
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    return launch_flat("grad_reduce_kernel", grad_reduce_kernel, s, n->grad_floats, b.gslots, grads_out, static_cast<long long>(n->grad_floats), accumulate ? 1 : 0);
 }
 
 int ake_pcnet_local_frames(const ake_pcnet* n, int frames, int* pooled_frames, int* map_frames) {
@@ -3305,10 +3215,8 @@ int ake_pcnet_tap_copy(const ake_pcnet* n, const char* name, int batch, int fram
     if (cl) {
         const long long total = shape[0] * shape[1] * shape[2] * shape[3];
         const unsigned short* h = reinterpret_cast<const unsigned short*>(p);
-        hipLaunchKernelGGL(cl_to_nchw_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), h,
-                           cl == 2 ? nullptr : h + total, out_dev, static_cast<int>(shape[1]), static_cast<int>(shape[2]), static_cast<int>(shape[3]), total);
-        AKE_HIP_CHECK(hipGetLastError());
-        return AKE_OK;
+        return ake::launch_untimed("cl_to_nchw_kernel", cl_to_nchw_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0,
+                                   static_cast<hipStream_t>(stream), h, cl == 2 ? nullptr : h + total, out_dev, shape[1], shape[2], shape[3], total);
     }
     AKE_HIP_CHECK(hipMemcpyAsync(out_dev, p, sizeof(float) * shape[0] * shape[1] * shape[2] * shape[3], hipMemcpyDeviceToDevice,
                                  static_cast<hipStream_t>(stream)));

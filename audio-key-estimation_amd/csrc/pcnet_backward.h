@@ -27,28 +27,24 @@ struct Bwd {
 
     // ga (gradient w.r.t. the activation a = lrelu(bn(z))) -> dz (gradient w.r.t. the raw conv output z), in place in `g`.
     // g and z share the layout [B][ctot][HT]; the BatchNorm layer `bn_name` owns channels [coff, coff + C).
-    void bn_block_backward(const std::string& bn_name, float* g, const float* z, const float* aff, int ctot, int coff, int HT) {
+    int bn_block_backward(const std::string& bn_name, float* g, const float* z, const float* aff, int ctot, int coff, int HT) {
         const int bn = bn_of(bn_name);
         const auto& l = n->bns[bn];
         double* st2 = b.stats2 + 3 * l.ch_off;
         const float* bst = b.bstats + 3 * l.ch_off;
         float* coef = b.coef + 4 * l.ch_off;
         dim3 grid(l.C, B);
-        {
-            ake::ProfScope ps("act_bwd_stats_kernel", s);
-            hipLaunchKernelGGL(act_bwd_stats_kernel, grid, dim3(256), 0, s, g, z, aff, bst, st2, static_cast<long long>(3) * n->bn_channels, ctot, coff, HT);
-        }
-        {
-            ake::ProfScope ps("bn_bwd_coef_kernel", s);
-            hipLaunchKernelGGL(bn_bwd_coef_kernel, dim3((l.C + 63) / 64), dim3(64), 0, s, st2, static_cast<long long>(3) * n->bn_channels, bst, n->blob_dev + l.gamma_off, coef,
-                               grad_of(bn_name + ".weight"), grad_of(bn_name + ".bias"), l.C);
-        }
+        int rc;
+        if ((rc = ake::launch("act_bwd_stats_kernel", act_bwd_stats_kernel, grid, dim3(256), 0, s, g, z, aff, bst, st2, static_cast<long long>(3) * n->bn_channels,
+                              ctot, coff, HT)))
+            return rc;
+        if ((rc = ake::launch("bn_bwd_coef_kernel", bn_bwd_coef_kernel, dim3((l.C + 63) / 64), dim3(64), 0, s, st2, static_cast<long long>(3) * n->bn_channels, bst,
+                              n->blob_dev + l.gamma_off, coef, grad_of(bn_name + ".weight"), grad_of(bn_name + ".bias"), l.C)))
+            return rc;
         unsigned int* cell = reinterpret_cast<unsigned int*>(b.stats2 + static_cast<size_t>(3) * n->bn_channels * kBwdStatSlots) + static_cast<size_t>(bn) * kAmaxSlots;
-        {
-            ake::ProfScope ps("bn_bwd_apply_kernel", s);
-            hipLaunchKernelGGL(bn_bwd_apply_kernel, grid, dim3(256), 0, s, g, z, aff, coef, ctot, coff, HT, cell);
-        }
+        if ((rc = ake::launch("bn_bwd_apply_kernel", bn_bwd_apply_kernel, grid, dim3(256), 0, s, g, z, aff, coef, ctot, coff, HT, cell))) return rc;
         amax_of = g; amax_cell = cell;
+        return AKE_OK;
     }
 
     // A weight-gradient kernel of n_wg workgroups and n_w weights leaves every workgroup's own sums in b.wg_partial where that buffer holds
@@ -59,9 +55,9 @@ struct Bwd {
         partial = b.wg_partial; partial_stride = n_w;
         return true;
     }
-    void reduce_partial(long long n_wg, long long n_w, gfx_t* dW) {
-        ake::ProfScope ps("wgrad_partial_reduce_kernel", s);
-        hipLaunchKernelGGL(wgrad_partial_reduce_kernel, dim3(static_cast<unsigned>((n_w + 63) / 64)), dim3(1024), 0, s, b.wg_partial, static_cast<int>(n_wg), n_w, dW);
+    int reduce_partial(long long n_wg, long long n_w, gfx_t* dW) {
+        return ake::launch("wgrad_partial_reduce_kernel", wgrad_partial_reduce_kernel, dim3(static_cast<unsigned>((n_w + 63) / 64)), dim3(1024), 0, s, b.wg_partial,
+                           n_wg, n_w, dW);
     }
 
     // weight gradient of one convolution: dW += corr(act(input), dz)
@@ -81,18 +77,12 @@ struct Bwd {
             dim3 grid((H + w.rows_per_wg - 1) / w.rows_per_wg, 1, B);
             const size_t lds = (static_cast<size_t>(2 * kWgARows + 2 * 64) * kWgKP + kWgKP) * sizeof(unsigned short);
             static ake::DeviceOnce attr_set;
-            if (attr_set.need()) {
-                AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_p2p_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-                attr_set.mark();
-            }
+            int rc = ake::raise_lds_limit(attr_set, 96 * 1024, conv_wgrad_p2p_bf16_kernel);
+            if (rc) return rc;
             const long long n_w = static_cast<long long>(8) * pc.cin * 49, n_wg = static_cast<long long>(grid.x) * B;
             const bool partial = use_partial(n_wg, n_w, w.partial, w.partial_stride);
-            {
-                ake::ProfScope ps("conv_wgrad_p2p_bf16_kernel", s);
-                hipLaunchKernelGGL(conv_wgrad_p2p_bf16_kernel, grid, dim3(256), lds, s, w);
-            }
-            if (partial) reduce_partial(n_wg, n_w, dW);
-            return AKE_OK;
+            rc = ake::launch("conv_wgrad_p2p_bf16_kernel", conv_wgrad_p2p_bf16_kernel, grid, dim3(256), lds, s, w);
+            return rc || !partial ? rc : reduce_partial(n_wg, n_w, dW);
         }
         // 12 x 7 pitch-class convolutions (the pitch-class stacks, the heads' first convs): split-bf16 MFMA, one workgroup per (clip, 16 x 16
         // channel block), see conv_wgrad_pc_f16x3_kernel
@@ -112,20 +102,14 @@ struct Bwd {
                 w.dW = dW; w.slot_stride = static_cast<long long>(n->grad_floats);
                 const size_t lds = static_cast<size_t>(2) * 12 * 16 * (w.AP + w.ZP) * sizeof(unsigned short);
                 static ake::DeviceOnce attr_set;
-                if (attr_set.need()) {
-                    AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_pc_f16x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-                    attr_set.mark();
-                }
+                int rc = ake::raise_lds_limit(attr_set, 128 * 1024, conv_wgrad_pc_f16x3_kernel);
+                if (rc) return rc;
                 const long long n_w = static_cast<long long>(pc.cout) * pc.cin * 84, n_wg = static_cast<long long>(B) * w.n_seg;
                 const bool partial = use_partial(n_wg, n_w, w.partial, w.partial_stride);
-                {
-                    const char* slash = std::strrchr(name, '/');
-                    const std::string pname = std::string("conv_wgrad_pc_f16x3_kernel") + (slash ? slash : "");
-                    ake::ProfScope ps(pname.c_str(), s);
-                    hipLaunchKernelGGL(conv_wgrad_pc_f16x3_kernel, dim3(w.n_seg * w.n_co_blocks, (pc.cin + 15) / 16, B), dim3(512), lds, s, w);
-                }
-                if (partial) reduce_partial(n_wg, n_w, dW);
-                return AKE_OK;
+                const char* slash = std::strrchr(name, '/');
+                const std::string pname = std::string("conv_wgrad_pc_f16x3_kernel") + (slash ? slash : "");
+                rc = ake::launch(pname.c_str(), conv_wgrad_pc_f16x3_kernel, dim3(w.n_seg * w.n_co_blocks, (pc.cin + 15) / 16, B), dim3(512), lds, s, w);
+                return rc || !partial ? rc : reduce_partial(n_wg, n_w, dW);
             }
         }
         // the kernel's accumulator tiles cover <= 32 output channels: wider convolutions (deeper / wider nets) run as slices of 32
@@ -182,18 +166,14 @@ struct Bwd {
             // partial sums per workgroup + an ordered reduction when the scratch buffer holds them (see WgradArgs::partial)
             const long long n_w = static_cast<long long>(co_n) * (src.c0 + src.c1) * KK, n_wg = static_cast<long long>(grid.x) * B;
             const bool partial = use_partial(n_wg, n_w, wa.partial, wa.partial_stride);
+            int rc = AKE_ERR_UNSUPPORTED;
             bool launched = false;
-            {
-                ake::ProfScope ps(name, s);
-    #define AKE_WG(M_, N_) if (!launched && MTC == M_ && NTK == N_) { hipLaunchKernelGGL((conv_wgrad_kernel<M_, N_>), grid, block, lds, s, wa); launched = true; }
-                AKE_WG(1, 4) AKE_WG(2, 4) AKE_WG(1, 6) AKE_WG(2, 6) AKE_WG(1, 1) AKE_WG(2, 1) AKE_WG(1, 2) AKE_WG(2, 2) AKE_WG(1, 3) AKE_WG(2, 3)
+    #define AKE_WG(M_, N_) if (!launched && MTC == M_ && NTK == N_) { rc = ake::launch(name, conv_wgrad_kernel<M_, N_>, grid, block, lds, s, wa); launched = true; }
+            AKE_WG(1, 4) AKE_WG(2, 4) AKE_WG(1, 6) AKE_WG(2, 6) AKE_WG(1, 1) AKE_WG(2, 1) AKE_WG(1, 2) AKE_WG(2, 2) AKE_WG(1, 3) AKE_WG(2, 3)
     #undef AKE_WG
-            }
-            if (!launched) {
-                ake::set_error("wgrad %s: no kernel for cout=%d taps=%d", name, co_n, KK);
-                return AKE_ERR_UNSUPPORTED;
-            }
-            if (partial) reduce_partial(n_wg, n_w, wa.dW);
+            if (!launched) ake::set_error("wgrad %s: no kernel for cout=%d taps=%d", name, co_n, KK);
+            if (rc) return rc;
+            if (partial && (rc = reduce_partial(n_wg, n_w, wa.dW))) return rc;
         }
         return AKE_OK;
     }
@@ -221,7 +201,8 @@ struct Bwd {
         // the transposed + flipped weights (f32-equivalent products; the f32 MFMA kernel took 0.17 ms per convolution and 256 clips)
         if (kind == 1 && same_time && planes_scratch && !accumulate && dst_coff == 0 && dst_ctot == pd.cout && T_dz == T_in && H == 12 &&
             pc_f16x3_ok(pd, T_dz, true)) {
-            run_nchw_to_cl16_f16x2(dz, pd.cin, B, T_dz, nullptr, planes_scratch, s, 0, amax_for(dz));
+            const int rc = run_nchw_to_cl16_f16x2(dz, pd.cin, B, T_dz, nullptr, planes_scratch, s, 0, amax_for(dz));
+            if (rc) return rc;
             PcBf16Opts o;
             o.f16x3 = true; o.in_amax = amax_for(dz);
             return run_pc_bf16(n, pd, planes_scratch, B, T_dz, true, false, dst, nullptr, s, "conv_pc_f16x3_kernel/pc2pc_dgrad", o);
@@ -235,7 +216,7 @@ struct Bwd {
             int rc2;
             for (int hf = 0; hf < 2; ++hf) {
                 unsigned short* pl = planes_scratch + hf * half;
-                run_nchw_to_cl16_f16x2(dz + static_cast<long long>(hf) * 16 * 12 * T_dz, 16, B, T_dz, nullptr, pl, s, 32, amax_for(dz));
+                if ((rc2 = run_nchw_to_cl16_f16x2(dz + static_cast<long long>(hf) * 16 * 12 * T_dz, 16, B, T_dz, nullptr, pl, s, 32, amax_for(dz)))) return rc2;
                 if ((rc2 = run_pc_f16x3_full(n, hf ? pd.bf_off2 : pd.bf_off, fwd.kh, pl, B, T_dz, dst, accumulate || hf == 1, s, "conv_pc_f16x3_kernel/head_dgrad",
                                              amax_for(dz))))
                     return rc2;
@@ -265,7 +246,7 @@ struct Bwd {
             PackedConv t2 = dp.c2;                         // true kernel size for the weight gradient (the pack may store 7 taps)
             t2.kh = kind == 1 ? 12 : k; t2.kw = k;
             if ((rc = wgrad(t2, kind, Src{botts[j], bott, nullptr, 0, 0}, aff2s[j], H, T, true, g_feat, ctot, cj, grad_of(dp.w2), wname, kind == 0))) return rc;
-            if (!dp.b2.empty()) bias_grad(g_feat, ctot, cj, nf, static_cast<int>(HT), grad_of(dp.b2));
+            if (!dp.b2.empty() && (rc = bias_grad(g_feat, ctot, cj, nf, static_cast<int>(HT), grad_of(dp.b2)))) return rc;
             {
                 const ConvGeom g2 = kind == 0 ? ConvGeom{k - 1 - k / 2, k - 1 - k / 2, T, H, 0} : ConvGeom{11, k - 1 - k / 2, T, H, 0};
                 ConvOpts o;
@@ -274,7 +255,7 @@ struct Bwd {
                                    dname, o)))
                     return rc;
             }
-            bn_block_backward(dp.norm2, g_bott, botts[j], aff2s[j], bott, 0, static_cast<int>(HT));
+            if ((rc = bn_block_backward(dp.norm2, g_bott, botts[j], aff2s[j], bott, 0, static_cast<int>(HT)))) return rc;
             // ---- conv1: bott_j = conv1(lrelu(norm1(feat[0, cj)))) (its bias, where it has one, is removed by norm2: zero gradient) ----
             PackedConv t1 = dp.c1;
             t1.kh = kind == 1 ? 12 : 1; t1.kw = 1;
@@ -285,11 +266,9 @@ struct Bwd {
                 o.geom = &g1; o.rows_zero = kind == 0;
                 if ((rc = run_conv(n, dp.d1, kind, Src{g_bott, bott, nullptr, 0, 0}, B, H, T, true, false, g_scr, ctot, 0, s, dname, o))) return rc;
             }
-            bn_block_backward(dp.norm1, g_scr, feat, aff1s[j], ctot, 0, static_cast<int>(HT));
-            {
-                const long long total = static_cast<long long>(B) * cj * HT;
-                launch_flat("add_channels_kernel", add_channels_kernel, s, total, g_feat, ctot, g_scr, ctot, cj, HT, total);
-            }
+            if ((rc = bn_block_backward(dp.norm1, g_scr, feat, aff1s[j], ctot, 0, static_cast<int>(HT)))) return rc;
+            const long long total = static_cast<long long>(B) * cj * HT;
+            if ((rc = launch_flat("add_channels_kernel", add_channels_kernel, s, total, g_feat, ctot, g_scr, ctot, cj, HT, total))) return rc;
         }
         return AKE_OK;
     }
@@ -309,8 +288,9 @@ struct Bwd {
                 const long long total = static_cast<long long>(B) * ctd * 12 * ((Tl / tp) + (Tl % tp ? 1 : 0));
                 const bool last = li == L - 1;
                 const int up_ctot = last ? ctd : n->dims[li + 1].prev_pc + n->dims[li + 1].out_p + g;
-                launch_flat("time_pool_bwd_kernel", time_pool_bwd_kernel, s, total, last ? b.g_pcf : b.g_cat[li + 1], b.cat[li], nullptr, b.g_cat[li], ctd, 12, Tl, tp,
-                            up_ctot, 0, total, 0);
+                if ((rc = launch_flat("time_pool_bwd_kernel", time_pool_bwd_kernel, s, total, last ? b.g_pcf : b.g_cat[li + 1], b.cat[li], nullptr, b.g_cat[li], ctd, 12,
+                                      Tl, tp, up_ctot, 0, total, 0)))
+                    return rc;
             }
             float* scr_pc = b.g_pc[li];                      // [B][ctd][12][Tl] scratch (g_pc[li] holds two of them)
             if ((rc = dense_block_backward(n->dense_pc[li], 1, b.cat[li], ctd, d.prev_pc + d.out_p, 12, Tl, b.g_cat[li], b.dn_gbott_pc, scr_pc, b.dn_bott_pc[li],
@@ -322,26 +302,26 @@ struct Bwd {
             if ((rc = semi_backward(li, b.pa[li], nullptr, b.g_cat[li], ctd, d.prev_pc, g_p))) return rc;
             if (li < L - 1) {   // second consumer of an inner layer's pitch features: their time-pooled copy is the next pitch block's input (channels [0, out_p))
                 const long long total = static_cast<long long>(B) * d.out_p * P * ((Tl / tp) + (Tl % tp ? 1 : 0));
-                launch_flat("time_pool_bwd_kernel", time_pool_bwd_kernel, s, total, b.g_p[li + 1], b.pa[li], nullptr, g_p, d.out_p, P, Tl, tp, n->dims[li + 1].out_p, 0,
-                            total, 1);
+                if ((rc = launch_flat("time_pool_bwd_kernel", time_pool_bwd_kernel, s, total, b.g_p[li + 1], b.pa[li], nullptr, g_p, d.out_p, P, Tl, tp,
+                                      n->dims[li + 1].out_p, 0, total, 1)))
+                    return rc;
             }
             if ((rc = dense_block_backward(n->dense_p[li], 0, b.pa[li], d.out_p, d.prev_p + d.prev_pc, P, Tl, g_p, b.dn_gbott_p, scr_p, b.dn_bott_p[li], b.dn_aff1_p[li],
                                            b.dn_aff2_p[li], "conv_wgrad_kernel/p2p", "conv_mfma_kernel/p2p_dgrad")))
                 return rc;
             {   // repeat (x P / 36) backward: channels [prev_p, prev_p + prev_pc) of the pitch block's input gradient -> the up_sixth map
                 const long long total = static_cast<long long>(B) * d.prev_pc * 36 * Tl;
-                launch_flat("repeat_sum_kernel", repeat_sum_kernel, s, total, g_p, b.g_psix[li], d.out_p, d.prev_p, d.prev_pc, P, Tl, total);
+                if ((rc = launch_flat("repeat_sum_kernel", repeat_sum_kernel, s, total, g_p, b.g_psix[li], d.out_p, d.prev_p, d.prev_pc, P, Tl, total))) return rc;
             }
-            bn_block_backward(m + "up_sixth_b", b.g_psix[li], b.psix[li], b.aff_p2pin[li] + 3 * d.prev_p, d.prev_pc, 0, 36 * Tl);
-            {
-                ake::ProfScope ps("up_sixth_bwd_weight_kernel", s);
-                hipLaunchKernelGGL(up_sixth_bwd_weight_kernel, dim3(d.prev_pc * d.prev_pc * 3, B), dim3(64), 0, s, b.g_psix[li], b.cat[li], static_cast<long long>(ctd) * 12 * Tl,
-                                   static_cast<const float*>(nullptr), grad_of(m + "up_sixth.weight"), static_cast<long long>(n->grad_floats), d.prev_pc, Tl);
-            }
+            if ((rc = bn_block_backward(m + "up_sixth_b", b.g_psix[li], b.psix[li], b.aff_p2pin[li] + 3 * d.prev_p, d.prev_pc, 0, 36 * Tl))) return rc;
+            if ((rc = ake::launch("up_sixth_bwd_weight_kernel", up_sixth_bwd_weight_kernel, dim3(d.prev_pc * d.prev_pc * 3, B), dim3(64), 0, s, b.g_psix[li], b.cat[li],
+                                  static_cast<long long>(ctd) * 12 * Tl, nullptr, grad_of(m + "up_sixth.weight"), static_cast<long long>(n->grad_floats), d.prev_pc, Tl)))
+                return rc;
             {
                 const long long total = static_cast<long long>(B) * d.prev_pc * 12 * Tl;
-                launch_flat("up_sixth_bwd_data_kernel", up_sixth_bwd_data_kernel, s, total, b.g_psix[li], raw_of(m + "up_sixth.weight"), b.g_cat[li], ctd, d.prev_pc, Tl,
-                            total);
+                if ((rc = launch_flat("up_sixth_bwd_data_kernel", up_sixth_bwd_data_kernel, s, total, b.g_psix[li], raw_of(m + "up_sixth.weight"), b.g_cat[li], ctd,
+                                      d.prev_pc, Tl, total)))
+                    return rc;
             }
         }
         // layer 0's block: channels [0, 1 + g) of layer 1's buffer, input = the fold (channel 0)
@@ -353,9 +333,8 @@ struct Bwd {
         return semi_backward(0, mel, nullptr, b.g_cat[1], ctd1, 0, nullptr);
     }
 
-    void bias_grad(const float* dz, int ctot, int coff, int C, int HT, gfx_t* db) {
-        ake::ProfScope ps("channel_sum_kernel", s);
-        hipLaunchKernelGGL(channel_sum_kernel, dim3(C, B), dim3(256), 0, s, dz, db, static_cast<long long>(n->grad_floats), ctot, coff, HT);
+    int bias_grad(const float* dz, int ctot, int coff, int C, int HT, gfx_t* db) {
+        return ake::launch("channel_sum_kernel", channel_sum_kernel, dim3(C, B), dim3(256), 0, s, dz, db, static_cast<long long>(n->grad_floats), ctot, coff, HT);
     }
 
     // A stack of `nconv` convolutions (conv -> BN -> LReLU each).  g holds ga w.r.t. the last activation on entry and is
@@ -371,7 +350,7 @@ struct Bwd {
         for (int j = nconv - 1; j >= 0; --j) {
             const PackedConv& pc = fwd_t[j];
             const std::string cname = prefix + std::to_string(3 * j) + (conv2d_suffix ? ".conv2d" : "");
-            bn_block_backward(prefix + std::to_string(3 * j + 1), g, z[j], aff[j], pc.cout, 0, H * Tn);
+            if ((rc = bn_block_backward(prefix + std::to_string(3 * j + 1), g, z[j], aff[j], pc.cout, 0, H * Tn))) return rc;
             // bias gradient under BatchNorm is exactly zero (the mean subtraction removes it); grads were zero-filled
             Src in = j == 0 ? stack_in : Src{z[j - 1], fwd_t[j - 1].cout, nullptr, 0, 0};
             const float* in_aff = j == 0 ? stack_in_aff : aff[j - 1];
@@ -399,17 +378,15 @@ struct Bwd {
         int rc;
         for (int r = nb - 1; r >= 0; --r) {
             const std::string bp = prefix + std::to_string(3 + r) + ".";
-            {
-                const long long total = static_cast<long long>(B) * C * H * Tn;
-                launch_flat("res_act_bwd_kernel", res_act_bwd_kernel, s, total, g, z[3 + 3 * r], gs, total);
-            }
+            const long long total = static_cast<long long>(B) * C * H * Tn;
+            if ((rc = launch_flat("res_act_bwd_kernel", res_act_bwd_kernel, s, total, g, z[3 + 3 * r], gs, total))) return rc;
             // b2 has no activation of its own: its table carries slope 1, so the generic block applies LeakyReLU' = 1
-            bn_block_backward(bp + "b2", g, z[2 + 3 * r], aff[2 + 3 * r], C, 0, H * Tn);
+            if ((rc = bn_block_backward(bp + "b2", g, z[2 + 3 * r], aff[2 + 3 * r], C, 0, H * Tn))) return rc;
             if ((rc = wgrad(fwd_t[2 + 2 * r], kind, Src{z[1 + 3 * r], 2 * C, nullptr, 0, 0}, aff[1 + 3 * r], H, Tn, true, g, C, 0,
                             grad_of(bp + "conv2" + sfx + ".weight"), wname)))
                 return rc;
             if ((rc = dgrad(dpack[2 + 2 * r], fwd_t[2 + 2 * r], kind, g, H, Tn, Tn, true, gh, 2 * C, 0, false, dname))) return rc;
-            bn_block_backward(bp + "b1", gh, z[1 + 3 * r], aff[1 + 3 * r], 2 * C, 0, H * Tn);
+            if ((rc = bn_block_backward(bp + "b1", gh, z[1 + 3 * r], aff[1 + 3 * r], 2 * C, 0, H * Tn))) return rc;
             // the block's input: the previous block's output (final, identity table) or conv0's raw output + its BatchNorm
             if ((rc = wgrad(fwd_t[1 + 2 * r], kind, Src{z[3 * r], C, nullptr, 0, 0}, aff[3 * r], H, Tn, true, gh, 2 * C, 0,
                             grad_of(bp + "conv1" + sfx + ".weight"), wname)))
@@ -417,7 +394,7 @@ struct Bwd {
             if ((rc = dgrad(dpack[1 + 2 * r], fwd_t[1 + 2 * r], kind, gh, H, Tn, Tn, true, gs, C, 0, true, dname))) return rc;   // + the skip copy
             std::swap(g, gs);
         }
-        bn_block_backward(prefix + "1", g, z[0], aff[0], C, 0, H * Tn);
+        if ((rc = bn_block_backward(prefix + "1", g, z[0], aff[0], C, 0, H * Tn))) return rc;
         if ((rc = wgrad(fwd_t[0], kind, stack_in, stack_in_aff, H, Tn, true, g, C, 0, grad_of(prefix + "0" + sfx + ".weight"), wname))) return rc;
         if (g_in && (rc = dgrad(dpack[0], fwd_t[0], kind, g, H, Tn, Tn, true, g_in, g_in_ctot, 0, false, dname))) return rc;
         return AKE_OK;
@@ -451,12 +428,12 @@ struct Bwd {
             for (int h = 0; h < 3; ++h) { la.d_out[h] = pa.d_out[h]; la.maps[h] = pa.maps[h]; la.d_map[h] = pa.d_map[h]; }
             la.key_out = key_out;
             la.Tm = Tm; la.Tq = Tm - c.local + 1; la.W = c.local; la.batch = B;
-            ake::ProfScope ps("local_pool_bwd_kernel", s);
-            hipLaunchKernelGGL(local_pool_bwd_kernel, dim3(static_cast<unsigned>((static_cast<long long>(B) * 12 * Tm + 255) / 256), 3), dim3(256), 0, s, la);
+            rc = ake::launch("local_pool_bwd_kernel", local_pool_bwd_kernel, dim3(static_cast<unsigned>((static_cast<long long>(B) * 12 * Tm + 255) / 256), 3),
+                             dim3(256), 0, s, la);
         } else {
-            ake::ProfScope ps("head_pool_bwd_kernel", s);
-            hipLaunchKernelGGL(head_pool_bwd_kernel, dim3((B * 12 + 63) / 64, 3), dim3(64), 0, s, pa);
+            rc = ake::launch("head_pool_bwd_kernel", head_pool_bwd_kernel, dim3((B * 12 + 63) / 64, 3), dim3(64), 0, s, pa);
         }
+        if (rc) return rc;
         // features feeding the heads: pcf (final) for L > 1, the raw last pc2pc output (+affine) for L == 1
         const Slot feat_s = L > 1 ? Slot{b.pcf, nullptr} : (c.denseblock ? Slot{b.fold0, nullptr} : b.pc_last(0));      // (--denseblock, one layer: the block's feature buffer itself)
         const float* feat = feat_s.p;
@@ -486,8 +463,9 @@ struct Bwd {
                 const int T_in = Tcur + c.kernel_size - 1;
                 const int H_out = heads[h].kind == 2 ? 12 - pc.kh + 1 : 12;
                 const Slot z = b.head_out(true, h, j, j == nl - 1), zin = j == 0 ? Slot{} : b.head_out(true, h, j - 1, false);
-                if (j < nl - 1) bn_block_backward(std::string(heads[h].nm) + "." + std::to_string(3 * j + 1), g, z.p, z.aff, pc.cout, 0, 12 * Tcur);
-                else bias_grad(g, pc.cout, 0, pc.cout, 12 * Tcur, grad_of(cname + ".bias"));   // row 11 of the genre map gradient is zero
+                if (j < nl - 1) rc = bn_block_backward(std::string(heads[h].nm) + "." + std::to_string(3 * j + 1), g, z.p, z.aff, pc.cout, 0, 12 * Tcur);
+                else rc = bias_grad(g, pc.cout, 0, pc.cout, 12 * Tcur, grad_of(cname + ".bias"));   // row 11 of the genre map gradient is zero
+                if (rc) return rc;
                 Src in = j == 0 ? Src{feat, fin, nullptr, 0, 0} : Src{zin.p, ct[j - 1].cout, nullptr, 0, 0};
                 const float* in_aff = j == 0 ? feat_aff : zin.aff;
                 // the genre gradient maps carry 12 rows (the last one zero), so circular rows reproduce its "valid" rows exactly
@@ -515,8 +493,9 @@ struct Bwd {
         float* g_last2 = b.g_pc[i] + static_cast<size_t>(B) * (i == 0 ? c.n_filters : d.out_pc) * 12 * Ti;
         if (L > 1) {
             const long long total = static_cast<long long>(B) * d.out_pc * 12 * ((Ti / tp) + (Ti % tp ? 1 : 0));
-            launch_flat("time_pool_bwd_kernel", time_pool_bwd_kernel, s, total, b.g_pcf, b.pc_last(i).p, b.pc_last(i).aff, g_last, d.out_pc, 12, Ti, tp, d.out_pc,
-                        0, total, 0);
+            if ((rc = launch_flat("time_pool_bwd_kernel", time_pool_bwd_kernel, s, total, b.g_pcf, b.pc_last(i).p, b.pc_last(i).aff, g_last, d.out_pc, 12, Ti, tp,
+                                  d.out_pc, 0, total, 0)))
+                return rc;
         }
         if (L == 1) {
             // single layer: pc2pc0 stack straight down to fold0
@@ -550,14 +529,15 @@ struct Bwd {
             float* g_p2 = b.g_p[li] + static_cast<size_t>(B) * dl.out_p * P * Tl;
             if (c.stay_sixth) {   // models.py:391: the stack's output (semitone resolution) was folded as it is
                 const long long total = static_cast<long long>(B) * dl.out_p * 12 * Tl;
-                launch_flat("fold_bwd_kernel", fold_bwd_kernel, s, total, b.g_cat[li], zl.p, zl.aff, g_p, dl.out_p, Pp / 12, Tl, ctot, dl.prev_pc,
-                            total);
+                if ((rc = launch_flat("fold_bwd_kernel", fold_bwd_kernel, s, total, b.g_cat[li], zl.p, zl.aff, g_p, dl.out_p, Pp / 12, Tl, ctot, dl.prev_pc, total)))
+                    return rc;
             } else if ((rc = semi_backward(li, zl.p, zl.aff, b.g_cat[li], ctot, dl.prev_pc, g_p))) return rc;
             if (inner) {   // second consumer of an inner layer's pitch stream: its time-pooled copy is the next layer's pitch input (models.py:395)
                 const LayerDims& dn = n->dims[li + 1];
                 const long long total = static_cast<long long>(B) * dl.out_p * Pp * ((Tl / tp) + (Tl % tp ? 1 : 0));
-                launch_flat("time_pool_bwd_kernel", time_pool_bwd_kernel, s, total, b.g_pin[li + 1], zl.p, zl.aff, g_p, dl.out_p, Pp, Tl, tp,
-                            c.pc2p_mem ? dn.prev_p : dn.prev_p + dn.prev_pc, 0, total, 1);
+                if ((rc = launch_flat("time_pool_bwd_kernel", time_pool_bwd_kernel, s, total, b.g_pin[li + 1], zl.p, zl.aff, g_p, dl.out_p, Pp, Tl, tp,
+                                      c.pc2p_mem ? dn.prev_p : dn.prev_p + dn.prev_pc, 0, total, 1)))
+                    return rc;
             }
             // ---- pitch convs; input = (pitch stream | psix repeated) ----
             // (--pc2p_mem, models.py:145-166: the stack read the pitch stream + the summed up_sixth map, kept in b.pin by the forward)
@@ -570,35 +550,34 @@ struct Bwd {
             // ---- repeat (x P/36) backward, then up_sixth ----
             if (c.stay_sixth) {   // no up_sixth: the pitch classes were repeated as they are
                 const long long total = static_cast<long long>(B) * dl.prev_pc * 12 * Tl;
-                launch_flat("repeat_sum_kernel", repeat_sum_add_kernel, s, total, b.g_pin[li], b.g_cat[li], dl.prev_p + dl.prev_pc, dl.prev_p, dl.prev_pc, Pp, Tl, ctot,
-                            total);
+                rc = launch_flat("repeat_sum_kernel", repeat_sum_add_kernel, s, total, b.g_pin[li], b.g_cat[li], dl.prev_p + dl.prev_pc, dl.prev_p, dl.prev_pc, Pp, Tl,
+                                 ctot, total);
             } else if (c.pc2p_mem) {
                 const long long total = static_cast<long long>(B) * dl.prev_pc * 36 * Tl;
-                launch_flat("pc2p_mem_bwd_kernel", pc2p_mem_bwd_kernel, s, total, b.g_pin[li], b.g_psix[li], dl.prev_p, dl.prev_pc / dl.prev_p, P, Tl, total);
+                rc = launch_flat("pc2p_mem_bwd_kernel", pc2p_mem_bwd_kernel, s, total, b.g_pin[li], b.g_psix[li], dl.prev_p, dl.prev_pc / dl.prev_p, P, Tl, total);
             } else {
                 const long long total = static_cast<long long>(B) * dl.prev_pc * 36 * Tl;
-                launch_flat("repeat_sum_kernel", repeat_sum_kernel, s, total, b.g_pin[li], b.g_psix[li], dl.prev_p + dl.prev_pc, dl.prev_p, dl.prev_pc, P, Tl, total);
+                rc = launch_flat("repeat_sum_kernel", repeat_sum_kernel, s, total, b.g_pin[li], b.g_psix[li], dl.prev_p + dl.prev_pc, dl.prev_p, dl.prev_pc, P, Tl, total);
             }
+            if (rc) return rc;
             if (!c.stay_sixth) {
-                bn_block_backward(m + "up_sixth_b", b.g_psix[li], b.psix[li], b.aff_p2pin[li] + 3 * dl.prev_p, dl.prev_pc, 0, 36 * Tl);
-                {
-                    ake::ProfScope ps("up_sixth_bwd_weight_kernel", s);
-                    hipLaunchKernelGGL(up_sixth_bwd_weight_kernel, dim3(dl.prev_pc * dl.prev_pc * 3, B), dim3(64), 0, s, b.g_psix[li], b.cat[li],
-                                       static_cast<long long>(ctot) * 12 * Tl, b.aff_cat[li], grad_of(m + "up_sixth.weight"),
-                                       static_cast<long long>(n->grad_floats), dl.prev_pc, Tl);
-                }
-                {
-                    const long long total = static_cast<long long>(B) * dl.prev_pc * 12 * Tl;
-                    launch_flat("up_sixth_bwd_data_kernel", up_sixth_bwd_data_kernel, s, total, b.g_psix[li], raw_of(m + "up_sixth.weight"), b.g_cat[li], ctot,
-                                dl.prev_pc, Tl, total);
-                }
+                if ((rc = bn_block_backward(m + "up_sixth_b", b.g_psix[li], b.psix[li], b.aff_p2pin[li] + 3 * dl.prev_p, dl.prev_pc, 0, 36 * Tl))) return rc;
+                if ((rc = ake::launch("up_sixth_bwd_weight_kernel", up_sixth_bwd_weight_kernel, dim3(dl.prev_pc * dl.prev_pc * 3, B), dim3(64), 0, s, b.g_psix[li],
+                                      b.cat[li], static_cast<long long>(ctot) * 12 * Tl, b.aff_cat[li], grad_of(m + "up_sixth.weight"),
+                                      static_cast<long long>(n->grad_floats), dl.prev_pc, Tl)))
+                    return rc;
+                const long long total = static_cast<long long>(B) * dl.prev_pc * 12 * Tl;
+                if ((rc = launch_flat("up_sixth_bwd_data_kernel", up_sixth_bwd_data_kernel, s, total, b.g_psix[li], raw_of(m + "up_sixth.weight"), b.g_cat[li], ctot,
+                                      dl.prev_pc, Tl, total)))
+                    return rc;
             }
             if (li >= 2) {   // channels [0, prev_pc) of the concat buffer = the time-pooled pitch classes of the layer below (models.py:394)
                 const LayerDims& dp = n->dims[li - 1];
                 const int Tp = b.Tl[li - 1];
                 const long long total = static_cast<long long>(B) * dp.out_pc * 12 * ((Tp / tp) + (Tp % tp ? 1 : 0));
-                launch_flat("time_pool_bwd_kernel", time_pool_bwd_kernel, s, total, b.g_cat[li], b.pc_last(li - 1).p, b.pc_last(li - 1).aff, b.g_pc[li - 1],
-                            dp.out_pc, 12, Tp, tp, ctot, 0, total, 0);
+                if ((rc = launch_flat("time_pool_bwd_kernel", time_pool_bwd_kernel, s, total, b.g_cat[li], b.pc_last(li - 1).p, b.pc_last(li - 1).aff, b.g_pc[li - 1],
+                                      dp.out_pc, 12, Tp, tp, ctot, 0, total, 0)))
+                    return rc;
             }
         }
         const int ctot = n->dims[1].prev_pc + n->dims[1].out_p;
@@ -631,33 +610,31 @@ struct Bwd {
         const int C = pc.cin, P = n->cfg.pitches, Tn = b.Tl[layer];
         const std::string m = "model." + std::to_string(layer) + ".";
         float* g = b.g_semi[layer];
+        int rc;
         if (n->cfg.p2pc_conv) {   // models.py:108-133: the fold is a convolution over the octaves + pool.bn + LeakyReLU
             const long long per_clip = static_cast<long long>(C) * 12 * Tn, total = per_clip * B;
             float* gf = b.g_foldc[layer];
             // the slice of the concat gradient that belongs to the folded channels, dense
-            launch_flat("slice_channels_kernel", slice_channels_kernel, s, total, gfold + static_cast<long long>(g_coff) * 12 * Tn, static_cast<long long>(g_ctot) * 12 * Tn, gf,
-                        per_clip, total);
-            bn_block_backward(m + "pool.bn", gf, b.foldc_raw[layer], b.aff_foldc[layer], C, 0, 12 * Tn);
-            {
-                ake::ProfScope ps("fold_conv_bwd_weight_kernel", s);
-                hipLaunchKernelGGL(fold_conv_bwd_weight_kernel, dim3(C * C * (P / 36), B), dim3(64), 0, s, gf, b.semi_raw[layer], b.aff_semi[layer],
-                                   grad_of(m + "pool.conv.weight"), static_cast<long long>(n->grad_floats), C, P / 36, Tn);
-            }
-            {
-                const long long tot = static_cast<long long>(B) * C * (P / 3) * Tn;
-                launch_flat("fold_conv_bwd_data_kernel", fold_conv_bwd_data_kernel, s, tot, gf, raw_of(m + "pool.conv.weight"), g, C, P / 36, Tn, tot);
-            }
+            if ((rc = launch_flat("slice_channels_kernel", slice_channels_kernel, s, total, gfold + static_cast<long long>(g_coff) * 12 * Tn,
+                                  static_cast<long long>(g_ctot) * 12 * Tn, gf, per_clip, total)))
+                return rc;
+            if ((rc = bn_block_backward(m + "pool.bn", gf, b.foldc_raw[layer], b.aff_foldc[layer], C, 0, 12 * Tn))) return rc;
+            if ((rc = ake::launch("fold_conv_bwd_weight_kernel", fold_conv_bwd_weight_kernel, dim3(C * C * (P / 36), B), dim3(64), 0, s, gf, b.semi_raw[layer],
+                                  b.aff_semi[layer], grad_of(m + "pool.conv.weight"), static_cast<long long>(n->grad_floats), C, P / 36, Tn)))
+                return rc;
+            const long long tot = static_cast<long long>(B) * C * (P / 3) * Tn;
+            rc = launch_flat("fold_conv_bwd_data_kernel", fold_conv_bwd_data_kernel, s, tot, gf, raw_of(m + "pool.conv.weight"), g, C, P / 36, Tn, tot);
         } else {
             const long long total = static_cast<long long>(B) * C * 12 * Tn;
-            launch_flat("fold_bwd_kernel", fold_bwd_kernel, s, total, gfold, b.semi_raw[layer], b.aff_semi[layer], g, C, P / 36, Tn, g_ctot, g_coff, total);
+            rc = launch_flat("fold_bwd_kernel", fold_bwd_kernel, s, total, gfold, b.semi_raw[layer], b.aff_semi[layer], g, C, P / 36, Tn, g_ctot, g_coff, total);
         }
+        if (rc) return rc;
         if (extra_g) {   // a second consumer of the activated semitone map: add its gradient (channels [0, C) of a wider tensor)
             const long long HT = static_cast<long long>(P / 3) * Tn, total = static_cast<long long>(B) * C * HT;
-            launch_flat("add_slice_kernel", add_slice_kernel, s, total, g, extra_g, C, HT, extra_ctot, total);
+            if ((rc = launch_flat("add_slice_kernel", add_slice_kernel, s, total, g, extra_g, C, HT, extra_ctot, total))) return rc;
         }
-        bn_block_backward(m + "pool_semi_b", g, b.semi_raw[layer], b.aff_semi[layer], C, 0, (P / 3) * Tn);
+        if ((rc = bn_block_backward(m + "pool_semi_b", g, b.semi_raw[layer], b.aff_semi[layer], C, 0, (P / 3) * Tn))) return rc;
         {
-            ake::ProfScope ps("semi_bwd_weight_kernel", s);
             const size_t cap = 160 * 1024;          // one workgroup per CU beyond 64 KB (--local clips: no time pooling, more frames)
             // frames staged at a time: the whole clip where it fits (one tile), else the most that fit (whole songs: 318 of 592 at 8 channels)
             auto lds_of = [&](int tc) { return std::max<size_t>(static_cast<size_t>(4) * (C * tc + 3 * C * (tc + 2)), 4 * 9 * 64) * sizeof(float); };
@@ -667,24 +644,19 @@ struct Bwd {
                         "backward: pool_semi weight gradient: %d channels do not fit its LDS slices", C);
             const size_t lds = lds_of(std::min(tile, Tn));
             static ake::DeviceOnce semi_attr;
-            if (lds > kLdsBudget && semi_attr.need()) {
-                AKE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(semi_bwd_weight_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(cap)));
-                semi_attr.mark();
-            }
+            if (lds > kLdsBudget && (rc = ake::raise_lds_limit(semi_attr, static_cast<int>(cap), semi_bwd_weight_kernel))) return rc;
             // rows per workgroup: kSemiRows at training batch sizes (few atomics), down to one row per wave when the batch is small
             const int S = P / 3, pair_groups = (C * C + 63) / 64;
             const int want = (std::max(device_cus(), 1) + B * pair_groups - 1) / (B * pair_groups);     // workgroups per clip that fill the chip
             const int rows = std::min(kSemiRows, std::max(4, (S + want - 1) / want));
-            hipLaunchKernelGGL(semi_bwd_weight_kernel, dim3((S + rows - 1) / rows, B, pair_groups), dim3(256), lds, s, g, x, x_aff,
-                               grad_of(m + "pool_semi.weight"), static_cast<long long>(n->grad_floats), C, P, Tn, rows, tile);
+            if ((rc = ake::launch("semi_bwd_weight_kernel", semi_bwd_weight_kernel, dim3((S + rows - 1) / rows, B, pair_groups), dim3(256), lds, s, g, x, x_aff,
+                                  grad_of(m + "pool_semi.weight"), static_cast<long long>(n->grad_floats), C, P, Tn, rows, tile)))
+                return rc;
         }
-        if (ga_x) {
-            const long long total = static_cast<long long>(B) * P * Tn;
-            ake::ProfScope ps("semi_bwd_data_kernel", s);
-            hipLaunchKernelGGL(semi_bwd_data_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), sizeof(float) * C * C * 9, s, g,
-                               raw_of(m + "pool_semi.weight"), ga_x, C, P, Tn, total);
-        }
-        return AKE_OK;
+        if (!ga_x) return AKE_OK;
+        const long long total = static_cast<long long>(B) * P * Tn;
+        return ake::launch("semi_bwd_data_kernel", semi_bwd_data_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), sizeof(float) * C * C * 9, s, g,
+                           raw_of(m + "pool_semi.weight"), ga_x, C, P, Tn, total);
     }
 };
 

@@ -106,10 +106,11 @@ static int pipeline_impl(const ake_cqt_plan* plan, const ake_pcnet* net, const f
                     : ake_cqt_logmag_f32(plan, audio_dev, batch, n_samples, audio_stride, pc.mel, T, pc.cqt_ws, pc.cqt_bytes, stream);
     if (rc) return rc;
     if (n_clip_dev)   // seq_length of every clip = its own frame count (KeyDataset.py:248: mel.shape[2] before padding)
-        hipLaunchKernelGGL(frames_i64_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, pc.seq, reinterpret_cast<const long long*>(n_clip_dev), hop,
-                           static_cast<long long>(T), batch);
+        rc = ake::launch_untimed("frames_i64_kernel", frames_i64_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, pc.seq,
+                                 reinterpret_cast<const long long*>(n_clip_dev), hop, T, batch);
     else
-        hipLaunchKernelGGL(fill_i64_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, pc.seq, static_cast<long long>(T), batch);
+        rc = ake::launch_untimed("fill_i64_kernel", fill_i64_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, pc.seq, T, batch);
+    if (rc) return rc;
     if (fm)
         return ake_pcnet_forward_frames_major_f32(net, pc.mel, batch, static_cast<int>(T), reinterpret_cast<const int64_t*>(pc.seq), key_out_dev,
                                                   tonic_out_dev, genre_out_dev, pc.net_ws, pc.net_bytes, stream);

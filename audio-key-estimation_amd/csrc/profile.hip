@@ -186,20 +186,12 @@ int ake_profile_emissions_f32(const float* mel_dev, int frames_major, int record
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int chunks = (frames + kProfChunk - 1) / kProfChunk;
     ProfChromaArgs c{mel_dev, counts_dev, static_cast<double*>(workspace), pitches, frames, compression};
-    {
-        ake::ProfScope ps("profile_chroma_kernel", s);
-        if (frames_major) hipLaunchKernelGGL(profile_chroma_kernel<true>, dim3(chunks, recordings), dim3(kProfThreads), 0, s, c);
-        else hipLaunchKernelGGL(profile_chroma_kernel<false>, dim3(chunks, recordings), dim3(kProfThreads), 0, s, c);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
+    const int rc = frames_major ? ake::launch("profile_chroma_kernel", profile_chroma_kernel<true>, dim3(chunks, recordings), dim3(kProfThreads), 0, s, c)
+                                : ake::launch("profile_chroma_kernel", profile_chroma_kernel<false>, dim3(chunks, recordings), dim3(kProfThreads), 0, s, c);
+    if (rc) return rc;
     ProfScoreArgs f{static_cast<const double*>(workspace), counts_dev, profiles_dev, chroma_out, emissions_out, key_id_out, confidence_out,
                     frames, window_frames, stride_frames, windows, static_cast<double>(sharpness)};
-    {
-        ake::ProfScope ps("profile_score_kernel", s);
-        hipLaunchKernelGGL(profile_score_kernel, dim3(windows, recordings), dim3(kProfScoreThreads), 0, s, f);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    return ake::launch("profile_score_kernel", profile_score_kernel, dim3(windows, recordings), dim3(kProfScoreThreads), 0, s, f);
 }
 
 }  // extern "C"

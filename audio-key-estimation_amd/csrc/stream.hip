@@ -95,12 +95,7 @@ int stream_history(float* hist, int recordings, int64_t stride, int64_t drop, in
     if (m == 0 && (keep == 0 || drop == 0)) return AKE_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     HistArgs<T> a{hist, chunk, stride, chunk_stride, drop, keep, m};
-    {
-        ake::ProfScope ps("stream_history_kernel", s);
-        hipLaunchKernelGGL(stream_history_kernel<T>, dim3(recordings), dim3(kHistThreads), 0, s, a);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    return ake::launch("stream_history_kernel", stream_history_kernel<T>, dim3(recordings), dim3(kHistThreads), 0, s, a);
 }
 
 }  // namespace
@@ -135,14 +130,9 @@ int ake_stream_frames_f32(float* dst_dev, const float* old_dev, const float* mel
     if (frames_major) {
         AKE_REQUIRE(pitches % 4 == 0 && ((reinterpret_cast<uintptr_t>(dst_dev) | reinterpret_cast<uintptr_t>(old_dev) | reinterpret_cast<uintptr_t>(mel_dev)) & 15) == 0,
                     AKE_ERR_INVALID, "stream_frames: frames-major needs pitches %% 4 == 0 and 16-byte aligned buffers");
-        ake::ProfScope ps("stream_frames_fm_kernel", s);
-        hipLaunchKernelGGL(stream_frames_fm_kernel, dim3(static_cast<unsigned>((a.quads + 255) / 256), recordings), dim3(256), 0, s, a);
-    } else {
-        ake::ProfScope ps("stream_frames_pm_kernel", s);
-        hipLaunchKernelGGL(stream_frames_pm_kernel, dim3(static_cast<unsigned>((cf + 255) / 256), pitches, recordings), dim3(256), 0, s, a);
+        return ake::launch("stream_frames_fm_kernel", stream_frames_fm_kernel, dim3(static_cast<unsigned>((a.quads + 255) / 256), recordings), dim3(256), 0, s, a);
     }
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    return ake::launch("stream_frames_pm_kernel", stream_frames_pm_kernel, dim3(static_cast<unsigned>((cf + 255) / 256), pitches, recordings), dim3(256), 0, s, a);
 }
 
 }  // extern "C"

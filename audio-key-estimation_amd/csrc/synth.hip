@@ -200,20 +200,12 @@ int ake_synth_partials_f32(const int32_t* offsets_dev, const double* cps_dev, co
     }
     SynthArgs a{offsets_dev, cps_dev, phase_dev, amp_dev, reinterpret_cast<const long long*>(start_dev), reinterpret_cast<const long long*>(end_dev),
                 reinterpret_cast<const long long*>(n_dev), reinterpret_cast<const long long*>(seed_dev), out_dev, peak_bits, stride, fade, noise_sigma};
-    {
-        ake::ProfScope ps("synth_kernel", s);
-        hipLaunchKernelGGL(synth_kernel, dim3(static_cast<unsigned>(tiles), recordings), dim3(kSynthBlock), 0, s, a);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
-    if (peak_bits) {
-        const long long quads = stride / 4;
-        const unsigned blocks = static_cast<unsigned>(std::min<long long>((quads + 255) / 256, 1024));
-        ake::ProfScope ps("synth_scale_kernel", s);
-        hipLaunchKernelGGL(synth_scale_kernel, dim3(blocks, recordings), dim3(256), 0, s, out_dev, peak_bits, reinterpret_cast<const long long*>(n_dev),
-                           static_cast<long long>(stride), peak);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    const int rc = ake::launch("synth_kernel", synth_kernel, dim3(static_cast<unsigned>(tiles), recordings), dim3(kSynthBlock), 0, s, a);
+    if (rc || !peak_bits) return rc;
+    const long long quads = stride / 4;
+    const unsigned blocks = static_cast<unsigned>(std::min<long long>((quads + 255) / 256, 1024));
+    return ake::launch("synth_scale_kernel", synth_scale_kernel, dim3(blocks, recordings), dim3(256), 0, s, out_dev, peak_bits,
+                       reinterpret_cast<const long long*>(n_dev), stride, peak);
 }
 
 }  // extern "C"

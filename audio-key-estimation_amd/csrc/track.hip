@@ -1336,9 +1336,9 @@ int track_impl(const ake_cqt_plan* plan, const ake_pcnet* net, const float* audi
     rc = ake_pcnet_forward_windows_f32(net, tc.mel, fm ? 1 : 0, recordings, tc.T, window_frames, stride_frames, key_out, tonic_out, genre_out,
                                        tc.win_ws, tc.win_bytes, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(track_counts_kernel, dim3((recordings + 255) / 256), dim3(256), 0, s, counts, reinterpret_cast<const long long*>(n_clip_dev),
-                       ake_cqt_plan_hop(plan), tc.T, window_frames, stride_frames, recordings);
-    AKE_HIP_CHECK(hipGetLastError());
+    rc = ake::launch_untimed("track_counts_kernel", track_counts_kernel, dim3((recordings + 255) / 256), dim3(256), 0, s, counts,
+                             reinterpret_cast<const long long*>(n_clip_dev), ake_cqt_plan_hop(plan), tc.T, window_frames, stride_frames, recordings);
+    if (rc) return rc;
     const int windows = (tc.T - window_frames) / stride_frames + 1;
     return ake_decode_keys_f32(key_out, tonic_out, recordings * windows, n_clip_dev ? counts : nullptr, windows, key_id, sig, tonic_id, confidence,
                                stream);
@@ -1365,17 +1365,15 @@ int ake_pcnet_forward_windows_f32(const ake_pcnet* net, const float* mel_dev, in
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int P = ake_pcnet_pitches(net);
     const long long total = wc.windows * recordings;
-    hipLaunchKernelGGL(fill_i64_kernel, dim3((wc.chunk + 255) / 256), dim3(256), 0, s, wc.seq, static_cast<long long>(window_frames), wc.chunk);
+    rc = ake::launch_untimed("fill_i64_kernel", fill_i64_kernel, dim3((wc.chunk + 255) / 256), dim3(256), 0, s, wc.seq, window_frames, wc.chunk);
+    if (rc) return rc;
     for (long long c0 = 0; c0 < total; c0 += wc.chunk) {
         const int B = static_cast<int>(std::min<long long>(wc.chunk, total - c0));
         GatherArgs ga{mel_dev, wc.mel, P, total_frames, window_frames, stride_frames, static_cast<int>(wc.windows), static_cast<int>(c0)};
         const dim3 grid((P + kTile - 1) / kTile, (window_frames + kTile - 1) / kTile, B);
-        {
-            ake::ProfScope ps("window_gather_kernel", s);
-            if (frames_major) hipLaunchKernelGGL(window_gather_kernel<true>, grid, dim3(256), 0, s, ga);
-            else hipLaunchKernelGGL(window_gather_kernel<false>, grid, dim3(256), 0, s, ga);
-        }
-        AKE_HIP_CHECK(hipGetLastError());
+        rc = frames_major ? ake::launch("window_gather_kernel", window_gather_kernel<true>, grid, dim3(256), 0, s, ga)
+                          : ake::launch("window_gather_kernel", window_gather_kernel<false>, grid, dim3(256), 0, s, ga);
+        if (rc) return rc;
         rc = ake_pcnet_forward_f32(net, wc.mel, B, window_frames, reinterpret_cast<const int64_t*>(wc.seq), key_out_dev + c0 * 12, tonic_out_dev + c0 * 12,
                                    genre_out_dev ? genre_out_dev + c0 * 11 : nullptr, wc.net_ws, wc.net_bytes, stream);
         if (rc) return rc;
@@ -1391,12 +1389,7 @@ int ake_decode_keys_f32(const float* key_dev, const float* tonic_dev, int rows, 
     if (rows == 0) return AKE_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     DecodeArgs a{key_dev, tonic_dev, counts_dev, rows, counts_dev ? windows_per_recording : 1, key_id_dev, sig_dev, tonic_id_dev, confidence_dev};
-    {
-        ake::ProfScope ps("decode_keys_kernel", s);
-        hipLaunchKernelGGL(decode_keys_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, a);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    return ake::launch_flat("decode_keys_kernel", decode_keys_kernel, s, rows, a);
 }
 
 int ake_key_emissions_f32(const float* key_dev, const float* tonic_dev, int rows, const int32_t* counts_dev, int windows_per_recording,
@@ -1410,12 +1403,7 @@ int ake_key_emissions_f32(const float* key_dev, const float* tonic_dev, int rows
     if (rows == 0) return AKE_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     EmisArgs a{key_dev, tonic_dev, counts_dev, rows, counts_dev ? windows_per_recording : 1, signature_weight / 12.f, emis_dev};
-    {
-        ake::ProfScope ps("key_emissions_kernel", s);
-        hipLaunchKernelGGL(key_emissions_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, a);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    return ake::launch_flat("key_emissions_kernel", key_emissions_kernel, s, rows, a);
 }
 
 int ake_viterbi_chunk_windows(void) { return kVitChunk; }
@@ -1434,12 +1422,7 @@ int ake_viterbi_keys_f32(const float* emis_dev, int recordings, int windows, con
     AKE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, AKE_ERR_INVALID, "viterbi_keys: the workspace must be 16-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     VitArgs a{emis_dev, counts_dev, log_trans_dev, log_prior_dev, path_dev, static_cast<unsigned*>(workspace), windows, (windows + 3) / 4};
-    {
-        ake::ProfScope ps("viterbi_keys_kernel", s);
-        hipLaunchKernelGGL(viterbi_keys_kernel, dim3(recordings), dim3(64), 0, s, a);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    return ake::launch("viterbi_keys_kernel", viterbi_keys_kernel, dim3(recordings), dim3(64), 0, s, a);
 }
 
 int ake_key_posteriors_chunk_windows(void) { return kPostChunk; }
@@ -1462,24 +1445,13 @@ int ake_key_posteriors_f32(const float* emis_dev, int recordings, int windows, c
                 "key_posteriors: the workspace and post_dev must be 16-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     FbArgs fa{emis_dev, counts_dev, log_trans_dev, log_prior_dev, pc.a, pc.b, loglik_dev, windows};
-    {
-        ake::ProfScope ps("key_forward_backward_kernel", s);
-        hipLaunchKernelGGL(key_forward_backward_kernel, dim3(recordings, 2), dim3(64), 0, s, fa);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
+    int rc = ake::launch("key_forward_backward_kernel", key_forward_backward_kernel, dim3(recordings, 2), dim3(64), 0, s, fa);
+    if (rc) return rc;
     PostArgs pa{emis_dev, counts_dev, log_trans_dev, path_post_dev ? path_dev : nullptr, pc.a, pc.b, post_dev, path_post_dev,
                 xi_sum_dev ? pc.part : nullptr, windows, pc.chunks};
-    {
-        ake::ProfScope ps("key_posteriors_kernel", s);
-        hipLaunchKernelGGL(key_posteriors_kernel, dim3(recordings * pc.chunks), dim3(256), 0, s, pa);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
-    if (xi_sum_dev) {
-        ake::ProfScope ps("key_xi_reduce_kernel", s);
-        hipLaunchKernelGGL(key_xi_reduce_kernel, dim3(recordings), dim3(192), 0, s, pc.part, xi_sum_dev, pc.chunks);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    rc = ake::launch("key_posteriors_kernel", key_posteriors_kernel, dim3(recordings * pc.chunks), dim3(256), 0, s, pa);
+    if (rc || !xi_sum_dev) return rc;
+    return ake::launch("key_xi_reduce_kernel", key_xi_reduce_kernel, dim3(recordings), dim3(192), 0, s, pc.part, xi_sum_dev, pc.chunks);
 }
 
 size_t ake_key_stream_state_bytes(int recordings, int lag) {
@@ -1508,12 +1480,7 @@ int ake_key_stream_step_f32(const float* emis_dev, int recordings, int k, int64_
     StreamStepArgs a{emis_dev, log_trans_dev, log_prior_dev, static_cast<unsigned char*>(state_dev), filtered_dev, path_dev,
                      static_cast<long long>(windows_before), k, lag, flush ? 1 : 0, static_cast<int>(n_out),
                      lag > 0 ? static_cast<int>(windows_before % lag) : 0};
-    {
-        ake::ProfScope ps("key_stream_step_kernel", s);
-        hipLaunchKernelGGL(key_stream_step_kernel, dim3(recordings), dim3(64), 0, s, a);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    return ake::launch("key_stream_step_kernel", key_stream_step_kernel, dim3(recordings), dim3(64), 0, s, a);
 }
 
 size_t ake_key_sequence_loss_workspace_bytes(int recordings, int windows) {
@@ -1540,40 +1507,15 @@ int ake_key_sequence_loss_f32(const float* key_dev, const float* tonic_dev, cons
     SeqArgs a{key_dev, tonic_dev, labels_dev, counts_dev, log_trans_dev, log_prior_dev, rows, windows, recordings,
               static_cast<double>(signature_weight) / 12.0, sc.emis, sc.a, sc.b, sc.emis32, sc.a32, sc.b32, sc.loglik, sc.inv_n, scalars_dev,
               d_key_dev, d_tonic_dev, d_emis_dev};
-    {
-        ake::ProfScope ps("sequence_emissions_kernel", s);
-        hipLaunchKernelGGL(sequence_emissions_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, a);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
-    {
-        ake::ProfScope ps("key_sequence_chains_kernel", s);
-        hipLaunchKernelGGL(key_sequence_chains_kernel, dim3(recordings, 4), dim3(64), 0, s, a);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
-    {
-        ake::ProfScope ps("sequence_scalars_kernel", s);
-        hipLaunchKernelGGL(sequence_scalars_kernel, dim3(1), dim3(256), 0, s, a);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
-    {
-        ake::ProfScope ps("sequence_grad_kernel", s);
-        hipLaunchKernelGGL(sequence_grad_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, a);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
-    if (d_trans_dev) {
-        PostArgs pa{sc.emis32, counts_dev, log_trans_dev, nullptr, sc.a32, sc.b32, nullptr, nullptr, sc.part, windows, sc.chunks};
-        {
-            ake::ProfScope ps("key_sequence_xi_kernel", s);
-            hipLaunchKernelGGL(key_sequence_xi_kernel, dim3(recordings * sc.chunks, 2), dim3(256), 0, s, pa, recordings);
-        }
-        AKE_HIP_CHECK(hipGetLastError());
-        {
-            ake::ProfScope ps("sequence_trans_kernel", s);
-            hipLaunchKernelGGL(sequence_trans_kernel, dim3(1), dim3(192), 0, s, sc.part, sc.inv_n, d_trans_dev, recordings, sc.chunks);
-        }
-        AKE_HIP_CHECK(hipGetLastError());
-    }
-    return AKE_OK;
+    int rc;
+    if ((rc = ake::launch_flat("sequence_emissions_kernel", sequence_emissions_kernel, s, rows, a))) return rc;
+    if ((rc = ake::launch("key_sequence_chains_kernel", key_sequence_chains_kernel, dim3(recordings, 4), dim3(64), 0, s, a))) return rc;
+    if ((rc = ake::launch("sequence_scalars_kernel", sequence_scalars_kernel, dim3(1), dim3(256), 0, s, a))) return rc;
+    rc = ake::launch_flat("sequence_grad_kernel", sequence_grad_kernel, s, rows, a);
+    if (rc || !d_trans_dev) return rc;
+    PostArgs pa{sc.emis32, counts_dev, log_trans_dev, nullptr, sc.a32, sc.b32, nullptr, nullptr, sc.part, windows, sc.chunks};
+    if ((rc = ake::launch("key_sequence_xi_kernel", key_sequence_xi_kernel, dim3(recordings * sc.chunks, 2), dim3(256), 0, s, pa, recordings))) return rc;
+    return ake::launch("sequence_trans_kernel", sequence_trans_kernel, dim3(1), dim3(192), 0, s, sc.part, sc.inv_n, d_trans_dev, recordings, sc.chunks);
 }
 
 size_t ake_pipeline_track_workspace_bytes(const ake_cqt_plan* plan, const ake_pcnet* net, int recordings, int64_t n_samples, int window_frames,
@@ -1620,12 +1562,7 @@ int ake_track_score_i32(const int32_t* pred_dev, const int32_t* counts_dev, cons
     hipStream_t s = static_cast<hipStream_t>(stream);
     ScoreArgs a{pred_dev, counts_dev, reinterpret_cast<const long long*>(seg_start_dev), seg_key_dev, seg_count_dev, truth_dev, category_dev,
                 tally_dev, changes_dev, windows, max_segments, hop, window_frames, stride_frames};
-    {
-        ake::ProfScope ps("track_score_kernel", s);
-        hipLaunchKernelGGL(track_score_kernel, dim3(recordings), dim3(256), 0, s, a);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    return ake::launch("track_score_kernel", track_score_kernel, dim3(recordings), dim3(256), 0, s, a);
 }
 
 int ake_draw_windows_i32(const int64_t* prefix_dev, int recordings, uint64_t seed, uint32_t epoch, int64_t first_slot, int batch,
@@ -1637,12 +1574,7 @@ int ake_draw_windows_i32(const int64_t* prefix_dev, int recordings, uint64_t see
     hipStream_t s = static_cast<hipStream_t>(stream);
     DrawArgs a{reinterpret_cast<const long long*>(prefix_dev), recordings, static_cast<unsigned>(seed), static_cast<unsigned>(seed >> 32), epoch,
                static_cast<unsigned long long>(first_slot), batch, recording_out_dev, start_out_dev};
-    {
-        ake::ProfScope ps("draw_windows_kernel", s);
-        hipLaunchKernelGGL(draw_windows_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, a);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    return ake::launch_flat("draw_windows_kernel", draw_windows_kernel, s, batch, a);
 }
 
 int ake_window_batch_f32(const float* mel_dev, int frames_major, int recordings, int total_frames, int pitches, int window_frames, int hop,
@@ -1667,13 +1599,8 @@ int ake_window_batch_f32(const float* mel_dev, int frames_major, int recordings,
                 reinterpret_cast<const long long*>(seg_start_dev), seg_key_dev, seg_count_dev, max_segments, min_purity, uniform,
                 key_labels_dev, tonic_labels_dev, key_signature_id_dev, reinterpret_cast<long long*>(seq_length_dev), weight_dev};
     const dim3 grid(mel_out_dev ? (pitches + kTile - 1) / kTile : 1, mel_out_dev ? (window_frames + kTile - 1) / kTile : 1, batch);
-    {
-        ake::ProfScope ps("window_batch_kernel", s);
-        if (frames_major) hipLaunchKernelGGL(window_batch_kernel<true>, grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(window_batch_kernel<false>, grid, dim3(256), 0, s, a);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    return frames_major ? ake::launch("window_batch_kernel", window_batch_kernel<true>, grid, dim3(256), 0, s, a)
+                        : ake::launch("window_batch_kernel", window_batch_kernel<false>, grid, dim3(256), 0, s, a);
 }
 
 }  // extern "C"

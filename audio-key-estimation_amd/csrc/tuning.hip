@@ -118,19 +118,11 @@ int ake_tuning_estimate_f32(const float* mel_dev, int frames_major, int batch, i
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int chunks = tune_chunks(frames);
     TuneArgs a{mel_dev, counts_dev, static_cast<double*>(workspace), pitches, frames, chunks};
-    {
-        ake::ProfScope ps("tuning_sums_kernel", s);
-        if (frames_major) hipLaunchKernelGGL(tuning_sums_kernel<true>, dim3(chunks, batch), dim3(kTuneThreads), 0, s, a);
-        else hipLaunchKernelGGL(tuning_sums_kernel<false>, dim3(chunks, batch), dim3(kTuneThreads), 0, s, a);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
+    const int rc = frames_major ? ake::launch("tuning_sums_kernel", tuning_sums_kernel<true>, dim3(chunks, batch), dim3(kTuneThreads), 0, s, a)
+                                : ake::launch("tuning_sums_kernel", tuning_sums_kernel<false>, dim3(chunks, batch), dim3(kTuneThreads), 0, s, a);
+    if (rc) return rc;
     TuneFinishArgs f{static_cast<const double*>(workspace), cents_dev, strength_dev, batch, chunks, min_strength};
-    {
-        ake::ProfScope ps("tuning_finish_kernel", s);
-        hipLaunchKernelGGL(tuning_finish_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, f);
-    }
-    AKE_HIP_CHECK(hipGetLastError());
-    return AKE_OK;
+    return ake::launch("tuning_finish_kernel", tuning_finish_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, f);
 }
 
 }  // extern "C"
