@@ -66,10 +66,27 @@ struct DensePack {
     PackedConv c1, c2;       // 1-wide bottleneck (stored as 7 taps, centre one non-zero), k-wide convolution
     size_t aff1 = 0, aff2 = 0;   // float offsets of the two (eval-mode) tables
     // training: the two BatchNorm layers (indices into ake_pcnet::bns), the data-gradient packs (transposed + flipped weights, stored like c1 / c2)
-    // and the parameter names
+    // and the parameters (indices into ake_pcnet::specs)
     int bn1 = -1, bn2 = -1;
     PackedConv d1, d2;
-    std::string norm1, norm2, w1, w2, b2;       // b2 empty: bias=False (the plain Conv2d form)
+    int w1 = -1, b1 = -1, w2 = -1, b2 = -1;     // b1 / b2 == -1: bias=False (the plain Conv2d form)
+};
+
+// One convolution of the net, resolved once by build_packs: its three packs, the BatchNorm behind it and its parameters.  Fwd, Bwd, the
+// fragment packing and the train-mode taps all take their tensors from here: none of them spells a state_dict name.
+struct ConvSite {
+    PackedConv eval, train, dgrad;   // BatchNorm folded (inference) | raw weights (training) | transposed + flipped raw weights (data gradient)
+    int bn = -1;                     // index into ake_pcnet::bns, -1: no BatchNorm behind it (a head's last conv)
+    int w = -1, b = -1;              // indices into ake_pcnet::specs
+};
+
+struct BnSpecs { int weight = -1, bias = -1, mean = -1, var = -1; };   // one BatchNorm's tensors, indices into ake_pcnet::specs
+
+struct Head {
+    std::vector<ConvSite> convs;     // head_layers entries (empty: a net without the genre head)
+    int kind;                        // run_conv's: 1 rows circular (12 x k), 2 rows valid (the genre head)
+    const char* nm;                  // module name
+    bool conv2d;                     // its convolutions are wrappers ("<nm>.<3j>.conv2d.weight")
 };
 
 int pick_co(int cout) { return cout >= 8 ? 8 : (cout >= 2 ? 4 : 1); }
@@ -90,23 +107,17 @@ struct ake_pcnet {
     // packed parameters
     std::vector<float> blob;
     float* blob_dev = nullptr;
-    std::vector<PackedConv> foldc, foldc_t;       // per layer: --p2pc_conv's octave-fold convolution [co][ci][n_oct]
-    std::vector<PackedConv> semi;                 // per layer
-    std::vector<std::vector<PackedConv>> pc2pc;   // per layer, conv_layers entries
-    std::vector<PackedConv> up;                   // per layer (index 0 unused)
-    std::vector<std::vector<PackedConv>> p2p;     // per layer (index 0 empty)
-    std::vector<PackedConv> head_key, head_tonic, head_genre;
+    std::vector<ConvSite> foldc;                  // per layer: --p2pc_conv's octave-fold convolution [co][ci][n_oct] (no dgrad pack)
+    std::vector<ConvSite> semi;                   // per layer (no dgrad pack)
+    std::vector<std::vector<ConvSite>> pc2pc;     // per layer, conv_layers entries (--resblock: conv0, then conv1, conv2 per block)
+    std::vector<ConvSite> up;                     // per layer (index 0 unused; no dgrad pack)
+    std::vector<std::vector<ConvSite>> p2p;       // per layer (index 0 empty)
+    Head heads[3] = {{{}, 1, "key_classifier", true}, {{}, 1, "tonic_classifier", true}, {{}, 2, "genre_classifier", false}};
 
-    // training-mode packs: raw convolution weights (no BatchNorm folding) + the BatchNorm layers themselves
-    std::vector<PackedConv> semi_t, up_t, head_key_t, head_tonic_t, head_genre_t;
-    std::vector<std::vector<PackedConv>> pc2pc_t, p2p_t;
-    struct BnLayer { std::string name; int C; size_t gamma_off, beta_off; int ch_off; };
+    // the BatchNorm layers of the training-mode forward, in forward order (gamma / beta in the blob)
+    struct BnLayer { std::string name; int C; size_t gamma_off, beta_off; int ch_off; BnSpecs p; };
     std::vector<BnLayer> bns;
-    std::map<std::string, int> bn_index;
     int bn_channels = 0;
-    // backward: data-gradient packs (transposed + flipped raw weights, same fragment format) and the flat gradient layout
-    std::vector<std::vector<PackedConv>> pc2pc_d, p2p_d;
-    std::vector<PackedConv> head_key_d, head_tonic_d, head_genre_d;
     std::vector<size_t> grad_off;      // float offset of specs[i] in the flat gradient buffer
     size_t grad_floats = 0;
     std::vector<size_t> raw_w_off;     // float offset in the blob of specs[i]'s raw values (convolution weights used by small kernels)
@@ -114,7 +125,7 @@ struct ake_pcnet {
     // device-side rebuild of the blob from a flat parameter buffer (same layout as the gradient buffer):
     //   folded[i] = eval-mode BatchNorm folded into params[i] (conv weights / biases in front of a BatchNorm), else params[i]
     //   blob[j]   = map[j] < 0 ? 0 : (map[j] & kMapFolded ? folded : params)[map[j] & kMapIndex]
-    struct FoldRecord { std::string wkey, bkey, bn; int cout; size_t per_out; bool transposed; int cin; };
+    struct FoldRecord { int w, b; BnSpecs bn; int cout; size_t per_out; bool transposed; int cin; };
     std::vector<FoldRecord> fold_records;
     std::vector<int32_t> map_host;     // one entry per blob float
     int32_t* map_dev = nullptr;
@@ -126,7 +137,7 @@ struct ake_pcnet {
     float* folded_dev = nullptr;
     bool tracing = false;
     std::vector<std::vector<DensePack>> dense_pc, dense_p;   // --denseblock: per layer, conv_layers entries
-    struct AffRec { std::string bn; int C; float slope; size_t off; };
+    struct AffRec { BnSpecs bn; int C; float slope; size_t off; };
     std::vector<AffRec> aff_recs;      // BatchNorm layers behind dense_aff_dev, in table order
     size_t dense_aff_floats = 0;
     float* dense_aff_dev = nullptr;
@@ -157,24 +168,23 @@ void add_bn_specs(ake_pcnet* n, const std::string& prefix, int c) {
     for (const char* f : {".weight", ".bias", ".running_mean", ".running_var"}) add_spec(n, prefix + f, {c});
 }
 
-const std::vector<float>& T(const ake_pcnet* n, const std::string& name) {
-    return n->host[n->spec_index.at(name)].data;
-}
+// the host copy of specs[spec] (build_packs resolves every name before it packs: the pack helpers below only see valid indices)
+const std::vector<float>& T(const ake_pcnet* n, int spec) { return n->host[spec].data; }
 
-// conv weight [cout][cin][kh][kw] + bias, optionally followed by BatchNorm(bn_prefix) in eval mode:
+// conv weight [cout][cin][kh][kw] + bias, optionally followed by the BatchNorm `bn` (null: none) in eval mode:
 //   y = (conv(x) - mean) * gamma / sqrt(var + eps) + beta  ==  conv'(x) with w' = w*s, b' = (b - mean)*s + beta
-void fold(const ake_pcnet* n, const std::string& wkey, const std::string& bkey, const std::string& bn_prefix,
-          int cout, size_t per_out, bool transposed_cin_first, int cin, std::vector<double>& w, std::vector<double>& b) {
-    const auto& w32 = T(n, wkey);
-    const auto& b32 = T(n, bkey);
+void fold(const ake_pcnet* n, int wspec, int bspec, const BnSpecs* bn, int cout, size_t per_out, bool transposed_cin_first, int cin,
+          std::vector<double>& w, std::vector<double>& b) {
+    const auto& w32 = T(n, wspec);
+    const auto& b32 = T(n, bspec);
     w.assign(w32.begin(), w32.end());
     b.assign(b32.begin(), b32.end());
-    if (bn_prefix.empty()) return;
-    if (n->tracing) const_cast<ake_pcnet*>(n)->fold_records.push_back({wkey, bkey, bn_prefix, cout, per_out, transposed_cin_first, cin});
-    const auto& g = T(n, bn_prefix + ".weight");
-    const auto& be = T(n, bn_prefix + ".bias");
-    const auto& mu = T(n, bn_prefix + ".running_mean");
-    const auto& var = T(n, bn_prefix + ".running_var");
+    if (!bn) return;
+    if (n->tracing) const_cast<ake_pcnet*>(n)->fold_records.push_back({wspec, bspec, *bn, cout, per_out, transposed_cin_first, cin});
+    const auto& g = T(n, bn->weight);
+    const auto& be = T(n, bn->bias);
+    const auto& mu = T(n, bn->mean);
+    const auto& var = T(n, bn->var);
     for (int co = 0; co < cout; ++co) {
         const double s = static_cast<double>(g[co]) / std::sqrt(static_cast<double>(var[co]) + kBnEps);
         if (!transposed_cin_first) {
@@ -239,8 +249,8 @@ PackedConv pack_conv(ake_pcnet* n, const std::vector<double>& w, const std::vect
 }
 
 // Data-gradient pack of a convolution: the transposed + flipped raw weights as a forward-type conv (cin' = cout, cout' = cin)
-PackedConv dgrad_pack(ake_pcnet* n, const std::string& wkey, int cout, int cin, int kh, int kw) {
-    const auto& w32 = T(n, wkey);
+PackedConv dgrad_pack(ake_pcnet* n, int wspec, int cout, int cin, int kh, int kw) {
+    const auto& w32 = T(n, wspec);
     std::vector<double> w(static_cast<size_t>(cin) * cout * kh * kw), b(cin, 0.0);
     for (int co = 0; co < cout; ++co)
         for (int ci = 0; ci < cin; ++ci)
@@ -251,21 +261,15 @@ PackedConv dgrad_pack(ake_pcnet* n, const std::string& wkey, int cout, int cin, 
     return pack_conv(n, w, b, cin, cout, kh, kw);
 }
 
-PackedConv fold_pack(ake_pcnet* n, const std::string& conv_prefix, const std::string& bn_prefix, int cout, int cin, int kh, int kw) {
-    std::vector<double> w, b;
-    fold(n, conv_prefix + ".weight", conv_prefix + ".bias", bn_prefix, cout, static_cast<size_t>(cin) * kh * kw, false, cin, w, b);
-    return pack_conv(n, w, b, cout, cin, kh, kw);
-}
-
 // --denseblock: a convolution with its raw weights (no BatchNorm behind it); a 1-wide kernel is stored as 7 taps with only the centre
-// one non-zero, so that the 7-tap Toeplitz kernels run it (bkey empty: bias=False)
+// one non-zero, so that the 7-tap Toeplitz kernels run it (bspec < 0: bias=False)
 PackedConv dense_conv_pack_w(ake_pcnet* n, const std::vector<float>& w32, const std::vector<float>* b32p, int cout, int cin, int kh, int kw_src);
-PackedConv dense_conv_pack(ake_pcnet* n, const std::string& wkey, const std::string& bkey, int cout, int cin, int kh, int kw_src) {
-    return dense_conv_pack_w(n, T(n, wkey), bkey.empty() ? nullptr : &T(n, bkey), cout, cin, kh, kw_src);
+PackedConv dense_conv_pack(ake_pcnet* n, int wspec, int bspec, int cout, int cin, int kh, int kw_src) {
+    return dense_conv_pack_w(n, T(n, wspec), bspec < 0 ? nullptr : &T(n, bspec), cout, cin, kh, kw_src);
 }
 // the data-gradient pack of such a convolution: the weights transposed (cin <-> cout) and flipped on both axes, stored the same way
-PackedConv dense_dgrad_pack(ake_pcnet* n, const std::string& wkey, int cout, int cin, int kh, int kw_src) {
-    const auto& w32 = T(n, wkey);
+PackedConv dense_dgrad_pack(ake_pcnet* n, int wspec, int cout, int cin, int kh, int kw_src) {
+    const auto& w32 = T(n, wspec);
     std::vector<float> w(static_cast<size_t>(cin) * cout * kh * kw_src);
     for (int co = 0; co < cout; ++co)
         for (int ci = 0; ci < cin; ++ci)
@@ -464,7 +468,7 @@ bool p2p_uses_f16(const ake_pcnet* n, int i, int T) {
     const auto& c = n->cfg;
     if (c.precision == AKE_PRECISION_F32X3 || c.resblock || i < 1 || c.conv_layers < 2 || n->dims[i].out_p != 8 || T > 146) return false;
     for (int j = 0; j < c.conv_layers; ++j)
-        if (n->p2p[i][j].bf_off < 0) return false;
+        if (n->p2p[i][j].eval.bf_off < 0) return false;
     return true;
 }
 
@@ -472,8 +476,8 @@ bool p2p_uses_f16(const ake_pcnet* n, int i, int T) {
 constexpr int kPcBf16MaxFrames = 120;
 bool pc2pc_uses_bf16(const ake_pcnet* n, int i, int T) {
     if (n->cfg.resblock || n->pc2pc[i].empty() || T > kPcBf16MaxFrames) return false;
-    for (const PackedConv& pc : n->pc2pc[i])
-        if (pc.bf_off < 0 || pc.cout != 16) return false;
+    for (const ConvSite& cs : n->pc2pc[i])
+        if (cs.eval.bf_off < 0 || cs.eval.cout != 16) return false;
     return true;
 }
 
@@ -544,7 +548,7 @@ int p2p_ps_rows(int H, int T, bool semi, int* plane_pos, size_t* lds, int nw = 8
 // does inference fuse the semitone conv of layer i into the last pitch conv of its stack (the pitch tensor is then never written)?
 // Only in the net's last layer: an inner layer's pitch tensor is also the next layer's pitch stream (time_pool_p, models.py:395).
 bool p2p_fuses_semi(const ake_pcnet* n, int i, int P, int T) {
-    return !g_keep_taps && !n->cfg.p2pc_conv && !n->cfg.stay_sixth && i == n->cfg.num_layers - 1 && p2p_uses_f16(n, i, T) && static_cast<size_t>(i) < n->semi.size() && n->semi[i].bf_off >= 0 &&
+    return !g_keep_taps && !n->cfg.p2pc_conv && !n->cfg.stay_sixth && i == n->cfg.num_layers - 1 && p2p_uses_f16(n, i, T) && static_cast<size_t>(i) < n->semi.size() && n->semi[i].eval.bf_off >= 0 &&
            p2p_ps_rows(P, T, true, nullptr, nullptr) > 0;
 }
 
@@ -699,7 +703,7 @@ P2pStackPlan p2p_stack_plan(int convs, int c0, int c1, bool semi_frags, int batc
 }
 
 // the launch of a planned stack (the same contract as run_p2p_f16_ps: it cannot decline).  planes[j]: where conv j < n - 1 leaves its plane
-int run_p2p_stack(const ake_pcnet* n, const std::vector<PackedConv>& convs, const PackedConv& semi, const P2pStackPlan& g, const unsigned int* melh, const uint2* psix_h,
+int run_p2p_stack(const ake_pcnet* n, const std::vector<ConvSite>& convs, const PackedConv& semi, const P2pStackPlan& g, const unsigned int* melh, const uint2* psix_h,
                   int c1, unsigned short* const planes[], float* cat, int cat_ctot, int fold_coff, int batch, int H, int T, hipStream_t s, const char* name) {
     AKE_REQUIRE(g.ok && g.n == static_cast<int>(convs.size()) && batch <= device_cus(), AKE_ERR_STATE,
                 "conv %s: the route sent a stack to the one-launch kernel that does not qualify for it", name);
@@ -712,7 +716,7 @@ int run_p2p_stack(const ake_pcnet* n, const std::vector<PackedConv>& convs, cons
         P2pPsArgs& a = sa.ph[j];
         AKE_REQUIRE(fold || planes[j], AKE_ERR_STATE, "conv %s: the one-launch stack lacks a plane", name);
         a.R = g.R[fold]; a.plane_pos = g.plane_pos[fold]; a.n_row_tiles = g.n_row_tiles[fold]; a.n_tiles = a.n_row_tiles * batch;
-        a.bfrag = n->bf_frags_dev + convs[j].bf_off; a.bias = n->blob_dev + convs[j].b_off;
+        a.bfrag = n->bf_frags_dev + convs[j].eval.bf_off; a.bias = n->blob_dev + convs[j].eval.b_off;
         a.H = H; a.T = T; a.J = T / 2; a.Tp = p2p_pitch(a.J);
         if (j == 0) { a.ph = melh; a.uh = psix_h; a.c0 = 1; a.c1 = c1; a.h1 = 36; }
         else a.xh = planes[j - 1];
@@ -804,8 +808,8 @@ bool pc2pc_fuses(const ake_pcnet* n, int i, int T) {
     const auto& c = n->cfg;
     if (g_keep_taps || i < 1 || i != c.num_layers - 1 || c.time_pool_size != 2 || c.conv_layers < 1 || c.conv_layers > 4) return false;
     if (!pc2pc_uses_bf16(n, i, T) || T % 4 || 12 * T > 1024 || 3 * ((T + 15) / 16) > 16) return false;   // (16 waves: 3 row groups x 16-frame tiles)
-    for (const PackedConv& pc : n->pc2pc[i])
-        if (pc.cout != 16 || pc.cin > 16 || pc.kh != 12) return false;
+    for (const ConvSite& cs : n->pc2pc[i])
+        if (cs.eval.cout != 16 || cs.eval.cin > 16 || cs.eval.kh != 12) return false;
     return (static_cast<size_t>(4) * 12 * (T + 8) * 2 + 2 * 512) * sizeof(uint4) <= 160 * 1024;     // two maps + the weight ring
 }
 
@@ -814,7 +818,7 @@ int run_pc2pc_fused(const ake_pcnet* n, int i, const float* src, int cin, int ba
     std::memset(&a, 0, sizeof(a));
     a.src = src; a.src_clip_stride = static_cast<long long>(cin) * 12 * T; a.cin = cin;
     a.n_conv = static_cast<int>(n->pc2pc[i].size());
-    for (int j = 0; j < a.n_conv; ++j) { a.bfrag[j] = n->bf_frags_dev + n->pc2pc[i][j].bf_off; a.bias[j] = n->blob_dev + n->pc2pc[i][j].b_off; }
+    for (int j = 0; j < a.n_conv; ++j) { a.bfrag[j] = n->bf_frags_dev + n->pc2pc[i][j].eval.bf_off; a.bias[j] = n->blob_dev + n->pc2pc[i][j].eval.b_off; }
     a.pooled = pooled;
     if (feat_cl) { a.fh = feat_cl; a.fl = feat_cl + static_cast<long long>(batch) * 12 * (T / 2) * 16; }
     a.T = T; a.Tp = T + 8;
@@ -1208,11 +1212,11 @@ Layer0Plan layer0_plan(const ake_pcnet* n, int T0, bool mel16, bool mel_fm) {
     const int P = c.pitches, NF = c.n_filters;
     Layer0Plan g;
     if (c.num_layers < 2 || c.resblock || c.denseblock || c.p2pc_conv || c.stay_sixth || NF < 2 || NF > 4 || c.conv_layers < 1 || c.conv_layers > 4 || c.kernel_size != 7 || P % 36 || T0 < 1) return g;
-    const PackedConv& sp = n->semi[0];
+    const PackedConv& sp = n->semi[0].eval;
     if (sp.cin != 1 || sp.co != 1) return g;
     bool mfma = c.precision == AKE_PRECISION_MIXED;      // (the MFMA form multiplies f16 x f16; f32x3: the exact-f32 VALU form)
     for (int j = 0; j < c.conv_layers; ++j) {
-        const PackedConv& pc = n->pc2pc[0][j];
+        const PackedConv& pc = n->pc2pc[0][j].eval;
         if (pc.co != 4 || pc.groups != 1 || pc.kh != 12 || pc.kw != 7 || pc.cout != NF || pc.cin != (j == 0 ? 1 : NF)) return g;
         mfma = mfma && pc.l0_off >= 0;
     }
@@ -1302,7 +1306,7 @@ Route build_route(const ake_pcnet* n, bool train, int batch, int chunk, int fram
                 rp.k[k].x3[1] = p2p_f16x3_plan(d.out_p, 0, d.out_p, B, P, Ti, ws16);
             }
             for (int j = 0; j < c.conv_layers && j < 32; ++j)          // (eligibility does not depend on the clip count)
-                if ((train ? n->p2p_t[i][j] : n->p2p[i][j]).bf_off >= 0 && rp.k[0].x3[j > 0].ok) rp.x3_convs |= 1u << j;
+                if ((train ? n->p2p[i][j].train : n->p2p[i][j].eval).bf_off >= 0 && rp.k[0].x3[j > 0].ok) rp.x3_convs |= 1u << j;
             if (rp.x3_convs) rp.stack = PStack::F16x3;
         }
         cp = d.out_p;
@@ -1316,23 +1320,23 @@ Route build_route(const ake_pcnet* n, bool train, int batch, int chunk, int fram
     else if (!train && pc2pc_uses_bf16(n, i, Ti)) r.pc = PcStack::Bf16;
     else if (train && L > 1 && !c.resblock && !c.denseblock) {
         for (int j = 0; j < c.conv_layers && j < 32; ++j)
-            if (pc_f16x3_ok(n->pc2pc_t[i][j], Ti, true)) r.pc_x3_convs |= 1u << j;
+            if (pc_f16x3_ok(n->pc2pc[i][j].train, Ti, true)) r.pc_x3_convs |= 1u << j;
         if (r.pc_x3_convs) r.pc = PcStack::F16x3;
     }
 
     // ---- heads (training keeps its own per-conv choices in Fwd::tail) ----
     // key / tonic heads: the first convolution (16 -> 32 channels, most of a head's work) on the bf16 kernel
-    const bool head_bf = !train && L > 1 && n->final_ch == 16 && c.head_layers >= 2 && n->head_key[0].bf_off >= 0 && n->head_tonic[0].bf_off >= 0 &&
+    const std::vector<ConvSite>&hk = n->heads[0].convs, &ht = n->heads[1].convs, &hg = n->heads[2].convs;      // key, tonic, genre
+    const bool head_bf = !train && L > 1 && n->final_ch == 16 && c.head_layers >= 2 && hk[0].eval.bf_off >= 0 && ht[0].eval.bf_off >= 0 &&
                          Tf <= kPcBf16MaxFrames;
     if (!head_bf) return r;
     r.heads = HeadForm::Bf16First;
     // two-conv heads: conv0 leaves its 32 channels as channels-last planes and ONE launch of conv_head1_bf16_kernel finishes both maps
     r.T1 = Tf - (c.kernel_size - 1); r.T2 = r.T1 - (c.kernel_size - 1);
     const int T1 = r.T1, T2 = r.T2;
-    if (!(c.head_layers == 2 && n->head_key[1].bf_off >= 0 && n->head_tonic[1].bf_off >= 0 && T2 > 0 && (12 * ((T2 + 15) / 16) + 15) / 16 <= kHead1MT)) return r;
+    if (!(c.head_layers == 2 && hk[1].eval.bf_off >= 0 && ht[1].eval.bf_off >= 0 && T2 > 0 && (12 * ((T2 + 15) / 16) + 15) / 16 <= kHead1MT)) return r;
     r.heads = HeadForm::Head1;
-    r.genre_bf = c.genre && n->head_genre.size() == 2 && n->head_genre[0].bf_off >= 0 && n->head_genre[1].bf_off >= 0 && n->head_genre[0].kh == 1 &&
-                 n->head_genre[1].kh == 2;
+    r.genre_bf = c.genre && hg.size() == 2 && hg[0].eval.bf_off >= 0 && hg[1].eval.bf_off >= 0 && hg[0].eval.kh == 1 && hg[1].eval.kh == 2;
     r.heads_pool = c.local == 0;
     // ... and when the stack above ran as one launch both convolutions of a head run as ONE launch too (heads_fused_kernel): the 32 hidden
     // channels stay in LDS.  ake_debug_keep_taps(1), other head depths and shapes whose patches do not fit keep the two launches.
@@ -1341,8 +1345,8 @@ Route build_route(const ake_pcnet* n, bool train, int batch, int chunk, int fram
                          static_cast<size_t>(2) * 12 * r.TpB * 4 * sizeof(uint4),                                // phase B: patch,
                          static_cast<size_t>(8) * kHead1MT * 4 * 64 * sizeof(float)}) +                          // then the partial tiles
                static_cast<size_t>(12) * T2 * sizeof(float);                                                     // the finished map
-    if (r.pc == PcStack::Fused && !g_keep_taps && c.local == 0 && n->head_key[0].cout == 32 && n->head_tonic[0].cout == 32 && n->head_key[0].kh == 12 &&
-        n->head_tonic[0].kh == 12 && n->head_key[1].kh == 12 && n->head_tonic[1].kh == 12 && (!r.genre_bf || n->head_genre[0].cout == 32) &&
+    if (r.pc == PcStack::Fused && !g_keep_taps && c.local == 0 && hk[0].eval.cout == 32 && ht[0].eval.cout == 32 && hk[0].eval.kh == 12 &&
+        ht[0].eval.kh == 12 && hk[1].eval.kh == 12 && ht[1].eval.kh == 12 && (!r.genre_bf || hg[0].eval.cout == 32) &&
         (12 * T1 + 15) / 16 <= 32 && r.hf_lds <= 150 * 1024) {
         r.heads = HeadForm::Fused;
         // phase A's M-tiles over the 8 waves: three each where 24 cover the hidden map (12 x 32 positions and fewer), else four
@@ -1565,70 +1569,151 @@ int ake_pcnet_set_tensor(ake_pcnet* n, const char* name, const float* host_data,
     return AKE_OK;
 }
 
-// Packs every convolution of the net into the blob.  train == false: eval-mode BatchNorm folded into w/b.
-// train == true: raw weights; each BatchNorm is registered as a layer of its own (gamma/beta in the blob).
-static void build_packs(ake_pcnet* n, bool train) {
+// Every BatchNorm layer is referenced by exactly one site, and every parameter that is not a running statistic by exactly one site or
+// BatchNorm layer: a convolution or a BatchNorm that the walk over the sites forgets would train with a gradient of exact zeros.
+static int check_sites(const ake_pcnet* n) {
+    std::vector<int> bn_refs(n->bns.size(), 0), spec_refs(n->specs.size(), 0);
+    auto ref_bn = [&](int bn) { if (bn >= 0) ++bn_refs[bn]; };
+    auto ref_spec = [&](int spec) { if (spec >= 0) ++spec_refs[spec]; };
+    auto see = [&](const ConvSite& cs) { ref_bn(cs.bn); ref_spec(cs.w); ref_spec(cs.b); };
+    for (const auto* v : {&n->semi, &n->up, &n->foldc})
+        for (const ConvSite& cs : *v) see(cs);
+    for (const auto* vv : {&n->pc2pc, &n->p2p})
+        for (const auto& v : *vv)
+            for (const ConvSite& cs : v) see(cs);
+    for (const Head& h : n->heads)
+        for (const ConvSite& cs : h.convs) see(cs);
+    for (const auto* vv : {&n->dense_pc, &n->dense_p})
+        for (const auto& v : *vv)
+            for (const DensePack& dp : v) { ref_bn(dp.bn1); ref_bn(dp.bn2); ref_spec(dp.w1); ref_spec(dp.b1); ref_spec(dp.w2); ref_spec(dp.b2); }
+    for (size_t i = 0; i < n->bns.size(); ++i) {
+        AKE_REQUIRE(bn_refs[i] == 1, AKE_ERR_STATE, "finalize: BatchNorm '%s' belongs to %d sites, not one", n->bns[i].name.c_str(), bn_refs[i]);
+        ref_spec(n->bns[i].p.weight); ref_spec(n->bns[i].p.bias);
+        spec_refs[n->bns[i].p.mean] = spec_refs[n->bns[i].p.var] = 1;      // running statistics: no gradient, their BatchNorm owns them
+    }
+    for (size_t i = 0; i < n->specs.size(); ++i)
+        AKE_REQUIRE(spec_refs[i] == 1, AKE_ERR_STATE, "finalize: parameter '%s' belongs to %d sites, not one", n->specs[i].name.c_str(), spec_refs[i]);
+    return AKE_OK;
+}
+
+// Packs every convolution of the net into the blob and resolves its site.  train == false (the first pass; it starts the sites afresh):
+// eval-mode BatchNorm folded into w/b.  train == true: raw weights, the data-gradient packs, and each BatchNorm registered as a layer of
+// its own (gamma/beta in the blob); the sites get their BatchNorm and parameter indices here.  This is the one place that spells the
+// reference's state_dict names: a name that does not resolve, or a parameter left without a site, is AKE_ERR_STATE.
+static int build_packs(ake_pcnet* n, bool train) {
     const auto& c = n->cfg;
     const int L = c.num_layers, k = c.kernel_size;
-    auto& semi = train ? n->semi_t : n->semi;
-    auto& up = train ? n->up_t : n->up;
-    auto& pc2pc = train ? n->pc2pc_t : n->pc2pc;
-    auto& p2p = train ? n->p2p_t : n->p2p;
-    semi.assign(L, PackedConv()); up.assign(L, PackedConv());
-    (train ? n->foldc_t : n->foldc).assign(L, PackedConv());
-    pc2pc.assign(L, {}); p2p.assign(L, {});
-    if (!train) { n->dense_pc.assign(L, {}); n->dense_p.assign(L, {}); }
-    // --denseblock (eval packs only): layer j of a block reads cin + j * nf channels
-    auto dense_block = [&](const std::string& base, int cin, bool equiv, std::vector<DensePack>& out) {
+    if (!train) {
+        n->semi.assign(L, {}); n->up.assign(L, {}); n->foldc.assign(L, {});
+        n->pc2pc.assign(L, {}); n->p2p.assign(L, {});
+        n->dense_pc.assign(L, {}); n->dense_p.assign(L, {});
+        for (Head& h : n->heads) h.convs.clear();
+    }
+    std::string missing;             // the first name that did not resolve
+    auto spec = [&](const std::string& name) {
+        const auto it = n->spec_index.find(name);
+        if (it != n->spec_index.end()) return it->second;
+        if (missing.empty()) missing = name;
+        return -1;
+    };
+    auto bn_specs = [&](const std::string& prefix) {
+        return BnSpecs{spec(prefix + ".weight"), spec(prefix + ".bias"), spec(prefix + ".running_mean"), spec(prefix + ".running_var")};
+    };
+    auto add_bn = [&](const std::string& prefix, const BnSpecs& p, int C) {      // training pass: registers the layer, returns its index
+        ake_pcnet::BnLayer l;
+        l.name = prefix; l.C = C; l.ch_off = n->bn_channels; l.p = p;
+        n->blob.resize(ake::align_up(n->blob.size(), 64));
+        l.gamma_off = n->blob.size();
+        for (float v : T(n, p.weight)) n->blob.push_back(v);
+        l.beta_off = n->blob.size();
+        for (float v : T(n, p.bias)) n->blob.push_back(v);
+        n->bns.push_back(l);
+        n->bn_channels += C;
+        return static_cast<int>(n->bns.size()) - 1;
+    };
+    // One site: convolution `conv` (+ BatchNorm `bnp`, empty: none).  The eval pass folds and packs it, the training pass registers the
+    // BatchNorm, packs the raw values and records the indices; pack(w, b) lays the values out in the blob.
+    auto site = [&](ConvSite& cs, const std::string& conv, const std::string& bnp, int cout, size_t per_out, bool transposed, int cin, auto&& pack) {
+        const int w = spec(conv + ".weight"), b = spec(conv + ".bias");
+        const BnSpecs p = bnp.empty() ? BnSpecs{} : bn_specs(bnp);
+        if (!missing.empty()) return;
+        if (train) { cs.w = w; cs.b = b; cs.bn = bnp.empty() ? -1 : add_bn(bnp, p, cout); }
+        std::vector<double> wv, bv;
+        fold(n, w, b, train || bnp.empty() ? nullptr : &p, cout, per_out, transposed, cin, wv, bv);
+        (train ? cs.train : cs.eval) = pack(wv, bv);
+    };
+    auto conv_site = [&](ConvSite& cs, const std::string& conv, const std::string& bnp, int cout, int cin, int kh, int kw) {
+        site(cs, conv, bnp, cout, static_cast<size_t>(cin) * kh * kw, false, cin,
+             [&](const std::vector<double>& w, const std::vector<double>& b) { return pack_conv(n, w, b, cout, cin, kh, kw); });
+    };
+    auto dgrad_site = [&](ConvSite& cs) {      // training pass: the data-gradient pack of a site conv_site has packed
+        if (train && cs.w >= 0) cs.dgrad = dgrad_pack(n, cs.w, cs.train.cout, cs.train.cin, cs.train.kh, cs.train.kw);
+    };
+    // ch -> ch channels over kh taps, the values as they are stored ([ci][co][3] for up_sixth, [co][ci][n_oct] for the octave fold)
+    auto plain = [&](int ch, int kh) {
+        return [n, ch, kh](const std::vector<double>& w, const std::vector<double>& b) {
+            PackedConv u;
+            u.cin = u.cout = ch; u.kh = kh; u.kw = 1;
+            n->blob.resize(ake::align_up(n->blob.size(), 64));
+            u.w_off = n->blob.size();
+            for (double v : w) n->blob.push_back(static_cast<float>(v));
+            n->blob.resize(ake::align_up(n->blob.size(), 64));
+            u.b_off = n->blob.size();
+            for (double v : b) n->blob.push_back(static_cast<float>(v));
+            return u;
+        };
+    };
+    // a stack: conv_layers x (conv + BatchNorm), or --resblock's [conv0, (conv1, conv2) per block] with the data-gradient packs behind each block's two
+    auto stack = [&](std::vector<ConvSite>& st, const std::string& prefix, const char* cv, int cin0, int cout, int kh) {
+        st.resize(c.resblock ? 1 + 2 * c.conv_layers : c.conv_layers);
+        if (c.resblock) {
+            conv_site(st[0], prefix + "0" + cv, prefix + "1", cout, cin0, kh, k);
+            dgrad_site(st[0]);
+            for (int r = 0; r < c.conv_layers; ++r) {
+                const std::string bp = prefix + std::to_string(3 + r) + ".";
+                conv_site(st[1 + 2 * r], bp + "conv1" + cv, bp + "b1", 2 * cout, cout, kh, k);
+                conv_site(st[2 + 2 * r], bp + "conv2" + cv, bp + "b2", cout, 2 * cout, kh, k);
+                dgrad_site(st[1 + 2 * r]);
+                dgrad_site(st[2 + 2 * r]);
+            }
+            return;
+        }
+        for (int j = 0; j < c.conv_layers; ++j) {
+            conv_site(st[j], prefix + std::to_string(3 * j) + cv, prefix + std::to_string(3 * j + 1), cout, j == 0 ? cin0 : cout, kh, k);
+            dgrad_site(st[j]);
+        }
+    };
+    // --denseblock: layer j of a block reads cin + j * nf channels.  The convolutions keep their raw weights in both modes (the eval packs
+    // serve the training forward); the training pass adds the blocks' BatchNorm layers in forward order and the data-gradient packs
+    auto dense_block = [&](const std::string& base, int cin, bool equiv, std::vector<DensePack>& packs) {
         const int nf = c.n_filters, bott = (cin > 1 ? cin / 2 : 1) * nf;
-        auto table = [&](const std::string& bnp, int C, float slope) {
+        auto table = [&](const BnSpecs& bnp, int C, float slope) {
             const size_t off = n->dense_aff_floats;
             n->aff_recs.push_back({bnp, C, slope, off});
             n->dense_aff_floats += static_cast<size_t>(3) * C;
             return off;
         };
+        packs.resize(c.conv_layers);
         for (int j = 0; j < c.conv_layers; ++j) {
-            const std::string lp = base + "denselayer" + std::to_string(j + 1) + ".";
+            const std::string lp = base + "denselayer" + std::to_string(j + 1) + ".", cv = equiv ? ".conv2d" : "";
             const int cj = cin + j * nf;
-            DensePack dp;
-            dp.norm1 = lp + "norm1"; dp.norm2 = lp + "norm2";
-            dp.w1 = lp + (equiv ? "conv1.conv2d.weight" : "conv1.weight"); dp.w2 = lp + (equiv ? "conv2.conv2d.weight" : "conv2.weight");
-            dp.b2 = equiv ? lp + "conv2.conv2d.bias" : "";
-            dp.aff1 = table(lp + "norm1", cj, 0.01f);                                  // relu1 = nn.LeakyReLU, models.py:463 / :526
-            dp.c1 = equiv ? dense_conv_pack(n, lp + "conv1.conv2d.weight", lp + "conv1.conv2d.bias", bott, cj, 12, 1)
-                          : dense_conv_pack(n, lp + "conv1.weight", "", bott, cj, 1, 1);
-            dp.aff2 = table(lp + "norm2", bott, 0.f);                                  // relu2 = nn.ReLU, models.py:467 / :530
-            dp.c2 = equiv ? dense_conv_pack(n, lp + "conv2.conv2d.weight", lp + "conv2.conv2d.bias", nf, bott, 12, k)
-                          : dense_conv_pack(n, lp + "conv2.weight", "", nf, bott, k, k);
-            out.push_back(dp);
-        }
-    };
-    if (train) { n->pc2pc_d.assign(L, {}); n->p2p_d.assign(L, {}); n->head_key_d.clear(); n->head_tonic_d.clear(); n->head_genre_d.clear(); }
-    auto bn = [&](const std::string& prefix, int C) -> std::string {
-        if (!train) return prefix;
-        ake_pcnet::BnLayer l;
-        l.name = prefix; l.C = C; l.ch_off = n->bn_channels;
-        n->blob.resize(ake::align_up(n->blob.size(), 64));
-        l.gamma_off = n->blob.size();
-        for (float v : T(n, prefix + ".weight")) n->blob.push_back(v);
-        l.beta_off = n->blob.size();
-        for (float v : T(n, prefix + ".bias")) n->blob.push_back(v);
-        n->bn_index[prefix] = static_cast<int>(n->bns.size());
-        n->bns.push_back(l);
-        n->bn_channels += C;
-        return "";
-    };
-    // --denseblock, training pass: the blocks' BatchNorm layers in forward order and the data-gradient packs (the convolutions themselves
-    // keep their raw weights in both modes: the eval packs serve the training forward)
-    auto dense_block_train = [&](int cin, bool equiv, std::vector<DensePack>& packs) {
-        const int nf = c.n_filters;
-        for (size_t j = 0; j < packs.size(); ++j) {
             DensePack& dp = packs[j];
-            const int cj = cin + static_cast<int>(j) * nf, bott = dp.c1.cout;
-            bn(dp.norm1, cj); dp.bn1 = n->bn_index.at(dp.norm1);
-            bn(dp.norm2, bott); dp.bn2 = n->bn_index.at(dp.norm2);
-            dp.d1 = dense_dgrad_pack(n, dp.w1, bott, cj, equiv ? 12 : 1, 1);
-            dp.d2 = dense_dgrad_pack(n, dp.w2, nf, bott, equiv ? 12 : k, k);
+            const BnSpecs n1 = bn_specs(lp + "norm1"), n2 = bn_specs(lp + "norm2");
+            const int w1 = spec(lp + "conv1" + cv + ".weight"), w2 = spec(lp + "conv2" + cv + ".weight");
+            const int b1 = equiv ? spec(lp + "conv1" + cv + ".bias") : -1, b2 = equiv ? spec(lp + "conv2" + cv + ".bias") : -1;      // plain Conv2d: bias=False, models.py:464
+            if (!missing.empty()) return;
+            if (!train) {
+                dp.aff1 = table(n1, cj, 0.01f);                                        // relu1 = nn.LeakyReLU, models.py:463 / :526
+                dp.c1 = dense_conv_pack(n, w1, b1, bott, cj, equiv ? 12 : 1, 1);
+                dp.aff2 = table(n2, bott, 0.f);                                        // relu2 = nn.ReLU, models.py:467 / :530
+                dp.c2 = dense_conv_pack(n, w2, b2, nf, bott, equiv ? 12 : k, k);
+            } else {
+                dp.w1 = w1; dp.b1 = b1; dp.w2 = w2; dp.b2 = b2;
+                dp.bn1 = add_bn(lp + "norm1", n1, cj);
+                dp.bn2 = add_bn(lp + "norm2", n2, bott);
+                dp.d1 = dense_dgrad_pack(n, w1, bott, cj, equiv ? 12 : 1, 1);
+                dp.d2 = dense_dgrad_pack(n, w2, nf, bott, equiv ? 12 : k, k);
+            }
         }
     };
     for (int i = 0; i < L; ++i) {
@@ -1636,110 +1721,48 @@ static void build_packs(ake_pcnet* n, bool train) {
         const LayerDims& d = n->dims[i];
         const int cs = i == 0 ? 1 : d.out_p;
         if (i >= 1) {   // creation order mirrors the forward order: up_sixth, p2p, pool_semi, pc2pc
-            if (!c.stay_sixth) {
-            std::vector<double> w, b;
-            fold(n, m + "up_sixth.weight", m + "up_sixth.bias", bn(m + "up_sixth_b", d.prev_pc), d.prev_pc,
-                 static_cast<size_t>(d.prev_pc) * 3, true, d.prev_pc, w, b);
-            PackedConv u;
-            u.cin = u.cout = d.prev_pc; u.kh = 3; u.kw = 1;
-            n->blob.resize(ake::align_up(n->blob.size(), 64));
-            u.w_off = n->blob.size();
-            for (double v : w) n->blob.push_back(static_cast<float>(v));   // stays [ci][co][3]
-            n->blob.resize(ake::align_up(n->blob.size(), 64));
-            u.b_off = n->blob.size();
-            for (double v : b) n->blob.push_back(static_cast<float>(v));
-            up[i] = u;
-            }
-            if (c.resblock) {   // [conv0, (conv1, conv2) per block]; the data-gradient packs in the same order
-                const int cin0 = c.pc2p_mem ? d.prev_p : d.prev_pc + d.prev_p;
-                p2p[i].push_back(fold_pack(n, m + "p2p.layer.0", bn(m + "p2p.layer.1", d.out_p), d.out_p, cin0, k, k));
-                if (train) n->p2p_d[i].push_back(dgrad_pack(n, m + "p2p.layer.0.weight", d.out_p, cin0, k, k));
-                for (int r = 0; r < c.conv_layers; ++r) {
-                    const std::string bp = m + "p2p.layer." + std::to_string(3 + r) + ".";
-                    p2p[i].push_back(fold_pack(n, bp + "conv1", bn(bp + "b1", 2 * d.out_p), 2 * d.out_p, d.out_p, k, k));
-                    p2p[i].push_back(fold_pack(n, bp + "conv2", bn(bp + "b2", d.out_p), d.out_p, 2 * d.out_p, k, k));
-                    if (train) {
-                        n->p2p_d[i].push_back(dgrad_pack(n, bp + "conv1.weight", 2 * d.out_p, d.out_p, k, k));
-                        n->p2p_d[i].push_back(dgrad_pack(n, bp + "conv2.weight", d.out_p, 2 * d.out_p, k, k));
-                    }
-                }
-            }
-            if (c.denseblock && !train) dense_block(m + "p2p.layer.0.", d.prev_pc + d.prev_p, false, n->dense_p[i]);
-            if (c.denseblock && train) dense_block_train(d.prev_pc + d.prev_p, false, n->dense_p[i]);
-            for (int j = 0; j < c.conv_layers && !c.resblock && !c.denseblock; ++j) {
-                const int cin_j = j == 0 ? (c.pc2p_mem ? d.prev_p : d.prev_pc + d.prev_p) : d.out_p;
-                p2p[i].push_back(fold_pack(n, m + "p2p.layer." + std::to_string(3 * j), bn(m + "p2p.layer." + std::to_string(3 * j + 1), d.out_p),
-                                           d.out_p, cin_j, k, k));
-                if (train) n->p2p_d[i].push_back(dgrad_pack(n, m + "p2p.layer." + std::to_string(3 * j) + ".weight", d.out_p, cin_j, k, k));
-            }
+            if (!c.stay_sixth)      // ConvTranspose2d: the weight is [cin][cout][3]
+                site(n->up[i], m + "up_sixth", m + "up_sixth_b", d.prev_pc, static_cast<size_t>(d.prev_pc) * 3, true, d.prev_pc, plain(d.prev_pc, 3));
+            if (c.denseblock) dense_block(m + "p2p.layer.0.", d.prev_pc + d.prev_p, false, n->dense_p[i]);
+            else stack(n->p2p[i], m + "p2p.layer.", "", c.pc2p_mem ? d.prev_p : d.prev_pc + d.prev_p, d.out_p, k);
         }
-        if (i == 0 || !c.stay_sixth) semi[i] = fold_pack(n, m + "pool_semi", bn(m + "pool_semi_b", cs), cs, cs, 3, 3);
-        if (c.p2pc_conv) {   // [co][ci][n_oct], BatchNorm folded (eval); plain layout as up_sixth's
-            std::vector<double> w, bb;
-            fold(n, m + "pool.conv.weight", m + "pool.conv.bias", bn(m + "pool.bn", cs), cs, static_cast<size_t>(cs) * (c.pitches / 36), false, cs, w, bb);
-            PackedConv u;
-            u.cin = u.cout = cs; u.kh = c.pitches / 36; u.kw = 1;
-            n->blob.resize(ake::align_up(n->blob.size(), 64));
-            u.w_off = n->blob.size();
-            for (double v : w) n->blob.push_back(static_cast<float>(v));
-            n->blob.resize(ake::align_up(n->blob.size(), 64));
-            u.b_off = n->blob.size();
-            for (double v : bb) n->blob.push_back(static_cast<float>(v));
-            (train ? n->foldc_t : n->foldc)[i] = u;
-        }
+        if (i == 0 || !c.stay_sixth) conv_site(n->semi[i], m + "pool_semi", m + "pool_semi_b", cs, cs, 3, 3);
+        if (c.p2pc_conv)
+            site(n->foldc[i], m + "pool.conv", m + "pool.bn", cs, static_cast<size_t>(cs) * (c.pitches / 36), false, cs, plain(cs, c.pitches / 36));
         const int pc_in = i == 0 ? 1 : d.out_p + d.prev_pc, pc_out = i == 0 ? c.n_filters : d.out_pc;
-        if (c.resblock) {
-            pc2pc[i].push_back(fold_pack(n, m + "pc2pc.layer.0.conv2d", bn(m + "pc2pc.layer.1", pc_out), pc_out, pc_in, 12, k));
-            if (train) n->pc2pc_d[i].push_back(dgrad_pack(n, m + "pc2pc.layer.0.conv2d.weight", pc_out, pc_in, 12, k));
-            for (int r = 0; r < c.conv_layers; ++r) {
-                const std::string bp = m + "pc2pc.layer." + std::to_string(3 + r) + ".";
-                pc2pc[i].push_back(fold_pack(n, bp + "conv1.conv2d", bn(bp + "b1", 2 * pc_out), 2 * pc_out, pc_out, 12, k));
-                pc2pc[i].push_back(fold_pack(n, bp + "conv2.conv2d", bn(bp + "b2", pc_out), pc_out, 2 * pc_out, 12, k));
-                if (train) {
-                    n->pc2pc_d[i].push_back(dgrad_pack(n, bp + "conv1.conv2d.weight", 2 * pc_out, pc_out, 12, k));
-                    n->pc2pc_d[i].push_back(dgrad_pack(n, bp + "conv2.conv2d.weight", pc_out, 2 * pc_out, 12, k));
-                }
-            }
-        }
-        if (c.denseblock && !train) dense_block(m + "pc2pc.layer.0.", pc_in, true, n->dense_pc[i]);
-        if (c.denseblock && train) dense_block_train(pc_in, true, n->dense_pc[i]);
-        for (int j = 0; j < c.conv_layers && !c.resblock && !c.denseblock; ++j) {
-            pc2pc[i].push_back(fold_pack(n, m + "pc2pc.layer." + std::to_string(3 * j) + ".conv2d",
-                                         bn(m + "pc2pc.layer." + std::to_string(3 * j + 1), pc_out), pc_out, j == 0 ? pc_in : pc_out, 12, k));
-            if (train) n->pc2pc_d[i].push_back(dgrad_pack(n, m + "pc2pc.layer." + std::to_string(3 * j) + ".conv2d.weight", pc_out,
-                                                          j == 0 ? pc_in : pc_out, 12, k));
-        }
+        if (c.denseblock) dense_block(m + "pc2pc.layer.0.", pc_in, true, n->dense_pc[i]);
+        else stack(n->pc2pc[i], m + "pc2pc.layer.", ".conv2d", pc_in, pc_out, 12);
     }
-    for (const char* head : {"tonic_classifier", "key_classifier", "genre_classifier"}) {
-        const bool g = std::strcmp(head, "genre_classifier") == 0;
+    for (int h : {1, 0, 2}) {       // tonic, key, genre: the order the reference creates them in (models.py:716-737)
+        Head& hd = n->heads[h];
+        const bool g = hd.kind == 2;
         if (g && !c.genre) continue;
-        const bool is_key = std::strcmp(head, "key_classifier") == 0;
-        auto& vec = train ? (g ? n->head_genre_t : (is_key ? n->head_key_t : n->head_tonic_t))
-                          : (g ? n->head_genre : (is_key ? n->head_key : n->head_tonic));
-        vec.clear();
+        hd.convs.resize(c.head_layers);
         int ch = n->final_ch;
         for (int i = 0; i < c.head_layers; ++i) {
-            const std::string base = std::string(head) + "." + std::to_string(3 * i) + (g ? "" : ".conv2d");
-            auto& dvec = g ? n->head_genre_d : (is_key ? n->head_key_d : n->head_tonic_d);
-            if (i == c.head_layers - 1) {
-                vec.push_back(fold_pack(n, base, "", 1, ch, g ? 2 : 12, k));
-                if (train) dvec.push_back(dgrad_pack(n, base + ".weight", 1, ch, g ? 2 : 12, k));
-            } else {
+            const std::string base = std::string(hd.nm) + "." + std::to_string(3 * i) + (hd.conv2d ? ".conv2d" : "");
+            if (i == c.head_layers - 1) conv_site(hd.convs[i], base, "", 1, ch, g ? 2 : 12, k);
+            else {
                 const int co = i == 0 ? 2 * ch : ch;
-                vec.push_back(fold_pack(n, base, bn(std::string(head) + "." + std::to_string(3 * i + 1), co), co, ch, g ? 1 : 12, k));
-                if (train) dvec.push_back(dgrad_pack(n, base + ".weight", co, ch, g ? 1 : 12, k));
+                conv_site(hd.convs[i], base, std::string(hd.nm) + "." + std::to_string(3 * i + 1), co, ch, g ? 1 : 12, k);
                 ch = co;
             }
+            dgrad_site(hd.convs[i]);
         }
     }
-    if (train) {   // raw copies of every tensor (small backward kernels read the reference layout) + the flat gradient layout
-        n->raw_w_off.assign(n->specs.size(), 0);
-        for (size_t i = 0; i < n->specs.size(); ++i) {
-            n->blob.resize(ake::align_up(n->blob.size(), 64));
-            n->raw_w_off[i] = n->blob.size();
-            for (float v : n->host[i].data) n->blob.push_back(v);
-        }
+    if (!missing.empty()) {
+        ake::set_error("finalize: the net reads tensor '%s', which this configuration's state_dict does not have", missing.c_str());
+        return AKE_ERR_STATE;
     }
+    if (!train) return AKE_OK;
+    // raw copies of every tensor (small backward kernels read the reference layout)
+    n->raw_w_off.assign(n->specs.size(), 0);
+    for (size_t i = 0; i < n->specs.size(); ++i) {
+        n->blob.resize(ake::align_up(n->blob.size(), 64));
+        n->raw_w_off[i] = n->blob.size();
+        for (float v : n->host[i].data) n->blob.push_back(v);
+    }
+    return check_sites(n);
 }
 
 constexpr int32_t kMapFolded = 1 << 30, kMapIndex = kMapFolded - 1;
@@ -1784,7 +1807,7 @@ __global__ void running_stats_kernel(const float* __restrict__ bstats, const int
 
 void reset_packs(ake_pcnet* n) {
     n->blob.clear();
-    n->bns.clear(); n->bn_index.clear(); n->bn_channels = 0;
+    n->bns.clear(); n->bn_channels = 0;
     n->aff_recs.clear(); n->dense_aff_floats = 0;
 }
 
@@ -1813,12 +1836,14 @@ int trace_maps(ake_pcnet* n) {
     reset_packs(n);
     n->fold_records.clear();
     n->tracing = true;
-    build_packs(n, false);
+    int rc = build_packs(n, false);
     n->tracing = false;
     const size_t eval_end = n->blob.size();
     // pass B: training packs (raw values everywhere)
     for (size_t i = 0; i < n->specs.size(); ++i) fill_index(i);
-    build_packs(n, true);
+    if (!rc) rc = build_packs(n, true);
+    for (size_t i = 0; i < n->specs.size(); ++i) n->host[i].data = saved[i];
+    if (rc) return rc;
     n->blob.resize(ake::align_up(n->blob.size() + 64, 64), 0.f);
     n->map_host.assign(n->blob.size(), -1);
     for (size_t j = 0; j < n->blob.size(); ++j) {
@@ -1827,7 +1852,6 @@ int trace_maps(ake_pcnet* n) {
         AKE_REQUIRE(static_cast<size_t>(v) <= n->grad_floats, AKE_ERR_STATE, "finalize: index trace out of range at blob[%zu]", j);
         n->map_host[j] = static_cast<int32_t>(v - 1) | (j < eval_end ? kMapFolded : 0);
     }
-    for (size_t i = 0; i < n->specs.size(); ++i) n->host[i].data = saved[i];
     return AKE_OK;
 }
 
@@ -1845,12 +1869,11 @@ int rebuild_dense_affine(ake_pcnet* n, const float* params_dev, hipStream_t s) {
     if (!n->dense_aff_dev) {
         std::vector<int32_t> idx;
         idx.reserve(static_cast<size_t>(rows) * 5);
-        auto off = [&](const std::string& key) { return static_cast<int32_t>(n->grad_off[n->spec_index.at(key)]); };
         for (const auto& r : n->aff_recs)
             for (int ch = 0; ch < r.C; ++ch) {
                 int32_t bits;
                 std::memcpy(&bits, &r.slope, sizeof(bits));
-                for (const char* f : {".weight", ".bias", ".running_mean", ".running_var"}) idx.push_back(off(r.bn + f) + ch);
+                for (int spec : {r.bn.weight, r.bn.bias, r.bn.mean, r.bn.var}) idx.push_back(static_cast<int32_t>(n->grad_off[spec]) + ch);
                 idx.push_back(bits);
             }
         int rc = upload_i32(idx, &n->dense_aff_idx_dev);
@@ -1863,10 +1886,10 @@ int rebuild_dense_affine(ake_pcnet* n, const float* params_dev, hipStream_t s) {
 int build_fold_tables(ake_pcnet* n) {
     std::vector<int32_t> fold_ch(n->grad_floats, -1), fold_bn, run_off(static_cast<size_t>(n->bn_channels) * 2, 0), run_off2(static_cast<size_t>(n->bn_channels) * 2, -1);
     n->recomputed_bn_channels = 0;
-    auto off = [&](const std::string& key) { return static_cast<int32_t>(n->grad_off[n->spec_index.at(key)]); };
+    auto off = [&](int spec) { return static_cast<int32_t>(n->grad_off[spec]); };
     int base = 0;
     for (const auto& r : n->fold_records) {
-        const int32_t w0 = off(r.wkey), b0 = off(r.bkey);
+        const int32_t w0 = off(r.w), b0 = off(r.b);
         const size_t total = r.per_out * r.cout, k = r.transposed ? r.per_out / r.cin : 0;
         for (size_t i = 0; i < total; ++i) {
             const int co = r.transposed ? static_cast<int>((i / k) % r.cout) : static_cast<int>(i / r.per_out);
@@ -1874,17 +1897,14 @@ int build_fold_tables(ake_pcnet* n) {
         }
         for (int co = 0; co < r.cout; ++co) {
             fold_ch[b0 + co] = ((base + co) << 1) | 1;
-            fold_bn.push_back(off(r.bn + ".weight") + co);
-            fold_bn.push_back(off(r.bn + ".bias") + co);
-            fold_bn.push_back(off(r.bn + ".running_mean") + co);
-            fold_bn.push_back(off(r.bn + ".running_var") + co);
+            for (int spec : {r.bn.weight, r.bn.bias, r.bn.mean, r.bn.var}) fold_bn.push_back(off(spec) + co);
         }
         base += r.cout;
     }
     for (const auto& l : n->bns)
         for (int c = 0; c < l.C; ++c) {
-            run_off[2 * (l.ch_off + c)] = off(l.name + ".running_mean") + c;
-            run_off[2 * (l.ch_off + c) + 1] = off(l.name + ".running_var") + c;
+            run_off[2 * (l.ch_off + c)] = off(l.p.mean) + c;
+            run_off[2 * (l.ch_off + c) + 1] = off(l.p.var) + c;
             // --denseblock: the reference checkpoints norm1 + conv1 of every dense layer (models.py:484-489, 553): autograd's backward runs that
             // half again, in train mode -- its BatchNorm blends the batch statistics into the running ones a second time
             const bool again = n->cfg.denseblock && l.name.size() > 6 && l.name.compare(l.name.size() - 6, 6, ".norm1") == 0;
@@ -1910,8 +1930,8 @@ bool pc_bf16_eligible(const PackedConv& pc) { return (pc.kh == 12 || pc.kh == 1)
 int rebuild_bf16_frags(ake_pcnet* n, hipStream_t s, bool train_only = false) {
     size_t count = 0;
     for (auto& layer : n->p2p)
-        for (size_t j = 0; j < layer.size(); ++j) {
-            PackedConv& pc = layer[j];
+        for (ConvSite& cs : layer) {
+            PackedConv& pc = cs.eval;
             pc.bf_off = -1;
             if (pc.cin <= 8 && pc.cout == 8 && pc.kh == 7 && pc.kw == 7 && pc.co == 8) { pc.bf_off = static_cast<long long>(count); count += kBfFragsPerConv; }
         }
@@ -1919,14 +1939,13 @@ int rebuild_bf16_frags(ake_pcnet* n, hipStream_t s, bool train_only = false) {
     struct TrainFrag { PackedConv* pc; size_t raw; int cin, cout, flip; };
     std::vector<TrainFrag> tfr;
     if (!n->raw_w_off.empty())
-        for (size_t i = 1; i < n->p2p_t.size() && i < n->p2p_d.size(); ++i)
-            for (size_t j = 0; j < n->p2p_t[i].size() && j < n->p2p_d[i].size(); ++j) {
-                PackedConv& pt = n->p2p_t[i][j];
-                PackedConv& pd = n->p2p_d[i][j];
+        for (size_t i = 1; i < n->p2p.size(); ++i)
+            for (ConvSite& cs : n->p2p[i]) {
+                PackedConv& pt = cs.train;
+                PackedConv& pd = cs.dgrad;
                 pt.bf_off = pd.bf_off = -1;
-                const auto it = n->spec_index.find("model." + std::to_string(i) + ".p2p.layer." + std::to_string(3 * j) + ".weight");
-                if (it == n->spec_index.end() || pt.kh != 7 || pt.kw != 7 || pt.cin > 8 || pt.cout > 8 || n->cfg.resblock || n->cfg.denseblock) continue;
-                const size_t raw = n->raw_w_off[it->second];
+                if (pt.kh != 7 || pt.kw != 7 || pt.cin > 8 || pt.cout > 8 || n->cfg.resblock || n->cfg.denseblock) continue;
+                const size_t raw = n->raw_w_off[cs.w];
                 pt.bf_off = static_cast<long long>(count); count += kBfFragsPerConv;
                 tfr.push_back({&pt, raw, pt.cin, pt.cout, 0});
                 pd.bf_off = static_cast<long long>(count); count += kBfFragsPerConv;
@@ -1936,11 +1955,10 @@ int rebuild_bf16_frags(ake_pcnet* n, hipStream_t s, bool train_only = false) {
     // from the training packs (raw weights in the VALU layout)
     std::vector<PackedConv*> tpc;
     if (!n->raw_w_off.empty() && !n->cfg.resblock && !n->cfg.denseblock) {
-        for (size_t i = 1; i < n->pc2pc_t.size(); ++i)
-            for (PackedConv& pc : n->pc2pc_t[i]) tpc.push_back(&pc);
-        if (!n->head_key_t.empty()) tpc.push_back(&n->head_key_t[0]);
-        if (!n->head_tonic_t.empty()) tpc.push_back(&n->head_tonic_t[0]);
-        if (n->head_genre_t.size() == 2) tpc.push_back(&n->head_genre_t[0]);
+        for (size_t i = 1; i < n->pc2pc.size(); ++i)
+            for (ConvSite& cs : n->pc2pc[i]) tpc.push_back(&cs.train);
+        for (Head& h : n->heads)
+            if (h.kind == 2 ? h.convs.size() == 2 : !h.convs.empty()) tpc.push_back(&h.convs[0].train);
     }
     for (PackedConv* pc : tpc) {
         pc->bf_off = -1;
@@ -1950,8 +1968,8 @@ int rebuild_bf16_frags(ake_pcnet* n, hipStream_t s, bool train_only = false) {
     // f16 x 3 kernel; the transposed + flipped weights are the data-gradient packs
     std::vector<PackedConv*> tpd;
     if (!n->raw_w_off.empty() && !n->cfg.resblock && !n->cfg.denseblock)
-        for (size_t i = 1; i < n->pc2pc_d.size(); ++i)
-            for (PackedConv& pc : n->pc2pc_d[i]) tpd.push_back(&pc);
+        for (size_t i = 1; i < n->pc2pc.size(); ++i)
+            for (ConvSite& cs : n->pc2pc[i]) tpd.push_back(&cs.dgrad);
     for (PackedConv* pc : tpd) {
         pc->bf_off = -1;
         if (pc->kh == 12 && pc->kw == 7 && pc->cin == 16 && pc->cout <= 32) {
@@ -1961,11 +1979,9 @@ int rebuild_bf16_frags(ake_pcnet* n, hipStream_t s, bool train_only = false) {
     }
     // ... and of the heads' first convolutions (32 gradient channels -> 16 features: two 16-channel halves, bf_off / bf_off2)
     std::vector<PackedConv*> thd;
-    if (!n->raw_w_off.empty() && !n->cfg.resblock && !n->cfg.denseblock && n->cfg.head_layers == 2) {
-        if (!n->head_key_d.empty()) thd.push_back(&n->head_key_d[0]);
-        if (!n->head_tonic_d.empty()) thd.push_back(&n->head_tonic_d[0]);
-        if (!n->head_genre_d.empty()) thd.push_back(&n->head_genre_d[0]);
-    }
+    if (!n->raw_w_off.empty() && !n->cfg.resblock && !n->cfg.denseblock && n->cfg.head_layers == 2)
+        for (Head& h : n->heads)
+            if (!h.convs.empty()) thd.push_back(&h.convs[0].dgrad);
     for (PackedConv* pc : thd) {
         pc->bf_off = pc->bf_off2 = -1;
         if ((pc->kh == 12 || pc->kh == 1) && pc->kw == 7 && pc->cin == 32 && pc->cout == 16) {
@@ -1976,33 +1992,32 @@ int rebuild_bf16_frags(ake_pcnet* n, hipStream_t s, bool train_only = false) {
     }
     std::vector<PackedConv*> pcs;                             // pitch-class convolutions: the PitchClass2PitchClass stacks and the heads' first conv
     for (auto& layer : n->pc2pc)
-        for (PackedConv& pc : layer) pcs.push_back(&pc);
-    if (!n->head_key.empty()) pcs.push_back(&n->head_key[0]);
-    if (!n->head_tonic.empty()) pcs.push_back(&n->head_tonic[0]);
-    if (n->head_genre.size() == 2) pcs.push_back(&n->head_genre[0]);            // 1 x 7: rows independent
+        for (ConvSite& cs : layer) pcs.push_back(&cs.eval);
+    for (Head& h : n->heads)                                  // (the genre head's is 1 x 7: rows independent)
+        if (h.kind == 2 ? h.convs.size() == 2 : !h.convs.empty()) pcs.push_back(&h.convs[0].eval);
     for (PackedConv* pc : pcs) {
         pc->bf_off = -1;
         if (pc_bf16_eligible(*pc)) { pc->bf_off = static_cast<long long>(count); count += static_cast<size_t>(pc->kh) * 4 * (pc->cout / 16) * 2 * 64; }
     }
     std::vector<PackedConv*> h1;                              // 32 -> 1 last convolutions of the key / tonic heads (2-conv heads only)
-    if (n->head_key.size() == 2) h1.push_back(&n->head_key[1]);
-    if (n->head_tonic.size() == 2) h1.push_back(&n->head_tonic[1]);
-    if (n->head_genre.size() == 2) h1.push_back(&n->head_genre[1]);              // 2 x 7 over valid rows
+    for (Head& h : n->heads)                                  // (the genre head's is 2 x 7 over valid rows)
+        if (h.convs.size() == 2) h1.push_back(&h.convs[1].eval);
     for (PackedConv* pc : h1) {
         pc->bf_off = -1;
         if ((pc->kh == 12 || pc->kh == 2) && pc->kw == 7 && pc->cout == 1 && pc->co == 1 && pc->cin == 32) { pc->bf_off = static_cast<long long>(count); count += static_cast<size_t>(head1_ksteps(pc->kh)) * 2 * 64; }
     }
     if (!n->pc2pc.empty())                                   // layer 0's pitch-class stack (<= 4 channels): layer0_mfma_kernel
-        for (PackedConv& pc : n->pc2pc[0]) {
+        for (ConvSite& cs : n->pc2pc[0]) {
+            PackedConv& pc = cs.eval;
             pc.l0_off = -1;
             if (n->cfg.num_layers > 1 && pc.kh == 12 && pc.kw == 7 && pc.co == 4 && pc.groups == 1 && pc.cout <= 4 && pc.cin <= 4) {
                 pc.l0_off = static_cast<long long>(count); count += 24 * 64 + 64;     // ... and the 4 inverse channel scales
             }
         }
     for (size_t i = 1; i < n->semi.size(); ++i) {            // semitone convs that follow an 8-channel pitch stack: fused into its last conv
-        PackedConv& pc = n->semi[i];
+        PackedConv& pc = n->semi[i].eval;
         pc.bf_off = -1;
-        if (pc.cin == 8 && pc.co == 8 && pc.groups == 1 && i < n->p2p.size() && !n->p2p[i].empty() && n->p2p[i].back().bf_off >= 0) {
+        if (pc.cin == 8 && pc.co == 8 && pc.groups == 1 && i < n->p2p.size() && !n->p2p[i].empty() && n->p2p[i].back().eval.bf_off >= 0) {
             pc.bf_off = static_cast<long long>(count); count += 6 * 64 + 64;      // ... and the 8 inverse channel scales
         }
     }
@@ -2019,9 +2034,9 @@ int rebuild_bf16_frags(ake_pcnet* n, hipStream_t s, bool train_only = false) {
     n->eval_frags_stale = train_only;
     if (!train_only)
     for (const auto& layer : n->p2p)
-        for (const PackedConv& pc : layer)
-            if (pc.bf_off >= 0 && (rc = ake::launch_untimed("pack_p2p_f16_kernel", pack_p2p_f16_kernel, dim3((14 * 64 + 255) / 256), dim3(256), 0, s,
-                                                            n->blob_dev + pc.w_off, n->bf_frags_dev + pc.bf_off, pc.cin)))
+        for (const ConvSite& cs : layer)
+            if (cs.eval.bf_off >= 0 && (rc = ake::launch_untimed("pack_p2p_f16_kernel", pack_p2p_f16_kernel, dim3((14 * 64 + 255) / 256), dim3(256), 0, s,
+                                                                 n->blob_dev + cs.eval.w_off, n->bf_frags_dev + cs.eval.bf_off, cs.eval.cin)))
                 return rc;
     if (!train_only)
     for (const PackedConv* pc : pcs)
@@ -2032,9 +2047,9 @@ int rebuild_bf16_frags(ake_pcnet* n, hipStream_t s, bool train_only = false) {
                 return rc;
         }
     if (!train_only && !n->pc2pc.empty())
-        for (const PackedConv& pc : n->pc2pc[0])
-            if (pc.l0_off >= 0 && (rc = ake::launch_untimed("pack_l0_f16_kernel", pack_l0_f16_kernel, dim3(3), dim3(256), 0, s, n->blob_dev + pc.w_off,
-                                                            n->bf_frags_dev + pc.l0_off, pc.cin, pc.cout)))
+        for (const ConvSite& cs : n->pc2pc[0])
+            if (cs.eval.l0_off >= 0 && (rc = ake::launch_untimed("pack_l0_f16_kernel", pack_l0_f16_kernel, dim3(3), dim3(256), 0, s, n->blob_dev + cs.eval.w_off,
+                                                                 n->bf_frags_dev + cs.eval.l0_off, cs.eval.cin, cs.eval.cout)))
                 return rc;
     {   // the training-mode packs (pitch-class stacks, their data gradients, the heads' data gradients; the pitch convs' raw forms): ONE launch per
         // kernel for all of them, the jobs in the kernel argument (28 dependent launches of a few microseconds of work each were 0.39 ms per step)
@@ -2073,8 +2088,8 @@ int rebuild_bf16_frags(ake_pcnet* n, hipStream_t s, bool train_only = false) {
         }
     }
     for (size_t i = 1; !train_only && i < n->semi.size(); ++i)
-        if (n->semi[i].bf_off >= 0 && (rc = ake::launch_untimed("pack_semi_f16_kernel", pack_semi_f16_kernel, dim3(1), dim3(192), 0, s,
-                                                                n->blob_dev + n->semi[i].w_off, n->bf_frags_dev + n->semi[i].bf_off)))
+        if (n->semi[i].eval.bf_off >= 0 && (rc = ake::launch_untimed("pack_semi_f16_kernel", pack_semi_f16_kernel, dim3(1), dim3(192), 0, s,
+                                                                     n->blob_dev + n->semi[i].eval.w_off, n->bf_frags_dev + n->semi[i].eval.bf_off)))
             return rc;
     if (!train_only)
     for (const PackedConv* pc : h1)
@@ -2096,8 +2111,7 @@ int ake_pcnet_finalize(ake_pcnet* n) {
         if ((rc = build_fold_tables(n))) return rc;
     }
     reset_packs(n);
-    build_packs(n, false);
-    build_packs(n, true);
+    if ((rc = build_packs(n, false)) || (rc = build_packs(n, true))) return rc;
     n->blob.resize(ake::align_up(n->blob.size() + 64, 64), 0.f);
     AKE_REQUIRE(n->blob.size() == n->map_host.size(), AKE_ERR_STATE, "finalize: blob layout changed between builds");
     if (!n->blob_dev) AKE_HIP_CHECK(hipMalloc(&n->blob_dev, n->blob.size() * sizeof(float)));
@@ -2215,7 +2229,6 @@ struct Fwd {
     bool train;
     const Route& r;                  // what this call launches (build_route)
 
-    int bn_of(const std::string& name) const { return n->bn_index.at(name); }
     // training: the rows of layer i's pitch-stack input table that belong to the up_sixth map (they follow the pitch stream's prev_p rows)
     float* p2pin_up(int i) const { return train ? b.aff_p2pin[i] + 3 * n->dims[i].prev_p : nullptr; }
 
@@ -2230,16 +2243,18 @@ struct Fwd {
         return ake::launch_untimed("affine_identity_kernel", affine_identity_kernel, dim3((C + 63) / 64), dim3(64), 0, s, aff, C);
     }
 
-    // conv (+BatchNorm `bn_name` + LeakyReLU unless bn_name is empty).  Returns via *aff_out_used whether dst is raw.
-    int conv(const PackedConv& pe, const PackedConv& pt, const std::string& bn_name, int kind, Src src, const float* in_aff,
-             int B, int H, int T_in, bool same, float* dst, int ctot, int coff, float* aff_dst, const char* name, const float* residual = nullptr) {
+    // the convolution of site `cs` (+ its BatchNorm + LeakyReLU where it has one).  Inference: the folded pack, dst is final.  Training: the
+    // raw pack, dst is raw and the BatchNorm's table lands in aff_dst.
+    int conv(const ConvSite& cs, int kind, Src src, const float* in_aff, int B, int H, int T_in, bool same, float* dst, int ctot, int coff,
+             float* aff_dst, const char* name, const float* residual = nullptr) {
         ConvOpts o;
+        const int bn = cs.bn;
+        const bool has_bn = bn >= 0;
         if (!train) {
             o.residual = residual;
-            return run_conv(n, pe, kind, src, B, H, T_in, same, !bn_name.empty(), dst, ctot, coff, s, name, o);
+            return run_conv(n, cs.eval, kind, src, B, H, T_in, same, has_bn, dst, ctot, coff, s, name, o);
         }
-        const bool has_bn = !bn_name.empty();
-        const int bn = has_bn ? bn_of(bn_name) : -1;
+        const PackedConv& pt = cs.train;
         o.in_affine = in_aff;
         if (has_bn) o.stats = b.stats + 2 * n->bns[bn].ch_off;
         int rc = run_conv(n, pt, kind, src, B, H, T_in, same, false, dst, ctot, coff, s, name, o);
@@ -2305,47 +2320,45 @@ struct Fwd {
     // --resblock stack (models.py:181-187 / 218-224, 402-454), inference: st = [conv0, (conv1, conv2) per block].  x lives in X
     // (C channels, dense), a block's hidden map (2C channels) in Hb; conv2 adds x before its LeakyReLU, in place -- the last block
     // may write channels [0, C) of a wider buffer instead (final_dst with final_ctot channels).
-    int res_stack(const std::vector<PackedConv>& st, int kind, Src first, int B, int H, int T, float* X, float* Hb, float* final_dst,
+    int res_stack(const std::vector<ConvSite>& st, int kind, Src first, int B, int H, int T, float* X, float* Hb, float* final_dst,
                   int final_ctot, const char* label) {
-        const int C = st[0].cout;
-        int rc = conv(st[0], st[0], "bn", kind, first, nullptr, B, H, T, true, X, C, 0, nullptr, label);
+        const int C = st[0].eval.cout;
+        int rc = conv(st[0], kind, first, nullptr, B, H, T, true, X, C, 0, nullptr, label);
         if (rc) return rc;
         const int nb = (static_cast<int>(st.size()) - 1) / 2;
         for (int r = 0; r < nb; ++r) {
-            if ((rc = conv(st[1 + 2 * r], st[1 + 2 * r], "bn", kind, Src{X, C, nullptr, 0, 0}, nullptr, B, H, T, true, Hb, 2 * C, 0, nullptr, label))) return rc;
+            if ((rc = conv(st[1 + 2 * r], kind, Src{X, C, nullptr, 0, 0}, nullptr, B, H, T, true, Hb, 2 * C, 0, nullptr, label))) return rc;
             const bool to_final = r == nb - 1 && final_dst;
-            if ((rc = conv(st[2 + 2 * r], st[2 + 2 * r], "bn", kind, Src{Hb, 2 * C, nullptr, 0, 0}, nullptr, B, H, T, true, to_final ? final_dst : X,
+            if ((rc = conv(st[2 + 2 * r], kind, Src{Hb, 2 * C, nullptr, 0, 0}, nullptr, B, H, T, true, to_final ? final_dst : X,
                            to_final ? final_ctot : C, 0, nullptr, label, X)))
                 return rc;
         }
         return AKE_OK;
     }
 
-    // --resblock stack, training (batch statistics): st = the raw-weight packs [conv0, (conv1, conv2) per block], BatchNorms
-    // `prefix`1 and `prefix`{3+r}.b1 / .b2.  Every tensor the backward needs stays: z = [conv0 raw, (conv1 raw (2C), conv2 raw,
+    // --resblock stack, training (batch statistics): st = the sites [conv0, (conv1, conv2) per block].  Every tensor the backward needs stays: z = [conv0 raw, (conv1 raw (2C), conv2 raw,
     // block output) per block] with the pending tables in aff (b2's carries slope 1: no activation of its own; a block output's is
     // the identity).  The last block writes channels [0, C) of final_dst (final_ctot channels) instead of z.back() when given.
-    int res_stack_train(const std::vector<PackedConv>& st, const std::string& prefix, int kind, Src first, const float* first_aff, int B, int H, int T,
+    int res_stack_train(const std::vector<ConvSite>& st, int kind, Src first, const float* first_aff, int B, int H, int T,
                         const std::vector<float*>& z, const std::vector<float*>& aff, float* final_dst, int final_ctot, const char* label) {
-        const int C = st[0].cout;
+        const int C = st[0].train.cout;
         const int nb = (static_cast<int>(st.size()) - 1) / 2;
         AKE_REQUIRE(static_cast<int>(z.size()) == 1 + 3 * nb && z.size() == aff.size(), AKE_ERR_STATE, "resblock %s: buffer bookkeeping", label);
-        int rc = conv(st[0], st[0], prefix + "1", kind, first, first_aff, B, H, T, true, z[0], C, 0, aff[0], label);
+        int rc = conv(st[0], kind, first, first_aff, B, H, T, true, z[0], C, 0, aff[0], label);
         if (rc) return rc;
         const float* x = z[0];
         const float* x_aff = aff[0];
         const double count = static_cast<double>(B) * H * T;
         for (int r = 0; r < nb; ++r) {
-            const std::string bp = prefix + std::to_string(3 + r) + ".";
             float* z1 = z[1 + 3 * r];
             float* z2 = z[2 + 3 * r];
-            if ((rc = conv(st[1 + 2 * r], st[1 + 2 * r], bp + "b1", kind, Src{x, C, nullptr, 0, 0}, x_aff, B, H, T, true, z1, 2 * C, 0, aff[1 + 3 * r], label)))
+            if ((rc = conv(st[1 + 2 * r], kind, Src{x, C, nullptr, 0, 0}, x_aff, B, H, T, true, z1, 2 * C, 0, aff[1 + 3 * r], label)))
                 return rc;
-            const int bn2 = bn_of(bp + "b2");
+            const int bn2 = st[2 + 2 * r].bn;
             ConvOpts o2;
             o2.in_affine = aff[1 + 3 * r];
             o2.stats = b.stats + 2 * n->bns[bn2].ch_off;
-            if ((rc = run_conv(n, st[2 + 2 * r], kind, Src{z1, 2 * C, nullptr, 0, 0}, B, H, T, true, false, z2, C, 0, s, label, o2))) return rc;
+            if ((rc = run_conv(n, st[2 + 2 * r].train, kind, Src{z1, 2 * C, nullptr, 0, 0}, B, H, T, true, false, z2, C, 0, s, label, o2))) return rc;
             if ((rc = finalize_bn(bn2, count, aff[2 + 3 * r], 1.f))) return rc;
             const bool to_final = r == nb - 1 && final_dst;
             float* xo = to_final ? final_dst : z[3 + 3 * r];
@@ -2376,19 +2389,19 @@ struct Fwd {
         const char* nm = layer == 0 ? "semi_fold_kernel/L0" : "semi_fold_kernel/L1+";
         int rc;
         if (!train && n->cfg.p2pc_conv) {   // semitone conv (raw, BatchNorm folded) -> octave-fold convolution (LeakyReLU applied on load)
-            const PackedConv& pc = n->semi[layer];
+            const PackedConv& pc = n->semi[layer].eval;
             SemiTrainArgs ta;
             std::memset(&ta, 0, sizeof(ta));
             ta.s = semi_args(n, pc, src, P, Tn, b.smap);
             if ((rc = launch_semi_conv(pc, ta, P, B))) return rc;
-            const PackedConv& fc = n->foldc[layer];
+            const PackedConv& fc = n->foldc[layer].eval;
             const long long total = static_cast<long long>(B) * pc.cin * 12 * Tn;
             return launch_flat("fold_conv_kernel", fold_conv_kernel, s, total, b.smap, n->blob_dev + fc.w_off, n->blob_dev + fc.b_off, dst, pc.cin, P / 36, Tn, 1,
                                static_cast<long long>(ctot) * 12 * Tn, coff, total);
         }
-        if (!train) return run_semi(n, n->semi[layer], src, B, P, Tn, dst, ctot, coff, s, nm);
-        const PackedConv& pc = n->semi_t[layer];
-        const int bn = bn_of("model." + std::to_string(layer) + ".pool_semi_b");
+        if (!train) return run_semi(n, n->semi[layer].eval, src, B, P, Tn, dst, ctot, coff, s, nm);
+        const PackedConv& pc = n->semi[layer].train;
+        const int bn = n->semi[layer].bn;
         SemiTrainArgs ta;
         std::memset(&ta, 0, sizeof(ta));
         ta.s = semi_args(n, pc, src, P, Tn, b.semi_raw[layer]);
@@ -2397,8 +2410,8 @@ struct Fwd {
         if ((rc = finalize_bn(bn, static_cast<double>(B) * (P / 3) * Tn, b.aff_semi[layer]))) return rc;
         const long long total = static_cast<long long>(B) * pc.cin * 12 * Tn;
         if (n->cfg.p2pc_conv) {   // models.py:108-133: the fold is a learned convolution over the octaves + BatchNorm (batch statistics) + LeakyReLU
-            const PackedConv& fc = n->foldc_t[layer];
-            const int bnf = bn_of("model." + std::to_string(layer) + ".pool.bn");
+            const PackedConv& fc = n->foldc[layer].train;
+            const int bnf = n->foldc[layer].bn;
             AKE_REQUIRE(pc.cin <= 64, AKE_ERR_UNSUPPORTED, "p2pc_conv training: %d channels", pc.cin);
             if ((rc = launch_flat("fold_conv_kernel", fold_conv_train_kernel, s, total, b.semi_raw[layer], b.aff_semi[layer], n->blob_dev + fc.w_off,
                                   n->blob_dev + fc.b_off, b.foldc_raw[layer], b.stats + 2 * n->bns[bnf].ch_off, 2 * n->bn_channels, pc.cin, P / 36, Tn, total)))
@@ -2415,12 +2428,12 @@ struct Fwd {
     int up_sixth(int layer, const float* src, long long src_clip_stride, const float* in_aff, int B, int C, int Tn, float* dst, float* aff_dst) {
         const long long total = static_cast<long long>(B) * C * 36 * Tn;
         if (!train)
-            return launch_flat("up_sixth_kernel", up_sixth_kernel<false>, s, total, src, src_clip_stride, nullptr, n->blob_dev + n->up[layer].w_off,
-                               n->blob_dev + n->up[layer].b_off, dst, nullptr, 0, C, Tn, total);
-        const int bn = bn_of("model." + std::to_string(layer) + ".up_sixth_b");
+            return launch_flat("up_sixth_kernel", up_sixth_kernel<false>, s, total, src, src_clip_stride, nullptr, n->blob_dev + n->up[layer].eval.w_off,
+                               n->blob_dev + n->up[layer].eval.b_off, dst, nullptr, 0, C, Tn, total);
+        const int bn = n->up[layer].bn;
         AKE_REQUIRE(C <= kBlockStatCh, AKE_ERR_UNSUPPORTED, "up_sixth training: %d channels", C);
-        const int rc = launch_flat("up_sixth_train_kernel", up_sixth_kernel<true>, s, total, src, src_clip_stride, in_aff, n->blob_dev + n->up_t[layer].w_off,
-                                   n->blob_dev + n->up_t[layer].b_off, dst, b.stats + 2 * n->bns[bn].ch_off, 2 * n->bn_channels, C, Tn, total);
+        const int rc = launch_flat("up_sixth_train_kernel", up_sixth_kernel<true>, s, total, src, src_clip_stride, in_aff, n->blob_dev + n->up[layer].train.w_off,
+                                   n->blob_dev + n->up[layer].train.b_off, dst, b.stats + 2 * n->bns[bn].ch_off, 2 * n->bn_channels, C, Tn, total);
         return rc ? rc : finalize_bn(bn, static_cast<double>(B) * 36 * Tn, aff_dst);
     }
 
@@ -2432,7 +2445,7 @@ struct Fwd {
 
     // inference: semitone conv + BN + LeakyReLU of `src` [B][C][P][T] as a map of its own [B][C][P / 3][T] (raw = before the LeakyReLU)
     int semi_map(int layer, const float* src, int B, int P, int Tn, float* dst, bool raw) {
-        const PackedConv& pc = n->semi[layer];
+        const PackedConv& pc = n->semi[layer].eval;
         SemiTrainArgs ta;
         std::memset(&ta, 0, sizeof(ta));
         ta.s = semi_args(n, pc, src, P, Tn, dst);
@@ -2443,7 +2456,7 @@ struct Fwd {
     // the octave fold of ready maps [B][C][S][T] into channels [coff, coff + C) of dst: max (models.py:95-106) or --p2pc_conv's convolution
     int fold_maps(int layer, const float* maps, int C, int S, int B, int Tn, float* dst, int ctot, int coff) {
         if (!n->cfg.p2pc_conv) return run_fold_max("fold_max_kernel", maps, nullptr, C, S, B, Tn, dst, ctot, coff, s);
-        const PackedConv& fc = n->foldc[layer];
+        const PackedConv& fc = n->foldc[layer].eval;
         const long long total = static_cast<long long>(B) * C * 12 * Tn;
         return launch_flat("fold_conv_kernel", fold_conv_kernel, s, total, maps, n->blob_dev + fc.w_off, n->blob_dev + fc.b_off, dst, C, S / 12, Tn, 0,
                            static_cast<long long>(ctot) * 12 * Tn, coff, total);
@@ -2458,7 +2471,7 @@ struct Fwd {
                     "pcnet: the route sent layer 0 to its one-launch form, which this call does not qualify for");
         AKE_REQUIRE(!r.frames_major || take_mfma, AKE_ERR_STATE, "pcnet: the route promised the frames-major input to a layer-0 form that cannot read it");
         AKE_REQUIRE(!r.psix_f16 || (take_mfma && b.melh), AKE_ERR_STATE, "pcnet: the route promised the f16 up_sixth map to a layer-0 form that does not write it");
-        const PackedConv& sp = n->semi[0];
+        const PackedConv& sp = n->semi[0].eval;
         const LayerDims& d1 = n->dims[1];
         Layer0Args a;
         std::memset(&a, 0, sizeof(a));
@@ -2466,14 +2479,14 @@ struct Fwd {
         a.mel = mel; a.sw = n->blob_dev + sp.w_off; a.sb = n->blob_dev + sp.b_off;
         const int ctot1 = d1.prev_pc + d1.out_p;
         for (int j = 0; j < c.conv_layers; ++j) {
-            const PackedConv& pc = n->pc2pc[0][j];
+            const PackedConv& pc = n->pc2pc[0][j].eval;
             const bool lastj = j == c.conv_layers - 1;
             a.w[j] = n->blob_dev + pc.w_off; a.b[j] = n->blob_dev + pc.b_off;
             if (take_mfma) a.frag[j] = n->bf_frags_dev + pc.l0_off;
             a.dst[j] = lastj ? b.cat[1] : b.pc_out(false, 0, j).p;
             a.dst_clip_stride[j] = static_cast<long long>(lastj ? ctot1 : NF) * 12 * T0;
         }
-        a.uw = n->blob_dev + n->up[1].w_off; a.ub = n->blob_dev + n->up[1].b_off;
+        a.uw = n->blob_dev + n->up[1].eval.w_off; a.ub = n->blob_dev + n->up[1].eval.b_off;
         a.fold0 = b.fold0; a.psix = b.psix[1];
         a.H = P; a.T = T0; a.NF = NF; a.n_conv = c.conv_layers;
         static ake::DeviceOnce fused_attr, mfma_attr;
@@ -2518,9 +2531,8 @@ struct Fwd {
         const int ctot1 = d1.prev_pc + d1.out_p;
         Slot src{b.fold0, nullptr};
         int cin = 1;
-        const std::string m = "model.0.pc2pc.layer.";
         if (c.resblock && train) {   // the last block's output = channels [0, nf) of layer 1's concat buffer, final (identity table)
-            if ((rc = res_stack_train(n->pc2pc_t[0], m, 1, Src{b.fold0, 1, nullptr, 0, 0}, nullptr, B, 12, T0, b.pcst[0], b.aff_pcst[0], b.cat[1], ctot1,
+            if ((rc = res_stack_train(n->pc2pc[0], 1, Src{b.fold0, 1, nullptr, 0, 0}, nullptr, B, 12, T0, b.pcst[0], b.aff_pcst[0], b.cat[1], ctot1,
                                       "conv_mfma_kernel/pc2pc0")))
                 return rc;
             if ((rc = identity(b.aff_cat[1], c.n_filters))) return rc;
@@ -2530,8 +2542,7 @@ struct Fwd {
         for (int j = 0; j < c.conv_layers && !c.resblock; ++j) {
             const bool lastj = j == c.conv_layers - 1;           // the last conv writes channels [0, nf) of layer 1's concat buffer
             const Slot dst = lastj ? b.cat_slot(train, 1) : b.pc_out(train, 0, j);
-            if ((rc = conv(n->pc2pc[0][j], train ? n->pc2pc_t[0][j] : n->pc2pc[0][j], m + std::to_string(3 * j + 1), 1,
-                           Src{src.p, cin, nullptr, 0, 0}, src.aff, B, 12, T0, true, dst.p, lastj ? ctot1 : c.n_filters, 0, dst.aff,
+            if ((rc = conv(n->pc2pc[0][j], 1, Src{src.p, cin, nullptr, 0, 0}, src.aff, B, 12, T0, true, dst.p, lastj ? ctot1 : c.n_filters, 0, dst.aff,
                            "conv_mfma_kernel/pc2pc0")))
                 return rc;
             src = dst; cin = c.n_filters;
@@ -2581,7 +2592,6 @@ struct Fwd {
                 continue;
             }
             const int ctot = d.prev_pc + d.out_p;
-            const std::string m = "model." + std::to_string(i) + ".";
             float* cat = b.cat[i] + (last || i == 1 ? static_cast<size_t>(c0) * ctot * 12 * Ti : 0);
             float* psix = b.psix[i] + (i == 1 ? static_cast<size_t>(c0) * d.prev_pc * 36 * Ti : 0);
             if (i > 1 && !c.stay_sixth) {   // layer 1's up_sixth ran batch-wide in entry(); pc_cur = pooled (final) features here
@@ -2617,7 +2627,7 @@ struct Fwd {
             const Route::Pitch::PerChunk& rk = rp.k[r.chunk_kind(B)];
             P2pOut last_out = P2pOut::Nchw;       // what the stack's last launch left: the pitch tensor, the semitone maps, or the folded maps in `cat`
             if (c.resblock && train) {
-                if ((rc = res_stack_train(n->p2p_t[i], m + "p2p.layer.", 0, sdesc, in_aff, B, P, Ti, b.pst[i], b.aff_pst[i], nullptr, 0, "conv_mfma_kernel/p2p")))
+                if ((rc = res_stack_train(n->p2p[i], 0, sdesc, in_aff, B, P, Ti, b.pst[i], b.aff_pst[i], nullptr, 0, "conv_mfma_kernel/p2p")))
                     return rc;
                 out = b.p_last(i);
             } else if (c.resblock) {
@@ -2628,7 +2638,7 @@ struct Fwd {
             if (one_launch) {      // the whole stack, semitone conv and fold as one launch
                 unsigned short* planes[kP2pStackMax];
                 for (int j = 0; j < kP2pStackMax; ++j) planes[j] = reinterpret_cast<unsigned short*>(b.p_out(false, i, j).p);
-                if ((rc = run_p2p_stack(n, n->p2p[i], n->semi[i], rk.stack, b.melh + static_cast<size_t>(c0) * P * Ti,
+                if ((rc = run_p2p_stack(n, n->p2p[i], n->semi[i].eval, rk.stack, b.melh + static_cast<size_t>(c0) * P * Ti,
                                         reinterpret_cast<const uint2*>(b.psix[1]) + static_cast<size_t>(c0) * 36 * Ti, d.prev_pc, planes, cat, ctot, d.prev_pc, B, P, Ti, s,
                                         "conv_p2p_f16_kernel")))
                     return rc;
@@ -2651,28 +2661,27 @@ struct Fwd {
                     switch (g.out) {
                         case P2pOut::Plane: io.plane = reinterpret_cast<unsigned short*>(out.p); break;
                         case P2pOut::Nchw: io.dst = out.p; break;
-                        case P2pOut::Semi: io.dst = out.p; io.semi = &n->semi[i]; break;       // `out` receives the semitone maps [clip][8][P / 3][T]
-                        case P2pOut::SemiFold: io.dst = cat; io.dst_ctot = ctot; io.fold_coff = d.prev_pc; io.semi = &n->semi[i]; break;
+                        case P2pOut::Semi: io.dst = out.p; io.semi = &n->semi[i].eval; break;       // `out` receives the semitone maps [clip][8][P / 3][T]
+                        case P2pOut::SemiFold: io.dst = cat; io.dst_ctot = ctot; io.fold_coff = d.prev_pc; io.semi = &n->semi[i].eval; break;
                     }
                     if (last_conv) last_out = g.out;
                     AKE_REQUIRE(g.ok || g.in == P2pIn::Planes || g.in == P2pIn::Src, AKE_ERR_STATE,
                                 "pcnet: the route promised an input form only the persistent pitch conv reads, for a chunk (%d clips) it does not take", B);
-                    if (g.ok) rc = run_p2p_f16_ps(n, n->p2p[i][j], g, io, B, P, Ti, s, "conv_p2p_f16_kernel");
-                    else rc = run_p2p_f16(n, n->p2p[i][j], io.planes, j == 0 ? &io.src : nullptr, B, P, Ti, io.dst, d.out_p, io.plane, s, "conv_p2p_f16_kernel");
+                    if (g.ok) rc = run_p2p_f16_ps(n, n->p2p[i][j].eval, g, io, B, P, Ti, s, "conv_p2p_f16_kernel");
+                    else rc = run_p2p_f16(n, n->p2p[i][j].eval, io.planes, j == 0 ? &io.src : nullptr, B, P, Ti, io.dst, d.out_p, io.plane, s, "conv_p2p_f16_kernel");
                     if (rc) return rc;
                     continue;
                 }
                 if (rp.x3_convs >> j & 1) {   // f16 x 3 on the persistent form; else the f32 MFMA kernel
-                    const PackedConv& px = train ? n->p2p_t[i][j] : n->p2p[i][j];
-                    const int bn = train ? bn_of(m + "p2p.layer." + std::to_string(3 * j + 1)) : -1;
+                    const PackedConv& px = train ? n->p2p[i][j].train : n->p2p[i][j].eval;
+                    const int bn = train ? n->p2p[i][j].bn : -1;
                     P2pX3Opts ox;
                     ox.lrelu = !train;             // (training: the BatchNorm finalised below comes first)
                     if ((rc = run_p2p_f16x3(n, rk.x3[j > 0], px.bf_off, sdesc, in_aff, n->blob_dev + px.b_off, B, P, Ti, out.p, d.out_p,
                                             train ? b.stats + 2 * n->bns[bn].ch_off : nullptr, train ? 2 * n->bn_channels : 0, s, "conv_p2p_f16x3_kernel/p2p", ox)))
                         return rc;
                     if (train && (rc = finalize_bn(bn, static_cast<double>(B) * P * Ti, out.aff))) return rc;
-                } else if ((rc = conv(n->p2p[i][j], train ? n->p2p_t[i][j] : n->p2p[i][j], m + "p2p.layer." + std::to_string(3 * j + 1), 0, sdesc,
-                                      in_aff, B, P, Ti, true, out.p, d.out_p, 0, out.aff, "conv_mfma_kernel/p2p")))
+                } else if ((rc = conv(n->p2p[i][j], 0, sdesc, in_aff, B, P, Ti, true, out.p, d.out_p, 0, out.aff, "conv_mfma_kernel/p2p")))
                     return rc;
                 sdesc = Src{out.p, d.out_p, nullptr, 0, 0};
                 in_aff = out.aff;
@@ -2693,7 +2702,7 @@ struct Fwd {
             int cin = ctot;
             Slot pdst;
             if (c.resblock && train) {
-                if ((rc = res_stack_train(n->pc2pc_t[i], m + "pc2pc.layer.", 1, Src{psrc.p, cin, nullptr, 0, 0}, psrc.aff, B, 12, Ti, b.pcst[i], b.aff_pcst[i],
+                if ((rc = res_stack_train(n->pc2pc[i], 1, Src{psrc.p, cin, nullptr, 0, 0}, psrc.aff, B, 12, Ti, b.pcst[i], b.aff_pcst[i],
                                           nullptr, 0, "conv_mfma_kernel/pc2pc")))
                     return rc;
                 pdst = b.pc_last(i);
@@ -2703,8 +2712,7 @@ struct Fwd {
             }
             for (int j = 0; j < c.conv_layers && !c.resblock; ++j) {
                 pdst = b.pc_out(train, i, j);
-                if ((rc = conv(n->pc2pc[i][j], train ? n->pc2pc_t[i][j] : n->pc2pc[i][j], m + "pc2pc.layer." + std::to_string(3 * j + 1), 1,
-                               Src{psrc.p, cin, nullptr, 0, 0}, psrc.aff, B, 12, Ti, true, pdst.p, d.out_pc, 0, pdst.aff, "conv_mfma_kernel/pc2pc")))
+                if ((rc = conv(n->pc2pc[i][j], 1, Src{psrc.p, cin, nullptr, 0, 0}, psrc.aff, B, 12, Ti, true, pdst.p, d.out_pc, 0, pdst.aff, "conv_mfma_kernel/pc2pc")))
                     return rc;
                 psrc = pdst; cin = d.out_pc;
             }
@@ -2732,7 +2740,6 @@ struct Fwd {
         int cin = L == 1 ? 1 : d.prev_pc + d.out_p;
         const int cout_default = L == 1 ? c.n_filters : d.out_pc;
         const int cout = cout_default;
-        const std::string m = "model." + std::to_string(i) + ".pc2pc.layer.";
         Slot pdst;
         // inference, 16-channel stacks: bf16 MFMA with split operands; the stack's input is converted to channels-last planes once,
         // the intermediate activations stay in that format (same 64 B per position as 16 f32 channels: the ping-pong buffers are
@@ -2745,7 +2752,7 @@ struct Fwd {
         } else if (pc_bf && (rc = run_nchw_to_cl16(psrc.p, cin, B, Ti, reinterpret_cast<unsigned short*>(b.pcb[i]), s))) return rc;
         const char* const pc_label = L == 1 ? "conv_mfma_kernel/pc2pc0" : "conv_mfma_kernel/pc2pc";
         if (c.resblock && train) {
-            if ((rc = res_stack_train(n->pc2pc_t[i], m, 1, Src{psrc.p, cin, nullptr, 0, 0}, psrc.aff, B, 12, Ti, b.pcst[i], b.aff_pcst[i], nullptr, 0, pc_label)))
+            if ((rc = res_stack_train(n->pc2pc[i], 1, Src{psrc.p, cin, nullptr, 0, 0}, psrc.aff, B, 12, Ti, b.pcst[i], b.aff_pcst[i], nullptr, 0, pc_label)))
                 return rc;
             pdst = b.pc_last(i);
         } else if (c.resblock) {
@@ -2761,22 +2768,21 @@ struct Fwd {
             if (pc_bf) {
                 const bool last_conv = j == c.conv_layers - 1;
                 const unsigned short* in = reinterpret_cast<const unsigned short*>(j == 0 ? b.pcb[i] : b.pc_out(false, i, j - 1).p);   // (the stack's input planes: pcb)
-                if ((rc = run_pc_bf16(n, n->pc2pc[i][j], in, B, Ti, true, true, last_conv ? pdst.p : nullptr,
+                if ((rc = run_pc_bf16(n, n->pc2pc[i][j].eval, in, B, Ti, true, true, last_conv ? pdst.p : nullptr,
                                       last_conv ? nullptr : reinterpret_cast<unsigned short*>(pdst.p), s, "conv_pc_bf16_kernel/pc2pc")))
                     return rc;
                 continue;
             }
             if (r.pc_x3_convs >> j & 1) {   // f16 x 3 MFMA (f32-equivalent products) instead of the f32 MFMA kernel
-                const PackedConv& pt = n->pc2pc_t[i][j];
+                const PackedConv& pt = n->pc2pc[i][j].train;
                 unsigned short* planes = reinterpret_cast<unsigned short*>(b.pcb[i]);       // (the inference ping-pong buffer: idle in training)
                 if ((rc = run_nchw_to_cl16_f16x2(psrc.p, cin, B, Ti, psrc.aff, planes, s))) return rc;
-                const int bn = bn_of(m + std::to_string(3 * j + 1));
+                const int bn = n->pc2pc[i][j].bn;
                 PcBf16Opts o;
                 o.f16x3 = true; o.stats = b.stats + 2 * n->bns[bn].ch_off; o.stats_stride = 2 * n->bn_channels;
                 if ((rc = run_pc_bf16(n, pt, planes, B, Ti, true, false, pdst.p, nullptr, s, "conv_pc_f16x3_kernel/pc2pc", o))) return rc;
                 if ((rc = finalize_bn(bn, static_cast<double>(B) * 12 * Ti, pdst.aff))) return rc;
-            } else if ((rc = conv(n->pc2pc[i][j], train ? n->pc2pc_t[i][j] : n->pc2pc[i][j], m + std::to_string(3 * j + 1), 1,
-                                  Src{psrc.p, cin, nullptr, 0, 0}, psrc.aff, B, 12, Ti, true, pdst.p, cout, 0, pdst.aff, pc_label)))
+            } else if ((rc = conv(n->pc2pc[i][j], 1, Src{psrc.p, cin, nullptr, 0, 0}, psrc.aff, B, 12, Ti, true, pdst.p, cout, 0, pdst.aff, pc_label)))
                 return rc;
             psrc = pdst; cin = cout;
         }
@@ -2789,10 +2795,7 @@ struct Fwd {
         }
         // ---- heads (models.py:750-753) ----
         const int Tf = b.Tf;
-        struct HeadRun { const std::vector<PackedConv>* ce; const std::vector<PackedConv>* ct; int kind; const char* nm; };
-        HeadRun heads[3] = {{&n->head_key, &n->head_key_t, 1, "key_classifier"},
-                            {&n->head_tonic, &n->head_tonic_t, 1, "tonic_classifier"},
-                            {&n->head_genre, &n->head_genre_t, 2, "genre_classifier"}};
+        const Head* const heads = n->heads;     // key, tonic, genre
         int Tm = Tf;
         bool head_planes_ready = false;           // training: the f16 hi / lo planes of the pooled features (b.feat_cl) exist
         int pooled_heads = 0;                     // heads whose outputs conv_head1_bf16_kernel already wrote
@@ -2806,7 +2809,6 @@ struct Fwd {
         const int nh_bf = genre_bf ? 3 : 2;
         float* const maps[3] = {b.map_k, b.map_t, b.map_g};
         float* const outs[3] = {key_out, tonic_out, genre_out};
-        const std::vector<PackedConv>* const hconv[3] = {&n->head_key, &n->head_tonic, &n->head_genre};
         PoolArgs pool;
         pool.seq = reinterpret_cast<const long long*>(seq);
         pool.n_pool_layers = L - 1; pool.tp = tp; pool.shrink = (c.kernel_size - 1) * c.head_layers; pool.max_pool = c.max_pool; pool.clip0 = 0;
@@ -2816,8 +2818,8 @@ struct Fwd {
             std::memset(&ha, 0, sizeof(ha));
             ha.xh = feat_cl; ha.xl = feat_cl + static_cast<long long>(B) * 12 * Tf * 16;
             for (int h = 0; h < nh_bf; ++h) {
-                const PackedConv& p0 = (*hconv[h])[0];
-                const PackedConv& p1 = (*hconv[h])[1];
+                const PackedConv& p0 = heads[h].convs[0].eval;
+                const PackedConv& p1 = heads[h].convs[1].eval;
                 ha.bfragA[h] = n->bf_frags_dev + p0.bf_off; ha.biasA[h] = n->blob_dev + p0.b_off; ha.KHA[h] = p0.kh;
                 ha.bfragB[h] = n->bf_frags_dev + p1.bf_off; ha.biasB[h] = n->blob_dev + p1.b_off; ha.KHB[h] = p1.kh;
                 ha.dst[h] = maps[h];
@@ -2840,12 +2842,12 @@ struct Fwd {
             Head1BfArgs ha;
             std::memset(&ha, 0, sizeof(ha));
             for (int h = 0; h < nh_bf; ++h) {
-                const PackedConv& p0 = (*hconv[h])[0];
-                const PackedConv& p1 = (*hconv[h])[1];
+                const PackedConv& p0 = heads[h].convs[0].eval;
+                const PackedConv& p1 = heads[h].convs[1].eval;
                 unsigned short* planes = reinterpret_cast<unsigned short*>(b.head_out(false, h, 0, false).p);
                 if (h == 0) {   // the key and the tonic head read the same features with the same geometry: one launch, blockIdx.y picks the head
                     PcBf16Opts tonic;
-                    tonic.pc2 = &(*hconv[1])[0]; tonic.planes_out2 = reinterpret_cast<unsigned short*>(b.head_out(false, 1, 0, false).p);
+                    tonic.pc2 = &heads[1].convs[0].eval; tonic.planes_out2 = reinterpret_cast<unsigned short*>(b.head_out(false, 1, 0, false).p);
                     if ((rc = run_pc_bf16(n, p0, feat_cl, B, Tf, false, true, nullptr, planes, s, "conv_pc_bf16_kernel/head", tonic))) return rc;
                 }
                 if (h == 2 && (rc = run_pc_bf16(n, p0, feat_cl, B, Tf, false, true, nullptr, planes, s, "conv_pc_bf16_kernel/genre_head")))
@@ -2872,23 +2874,24 @@ struct Fwd {
         }
         for (int h = head1_bf ? nh_bf : 0; h < (c.genre ? 3 : 2); ++h) {
             for (int j = 0; j < c.head_layers; ++j) {
-                const PackedConv& pe = (*heads[h].ce)[j];
+                const ConvSite& cs = heads[h].convs[j];
+                const PackedConv& pe = cs.eval;
                 const bool lastj = j == c.head_layers - 1;
                 // conv j reads the features or conv j - 1's output, hc channels of Tcur frames
                 const Slot src = j == 0 ? feat : b.head_out(train, h, j - 1, false);
-                const int hc = j == 0 ? n->final_ch : (*heads[h].ce)[j - 1].cout, Tcur = Tf - j * (c.kernel_size - 1);
+                const int hc = j == 0 ? n->final_ch : heads[h].convs[j - 1].eval.cout, Tcur = Tf - j * (c.kernel_size - 1);
                 const Slot dst = b.head_out(train, h, j, lastj);
                 if (head_bf && h < 2 && j == 0) {
                     if ((rc = run_pc_bf16(n, pe, feat_cl, B, Tcur, false, true, dst.p, nullptr, s, "conv_pc_bf16_kernel/head"))) return rc;
                     continue;
                 }
-                if (train && j == 0 && !lastj && pc_f16x3_ok((*heads[h].ct)[0], Tcur, false)) {   // the heads' first convs: f16 x 3 MFMA
-                    const PackedConv& pt = (*heads[h].ct)[0];
+                if (train && j == 0 && !lastj && pc_f16x3_ok(cs.train, Tcur, false)) {   // the heads' first convs: f16 x 3 MFMA
+                    const PackedConv& pt = cs.train;
                     if (!head_planes_ready) {               // one conversion of the pooled features serves the three heads
                         if ((rc = run_nchw_to_cl16_f16x2(src.p, hc, B, Tcur, src.aff, b.feat_cl, s))) return rc;
                         head_planes_ready = true;
                     }
-                    const int bn = bn_of(std::string(heads[h].nm) + ".1");
+                    const int bn = cs.bn;
                     PcBf16Opts o;
                     o.f16x3 = true; o.stats = b.stats + 2 * n->bns[bn].ch_off; o.stats_stride = 2 * n->bn_channels;
                     if ((rc = run_pc_bf16(n, pt, b.feat_cl, B, Tcur, false, false, dst.p, nullptr, s,
@@ -2899,21 +2902,18 @@ struct Fwd {
                     continue;
                 }
                 if (train && lastj && j > 0 && pe.cout == 1 && pe.kw == 7 && !n->raw_w_off.empty()) {   // cin -> 1: one workgroup per clip, f32 VALU
-                    const std::string wn = std::string(heads[h].nm) + "." + std::to_string(3 * j) + (heads[h].kind == 2 ? "" : ".conv2d");
-                    const auto wi = n->spec_index.find(wn + ".weight"), bi = n->spec_index.find(wn + ".bias");
                     const size_t lds = (static_cast<size_t>(hc) * 12 * Tcur + static_cast<size_t>(hc) * pe.kh * 7) * sizeof(float);
-                    if (wi != n->spec_index.end() && bi != n->spec_index.end() && lds <= 150 * 1024 && Tcur - 6 >= 1) {
+                    if (lds <= 150 * 1024 && Tcur - 6 >= 1) {
                         static ake::DeviceOnce hl_attr;
                         if ((rc = ake::raise_lds_limit(hl_attr, 150 * 1024, conv_head_last_kernel))) return rc;
                         if ((rc = ake::launch(h == 2 ? "conv_head_last_kernel/genre" : "conv_head_last_kernel", conv_head_last_kernel, dim3(B), dim3(384), lds, s,
-                                              src.p, src.aff, n->blob_dev + n->raw_w_off[wi->second], n->blob_dev + n->raw_w_off[bi->second], dst.p, hc, pe.kh,
+                                              src.p, src.aff, n->blob_dev + n->raw_w_off[cs.w], n->blob_dev + n->raw_w_off[cs.b], dst.p, hc, pe.kh,
                                               heads[h].kind == 2 ? 0 : 1, Tcur, Tcur - 6)))
                             return rc;
                         continue;
                     }
                 }
-                if ((rc = conv(pe, train ? (*heads[h].ct)[j] : pe, lastj ? "" : std::string(heads[h].nm) + "." + std::to_string(3 * j + 1),
-                               heads[h].kind, Src{src.p, hc, nullptr, 0, 0}, src.aff, B, 12, Tcur, false, dst.p, pe.cout, 0, dst.aff,
+                if ((rc = conv(cs, heads[h].kind, Src{src.p, hc, nullptr, 0, 0}, src.aff, B, 12, Tcur, false, dst.p, pe.cout, 0, dst.aff,
                                h == 2 ? "conv_mfma_kernel/genre_head" : "conv_mfma_kernel/head")))
                     return rc;
             }
@@ -3065,35 +3065,32 @@ static int train_site_lookup(const ake_pcnet* n, const Buffers& b, const std::st
     if (!site.empty() && site.back() == '.') site.pop_back();
     AKE_REQUIRE(!c.resblock && !c.denseblock && !c.p2pc_conv && !c.stay_sixth && !c.pc2p_mem && c.local == 0, AKE_ERR_INVALID,
                 "tap: 'train:%s': the raw / table taps cover the default architecture family only", t.c_str());
+    AKE_REQUIRE(n->finalized, AKE_ERR_STATE, "tap: 'train:%s': ake_pcnet_finalize has not been called", t.c_str());
     const int L = c.num_layers, P = c.pitches;
     float *z = nullptr, *aff = nullptr;
     int64_t C = 0, H = 0, Tn = 0;
     long long stride = 0;
     bool hit = false;            // (the pointers are null in the dry run of ake_pcnet_tap_info)
     auto found = [&](Slot t_, int64_t C_, int64_t H_, int64_t T_, long long stride_ = 0) { z = t_.p; aff = t_.aff; C = C_; H = H_; Tn = T_; stride = stride_; hit = true; };
-    for (int i = 0; i < L && !hit; ++i) {
-        const std::string m = "model." + std::to_string(i) + ".";
+    auto is = [&](const ConvSite& cs) { return !hit && cs.bn >= 0 && site == n->bns[cs.bn].name; };      // the sites know their BatchNorm's name
+    for (int i = 0; i < L; ++i) {
         const LayerDims& d = n->dims[i];
         const int Ti = b.Tl[i];
-        if (site == m + "pool_semi_b") found(Slot{b.semi_raw[i], b.aff_semi[i]}, i == 0 ? 1 : d.out_p, P / 3, Ti);
-        if (i >= 1 && site == m + "up_sixth_b") found(Slot{b.psix[i], b.aff_p2pin[i] ? b.aff_p2pin[i] + 3 * d.prev_p : nullptr}, d.prev_pc, 36, Ti);
-        for (int j = 0; j < c.conv_layers && !hit; ++j) {
-            const std::string bn = "layer." + std::to_string(3 * j + 1);
-            if (i >= 1 && site == m + "p2p." + bn) found(b.p_out(true, i, j), d.out_p, P, Ti);
-            if (site == m + "pc2pc." + bn) {
+        if (is(n->semi[i])) found(Slot{b.semi_raw[i], b.aff_semi[i]}, i == 0 ? 1 : d.out_p, P / 3, Ti);
+        if (is(n->up[i])) found(Slot{b.psix[i], b.aff_p2pin[i] ? b.aff_p2pin[i] + 3 * d.prev_p : nullptr}, d.prev_pc, 36, Ti);
+        for (int j = 0; j < static_cast<int>(n->p2p[i].size()); ++j)
+            if (is(n->p2p[i][j])) found(b.p_out(true, i, j), d.out_p, P, Ti);
+        for (int j = 0; j < static_cast<int>(n->pc2pc[i].size()); ++j)
+            if (is(n->pc2pc[i][j])) {
                 // layer 0's last convolution of a deeper net writes channels [0, n_filters) of layer 1's concat buffer (table: aff_cat[1])
                 if (i == 0 && L > 1 && j == c.conv_layers - 1) {
                     found(b.cat_slot(true, 1), c.n_filters, 12, Ti, static_cast<long long>(n->dims[1].prev_pc + n->dims[1].out_p) * 12 * Ti);
                 } else found(b.pc_out(true, i, j), i == 0 ? c.n_filters : d.out_pc, 12, Ti);
             }
-        }
     }
-    const std::vector<PackedConv>* head_t[3] = {&n->head_key_t, &n->head_tonic_t, &n->head_genre_t};
-    const char* head_nm[3] = {"key_classifier", "tonic_classifier", "genre_classifier"};
-    for (int h = 0; h < (c.genre ? 3 : 2) && !hit; ++h)
-        for (int j = 0; j + 1 < c.head_layers; ++j)
-            if (site == std::string(head_nm[h]) + "." + std::to_string(3 * j + 1))
-                found(b.head_out(true, h, j, false), (*head_t[h])[j].cout, 12, b.Tf - (j + 1) * (c.kernel_size - 1));
+    for (int h = 0; h < 3; ++h)
+        for (int j = 0; j < static_cast<int>(n->heads[h].convs.size()); ++j)
+            if (is(n->heads[h].convs[j])) found(b.head_out(true, h, j, false), n->heads[h].convs[j].train.cout, 12, b.Tf - (j + 1) * (c.kernel_size - 1));
     AKE_REQUIRE(hit && Tn >= 1, AKE_ERR_INVALID, "tap: 'train:%s' names no BatchNorm of this net", t.c_str());
     if (want_aff) { *p = aff; shape[0] = C; shape[1] = 3; shape[2] = 1; shape[3] = 1; }
     else { *p = z; shape[0] = batch; shape[1] = C; shape[2] = H; shape[3] = Tn; if (clip_stride) *clip_stride = stride; }

@@ -21,14 +21,13 @@ struct Bwd {
     const unsigned int* amax_cell = nullptr;
     const unsigned int* amax_for(const float* dz) const { return dz == amax_of ? amax_cell : nullptr; }
 
-    gfx_t* grad_of(const std::string& key) const { return grads + n->grad_off[n->spec_index.at(key)]; }
-    const float* raw_of(const std::string& key) const { return n->blob_dev + n->raw_w_off[n->spec_index.at(key)]; }
-    int bn_of(const std::string& name) const { return n->bn_index.at(name); }
+    // the gradient slot and the raw values of parameter `spec` (an index into ake_pcnet::specs: a site's w / b, a BatchNorm's weight / bias)
+    gfx_t* grad_of(int spec) const { return grads + n->grad_off[spec]; }
+    const float* raw_of(int spec) const { return n->blob_dev + n->raw_w_off[spec]; }
 
     // ga (gradient w.r.t. the activation a = lrelu(bn(z))) -> dz (gradient w.r.t. the raw conv output z), in place in `g`.
-    // g and z share the layout [B][ctot][HT]; the BatchNorm layer `bn_name` owns channels [coff, coff + C).
-    int bn_block_backward(const std::string& bn_name, float* g, const float* z, const float* aff, int ctot, int coff, int HT) {
-        const int bn = bn_of(bn_name);
+    // g and z share the layout [B][ctot][HT]; the BatchNorm layer `bn` (an index into ake_pcnet::bns) owns channels [coff, coff + C).
+    int bn_block_backward(int bn, float* g, const float* z, const float* aff, int ctot, int coff, int HT) {
         const auto& l = n->bns[bn];
         double* st2 = b.stats2 + 3 * l.ch_off;
         const float* bst = b.bstats + 3 * l.ch_off;
@@ -39,7 +38,7 @@ struct Bwd {
                               ctot, coff, HT)))
             return rc;
         if ((rc = ake::launch("bn_bwd_coef_kernel", bn_bwd_coef_kernel, dim3((l.C + 63) / 64), dim3(64), 0, s, st2, static_cast<long long>(3) * n->bn_channels, bst,
-                              n->blob_dev + l.gamma_off, coef, grad_of(bn_name + ".weight"), grad_of(bn_name + ".bias"), l.C)))
+                              n->blob_dev + l.gamma_off, coef, grad_of(l.p.weight), grad_of(l.p.bias), l.C)))
             return rc;
         unsigned int* cell = reinterpret_cast<unsigned int*>(b.stats2 + static_cast<size_t>(3) * n->bn_channels * kBwdStatSlots) + static_cast<size_t>(bn) * kAmaxSlots;
         if ((rc = ake::launch("bn_bwd_apply_kernel", bn_bwd_apply_kernel, grid, dim3(256), 0, s, g, z, aff, coef, ctot, coff, HT, cell))) return rc;
@@ -246,7 +245,7 @@ struct Bwd {
             PackedConv t2 = dp.c2;                         // true kernel size for the weight gradient (the pack may store 7 taps)
             t2.kh = kind == 1 ? 12 : k; t2.kw = k;
             if ((rc = wgrad(t2, kind, Src{botts[j], bott, nullptr, 0, 0}, aff2s[j], H, T, true, g_feat, ctot, cj, grad_of(dp.w2), wname, kind == 0))) return rc;
-            if (!dp.b2.empty() && (rc = bias_grad(g_feat, ctot, cj, nf, static_cast<int>(HT), grad_of(dp.b2)))) return rc;
+            if (dp.b2 >= 0 && (rc = bias_grad(g_feat, ctot, cj, nf, static_cast<int>(HT), grad_of(dp.b2)))) return rc;
             {
                 const ConvGeom g2 = kind == 0 ? ConvGeom{k - 1 - k / 2, k - 1 - k / 2, T, H, 0} : ConvGeom{11, k - 1 - k / 2, T, H, 0};
                 ConvOpts o;
@@ -255,7 +254,7 @@ struct Bwd {
                                    dname, o)))
                     return rc;
             }
-            if ((rc = bn_block_backward(dp.norm2, g_bott, botts[j], aff2s[j], bott, 0, static_cast<int>(HT)))) return rc;
+            if ((rc = bn_block_backward(dp.bn2, g_bott, botts[j], aff2s[j], bott, 0, static_cast<int>(HT)))) return rc;
             // ---- conv1: bott_j = conv1(lrelu(norm1(feat[0, cj)))) (its bias, where it has one, is removed by norm2: zero gradient) ----
             PackedConv t1 = dp.c1;
             t1.kh = kind == 1 ? 12 : 1; t1.kw = 1;
@@ -266,7 +265,7 @@ struct Bwd {
                 o.geom = &g1; o.rows_zero = kind == 0;
                 if ((rc = run_conv(n, dp.d1, kind, Src{g_bott, bott, nullptr, 0, 0}, B, H, T, true, false, g_scr, ctot, 0, s, dname, o))) return rc;
             }
-            if ((rc = bn_block_backward(dp.norm1, g_scr, feat, aff1s[j], ctot, 0, static_cast<int>(HT)))) return rc;
+            if ((rc = bn_block_backward(dp.bn1, g_scr, feat, aff1s[j], ctot, 0, static_cast<int>(HT)))) return rc;
             const long long total = static_cast<long long>(B) * cj * HT;
             if ((rc = launch_flat("add_channels_kernel", add_channels_kernel, s, total, g_feat, ctot, g_scr, ctot, cj, HT, total))) return rc;
         }
@@ -283,7 +282,6 @@ struct Bwd {
         for (int li = L - 1; li >= 1; --li) {
             const LayerDims& d = n->dims[li];
             const int Tl = b.Tl[li], ctd = d.prev_pc + d.out_p + g;
-            const std::string m = "model." + std::to_string(li) + ".";
             {   // the time-pooled copy of the whole concat buffer: the heads' input (last layer) or the first channels of the next layer's buffer
                 const long long total = static_cast<long long>(B) * ctd * 12 * ((Tl / tp) + (Tl % tp ? 1 : 0));
                 const bool last = li == L - 1;
@@ -313,13 +311,13 @@ struct Bwd {
                 const long long total = static_cast<long long>(B) * d.prev_pc * 36 * Tl;
                 if ((rc = launch_flat("repeat_sum_kernel", repeat_sum_kernel, s, total, g_p, b.g_psix[li], d.out_p, d.prev_p, d.prev_pc, P, Tl, total))) return rc;
             }
-            if ((rc = bn_block_backward(m + "up_sixth_b", b.g_psix[li], b.psix[li], b.aff_p2pin[li] + 3 * d.prev_p, d.prev_pc, 0, 36 * Tl))) return rc;
+            if ((rc = bn_block_backward(n->up[li].bn, b.g_psix[li], b.psix[li], b.aff_p2pin[li] + 3 * d.prev_p, d.prev_pc, 0, 36 * Tl))) return rc;
             if ((rc = ake::launch("up_sixth_bwd_weight_kernel", up_sixth_bwd_weight_kernel, dim3(d.prev_pc * d.prev_pc * 3, B), dim3(64), 0, s, b.g_psix[li], b.cat[li],
-                                  static_cast<long long>(ctd) * 12 * Tl, nullptr, grad_of(m + "up_sixth.weight"), static_cast<long long>(n->grad_floats), d.prev_pc, Tl)))
+                                  static_cast<long long>(ctd) * 12 * Tl, nullptr, grad_of(n->up[li].w), static_cast<long long>(n->grad_floats), d.prev_pc, Tl)))
                 return rc;
             {
                 const long long total = static_cast<long long>(B) * d.prev_pc * 12 * Tl;
-                if ((rc = launch_flat("up_sixth_bwd_data_kernel", up_sixth_bwd_data_kernel, s, total, b.g_psix[li], raw_of(m + "up_sixth.weight"), b.g_cat[li], ctd,
+                if ((rc = launch_flat("up_sixth_bwd_data_kernel", up_sixth_bwd_data_kernel, s, total, b.g_psix[li], raw_of(n->up[li].w), b.g_cat[li], ctd,
                                       d.prev_pc, Tl, total)))
                     return rc;
             }
@@ -339,26 +337,24 @@ struct Bwd {
 
     // A stack of `nconv` convolutions (conv -> BN -> LReLU each).  g holds ga w.r.t. the last activation on entry and is
     // ping-ponged with g2.  On exit *g_in_out holds ga w.r.t. the stack input (shape of the input: in_ctot channels).
-    int stack_backward(const std::vector<PackedConv>& fwd_t, const std::vector<PackedConv>& dpack, const std::string& prefix, bool conv2d_suffix,
-                       int kind, Src stack_in, const float* stack_in_aff, const std::vector<float*>& z, const std::vector<float*>& aff,
+    int stack_backward(const std::vector<ConvSite>& st, int kind, Src stack_in, const float* stack_in_aff, const std::vector<float*>& z, const std::vector<float*>& aff,
                        int H, int Tn, float* g, float* g2, float* g_in, int g_in_ctot, const char* wname, const char* dname) {
-        const int nconv = static_cast<int>(fwd_t.size());
+        const int nconv = static_cast<int>(st.size());
         int rc;
         if (n->cfg.resblock)   // the gradient buffers of a --resblock net are 4 maps wide: g | skip copy | the blocks' 2C-channel hidden map
-            return res_stack_backward(fwd_t, dpack, prefix, conv2d_suffix, kind, stack_in, stack_in_aff, z, aff, H, Tn, g, g2,
-                                      g2 + static_cast<size_t>(B) * fwd_t[0].cout * H * Tn, g_in, g_in_ctot, wname, dname);
+            return res_stack_backward(st, kind, stack_in, stack_in_aff, z, aff, H, Tn, g, g2, g2 + static_cast<size_t>(B) * st[0].train.cout * H * Tn, g_in,
+                                      g_in_ctot, wname, dname);
         for (int j = nconv - 1; j >= 0; --j) {
-            const PackedConv& pc = fwd_t[j];
-            const std::string cname = prefix + std::to_string(3 * j) + (conv2d_suffix ? ".conv2d" : "");
-            if ((rc = bn_block_backward(prefix + std::to_string(3 * j + 1), g, z[j], aff[j], pc.cout, 0, H * Tn))) return rc;
+            const PackedConv& pc = st[j].train;
+            if ((rc = bn_block_backward(st[j].bn, g, z[j], aff[j], pc.cout, 0, H * Tn))) return rc;
             // bias gradient under BatchNorm is exactly zero (the mean subtraction removes it); grads were zero-filled
-            Src in = j == 0 ? stack_in : Src{z[j - 1], fwd_t[j - 1].cout, nullptr, 0, 0};
+            Src in = j == 0 ? stack_in : Src{z[j - 1], st[j - 1].train.cout, nullptr, 0, 0};
             const float* in_aff = j == 0 ? stack_in_aff : aff[j - 1];
-            if ((rc = wgrad(pc, kind, in, in_aff, H, Tn, true, g, pc.cout, 0, grad_of(cname + ".weight"), wname))) return rc;
+            if ((rc = wgrad(pc, kind, in, in_aff, H, Tn, true, g, pc.cout, 0, grad_of(st[j].w), wname))) return rc;
             float* dst = j == 0 ? g_in : g2;
-            const int dst_ctot = j == 0 ? g_in_ctot : fwd_t[j - 1].cout;
+            const int dst_ctot = j == 0 ? g_in_ctot : st[j - 1].train.cout;
             if (dst) {
-                if ((rc = dgrad(dpack[j], pc, kind, g, H, Tn, Tn, true, dst, dst_ctot, 0, false, dname))) return rc;
+                if ((rc = dgrad(st[j].dgrad, pc, kind, g, H, Tn, Tn, true, dst, dst_ctot, 0, false, dname))) return rc;
             }
             if (j > 0) std::swap(g, g2);
         }
@@ -366,37 +362,31 @@ struct Bwd {
     }
 
     // --resblock stack (models.py:181-187 / 218-224, 402-454): conv0 + BN + LReLU, then per block x <- LReLU(x + b2(conv2(LReLU(b1(conv1(x)))))).
-    // fwd_t / dpack = [conv0, (conv1, conv2) per block]; z / aff = res_stack_train's tensors [conv0 raw, (conv1 raw, conv2 raw, block
+    // st = the sites [conv0, (conv1, conv2) per block]; z / aff = res_stack_train's tensors [conv0 raw, (conv1 raw, conv2 raw, block
     // output) per block].  g: ga w.r.t. the last block's output on entry; gs: skip copy; gh: the 2C-channel hidden gradient.
-    int res_stack_backward(const std::vector<PackedConv>& fwd_t, const std::vector<PackedConv>& dpack, const std::string& prefix, bool conv2d_suffix,
-                           int kind, Src stack_in, const float* stack_in_aff, const std::vector<float*>& z, const std::vector<float*>& aff, int H, int Tn,
+    int res_stack_backward(const std::vector<ConvSite>& st, int kind, Src stack_in, const float* stack_in_aff, const std::vector<float*>& z, const std::vector<float*>& aff, int H, int Tn,
                            float* g, float* gs, float* gh, float* g_in, int g_in_ctot, const char* wname, const char* dname) {
-        const int nb = (static_cast<int>(fwd_t.size()) - 1) / 2;
-        const int C = fwd_t[0].cout;
-        const std::string sfx = conv2d_suffix ? ".conv2d" : "";
-        AKE_REQUIRE(static_cast<int>(z.size()) == 1 + 3 * nb && dpack.size() == fwd_t.size(), AKE_ERR_STATE, "resblock backward: buffer bookkeeping");
+        const int nb = (static_cast<int>(st.size()) - 1) / 2;
+        const int C = st[0].train.cout;
+        AKE_REQUIRE(static_cast<int>(z.size()) == 1 + 3 * nb, AKE_ERR_STATE, "resblock backward: buffer bookkeeping");
         int rc;
         for (int r = nb - 1; r >= 0; --r) {
-            const std::string bp = prefix + std::to_string(3 + r) + ".";
+            const ConvSite &c1 = st[1 + 2 * r], &c2 = st[2 + 2 * r];
             const long long total = static_cast<long long>(B) * C * H * Tn;
             if ((rc = launch_flat("res_act_bwd_kernel", res_act_bwd_kernel, s, total, g, z[3 + 3 * r], gs, total))) return rc;
             // b2 has no activation of its own: its table carries slope 1, so the generic block applies LeakyReLU' = 1
-            if ((rc = bn_block_backward(bp + "b2", g, z[2 + 3 * r], aff[2 + 3 * r], C, 0, H * Tn))) return rc;
-            if ((rc = wgrad(fwd_t[2 + 2 * r], kind, Src{z[1 + 3 * r], 2 * C, nullptr, 0, 0}, aff[1 + 3 * r], H, Tn, true, g, C, 0,
-                            grad_of(bp + "conv2" + sfx + ".weight"), wname)))
-                return rc;
-            if ((rc = dgrad(dpack[2 + 2 * r], fwd_t[2 + 2 * r], kind, g, H, Tn, Tn, true, gh, 2 * C, 0, false, dname))) return rc;
-            if ((rc = bn_block_backward(bp + "b1", gh, z[1 + 3 * r], aff[1 + 3 * r], 2 * C, 0, H * Tn))) return rc;
+            if ((rc = bn_block_backward(c2.bn, g, z[2 + 3 * r], aff[2 + 3 * r], C, 0, H * Tn))) return rc;
+            if ((rc = wgrad(c2.train, kind, Src{z[1 + 3 * r], 2 * C, nullptr, 0, 0}, aff[1 + 3 * r], H, Tn, true, g, C, 0, grad_of(c2.w), wname))) return rc;
+            if ((rc = dgrad(c2.dgrad, c2.train, kind, g, H, Tn, Tn, true, gh, 2 * C, 0, false, dname))) return rc;
+            if ((rc = bn_block_backward(c1.bn, gh, z[1 + 3 * r], aff[1 + 3 * r], 2 * C, 0, H * Tn))) return rc;
             // the block's input: the previous block's output (final, identity table) or conv0's raw output + its BatchNorm
-            if ((rc = wgrad(fwd_t[1 + 2 * r], kind, Src{z[3 * r], C, nullptr, 0, 0}, aff[3 * r], H, Tn, true, gh, 2 * C, 0,
-                            grad_of(bp + "conv1" + sfx + ".weight"), wname)))
-                return rc;
-            if ((rc = dgrad(dpack[1 + 2 * r], fwd_t[1 + 2 * r], kind, gh, H, Tn, Tn, true, gs, C, 0, true, dname))) return rc;   // + the skip copy
+            if ((rc = wgrad(c1.train, kind, Src{z[3 * r], C, nullptr, 0, 0}, aff[3 * r], H, Tn, true, gh, 2 * C, 0, grad_of(c1.w), wname))) return rc;
+            if ((rc = dgrad(c1.dgrad, c1.train, kind, gh, H, Tn, Tn, true, gs, C, 0, true, dname))) return rc;   // + the skip copy
             std::swap(g, gs);
         }
-        if ((rc = bn_block_backward(prefix + "1", g, z[0], aff[0], C, 0, H * Tn))) return rc;
-        if ((rc = wgrad(fwd_t[0], kind, stack_in, stack_in_aff, H, Tn, true, g, C, 0, grad_of(prefix + "0" + sfx + ".weight"), wname))) return rc;
-        if (g_in && (rc = dgrad(dpack[0], fwd_t[0], kind, g, H, Tn, Tn, true, g_in, g_in_ctot, 0, false, dname))) return rc;
+        if ((rc = bn_block_backward(st[0].bn, g, z[0], aff[0], C, 0, H * Tn))) return rc;
+        if ((rc = wgrad(st[0].train, kind, stack_in, stack_in_aff, H, Tn, true, g, C, 0, grad_of(st[0].w), wname))) return rc;
+        if (g_in && (rc = dgrad(st[0].dgrad, st[0].train, kind, g, H, Tn, Tn, true, g_in, g_in_ctot, 0, false, dname))) return rc;
         return AKE_OK;
     }
 
@@ -441,10 +431,6 @@ struct Bwd {
         float* g_feat = L > 1 ? b.g_pcf : b.g_pc[0];          // gradient w.r.t. the head input activation
         AKE_HIP_CHECK(hipMemsetAsync(g_feat, 0, sizeof(float) * B * fin * 12 * Tf, s));
 
-        struct HeadRun { const std::vector<PackedConv>* ct; const std::vector<PackedConv>* cd; int kind; const char* nm; bool conv2d; };
-        HeadRun heads[3] = {{&n->head_key_t, &n->head_key_d, 1, "key_classifier", true},
-                            {&n->head_tonic_t, &n->head_tonic_d, 1, "tonic_classifier", true},
-                            {&n->head_genre_t, &n->head_genre_d, 2, "genre_classifier", false}};
         {   // scratch for the f16 planes of the heads' 32-channel gradients: the last layer's inference ping-pong buffer (idle in training)
             const int T1 = Tf - (c.kernel_size - 1);
             const size_t need = static_cast<size_t>(2) * B * 12 * T1 * 16 * 2 * sizeof(unsigned short);
@@ -452,31 +438,27 @@ struct Bwd {
             planes_scratch = (L > 1 && fin == 16 && !c.resblock && !c.denseblock && T1 > 0 && need <= have) ? reinterpret_cast<unsigned short*>(b.pcb[i]) : nullptr;
         }
         for (int h = 0; h < (c.genre ? 3 : 2); ++h) {
-            const auto& ct = *heads[h].ct;
-            const auto& cd = *heads[h].cd;
+            const std::vector<ConvSite>& hc = n->heads[h].convs;
             const int nl = c.head_layers;
             float* g = b.g_map[h];                 // dz of the last conv (no BatchNorm): [B][1][12][Tm] (genre: row 11 zero)
             int Tcur = Tm;
             for (int j = nl - 1; j >= 0; --j) {
-                const PackedConv& pc = ct[j];
-                const std::string cname = std::string(heads[h].nm) + "." + std::to_string(3 * j) + (heads[h].conv2d ? ".conv2d" : "");
+                const PackedConv& pc = hc[j].train;
                 const int T_in = Tcur + c.kernel_size - 1;
-                const int H_out = heads[h].kind == 2 ? 12 - pc.kh + 1 : 12;
                 const Slot z = b.head_out(true, h, j, j == nl - 1), zin = j == 0 ? Slot{} : b.head_out(true, h, j - 1, false);
-                if (j < nl - 1) rc = bn_block_backward(std::string(heads[h].nm) + "." + std::to_string(3 * j + 1), g, z.p, z.aff, pc.cout, 0, 12 * Tcur);
-                else rc = bias_grad(g, pc.cout, 0, pc.cout, 12 * Tcur, grad_of(cname + ".bias"));   // row 11 of the genre map gradient is zero
+                if (j < nl - 1) rc = bn_block_backward(hc[j].bn, g, z.p, z.aff, pc.cout, 0, 12 * Tcur);
+                else rc = bias_grad(g, pc.cout, 0, pc.cout, 12 * Tcur, grad_of(hc[j].b));   // row 11 of the genre map gradient is zero
                 if (rc) return rc;
-                Src in = j == 0 ? Src{feat, fin, nullptr, 0, 0} : Src{zin.p, ct[j - 1].cout, nullptr, 0, 0};
+                Src in = j == 0 ? Src{feat, fin, nullptr, 0, 0} : Src{zin.p, hc[j - 1].train.cout, nullptr, 0, 0};
                 const float* in_aff = j == 0 ? feat_aff : zin.aff;
                 // the genre gradient maps carry 12 rows (the last one zero), so circular rows reproduce its "valid" rows exactly
                 const int kind_w = 1;
-                if ((rc = wgrad(pc, kind_w, in, in_aff, 12, T_in, false, g, pc.cout, 0, grad_of(cname + ".weight"), "conv_wgrad_kernel/head"))) return rc;
+                if ((rc = wgrad(pc, kind_w, in, in_aff, 12, T_in, false, g, pc.cout, 0, grad_of(hc[j].w), "conv_wgrad_kernel/head"))) return rc;
                 float* dst = j == 0 ? g_feat : b.g_hid;
-                if ((rc = dgrad(cd[j], pc, 1, g, 12, Tcur, T_in, false, dst, j == 0 ? fin : ct[j - 1].cout, 0, j == 0, "conv_mfma_kernel/head_dgrad")))
+                if ((rc = dgrad(hc[j].dgrad, pc, 1, g, 12, Tcur, T_in, false, dst, j == 0 ? fin : hc[j - 1].train.cout, 0, j == 0, "conv_mfma_kernel/head_dgrad")))
                     return rc;
                 g = b.g_hid;
                 Tcur = T_in;
-                (void)H_out;
             }
         }
 
@@ -499,7 +481,7 @@ struct Bwd {
         }
         if (L == 1) {
             // single layer: pc2pc0 stack straight down to fold0
-            if ((rc = stack_backward(n->pc2pc_t[0], n->pc2pc_d[0], "model.0.pc2pc.layer.", true, 1, Src{b.fold0, 1, nullptr, 0, 0}, nullptr,
+            if ((rc = stack_backward(n->pc2pc[0], 1, Src{b.fold0, 1, nullptr, 0, 0}, nullptr,
                                      b.pcst[0], b.aff_pcst[0], 12, Ti, g_last, g_last2, b.g_fold0, 1, "conv_wgrad_kernel/pc2pc0", "conv_mfma_kernel/pc2pc0_dgrad")))
                 return rc;
             return semi_backward(0, mel, nullptr, b.g_fold0, 1, 0, nullptr);
@@ -512,13 +494,12 @@ struct Bwd {
             const int Pp = c.stay_sixth ? P / 3 : P;              // rows of the pitch stream (--stay_sixth: semitone resolution)
             const int ctot = dl.prev_pc + dl.out_p;
             const bool inner = li < L - 1;
-            const std::string m = "model." + std::to_string(li) + ".";
             float* gl = b.g_pc[li];
             float* gl2 = gl + static_cast<size_t>(B) * dl.out_pc * 12 * Tl;
             // pc2pc stack (input = concat buffer: pitch classes of the layer below | folded semitone maps)
             // (the inference ping-pong buffer of the layer is idle in training: the gradient's f16 planes go there)
             planes_scratch = (dl.out_pc == 16 && !c.resblock) ? reinterpret_cast<unsigned short*>(b.pcb[li]) : nullptr;
-            rc = stack_backward(n->pc2pc_t[li], n->pc2pc_d[li], m + "pc2pc.layer.", true, 1, Src{b.cat[li], ctot, nullptr, 0, 0}, b.aff_cat[li],
+            rc = stack_backward(n->pc2pc[li], 1, Src{b.cat[li], ctot, nullptr, 0, 0}, b.aff_cat[li],
                                 b.pcst[li], b.aff_pcst[li], 12, Tl, gl, gl2, b.g_cat[li], ctot, "conv_wgrad_kernel/pc2pc", "conv_mfma_kernel/pc2pc_dgrad");
             planes_scratch = nullptr;
             if (rc) return rc;
@@ -544,7 +525,7 @@ struct Bwd {
             Src pin = c.pc2p_mem ? Src{b.pin[li], dl.prev_p, nullptr, 0, 0} : Src{li == 1 ? mel : b.ppool[li - 1], dl.prev_p, b.psix[li], dl.prev_pc, 36};
             if (c.stay_sixth) pin = Src{li == 1 ? b.semi_raw[0] : b.ppool[li - 1], dl.prev_p, b.pcd[li], dl.prev_pc, 12};   // (table: aff_p2pin, set by the forward)
             const int pin_ch = c.pc2p_mem ? dl.prev_p : dl.prev_p + dl.prev_pc;
-            if ((rc = stack_backward(n->p2p_t[li], n->p2p_d[li], m + "p2p.layer.", false, 0, pin, b.aff_p2pin[li], zp, b.aff_pst[li], Pp, Tl, g_p, g_p2,
+            if ((rc = stack_backward(n->p2p[li], 0, pin, b.aff_p2pin[li], zp, b.aff_pst[li], Pp, Tl, g_p, g_p2,
                                      b.g_pin[li], pin_ch, "conv_wgrad_kernel/p2p", "conv_mfma_kernel/p2p_dgrad")))
                 return rc;
             // ---- repeat (x P/36) backward, then up_sixth ----
@@ -561,13 +542,13 @@ struct Bwd {
             }
             if (rc) return rc;
             if (!c.stay_sixth) {
-                if ((rc = bn_block_backward(m + "up_sixth_b", b.g_psix[li], b.psix[li], b.aff_p2pin[li] + 3 * dl.prev_p, dl.prev_pc, 0, 36 * Tl))) return rc;
+                if ((rc = bn_block_backward(n->up[li].bn, b.g_psix[li], b.psix[li], b.aff_p2pin[li] + 3 * dl.prev_p, dl.prev_pc, 0, 36 * Tl))) return rc;
                 if ((rc = ake::launch("up_sixth_bwd_weight_kernel", up_sixth_bwd_weight_kernel, dim3(dl.prev_pc * dl.prev_pc * 3, B), dim3(64), 0, s, b.g_psix[li],
-                                      b.cat[li], static_cast<long long>(ctot) * 12 * Tl, b.aff_cat[li], grad_of(m + "up_sixth.weight"),
+                                      b.cat[li], static_cast<long long>(ctot) * 12 * Tl, b.aff_cat[li], grad_of(n->up[li].w),
                                       static_cast<long long>(n->grad_floats), dl.prev_pc, Tl)))
                     return rc;
                 const long long total = static_cast<long long>(B) * dl.prev_pc * 12 * Tl;
-                if ((rc = launch_flat("up_sixth_bwd_data_kernel", up_sixth_bwd_data_kernel, s, total, b.g_psix[li], raw_of(m + "up_sixth.weight"), b.g_cat[li], ctot,
+                if ((rc = launch_flat("up_sixth_bwd_data_kernel", up_sixth_bwd_data_kernel, s, total, b.g_psix[li], raw_of(n->up[li].w), b.g_cat[li], ctot,
                                       dl.prev_pc, Tl, total)))
                     return rc;
             }
@@ -594,7 +575,7 @@ struct Bwd {
             std::vector<float*> aff0 = b.aff_pcst[0];
             aff0.back() = b.aff_cat[1];
             float* g02 = g0 + static_cast<size_t>(B) * c.n_filters * 12 * T0;
-            if ((rc = stack_backward(n->pc2pc_t[0], n->pc2pc_d[0], "model.0.pc2pc.layer.", true, 1, Src{b.fold0, 1, nullptr, 0, 0}, nullptr, b.pcst[0],
+            if ((rc = stack_backward(n->pc2pc[0], 1, Src{b.fold0, 1, nullptr, 0, 0}, nullptr, b.pcst[0],
                                      aff0, 12, T0, g0, g02, b.g_fold0, 1, "conv_wgrad_kernel/pc2pc0", "conv_mfma_kernel/pc2pc0_dgrad")))
                 return rc;
         }
@@ -606,9 +587,8 @@ struct Bwd {
     // gradient.  x / x_aff: the pitch tensor the semitone conv read.  ga_x (nullable): receives dL/d(act(x)).
     int semi_backward(int layer, const float* x, const float* x_aff, const float* gfold, int g_ctot, int g_coff, float* ga_x,
                       const float* extra_g = nullptr, int extra_ctot = 0) {
-        const PackedConv& pc = n->semi_t[layer];
-        const int C = pc.cin, P = n->cfg.pitches, Tn = b.Tl[layer];
-        const std::string m = "model." + std::to_string(layer) + ".";
+        const ConvSite& semi = n->semi[layer];
+        const int C = semi.train.cin, P = n->cfg.pitches, Tn = b.Tl[layer];
         float* g = b.g_semi[layer];
         int rc;
         if (n->cfg.p2pc_conv) {   // models.py:108-133: the fold is a convolution over the octaves + pool.bn + LeakyReLU
@@ -618,12 +598,12 @@ struct Bwd {
             if ((rc = launch_flat("slice_channels_kernel", slice_channels_kernel, s, total, gfold + static_cast<long long>(g_coff) * 12 * Tn,
                                   static_cast<long long>(g_ctot) * 12 * Tn, gf, per_clip, total)))
                 return rc;
-            if ((rc = bn_block_backward(m + "pool.bn", gf, b.foldc_raw[layer], b.aff_foldc[layer], C, 0, 12 * Tn))) return rc;
+            if ((rc = bn_block_backward(n->foldc[layer].bn, gf, b.foldc_raw[layer], b.aff_foldc[layer], C, 0, 12 * Tn))) return rc;
             if ((rc = ake::launch("fold_conv_bwd_weight_kernel", fold_conv_bwd_weight_kernel, dim3(C * C * (P / 36), B), dim3(64), 0, s, gf, b.semi_raw[layer],
-                                  b.aff_semi[layer], grad_of(m + "pool.conv.weight"), static_cast<long long>(n->grad_floats), C, P / 36, Tn)))
+                                  b.aff_semi[layer], grad_of(n->foldc[layer].w), static_cast<long long>(n->grad_floats), C, P / 36, Tn)))
                 return rc;
             const long long tot = static_cast<long long>(B) * C * (P / 3) * Tn;
-            rc = launch_flat("fold_conv_bwd_data_kernel", fold_conv_bwd_data_kernel, s, tot, gf, raw_of(m + "pool.conv.weight"), g, C, P / 36, Tn, tot);
+            rc = launch_flat("fold_conv_bwd_data_kernel", fold_conv_bwd_data_kernel, s, tot, gf, raw_of(n->foldc[layer].w), g, C, P / 36, Tn, tot);
         } else {
             const long long total = static_cast<long long>(B) * C * 12 * Tn;
             rc = launch_flat("fold_bwd_kernel", fold_bwd_kernel, s, total, gfold, b.semi_raw[layer], b.aff_semi[layer], g, C, P / 36, Tn, g_ctot, g_coff, total);
@@ -633,7 +613,7 @@ struct Bwd {
             const long long HT = static_cast<long long>(P / 3) * Tn, total = static_cast<long long>(B) * C * HT;
             if ((rc = launch_flat("add_slice_kernel", add_slice_kernel, s, total, g, extra_g, C, HT, extra_ctot, total))) return rc;
         }
-        if ((rc = bn_block_backward(m + "pool_semi_b", g, b.semi_raw[layer], b.aff_semi[layer], C, 0, (P / 3) * Tn))) return rc;
+        if ((rc = bn_block_backward(semi.bn, g, b.semi_raw[layer], b.aff_semi[layer], C, 0, (P / 3) * Tn))) return rc;
         {
             const size_t cap = 160 * 1024;          // one workgroup per CU beyond 64 KB (--local clips: no time pooling, more frames)
             // frames staged at a time: the whole clip where it fits (one tile), else the most that fit (whole songs: 318 of 592 at 8 channels)
@@ -650,13 +630,13 @@ struct Bwd {
             const int want = (std::max(device_cus(), 1) + B * pair_groups - 1) / (B * pair_groups);     // workgroups per clip that fill the chip
             const int rows = std::min(kSemiRows, std::max(4, (S + want - 1) / want));
             if ((rc = ake::launch("semi_bwd_weight_kernel", semi_bwd_weight_kernel, dim3((S + rows - 1) / rows, B, pair_groups), dim3(256), lds, s, g, x, x_aff,
-                                  grad_of(m + "pool_semi.weight"), static_cast<long long>(n->grad_floats), C, P, Tn, rows, tile)))
+                                  grad_of(semi.w), static_cast<long long>(n->grad_floats), C, P, Tn, rows, tile)))
                 return rc;
         }
         if (!ga_x) return AKE_OK;
         const long long total = static_cast<long long>(B) * P * Tn;
         return ake::launch("semi_bwd_data_kernel", semi_bwd_data_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), sizeof(float) * C * C * 9, s, g,
-                           raw_of(m + "pool_semi.weight"), ga_x, C, P, Tn, total);
+                           raw_of(semi.w), ga_x, C, P, Tn, total);
     }
 };
 
