@@ -103,6 +103,8 @@ SYMBOLS = {
     "ake_key_posteriors_f32": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "ake_key_stream_state_bytes": (_SZ, [_I, _I]),
     "ake_key_stream_step_f32": (_I, [_P, _I, _I, _I64, _I, _I, _P, _P, _P, _SZ, _P, _P, C.POINTER(_I), _P]),
+    "ake_key_stream_posteriors_state_bytes": (_SZ, [_I, _I]),
+    "ake_key_stream_posteriors_f32": (_I, [_P, _P, _I, _I, _I64, _I, _I, _P, _P, _P, _P, _SZ, _P, _P, _P, C.POINTER(_I), _P]),
     "ake_stream_history_f32": (_I, [_P, _I, _I64, _I64, _I64, _P, _I64, _I64, _P]),
     "ake_stream_history_pcm16": (_I, [_P, _I, _I64, _I64, _I64, _P, _I64, _I64, _P]),
     "ake_stream_frames_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

@@ -25,7 +25,10 @@
 // A stream of audio is smoothed a call at a time by key_stream_step_kernel (ake_key_stream_step_f32): the Viterbi step and the forward
 // step on every new window, with d, a and a ring of the last `lag` back-pointer rows carried in device memory between calls, and a
 // fixed-lag path out of the ring.  The steps are device functions (viterbi_step, lse_step, states_lse, first_best_state) that the
-// Viterbi and the forward-backward kernel call too.  The stream's front end is csrc/stream.hip.
+// Viterbi and the forward-backward kernel call too.  The stream's front end is csrc/stream.hip.  Fixed-lag posteriors and a running
+// log-likelihood come from two launches behind the step (ake_key_stream_posteriors_f32): key_stream_sweep_kernel, a backward sweep of
+// at most `lag` steps per written window, and key_stream_loglik_kernel, which adds the new windows' c and keeps a second state -- the
+// last `lag` rows of e and of a -- for the sweeps of later calls.
 //
 // A track is scored against key annotations by track_score_kernel (one launch, integers only), below the posterior kernels.
 //
@@ -652,6 +655,165 @@ __global__ __launch_bounds__(64) void key_stream_step_kernel(StreamStepArgs a) {
         reinterpret_cast<float*>(st)[kKeys + lane] = f;
     }
     for (int x = lane; x < ring_quads; x += 64) reinterpret_cast<uint4*>(st + kStreamScores)[x] = ring_lds[x];
+}
+
+// ---- fixed-lag posteriors and the running log-likelihood of a stream (semantics: include/ake_hip.h; host model:
+// metrics.key_stream_posteriors) ----
+// A second state beside the step kernel's, per recording: the double sum of c (in a 16-byte piece of its own), then a ring of the last
+// `lag` emission rows and a ring of the last `lag` filtered rows, row w % lag for window w (one row each for lag 0: the forward step of
+// a call's first window needs a_{w-1} whatever the lag).
+constexpr int kStreamPostHead = 16;
+constexpr int stream_post_rows(int lag) { return lag > 0 ? lag : 1; }
+constexpr size_t stream_post_stride(int lag) {
+    return static_cast<size_t>(kStreamPostHead) + 2 * static_cast<size_t>(stream_post_rows(lag)) * kKeys * sizeof(float);
+}
+
+struct StreamPostArgs {
+    const float* emis;         // [recordings][k][24]: the new windows
+    const float* filtered;     // [recordings][k][24]: key_stream_step_kernel's a rows of the same windows
+    const float* trans;        // [24][24], from i (row) to j
+    const float* prior;        // [24], nullable = zeros
+    const int* path;           // [recordings][k_out], nullable
+    unsigned char* state;      // [recordings][stream_post_stride(lag)]
+    float* post;               // [recordings][k_out][24]
+    float* path_post;          // [recordings][k_out], nullable
+    float* loglik;             // [recordings][k], nullable
+    long long before;          // windows of the stream before this call
+    int k, lag, k_out;         // (a flush shows in k_out alone: its windows end at the last one, total - 1)
+};
+
+// One wave per (recording, written window v), in forward_backward_chain<true>'s layout: the backward sweep from the end window
+// s = min(v + lag, total - 1) down to v, at most `lag` steps of lse_step<true> / states_lse with b_s = 0, then softmax(a_v + b_v) over the
+// wave's 24 states.  A row of window u comes from the call's inputs (u >= before) or from the state's rings (u < before; never on a fresh
+// stream): the choice moves a pointer and nothing else, so a sweep's operations do not depend on how the stream was cut into calls.
+// The sweep's emission rows are loaded kVitBatch steps ahead, with clamped indices.  The kernel only reads the state.
+__global__ __launch_bounds__(64) void key_stream_sweep_kernel(StreamPostArgs a) {
+    __shared__ float4 d_lds[kKeys / 4];
+    const int r = blockIdx.x / a.k_out, x = blockIdx.x - r * a.k_out, lane = threadIdx.x, k = a.k, lag = a.lag;
+    constexpr int kHalf = kKeys / 2;
+    const int half = lane >> 5;
+    const bool own = (lane & 31) < kKeys, writer = lane < kKeys;
+    const int j = own ? lane & 31 : 0;
+    float A[kHalf];
+#pragma unroll
+    for (int i = 0; i < kHalf; ++i) A[i] = a.trans[j * kKeys + half * kHalf + i];
+    const float4* const dsrc = d_lds + half * (kHalf / 4);
+    const int rows = stream_post_rows(lag);
+    const float* const e_ring = reinterpret_cast<const float*>(a.state + static_cast<size_t>(r) * stream_post_stride(lag) + kStreamPostHead);
+    const float* const a_ring = e_ring + static_cast<size_t>(rows) * kKeys;
+    const long long before = a.before, total = before + k;
+    const long long v = (before > lag ? before - lag : 0) + x;           // the window this wave writes
+    const long long s = v + lag < total - 1 ? v + lag : total - 1;       // its end window (without a flush v + lag <= total - 1 anyway)
+    const int steps = static_cast<int>(s - v);                           // 0..lag
+    const size_t in0 = static_cast<size_t>(r) * k;
+    // the emission row step t = 1..steps adds: window s - t + 1, in v + 1..s (clamped into it; window s itself where there is no step)
+    auto step_e = [&](int t) {
+        const long long u = s + 1 - (t < 1 ? 1 : t > steps ? (steps > 0 ? steps : 1) : t);
+        const float* const row = u >= before ? a.emis + (in0 + static_cast<size_t>(u - before)) * kKeys : e_ring + static_cast<size_t>(u % rows) * kKeys;
+        return row[j];
+    };
+    const float av = (v >= before ? a.filtered + (in0 + static_cast<size_t>(v - before)) * kKeys : a_ring + static_cast<size_t>(v % rows) * kKeys)[j];
+    float d = 0.f;                                                       // b_s = 0
+    float eb[kVitBatch];
+#pragma unroll
+    for (int q = 0; q < kVitBatch; ++q) eb[q] = step_e(1 + q);
+    for (int t0 = 0; t0 < steps; t0 += kVitBatch) {
+        float en[kVitBatch];
+#pragma unroll
+        for (int q = 0; q < kVitBatch; ++q) en[q] = step_e(t0 + kVitBatch + 1 + q);
+#pragma unroll
+        for (int q = 0; q < kVitBatch; ++q) {
+            if (t0 + q >= steps) break;                                  // wave-uniform
+            const float raw = lse_step<true>(d, eb[q], d_lds, dsrc, A, writer, lane);
+            d = raw - states_lse(raw, own);
+        }
+#pragma unroll
+        for (int q = 0; q < kVitBatch; ++q) eb[q] = en[q];
+    }
+    const float xv = av + d;
+    const float ex = __expf(xv - states_max(xv, own));
+    const float p = ex / states_sum(ex, own);
+    const size_t out = static_cast<size_t>(r) * a.k_out + x;
+    if (writer) a.post[out * kKeys + lane] = p;
+    if (a.path_post) {
+        const int k0 = a.path[out];                                      // wave-uniform; -1 (or anything that is no key) gives 0
+        const float pp = __shfl(p, k0 >= 0 && k0 < kKeys ? k0 : 0);
+        if (lane == 0) a.path_post[out] = k0 >= 0 && k0 < kKeys ? pp : 0.f;
+    }
+}
+
+// One wave per recording, after the sweeps on the same stream: the only kernel that writes the state.  It recomputes c_w of every new
+// window through the step kernel's own forward step (lse_step<false> on a_{w-1}, + e_w, states_lse) -- the steps do not chain: a_{w-1}
+// is the filtered row the step kernel wrote, or the state's last one in front of the call's first window --, adds them in window order
+// to the double that forward_backward_chain keeps, writes the running sums, and moves the call's last rows into the rings.  A fresh
+// stream (before == 0) reads nothing from the state and writes all of it, zeros where no window has been.
+__global__ __launch_bounds__(64) void key_stream_loglik_kernel(StreamPostArgs a) {
+    __shared__ float4 f_lds[kKeys / 4];
+    const int r = blockIdx.x, lane = threadIdx.x, k = a.k, lag = a.lag;
+    constexpr int kHalf = kKeys / 2;
+    const int half = lane >> 5;
+    const bool own = (lane & 31) < kKeys, writer = lane < kKeys;
+    const int j = own ? lane & 31 : 0;
+    float A[kHalf];
+#pragma unroll
+    for (int i = 0; i < kHalf; ++i) A[i] = a.trans[(half * kHalf + i) * kKeys + j];
+    const float4* const fsrc = f_lds + half * (kHalf / 4);
+    const int rows = stream_post_rows(lag);
+    unsigned char* const st = a.state + static_cast<size_t>(r) * stream_post_stride(lag);
+    float* const e_ring = reinterpret_cast<float*>(st + kStreamPostHead);
+    float* const a_ring = e_ring + static_cast<size_t>(rows) * kKeys;
+    const long long before = a.before;
+    double ll = 0.0;
+    float f = a.prior ? a.prior[j] : 0.f;                                // window 0 adds its emissions to the prior
+    if (before > 0) {
+        ll = *reinterpret_cast<const double*>(st);
+        f = a_ring[static_cast<size_t>((before - 1) % rows) * kKeys + j];
+    }
+    const float* const e = a.emis + static_cast<size_t>(r) * k * kKeys;
+    const float* const fl = a.filtered + static_cast<size_t>(r) * k * kKeys;
+    float* const out = a.loglik ? a.loglik + static_cast<size_t>(r) * k : nullptr;
+    const int wl = k - 1;                                                // (k >= 1: the host launches nothing for k == 0)
+    float eb[kVitBatch], fb[kVitBatch];
+#pragma unroll
+    for (int q = 0; q < kVitBatch; ++q) {
+        const size_t at = static_cast<size_t>(q < wl ? q : wl) * kKeys + j;
+        eb[q] = e[at]; fb[q] = fl[at];
+    }
+    for (int i0 = 0; i0 < k; i0 += kVitBatch) {
+        float en[kVitBatch], fn[kVitBatch];
+#pragma unroll
+        for (int q = 0; q < kVitBatch; ++q) {
+            const int i = i0 + kVitBatch + q;
+            const size_t at = static_cast<size_t>(i < wl ? i : wl) * kKeys + j;
+            en[q] = e[at]; fn[q] = fl[at];
+        }
+#pragma unroll
+        for (int q = 0; q < kVitBatch; ++q) {
+            const int i = i0 + q;
+            if (i >= k) break;                                           // wave-uniform
+            float fr = f;
+            if (before + i > 0) fr = lse_step<false>(f, 0.f, f_lds, fsrc, A, writer, lane);
+            ll += static_cast<double>(states_lse(fr + eb[q], own));
+            if (out && lane == 0) out[i] = static_cast<float>(ll);
+            f = fb[q];                                                   // a_w, the bits the step kernel went on with
+        }
+#pragma unroll
+        for (int q = 0; q < kVitBatch; ++q) { eb[q] = en[q]; fb[q] = fn[q]; }
+    }
+    // the state: every read of it lies above
+    if (lane == 0) {
+        reinterpret_cast<double*>(st)[0] = ll;
+        if (before == 0) reinterpret_cast<double*>(st)[1] = 0.0;
+    }
+    const int m = k < rows ? k : rows;                                   // the call's last m windows are the ring's newest
+    for (int c = lane; c < m * kKeys; c += 64) {
+        const int i = k - m + c / kKeys, key = c - c / kKeys * kKeys;
+        const size_t to = static_cast<size_t>((before + i) % rows) * kKeys + key;
+        e_ring[to] = e[static_cast<size_t>(i) * kKeys + key];
+        a_ring[to] = fl[static_cast<size_t>(i) * kKeys + key];
+    }
+    if (before == 0)                                                     // rows 0..m-1 were just written: the rest has seen no window yet
+        for (int c = m * kKeys + lane; c < rows * kKeys; c += 64) e_ring[c] = a_ring[c] = 0.f;
 }
 
 struct PostArgs {
@@ -1481,6 +1643,42 @@ int ake_key_stream_step_f32(const float* emis_dev, int recordings, int k, int64_
                      static_cast<long long>(windows_before), k, lag, flush ? 1 : 0, static_cast<int>(n_out),
                      lag > 0 ? static_cast<int>(windows_before % lag) : 0};
     return ake::launch("key_stream_step_kernel", key_stream_step_kernel, dim3(recordings), dim3(64), 0, s, a);
+}
+
+size_t ake_key_stream_posteriors_state_bytes(int recordings, int lag) {
+    if (recordings <= 0 || lag < 0 || lag > kStreamMaxLag) return 0;
+    return static_cast<size_t>(recordings) * stream_post_stride(lag);
+}
+
+int ake_key_stream_posteriors_f32(const float* emis_dev, const float* filtered_dev, int recordings, int k, int64_t windows_before, int lag,
+                                  int flush, const float* log_trans_dev, const float* log_prior_dev, const int32_t* path_dev, void* state_dev,
+                                  size_t state_bytes, float* post_dev, float* path_post_dev, float* loglik_dev, int* k_out,
+                                  ake_stream_t stream) {
+    AKE_REQUIRE(lag >= 0 && lag <= kStreamMaxLag, AKE_ERR_INVALID, "key_stream_posteriors: lag %d outside 0..%d", lag, kStreamMaxLag);
+    AKE_REQUIRE(recordings > 0 && k >= 0 && windows_before >= 0 && static_cast<long long>(recordings) * k <= (1ll << 30), AKE_ERR_INVALID,
+                "key_stream_posteriors: bad shape (%d recordings, %d windows after %lld)", recordings, k, static_cast<long long>(windows_before));
+    AKE_REQUIRE(log_trans_dev && state_dev && k_out, AKE_ERR_INVALID, "key_stream_posteriors: null argument");
+    AKE_REQUIRE(!path_post_dev || path_dev, AKE_ERR_INVALID, "key_stream_posteriors: path_post_dev needs the path it reads (path_dev)");
+    // the step entry's count
+    const int64_t first = windows_before > lag ? windows_before - lag : 0, total = windows_before + k;
+    const int64_t n_out = (flush ? total : (total > lag ? total - lag : 0)) - first;
+    AKE_REQUIRE(n_out <= INT_MAX && static_cast<long long>(recordings) * n_out <= INT_MAX, AKE_ERR_INVALID,
+                "key_stream_posteriors: %lld windows to write", static_cast<long long>(n_out));
+    AKE_REQUIRE((k == 0 || (emis_dev && filtered_dev)) && (n_out == 0 || post_dev), AKE_ERR_INVALID, "key_stream_posteriors: null argument");
+    const size_t need = ake_key_stream_posteriors_state_bytes(recordings, lag);
+    AKE_REQUIRE(state_bytes >= need, AKE_ERR_WORKSPACE, "key_stream_posteriors: state %zu < %zu bytes", state_bytes, need);
+    AKE_REQUIRE((reinterpret_cast<uintptr_t>(state_dev) & 15) == 0, AKE_ERR_INVALID, "key_stream_posteriors: the state must be 16-byte aligned");
+    *k_out = static_cast<int>(n_out);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    StreamPostArgs a{emis_dev, filtered_dev, log_trans_dev, log_prior_dev, path_post_dev ? path_dev : nullptr,
+                     static_cast<unsigned char*>(state_dev), post_dev, path_post_dev, loglik_dev, static_cast<long long>(windows_before), k, lag,
+                     static_cast<int>(n_out)};
+    if (n_out > 0) {                                                     // the sweeps read the state of the calls before
+        const int rc = ake::launch("key_stream_sweep_kernel", key_stream_sweep_kernel, dim3(static_cast<unsigned>(recordings * n_out)), dim3(64), 0, s, a);
+        if (rc) return rc;
+    }
+    if (k == 0) return AKE_OK;                                           // no new window: the state stands
+    return ake::launch("key_stream_loglik_kernel", key_stream_loglik_kernel, dim3(recordings), dim3(64), 0, s, a);
 }
 
 size_t ake_key_sequence_loss_workspace_bytes(int recordings, int windows) {

@@ -425,6 +425,88 @@ def key_stream(emissions, log_trans, log_prior=None, lag=6, state=None, flush=Tr
     return filtered, path
 
 
+def key_stream_posteriors(emissions, log_trans, log_prior=None, lag=6, state=None, flush=True, return_state=False, path=None):
+    """Fixed-lag posteriors and the running log-likelihood of (R, W, 24) or (W, 24) ``emissions`` -> ``(post, loglik)``, or
+    ``(post, loglik, path_post)`` with ``path``.
+
+    The host model of ``ake_key_stream_posteriors_f32``, in torch ops, in the emissions' dtype.  ``log_trans``, ``log_prior`` and ``lag``
+    as in ``key_stream``.  With a_u ``key_stream``'s ``filtered`` rows and c_u what their steps subtract, window v's row is the posterior
+    given everything up to its end window s = v + lag (with ``flush``, for the windows still inside the lag: the last window)::
+
+        b_s[i] = 0
+        b_u[i] = LSE_j (A[i][j] + e[u+1][j] + b_{u+1}[j]);  b_u[i] -= LSE_i b_u[i]        u = s-1 .. v
+        post[v][j] = softmax_j (a_v[j] + b_v[j])
+
+    which is ``key_posteriors(e[:s + 1])[0][v]``: the evidence ``key_stream``'s label of window v was decided on.  ``post`` (R, k_out, 24)
+    holds the ``key_stream_count`` windows this call decides, as ``key_stream``'s path does; with ``lag`` 0 it is ``softmax(filtered)``.
+    ``loglik`` (R, W): ``loglik[w]`` = sum of c_u up to window w = ``key_posteriors(e[:w + 1])[1]``, added in a float64 and rounded to
+    the emissions' dtype on the way out.  ``path`` (R, k_out) or (k_out,), ``key_stream``'s path of the same call: ``path_post[v]`` =
+    ``post[v][path[v]]``, 0 where the path holds -1.
+
+    In pieces: ``state`` and ``return_state`` as in ``key_stream`` (the state: the last ``lag`` rows of e and of a, row w % lag for
+    window w -- one row for lag 0 --, and the float64 sum); the results do not depend on how the windows are cut into calls, to the
+    bit."""
+    single = emissions.dim() == 2
+    e = emissions[None] if single else emissions
+    if e.dim() != 3 or e.shape[2] != 24:
+        raise ValueError(f"key_stream_posteriors: emissions must be (R, W, 24) or (W, 24), got {tuple(emissions.shape)}")
+    lag = int(lag)
+    if not 0 <= lag <= 255:
+        raise ValueError(f"key_stream_posteriors: lag must lie in 0..255, got {lag}")
+    R, W, K = e.shape
+    dev = e.device
+    A = torch.as_tensor(log_trans).to(device=dev, dtype=e.dtype)
+    if A.shape != (K, K):
+        raise ValueError(f"key_stream_posteriors: log_trans must be (24, 24), got {tuple(A.shape)}")
+    prior = torch.zeros(K, device=dev, dtype=e.dtype) if log_prior is None else torch.as_tensor(log_prior).to(device=dev, dtype=e.dtype).reshape(K)
+    _check_finite("log_trans", A)
+    _check_finite("log_prior", prior)
+    _check_finite("emissions", e)
+    rows = max(lag, 1)
+    if state is None:
+        before = 0
+        e_ring, a_ring = e.new_zeros((rows, R, K)), e.new_zeros((rows, R, K))       # row w % rows: e_w, a_w
+        ll = torch.zeros((R,), device=dev, dtype=torch.float64)
+    else:
+        before, e_ring, a_ring, ll = state["windows"], state["e"].clone(), state["a"].clone(), state["loglik"].clone()
+    first_out, k_out = key_stream_count(before, W, lag, flush)
+    if path is not None:
+        path = torch.as_tensor(path, device=dev).to(torch.int64)
+        path = path[None] if single and path.dim() == 1 else path
+        if tuple(path.shape) != (R, k_out):
+            raise ValueError(f"key_stream_posteriors: path must hold the {k_out} windows this call decides, got {tuple(path.shape)}")
+    total = before + W
+    e_at = {u: e_ring[u % rows] for u in range(max(0, before - lag), before)}       # the rows a sweep may read, by window
+    a_at = {u: a_ring[u % rows] for u in range(max(0, before - lag), before)}
+    a = a_ring[(before - 1) % rows] if before > 0 else None
+    loglik = e.new_zeros((R, W))
+    for i in range(W):
+        w = before + i
+        fraw = prior[None, :] + e[:, 0] if w == 0 else e[:, i] + torch.logsumexp(a[:, :, None] + A[None, :, :], dim=1)
+        c = torch.logsumexp(fraw, dim=1)
+        a = fraw - c[:, None]
+        ll = ll + c.double()
+        loglik[:, i] = ll.to(e.dtype)
+        e_at[w], a_at[w] = e[:, i], a
+    post = e.new_zeros((R, k_out, K))
+    for v in range(first_out, first_out + k_out):                                  # one sweep per written window, each on its own
+        b = e.new_zeros((R, K))
+        for u in range(min(v + lag, total - 1) - 1, v - 1, -1):
+            raw = torch.logsumexp(A[None, :, :] + (e_at[u + 1] + b)[:, None, :], dim=2)
+            b = raw - torch.logsumexp(raw, dim=1, keepdim=True)
+        post[:, v - first_out] = torch.softmax(a_at[v] + b, dim=1)
+    for w in range(max(before, total - rows), total):
+        e_ring[w % rows], a_ring[w % rows] = e_at[w], a_at[w]
+    out = [post, loglik]
+    if path is not None:
+        out.append(torch.where(path >= 0, post.gather(2, path.clamp(min=0)[..., None])[..., 0], torch.zeros_like(post[..., 0])))
+    if single:
+        out = [t[0] for t in out]
+    if return_state:
+        out.append({"windows": total, "e": e_ring, "a": a_ring, "loglik": ll})
+    return tuple(out)
+
+
 def _transposition_classes():
     """(24, 24) int64: the class 0..47 of cell (i, j) under transposition -- (mode of i, mode of j, (t_j - t_i) mod 12); 12 cells each."""
     k = torch.arange(24)

@@ -533,7 +533,7 @@ class KeyEstimator:
     def stream(self, recordings: int, window_seconds: float = 15.0, stride_seconds: float = 5.0, smooth: bool = True, lag_windows: int = 6,
                mean_key_seconds: float = 60.0, transition: torch.Tensor | None = None, log_prior: torch.Tensor | None = None,
                signature_weight: float = 1.0, keep_frames: bool = False, max_chunk_samples: int | None = None, rate: int | None = None,
-               tuning=None):
+               tuning=None, posteriors: bool = False):
         """Track keys on audio as it arrives -> ``ake_amd.KeyStream``: ``push(chunk)`` takes the next (R, m) samples of all
         ``recordings`` = R recordings at once (float32, or int16 = 16-bit PCM; any m >= 0, the same m for every recording) and returns
         a ``StreamUpdate`` with the windows that chunk completed; ``finish()`` ends the recordings and returns the rest.
@@ -557,7 +557,14 @@ class KeyEstimator:
         ``mean_key_seconds`` as in ``track``; ``log_prior`` (24,), default zeros.  ``keep_frames=True`` keeps every final frame in
         ``KeyStream.frames`` (R, P, T), for tests and debugging.
 
-        Refused with a ``ValueError``: what ``track`` refuses (``frames=0``, ``wrap_mode="true_end"``, ``--local`` nets), an estimator
+        ``posteriors=True`` (with ``smooth=True``) adds what ``track(smooth=True, posteriors=True)`` has offline, at the same lag as the
+        path: ``posteriors`` (R, k2, 24), the probability of each key at window v given the audio up to window ``v + lag_windows`` --
+        ``metrics.key_posteriors`` on that prefix, the evidence the label of v was decided on; after ``finish()`` the last
+        ``lag_windows`` windows hold the offline posteriors --, ``smooth_confidence`` (R, k2), its entry at ``smooth_key_id``, and
+        ``log_likelihood`` (R, k), the running log-score of the recording under the transition after each new window
+        (``metrics.key_stream_posteriors``; two more launches a push, ``ake_key_stream_posteriors_f32``).
+
+        Refused with a ``ValueError``: ``posteriors=True`` with ``smooth=False``; what ``track`` refuses (``frames=0``, ``wrap_mode="true_end"``, ``--local`` nets), an estimator
         without a net, ``rate`` other than the estimator's and multi-channel chunks (the resampler keeps no state across chunks),
         ``tuning``, ``lag_windows`` outside 0..255; by ``push``: a chunk after ``finish()``, a chunk whose R or dtype differs from
         the first.  ``method="profile"`` streams do not exist."""
@@ -568,7 +575,7 @@ class KeyEstimator:
         if tuning is not None:
             raise ValueError("stream: tuning is not offered inside a stream (the estimate needs the whole recording)")
         return KeyStream(self, recordings, window_seconds, stride_seconds, smooth, lag_windows, mean_key_seconds, transition, log_prior,
-                         signature_weight, keep_frames, max_chunk_samples)
+                         signature_weight, keep_frames, max_chunk_samples, posteriors)
 
     def _refuse_untrackable(self):
         """What ``track`` and ``training_windows`` cannot slide windows over."""

@@ -2,7 +2,8 @@
 
 A stream takes the audio of R recordings in chunks, all R in lockstep, and emits ``KeyEstimator.track``'s windows exactly once each, as
 soon as every frame of a window is final; a smoother with carried state (``ake_key_stream_step_f32``, host model
-``metrics.key_stream``) adds the filtered key scores and a fixed-lag Viterbi path.  Every count is known on the host from the number of
+``metrics.key_stream``) adds the filtered key scores and a fixed-lag Viterbi path, and on request the fixed-lag posteriors and the
+running log-likelihood (``ake_key_stream_posteriors_f32``, host model ``metrics.key_stream_posteriors``).  Every count is known on the host from the number of
 samples pushed: a push reads nothing back from the device and waits for nothing.
 
 The geometry, as pure host functions (``H`` = ``ake_cqt_plan_half_support``: frame t depends on samples ``[t*hop - H, t*hop + H]``):
@@ -60,7 +61,10 @@ class StreamUpdate:
     ``confidence`` (R, k): as ``KeyTrack`` names them (``signature_id`` is ``KeyTrack.sig``).  ``times`` (k,) float64 on the host: window
     centres in seconds, as ``KeyTrack.times``.  A smooth stream adds ``emissions`` (R, k, 24), ``filtered`` (R, k, 24) -- the normalised
     log forward scores: ``exp`` is the probability of each key given the audio so far -- and the fixed-lag path ``smooth_key_id`` int32
-    (R, k2) for the k2 windows from ``smooth_first_window`` on that have left the lag; None on a stream without a smoother."""
+    (R, k2) for the k2 windows from ``smooth_first_window`` on that have left the lag; None on a stream without a smoother.  A stream
+    opened with ``posteriors=True`` adds ``posteriors`` (R, k2, 24) and ``smooth_confidence`` (R, k2) for those k2 windows -- the
+    probability of each key given the audio up to ``lag_windows`` windows later, and its entry at ``smooth_key_id`` -- and
+    ``log_likelihood`` (R, k), the running log-score after each new window; None otherwise."""
     first_window: int
     windows: int
     key: torch.Tensor
@@ -75,6 +79,9 @@ class StreamUpdate:
     filtered: torch.Tensor | None = None
     smooth_first_window: int | None = None
     smooth_key_id: torch.Tensor | None = None
+    posteriors: torch.Tensor | None = None
+    smooth_confidence: torch.Tensor | None = None
+    log_likelihood: torch.Tensor | None = None
 
     @staticmethod
     def concat(parts):
@@ -84,7 +91,8 @@ class StreamUpdate:
         cat = lambda name: None if getattr(parts[0], name) is None else torch.cat([getattr(p, name) for p in parts], dim=1)
         return StreamUpdate(parts[0].first_window, sum(p.windows for p in parts), cat("key"), cat("tonic"), cat("genre"), cat("key_id"),
                             cat("signature_id"), cat("tonic_id"), cat("confidence"), torch.cat([p.times for p in parts]), cat("emissions"),
-                            cat("filtered"), parts[0].smooth_first_window, cat("smooth_key_id"))
+                            cat("filtered"), parts[0].smooth_first_window, cat("smooth_key_id"), cat("posteriors"), cat("smooth_confidence"),
+                            cat("log_likelihood"))
 
 
 class KeyStream:
@@ -92,12 +100,12 @@ class KeyStream:
 
     Everything a push needs between calls is sized here, from R, the window geometry, ``lag_windows`` and ``max_chunk_samples``: the
     audio history (float32, ``2*H + hop + max_chunk_samples`` samples a recording), the transform's output and workspace, the two
-    halves of the frame cache, the net's workspace and the smoother's state.  After the first push a push allocates only the tensors
+    halves of the frame cache, the net's workspace, the smoother's state and, with ``posteriors``, the posteriors' state.  After the first push a push allocates only the tensors
     it returns (a chunk longer than ``max_chunk_samples`` is pushed as several pieces, whose updates are joined by one ``torch.cat``
     each).  ``push`` runs on the current stream."""
 
     def __init__(self, est, recordings, window_seconds=15.0, stride_seconds=5.0, smooth=True, lag_windows=6, mean_key_seconds=60.0,
-                 transition=None, log_prior=None, signature_weight=1.0, keep_frames=False, max_chunk_samples=None):
+                 transition=None, log_prior=None, signature_weight=1.0, keep_frames=False, max_chunk_samples=None, posteriors=False):
         R = int(recordings)
         if R < 1:
             raise ValueError("stream: recordings must be at least 1")
@@ -106,7 +114,9 @@ class KeyStream:
             raise ValueError(f"stream: lag_windows must lie in 0..255, got {lag_windows}")
         est._need_net("KeyEstimator.stream")
         est._refuse_untrackable()
-        self.est, self.R, self.lag, self.smooth = est, R, lag, bool(smooth)
+        if posteriors and not smooth:
+            raise ValueError("stream: posteriors=True needs smooth=True (the posteriors are the smoother's)")
+        self.est, self.R, self.lag, self.smooth, self.posteriors = est, R, lag, bool(smooth), bool(posteriors)
         dev = self.device = est.device
         L = _lib.lib()
         plan, net = est.plan, est.net
@@ -158,6 +168,9 @@ class KeyStream:
         self.state = None
         if self.smooth:
             self.state = torch.empty(max(int(L.ake_key_stream_state_bytes(R, lag)), 16), dtype=torch.uint8, device=dev)
+        self.post_state = None
+        if self.posteriors:
+            self.post_state = torch.empty(int(L.ake_key_stream_posteriors_state_bytes(R, lag)), dtype=torch.uint8, device=dev)
         self.keep_frames = bool(keep_frames)
         self._frames = [] if keep_frames else None
 
@@ -287,5 +300,18 @@ class KeyStream:
                                                          up.smooth_key_id.data_ptr() if k2 else None, C.byref(k_out), stream),
                                "ake_key_stream_step_f32")
                     assert k_out.value == k2
+                if self.posteriors:
+                    up.posteriors, up.smooth_confidence, up.log_likelihood = f32(R, k2, 24), f32(R, k2), f32(R, k)
+                    if k > 0 or k2 > 0:
+                        k_out = C.c_int(-1)
+                        _lib.check(L.ake_key_stream_posteriors_f32(up.emissions.data_ptr() if k else None, up.filtered.data_ptr() if k else None,
+                                                                   R, k, self.W, self.lag, int(finishing), self.trans.data_ptr(),
+                                                                   self.prior.data_ptr() if self.prior is not None else None,
+                                                                   up.smooth_key_id.data_ptr() if k2 else None, self.post_state.data_ptr(),
+                                                                   self.post_state.numel(), up.posteriors.data_ptr() if k2 else None,
+                                                                   up.smooth_confidence.data_ptr() if k2 else None,
+                                                                   up.log_likelihood.data_ptr() if k else None, C.byref(k_out), stream),
+                                   "ake_key_stream_posteriors_f32")
+                        assert k_out.value == k2
             self.W += k
         return up

@@ -541,6 +541,35 @@ int ake_key_stream_step_f32(const float* emis_dev, int recordings, int k, int64_
                             const float* log_trans_dev, const float* log_prior_dev, void* state_dev, size_t state_bytes,
                             float* filtered_dev, int32_t* path_dev, int* k_out, ake_stream_t stream);
 
+/* Fixed-lag posteriors and a running log-likelihood beside the step above: called right after it, on the same stream, with the same
+ * recordings, k, windows_before, lag and flush, on the same emis_dev and on the filtered_dev [recordings][k][24] the step wrote (both
+ * required with k > 0).  With a_u the filtered rows and c_u what their steps subtracted, window v with end window s runs
+ *   b_s[i] = 0
+ *   b_u[i] = LSE_j ( A[i][j] + e[u+1][j] + b_{u+1}[j] );  then b_u[i] -= LSE_i b_u[i]          u = s-1 .. v
+ *   post_v[j] = softmax_j ( a_v[j] + b_v[j] )
+ * in float32 and the log domain, as ake_key_posteriors_f32's backward chain (finite for what that accepts).  Window v is written once
+ * window s = v + lag has been stepped, so post_v is what ake_key_posteriors_f32 on windows 0..v + lag gives for it: the posterior given
+ * the evidence the step's label of v was decided on.  flush != 0: the windows still inside the lag end at the stream's last window and
+ * hold the posteriors of the whole recording.  lag 0: post = softmax(filtered).  The written windows are the step's: post_dev is
+ * [recordings][*k_out][24] and *k_out (a host integer, required) the step's formula.  path_dev int32 [recordings][*k_out] (nullable):
+ * the step's path_dev of the same call; path_post_dev [recordings][*k_out] (nullable) = post[r][v][path[r][v]], 0 where the path holds
+ * -1 -- path_post_dev without path_dev is AKE_ERR_INVALID.  loglik_dev [recordings][k] (nullable): the sum of c_u up to each new
+ * window, what ake_key_posteriors_f32 gives as loglik on windows 0..w; the sum is carried in a double and rounded on the way out.
+ * state_dev holds, per recording, that double (in a 16-byte piece), then the last `lag` rows of e and the last `lag` rows of a, row
+ * w % lag for window w (one row each for lag 0): ake_key_stream_posteriors_state_bytes(recordings, lag) bytes (0 for a bad shape),
+ * 16-byte aligned.  With windows_before == 0 it is not read, and written whole.  The device keeps no count.
+ * Launches: key_stream_sweep_kernel, one wave per (recording, written window), each running its <= lag backward steps on rows that
+ * exist before the launch (from the call's inputs or the state, which it only reads); then key_stream_loglik_kernel, one wave per
+ * recording, which recomputes c_w by the step's own forward step from a_{w-1} and e_w, adds them in window order, and moves the new
+ * rows into the state.  *k_out == 0 skips the first, k == 0 the second (the state stands); a call with neither launches nothing.
+ * No atomics: reruns are bit-identical, and results do not depend on how a stream's windows are cut into calls, to the bit.
+ * AKE_ERR_INVALID and AKE_ERR_WORKSPACE as the step entry's (filtered_dev as emis_dev, post_dev as its path_dev). */
+size_t ake_key_stream_posteriors_state_bytes(int recordings, int lag);
+int ake_key_stream_posteriors_f32(const float* emis_dev, const float* filtered_dev, int recordings, int k, int64_t windows_before,
+                                  int lag, int flush, const float* log_trans_dev, const float* log_prior_dev, const int32_t* path_dev,
+                                  void* state_dev, size_t state_bytes, float* post_dev, float* path_post_dev, float* loglik_dev,
+                                  int* k_out, ake_stream_t stream);
+
 /* The front end of a stream of audio in lockstep (csrc/stream.hip), both in one launch each, plain loads and stores, no atomics.
  * ake_stream_history_*: the audio history [recordings][history_stride] float32 moves `drop` samples to the front -- `keep` samples
  * survive, history[r][i] = history[r][i + drop] for i < keep -- and the m new samples of chunk_dev [recordings][chunk_stride] follow

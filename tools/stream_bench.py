@@ -14,7 +14,13 @@
   --accuracy: tools/track_accuracy.py's net and modulating recordings (one run on sine mixes): the fixed-lag path at lags 0, 3, 6, 12 scored
               as KeyTrack.score scores, beside the raw labels and the offline Viterbi path, at a 5 s stride.
 
-Usage: python tools/stream_bench.py [--pushes 200] [--accuracy]"""
+  --posteriors: this section alone.  est.stream(R, posteriors=True) at strides of 15 / 5 / 1 s and lags 6 and 30, fed 1 s chunks; once
+              every sweep runs its whole lag, --pushes pushes under the library's kernel timer: the two added launches
+              (key_stream_sweep_kernel, key_stream_loglik_kernel) per launch, beside key_stream_step_kernel's; and the host route on the
+              same pushes -- the emissions copied to the CPU, then metrics.key_stream_posteriors with its carried state -- per push that
+              completed a window, by the host clock.
+
+Usage: python tools/stream_bench.py [--pushes 200] [--accuracy] [--posteriors]"""
 import argparse
 import ctypes as C
 import importlib.util
@@ -22,6 +28,7 @@ import json
 import os
 import statistics
 import sys
+import time
 from argparse import Namespace
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -136,6 +143,42 @@ def smoother_rows():
     return rows
 
 
+def posteriors_rows(est, recordings, pushes):
+    rows = []
+    chunk = torch.randn((max(recordings), SR), device=DEV) * 0.3
+    names = ("key_stream_step_kernel", "key_stream_sweep_kernel", "key_stream_loglik_kernel")
+    for R in recordings:
+        for stride in (15.0, 5.0, 1.0):
+            for lag in (6, 30):
+                s = est.stream(R, stride_seconds=stride, lag_windows=lag, posteriors=True)
+                A = s.trans.cpu()
+                state = None
+                for _ in range(int(15 + (lag + 2) * stride) + 1):                    # warm: every sweep runs its whole lag from here on
+                    u = s.push(chunk[:R])
+                    if u.windows:
+                        *_, state = metrics.key_stream_posteriors(u.emissions.cpu(), A, lag=lag, state=state, flush=False, return_state=True)
+                torch.cuda.synchronize()
+                _lib.prof_enable("", True)
+                ups = [s.push(chunk[:R]) for _ in range(pushes)]
+                prof = _lib.prof_results()
+                _lib.prof_enable("", False)
+                host, worst = [], 0.0
+                for u in ups:
+                    if not u.windows:
+                        continue
+                    t0 = time.perf_counter()
+                    post, ll, state = metrics.key_stream_posteriors(u.emissions.cpu(), A, lag=lag, state=state, flush=False, return_state=True)
+                    host.append(1e3 * (time.perf_counter() - t0))
+                    worst = max(worst, float((post - u.posteriors.cpu()).abs().max()))
+                rows.append({"recordings": R, "stride_s": stride, "lag": lag, "pushes_with_window": len(host),
+                             "windows_per_such_push": round(sum(u.windows for u in ups) / max(1, len(host)), 2),
+                             "kernel_us_per_launch": {n: round(1e3 * prof[n][0] / prof[n][1], 2) for n in names if n in prof},
+                             "host_route_ms_per_push": round(statistics.median(host), 3) if host else None,
+                             "max_abs_diff_to_host_float32": worst})
+                del s
+    return rows
+
+
 def frame_rows(est):
     plan = est.plan
     H = int(_lib.lib().ake_cqt_plan_half_support(plan.handle))
@@ -185,6 +228,7 @@ def main():
     ap.add_argument("--baseline-reps", type=int, default=10)
     ap.add_argument("--recordings", type=int, nargs="+", default=[1, 16, 256])
     ap.add_argument("--accuracy", action="store_true")
+    ap.add_argument("--posteriors", action="store_true")
     args = ap.parse_args()
     torch.manual_seed(0)
     gold = np.load(os.path.join(REPO, "tests", "golden", "pcnet_default.npz"))
@@ -192,6 +236,10 @@ def main():
     net = ake_amd.PitchClassNet(288, 12, 2, 7, Namespace(genre=True))
     net.load_state_dict(sd, strict=True)
     est = ake_amd.KeyEstimator(net.to(DEV).eval(), SR, 5)
+    if args.posteriors:
+        print(json.dumps({"device": torch.cuda.get_device_name(0), "pushes": args.pushes, "chunk_s": 1.0,
+                          "posteriors": posteriors_rows(est, args.recordings, args.pushes)}))
+        return
     rows = [push_row(est, R, chunk, dtype, args.pushes, args.baseline_reps)
             for R in args.recordings for chunk in (HOP, SR) for dtype in (torch.float32, torch.int16)]
     H, frames = frame_rows(est)
