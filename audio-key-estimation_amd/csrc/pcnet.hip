@@ -810,7 +810,7 @@ bool pc2pc_fuses(const ake_pcnet* n, int i, int T) {
     if (!pc2pc_uses_bf16(n, i, T) || T % 4 || 12 * T > 1024 || 3 * ((T + 15) / 16) > 16) return false;   // (16 waves: 3 row groups x 16-frame tiles)
     for (const ConvSite& cs : n->pc2pc[i])
         if (cs.eval.cout != 16 || cs.eval.cin > 16 || cs.eval.kh != 12) return false;
-    return (static_cast<size_t>(4) * 12 * (T + 8) * 2 + 2 * 512) * sizeof(uint4) <= 160 * 1024;     // two maps + the weight ring
+    return pc2pc_fused_lds_bytes(T) <= 160 * 1024;                                                  // two maps + the weight ring
 }
 
 int run_pc2pc_fused(const ake_pcnet* n, int i, const float* src, int cin, int batch, int T, float* pooled, unsigned short* feat_cl, hipStream_t s) {
@@ -822,7 +822,7 @@ int run_pc2pc_fused(const ake_pcnet* n, int i, const float* src, int cin, int ba
     a.pooled = pooled;
     if (feat_cl) { a.fh = feat_cl; a.fl = feat_cl + static_cast<long long>(batch) * 12 * (T / 2) * 16; }
     a.T = T; a.Tp = T + 8;
-    const size_t lds = (static_cast<size_t>(4) * 12 * a.Tp * 2 + 2 * 512) * sizeof(uint4);
+    const size_t lds = pc2pc_fused_lds_bytes(T);
     static ake::DeviceOnce attr_set;
     const int rc = ake::raise_lds_limit(attr_set, 160 * 1024, pc2pc_fused_kernel);
     if (rc) return rc;

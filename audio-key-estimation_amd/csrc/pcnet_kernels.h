@@ -21,6 +21,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "bf16_split.h"   // bf16_bits, bf16_split2
 #include "common.h"
 
 namespace ake_k {
@@ -112,12 +113,6 @@ struct ShiftStat {
 __device__ __forceinline__ long long shfl_xor_ll(long long v, int o) {
     const int lo = __shfl_xor(static_cast<int>(v & 0xffffffffll), o), hi = __shfl_xor(static_cast<int>(v >> 32), o);
     return (static_cast<long long>(hi) << 32) | static_cast<unsigned int>(lo);
-}
-
-// float -> bf16 bits, round to nearest even (finite inputs)
-__device__ __forceinline__ unsigned int bf16_bits(float v) {
-    const unsigned int u = __float_as_uint(v);
-    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
 }
 
 __device__ __forceinline__ int wrap(int i, int n) {
@@ -1771,7 +1766,24 @@ __global__ __launch_bounds__(512) void conv_pc_bf16_kernel(PcBfArgs a) {
 // k-step pair as the outer loop; it shares no code with it), and the last epilogue takes the max over frame pairs in registers and writes the pooled features twice: NCHW f32 (taps, f32 heads) and channels-last planes (bf16 heads).
 // Measured on the per-conv launches (phases switched off one at a time): 13 us of launch + epilogue and 4 us of patch load per
 // 21 us of MFMA loop, three times, plus the conversion and pooling passes.
+//
+// The weight fragments travel in chunks of 8 KB (one k-step pair p of four kernel rows, 12 chunks per conv) through a ring of
+// kPc2pcRingSlots = 3 slots in LDS, fetched once per workgroup by LDS-DMA (ake::lds_dma_16, no registers) TWO chunks ahead of their
+// MFMAs: while chunk c is multiplied out of registers, every wave refills a kernel row's fragment registers with chunk c + 1's as that
+// row retires, and chunk c + 2 lands in the third slot.  A wave waits for its own DMA pieces in front of the chunk's barrier, so behind
+// the barrier the next MFMA's operands are already in registers.  The chunks of the launch form one sequence: the convs hand the
+// ring over without a drain (12 chunks per conv and 3 slots: chunk c of every conv lives in slot c % 3).
+// Only the halo frames of the four planes are zeroed (8 of T + 8 frames per row): the input conversion and the epilogues write every
+// channel of every other frame before a conv reads it.
 // ==========================================================================================
+constexpr int kPc2pcRingSlots = 3;
+constexpr int kPc2pcChunk = 4 * 2 * 64;                                       // uint4 per ring chunk: 4 kernel rows x (hi | lo) x 64 lanes
+__host__ __device__ constexpr int pc2pc_plane_u4(int T) { return 12 * (T + 8) * 2; }     // uint4 per plane (two maps x (hi | lo) = four planes)
+// dynamic LDS of the launch: pc2pc_fuses, run_pc2pc_fused and the kernel's own layout all come from these
+__host__ __device__ constexpr size_t pc2pc_fused_lds_bytes(int T) {
+    return (static_cast<size_t>(4) * pc2pc_plane_u4(T) + kPc2pcRingSlots * kPc2pcChunk) * sizeof(uint4);
+}
+
 struct Pc2pcFusedArgs {
     const float* src;             // NCHW f32 [clip][cin][12][T]
     long long src_clip_stride;
@@ -1792,46 +1804,68 @@ __global__ __launch_bounds__(1024) void pc2pc_fused_kernel(Pc2pcFusedArgs a) {
     const int r16 = lane & 15, q = lane >> 4;
     const int T = a.T, Tp = a.Tp;
     constexpr int MT = 4;
-    const int n16 = 12 * Tp * 2;                              // uint4 per plane
+    const int n16 = pc2pc_plane_u4(T);                        // uint4 per plane
     uint4* const map0 = lds4;                                 // two maps, each: hi plane, lo plane
     uint4* const map1 = lds4 + 2 * n16;
-    // weight fragments of one kernel row dy (4 k-steps x (hi | lo) x 64 lanes = 8 KB), double-buffered: the workgroup fetches every
-    // fragment ONCE and its 16 waves read it from here.  Streamed per wave from L1 they were 16 x 2 KB per k-step -- two thirds of the
-    // L1's 64 B / clk next to 768 cycles of MFMAs -- and 49 of the launch's 130 us (measured by leaving the loads out)
+    // weight fragments, a ring of three chunks of 8 KB: the workgroup fetches every fragment ONCE and its 16 waves read it from here.
+    // Streamed per wave from L1 they were 16 x 2 KB per k-step -- two thirds of the L1's 64 B / clk next to 768 cycles of MFMAs -- and
+    // 49 of the launch's 130 us (measured by leaving the loads out)
     uint4* const wring = lds4 + 4 * n16;
-    constexpr int kRow = 4 * 2 * 64;                          // uint4 per kernel row
-    for (int i = threadIdx.x; i < 4 * n16; i += 1024) lds4[i] = make_uint4(0, 0, 0, 0);
-    // ring chunk c = (p = c / 3, dq = c % 3): the fragments of k-step pair p of kernel rows 4 dq .. 4 dq + 3, [i][hi | lo][64 lanes];
-    // thread x < 512 copies fragment (i = x >> 7, h = (x >> 6) & 1, lane x & 63) from the packed order [dy][p][h][lane]
-    const int wsrc0 = (((threadIdx.x >> 7) * 4) * 2 + ((threadIdx.x >> 6) & 1)) * 64 + (threadIdx.x & 63);
-    auto wsrc = [&](int p, int dq) { return wsrc0 + (16 * dq * 2 + p * 2) * 64; };
-    if (threadIdx.x < kRow) wring[threadIdx.x] = a.bfrag[0][wsrc(0, 0)];
-    __syncthreads();
-    {   // input: NCHW f32 -> split channels-last, frame t at patch position t + 3
+    // ring chunk c = (p = c / 3, dq = c % 3), in slot dq: the fragments of k-step pair p of kernel rows 4 dq .. 4 dq + 3,
+    // [i][hi | lo][64 lanes], from the packed order [dy][p][h][lane].  Eight DMA pieces of 64 lanes x 16 bytes, piece (i, h) requested
+    // by wave 2 i + h of the lower or the upper eight waves, in turns.  Nothing waits here.
+    const unsigned int ring_lds = static_cast<unsigned int>(reinterpret_cast<unsigned long long>(wring));
+    auto request = [&](const uint4* bfr, int p, int dq) {
+        if ((wave >> 3) == ((p + dq) & 1)) {
+            const int piece = wave & 7;                       // (i = piece >> 1, h = piece & 1)
+            ake::lds_dma_16(bfr + (((4 * dq + (piece >> 1)) * 4 + p) * 2 + (piece & 1)) * 64 + lane,
+                            ring_lds + static_cast<unsigned int>((dq * kPc2pcChunk + piece * 64) * sizeof(uint4)));
+        }
+    };
+    request(a.bfrag[0], 0, 0);
+    request(a.bfrag[0], 0, 1);
+    {   // input: NCHW f32 -> split channels-last, frame t at patch position t + 3.  Every load is requested before the first is used:
+        // no guard around a load (out-of-range items and channels >= cin read a valid address and are dropped afterwards)
         const float* src = a.src + clip * a.src_clip_stride;
-        for (int i = threadIdx.x; i < 12 * T * 2; i += 1024) {
+        const int nitem = 12 * T * 2;                         // (position, half of the channels): at most 2 per thread
+        float xin[2][8];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int i = min(static_cast<int>(threadIdx.x) + 1024 * r, nitem - 1);
+            const int half = i & 1, pos = i >> 1;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) xin[r][k] = src[min(half * 8 + k, a.cin - 1) * (12 * T) + pos];
+        }
+        // the halo: frames 0 .. 2 and T + 3 .. T + 7 of every row of the four planes, 16 uint4 per row, while the loads travel
+        if (threadIdx.x < 4 * 12 * 16) {
+            const int plane = threadIdx.x / 192, rem = threadIdx.x - plane * 192;
+            const int row = rem >> 4, k = rem & 15;
+            lds4[plane * n16 + row * Tp * 2 + (k < 6 ? k : (T + 3) * 2 + k - 6)] = make_uint4(0, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int i = threadIdx.x + 1024 * r;
             const int half = i & 1, pos = i >> 1;
             const int y = pos / T, t = pos - y * T;
-            unsigned int hi[4] = {0, 0, 0, 0}, lo[4] = {0, 0, 0, 0};
+            unsigned int hi[4], lo[4];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int c = half * 8 + k;
-                const float v = c < a.cin ? src[(static_cast<long long>(c) * 12 + y) * T + t] : 0.f;
-                const unsigned int hb = bf16_bits(v);
-                hi[k >> 1] |= hb << (16 * (k & 1));
-                lo[k >> 1] |= bf16_bits(v - __uint_as_float(hb << 16)) << (16 * (k & 1));
+            for (int k = 0; k < 8; k += 2)
+                bf16_split2(half * 8 + k < a.cin ? xin[r][k] : 0.f, half * 8 + k + 1 < a.cin ? xin[r][k + 1] : 0.f, hi[k >> 1], lo[k >> 1]);
+            if (i < nitem) {
+                const int idx = ((y * Tp + t + 3) << 1) + half;
+                map0[idx] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
+                map0[n16 + idx] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
             }
-            const int idx = ((y * Tp + t + 3) << 1) + half;
-            map0[idx] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-            map0[n16 + idx] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
         }
     }
+    __builtin_amdgcn_s_waitcnt(0x0F70);                      // vmcnt(0): this wave's pieces of chunks 0 and 1 have landed
     __syncthreads();
     // Wave = (16-frame tile tt, four output rows y0 .. y0 + 3).  Output row y at kernel row dy reads input row (y + dy) % 12, so the
     // A fragment tile mt used at dy is the one tile mt + 1 used at dy - 1: per kernel row ONE new fragment pair is read from LDS, not
     // four (the multiply loop was bound by its A-fragment reads: 10 ds_read_b128 per 12 MFMAs, 1 280 LDS cycles per CU next to 768
     // matrix cycles; now 4 per 12).  The k-step pair p is the outer loop -- the four slots hold one p -- and the weight ring moves
-    // in chunks of (p, four kernel rows).
+    // in chunks of (p, four kernel rows).  The new pair is requested as soon as tile 0 has issued its third product, nine MFMAs into the
+    // row, and first used four MFMAs into the next one.
     const int n_tt = (T + 15) >> 4;
     const bool active = wave < 3 * n_tt;
     const int tt = wave / 3, y0 = 4 * (wave - 3 * tt);
@@ -1850,6 +1884,16 @@ __global__ __launch_bounds__(1024) void pc2pc_fused_kernel(Pc2pcFusedArgs a) {
     float* const pooled_c = a.pooled + static_cast<long long>(clip) * 16 * 12 * Tf;
     unsigned short* const fh_c = a.fh ? a.fh + static_cast<long long>(clip) * 12 * Tf * 16 : nullptr;
     unsigned short* const fl_c = a.fh ? a.fl + static_cast<long long>(clip) * 12 * Tf * 16 : nullptr;
+    // the weight fragments of the chunk being multiplied, [kernel row i][hi | lo]: chunk 0's now, and from then on row i's are replaced
+    // by the next chunk's as soon as row i's MFMAs are issued (across p and across the convs: one sequence of chunks)
+    uint4 bw[4][2];
+    if (active) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            bw[i][0] = wring[(i * 2 + 0) * 64 + lane];
+            bw[i][1] = wring[(i * 2 + 1) * 64 + lane];
+        }
+    }
     for (int j = 0; j < a.n_conv; ++j) {
         const uint4* const pH = (j & 1) ? map1 : map0;
         const uint4* const pL = pH + n16;
@@ -1866,7 +1910,6 @@ __global__ __launch_bounds__(1024) void pc2pc_fused_kernel(Pc2pcFusedArgs a) {
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4c{0.f, 0.f, 0.f, 0.f};
             bf16x8c fh[4], fl[4];                             // slot s: input row y0 + (fragment index == s mod 4)
-            int c = 0;
             // one k-step pair p: three ring chunks of four kernel rows.  PAIR (p == 3): the paired seventh taps -- even kernel rows only,
             // the fragments move two slots per step
             auto run_p = [&](auto pair_c, const int p) __attribute__((always_inline)) {
@@ -1880,37 +1923,61 @@ __global__ __launch_bounds__(1024) void pc2pc_fused_kernel(Pc2pcFusedArgs a) {
                     }
                 }
 #pragma unroll 1
-                for (int dq = 0; dq < 3; ++dq, ++c) {
-                    // the next chunk's fragments travel to registers during this chunk's MFMAs and into the other half of the ring after them
-                    uint4 wpre = make_uint4(0, 0, 0, 0);
-                    const bool fetch = threadIdx.x < kRow && (c + 1 < 12 || j + 1 < a.n_conv);
-                    if (fetch) wpre = c + 1 < 12 ? bfrag_j[dq < 2 ? wsrc(p, dq + 1) : wsrc(p + 1, 0)] : bfrag_n[wsrc(0, 0)];
-                    const uint4* const wr = wring + (c & 1) * kRow + lane;
+                for (int dq = 0; dq < 3; ++dq) {
+                    // chunk c = 3 p + dq is multiplied; chunk c + 2 is requested into the slot chunk c - 1 left (every wave has had
+                    // c - 1's fragments in registers since the last barrier but one); past this conv's twelve it is the next conv's
+                    // chunk 0 or 1, which belongs in the same slot (12 chunks, 3 slots)
+                    {
+                        const int dq2 = dq == 0 ? 2 : dq - 1, p2 = p + (dq > 0);
+                        if (!PAIR || dq == 0) request(bfrag_j, p2, dq2);
+                        else if (j + 1 < a.n_conv) request(bfrag_n, 0, dq2);
+                    }
+                    // chunk c + 1, landed and published by the last barrier
+                    const uint4* const wn = wring + (dq == 2 ? 0 : dq + 1) * kPc2pcChunk + lane;
                     if (active) {
 #pragma unroll
                         for (int i = 0; i < 4; i += PAIR ? 2 : 1) {   // kernel row dy = 4 dq + i: tile mt reads fragment dy + mt = slot (mt + i) & 3
-                            const bf16x8c bh = __builtin_bit_cast(bf16x8c, wr[(i * 2 + 0) * 64]), bl = __builtin_bit_cast(bf16x8c, wr[(i * 2 + 1) * 64]);
+                            const bf16x8c bh = __builtin_bit_cast(bf16x8c, bw[i][0]), bl = __builtin_bit_cast(bf16x8c, bw[i][1]);
+                            // (worked out in front of the row's MFMAs.  No branch: the last rows of a p, which need no further fragment,
+                            //  read the last one again into slots that are dead by then)
+                            int off_new[PAIR ? 2 : 1];
+#pragma unroll
+                            for (int u = 0; u < (PAIR ? 2 : 1); ++u) off_new[u] = frag_off(min(4 * dq + i + 4 + u, 12 + MT - (PAIR ? 2 : 1) - 1), PAIR ? 3 : p);
 #pragma unroll
                             for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[(mt + i) & 3], bh, acc[mt], 0, 0, 0);
 #pragma unroll
                             for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fl[(mt + i) & 3], bh, acc[mt], 0, 0, 0);
+                            // Slot i (tile 0's; PAIR: and slot i + 1, tile 1's) is free as soon as that tile's third product is issued:
+                            // the fragment(s) the next step's last tile(s) need are requested there, not behind the row
+                            constexpr int kFree = PAIR ? 2 : 1;
 #pragma unroll
-                            for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[(mt + i) & 3], bl, acc[mt], 0, 0, 0);
-                            // slot i (tile 0's; PAIR: and slot i + 1, tile 1's) is free: the fragment(s) the next step's last tile(s) need
+                            for (int mt = 0; mt < kFree; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[(mt + i) & 3], bl, acc[mt], 0, 0, 0);
 #pragma unroll
-                            for (int u = 0; u < (PAIR ? 2 : 1); ++u) {
-                                const int s_new = 4 * dq + i + 4 + u;
-                                if (s_new < 12 + MT - (PAIR ? 2 : 1)) {
-                                    const int off = frag_off(s_new, PAIR ? 3 : p);
-                                    fh[i + u] = __builtin_bit_cast(bf16x8c, pH[off]);
-                                    fl[i + u] = __builtin_bit_cast(bf16x8c, pL[off]);
-                                }
+                            for (int u = 0; u < kFree; ++u) {
+                                fh[i + u] = __builtin_bit_cast(bf16x8c, pH[off_new[u]]);
+                                fl[i + u] = __builtin_bit_cast(bf16x8c, pL[off_new[u]]);
+                            }
+                            __builtin_amdgcn_sched_barrier(0);   // (left alone, hipcc sinks these reads to one MFMA in front of their use)
+#pragma unroll
+                            for (int mt = kFree; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[(mt + i) & 3], bl, acc[mt], 0, 0, 0);
+                            // ... and this row's weight registers take the next chunk's (PAIR: the odd row's too, which the chunk
+                            // after the paired ones needs; behind the launch's last chunk they read a stale slot, unused)
+#pragma unroll
+                            for (int u = 0; u < kFree; ++u) {
+                                bw[i + u][0] = wn[((i + u) * 2 + 0) * 64];
+                                bw[i + u][1] = wn[((i + u) * 2 + 1) * 64];
                             }
                         }
                     }
-                    // (12 chunks: chunk 11 read half 1, so the next convolution's chunk 0 lands in half 0, where it expects it)
-                    if (fetch) wring[((c + 1) & 1) * kRow + threadIdx.x] = wpre;
-                    if (c + 1 < 12) __syncthreads();          // (after the last chunk the barrier at the end of the convolution serves)
+                    // This wave's pieces of chunk c + 2 have landed; behind the barrier everybody's have.  No LDS wait: the refills
+                    // above stay in flight across the barrier (their slot is requested again two barriers on, behind the MFMAs that
+                    // consume them).  After the conv's last chunk the barrier behind the epilogue serves.
+                    // (the wait as a builtin: a wait hidden in inline asm leaves hipcc believing the prologue's loads in flight, and
+                    //  it then drains vmcnt in the middle of every chunk; the bare barrier in asm: no LDS wait comes with it)
+                    if (!PAIR || dq < 2) {
+                        __builtin_amdgcn_s_waitcnt(0x0F70);
+                        asm volatile("s_barrier" ::: "memory");
+                    }
                 }
             };
 #pragma unroll 1
@@ -1922,9 +1989,12 @@ __global__ __launch_bounds__(1024) void pc2pc_fused_kernel(Pc2pcFusedArgs a) {
             const float bias = bias_j[co];
             const int tq0 = t0 + 4 * q;
             if (tq0 < T) {
+                // the offsets of (row y0, frame tq0, channel co) walk on: 16 shorts per frame, a row of the map per tile
+                int e = ((y0 * Tp + tq0 + 3) << 4) + co;                 // map: [row][Tp][16]
+                int g = (co * 12 + y0) * Tf + (tq0 >> 1);                // pooled, NCHW: [16][12][Tf]
+                int ec = (y0 * Tf + (tq0 >> 1)) * 16 + co;               // pooled, channels-last: [12][Tf][16]
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                    const int y = y0 + mt;
+                for (int mt = 0; mt < MT; ++mt, e += Tp * 16, g += Tf, ec += Tf * 16) {
                     float v[4];
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
@@ -1933,30 +2003,34 @@ __global__ __launch_bounds__(1024) void pc2pc_fused_kernel(Pc2pcFusedArgs a) {
                     }
                     if (!last) {
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const int e = ((((y * Tp + tq0 + i + 3) << 1) + (co >> 3)) << 3) + (co & 7);
-                            const unsigned int hb = bf16_bits(v[i]);
-                            oH[e] = static_cast<unsigned short>(hb);
-                            oL[e] = static_cast<unsigned short>(bf16_bits(v[i] - __uint_as_float(hb << 16)));
+                        for (int i = 0; i < 4; i += 2) {
+                            unsigned int hi, lo;
+                            bf16_split2(v[i], v[i + 1], hi, lo);
+                            oH[e + 16 * i] = static_cast<unsigned short>(hi);
+                            oH[e + 16 * i + 16] = static_cast<unsigned short>(hi >> 16);
+                            oL[e + 16 * i] = static_cast<unsigned short>(lo);
+                            oL[e + 16 * i + 16] = static_cast<unsigned short>(lo >> 16);
                         }
                     } else {                                             // nn.MaxPool2d((1, 2)), models.py:396
-#pragma unroll
-                        for (int i = 0; i < 4; i += 2) {
-                            const float pv = fmaxf(v[i], v[i + 1]);
-                            const int tq = (tq0 + i) >> 1;
-                            pooled_c[(co * 12 + y) * Tf + tq] = pv;      // (uniform clip base + 32-bit offsets: few address registers)
-                            if (a.fh) {
-                                const int e = (y * Tf + tq) * 16 + co;
-                                const unsigned int hb = bf16_bits(pv);
-                                fh_c[e] = static_cast<unsigned short>(hb);
-                                fl_c[e] = static_cast<unsigned short>(bf16_bits(pv - __uint_as_float(hb << 16)));
-                            }
+                        const float pv0 = fmaxf(v[0], v[1]), pv1 = fmaxf(v[2], v[3]);
+                        pooled_c[g] = pv0;                               // (uniform clip base + 32-bit offsets: few address registers)
+                        pooled_c[g + 1] = pv1;
+                        if (a.fh) {
+                            unsigned int hi, lo;
+                            bf16_split2(pv0, pv1, hi, lo);
+                            fh_c[ec] = static_cast<unsigned short>(hi);
+                            fh_c[ec + 16] = static_cast<unsigned short>(hi >> 16);
+                            fl_c[ec] = static_cast<unsigned short>(lo);
+                            fl_c[ec + 16] = static_cast<unsigned short>(lo >> 16);
                         }
                     }
-            }
+                }
             }
             }
         }
+        // the next conv's chunk 1, requested during this conv's last chunk, has landed (not behind the last conv: nothing is in
+        // flight there but the stores of the result)
+        if (!last) __builtin_amdgcn_s_waitcnt(0x0F70);
         __syncthreads();
     }
 }
