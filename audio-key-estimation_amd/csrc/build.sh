@@ -7,7 +7,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-result"
 BUILD=build
 mkdir -p $BUILD
-HEADERS="common.h bf16_split.h philox.h keys.h cqt_stream.h pcnet_kernels.h pcnet_bwd_kernels.h pcnet_backward.h ../../include/ake_hip.h"
+HEADERS="common.h bf16_split.h philox.h keys.h cqt_stream.h pcnet_kernels.h pcnet_bwd_kernels.h pcnet_net.h pcnet_plan.h pcnet_forward.h pcnet_backward.h ../../include/ake_hip.h"
 pids=()
 for f in common.cpp cqt.hip pcnet.hip pipeline.hip optim.hip audio.hip loss.hip track.hip smooth.hip synth.hip tuning.hip profile.hip stream.hip; do
   obj=$BUILD/${f%.*}.o

@@ -1,4 +1,6 @@
-// PitchClassNet forward on gfx950: handle, weight registry, BatchNorm folding, packing, launch plan.
+// PitchClassNet on gfx950, host side: BatchNorm folding, packing, the per-kernel launchers and the C entries.  One translation unit; the
+// handle (pcnet_net.h), workspace carve and route (pcnet_plan.h), forward (pcnet_forward.h) and backward pass (pcnet_backward.h) are
+// included where they stood.
 //
 // Replaces PitchClassNet.forward (models.py:747-817) for the default architecture family
 // (models.py:190-197, 227-234, 311-350).  Channel algebra follows models.py:279-308 / 693-710.
@@ -27,146 +29,9 @@
 
 using namespace ake_k;
 
-namespace {
-
-constexpr double kBnEps = 1e-5;          // nn.BatchNorm2d default
-constexpr size_t kLdsBudget = 64 * 1024; // dynamic LDS per workgroup we allow ourselves
-constexpr size_t kBfFragsPerConv = 14 * 2 * 64 + 64;   // uint4 entries per 8->8 pitch convolution: f16 weight fragments [14 k-steps][hi|lo][64 lanes], then the 8 inverse channel scales
-
-struct TensorSpec {
-    std::string name;
-    int64_t shape[4];
-    int ndim;
-};
-
-struct HostTensor {
-    std::vector<float> data;
-    bool set = false;
-};
-
-struct PackedConv {          // device-resident folded + packed convolution
-    int cin = 0, cout = 0, kh = 0, kw = 0, co = 1, groups = 1;
-    size_t w_off = 0, b_off = 0;   // float offsets into the blob (VALU layout [group][ci][dy][dx][CO])
-    // f32-MFMA fragment layout [ci][dy][s][ntile][64 lanes] (Toeplitz over TB frames), see pcnet_kernels.h
-    int tb = 0, ku = 0, ntiles = 0, nt = 1;
-    int row_k = 0;                 // 1: 12 x 1 kernel in the row-k fragment form (k = four consecutive rows, kh / 4 steps per channel)
-    size_t f_off = 0;
-    long long bf_off = -1;         // 16-byte offset of the bf16x3 fragments in ake_pcnet::bf_frags_dev (8 -> 8 channel 7x7 pitch convs), or -1
-    long long l0_off = -1;         // ... of the layer-0 form (layer0_mfma_kernel: <= 4 channels, 12 x 7), or -1
-    long long bf_off2 = -1;        // ... of input channels [16, 32) of a 32-channel data-gradient pack (heads' first conv, f16 x 3), or -1
-};
-
-struct LayerDims {
-    int prev_p = 0, prev_pc = 0, out_p = 0, out_pc = 0;
-};
-
-// --denseblock: one _DenseLayer / _DenseLayerEquivariant (models.py:456-582).  Both convolutions keep their raw weights; the BatchNorm +
-// activation in FRONT of each is a row table (scale, shift, negative slope) in ake_pcnet::dense_aff_dev that the kernel applies on load.
-struct DensePack {
-    PackedConv c1, c2;       // 1-wide bottleneck (stored as 7 taps, centre one non-zero), k-wide convolution
-    size_t aff1 = 0, aff2 = 0;   // float offsets of the two (eval-mode) tables
-    // training: the two BatchNorm layers (indices into ake_pcnet::bns), the data-gradient packs (transposed + flipped weights, stored like c1 / c2)
-    // and the parameters (indices into ake_pcnet::specs)
-    int bn1 = -1, bn2 = -1;
-    PackedConv d1, d2;
-    int w1 = -1, b1 = -1, w2 = -1, b2 = -1;     // b1 / b2 == -1: bias=False (the plain Conv2d form)
-};
-
-// One convolution of the net, resolved once by build_packs: its three packs, the BatchNorm behind it and its parameters.  Fwd, Bwd, the
-// fragment packing and the train-mode taps all take their tensors from here: none of them spells a state_dict name.
-struct ConvSite {
-    PackedConv eval, train, dgrad;   // BatchNorm folded (inference) | raw weights (training) | transposed + flipped raw weights (data gradient)
-    int bn = -1;                     // index into ake_pcnet::bns, -1: no BatchNorm behind it (a head's last conv)
-    int w = -1, b = -1;              // indices into ake_pcnet::specs
-};
-
-struct BnSpecs { int weight = -1, bias = -1, mean = -1, var = -1; };   // one BatchNorm's tensors, indices into ake_pcnet::specs
-
-struct Head {
-    std::vector<ConvSite> convs;     // head_layers entries (empty: a net without the genre head)
-    int kind;                        // run_conv's: 1 rows circular (12 x k), 2 rows valid (the genre head)
-    const char* nm;                  // module name
-    bool conv2d;                     // its convolutions are wrappers ("<nm>.<3j>.conv2d.weight")
-};
-
-int pick_co(int cout) { return cout >= 8 ? 8 : (cout >= 2 ? 4 : 1); }
-
-}  // namespace
-
-struct ake_pcnet {
-    ake_pcnet_config cfg;
-    std::vector<LayerDims> dims;
-    int final_ch = 0;
-    std::vector<TensorSpec> specs;
-    std::map<std::string, int> spec_index;
-    std::vector<HostTensor> host;
-    bool finalized = false;
-    bool eval_frags_stale = false;   // ake_pcnet_load_for_training_f32 skipped the MFMA fragments only the inference kernels read
-    int chunk_clips = 256;
-
-    // packed parameters
-    std::vector<float> blob;
-    float* blob_dev = nullptr;
-    std::vector<ConvSite> foldc;                  // per layer: --p2pc_conv's octave-fold convolution [co][ci][n_oct] (no dgrad pack)
-    std::vector<ConvSite> semi;                   // per layer (no dgrad pack)
-    std::vector<std::vector<ConvSite>> pc2pc;     // per layer, conv_layers entries (--resblock: conv0, then conv1, conv2 per block)
-    std::vector<ConvSite> up;                     // per layer (index 0 unused; no dgrad pack)
-    std::vector<std::vector<ConvSite>> p2p;       // per layer (index 0 empty)
-    Head heads[3] = {{{}, 1, "key_classifier", true}, {{}, 1, "tonic_classifier", true}, {{}, 2, "genre_classifier", false}};
-
-    // the BatchNorm layers of the training-mode forward, in forward order (gamma / beta in the blob)
-    struct BnLayer { std::string name; int C; size_t gamma_off, beta_off; int ch_off; BnSpecs p; };
-    std::vector<BnLayer> bns;
-    int bn_channels = 0;
-    std::vector<size_t> grad_off;      // float offset of specs[i] in the flat gradient buffer
-    size_t grad_floats = 0;
-    std::vector<size_t> raw_w_off;     // float offset in the blob of specs[i]'s raw values (convolution weights used by small kernels)
-
-    // device-side rebuild of the blob from a flat parameter buffer (same layout as the gradient buffer):
-    //   folded[i] = eval-mode BatchNorm folded into params[i] (conv weights / biases in front of a BatchNorm), else params[i]
-    //   blob[j]   = map[j] < 0 ? 0 : (map[j] & kMapFolded ? folded : params)[map[j] & kMapIndex]
-    struct FoldRecord { int w, b; BnSpecs bn; int cout; size_t per_out; bool transposed; int cin; };
-    std::vector<FoldRecord> fold_records;
-    std::vector<int32_t> map_host;     // one entry per blob float
-    int32_t* map_dev = nullptr;
-    int32_t* fold_ch_dev = nullptr;    // per flat float: -1, or (eval BatchNorm channel << 1) | is_bias
-    int32_t* fold_bn_dev = nullptr;    // per eval BatchNorm channel: flat offsets of gamma, beta, running_mean, running_var
-    int32_t* run_off_dev = nullptr;    // per training BatchNorm channel (BnLayer::ch_off order): flat offsets of running_mean, running_var
-    int32_t* run_off2_dev = nullptr;   // the same for the layers the reference's BACKWARD runs a second time (checkpointed halves: --denseblock's norm1), -1 elsewhere
-    int recomputed_bn_channels = 0;
-    float* folded_dev = nullptr;
-    bool tracing = false;
-    std::vector<std::vector<DensePack>> dense_pc, dense_p;   // --denseblock: per layer, conv_layers entries
-    struct AffRec { BnSpecs bn; int C; float slope; size_t off; };
-    std::vector<AffRec> aff_recs;      // BatchNorm layers behind dense_aff_dev, in table order
-    size_t dense_aff_floats = 0;
-    float* dense_aff_dev = nullptr;
-    int32_t* dense_aff_idx_dev = nullptr;
-    uint4* bf_frags_dev = nullptr;     // split-bf16 weight fragments of conv_p2p_f16_kernel, rebuilt from the eval packs on the device
-    size_t bf_frags_count = 0;         // uint4 entries
-};
+#include "pcnet_net.h"
 
 namespace {
-
-void add_spec(ake_pcnet* n, const std::string& name, std::initializer_list<int64_t> shape) {
-    TensorSpec s;
-    s.name = name;
-    s.ndim = static_cast<int>(shape.size());
-    int i = 0;
-    for (auto v : shape) s.shape[i++] = v;
-    for (; i < 4; ++i) s.shape[i] = 1;
-    n->spec_index[name] = static_cast<int>(n->specs.size());
-    n->specs.push_back(s);
-}
-
-void add_conv_specs(ake_pcnet* n, const std::string& prefix, int cout, int cin, int kh, int kw) {
-    add_spec(n, prefix + ".weight", {cout, cin, kh, kw});
-    add_spec(n, prefix + ".bias", {cout});
-}
-
-void add_bn_specs(ake_pcnet* n, const std::string& prefix, int c) {
-    for (const char* f : {".weight", ".bias", ".running_mean", ".running_var"}) add_spec(n, prefix + f, {c});
-}
 
 // the host copy of specs[spec] (build_packs resolves every name before it packs: the pack helpers below only see valid indices)
 const std::vector<float>& T(const ake_pcnet* n, int spec) { return n->host[spec].data; }
@@ -956,406 +821,9 @@ int run_semi(const ake_pcnet* n, const PackedConv& pc, const float* src, int bat
     }
 }
 
-// A tensor and the pending BatchNorm + LeakyReLU table its readers apply while loading (null: the tensor is final), see Fwd
-struct Slot {
-    float* p = nullptr;
-    float* aff = nullptr;
-};
-
-struct Buffers {           // workspace carve
-    // per chunk (pitch stream): everything up to the last layer's semitone fold
-    float* fold0 = nullptr;
-    unsigned int* melh = nullptr;   // inference: the log-CQT as f16 hi | lo words, [batch][P][T] (layer0_mfma_kernel -> conv_p2p_f16_ps_kernel<1, 3>)
-    float* smap = nullptr;     // --p2pc_conv only
-    float* p0 = nullptr;       // --stay_sixth only
-    std::vector<float*> pcd;   // --stay_sixth only
-    std::vector<float*> cat, psix, pa, pb, pca, pcb, ppool, pin;
-    // whole batch (pitch-class tail): last layer's concat buffer, its pc stack, pooled features, heads
-    float *pcf = nullptr, *hid_k = nullptr, *hid_t = nullptr, *hid_g = nullptr;
-    float *map_k = nullptr, *map_t = nullptr, *map_g = nullptr;
-    size_t hid_half = 0;    // floats of one of the two maps a head's hid_* buffer holds
-    std::vector<int> Tl;    // frames at layer i
-    int Tf = 0;             // frames after the last layer
-    size_t bytes = 0;
-    // training-mode forward only: BatchNorm statistics, raw semitone-conv outputs and the pending-affine table
-    // ([C][3] = scale, shift, negative slope) of every buffer that can hold a raw (pre-BatchNorm) tensor
-    double* stats = nullptr;           // [kStatSlots][bn_channels][2]
-    float* bstats = nullptr;           // [bn_channels][3] batch mean, biased variance, element count
-    std::vector<float*> semi_raw, aff_semi, aff_cat, aff_p2pin;
-    std::vector<float*> foldc_raw, aff_foldc, g_foldc;                // --p2pc_conv training: raw fold-conv output [B][C][12][T], pool.bn's table, its gradient
-    // every convolution keeps its own raw output in training mode (the backward pass needs all of them)
-    std::vector<std::vector<float*>> pst, aff_pst, pcst, aff_pcst;   // [layer][conv]
-    std::vector<float*> hst[3], aff_hst[3];                            // [head][hidden conv]
-    // backward
-    double* stats2 = nullptr;          // [bn_channels][3]  (sum g1, sum g1*zhat, sum (z - mean)); then one 8-byte cell per BatchNorm layer: the bits of max |dz| (dz_amax)
-    gfx_t* gslots = nullptr;           // [kGradSlots][grad_floats] partial weight gradients (backward), 64-bit fixed point
-    float* wg_partial = nullptr;       // per-workgroup partial weight gradients of one convolution (conv_wgrad_kernel), reduced in order
-    size_t wg_partial_floats = 0;
-    unsigned short* feat_cl = nullptr; // [2 planes][B][12][Tf][16]
-    float* coef = nullptr;             // [bn_channels][4]  (c0, c1, c2, mean)
-    float* g_map[3] = {nullptr, nullptr, nullptr};
-    float *g_hid = nullptr, *g_pcf = nullptr, *g_fold0 = nullptr;
-    std::vector<float*> g_pc, g_cat, g_semi, g_p, g_pin, g_psix;      // per layer (g_pc / g_p: ping-pong pair packed as 2x)
-    // --denseblock training: per block [pitch-class block of layer i | pitch block of layer i] and dense layer: the bottleneck map (kept for
-    // the backward pass) and the two on-load tables (norm1 over the block's features so far, norm2 over the bottleneck map); one gradient
-    // buffer of the widest bottleneck per block kind
-    std::vector<std::vector<float*>> dn_bott_pc, dn_aff1_pc, dn_aff2_pc, dn_bott_p, dn_aff1_p, dn_aff2_p;
-    float *dn_gbott_pc = nullptr, *dn_gbott_p = nullptr;
-
-    // Where conv j of a stack writes: training keeps every raw output next to its table (the backward pass reads all of them), inference
-    // ping-pongs between two buffers of final activations.  p_out: layer i's pitch stack, pc_out: its pitch-class stack, head_out: head
-    // h (key, tonic, genre), whose last conv writes the head's map (no BatchNorm); cat_slot: layer i's concat buffer.
-    Slot p_out(bool train, int i, int j) const { return train ? Slot{pst[i][j], aff_pst[i][j]} : Slot{(j & 1) ? pb[i] : pa[i], nullptr}; }
-    Slot pc_out(bool train, int i, int j) const { return train ? Slot{pcst[i][j], aff_pcst[i][j]} : Slot{(j & 1) ? pcb[i] : pca[i], nullptr}; }
-    Slot head_out(bool train, int h, int j, bool last) const {
-        float* const hid[3] = {hid_k, hid_t, hid_g};
-        float* const map[3] = {map_k, map_t, map_g};
-        if (last) return Slot{map[h], nullptr};
-        return train ? Slot{hst[h][j], aff_hst[h][j]} : Slot{hid[h] + (j & 1) * hid_half, nullptr};
-    }
-    Slot cat_slot(bool train, int i) const { return Slot{cat[i], train ? aff_cat[i] : nullptr}; }
-    // training: what layer i's pitch / pitch-class stack leaves (the last conv's raw output, or a --resblock stack's last block output)
-    Slot p_last(int i) const { return Slot{pst[i].back(), aff_pst[i].back()}; }
-    Slot pc_last(int i) const { return Slot{pcst[i].back(), aff_pcst[i].back()}; }
-};
-
-// chunk = clips per pitch-stream pass, batch = clips of the call (tail buffers)
-int plan_buffers(const ake_pcnet* n, int batch, int chunk, int frames, void* ws, Buffers* b, bool train = false) {
-    const auto& c = n->cfg;
-    const int L = c.num_layers, P = c.pitches;
-    ake::Carver cv(ws, 0);
-    b->Tl.assign(L, frames);
-    for (int i = 2; i < L; ++i) b->Tl[i] = b->Tl[i - 1] / c.time_pool_size;
-    b->Tf = L > 1 ? b->Tl[L - 1] / c.time_pool_size : frames;
-    AKE_REQUIRE(b->Tf >= 1, AKE_ERR_INVALID, "pcnet: %d frames vanish under the time pooling", frames);
-    b->cat.assign(L + 1, nullptr); b->psix.assign(L, nullptr); b->pa.assign(L, nullptr); b->pb.assign(L, nullptr);
-    b->pca.assign(L, nullptr); b->pcb.assign(L, nullptr); b->ppool.assign(L, nullptr); b->pin.assign(L, nullptr);
-    const size_t C = chunk, B = batch;
-    const size_t dg = c.denseblock ? static_cast<size_t>(c.n_filters) * c.conv_layers : 0;   // channels a dense block appends in place
-    b->fold0 = cv.take<float>(B * (L == 1 ? 1 + dg : 1) * 12 * frames);
-    if (!train && L > 1) b->melh = cv.take<unsigned int>(B * P * frames);
-    if (c.stay_sixth) {  // --stay_sixth: layer 0's activated semitone map is the pitch stream; dense copies of the pitch-class stream for the repeat
-        b->p0 = cv.take<float>(B * (P / 3) * frames);
-        b->pcd.assign(L, nullptr);
-        for (int i = 1; i < L; ++i) b->pcd[i] = cv.take<float>(C * n->dims[i].prev_pc * 12 * b->Tl[i]);
-    }
-    if (c.p2pc_conv) {   // --p2pc_conv: raw semitone maps between the semitone conv and the octave-fold conv (largest layer)
-        size_t m = B * (P / 3) * frames;
-        for (int i = 1; i < L; ++i) m = std::max(m, C * n->dims[i].out_p * (P / 3) * b->Tl[i]);
-        b->smap = cv.take<float>(m);
-    }
-    for (int i = 0; i < L; ++i) {
-        const int Ti = b->Tl[i];
-        const auto& d = n->dims[i];
-        const bool last = i == L - 1;
-        const int pc_out = i == 0 ? c.n_filters : d.out_pc;
-        if (i >= 1) {
-            b->cat[i] = cv.take<float>((last || i == 1 ? B : C) * (d.prev_pc + d.out_p + dg) * 12 * Ti);
-            b->psix[i] = cv.take<float>((i == 1 ? B : C) * d.prev_pc * 36 * Ti);
-            if (c.pc2p_mem) b->pin[i] = cv.take<float>(C * d.prev_p * P * Ti);             // --pc2p_mem: pitch stream + summed up_sixth map
-            b->pa[i] = cv.take<float>(C * d.out_p * P * Ti);
-            b->pb[i] = cv.take<float>((c.resblock ? 2 : 1) * C * (c.denseblock ? static_cast<size_t>((d.prev_pc + d.prev_p) / 2) * c.n_filters : d.out_p) * P * Ti);   // --resblock: the blocks' 2C-channel hidden map; --denseblock: the bottleneck map
-            if (!last) b->ppool[i] = cv.take<float>(C * d.out_p * P * (Ti / c.time_pool_size));
-        }
-        const size_t pca_ch = (c.denseblock && i >= 1) ? static_cast<size_t>((d.out_p + d.prev_pc) / 2) * c.n_filters : pc_out;   // --denseblock: bottleneck
-        b->pca[i] = cv.take<float>((last || i == 0 ? B : C) * pca_ch * 12 * Ti);
-        b->pcb[i] = cv.take<float>((c.resblock ? 2 : 1) * (last || i == 0 ? B : C) * pc_out * 12 * Ti);
-    }
-    b->pcf = cv.take<float>(B * n->final_ch * 12 * b->Tf);
-    const size_t hid = B * 2 * n->final_ch * 12 * b->Tf;
-    b->hid_half = hid;
-    b->hid_k = cv.take<float>(2 * hid); b->hid_t = cv.take<float>(2 * hid);
-    b->feat_cl = cv.take<unsigned short>(B * 12 * b->Tf * 16 * 2);     // channels-last split copy of the head input (bf16 head convs)
-    b->map_k = cv.take<float>(B * 12 * b->Tf); b->map_t = cv.take<float>(B * 12 * b->Tf);
-    if (c.genre) { b->hid_g = cv.take<float>(2 * hid); b->map_g = cv.take<float>(B * 12 * b->Tf); }
-    if (train) {
-        b->stats = cv.take<double>(static_cast<size_t>(n->bn_channels) * 2 * kStatSlots);
-        b->stats2 = cv.take<double>(static_cast<size_t>(n->bn_channels) * 3 * kBwdStatSlots + n->bns.size() * (kAmaxSlots / 2));       // [slot][bn_channels][3], then [bn layer][kAmaxSlots] unsigned: partial maxima of |dz| (float bits)
-        b->gslots = cv.take<gfx_t>(static_cast<size_t>(kGradSlots) * n->grad_floats);
-        b->wg_partial_floats = static_cast<size_t>(B) * 98304;                         // 384 KB per clip: e.g. two workgroups per clip x the 43 K weights of a head conv
-        b->wg_partial = cv.take<float>(b->wg_partial_floats);
-        b->bstats = cv.take<float>(static_cast<size_t>(n->bn_channels) * 3);
-        b->coef = cv.take<float>(static_cast<size_t>(n->bn_channels) * 4);
-        for (auto* v : {&b->semi_raw, &b->aff_semi, &b->aff_cat, &b->aff_p2pin, &b->g_pc, &b->g_cat, &b->g_semi, &b->g_p, &b->g_pin, &b->g_psix,
-                        &b->foldc_raw, &b->aff_foldc, &b->g_foldc})
-            v->assign(L + 1, nullptr);
-        b->pst.assign(L, {}); b->aff_pst.assign(L, {}); b->pcst.assign(L, {}); b->aff_pcst.assign(L, {});
-        for (int i = 0; i < L; ++i) {
-            const auto& d = n->dims[i];
-            const int Ti = b->Tl[i];
-            const int cs = i == 0 ? 1 : d.out_p, pc_out = i == 0 ? c.n_filters : d.out_pc;
-            b->semi_raw[i] = cv.take<float>(B * cs * (P / 3) * Ti);
-            b->g_semi[i] = cv.take<float>(B * cs * (P / 3) * Ti);
-            if (c.p2pc_conv) {
-                b->foldc_raw[i] = cv.take<float>(B * cs * 12 * Ti);
-                b->g_foldc[i] = cv.take<float>(B * cs * 12 * Ti);
-                b->aff_foldc[i] = cv.take<float>(3 * cs);
-            }
-            b->aff_semi[i] = cv.take<float>(3 * cs);
-            // --resblock: [conv0, (conv1 (2C), conv2, block output) per block] (res_stack_train); gradients: g, skip copy, 2C hidden map
-            const int n_st = c.denseblock ? 0 : (c.resblock ? 1 + 3 * c.conv_layers : c.conv_layers);
-            auto width = [&](int j) { return c.resblock && j % 3 == 1 ? 2 : 1; };
-            for (int j = 0; j < n_st; ++j) {
-                b->pcst[i].push_back(cv.take<float>(width(j) * B * pc_out * 12 * Ti));
-                b->aff_pcst[i].push_back(cv.take<float>(3 * width(j) * pc_out));
-            }
-            b->g_pc[i] = cv.take<float>((c.resblock ? 4 : 2) * B * (c.denseblock && i == 0 ? 1 + dg : pc_out) * 12 * Ti);   // (--denseblock, one layer: dL/d(fold | growth))
-            if (i >= 1) {
-                b->aff_cat[i] = cv.take<float>(3 * (d.prev_pc + d.out_p));
-                b->aff_p2pin[i] = cv.take<float>(3 * (d.prev_pc + d.prev_p));
-                b->g_cat[i] = cv.take<float>(B * (d.prev_pc + d.out_p + dg) * 12 * Ti);
-                for (int j = 0; j < n_st; ++j) {
-                    b->pst[i].push_back(cv.take<float>(width(j) * B * d.out_p * P * Ti));
-                    b->aff_pst[i].push_back(cv.take<float>(3 * width(j) * d.out_p));
-                }
-                b->g_p[i] = cv.take<float>((c.resblock ? 4 : 2) * B * d.out_p * P * Ti);
-                b->g_pin[i] = cv.take<float>(B * (d.prev_p + d.prev_pc) * P * Ti);
-                b->g_psix[i] = cv.take<float>(B * d.prev_pc * 36 * Ti);
-            }
-        }
-        if (c.denseblock) {
-            for (auto* v : {&b->dn_bott_pc, &b->dn_aff1_pc, &b->dn_aff2_pc, &b->dn_bott_p, &b->dn_aff1_p, &b->dn_aff2_p}) v->assign(L, {});
-            size_t gb_pc = 0, gb_p = 0;
-            for (int i = 0; i < L; ++i) {
-                const int Ti = b->Tl[i];
-                const auto& d = n->dims[i];
-                for (size_t j = 0; j < n->dense_pc[i].size(); ++j) {
-                    const DensePack& dp = n->dense_pc[i][j];
-                    b->dn_bott_pc[i].push_back(cv.take<float>(B * dp.c1.cout * 12 * Ti));
-                    b->dn_aff1_pc[i].push_back(cv.take<float>(3 * static_cast<size_t>(dp.c1.cin)));
-                    b->dn_aff2_pc[i].push_back(cv.take<float>(3 * static_cast<size_t>(dp.c1.cout)));
-                    gb_pc = std::max(gb_pc, B * dp.c1.cout * 12 * Ti);
-                }
-                for (size_t j = 0; i >= 1 && j < n->dense_p[i].size(); ++j) {
-                    const DensePack& dp = n->dense_p[i][j];
-                    b->dn_bott_p[i].push_back(cv.take<float>(B * dp.c1.cout * P * Ti));
-                    b->dn_aff1_p[i].push_back(cv.take<float>(3 * static_cast<size_t>(dp.c1.cin)));
-                    b->dn_aff2_p[i].push_back(cv.take<float>(3 * static_cast<size_t>(dp.c1.cout)));
-                    gb_p = std::max(gb_p, B * dp.c1.cout * P * Ti);
-                }
-                (void)d;
-            }
-            b->dn_gbott_pc = cv.take<float>(gb_pc);
-            b->dn_gbott_p = cv.take<float>(gb_p);
-        }
-        b->g_fold0 = cv.take<float>(B * 12 * frames);
-        b->g_pcf = cv.take<float>(B * n->final_ch * 12 * b->Tf);
-        b->g_hid = cv.take<float>(hid);
-        for (int h = 0; h < 3; ++h) {
-            if (h == 2 && !c.genre) break;
-            for (int j = 0; j + 1 < c.head_layers; ++j) {
-                b->hst[h].push_back(cv.take<float>(hid));
-                b->aff_hst[h].push_back(cv.take<float>(3 * 2 * n->final_ch));
-            }
-            b->g_map[h] = cv.take<float>(B * 12 * b->Tf);
-        }
-    }
-    b->bytes = ake::align_up(cv.off, 256);
-    return AKE_OK;
-}
-
-// ---- the route: which kernel form every stage of one forward call launches -------------------------------------------------------
-// Decided once per call by build_route() from the handle, the mode, the shape, the two alignments that are conditions and
-// ake_debug_keep_taps; plain data, no allocation.  Fwd launches what it says, ake_pcnet_accepts_frames_major returns its flag and the
-// debug taps answer from it, so none of them can disagree about what was written where.  It does not touch the workspace layout
-// (plan_buffers knows nothing of it).
-enum class L0Form : unsigned char { Generic, FusedValu, FusedMfma };       // layer 0 + layer 1's up_sixth: per-stage kernels | layer0_fused_kernel | layer0_mfma_kernel
-enum class PStack : unsigned char { Generic, F16x3, F16 };                 // a layer's pitch convs: conv_mfma_kernel | conv_p2p_f16x3_kernel where `x3_convs` says | the f16 kernels
-enum class PcStack : unsigned char { Generic, F16x3, Bf16, Fused };        // the last pitch-class stack: conv_mfma_kernel | conv_pc_f16x3 where `pc_x3_convs` says | conv_pc_bf16_kernel | pc2pc_fused_kernel
-enum class HeadForm : unsigned char { Generic, Bf16First, Head1, Fused };  // key / tonic heads: conv_mfma_kernel | bf16 first conv | + conv_head1_bf16_kernel | heads_fused_kernel
-
-struct Layer0Plan {
-    L0Form form = L0Form::Generic;
-    int RP = 0, RPp = 0;
-    size_t lds = 0;
-    // FusedMfma: where float (bin r, frame t) of the clip's CQT sits in the LDS image (Layer0Args::img_*).  A frames-major clip is stored
-    // tiled, [frame quad][bin & 3][bin >> 2][frame & 3]: its loader's 16-byte stores (a thread's 4 frames of one bin, adjacent lanes 4 bins
-    // apart) then lie side by side, and a frame quad's pitch of 4 (mod 32) floats keeps the semitone phase's frame-wise reads on 32 banks
-    bool tiled = false;
-    int img_sq = 0, img_sb = 0, img_sr = 0;
-    // FusedMfma: the convs >= 1 find their weight fragments in two LDS regions laid over the dead image (else, where the maps leave no room
-    // for them -- few bins, many frames -- every conv fetches its own from global memory at its start)
-    bool frag_lds = false;
-};
-
-struct Route {
-    bool frames_major = false;       // the call was asked to read mel frames-major and every reader of mel takes it
-    Layer0Plan l0;
-    bool psix_f16 = false;           // layer 0 leaves layer 1's up_sixth map as f16 x 4 words in psix[1] (and the CQT in melh) for conv_p2p_f16_ps_kernel<1, 3>
-    int chunk_clips[2] = {0, 0};     // clips of a full pitch_chunk call and of the remainder call (0: none); `k` below indexes them
-    struct Pitch {                   // layers >= 1
-        PStack stack = PStack::Generic;
-        unsigned x3_convs = 0;       // F16x3: bit j = conv j runs on conv_p2p_f16x3_kernel
-        struct PerChunk {
-            P2pPsPlan first, mid, last;   // F16: the persistent form of the first / an inner / the last conv (!ok: the tiled conv_p2p_f16_kernel);
-                                          // last.out: plain (Nchw), semitone conv fused (Semi), semitone conv and fold fused (SemiFold)
-            P2pStackPlan stack;           // F16, ok: the whole stack is ONE launch of p2p_stack_kernel, and first / mid / last launch nothing
-            P2pX3Plan x3[2];              // F16x3: geometry of conv 0 and of the later convs
-        } k[2];
-    } p[4];
-    PcStack pc = PcStack::Generic;
-    unsigned pc_x3_convs = 0;
-    HeadForm heads = HeadForm::Generic;
-    bool genre_bf = false;           // Head1 / Fused: the genre head rides in the same launches
-    bool heads_pool = false;         // Head1 / Fused: the masked mean + sigmoid ride in the launch
-    int heads_mt = 0;                // Fused: M-tiles per wave of phase A (heads_fused_kernel<MT>)
-    int T1 = 0, T2 = 0, TpB = 0;     // Head1 / Fused: frames after each head conv, phase B's patch pitch
-    size_t hf_lds = 0;               // Fused
-
-    int chunk_kind(int B) const { return B == chunk_clips[0] ? 0 : 1; }
-};
-
-// layer 0 as one launch per clip (default family, inference): which form fits, and its LDS geometry
-constexpr size_t kL0MaxLds = 160 * 1024;      // layer0_mfma_kernel's dynamic LDS limit (at the rule's edge, T = 86 frames-major, it takes 152.6 KiB)
-Layer0Plan layer0_plan(const ake_pcnet* n, int T0, bool mel16, bool mel_fm) {
-    const auto& c = n->cfg;
-    const int P = c.pitches, NF = c.n_filters;
-    Layer0Plan g;
-    if (c.num_layers < 2 || c.resblock || c.denseblock || c.p2pc_conv || c.stay_sixth || NF < 2 || NF > 4 || c.conv_layers < 1 || c.conv_layers > 4 || c.kernel_size != 7 || P % 36 || T0 < 1) return g;
-    const PackedConv& sp = n->semi[0].eval;
-    if (sp.cin != 1 || sp.co != 1) return g;
-    bool mfma = c.precision == AKE_PRECISION_MIXED;      // (the MFMA form multiplies f16 x f16; f32x3: the exact-f32 VALU form)
-    for (int j = 0; j < c.conv_layers; ++j) {
-        const PackedConv& pc = n->pc2pc[0][j].eval;
-        if (pc.co != 4 || pc.groups != 1 || pc.kh != 12 || pc.kw != 7 || pc.cout != NF || pc.cin != (j == 0 ? 1 : NF)) return g;
-        mfma = mfma && pc.l0_off >= 0;
-    }
-    if (n->dims[1].prev_pc != NF) return g;
-    g.RP = 4 * ((T0 + 3) / 4) + 8;
-    g.RPp = (T0 + 8 + 1) / 2 * 2;
-    const size_t lds_v = (static_cast<size_t>(9) * 12 * g.RP + static_cast<size_t>(P) * T0) * sizeof(float);   // maps + the clip's CQT
-    if (lds_v > 150 * 1024 || (static_cast<long long>(P) * T0) % 4 || !mel16) return g;
-    const size_t lds_m = (static_cast<size_t>(4) * 12 * g.RP + static_cast<size_t>(2) * 12 * g.RPp * 4 + static_cast<size_t>(P) * T0) * sizeof(float);
-    const bool take_mfma = mfma && lds_m <= 150 * 1024;
-    if (mel_fm && (!take_mfma || P % 4)) return g;        // only the MFMA form's loader transposes
-    g.form = take_mfma ? L0Form::FusedMfma : L0Form::FusedValu;
-    g.lds = take_mfma ? lds_m : lds_v;
-    if (take_mfma) {      // what the kernel really takes (lds_m stays the rule): the maps, then the image or the fragment regions laid over it
-        const size_t maps = lds_m - static_cast<size_t>(P) * T0 * sizeof(float);
-        const size_t frag_bytes = c.conv_layers > 1 ? static_cast<size_t>(2) * 24 * 64 * sizeof(uint4) : 0;
-        const int sq = 4 * P + ((36 - (4 * P & 31)) & 31);
-        const size_t tiled_bytes = static_cast<size_t>((T0 + 3) / 4) * sq * sizeof(float);
-        // The untiled frames-major image (every frame through the scalar stores that otherwise take the frames past the last quad) is for
-        // pitch counts far above any net that is tested as a whole clip: at 288 and 360 bins the tiled image fits at every eligible frame count.
-        g.tiled = mel_fm && maps + tiled_bytes <= kL0MaxLds;
-        g.img_sq = g.tiled ? sq : 4;
-        g.img_sb = g.tiled ? P : T0;
-        g.img_sr = g.tiled ? 4 : 4 * T0;
-        const size_t img_bytes = g.tiled ? tiled_bytes : static_cast<size_t>(P) * T0 * sizeof(float);
-        g.frag_lds = frag_bytes && maps + std::max(img_bytes, frag_bytes) <= kL0MaxLds;
-        g.lds = maps + (g.frag_lds ? std::max(img_bytes, frag_bytes) : img_bytes);       // <= kL0MaxLds either way: lds_m <= 150 KiB
-    }
-    return g;
-}
-
-// mel, ws: only their 16-byte alignment is read (null counts as aligned).  chunk: clips per pitch_chunk call.
-Route build_route(const ake_pcnet* n, bool train, int batch, int chunk, int frames, const float* mel, const void* ws, bool mel_fm) {
-    Route r;
-    const auto& c = n->cfg;
-    const int L = c.num_layers;
-    const bool ws16 = !(reinterpret_cast<uintptr_t>(ws) & 15);
-    int Tl[4];
-    for (int i = 0; i < L; ++i) Tl[i] = i < 2 ? frames : Tl[i - 1] / c.time_pool_size;
-    const int Tf = L > 1 ? Tl[L - 1] / c.time_pool_size : frames;
-    if (batch < 1 || chunk < 1 || Tf < 1) return r;
-    r.chunk_clips[0] = std::min(batch, chunk);
-    r.chunk_clips[1] = batch > chunk ? batch % chunk : 0;
-
-    // ---- layer 0 ----
-    if (!train && L > 1) r.l0 = layer0_plan(n, Tl[0], !(reinterpret_cast<uintptr_t>(mel) & 15), mel_fm);
-    // the up_sixth map as f16 x 4 when the conv that reads it is the persistent f16 kernel for every chunk of this batch (it rounds to f16
-    // itself otherwise: same values); psix[1]'s buffer holds either form
-    if (r.l0.form == L0Form::FusedMfma && !g_keep_taps && !c.pc2p_mem && n->dims[1].prev_p == 1 && p2p_uses_f16(n, 1, Tl[1])) {
-        r.psix_f16 = true;
-        for (int k = 0; k < 2 && r.psix_f16; ++k)
-            if (r.chunk_clips[k])
-                r.psix_f16 = p2p_ps_plan(P2pIn::SrcF16x4, 1, n->dims[1].prev_pc, P2pOut::Plane, n->dims[1].out_p, false, r.chunk_clips[k], c.pitches, Tl[1], ws16).ok;
-    }
-
-    // ---- pitch stacks of the layers >= 1 (--denseblock runs its own blocks, --resblock the f32 MFMA kernel) ----
-    const int P = c.stay_sixth ? c.pitches / 3 : c.pitches;
-    int cp = 1;
-    for (int i = 1; i < L && !c.denseblock && !c.resblock; ++i) {
-        const LayerDims& d = n->dims[i];
-        Route::Pitch& rp = r.p[i];
-        const int Ti = Tl[i], c0 = cp, c1 = c.pc2p_mem ? 0 : d.prev_pc;     // (--pc2p_mem: the summed map was added to the pitch stream)
-        if (!train && p2p_uses_f16(n, i, Ti)) {
-            rp.stack = PStack::F16;
-            const bool semi = p2p_fuses_semi(n, i, P, Ti);
-            for (int k = 0; k < 2; ++k) {
-                const int B = r.chunk_clips[k];
-                if (!B) continue;
-                const P2pIn in0 = (i == 1 && r.psix_f16) ? P2pIn::SrcF16x4 : ((mel_fm && i == 1) ? P2pIn::SrcFramesMajor : P2pIn::Src);
-                rp.k[k].first = p2p_ps_plan(in0, c0, c1, P2pOut::Plane, d.out_p, false, B, P, Ti, ws16);
-                rp.k[k].mid = p2p_ps_plan(P2pIn::Planes, 0, 0, P2pOut::Plane, d.out_p, false, B, P, Ti, ws16);
-                P2pPsPlan& last = rp.k[k].last;
-                if (semi) last = p2p_ps_plan(P2pIn::Planes, 0, 0, P2pOut::SemiFold, d.prev_pc + d.out_p, true, B, P, Ti, ws16);
-                if (semi && !last.ok) last = p2p_ps_plan(P2pIn::Planes, 0, 0, P2pOut::Semi, d.out_p, true, B, P, Ti, ws16);
-                if (!last.ok) last = p2p_ps_plan(P2pIn::Planes, 0, 0, P2pOut::Nchw, d.out_p, false, B, P, Ti, ws16);
-                // one launch for the stack: fed by layer 0's f16 words, its last conv fused with the semitone conv (what was written where
-                // stays as the taps know it: planes in the ping-pong buffers, the folded maps in `cat`)
-                if (in0 == P2pIn::SrcF16x4 && semi) rp.k[k].stack = p2p_stack_plan(c.conv_layers, c0, c1, true, B, P, Ti);
-            }
-        } else if (!c.pc2p_mem && !c.stay_sixth && (train || (c.precision == AKE_PRECISION_F32X3 && !g_keep_taps))) {
-            // training: f16 x 3 on the persistent form (f32-equivalent products).  Inference in the f32x3 precision mode: the same kernel with
-            // the EVAL fragments (BatchNorm folded; three products: f32-equivalent to 2^-22) and LeakyReLU in its epilogue
-            for (int k = 0; k < 2; ++k) {
-                const int B = r.chunk_clips[k];
-                if (!B) continue;
-                rp.k[k].x3[0] = p2p_f16x3_plan(c0, c1, d.out_p, B, P, Ti, ws16);
-                rp.k[k].x3[1] = p2p_f16x3_plan(d.out_p, 0, d.out_p, B, P, Ti, ws16);
-            }
-            for (int j = 0; j < c.conv_layers && j < 32; ++j)          // (eligibility does not depend on the clip count)
-                if ((train ? n->p2p[i][j].train : n->p2p[i][j].eval).bf_off >= 0 && rp.k[0].x3[j > 0].ok) rp.x3_convs |= 1u << j;
-            if (rp.x3_convs) rp.stack = PStack::F16x3;
-        }
-        cp = d.out_p;
-    }
-    r.frames_major = mel_fm && !train && L == 2 && !c.resblock && !c.denseblock && !c.pc2p_mem && !c.p2pc_conv && !c.stay_sixth && !c.local &&
-                     batch <= chunk && r.l0.form == L0Form::FusedMfma && r.p[1].stack == PStack::F16 && r.p[1].k[0].first.ok;
-
-    // ---- the last layer's pitch-class stack ----
-    const int i = L - 1, Ti = Tl[i];
-    if (!train && L > 1 && !c.denseblock && pc2pc_fuses(n, i, Ti)) r.pc = PcStack::Fused;
-    else if (!train && pc2pc_uses_bf16(n, i, Ti)) r.pc = PcStack::Bf16;
-    else if (train && L > 1 && !c.resblock && !c.denseblock) {
-        for (int j = 0; j < c.conv_layers && j < 32; ++j)
-            if (pc_f16x3_ok(n->pc2pc[i][j].train, Ti, true)) r.pc_x3_convs |= 1u << j;
-        if (r.pc_x3_convs) r.pc = PcStack::F16x3;
-    }
-
-    // ---- heads (training keeps its own per-conv choices in Fwd::tail) ----
-    // key / tonic heads: the first convolution (16 -> 32 channels, most of a head's work) on the bf16 kernel
-    const std::vector<ConvSite>&hk = n->heads[0].convs, &ht = n->heads[1].convs, &hg = n->heads[2].convs;      // key, tonic, genre
-    const bool head_bf = !train && L > 1 && n->final_ch == 16 && c.head_layers >= 2 && hk[0].eval.bf_off >= 0 && ht[0].eval.bf_off >= 0 &&
-                         Tf <= kPcBf16MaxFrames;
-    if (!head_bf) return r;
-    r.heads = HeadForm::Bf16First;
-    // two-conv heads: conv0 leaves its 32 channels as channels-last planes and ONE launch of conv_head1_bf16_kernel finishes both maps
-    r.T1 = Tf - (c.kernel_size - 1); r.T2 = r.T1 - (c.kernel_size - 1);
-    const int T1 = r.T1, T2 = r.T2;
-    if (!(c.head_layers == 2 && hk[1].eval.bf_off >= 0 && ht[1].eval.bf_off >= 0 && T2 > 0 && (12 * ((T2 + 15) / 16) + 15) / 16 <= kHead1MT)) return r;
-    r.heads = HeadForm::Head1;
-    r.genre_bf = c.genre && hg.size() == 2 && hg[0].eval.bf_off >= 0 && hg[1].eval.bf_off >= 0 && hg[0].eval.kh == 1 && hg[1].eval.kh == 2;
-    r.heads_pool = c.local == 0;
-    // ... and when the stack above ran as one launch both convolutions of a head run as ONE launch too (heads_fused_kernel): the 32 hidden
-    // channels stay in LDS.  ake_debug_keep_taps(1), other head depths and shapes whose patches do not fit keep the two launches.
-    r.TpB = 16 * ((T2 + 15) / 16 - 1) + 22;
-    r.hf_lds = std::max({(static_cast<size_t>(2) * 12 * (T1 + 8) * 2 + 2 * 4 * 2 * 2 * 64) * sizeof(uint4),      // phase A: patch + weight ring
-                         static_cast<size_t>(2) * 12 * r.TpB * 4 * sizeof(uint4),                                // phase B: patch,
-                         static_cast<size_t>(8) * kHead1MT * 4 * 64 * sizeof(float)}) +                          // then the partial tiles
-               static_cast<size_t>(12) * T2 * sizeof(float);                                                     // the finished map
-    if (r.pc == PcStack::Fused && !g_keep_taps && c.local == 0 && hk[0].eval.cout == 32 && ht[0].eval.cout == 32 && hk[0].eval.kh == 12 &&
-        ht[0].eval.kh == 12 && hk[1].eval.kh == 12 && ht[1].eval.kh == 12 && (!r.genre_bf || hg[0].eval.cout == 32) &&
-        (12 * T1 + 15) / 16 <= 32 && r.hf_lds <= 150 * 1024) {
-        r.heads = HeadForm::Fused;
-        // phase A's M-tiles over the 8 waves: three each where 24 cover the hidden map (12 x 32 positions and fewer), else four
-        r.heads_mt = (12 * T1 + 15) / 16 <= 24 ? 3 : 4;
-    }
-    return r;
-}
-
 }  // namespace
+
+#include "pcnet_plan.h"
 
 // (for the other translation units of the library: the handle's layout is private to this one)
 int ake::pcnet_local_window(const ake_pcnet* n) { return n ? n->cfg.local : 0; }
@@ -2136,11 +1604,6 @@ int ake_pcnet_finalize(ake_pcnet* n) {
 // Device-resident parameters: (re)build every packed weight from a flat f32 parameter buffer on the device (layout =
 // ake_pcnet_grad_offset).  No host round trip after the first call; asynchronous on `stream`.
 namespace {
-int load_from_device_impl(ake_pcnet* n, const float* params_dev, ake_stream_t stream, bool train_only);
-}
-int ake_pcnet_load_from_device_f32(ake_pcnet* n, const float* params_dev, ake_stream_t stream) { return load_from_device_impl(n, params_dev, stream, false); }
-int ake_pcnet_load_for_training_f32(ake_pcnet* n, const float* params_dev, ake_stream_t stream) { return load_from_device_impl(n, params_dev, stream, true); }
-namespace {
 int load_from_device_impl(ake_pcnet* n, const float* params_dev, ake_stream_t stream, bool train_only) {
     AKE_REQUIRE(n && params_dev, AKE_ERR_INVALID, "load_from_device: null argument");
     if (n->map_host.empty()) {          // first use: learn the layout (values are irrelevant; host tensors only need their sizes)
@@ -2165,6 +1628,8 @@ int load_from_device_impl(ake_pcnet* n, const float* params_dev, ake_stream_t st
     return AKE_OK;
 }
 }  // namespace
+int ake_pcnet_load_from_device_f32(ake_pcnet* n, const float* params_dev, ake_stream_t stream) { return load_from_device_impl(n, params_dev, stream, false); }
+int ake_pcnet_load_for_training_f32(ake_pcnet* n, const float* params_dev, ake_stream_t stream) { return load_from_device_impl(n, params_dev, stream, true); }
 
 // running_mean / running_var inside the flat parameter buffer <- momentum blend with the batch statistics that
 // ake_pcnet_forward_train_f32 returned in bn_stats (torch semantics: unbiased variance; models use momentum 0.1).
@@ -2217,763 +1682,7 @@ size_t ake_pcnet_train_workspace_bytes(const ake_pcnet* n, int batch, int frames
     return b.bytes;
 }
 
-namespace {
-
-// One forward pass.  In eval mode BatchNorm is folded into the convolutions and every tensor is final.  In training
-// mode a convolution followed by BatchNorm leaves its RAW output plus a pending (scale, shift, slope) table that the
-// next reader applies while loading: the two travel together as a Slot (aff null = nothing pending), handed out by Buffers.
-struct Fwd {
-    const ake_pcnet* n;
-    Buffers& b;
-    hipStream_t s;
-    bool train;
-    const Route& r;                  // what this call launches (build_route)
-
-    // training: the rows of layer i's pitch-stack input table that belong to the up_sixth map (they follow the pitch stream's prev_p rows)
-    float* p2pin_up(int i) const { return train ? b.aff_p2pin[i] + 3 * n->dims[i].prev_p : nullptr; }
-
-    // launch BatchNorm finalisation of layer `bn` (count values per channel) into the affine table `aff_out`
-    int finalize_bn(int bn, double count, float* aff_out, float slope = kSlope) {
-        const auto& l = n->bns[bn];
-        // the element count rides along for the unbiased running variance (written by the host-visible copy below)
-        return ake::launch("bn_finalize_kernel", bn_finalize_kernel, dim3((l.C + 63) / 64), dim3(64), 0, s, b.stats + 2 * l.ch_off, 2 * n->bn_channels,
-                           count, n->blob_dev + l.gamma_off, n->blob_dev + l.beta_off, aff_out, b.bstats + 3 * l.ch_off, l.C, slope);
-    }
-    int identity(float* aff, int C) {
-        return ake::launch_untimed("affine_identity_kernel", affine_identity_kernel, dim3((C + 63) / 64), dim3(64), 0, s, aff, C);
-    }
-
-    // the convolution of site `cs` (+ its BatchNorm + LeakyReLU where it has one).  Inference: the folded pack, dst is final.  Training: the
-    // raw pack, dst is raw and the BatchNorm's table lands in aff_dst.
-    int conv(const ConvSite& cs, int kind, Src src, const float* in_aff, int B, int H, int T_in, bool same, float* dst, int ctot, int coff,
-             float* aff_dst, const char* name, const float* residual = nullptr) {
-        ConvOpts o;
-        const int bn = cs.bn;
-        const bool has_bn = bn >= 0;
-        if (!train) {
-            o.residual = residual;
-            return run_conv(n, cs.eval, kind, src, B, H, T_in, same, has_bn, dst, ctot, coff, s, name, o);
-        }
-        const PackedConv& pt = cs.train;
-        o.in_affine = in_aff;
-        if (has_bn) o.stats = b.stats + 2 * n->bns[bn].ch_off;
-        int rc = run_conv(n, pt, kind, src, B, H, T_in, same, false, dst, ctot, coff, s, name, o);
-        if (rc) return rc;
-        if (has_bn) {
-            const int T_out = same ? T_in : T_in - pt.kw + 1;
-            const int H_out = kind == 2 ? H - pt.kh + 1 : H;
-            return finalize_bn(bn, static_cast<double>(B) * H_out * T_out, aff_dst);
-        }
-        return AKE_OK;
-    }
-
-    // --denseblock (models.py:584-648): layer i's pitch block (kind 0) or pitch-class block (kind 1) IN PLACE on feat [B][ctot][H][T] whose
-    // channels [0, cin) are filled; dense layer j reads channels [0, cin + j*nf) through its norm1 table, writes the bottleneck map, and its
-    // k-wide convolution (input through the norm2 table, ReLU) appends nf channels at cin + j*nf.  kind 0: plain Conv2d -- 1 x 1, then
-    // k x k ZERO-padded on both axes; kind 1: equivariant 12 x 1 and 12 x k (rows circular, frames zero-padded).
-    // Inference: the tables are the folded ones of n->dense_aff_dev and every layer's bottleneck map goes to `bott`.
-    // Training (batch statistics): BatchNorm sits in FRONT of both convolutions here, so every norm1 needs the statistics of features other
-    // kernels produced: the block input's are taken by channel_stats_kernel, a layer's new features leave theirs in the NEXT layer's norm1
-    // cells (conv2's statistics epilogue) and every later norm1 copies the prefix it shares (stats_copy_kernel).  The bottleneck maps and
-    // both tables of every layer stay in the workspace (dn_*) for the backward pass.
-    int dense_stack(int i, int kind, float* feat, int ctot, int cin, int B, int H, int T, float* bott, const char* label) {
-        const std::vector<DensePack>& packs = kind == 0 ? n->dense_p[i] : n->dense_pc[i];
-        const auto& botts = kind == 0 ? b.dn_bott_p : b.dn_bott_pc;
-        const auto& aff1s = kind == 0 ? b.dn_aff1_p : b.dn_aff1_pc;
-        const auto& aff2s = kind == 0 ? b.dn_aff2_p : b.dn_aff2_pc;
-        const int nf = n->cfg.n_filters, k = n->cfg.kernel_size;
-        const double count = static_cast<double>(B) * H * T;
-        const int sstride = 2 * n->bn_channels;
-        int rc;
-        if (train && (rc = ake::launch("channel_stats_kernel", channel_stats_kernel, dim3(cin, 1, B), dim3(256), 0, s, feat, static_cast<long long>(ctot) * H * T,
-                                       static_cast<long long>(H) * T, b.stats + 2 * n->bns[packs[0].bn1].ch_off, sstride)))
-            return rc;
-        for (size_t j = 0; j < packs.size(); ++j) {
-            const DensePack& dp = packs[j];
-            const int cj = cin + static_cast<int>(j) * nf;
-            AKE_REQUIRE(dp.c1.cin == cj && cj + nf <= ctot && (!train || (dp.bn1 >= 0 && dp.bn2 >= 0)), AKE_ERR_STATE, "dense %s: channel bookkeeping", label);
-            if (train && j > 0) {   // the statistics of channels [0, cj - nf): the previous norm1 has them (its own copy or the block input's)
-                const int C = cj - nf;
-                if ((rc = launch_flat("stats_copy_kernel", stats_copy_kernel, s, kStatSlots * 2 * C, b.stats, sstride, n->bns[packs[j - 1].bn1].ch_off,
-                                      n->bns[dp.bn1].ch_off, C)))
-                    return rc;
-            }
-            if (train && (rc = finalize_bn(dp.bn1, count, aff1s[i][j], kSlope))) return rc;   // relu1 = nn.LeakyReLU
-            float* const bott_j = train ? botts[i][j] : bott;
-            const ConvGeom g1{0, 3, T, H, 0};                  // the single tap sits at offset 3 of the 7 stored
-            ConvOpts o1;
-            o1.in_affine = train ? aff1s[i][j] : n->dense_aff_dev + dp.aff1;
-            if (train) o1.stats = b.stats + 2 * n->bns[dp.bn2].ch_off;
-            if (kind == 0) o1.geom = &g1;
-            if ((rc = run_conv(n, dp.c1, kind, Src{feat, cj, nullptr, 0, 0, ctot}, B, H, T, true, false, bott_j, dp.c1.cout, 0, s, label, o1))) return rc;
-            if (train && (rc = finalize_bn(dp.bn2, count, aff2s[i][j], 0.f))) return rc;      // relu2 = nn.ReLU
-            const ConvGeom g2{k / 2, k / 2, T, H, 0};
-            ConvOpts o2;
-            o2.in_affine = train ? aff2s[i][j] : n->dense_aff_dev + dp.aff2;
-            if (train && j + 1 < packs.size()) o2.stats = b.stats + 2 * (n->bns[packs[j + 1].bn1].ch_off + cj);
-            if (kind == 0) { o2.geom = &g2; o2.rows_zero = true; }
-            if ((rc = run_conv(n, dp.c2, kind, Src{bott_j, dp.c1.cout, nullptr, 0, 0}, B, H, T, true, false, feat, ctot, cj, s, label, o2))) return rc;
-        }
-        return AKE_OK;
-    }
-
-    // --resblock stack (models.py:181-187 / 218-224, 402-454), inference: st = [conv0, (conv1, conv2) per block].  x lives in X
-    // (C channels, dense), a block's hidden map (2C channels) in Hb; conv2 adds x before its LeakyReLU, in place -- the last block
-    // may write channels [0, C) of a wider buffer instead (final_dst with final_ctot channels).
-    int res_stack(const std::vector<ConvSite>& st, int kind, Src first, int B, int H, int T, float* X, float* Hb, float* final_dst,
-                  int final_ctot, const char* label) {
-        const int C = st[0].eval.cout;
-        int rc = conv(st[0], kind, first, nullptr, B, H, T, true, X, C, 0, nullptr, label);
-        if (rc) return rc;
-        const int nb = (static_cast<int>(st.size()) - 1) / 2;
-        for (int r = 0; r < nb; ++r) {
-            if ((rc = conv(st[1 + 2 * r], kind, Src{X, C, nullptr, 0, 0}, nullptr, B, H, T, true, Hb, 2 * C, 0, nullptr, label))) return rc;
-            const bool to_final = r == nb - 1 && final_dst;
-            if ((rc = conv(st[2 + 2 * r], kind, Src{Hb, 2 * C, nullptr, 0, 0}, nullptr, B, H, T, true, to_final ? final_dst : X,
-                           to_final ? final_ctot : C, 0, nullptr, label, X)))
-                return rc;
-        }
-        return AKE_OK;
-    }
-
-    // --resblock stack, training (batch statistics): st = the sites [conv0, (conv1, conv2) per block].  Every tensor the backward needs stays: z = [conv0 raw, (conv1 raw (2C), conv2 raw,
-    // block output) per block] with the pending tables in aff (b2's carries slope 1: no activation of its own; a block output's is
-    // the identity).  The last block writes channels [0, C) of final_dst (final_ctot channels) instead of z.back() when given.
-    int res_stack_train(const std::vector<ConvSite>& st, int kind, Src first, const float* first_aff, int B, int H, int T,
-                        const std::vector<float*>& z, const std::vector<float*>& aff, float* final_dst, int final_ctot, const char* label) {
-        const int C = st[0].train.cout;
-        const int nb = (static_cast<int>(st.size()) - 1) / 2;
-        AKE_REQUIRE(static_cast<int>(z.size()) == 1 + 3 * nb && z.size() == aff.size(), AKE_ERR_STATE, "resblock %s: buffer bookkeeping", label);
-        int rc = conv(st[0], kind, first, first_aff, B, H, T, true, z[0], C, 0, aff[0], label);
-        if (rc) return rc;
-        const float* x = z[0];
-        const float* x_aff = aff[0];
-        const double count = static_cast<double>(B) * H * T;
-        for (int r = 0; r < nb; ++r) {
-            float* z1 = z[1 + 3 * r];
-            float* z2 = z[2 + 3 * r];
-            if ((rc = conv(st[1 + 2 * r], kind, Src{x, C, nullptr, 0, 0}, x_aff, B, H, T, true, z1, 2 * C, 0, aff[1 + 3 * r], label)))
-                return rc;
-            const int bn2 = st[2 + 2 * r].bn;
-            ConvOpts o2;
-            o2.in_affine = aff[1 + 3 * r];
-            o2.stats = b.stats + 2 * n->bns[bn2].ch_off;
-            if ((rc = run_conv(n, st[2 + 2 * r].train, kind, Src{z1, 2 * C, nullptr, 0, 0}, B, H, T, true, false, z2, C, 0, s, label, o2))) return rc;
-            if ((rc = finalize_bn(bn2, count, aff[2 + 3 * r], 1.f))) return rc;
-            const bool to_final = r == nb - 1 && final_dst;
-            float* xo = to_final ? final_dst : z[3 + 3 * r];
-            const long long total = static_cast<long long>(B) * C * H * T;
-            if ((rc = launch_flat("res_add_act_kernel", res_add_act_kernel, s, total, z2, aff[2 + 3 * r], x, x_aff, xo, C, H * T, to_final ? final_ctot : C, total)))
-                return rc;
-            if ((rc = identity(aff[3 + 3 * r], C))) return rc;
-            x = xo; x_aff = aff[3 + 3 * r];
-        }
-        return AKE_OK;
-    }
-
-    // one launch of semi_conv_stats_kernel over [B][pc.cin][P][ta.s.T]: thread = (semitone row, strip of frames), CO channels per thread
-    int launch_semi_conv(const PackedConv& pc, const SemiTrainArgs& ta, int P, int B) {
-        const int per_clip = (P / 3) * ta.s.n_strips;
-        const int threads = per_clip >= 256 ? 256 : (per_clip + 63) / 64 * 64;
-        dim3 grid((per_clip + threads - 1) / threads, pc.groups, B), block(threads);
-        switch (pc.co) {
-            case 8: return ake::launch("semi_conv_stats_kernel", semi_conv_stats_kernel<8>, grid, block, 0, s, ta);
-            case 4: return ake::launch("semi_conv_stats_kernel", semi_conv_stats_kernel<4>, grid, block, 0, s, ta);
-            case 1: return ake::launch("semi_conv_stats_kernel", semi_conv_stats_kernel<1>, grid, block, 0, s, ta);
-            default: ake::set_error("semi: bad CO"); return AKE_ERR_UNSUPPORTED;
-        }
-    }
-
-    // pool_semi (+BN+LReLU) + octave fold of `src` [B][C][P][T] into channels [coff, coff+C) of dst [B][ctot][12][T]
-    int semi(int layer, const float* src, const float* in_aff, int B, int P, int Tn, float* dst, int ctot, int coff, float* aff_cat_rows) {
-        const char* nm = layer == 0 ? "semi_fold_kernel/L0" : "semi_fold_kernel/L1+";
-        int rc;
-        if (!train && n->cfg.p2pc_conv) {   // semitone conv (raw, BatchNorm folded) -> octave-fold convolution (LeakyReLU applied on load)
-            const PackedConv& pc = n->semi[layer].eval;
-            SemiTrainArgs ta;
-            std::memset(&ta, 0, sizeof(ta));
-            ta.s = semi_args(n, pc, src, P, Tn, b.smap);
-            if ((rc = launch_semi_conv(pc, ta, P, B))) return rc;
-            const PackedConv& fc = n->foldc[layer].eval;
-            const long long total = static_cast<long long>(B) * pc.cin * 12 * Tn;
-            return launch_flat("fold_conv_kernel", fold_conv_kernel, s, total, b.smap, n->blob_dev + fc.w_off, n->blob_dev + fc.b_off, dst, pc.cin, P / 36, Tn, 1,
-                               static_cast<long long>(ctot) * 12 * Tn, coff, total);
-        }
-        if (!train) return run_semi(n, n->semi[layer].eval, src, B, P, Tn, dst, ctot, coff, s, nm);
-        const PackedConv& pc = n->semi[layer].train;
-        const int bn = n->semi[layer].bn;
-        SemiTrainArgs ta;
-        std::memset(&ta, 0, sizeof(ta));
-        ta.s = semi_args(n, pc, src, P, Tn, b.semi_raw[layer]);
-        ta.in_affine = in_aff; ta.stats = b.stats + 2 * n->bns[bn].ch_off; ta.stats_stride = 2 * n->bn_channels;
-        if ((rc = launch_semi_conv(pc, ta, P, B))) return rc;
-        if ((rc = finalize_bn(bn, static_cast<double>(B) * (P / 3) * Tn, b.aff_semi[layer]))) return rc;
-        const long long total = static_cast<long long>(B) * pc.cin * 12 * Tn;
-        if (n->cfg.p2pc_conv) {   // models.py:108-133: the fold is a learned convolution over the octaves + BatchNorm (batch statistics) + LeakyReLU
-            const PackedConv& fc = n->foldc[layer].train;
-            const int bnf = n->foldc[layer].bn;
-            AKE_REQUIRE(pc.cin <= 64, AKE_ERR_UNSUPPORTED, "p2pc_conv training: %d channels", pc.cin);
-            if ((rc = launch_flat("fold_conv_kernel", fold_conv_train_kernel, s, total, b.semi_raw[layer], b.aff_semi[layer], n->blob_dev + fc.w_off,
-                                  n->blob_dev + fc.b_off, b.foldc_raw[layer], b.stats + 2 * n->bns[bnf].ch_off, 2 * n->bn_channels, pc.cin, P / 36, Tn, total)))
-                return rc;
-            if ((rc = finalize_bn(bnf, static_cast<double>(B) * 12 * Tn, b.aff_foldc[layer]))) return rc;
-            // the folded channels are materialised as final activations: every reader of the concat buffer takes them as they are
-            if ((rc = launch_flat("apply_affine_kernel", apply_affine_kernel, s, total, b.foldc_raw[layer], b.aff_foldc[layer], dst, pc.cin,
-                                  static_cast<long long>(12) * Tn, ctot, coff, total)))
-                return rc;
-        } else if ((rc = run_fold_max("fold_affine_kernel", b.semi_raw[layer], b.aff_semi[layer], pc.cin, P / 3, B, Tn, dst, ctot, coff, s))) return rc;
-        return aff_cat_rows ? identity(aff_cat_rows, pc.cin) : AKE_OK;     // the folded channels are final activations
-    }
-
-    int up_sixth(int layer, const float* src, long long src_clip_stride, const float* in_aff, int B, int C, int Tn, float* dst, float* aff_dst) {
-        const long long total = static_cast<long long>(B) * C * 36 * Tn;
-        if (!train)
-            return launch_flat("up_sixth_kernel", up_sixth_kernel<false>, s, total, src, src_clip_stride, nullptr, n->blob_dev + n->up[layer].eval.w_off,
-                               n->blob_dev + n->up[layer].eval.b_off, dst, nullptr, 0, C, Tn, total);
-        const int bn = n->up[layer].bn;
-        AKE_REQUIRE(C <= kBlockStatCh, AKE_ERR_UNSUPPORTED, "up_sixth training: %d channels", C);
-        const int rc = launch_flat("up_sixth_train_kernel", up_sixth_kernel<true>, s, total, src, src_clip_stride, in_aff, n->blob_dev + n->up[layer].train.w_off,
-                                   n->blob_dev + n->up[layer].train.b_off, dst, b.stats + 2 * n->bns[bn].ch_off, 2 * n->bn_channels, C, Tn, total);
-        return rc ? rc : finalize_bn(bn, static_cast<double>(B) * 36 * Tn, aff_dst);
-    }
-
-    int time_pool(const float* src, const float* in_aff, int B, int C, int H, int Tn, float* dst, int ctot, int coff) {
-        const int tp = n->cfg.time_pool_size;
-        const long long total = static_cast<long long>(B) * C * H * (Tn / tp);
-        return launch_flat("time_pool_kernel", time_pool_kernel, s, total, src, in_aff, dst, C, H, Tn, tp, ctot, coff, total);
-    }
-
-    // inference: semitone conv + BN + LeakyReLU of `src` [B][C][P][T] as a map of its own [B][C][P / 3][T] (raw = before the LeakyReLU)
-    int semi_map(int layer, const float* src, int B, int P, int Tn, float* dst, bool raw) {
-        const PackedConv& pc = n->semi[layer].eval;
-        SemiTrainArgs ta;
-        std::memset(&ta, 0, sizeof(ta));
-        ta.s = semi_args(n, pc, src, P, Tn, dst);
-        ta.out_lrelu = raw ? 0 : 1;
-        return launch_semi_conv(pc, ta, P, B);
-    }
-
-    // the octave fold of ready maps [B][C][S][T] into channels [coff, coff + C) of dst: max (models.py:95-106) or --p2pc_conv's convolution
-    int fold_maps(int layer, const float* maps, int C, int S, int B, int Tn, float* dst, int ctot, int coff) {
-        if (!n->cfg.p2pc_conv) return run_fold_max("fold_max_kernel", maps, nullptr, C, S, B, Tn, dst, ctot, coff, s);
-        const PackedConv& fc = n->foldc[layer].eval;
-        const long long total = static_cast<long long>(B) * C * 12 * Tn;
-        return launch_flat("fold_conv_kernel", fold_conv_kernel, s, total, maps, n->blob_dev + fc.w_off, n->blob_dev + fc.b_off, dst, C, S / 12, Tn, 0,
-                           static_cast<long long>(ctot) * 12 * Tn, coff, total);
-    }
-
-    // inference, default family: the whole of phase A as one launch, one workgroup per clip (the form and geometry are the route's)
-    int layer0_fused(const float* mel, int B) {
-        const auto& c = n->cfg;
-        const int P = c.pitches, T0 = b.Tl[0], NF = c.n_filters;
-        const bool take_mfma = r.l0.form == L0Form::FusedMfma;
-        AKE_REQUIRE(r.l0.form != L0Form::Generic && r.l0.lds > 0 && !(reinterpret_cast<uintptr_t>(mel) & 15), AKE_ERR_STATE,
-                    "pcnet: the route sent layer 0 to its one-launch form, which this call does not qualify for");
-        AKE_REQUIRE(!r.frames_major || take_mfma, AKE_ERR_STATE, "pcnet: the route promised the frames-major input to a layer-0 form that cannot read it");
-        AKE_REQUIRE(!r.psix_f16 || (take_mfma && b.melh), AKE_ERR_STATE, "pcnet: the route promised the f16 up_sixth map to a layer-0 form that does not write it");
-        const PackedConv& sp = n->semi[0].eval;
-        const LayerDims& d1 = n->dims[1];
-        Layer0Args a;
-        std::memset(&a, 0, sizeof(a));
-        a.RP = r.l0.RP; a.RPp = r.l0.RPp;
-        a.mel = mel; a.sw = n->blob_dev + sp.w_off; a.sb = n->blob_dev + sp.b_off;
-        const int ctot1 = d1.prev_pc + d1.out_p;
-        for (int j = 0; j < c.conv_layers; ++j) {
-            const PackedConv& pc = n->pc2pc[0][j].eval;
-            const bool lastj = j == c.conv_layers - 1;
-            a.w[j] = n->blob_dev + pc.w_off; a.b[j] = n->blob_dev + pc.b_off;
-            if (take_mfma) a.frag[j] = n->bf_frags_dev + pc.l0_off;
-            a.dst[j] = lastj ? b.cat[1] : b.pc_out(false, 0, j).p;
-            a.dst_clip_stride[j] = static_cast<long long>(lastj ? ctot1 : NF) * 12 * T0;
-        }
-        a.uw = n->blob_dev + n->up[1].eval.w_off; a.ub = n->blob_dev + n->up[1].eval.b_off;
-        a.fold0 = b.fold0; a.psix = b.psix[1];
-        a.H = P; a.T = T0; a.NF = NF; a.n_conv = c.conv_layers;
-        static ake::DeviceOnce fused_attr, mfma_attr;
-        int rc;
-        if ((rc = ake::raise_lds_limit(fused_attr, 150 * 1024, layer0_fused_kernel))) return rc;
-        if ((rc = ake::raise_lds_limit(mfma_attr, static_cast<int>(kL0MaxLds), layer0_mfma_kernel))) return rc;
-        a.mel_fm = r.frames_major ? 1 : 0;
-        a.frag_lds = r.l0.frag_lds ? 1 : 0;
-        a.img_tiled = r.l0.tiled ? 1 : 0; a.img_sq = r.l0.img_sq; a.img_sb = r.l0.img_sb; a.img_sr = r.l0.img_sr;
-        AKE_REQUIRE(!r.l0.tiled || r.frames_major, AKE_ERR_STATE, "pcnet: layer 0's image was planned for a frames-major input that the route refused");
-        AKE_REQUIRE(r.l0.lds <= kL0MaxLds, AKE_ERR_STATE, "pcnet: layer 0's one-launch form does not fit the LDS at this shape");
-        a.taps = g_keep_taps ? 1 : 0;
-        if (r.psix_f16) { a.psix_h = reinterpret_cast<uint2*>(b.psix[1]); a.psix = nullptr; a.melh = b.melh; }
-        if (take_mfma) return ake::launch("layer0_fused_kernel", layer0_mfma_kernel, dim3(B), dim3(512), r.l0.lds, s, a);
-        return ake::launch("layer0_fused_kernel", layer0_fused_kernel, dim3(B), dim3(512), r.l0.lds, s, a);
-    }
-
-    // Phase A, whole batch: layer 0 (models.py:361-369) and layer 1's up_sixth (models.py:372-374).
-    int entry(const float* mel, int B) {
-        const auto& c = n->cfg;
-        const int L = c.num_layers, P = c.pitches, T0 = b.Tl[0];
-        int rc;
-        if (r.l0.form != L0Form::Generic) return layer0_fused(mel, B);
-        if (c.stay_sixth && L > 1 && train) {   // training: the RAW semitone map (semi_raw[0]) + its pending table are the pitch stream
-            if ((rc = semi(0, mel, nullptr, B, P, T0, b.fold0, 1, 0, nullptr))) return rc;
-        } else if (c.stay_sixth && L > 1) {   // models.py:366-367: the activated semitone map is the pitch stream from here on; its fold feeds pc2pc
-            if ((rc = semi_map(0, mel, B, P, T0, b.p0, false))) return rc;
-            if ((rc = fold_maps(0, b.p0, 1, P / 3, B, T0, b.fold0, 1, 0))) return rc;
-        } else if (c.denseblock) {   // the fold is channel 0 of the block's feature buffer (L == 1: fold0 itself, else layer 1's concat buffer)
-            const int g = c.n_filters * c.conv_layers;
-            const int ctot1 = L == 1 ? 1 + g : n->dims[1].prev_pc + n->dims[1].out_p + g;
-            float* feat = L == 1 ? b.fold0 : b.cat[1];
-            if ((rc = semi(0, mel, nullptr, B, P, T0, feat, ctot1, 0, nullptr))) return rc;
-            if (L == 1) return AKE_OK;                           // its block runs in the tail
-            if ((rc = dense_stack(0, 1, feat, ctot1, 1, B, 12, T0, b.pca[0], "conv_mfma_kernel/pc2pc0"))) return rc;
-            // training: the raw up_sixth map + its table (rows [prev_p, ..) of the pitch block's input table, as in the default net)
-            if ((rc = up_sixth(1, feat, static_cast<long long>(ctot1) * 12 * T0, nullptr, B, n->dims[1].prev_pc, T0, b.psix[1], p2pin_up(1)))) return rc;
-            return AKE_OK;
-        } else if ((rc = semi(0, mel, nullptr, B, P, T0, b.fold0, 1, 0, nullptr))) return rc;
-        if (L == 1) return AKE_OK;                               // its pc2pc runs in the tail
-        const LayerDims& d1 = n->dims[1];
-        const int ctot1 = d1.prev_pc + d1.out_p;
-        Slot src{b.fold0, nullptr};
-        int cin = 1;
-        if (c.resblock && train) {   // the last block's output = channels [0, nf) of layer 1's concat buffer, final (identity table)
-            if ((rc = res_stack_train(n->pc2pc[0], 1, Src{b.fold0, 1, nullptr, 0, 0}, nullptr, B, 12, T0, b.pcst[0], b.aff_pcst[0], b.cat[1], ctot1,
-                                      "conv_mfma_kernel/pc2pc0")))
-                return rc;
-            if ((rc = identity(b.aff_cat[1], c.n_filters))) return rc;
-        } else if (c.resblock) {
-            if ((rc = res_stack(n->pc2pc[0], 1, Src{b.fold0, 1, nullptr, 0, 0}, B, 12, T0, b.pca[0], b.pcb[0], b.cat[1], ctot1, "conv_mfma_kernel/pc2pc0"))) return rc;
-        }
-        for (int j = 0; j < c.conv_layers && !c.resblock; ++j) {
-            const bool lastj = j == c.conv_layers - 1;           // the last conv writes channels [0, nf) of layer 1's concat buffer
-            const Slot dst = lastj ? b.cat_slot(train, 1) : b.pc_out(train, 0, j);
-            if ((rc = conv(n->pc2pc[0][j], 1, Src{src.p, cin, nullptr, 0, 0}, src.aff, B, 12, T0, true, dst.p, lastj ? ctot1 : c.n_filters, 0, dst.aff,
-                           "conv_mfma_kernel/pc2pc0")))
-                return rc;
-            src = dst; cin = c.n_filters;
-        }
-        if (c.stay_sixth) return AKE_OK;                         // no up_sixth: the pitch classes are repeated as they are
-        // psix's BatchNorm lands in rows [prev_p, ..) of the pitch-conv input table (row 0.. = the pitch stream itself)
-        if (train && (rc = identity(b.aff_p2pin[1], d1.prev_p))) return rc;
-        return up_sixth(1, b.cat[1], static_cast<long long>(ctot1) * 12 * T0, b.cat_slot(train, 1).aff, B, d1.prev_pc, T0, b.psix[1], p2pin_up(1));
-    }
-
-    // Phase B, per chunk of clips [c0, c0+B): pitch convs -> semitone fold for every layer >= 1 (plus pc2pc / pooling /
-    // the next up_sixth for the inner layers of deeper nets).
-    int pitch_chunk(const float* mel, int c0, int B) {
-        const auto& c = n->cfg;
-        const int L = c.num_layers, tp = c.time_pool_size;
-        const int P = c.stay_sixth ? c.pitches / 3 : c.pitches;  // rows of the pitch stream (--stay_sixth: semitones)
-        int rc;
-        // pitch stream [B][cp][P][T]: a final activation, except --stay_sixth in training (layer 0's raw semitone map + aff_semi[0])
-        const float* p_cur = c.stay_sixth ? (train ? b.semi_raw[0] : b.p0 + static_cast<size_t>(c0) * P * b.Tl[0]) : mel;
-        int cp = 1;
-        const float* pc_cur = nullptr;
-        for (int i = 1; i < L; ++i) {
-            const int Ti = b.Tl[i];
-            const LayerDims& d = n->dims[i];
-            const bool last = i == L - 1;
-            if (c.denseblock) {   // models.py:370-396 with dense stacks: both blocks grow their concat buffers in place
-                const int g = c.n_filters * c.conv_layers;
-                const int ctd = d.prev_pc + d.out_p + g;                             // = d.out_pc
-                float* catd = b.cat[i] + (last || i == 1 ? static_cast<size_t>(c0) * ctd * 12 * Ti : 0);
-                float* psixd = b.psix[i] + (i == 1 ? static_cast<size_t>(c0) * d.prev_pc * 36 * Ti : 0);
-                if (i > 1 && (rc = up_sixth(i, pc_cur, static_cast<long long>(ctd) * 12 * Ti, nullptr, B, d.prev_pc, Ti, psixd, p2pin_up(i)))) return rc;
-                float* fp = b.pa[i];                                                  // [B][out_p][P][Ti]
-                const long long total = static_cast<long long>(B) * (cp + d.prev_pc) * P * Ti;
-                if ((rc = launch_flat("concat_repeat_kernel", concat_repeat_kernel, s, total, p_cur, cp, psixd, d.prev_pc, 36, fp, d.out_p, P, Ti, total, p2pin_up(i))))
-                    return rc;
-                if ((rc = dense_stack(i, 0, fp, d.out_p, cp + d.prev_pc, B, P, Ti, b.pb[i], "conv_mfma_kernel/p2p"))) return rc;
-                if ((rc = semi(i, fp, nullptr, B, P, Ti, catd, ctd, d.prev_pc, nullptr))) return rc;
-                if (last) return AKE_OK;                                              // its pitch-class block + pooling + heads run batch-wide
-                if ((rc = dense_stack(i, 1, catd, ctd, d.prev_pc + d.out_p, B, 12, Ti, b.pca[i], "conv_mfma_kernel/pc2pc"))) return rc;
-                const LayerDims& dn = n->dims[i + 1];
-                const int ctn = dn.prev_pc + dn.out_p + g;
-                const int Tn = Ti / tp;
-                float* catn = b.cat[i + 1] + (i + 1 == L - 1 ? static_cast<size_t>(c0) * ctn * 12 * Tn : 0);
-                if ((rc = time_pool(catd, nullptr, B, ctd, 12, Ti, catn, ctn, 0))) return rc;
-                if ((rc = time_pool(fp, nullptr, B, d.out_p, P, Ti, b.ppool[i], d.out_p, 0))) return rc;
-                pc_cur = catn; p_cur = b.ppool[i]; cp = d.out_p;
-                continue;
-            }
-            const int ctot = d.prev_pc + d.out_p;
-            float* cat = b.cat[i] + (last || i == 1 ? static_cast<size_t>(c0) * ctot * 12 * Ti : 0);
-            float* psix = b.psix[i] + (i == 1 ? static_cast<size_t>(c0) * d.prev_pc * 36 * Ti : 0);
-            if (i > 1 && !c.stay_sixth) {   // layer 1's up_sixth ran batch-wide in entry(); pc_cur = pooled (final) features here
-                if (train && (rc = identity(b.aff_p2pin[i], d.prev_p))) return rc;
-                if ((rc = up_sixth(i, pc_cur, static_cast<long long>(ctot) * 12 * Ti, nullptr, B, d.prev_pc, Ti, psix, p2pin_up(i)))) return rc;
-            }
-            // models.py:378-384  repeat + concat (never materialised) + pitch convs
-            Src sdesc{p_cur, cp, psix, d.prev_pc, 36};
-            if (c.stay_sixth) {   // models.py:322-323, 379-383: the pitch classes themselves, repeated over the octaves (a dense copy: they live
-                                  // in channels [0, prev_pc) of a concat buffer)
-                const float* pcs = i == 1 ? b.cat[1] + static_cast<size_t>(c0) * ctot * 12 * Ti : pc_cur;
-                const long long per_clip = static_cast<long long>(d.prev_pc) * 12 * Ti, total = per_clip * B;
-                if ((rc = launch_flat("slice_channels_kernel", slice_channels_kernel, s, total, pcs, static_cast<long long>(ctot) * 12 * Ti, b.pcd[i], per_clip, total)))
-                    return rc;
-                sdesc = Src{p_cur, cp, b.pcd[i], d.prev_pc, 12};
-                if (train) {   // the stack's input table: the pitch stream's rows, then the pitch classes' (they were copied raw)
-                    if (i == 1) AKE_HIP_CHECK(hipMemcpyAsync(b.aff_p2pin[i], b.aff_semi[0], sizeof(float) * 3 * cp, hipMemcpyDeviceToDevice, s));
-                    else if ((rc = identity(b.aff_p2pin[i], cp))) return rc;
-                    AKE_HIP_CHECK(hipMemcpyAsync(b.aff_p2pin[i] + 3 * cp, b.aff_cat[i], sizeof(float) * 3 * d.prev_pc, hipMemcpyDeviceToDevice, s));
-                }
-            }
-            if (c.pc2p_mem) {   // models.py:376-377: no concat, the summed up_sixth map is added to the pitch stream
-                const long long total = static_cast<long long>(B) * cp * P * Ti;
-                // (training: psix is raw, its up_sixth_b table sits behind the pitch stream's identity rows; the sum itself is final)
-                if ((rc = launch_flat("pc2p_mem_kernel", pc2p_mem_kernel, s, total, p_cur, psix, b.pin[i], cp, d.prev_pc / cp, P, Ti, total, p2pin_up(i)))) return rc;
-                sdesc = Src{b.pin[i], cp, nullptr, 0, 0};
-            }
-            const float* in_aff = train ? b.aff_p2pin[i] : nullptr;
-            Slot out;                             // the stack's last output
-            // inference: the stack runs on f16 MFMA (f16 activations x hi + lo f16 weights, see conv_p2p_f16_kernel); the activations
-            // between its convs are ONE channels-last f16 plane (16 B per position) in the same ping-pong buffers
-            const Route::Pitch& rp = r.p[i];
-            const Route::Pitch::PerChunk& rk = rp.k[r.chunk_kind(B)];
-            P2pOut last_out = P2pOut::Nchw;       // what the stack's last launch left: the pitch tensor, the semitone maps, or the folded maps in `cat`
-            if (c.resblock && train) {
-                if ((rc = res_stack_train(n->p2p[i], 0, sdesc, in_aff, B, P, Ti, b.pst[i], b.aff_pst[i], nullptr, 0, "conv_mfma_kernel/p2p")))
-                    return rc;
-                out = b.p_last(i);
-            } else if (c.resblock) {
-                if ((rc = res_stack(n->p2p[i], 0, sdesc, B, P, Ti, b.pa[i], b.pb[i], nullptr, 0, "conv_mfma_kernel/p2p"))) return rc;
-                out = Slot{b.pa[i], nullptr};
-            }
-            const bool one_launch = rp.stack == PStack::F16 && rk.stack.ok;
-            if (one_launch) {      // the whole stack, semitone conv and fold as one launch
-                unsigned short* planes[kP2pStackMax];
-                for (int j = 0; j < kP2pStackMax; ++j) planes[j] = reinterpret_cast<unsigned short*>(b.p_out(false, i, j).p);
-                if ((rc = run_p2p_stack(n, n->p2p[i], n->semi[i].eval, rk.stack, b.melh + static_cast<size_t>(c0) * P * Ti,
-                                        reinterpret_cast<const uint2*>(b.psix[1]) + static_cast<size_t>(c0) * 36 * Ti, d.prev_pc, planes, cat, ctot, d.prev_pc, B, P, Ti, s,
-                                        "conv_p2p_f16_kernel")))
-                    return rc;
-                out = b.p_out(false, i, c.conv_layers - 1);
-                last_out = P2pOut::SemiFold;
-            }
-            for (int j = 0; j < c.conv_layers && !c.resblock && !one_launch; ++j) {
-                out = b.p_out(train, i, j);
-                if (rp.stack == PStack::F16) {
-                    const bool last_conv = j == c.conv_layers - 1;
-                    const P2pPsPlan& g = j == 0 ? rk.first : (last_conv ? rk.last : rk.mid);
-                    P2pPsIo io;
-                    io.in = g.in; io.out = g.out;
-                    io.dst_ctot = d.out_p;
-                    if (j > 0) io.planes = reinterpret_cast<const unsigned short*>(b.p_out(false, i, j - 1).p);
-                    else if (g.in == P2pIn::SrcF16x4)   // layer 0 left the CQT and the up_sixth map as f16 words (8 bytes per position of the map, clip stride 36 T words)
-                        io.src = Src{reinterpret_cast<const float*>(b.melh + static_cast<size_t>(c0) * P * Ti), 1,
-                                     reinterpret_cast<const float*>(reinterpret_cast<const uint2*>(b.psix[1]) + static_cast<size_t>(c0) * 36 * Ti), d.prev_pc, 36};
-                    else io.src = sdesc;              // the stack's input (pitch stream | repeated up_sixth output) is assembled by the kernel's own loader
-                    switch (g.out) {
-                        case P2pOut::Plane: io.plane = reinterpret_cast<unsigned short*>(out.p); break;
-                        case P2pOut::Nchw: io.dst = out.p; break;
-                        case P2pOut::Semi: io.dst = out.p; io.semi = &n->semi[i].eval; break;       // `out` receives the semitone maps [clip][8][P / 3][T]
-                        case P2pOut::SemiFold: io.dst = cat; io.dst_ctot = ctot; io.fold_coff = d.prev_pc; io.semi = &n->semi[i].eval; break;
-                    }
-                    if (last_conv) last_out = g.out;
-                    AKE_REQUIRE(g.ok || g.in == P2pIn::Planes || g.in == P2pIn::Src, AKE_ERR_STATE,
-                                "pcnet: the route promised an input form only the persistent pitch conv reads, for a chunk (%d clips) it does not take", B);
-                    if (g.ok) rc = run_p2p_f16_ps(n, n->p2p[i][j].eval, g, io, B, P, Ti, s, "conv_p2p_f16_kernel");
-                    else rc = run_p2p_f16(n, n->p2p[i][j].eval, io.planes, j == 0 ? &io.src : nullptr, B, P, Ti, io.dst, d.out_p, io.plane, s, "conv_p2p_f16_kernel");
-                    if (rc) return rc;
-                    continue;
-                }
-                if (rp.x3_convs >> j & 1) {   // f16 x 3 on the persistent form; else the f32 MFMA kernel
-                    const PackedConv& px = train ? n->p2p[i][j].train : n->p2p[i][j].eval;
-                    const int bn = train ? n->p2p[i][j].bn : -1;
-                    P2pX3Opts ox;
-                    ox.lrelu = !train;             // (training: the BatchNorm finalised below comes first)
-                    if ((rc = run_p2p_f16x3(n, rk.x3[j > 0], px.bf_off, sdesc, in_aff, n->blob_dev + px.b_off, B, P, Ti, out.p, d.out_p,
-                                            train ? b.stats + 2 * n->bns[bn].ch_off : nullptr, train ? 2 * n->bn_channels : 0, s, "conv_p2p_f16x3_kernel/p2p", ox)))
-                        return rc;
-                    if (train && (rc = finalize_bn(bn, static_cast<double>(B) * P * Ti, out.aff))) return rc;
-                } else if ((rc = conv(n->p2p[i][j], 0, sdesc, in_aff, B, P, Ti, true, out.p, d.out_p, 0, out.aff, "conv_mfma_kernel/p2p")))
-                    return rc;
-                sdesc = Src{out.p, d.out_p, nullptr, 0, 0};
-                in_aff = out.aff;
-            }
-            // models.py:386-392  pool_semi -> fold, written next to pc in the concat buffer
-            if (last_out == P2pOut::SemiFold) {
-            } else if (last_out == P2pOut::Semi) {
-                if ((rc = run_fold_max("fold_max_kernel", out.p, nullptr, d.out_p, P / 3, B, Ti, cat, ctot, d.prev_pc, s))) return rc;
-            } else if (c.stay_sixth && train) {   // ... through the last conv's pending BatchNorm + LeakyReLU
-                if ((rc = run_fold_max("fold_affine_kernel", out.p, out.aff, d.out_p, P, B, Ti, cat, ctot, d.prev_pc, s))) return rc;
-                if ((rc = identity(b.aff_cat[i] + 3 * d.prev_pc, d.out_p))) return rc;
-            } else if (c.stay_sixth) {   // models.py:391: the stack's output is folded as it is (no semitone conv)
-                if ((rc = fold_maps(i, out.p, d.out_p, P, B, Ti, cat, ctot, d.prev_pc))) return rc;
-            } else if ((rc = semi(i, out.p, out.aff, B, P, Ti, cat, ctot, d.prev_pc, train ? b.aff_cat[i] + 3 * d.prev_pc : nullptr))) return rc;
-            if (last) return AKE_OK;                             // pc2pc + pooling + heads run batch-wide
-            // inner layers of deeper nets: pc2pc, then both time pools (models.py:393-396)
-            Slot psrc{cat, b.cat_slot(train, i).aff};
-            int cin = ctot;
-            Slot pdst;
-            if (c.resblock && train) {
-                if ((rc = res_stack_train(n->pc2pc[i], 1, Src{psrc.p, cin, nullptr, 0, 0}, psrc.aff, B, 12, Ti, b.pcst[i], b.aff_pcst[i],
-                                          nullptr, 0, "conv_mfma_kernel/pc2pc")))
-                    return rc;
-                pdst = b.pc_last(i);
-            } else if (c.resblock) {
-                if ((rc = res_stack(n->pc2pc[i], 1, Src{psrc.p, cin, nullptr, 0, 0}, B, 12, Ti, b.pca[i], b.pcb[i], nullptr, 0, "conv_mfma_kernel/pc2pc"))) return rc;
-                pdst = Slot{b.pca[i], nullptr};
-            }
-            for (int j = 0; j < c.conv_layers && !c.resblock; ++j) {
-                pdst = b.pc_out(train, i, j);
-                if ((rc = conv(n->pc2pc[i][j], 1, Src{psrc.p, cin, nullptr, 0, 0}, psrc.aff, B, 12, Ti, true, pdst.p, d.out_pc, 0, pdst.aff, "conv_mfma_kernel/pc2pc")))
-                    return rc;
-                psrc = pdst; cin = d.out_pc;
-            }
-            const LayerDims& dn = n->dims[i + 1];
-            const int ctn = dn.prev_pc + dn.out_p;
-            const int Tn = Ti / tp;
-            float* catn = b.cat[i + 1] + (i + 1 == L - 1 ? static_cast<size_t>(c0) * ctn * 12 * Tn : 0);
-            if ((rc = time_pool(pdst.p, pdst.aff, B, d.out_pc, 12, Ti, catn, ctn, 0))) return rc;
-            if (train && (rc = identity(b.aff_cat[i + 1], d.out_pc))) return rc;
-            if ((rc = time_pool(out.p, out.aff, B, d.out_p, P, Ti, b.ppool[i], d.out_p, 0))) return rc;
-            pc_cur = catn; p_cur = b.ppool[i]; cp = d.out_p;
-        }
-        return AKE_OK;
-    }
-
-    // Phase C, whole batch: last layer's pc2pc, time pool, heads, masked mean.
-    int tail(int B, const int64_t* seq, float* key_out, float* tonic_out, float* genre_out) {
-        const auto& c = n->cfg;
-        const int L = c.num_layers, tp = c.time_pool_size;
-        const int i = L - 1;
-        const int Ti = b.Tl[i];
-        const LayerDims& d = n->dims[i];
-        int rc;
-        Slot psrc = L == 1 ? Slot{b.fold0, nullptr} : b.cat_slot(train, i);
-        int cin = L == 1 ? 1 : d.prev_pc + d.out_p;
-        const int cout_default = L == 1 ? c.n_filters : d.out_pc;
-        const int cout = cout_default;
-        Slot pdst;
-        // inference, 16-channel stacks: bf16 MFMA with split operands; the stack's input is converted to channels-last planes once,
-        // the intermediate activations stay in that format (same 64 B per position as 16 f32 channels: the ping-pong buffers are
-        // reused), the last convolution writes NCHW f32 for the pooling / heads
-        const bool pc_bf = r.pc == PcStack::Bf16, pc_fused = r.pc == PcStack::Fused;
-        // heads on the bf16 kernels read a channels-last copy of the pooled features (the fused stack writes it itself)
-        const bool head_bf = r.heads != HeadForm::Generic;
-        if (pc_fused) {
-            if ((rc = run_pc2pc_fused(n, i, psrc.p, cin, B, Ti, b.pcf, head_bf ? b.feat_cl : nullptr, s))) return rc;
-        } else if (pc_bf && (rc = run_nchw_to_cl16(psrc.p, cin, B, Ti, reinterpret_cast<unsigned short*>(b.pcb[i]), s))) return rc;
-        const char* const pc_label = L == 1 ? "conv_mfma_kernel/pc2pc0" : "conv_mfma_kernel/pc2pc";
-        if (c.resblock && train) {
-            if ((rc = res_stack_train(n->pc2pc[i], 1, Src{psrc.p, cin, nullptr, 0, 0}, psrc.aff, B, 12, Ti, b.pcst[i], b.aff_pcst[i], nullptr, 0, pc_label)))
-                return rc;
-            pdst = b.pc_last(i);
-        } else if (c.resblock) {
-            if ((rc = res_stack(n->pc2pc[i], 1, Src{psrc.p, cin, nullptr, 0, 0}, B, 12, Ti, b.pca[i], b.pcb[i], nullptr, 0, pc_label))) return rc;
-            pdst = Slot{b.pca[i], nullptr};
-        }
-        if (c.denseblock) {   // the last layer's pitch-class block, in place on its concat buffer: the features are the buffer itself
-            if ((rc = dense_stack(i, 1, psrc.p, n->final_ch, cin, B, 12, Ti, b.pca[i], pc_label))) return rc;
-            pdst = Slot{psrc.p, nullptr};
-        }
-        for (int j = 0; j < c.conv_layers && !pc_fused && !c.resblock && !c.denseblock; ++j) {
-            pdst = b.pc_out(train, i, j);
-            if (pc_bf) {
-                const bool last_conv = j == c.conv_layers - 1;
-                const unsigned short* in = reinterpret_cast<const unsigned short*>(j == 0 ? b.pcb[i] : b.pc_out(false, i, j - 1).p);   // (the stack's input planes: pcb)
-                if ((rc = run_pc_bf16(n, n->pc2pc[i][j].eval, in, B, Ti, true, true, last_conv ? pdst.p : nullptr,
-                                      last_conv ? nullptr : reinterpret_cast<unsigned short*>(pdst.p), s, "conv_pc_bf16_kernel/pc2pc")))
-                    return rc;
-                continue;
-            }
-            if (r.pc_x3_convs >> j & 1) {   // f16 x 3 MFMA (f32-equivalent products) instead of the f32 MFMA kernel
-                const PackedConv& pt = n->pc2pc[i][j].train;
-                unsigned short* planes = reinterpret_cast<unsigned short*>(b.pcb[i]);       // (the inference ping-pong buffer: idle in training)
-                if ((rc = run_nchw_to_cl16_f16x2(psrc.p, cin, B, Ti, psrc.aff, planes, s))) return rc;
-                const int bn = n->pc2pc[i][j].bn;
-                PcBf16Opts o;
-                o.f16x3 = true; o.stats = b.stats + 2 * n->bns[bn].ch_off; o.stats_stride = 2 * n->bn_channels;
-                if ((rc = run_pc_bf16(n, pt, planes, B, Ti, true, false, pdst.p, nullptr, s, "conv_pc_f16x3_kernel/pc2pc", o))) return rc;
-                if ((rc = finalize_bn(bn, static_cast<double>(B) * 12 * Ti, pdst.aff))) return rc;
-            } else if ((rc = conv(n->pc2pc[i][j], 1, Src{psrc.p, cin, nullptr, 0, 0}, psrc.aff, B, 12, Ti, true, pdst.p, cout, 0, pdst.aff, pc_label)))
-                return rc;
-            psrc = pdst; cin = cout;
-        }
-        Slot feat = pdst;                         // features feeding the heads
-        if (pc_fused) feat = Slot{b.pcf, nullptr};
-        else if (L > 1) {   // models.py:396  (the pitch stream of the last layer feeds nothing: its pool is skipped)
-            const int cout = c.denseblock ? n->final_ch : cout_default;
-            if ((rc = time_pool(pdst.p, pdst.aff, B, cout, 12, Ti, b.pcf, cout, 0))) return rc;
-            feat = Slot{b.pcf, nullptr};
-        }
-        // ---- heads (models.py:750-753) ----
-        const int Tf = b.Tf;
-        const Head* const heads = n->heads;     // key, tonic, genre
-        int Tm = Tf;
-        bool head_planes_ready = false;           // training: the f16 hi / lo planes of the pooled features (b.feat_cl) exist
-        int pooled_heads = 0;                     // heads whose outputs conv_head1_bf16_kernel already wrote
-        // key / tonic heads: the first convolution (16 -> 32 channels, most of a head's work) on the bf16 kernel; both read the same
-        // channels-last copy of the features
-        unsigned short* feat_cl = b.feat_cl;
-        if (head_bf && !pc_fused && (rc = run_nchw_to_cl16(feat.p, n->final_ch, B, Tf, feat_cl, s))) return rc;
-        const bool head1_bf = r.heads == HeadForm::Head1 || r.heads == HeadForm::Fused, genre_bf = r.genre_bf;
-        const int T1 = r.T1, T2 = r.T2, TpB = r.TpB;
-        // per-head tables of the two bf16 paths (key, tonic, genre), and the pooling of a finished map
-        const int nh_bf = genre_bf ? 3 : 2;
-        float* const maps[3] = {b.map_k, b.map_t, b.map_g};
-        float* const outs[3] = {key_out, tonic_out, genre_out};
-        PoolArgs pool;
-        pool.seq = reinterpret_cast<const long long*>(seq);
-        pool.n_pool_layers = L - 1; pool.tp = tp; pool.shrink = (c.kernel_size - 1) * c.head_layers; pool.max_pool = c.max_pool; pool.clip0 = 0;
-        if (r.heads == HeadForm::Fused) {
-            const size_t hf_lds = r.hf_lds;
-            HeadsFusedArgs ha;
-            std::memset(&ha, 0, sizeof(ha));
-            ha.xh = feat_cl; ha.xl = feat_cl + static_cast<long long>(B) * 12 * Tf * 16;
-            for (int h = 0; h < nh_bf; ++h) {
-                const PackedConv& p0 = heads[h].convs[0].eval;
-                const PackedConv& p1 = heads[h].convs[1].eval;
-                ha.bfragA[h] = n->bf_frags_dev + p0.bf_off; ha.biasA[h] = n->blob_dev + p0.b_off; ha.KHA[h] = p0.kh;
-                ha.bfragB[h] = n->bf_frags_dev + p1.bf_off; ha.biasB[h] = n->blob_dev + p1.b_off; ha.KHB[h] = p1.kh;
-                ha.dst[h] = maps[h];
-                ha.pout[h] = outs[h];
-            }
-            // workgroups [i * B, (i + 1) * B) run head hs[i]; with a genre head its short workgroups come first: they hand their slots on early
-            if (genre_bf) { ha.hs[0] = 2; ha.hs[1] = 0; ha.hs[2] = 1; }
-            else { ha.hs[0] = 0; ha.hs[1] = 1; ha.hs[2] = 1; }
-            ha.batch = B; ha.T_in = Tf; ha.T1 = T1; ha.T2 = T2; ha.TpA = T1 + 8; ha.TpB = TpB; ha.JB = (T2 + 15) / 16;
-            ha.fin_off = static_cast<int>(hf_lds / sizeof(float)) - 12 * T2;
-            ha.pool = pool;
-            static ake::DeviceOnce hf_attr;
-            if ((rc = ake::raise_lds_limit(hf_attr, 150 * 1024, heads_fused_kernel<3>, heads_fused_kernel<4>))) return rc;
-            rc = r.heads_mt == 3 ? ake::launch("heads_fused_kernel", heads_fused_kernel<3>, dim3(nh_bf * B), dim3(512), hf_lds, s, ha)
-                                 : ake::launch("heads_fused_kernel", heads_fused_kernel<4>, dim3(nh_bf * B), dim3(512), hf_lds, s, ha);
-            if (rc) return rc;
-            pooled_heads = nh_bf;
-            Tm = T2;
-        } else if (head1_bf) {
-            Head1BfArgs ha;
-            std::memset(&ha, 0, sizeof(ha));
-            for (int h = 0; h < nh_bf; ++h) {
-                const PackedConv& p0 = heads[h].convs[0].eval;
-                const PackedConv& p1 = heads[h].convs[1].eval;
-                unsigned short* planes = reinterpret_cast<unsigned short*>(b.head_out(false, h, 0, false).p);
-                if (h == 0) {   // the key and the tonic head read the same features with the same geometry: one launch, blockIdx.y picks the head
-                    PcBf16Opts tonic;
-                    tonic.pc2 = &heads[1].convs[0].eval; tonic.planes_out2 = reinterpret_cast<unsigned short*>(b.head_out(false, 1, 0, false).p);
-                    if ((rc = run_pc_bf16(n, p0, feat_cl, B, Tf, false, true, nullptr, planes, s, "conv_pc_bf16_kernel/head", tonic))) return rc;
-                }
-                if (h == 2 && (rc = run_pc_bf16(n, p0, feat_cl, B, Tf, false, true, nullptr, planes, s, "conv_pc_bf16_kernel/genre_head")))
-                    return rc;
-                ha.xh[h] = planes; ha.xl[h] = planes + static_cast<long long>(B) * 12 * T1 * 32;
-                ha.bfrag[h] = n->bf_frags_dev + p1.bf_off; ha.bias[h] = n->blob_dev + p1.b_off; ha.dst[h] = maps[h];
-                ha.KH[h] = p1.kh; ha.circular[h] = p1.kh == 12 ? 1 : 0; ha.H_out[h] = ha.circular[h] ? 12 : 12 - p1.kh + 1;
-            }
-            ha.T_in = T1; ha.T_out = T2; ha.JB = (T2 + 15) / 16; ha.Tp = TpB;
-            // the patch, and after the multiply loop the partial tiles of the 8 waves in the same bytes (two workgroups per CU fit)
-            size_t lds = std::max(static_cast<size_t>(2) * 12 * ha.Tp * 4 * sizeof(uint4), static_cast<size_t>(8) * kHead1MT * 4 * 64 * sizeof(float));
-            if (r.heads_pool) {   // the masked mean + sigmoid of each finished map in the same launch (its LDS copy sits behind the patch / partial tiles)
-                ha.fin_off = static_cast<int>(lds / sizeof(float));
-                lds += static_cast<size_t>(12) * T2 * sizeof(float);
-                for (int h = 0; h < nh_bf; ++h) ha.pout[h] = outs[h];
-                ha.pool = pool;
-                pooled_heads = nh_bf;
-            }
-            static ake::DeviceOnce h1_attr;
-            if ((rc = ake::raise_lds_limit(h1_attr, 150 * 1024, conv_head1_bf16_kernel))) return rc;
-            AKE_REQUIRE(lds <= 150 * 1024, AKE_ERR_UNSUPPORTED, "heads: %d frames do not fit conv_head1_bf16_kernel", T1);
-            if ((rc = ake::launch("conv_head1_bf16_kernel", conv_head1_bf16_kernel, dim3(B, nh_bf), dim3(512), lds, s, ha))) return rc;
-            Tm = T2;
-        }
-        for (int h = head1_bf ? nh_bf : 0; h < (c.genre ? 3 : 2); ++h) {
-            for (int j = 0; j < c.head_layers; ++j) {
-                const ConvSite& cs = heads[h].convs[j];
-                const PackedConv& pe = cs.eval;
-                const bool lastj = j == c.head_layers - 1;
-                // conv j reads the features or conv j - 1's output, hc channels of Tcur frames
-                const Slot src = j == 0 ? feat : b.head_out(train, h, j - 1, false);
-                const int hc = j == 0 ? n->final_ch : heads[h].convs[j - 1].eval.cout, Tcur = Tf - j * (c.kernel_size - 1);
-                const Slot dst = b.head_out(train, h, j, lastj);
-                if (head_bf && h < 2 && j == 0) {
-                    if ((rc = run_pc_bf16(n, pe, feat_cl, B, Tcur, false, true, dst.p, nullptr, s, "conv_pc_bf16_kernel/head"))) return rc;
-                    continue;
-                }
-                if (train && j == 0 && !lastj && pc_f16x3_ok(cs.train, Tcur, false)) {   // the heads' first convs: f16 x 3 MFMA
-                    const PackedConv& pt = cs.train;
-                    if (!head_planes_ready) {               // one conversion of the pooled features serves the three heads
-                        if ((rc = run_nchw_to_cl16_f16x2(src.p, hc, B, Tcur, src.aff, b.feat_cl, s))) return rc;
-                        head_planes_ready = true;
-                    }
-                    const int bn = cs.bn;
-                    PcBf16Opts o;
-                    o.f16x3 = true; o.stats = b.stats + 2 * n->bns[bn].ch_off; o.stats_stride = 2 * n->bn_channels;
-                    if ((rc = run_pc_bf16(n, pt, b.feat_cl, B, Tcur, false, false, dst.p, nullptr, s,
-                                          h == 2 ? "conv_pc_f16x3_kernel/genre_head" : "conv_pc_f16x3_kernel/head", o)))
-                        return rc;
-                    const int H_out = heads[h].kind == 2 ? 12 - pt.kh + 1 : 12;
-                    if ((rc = finalize_bn(bn, static_cast<double>(B) * H_out * (Tcur - pt.kw + 1), dst.aff))) return rc;
-                    continue;
-                }
-                if (train && lastj && j > 0 && pe.cout == 1 && pe.kw == 7 && !n->raw_w_off.empty()) {   // cin -> 1: one workgroup per clip, f32 VALU
-                    const size_t lds = (static_cast<size_t>(hc) * 12 * Tcur + static_cast<size_t>(hc) * pe.kh * 7) * sizeof(float);
-                    if (lds <= 150 * 1024 && Tcur - 6 >= 1) {
-                        static ake::DeviceOnce hl_attr;
-                        if ((rc = ake::raise_lds_limit(hl_attr, 150 * 1024, conv_head_last_kernel))) return rc;
-                        if ((rc = ake::launch(h == 2 ? "conv_head_last_kernel/genre" : "conv_head_last_kernel", conv_head_last_kernel, dim3(B), dim3(384), lds, s,
-                                              src.p, src.aff, n->blob_dev + n->raw_w_off[cs.w], n->blob_dev + n->raw_w_off[cs.b], dst.p, hc, pe.kh,
-                                              heads[h].kind == 2 ? 0 : 1, Tcur, Tcur - 6)))
-                            return rc;
-                        continue;
-                    }
-                }
-                if ((rc = conv(cs, heads[h].kind, Src{src.p, hc, nullptr, 0, 0}, src.aff, B, 12, Tcur, false, dst.p, pe.cout, 0, dst.aff,
-                               h == 2 ? "conv_mfma_kernel/genre_head" : "conv_mfma_kernel/head")))
-                    return rc;
-            }
-            Tm = Tf - c.head_layers * (c.kernel_size - 1);
-        }
-        if (c.local > 0) {   // ---- --local: sliding-window max over the maps, per-frame outputs (models.py:720-722, 805-810) ----
-            AKE_REQUIRE(Tm >= c.local, AKE_ERR_INVALID, "pcnet --local: %d map frames are fewer than the pooling window %d", Tm, c.local);
-            LocalPoolArgs la;
-            std::memset(&la, 0, sizeof(la));
-            la.maps[0] = b.map_k; la.maps[1] = b.map_t; la.maps[2] = c.genre ? b.map_g : nullptr;
-            la.outs[0] = key_out; la.outs[1] = tonic_out; la.outs[2] = genre_out;
-            la.Tm = Tm; la.Tq = Tm - c.local + 1; la.W = c.local; la.batch = B;
-            return ake::launch("local_pool_kernel", local_pool_kernel, dim3(static_cast<unsigned>((static_cast<long long>(B) * 12 * Tm + 255) / 256), 3), dim3(256),
-                               0, s, la);
-        }
-        // ---- masked temporal mean, sigmoid (models.py:754-804) ----
-        PoolHeadArgs pa;
-        std::memset(&pa, 0, sizeof(pa));
-        pa.maps[0] = b.map_k; pa.maps[1] = b.map_t; pa.maps[2] = c.genre ? b.map_g : nullptr;
-        for (int h = 0; h < pooled_heads; ++h) pa.maps[h] = nullptr;
-        if (!pa.maps[0] && !pa.maps[1] && !pa.maps[2]) return AKE_OK;
-        pa.outs[0] = key_out; pa.outs[1] = tonic_out; pa.outs[2] = genre_out;
-        pa.rows[0] = 12; pa.rows[1] = 12; pa.rows[2] = 11;
-        pa.Tm = Tm; pa.batch = B; pa.pool = pool;
-        return ake::launch("head_pool_kernel", head_pool_kernel, dim3((B * 12 + 63) / 64, 3), dim3(64), 0, s, pa);
-    }
-};
-
-int forward_impl(const ake_pcnet* n, bool train, const float* mel, int batch, int frames, const int64_t* seq_length, float* key_out,
-                 float* tonic_out, float* genre_out, float* bn_stats_out, void* workspace, size_t ws_bytes, ake_stream_t stream,
-                 bool mel_frames_major = false) {
-    AKE_REQUIRE(n && mel && key_out && tonic_out, AKE_ERR_INVALID, "pcnet forward: null argument");
-    AKE_REQUIRE(n->finalized, AKE_ERR_STATE, "pcnet: ake_pcnet_finalize has not been called");
-    AKE_REQUIRE(train || !n->eval_frags_stale, AKE_ERR_STATE,
-                "pcnet: the last weight load was ake_pcnet_load_for_training_f32 (training fragments only): call ake_pcnet_load_from_device_f32 before inference");
-    AKE_REQUIRE(batch > 0 && frames > 0, AKE_ERR_INVALID, "pcnet: bad batch/frames");
-    AKE_REQUIRE(!n->cfg.genre || genre_out, AKE_ERR_INVALID, "pcnet: genre head enabled but genre_out is null");
-    const int chunk = train ? batch : std::min(batch, n->chunk_clips);     // batch statistics need the whole batch at once
-    Buffers b;
-    int rc = plan_buffers(n, batch, chunk, frames, workspace, &b, train);
-    if (rc) return rc;
-    AKE_REQUIRE(workspace && ws_bytes >= b.bytes, AKE_ERR_WORKSPACE, "pcnet: workspace %zu < %zu bytes", ws_bytes, b.bytes);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Route route = build_route(n, train, batch, chunk, frames, mel, workspace, mel_frames_major);
-    AKE_REQUIRE(!mel_frames_major || route.frames_major, AKE_ERR_UNSUPPORTED,
-                "pcnet: this configuration does not take the frames-major input (ake_pcnet_accepts_frames_major)");
-    if (train) AKE_HIP_CHECK(hipMemsetAsync(b.stats, 0, sizeof(double) * 2 * n->bn_channels * kStatSlots, s));
-    Fwd f{n, b, s, train, route};
-    if ((rc = f.entry(mel, batch))) return rc;
-    for (int c0 = 0; c0 < batch && n->cfg.num_layers > 1; c0 += chunk) {
-        const int B = std::min(chunk, batch - c0);
-        if ((rc = f.pitch_chunk(mel + static_cast<size_t>(c0) * n->cfg.pitches * frames, c0, B))) return rc;
-    }
-    if ((rc = f.tail(batch, seq_length, key_out, tonic_out, genre_out))) return rc;
-    if (train && bn_stats_out)
-        AKE_HIP_CHECK(hipMemcpyAsync(bn_stats_out, b.bstats, sizeof(float) * 3 * n->bn_channels, hipMemcpyDeviceToDevice, s));
-    return AKE_OK;
-}
-
-}  // namespace
+#include "pcnet_forward.h"
 
 #include "pcnet_backward.h"
 
@@ -3084,7 +1793,7 @@ static int train_site_lookup(const ake_pcnet* n, const Buffers& b, const std::st
             if (is(n->pc2pc[i][j])) {
                 // layer 0's last convolution of a deeper net writes channels [0, n_filters) of layer 1's concat buffer (table: aff_cat[1])
                 if (i == 0 && L > 1 && j == c.conv_layers - 1) {
-                    found(b.cat_slot(true, 1), c.n_filters, 12, Ti, static_cast<long long>(n->dims[1].prev_pc + n->dims[1].out_p) * 12 * Ti);
+                    found(b.cat_slot(true, 1), c.n_filters, 12, Ti, static_cast<long long>(b.cat_ch(1)) * 12 * Ti);
                 } else found(b.pc_out(true, i, j), i == 0 ? c.n_filters : d.out_pc, 12, Ti);
             }
     }

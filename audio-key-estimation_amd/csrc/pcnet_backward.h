@@ -277,22 +277,22 @@ struct Bwd {
     // cat[1].  An inner layer's two streams each have a second consumer, the time-pooled copies the layer above starts from (models.py:394-395).
     int run_dense(const float* mel) {
         const auto& c = n->cfg;
-        const int L = c.num_layers, P = c.pitches, tp = c.time_pool_size, g = c.n_filters * c.conv_layers;
+        const int L = c.num_layers, P = c.pitches, tp = c.time_pool_size;
         int rc;
         for (int li = L - 1; li >= 1; --li) {
             const LayerDims& d = n->dims[li];
-            const int Tl = b.Tl[li], ctd = d.prev_pc + d.out_p + g;
+            const int Tl = b.Tl[li], ctd = b.cat_ch(li);
             {   // the time-pooled copy of the whole concat buffer: the heads' input (last layer) or the first channels of the next layer's buffer
                 const long long total = static_cast<long long>(B) * ctd * 12 * ((Tl / tp) + (Tl % tp ? 1 : 0));
                 const bool last = li == L - 1;
-                const int up_ctot = last ? ctd : n->dims[li + 1].prev_pc + n->dims[li + 1].out_p + g;
+                const int up_ctot = last ? ctd : b.cat_ch(li + 1);
                 if ((rc = launch_flat("time_pool_bwd_kernel", time_pool_bwd_kernel, s, total, last ? b.g_pcf : b.g_cat[li + 1], b.cat[li], nullptr, b.g_cat[li], ctd, 12,
                                       Tl, tp, up_ctot, 0, total, 0)))
                     return rc;
             }
             float* scr_pc = b.g_pc[li];                      // [B][ctd][12][Tl] scratch (g_pc[li] holds two of them)
-            if ((rc = dense_block_backward(n->dense_pc[li], 1, b.cat[li], ctd, d.prev_pc + d.out_p, 12, Tl, b.g_cat[li], b.dn_gbott_pc, scr_pc, b.dn_bott_pc[li],
-                                           b.dn_aff1_pc[li], b.dn_aff2_pc[li], "conv_wgrad_kernel/pc2pc", "conv_mfma_kernel/pc2pc_dgrad")))
+            if ((rc = dense_block_backward(n->dense_pc[li], 1, b.cat[li], ctd, d.prev_pc + d.out_p, 12, Tl, b.g_cat[li], b.dn[1].gbott, scr_pc, b.dn[1].bott[li],
+                                           b.dn[1].aff1[li], b.dn[1].aff2[li], "conv_wgrad_kernel/pc2pc", "conv_mfma_kernel/pc2pc_dgrad")))
                 return rc;
             // folded semitone maps -> pool_semi(li) -> dL/d(pitch features), all out_p channels
             float* g_p = b.g_p[li];
@@ -304,8 +304,8 @@ struct Bwd {
                                       n->dims[li + 1].out_p, 0, total, 1)))
                     return rc;
             }
-            if ((rc = dense_block_backward(n->dense_p[li], 0, b.pa[li], d.out_p, d.prev_p + d.prev_pc, P, Tl, g_p, b.dn_gbott_p, scr_p, b.dn_bott_p[li], b.dn_aff1_p[li],
-                                           b.dn_aff2_p[li], "conv_wgrad_kernel/p2p", "conv_mfma_kernel/p2p_dgrad")))
+            if ((rc = dense_block_backward(n->dense_p[li], 0, b.pa[li], d.out_p, d.prev_p + d.prev_pc, P, Tl, g_p, b.dn[0].gbott, scr_p, b.dn[0].bott[li], b.dn[0].aff1[li],
+                                           b.dn[0].aff2[li], "conv_wgrad_kernel/p2p", "conv_mfma_kernel/p2p_dgrad")))
                 return rc;
             {   // repeat (x P / 36) backward: channels [prev_p, prev_p + prev_pc) of the pitch block's input gradient -> the up_sixth map
                 const long long total = static_cast<long long>(B) * d.prev_pc * 36 * Tl;
@@ -323,10 +323,9 @@ struct Bwd {
             }
         }
         // layer 0's block: channels [0, 1 + g) of layer 1's buffer, input = the fold (channel 0)
-        const LayerDims& d1 = n->dims[1];
-        const int T1 = b.Tl[1], ctd1 = d1.prev_pc + d1.out_p + g;
-        if ((rc = dense_block_backward(n->dense_pc[0], 1, b.cat[1], ctd1, 1, 12, T1, b.g_cat[1], b.dn_gbott_pc, b.g_pc[1], b.dn_bott_pc[0], b.dn_aff1_pc[0],
-                                       b.dn_aff2_pc[0], "conv_wgrad_kernel/pc2pc0", "conv_mfma_kernel/pc2pc0_dgrad")))
+        const int T1 = b.Tl[1], ctd1 = b.cat_ch(1);
+        if ((rc = dense_block_backward(n->dense_pc[0], 1, b.cat[1], ctd1, 1, 12, T1, b.g_cat[1], b.dn[1].gbott, b.g_pc[1], b.dn[1].bott[0], b.dn[1].aff1[0],
+                                       b.dn[1].aff2[0], "conv_wgrad_kernel/pc2pc0", "conv_mfma_kernel/pc2pc0_dgrad")))
             return rc;
         return semi_backward(0, mel, nullptr, b.g_cat[1], ctd1, 0, nullptr);
     }
@@ -465,8 +464,8 @@ struct Bwd {
         planes_scratch = nullptr;
         if (c.denseblock && L == 1) {   // g_pc[0] = dL/d(fold | the block's growth), [B][fin][12][T]; its second half is the block's scratch
             float* gf = b.g_pc[0];
-            if ((rc = dense_block_backward(n->dense_pc[0], 1, b.fold0, fin, 1, 12, Ti, gf, b.dn_gbott_pc, gf + static_cast<size_t>(B) * fin * 12 * Ti, b.dn_bott_pc[0],
-                                           b.dn_aff1_pc[0], b.dn_aff2_pc[0], "conv_wgrad_kernel/pc2pc0", "conv_mfma_kernel/pc2pc0_dgrad")))
+            if ((rc = dense_block_backward(n->dense_pc[0], 1, b.fold0, fin, 1, 12, Ti, gf, b.dn[1].gbott, gf + static_cast<size_t>(B) * fin * 12 * Ti, b.dn[1].bott[0],
+                                           b.dn[1].aff1[0], b.dn[1].aff2[0], "conv_wgrad_kernel/pc2pc0", "conv_mfma_kernel/pc2pc0_dgrad")))
                 return rc;
             return semi_backward(0, mel, nullptr, gf, fin, 0, nullptr);
         }
@@ -492,7 +491,7 @@ struct Bwd {
             const LayerDims& dl = n->dims[li];
             const int Tl = b.Tl[li];
             const int Pp = c.stay_sixth ? P / 3 : P;              // rows of the pitch stream (--stay_sixth: semitone resolution)
-            const int ctot = dl.prev_pc + dl.out_p;
+            const int ctot = b.cat_ch(li);
             const bool inner = li < L - 1;
             float* gl = b.g_pc[li];
             float* gl2 = gl + static_cast<size_t>(B) * dl.out_pc * 12 * Tl;
@@ -561,7 +560,7 @@ struct Bwd {
                     return rc;
             }
         }
-        const int ctot = n->dims[1].prev_pc + n->dims[1].out_p;
+        const int ctot = b.cat_ch(1);
         const int T0 = b.Tl[1];
         // ---- layer 0: its last conv's activation = channels [0, nf) of the concat buffer (two consumers, both summed into g_cat) ----
         {

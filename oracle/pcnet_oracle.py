@@ -293,7 +293,7 @@ def _p2p_ps_rows_semi(H, T):
 
 def mixed_route(sd, frames, kernel_size=7, head_layers=2, time_pool_size=2, local=False, keep_taps=False, pitches=None):
     """Which convolutions the device's ``mixed`` inference forward multiplies in reduced precision for THIS net at THIS frame count, as
-    ``rounding_model`` wants them: a restatement of the arithmetic side of ``build_route()`` (csrc/pcnet.hip) and of the eligibility rules
+    ``rounding_model`` wants them: a restatement of the arithmetic side of ``build_route()`` (csrc/pcnet_plan.h) and of the eligibility rules
     of ``rebuild_bf16_frags()``.  Which launch form runs a stage (per tile, persistent, one launch, fused heads) does not change what is
     rounded -- those forms are bit-identical to one another -- so batch size and CU count do not enter.  tests/test_gpu_sensitive.py holds
     this restatement to the kernel timer's labels of the forward it models.

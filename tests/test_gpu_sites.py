@@ -1,6 +1,6 @@
 """Every configuration's convolution sites, through the C ABI: set_tensor + finalize, one training forward, one backward.
 
-ake_pcnet_finalize resolves each convolution's packs, BatchNorm and gradient slots once (ConvSite, csrc/pcnet.hip) and refuses a net in
+ake_pcnet_finalize resolves each convolution's packs, BatchNorm and gradient slots once (ConvSite, csrc/pcnet_net.h) and refuses a net in
 which a BatchNorm or a parameter belongs to no site.  A site that the forward or the backward walk then skipped would still leave that
 parameter's gradient at exact zeros, which the gradient tests only notice for the few configurations they cover.  This file runs the wider
 matrix at the smallest shapes and asks only what does not need a reference: the calls return 0, every learnable tensor has a range of

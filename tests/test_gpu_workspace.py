@@ -13,7 +13,7 @@ its 0xFF fill; every guard is intact.  The outputs under (c) are also held to th
 uses, so "all four agree" cannot mean "all four wrong".
 
 Before poisoning, the carves were read for regions that carry indices, offsets or counts a kernel reads before the call writes them:
-  - the net (plan_buffers, csrc/pcnet.hip): activations (f32, f16 / split-bf16 words), per-channel tables, fixed-point partial sums and
+  - the net (plan_buffers, csrc/pcnet_plan.h): activations (f32, f16 / split-bf16 words), per-channel tables, fixed-point partial sums and
     statistics that are memset at the start of the call that reads them -- no index-bearing region;
   - forward_windows / pipeline / track (csrc/track.hip, csrc/pipeline.hip): the gathered or transformed mel, a seq_length table that is
     refilled before every forward, then the embedded CQT and net workspaces;
