@@ -5,7 +5,7 @@ root aliases it).  Reference-shaped modules: ``models`` (PitchClassNet), ``KeyDa
 (KeyDataset + loaders), ``cqt`` (librosa.cqt stand-in), ``metrics`` (MIREX score).
 """
 from . import _lib  # noqa: F401
-from .audio import Resampler, get_resampler, pcm16_to_float, prepare as prepare_audio  # noqa: F401
+from .audio import Resampler, StreamResampler, get_resampler, pcm16_to_float, prepare as prepare_audio  # noqa: F401
 from .cqt import CQTPlan, cqt_logmag, get_any_hop_plan, get_plan, hop_for, hop_for_window  # noqa: F401
 from .KeyDataset import DatasetLoader, KeyDataset, SyntheticSineMixLoader, WaveformLoader  # noqa: F401
 from .metrics import (KEY_NAMES, KEY_PROFILES, KEY_SIGNATURE_MAP, decode_keys, key_emissions, key_posteriors, key_stream, key_stream_posteriors, key_transition_log, mirex_score,  # noqa: F401
@@ -30,4 +30,4 @@ __all__ = ["PitchClassNet", "KeyDataset", "DatasetLoader", "SyntheticSineMixLoad
            "transition_from_labels", "synth_partials", "TrackWindows", "draw_windows", "window_batch", "window_labels", "weighted_general_step",
            "estimate_tuning", "retune", "retune_out_len", "retune_reference",
            "profile_emissions", "fit_key_profiles", "KEY_PROFILES", "key_sequence_loss",
-           "key_stream", "KeyStream", "StreamUpdate", "key_stream_posteriors"]
+           "key_stream", "KeyStream", "StreamUpdate", "key_stream_posteriors", "StreamResampler"]

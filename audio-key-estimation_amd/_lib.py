@@ -121,6 +121,10 @@ SYMBOLS = {
     "ake_resampler_out_len": (_I64, [_P, _I64]),
     "ake_resample_f32": (_I, [_P, _P, _I, _I, _I64, _I64, _I64, _I, _P, _P, _I64, _P, _P]),
     "ake_resample_pcm16_f32": (_I, [_P, _P, _I, _I, _I64, _I64, _I64, _I64, _I, _P, _P, _I64, _P, _P]),
+    "ake_stream_resample_out_count": (_I64, [_P, _I64, _I]),
+    "ake_stream_resample_state_bytes": (_SZ, [_P, _I]),
+    "ake_stream_resample_f32": (_I, [_P, _P, _I, _I, _I64, _I64, _I64, _I, _I64, _I, _P, _SZ, _P, _I64, C.POINTER(_I64), _P]),
+    "ake_stream_resample_pcm16_f32": (_I, [_P, _P, _I, _I, _I64, _I64, _I64, _I64, _I, _I64, _I, _P, _SZ, _P, _I64, C.POINTER(_I64), _P]),
     "ake_tuning_workspace_bytes": (_SZ, [_I, _I]),
     "ake_tuning_estimate_f32": (_I, [_P, _I, _I, _I, _I, _P, C.c_float, _P, _P, _P, _SZ, _P]),
     "ake_retune_out_len": (_I64, [_I64]),

@@ -19,6 +19,7 @@
 #include "common.h"
 
 #include <cmath>
+#include <cstdint>
 #include <numeric>
 
 struct ake_resampler {
@@ -267,6 +268,136 @@ int retune_launch(const char* name, const T* in_dev, int batch, int64_t n_max, i
     return ake::launch(name, retune_kernel<T>, dim3(static_cast<unsigned>((width + per_block - 1) / per_block), batch), dim3(kRetuneThreads), 0, s, a);
 }
 
+// ---- the polyphase resampler on audio that arrives in chunks (ake_stream_resample_*) ----
+// resample_kernel's sum over "what came before, then the chunk".  Input i of the stream is final output k's as soon as
+// floor((k down + half) / up) <= i, and output k needs no input in front of ceil((k down - half) / up): with n_before inputs seen, the
+// first output still to come reaches back at most floor(2 half / up) inputs.  Those are carried per recording as a ring of `tail`
+// float32, input i at slot i % tail, holding the channel SUM (the 1 / channels scale comes last, as in resample_kernel), so a float32
+// and a 16-bit stream carry the same values.
+//   stream_resample_kernel: a workgroup makes kSrTile consecutive outputs of one recording.  It first stages the tile's input stretch in
+//     LDS, every sample mixed once (ring slot for i < n_before, the chunk behind it), then runs resample_kernel's ascending fmaf chain on
+//     it with the same i_lo / i_hi clamps: the output is bit-identical to the offline kernel's on the concatenated audio.
+//   stream_resample_tail_kernel: the last `tail` inputs of the chunk go into their ring slots.
+// Two launches, not one: the slots the chunk's end lands on are the slots the tile at the chunk's front still reads (whenever the chunk
+// is longer than the ring), and those are different workgroups as soon as there is more than one tile.  The stream orders the launches;
+// the first only reads the ring, the second only writes it, so no workgroup reads what another writes.  (One workgroup per recording
+// with load - barrier - store, stream_history_kernel's way, would put a 10 s chunk of one recording on a single CU.)
+constexpr int kSrThreads = 256, kSrTile = 512;
+constexpr size_t kSrMaxLds = 64 * 1024;
+
+template <typename T>
+struct StreamResampleArgs {
+    const T* chunk;             // [recordings][channels][m] by strides
+    long long rec_stride, channel_stride, sample_stride;
+    int channels, channel;
+    long long n_before, n_total;       // inputs in front of this chunk, and with it
+    long long k_first, k_count;        // outputs [k_first, k_first + k_count) are written
+    float* state;               // [recordings][tail]
+    int tail;
+    float* out;                 // [recordings][out_stride]
+    long long out_stride;
+    const float* h;
+    int up, down, half;
+};
+
+// sample i of the chunk, channels summed in channel order from 0.f as resample_kernel sums them
+template <typename T>
+__device__ __forceinline__ float stream_mixed(const StreamResampleArgs<T>& a, const T* x, long long i) {
+    const int nch = a.channel >= 0 ? 1 : a.channels;
+    const long long c0 = a.channel >= 0 ? a.channel : 0;
+    float v = 0.f;
+    for (int c = 0; c < nch; ++c) v += retune_sample<T>(x[(c0 + c) * a.channel_stride + i * a.sample_stride]);
+    return v;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kSrThreads) void stream_resample_kernel(StreamResampleArgs<T> a) {
+    extern __shared__ float sr_stretch[];
+    const int rec = blockIdx.y, tid = threadIdx.x;
+    const long long q0 = static_cast<long long>(blockIdx.x) * kSrTile;               // the tile, counted from k_first
+    const long long q1 = q0 + kSrTile < a.k_count ? q0 + kSrTile : a.k_count;
+    const T* x = a.chunk + rec * a.rec_stride;
+    float* y = a.out + rec * a.out_stride;
+    const float scale = a.channel >= 0 ? 1.f : 1.f / a.channels;
+    if (a.up == a.down) {                                         // same rate: output k is input k, out of the chunk; no state
+        for (long long q = q0 + tid; q < q1; q += kSrThreads) y[q] = stream_mixed(a, x, a.k_first + q - a.n_before) * scale;
+        return;
+    }
+    // the stretch: from the first output's i_lo to the last output's i_hi (both monotone in k)
+    const long long ta = (a.k_first + q0) * a.down;
+    const long long i_base = ta - a.half <= 0 ? 0 : (ta - a.half + a.up - 1) / a.up;
+    long long i_end = ((a.k_first + q1 - 1) * a.down + a.half) / a.up;
+    i_end = i_end < a.n_total - 1 ? i_end : a.n_total - 1;
+    const float* ring = a.state + static_cast<long long>(rec) * a.tail;
+    for (long long i = i_base + tid; i <= i_end; i += kSrThreads)
+        sr_stretch[i - i_base] = i < a.n_before ? ring[i % a.tail] : stream_mixed(a, x, i - a.n_before);
+    __syncthreads();
+    for (long long q = q0 + tid; q < q1; q += kSrThreads) {
+        const long long t = (a.k_first + q) * a.down;
+        const long long i_lo = t - a.half <= 0 ? 0 : (t - a.half + a.up - 1) / a.up;
+        long long i_hi = (t + a.half) / a.up;
+        i_hi = i_hi < a.n_total - 1 ? i_hi : a.n_total - 1;       // (binds only under flush: an output is final once its i_hi has arrived)
+        int j = static_cast<int>(t - i_lo * a.up + a.half);
+        const float* xs = sr_stretch + (i_lo - i_base);
+        float acc = 0.f;
+        for (long long i = i_lo; i <= i_hi; ++i, j -= a.up) acc = fmaf(*xs++, a.h[j], acc);
+        y[q] = acc * scale;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kSrThreads) void stream_resample_tail_kernel(StreamResampleArgs<T> a) {
+    const int rec = blockIdx.x;
+    const T* x = a.chunk + rec * a.rec_stride;
+    float* ring = a.state + static_cast<long long>(rec) * a.tail;
+    const long long first = a.n_total - a.tail > a.n_before ? a.n_total - a.tail : a.n_before;
+    for (long long i = first + threadIdx.x; i < a.n_total; i += kSrThreads) ring[i % a.tail] = stream_mixed(a, x, i - a.n_before);
+}
+
+int stream_resample_tail(const ake_resampler* r) { return (2 * r->half / r->up + 1 + 3) / 4 * 4; }
+
+int64_t stream_resample_count(const ake_resampler* r, int64_t n, int flush) {
+    if (r->up == r->down) return n;
+    if (flush) return (n * r->up + r->down - 1) / r->down;
+    const int64_t a = n * r->up - r->half - 1;                    // k is final iff k * down + half < n * up
+    return a < 0 ? 0 : a / r->down + 1;
+}
+
+template <typename T>
+int stream_resample(const char* name, const ake_resampler* r, const T* chunk_dev, int recordings, int channels, int64_t m, int64_t rec_stride,
+                    int64_t channel_stride, int64_t sample_stride, int channel, int64_t n_before, int flush, void* state_dev, size_t state_bytes,
+                    float* out_dev, int64_t out_stride, int64_t* k_out, ake_stream_t stream) {
+    AKE_REQUIRE(r && state_dev && k_out, AKE_ERR_INVALID, "%s: null resampler, state or k_out", name);
+    AKE_REQUIRE(recordings >= 1 && recordings <= 65535 && channels >= 1 && channel >= -1 && channel < channels, AKE_ERR_INVALID,
+                "%s: bad recordings %d / channels %d / channel %d", name, recordings, channels, channel);
+    AKE_REQUIRE(m >= 0 && n_before >= 0 && m <= (1ll << 40) && n_before <= (1ll << 40), AKE_ERR_INVALID, "%s: bad m %lld / n_before %lld", name,
+                static_cast<long long>(m), static_cast<long long>(n_before));
+    AKE_REQUIRE(m == 0 || (chunk_dev && rec_stride >= 0 && channel_stride >= 0 && sample_stride >= 1), AKE_ERR_INVALID,
+                "%s: null chunk or bad strides (%lld, %lld, %lld)", name, static_cast<long long>(rec_stride), static_cast<long long>(channel_stride),
+                static_cast<long long>(sample_stride));
+    AKE_REQUIRE((reinterpret_cast<uintptr_t>(state_dev) & 15) == 0, AKE_ERR_INVALID, "%s: the state must be 16-byte aligned", name);
+    const size_t need = ake_stream_resample_state_bytes(r, recordings);
+    AKE_REQUIRE(state_bytes >= need, AKE_ERR_WORKSPACE, "%s: state of %zu bytes, %zu needed", name, state_bytes, need);
+    const int64_t k_first = stream_resample_count(r, n_before, 0), k_count = stream_resample_count(r, n_before + m, flush) - k_first;
+    AKE_REQUIRE(k_count == 0 || (out_dev && out_stride >= k_count), AKE_ERR_INVALID, "%s: null output or out_stride %lld < %lld output samples",
+                name, static_cast<long long>(out_stride), static_cast<long long>(k_count));
+    const bool same = r->up == r->down;
+    const size_t lds = same ? 0 : ((static_cast<size_t>(kSrTile - 1) * r->down + 2 * static_cast<size_t>(r->half)) / r->up + 2) * sizeof(float);
+    AKE_REQUIRE(lds <= kSrMaxLds, AKE_ERR_UNSUPPORTED, "%s: %d -> %d Hz needs %zu bytes of LDS for a tile's input", name, r->rate_in, r->rate_out, lds);
+    *k_out = k_count;
+    StreamResampleArgs<T> a{chunk_dev, rec_stride, channel_stride, sample_stride, channels, channel, n_before, n_before + m, k_first, k_count,
+                            static_cast<float*>(state_dev), stream_resample_tail(r), out_dev, out_stride, r->h_dev, r->up, r->down, r->half};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (k_count > 0) {
+        const int rc = ake::launch("stream_resample_kernel", stream_resample_kernel<T>,
+                                   dim3(static_cast<unsigned>((k_count + kSrTile - 1) / kSrTile), recordings), dim3(kSrThreads), lds, s, a);
+        if (rc) return rc;
+    }
+    if (m > 0 && !same)
+        return ake::launch("stream_resample_tail_kernel", stream_resample_tail_kernel<T>, dim3(recordings), dim3(kSrThreads), 0, s, a);
+    return AKE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -349,6 +480,31 @@ int ake_resample_pcm16_f32(const ake_resampler* r, const int16_t* in_dev, int ba
     a.h = r->h_dev; a.up = r->up; a.down = r->down; a.half = r->half;
     hipStream_t s = static_cast<hipStream_t>(stream);
     return ake::launch("resample_pcm16_kernel", resample_pcm16_kernel, dim3(static_cast<unsigned>((n_out + 255) / 256), batch), dim3(256), 0, s, a);
+}
+
+int64_t ake_stream_resample_out_count(const ake_resampler* r, int64_t n_in, int flush) {
+    if (!r || n_in < 0 || n_in > (1ll << 40)) return -1;
+    return stream_resample_count(r, n_in, flush);
+}
+
+size_t ake_stream_resample_state_bytes(const ake_resampler* r, int recordings) {
+    if (!r || recordings < 1 || recordings > 65535) return 0;
+    return static_cast<size_t>(recordings) * stream_resample_tail(r) * sizeof(float);
+}
+
+int ake_stream_resample_f32(const ake_resampler* r, const float* chunk_dev, int recordings, int channels, int64_t m, int64_t rec_stride,
+                            int64_t channel_stride, int channel, int64_t n_before, int flush, void* state_dev, size_t state_bytes,
+                            float* out_dev, int64_t out_stride, int64_t* k_out, ake_stream_t stream) {
+    return stream_resample<float>("ake_stream_resample_f32", r, chunk_dev, recordings, channels, m, rec_stride, channel_stride, 1, channel, n_before,
+                                  flush, state_dev, state_bytes, out_dev, out_stride, k_out, stream);
+}
+
+int ake_stream_resample_pcm16_f32(const ake_resampler* r, const int16_t* chunk_dev, int recordings, int channels, int64_t m, int64_t rec_stride,
+                                  int64_t channel_stride, int64_t sample_stride, int channel, int64_t n_before, int flush, void* state_dev,
+                                  size_t state_bytes, float* out_dev, int64_t out_stride, int64_t* k_out, ake_stream_t stream) {
+    return stream_resample<short>("ake_stream_resample_pcm16_f32", r, reinterpret_cast<const short*>(chunk_dev), recordings, channels, m, rec_stride,
+                                  channel_stride, sample_stride, channel, n_before, flush, state_dev, state_bytes, out_dev, out_stride, k_out,
+                                  stream);
 }
 
 int64_t ake_retune_out_len(int64_t n) {

@@ -1049,6 +1049,84 @@ def retune_reference(x, cents, lengths=None):
     return (y[0], int(n_out[0])) if single else (y, n_out)
 
 
+# ---- the polyphase resampler on audio that arrives in chunks (ake_stream_resample_f32) ----
+
+def resample_ratio(rate_in, rate_out):
+    """``(up, down, half)`` of the resampler ``rate_in`` -> ``rate_out``: the rates reduced by their gcd, and the filter's half length
+    ``10 * max(up, down)`` (``scipy.signal.resample_poly``'s default), as ``ake_resampler_create`` sets them."""
+    import math
+    g = math.gcd(int(rate_in), int(rate_out))
+    up, down = int(rate_out) // g, int(rate_in) // g
+    return up, down, 10 * max(up, down)
+
+
+def resampled_final(n_in, up, down, half, finished=False):
+    """Outputs of the resampler that are final after ``n_in`` inputs (``ake_stream_resample_out_count``): output k reads the inputs up to
+    ``floor((k*down + half) / up)``, so it is final iff ``k*down + half < n_in*up``; at the end (``finished``) all
+    ``ceil(n_in*up / down)`` are.  With ``up == down`` nothing is filtered and every input is an output."""
+    n_in, up, down, half = int(n_in), int(up), int(down), int(half)
+    if up == down:
+        return n_in
+    if finished:
+        return -((-n_in * up) // down)
+    a = n_in * up - half - 1
+    return 0 if a < 0 else a // down + 1
+
+
+def resample_first_input(k, up, down, half):
+    """The first input output ``k`` reads: ``max(0, ceil((k*down - half) / up))``."""
+    return max(0, -((int(half) - int(k) * int(down)) // int(up)))
+
+
+def resample_tail(n_in, up, down, half):
+    """Inputs a stream must still hold after ``n_in`` of them: from the first input of the first output that is not final yet.  Never
+    more than ``2*half // up`` (``k*down + half >= n_in*up`` for that output, so its first input lies at or behind
+    ``n_in - 2*half/up``)."""
+    if up == down:
+        return 0
+    return int(n_in) - min(int(n_in), resample_first_input(resampled_final(n_in, up, down, half), up, down, half))
+
+
+def stream_resample(chunks, rate_in, rate_out, channel=0):
+    """Float64 model of ``ake_stream_resample_f32``: ``chunks`` is a sequence of (C, m) or (m,) arrays, the consecutive pieces of one
+    recording (m >= 0, any mix of lengths) -> a list of ``len(chunks) + 1`` float64 arrays: the outputs each piece makes final, and last
+    what ``finish()`` adds.  Joined they are ``resample_poly`` of the joined pieces, ``ceil(n*up / down)`` samples.
+
+    Between pieces the model keeps what the kernel keeps: the last ``resample_tail`` inputs with their channels summed (``channel`` >= 0
+    takes that channel, -1 the mean; the ``1 / C`` scale is applied to the output).  Every output is one sum in ascending input order over
+    "tail, then piece", with the offline sum's limits: the first input never below 0, the last never beyond the end once that is known."""
+    import numpy as np
+    up, down, half = resample_ratio(rate_in, rate_out)
+    mr = max(up, down)
+    taps = np.arange(2 * half + 1, dtype=np.float64) - half
+    h = np.sinc(taps / mr) / mr * np.kaiser(2 * half + 1, 5.0)         # firwin(2 half + 1, 1 / mr, window=("kaiser", 5.0))
+    h = h / h.sum() * up
+    held, held_first, n, outs, scale = np.zeros(0), 0, 0, [], 1.0      # held[0] is input `held_first`
+    for piece in list(chunks) + [None]:
+        finished = piece is None
+        if finished:
+            summed = np.zeros(0)
+        else:
+            x = np.atleast_2d(np.asarray(piece, dtype=np.float64))
+            scale = 1.0 if channel >= 0 else 1.0 / x.shape[0]
+            summed = x[channel] if channel >= 0 else x.sum(axis=0)
+        if up == down:
+            outs.append(summed * scale)
+            continue
+        held = np.concatenate([held, summed])
+        k0 = resampled_final(n, up, down, half)
+        n += summed.shape[0]
+        k1 = resampled_final(n, up, down, half, finished)
+        y = np.zeros(k1 - k0)
+        for k in range(k0, k1):
+            i = np.arange(resample_first_input(k, up, down, half), min(n - 1, (k * down + half) // up) + 1)
+            y[k - k0] = np.dot(held[i - held_first], h[k * down - i * up + half]) * scale
+        keep = resample_tail(n, up, down, half)
+        held, held_first = held[held.shape[0] - keep:], n - keep
+        outs.append(y)
+    return outs
+
+
 # ---- key-profile emissions: a key track without a trained net (ake_profile_emissions_f32) ----
 
 # Published tone profiles, rows minor and major (the order of KEY_NAMES' two halves), tonic first.  "krumhansl": Krumhansl & Kessler

@@ -533,10 +533,19 @@ class KeyEstimator:
     def stream(self, recordings: int, window_seconds: float = 15.0, stride_seconds: float = 5.0, smooth: bool = True, lag_windows: int = 6,
                mean_key_seconds: float = 60.0, transition: torch.Tensor | None = None, log_prior: torch.Tensor | None = None,
                signature_weight: float = 1.0, keep_frames: bool = False, max_chunk_samples: int | None = None, rate: int | None = None,
-               tuning=None, posteriors: bool = False):
+               tuning=None, posteriors: bool = False, source_rate: int | None = None, source_channels: int | None = None, channel: int = 0):
         """Track keys on audio as it arrives -> ``ake_amd.KeyStream``: ``push(chunk)`` takes the next (R, m) samples of all
         ``recordings`` = R recordings at once (float32, or int16 = 16-bit PCM; any m >= 0, the same m for every recording) and returns
         a ``StreamUpdate`` with the windows that chunk completed; ``finish()`` ends the recordings and returns the rest.
+
+        ``source_rate`` / ``source_channels`` / ``channel``: what arrives is at ``source_rate`` Hz with ``source_channels`` channels --
+        chunks are then (R, C, m) ((R, m) with one channel), float32 or int16 with any strides (interleaved (R, m, C) storage goes in as
+        ``buf.transpose(1, 2)``) -- and passes an ``ake_amd.StreamResampler`` in front of the history: ``channel`` >= 0 takes that
+        channel, -1 the mean, and the polyphase filter carries its last few dozen inputs from push to push, so the stream sees
+        ``prepare_audio(whole, source_rate, rate, channel)`` bit for bit however the audio is cut (one or two small launches a push:
+        ``ake_stream_resample_f32``).  ``max_chunk_samples`` then counts source samples, and ``finish()`` first pushes what the resampler
+        held back: after N source samples the stream has emitted the windows ``track(audio, rate=source_rate, channel=channel)`` gives.
+        Times stay seconds of audio.  With ``source_rate`` the estimator's (or None) and one channel nothing is added to a push.
 
         The windows are ``track``'s (``window_seconds``, ``stride_seconds``), each emitted exactly once, in order, as soon as all its
         frames are final: a frame of the transform depends on ``H`` = ``ake_cqt_plan_half_support`` samples to either side, so frame
@@ -565,17 +574,18 @@ class KeyEstimator:
         (``metrics.key_stream_posteriors``; two more launches a push, ``ake_key_stream_posteriors_f32``).
 
         Refused with a ``ValueError``: ``posteriors=True`` with ``smooth=False``; what ``track`` refuses (``frames=0``, ``wrap_mode="true_end"``, ``--local`` nets), an estimator
-        without a net, ``rate`` other than the estimator's and multi-channel chunks (the resampler keeps no state across chunks),
-        ``tuning``, ``lag_windows`` outside 0..255; by ``push``: a chunk after ``finish()``, a chunk whose R or dtype differs from
-        the first.  ``method="profile"`` streams do not exist."""
+        without a net, ``rate`` other than the estimator's (``rate`` names the rate the stream works at; what arrives is
+        ``source_rate``), multi-channel chunks on a stream opened without ``source_channels``, ``tuning``, ``lag_windows`` outside
+        0..255; by ``push``: a chunk after ``finish()``, a chunk whose R (or C) differs from the stream's, on a stream without a source
+        format a dtype that differs from the first chunk's.  ``method="profile"`` streams do not exist."""
         from .stream import KeyStream
         if rate is not None and int(rate) != self.sample_rate:
-            raise ValueError(f"stream: chunks must be at the estimator's rate ({self.sample_rate} Hz): the resampler keeps no state across "
-                             "chunks, so a stream does not convert rates or channels")
+            raise ValueError(f"stream: rate is the rate the stream works at, the estimator's ({self.sample_rate} Hz); for chunks at "
+                             f"another rate pass source_rate={int(rate)} (and source_channels), which resamples them with carried state")
         if tuning is not None:
             raise ValueError("stream: tuning is not offered inside a stream (the estimate needs the whole recording)")
         return KeyStream(self, recordings, window_seconds, stride_seconds, smooth, lag_windows, mean_key_seconds, transition, log_prior,
-                         signature_weight, keep_frames, max_chunk_samples, posteriors)
+                         signature_weight, keep_frames, max_chunk_samples, posteriors, source_rate, source_channels, channel)
 
     def _refuse_untrackable(self):
         """What ``track`` and ``training_windows`` cannot slide windows over."""

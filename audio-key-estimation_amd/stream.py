@@ -4,7 +4,9 @@ A stream takes the audio of R recordings in chunks, all R in lockstep, and emits
 soon as every frame of a window is final; a smoother with carried state (``ake_key_stream_step_f32``, host model
 ``metrics.key_stream``) adds the filtered key scores and a fixed-lag Viterbi path, and on request the fixed-lag posteriors and the
 running log-likelihood (``ake_key_stream_posteriors_f32``, host model ``metrics.key_stream_posteriors``).  Every count is known on the host from the number of
-samples pushed: a push reads nothing back from the device and waits for nothing.
+samples pushed: a push reads nothing back from the device and waits for nothing.  Chunks in a source format (another rate, several
+channels) first pass ``audio.StreamResampler``, the polyphase resampler with a carried tail (``resampled_final`` below), whose output is
+the offline resampler's on the whole audio to the bit; everything here then counts samples at the estimator's rate.
 
 The geometry, as pure host functions (``H`` = ``ake_cqt_plan_half_support``: frame t depends on samples ``[t*hop - H, t*hop + H]``):
 
@@ -26,6 +28,7 @@ import ctypes as C
 import torch
 
 from . import _lib, metrics
+from .audio import StreamResampler
 from .pipeline import track_counts, track_stride_frames, track_window_frames
 
 
@@ -51,6 +54,11 @@ def transform_start(first_frame: int, hop: int, half_support: int) -> int:
 
 
 smooth_count = metrics.key_stream_count      # (windows_before, k, lag, flush) -> (first smoothed window, k_out)
+
+# a stream opened with source_rate / source_channels resamples in front of its history (ake_stream_resample_f32): the geometry
+resampled_final = metrics.resampled_final            # (n_in, up, down, half, finished=False) -> outputs that are final
+resample_first_input = metrics.resample_first_input  # (k, up, down, half) -> the first input output k reads
+resample_tail = metrics.resample_tail                # (n_in, up, down, half) -> inputs still to be held, <= 2*half // up
 
 
 @dataclass
@@ -102,10 +110,16 @@ class KeyStream:
     audio history (float32, ``2*H + hop + max_chunk_samples`` samples a recording), the transform's output and workspace, the two
     halves of the frame cache, the net's workspace, the smoother's state and, with ``posteriors``, the posteriors' state.  After the first push a push allocates only the tensors
     it returns (a chunk longer than ``max_chunk_samples`` is pushed as several pieces, whose updates are joined by one ``torch.cat``
-    each).  ``push`` runs on the current stream."""
+    each).  ``push`` runs on the current stream.
+
+    With ``source_rate`` / ``source_channels`` a ``StreamResampler`` stands in front of the history: a push first resamples its chunk
+    (``max_chunk_samples`` source samples at a time) into a buffer sized here, and what that made final goes the way of a mono chunk."""
+
+    resampler = None                                                 # the StreamResampler of a stream with a source format
 
     def __init__(self, est, recordings, window_seconds=15.0, stride_seconds=5.0, smooth=True, lag_windows=6, mean_key_seconds=60.0,
-                 transition=None, log_prior=None, signature_weight=1.0, keep_frames=False, max_chunk_samples=None, posteriors=False):
+                 transition=None, log_prior=None, signature_weight=1.0, keep_frames=False, max_chunk_samples=None, posteriors=False,
+                 source_rate=None, source_channels=None, channel=0):
         R = int(recordings)
         if R < 1:
             raise ValueError("stream: recordings must be at least 1")
@@ -127,6 +141,22 @@ class KeyStream:
         self.H = int(L.ake_cqt_plan_half_support(plan.handle))
         if self.H < 0:
             _lib.check(-1, "ake_cqt_plan_half_support")
+        # ---- the source: chunks at another rate or with several channels pass a resampler with carried state first ----
+        rate_in = est.sample_rate if source_rate is None else int(source_rate)
+        channels = 1 if source_channels is None else int(source_channels)
+        if rate_in < 1 or channels < 1 or not -1 <= int(channel) < channels:
+            raise ValueError(f"stream: source_rate {source_rate}, source_channels {source_channels}, channel {channel}")
+        self.resampler = None
+        if rate_in != est.sample_rate or channels > 1:
+            # max_chunk_samples counts source samples; the history takes what a piece of that many can make final (no more than
+            # ceil(m*up / down)), or what finish() adds behind the last piece (fewer than (half + 1) / down + 2)
+            src_max = 10 * rate_in if max_chunk_samples is None else int(max_chunk_samples)
+            if src_max < 1:
+                raise ValueError("stream: max_chunk_samples must be at least 1")
+            up, down, half = metrics.resample_ratio(rate_in, est.sample_rate)
+            self.resampler = StreamResampler(rate_in, est.sample_rate, R, channels, int(channel), dev, src_max)
+            max_chunk_samples = max(resampled_final(src_max, up, down, half, True), (half + 1) // down + 2)
+            self.resampled = torch.empty((R, max_chunk_samples), dtype=torch.float32, device=dev)
         self.max_chunk = 10 * est.sample_rate if max_chunk_samples is None else int(max_chunk_samples)
         if self.max_chunk < 1:
             raise ValueError("stream: max_chunk_samples must be at least 1")
@@ -145,7 +175,7 @@ class KeyStream:
         self.N = self.F = self.W = 0
         self.s0 = 0                                                  # the history's first sample
         self.finished = False
-        self.dtype = None
+        self.dtype = None if self.resampler is None else torch.float32       # (what the history is fed: the resampler's output)
         # the history holds [s0, N): at most 2H + hop samples survive a push (frame F is not final, so N <= F*hop + H, and
         # s0 > F*hop - H - hop), and a piece adds at most max_chunk
         self.hist_cap = (2 * self.H + hop + self.max_chunk + 3) // 4 * 4
@@ -187,12 +217,21 @@ class KeyStream:
 
     @torch.no_grad()
     def push(self, chunk: torch.Tensor) -> StreamUpdate:
-        """(R, m) float32 or int16 (16-bit PCM, sample / 32768) at the estimator's rate, any m >= 0 -> ``StreamUpdate``."""
+        """(R, m) float32 or int16 (16-bit PCM, sample / 32768) at the estimator's rate, any m >= 0 -> ``StreamUpdate``.  A stream
+        opened with ``source_rate`` / ``source_channels`` takes (R, C, m) chunks at that rate instead ((R, m) with one channel; int16 with
+        any strides, so interleaved storage goes in as ``buf.transpose(1, 2)``): they pass the carried resampler, and what that makes
+        final goes the way of a mono chunk."""
         if self.finished:
             raise ValueError("KeyStream.push: the stream has been finished")
+        if self.resampler is not None:
+            self.est.net._sync_weights(self.device, for_eval=True)
+            chunk = self.resampler._checked(chunk)
+            step = self.resampler.max_chunk
+            return StreamUpdate.concat([self._piece(self.resampler._piece(chunk[:, :, a:a + step], False, out=self.resampled), False)
+                                        for a in range(0, max(chunk.shape[2], 1), step)])
         if not isinstance(chunk, torch.Tensor) or chunk.dim() != 2 or chunk.shape[0] != self.R:
-            raise ValueError(f"KeyStream.push: a chunk is (R, m) with R = {self.R}: mono audio at the estimator's rate (a stream does not "
-                             "resample or pick channels: the resampler keeps no state across chunks)")
+            raise ValueError(f"KeyStream.push: a chunk is (R, m) with R = {self.R}: mono audio at the estimator's rate (open the stream "
+                             "with source_rate / source_channels for anything else: it then resamples and picks channels with carried state)")
         if chunk.dtype not in (torch.float32, torch.int16):
             raise ValueError("KeyStream.push: a chunk is float32 or int16 (16-bit PCM)")
         if self.dtype is None:
@@ -214,9 +253,15 @@ class KeyStream:
         and the rest of the smoothed path."""
         if self.finished:
             raise ValueError("KeyStream.finish: the stream has been finished")
-        out = self._piece(None, True)
+        parts = []
+        if self.resampler is not None:                               # first what the resampler still held back
+            rest = self.resampler._piece(None, True, out=self.resampled)
+            self.resampler.finished = True
+            if rest.shape[1]:
+                parts.append(self._piece(rest, False))
+        parts.append(self._piece(None, True))
         self.finished = True
-        return out
+        return StreamUpdate.concat(parts)
 
     def _piece(self, chunk, finishing):
         L, dev, R, hop, P = _lib.lib(), self.device, self.R, self.hop, self.P

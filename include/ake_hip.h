@@ -382,6 +382,39 @@ int ake_resample_pcm16_f32(const ake_resampler* r, const int16_t* in_dev, int ba
                            int64_t channel_stride, int64_t sample_stride, int channel, const int64_t* n_in_clip_dev, float* out_dev,
                            int64_t out_stride, int64_t* n_out_clip_dev, ake_stream_t stream);
 
+/* The same resampler on audio that arrives in chunks, all recordings in lockstep (KeyEstimator.stream(source_rate=...),
+ * ake_amd.StreamResampler; host model metrics.stream_resample).  Output k depends on the inputs ceil((k down - half) / up) ..
+ * floor((k down + half) / up), so it is final once the latter has arrived:
+ *   ake_stream_resample_out_count(r, n_in, flush) (host only; -1 for a null r or a negative n_in) = the outputs that are final after n_in
+ *   inputs: without flush 0 if n_in up - half - 1 < 0, else (n_in up - half - 1) / down + 1; with flush ceil(n_in up / down) =
+ *   ake_resampler_out_len (the rest see nothing behind the end, as the offline outputs do); with up == down, n_in.
+ * A call takes the next m samples of every recording, chunk_dev[rec * rec_stride + c * channel_stride + i (* sample_stride)], after the
+ * n_before it has been given so far, and writes the outputs k in [out_count(n_before, 0), out_count(n_before + m, flush)) to
+ * out_dev[rec * out_stride + (k - first)]; *k_out (a host integer, required) is their number, computed on the host; out_dev behind it
+ * is not touched.  The outputs equal ake_resample_f32 / ake_resample_pcm16_f32 on the concatenated audio BIT FOR BIT, however the audio
+ * is cut into calls: the same order of channel additions, the same ascending fmaf chain from the same first input (never below 0; under
+ * flush never beyond the last), the 1 / channels scale last, the 16-bit form converting float(s) * 2^-15 where the offline one does.
+ * channel >= 0 takes that channel, -1 the mean.  m = 0 is allowed (with flush: flush only); m may be shorter than the filter.
+ * state_dev: ake_stream_resample_state_bytes(r, recordings) bytes (0 for a null r or recordings outside 1..65535), 16-byte aligned: per
+ * recording a ring of the last 2 half / up + 1 (rounded up to a multiple of 4) inputs as float32, input i at slot i % ring, channels
+ * summed and not yet scaled -- the same values from float32 and 16-bit chunks.  With n_before == 0 it is not read, so a fresh stream needs
+ * no initialising launch; up == down (a channel pick or mix alone) never touches it.  The device keeps no count: the host passes n_before.
+ * Launches: stream_resample_kernel (512 outputs a workgroup, the tile's input mixed once into LDS; reads the ring), then
+ * stream_resample_tail_kernel (writes the ring from the chunk's end) -- two, so that no workgroup reads what another writes.  A call with
+ * no output skips the first, m == 0 or up == down the second; a call with neither launches nothing.  Plain loads and stores, no atomics.
+ * AKE_ERR_INVALID: a null r, state_dev or k_out, chunk_dev with m > 0, out_dev with *k_out > 0; recordings outside 1..65535; channels < 1;
+ * channel outside -1..channels-1; m or n_before negative; rec_stride or channel_stride negative, sample_stride < 1, out_stride < *k_out;
+ * a misaligned state.  AKE_ERR_WORKSPACE: state_bytes below the query.  AKE_ERR_UNSUPPORTED: a ratio down / up so large (beyond about 30)
+ * that a tile's input exceeds 64 KiB of LDS.  Nothing is launched after any of them. */
+int64_t ake_stream_resample_out_count(const ake_resampler* r, int64_t n_in, int flush);
+size_t ake_stream_resample_state_bytes(const ake_resampler* r, int recordings);
+int ake_stream_resample_f32(const ake_resampler* r, const float* chunk_dev, int recordings, int channels, int64_t m, int64_t rec_stride,
+                            int64_t channel_stride, int channel, int64_t n_before, int flush, void* state_dev, size_t state_bytes,
+                            float* out_dev, int64_t out_stride, int64_t* k_out, ake_stream_t stream);
+int ake_stream_resample_pcm16_f32(const ake_resampler* r, const int16_t* chunk_dev, int recordings, int channels, int64_t m, int64_t rec_stride,
+                                  int64_t channel_stride, int64_t sample_stride, int channel, int64_t n_before, int flush, void* state_dev,
+                                  size_t state_bytes, float* out_dev, int64_t out_stride, int64_t* k_out, ake_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Whole hot path for a batch of equal-length clips: CQT then forward
  * (DatasetLoader.get_all -> __getitem__ -> general_step's forward; KeyDataset.py:469-509,

@@ -20,7 +20,12 @@
               same pushes -- the emissions copied to the CPU, then metrics.key_stream_posteriors with its carried state -- per push that
               completed a window, by the host clock.
 
-Usage: python tools/stream_bench.py [--pushes 200] [--accuracy] [--posteriors]"""
+  --source-rate HZ [--source-channels C]: this section alone.  est.stream(R, source_rate=HZ, source_channels=C, channel=-1) fed interleaved
+              int16 chunks of 0.2 s and 1 s, beside a plain stream fed the same seconds of mono int16 audio at the estimator's rate (the only
+              push there was before the carried resampler): per push by events on the stream, median and 95th percentile; and the two
+              added launches (stream_resample_kernel, stream_resample_tail_kernel) per launch under the library's kernel timer.
+
+Usage: python tools/stream_bench.py [--pushes 200] [--accuracy] [--posteriors] [--source-rate 48000 --source-channels 2]"""
 import argparse
 import ctypes as C
 import importlib.util
@@ -179,6 +184,53 @@ def posteriors_rows(est, recordings, pushes):
     return rows
 
 
+def timed_pushes(s, pieces, pushes, warm):
+    """Milliseconds of each of `pushes` pushes, by events on the stream, after `warm` pushes."""
+    for i in range(warm):
+        s.push(pieces[i % len(pieces)])
+    torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(pushes)]
+    for i, (a, b) in enumerate(ev):
+        a.record()
+        s.push(pieces[i % len(pieces)])
+        b.record()
+    torch.cuda.synchronize()
+    return [a.elapsed_time(b) for a, b in ev]
+
+
+def source_rows(est, recordings, pushes, rate, channels):
+    """A push of int16 audio at `rate` Hz with `channels` interleaved channels (their mean taken) through the carried resampler, beside a
+    push of the same seconds of mono int16 audio at the estimator's rate -- the only push there was before --, and the two added
+    launches on their own."""
+    rows = []
+    for R in recordings:
+        for seconds in (0.2, 1.0):
+            m_src, m = int(round(seconds * rate)), int(round(seconds * SR))
+            noise = lambda *shape: (torch.randn(shape, device=DEV) * 0.3).clamp(-1, 1).mul(32767).to(torch.int16)   # noqa: E731
+            src = [noise(R, m_src, channels).transpose(1, 2) for _ in range(8)]            # interleaved storage, read in place
+            mono = [noise(R, m) for _ in range(8)]
+            warm = int(30 / seconds) + 1
+            kw = dict(source_rate=rate, source_channels=channels, channel=-1 if channels > 1 else 0)
+            ms_src = timed_pushes(est.stream(R, **kw), src, pushes, warm)
+            ms_mono = timed_pushes(est.stream(R), mono, pushes, warm)
+            s = est.stream(R, **kw)
+            for i in range(warm):
+                s.push(src[i % 8])
+            torch.cuda.synchronize()
+            _lib.prof_enable("stream_resample", True)
+            for i in range(pushes):
+                s.push(src[i % 8])
+            prof = _lib.prof_results()
+            _lib.prof_enable("", False)
+            stat = lambda ms: {"median": round(statistics.median(ms), 4), "p95": round(percentile(ms, 0.95), 4)}   # noqa: E731
+            rows.append({"recordings": R, "chunk_s": seconds, "source": f"{rate} Hz x {channels} int16 interleaved", "push_ms_source": stat(ms_src),
+                         "push_ms_mono_int16_at_the_estimators_rate": stat(ms_mono),
+                         "added_ms_median": round(statistics.median(ms_src) - statistics.median(ms_mono), 4),
+                         "kernel_us_per_launch": {n: round(1e3 * t / k, 2) for n, (t, k) in prof.items()}})
+            del s, src, mono
+    return rows
+
+
 def frame_rows(est):
     plan = est.plan
     H = int(_lib.lib().ake_cqt_plan_half_support(plan.handle))
@@ -229,6 +281,8 @@ def main():
     ap.add_argument("--recordings", type=int, nargs="+", default=[1, 16, 256])
     ap.add_argument("--accuracy", action="store_true")
     ap.add_argument("--posteriors", action="store_true")
+    ap.add_argument("--source-rate", type=int, default=None)
+    ap.add_argument("--source-channels", type=int, default=1)
     args = ap.parse_args()
     torch.manual_seed(0)
     gold = np.load(os.path.join(REPO, "tests", "golden", "pcnet_default.npz"))
@@ -239,6 +293,10 @@ def main():
     if args.posteriors:
         print(json.dumps({"device": torch.cuda.get_device_name(0), "pushes": args.pushes, "chunk_s": 1.0,
                           "posteriors": posteriors_rows(est, args.recordings, args.pushes)}))
+        return
+    if args.source_rate is not None:
+        print(json.dumps({"device": torch.cuda.get_device_name(0), "pushes": args.pushes,
+                          "source": source_rows(est, args.recordings, args.pushes, args.source_rate, args.source_channels)}))
         return
     rows = [push_row(est, R, chunk, dtype, args.pushes, args.baseline_reps)
             for R in args.recordings for chunk in (HOP, SR) for dtype in (torch.float32, torch.int16)]
