@@ -8,20 +8,19 @@
 // profile_score_kernel adds one window's frames in ascending order, forms the 24 Pearson correlations in double and writes the float32
 // outputs.  No floating-point atomics, every sum in a fixed order: two runs give the same bits.  expm1 is the double library form.
 #include "common.h"
+#include "profile.h"
 
 #include <cmath>
 
 namespace {
+
+using namespace ake_profile;                                      // the arithmetic itself: shared with the streamed kernels
 
 // 256 threads on a tile of 64 frames x 12 pitch classes: 768 sums of pitches / 12 bins each, three per thread.  Pitch-major input:
 // lanes run along the frames, which are contiguous; frames-major: lanes run along the pitch classes, whose three-bin groups are 12
 // bytes apart.  Left as it is until the two launches have been timed (tools/profile_baseline.py).
 constexpr int kProfChunk = 64;       // frames per block
 constexpr int kProfThreads = 256;
-constexpr int kProfClasses = 12;
-constexpr int kProfKeys = 24;
-constexpr int kProfScoreThreads = 64;
-constexpr double kProfSilence = 1e-12;
 
 struct ProfChromaArgs {
     const float* mel;           // [recordings][pitches][frames], or [recordings][frames][pitches] (frames_major)
@@ -47,17 +46,9 @@ __global__ __launch_bounds__(kProfThreads) void profile_chroma_kernel(ProfChroma
         if (t >= a.frames) continue;
         double s = 0.0;
         if (t < T)                                                // frames at or behind the count are written as zeros
-            for (int sem = j; 3 * sem - 1 < a.pitches; sem += kProfClasses)
-                for (int k = sem ? 3 * sem - 1 : 0; k <= 3 * sem + 1 && k < a.pitches; ++k) {     // ascending k
-                    const double L = static_cast<double>(kFramesMajor ? mel[static_cast<long long>(t) * a.pitches + k]
-                                                                      : mel[static_cast<long long>(k) * a.frames + t]);
-                    double v = L;
-                    if (a.compression != 0) {
-                        v = expm1(L);
-                        if (a.compression == 2) v = v * v;
-                    }
-                    s += v;
-                }
+            s = prof_class_sum(j, a.pitches, a.compression, [&](int k) {
+                return kFramesMajor ? mel[static_cast<long long>(t) * a.pitches + k] : mel[static_cast<long long>(k) * a.frames + t];
+            });
         a.chroma[(static_cast<long long>(rec) * a.frames + t) * kProfClasses + j] = s;
     }
 }
@@ -66,84 +57,24 @@ struct ProfScoreArgs {
     const double* frame_chroma; // [recordings][frames][12]
     const int* counts;
     const float* profiles;      // [2][12]: minor, major, tonic first
-    float* chroma;              // [recordings][windows][12]
-    float* emissions;           // [recordings][windows][24]
-    int* key_id;                // [recordings][windows]
-    float* confidence;          // [recordings][windows]
+    ProfScoreOut out;           // [recordings][windows] cells
     int frames, window_frames, stride_frames, windows;
     double sharpness;
 };
 
 __global__ __launch_bounds__(kProfScoreThreads) void profile_score_kernel(ProfScoreArgs a) {
-    __shared__ double x[kProfClasses], d[kProfClasses], e[2][kProfClasses], see[2], r[kProfKeys];
-    __shared__ double sxx_s, total_s;
-    __shared__ int best_k;                                        // -1: silent, or behind the recording's windows
-    const int rec = blockIdx.y, w = blockIdx.x, tid = threadIdx.x;
+    __shared__ ProfScoreLds lds;
+    const int rec = blockIdx.y, w = blockIdx.x;
     const int T = prof_count(a.counts, rec, a.frames);
     int n_win, first, len;
     if (a.window_frames == 0) { n_win = T > 0 ? 1 : 0; first = 0; len = T; }                 // the whole clip
     else { n_win = T < a.window_frames ? 0 : (T - a.window_frames) / a.stride_frames + 1; first = w * a.stride_frames; len = a.window_frames; }
-    const bool live = w < n_win;
-    if (tid < kProfClasses) {
+    prof_score_block(lds, w < n_win, [&](int j) {
+        const double* c = a.frame_chroma + (static_cast<long long>(rec) * a.frames + first) * kProfClasses + j;
         double s = 0.0;
-        if (live) {
-            const double* c = a.frame_chroma + (static_cast<long long>(rec) * a.frames + first) * kProfClasses + tid;
-            for (int t = 0; t < len; ++t) s += c[static_cast<long long>(t) * kProfClasses];  // ascending t
-        }
-        x[tid] = s;
-    } else if (tid >= 32 && tid < 34) {                           // the two profile rows' statistics, once per block
-        const int mode = tid - 32;
-        double sum = 0.0;
-        for (int i = 0; i < kProfClasses; ++i) sum += static_cast<double>(a.profiles[mode * kProfClasses + i]);
-        const double mean = sum / 12.0;
-        double ss = 0.0;
-        for (int i = 0; i < kProfClasses; ++i) {
-            const double v = static_cast<double>(a.profiles[mode * kProfClasses + i]) - mean;
-            e[mode][i] = v;
-            ss += v * v;
-        }
-        see[mode] = ss;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double sum = 0.0;
-        for (int j = 0; j < kProfClasses; ++j) sum += x[j];
-        const double mean = sum / 12.0;
-        double ss = 0.0;
-        for (int j = 0; j < kProfClasses; ++j) { const double v = x[j] - mean; d[j] = v; ss += v * v; }
-        sxx_s = ss;
-        total_s = sum;
-        best_k = (!live || ss <= kProfSilence * 12.0 * mean * mean) ? -1 : 0;
-    }
-    __syncthreads();
-    const bool silent = best_k < 0;
-    if (tid < kProfKeys) {
-        double rk = 0.0;
-        if (!silent) {
-            const int mode = tid / kProfClasses, tonic = tid % kProfClasses;
-            double num = 0.0;
-            for (int j = 0; j < kProfClasses; ++j) num += d[j] * e[mode][(j - tonic + kProfClasses) % kProfClasses];
-            const double den = sqrt(sxx_s * see[mode]);
-            rk = den > 0.0 ? num / den : 0.0;
-        }
-        r[tid] = rk;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double best = 0.0;
-        int k = -1;
-        if (!silent) {
-            best = r[0]; k = 0;
-            for (int i = 1; i < kProfKeys; ++i)
-                if (r[i] > best) { best = r[i]; k = i; }          // the first maximum, on the double values
-        }
-        const long long cell = static_cast<long long>(rec) * a.windows + w;
-        a.key_id[cell] = k;
-        a.confidence[cell] = static_cast<float>(best);
-    }
-    const long long cell = static_cast<long long>(rec) * a.windows + w;
-    if (tid < kProfKeys) a.emissions[cell * kProfKeys + tid] = static_cast<float>(a.sharpness * r[tid]);
-    if (tid < kProfClasses) a.chroma[cell * kProfClasses + tid] = silent ? 0.0f : static_cast<float>(x[tid] / total_s);
+        for (int t = 0; t < len; ++t) s += c[static_cast<long long>(t) * kProfClasses];      // ascending t
+        return s;
+    }, a.profiles, a.sharpness, static_cast<long long>(rec) * a.windows + w, a.out);
 }
 
 bool prof_shape_ok(int recordings, int frames) { return recordings > 0 && recordings <= 65535 && frames > 0; }
@@ -189,7 +120,7 @@ int ake_profile_emissions_f32(const float* mel_dev, int frames_major, int record
     const int rc = frames_major ? ake::launch("profile_chroma_kernel", profile_chroma_kernel<true>, dim3(chunks, recordings), dim3(kProfThreads), 0, s, c)
                                 : ake::launch("profile_chroma_kernel", profile_chroma_kernel<false>, dim3(chunks, recordings), dim3(kProfThreads), 0, s, c);
     if (rc) return rc;
-    ProfScoreArgs f{static_cast<const double*>(workspace), counts_dev, profiles_dev, chroma_out, emissions_out, key_id_out, confidence_out,
+    ProfScoreArgs f{static_cast<const double*>(workspace), counts_dev, profiles_dev, {chroma_out, emissions_out, key_id_out, confidence_out},
                     frames, window_frames, stride_frames, windows, static_cast<double>(sharpness)};
     return ake::launch("profile_score_kernel", profile_score_kernel, dim3(windows, recordings), dim3(kProfScoreThreads), 0, s, f);
 }

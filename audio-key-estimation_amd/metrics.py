@@ -968,6 +968,11 @@ def estimate_tuning(logmag, counts=None, min_strength=0.0):
     if counts is not None:
         power = torch.where(_behind_count(counts, B, T, L.device)[:, None, :], torch.zeros_like(power), power)
     P0, P1, P2 = (power[:, j::3].sum(dim=(1, 2)) for j in range(3))
+    return _tuning_finish(P0, P1, P2, min_strength)
+
+
+def _tuning_finish(P0, P1, P2, min_strength):
+    """The three sums over bin positions, float64 (B,) -> ``estimate_tuning``'s ``(cents, strength)``."""
     re, im = P0 - 0.5 * (P1 + P2), (3.0 ** 0.5 / 2.0) * (P1 - P2)
     total = P0 + P1 + P2
     live = total > 0
@@ -1217,10 +1222,7 @@ def profile_emissions(logmag, window_frames, stride_frames, counts=None, profile
     n = torch.full((R,), T, dtype=torch.int64) if counts is None else torch.as_tensor(counts).detach().cpu().to(torch.int64).reshape(R).clamp(0, T)
     W = int(profile_window_counts(torch.tensor(T), wf, sf))
     n_win = profile_window_counts(n, wf, sf)
-    v = L if mode == 0 else torch.expm1(L) if mode == 1 else torch.expm1(L) ** 2
-    c = torch.zeros((R, T, 12), dtype=torch.float64)
-    for k in range(P):                                                                       # ascending k
-        c[:, :, ((k + 1) // 3) % 12] += v[:, k, :]
+    c = _profile_frame_chroma(L, mode)
     c = torch.where((torch.arange(T)[None, :] < n[:, None])[:, :, None], c, torch.zeros_like(c))
     x = torch.zeros((R, W, 12), dtype=torch.float64)
     if W > 0:
@@ -1229,6 +1231,22 @@ def profile_emissions(logmag, window_frames, stride_frames, counts=None, profile
             x += c[:, start + i, :]
     live = torch.arange(W)[None, :] < n_win[:, None]                                         # (R, W)
     x = torch.where(live[:, :, None], x, torch.zeros_like(x))
+    return _profile_score(x, live, prof, sharpness)
+
+
+def _profile_frame_chroma(L, mode):
+    """(R, n_bins, T) float64 log-CQT -> per-frame chroma c (R, T, 12): the bins of every pitch class added in ascending k."""
+    R, P, T = L.shape
+    v = L if mode == 0 else torch.expm1(L) if mode == 1 else torch.expm1(L) ** 2
+    c = torch.zeros((R, T, 12), dtype=torch.float64)
+    for k in range(P):                                                                       # ascending k
+        c[:, :, ((k + 1) // 3) % 12] += v[:, k, :]
+    return c
+
+
+def _profile_score(x, live, prof, sharpness):
+    """Window chroma x (R, W, 12) float64 (zeros where not ``live`` (R, W)) -> ``profile_emissions``' four outputs."""
+    R, W = x.shape[:2]
     seq_sum = _ascending_sum
     m = seq_sum(x) / 12.0
     d = x - m[..., None]
@@ -1287,3 +1305,118 @@ def fit_key_profiles(chroma, key_id, weight=None):
         p = (rolled * wm[:, None]).sum(dim=0) / wm.sum()
         out.append(p / p.sum())
     return torch.stack(out)
+
+
+# ---- the profile method and the tuning estimate on frames that arrive in pieces (ake_stream_frame_stats_f32 / ake_stream_profile_emissions_f32) ----
+
+def stream_profile_ring_frames(window_frames, max_new_frames):
+    """Rows a stream's chroma ring needs when no piece brings more than ``max_new_frames`` frames: ``window_frames + max_new_frames``.
+
+    With ``F_old`` frames before a piece and ``W_old = track_counts(F_old)`` windows emitted, the new windows read the frames
+    ``[W_old * sf, F)``.  Window ``W_old`` was not complete, so ``W_old * sf + wf > F_old``, that is ``W_old * sf > F_old - wf``: the span
+    is shorter than ``wf + (F - F_old)``, and a ring of that many rows still holds all of it after the piece's frames are written."""
+    wf, m = int(window_frames), int(max_new_frames)
+    if wf < 1 or m < 0:
+        raise ValueError("stream_profile_ring_frames: window_frames must be >= 1 and max_new_frames >= 0")
+    return wf + m
+
+
+def _stream_windows(frames, wf, sf):
+    return 0 if frames < wf else (frames - wf) // sf + 1
+
+
+def stream_profile(pieces, window_frames, stride_frames, profiles="krumhansl", compression="log", sharpness=10.0, ring_frames=None,
+                   state=None, return_state=False):
+    """Float64 model of a ``method="profile"`` stream (``ake_stream_frame_stats_f32``'s chroma part, then
+    ``ake_stream_profile_emissions_f32``): ``pieces`` is a sequence of (R, n_bins, m) log-CQT frames, the consecutive pieces of R
+    recordings in lockstep (m >= 0, any mix) -> a list with one ``(chroma (R, k, 12), emissions (R, k, 24), key_id int32 (R, k),
+    confidence (R, k))`` per piece: the k windows that piece completed.  Joined along the windows they are ``profile_emissions`` of the
+    joined pieces, to the bit: the same additions in the same order.
+
+    Between pieces the model keeps what the kernels keep: a ring of per-frame chroma, float64 (R, ring_frames, 12), frame t in row
+    ``t % ring_frames`` -- every frame is written, also one that a stride longer than the window skips -- and two host integers, the
+    frames and the windows so far.  A window's chroma is the sum of its rows in ascending t (the row index wraps).  ``ring_frames``
+    (default: ``stream_profile_ring_frames`` of the longest piece) must be at least ``window_frames``; a piece so long that a window's
+    first frames have been overwritten is a ``ValueError``, as are ``window_frames < 1`` (there is no whole-clip mode on a stream),
+    ``stride_frames < 1``, ``n_bins`` no multiple of 3 and a ``sharpness`` that is not positive.  ``state`` / ``return_state``: continue
+    from, and return as a last list element, the carried state (``{"ring", "frames", "windows"}``)."""
+    pieces = [torch.as_tensor(p).detach().to(device="cpu", dtype=torch.float64) for p in pieces]
+    mode = _profile_compression(compression)
+    prof = key_profile_table(profiles)
+    sharpness = float(sharpness)
+    if not sharpness > 0.0:
+        raise ValueError("stream_profile: sharpness must be positive")
+    wf, sf = int(window_frames), int(stride_frames)
+    if wf < 1 or sf < 1:
+        raise ValueError("stream_profile: window_frames and stride_frames must be >= 1")
+    for p in pieces:
+        if p.dim() != 3 or p.shape[1] % TUNING_BINS_PER_SEMITONE != 0 or p.shape[:2] != pieces[0].shape[:2]:
+            raise ValueError(f"stream_profile: every piece must be (R, n_bins, m) with n_bins a multiple of 3, got {tuple(p.shape)}")
+    if ring_frames is None:
+        ring_frames = state["ring"].shape[1] if state is not None else stream_profile_ring_frames(wf, max([p.shape[2] for p in pieces], default=0))
+    ring_frames = int(ring_frames)
+    if ring_frames < wf:
+        raise ValueError(f"stream_profile: a ring of {ring_frames} frames cannot hold a window of {wf}")
+    if state is None:
+        ring, F, W = None, 0, 0
+    else:
+        ring, F, W = state["ring"].clone(), int(state["frames"]), int(state["windows"])
+        if ring.shape[1] != ring_frames:
+            raise ValueError("stream_profile: the state's ring has another length")
+    outs = []
+    for p in pieces:
+        R, m = p.shape[0], p.shape[2]
+        if ring is None:
+            ring = torch.zeros((R, ring_frames, 12), dtype=torch.float64)
+        c = _profile_frame_chroma(p, mode) if m else None
+        for i in range(m):
+            ring[:, (F + i) % ring_frames, :] = c[:, i, :]
+        F += m
+        W_new = _stream_windows(F, wf, sf)
+        k = W_new - W
+        if k > 0 and W * sf < F - ring_frames:
+            raise ValueError(f"stream_profile: window {W} begins at frame {W * sf}, and the ring of {ring_frames} holds {F - ring_frames} on")
+        x = torch.zeros((R, k, 12), dtype=torch.float64)
+        start = (torch.arange(k) + W) * sf
+        for i in range(wf if k > 0 else 0):                                                  # ascending t
+            x += ring[:, (start + i) % ring_frames, :]
+        if k > 0:
+            outs.append(_profile_score(x, torch.ones((R, k), dtype=torch.bool), prof, sharpness))
+        else:                                                                                # no window: the four outputs, empty
+            outs.append((x, torch.zeros((R, 0, 24), dtype=torch.float64), torch.zeros((R, 0), dtype=torch.int32), torch.zeros((R, 0), dtype=torch.float64)))
+        W = W_new
+    if return_state:
+        outs.append({"ring": ring, "frames": F, "windows": W})
+    return outs
+
+
+def stream_tuning(pieces, min_strength=0.0, state=None, return_state=False):
+    """Float64 model of ``ake_stream_frame_stats_f32``'s tuning part: ``pieces`` as in ``stream_profile`` -> a list with one
+    ``(cents, strength)``, float64 (R,), per piece: ``estimate_tuning`` over every frame up to and including that piece.
+
+    Carried between pieces: the three sums ``P_j`` (R, 3).  Per frame ``p_j(t)`` is the sum of ``expm1(L) ** 2`` over the bins
+    ``k = j (mod 3)`` in ascending k, and ``P_j += p_j(t)`` in ascending t; the two numbers then follow from ``P`` by
+    ``estimate_tuning``'s formulas.  The doubles are ``estimate_tuning``'s, added in another order.  ``state`` / ``return_state``: the sums
+    (R, 3) float64."""
+    pieces = [torch.as_tensor(p).detach().to(device="cpu", dtype=torch.float64) for p in pieces]
+    if float(min_strength) != float(min_strength):
+        raise ValueError("stream_tuning: min_strength is NaN")
+    sums = None if state is None else torch.as_tensor(state).detach().to(torch.float64).clone()
+    outs = []
+    for p in pieces:
+        if p.dim() != 3 or p.shape[1] % TUNING_BINS_PER_SEMITONE != 0 or p.shape[:2] != pieces[0].shape[:2]:
+            raise ValueError(f"stream_tuning: every piece must be (R, n_bins, m) with n_bins a multiple of 3, got {tuple(p.shape)}")
+        R, P, m = p.shape
+        if sums is None:
+            sums = torch.zeros((R, 3), dtype=torch.float64)
+        power = torch.expm1(p) ** 2
+        for j in range(3):
+            pj = torch.zeros((R, m), dtype=torch.float64)
+            for k in range(j, P, 3):                                                         # ascending k
+                pj += power[:, k, :]
+            for t in range(m):                                                               # ascending t
+                sums[:, j] += pj[:, t]
+        outs.append(_tuning_finish(sums[:, 0].clone(), sums[:, 1].clone(), sums[:, 2].clone(), min_strength))
+    if return_state:
+        outs.append(sums if sums is not None else torch.zeros((0, 3), dtype=torch.float64))
+    return outs

@@ -288,8 +288,8 @@ class KeyEstimator:
     0.94 of the Nyquist frequency: an estimator whose transform reaches that far refuses ``tuning`` with a ``ValueError``.
 
     ``KeyEstimator(None, device=..., pitches=288)``: an estimator without a net, for the calls that need none --
-    ``track(method="profile")``, ``profile_key`` and ``fit_key_profiles`` (and ``estimate_tuning``).  ``__call__``,
-    ``track(method="net")`` and ``training_windows`` raise a ``ValueError`` on it.  With a net, ``device`` and ``pitches`` are the net's
+    ``track(method="profile")``, ``stream(method="profile")``, ``profile_key`` and ``fit_key_profiles`` (and ``estimate_tuning``).
+    ``__call__``, ``track(method="net")``, ``stream(method="net")`` and ``training_windows`` raise a ``ValueError`` on it.  With a net, ``device`` and ``pitches`` are the net's
     and must be left at None."""
 
     def __init__(self, net: PitchClassNet | None, sample_rate: int = 22050, frames: int = 5, streams: int = 1, wrap_mode: str = "dataset_max",
@@ -324,7 +324,7 @@ class KeyEstimator:
     def _need_net(self, what):
         if self.net is None:
             raise ValueError(f"{what} runs the net, and this estimator was built without one (KeyEstimator(None, ...)): it serves "
-                             'track(method="profile"), profile_key and fit_key_profiles')
+                             'track(method="profile"), stream(method="profile"), profile_key and fit_key_profiles')
 
     def join(self):
         """Make the caller's current stream wait for every call issued so far (``streams`` > 1; a no-op otherwise)."""
@@ -533,7 +533,9 @@ class KeyEstimator:
     def stream(self, recordings: int, window_seconds: float = 15.0, stride_seconds: float = 5.0, smooth: bool = True, lag_windows: int = 6,
                mean_key_seconds: float = 60.0, transition: torch.Tensor | None = None, log_prior: torch.Tensor | None = None,
                signature_weight: float = 1.0, keep_frames: bool = False, max_chunk_samples: int | None = None, rate: int | None = None,
-               tuning=None, posteriors: bool = False, source_rate: int | None = None, source_channels: int | None = None, channel: int = 0):
+               tuning=None, posteriors: bool = False, source_rate: int | None = None, source_channels: int | None = None, channel: int = 0,
+               method: str = "net", profiles="krumhansl", compression: str = "log", profile_sharpness: float = 10.0,
+               tuning_meter: bool = False, tuning_min_strength: float = 0.0):
         """Track keys on audio as it arrives -> ``ake_amd.KeyStream``: ``push(chunk)`` takes the next (R, m) samples of all
         ``recordings`` = R recordings at once (float32, or int16 = 16-bit PCM; any m >= 0, the same m for every recording) and returns
         a ``StreamUpdate`` with the windows that chunk completed; ``finish()`` ends the recordings and returns the rest.
@@ -573,19 +575,36 @@ class KeyEstimator:
         ``log_likelihood`` (R, k), the running log-score of the recording under the transition after each new window
         (``metrics.key_stream_posteriors``; two more launches a push, ``ake_key_stream_posteriors_f32``).
 
-        Refused with a ``ValueError``: ``posteriors=True`` with ``smooth=False``; what ``track`` refuses (``frames=0``, ``wrap_mode="true_end"``, ``--local`` nets), an estimator
-        without a net, ``rate`` other than the estimator's (``rate`` names the rate the stream works at; what arrives is
+        ``method="profile"`` needs no net, so ``KeyEstimator(None, ...)`` streams: the windows are scored as
+        ``track(method="profile")`` scores them, with ``profiles``, ``compression`` and ``profile_sharpness`` as there.  Such a stream keeps
+        no frame cache and no net workspace but a ring of per-frame chroma, 12 doubles a frame: a push computes the chroma of every new
+        frame once (``ake_stream_frame_stats_f32``) and scores the windows it completed from the ring
+        (``ake_stream_profile_emissions_f32``), two launches in place of the net's; on the stream's own frames
+        (``keep_frames=True``) the result is ``ake_amd.profile_emissions``' to the bit, however the audio is cut.  The ``StreamUpdate`` holds
+        what ``KeyTrack`` documents for the method (``key`` the chroma, ``genre`` None), ``emissions`` always, and the smoother and
+        ``posteriors`` take those emissions as they take the net's.  ``signature_weight`` must be left at 1.
+
+        ``tuning_meter=True``, with either method, adds ``StreamUpdate.tuning_cents`` and ``.tuning_strength`` (R,): ``estimate_tuning``
+        over every final frame so far, from three sums carried on the device (``metrics.stream_tuning``; ``tuning_min_strength`` as
+        ``min_strength`` there).  It rides in the profile method's frame launch; on a ``"net"`` stream it is that launch with the chroma
+        part off, one more launch per piece that has new frames.  A meter only: the stream is not retuned.
+
+        Refused with a ``ValueError``: ``posteriors=True`` with ``smooth=False``; what ``track`` refuses (``frames=0``, ``wrap_mode="true_end"``, ``--local`` nets), with
+        ``method="net"`` an estimator without a net, ``rate`` other than the estimator's (``rate`` names the rate the stream works at; what arrives is
         ``source_rate``), multi-channel chunks on a stream opened without ``source_channels``, ``tuning``, ``lag_windows`` outside
         0..255; by ``push``: a chunk after ``finish()``, a chunk whose R (or C) differs from the stream's, on a stream without a source
-        format a dtype that differs from the first chunk's.  ``method="profile"`` streams do not exist."""
+        format a dtype that differs from the first chunk's.  Not built: retuning inside a stream (a carried retuner), chunk lengths
+        that differ between recordings, and a weighting of the bins in the chroma."""
         from .stream import KeyStream
         if rate is not None and int(rate) != self.sample_rate:
             raise ValueError(f"stream: rate is the rate the stream works at, the estimator's ({self.sample_rate} Hz); for chunks at "
                              f"another rate pass source_rate={int(rate)} (and source_channels), which resamples them with carried state")
         if tuning is not None:
-            raise ValueError("stream: tuning is not offered inside a stream (the estimate needs the whole recording)")
+            raise ValueError("stream: tuning (retuning the audio) is not offered inside a stream; tuning_meter=True reports the running "
+                             "estimate in StreamUpdate.tuning_cents / .tuning_strength")
         return KeyStream(self, recordings, window_seconds, stride_seconds, smooth, lag_windows, mean_key_seconds, transition, log_prior,
-                         signature_weight, keep_frames, max_chunk_samples, posteriors, source_rate, source_channels, channel)
+                         signature_weight, keep_frames, max_chunk_samples, posteriors, source_rate, source_channels, channel, method,
+                         profiles, compression, profile_sharpness, tuning_meter, tuning_min_strength)
 
     def _refuse_untrackable(self):
         """What ``track`` and ``training_windows`` cannot slide windows over."""

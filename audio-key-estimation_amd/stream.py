@@ -8,6 +8,13 @@ samples pushed: a push reads nothing back from the device and waits for nothing.
 channels) first pass ``audio.StreamResampler``, the polyphase resampler with a carried tail (``resampled_final`` below), whose output is
 the offline resampler's on the whole audio to the bit; everything here then counts samples at the estimator's rate.
 
+``method="profile"`` streams need no net (``KeyEstimator(None, ...)``): in place of the frame cache and the net's workspace they carry a
+ring of per-frame chroma, 12 doubles a frame, which ``ake_stream_frame_stats_f32`` fills from every push's new frames and
+``ake_stream_profile_emissions_f32`` scores the newly complete windows from (host model ``metrics.stream_profile``, ring capacity
+``metrics.stream_profile_ring_frames``).  ``tuning_meter=True`` carries ``estimate_tuning``'s three sums in the same state and the same
+launch (``metrics.stream_tuning``) and reports the detuning of the audio so far with every update.  Not built: retuning inside a stream
+(a carried retuner), chunk lengths that differ between recordings, a weighting of the bins.
+
 The geometry, as pure host functions (``H`` = ``ake_cqt_plan_half_support``: frame t depends on samples ``[t*hop - H, t*hop + H]``):
 
 - ``final_frames``: with N samples received, frame t is final iff ``t*hop + H <= N - 1``; at the end all ``1 + N // hop`` frames are.
@@ -72,7 +79,12 @@ class StreamUpdate:
     (R, k2) for the k2 windows from ``smooth_first_window`` on that have left the lag; None on a stream without a smoother.  A stream
     opened with ``posteriors=True`` adds ``posteriors`` (R, k2, 24) and ``smooth_confidence`` (R, k2) for those k2 windows -- the
     probability of each key given the audio up to ``lag_windows`` windows later, and its entry at ``smooth_key_id`` -- and
-    ``log_likelihood`` (R, k), the running log-score after each new window; None otherwise."""
+    ``log_likelihood`` (R, k), the running log-score after each new window; None otherwise.
+
+    On a ``method="profile"`` stream the fields hold what ``KeyTrack`` documents for that method: ``key`` is the window's chroma,
+    ``tonic`` the larger of each tonic's two emissions, ``genre`` None, ``confidence`` the winning correlation, and ``emissions`` is
+    always there, also with ``smooth=False``.  A stream opened with ``tuning_meter=True`` adds ``tuning_cents`` and ``tuning_strength``,
+    float32 (R,): the detuning estimate over every final frame so far (zeros before the first frame); None otherwise."""
     first_window: int
     windows: int
     key: torch.Tensor
@@ -90,17 +102,19 @@ class StreamUpdate:
     posteriors: torch.Tensor | None = None
     smooth_confidence: torch.Tensor | None = None
     log_likelihood: torch.Tensor | None = None
+    tuning_cents: torch.Tensor | None = None
+    tuning_strength: torch.Tensor | None = None
 
     @staticmethod
     def concat(parts):
-        """One update out of the consecutive updates of a push that was cut into pieces."""
+        """One update out of the consecutive updates of a push that was cut into pieces (the tuning meter's value: the last piece's)."""
         if len(parts) == 1:
             return parts[0]
         cat = lambda name: None if getattr(parts[0], name) is None else torch.cat([getattr(p, name) for p in parts], dim=1)
         return StreamUpdate(parts[0].first_window, sum(p.windows for p in parts), cat("key"), cat("tonic"), cat("genre"), cat("key_id"),
                             cat("signature_id"), cat("tonic_id"), cat("confidence"), torch.cat([p.times for p in parts]), cat("emissions"),
                             cat("filtered"), parts[0].smooth_first_window, cat("smooth_key_id"), cat("posteriors"), cat("smooth_confidence"),
-                            cat("log_likelihood"))
+                            cat("log_likelihood"), parts[-1].tuning_cents, parts[-1].tuning_strength)
 
 
 class KeyStream:
@@ -108,7 +122,10 @@ class KeyStream:
 
     Everything a push needs between calls is sized here, from R, the window geometry, ``lag_windows`` and ``max_chunk_samples``: the
     audio history (float32, ``2*H + hop + max_chunk_samples`` samples a recording), the transform's output and workspace, the two
-    halves of the frame cache, the net's workspace, the smoother's state and, with ``posteriors``, the posteriors' state.  After the first push a push allocates only the tensors
+    halves of the frame cache, the net's workspace, the smoother's state and, with ``posteriors``, the posteriors' state.  A
+    ``method="profile"`` stream has neither frame cache nor net workspace: in their place stands the state of
+    ``ake_stream_frame_stats_f32``, a ring of ``window_frames + max_mel`` rows of per-frame chroma (96 bytes a frame) and three sums for
+    the tuning meter.  After the first push a push allocates only the tensors
     it returns (a chunk longer than ``max_chunk_samples`` is pushed as several pieces, whose updates are joined by one ``torch.cat``
     each).  ``push`` runs on the current stream.
 
@@ -119,22 +136,39 @@ class KeyStream:
 
     def __init__(self, est, recordings, window_seconds=15.0, stride_seconds=5.0, smooth=True, lag_windows=6, mean_key_seconds=60.0,
                  transition=None, log_prior=None, signature_weight=1.0, keep_frames=False, max_chunk_samples=None, posteriors=False,
-                 source_rate=None, source_channels=None, channel=0):
+                 source_rate=None, source_channels=None, channel=0, method="net", profiles="krumhansl", compression="log",
+                 profile_sharpness=10.0, tuning_meter=False, tuning_min_strength=0.0):
         R = int(recordings)
         if R < 1:
             raise ValueError("stream: recordings must be at least 1")
         lag = int(lag_windows)
         if not 0 <= lag <= 255:
             raise ValueError(f"stream: lag_windows must lie in 0..255, got {lag_windows}")
-        est._need_net("KeyEstimator.stream")
-        est._refuse_untrackable()
+        if method not in ("net", "profile"):
+            raise ValueError('stream: method must be "net" or "profile"')
+        self.profile = method == "profile"
+        if self.profile:
+            est._refuse_unprofilable('stream(method="profile")')
+            if float(signature_weight) != 1.0:
+                raise ValueError('stream(method="profile"): signature_weight weighs the net\'s key head, which this method does not run; leave it at 1')
+            self.mode = metrics._profile_compression(compression)
+            self.sharpness = float(profile_sharpness)
+            if not self.sharpness > 0.0:
+                raise ValueError('stream(method="profile"): profile_sharpness must be positive')
+        else:
+            est._need_net('KeyEstimator.stream(method="net")')
+            est._refuse_untrackable()
+        self.meter, self.min_strength = bool(tuning_meter), float(tuning_min_strength)
+        if self.meter and self.min_strength != self.min_strength:
+            raise ValueError("stream: tuning_min_strength is NaN")
         if posteriors and not smooth:
             raise ValueError("stream: posteriors=True needs smooth=True (the posteriors are the smoother's)")
         self.est, self.R, self.lag, self.smooth, self.posteriors = est, R, lag, bool(smooth), bool(posteriors)
         dev = self.device = est.device
         L = _lib.lib()
         plan, net = est.plan, est.net
-        net._sync_weights(dev, for_eval=True)
+        if not self.profile:
+            net._sync_weights(dev, for_eval=True)
         hop = self.hop = int(plan.hop_length)
         self.wf = track_window_frames(int(round(window_seconds * est.sample_rate)), hop)
         self.sf = track_stride_frames(stride_seconds, est.frames)
@@ -184,17 +218,32 @@ class KeyStream:
         f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         self.hist = f32(R, self.hist_cap)
         self.mel = f32(R * self.P * self.max_mel)
-        self.cache = [f32(R * self.P * self.cache_cap), f32(R * self.P * self.cache_cap)]
+        self.cache = None if self.profile else [f32(R * self.P * self.cache_cap), f32(R * self.P * self.cache_cap)]
         # which half is current, the stream's frame it begins at (W * sf: ahead of F when the stride skips frames) and the frames it holds
         self.cache_at, self.cache_start, self.cache_frames = 0, 0, 0
         with torch.cuda.device(dev):
             cqt_bytes = max(int(L.ake_cqt_workspace_bytes(plan.handle, R, n)) for n in (self.hist_cap, self.hist_cap // 2, hop))
-            net_bytes = max(int(L.ake_pcnet_forward_windows_workspace_bytes(net.handle, R, t, self.wf, self.sf))
-                            for t in (self.cache_cap, self.wf))
+            net_bytes = None if self.profile else max(int(L.ake_pcnet_forward_windows_workspace_bytes(net.handle, R, t, self.wf, self.sf))
+                                                      for t in (self.cache_cap, self.wf))
         if cqt_bytes == 0 or net_bytes == 0:
             _lib.check(-1, "stream: workspace query")
         self.cqt_ws = torch.empty(cqt_bytes, dtype=torch.uint8, device=dev)
-        self.net_ws = torch.empty(net_bytes, dtype=torch.uint8, device=dev)
+        self.net_ws = None if self.profile else torch.empty(net_bytes, dtype=torch.uint8, device=dev)
+        # ---- the profile method's chroma ring and the tuning meter's sums (ake_stream_frame_stats_f32): a piece brings at most max_mel frames
+        self.stats_parts = (1 if self.profile else 0) | (2 if self.meter else 0)
+        self.stats_state = self.tuning = None
+        if self.stats_parts:
+            self.ring_frames = metrics.stream_profile_ring_frames(self.wf, self.max_mel) if self.profile else 1
+            nbytes = int(L.ake_stream_profile_state_bytes(R, self.ring_frames))
+            if nbytes == 0:
+                _lib.check(-1, "ake_stream_profile_state_bytes")
+            self.stats_state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        if self.meter:
+            self.tuning = (torch.zeros(R, dtype=torch.float32, device=dev), torch.zeros(R, dtype=torch.float32, device=dev))
+        if self.profile:
+            from . import keyprofile
+            self.prof = keyprofile.device_profiles(profiles, dev)
+            self.key_sig = est._key_sig_table(dev)
         self.state = None
         if self.smooth:
             self.state = torch.empty(max(int(L.ake_key_stream_state_bytes(R, lag)), 16), dtype=torch.uint8, device=dev)
@@ -224,7 +273,7 @@ class KeyStream:
         if self.finished:
             raise ValueError("KeyStream.push: the stream has been finished")
         if self.resampler is not None:
-            self.est.net._sync_weights(self.device, for_eval=True)
+            self._sync_weights()
             chunk = self.resampler._checked(chunk)
             step = self.resampler.max_chunk
             return StreamUpdate.concat([self._piece(self.resampler._piece(chunk[:, :, a:a + step], False, out=self.resampled), False)
@@ -238,7 +287,7 @@ class KeyStream:
             self.dtype = chunk.dtype
         elif chunk.dtype != self.dtype:
             raise ValueError(f"KeyStream.push: this stream takes {self.dtype} chunks, got {chunk.dtype}")
-        self.est.net._sync_weights(self.device, for_eval=True)
+        self._sync_weights()
         chunk = chunk.to(self.device)
         if chunk.stride(1) != 1 and chunk.shape[1] > 1:
             chunk = chunk.contiguous()
@@ -246,6 +295,10 @@ class KeyStream:
         if m <= self.max_chunk:
             return self._piece(chunk, False)
         return StreamUpdate.concat([self._piece(chunk[:, a:a + self.max_chunk], False) for a in range(0, m, self.max_chunk)])
+
+    def _sync_weights(self):
+        if not self.profile:
+            self.est.net._sync_weights(self.device, for_eval=True)
 
     @torch.no_grad()
     def finish(self) -> StreamUpdate:
@@ -297,7 +350,15 @@ class KeyStream:
                 assert 0 <= first and first + new_frames <= T
                 # ---- the frame cache: what it holds, then the new frames (those no window needs left out), into the other half ----
                 skip = min(new_frames, max(0, self.cache_start - self.F))
-                if new_frames > skip:
+                if self.stats_parts:                                 # the chroma of every new frame into its ring row, the meter's sums
+                    if self.meter:
+                        self.tuning = (f32(R), f32(R))
+                    _lib.check(L.ake_stream_frame_stats_f32(self.mel.data_ptr(), int(self.fm), R, P, T, first, new_frames, self.F, self.ring_frames,
+                                                            self.stats_parts, self.mode if self.profile else 0, self.min_strength,
+                                                            self.stats_state.data_ptr(), self.stats_state.numel(),
+                                                            self.tuning[0].data_ptr() if self.meter else None,
+                                                            self.tuning[1].data_ptr() if self.meter else None, stream), "ake_stream_frame_stats_f32")
+                if not self.profile and new_frames > skip:
                     assert self.cache_frames + new_frames - skip <= self.cache_cap
                     dst, old = self.cache[1 - self.cache_at], self.cache[self.cache_at]
                     _lib.check(L.ake_stream_frames_f32(dst.data_ptr(), old.data_ptr(), self.mel.data_ptr(), int(self.fm), R, P, self.cache_frames, 0,
@@ -311,11 +372,20 @@ class KeyStream:
                 new_frames, F, k = 0, self.F, 0
             self.F = F
             # ---- the newly complete windows: one call of the net over the cached frames ----
-            key, tonic, genre = f32(R, k, 12), f32(R, k, 12), f32(R, k, 11) if self.est.net.genre else None
+            key, tonic, genre = f32(R, k, 12), f32(R, k, 12), f32(R, k, 11) if not self.profile and self.est.net.genre else None
             key_id, sig, tonic_id, conf = i32(R, k), i32(R, k), i32(R, k), f32(R, k)
             times = (torch.arange(self.W, self.W + k, dtype=torch.float64) * self.sf + (self.wf - 1) / 2) * hop / self.est.sample_rate
             up = StreamUpdate(self.W, k, key, tonic, genre, key_id, sig, tonic_id, conf, times)
-            if k > 0:
+            if self.meter:
+                up.tuning_cents, up.tuning_strength = self.tuning
+            if self.profile:                                         # one launch scores the new windows from the ring
+                up.emissions = f32(R, k, 24)
+                _lib.check(L.ake_stream_profile_emissions_f32(self.stats_state.data_ptr(), self.stats_state.numel(), R, self.ring_frames, self.F,
+                                                              self.wf, self.sf, self.W, k, self.prof.data_ptr(), self.sharpness,
+                                                              self.key_sig.data_ptr(), key.data_ptr(), up.emissions.data_ptr(), key_id.data_ptr(),
+                                                              conf.data_ptr(), tonic.data_ptr(), tonic_id.data_ptr(), sig.data_ptr(), stream),
+                           "ake_stream_profile_emissions_f32")
+            elif k > 0:
                 cur = self.cache[self.cache_at]
                 assert self.cache_start == self.W * self.sf and track_counts(self.cache_frames, self.wf, self.sf) == k
                 _lib.check(L.ake_pcnet_forward_windows_f32(self.est.net.handle, cur.data_ptr(), int(self.fm), R, self.cache_frames, self.wf, self.sf,
@@ -332,9 +402,11 @@ class KeyStream:
             # ---- the smoother ----
             if self.smooth:
                 first_s, k2 = smooth_count(self.W, k, self.lag, finishing)
-                up.emissions, up.filtered = f32(R, k, 24), f32(R, k, 24)
+                up.filtered = f32(R, k, 24)
                 up.smooth_first_window, up.smooth_key_id = first_s, i32(R, k2)
-                if k > 0:
+                if not self.profile:
+                    up.emissions = f32(R, k, 24)
+                if k > 0 and not self.profile:
                     _lib.check(L.ake_key_emissions_f32(key.data_ptr(), tonic.data_ptr(), R * k, None, 1, self.signature_weight,
                                                        up.emissions.data_ptr(), stream), "ake_key_emissions_f32")
                 if k > 0 or k2 > 0:

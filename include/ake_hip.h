@@ -828,6 +828,49 @@ int ake_profile_emissions_f32(const float* mel_dev, int frames_major, int record
                               float sharpness, float* chroma_out, float* emissions_out, int32_t* key_id_out, float* confidence_out,
                               void* workspace, size_t workspace_bytes, ake_stream_t stream);
 
+/* The profile method and a tuning meter on a stream of audio in lockstep (csrc/stream_profile.hip; KeyEstimator.stream(method="profile",
+ * tuning_meter=True)).  Host models: metrics.stream_profile and metrics.stream_tuning.
+ * state_dev holds, per recording, a ring of per-frame chroma, double [recordings][ring_frames][12] with the stream's frame t in row
+ * t % ring_frames (c[t][j] as above), and behind all rings the running sums P_0, P_1, P_2 of ake_tuning_estimate_f32 as double
+ * [recordings][3]: ake_stream_profile_state_bytes(recordings, ring_frames) bytes (0 for recordings outside 1..65535 or ring_frames < 1),
+ * 16-byte aligned.  The device keeps no count: frames_before and first_window are the host's.
+ * ake_stream_frame_stats_f32 takes the n_new frames from frame `first` on of a transform's output mel_dev (mel_frames frames,
+ * [recordings][pitches][mel_frames], or [recordings][mel_frames][pitches] with frames_major != 0), the stream's frames frames_before ..
+ * frames_before + n_new - 1.  parts: 1 the chroma, 2 the tuning, 3 both; the part that is off is neither read nor written.
+ *   chroma: c[t][j] in double, ake_profile_emissions_f32's sum to the bit (compression 0 / 1 / 2 as there), into the ring row of every
+ *     new frame, whether a window needs it or not, so the ring's bytes after N frames do not depend on how they were cut into calls;
+ *     of more than ring_frames new frames the last ring_frames are written.
+ *   tuning: p_j(t) = the sum of expm1(L)^2 over the bins k = j (mod 3) of frame t, in ascending k, in double; P_j += p_j(t) in ascending
+ *     t; then cents_out / strength_out float32 [recordings] by ake_tuning_estimate_f32's formulas on P (atan2 in double, strength
+ *     clamped to 1, (0, 0) without power, cents = 0 where the double strength < min_strength): the estimate over every frame so far.
+ * With frames_before == 0 the state is not read, and every part that is on is written whole (ring rows no frame has reached: zeros).
+ * n_new == 0 launches nothing and leaves the state and the two outputs alone (there is no read-out without new frames: a caller keeps
+ * the last call's outputs).  One launch, stream_frame_stats_kernel: a workgroup per recording walks the new frames in tiles of 64, the
+ * loads of twelve bins in flight at a time; the squared magnitudes of the tuning part are computed an element per thread into the LDS
+ * (up to 4623 bins; beyond, by the thread that adds them), and the frame-order addition is one thread's per P_j, behind a barrier.
+ * ake_stream_profile_emissions_f32 scores the k windows from first_window on of a stream that has `frames` frames so far (frames_before
+ * + n_new of the last call): window w covers the frames w * stride_frames .. w * stride_frames + window_frames - 1, read from the ring
+ * in ascending t, then ake_profile_emissions_f32's scoring (means first, Pearson correlation in double, the silence rule, the first
+ * maximum on the doubles).  Outputs [recordings][k][...]: chroma_out (12), emissions_out (24), key_id_out, confidence_out as there;
+ * tonic_out (12) = max(emissions[t], emissions[12 + t]); tonic_id_out = key_id % 12, or -1; signature_id_out =
+ * key_signature_dev[key_id] (int32 [24], the caller's table), or -1 for a silent window.  One launch, stream_profile_score_kernel, a
+ * block per (new window, recording); k == 0 launches nothing.
+ * No atomics: reruns are bit-identical, and neither the outputs nor the state depend on how a stream's frames are cut into calls.
+ * AKE_ERR_INVALID: null arguments, recordings outside 1..65535, ring_frames < 1 (emissions: < window_frames), window_frames < 1,
+ * stride_frames < 1, first / n_new outside mel_frames, parts outside 1..3, compression outside 0..2 (with the chroma part), min_strength
+ * NaN (with the tuning part), sharpness NaN or <= 0, a window that ends behind `frames` or begins in front of frames - ring_frames (its
+ * frames are not yet, or no longer, in the ring).  AKE_ERR_UNSUPPORTED: pitches % 3 != 0.  AKE_ERR_WORKSPACE: state_bytes short.
+ * Nothing is launched on a refusal. */
+size_t ake_stream_profile_state_bytes(int recordings, int ring_frames);
+int ake_stream_frame_stats_f32(const float* mel_dev, int frames_major, int recordings, int pitches, int mel_frames, int first, int n_new,
+                               int64_t frames_before, int ring_frames, int parts, int compression, float min_strength, void* state_dev,
+                               size_t state_bytes, float* cents_out, float* strength_out, ake_stream_t stream);
+int ake_stream_profile_emissions_f32(const void* state_dev, size_t state_bytes, int recordings, int ring_frames, int64_t frames,
+                                     int window_frames, int stride_frames, int64_t first_window, int k, const float* profiles_dev /* [2][12] */,
+                                     float sharpness, const int32_t* key_signature_dev /* [24] */, float* chroma_out, float* emissions_out,
+                                     int32_t* key_id_out, float* confidence_out, float* tonic_out, int32_t* tonic_id_out,
+                                     int32_t* signature_id_out, ake_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Per-kernel timing with hipEvents recorded on the launch stream (bench.py roofline leg).
  * ---------------------------------------------------------------------------------------- */

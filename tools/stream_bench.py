@@ -25,7 +25,14 @@
               push there was before the carried resampler): per push by events on the stream, median and 95th percentile; and the two
               added launches (stream_resample_kernel, stream_resample_tail_kernel) per launch under the library's kernel timer.
 
-Usage: python tools/stream_bench.py [--pushes 200] [--accuracy] [--posteriors] [--source-rate 48000 --source-channels 2]"""
+  --method profile [--tuning-meter]: this section alone.  est.stream(R, method="profile") on an estimator without a net beside
+              est.stream(R) with the net, both fed 0.5 s float32 chunks, at strides of 5 s and 1 s (15 s windows): per push by events on
+              the stream, median and 95th percentile; the two added launches (stream_frame_stats_kernel, stream_profile_score_kernel) per
+              launch under the library's kernel timer; and, on synthesised recordings, how many of a profile stream's key labels are those
+              of track(method="profile") on the whole audio.  --tuning-meter (also with --method net) opens the streams with the meter.
+
+Usage: python tools/stream_bench.py [--pushes 200] [--accuracy] [--posteriors] [--source-rate 48000 --source-channels 2]
+                                    [--method profile] [--tuning-meter]"""
 import argparse
 import ctypes as C
 import importlib.util
@@ -231,6 +238,56 @@ def source_rows(est, recordings, pushes, rate, channels):
     return rows
 
 
+def method_rows(est, recordings, pushes, method, meter):
+    """A push of a stream opened with `method` (and the tuning meter) beside a push of the net's stream without it, 0.5 s chunks."""
+    free = ake_amd.KeyEstimator(None, SR, 5, device=DEV, pitches=288)
+    chunk = SR // 2
+    stat = lambda ms: {"median": round(statistics.median(ms), 4), "p95": round(percentile(ms, 0.95), 4), "mean": round(statistics.fmean(ms), 4)}   # noqa: E731
+    rows = []
+    for R in recordings:
+        pieces = [torch.randn((R, chunk), device=DEV) * 0.3 for _ in range(8)]
+        for stride in (5.0, 1.0):
+            warm = 30 * SR // chunk + 1
+            kw = dict(stride_seconds=stride, method=method, tuning_meter=meter)
+            owner = free if method == "profile" else est
+            ms_new = timed_pushes(owner.stream(R, **kw), pieces, pushes, warm)
+            ms_net = timed_pushes(est.stream(R, stride_seconds=stride), pieces, pushes, warm)
+            s = owner.stream(R, **kw)
+            for i in range(warm):
+                s.push(pieces[i % 8])
+            torch.cuda.synchronize()
+            _lib.prof_enable("", True)
+            for i in range(pushes):
+                s.push(pieces[i % 8])
+            prof = _lib.prof_results()
+            _lib.prof_enable("", False)
+            rows.append({"recordings": R, "chunk_s": 0.5, "window_s": 15, "stride_s": stride, "method": method, "tuning_meter": meter,
+                         "push_ms": stat(ms_new), "push_ms_net_stream": stat(ms_net),
+                         "kernel_us_per_launch": {n: round(1e3 * t / k, 2) for n, (t, k) in prof.items() if n.startswith("stream_") and k},
+                         "launches_per_push": round(sum(k for _, k in prof.values()) / pushes, 2),
+                         "kernels_ms_per_push": round(sum(t for t, _ in prof.values()) / pushes, 4)})
+            del s
+    return rows
+
+
+def agreement_rows():
+    """A profile stream's key labels against track(method="profile") on the whole audio: 24 synthesised modulating recordings of 5 min."""
+    from ake_amd import synthetic
+    free = ake_amd.KeyEstimator(None, SR, 5, device=DEV, pitches=288)
+    audio, _ = synthetic.make_modulating_batch_device(range(24), 300.0, DEV)
+    rows = []
+    for stride in (5.0, 1.0):
+        tr = free.track(audio, stride_seconds=stride, method="profile")
+        s = free.stream(24, stride_seconds=stride, method="profile", smooth=False)
+        ups = [s.push(audio[:, a:a + SR // 2]) for a in range(0, audio.shape[1], SR // 2)] + [s.finish()]
+        key_id = torch.cat([u.key_id for u in ups], dim=1)
+        chroma = torch.cat([u.key for u in ups], dim=1)
+        assert key_id.shape == tr.key_id.shape
+        rows.append({"stride_s": stride, "windows": int(key_id.numel()), "labels_equal": int((key_id == tr.key_id).sum()),
+                     "share": round(float((key_id == tr.key_id).float().mean()), 5), "largest_chroma_difference": float((chroma - tr.key).abs().max())})
+    return rows
+
+
 def frame_rows(est):
     plan = est.plan
     H = int(_lib.lib().ake_cqt_plan_half_support(plan.handle))
@@ -283,6 +340,8 @@ def main():
     ap.add_argument("--posteriors", action="store_true")
     ap.add_argument("--source-rate", type=int, default=None)
     ap.add_argument("--source-channels", type=int, default=1)
+    ap.add_argument("--method", choices=("net", "profile"), default=None)
+    ap.add_argument("--tuning-meter", action="store_true")
     args = ap.parse_args()
     torch.manual_seed(0)
     gold = np.load(os.path.join(REPO, "tests", "golden", "pcnet_default.npz"))
@@ -297,6 +356,13 @@ def main():
     if args.source_rate is not None:
         print(json.dumps({"device": torch.cuda.get_device_name(0), "pushes": args.pushes,
                           "source": source_rows(est, args.recordings, args.pushes, args.source_rate, args.source_channels)}))
+        return
+    if args.method is not None or args.tuning_meter:
+        method = args.method or "net"
+        out = {"device": torch.cuda.get_device_name(0), "pushes": args.pushes, "method": method_rows(est, args.recordings, args.pushes, method, args.tuning_meter)}
+        if method == "profile":
+            out["streamed_against_offline_labels"] = agreement_rows()
+        print(json.dumps(out))
         return
     rows = [push_row(est, R, chunk, dtype, args.pushes, args.baseline_reps)
             for R in args.recordings for chunk in (HOP, SR) for dtype in (torch.float32, torch.int16)]
