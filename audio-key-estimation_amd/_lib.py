@@ -130,6 +130,11 @@ SYMBOLS = {
     "ake_retune_out_len": (_I64, [_I64]),
     "ake_retune_f32": (_I, [_P, _I, _I64, _I64, _P, _P, _P, _I64, _P, _P]),
     "ake_retune_pcm16_f32": (_I, [_P, _I, _I64, _I64, _P, _P, _P, _I64, _P, _P]),
+    "ake_retune_ratio": (_I, [C.c_float, C.POINTER(C.c_double), _P]),
+    "ake_stream_retune_out_count": (_I64, [C.c_float, C.c_double, _I64, _I]),
+    "ake_stream_retune_state_bytes": (_SZ, [_I]),
+    "ake_stream_retune_f32": (_I, [_P, _I, _I64, _I64, C.c_float, C.c_double, _I64, _I, _P, _SZ, _P, _I64, C.POINTER(_I64), _P]),
+    "ake_stream_retune_pcm16_f32": (_I, [_P, _I, _I64, _I64, C.c_float, C.c_double, _I64, _I, _P, _SZ, _P, _I64, C.POINTER(_I64), _P]),
     "ake_profile_workspace_bytes": (_SZ, [_I, _I]),
     "ake_profile_windows": (_I, [_I, _I, _I]),
     "ake_profile_emissions_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _I, C.c_float, _P, _P, _P, _P, _P, _SZ, _P]),

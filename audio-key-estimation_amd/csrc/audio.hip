@@ -16,6 +16,9 @@
 // Retuning (ake_retune_f32, not in the reference either) is the same stage with a ratio per row that is no fraction of small integers:
 // rho = 2^(cents / 1200) undoes a detuning of `cents` (ake_tuning_estimate_f32 measures it).  Definition, table and order of the sums:
 // metrics.retune_reference, the float64 model of retune_kernel.
+//
+// Both stages also run on audio that arrives in chunks (ake_stream_resample_*, ake_stream_retune_*): the offline kernel's sums over a
+// short carried ring of inputs and the chunk, bit-identical to the offline call on the joined audio however it is cut.
 #include "common.h"
 
 #include <cmath>
@@ -159,6 +162,40 @@ template <typename T> __device__ __forceinline__ float retune_sample(T v);
 template <> __device__ __forceinline__ float retune_sample<float>(float v) { return v; }
 template <> __device__ __forceinline__ float retune_sample<short>(short v) { return static_cast<float>(v) * (1.f / 32768.f); }
 
+// `cents` as a caller gives them -> what the retuner reads: NaN as 0, beyond +-50 as +-50.  Host and device.
+__host__ __device__ __forceinline__ float retune_clamped(float cents) {
+    return cents != cents ? 0.f : fminf(fmaxf(cents, -static_cast<float>(kRetuneMaxCents)), static_cast<float>(kRetuneMaxCents));
+}
+
+// clamped cents -> rho.  Device only: the host's exp2 may round the last place another way, and every count and every read position
+// hangs on this double (ake_retune_ratio hands it to the host).
+__device__ __forceinline__ double retune_ratio(float cents) {
+    // at the clamp the ratio is the literal the buffer's width was sized with, so n_out < width whatever exp2 rounds to
+    return cents >= static_cast<float>(kRetuneMaxCents) ? kRetuneMaxRatio
+         : cents <= -static_cast<float>(kRetuneMaxCents) ? 1.0 / kRetuneMaxRatio : exp2(static_cast<double>(cents) / 1200.0);
+}
+
+// Output sample k of a row: G the filter table and X the staged input stretch, both in LDS, X[j - j_base] = x[j] (zeros outside the row).
+__device__ __forceinline__ float retune_output(long long k, double inv, const float* G, const float* X, long long j_base) {
+    // the read position in double; only its fraction is rounded to float32, so the error does not grow with k
+    const double pos = static_cast<double>(k) * inv, j0d = floor(pos);
+    const float fr = static_cast<float>(pos - j0d) * kRetuneRes;
+    int r = static_cast<int>(fr);
+    r = r < kRetuneRes - 1 ? r : kRetuneRes - 1;
+    const float t = fr - static_cast<float>(r);
+    const float* xs = X + (static_cast<long long>(j0d) - j_base);     // xs[m] = x[j0 + m], m = -Z + 1 .. Z
+    float acc = 0.f;
+    int q = r + (kRetuneZeros - 1) * kRetuneRes;
+#pragma unroll 8
+    for (int m = -kRetuneZeros + 1; m <= 0; ++m, q -= kRetuneRes)    // d = fraction - m >= 0
+        acc = fmaf(xs[m], fmaf(t, G[q + 1] - G[q], G[q]), acc);
+    q = kRetuneRes - r - 1;
+#pragma unroll 8
+    for (int m = 1; m <= kRetuneZeros; ++m, q += kRetuneRes)         // d < 0: h(-d), read downwards
+        acc = fmaf(xs[m], fmaf(t, G[q] - G[q + 1], G[q + 1]), acc);
+    return acc;
+}
+
 template <typename T>
 struct RetuneArgs {
     const T* in;                // [batch][in_stride]
@@ -177,12 +214,9 @@ __global__ __launch_bounds__(kRetuneThreads) void retune_kernel(RetuneArgs<T> a)
     const int row = blockIdx.y, tid = threadIdx.x;
     long long n = a.n_max;
     if (a.n_in) { const long long nc = a.n_in[row]; n = nc < 0 ? 0 : (nc < n ? nc : n); }
-    float cents = a.cents[row];
-    cents = cents != cents ? 0.f : fminf(fmaxf(cents, -static_cast<float>(kRetuneMaxCents)), static_cast<float>(kRetuneMaxCents));
+    const float cents = retune_clamped(a.cents[row]);
     const bool copy = cents == 0.f;
-    // at the clamp the ratio is the literal the buffer's width was sized with, so n_out < width whatever exp2 rounds to
-    const double rho = cents >= static_cast<float>(kRetuneMaxCents) ? kRetuneMaxRatio
-                     : cents <= -static_cast<float>(kRetuneMaxCents) ? 1.0 / kRetuneMaxRatio : exp2(static_cast<double>(cents) / 1200.0);
+    const double rho = retune_ratio(cents);
     const double inv = 1.0 / rho;
     long long n_out = copy ? n : static_cast<long long>(floor(static_cast<double>(n) * rho));
     n_out = n_out < a.width ? n_out : a.width - 1;                // (|cents| < 50: rho < the literal by far more than an ulp; a guard all the same)
@@ -215,23 +249,7 @@ __global__ __launch_bounds__(kRetuneThreads) void retune_kernel(RetuneArgs<T> a)
             const long long k = k0 + i;
             if (k >= a.width) break;
             if (k >= n_out) { y[k] = 0.f; continue; }
-            // the read position in double; only its fraction is rounded to float32, so the error does not grow with k
-            const double pos = static_cast<double>(k) * inv, j0d = floor(pos);
-            const float fr = static_cast<float>(pos - j0d) * kRetuneRes;
-            int r = static_cast<int>(fr);
-            r = r < kRetuneRes - 1 ? r : kRetuneRes - 1;
-            const float t = fr - static_cast<float>(r);
-            const float* xs = X + (static_cast<long long>(j0d) - j_base);     // xs[m] = x[j0 + m], m = -Z + 1 .. Z
-            float acc = 0.f;
-            int q = r + (kRetuneZeros - 1) * kRetuneRes;
-#pragma unroll 8
-            for (int m = -kRetuneZeros + 1; m <= 0; ++m, q -= kRetuneRes)    // d = fraction - m >= 0
-                acc = fmaf(xs[m], fmaf(t, G[q + 1] - G[q], G[q]), acc);
-            q = kRetuneRes - r - 1;
-#pragma unroll 8
-            for (int m = 1; m <= kRetuneZeros; ++m, q += kRetuneRes)         // d < 0: h(-d), read downwards
-                acc = fmaf(xs[m], fmaf(t, G[q] - G[q + 1], G[q + 1]), acc);
-            y[k] = acc;
+            y[k] = retune_output(k, inv, G, X, j_base);
         }
     }
 }
@@ -398,6 +416,138 @@ int stream_resample(const char* name, const ake_resampler* r, const T* chunk_dev
     return AKE_OK;
 }
 
+// ---- the retuner on audio that arrives in chunks (ake_stream_retune_*) ----
+// retune_kernel's sum over "what came before, then the chunk", as stream_resample_kernel is resample_kernel's.  With inv = 1 / rho output k
+// reads the inputs floor(k inv) - Z + 1 .. floor(k inv) + Z, so it is final once floor(double(k) inv) + Z <= N - 1 (N inputs so far; a
+// prefix of the outputs, the product being monotone in k), and the first output still to come reaches back at most 2 Z - 1 = 63 inputs
+// (floor(k inv) + Z > N - 1 for it).  Those are carried per recording as a ring of 2 Z float32, input i at slot i % 64, converted from PCM
+// before they are stored.  Every count is the host's (stream_retune_count), from the rho that ake_retune_ratio read off the device once.
+//   stream_retune_kernel: a workgroup loads the table and makes kSrtTiles tiles of kSrtTile consecutive outputs of one recording; a
+//     tile's input stretch is staged in LDS (ring slot for i < n_before, the chunk behind it, zeros below 0 and -- under flush only -- at
+//     and behind n_total), then every thread runs retune_output, retune_kernel's own per-sample code.
+//   stream_retune_tail_kernel: the last 64 inputs of the chunk go into their ring slots.  A second launch for stream_resample_tail_kernel's
+//     reason: the first only reads the ring, the second only writes it.
+// Tiling: a push is 0.1 to 10 s, 2205 to 220500 outputs a recording.  The offline 2048 x 8 would put anything under 0.74 s on one workgroup
+// a recording.  256 x 4: one output a thread and tile, 1024 a workgroup, so a 0.1 s push of one recording runs on 3 workgroups and a 10 s
+// push on 216, one per CU; the 32 KiB table load (32 loads a thread) stands against 4 x 64 taps a thread, and 34 KiB of LDS let four
+// workgroups share a CU.  Smaller tiles pay the table more often than they gain: a 0.1 s push is bound by its launches either way.
+constexpr int kSrtThreads = 256, kSrtTile = 256, kSrtTiles = 4, kSrtRing = 2 * kRetuneZeros;
+constexpr int kSrtStretch = 336;                                  // >= floor(255 * 1.02931) + 2 + 2 Z = 328
+static_assert(kSrtTile == kSrtThreads && kSrtStretch >= static_cast<int>((kSrtTile - 1) * kRetuneMaxRatio) + 2 + 2 * kRetuneZeros, "stream retune tiling");
+
+template <typename T>
+struct StreamRetuneArgs {
+    const T* chunk;             // [recordings][rec_stride]: m = n_total - n_before samples each
+    long long rec_stride;
+    long long n_before, n_total;       // inputs in front of this chunk, and with it
+    long long k_first, k_count;        // outputs [k_first, k_first + k_count) are written
+    double rho;
+    int copy;                   // cents == 0: output k is input k, no state
+    float* state;               // [recordings][kSrtRing]
+    float* out;                 // [recordings][out_stride]
+    long long out_stride;
+};
+
+template <typename T>
+__global__ __launch_bounds__(kSrtThreads) void stream_retune_kernel(StreamRetuneArgs<T> a) {
+    __shared__ float G[kRetuneTable + 1];
+    __shared__ float X[kSrtStretch];
+    const int rec = blockIdx.y, tid = threadIdx.x;
+    const T* x = a.chunk + rec * a.rec_stride;
+    float* y = a.out + rec * a.out_stride;
+    const long long q_first = static_cast<long long>(blockIdx.x) * (kSrtTile * kSrtTiles);       // counted from k_first
+    if (a.copy) {                                                 // k_first == n_before: output q of the call is sample q of the chunk
+        const long long q_end = q_first + kSrtTile * kSrtTiles < a.k_count ? q_first + kSrtTile * kSrtTiles : a.k_count;
+        for (long long q = q_first + tid; q < q_end; q += kSrtThreads) y[q] = retune_sample<T>(x[q]);
+        return;
+    }
+    for (int i = tid; i < kRetuneTable + 1; i += kSrtThreads) G[i] = g_retune_table[i];
+    const double inv = 1.0 / a.rho;
+    const float* ring = a.state + static_cast<long long>(rec) * kSrtRing;
+    for (int tile = 0; tile < kSrtTiles; ++tile) {
+        const long long q0 = q_first + static_cast<long long>(tile) * kSrtTile;
+        if (q0 >= a.k_count) break;                               // (uniform over the workgroup)
+        // the tile's input stretch: input j of the stream at X[j - j_base]; j >= n_before - 63 for the first tile, so the ring holds it
+        const long long j_base = static_cast<long long>(floor(static_cast<double>(a.k_first + q0) * inv)) - kRetuneZeros + 1;
+        __syncthreads();                                          // (the last tile's reads of X are done)
+        for (int i = tid; i < kSrtStretch; i += kSrtThreads) {
+            const long long j = j_base + i;
+            float v = 0.f;
+            if (j >= 0 && j < a.n_total) v = j < a.n_before ? ring[j % kSrtRing] : retune_sample<T>(x[j - a.n_before]);
+            X[i] = v;
+        }
+        __syncthreads();
+        const long long q = q0 + tid;
+        if (q < a.k_count) y[q] = retune_output(a.k_first + q, inv, G, X, j_base);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kSrtRing) void stream_retune_tail_kernel(StreamRetuneArgs<T> a) {
+    const int rec = blockIdx.x;
+    const T* x = a.chunk + rec * a.rec_stride;
+    float* ring = a.state + static_cast<long long>(rec) * kSrtRing;
+    const long long first = a.n_total - kSrtRing > a.n_before ? a.n_total - kSrtRing : a.n_before;
+    const long long i = first + threadIdx.x;
+    if (i < a.n_total) ring[i % kSrtRing] = retune_sample<T>(x[i - a.n_before]);
+}
+
+__global__ void retune_ratio_kernel(float cents, double* rho) { *rho = retune_ratio(retune_clamped(cents)); }
+
+bool retune_ratio_ok(double rho) { return rho >= 1.0 / kRetuneMaxRatio && rho <= kRetuneMaxRatio; }      // (false for NaN)
+
+// `cents` clamped.  The predicate is evaluated in the double expression the kernel's read position is, never in a closed form.
+int64_t stream_retune_count(float cents, double rho, int64_t n, int flush) {
+    if (cents == 0.f) return n;
+    if (flush) {                                                  // the offline count, under retune_kernel's width guard
+        const int64_t n_out = static_cast<int64_t>(std::floor(static_cast<double>(n) * rho)), width = ake_retune_out_len(n);
+        return n_out < width ? n_out : width - 1;
+    }
+    const double inv = 1.0 / rho;
+    auto is_final = [&](int64_t k) { return static_cast<int64_t>(std::floor(static_cast<double>(k) * inv)) + kRetuneZeros <= n - 1; };
+    int64_t k = n > kRetuneZeros ? static_cast<int64_t>(std::floor(static_cast<double>(n - kRetuneZeros) * rho)) : 0;
+    while (k > 0 && !is_final(k - 1)) --k;                           // (a step or two: the guess is off by the roundings alone)
+    while (is_final(k)) ++k;
+    return k;
+}
+
+template <typename T>
+int stream_retune(const char* name, const T* chunk_dev, int recordings, int64_t m, int64_t rec_stride, float cents, double rho, int64_t n_before,
+                  int flush, void* state_dev, size_t state_bytes, float* out_dev, int64_t out_stride, int64_t* k_out, ake_stream_t stream) {
+    AKE_REQUIRE(state_dev && k_out, AKE_ERR_INVALID, "%s: null state or k_out", name);
+    AKE_REQUIRE(recordings >= 1 && recordings <= 65535, AKE_ERR_INVALID, "%s: bad recordings %d", name, recordings);
+    AKE_REQUIRE(m >= 0 && n_before >= 0 && m <= (1ll << 40) && n_before <= (1ll << 40), AKE_ERR_INVALID, "%s: bad m %lld / n_before %lld", name,
+                static_cast<long long>(m), static_cast<long long>(n_before));
+    AKE_REQUIRE(m == 0 || (chunk_dev && rec_stride >= 0), AKE_ERR_INVALID, "%s: null chunk or bad row stride %lld", name,
+                static_cast<long long>(rec_stride));
+    AKE_REQUIRE(retune_ratio_ok(rho), AKE_ERR_INVALID, "%s: rho %g is no ratio of the retuner (ake_retune_ratio gives it)", name, rho);
+    AKE_REQUIRE((reinterpret_cast<uintptr_t>(state_dev) & 15) == 0, AKE_ERR_INVALID, "%s: the state must be 16-byte aligned", name);
+    const size_t need = ake_stream_retune_state_bytes(recordings);
+    AKE_REQUIRE(state_bytes >= need, AKE_ERR_WORKSPACE, "%s: state of %zu bytes, %zu needed", name, state_bytes, need);
+    cents = retune_clamped(cents);
+    const bool copy = cents == 0.f;
+    const int64_t k_first = stream_retune_count(cents, rho, n_before, 0), k_count = stream_retune_count(cents, rho, n_before + m, flush) - k_first;
+    AKE_REQUIRE(k_count >= 0 && (k_count == 0 || (out_dev && out_stride >= k_count)), AKE_ERR_INVALID,
+                "%s: null output or out_stride %lld < %lld output samples", name, static_cast<long long>(out_stride), static_cast<long long>(k_count));
+    if (k_count > 0 && !copy) {
+        const int rc = retune_table_upload();
+        if (rc) return rc;
+    }
+    *k_out = k_count;
+    StreamRetuneArgs<T> a{chunk_dev, rec_stride, n_before, n_before + m, k_first, k_count, rho, copy ? 1 : 0, static_cast<float*>(state_dev), out_dev,
+                          out_stride};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (k_count > 0) {
+        constexpr int per_block = kSrtTile * kSrtTiles;
+        const int rc = ake::launch("stream_retune_kernel", stream_retune_kernel<T>, dim3(static_cast<unsigned>((k_count + per_block - 1) / per_block), recordings),
+                                   dim3(kSrtThreads), 0, s, a);
+        if (rc) return rc;
+    }
+    if (m > 0 && !copy && !flush)                                 // (behind a flush nothing is carried)
+        return ake::launch("stream_retune_tail_kernel", stream_retune_tail_kernel<T>, dim3(recordings), dim3(kSrtRing), 0, s, a);
+    return AKE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -521,6 +671,46 @@ int ake_retune_pcm16_f32(const int16_t* in_dev, int batch, int64_t n_max, int64_
                          float* out_dev, int64_t out_stride, int64_t* lengths_out_dev, ake_stream_t stream) {
     return retune_launch<short>("retune_pcm16_kernel", reinterpret_cast<const short*>(in_dev), batch, n_max, in_stride, lengths_dev, cents_dev,
                                 out_dev, out_stride, lengths_out_dev, stream);
+}
+
+int ake_retune_ratio(float cents, double* rho_out, ake_stream_t stream) {
+    AKE_REQUIRE(rho_out, AKE_ERR_INVALID, "ake_retune_ratio: null rho_out");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double* rho_dev = nullptr;
+    AKE_HIP_CHECK(hipMalloc(&rho_dev, sizeof(double)));
+    int rc = ake::launch("retune_ratio_kernel", retune_ratio_kernel, dim3(1), dim3(1), 0, s, cents, rho_dev);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemcpyAsync(rho_out, rho_dev, sizeof(double), hipMemcpyDeviceToHost, s);
+    if (!rc && e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(rho_dev);
+    if (e != hipSuccess) {
+        ake::set_error("ake_retune_ratio: reading the ratio back failed: %s", hipGetErrorString(e));
+        return AKE_ERR_HIP;
+    }
+    return rc;
+}
+
+int64_t ake_stream_retune_out_count(float cents, double rho, int64_t n_in, int flush) {
+    if (n_in < 0 || n_in > (1ll << 40) || !retune_ratio_ok(rho)) return -1;
+    return stream_retune_count(retune_clamped(cents), rho, n_in, flush);
+}
+
+size_t ake_stream_retune_state_bytes(int recordings) {
+    if (recordings < 1 || recordings > 65535) return 0;
+    return static_cast<size_t>(recordings) * kSrtRing * sizeof(float);
+}
+
+int ake_stream_retune_f32(const float* chunk_dev, int recordings, int64_t m, int64_t rec_stride, float cents, double rho, int64_t n_before, int flush,
+                          void* state_dev, size_t state_bytes, float* out_dev, int64_t out_stride, int64_t* k_out, ake_stream_t stream) {
+    return stream_retune<float>("ake_stream_retune_f32", chunk_dev, recordings, m, rec_stride, cents, rho, n_before, flush, state_dev, state_bytes,
+                                out_dev, out_stride, k_out, stream);
+}
+
+int ake_stream_retune_pcm16_f32(const int16_t* chunk_dev, int recordings, int64_t m, int64_t rec_stride, float cents, double rho, int64_t n_before,
+                                int flush, void* state_dev, size_t state_bytes, float* out_dev, int64_t out_stride, int64_t* k_out,
+                                ake_stream_t stream) {
+    return stream_retune<short>("ake_stream_retune_pcm16_f32", reinterpret_cast<const short*>(chunk_dev), recordings, m, rec_stride, cents, rho,
+                                n_before, flush, state_dev, state_bytes, out_dev, out_stride, k_out, stream);
 }
 
 }  // extern "C"

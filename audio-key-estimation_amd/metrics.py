@@ -1132,6 +1132,107 @@ def stream_resample(chunks, rate_in, rate_out, channel=0):
     return outs
 
 
+# ---- the retuner on audio that arrives in chunks (ake_stream_retune_f32) ----
+
+def retune_ratio(cents):
+    """``cents`` as the retuner reads them -> ``(cents, rho)``: rounded to float32, NaN as 0, beyond +-50 as +-50; ``rho = 2 ** (cents /
+    1200)``, the literal ``RETUNE_MAX_RATIO`` (or its inverse) at the clamp.  The host's power: the device's own (``ake_retune_ratio``,
+    ``StreamRetuner.rho``) may differ from it in the last place."""
+    import numpy as np
+    c = float(np.float32(cents))
+    c = 0.0 if c != c else min(max(c, -RETUNE_MAX_CENTS), RETUNE_MAX_CENTS)
+    rho = RETUNE_MAX_RATIO if c >= RETUNE_MAX_CENTS else 1.0 / RETUNE_MAX_RATIO if c <= -RETUNE_MAX_CENTS else 2.0 ** (c / 1200.0)
+    return c, rho
+
+
+def _retune_is_final(k, inv, n_in):
+    """Output k reads the inputs up to ``floor(k * inv) + Z``: the double product the kernel's read position is."""
+    import math
+    return math.floor(float(k) * inv) + RETUNE_ZEROS <= n_in - 1
+
+
+def retune_final(n_in, rho, finished=False, copy=None):
+    """Outputs of the retuner that are final after ``n_in`` inputs (``ake_stream_retune_out_count``).  With ``inv = 1.0 / rho`` output k
+    reads the inputs ``floor(k*inv) - Z + 1 .. floor(k*inv) + Z``, so it is final iff ``floor(float(k) * inv) + Z <= n_in - 1``; the final
+    outputs are a prefix (the product is monotone in k), whose size is found from the guess ``floor((n_in - Z) * rho)`` by testing that
+    very expression, not from a closed form.  At the end (``finished``) all ``floor(n_in * rho)`` are (never above ``retune_out_len(n_in)
+    - 1``).  ``copy``: the stream is not retuned (``cents == 0``: output k is input k, all ``n_in`` are final); default ``rho == 1.0``."""
+    import math
+    n_in, rho = int(n_in), float(rho)
+    if (rho == 1.0) if copy is None else copy:
+        return n_in
+    if finished:
+        return min(int(math.floor(float(n_in) * rho)), retune_out_len(n_in) - 1)
+    inv = 1.0 / rho
+    k = int(math.floor(float(n_in - RETUNE_ZEROS) * rho)) if n_in > RETUNE_ZEROS else 0
+    while k > 0 and not _retune_is_final(k - 1, inv, n_in):
+        k -= 1
+    while _retune_is_final(k, inv, n_in):
+        k += 1
+    return k
+
+
+def retune_tail(n_in, rho, copy=None):
+    """Inputs a stream must still hold after ``n_in`` of them: from the first input of the first output that is not final yet,
+    ``floor(k*inv) - Z + 1``.  Never more than ``2*Z - 1`` = 63 (``floor(k*inv) + Z > n_in - 1`` for that output)."""
+    import math
+    if (float(rho) == 1.0) if copy is None else copy:
+        return 0
+    first = math.floor(float(retune_final(n_in, rho, copy=False)) * (1.0 / float(rho))) - RETUNE_ZEROS + 1
+    return int(n_in) - min(int(n_in), max(0, first))
+
+
+def stream_retune(pieces, cents):
+    """Float64 model of ``ake_stream_retune_f32``: ``pieces`` is a sequence of (m,) arrays, the consecutive pieces of one recording (m >= 0,
+    any mix of lengths) -> a list of ``len(pieces) + 1`` float64 arrays: the outputs each piece makes final, and last what ``finish()``
+    adds.  Joined they are ``retune_reference`` on the joined pieces, ``floor(n * rho)`` samples, exactly: the same products added in the
+    same order.
+
+    Between pieces the model keeps what the kernel keeps, the last ``retune_tail`` (at most 63) inputs.  Every output is
+    ``retune_reference``'s sum over "tail, then piece": the position ``k / rho`` in float64, its fraction rounded to float32, the two table
+    blends, the taps added in ascending j, zeros in front of sample 0 and -- for ``finish()`` alone -- behind the end.  ``cents == 0`` (after
+    the clamp): every piece is its own output and nothing is kept."""
+    import numpy as np
+    c, rho = retune_ratio(cents)
+    copy = c == 0.0
+    Z, R = RETUNE_ZEROS, RETUNE_RESOLUTION
+    G = retune_table().astype(np.float64)
+    inv = 1.0 / rho
+    held, held_first, n, outs = np.zeros(0), 0, 0, []                  # held[0] is input `held_first`
+    for piece in list(pieces) + [None]:
+        finished = piece is None
+        x = np.zeros(0) if finished else np.asarray(piece, dtype=np.float64).reshape(-1)
+        if copy:
+            outs.append(x.copy())
+            continue
+        held = np.concatenate([held, x])
+        k0 = retune_final(n, rho, copy=False)
+        n += x.shape[0]
+        k1 = retune_final(n, rho, finished, copy=False)
+        pos = np.arange(k0, k1, dtype=np.float64) * inv
+        j0 = np.floor(pos)
+        fr = (pos - j0).astype(np.float32) * np.float32(R)
+        r = np.minimum(fr.astype(np.int64), R - 1)
+        t = (fr - r.astype(np.float32)).astype(np.float64)
+        j0 = j0.astype(np.int64)
+        assert k1 == k0 or (j0[0] - Z + 1 >= held_first or held_first == 0) and (finished or j0[-1] + Z <= n - 1)
+        # input j at xp[j - held_first + 2 Z]: what is held, zeros in front of sample 0 and behind the end
+        xp = np.concatenate([np.zeros(2 * Z), held, np.zeros(2 * Z + 1)])
+        acc = np.zeros(k1 - k0, dtype=np.float64)
+        for m in range(-Z + 1, Z + 1):
+            if m <= 0:
+                q = r - m * R
+                w = G[q] + t * (G[q + 1] - G[q])
+            else:
+                q = m * R - r - 1
+                w = G[q + 1] + t * (G[q] - G[q + 1])
+            acc += xp[j0 + m - held_first + 2 * Z] * w
+        outs.append(acc)
+        keep = retune_tail(n, rho, copy=False)
+        held, held_first = held[held.shape[0] - keep:], n - keep
+    return outs
+
+
 # ---- key-profile emissions: a key track without a trained net (ake_profile_emissions_f32) ----
 
 # Published tone profiles, rows minor and major (the order of KEY_NAMES' two halves), tonic first.  "krumhansl": Krumhansl & Kessler

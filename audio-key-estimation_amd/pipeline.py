@@ -363,10 +363,7 @@ class KeyEstimator:
 
     def _given_tuning(self, tuning, B):
         """``tuning`` of ``__call__`` / ``track`` checked -> None for "auto", else the (B,) float32 cents on the device."""
-        top = 32.70319566257483 * 2.0 ** ((self.plan.n_bins - 1) / self.plan.bins_per_octave)           # C1, the plan's fmin
-        if top >= metrics.RETUNE_CUTOFF * self.sample_rate / 2:
-            raise ValueError(f"tuning: the retuner keeps {metrics.RETUNE_CUTOFF} of the Nyquist frequency, and this estimator's top bin "
-                             f"({top:.0f} Hz at {self.sample_rate} Hz) lies beyond it")
+        self._refuse_unretunable("tuning")
         if isinstance(tuning, str):
             if tuning != "auto":
                 raise ValueError('tuning must be None, "auto", a number of cents or a (B,) tensor of cents')
@@ -381,6 +378,13 @@ class KeyEstimator:
         if not abs(float(tuning)) <= metrics.RETUNE_MAX_CENTS:
             raise ValueError(f"tuning: {tuning} cents; a detuning lies within +-{metrics.RETUNE_MAX_CENTS:g} cents (beyond that it is the next semitone)")
         return torch.full((B,), float(tuning), dtype=torch.float32, device=self.device)
+
+    def _refuse_unretunable(self, what):
+        """The retuner discards what lies above 0.94 of the Nyquist frequency: an estimator whose top bin lies there cannot use it."""
+        top = 32.70319566257483 * 2.0 ** ((self.plan.n_bins - 1) / self.plan.bins_per_octave)           # C1, the plan's fmin
+        if top >= metrics.RETUNE_CUTOFF * self.sample_rate / 2:
+            raise ValueError(f"{what}: the retuner keeps {metrics.RETUNE_CUTOFF} of the Nyquist frequency, and this estimator's top bin "
+                             f"({top:.0f} Hz at {self.sample_rate} Hz) lies beyond it")
 
     def _slot_ws(self, slot, nbytes):
         if slot["ws"] is None or slot["ws"].numel() < nbytes:
@@ -535,7 +539,7 @@ class KeyEstimator:
                signature_weight: float = 1.0, keep_frames: bool = False, max_chunk_samples: int | None = None, rate: int | None = None,
                tuning=None, posteriors: bool = False, source_rate: int | None = None, source_channels: int | None = None, channel: int = 0,
                method: str = "net", profiles="krumhansl", compression: str = "log", profile_sharpness: float = 10.0,
-               tuning_meter: bool = False, tuning_min_strength: float = 0.0):
+               tuning_meter: bool = False, tuning_min_strength: float = 0.0, retune_cents: float | None = None):
         """Track keys on audio as it arrives -> ``ake_amd.KeyStream``: ``push(chunk)`` takes the next (R, m) samples of all
         ``recordings`` = R recordings at once (float32, or int16 = 16-bit PCM; any m >= 0, the same m for every recording) and returns
         a ``StreamUpdate`` with the windows that chunk completed; ``finish()`` ends the recordings and returns the rest.
@@ -587,24 +591,37 @@ class KeyEstimator:
         ``tuning_meter=True``, with either method, adds ``StreamUpdate.tuning_cents`` and ``.tuning_strength`` (R,): ``estimate_tuning``
         over every final frame so far, from three sums carried on the device (``metrics.stream_tuning``; ``tuning_min_strength`` as
         ``min_strength`` there).  It rides in the profile method's frame launch; on a ``"net"`` stream it is that launch with the chroma
-        part off, one more launch per piece that has new frames.  A meter only: the stream is not retuned.
+        part off, one more launch per piece that has new frames.  The meter itself retunes nothing.
+
+        ``retune_cents=c`` (one number within +-50, the same for all recordings) retunes the stream as ``track(tuning=c)`` retunes a
+        recording: an ``ake_amd.StreamRetuner`` stands behind the optional resampler and in front of the history, the offline 64-tap
+        varispeed filter carrying its last 64 inputs from push to push, so the stream sees ``ake_amd.retune(whole, c)`` bit for bit
+        however the audio is cut (one or two small launches a push: ``ake_stream_retune_f32``; the ratio ``rho = 2 ** (c / 1200)`` is
+        read off the device once, here, and a push still reads nothing back).  Everything downstream counts retuned samples: after N
+        samples the stream has emitted the windows ``track(audio, tuning=c)`` gives.  ``StreamUpdate.times`` are divided by ``rho``, so
+        they are seconds of the recording as it was pushed; ``StreamUpdate.retune_cents`` carries c; with ``tuning_meter=True`` the meter
+        sees the retuned audio and reports the detuning that is left.  ``max_chunk_samples`` counts samples in front of the retuner.
+        ``None`` and ``0`` leave the stream as it is without the keyword: the same launches, the same bits.  The number is the caller's:
+        a stream does not retune itself from its meter, which would take a read-back or a ratio that changes in mid-stream.
 
         Refused with a ``ValueError``: ``posteriors=True`` with ``smooth=False``; what ``track`` refuses (``frames=0``, ``wrap_mode="true_end"``, ``--local`` nets), with
         ``method="net"`` an estimator without a net, ``rate`` other than the estimator's (``rate`` names the rate the stream works at; what arrives is
         ``source_rate``), multi-channel chunks on a stream opened without ``source_channels``, ``tuning``, ``lag_windows`` outside
         0..255; by ``push``: a chunk after ``finish()``, a chunk whose R (or C) differs from the stream's, on a stream without a source
-        format a dtype that differs from the first chunk's.  Not built: retuning inside a stream (a carried retuner), chunk lengths
-        that differ between recordings, and a weighting of the bins in the chroma."""
+        format a dtype that differs from the first chunk's; ``retune_cents`` that is no number within +-50, or on an estimator whose
+        top bin lies above 0.94 of the Nyquist frequency (as ``track(tuning=...)``).  Not built: automatic retuning inside a stream
+        (from its own meter), chunk lengths that differ between recordings, and a weighting of the bins in the chroma."""
         from .stream import KeyStream
         if rate is not None and int(rate) != self.sample_rate:
             raise ValueError(f"stream: rate is the rate the stream works at, the estimator's ({self.sample_rate} Hz); for chunks at "
                              f"another rate pass source_rate={int(rate)} (and source_channels), which resamples them with carried state")
         if tuning is not None:
-            raise ValueError("stream: tuning (retuning the audio) is not offered inside a stream; tuning_meter=True reports the running "
-                             "estimate in StreamUpdate.tuning_cents / .tuning_strength")
+            raise ValueError("stream: tuning (estimating and retuning as track does) is not offered inside a stream; tuning_meter=True "
+                             "reports the running estimate in StreamUpdate.tuning_cents / .tuning_strength, and retune_cents=c retunes "
+                             "the stream by a number of cents the caller names")
         return KeyStream(self, recordings, window_seconds, stride_seconds, smooth, lag_windows, mean_key_seconds, transition, log_prior,
                          signature_weight, keep_frames, max_chunk_samples, posteriors, source_rate, source_channels, channel, method,
-                         profiles, compression, profile_sharpness, tuning_meter, tuning_min_strength)
+                         profiles, compression, profile_sharpness, tuning_meter, tuning_min_strength, retune_cents)
 
     def _refuse_untrackable(self):
         """What ``track`` and ``training_windows`` cannot slide windows over."""

@@ -12,8 +12,13 @@ the offline resampler's on the whole audio to the bit; everything here then coun
 ring of per-frame chroma, 12 doubles a frame, which ``ake_stream_frame_stats_f32`` fills from every push's new frames and
 ``ake_stream_profile_emissions_f32`` scores the newly complete windows from (host model ``metrics.stream_profile``, ring capacity
 ``metrics.stream_profile_ring_frames``).  ``tuning_meter=True`` carries ``estimate_tuning``'s three sums in the same state and the same
-launch (``metrics.stream_tuning``) and reports the detuning of the audio so far with every update.  Not built: retuning inside a stream
-(a carried retuner), chunk lengths that differ between recordings, a weighting of the bins.
+launch (``metrics.stream_tuning``) and reports the detuning of the audio so far with every update.  ``retune_cents=c`` puts
+``tuning.StreamRetuner`` behind the resampler and in front of the history: the offline varispeed filter with a carried ring of 64 inputs
+(``retune_final`` below; ``ake_stream_retune_f32``, host model ``metrics.stream_retune``), whose output is ``retune``'s on the whole audio
+to the bit.  Everything here then counts retuned samples; only ``StreamUpdate.times`` are divided by ``rho`` again, and the meter reports
+the detuning that is left.  Not built: automatic retuning inside a stream (the number of cents is the caller's: taking it from the
+stream's own meter needs a read-back or a ratio that changes in mid-stream), chunk lengths that differ between recordings, a weighting
+of the bins.
 
 The geometry, as pure host functions (``H`` = ``ake_cqt_plan_half_support``: frame t depends on samples ``[t*hop - H, t*hop + H]``):
 
@@ -36,6 +41,7 @@ import torch
 
 from . import _lib, metrics
 from .audio import StreamResampler
+from .tuning import StreamRetuner
 from .pipeline import track_counts, track_stride_frames, track_window_frames
 
 
@@ -67,6 +73,10 @@ resampled_final = metrics.resampled_final            # (n_in, up, down, half, fi
 resample_first_input = metrics.resample_first_input  # (k, up, down, half) -> the first input output k reads
 resample_tail = metrics.resample_tail                # (n_in, up, down, half) -> inputs still to be held, <= 2*half // up
 
+# a stream opened with retune_cents retunes behind that, in front of its history (ake_stream_retune_f32): the geometry
+retune_final = metrics.retune_final                  # (n_in, rho, finished=False) -> outputs that are final
+retune_tail = metrics.retune_tail                    # (n_in, rho) -> inputs still to be held, <= 63
+
 
 @dataclass
 class StreamUpdate:
@@ -84,7 +94,11 @@ class StreamUpdate:
     On a ``method="profile"`` stream the fields hold what ``KeyTrack`` documents for that method: ``key`` is the window's chroma,
     ``tonic`` the larger of each tonic's two emissions, ``genre`` None, ``confidence`` the winning correlation, and ``emissions`` is
     always there, also with ``smooth=False``.  A stream opened with ``tuning_meter=True`` adds ``tuning_cents`` and ``tuning_strength``,
-    float32 (R,): the detuning estimate over every final frame so far (zeros before the first frame); None otherwise."""
+    float32 (R,): the detuning estimate over every final frame so far (zeros before the first frame); None otherwise.
+
+    A stream opened with ``retune_cents`` carries that number (float32-rounded, as the kernel reads it) in ``retune_cents``; its ``times``
+    are divided by ``rho``, so they are seconds of the recording as it was pushed, not of its retuned copy, and its meter reports the
+    detuning that is left.  None on a stream opened without the keyword."""
     first_window: int
     windows: int
     key: torch.Tensor
@@ -104,6 +118,7 @@ class StreamUpdate:
     log_likelihood: torch.Tensor | None = None
     tuning_cents: torch.Tensor | None = None
     tuning_strength: torch.Tensor | None = None
+    retune_cents: float | None = None
 
     @staticmethod
     def concat(parts):
@@ -114,7 +129,7 @@ class StreamUpdate:
         return StreamUpdate(parts[0].first_window, sum(p.windows for p in parts), cat("key"), cat("tonic"), cat("genre"), cat("key_id"),
                             cat("signature_id"), cat("tonic_id"), cat("confidence"), torch.cat([p.times for p in parts]), cat("emissions"),
                             cat("filtered"), parts[0].smooth_first_window, cat("smooth_key_id"), cat("posteriors"), cat("smooth_confidence"),
-                            cat("log_likelihood"), parts[-1].tuning_cents, parts[-1].tuning_strength)
+                            cat("log_likelihood"), parts[-1].tuning_cents, parts[-1].tuning_strength, parts[0].retune_cents)
 
 
 class KeyStream:
@@ -130,14 +145,17 @@ class KeyStream:
     each).  ``push`` runs on the current stream.
 
     With ``source_rate`` / ``source_channels`` a ``StreamResampler`` stands in front of the history: a push first resamples its chunk
-    (``max_chunk_samples`` source samples at a time) into a buffer sized here, and what that made final goes the way of a mono chunk."""
+    (``max_chunk_samples`` source samples at a time) into a buffer sized here, and what that made final goes the way of a mono chunk.
+    With ``retune_cents`` a ``StreamRetuner`` stands behind it (or alone): what it makes final of a mono piece, in a second buffer sized
+    here, is what the history gets, and ``max_chunk_samples`` counts the samples in front of it."""
 
     resampler = None                                                 # the StreamResampler of a stream with a source format
+    retuner = None                                                   # the StreamRetuner of a stream with retune_cents
 
     def __init__(self, est, recordings, window_seconds=15.0, stride_seconds=5.0, smooth=True, lag_windows=6, mean_key_seconds=60.0,
                  transition=None, log_prior=None, signature_weight=1.0, keep_frames=False, max_chunk_samples=None, posteriors=False,
                  source_rate=None, source_channels=None, channel=0, method="net", profiles="krumhansl", compression="log",
-                 profile_sharpness=10.0, tuning_meter=False, tuning_min_strength=0.0):
+                 profile_sharpness=10.0, tuning_meter=False, tuning_min_strength=0.0, retune_cents=None):
         R = int(recordings)
         if R < 1:
             raise ValueError("stream: recordings must be at least 1")
@@ -191,7 +209,25 @@ class KeyStream:
             self.resampler = StreamResampler(rate_in, est.sample_rate, R, channels, int(channel), dev, src_max)
             max_chunk_samples = max(resampled_final(src_max, up, down, half, True), (half + 1) // down + 2)
             self.resampled = torch.empty((R, max_chunk_samples), dtype=torch.float32, device=dev)
-        self.max_chunk = 10 * est.sample_rate if max_chunk_samples is None else int(max_chunk_samples)
+        # ---- the retuner: behind the resampler, in front of the history; everything from here on counts retuned samples ----
+        self.retuner, self.retune_cents, self.rho = None, None, 1.0
+        if retune_cents is not None:
+            if isinstance(retune_cents, (bool, str, torch.Tensor)) or not abs(float(retune_cents)) <= metrics.RETUNE_MAX_CENTS:
+                raise ValueError(f"stream: retune_cents is one number within +-{metrics.RETUNE_MAX_CENTS:g} cents for all recordings (they "
+                                 f"advance in lockstep), got {retune_cents!r}")
+            self.retune_cents = float(retune_cents)
+        if self.retune_cents:                                        # (None and 0: the stream as it is without a retuner)
+            est._refuse_unretunable("stream(retune_cents=...)")
+            in_max = 10 * est.sample_rate if max_chunk_samples is None else int(max_chunk_samples)      # what a piece hands the retuner at most
+            if in_max < 1:
+                raise ValueError("stream: max_chunk_samples must be at least 1")
+            self.retuner = StreamRetuner(self.retune_cents, R, dev, in_max)
+            self.retune_cents, self.rho = self.retuner.cents, self.retuner.rho
+            # m inputs make at most m*rho + 2 outputs final (each of the two counts lies within one of its real value), finish() at
+            # most Z*rho + 1 more
+            max_chunk_samples = metrics.retune_out_len(in_max) + 2 * metrics.RETUNE_ZEROS
+            self.retuned = torch.empty((R, max_chunk_samples), dtype=torch.float32, device=dev)
+        self.max_chunk =10 * est.sample_rate if max_chunk_samples is None else int(max_chunk_samples)
         if self.max_chunk < 1:
             raise ValueError("stream: max_chunk_samples must be at least 1")
         self.signature_weight = float(signature_weight)
@@ -209,7 +245,8 @@ class KeyStream:
         self.N = self.F = self.W = 0
         self.s0 = 0                                                  # the history's first sample
         self.finished = False
-        self.dtype = None if self.resampler is None else torch.float32       # (what the history is fed: the resampler's output)
+        fed = self.resampler is not None or self.retuner is not None
+        self.dtype = torch.float32 if fed else None                  # (what the history is fed: the resampler's or the retuner's output)
         # the history holds [s0, N): at most 2H + hop samples survive a push (frame F is not final, so N <= F*hop + H, and
         # s0 > F*hop - H - hop), and a piece adds at most max_chunk
         self.hist_cap = (2 * self.H + hop + self.max_chunk + 3) // 4 * 4
@@ -269,20 +306,26 @@ class KeyStream:
         """(R, m) float32 or int16 (16-bit PCM, sample / 32768) at the estimator's rate, any m >= 0 -> ``StreamUpdate``.  A stream
         opened with ``source_rate`` / ``source_channels`` takes (R, C, m) chunks at that rate instead ((R, m) with one channel; int16 with
         any strides, so interleaved storage goes in as ``buf.transpose(1, 2)``): they pass the carried resampler, and what that makes
-        final goes the way of a mono chunk."""
+        final goes the way of a mono chunk.  On a stream opened with ``retune_cents`` the mono audio then passes the carried retuner, which
+        takes float32 and int16 chunks in any order."""
         if self.finished:
             raise ValueError("KeyStream.push: the stream has been finished")
         if self.resampler is not None:
             self._sync_weights()
             chunk = self.resampler._checked(chunk)
             step = self.resampler.max_chunk
-            return StreamUpdate.concat([self._piece(self.resampler._piece(chunk[:, :, a:a + step], False, out=self.resampled), False)
+            return StreamUpdate.concat([self._through(self.resampler._piece(chunk[:, :, a:a + step], False, out=self.resampled))
                                         for a in range(0, max(chunk.shape[2], 1), step)])
         if not isinstance(chunk, torch.Tensor) or chunk.dim() != 2 or chunk.shape[0] != self.R:
             raise ValueError(f"KeyStream.push: a chunk is (R, m) with R = {self.R}: mono audio at the estimator's rate (open the stream "
                              "with source_rate / source_channels for anything else: it then resamples and picks channels with carried state)")
         if chunk.dtype not in (torch.float32, torch.int16):
             raise ValueError("KeyStream.push: a chunk is float32 or int16 (16-bit PCM)")
+        if self.retuner is not None:                                 # (the history is fed float32 whatever arrives)
+            self._sync_weights()
+            chunk = self.retuner._checked(chunk)
+            step = self.retuner.max_chunk
+            return StreamUpdate.concat([self._through(chunk[:, a:a + step]) for a in range(0, max(chunk.shape[1], 1), step)])
         if self.dtype is None:
             self.dtype = chunk.dtype
         elif chunk.dtype != self.dtype:
@@ -295,6 +338,12 @@ class KeyStream:
         if m <= self.max_chunk:
             return self._piece(chunk, False)
         return StreamUpdate.concat([self._piece(chunk[:, a:a + self.max_chunk], False) for a in range(0, m, self.max_chunk)])
+
+    def _through(self, mono):
+        """A mono piece at the estimator's rate -> its update, by way of the retuner where the stream has one."""
+        if self.retuner is not None:
+            mono = self.retuner._piece(mono, False, out=self.retuned)
+        return self._piece(mono, False)
 
     def _sync_weights(self):
         if not self.profile:
@@ -310,6 +359,11 @@ class KeyStream:
         if self.resampler is not None:                               # first what the resampler still held back
             rest = self.resampler._piece(None, True, out=self.resampled)
             self.resampler.finished = True
+            if rest.shape[1]:
+                parts.append(self._through(rest))
+        if self.retuner is not None:                                 # then what the retuner still held back
+            rest = self.retuner._piece(None, True, out=self.retuned)
+            self.retuner.finished = True
             if rest.shape[1]:
                 parts.append(self._piece(rest, False))
         parts.append(self._piece(None, True))
@@ -375,7 +429,9 @@ class KeyStream:
             key, tonic, genre = f32(R, k, 12), f32(R, k, 12), f32(R, k, 11) if not self.profile and self.est.net.genre else None
             key_id, sig, tonic_id, conf = i32(R, k), i32(R, k), i32(R, k), f32(R, k)
             times = (torch.arange(self.W, self.W + k, dtype=torch.float64) * self.sf + (self.wf - 1) / 2) * hop / self.est.sample_rate
-            up = StreamUpdate(self.W, k, key, tonic, genre, key_id, sig, tonic_id, conf, times)
+            if self.retuner is not None:                             # seconds of the recording as it was pushed
+                times = times / self.rho
+            up = StreamUpdate(self.W, k, key, tonic, genre, key_id, sig, tonic_id, conf, times, retune_cents=self.retune_cents)
             if self.meter:
                 up.tuning_cents, up.tuning_strength = self.tuning
             if self.profile:                                         # one launch scores the new windows from the ring

@@ -7,6 +7,8 @@ as they come, so a recording that is 35 cents sharp lands one full bin off.  Hos
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import torch
 
 from . import _lib, metrics
@@ -100,3 +102,99 @@ def retune(audio: torch.Tensor, cents, lengths: torch.Tensor | None = None):
         _lib.check(fn(audio.data_ptr(), B, n, audio.stride(0) if B > 1 else max(n, 1), lengths.data_ptr() if lengths is not None else None,
                       cents.data_ptr(), out.data_ptr(), out.stride(0), len_out.data_ptr(), torch.cuda.current_stream().cuda_stream), name)
     return out, len_out
+
+
+class StreamRetuner:
+    """``retune`` on audio that arrives in chunks: R recordings in lockstep, all retuned by the one ``cents``.
+
+    ``push(chunk)`` takes the next m samples of every recording -- (R, m) float32, or int16 = 16-bit PCM (``pcm16_to_float``); any m >= 0;
+    the format may change from push to push -- and returns the (R, k) float32 outputs that chunk made final; ``finish()`` returns the
+    rest.  Joined, the pieces are ``retune(whole, cents)[0][:, :floor(n * rho)]`` on the joined chunks, bit for bit, however the audio was
+    cut (``ake_stream_retune_f32``; host model ``metrics.stream_retune``).  An output is final once the last of its 64 taps has arrived,
+    so the outputs trail the input by 32 samples.
+
+    ``cents``: one number within +-50 (all recordings share it: recordings with ratios of their own would finish different numbers of
+    samples per push).  ``rho`` is the ratio as the device computes it, read back once, here (``ake_retune_ratio``): the offline kernel's
+    own double, which the host's ``2 ** (cents / 1200)`` may miss by a last place.  With ``cents == 0`` the stream is a copy, as it is
+    offline.  The carried state (64 float32 a recording) is sized here; a push allocates only what it returns, reads nothing back from the
+    device and runs on the current stream.  A chunk longer than ``max_chunk_samples`` (default: no limit) goes in several pieces, joined
+    by one ``torch.cat``."""
+
+    def __init__(self, cents, recordings: int, device=None, max_chunk_samples: int | None = None):
+        if not torch.cuda.is_available():
+            raise _lib.AkeError("the retuner needs a HIP device; there is no CPU fallback (the float64 model is metrics.stream_retune)")
+        self.R = int(recordings)
+        if not 1 <= self.R <= 65535:
+            raise ValueError(f"StreamRetuner: recordings must lie in 1..65535, got {recordings}")
+        if isinstance(cents, torch.Tensor):
+            if cents.numel() != 1:
+                raise ValueError("StreamRetuner: one number of cents for all recordings (they advance in lockstep)")
+            cents = cents.item()
+        if not abs(float(cents)) <= metrics.RETUNE_MAX_CENTS:
+            raise ValueError(f"StreamRetuner: {cents} cents; a detuning lies within +-{metrics.RETUNE_MAX_CENTS:g} cents")
+        self.max_chunk = None if max_chunk_samples is None else int(max_chunk_samples)
+        if self.max_chunk is not None and self.max_chunk < 1:
+            raise ValueError("StreamRetuner: max_chunk_samples must be at least 1")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.cents = C.c_float(float(cents)).value                   # what the kernel is given: float32
+        L = _lib.lib()
+        rho = C.c_double(0.0)
+        with torch.cuda.device(self.device):
+            _lib.check(L.ake_retune_ratio(self.cents, C.byref(rho), torch.cuda.current_stream().cuda_stream), "ake_retune_ratio")
+        self.rho = rho.value
+        self.state = torch.empty(int(L.ake_stream_retune_state_bytes(self.R)), dtype=torch.uint8, device=self.device)
+        self.n = 0                                                   # inputs so far: the device keeps no count
+        self.finished = False
+
+    def out_count(self, n_in: int, finished: bool = False) -> int:
+        """Outputs that are final after ``n_in`` inputs (``metrics.retune_final`` with this stream's ``rho``)."""
+        return int(_lib.lib().ake_stream_retune_out_count(self.cents, self.rho, int(n_in), int(finished)))
+
+    def _checked(self, chunk):
+        if not isinstance(chunk, torch.Tensor) or chunk.dtype not in (torch.float32, torch.int16):
+            raise ValueError("StreamRetuner.push: a chunk is a float32 or int16 (16-bit PCM) tensor")
+        if chunk.dim() != 2 or chunk.shape[0] != self.R:
+            raise ValueError(f"StreamRetuner.push: a chunk is (R, m) with R = {self.R}, got {tuple(chunk.shape)}")
+        chunk = chunk.to(self.device)
+        if chunk.stride(1) != 1 and chunk.shape[1] > 1:
+            chunk = chunk.contiguous()
+        return chunk
+
+    def _piece(self, chunk, finishing, out=None):
+        """One call of the entry point: ``chunk`` (R, m) as ``_checked`` leaves it, or None -> the (R, k) outputs, written to the front
+        of ``out`` (R, >= k) when that is given."""
+        L = _lib.lib()
+        m = 0 if chunk is None else int(chunk.shape[1])
+        k = self.out_count(self.n + m, finishing) - self.out_count(self.n)
+        if out is None:
+            out = torch.empty((self.R, k), dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.shape[0] == self.R and out.shape[1] >= k and (out.stride(1) == 1 or out.shape[1] <= 1)
+        k_out = C.c_int64(-1)
+        fn, name = ((L.ake_stream_retune_pcm16_f32, "ake_stream_retune_pcm16_f32") if m and chunk.dtype == torch.int16
+                    else (L.ake_stream_retune_f32, "ake_stream_retune_f32"))
+        with torch.cuda.device(self.device):
+            _lib.check(fn(chunk.data_ptr() if m else None, self.R, m, (chunk.stride(0) if self.R > 1 else m) if m else 0, self.cents, self.rho,
+                          self.n, int(finishing), self.state.data_ptr(), self.state.numel(), out.data_ptr() if k else None,
+                          max(out.stride(0), k), C.byref(k_out), torch.cuda.current_stream().cuda_stream), name)
+        assert k_out.value == k
+        self.n += m
+        return out[:, :k]
+
+    @torch.no_grad()
+    def push(self, chunk: torch.Tensor) -> torch.Tensor:
+        if self.finished:
+            raise ValueError("StreamRetuner.push: the stream has been finished")
+        chunk = self._checked(chunk)
+        m = chunk.shape[1]
+        if self.max_chunk is None or m <= self.max_chunk:
+            return self._piece(chunk, False)
+        return torch.cat([self._piece(chunk[:, a:a + self.max_chunk], False) for a in range(0, m, self.max_chunk)], dim=1)
+
+    @torch.no_grad()
+    def finish(self) -> torch.Tensor:
+        """The recordings end here: the outputs whose taps reach behind the end, which see zeros there, as the offline ones do."""
+        if self.finished:
+            raise ValueError("StreamRetuner.finish: the stream has been finished")
+        out = self._piece(None, True)
+        self.finished = True
+        return out

@@ -793,6 +793,44 @@ int ake_retune_f32(const float* in_dev, int batch, int64_t n_max, int64_t in_str
 int ake_retune_pcm16_f32(const int16_t* in_dev, int batch, int64_t n_max, int64_t in_stride, const int64_t* lengths_dev,
                          const float* cents_dev, float* out_dev, int64_t out_stride, int64_t* lengths_out_dev, ake_stream_t stream);
 
+/* The retuner on audio that arrives in chunks, all recordings in lockstep (KeyEstimator.stream(retune_cents=...), ake_amd.StreamRetuner;
+ * host model metrics.stream_retune).  Z, the table, beta and the cutoff are ake_retune_f32's.
+ *   ake_retune_ratio(cents, rho_out, stream): rho = 2^(cents / 1200) as retune_kernel itself computes it (NaN as 0, the literal at the
+ *   +-50 clamp), by a one-thread launch of the kernel's own device function and a copy back; it waits for `stream`.  The host's exp2 may
+ *   differ from the device's in the last place, and one ulp of rho moves read positions and counts.  Call it once per stream; every
+ *   other entry here takes `cents` and this rho, and none of them reads anything back.
+ * With inv = 1.0 / rho, output k reads the inputs floor(k inv) - 31 .. floor(k inv) + 32 (zeros outside [0, n)), so it is final once
+ * floor(double(k) * inv) + 32 <= n_in - 1.
+ *   ake_stream_retune_out_count(cents, rho, n_in, flush) (host only; -1 for n_in outside 0..2^40 or a rho outside
+ *   [1 / 1.029302236643492, 1.029302236643492]) = the size of that prefix, found by testing this very double expression around
+ *   floor((n_in - 32) * rho); with flush floor(double(n_in) * rho), the offline count (never above ake_retune_out_len(n_in) - 1); with
+ *   cents == 0 after the clamp, n_in: such a stream is a stateless copy, output k is input k.
+ * A call takes the next m samples of every recording, chunk_dev[rec * rec_stride + i], after the n_before it has been given so far, and
+ * writes the outputs k in [out_count(n_before, 0), out_count(n_before + m, flush)) to out_dev[rec * out_stride + (k - first)]; *k_out (a
+ * host integer, required) is their number; out_dev behind it is not touched.  The outputs equal ake_retune_f32 / ake_retune_pcm16_f32 on
+ * the concatenated audio BIT FOR BIT, however the audio is cut into calls: the kernels share the offline kernel's per-sample code.
+ * ONE RATIO PER CALL: all recordings of a call share cents and rho.  Recordings with ratios of their own would finish different numbers
+ * of samples per push; that needs streams that do not advance in lockstep, which are not built.
+ * state_dev: ake_stream_retune_state_bytes(recordings) = recordings * 256 bytes (0 for recordings outside 1..65535), 16-byte aligned: per
+ * recording a ring of the last 64 inputs as float32 (16-bit samples converted, s / 32768, before they are stored), input i at slot i % 64.
+ * With n_before == 0 it is not read, so a fresh stream needs no initialising launch; cents == 0 never touches it.
+ * Launches: stream_retune_kernel (1024 outputs a workgroup in four tiles of 256, the table and each tile's input staged in LDS; reads
+ * the ring), then stream_retune_tail_kernel (writes the ring from the chunk's end) -- two, so that no workgroup reads what another
+ * writes.  A call with no output skips the first; m == 0, cents == 0 or flush the second; a call with neither launches nothing.  Plain
+ * loads and stores, no atomics.  The first filtering call on a device uploads the filter table, as ake_retune_f32's does.
+ * AKE_ERR_INVALID: a null state_dev or k_out, chunk_dev with m > 0, out_dev with *k_out > 0; recordings outside 1..65535; m or n_before
+ * outside 0..2^40; rec_stride negative; out_stride < *k_out; a rho outside the range above (NaN included); a misaligned state.
+ * AKE_ERR_WORKSPACE: state_bytes below the query.  Nothing is launched after any of them. */
+int ake_retune_ratio(float cents, double* rho_out, ake_stream_t stream);
+int64_t ake_stream_retune_out_count(float cents, double rho, int64_t n_in, int flush);
+size_t ake_stream_retune_state_bytes(int recordings);
+int ake_stream_retune_f32(const float* chunk_dev, int recordings, int64_t m, int64_t rec_stride, float cents, double rho, int64_t n_before,
+                          int flush, void* state_dev, size_t state_bytes, float* out_dev, int64_t out_stride, int64_t* k_out,
+                          ake_stream_t stream);
+int ake_stream_retune_pcm16_f32(const int16_t* chunk_dev, int recordings, int64_t m, int64_t rec_stride, float cents, double rho,
+                                int64_t n_before, int flush, void* state_dev, size_t state_bytes, float* out_dev, int64_t out_stride,
+                                int64_t* k_out, ake_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Key-profile emissions: a key track without a trained net (Krumhansl-Schmuckler).  Not in the reference.  Opt-in: nothing else in this
  * library calls it.  Host model: metrics.profile_emissions.

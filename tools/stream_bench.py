@@ -31,8 +31,13 @@
               launch under the library's kernel timer; and, on synthesised recordings, how many of a profile stream's key labels are those
               of track(method="profile") on the whole audio.  --tuning-meter (also with --method net) opens the streams with the meter.
 
+  --retune-cents C: this section alone.  est.stream(R, retune_cents=C) beside est.stream(R), both fed float32 chunks of 0.1 s and 1 s: three
+              rounds of --pushes pushes each, the two streams taking turns; per push by events on the stream, the median of each round, and
+              over the rounds their median and spread; and the two added launches (stream_retune_kernel, stream_retune_tail_kernel) per
+              launch under the library's kernel timer.
+
 Usage: python tools/stream_bench.py [--pushes 200] [--accuracy] [--posteriors] [--source-rate 48000 --source-channels 2]
-                                    [--method profile] [--tuning-meter]"""
+                                    [--method profile] [--tuning-meter] [--retune-cents 33.3]"""
 import argparse
 import ctypes as C
 import importlib.util
@@ -270,6 +275,39 @@ def method_rows(est, recordings, pushes, method, meter):
     return rows
 
 
+def retune_rows(est, recordings, pushes, cents, rounds=3):
+    """A push of est.stream(R, retune_cents=cents) beside a push of est.stream(R), float32 chunks of 0.1 s and 1 s: `rounds` rounds of
+    `pushes` pushes each, the two streams taking turns in one process; per round the median, and over the rounds the median of those and
+    their spread (largest - smallest).  And the two added launches on their own, under the library's kernel timer."""
+    rows = []
+    for R in recordings:
+        for seconds in (0.1, 1.0):
+            m = int(round(seconds * SR))
+            pieces = [torch.randn((R, m), device=DEV) * 0.3 for _ in range(8)]
+            warm = int(30 / seconds) + 1
+            meds = {"retuned": [], "plain": []}
+            for _ in range(rounds):
+                for kind, kw in (("retuned", dict(retune_cents=cents)), ("plain", {})):
+                    meds[kind].append(statistics.median(timed_pushes(est.stream(R, **kw), pieces, pushes, warm)))
+            s = est.stream(R, retune_cents=cents)
+            for i in range(warm):
+                s.push(pieces[i % 8])
+            torch.cuda.synchronize()
+            _lib.prof_enable("stream_retune", True)
+            for i in range(pushes):
+                s.push(pieces[i % 8])
+            prof = _lib.prof_results()
+            _lib.prof_enable("", False)
+            stat = lambda xs: {"median_of_rounds": round(statistics.median(xs), 4), "spread": round(max(xs) - min(xs), 4),   # noqa: E731
+                               "rounds": [round(x, 4) for x in xs]}
+            rows.append({"recordings": R, "chunk_s": seconds, "retune_cents": cents, "push_ms_retuned": stat(meds["retuned"]),
+                         "push_ms_plain": stat(meds["plain"]),
+                         "added_ms_median": round(statistics.median(meds["retuned"]) - statistics.median(meds["plain"]), 4),
+                         "kernel_us_per_launch": {n: round(1e3 * t / k, 2) for n, (t, k) in prof.items() if k}})
+            del s, pieces
+    return rows
+
+
 def agreement_rows():
     """A profile stream's key labels against track(method="profile") on the whole audio: 24 synthesised modulating recordings of 5 min."""
     from ake_amd import synthetic
@@ -342,6 +380,7 @@ def main():
     ap.add_argument("--source-channels", type=int, default=1)
     ap.add_argument("--method", choices=("net", "profile"), default=None)
     ap.add_argument("--tuning-meter", action="store_true")
+    ap.add_argument("--retune-cents", type=float, default=None)
     args = ap.parse_args()
     torch.manual_seed(0)
     gold = np.load(os.path.join(REPO, "tests", "golden", "pcnet_default.npz"))
@@ -356,6 +395,10 @@ def main():
     if args.source_rate is not None:
         print(json.dumps({"device": torch.cuda.get_device_name(0), "pushes": args.pushes,
                           "source": source_rows(est, args.recordings, args.pushes, args.source_rate, args.source_channels)}))
+        return
+    if args.retune_cents is not None:
+        print(json.dumps({"device": torch.cuda.get_device_name(0), "pushes": args.pushes,
+                          "retune": retune_rows(est, args.recordings, args.pushes, args.retune_cents)}))
         return
     if args.method is not None or args.tuning_meter:
         method = args.method or "net"
