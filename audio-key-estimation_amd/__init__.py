@@ -16,6 +16,7 @@ from .optim import FusedAdam  # noqa: F401
 from .lightning_shim import Trainer  # noqa: F401
 from .pipeline import KeyAnnotations, KeyEstimator, KeyTrack, TrackScore, fit_key_transition  # noqa: F401
 from .keyprofile import fit_key_profiles, profile_emissions  # noqa: F401
+from .keychanges import key_changes  # noqa: F401
 from .synth import synth_partials  # noqa: F401
 from .tuning import StreamRetuner, estimate_tuning, retune, retune_out_len  # noqa: F401
 from .windows import TrackWindows, draw_windows, window_batch  # noqa: F401
@@ -30,4 +31,4 @@ __all__ = ["PitchClassNet", "KeyDataset", "DatasetLoader", "SyntheticSineMixLoad
            "transition_from_labels", "synth_partials", "TrackWindows", "draw_windows", "window_batch", "window_labels", "weighted_general_step",
            "estimate_tuning", "retune", "retune_out_len", "retune_reference",
            "profile_emissions", "fit_key_profiles", "KEY_PROFILES", "key_sequence_loss",
-           "key_stream", "KeyStream", "StreamUpdate", "key_stream_posteriors", "StreamResampler", "StreamRetuner"]
+           "key_stream", "KeyStream", "StreamUpdate", "key_stream_posteriors", "StreamResampler", "StreamRetuner", "key_changes"]

@@ -1408,6 +1408,96 @@ def fit_key_profiles(chroma, key_id, weight=None):
     return torch.stack(out)
 
 
+# ---- key changes to the frame: a change point between two windows' centres (ake_key_changes_f32) ----
+
+KEY_CHANGES_MAX_SPAN = 1024              # kMaxSpan of csrc/changes.hip: stride_frames + 2 * slack_frames at most, on the device
+
+
+def key_frame_scores(logmag, counts=None, profiles="krumhansl", compression="log"):
+    """Every frame's Pearson correlation with the 24 keys' profiles -> (R, T, 24) float64: ``profile_emissions(window_frames=1,
+    stride_frames=1, sharpness=1)``'s emissions, the silence rule included (a silent frame, or one at or behind ``counts[r]``, scores 0
+    for every key).  What ``key_changes`` places its boundaries by."""
+    L = torch.as_tensor(logmag).detach().to(device="cpu", dtype=torch.float64)
+    if L.dim() != 3 or L.shape[1] % TUNING_BINS_PER_SEMITONE != 0:
+        raise ValueError(f"key_changes: logmag must be (R, n_bins, T) with n_bins a multiple of 3, got {tuple(L.shape)}")
+    R, P, T = L.shape
+    n = torch.full((R,), T, dtype=torch.int64) if counts is None else torch.as_tensor(counts).detach().cpu().to(torch.int64).reshape(R).clamp(0, T)
+    live = torch.arange(T)[None, :] < n[:, None]
+    c = _profile_frame_chroma(L, _profile_compression(compression))
+    c = torch.where(live[:, :, None], c, torch.zeros_like(c))
+    return _profile_score(c, live, key_profile_table(profiles), 1.0)[1]
+
+
+def key_changes(logmag, labels, window_frames, stride_frames, counts=None, window_counts=None, slack_frames=None, profiles="krumhansl",
+                compression="log"):
+    """Where the key changes between two windows of a key track, to the frame -> ``(change_frame int32 (R, W-1), gain (R, W-1),
+    contrast (R, W-1), margin (R, W-1))``, the last three float64: the float64 model of ``ake_key_changes_f32`` and its definition.
+
+    ``logmag`` (R, n_bins, T), ``profiles`` and ``compression`` as in ``profile_emissions``; ``counts`` (R,): frames of every
+    recording, ``T_r``, clamped to 0..T (default T).  ``labels`` integer (R, W): a key 0..23 per window of ``window_frames`` frames,
+    ``stride_frames`` apart (``KeyTrack.key_id`` or ``smooth_key_id``; anything else, -1 included, is no key).  ``window_counts`` (R,):
+    windows of every recording, clamped to 0..W and to the ``track_counts(T_r, ...)`` windows its frames hold (the default).
+
+    ``s[r, t, k]`` is frame t's correlation with key k (``key_frame_scores``).  ``m_w = w * stride_frames + window_frames // 2`` is
+    window w's centre frame.  Boundary w, between the windows w and w + 1, exists iff ``w + 1 < window_counts[r]`` and
+    ``a = labels[r, w]``, ``b = labels[r, w + 1]`` are two different keys.  Its span is ``lo = max(m_w - slack, 0)`` ..
+    ``hi = min(m_{w+1} + slack, T_r)``, and never crosses the centre of a window that ends another run: if ``w >= 1`` and
+    ``labels[r, w - 1] != a`` then ``lo = max(lo, m_w)``; if ``w + 2 < window_counts[r]`` and ``labels[r, w + 2] != b`` then
+    ``hi = min(hi, m_{w+1})``.  The spans on either side of a run of one window then share one frame at the most, and those of a run of
+    k windows lie apart when ``(k - 1) * stride_frames >= 2 * slack_frames``: there a recording's change frames never decrease.
+    (With the default slack a run of two windows still has spans that share a stride.)  ``slack_frames`` defaults to ``stride_frames``.
+
+    ``d_i = s[lo + i, a] - s[lo + i, b]``, ``C_0 = 0``, ``C_{i+1} = C_i + d_i`` added in ascending i; ``j*`` is the smallest j in
+    0..hi-lo that attains the maximum of C and ``change_frame = lo + j*``: the frames below it belong to a, the rest to b (the split
+    that maximises the summed score of each side's own key; an objective that is additive over the frames).
+    ``gain = C_{j*} - C_{g - lo}`` with ``g = clamp(m_w + (stride_frames + 1) // 2, lo, hi)``, where the grid puts the boundary: how
+    much the objective gains over it, never negative.  ``contrast = (2 * C_{j*} - C_{hi-lo}) / (hi - lo)``: the mean per-frame
+    advantage of each side's own key, in [-2, 2]; near 0 or below, the labels do not fit the frames.  ``margin`` is ``C_{j*}`` minus the
+    largest other ``C_j`` (for tests: how far the decision is from a tie).  Where there is no boundary: -1 and zeros."""
+    wf, sf = int(window_frames), int(stride_frames)
+    if wf < 1 or sf < 1:
+        raise ValueError("key_changes: window_frames and stride_frames must be >= 1")
+    slack = sf if slack_frames is None else int(slack_frames)
+    if slack < 0:
+        raise ValueError("key_changes: slack_frames must be >= 0")
+    s = key_frame_scores(logmag, counts, profiles, compression)
+    R, T = s.shape[:2]
+    lab = torch.as_tensor(labels).detach().cpu().to(torch.int64)
+    if lab.dim() != 2 or lab.shape[0] != R:
+        raise ValueError(f"key_changes: labels must be (R, W) with R = {R}, got {tuple(lab.shape)}")
+    W = lab.shape[1]
+    n = torch.full((R,), T, dtype=torch.int64) if counts is None else torch.as_tensor(counts).detach().cpu().to(torch.int64).reshape(R).clamp(0, T)
+    fits = profile_window_counts(n, wf, sf)
+    n_win = fits.clamp(max=W) if window_counts is None else \
+        torch.minimum(torch.as_tensor(window_counts).detach().cpu().to(torch.int64).reshape(R).clamp(0, W), fits)
+    B = max(W - 1, 0)
+    frame = torch.full((R, B), -1, dtype=torch.int32)
+    gain, contrast, margin = (torch.zeros((R, B), dtype=torch.float64) for _ in range(3))
+    lab, s = lab.tolist(), s.tolist()
+    for r in range(R):
+        for w in range(min(int(n_win[r]), W) - 1):
+            a, b = lab[r][w], lab[r][w + 1]
+            if not (0 <= a < 24 and 0 <= b < 24) or a == b:
+                continue
+            m0, m1 = w * sf + wf // 2, (w + 1) * sf + wf // 2
+            lo, hi = max(m0 - slack, 0), min(m1 + slack, int(n[r]))
+            if w >= 1 and lab[r][w - 1] != a:
+                lo = max(lo, m0)
+            if w + 2 < int(n_win[r]) and lab[r][w + 2] != b:
+                hi = min(hi, m1)
+            C = [0.0]
+            for t in range(lo, hi):                                                          # ascending i
+                C.append(C[-1] + (s[r][t][a] - s[r][t][b]))
+            best = max(C)
+            j = C.index(best)                                                                # the first maximum
+            g = min(max(m0 + (sf + 1) // 2, lo), hi)
+            frame[r, w] = lo + j
+            gain[r, w] = best - C[g - lo]
+            contrast[r, w] = (2.0 * best - C[-1]) / (hi - lo)
+            margin[r, w] = best - max(C[:j] + C[j + 1:])
+    return frame, gain, contrast, margin
+
+
 # ---- the profile method and the tuning estimate on frames that arrive in pieces (ake_stream_frame_stats_f32 / ake_stream_profile_emissions_f32) ----
 
 def stream_profile_ring_frames(window_frames, max_new_frames):

@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from . import _lib, keyprofile as _keyprofile, metrics, tuning as _tuning
+from . import _lib, keychanges as _keychanges, keyprofile as _keyprofile, metrics, tuning as _tuning
 from .audio import get_resampler, pcm16_rows
 from .cqt import WHOLE_SONG_FRAMES, CQTPlan, get_any_hop_plan, hop_for, hop_for_window
 from .models import PitchClassNet
@@ -150,7 +150,13 @@ class KeyTrack:
     sum-normalised chroma, ``emissions`` (always there) ``sharpness`` times the 24 profile correlations, ``tonic[..., t]`` the larger of
     ``emissions[..., t]`` and ``emissions[..., 12 + t]``, ``genre`` None, ``key_id`` the best-correlated key and ``confidence`` its
     correlation, ``tonic_id = key_id % 12`` and ``sig`` the first ``KEY_SIGNATURE_MAP`` row of the key's scale; a silent window holds -1
-    in the three labels and zeros elsewhere."""
+    in the three labels and zeros elsewhere.
+
+    ``track(refine=True)`` adds where the key changes, to the frame (``metrics.key_changes``): ``change_frame`` int32 (R, W - 1), the
+    frame from which the key of window w + 1 holds, where ``refined_source`` (``"smooth_key_id"`` or ``"key_id"``, the labels that were
+    refined) names two different keys at the windows w and w + 1, else -1; ``change_gain`` and ``change_contrast`` (R, W - 1): what the
+    frames' own scores gain over the grid's placement, and the mean per-frame advantage of each side's own key (near 0 or below: the
+    labels do not fit the frames).  All four are None otherwise.  ``segments``, ``change_points`` and ``boundary_score`` read them."""
     key: torch.Tensor
     tonic: torch.Tensor
     genre: torch.Tensor | None
@@ -173,18 +179,34 @@ class KeyTrack:
     sample_rate: int = 0
     tuning_cents: torch.Tensor | None = None
     tuning_strength: torch.Tensor | None = None
+    change_frame: torch.Tensor | None = None
+    change_gain: torch.Tensor | None = None
+    change_contrast: torch.Tensor | None = None
+    refined_source: str | None = None
 
     def _tensors(self):
-        """Every device tensor of the track; the two of a smooth track, the three of its posteriors and the two of a retuned track only
-        when it has them (a plain track lists what it always did)."""
+        """Every device tensor of the track; the two of a smooth track, the three of its posteriors, the two of a retuned track and
+        the three of a refined one only when it has them (a plain track lists what it always did)."""
         out = (self.key, self.tonic, self.genre, self.key_id, self.sig, self.tonic_id, self.confidence, self.counts)
         if self.emissions is not None or self.smooth_key_id is not None:
             out += (self.emissions, self.smooth_key_id)
             if self.posteriors is not None:
                 out += (self.posteriors, self.smooth_confidence, self.log_likelihood)
-        return out + tuple(t for t in (self.tuning_cents, self.tuning_strength) if t is not None)
+        return out + tuple(t for t in (self.tuning_cents, self.tuning_strength, self.change_frame, self.change_gain, self.change_contrast)
+                           if t is not None)
 
-    def segments(self, recording: int, smoothed: bool | None = None, confidence: bool = False):
+    def _source(self, what, smoothed, refined):
+        """``smoothed`` and ``refined`` of ``segments`` and its kin checked -> ``(labels (R, W), whether to read change_frame)``."""
+        if smoothed and self.smooth_key_id is None:
+            raise ValueError(f"{what}(smoothed=True): this track has no smoothed path; make it with track(..., smooth=True)")
+        smoothed = bool(smoothed) or (smoothed is None and self.smooth_key_id is not None)
+        has = self.change_frame is not None and self.refined_source == ("smooth_key_id" if smoothed else "key_id")
+        if refined and not has:
+            raise ValueError(f"{what}(refined=True): this track has no refined boundaries of its {'smooth_key_id' if smoothed else 'key_id'}; "
+                             "make it with track(..., refine=True), which refines the smoothed path when there is one")
+        return (self.smooth_key_id if smoothed else self.key_id), (has if refined is None else bool(refined))
+
+    def segments(self, recording: int, smoothed: bool | None = None, confidence: bool = False, refined: bool | None = None):
         """Run-length encoding of one recording's key labels on the host -> list of ``(start_s, end_s, key_id, name)``.  A window stands
         for the stride around its centre; the first segment starts at 0 and the last ends with the last window.  ``name`` is
         ``metrics.KEY_NAMES[key_id]`` ("A minor"), or "unknown" where signature and tonic disagree (-1).
@@ -195,14 +217,23 @@ class KeyTrack:
         ``confidence=True``: every tuple gets a fifth item, the mean of ``smooth_confidence`` over the segment's windows: how sure the
         smoother is of the key it names there (``ValueError`` on a track without posteriors).
 
+        ``refined``: with True a key change lies at ``change_frame * hop / sample_rate`` instead of halfway between two window centres
+        (``ValueError`` on a track without ``change_frame``, or whose ``refined_source`` is the other labels); a change to or from
+        "unknown" has no refined frame and stays on the grid.  False: the grid.  None (default): refined when the track has them for the
+        labels being read.  Where the search spans on either side of a short run overlap and the later change was placed before the
+        earlier one (``metrics.key_changes``), the later one is read at the earlier one's frame: the run between them is empty.
+
         On a retuned track (``tuning_cents``) the times are divided by the recording's ``rho``: they are seconds of the recording as it
         was handed in, not of its retuned copy."""
         if confidence and self.smooth_confidence is None:
             raise ValueError("segments(confidence=True): this track has no posteriors; make it with track(..., smooth=True, posteriors=True)")
-        if smoothed and self.smooth_key_id is None:
-            raise ValueError("segments(smoothed=True): this track has no smoothed path; make it with track(..., smooth=True)")
-        source = self.smooth_key_id if (smoothed or (smoothed is None and self.smooth_key_id is not None)) else self.key_id
+        source, refined = self._source("segments", smoothed, refined)
         n = int(self.counts[recording])
+        change = self.change_frame[recording, :max(n - 1, 0)].cpu().tolist() if refined else None
+        latest = -1
+        for w in range(len(change or ())):                           # the spans of a short run may overlap: no segment ends before it starts
+            if change[w] >= 0:
+                latest = change[w] = max(change[w], latest)
         ids = source[recording, :n].cpu().tolist()
         times = self.times[:n].tolist()
         conf = self.smooth_confidence[recording, :n].cpu().tolist() if confidence else None
@@ -214,11 +245,72 @@ class KeyTrack:
                 continue
             start = 0.0 if a == 0 else (times[a] - half_s) / rho
             end = (times[b] + (half_w if b == n - 1 else half_s)) / rho
+            if refined and a > 0 and change[a - 1] >= 0:
+                start = change[a - 1] * self.hop / self.sample_rate / rho
+            if refined and b < n - 1 and change[b] >= 0:
+                end = change[b] * self.hop / self.sample_rate / rho
             seg = (start, end, ids[a], metrics.KEY_NAMES[ids[a]] if ids[a] >= 0 else "unknown")
             out.append(seg + (sum(conf[a:b + 1]) / (b + 1 - a),) if confidence else seg)
             a = b + 1
         return out
 
+    def change_points(self, recording: int):
+        """The refined key changes of one recording on the host -> list of ``(time_s, from_key, to_key, gain, contrast)`` in ascending
+        time: ``change_frame * hop / sample_rate`` (divided by ``rho`` on a retuned track, as in ``segments``), the two keys of
+        ``refined_source`` around it, ``change_gain`` and ``change_contrast``.  ``ValueError`` on a track without ``refine=True``."""
+        if self.change_frame is None:
+            raise ValueError("change_points: this track has no refined boundaries; make it with track(..., refine=True)")
+        n = int(self.counts[recording])
+        ids = getattr(self, self.refined_source)[recording, :n].cpu().tolist()
+        frame, gain, contrast = (t[recording, :max(n - 1, 0)].cpu().tolist() for t in (self.change_frame, self.change_gain, self.change_contrast))
+        rho = 1.0 if self.tuning_cents is None else 2.0 ** (float(self.tuning_cents[recording]) / 1200.0)
+        return [(frame[w] * self.hop / self.sample_rate / rho, ids[w], ids[w + 1], gain[w], contrast[w]) for w in range(n - 1) if frame[w] >= 0]
+
+    def boundary_score(self, annotations: KeyAnnotations, refined: bool | None = None, tolerance_seconds: float = 1.0):
+        """How far the track's key changes lie from the annotated ones -> ``{"count", "median_abs_seconds", "within_tolerance"}``: for
+        every annotated key change (a segment whose key differs from the one before it, both labelled) the distance to the nearest
+        predicted boundary of that recording (infinite where the track never changes); their number, the median distance in seconds
+        and the share within ``tolerance_seconds`` (NaN where there is none).  The labels are the smoothed path when the track has one,
+        else ``key_id``; ``refined`` picks their boundaries as in ``segments``.  Torch ops on the device; the three numbers are read at
+        the end.
+
+        On a retuned track the annotations are moved onto the retuned time axis first (``metrics.scale_boundaries``, as ``score``
+        does), and every distance is divided by the recording's ``rho``: seconds of the recording as it was handed in."""
+        pred, refined = self._source("boundary_score", None, refined)
+        if self.hop <= 0 or self.window_frames <= 0 or self.stride_frames <= 0 or self.sample_rate <= 0:
+            raise ValueError("boundary_score: this track does not know its geometry (hop, window_frames, stride_frames, sample_rate); "
+                             "KeyEstimator.track fills it in")
+        if annotations.sample_rate and annotations.sample_rate != self.sample_rate:
+            raise ValueError(f"boundary_score: the annotations are in samples at {annotations.sample_rate} Hz, the track at {self.sample_rate} Hz")
+        dev = pred.device
+        R, W = pred.shape
+        if annotations.seg_start.shape[0] != R:
+            raise ValueError(f"boundary_score: the track has {R} recordings, the annotations {annotations.seg_start.shape[0]}")
+        start = annotations.seg_start.to(device=dev, dtype=torch.int64)
+        rho = torch.ones((R, 1), dtype=torch.float64, device=dev)
+        if self.tuning_cents is not None:
+            start = metrics.scale_boundaries(start, self.tuning_cents)
+            rho = metrics.tuning_ratio(self.tuning_cents.to(dev)).reshape(R, 1)
+        key = annotations.seg_key.to(device=dev, dtype=torch.int64)
+        S = start.shape[1]
+        count = annotations.seg_count.to(dev).to(torch.int64).reshape(R, 1).clamp(0, S)
+        s_idx = torch.arange(1, S, device=dev)[None, :]
+        wanted = (s_idx < count) & (key[:, 1:] >= 0) & (key[:, :-1] >= 0) & (key[:, 1:] != key[:, :-1])              # (R, S - 1)
+        # the predicted boundaries in samples: the grid's halfway point, or the refined frame where there is one
+        w_idx = torch.arange(max(W - 1, 0), device=dev, dtype=torch.float64)[None, :]
+        at = ((w_idx * self.stride_frames + (self.window_frames - 1) / 2 + self.stride_frames / 2) * self.hop).expand(R, -1)
+        if refined:
+            at = torch.where(self.change_frame >= 0, self.change_frame.to(torch.float64) * self.hop, at)
+        moves = (pred[:, 1:] != pred[:, :-1]) & (torch.arange(1, max(W, 1), device=dev)[None, :] < self.counts.to(dev).reshape(R, 1))
+        at = torch.where(moves, at, torch.full_like(at, float("inf")))
+        dist = (start[:, 1:].to(torch.float64)[:, :, None] - at[:, None, :]).abs()                                  # (R, S - 1, W - 1)
+        nearest = dist.amin(dim=2) if W > 1 else torch.full((R, S - 1), float("inf"), dtype=torch.float64, device=dev)
+        d = (nearest / rho / self.sample_rate)[wanted].sort().values
+        n = int(d.numel())
+        if n == 0:
+            return {"count": 0, "median_abs_seconds": float("nan"), "within_tolerance": float("nan")}
+        return {"count": n, "median_abs_seconds": float((d[(n - 1) // 2] + d[n // 2]) / 2),
+                "within_tolerance": float((d <= float(tolerance_seconds)).to(torch.float64).mean())}
 
     def score(self, annotations: KeyAnnotations, smoothed: bool | None = None) -> TrackScore:
         """Score the track against ``annotations`` on the device (``ake_track_score_i32``, one launch; ``metrics.track_score`` is its
@@ -462,7 +554,7 @@ class KeyEstimator:
               window_seconds: float = 15.0, stride_seconds: float = 5.0, smooth: bool = False, mean_key_seconds: float = 60.0,
               transition: torch.Tensor | None = None, signature_weight: float = 1.0, posteriors: bool = False,
               tuning=None, min_strength: float = 0.0, method: str = "net", profiles="krumhansl", compression: str = "log",
-              profile_sharpness: float = 10.0) -> KeyTrack:
+              profile_sharpness: float = 10.0, refine: bool = False, refine_slack_seconds: float | None = None) -> KeyTrack:
         """The key of long recordings over time: audio (R, n) or (R, C, n) float32 on the GPU -> ``KeyTrack``.  int16 audio is 16-bit
         PCM, as in ``__call__``.
 
@@ -504,12 +596,22 @@ class KeyEstimator:
         Viterbi and forward-backward launches to it.  ``signature_weight`` has no meaning there and must be left at 1.  ``lengths``,
         ``rate``, ``channel``, int16 audio, ``tuning`` and ``streams`` > 1 work as with the net; ``frames=0`` estimators and ``--local``
         nets are refused.  ``profile_sharpness = 10`` and ``compression = "log"`` are unmeasured starting values
-        (``profiles/key_profiles.md``)."""
+        (``profiles/key_profiles.md``).
+
+        ``refine=True`` (both methods) places every key change to the frame: one more launch (``ake_amd.key_changes``;
+        ``metrics.key_changes`` is the definition) on ``smooth_key_id`` with ``smooth=True``, else on ``key_id``, with the call's
+        ``profiles`` and ``compression``, and the change is looked for ``refine_slack_seconds`` (default: the stride) beyond the two
+        windows' centres.  It fills ``KeyTrack.change_frame``, ``change_gain``, ``change_contrast`` and ``refined_source``, which
+        ``KeyTrack.segments``, ``change_points`` and ``boundary_score`` read; nothing else of the track changes with it.  The profile
+        method reads the log-CQT it already holds.  The net method transforms the audio once more for it: the fused track call keeps
+        its own transform inside its workspace and does not expose it.  How far the boundaries then lie from the
+        truth on synthesised recordings is in ``profiles/track_refine.md``."""
         if posteriors and not smooth:
             raise ValueError("track(posteriors=True) needs smooth=True: the posteriors belong to the smoothed track's emissions and transition")
         if method == "profile":
             return self._track_profile(audio, lengths, rate, channel, window_seconds, stride_seconds, smooth, mean_key_seconds, transition,
-                                       signature_weight, posteriors, tuning, min_strength, profiles, compression, profile_sharpness)
+                                       signature_weight, posteriors, tuning, min_strength, profiles, compression, profile_sharpness,
+                                       refine, refine_slack_seconds)
         if method != "net":
             raise ValueError('track: method must be "net" or "profile"')
         self._need_net('KeyEstimator.track(method="net")')
@@ -523,16 +625,47 @@ class KeyEstimator:
         sf = track_stride_frames(stride_seconds, self.frames)
         # (made on the caller's stream, which every side stream waits for before it runs the call)
         smoothing = (self._transition(sf, mean_key_seconds, transition), float(signature_weight), bool(posteriors)) if smooth else None
-        if tuning is None:
+        refining = self._refining(sf, refine_slack_seconds, profiles, compression) if refine else None
+        if tuning is None and refining is None:
             return self._issue(lambda slot, a, l: self._run_track(slot, a, l, wf, sf, smoothing), audio, lengths)
-        cents = self._given_tuning(tuning, audio.shape[0])
+        cents = None if tuning is None else self._given_tuning(tuning, audio.shape[0])
 
         def run(slot, a, l):
-            a, l, used, strength = self._retuned(slot, a, l, cents, min_strength)
+            used = strength = None
+            if tuning is not None:
+                a, l, used, strength = self._retuned(slot, a, l, cents, min_strength)
             track = self._run_track(slot, a, l, wf, sf, smoothing)
             track.tuning_cents, track.tuning_strength = used, strength
+            if refining is not None:                                 # the fused call's transform stays in its workspace: one more
+                mel, frames = self._profile_logmag(slot, a, l)[:2] if track.key_id.shape[1] > 1 else (None, None)
+                self._refine(track, mel, frames, refining)
             return track
         return self._issue(run, audio, lengths)
+
+    def _refining(self, sf, slack_seconds, profiles, compression):
+        """``track(refine=True)``'s arguments checked -> ``(slack_frames, the profile table on the device, compression 0..2)`` (made on
+        the caller's stream, which every side stream waits for)."""
+        slack = sf if slack_seconds is None else int(round(float(slack_seconds) * self.frames))
+        if slack < 0:
+            raise ValueError("track(refine=True): refine_slack_seconds must not be negative")
+        _keychanges.check_span(sf, slack)
+        return slack, _keyprofile.device_profiles(profiles, self.device), metrics._profile_compression(compression)
+
+    def _refine(self, track, mel, frames, refining):
+        """``ake_key_changes_f32`` on the track's labels (the smoothed path when it has one) and the log-CQT ``mel`` (R, P, T) with
+        ``frames`` int32 (R,) or None; ``mel`` None: the track has no pair of windows."""
+        slack, prof, mode = refining
+        track.refined_source = "smooth_key_id" if track.smooth_key_id is not None else "key_id"
+        labels = getattr(track, track.refined_source)
+        if mel is None:
+            R, B = labels.shape[0], max(labels.shape[1] - 1, 0)
+            track.change_frame = torch.empty((R, B), dtype=torch.int32, device=self.device)
+            track.change_gain, track.change_contrast = (torch.empty((R, B), dtype=torch.float32, device=self.device) for _ in range(2))
+            return
+        if self.streams > 1:                                         # (a user's table is a fresh tensor of the caller's stream)
+            prof.record_stream(torch.cuda.current_stream(self.device))
+        track.change_frame, track.change_gain, track.change_contrast = _keychanges._launch(
+            mel, False, frames, labels.contiguous(), track.counts, track.window_frames, track.stride_frames, slack, prof, mode)
 
     def stream(self, recordings: int, window_seconds: float = 15.0, stride_seconds: float = 5.0, smooth: bool = True, lag_windows: int = 6,
                mean_key_seconds: float = 60.0, transition: torch.Tensor | None = None, log_prior: torch.Tensor | None = None,
@@ -821,7 +954,8 @@ class KeyEstimator:
         return audio, lengths
 
     def _track_profile(self, audio, lengths, rate, channel, window_seconds, stride_seconds, smooth, mean_key_seconds, transition,
-                       signature_weight, posteriors, tuning, min_strength, profiles, compression, sharpness):
+                       signature_weight, posteriors, tuning, min_strength, profiles, compression, sharpness, refine=False,
+                       refine_slack_seconds=None):
         self._refuse_unprofilable('track(method="profile")')
         if float(signature_weight) != 1.0:
             raise ValueError('track(method="profile"): signature_weight weighs the net\'s key head, which this method does not run; leave it at 1')
@@ -835,6 +969,7 @@ class KeyEstimator:
         sf = track_stride_frames(stride_seconds, self.frames)
         smoothing = (self._transition(sf, mean_key_seconds, transition), bool(posteriors)) if smooth else None
         cents = None if tuning is None else self._given_tuning(tuning, audio.shape[0])
+        refining = (self._refining(sf, refine_slack_seconds, profiles, compression)[0], prof, mode) if refine else None
 
         def run(slot, a, l):
             used = strength = None
@@ -842,7 +977,7 @@ class KeyEstimator:
                 prof.record_stream(torch.cuda.current_stream(self.device))
             if tuning is not None:
                 a, l, used, strength = self._retuned(slot, a, l, cents, min_strength)
-            track = self._run_profile_track(slot, a, l, wf, sf, smoothing, prof, mode, sharpness)
+            track = self._run_profile_track(slot, a, l, wf, sf, smoothing, prof, mode, sharpness, refining)
             track.tuning_cents, track.tuning_strength = used, strength
             return track
         return self._issue(run, audio, lengths)
@@ -876,7 +1011,7 @@ class KeyEstimator:
             cls._sig_tables[key] = torch.tensor([rows.index(m) for m in metrics.KEY_MAJOR_TONIC], dtype=torch.int32, device=device)
         return cls._sig_tables[key]
 
-    def _run_profile_track(self, slot, audio, lengths, wf, sf, smoothing, prof, mode, sharpness):
+    def _run_profile_track(self, slot, audio, lengths, wf, sf, smoothing, prof, mode, sharpness, refining=None):
         dev = self.device
         R, n = audio.shape
         hop = self.plan.hop_length
@@ -911,6 +1046,8 @@ class KeyEstimator:
             else:
                 with torch.cuda.device(dev):
                     self._smooth(track, smoothing[0], smoothing[1], ws, torch.cuda.current_stream().cuda_stream)
+        if refining is not None:                                     # on the log-CQT this track was made from
+            self._refine(track, mel if W > 1 else None, frames if W > 1 else None, refining)
         return track
 
     @torch.no_grad()

@@ -910,6 +910,35 @@ int ake_stream_profile_emissions_f32(const void* state_dev, size_t state_bytes, 
                                      int32_t* signature_id_out, ake_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Key changes to the frame (csrc/changes.hip): where, between the centres of two windows of a key track that carry different keys,
+ * the key changes.  Not in the reference.  Opt-in: nothing else in this library calls it.  Host model: metrics.key_changes.
+ * ---------------------------------------------------------------------------------------- */
+/* mel_dev, frames_major, pitches, frames, profiles_dev and compression as in ake_profile_emissions_f32; frame_counts_dev (nullable)
+ * gives every recording's frames T_r, clamped to 0..frames.  labels_dev is int32 [recordings][windows], a key 0..23 per window of
+ * window_frames frames, stride_frames apart (anything else is no key); window_counts_dev (nullable) the windows of every recording,
+ * clamped to 0..windows and to the (T_r - window_frames) / stride_frames + 1 windows that T_r frames hold.
+ * s[t][k] is frame t's Pearson correlation with key k's profile: ake_profile_emissions_f32's with window_frames = stride_frames =
+ * sharpness = 1, in double and unfused, the silence rule included (a silent frame scores 0 for every key).
+ * With m_w = w * stride_frames + window_frames / 2, boundary w (between the windows w and w + 1) exists iff w + 1 < the recording's
+ * window count and a = labels[w], b = labels[w + 1] are two different keys.  Its span is lo = max(m_w - slack_frames, 0) ..
+ * hi = min(m_{w+1} + slack_frames, T_r), with lo = max(lo, m_w) if w >= 1 and labels[w - 1] != a, and hi = min(hi, m_{w+1}) if
+ * w + 2 < the window count and labels[w + 2] != b: the spans on either side of a run of one window share one frame at the most (those
+ * of a run of k windows lie apart when (k - 1) * stride_frames >= 2 * slack_frames), and there the change frames never decrease.
+ *   d_i = s[lo + i][a] - s[lo + i][b],  C_0 = 0,  C_{i+1} = C_i + d_i in ascending i,  j* = the smallest j in 0..hi-lo with C_j maximal
+ *   change_frame_out [recordings][windows - 1] = lo + j*: the frames below it belong to a, the rest to b
+ *   gain_out         [recordings][windows - 1] = C_{j*} - C_{g - lo}, g = clamp(m_w + (stride_frames + 1) / 2, lo, hi), the grid's place
+ *   contrast_out     [recordings][windows - 1] = (2 C_{j*} - C_{hi-lo}) / (hi - lo), the mean advantage of each side's own key, in -2..2
+ * Where there is no boundary: -1, 0, 0.  Every output element is written by every call; two runs give the same bits.
+ * One launch, key_changes_kernel, a workgroup per (boundary, recording), no workspace; the C_j are added by one thread, in order.
+ * windows < 2: AKE_OK, nothing launched.  AKE_ERR_INVALID: null arguments (the two counts excepted), recordings outside 1..65535,
+ * pitches, frames < 1, windows < 0, compression outside 0..2, window_frames < 1, stride_frames < 1, slack_frames < 0.
+ * AKE_ERR_UNSUPPORTED: pitches % 3 != 0; stride_frames + 2 * slack_frames > 1024, the longest span the kernel holds. */
+int ake_key_changes_f32(const float* mel_dev, int frames_major, int recordings, int pitches, int frames, const int32_t* frame_counts_dev,
+                        const int32_t* labels_dev, int windows, const int32_t* window_counts_dev, int window_frames, int stride_frames,
+                        int slack_frames, const float* profiles_dev /* [2][12] */, int compression, int32_t* change_frame_out,
+                        float* gain_out, float* contrast_out, ake_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel timing with hipEvents recorded on the launch stream (bench.py roofline leg).
  * ---------------------------------------------------------------------------------------- */
 int ake_prof_enable(const char* name_filter /* substring, NULL or "" = all */, int on);
