@@ -5,19 +5,18 @@
 // add the 12 pitch-class sums of 64 frames with profile.h's prof_class_sum (the bits of the offline and the streamed chroma), then a
 // thread per frame forms that frame's Pearson correlation with the two keys in question, in double and unfused, and leaves their
 // difference d_i in the LDS.  One thread then adds C_{i+1} = C_i + d_i in ascending i and keeps the first maximum: the definition fixes
-// that order, and the span has at most kMaxSpan frames.  No atomics, no workspace: two runs give the same bits.
+// that order, and the span has at most kMaxSpan frames.  No atomics, no workspace: two runs give the same bits.  The span, the
+// per-frame arithmetic and the scan are changes.h's, which the streamed kernel (stream_changes.hip) calls too.
 #include "common.h"
-#include "profile.h"
+#include "changes.h"
 
 #include <cmath>
 
 namespace {
 
-using namespace ake_profile;
+using namespace ake_changes;
 
-constexpr int kMaxSpan = 1024;       // stride_frames + 2 * slack_frames at most: the d_i of one span, 8 KB of the LDS
 constexpr int kChgTile = 64;         // frames scored at a time
-constexpr int kChgThreads = 256;
 
 struct KeyChangesArgs {
     const float* mel;           // [recordings][pitches][frames], or [recordings][frames][pitches] (frames_major)
@@ -40,7 +39,7 @@ __device__ __forceinline__ int chg_count(const int* counts, int rec, int limit) 
 struct KeyChangesLds {
     double d[kMaxSpan];
     double x[kProfClasses][kChgTile];
-    double e[2][kProfClasses], see[2];
+    ChgProfileLds prof;
 };
 
 template <bool kFramesMajor>
@@ -54,32 +53,13 @@ __global__ __launch_bounds__(kChgThreads) void key_changes_kernel(KeyChangesArgs
     int n_win = chg_count(a.window_counts, rec, a.windows);
     n_win = n_win < fits ? n_win : fits;
     const int* lab = a.labels + static_cast<long long>(rec) * a.windows;
-    const int ka = w + 1 < n_win ? lab[w] : -1, kb = w + 1 < n_win ? lab[w + 1] : -1;
-    if (ka < 0 || kb < 0 || ka >= kProfKeys || kb >= kProfKeys || ka == kb) {          // no boundary here (the same for every thread)
-        if (tid == 0) { a.change_frame[cell] = -1; a.gain[cell] = 0.f; a.contrast[cell] = 0.f; }
+    ChgSpan span;
+    if (w + 1 >= n_win || !chg_span(span, w, n_win, T, a.window_frames, a.stride_frames, a.slack_frames, [&](int v) { return lab[v]; })) {
+        if (tid == 0) { a.change_frame[cell] = -1; a.gain[cell] = 0.f; a.contrast[cell] = 0.f; }      // no boundary here (the same for every thread)
         return;
     }
-    // the span: the slack on either side of the two centres, clipped where the neighbouring window ends another run.  Window w + 1
-    // lies inside the recording's frames, so m1 < T and lo < hi <= T.
-    const int m0 = w * a.stride_frames + a.window_frames / 2, m1 = m0 + a.stride_frames;
-    int lo = m0 - a.slack_frames > 0 ? m0 - a.slack_frames : 0;
-    int hi = m1 + a.slack_frames < T ? m1 + a.slack_frames : T;
-    if (w >= 1 && lab[w - 1] != ka && lo < m0) lo = m0;
-    if (w + 2 < n_win && lab[w + 2] != kb && hi > m1) hi = m1;
-    const int n = hi - lo;                                            // 1 .. stride_frames + 2 * slack_frames <= kMaxSpan
-
-    if (tid < 2) {                                                    // the two profile rows' statistics, once per block
-        double sum = 0.0;
-        for (int i = 0; i < kProfClasses; ++i) sum += static_cast<double>(a.profiles[tid * kProfClasses + i]);
-        const double mean = sum / 12.0;
-        double ss = 0.0;
-        for (int i = 0; i < kProfClasses; ++i) {
-            const double v = static_cast<double>(a.profiles[tid * kProfClasses + i]) - mean;
-            lds.e[tid][i] = v;
-            ss += v * v;
-        }
-        lds.see[tid] = ss;
-    }
+    const int lo = span.lo, n = span.hi - span.lo;                    // 1 .. stride_frames + 2 * slack_frames <= kMaxSpan
+    if (tid < 2) chg_profile_stats(lds.prof, a.profiles, tid);        // the two profile rows' statistics, once per block
     const float* mel = a.mel + static_cast<long long>(rec) * a.pitches * a.frames;
     for (int t0 = 0; t0 < n; t0 += kChgTile) {
         // pitch-major: lanes run along the frames, which are contiguous; frames-major: along the pitch classes (profile_chroma_kernel)
@@ -93,43 +73,15 @@ __global__ __launch_bounds__(kChgThreads) void key_changes_kernel(KeyChangesArgs
                 });
         }
         __syncthreads();                                              // (the first one also publishes e and see)
-        if (tid < kChgTile && t0 + tid < n) {                         // one frame's scores of the two keys: prof_score_block's arithmetic
-            double x[kProfClasses], sum = 0.0;
-            for (int j = 0; j < kProfClasses; ++j) { x[j] = lds.x[j][tid]; sum += x[j]; }
-            const double mean = sum / 12.0;
-            double sxx = 0.0;
-            for (int j = 0; j < kProfClasses; ++j) { x[j] = x[j] - mean; sxx += x[j] * x[j]; }
-            double diff = 0.0;
-            if (!(sxx <= kProfSilence * 12.0 * mean * mean)) {        // a silent frame scores 0 for every key
-                double r[2];
-                for (int side = 0; side < 2; ++side) {
-                    const int key = side == 0 ? ka : kb, mode = key / kProfClasses, tonic = key % kProfClasses;
-                    double num = 0.0;
-                    for (int j = 0; j < kProfClasses; ++j) num += x[j] * lds.e[mode][(j - tonic + kProfClasses) % kProfClasses];
-                    const double den = sqrt(sxx * lds.see[mode]);
-                    r[side] = den > 0.0 ? num / den : 0.0;
-                }
-                diff = r[0] - r[1];
-            }
-            lds.d[t0 + tid] = diff;
+        if (tid < kChgTile && t0 + tid < n) {                         // one frame's scores of the two keys
+            double x[kProfClasses];
+#pragma unroll
+            for (int j = 0; j < kProfClasses; ++j) x[j] = lds.x[j][tid];
+            lds.d[t0 + tid] = chg_frame_diff(x, span.ka, span.kb, lds.prof);
         }
         __syncthreads();
     }
-    if (tid == 0) {
-        // g: where the grid puts this boundary (KeyTrack.segments without refinement), inside the span
-        int g = m0 + (a.stride_frames + 1) / 2;
-        g = g < lo ? lo : (g > hi ? hi : g);
-        double c = 0.0, best = 0.0, at_g = 0.0;
-        int j_best = 0;
-        for (int i = 0; i < n; ++i) {                                 // ascending i; the first maximum
-            c += lds.d[i];
-            if (c > best) { best = c; j_best = i + 1; }
-            if (i + 1 == g - lo) at_g = c;
-        }
-        a.change_frame[cell] = lo + j_best;
-        a.gain[cell] = static_cast<float>(best - at_g);
-        a.contrast[cell] = static_cast<float>((2.0 * best - c) / static_cast<double>(n));
-    }
+    if (tid == 0) chg_scan(lds.d, span, a.stride_frames, &a.change_frame[cell], &a.gain[cell], &a.contrast[cell]);
 }
 
 }  // namespace

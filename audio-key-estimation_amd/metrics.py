@@ -1428,6 +1428,33 @@ def key_frame_scores(logmag, counts=None, profiles="krumhansl", compression="log
     return _profile_score(c, live, key_profile_table(profiles), 1.0)[1]
 
 
+def _key_change_span(lab, w, n_win, T, wf, sf, slack):
+    """Boundary w of one recording (``lab``: its labels, ``n_win`` windows, ``T`` frames; ``w + 1 < n_win``) -> ``(a, b, m_w, lo, hi)``,
+    or None where the two windows do not carry two different keys: ``key_changes``' span."""
+    a, b = lab[w], lab[w + 1]
+    if not (0 <= a < 24 and 0 <= b < 24) or a == b:
+        return None
+    m0, m1 = w * sf + wf // 2, (w + 1) * sf + wf // 2
+    lo, hi = max(m0 - slack, 0), min(m1 + slack, T)
+    if w >= 1 and lab[w - 1] != a:
+        lo = max(lo, m0)
+    if w + 2 < n_win and lab[w + 2] != b:
+        hi = min(hi, m1)
+    return a, b, m0, lo, hi
+
+
+def _key_change_scan(d, m0, lo, hi, sf):
+    """The span's differences ``d`` (a list of hi - lo floats) -> ``(change_frame, gain, contrast, margin)``: ``key_changes``' sum in
+    ascending i and its first maximum."""
+    C = [0.0]
+    for x in d:                                                                              # ascending i
+        C.append(C[-1] + x)
+    best = max(C)
+    j = C.index(best)                                                                        # the first maximum
+    g = min(max(m0 + (sf + 1) // 2, lo), hi)
+    return lo + j, best - C[g - lo], (2.0 * best - C[-1]) / (hi - lo), best - max(C[:j] + C[j + 1:])
+
+
 def key_changes(logmag, labels, window_frames, stride_frames, counts=None, window_counts=None, slack_frames=None, profiles="krumhansl",
                 compression="log"):
     """Where the key changes between two windows of a key track, to the frame -> ``(change_frame int32 (R, W-1), gain (R, W-1),
@@ -1476,25 +1503,11 @@ def key_changes(logmag, labels, window_frames, stride_frames, counts=None, windo
     lab, s = lab.tolist(), s.tolist()
     for r in range(R):
         for w in range(min(int(n_win[r]), W) - 1):
-            a, b = lab[r][w], lab[r][w + 1]
-            if not (0 <= a < 24 and 0 <= b < 24) or a == b:
+            span = _key_change_span(lab[r], w, int(n_win[r]), int(n[r]), wf, sf, slack)
+            if span is None:
                 continue
-            m0, m1 = w * sf + wf // 2, (w + 1) * sf + wf // 2
-            lo, hi = max(m0 - slack, 0), min(m1 + slack, int(n[r]))
-            if w >= 1 and lab[r][w - 1] != a:
-                lo = max(lo, m0)
-            if w + 2 < int(n_win[r]) and lab[r][w + 2] != b:
-                hi = min(hi, m1)
-            C = [0.0]
-            for t in range(lo, hi):                                                          # ascending i
-                C.append(C[-1] + (s[r][t][a] - s[r][t][b]))
-            best = max(C)
-            j = C.index(best)                                                                # the first maximum
-            g = min(max(m0 + (sf + 1) // 2, lo), hi)
-            frame[r, w] = lo + j
-            gain[r, w] = best - C[g - lo]
-            contrast[r, w] = (2.0 * best - C[-1]) / (hi - lo)
-            margin[r, w] = best - max(C[:j] + C[j + 1:])
+            a, b, m0, lo, hi = span
+            frame[r, w], gain[r, w], contrast[r, w], margin[r, w] = _key_change_scan([s[r][t][a] - s[r][t][b] for t in range(lo, hi)], m0, lo, hi, sf)
     return frame, gain, contrast, margin
 
 
@@ -1611,3 +1624,153 @@ def stream_tuning(pieces, min_strength=0.0, state=None, return_state=False):
     if return_state:
         outs.append(sums if sums is not None else torch.zeros((0, 3), dtype=torch.float64))
     return outs
+
+
+# ---- key changes to the frame on frames and labels that arrive in pieces (ake_stream_key_changes_f32) ----
+
+def stream_changes_ready(labels, frames, window_frames, stride_frames, slack_frames, finishing=False):
+    """``B``: how many boundaries of a stream are final once ``labels`` = L windows have their label (``key_id`` without the smoother,
+    ``smooth_key_id`` with it, which trails the windows by the lag until the flush) and ``frames`` = F frames are final.
+
+    Boundary w lies between the windows w and w + 1.  By ``key_changes`` it depends on ``labels[w-1 .. w+2]``, on the frames
+    ``lo .. hi - 1`` with ``hi <= m_{w+1} + slack`` (``m_w = w * stride_frames + window_frames // 2``), and at the recording's end on
+    ``T_r`` and the window count.  It is final iff ``w + 2 < L`` and ``F >= m_{w+1} + slack_frames`` -- nothing that arrives later can
+    then change what ``key_changes`` reads for it -- or the stream is ``finishing`` and ``w + 1 < L``: then ``T_r = F`` and the window
+    count is L, as offline.  Both conditions hold for a prefix of the boundaries, so B is a count, monotone in L, F and ``finishing``; a
+    push emits the boundaries ``B_before .. B - 1``, each once and for good."""
+    L, F, wf, sf, slack = int(labels), int(frames), int(window_frames), int(stride_frames), int(slack_frames)
+    if L < 0 or F < 0 or wf < 1 or sf < 1 or slack < 0:
+        raise ValueError("stream_changes_ready: labels, frames and slack_frames must be >= 0, window_frames and stride_frames >= 1")
+    if finishing:
+        return max(L - 1, 0)
+    # F >= (w + 1) * sf + wf // 2 + slack  <=>  w + 1 <= (F - wf // 2 - slack) // sf
+    by_frames = (F - wf // 2 - slack) // sf if F >= wf // 2 + slack else 0
+    return max(min(L - 2, by_frames), 0)
+
+
+def stream_changes_ring_frames(window_frames, stride_frames, slack_frames, lag_windows, max_new_frames):
+    """Rows a stream's chroma ring needs for ``stream_key_changes`` when no piece brings more than ``max_new_frames`` frames and the
+    labels trail the windows by ``lag_windows`` (0 without the smoother):
+    ``max_new_frames + max(sf + 2 * slack, wf - wf // 2 + (lag + 2) * sf + slack) - 1``, at least 1.
+
+    With ``F_old`` frames, ``W_old = track_counts(F_old)`` windows and ``L_old >= W_old - lag`` labels before a piece,
+    ``B = stream_changes_ready(L_old, F_old)`` is the oldest boundary the piece can make final, and its span begins at
+    ``max(m_B - slack, 0)``; after the piece's frames are written the ring must still hold that frame, so it needs
+    ``F - max(m_B - slack, 0)`` rows with ``F <= F_old + max_new_frames``.  Boundary B was not final, for one of two reasons.  Its frames
+    had not arrived: ``F_old <= m_{B+1} + slack - 1 = m_B + sf + slack - 1``, so ``F - (m_B - slack) <= max_new_frames + sf + 2 * slack - 1``.
+    Or its labels had not: ``B >= L_old - 2 >= W_old - lag - 2``, and window ``W_old`` was not complete, ``W_old * sf + wf >= F_old + 1``,
+    so ``m_B >= F_old + 1 - wf - (lag + 2) * sf + wf // 2`` and ``F - (m_B - slack) <= max_new_frames + wf - wf // 2 + (lag + 2) * sf +
+    slack - 1``.  Either bound is attained, so the rule is tight."""
+    wf, sf, slack, lag, m = int(window_frames), int(stride_frames), int(slack_frames), int(lag_windows), int(max_new_frames)
+    if wf < 1 or sf < 1 or slack < 0 or lag < 0 or m < 0:
+        raise ValueError("stream_changes_ring_frames: window_frames and stride_frames must be >= 1, slack_frames, lag_windows and max_new_frames >= 0")
+    return max(m + max(sf + 2 * slack, wf - wf // 2 + (lag + 2) * sf + slack) - 1, 1)
+
+
+def stream_changes_labels_carried(window_frames, stride_frames, slack_frames):
+    """How many decided labels a stream must carry between pieces for ``stream_key_changes`` at the most: those from window ``B - 1`` on,
+    with ``B = stream_changes_ready(L, F)`` the first boundary that is not final, ``L - B + 1`` of them:
+    ``3 + max(0, (slack - 1 - (wf - wf // 2)) // sf)``.
+
+    Either B waits for a label, ``B >= L - 2``: 3 labels.  Or it waits for its frames, ``F <= m_{B+1} + slack - 1``; the L windows lie
+    inside the F frames, ``(L - 1) * sf + wf <= F``, so ``(L - B - 2) * sf <= slack - 1 - (wf - wf // 2)``.  A label ring of that many
+    slots and a piece's new labels (``ake_stream_key_changes_f32``'s ``label_ring``) keeps the slots a piece reads apart from the ones
+    it writes."""
+    wf, sf, slack = int(window_frames), int(stride_frames), int(slack_frames)
+    if wf < 1 or sf < 1 or slack < 0:
+        raise ValueError("stream_changes_labels_carried: window_frames and stride_frames must be >= 1 and slack_frames >= 0")
+    return 3 + max(0, (slack - 1 - (wf - wf // 2)) // sf)
+
+
+def stream_key_changes(pieces, window_frames, stride_frames, slack_frames=None, profiles="krumhansl", compression="log", ring_frames=None,
+                       state=None, return_state=False):
+    """Float64 model of ``ake_stream_frame_stats_f32``'s chroma part followed by ``ake_stream_key_changes_f32``: ``pieces`` is a sequence
+    of ``(frames, labels, finishing)`` -- the next (R, n_bins, m) log-CQT frames of R recordings in lockstep, the next (R, k) integer
+    labels of their windows (the windows ``L .. L + k - 1``, any k >= 0 whose windows lie inside the frames so far) and whether the
+    recordings end with this piece -> a list with one ``(first_boundary, change_frame int32 (R, b), gain (R, b), contrast (R, b))`` per
+    piece, the last two float64: the b boundaries that piece made final (``stream_changes_ready``).  Joined over the pieces they are
+    ``key_changes`` on the joined frames and labels, with ``counts`` = the frames and ``window_counts`` = the labels at the end, to the
+    bit: the same additions in the same order.
+
+    Between pieces the model keeps what the kernels keep: the ring of per-frame chroma of ``stream_profile`` (``ring_frames`` rows,
+    default: every frame of all pieces; a boundary whose first frame has been overwritten is a ``ValueError``), the labels from window
+    ``B - 1`` on, and the host's integers: the frames F, the labels L and the boundaries B so far.  ``slack_frames`` defaults to
+    ``stride_frames``.  ``state`` / ``return_state``: continue from, and return as a last list element, the carried state
+    (``{"ring", "labels", "frames", "windows", "boundaries"}``, ``labels`` a list per recording that begins at window
+    ``max(boundaries - 1, 0)``)."""
+    wf, sf = int(window_frames), int(stride_frames)
+    if wf < 1 or sf < 1:
+        raise ValueError("stream_key_changes: window_frames and stride_frames must be >= 1")
+    slack = sf if slack_frames is None else int(slack_frames)
+    if slack < 0:
+        raise ValueError("stream_key_changes: slack_frames must be >= 0")
+    mode = _profile_compression(compression)
+    prof = key_profile_table(profiles)
+    pieces = [(torch.as_tensor(p).detach().to(device="cpu", dtype=torch.float64), torch.as_tensor(l).detach().cpu().to(torch.int64), bool(f))
+              for p, l, f in pieces]
+    for p, l, _ in pieces:
+        if p.dim() != 3 or p.shape[1] % TUNING_BINS_PER_SEMITONE != 0 or p.shape[:2] != pieces[0][0].shape[:2] or l.dim() != 2 or l.shape[0] != p.shape[0]:
+            raise ValueError(f"stream_key_changes: a piece is (R, n_bins, m) frames with n_bins a multiple of 3 and (R, k) labels, got "
+                             f"{tuple(p.shape)} and {tuple(l.shape)}")
+    if state is None:
+        ring, carried, F, L, B = None, None, 0, 0, 0
+        if ring_frames is None:
+            ring_frames = max(sum(p.shape[2] for p, _, _ in pieces), 1)
+    else:
+        ring, carried, F, L, B = state["ring"].clone(), [list(row) for row in state["labels"]], int(state["frames"]), int(state["windows"]), int(state["boundaries"])
+        ring_frames = ring.shape[1] if ring_frames is None else ring_frames
+        if ring.shape[1] != ring_frames:
+            raise ValueError("stream_key_changes: the state's ring has another length")
+    ring_frames = int(ring_frames)
+    outs = []
+    for p, l, finishing in pieces:
+        R, m, k = p.shape[0], p.shape[2], l.shape[1]
+        if ring is None:
+            ring, carried = torch.zeros((R, ring_frames, 12), dtype=torch.float64), [[] for _ in range(R)]
+        c = _profile_frame_chroma(p, mode) if m else None
+        for i in range(max(m - ring_frames, 0), m):
+            ring[:, (F + i) % ring_frames, :] = c[:, i, :]
+        F += m
+        first_label = L - len(carried[0])                                                    # the window carried[r][0] belongs to
+        for r in range(R):
+            carried[r] += l[r].tolist()
+        L += k
+        if L > 0 and (L - 1) * sf + wf > F:
+            raise ValueError(f"stream_key_changes: window {L - 1} ends at frame {(L - 1) * sf + wf}, and the stream has {F}")
+        B_new = stream_changes_ready(L, F, wf, sf, slack, finishing)
+        b = B_new - B
+        frame = torch.full((R, b), -1, dtype=torch.int32)
+        gain, contrast = torch.zeros((R, b), dtype=torch.float64), torch.zeros((R, b), dtype=torch.float64)
+        if b > 0 and max(B * sf + wf // 2 - slack, 0) < F - ring_frames:
+            raise ValueError(f"stream_key_changes: boundary {B} reads from frame {max(B * sf + wf // 2 - slack, 0)} on, and the ring of "
+                             f"{ring_frames} holds {F - ring_frames} on")
+        for r in range(R):
+            lab = _OffsetList(carried[r], first_label)
+            for w in range(B, B_new):
+                span = _key_change_span(lab, w, L, F, wf, sf, slack)
+                if span is None:
+                    continue
+                ka, kb, m0, lo, hi = span
+                rows = ring[r:r + 1, torch.arange(lo, hi) % ring_frames, :]                  # (1, hi - lo, 12)
+                s = _profile_score(rows, torch.ones((1, hi - lo), dtype=torch.bool), prof, 1.0)[1][0]
+                d = (s[:, ka] - s[:, kb]).tolist()
+                frame[r, w - B], gain[r, w - B], contrast[r, w - B], _ = _key_change_scan(d, m0, lo, hi, sf)
+        outs.append((B, frame, gain, contrast))
+        B = B_new
+        keep_from = max(B - 1, 0)
+        carried = [row[keep_from - first_label:] for row in carried]
+    if return_state:
+        outs.append({"ring": ring, "labels": carried, "frames": F, "windows": L, "boundaries": B})
+    return outs
+
+
+class _OffsetList:
+    """``lab[v]`` of a list that begins at window ``first``."""
+
+    def __init__(self, items, first):
+        self.items, self.first = items, first
+
+    def __getitem__(self, v):
+        if v < self.first:
+            raise IndexError(f"the label of window {v} is no longer carried (from {self.first} on)")
+        return self.items[v - self.first]

@@ -672,7 +672,8 @@ class KeyEstimator:
                signature_weight: float = 1.0, keep_frames: bool = False, max_chunk_samples: int | None = None, rate: int | None = None,
                tuning=None, posteriors: bool = False, source_rate: int | None = None, source_channels: int | None = None, channel: int = 0,
                method: str = "net", profiles="krumhansl", compression: str = "log", profile_sharpness: float = 10.0,
-               tuning_meter: bool = False, tuning_min_strength: float = 0.0, retune_cents: float | None = None):
+               tuning_meter: bool = False, tuning_min_strength: float = 0.0, retune_cents: float | None = None, refine: bool = False,
+               refine_slack_seconds: float | None = None):
         """Track keys on audio as it arrives -> ``ake_amd.KeyStream``: ``push(chunk)`` takes the next (R, m) samples of all
         ``recordings`` = R recordings at once (float32, or int16 = 16-bit PCM; any m >= 0, the same m for every recording) and returns
         a ``StreamUpdate`` with the windows that chunk completed; ``finish()`` ends the recordings and returns the rest.
@@ -737,7 +738,21 @@ class KeyEstimator:
         ``None`` and ``0`` leave the stream as it is without the keyword: the same launches, the same bits.  The number is the caller's:
         a stream does not retune itself from its meter, which would take a read-back or a ratio that changes in mid-stream.
 
-        Refused with a ``ValueError``: ``posteriors=True`` with ``smooth=False``; what ``track`` refuses (``frames=0``, ``wrap_mode="true_end"``, ``--local`` nets), with
+        ``refine=True`` (both methods) places every key change to the frame as ``track(refine=True)`` does, inside the stream: every update
+        carries the boundaries it made final -- boundary w, between the windows w and w + 1, once the label of window w + 2 is decided
+        (``smooth_key_id`` with ``smooth=True``, so ``lag_windows`` later, else ``key_id``) and frame ``m_{w+1} + slack`` is final, and at
+        ``finish()`` the rest (``metrics.stream_changes_ready``) -- in ``StreamUpdate.change_first_boundary``, ``change_frame`` (frames of
+        the stream), ``change_gain``, ``change_contrast`` and ``change_times`` (seconds of the recording as pushed).  One more launch per
+        push that brings labels (``ake_stream_key_changes_f32``; host model ``metrics.stream_key_changes``) reads the per-frame chroma
+        ring of the profile method, 96 bytes a frame, never the transform; a ``"net"`` stream keeps that ring for it (the chroma part of
+        ``ake_stream_frame_stats_f32``, one more launch per piece that has new frames, shared with the meter).  ``profiles`` and
+        ``compression`` apply as for ``method="profile"``, ``refine_slack_seconds`` (default: the stride) as on ``track``.  On the stream's
+        own frames and labels the joined fields are ``ake_amd.key_changes``' to the bit, however the audio is cut.  Labels are not
+        revised from the frames, and there is one change per pair of windows.  Without it a stream is what it was: the same launches,
+        the same bits.
+
+        Refused with a ``ValueError``: ``posteriors=True`` with ``smooth=False``; a ``refine_slack_seconds`` that is negative or whose span
+        ``stride + 2 * slack`` exceeds 1024 frames; what ``track`` refuses (``frames=0``, ``wrap_mode="true_end"``, ``--local`` nets), with
         ``method="net"`` an estimator without a net, ``rate`` other than the estimator's (``rate`` names the rate the stream works at; what arrives is
         ``source_rate``), multi-channel chunks on a stream opened without ``source_channels``, ``tuning``, ``lag_windows`` outside
         0..255; by ``push``: a chunk after ``finish()``, a chunk whose R (or C) differs from the stream's, on a stream without a source
@@ -754,7 +769,8 @@ class KeyEstimator:
                              "the stream by a number of cents the caller names")
         return KeyStream(self, recordings, window_seconds, stride_seconds, smooth, lag_windows, mean_key_seconds, transition, log_prior,
                          signature_weight, keep_frames, max_chunk_samples, posteriors, source_rate, source_channels, channel, method,
-                         profiles, compression, profile_sharpness, tuning_meter, tuning_min_strength, retune_cents)
+                         profiles, compression, profile_sharpness, tuning_meter, tuning_min_strength, retune_cents, refine,
+                         refine_slack_seconds)
 
     def _refuse_untrackable(self):
         """What ``track`` and ``training_windows`` cannot slide windows over."""

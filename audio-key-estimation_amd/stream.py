@@ -16,7 +16,11 @@ launch (``metrics.stream_tuning``) and reports the detuning of the audio so far 
 ``tuning.StreamRetuner`` behind the resampler and in front of the history: the offline varispeed filter with a carried ring of 64 inputs
 (``retune_final`` below; ``ake_stream_retune_f32``, host model ``metrics.stream_retune``), whose output is ``retune``'s on the whole audio
 to the bit.  Everything here then counts retuned samples; only ``StreamUpdate.times`` are divided by ``rho`` again, and the meter reports
-the detuning that is left.  Not built: automatic retuning inside a stream (the number of cents is the caller's: taking it from the
+the detuning that is left.  ``refine=True`` places every key change to the frame inside the stream, as ``track(refine=True)`` does
+offline: ``ake_stream_key_changes_f32`` reads the chroma ring (a ``"net"`` stream keeps one for it) and a carried ring of labels, and
+computes the boundaries a push made final -- ``metrics.stream_changes_ready`` on the host's counts; host model
+``metrics.stream_key_changes`` -- into ``StreamUpdate.change_frame`` and its kin: joined, ``ake_amd.key_changes`` on the stream's own
+frames and labels to the bit.  Not built: automatic retuning inside a stream (the number of cents is the caller's: taking it from the
 stream's own meter needs a read-back or a ratio that changes in mid-stream), chunk lengths that differ between recordings, a weighting
 of the bins.
 
@@ -98,7 +102,14 @@ class StreamUpdate:
 
     A stream opened with ``retune_cents`` carries that number (float32-rounded, as the kernel reads it) in ``retune_cents``; its ``times``
     are divided by ``rho``, so they are seconds of the recording as it was pushed, not of its retuned copy, and its meter reports the
-    detuning that is left.  None on a stream opened without the keyword."""
+    detuning that is left.  None on a stream opened without the keyword.
+
+    A stream opened with ``refine=True`` adds where the key changes, to the frame, for the b boundaries from ``change_first_boundary``
+    on that this update made final (boundary w lies between the windows w and w + 1; ``metrics.stream_changes_ready``):
+    ``change_frame`` int32 (R, b), the frame of the stream -- not of the push -- from which the key of window w + 1 holds, or -1 where
+    the two windows do not carry two different keys, ``change_gain`` and ``change_contrast`` (R, b) as ``KeyTrack`` names them, and
+    ``change_times`` float64 (R, b), ``change_frame * hop / sample_rate`` in seconds of the recording as it was pushed (divided by
+    ``rho`` under ``retune_cents``; negative where ``change_frame`` is -1).  None on a stream opened without the keyword."""
     first_window: int
     windows: int
     key: torch.Tensor
@@ -119,6 +130,11 @@ class StreamUpdate:
     tuning_cents: torch.Tensor | None = None
     tuning_strength: torch.Tensor | None = None
     retune_cents: float | None = None
+    change_first_boundary: int | None = None
+    change_frame: torch.Tensor | None = None
+    change_gain: torch.Tensor | None = None
+    change_contrast: torch.Tensor | None = None
+    change_times: torch.Tensor | None = None
 
     @staticmethod
     def concat(parts):
@@ -129,7 +145,8 @@ class StreamUpdate:
         return StreamUpdate(parts[0].first_window, sum(p.windows for p in parts), cat("key"), cat("tonic"), cat("genre"), cat("key_id"),
                             cat("signature_id"), cat("tonic_id"), cat("confidence"), torch.cat([p.times for p in parts]), cat("emissions"),
                             cat("filtered"), parts[0].smooth_first_window, cat("smooth_key_id"), cat("posteriors"), cat("smooth_confidence"),
-                            cat("log_likelihood"), parts[-1].tuning_cents, parts[-1].tuning_strength, parts[0].retune_cents)
+                            cat("log_likelihood"), parts[-1].tuning_cents, parts[-1].tuning_strength, parts[0].retune_cents,
+                            parts[0].change_first_boundary, cat("change_frame"), cat("change_gain"), cat("change_contrast"), cat("change_times"))
 
 
 class KeyStream:
@@ -140,7 +157,9 @@ class KeyStream:
     halves of the frame cache, the net's workspace, the smoother's state and, with ``posteriors``, the posteriors' state.  A
     ``method="profile"`` stream has neither frame cache nor net workspace: in their place stands the state of
     ``ake_stream_frame_stats_f32``, a ring of ``window_frames + max_mel`` rows of per-frame chroma (96 bytes a frame) and three sums for
-    the tuning meter.  After the first push a push allocates only the tensors
+    the tuning meter.  ``refine=True`` lengthens that ring to the larger of the two rules (``metrics.stream_profile_ring_frames``,
+    ``metrics.stream_changes_ring_frames``; a ``"net"`` stream then has the ring too) and adds a ring of labels
+    (``metrics.stream_changes_labels_carried`` + a piece's new ones).  After the first push a push allocates only the tensors
     it returns (a chunk longer than ``max_chunk_samples`` is pushed as several pieces, whose updates are joined by one ``torch.cat``
     each).  ``push`` runs on the current stream.
 
@@ -155,7 +174,8 @@ class KeyStream:
     def __init__(self, est, recordings, window_seconds=15.0, stride_seconds=5.0, smooth=True, lag_windows=6, mean_key_seconds=60.0,
                  transition=None, log_prior=None, signature_weight=1.0, keep_frames=False, max_chunk_samples=None, posteriors=False,
                  source_rate=None, source_channels=None, channel=0, method="net", profiles="krumhansl", compression="log",
-                 profile_sharpness=10.0, tuning_meter=False, tuning_min_strength=0.0, retune_cents=None):
+                 profile_sharpness=10.0, tuning_meter=False, tuning_min_strength=0.0, retune_cents=None, refine=False,
+                 refine_slack_seconds=None):
         R = int(recordings)
         if R < 1:
             raise ValueError("stream: recordings must be at least 1")
@@ -176,6 +196,9 @@ class KeyStream:
         else:
             est._need_net('KeyEstimator.stream(method="net")')
             est._refuse_untrackable()
+        self.refine = bool(refine)
+        if self.refine and not self.profile:                         # (the chroma the boundaries are placed by: compression as for the profile method)
+            self.mode = metrics._profile_compression(compression)
         self.meter, self.min_strength = bool(tuning_meter), float(tuning_min_strength)
         if self.meter and self.min_strength != self.min_strength:
             raise ValueError("stream: tuning_min_strength is NaN")
@@ -267,20 +290,42 @@ class KeyStream:
         self.cqt_ws = torch.empty(cqt_bytes, dtype=torch.uint8, device=dev)
         self.net_ws = None if self.profile else torch.empty(net_bytes, dtype=torch.uint8, device=dev)
         # ---- the profile method's chroma ring and the tuning meter's sums (ake_stream_frame_stats_f32): a piece brings at most max_mel frames
-        self.stats_parts = (1 if self.profile else 0) | (2 if self.meter else 0)
+        # refine=True: the boundaries are placed from the same ring (ake_stream_key_changes_f32), which then holds the larger of the two
+        # rules' rows; the labels trail the windows by the lag where the smoother decides them
+        self.slack = None
+        if self.refine:
+            self.slack = self.sf if refine_slack_seconds is None else int(round(float(refine_slack_seconds) * est.frames))
+            if self.slack < 0:
+                raise ValueError("stream(refine=True): refine_slack_seconds must not be negative")
+            from . import keychanges
+            keychanges.check_span(self.sf, self.slack)
+        self.stats_parts = (1 if self.profile or self.refine else 0) | (2 if self.meter else 0)
         self.stats_state = self.tuning = None
         if self.stats_parts:
-            self.ring_frames = metrics.stream_profile_ring_frames(self.wf, self.max_mel) if self.profile else 1
+            self.ring_frames = max(metrics.stream_profile_ring_frames(self.wf, self.max_mel) if self.profile else 1,
+                                   metrics.stream_changes_ring_frames(self.wf, self.sf, self.slack, lag if self.smooth else 0, self.max_mel)
+                                   if self.refine else 1)
             nbytes = int(L.ake_stream_profile_state_bytes(R, self.ring_frames))
             if nbytes == 0:
                 _lib.check(-1, "ake_stream_profile_state_bytes")
             self.stats_state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         if self.meter:
             self.tuning = (torch.zeros(R, dtype=torch.float32, device=dev), torch.zeros(R, dtype=torch.float32, device=dev))
-        if self.profile:
+        if self.profile or self.refine:
             from . import keyprofile
             self.prof = keyprofile.device_profiles(profiles, dev)
+        if self.profile:
             self.key_sig = est._key_sig_table(dev)
+        # the labels of the windows a boundary still needs, int32 (R, label_ring): those carried between pieces and a piece's new ones
+        # (at most one per stride of new frames, and the lag's at the flush), so the slots a piece reads and writes cannot meet
+        self.L = self.B = 0                                          # decided labels, final boundaries -- host integers
+        self.label_state = None
+        if self.refine:
+            self.label_ring = metrics.stream_changes_labels_carried(self.wf, self.sf, self.slack) + (self.max_mel + self.sf - 1) // self.sf + lag
+            nbytes = int(L.ake_stream_key_changes_state_bytes(R, self.label_ring))
+            if nbytes == 0:
+                _lib.check(-1, "ake_stream_key_changes_state_bytes")
+            self.label_state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self.state = None
         if self.smooth:
             self.state = torch.empty(max(int(L.ake_key_stream_state_bytes(R, lag)), 16), dtype=torch.uint8, device=dev)
@@ -408,7 +453,7 @@ class KeyStream:
                     if self.meter:
                         self.tuning = (f32(R), f32(R))
                     _lib.check(L.ake_stream_frame_stats_f32(self.mel.data_ptr(), int(self.fm), R, P, T, first, new_frames, self.F, self.ring_frames,
-                                                            self.stats_parts, self.mode if self.profile else 0, self.min_strength,
+                                                            self.stats_parts, self.mode if self.stats_parts & 1 else 0, self.min_strength,
                                                             self.stats_state.data_ptr(), self.stats_state.numel(),
                                                             self.tuning[0].data_ptr() if self.meter else None,
                                                             self.tuning[1].data_ptr() if self.meter else None, stream), "ake_stream_frame_stats_f32")
@@ -487,4 +532,22 @@ class KeyStream:
                                    "ake_key_stream_posteriors_f32")
                         assert k_out.value == k2
             self.W += k
+            # ---- the boundaries this piece made final, placed to the frame from the chroma ring ----
+            if self.refine:
+                labels = up.smooth_key_id if self.smooth else key_id
+                k_l = labels.shape[1]
+                B = metrics.stream_changes_ready(self.L + k_l, self.F, self.wf, self.sf, self.slack, finishing)
+                b = B - self.B
+                up.change_first_boundary, up.change_frame, up.change_gain, up.change_contrast = self.B, i32(R, b), f32(R, b), f32(R, b)
+                if k_l > 0 or b > 0:
+                    _lib.check(L.ake_stream_key_changes_f32(self.stats_state.data_ptr(), self.stats_state.numel(), R, self.ring_frames, self.F,
+                                                            labels.data_ptr() if k_l else None, k_l, self.L, int(finishing), self.wf, self.sf,
+                                                            self.slack, self.prof.data_ptr(), self.label_state.data_ptr(),
+                                                            self.label_state.numel(), self.label_ring, self.B, b,
+                                                            up.change_frame.data_ptr() if b else None, up.change_gain.data_ptr() if b else None,
+                                                            up.change_contrast.data_ptr() if b else None, stream), "ake_stream_key_changes_f32")
+                up.change_times = up.change_frame.to(torch.float64) * hop / self.est.sample_rate
+                if self.retuner is not None:                         # seconds of the recording as it was pushed
+                    up.change_times = up.change_times / self.rho
+                self.L, self.B = self.L + k_l, B
         return up

@@ -938,6 +938,44 @@ int ake_key_changes_f32(const float* mel_dev, int frames_major, int recordings, 
                         int slack_frames, const float* profiles_dev /* [2][12] */, int compression, int32_t* change_frame_out,
                         float* gain_out, float* contrast_out, ake_stream_t stream);
 
+/* The same inside a key stream (csrc/stream_changes.hip; KeyEstimator.stream(refine=True)).  Host model: metrics.stream_key_changes.
+ * Joined over a stream's calls the three outputs are ake_key_changes_f32's on the joined frames and labels with frame_counts = the
+ * stream's frames and window_counts = its decided windows at the end, to the bit: both kernels call csrc/changes.h.
+ * chroma_state_dev is the state of ake_stream_frame_stats_f32 with its chroma part on (ring_frames rows a recording, frame t in row
+ * t % ring_frames), read only, after the call that brought the stream to `frames` frames.  labels_dev is int32 [recordings][k]: the
+ * labels of the windows labels_before .. labels_before + k - 1, decided since the last call (a stream's key_id, or its smooth_key_id,
+ * which trails the windows by the lag until the flush).  label_state_dev carries the labels of earlier calls: int32
+ * [recordings][label_ring], window v in slot v % label_ring, ake_stream_key_changes_state_bytes(recordings, label_ring) bytes (0 for
+ * recordings outside 1..65535 or label_ring < 1).  The device keeps no count: labels_before, first_boundary and n_boundaries are the
+ * host's.
+ * With L = labels_before + k, boundary w (between the windows w and w + 1, m_w as above) is final iff w + 2 < L and
+ * frames >= m_{w+1} + slack_frames, or flush != 0 (the recordings end here: T_r = frames, the window count is L) and w + 1 < L
+ * (metrics.stream_changes_ready counts them).  A call computes the boundaries first_boundary .. first_boundary + n_boundaries - 1, all of
+ * which must be final; a stream passes those that became final with this call, each once.
+ *   change_frame_out, gain_out, contrast_out [recordings][n_boundaries]: as ake_key_changes_f32 defines them, change_frame_out counting
+ *   the stream's frames; -1, 0, 0 where the two windows do not carry two different keys.  Every element is written.
+ * One launch, stream_key_changes_kernel, a workgroup per (boundary, recording): the four labels out of the ring or the call's own,
+ * the span's chroma rows out of the chroma ring (a frame per thread, all of a span of up to 1024 frames in one pass), the ordered sum
+ * by one thread.  The first workgroup of every recording also writes the call's labels into the label ring (alone, where a call
+ * brings labels and completes no boundary); the ring must be long enough that these slots and the ones the call reads cannot meet:
+ * k <= label_ring, and L - max(first_boundary - 1, 0) <= label_ring where that window was decided before this call.
+ * With labels_before == 0 the label state is not read and is written whole (-1 in the slots no window has reached).  k == 0 with
+ * n_boundaries == 0 launches nothing.  No atomics, no workspace: reruns are bit-identical, and neither the outputs nor the label state
+ * depend on how a stream's labels and frames are cut into calls.
+ * AKE_ERR_INVALID: null arguments (labels_dev with k == 0 and the outputs with n_boundaries == 0 excepted), recordings outside
+ * 1..65535, ring_frames or label_ring < 1, window_frames < 1, stride_frames < 1, slack_frames < 0, k or n_boundaries outside 0..65535,
+ * frames, labels_before or first_boundary outside 0..2^30, a decided window that ends behind `frames`, and counts that break the
+ * rule: a boundary whose labels are not yet known, one whose frames have not yet arrived, one whose first frame
+ * max(m_w - slack_frames, 0) lies in front of frames - ring_frames (no longer in the chroma ring), and label slots that would meet.
+ * AKE_ERR_UNSUPPORTED: stride_frames + 2 * slack_frames > 1024.  AKE_ERR_WORKSPACE: either state's bytes short.  Nothing is launched
+ * on a refusal. */
+size_t ake_stream_key_changes_state_bytes(int recordings, int label_ring);
+int ake_stream_key_changes_f32(const void* chroma_state_dev, size_t chroma_state_bytes, int recordings, int ring_frames, int64_t frames,
+                               const int32_t* labels_dev, int k, int64_t labels_before, int flush, int window_frames, int stride_frames,
+                               int slack_frames, const float* profiles_dev /* [2][12] */, void* label_state_dev, size_t label_state_bytes,
+                               int label_ring, int64_t first_boundary, int n_boundaries, int32_t* change_frame_out, float* gain_out,
+                               float* contrast_out, ake_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Per-kernel timing with hipEvents recorded on the launch stream (bench.py roofline leg).
  * ---------------------------------------------------------------------------------------- */

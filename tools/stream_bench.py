@@ -36,8 +36,16 @@
               over the rounds their median and spread; and the two added launches (stream_retune_kernel, stream_retune_tail_kernel) per
               launch under the library's kernel timer.
 
+  --refine: this section alone.  est.stream(R, refine=True) beside est.stream(R), with the net and with method="profile", both fed float32
+              chunks of one hop and of 1 s: three rounds of --pushes pushes each, the two streams taking turns; per push by events on the
+              stream, the median of each round, over the rounds their median and spread, and what refine adds at the median; the launches
+              it adds (stream_key_changes_kernel, and on a net stream stream_frame_stats_kernel) per launch under the library's kernel
+              timer.  And the two change-point kernels per boundary on the same spans: alternating labels on 40 windows at the default
+              geometry (76 frames, 25 apart, slack 25: spans of 75 frames), key_changes_kernel on the log-CQT beside
+              stream_key_changes_kernel on the chroma ring, all boundaries in one call and one boundary a call (a push's shape).
+
 Usage: python tools/stream_bench.py [--pushes 200] [--accuracy] [--posteriors] [--source-rate 48000 --source-channels 2]
-                                    [--method profile] [--tuning-meter] [--retune-cents 33.3]"""
+                                    [--method profile] [--tuning-meter] [--retune-cents 33.3] [--refine]"""
 import argparse
 import ctypes as C
 import importlib.util
@@ -308,6 +316,94 @@ def retune_rows(est, recordings, pushes, cents, rounds=3):
     return rows
 
 
+def refine_rows(est, recordings, pushes, rounds=3):
+    """A push of a stream opened with refine=True beside a push of the same stream without it: `rounds` rounds of `pushes` pushes each,
+    the two taking turns in one process; and the launches refine adds, under the library's kernel timer."""
+    free = ake_amd.KeyEstimator(None, SR, 5, device=DEV, pitches=288)
+    rows = []
+    for R in recordings:
+        for method, owner in (("net", est), ("profile", free)):
+            for m in (HOP, SR):
+                pieces = [torch.randn((R, m), device=DEV) * 0.3 for _ in range(8)]
+                warm = 60 * SR // m + 1                                              # (30 s of lag behind the first window: boundaries are being emitted)
+                meds = {"refined": [], "plain": []}
+                for _ in range(rounds):
+                    for kind, kw in (("refined", dict(refine=True)), ("plain", {})):
+                        meds[kind].append(statistics.median(timed_pushes(owner.stream(R, method=method, **kw), pieces, pushes, warm)))
+                s = owner.stream(R, method=method, refine=True)
+                for i in range(warm):
+                    s.push(pieces[i % 8])
+                torch.cuda.synchronize()
+                _lib.prof_enable("", True)
+                ups = [s.push(pieces[i % 8]) for i in range(pushes)]
+                prof = _lib.prof_results()
+                _lib.prof_enable("", False)
+                cells = torch.cat([u.change_frame for u in ups], dim=1)
+                stat = lambda xs: {"median_of_rounds": round(statistics.median(xs), 4), "spread": round(max(xs) - min(xs), 4),   # noqa: E731
+                                   "rounds": [round(x, 4) for x in xs]}
+                rows.append({"recordings": R, "method": method, "chunk_s": round(m / SR, 3), "push_ms_refined": stat(meds["refined"]),
+                             "push_ms_plain": stat(meds["plain"]),
+                             "added_ms_median": round(statistics.median(meds["refined"]) - statistics.median(meds["plain"]), 4),
+                             "kernel_us_per_launch": {n: round(1e3 * t / k, 2) for n, (t, k) in prof.items()
+                                                      if k and n in ("stream_key_changes_kernel", "stream_frame_stats_kernel")},
+                             "launches_per_push": {n: round(k / pushes, 3) for n, (t, k) in prof.items()
+                                                   if k and n in ("stream_key_changes_kernel", "stream_frame_stats_kernel")},
+                             "boundaries_emitted": int(cells.shape[1]), "of_them_key_changes": int((cells >= 0).sum()) // R if R else 0})
+                del s, pieces
+    return rows
+
+
+def change_kernel_rows(recordings, reps=20):
+    """key_changes_kernel and stream_key_changes_kernel per boundary on the same spans, under the library's kernel timer."""
+    from ake_amd import keyprofile
+    L = _lib.lib()
+    wf, sf, slack, W, P = 76, 25, 25, 40, 288
+    T = wf + (W - 1) * sf
+    stream = torch.cuda.current_stream().cuda_stream
+    prof = keyprofile.device_profiles("krumhansl", torch.device(DEV))
+    rows = []
+    for R in recordings:
+        mel = torch.rand((R, P, T), device=DEV) * 3.0
+        labels = ((torch.arange(W, device=DEV)[None, :] + torch.arange(R, device=DEV)[:, None]) % 24).to(torch.int32).contiguous()
+        outs = [torch.empty((R, W - 1), dtype=torch.int32, device=DEV), torch.empty((R, W - 1), device=DEV), torch.empty((R, W - 1), device=DEV)]
+        ring, label_ring = T, W + 3
+        chroma = torch.empty(L.ake_stream_profile_state_bytes(R, ring), dtype=torch.uint8, device=DEV)
+        state = torch.empty(L.ake_stream_key_changes_state_bytes(R, label_ring), dtype=torch.uint8, device=DEV)
+        _lib.check(L.ake_stream_frame_stats_f32(mel.data_ptr(), 0, R, P, T, 0, T, 0, ring, 1, 0, 0.0, chroma.data_ptr(), chroma.numel(), None, None, stream),
+                   "ake_stream_frame_stats_f32")
+
+        def offline():
+            _lib.check(L.ake_key_changes_f32(mel.data_ptr(), 0, R, P, T, None, labels.data_ptr(), W, None, wf, sf, slack, prof.data_ptr(), 0,
+                                             *[o.data_ptr() for o in outs], stream), "ake_key_changes_f32")
+
+        def streamed(first, n, k, before, flush):
+            new = labels[:, before:before + k].contiguous()
+            _lib.check(L.ake_stream_key_changes_f32(chroma.data_ptr(), chroma.numel(), R, ring, T, new.data_ptr() if k else None, k, before, flush, wf, sf,
+                                                    slack, prof.data_ptr(), state.data_ptr(), state.numel(), label_ring, first, n,
+                                                    *[o.data_ptr() for o in outs], stream), "ake_stream_key_changes_f32")
+
+        offline()
+        want = [o.clone() for o in outs]
+        streamed(0, W - 1, W, 0, 1)
+        same = all(torch.equal(a, b) for a, b in zip(outs, want))
+        torch.cuda.synchronize()
+        _lib.prof_enable("key_changes_kernel", True)
+        for _ in range(reps):
+            offline()
+            streamed(0, W - 1, W, 0, 1)
+        whole = _lib.prof_results()
+        for _ in range(reps):                                                        # one boundary a call: window 21 arrives, boundary 18 is final
+            streamed(18, 1, 1, 21, 0)
+        one = _lib.prof_results()
+        _lib.prof_enable("", False)
+        per = lambda res, name, n: round(1e3 * res[name][0] / res[name][1] / n, 3)   # noqa: E731
+        rows.append({"recordings": R, "windows": W, "span_frames": sf + 2 * slack, "bits_equal": same,
+                     "all_in_one_call_us_per_boundary": {n: per(whole, n, (W - 1) * R) for n in whole},
+                     "all_in_one_call_us_per_launch": {n: per(whole, n, 1) for n in whole},
+                     "one_boundary_a_call_us_per_launch": {n: per(one, n, 1) for n in one}})
+    return rows
+
+
 def agreement_rows():
     """A profile stream's key labels against track(method="profile") on the whole audio: 24 synthesised modulating recordings of 5 min."""
     from ake_amd import synthetic
@@ -381,6 +477,7 @@ def main():
     ap.add_argument("--method", choices=("net", "profile"), default=None)
     ap.add_argument("--tuning-meter", action="store_true")
     ap.add_argument("--retune-cents", type=float, default=None)
+    ap.add_argument("--refine", action="store_true")
     args = ap.parse_args()
     torch.manual_seed(0)
     gold = np.load(os.path.join(REPO, "tests", "golden", "pcnet_default.npz"))
@@ -399,6 +496,10 @@ def main():
     if args.retune_cents is not None:
         print(json.dumps({"device": torch.cuda.get_device_name(0), "pushes": args.pushes,
                           "retune": retune_rows(est, args.recordings, args.pushes, args.retune_cents)}))
+        return
+    if args.refine:
+        print(json.dumps({"device": torch.cuda.get_device_name(0), "pushes": args.pushes,
+                          "refine": refine_rows(est, args.recordings, args.pushes), "change_kernels": change_kernel_rows(args.recordings)}))
         return
     if args.method is not None or args.tuning_meter:
         method = args.method or "net"
