@@ -393,13 +393,13 @@ int device_cus() {
 }
 
 // row-tile height of the persistent pitch-conv kernel for H x T maps (0: the shape does not qualify); `semi`: the form fused with the
-// semitone conv (tiles of 3k rows, no staging slabs but a double-buffered output patch).  nw: waves of the workgroup (8; 16: a phase of
+// semitone conv (tiles of 3k rows, no staging slabs but a double-buffered output patch and that conv's B fragments).  nw: waves of the workgroup (8; 16: a phase of
 // p2p_stack_kernel, whose semitone form always folds: its tile height also divides the octave's 36 rows)
 int p2p_ps_rows(int H, int T, bool semi, int* plane_pos, size_t* lds, int nw = 8) {
     if (T < 2 || (T & 1) || device_cus() < 8) return 0;
     const int J = T / 2, Tp = p2p_pitch(J);
     auto plane_of = [&](int R) { return ((R + 6) * Tp + 63) / 64 * 64; };
-    auto lds_of = [&](int R) { return (static_cast<size_t>(2) * plane_of(R) + (semi ? 2 * nw * kP2pMT * 16 * 2 : nw * kP2pMT * kP2pPsStage)) * sizeof(uint4); };
+    auto lds_of = [&](int R) { return (static_cast<size_t>(2) * plane_of(R) + (semi ? 2 * nw * kP2pMT * 16 * 2 + kP2pSemiFrags : nw * kP2pMT * kP2pPsStage)) * sizeof(uint4); };
     int R = std::max(1, std::min(H, nw * kP2pMT * 16 / J));
     if (semi) R = R / 3 * 3;
     while (R >= (semi ? 3 : 1) && (lds_of(R) > 156 * 1024 || plane_of(R) / 64 > nw * kP2pPieces || (semi && nw == 16 && 36 % R))) R -= semi ? 3 : 1;     // the loader: nw waves x kP2pPieces pieces

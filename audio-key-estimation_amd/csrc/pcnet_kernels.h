@@ -926,6 +926,8 @@ struct P2pPsArgs {
 
 constexpr int kP2pPieces = 3;        // 1 KB pieces of the patch a wave requests per tile (8 waves: planes of up to 24 pieces)
 constexpr int kP2pPsStage = 80;      // uint4 per M-tile of a wave's staging slab (NCHW form: 8 channels x 36 floats, padded)
+constexpr int kP2pSemiFrags = 6 * 64;  // uint4 of the semitone conv's B fragments, staged behind the output patches (OUT 2 / 3)
+constexpr int kP2pSlots = 4;         // register slots (one A fragment each) the multiply loop rotates its kP2pMT M-tiles through
 
 // OUT: 0 = NCHW f32, 1 = channels-last f16 plane (next conv of the stack), 2 = the stack's last conv FUSED with the semitone conv
 //   that follows it (3x3, stride (3,1), time circular + BN + LeakyReLU; models.py:337-339, 386-388): the activated tile (R = 3k rows)
@@ -951,6 +953,28 @@ __device__ __forceinline__ void p2p_phase_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
+// A wave-uniform value the tile loop needs, held in scalar registers from here on.  (A field of the argument block read where it is
+// used is re-read there: hipcc sinks the scalar load into the tile loop, in front of the patch request and of the stores, and every such
+// load is a round trip to memory behind an lgkmcnt(0) that also drains the LDS reads in flight.)
+template <typename V>
+__device__ __forceinline__ V p2p_held(V v) {
+    asm volatile("" : "+s"(v));
+    return v;
+}
+// A pointer rebuilt from its bits (p2p_held, uniform_ptr) is a generic one to the compiler, and loads and stores through it are flat_*
+// instructions, which count on lgkmcnt as well as on vmcnt and out of order with the LDS reads: every wait for an A fragment behind one
+// becomes lgkmcnt(0).  These buffers are all in global memory.
+template <typename V>
+__device__ __forceinline__ V* p2p_global(V* p) {
+    return (V*)reinterpret_cast<__attribute__((address_space(1))) V*>(reinterpret_cast<unsigned long long>(p));
+}
+template <typename V>
+__device__ __forceinline__ V* p2p_held(V* p) {
+    unsigned long long v = reinterpret_cast<unsigned long long>(p);
+    asm volatile("" : "+s"(v));
+    return p2p_global(reinterpret_cast<V*>(v));
+}
+
 template <int OUT, int NIN, int NW, bool CHAIN>
 __device__ __forceinline__ void p2p_ps_tiles(const P2pPsArgs& a, const int first, const int step, const int limit) {
     constexpr bool OUT_CL = OUT == 1, OUT_SEMI = OUT == 2 || OUT == 3, OUT_FOLD = OUT == 3;
@@ -959,13 +983,28 @@ __device__ __forceinline__ void p2p_ps_tiles(const P2pPsArgs& a, const int first
     constexpr int NV = IN_UH ? 1 : (IN_NCHW ? NIN : 1);
     extern __shared__ __attribute__((aligned(16))) uint4 lds4[];
     constexpr int MT = kP2pMT;
-    const int lane = threadIdx.x & 63;
+    constexpr int NS = kP2pSlots;
+    static_assert(NS > MT, "a fragment is requested MT MFMAs ahead, into a slot no pending MFMA reads");
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int r16 = lane & 15, q = lane >> 4;
-    const int Tp = a.Tp, J = a.J, T = a.T;
+    // The lane number and what the epilogues and stores derive from it are worked out again behind every tile's barrier, from a value
+    // the compiler cannot see through: hoisted out of the tile loop, those addresses, row numbers and masks held a dozen registers through
+    // the multiply loop, which has none to spare (a few vector instructions per tile against 14 k-steps)
+    int lane = threadIdx.x & 63, r16, q, tau, co;
+    auto lane_parts = [&]() {
+        asm volatile("" : "+v"(lane));
+        r16 = lane & 15; q = lane >> 4; tau = r16 >> 3; co = r16 & 7;
+    };
+    lane_parts();
+    const int Tp = p2p_held(a.Tp), J = p2p_held(a.J), T = p2p_held(a.T), H = p2p_held(a.H), R = p2p_held(a.R);
+    const int plane_pos = p2p_held(a.plane_pos);
+    const unsigned short* const xh = p2p_held(a.xh);
+    unsigned short* const oh = p2p_held(a.oh);
+    float* const dst = p2p_held(a.dst);
+    const long long dst_clip_stride = p2p_held(a.dst_clip_stride);
+    const int n_oct = p2p_held(a.n_oct);
     f16_saturate_mode();
-    const int nchunk = a.plane_pos >> 6;                        // 1 KB pieces per plane
-    const int npos = (a.R + 6) * Tp;
+    const int nchunk = plane_pos >> 6;                          // 1 KB pieces per plane
+    const int npos = (R + 6) * Tp;
     // ---- loader: the pieces c = wave, wave + NW, ... of the plane; lane -> patch position -> (row offset, frame) ----
     int pk[kP2pPieces];
 #pragma unroll
@@ -976,19 +1015,19 @@ __device__ __forceinline__ void p2p_ps_tiles(const P2pPsArgs& a, const int first
         const int rj = i / Tp, f = i - rj * Tp;
         pk[k] = (rj << 16) | wrap(f - 3, T);
     }
-    auto issue_loads = [&](int tile, int buf) {
-        const int clip = tile / a.n_row_tiles;
-        const int y0 = (tile - clip * a.n_row_tiles) * a.R;
-        const long long cbase = static_cast<long long>(clip) * a.H * T;
+    auto issue_loads = [&](int clip, int y0, int buf) {
+        const long long cbase = static_cast<long long>(clip) * H * T;
 #pragma unroll
         for (int k = 0; k < kP2pPieces; ++k) {
             const int c = wave + NW * k;
             if (c < nchunk) {
-                int row = y0 - 3 + (pk[k] >> 16);
-                row += row < 0 ? a.H : 0;
-                row -= row >= a.H ? a.H : 0;
-                const uint4* src = reinterpret_cast<const uint4*>(a.xh) + cbase + static_cast<long long>(row) * T + (pk[k] & 0xffff);
-                uint4* dstl = lds4 + buf * a.plane_pos + c * 64;
+                int pkk = pk[k];
+                asm volatile("" : "+v"(pkk));       // (unpacked here, not once for the launch in two more registers per piece)
+                int row = y0 - 3 + (pkk >> 16);
+                row += row < 0 ? H : 0;
+                row -= row >= H ? H : 0;
+                const uint4* src = reinterpret_cast<const uint4*>(xh) + cbase + static_cast<long long>(row) * T + (pkk & 0xffff);
+                uint4* dstl = lds4 + buf * plane_pos + c * 64;
                 // (lds_dma_16 waits for nothing: the wait is placed by hand before the barrier)
                 ake::lds_dma_16(src, static_cast<unsigned int>(reinterpret_cast<unsigned long long>(dstl)));
             }
@@ -1009,42 +1048,45 @@ __device__ __forceinline__ void p2p_ps_tiles(const P2pPsArgs& a, const int first
             pn[k] = (rj << 16) | wrap(f - 3, T);
         }
     }
-    auto load_regs = [&](int tile) {      // branch-free (a branch around a load makes hipcc wait for every load at the join)
-        const int clip = tile / a.n_row_tiles;
-        const int y0 = (tile - clip * a.n_row_tiles) * a.R;
+    const unsigned int* const in_ph = IN_UH ? p2p_held(a.ph) : nullptr;
+    const uint2* const in_uh = IN_UH ? p2p_held(a.uh) : nullptr;
+    const int h1 = IN_NCHW ? p2p_held(a.h1) : 1;
+    auto load_regs = [&](int clip, int y0) {      // branch-free (a branch around a load makes hipcc wait for every load at the join)
         const int ctot = a.c0 + a.c1;
         // Addressing: per channel a wave-uniform base (scalar registers), per patch position ONE 32-bit lane offset shared by all channels of a
         // source -- the loads then take the `saddr + voffset` form and cost no vector instruction each (round 2 built a 64-bit address per load:
         // 15 loads x ~4 vector instructions per thread and tile made this launch issue twice the vector instructions of its plane-fed siblings,
         // profiles/r03_a_pmc_mfma.md: 19.95 M against 9.84 M).
-        const float* const pb = a.p_fm ? a.p + static_cast<long long>(clip) * T * a.H : a.p + static_cast<long long>(clip) * a.c0 * a.H * T;
-        const float* const ub = a.u + static_cast<long long>(clip) * a.c1 * a.h1 * T;
-        const uint2* const uhb = IN_UH ? uniform_ptr(a.uh + static_cast<long long>(clip) * a.h1 * T) : nullptr;
+        const float* const pb = a.p_fm ? a.p + static_cast<long long>(clip) * T * H : a.p + static_cast<long long>(clip) * a.c0 * H * T;
+        const float* const ub = a.u + static_cast<long long>(clip) * a.c1 * h1 * T;
+        const uint2* const uhb = IN_UH ? p2p_global(uniform_ptr(in_uh + static_cast<long long>(clip) * h1 * T)) : nullptr;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            int row = y0 - 3 + (pn[k] >> 16);
-            row += row < 0 ? a.H : 0;
-            row -= row >= a.H ? a.H : 0;
-            const int t = pn[k] & 0xffff;
+            int pnk = pn[k];
+            asm volatile("" : "+v"(pnk));           // (as pk in issue_loads)
+            int row = y0 - 3 + (pnk >> 16);
+            row += row < 0 ? H : 0;
+            row -= row >= H ? H : 0;
+            const int t = pnk & 0xffff;
             if (IN_UH) {
-                vw[k] = uniform_ptr(a.ph + static_cast<long long>(clip) * a.H * T)[static_cast<unsigned int>(row * T + t)];
-                vuh[k] = uhb[static_cast<unsigned int>((row % a.h1) * T + t)];
+                vw[k] = p2p_global(uniform_ptr(in_ph + static_cast<long long>(clip) * H * T))[static_cast<unsigned int>(row * T + t)];
+                vuh[k] = uhb[static_cast<unsigned int>((row % h1) * T + t)];
                 continue;
             }
             // (frames-major p: one 64-byte line holds 16 bins of a frame = this tile's rows; the lanes of a request walk the frames, so
             // it costs a cache line per lane in the texture addresser, but every line is read 16 times from the L1)
-            const int poff = a.p_fm ? t * a.H + row : row * T + t;
-            const int uoff = (row % a.h1) * T + t;
+            const int poff = a.p_fm ? t * H + row : row * T + t;
+            const int uoff = (row % h1) * T + t;
 #pragma unroll
             for (int c = 0; c < NV; ++c) {
                 const int cc = c < ctot ? c : ctot - 1;               // (channels >= ctot re-read the last one; zeroed when the patch is written)
-                const float* const base = uniform_ptr(cc < a.c0 ? pb + static_cast<long long>(cc) * a.H * T : ub + static_cast<long long>(cc - a.c0) * a.h1 * T);
+                const float* const base = p2p_global(uniform_ptr(cc < a.c0 ? pb + static_cast<long long>(cc) * H * T : ub + static_cast<long long>(cc - a.c0) * h1 * T));
                 vin[k][c] = base[static_cast<unsigned int>(cc < a.c0 ? poff : uoff)];
             }
         }
     };
     auto write_lds = [&](int buf) {
-        uint4* const wH = lds4 + buf * a.plane_pos;
+        uint4* const wH = lds4 + buf * plane_pos;
         const int ctot = a.c0 + a.c1;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -1056,7 +1098,7 @@ __device__ __forceinline__ void p2p_ps_tiles(const P2pPsArgs& a, const int first
                 hi[1] = (vuh[k].x >> 16) | (vuh[k].y << 16);
                 hi[2] = (vuh[k].y >> 16) | (vw[k] & 0xffff0000u);
                 hi[3] = hb;
-                const int i = threadIdx.x + 64 * NW * k;
+                const int i = wave * 64 + lane + 64 * NW * k;
                 if (i < npos) wH[i] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
                 continue;
             }
@@ -1075,59 +1117,73 @@ __device__ __forceinline__ void p2p_ps_tiles(const P2pPsArgs& a, const int first
         }
     };
     // tile sequence: first, first + step, ...; OUT 3: units first, first + step, ..., each the n_oct tiles (clip, octave o, group g)
+    // The sequence is walked as (clip, place g within the clip: row tile, OUT 3: group), not divided out of a tile number per tile: the
+    // divisions below are the phase's only ones.
     const int G = OUT_FOLD ? a.n_row_tiles / a.n_oct : 1;
-    auto fold_tile = [&](int u, int o) { const int clip = u / G; return clip * a.n_row_tiles + o * G + (u - clip * G); };
-    const int tile0 = first < limit ? (OUT_FOLD ? fold_tile(first, 0) : first) : -1;
+    const int per = p2p_held(OUT_FOLD ? G : a.n_row_tiles);           // places per clip
+    int left = first < limit ? ((limit - first + step - 1) / step) * (OUT_FOLD ? n_oct : 1) : 0;     // tiles still to multiply
+    int clip = first / per, g = first - clip * per;
+    const int step_q = p2p_held(step < per ? 0 : step / per), step_r = p2p_held(step - step_q * per);
+    const int oct_rows = G * R;                                        // OUT 3: rows from a group to the same group an octave up
     auto first_patch = [&]() {
-        if (tile0 >= 0) {
-            if (IN_NCHW) { load_regs(tile0); write_lds(0); }
-            else issue_loads(tile0, 0);
+        if (left > 0) {
+            if (IN_NCHW) { load_regs(clip, g * R); write_lds(0); }
+            else issue_loads(clip, g * R, 0);
         }
     };
     if (!CHAIN) first_patch();
     // ---- weight fragments: registers, for the whole launch ----
     uint4 breg[28];                  // (kP2pProducts == 1: the lo halves are never used and never loaded)
 #pragma unroll
-    for (int i = 0; i < 28; ++i) breg[i] = a.bfrag[i * 64 + lane];
+    for (int i = 0; i < 28; ++i) breg[i] = p2p_global(uniform_ptr(a.bfrag + i * 64))[static_cast<unsigned int>(lane)];   // (scalar base + one lane offset: no address pair per load)
     int abase[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
         int m = (wave * MT + mt) * 16 + r16;
-        m = m < a.R * J ? m : a.R * J - 1;
+        m = m < R * J ? m : R * J - 1;
         const int r = m / J, j = m - r * J;
         abase[mt] = r * Tp + 2 * j + q;
     }
-    const int tau = r16 >> 3, co = r16 & 7;
     const float bias = a.bias[co];
     const float iscale = reinterpret_cast<const float*>(a.bfrag + kP2pFragScale)[co];
-    uint4* const stage = lds4 + 2 * a.plane_pos + wave * (MT * kP2pPsStage);          // OUT 0 / 1: wave-private slabs
-    uint4* const opatch = lds4 + 2 * a.plane_pos;                                      // OUT 2: [2 buffers][384 m][2 tau] positions
+    uint4* const stage = lds4 + 2 * plane_pos + wave * (MT * kP2pPsStage);            // OUT 0 / 1: wave-private slabs
+    uint4* const opatch = lds4 + 2 * plane_pos;                                        // OUT 2: [2 buffers][384 m][2 tau] positions
     constexpr int kOP = NW * MT * 16 * 2;                                               // positions of one output patch
     typedef float f32x2e __attribute__((ext_vector_type(2)));
     long long prev_base = 0;          // element offset of the pending tile's first position (channels-last: position index)
     int prev_mblk = 0;
     bool has_prev = false;
-    auto store_pending = [&]() {      // the finished tile waits in the staging slab (not in registers: the multiply loop needs them all)
+    // The finished tile waits in the staging slab (not in registers: the multiply loop needs them all) and leaves in two moves: the slab
+    // is read into ov0 .. ov2, a k-step ahead of the stores where the registers allow it (the first conv), so that the stores wait for a
+    // read that has long returned and not, with lgkmcnt(0), for the A fragments in flight as well
+    uint4 ov0 = make_uint4(0, 0, 0, 0), ov1 = ov0, ov2 = ov0;
+    auto read_pending = [&]() {
         if (OUT_CL) {       // lane = (M-tile of a pair, m, tau): position 2 * (mbase + m) + tau of the tile, 8 channels = 16 bytes
             static_assert(MT == 3, "the M-tiles leave as one pair and a single");
-            const uint4 o01 = stage[(lane >> 5) * kP2pPsStage + (lane & 31)], o2 = stage[2 * kP2pPsStage + (lane & 31)];
-            const int mb01 = (wave * MT + (lane >> 5)) * 16, mb2 = (wave * MT + 2) * 16, ml = (lane >> 1) & 15;
-            uint4* const o = reinterpret_cast<uint4*>(a.oh) + prev_base + (lane & 31);
-            if (mb01 + ml < prev_mblk) o[2 * mb01] = o01;
-            if (lane < 32 && mb2 + ml < prev_mblk) o[2 * mb2] = o2;
+            ov0 = stage[(lane >> 5) * kP2pPsStage + (lane & 31)];
+            ov1 = stage[2 * kP2pPsStage + (lane & 31)];
             return;
         }
-        uint4 outv[MT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) outv[mt] = stage[mt * kP2pPsStage + (lane >> 3) * 9 + (lane & 7)];
+        const uint4* const sl = stage + (lane >> 3) * 9 + (lane & 7);
+        ov0 = sl[0]; ov1 = sl[kP2pPsStage]; ov2 = sl[2 * kP2pPsStage];
+    };
+    auto store_pending = [&]() {
+        if (OUT_CL) {
+            const int mb01 = (wave * MT + (lane >> 5)) * 16, mb2 = (wave * MT + 2) * 16, ml = (lane >> 1) & 15;
+            uint4* const o = reinterpret_cast<uint4*>(oh) + prev_base + (lane & 31);
+            if (mb01 + ml < prev_mblk) o[2 * mb01] = ov0;
+            if (lane < 32 && mb2 + ml < prev_mblk) o[2 * mb2] = ov1;
+            return;
+        }
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
             const int mbase = (wave * MT + mt) * 16;
+            const uint4 ov = mt == 0 ? ov0 : mt == 1 ? ov1 : ov2;
             {               // lane = (channel, group of 4 frames)
                 const int m = mbase + 2 * (lane & 7);
-                float* o = a.dst + prev_base + static_cast<long long>(lane >> 3) * a.H * T + 2 * m;
-                if (m + 1 < prev_mblk) *reinterpret_cast<uint4*>(o) = outv[mt];
-                else if (m < prev_mblk) { o[0] = __uint_as_float(outv[mt].x); o[1] = __uint_as_float(outv[mt].y); }
+                float* o = dst + prev_base + static_cast<long long>(lane >> 3) * H * T + 2 * m;
+                if (m + 1 < prev_mblk) *reinterpret_cast<uint4*>(o) = ov;
+                else if (m < prev_mblk) { o[0] = __uint_as_float(ov.x); o[1] = __uint_as_float(ov.y); }
             }
         }
     };
@@ -1164,32 +1220,44 @@ __device__ __forceinline__ void p2p_ps_tiles(const P2pPsArgs& a, const int first
         }
     };
     // ---- OUT 2: semitone conv over the finished tile (one M-tile of 16 (semitone row, frame pair) positions per wave) ----
-    uint4 sreg[6];
+    // Its B fragments (three MFMAs a tile) live in LDS behind the two output patches, staged once per phase: held in registers for the
+    // whole phase they were 24 of the 128, and the multiply loop spilled.
+    uint4* const sfl = opatch + 2 * kOP;                               // [3 dy][hi | lo * 2^11][64 lanes]
+    uint4 sfrag_mine = make_uint4(0, 0, 0, 0);                         // the thread's share on its way there
     float sbias = 0.f, siscale = 1.f;
     int sbase = 0;
     if (OUT_SEMI) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) sreg[i] = a.sfrag[i * 64 + lane];
+        static_assert(NW * 64 >= kP2pSemiFrags, "one fragment word per thread");
+        if (threadIdx.x < kP2pSemiFrags) sfrag_mine = a.sfrag[threadIdx.x];
         sbias = a.sbias[co];
         siscale = reinterpret_cast<const float*>(a.sfrag + 6 * 64)[co];
         int ms = wave * 16 + r16;
-        ms = ms < (a.R / 3) * J ? ms : (a.R / 3) * J - 1;
+        ms = ms < (R / 3) * J ? ms : (R / 3) * J - 1;
         const int srow = ms / J, sj = ms - srow * J;
         sbase = 3 * srow * T + wrap(2 * sj - 1 + q, T);               // A[m][k = (position q, ci)] = X[3s + dy][2j - 1 + q][ci]
     }
     float smax[4] = {0.f, 0.f, 0.f, 0.f};                             // OUT 3: running maximum over the octaves of a unit
-    auto semi_stage = [&](int obuf, long long base, int mblk, int oct) {   // base: element offset of (clip, channel 0, first semitone row) in dst
+    // (`then`: what the caller wants issued behind the stage's MFMAs, in front of its vector work: the next multiply loop's first requests)
+    auto semi_stage = [&](int obuf, long long base, int mblk, int oct, auto then) {   // base: element offset of (clip, channel 0, first semitone row) in dst
         const uint4* const oH = opatch + obuf * kOP;
         f32x4c sacc = {0.f, 0.f, 0.f, 0.f}, saccl = {0.f, 0.f, 0.f, 0.f};
+        f16x8c sa[3], sbh[3], sbl[3];
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy) {                              // all six reads, then the products
+            sa[dy] = __builtin_bit_cast(f16x8c, oH[sbase + dy * T]);
+            sbh[dy] = __builtin_bit_cast(f16x8c, sfl[2 * dy * 64 + lane]);
+            if (kP2pProducts == 2) sbl[dy] = __builtin_bit_cast(f16x8c, sfl[(2 * dy + 1) * 64 + lane]);
+        }
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy) {
-            const f16x8c ah = __builtin_bit_cast(f16x8c, oH[sbase + dy * T]);
-            const f16x8c bh = __builtin_bit_cast(f16x8c, sreg[2 * dy]), bl = __builtin_bit_cast(f16x8c, sreg[2 * dy + 1]);
-            sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, sacc, 0, 0, 0);
-            if (kP2pProducts == 2) saccl = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, saccl, 0, 0, 0);
+            sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(sa[dy], sbh[dy], sacc, 0, 0, 0);
+            if (kP2pProducts == 2) saccl = __builtin_amdgcn_mfma_f32_16x16x32_f16(sa[dy], sbl[dy], saccl, 0, 0, 0);
         }
-        const int S = OUT_FOLD ? 12 : a.H / 3;
-        float* const o = a.dst + base + static_cast<long long>(co) * S * T + tau;
+        __builtin_amdgcn_sched_barrier(0);
+        then();
+        __builtin_amdgcn_sched_barrier(0);
+        const int S = OUT_FOLD ? 12 : H / 3;
+        float* const o = dst + base + static_cast<long long>(co) * S * T + tau;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {                                 // D[m = 4q + i][n = (tau, co)]: semitone position 2m + tau of the tile
             const int m = wave * 16 + 4 * q + i;
@@ -1199,11 +1267,13 @@ __device__ __forceinline__ void p2p_ps_tiles(const P2pPsArgs& a, const int first
                 if (3 * m < mblk) o[2 * m] = v;
             } else {
                 smax[i] = oct == 0 ? v : fmaxf(smax[i], v);
-                if (oct == a.n_oct - 1 && 3 * m < mblk) o[2 * m] = smax[i];
+                if (oct == n_oct - 1 && 3 * m < mblk) o[2 * m] = smax[i];
             }
         }
     };
-    if (CHAIN) { p2p_phase_sync(); first_patch(); }
+    if (CHAIN) p2p_phase_sync();      // (the conv before this one is done with the staging slabs the fragments go over)
+    if (OUT_SEMI && threadIdx.x < kP2pSemiFrags) sfl[threadIdx.x] = sfrag_mine;   // read behind the second tile's barrier at the earliest
+    if (CHAIN) first_patch();
     // The upper half of the waves runs its epilogue one barrier late (the accumulators wait in registers): each SIMD holds as many
     // waves of either half, so one half's epilogue, loads and stores issue under the other half's MFMAs instead of all waves
     // leaving the matrix pipe idle together
@@ -1212,23 +1282,51 @@ __device__ __forceinline__ void p2p_ps_tiles(const P2pPsArgs& a, const int first
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) { acc[mt] = f32x4c{0.f, 0.f, 0.f, 0.f}; accl[mt] = f32x4c{0.f, 0.f, 0.f, 0.f}; }
     int cur = 0;
-    int unit = first, oct = 0, prev_oct = 0;
-    for (int tile = tile0; tile >= 0; cur ^= 1) {
-        int next, n_unit = unit, n_oct_i = oct;
-        if (OUT_FOLD) {
-            if (++n_oct_i == a.n_oct) { n_oct_i = 0; n_unit += step; }
-            next = n_unit < limit ? fold_tile(n_unit, n_oct_i) : -1;
-        } else next = tile + step < limit ? tile + step : -1;
+    int oct = 0, prev_oct = 0;
+    // The multiply loop is a software pipeline over the tile's 14 x MT A fragments f = (k-step, M-tile), in the order of their MFMAs:
+    // fragment f + MT is requested in front of the MFMA of fragment f, into the slot (f + MT) % NS that an earlier MFMA has been
+    // issued from, so that a fragment has MT MFMAs of this wave (and those of the SIMD's other waves) between its request and the wait in
+    // front of its use.  Every sched_barrier below holds a request where it is written: left alone, hipcc sinks an LDS read to one MFMA in
+    // front of its use, and the wave then stands for an LDS round trip (more than 120 cycles with 16 waves reading) per 16 - 48 cycles of
+    // matrix work.  The waits are the compiler's own counted lgkmcnt(n): LDS reads return in order.  The order of the products into each
+    // accumulator is ks ascending, as before.
+    f16x8c ah[NS];
+    for (; left > 0; cur ^= 1, --left) {
+        const int y0 = OUT_FOLD ? oct * oct_rows + g * R : g * R;
+        int n_clip = clip, n_g = g, n_oct_i = oct;
+        if (!OUT_FOLD || ++n_oct_i == n_oct) {                        // the next place of the walk
+            if (OUT_FOLD) n_oct_i = 0;
+            n_clip += step_q; n_g += step_r;
+            if (n_g >= per) { n_g -= per; ++n_clip; }
+        }
+        const int n_y0 = OUT_FOLD ? n_oct_i * oct_rows + n_g * R : n_g * R;
         // this wave's share of the tile's patch has landed (and its stores have left).  The builtin, not asm: hipcc then knows that
         // nothing of its own is pending at the loop top and places no vmcnt wait inside the loop that would also drain the LDS-DMA
         __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
         __syncthreads();              // ... every wave's; and every wave is done with the other half
-        const bool more = next >= 0;
-        if (has_prev) {
-            if (OUT_SEMI) semi_stage(cur ^ 1, prev_base, prev_mblk, prev_oct);
-            else if (late) epilogue(acc, accl, 0);
+        const bool more = left > 1;
+        lane_parts();
+        const uint4* const pH = lds4 + cur * plane_pos;
+        int ab[MT];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) { ab[mt] = abase[mt]; asm volatile("" : "+v"(ab[mt])); }    // (one register per M-tile, not one per form of the address)
+        auto request_a = [&](int f) {
+            const int ks = f / MT, mt = f - ks * MT, dy = ks >> 1, h = ks & 1;
+            ah[f % NS] = __builtin_bit_cast(f16x8c, pH[ab[mt] + dy * Tp + 4 * h]);
+        };
+        // the first k-step's fragments: behind the barrier (the patch is not published before it), in front of the vector work of the
+        // previous tile's last stage (behind that stage's own operands: together they do not fit the registers)
+        auto request_first = [&]() {
+#pragma unroll
+            for (int f = 0; f < MT; ++f) request_a(f);
+        };
+        if (OUT_SEMI && has_prev) semi_stage(cur ^ 1, prev_base, prev_mblk, prev_oct, request_first);
+        else {
+            if (has_prev && late) epilogue(acc, accl, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            request_first();
+            __builtin_amdgcn_sched_barrier(0);
         }
-        const uint4* const pH = lds4 + cur * a.plane_pos;
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) { acc[mt] = f32x4c{0.f, 0.f, 0.f, 0.f}; accl[mt] = f32x4c{0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll
@@ -1237,43 +1335,47 @@ __device__ __forceinline__ void p2p_ps_tiles(const P2pPsArgs& a, const int first
             // where both waves of a SIMD sit right after the barrier with the matrix pipe idle (-2 % per launch; switched off
             // altogether, loads and stores account for 11 + 15 us of a 128 us launch wherever they are placed -- see DESIGN.md)
             if (ks == 2 && more) {
-                if (IN_NCHW) load_regs(next);
-                else issue_loads(next, cur ^ 1);
+                if (IN_NCHW) load_regs(n_clip, n_y0);
+                else issue_loads(n_clip, n_y0, cur ^ 1);
             }
-            if (ks == 6 && !OUT_SEMI && has_prev) store_pending();
-            const int dy = ks >> 1, h = ks & 1;
+            // (the assembling loader holds its loads in registers from k-step 2 on: its stores leave before that, read a k-step ahead.
+            //  The plane-fed forms read and store at k-step 6: read a k-step ahead they spill, profiles/p2p_stack_operands.md)
+            constexpr int kStoreAt = IN_NCHW ? 1 : 6;
+            constexpr bool kSplit = IN_NCHW;
+            if (kSplit && ks == kStoreAt - 1 && !OUT_SEMI && has_prev) read_pending();
+            if (ks == kStoreAt && !OUT_SEMI && has_prev) { if (!kSplit) read_pending(); store_pending(); }
             const f16x8c bh = __builtin_bit_cast(f16x8c, breg[2 * ks]), bl = __builtin_bit_cast(f16x8c, breg[2 * ks + 1]);
-            f16x8c ah[MT];
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt) ah[mt] = __builtin_bit_cast(f16x8c, pH[abase[mt] + dy * Tp + 4 * h]);
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[mt], bh, acc[mt], 0, 0, 0);
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-                if (kP2pProducts == 2) accl[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[mt], bl, accl[mt], 0, 0, 0);
+            for (int mt = 0; mt < MT; ++mt) {
+                const int f = ks * MT + mt;
+                if (f + MT < 14 * MT) request_a(f + MT);
+                __builtin_amdgcn_sched_barrier(0);
+                acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[f % NS], bh, acc[mt], 0, 0, 0);
+                if (kP2pProducts == 2) accl[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[f % NS], bl, accl[mt], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
         }
         if (!late) epilogue(acc, accl, cur);
         if (IN_NCHW && more) write_lds(cur ^ 1);
         {
-            const int clip = tile / a.n_row_tiles;
-            const int y0 = (tile - clip * a.n_row_tiles) * a.R;
-            const int rows_here = a.H - y0 < a.R ? a.H - y0 : a.R;
+            const int rows_here = H - y0 < R ? H - y0 : R;
             prev_mblk = rows_here * J;
-            prev_base = OUT_CL ? static_cast<long long>(clip) * a.H * T + static_cast<long long>(y0) * T
-                      : OUT_FOLD ? clip * a.dst_clip_stride + static_cast<long long>((y0 % 36) / 3) * T
-                      : OUT_SEMI ? clip * a.dst_clip_stride + static_cast<long long>(y0 / 3) * T
-                                 : clip * a.dst_clip_stride + static_cast<long long>(y0) * T;
+            prev_base = OUT_CL ? static_cast<long long>(clip) * H * T + static_cast<long long>(y0) * T
+                      : OUT_FOLD ? clip * dst_clip_stride + static_cast<long long>((y0 % 36) / 3) * T
+                      : OUT_SEMI ? clip * dst_clip_stride + static_cast<long long>(y0 / 3) * T
+                                 : clip * dst_clip_stride + static_cast<long long>(y0) * T;
             prev_oct = oct;
         }
         has_prev = true;
-        tile = next; unit = n_unit; oct = n_oct_i;
+        clip = n_clip; g = n_g; oct = n_oct_i;
     }
     if (has_prev) {
         if (OUT_SEMI) {
             __syncthreads();          // every wave's share of the last tile is in the output patch
-            semi_stage(cur ^ 1, prev_base, prev_mblk, prev_oct);
+            semi_stage(cur ^ 1, prev_base, prev_mblk, prev_oct, []() {});
         } else {
             if (late) epilogue(acc, accl, 0);
+            read_pending();
             store_pending();
         }
     }
