@@ -18,7 +18,8 @@ from .pipeline import KeyAnnotations, KeyEstimator, KeyTrack, TrackScore, fit_ke
 from .keyprofile import fit_key_profiles, profile_emissions  # noqa: F401
 from .keychanges import key_changes  # noqa: F401
 from .synth import synth_partials  # noqa: F401
-from .tuning import StreamRetuner, estimate_tuning, retune, retune_out_len  # noqa: F401
+from .tuning import (StreamRetuner, estimate_tuning, retune, retune_curve, retune_curve_positions, retune_out_len,  # noqa: F401
+                     tuning_track)
 from .windows import TrackWindows, draw_windows, window_batch  # noqa: F401
 from .sequence import key_sequence_loss  # noqa: F401
 from .feeder import HostFeeder  # noqa: F401
@@ -29,6 +30,6 @@ __all__ = ["PitchClassNet", "KeyDataset", "DatasetLoader", "SyntheticSineMixLoad
            "transition_m_step", "fit_key_transition", "KEY_NAMES", "KeyEstimator", "KeyTrack", "Resampler", "get_resampler",
            "prepare_audio", "pcm16_to_float", "HostFeeder", "KeyAnnotations", "TrackScore", "track_score", "window_truth",
            "transition_from_labels", "synth_partials", "TrackWindows", "draw_windows", "window_batch", "window_labels", "weighted_general_step",
-           "estimate_tuning", "retune", "retune_out_len", "retune_reference",
+           "estimate_tuning", "retune", "retune_out_len", "retune_reference", "tuning_track", "retune_curve", "retune_curve_positions",
            "profile_emissions", "fit_key_profiles", "KEY_PROFILES", "key_sequence_loss",
            "key_stream", "KeyStream", "StreamUpdate", "key_stream_posteriors", "StreamResampler", "StreamRetuner", "key_changes"]

@@ -127,6 +127,13 @@ SYMBOLS = {
     "ake_stream_resample_pcm16_f32": (_I, [_P, _P, _I, _I, _I64, _I64, _I64, _I64, _I, _I64, _I, _P, _SZ, _P, _I64, C.POINTER(_I64), _P]),
     "ake_tuning_workspace_bytes": (_SZ, [_I, _I]),
     "ake_tuning_estimate_f32": (_I, [_P, _I, _I, _I, _I, _P, C.c_float, _P, _P, _P, _SZ, _P]),
+    "ake_tuning_track_windows": (_I, [_I, _I, _I]),
+    "ake_tuning_track_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "ake_tuning_track_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, C.c_float, _P, _P, _P, _P, _P, _SZ, _P]),
+    "ake_retune_curve_workspace_bytes": (_SZ, [_I, _I]),
+    "ake_retune_curve_f32": (_I, [_P, _I, _I64, _I64, _P, _P, _I, _I64, _I64, _I64, _P, _I64, _P, _P, _SZ, _P]),
+    "ake_retune_curve_pcm16_f32": (_I, [_P, _I, _I64, _I64, _P, _P, _I, _I64, _I64, _I64, _P, _I64, _P, _P, _SZ, _P]),
+    "ake_retune_curve_positions": (_I, [_P, _I, _I, _I64, _I64, _I64, _P, _I64, _P, _P, _SZ, _P]),
     "ake_retune_out_len": (_I64, [_I64]),
     "ake_retune_f32": (_I, [_P, _I, _I64, _I64, _P, _P, _P, _I64, _P, _P]),
     "ake_retune_pcm16_f32": (_I, [_P, _I, _I64, _I64, _P, _P, _P, _I64, _P, _P]),

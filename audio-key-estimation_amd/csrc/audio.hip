@@ -175,15 +175,13 @@ __device__ __forceinline__ double retune_ratio(float cents) {
          : cents <= -static_cast<float>(kRetuneMaxCents) ? 1.0 / kRetuneMaxRatio : exp2(static_cast<double>(cents) / 1200.0);
 }
 
-// Output sample k of a row: G the filter table and X the staged input stretch, both in LDS, X[j - j_base] = x[j] (zeros outside the row).
-__device__ __forceinline__ float retune_output(long long k, double inv, const float* G, const float* X, long long j_base) {
-    // the read position in double; only its fraction is rounded to float32, so the error does not grow with k
-    const double pos = static_cast<double>(k) * inv, j0d = floor(pos);
-    const float fr = static_cast<float>(pos - j0d) * kRetuneRes;
+// The 64 taps of one output sample: xs[m] = x[j0 + m], m = -Z + 1 .. Z, in LDS, and `fraction` in [0, 1) the read position behind j0.
+// Shared by every retuner here (one ratio per row, a curve, chunks).
+__device__ __forceinline__ float retune_taps(const float* xs, float fraction, const float* G) {
+    const float fr = fraction * kRetuneRes;
     int r = static_cast<int>(fr);
     r = r < kRetuneRes - 1 ? r : kRetuneRes - 1;
     const float t = fr - static_cast<float>(r);
-    const float* xs = X + (static_cast<long long>(j0d) - j_base);     // xs[m] = x[j0 + m], m = -Z + 1 .. Z
     float acc = 0.f;
     int q = r + (kRetuneZeros - 1) * kRetuneRes;
 #pragma unroll 8
@@ -194,6 +192,13 @@ __device__ __forceinline__ float retune_output(long long k, double inv, const fl
     for (int m = 1; m <= kRetuneZeros; ++m, q += kRetuneRes)         // d < 0: h(-d), read downwards
         acc = fmaf(xs[m], fmaf(t, G[q] - G[q + 1], G[q + 1]), acc);
     return acc;
+}
+
+// Output sample k of a row: G the filter table and X the staged input stretch, both in LDS, X[j - j_base] = x[j] (zeros outside the row).
+__device__ __forceinline__ float retune_output(long long k, double inv, const float* G, const float* X, long long j_base) {
+    // the read position in double; only its fraction is rounded to float32, so the error does not grow with k
+    const double pos = static_cast<double>(k) * inv, j0d = floor(pos);
+    return retune_taps(X + (static_cast<long long>(j0d) - j_base), static_cast<float>(pos - j0d), G);
 }
 
 template <typename T>
@@ -284,6 +289,259 @@ int retune_launch(const char* name, const T* in_dev, int batch, int64_t n_max, i
     hipStream_t s = static_cast<hipStream_t>(stream);
     constexpr int per_block = kRetuneTile * kRetuneTiles;
     return ake::launch(name, retune_kernel<T>, dim3(static_cast<unsigned>((width + per_block - 1) / per_block), batch), dim3(kRetuneThreads), 0, s, a);
+}
+
+// ---- retuning along a curve: a ratio that is piecewise linear in the input position (ake_retune_curve_*) ----
+// Knot i of a row sits at input sample p_i = knot_first + i knot_step and carries rho_i = retune_ratio(retune_clamped(cents[i])); rho is
+// rho_0 in front of the first knot, rho_{K-1} behind the last and linear in p between two.  The output index of input position p is
+// K(p) = integral of rho, piecewise quadratic: K_0 = rho_0 p_0, K_{i+1} = K_i + knot_step (rho_i + rho_{i+1}) / 2, and inside segment i
+// K(p) = K_i + rho_i u + (rho_{i+1} - rho_i) u^2 / (2 knot_step), u = p - p_i.  Output k reads the position K^{-1}(k).
+//   retune_curve_prefix_kernel: a workgroup per row writes rho_i, then one thread adds K_i in ascending i (double), the row's
+//     n_out = floor(K(n)) and whether all its cents are 0 (such a row is copied) into the workspace.
+//   retune_curve_kernel: retune_kernel's tiling, staging and taps (retune_taps).  How a tile finds its segments: every thread runs
+//     the same binary search of the workspace for the segment of the tile's first output (uniform addresses, one search a tile), the
+//     knots from there on are staged in LDS -- a tile of kRetuneTile outputs spans at most kRetuneTile / (64 / kRetuneMaxRatio) + 2 =
+//     35 of them since knot_step >= 64 -- and every output searches those (six LDS reads).  The inverse inside a segment is the root
+//     form u = 2 c / (rho_s + sqrt(rho_s^2 + 4 a c)), stable at a = 0; a sqrt and a division in double per output are the new work.
+// The read position stays the integer p_s + floor(u) and the fraction u - floor(u): only the fraction is rounded to float32.
+constexpr int kCurveKnots = 40;                                   // knots a tile stages
+constexpr int kCurveMinStep = 64;
+static_assert(kRetuneTile * kRetuneMaxRatio / kCurveMinStep + 3 <= kCurveKnots, "curve knots per tile");
+
+// Where output k reads: -> the integer sample j0 and the fraction behind it.  kp / rh: K_i and rho_i of the `cnt` knots from knot
+// `s_lo` on (LDS, or the workspace itself with s_lo = 0), kp[0] <= k unless s_lo == 0; rho_row: all the row's ratios (global).
+__device__ __forceinline__ void retune_curve_read(long long k, const double* kp, const double* rh, int cnt, int s_lo, int knots,
+                                                  long long knot_first, long long knot_step, const double* rho_row, long long* j0,
+                                                  double* fraction) {
+    const double kd = static_cast<double>(k);
+    double u;
+    long long base = 0;
+    if (kd < kp[0]) {                                             // in front of the first knot
+        u = kd / rh[0];
+    } else {
+        int lo = 0, hi = cnt;                                     // the last e with kp[e] <= k
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (kp[mid] <= kd) lo = mid; else hi = mid;
+        }
+        const int s = s_lo + lo;
+        const double c = kd - kp[lo], r0 = rh[lo];
+        base = knot_first + s * knot_step;
+        if (s == knots - 1) {                                     // behind the last knot
+            u = c / r0;
+        } else {
+            const double r1 = lo + 1 < cnt ? rh[lo + 1] : rho_row[s + 1];
+            const double a = (r1 - r0) / (2.0 * static_cast<double>(knot_step));
+            u = 2.0 * c / (r0 + sqrt(r0 * r0 + 4.0 * a * c));
+        }
+    }
+    const double fl = floor(u);
+    *j0 = base + static_cast<long long>(fl);
+    *fraction = u - fl;
+}
+
+struct RetuneCurveKnots {
+    const float* cents;         // [batch][cents_stride]
+    long long cents_stride;
+    int knots;
+    long long knot_first, knot_step;
+    double* rho;                // workspace: [batch][knots]
+    double* kpos;               // workspace: [batch][knots]
+    long long* meta;            // workspace: [batch][2]: n_out, copy
+};
+
+struct RetuneCurvePrefixArgs {
+    RetuneCurveKnots c;
+    long long n_max, width;
+    const long long* n_in;      // or null
+    long long* n_out;           // [batch], or null
+};
+
+__global__ __launch_bounds__(64) void retune_curve_prefix_kernel(RetuneCurvePrefixArgs a) {
+    __shared__ int any_shared;
+    const int row = blockIdx.x, tid = threadIdx.x, K = a.c.knots;
+    const float* cents = a.c.cents + row * a.c.cents_stride;
+    double* rho = a.c.rho + static_cast<long long>(row) * K;
+    double* kpos = a.c.kpos + static_cast<long long>(row) * K;
+    if (tid == 0) any_shared = 0;
+    __syncthreads();
+    int any = 0;
+    for (int i = tid; i < K; i += 64) {
+        const float c = retune_clamped(cents[i]);
+        any |= c != 0.f;
+        rho[i] = retune_ratio(c);
+    }
+    if (any) any_shared = 1;                                      // (every writer writes the same value)
+    __syncthreads();
+    if (tid != 0) return;
+    const double step = static_cast<double>(a.c.knot_step);
+    double acc = rho[0] * static_cast<double>(a.c.knot_first);
+    kpos[0] = acc;
+    for (int i = 1; i < K; ++i) {                                 // ascending i
+        acc += step * (rho[i - 1] + rho[i]) / 2.0;
+        kpos[i] = acc;
+    }
+    long long n = a.n_max;
+    if (a.n_in) { const long long nc = a.n_in[row]; n = nc < 0 ? 0 : (nc < n ? nc : n); }
+    const bool copy = !any_shared;
+    long long n_out = n;
+    if (!copy) {                                                  // floor(K(n))
+        double kn;
+        if (n <= a.c.knot_first) {
+            kn = rho[0] * static_cast<double>(n);
+        } else {
+            long long i = (n - a.c.knot_first) / a.c.knot_step;
+            i = i < K - 1 ? i : K - 1;
+            const double u = static_cast<double>(n - (a.c.knot_first + i * a.c.knot_step));
+            kn = i == K - 1 ? kpos[i] + rho[i] * u : kpos[i] + rho[i] * u + (rho[i + 1] - rho[i]) * u * u / (2.0 * step);
+        }
+        n_out = static_cast<long long>(floor(kn));
+    }
+    n_out = n_out < a.width ? n_out : a.width - 1;                // (rho <= the literal everywhere; a guard all the same, as in retune_kernel)
+    a.c.meta[row * 2ll] = n_out;
+    a.c.meta[row * 2ll + 1] = copy ? 1 : 0;
+    if (a.n_out) a.n_out[row] = n_out;
+}
+
+template <typename T>
+struct RetuneCurveArgs {
+    const T* in;
+    long long in_stride, n_max;
+    const long long* n_in;
+    RetuneCurveKnots c;
+    float* out;
+    long long out_stride, width;
+};
+
+template <typename T>
+__global__ __launch_bounds__(kRetuneThreads) void retune_curve_kernel(RetuneCurveArgs<T> a) {
+    __shared__ float G[kRetuneTable + 1];
+    __shared__ float X[kRetuneStretch];
+    __shared__ double SK[kCurveKnots], SR[kCurveKnots];
+    const int row = blockIdx.y, tid = threadIdx.x, K = a.c.knots;
+    long long n = a.n_max;
+    if (a.n_in) { const long long nc = a.n_in[row]; n = nc < 0 ? 0 : (nc < n ? nc : n); }
+    const long long n_out = a.c.meta[row * 2ll];
+    const bool copy = a.c.meta[row * 2ll + 1] != 0;
+    const double* rho = a.c.rho + static_cast<long long>(row) * K;
+    const double* kpos = a.c.kpos + static_cast<long long>(row) * K;
+    const T* x = a.in + row * a.in_stride;
+    float* y = a.out + row * a.out_stride;
+    const long long k_first = static_cast<long long>(blockIdx.x) * (kRetuneTile * kRetuneTiles);
+    const bool filter = !copy && k_first < n_out;                 // (uniform over the workgroup)
+    if (filter)
+        for (int i = tid; i < kRetuneTable + 1; i += kRetuneThreads) G[i] = g_retune_table[i];
+    for (int tile = 0; tile < kRetuneTiles; ++tile) {
+        const long long k0 = k_first + static_cast<long long>(tile) * kRetuneTile;
+        if (k0 >= a.width) break;
+        if (copy || k0 >= n_out) {                                // a row that is not retuned, or the zeros behind a row's end
+            for (int i = tid; i < kRetuneTile; i += kRetuneThreads) {
+                const long long k = k0 + i;
+                if (k < a.width) y[k] = k < n_out ? retune_sample<T>(x[k]) : 0.f;
+            }
+            continue;
+        }
+        // the tile's knots: from the last one at or in front of its first output (from knot 0 in front of them all)
+        int lo = 0, hi = K;
+        const double kd0 = static_cast<double>(k0);
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (kpos[mid] <= kd0) lo = mid; else hi = mid;
+        }
+        const int s_lo = lo, cnt = K - s_lo < kCurveKnots ? K - s_lo : kCurveKnots;
+        __syncthreads();                                          // (the last tile's reads of X, SK and SR are done)
+        if (tid < cnt) { SK[tid] = kpos[s_lo + tid]; SR[tid] = rho[s_lo + tid]; }
+        __syncthreads();
+        // the tile's input stretch: sample j of the row at X[j - j_base], zeros outside [0, n)
+        long long j_first;
+        double fraction;
+        retune_curve_read(k0, SK, SR, cnt, s_lo, K, a.c.knot_first, a.c.knot_step, rho, &j_first, &fraction);
+        const long long j_base = j_first - kRetuneZeros + 1;
+        for (int i = tid; i < kRetuneStretch; i += kRetuneThreads) {
+            const long long j = j_base + i;
+            X[i] = (j >= 0 && j < n) ? retune_sample<T>(x[j]) : 0.f;
+        }
+        __syncthreads();
+        for (int i = tid; i < kRetuneTile; i += kRetuneThreads) {
+            const long long k = k0 + i;
+            if (k >= a.width) break;
+            if (k >= n_out) { y[k] = 0.f; continue; }
+            long long j0;
+            retune_curve_read(k, SK, SR, cnt, s_lo, K, a.c.knot_first, a.c.knot_step, rho, &j0, &fraction);
+            long long off = j0 - j_base;                          // Z - 1 .. kRetuneStretch - Z - 1 by the bound on rho; held there all the same
+            off = off < kRetuneZeros - 1 ? kRetuneZeros - 1 : (off > kRetuneStretch - kRetuneZeros - 1 ? kRetuneStretch - kRetuneZeros - 1 : off);
+            y[k] = retune_taps(X + off, static_cast<float>(fraction), G);
+        }
+    }
+}
+
+struct RetuneCurvePositionsArgs {
+    RetuneCurveKnots c;
+    const long long* index;     // [batch][m]
+    double* positions;          // [batch][m]
+    long long m;
+};
+
+__global__ __launch_bounds__(256) void retune_curve_positions_kernel(RetuneCurvePositionsArgs a) {
+    const int row = blockIdx.y, K = a.c.knots;
+    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= a.m) return;
+    const double* rho = a.c.rho + static_cast<long long>(row) * K;
+    const double* kpos = a.c.kpos + static_cast<long long>(row) * K;
+    long long j0;
+    double fraction;
+    retune_curve_read(a.index[row * a.m + i], kpos, rho, K, 0, K, a.c.knot_first, a.c.knot_step, rho, &j0, &fraction);
+    a.positions[row * a.m + i] = static_cast<double>(j0) + fraction;
+}
+
+constexpr int kCurveMaxKnots = 1 << 22;
+constexpr long long kCurveMaxStep = 1ll << 32;
+
+bool retune_curve_shape_ok(int batch, int knots) { return batch > 0 && batch <= 65535 && knots >= 1 && knots <= kCurveMaxKnots; }
+
+// The checks every curve entry point shares, and the carve-up of the workspace.
+int retune_curve_knots(const char* name, const float* cents_dev, int batch, int knots, int64_t cents_stride, int64_t knot_first, int64_t knot_step,
+                       void* workspace, size_t workspace_bytes, RetuneCurveKnots* c) {
+    AKE_REQUIRE(cents_dev, AKE_ERR_INVALID, "%s: null argument", name);
+    AKE_REQUIRE(batch > 0 && batch <= 65535, AKE_ERR_INVALID, "%s: bad batch %d", name, batch);
+    AKE_REQUIRE(knots >= 1 && knots <= kCurveMaxKnots, AKE_ERR_INVALID, "%s: %d knots; a curve has 1..%d", name, knots, kCurveMaxKnots);
+    AKE_REQUIRE(knot_step >= kCurveMinStep && knot_step <= kCurveMaxStep, AKE_ERR_INVALID, "%s: knot_step %lld; the knots lie %d..2^32 samples apart",
+                name, static_cast<long long>(knot_step), kCurveMinStep);
+    AKE_REQUIRE(knot_first >= 0 && knot_first <= (1ll << 40), AKE_ERR_INVALID, "%s: knot_first %lld lies outside 0..2^40", name,
+                static_cast<long long>(knot_first));
+    AKE_REQUIRE(cents_stride >= knots, AKE_ERR_INVALID, "%s: row stride %lld < %d knots", name, static_cast<long long>(cents_stride), knots);
+    const size_t need = ake_retune_curve_workspace_bytes(batch, knots);
+    AKE_REQUIRE(workspace && workspace_bytes >= need, AKE_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", name, workspace_bytes, need);
+    AKE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, AKE_ERR_INVALID, "%s: the workspace must be 8-byte aligned", name);
+    double* rho = static_cast<double*>(workspace);
+    double* kpos = rho + static_cast<size_t>(batch) * knots;
+    *c = RetuneCurveKnots{cents_dev, cents_stride, knots, knot_first, knot_step, rho, kpos,
+                          reinterpret_cast<long long*>(kpos + static_cast<size_t>(batch) * knots)};
+    return AKE_OK;
+}
+
+template <typename T>
+int retune_curve_launch(const char* name, const T* in_dev, int batch, int64_t n_max, int64_t in_stride, const int64_t* n_in_dev, const float* cents_dev,
+                        int knots, int64_t cents_stride, int64_t knot_first, int64_t knot_step, float* out_dev, int64_t out_stride,
+                        int64_t* n_out_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream) {
+    AKE_REQUIRE(in_dev && cents_dev && out_dev, AKE_ERR_INVALID, "%s: null argument", name);
+    AKE_REQUIRE(batch > 0 && batch <= 65535 && n_max >= 0 && n_max <= (1ll << 40), AKE_ERR_INVALID, "%s: bad batch %d / n_max %lld", name, batch,
+                static_cast<long long>(n_max));
+    const int64_t width = ake_retune_out_len(n_max);
+    AKE_REQUIRE(in_stride >= n_max && out_stride >= width, AKE_ERR_INVALID, "%s: row strides %lld, %lld < %lld input, %lld output samples", name,
+                static_cast<long long>(in_stride), static_cast<long long>(out_stride), static_cast<long long>(n_max), static_cast<long long>(width));
+    RetuneCurveKnots c;
+    int rc = retune_curve_knots(name, cents_dev, batch, knots, cents_stride, knot_first, knot_step, workspace, workspace_bytes, &c);
+    if (rc) return rc;
+    rc = retune_table_upload();
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RetuneCurvePrefixArgs p{c, n_max, width, reinterpret_cast<const long long*>(n_in_dev), reinterpret_cast<long long*>(n_out_dev)};
+    rc = ake::launch("retune_curve_prefix_kernel", retune_curve_prefix_kernel, dim3(batch), dim3(64), 0, s, p);
+    if (rc) return rc;
+    RetuneCurveArgs<T> a{in_dev, in_stride, n_max, reinterpret_cast<const long long*>(n_in_dev), c, out_dev, out_stride, width};
+    constexpr int per_block = kRetuneTile * kRetuneTiles;
+    return ake::launch(name, retune_curve_kernel<T>, dim3(static_cast<unsigned>((width + per_block - 1) / per_block), batch), dim3(kRetuneThreads), 0, s, a);
 }
 
 // ---- the polyphase resampler on audio that arrives in chunks (ake_stream_resample_*) ----
@@ -671,6 +929,44 @@ int ake_retune_pcm16_f32(const int16_t* in_dev, int batch, int64_t n_max, int64_
                          float* out_dev, int64_t out_stride, int64_t* lengths_out_dev, ake_stream_t stream) {
     return retune_launch<short>("retune_pcm16_kernel", reinterpret_cast<const short*>(in_dev), batch, n_max, in_stride, lengths_dev, cents_dev,
                                 out_dev, out_stride, lengths_out_dev, stream);
+}
+
+size_t ake_retune_curve_workspace_bytes(int batch, int knots) {
+    if (!retune_curve_shape_ok(batch, knots)) return 0;
+    return ake::align_up((static_cast<size_t>(batch) * knots * 2 + static_cast<size_t>(batch) * 2) * sizeof(double), 256);
+}
+
+int ake_retune_curve_f32(const float* in_dev, int batch, int64_t n_max, int64_t in_stride, const int64_t* lengths_dev, const float* cents_dev,
+                         int knots, int64_t cents_stride, int64_t knot_first, int64_t knot_step, float* out_dev, int64_t out_stride,
+                         int64_t* lengths_out_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream) {
+    return retune_curve_launch<float>("retune_curve_kernel", in_dev, batch, n_max, in_stride, lengths_dev, cents_dev, knots, cents_stride, knot_first,
+                                      knot_step, out_dev, out_stride, lengths_out_dev, workspace, workspace_bytes, stream);
+}
+
+int ake_retune_curve_pcm16_f32(const int16_t* in_dev, int batch, int64_t n_max, int64_t in_stride, const int64_t* lengths_dev,
+                               const float* cents_dev, int knots, int64_t cents_stride, int64_t knot_first, int64_t knot_step, float* out_dev,
+                               int64_t out_stride, int64_t* lengths_out_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream) {
+    return retune_curve_launch<short>("retune_curve_pcm16_kernel", reinterpret_cast<const short*>(in_dev), batch, n_max, in_stride, lengths_dev,
+                                      cents_dev, knots, cents_stride, knot_first, knot_step, out_dev, out_stride, lengths_out_dev, workspace,
+                                      workspace_bytes, stream);
+}
+
+int ake_retune_curve_positions(const float* cents_dev, int batch, int knots, int64_t cents_stride, int64_t knot_first, int64_t knot_step,
+                               const int64_t* out_index_dev, int64_t m, double* positions_dev, void* workspace, size_t workspace_bytes,
+                               ake_stream_t stream) {
+    const char* name = "ake_retune_curve_positions";
+    AKE_REQUIRE(out_index_dev && positions_dev, AKE_ERR_INVALID, "%s: null argument", name);
+    AKE_REQUIRE(m >= 1 && m <= (1ll << 31), AKE_ERR_INVALID, "%s: %lld indices a row; 1..2^31", name, static_cast<long long>(m));
+    RetuneCurveKnots c;
+    int rc = retune_curve_knots(name, cents_dev, batch, knots, cents_stride, knot_first, knot_step, workspace, workspace_bytes, &c);
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RetuneCurvePrefixArgs p{c, 0, 1, nullptr, nullptr};
+    rc = ake::launch("retune_curve_prefix_kernel", retune_curve_prefix_kernel, dim3(batch), dim3(64), 0, s, p);
+    if (rc) return rc;
+    RetuneCurvePositionsArgs a{c, reinterpret_cast<const long long*>(out_index_dev), positions_dev, m};
+    return ake::launch("retune_curve_positions_kernel", retune_curve_positions_kernel, dim3(static_cast<unsigned>((m + 255) / 256), batch), dim3(256), 0,
+                       s, a);
 }
 
 int ake_retune_ratio(float cents, double* rho_out, ake_stream_t stream) {

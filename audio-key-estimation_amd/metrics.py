@@ -6,6 +6,8 @@ at once on whatever device the predictions live on (no per-sample table upload, 
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 
@@ -1050,6 +1052,204 @@ def retune_reference(x, cents, lengths=None):
                 q = m * R - r - 1
                 w = G[q + 1] + t * (G[q] - G[q + 1])
             acc += xp[j0 + m + Z] * w
+        y[b, :no] = acc
+    return (y[0], int(n_out[0])) if single else (y, n_out)
+
+
+# ---- a tuning that drifts: the estimate over sliding windows and a retuner that follows a curve (ake_tuning_track_f32 / ake_retune_curve_f32) ----
+
+def tuning_track_windows(frames, window_frames, stride_frames):
+    """Windows of a recording of ``frames`` frames: ``1 + (frames - wf) // sf`` from ``wf`` frames on, one window over all of a shorter
+    recording, none of an empty one (``ake_tuning_track_windows``)."""
+    T, wf, sf = int(frames), int(window_frames), int(stride_frames)
+    if wf < 1 or sf < 1:
+        raise ValueError(f"tuning_track: windows of {wf} frames, {sf} apart; both must be at least 1")
+    return 0 if T <= 0 else 1 if T < wf else 1 + (T - wf) // sf
+
+
+def tuning_track(logmag, window_frames, stride_frames, counts=None, min_strength=0.0):
+    """The detuning of B recordings over time from their log-CQT (B, n_bins, T) -> ``(cents_raw, strength, curve, window_counts)``:
+    float64 (B, W) three times and int32 (B,), the float64 model of ``ake_tuning_track_f32``.
+
+    Recording i has ``T_i = counts[i]`` frames (default T) and ``W_i = tuning_track_windows(T_i, ...)`` windows; window w covers the frames
+    ``[w * sf, min(w * sf + wf, T_i))``; ``W = tuning_track_windows(T, ...)``.  ``cents_raw`` and ``strength`` are ``estimate_tuning`` on
+    each window's frames (``min_strength`` not applied), 0 in the columns ``>= W_i``.  ``curve`` is what a retuner follows
+    (``retune_curve_reference``), made per recording in window order: a window with ``strength < min_strength`` takes the value of the
+    nearest earlier window that is strong (the leading ones the first strong window's; 0 everywhere if none is); then each value ``v``
+    becomes ``v + 100 * floor((before - v) / 100 + 0.5)``, within 50 of the unwrapped value ``before`` it; then it is clamped to +-50, so a
+    drift that leaves the semitone saturates instead of jumping; columns ``>= W_i`` repeat the last valid value."""
+    L = torch.as_tensor(logmag).detach().to(torch.float64)
+    if L.dim() != 3 or L.shape[1] % TUNING_BINS_PER_SEMITONE != 0:
+        raise ValueError(f"tuning_track: logmag must be (B, n_bins, T) with n_bins a multiple of 3, got {tuple(L.shape)}")
+    B, P, T = L.shape
+    wf, sf = int(window_frames), int(stride_frames)
+    W = tuning_track_windows(T, wf, sf)
+    power = torch.expm1(L) ** 2
+    if counts is None:
+        frames = [T] * B
+    else:
+        power = torch.where(_behind_count(counts, B, T, L.device)[:, None, :], torch.zeros_like(power), power)
+        frames = torch.as_tensor(counts).reshape(B).clamp(0, T).tolist()
+    n_win = [tuning_track_windows(t, wf, sf) for t in frames]
+    cents = torch.zeros((B, W), dtype=torch.float64)
+    strength = torch.zeros((B, W), dtype=torch.float64)
+    for w in range(W):
+        f0, f1 = w * sf, min(w * sf + wf, T)
+        c, s = _tuning_finish(*(power[:, j::3, f0:f1].sum(dim=(1, 2)) for j in range(3)), 0.0)
+        cents[:, w], strength[:, w] = c.cpu(), s.cpu()
+    live = torch.arange(W)[None, :] < torch.tensor(n_win)[:, None]
+    cents, strength = torch.where(live, cents, torch.zeros_like(cents)), torch.where(live, strength, torch.zeros_like(strength))
+    curve = torch.zeros((B, W), dtype=torch.float64)
+    for b in range(B):
+        raw, strong = cents[b].tolist(), (strength[b, :n_win[b]] >= float(min_strength)).tolist()
+        if True not in strong:
+            continue
+        held = before = raw[strong.index(True)]
+        last = 0.0
+        for w in range(W):
+            if w < n_win[b]:
+                if strong[w]:
+                    held = raw[w]
+                before = held + 100.0 * math.floor((before - held) / 100.0 + 0.5)
+                last = min(max(before, -RETUNE_MAX_CENTS), RETUNE_MAX_CENTS)
+            curve[b, w] = last
+    return cents, strength, curve, torch.tensor(n_win, dtype=torch.int32)
+
+
+def _retune_curve_knots(cents, knot_first, knot_step):
+    """``cents`` (K,) or (B, K), read as the kernel reads them -> ``(rho, kpos)`` float64 (B, K) on the device of ``cents``: the ratio
+    at every knot and the output index ``K_i`` of every knot's input sample."""
+    c = torch.as_tensor(cents).detach().to(torch.float32)
+    c = c[None] if c.dim() == 1 else c
+    if c.dim() != 2 or c.shape[1] < 1:
+        raise ValueError(f"a tuning curve is (K,) or (B, K) with K >= 1, got {tuple(c.shape)}")
+    if int(knot_first) < 0 or int(knot_step) < 1:
+        raise ValueError(f"a tuning curve's knots start at a sample >= 0 and lie >= 1 apart, got {knot_first}, {knot_step}")
+    c = torch.where(torch.isnan(c), torch.zeros_like(c), c).clamp(-RETUNE_MAX_CENTS, RETUNE_MAX_CENTS).to(torch.float64)
+    rho = torch.exp2(c / 1200.0)
+    # (at the clamp the ratio is the literal, as in retune_reference)
+    rho = torch.where(c >= RETUNE_MAX_CENTS, torch.full_like(rho, RETUNE_MAX_RATIO), rho)
+    rho = torch.where(c <= -RETUNE_MAX_CENTS, torch.full_like(rho, 1.0 / RETUNE_MAX_RATIO), rho)
+    inc = float(knot_step) * (rho[:, :-1] + rho[:, 1:]) / 2.0
+    kpos = torch.cumsum(torch.cat([rho[:, :1] * float(knot_first), inc], dim=1), dim=1)
+    return rho, kpos
+
+
+def _curve_rows(v, rows, dtype=torch.float64):
+    v = torch.as_tensor(v).to(dtype)
+    single = v.dim() <= 1
+    v = v.reshape(1, -1) if single else v
+    return (v.expand(rows, -1) if v.shape[0] == 1 else v), single and rows == 1
+
+
+def retune_curve_forward(p, cents, knot_first, knot_step):
+    """``K(p)``: where input position ``p`` (samples; (m,) or (B, m), float64) of a recording lands in its copy retuned along a curve ->
+    float64 of ``p``'s shape ((B, m) for a (B, K) curve), torch ops on the device of ``cents``.
+
+    ``cents`` (K,) or (B, K): knot i sits at ``p_i = knot_first + i * knot_step`` with ``rho_i = 2 ** (cents_i / 1200)`` (rounded to
+    float32, NaN read as 0, clamped to +-50, as the kernel reads them); ``rho`` is ``rho_0`` in front of the first knot, ``rho_{K-1}``
+    behind the last, linear in between, and ``K`` is its integral: ``rho_0 p`` in front; ``K_0 = rho_0 p_0``,
+    ``K_{i+1} = K_i + knot_step (rho_i + rho_{i+1}) / 2``; ``K_i + rho_i u + (rho_{i+1} - rho_i) u ** 2 / (2 knot_step)`` with
+    ``u = p - p_i`` inside segment i."""
+    rho, kpos = _retune_curve_knots(cents, knot_first, knot_step)
+    B, K = rho.shape
+    p, single = _curve_rows(torch.as_tensor(p).to(rho.device), B)
+    first, step = float(knot_first), float(knot_step)
+    i = torch.floor((p - first) / step).clamp(0, K - 1).to(torch.int64)
+    u = p - (first + i.to(torch.float64) * step)
+    r0, r1, k0 = rho.gather(1, i), rho.gather(1, (i + 1).clamp(max=K - 1)), kpos.gather(1, i)
+    out = torch.where(p < first, rho[:, :1] * p, k0 + r0 * u + (r1 - r0) * u * u / (2.0 * step))
+    return out[0] if single else out
+
+
+def curve_boundaries(seg_start, cents, knot_first, knot_step):
+    """Annotation boundaries int64 (R, S) in samples of the recording -> in samples of the recording retuned along the curve ``cents``
+    (R, K): ``floor(K(start))`` (``retune_curve_forward``) as float64 torch ops on the boundaries' device; INT64_MAX (no segment) stays.
+    ``scale_boundaries`` for a followed track."""
+    start = seg_start.to(torch.int64)
+    cents = torch.as_tensor(cents).to(start.device)
+    if cents.dim() != 2 or cents.shape[0] != start.shape[0]:
+        raise ValueError(f"curve_boundaries: {start.shape[0]} recordings but curves of shape {tuple(cents.shape)}")
+    none = start == _I64_MAX
+    moved = retune_curve_forward(torch.where(none, torch.zeros_like(start), start).to(torch.float64), cents, knot_first, knot_step)
+    return torch.where(none, start, torch.floor(moved).to(torch.int64))
+
+
+def _retune_curve_read(k, rho, kpos, knot_first, knot_step):
+    """Output indices ``k`` (B, m) float64 -> ``(j0 int64, fraction float64)``: the read position ``K^{-1}(k)`` as the kernel keeps it."""
+    K = rho.shape[1]
+    s = torch.searchsorted(kpos, k.contiguous(), right=True) - 1                     # the last segment with K_s <= k
+    front = s < 0
+    s = s.clamp_min(0)
+    r0, r1 = rho.gather(1, s), rho.gather(1, (s + 1).clamp(max=K - 1))                # (behind the last knot a = 0: u = c / rho)
+    c = k - kpos.gather(1, s)
+    a = (r1 - r0) / (2.0 * float(knot_step))
+    u = torch.where(front, k / rho[:, :1], 2.0 * c / (r0 + torch.sqrt(r0 * r0 + 4.0 * a * c)))
+    base = torch.where(front, torch.zeros_like(s), int(knot_first) + s * int(knot_step))
+    fl = torch.floor(u)
+    return base + fl.to(torch.int64), u - fl
+
+
+def retune_curve_positions(k, cents, knot_first, knot_step):
+    """The inverse of ``retune_curve_forward``: the input position that output index ``k`` ((m,) or (B, m)) reads -> float64.  With s
+    the last segment with ``K_s <= k``, ``c = k - K_s`` and ``a = (rho_{s+1} - rho_s) / (2 knot_step)``:
+    ``p_s + 2 c / (rho_s + sqrt(rho_s ** 2 + 4 a c))``; ``k / rho_0`` in front of the first knot; ``p_{K-1} + c / rho_{K-1}`` behind the
+    last (the float64 model of ``ake_retune_curve_positions``)."""
+    rho, kpos = _retune_curve_knots(cents, knot_first, knot_step)
+    k, single = _curve_rows(torch.as_tensor(k).to(rho.device), rho.shape[0])
+    j0, fr = _retune_curve_read(k, rho, kpos, knot_first, knot_step)
+    out = j0.to(torch.float64) + fr
+    return out[0] if single else out
+
+
+def retune_curve_reference(x, cents, knot_first, knot_step, lengths=None):
+    """Varispeed resampling along a tuning curve: the float64 model of ``ake_retune_curve_f32`` -> ``(y, n_out)``, numpy.
+
+    ``x`` (B, n) or (n,); ``cents`` (B, K) or (K,) (one curve for every row) with its knots as in ``retune_curve_forward``; ``lengths``
+    as in ``retune_reference``.  ``n_out = floor(K(n_i))`` and ``y[k] = sum_j x[j] h(K^{-1}(k) - j)`` with ``retune_reference``'s ``h``,
+    table, blend and tap order: the read position is kept as an integer sample and a fraction (``retune_curve_positions``), and the
+    fraction is rounded to float32.  ``y`` is (B, ``retune_out_len(n)``), zeros behind ``n_out[i]``.  A row whose clamped cents are all
+    0 is copied."""
+    import numpy as np
+    x = np.asarray(x, dtype=np.float64)
+    single = x.ndim == 1
+    if single:
+        x = x[None]
+    B, n = x.shape
+    c32 = torch.as_tensor(np.asarray(cents, dtype=np.float32))
+    c32 = (c32[None] if c32.dim() == 1 else c32).expand(B, -1)
+    rho, kpos = _retune_curve_knots(c32, knot_first, knot_step)
+    moved = (torch.where(torch.isnan(c32), torch.zeros_like(c32), c32).clamp(-RETUNE_MAX_CENTS, RETUNE_MAX_CENTS) != 0).any(dim=1).tolist()
+    n_in = np.full(B, n, dtype=np.int64) if lengths is None else np.clip(np.asarray(lengths, dtype=np.int64).reshape(B), 0, n)
+    Z, R = RETUNE_ZEROS, RETUNE_RESOLUTION
+    G = retune_table().astype(np.float64)
+    width = retune_out_len(n)
+    y = np.zeros((B, width), dtype=np.float64)
+    n_out = np.zeros(B, dtype=np.int64)
+    for b in range(B):
+        nb = int(n_in[b])
+        if not moved[b]:
+            y[b, :nb], n_out[b] = x[b, :nb], nb
+            continue
+        end = retune_curve_forward(torch.tensor([float(nb)], dtype=torch.float64), c32[b], knot_first, knot_step)
+        no = min(int(math.floor(float(end[0]))), width - 1)
+        n_out[b] = no
+        j0, fr = _retune_curve_read(torch.arange(no, dtype=torch.float64)[None], rho[b:b + 1], kpos[b:b + 1], knot_first, knot_step)
+        j0 = j0[0].numpy()
+        fr = fr[0].numpy().astype(np.float32) * np.float32(R)
+        r = np.minimum(fr.astype(np.int64), R - 1)
+        t = (fr - r.astype(np.float32)).astype(np.float64)
+        xp = np.concatenate([np.zeros(Z), x[b, :nb], np.zeros(Z + 1)])                      # sample j at index j + Z
+        acc = np.zeros(no, dtype=np.float64)
+        for m in range(-Z + 1, Z + 1):
+            if m <= 0:
+                q = r - m * R
+                w = G[q] + t * (G[q + 1] - G[q])
+            else:
+                q = m * R - r - 1
+                w = G[q + 1] + t * (G[q] - G[q + 1])
+            at = j0 + m + Z                                                                 # (a tap outside the row reads a zero)
+            acc += np.where((at >= 0) & (at < len(xp)), xp[np.clip(at, 0, len(xp) - 1)], 0.0) * w
         y[b, :no] = acc
     return (y[0], int(n_out[0])) if single else (y, n_out)
 

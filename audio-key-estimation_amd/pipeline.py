@@ -120,6 +120,30 @@ class TrackScore:
 
 
 @dataclass
+class _Follow:
+    """``tuning="follow"`` checked: the windows of the tuning track, in frames."""
+    window_frames: int
+    stride_frames: int
+
+
+@dataclass
+class _Followed:
+    """What ``tuning="follow"`` retuned by: the curve (R, W_t) on the device and where its knots sit, in input samples."""
+    curve: torch.Tensor
+    knot_first: int
+    knot_step: int
+
+
+def _mark_tuning(track, used, strength):
+    """What a track was retuned by (``KeyEstimator._retuned``'s third and fourth item) -> its tuning fields."""
+    if isinstance(used, _Followed):
+        track.tuning_curve, track.tuning_curve_strength = used.curve, strength
+        track.tuning_knot_first, track.tuning_knot_step = int(used.knot_first), int(used.knot_step)
+    else:
+        track.tuning_cents, track.tuning_strength = used, strength
+
+
+@dataclass
 class KeyTrack:
     """The key of R recordings over time (``KeyEstimator.track``), W windows each; everything but ``times`` lives on the device.
 
@@ -145,6 +169,13 @@ class KeyTrack:
     ``tuning_strength`` (R,), how clearly it was measured (``metrics.estimate_tuning``); both are None on a plain track.  Such a track
     was made from audio whose time axis is stretched by ``rho_i = 2 ** (cents_i / 1200)``: ``times`` and the geometry are the
     retuned audio's, ``segments`` and ``score`` translate to and from the recording's own time.
+
+    ``track(tuning="follow")`` instead adds ``tuning_curve`` and ``tuning_curve_strength`` (R, W_t) float32, the curve every recording
+    was retuned along and the strength of the tuning track's windows (``metrics.tuning_track``), and ``tuning_knot_first`` /
+    ``tuning_knot_step``, where the curve's knots sit in samples of the recording; ``tuning_cents`` is None on such a track.  Its time
+    axis is stretched by a ratio that changes along the recording: ``segments``, ``change_points`` and ``boundary_score`` send their
+    boundaries through the curve's inverse map (``ake_amd.retune_curve_positions``), ``score`` moves the annotation boundaries with the
+    forward map (``metrics.curve_boundaries``).
 
     ``track(method="profile")`` fills the same fields without a net (``metrics.profile_emissions``): ``key`` is every window's
     sum-normalised chroma, ``emissions`` (always there) ``sharpness`` times the 24 profile correlations, ``tonic[..., t]`` the larger of
@@ -179,6 +210,10 @@ class KeyTrack:
     sample_rate: int = 0
     tuning_cents: torch.Tensor | None = None
     tuning_strength: torch.Tensor | None = None
+    tuning_curve: torch.Tensor | None = None
+    tuning_curve_strength: torch.Tensor | None = None
+    tuning_knot_first: int = 0
+    tuning_knot_step: int = 0
     change_frame: torch.Tensor | None = None
     change_gain: torch.Tensor | None = None
     change_contrast: torch.Tensor | None = None
@@ -192,8 +227,32 @@ class KeyTrack:
             out += (self.emissions, self.smooth_key_id)
             if self.posteriors is not None:
                 out += (self.posteriors, self.smooth_confidence, self.log_likelihood)
-        return out + tuple(t for t in (self.tuning_cents, self.tuning_strength, self.change_frame, self.change_gain, self.change_contrast)
-                           if t is not None)
+        return out + tuple(t for t in (self.tuning_cents, self.tuning_strength, self.change_frame, self.change_gain, self.change_contrast,
+                                       self.tuning_curve, self.tuning_curve_strength) if t is not None)
+
+    def _curve_positions(self, k, rows=None):
+        """Samples ``k`` (float64, (R, m), or (m,) of the one recording ``rows``) on the time axis of a followed track's retuned audio ->
+        samples of the recording as it was handed in, through the curve's inverse map: ``ake_amd.retune_curve_positions`` (the
+        retuner's own device function) at the two whole samples around ``k`` and a linear blend between them; a track that lives on the
+        host (built by hand) goes through the model, ``metrics.retune_curve_positions``."""
+        curve = self.tuning_curve if rows is None else self.tuning_curve[rows]
+        k = torch.as_tensor(k, dtype=torch.float64, device=curve.device)
+        lo = torch.floor(k)
+        fn = _tuning.retune_curve_positions if curve.is_cuda else \
+            (lambda i, c, first, step: metrics.retune_curve_positions(i.to(torch.float64), c, first, step))
+        both = fn(torch.cat([lo, lo + 1], dim=-1).to(torch.int64), curve, self.tuning_knot_first, self.tuning_knot_step)
+        a, b = both[..., :k.shape[-1]], both[..., k.shape[-1]:]
+        return a + (k - lo) * (b - a)
+
+    def _own_seconds(self, recording, seconds):
+        """Seconds on the track's time axis -> seconds of recording ``recording`` as it was handed in (list -> list)."""
+        if self.tuning_curve is not None:
+            if not seconds:
+                return []
+            k = torch.tensor(seconds, dtype=torch.float64) * self.sample_rate
+            return (self._curve_positions(k, recording).cpu() / self.sample_rate).tolist()
+        rho = 1.0 if self.tuning_cents is None else 2.0 ** (float(self.tuning_cents[recording]) / 1200.0)
+        return [t / rho for t in seconds]
 
     def _source(self, what, smoothed, refined):
         """``smoothed`` and ``refined`` of ``segments`` and its kin checked -> ``(labels (R, W), whether to read change_frame)``."""
@@ -224,7 +283,7 @@ class KeyTrack:
         earlier one (``metrics.key_changes``), the later one is read at the earlier one's frame: the run between them is empty.
 
         On a retuned track (``tuning_cents``) the times are divided by the recording's ``rho``: they are seconds of the recording as it
-        was handed in, not of its retuned copy."""
+        was handed in, not of its retuned copy.  On a followed track (``tuning_curve``) they go through the curve's inverse map."""
         if confidence and self.smooth_confidence is None:
             raise ValueError("segments(confidence=True): this track has no posteriors; make it with track(..., smooth=True, posteriors=True)")
         source, refined = self._source("segments", smoothed, refined)
@@ -238,7 +297,10 @@ class KeyTrack:
         times = self.times[:n].tolist()
         conf = self.smooth_confidence[recording, :n].cpu().tolist() if confidence else None
         half_w, half_s = self.window_seconds / 2, self.stride_seconds / 2
-        rho = 1.0 if self.tuning_cents is None else 2.0 ** (float(self.tuning_cents[recording]) / 1200.0)
+        if self.tuning_curve is not None:                            # a followed track: the boundaries go through the curve, all at once
+            rho = 1.0
+        else:
+            rho = 1.0 if self.tuning_cents is None else 2.0 ** (float(self.tuning_cents[recording]) / 1200.0)
         out, a = [], 0
         for b in range(n):
             if b + 1 < n and ids[b + 1] == ids[a]:
@@ -252,17 +314,24 @@ class KeyTrack:
             seg = (start, end, ids[a], metrics.KEY_NAMES[ids[a]] if ids[a] >= 0 else "unknown")
             out.append(seg + (sum(conf[a:b + 1]) / (b + 1 - a),) if confidence else seg)
             a = b + 1
+        if self.tuning_curve is not None and out:
+            own = self._own_seconds(recording, [t for seg in out for t in seg[:2]])
+            out = [(own[2 * i], own[2 * i + 1]) + seg[2:] for i, seg in enumerate(out)]
         return out
 
     def change_points(self, recording: int):
         """The refined key changes of one recording on the host -> list of ``(time_s, from_key, to_key, gain, contrast)`` in ascending
-        time: ``change_frame * hop / sample_rate`` (divided by ``rho`` on a retuned track, as in ``segments``), the two keys of
+        time: ``change_frame * hop / sample_rate`` (divided by ``rho`` on a retuned track, through the curve on a followed one, as in ``segments``), the two keys of
         ``refined_source`` around it, ``change_gain`` and ``change_contrast``.  ``ValueError`` on a track without ``refine=True``."""
         if self.change_frame is None:
             raise ValueError("change_points: this track has no refined boundaries; make it with track(..., refine=True)")
         n = int(self.counts[recording])
         ids = getattr(self, self.refined_source)[recording, :n].cpu().tolist()
         frame, gain, contrast = (t[recording, :max(n - 1, 0)].cpu().tolist() for t in (self.change_frame, self.change_gain, self.change_contrast))
+        if self.tuning_curve is not None:
+            at = [w for w in range(n - 1) if frame[w] >= 0]
+            own = self._own_seconds(recording, [frame[w] * self.hop / self.sample_rate for w in at])
+            return [(t, ids[w], ids[w + 1], gain[w], contrast[w]) for t, w in zip(own, at)]
         rho = 1.0 if self.tuning_cents is None else 2.0 ** (float(self.tuning_cents[recording]) / 1200.0)
         return [(frame[w] * self.hop / self.sample_rate / rho, ids[w], ids[w + 1], gain[w], contrast[w]) for w in range(n - 1) if frame[w] >= 0]
 
@@ -275,7 +344,8 @@ class KeyTrack:
         the end.
 
         On a retuned track the annotations are moved onto the retuned time axis first (``metrics.scale_boundaries``, as ``score``
-        does), and every distance is divided by the recording's ``rho``: seconds of the recording as it was handed in."""
+        does), and every distance is divided by the recording's ``rho``: seconds of the recording as it was handed in.  On a followed
+        track the predicted boundaries go back through the curve instead and meet the annotations on the recording's own axis."""
         pred, refined = self._source("boundary_score", None, refined)
         if self.hop <= 0 or self.window_frames <= 0 or self.stride_frames <= 0 or self.sample_rate <= 0:
             raise ValueError("boundary_score: this track does not know its geometry (hop, window_frames, stride_frames, sample_rate); "
@@ -301,6 +371,8 @@ class KeyTrack:
         at = ((w_idx * self.stride_frames + (self.window_frames - 1) / 2 + self.stride_frames / 2) * self.hop).expand(R, -1)
         if refined:
             at = torch.where(self.change_frame >= 0, self.change_frame.to(torch.float64) * self.hop, at)
+        if self.tuning_curve is not None and W > 1:                  # a followed track: the predicted boundaries go back through the curve,
+            at = self._curve_positions(at.contiguous())              # and meet the annotations on the recording's own axis
         moves = (pred[:, 1:] != pred[:, :-1]) & (torch.arange(1, max(W, 1), device=dev)[None, :] < self.counts.to(dev).reshape(R, 1))
         at = torch.where(moves, at, torch.full_like(at, float("inf")))
         dist = (start[:, 1:].to(torch.float64)[:, :, None] - at[:, None, :]).abs()                                  # (R, S - 1, W - 1)
@@ -319,7 +391,8 @@ class KeyTrack:
         sample rate.  ``ValueError`` on a track without its geometry (``hop``, ``window_frames``, ``stride_frames``).
 
         On a retuned track (``tuning_cents``) the annotation boundaries are first moved onto the retuned time axis,
-        ``floor(start * rho_i)`` in float64 torch ops on the device (``metrics.scale_boundaries``); the launch is the same."""
+        ``floor(start * rho_i)`` in float64 torch ops on the device (``metrics.scale_boundaries``); the launch is the same.  On a followed
+        track (``tuning_curve``) they are moved with the curve's forward map (``metrics.curve_boundaries``)."""
         if smoothed and self.smooth_key_id is None:
             raise ValueError("score(smoothed=True): this track has no smoothed path; make it with track(..., smooth=True)")
         if self.hop <= 0 or self.window_frames <= 0 or self.stride_frames <= 0:
@@ -339,6 +412,8 @@ class KeyTrack:
         start = annotations.seg_start.to(device=dev, dtype=torch.int64)
         if self.tuning_cents is not None:
             start = metrics.scale_boundaries(start, self.tuning_cents)
+        if self.tuning_curve is not None:
+            start = metrics.curve_boundaries(start, self.tuning_curve, self.tuning_knot_first, self.tuning_knot_step)
         start = start.contiguous()
         key = annotations.seg_key.to(device=dev, dtype=torch.int32).contiguous()
         count = annotations.seg_count.to(device=dev, dtype=torch.int32).contiguous()
@@ -378,6 +453,13 @@ class KeyEstimator:
     ``ake_retune_out_len(n)`` columns (the widest a row can get), so nothing waits for the device; ``lengths``, ``rate``, ``channel``,
     int16 audio, ``streams`` > 1, ``wrap_mode="true_end"`` and ``frames=0`` work as without it.  The resampler discards content above
     0.94 of the Nyquist frequency: an estimator whose transform reaches that far refuses ``tuning`` with a ``ValueError``.
+
+    ``tuning="follow"`` (``__call__``, ``track``, ``profile_key``) is for a tuning that drifts within a recording, a tape that changes
+    speed: one transform at the estimator's plan, the estimate on sliding windows of ``tuning_window_seconds`` (default 5, rounded to
+    an odd number of frames) every ``tuning_stride_seconds`` (default 1) (``tuning_track``, ``ake_amd.tuning_track``; windows weaker than
+    ``min_strength`` hold the last strong value), then a resampler whose ratio is linear in the input position between the window
+    centres (``ake_amd.retune_curve``, two launches), then the call on the retuned audio as with "auto".  Nothing is read back.
+    Refused with a ``ValueError`` on ``frames=0`` estimators, which have a hop per clip.
 
     ``KeyEstimator(None, device=..., pitches=288)``: an estimator without a net, for the calls that need none --
     ``track(method="profile")``, ``stream(method="profile")``, ``profile_key`` and ``fit_key_profiles`` (and ``estimate_tuning``).
@@ -429,7 +511,7 @@ class KeyEstimator:
 
     @torch.no_grad()
     def __call__(self, audio: torch.Tensor, lengths: torch.Tensor | None = None, rate: int | None = None, channel: int = 0,
-                 tuning=None, min_strength: float = 0.0):
+                 tuning=None, min_strength: float = 0.0, tuning_window_seconds: float = 5.0, tuning_stride_seconds: float = 1.0):
         """audio (B, n) or (B, C, n) float32 on the GPU -> tuple of (B,12), (B,12)[, (B,11)] float32 tensors.
 
         int16 audio is 16-bit PCM, sample / 32768 (``ake_amd.pcm16_to_float``): mono at the estimator's rate goes straight to the PCM
@@ -450,15 +532,18 @@ class KeyEstimator:
             lengths = len_out if lengths is not None else None
         if tuning is None:
             return self._issue(self._run_wrapped, audio, lengths)
-        cents = self._given_tuning(tuning, audio.shape[0])
+        cents = self._given_tuning(tuning, audio.shape[0], tuning_window_seconds, tuning_stride_seconds)
         return self._issue(lambda slot, a, l: self._run_wrapped(slot, *self._retuned(slot, a, l, cents, min_strength)[:2]), audio, lengths)
 
-    def _given_tuning(self, tuning, B):
-        """``tuning`` of ``__call__`` / ``track`` checked -> None for "auto", else the (B,) float32 cents on the device."""
+    def _given_tuning(self, tuning, B, window_seconds=5.0, stride_seconds=1.0):
+        """``tuning`` of ``__call__`` / ``track`` / ``profile_key`` checked -> None for "auto", the ``_Follow`` geometry for "follow",
+        else the (B,) float32 cents on the device."""
         self._refuse_unretunable("tuning")
         if isinstance(tuning, str):
+            if tuning == "follow":
+                return self._follow_geometry('tuning="follow"', window_seconds, stride_seconds)
             if tuning != "auto":
-                raise ValueError('tuning must be None, "auto", a number of cents or a (B,) tensor of cents')
+                raise ValueError('tuning must be None, "auto", "follow", a number of cents or a (B,) tensor of cents')
             return None
         if isinstance(tuning, torch.Tensor):
             cents = tuning.detach().to(device=self.device, dtype=torch.float32).reshape(-1)
@@ -507,8 +592,40 @@ class KeyEstimator:
             mel = self.plan.logmag(audio, lengths=lengths, workspace=ws)
         return _tuning.estimate_tuning(mel, None, min_strength, workspace=ws)
 
+    def _follow_geometry(self, what, window_seconds, stride_seconds):
+        """The windows of a tuning track -> ``_Follow``: ``window_seconds`` rounded to an odd number of frames (a window then has a frame
+        at its centre, where its knot sits), ``stride_seconds`` to at least one."""
+        if self.frames <= 0:
+            raise ValueError(f"{what} needs a fixed frame rate: this estimator was built with frames=0, which has a hop per clip")
+        wf = max(1, int(round(float(window_seconds) * self.frames)))
+        return _Follow(wf + 1 - wf % 2, max(1, int(round(float(stride_seconds) * self.frames))))
+
+    def _tuning_track(self, slot, audio, lengths, follow, min_strength):
+        """One transform at the estimator's plan in the slot's workspace, then ``ake_tuning_track_f32`` in the same place (same stream,
+        behind it) -> ``(cents_raw, strength, curve, window_counts)``."""
+        L = _lib.lib()
+        audio = audio.to(self.device)
+        B, n = audio.shape
+        T = self.plan.num_frames(n)
+        ws = self._slot_ws(slot, max(int(L.ake_cqt_workspace_bytes(self.plan.handle, B, n)),
+                                     int(L.ake_tuning_track_workspace_bytes(B, T, follow.window_frames, follow.stride_frames))))
+        frames = None
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths).to(device=self.device, dtype=torch.int64).contiguous()
+            frames = (1 + lengths.clamp(0, n) // self.plan.hop_length).clamp(max=T).to(torch.int32)
+        mel = self.plan.logmag(audio, lengths=lengths, workspace=ws)
+        return _tuning.tuning_track(mel, follow.window_frames, follow.stride_frames, frames, min_strength, workspace=ws)
+
     def _retuned(self, slot, audio, lengths, cents, min_strength):
-        """-> ``(retuned audio, retuned lengths, cents, strength)``; ``cents`` None: estimated here (``strength`` is None otherwise)."""
+        """-> ``(retuned audio, retuned lengths, cents, strength)``; ``cents`` None: estimated here (``strength`` is None otherwise);
+        ``cents`` a ``_Follow``: the tuning track is measured here and the audio retuned along its curve, with the knots at the window
+        centres; ``cents`` then comes back as a ``_Followed`` (``strength`` is that of the windows)."""
+        if isinstance(cents, _Follow):
+            _, strength, curve, _ = self._tuning_track(slot, audio, lengths, cents, min_strength)
+            hop = self.plan.hop_length
+            first, step = (cents.window_frames - 1) // 2 * hop, cents.stride_frames * hop
+            audio, lengths = _tuning.retune_curve(audio.to(self.device), curve, first, step, lengths)
+            return audio, lengths, _Followed(curve, first, step), strength
         strength = None
         if cents is None:
             cents, strength = self._estimate(slot, audio, lengths, min_strength)
@@ -527,6 +644,18 @@ class KeyEstimator:
             audio, len_out = rs(audio, channel=channel, lengths=lengths)
             lengths = len_out if lengths is not None else None
         return self._issue(lambda slot, a, l: self._estimate(slot, a, l, min_strength), audio, lengths)
+
+    @torch.no_grad()
+    def tuning_track(self, audio: torch.Tensor, lengths: torch.Tensor | None = None, rate: int | None = None, channel: int = 0,
+                     window_seconds: float = 5.0, stride_seconds: float = 1.0, min_strength: float = 0.0):
+        """How far every recording sits from A4 = 440 Hz over time -> ``(cents_raw, strength, curve, window_counts)``, float32 (B, W)
+        three times and int32 (B,) on the device: one transform at the estimator's plan, then ``ake_amd.tuning_track`` on windows of
+        ``window_seconds`` (rounded to an odd number of frames) every ``stride_seconds`` (``metrics.tuning_track`` is the definition).
+        It is the measurement ``tuning="follow"`` retunes by.  ``audio``, ``lengths``, ``rate``, ``channel``, ``streams`` > 1 and ``join()``
+        as in ``__call__``.  Refused with a ``ValueError`` on ``frames=0`` estimators."""
+        follow = self._follow_geometry("tuning_track", window_seconds, stride_seconds)
+        audio, lengths = self._resampled(audio, lengths, rate, channel)
+        return self._issue(lambda slot, a, l: self._tuning_track(slot, a, l, follow, min_strength), audio, lengths)
 
     def _issue(self, run, audio, lengths):
         """``run(slot, audio, lengths)`` on the caller's stream (``streams`` == 1) or on the next side stream in turn."""
@@ -554,7 +683,8 @@ class KeyEstimator:
               window_seconds: float = 15.0, stride_seconds: float = 5.0, smooth: bool = False, mean_key_seconds: float = 60.0,
               transition: torch.Tensor | None = None, signature_weight: float = 1.0, posteriors: bool = False,
               tuning=None, min_strength: float = 0.0, method: str = "net", profiles="krumhansl", compression: str = "log",
-              profile_sharpness: float = 10.0, refine: bool = False, refine_slack_seconds: float | None = None) -> KeyTrack:
+              profile_sharpness: float = 10.0, refine: bool = False, refine_slack_seconds: float | None = None,
+              tuning_window_seconds: float = 5.0, tuning_stride_seconds: float = 1.0) -> KeyTrack:
         """The key of long recordings over time: audio (R, n) or (R, C, n) float32 on the GPU -> ``KeyTrack``.  int16 audio is 16-bit
         PCM, as in ``__call__``.
 
@@ -587,7 +717,8 @@ class KeyEstimator:
 
         ``tuning``, ``min_strength``: see the class.  The track is then that of the retuned audio -- its ``times`` and geometry are the
         retuned time axis -- and carries ``tuning_cents`` (and ``tuning_strength`` with "auto"), by which ``KeyTrack.segments`` and
-        ``KeyTrack.score`` translate to and from the recording's own time.
+        ``KeyTrack.score`` translate to and from the recording's own time.  With ``tuning="follow"`` (``tuning_window_seconds``,
+        ``tuning_stride_seconds``: see the class) it carries ``tuning_curve`` and its kin instead, and they translate through the curve.
 
         ``method``: ``"net"`` (default) is all of the above.  ``"profile"`` needs no net: the same one transform per recording, then
         ``ake_amd.profile_emissions`` on the same windows (two launches, no net launch) with ``profiles`` (a name of
@@ -611,7 +742,7 @@ class KeyEstimator:
         if method == "profile":
             return self._track_profile(audio, lengths, rate, channel, window_seconds, stride_seconds, smooth, mean_key_seconds, transition,
                                        signature_weight, posteriors, tuning, min_strength, profiles, compression, profile_sharpness,
-                                       refine, refine_slack_seconds)
+                                       refine, refine_slack_seconds, tuning_window_seconds, tuning_stride_seconds)
         if method != "net":
             raise ValueError('track: method must be "net" or "profile"')
         self._need_net('KeyEstimator.track(method="net")')
@@ -628,14 +759,14 @@ class KeyEstimator:
         refining = self._refining(sf, refine_slack_seconds, profiles, compression) if refine else None
         if tuning is None and refining is None:
             return self._issue(lambda slot, a, l: self._run_track(slot, a, l, wf, sf, smoothing), audio, lengths)
-        cents = None if tuning is None else self._given_tuning(tuning, audio.shape[0])
+        cents = None if tuning is None else self._given_tuning(tuning, audio.shape[0], tuning_window_seconds, tuning_stride_seconds)
 
         def run(slot, a, l):
             used = strength = None
             if tuning is not None:
                 a, l, used, strength = self._retuned(slot, a, l, cents, min_strength)
             track = self._run_track(slot, a, l, wf, sf, smoothing)
-            track.tuning_cents, track.tuning_strength = used, strength
+            _mark_tuning(track, used, strength)
             if refining is not None:                                 # the fused call's transform stays in its workspace: one more
                 mel, frames = self._profile_logmag(slot, a, l)[:2] if track.key_id.shape[1] > 1 else (None, None)
                 self._refine(track, mel, frames, refining)
@@ -971,7 +1102,7 @@ class KeyEstimator:
 
     def _track_profile(self, audio, lengths, rate, channel, window_seconds, stride_seconds, smooth, mean_key_seconds, transition,
                        signature_weight, posteriors, tuning, min_strength, profiles, compression, sharpness, refine=False,
-                       refine_slack_seconds=None):
+                       refine_slack_seconds=None, tuning_window_seconds=5.0, tuning_stride_seconds=1.0):
         self._refuse_unprofilable('track(method="profile")')
         if float(signature_weight) != 1.0:
             raise ValueError('track(method="profile"): signature_weight weighs the net\'s key head, which this method does not run; leave it at 1')
@@ -984,7 +1115,7 @@ class KeyEstimator:
         wf = track_window_frames(int(round(window_seconds * self.sample_rate)), self.plan.hop_length)
         sf = track_stride_frames(stride_seconds, self.frames)
         smoothing = (self._transition(sf, mean_key_seconds, transition), bool(posteriors)) if smooth else None
-        cents = None if tuning is None else self._given_tuning(tuning, audio.shape[0])
+        cents = None if tuning is None else self._given_tuning(tuning, audio.shape[0], tuning_window_seconds, tuning_stride_seconds)
         refining = (self._refining(sf, refine_slack_seconds, profiles, compression)[0], prof, mode) if refine else None
 
         def run(slot, a, l):
@@ -994,7 +1125,7 @@ class KeyEstimator:
             if tuning is not None:
                 a, l, used, strength = self._retuned(slot, a, l, cents, min_strength)
             track = self._run_profile_track(slot, a, l, wf, sf, smoothing, prof, mode, sharpness, refining)
-            track.tuning_cents, track.tuning_strength = used, strength
+            _mark_tuning(track, used, strength)
             return track
         return self._issue(run, audio, lengths)
 
@@ -1068,7 +1199,8 @@ class KeyEstimator:
 
     @torch.no_grad()
     def profile_key(self, audio: torch.Tensor, lengths: torch.Tensor | None = None, rate: int | None = None, channel: int = 0,
-                    tuning=None, min_strength: float = 0.0, profiles="krumhansl", compression: str = "log", sharpness: float = 10.0):
+                    tuning=None, min_strength: float = 0.0, profiles="krumhansl", compression: str = "log", sharpness: float = 10.0,
+                    tuning_window_seconds: float = 5.0, tuning_stride_seconds: float = 1.0):
         """One key per clip without a net -> ``(key_id int32 (B,), confidence (B,), chroma (B, 12), emissions (B, 24))`` on the device:
         one transform at the estimator's plan, then ``ake_amd.profile_emissions`` in its whole-clip mode (``window_frames=0``: every
         clip's chroma over its own ``1 + lengths[i] // hop`` frames; ``metrics.profile_emissions`` is the definition).  ``audio``,
@@ -1082,7 +1214,7 @@ class KeyEstimator:
             raise ValueError("profile_key: sharpness must be positive")
         prof = _keyprofile.device_profiles(profiles, self.device)
         audio, lengths = self._resampled(audio, lengths, rate, channel)
-        cents = None if tuning is None else self._given_tuning(tuning, audio.shape[0])
+        cents = None if tuning is None else self._given_tuning(tuning, audio.shape[0], tuning_window_seconds, tuning_stride_seconds)
 
         def run(slot, a, l):
             if self.streams > 1:

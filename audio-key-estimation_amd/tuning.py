@@ -3,7 +3,9 @@
 Not part of the reference: it pins librosa 0.9.2, whose ``cqt`` runs at ``tuning=0.0``, and its net collapses each semitone's three bins
 as they come, so a recording that is 35 cents sharp lands one full bin off.  Host wrappers of ``ake_tuning_estimate_f32``
 (csrc/tuning.hip) and ``ake_retune_f32`` / ``ake_retune_pcm16_f32`` (csrc/audio.hip); the float64 models are
-``metrics.estimate_tuning`` and ``metrics.retune_reference``.  There is no CPU fallback.
+``metrics.estimate_tuning`` and ``metrics.retune_reference``.  For a tuning that drifts within a recording: ``tuning_track``
+(``ake_tuning_track_f32``) and ``retune_curve`` / ``retune_curve_positions`` (``ake_retune_curve_f32`` / ``_pcm16_f32`` /
+``ake_retune_curve_positions``), with the models ``metrics.tuning_track`` and ``metrics.retune_curve_reference``.  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -102,6 +104,134 @@ def retune(audio: torch.Tensor, cents, lengths: torch.Tensor | None = None):
         _lib.check(fn(audio.data_ptr(), B, n, audio.stride(0) if B > 1 else max(n, 1), lengths.data_ptr() if lengths is not None else None,
                       cents.data_ptr(), out.data_ptr(), out.stride(0), len_out.data_ptr(), torch.cuda.current_stream().cuda_stream), name)
     return out, len_out
+
+
+def tuning_track(logmag: torch.Tensor, window_frames: int, stride_frames: int, counts: torch.Tensor | None = None,
+                 min_strength: float = 0.0, frames_major: bool = False, workspace: torch.Tensor | None = None):
+    """The detuning of B recordings over time, for a tuning that drifts -> ``(cents_raw, strength, curve, window_counts)``: float32
+    (B, W) three times and int32 (B,), on the device (``ake_tuning_track_f32``; ``metrics.tuning_track`` is the definition).
+
+    ``logmag``, ``counts``, ``frames_major`` and ``workspace`` (``ake_tuning_track_workspace_bytes``) as in ``estimate_tuning``.  Windows of
+    ``window_frames`` frames, ``stride_frames`` apart; ``W = metrics.tuning_track_windows(T, ...)`` is computed from the shape, so nothing is
+    read back.  ``cents_raw`` and ``strength`` are every window's estimate; ``curve`` is what ``retune_curve`` follows: windows weaker
+    than ``min_strength`` hold the last strong value, the sequence is unwrapped across the +-50 seam and clamped to +-50.  Three launches
+    on the current stream."""
+    _need_device(logmag, "tuning_track")
+    if logmag.dim() != 3:
+        raise ValueError(f"tuning_track: logmag must be (B, n_bins, T), got {tuple(logmag.shape)}")
+    mel = logmag.to(torch.float32).contiguous()
+    B, P, T = (mel.shape[0], mel.shape[2], mel.shape[1]) if frames_major else mel.shape
+    if P % metrics.TUNING_BINS_PER_SEMITONE != 0:
+        raise ValueError(f"tuning_track: {P} bins are no multiple of 3 (3 bins per semitone)")
+    wf, sf = int(window_frames), int(stride_frames)
+    W = metrics.tuning_track_windows(T, wf, sf)
+    dev = mel.device
+    cents, strength, curve = (torch.empty((B, W), dtype=torch.float32, device=dev) for _ in range(3))
+    n_win = torch.empty((B,), dtype=torch.int32, device=dev)
+    if B == 0 or T == 0:
+        return cents, strength, curve, n_win.zero_()
+    if counts is not None:
+        counts = torch.as_tensor(counts).to(device=dev, dtype=torch.int32).contiguous()
+        assert counts.shape == (B,)
+    L = _lib.lib()
+    nbytes = int(L.ake_tuning_track_workspace_bytes(B, T, wf, sf))
+    if nbytes == 0:
+        _lib.check(-1, "ake_tuning_track_workspace_bytes")
+    ws = workspace if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.ake_tuning_track_f32(mel.data_ptr(), 1 if frames_major else 0, B, P, T, counts.data_ptr() if counts is not None else None,
+                                          wf, sf, float(min_strength), cents.data_ptr(), strength.data_ptr(), curve.data_ptr(), n_win.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream), "ake_tuning_track_f32")
+    return cents, strength, curve, n_win
+
+
+def _curve_on_device(cents, B, dev, what):
+    """``cents`` (K,) or (B, K) -> float32 (B, K) on ``dev`` with unit stride along the knots."""
+    if not isinstance(cents, torch.Tensor):
+        cents = torch.as_tensor(cents, dtype=torch.float32)
+    cents = cents.to(device=dev, dtype=torch.float32)
+    if cents.dim() == 1:
+        cents = cents[None]
+    if cents.dim() != 2 or cents.shape[1] < 1:
+        raise ValueError(f"{what}: a curve is (K,) or (B, K) with K >= 1, got {tuple(cents.shape)}")
+    if cents.shape[0] == 1 and B != 1:
+        cents = cents.expand(B, -1)
+    if cents.shape[0] != B:
+        raise ValueError(f"{what}: {B} rows but {cents.shape[0]} curves")
+    return cents.contiguous()
+
+
+def _curve_workspace(L, B, K, dev):
+    nbytes = int(L.ake_retune_curve_workspace_bytes(B, K))
+    if nbytes == 0:
+        _lib.check(-1, "ake_retune_curve_workspace_bytes")
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def retune_curve(audio: torch.Tensor, cents, knot_first: int, knot_step: int, lengths: torch.Tensor | None = None):
+    """``retune`` along a tuning curve -> ``(audio (B, retune_out_len(n)) float32, lengths (B,) int64)``.
+
+    ``audio`` and ``lengths`` as in ``retune``.  ``cents`` (B, K) or (K,) float32 (``tuning_track``'s ``curve`` goes straight in; nothing
+    is read back): knot i sits at input sample ``knot_first + i * knot_step`` (``knot_first >= 0``, ``knot_step >= 64``); the ratio is
+    ``2 ** (cents / 1200)`` at the knots, linear in the input position between them and constant outside
+    (``metrics.retune_curve_reference``).  A row whose cents are all 0 is copied bit for bit.  Two launches on the current stream."""
+    _need_device(audio, "retune_curve")
+    if audio.dim() != 2:
+        raise ValueError(f"retune_curve: audio must be (B, n), got {tuple(audio.shape)}")
+    pcm = audio.dtype == torch.int16
+    if not pcm:
+        audio = audio.to(torch.float32)
+    if audio.stride(1) != 1 or (audio.shape[0] > 1 and audio.stride(0) < audio.shape[1]):
+        audio = audio.contiguous()
+    dev = audio.device
+    B, n = audio.shape
+    if int(knot_first) < 0 or int(knot_step) < 64:
+        raise ValueError(f"retune_curve: knot_first {knot_first} must be >= 0 and knot_step {knot_step} >= 64 samples")
+    L = _lib.lib()
+    width = retune_out_len(n)
+    out = torch.empty((B, width), dtype=torch.float32, device=dev)
+    len_out = torch.empty((B,), dtype=torch.int64, device=dev)
+    if B == 0 or n == 0:
+        return out.zero_(), len_out.zero_()
+    cents = _curve_on_device(cents, B, dev, "retune_curve")
+    K = cents.shape[1]
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths).to(device=dev, dtype=torch.int64).contiguous()
+        assert lengths.shape == (B,)
+    ws = _curve_workspace(L, B, K, dev)
+    fn, name = (L.ake_retune_curve_pcm16_f32, "ake_retune_curve_pcm16_f32") if pcm else (L.ake_retune_curve_f32, "ake_retune_curve_f32")
+    with torch.cuda.device(dev):
+        _lib.check(fn(audio.data_ptr(), B, n, audio.stride(0) if B > 1 else max(n, 1), lengths.data_ptr() if lengths is not None else None,
+                      cents.data_ptr(), K, cents.stride(0), int(knot_first), int(knot_step), out.data_ptr(), out.stride(0), len_out.data_ptr(),
+                      ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream), name)
+    return out, len_out
+
+
+def retune_curve_positions(out_index: torch.Tensor, cents, knot_first: int, knot_step: int):
+    """Where the outputs ``out_index`` (B, m) or (m,) int64 of ``retune_curve`` read their input -> float64 positions in samples, of the
+    same shape, by the device function the resampler uses (``ake_retune_curve_positions``; ``metrics.retune_curve_positions``)."""
+    idx = torch.as_tensor(out_index)
+    _need_device(idx, "retune_curve_positions")
+    single = idx.dim() == 1
+    idx = (idx[None] if single else idx).to(torch.int64).contiguous()
+    if idx.dim() != 2:
+        raise ValueError(f"retune_curve_positions: out_index must be (m,) or (B, m), got {tuple(out_index.shape)}")
+    if int(knot_first) < 0 or int(knot_step) < 64:
+        raise ValueError(f"retune_curve_positions: knot_first {knot_first} must be >= 0 and knot_step {knot_step} >= 64 samples")
+    B, m = idx.shape
+    dev = idx.device
+    pos = torch.empty((B, m), dtype=torch.float64, device=dev)
+    if B == 0 or m == 0:
+        return pos[0] if single else pos
+    cents = _curve_on_device(cents, B, dev, "retune_curve_positions")
+    K = cents.shape[1]
+    L = _lib.lib()
+    ws = _curve_workspace(L, B, K, dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.ake_retune_curve_positions(cents.data_ptr(), B, K, cents.stride(0), int(knot_first), int(knot_step), idx.data_ptr(), m,
+                                                pos.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
+                   "ake_retune_curve_positions")
+    return pos[0] if single else pos
 
 
 class StreamRetuner:

@@ -773,6 +773,29 @@ size_t ake_tuning_workspace_bytes(int batch, int frames);
 int ake_tuning_estimate_f32(const float* mel_dev, int frames_major, int batch, int pitches, int frames, const int32_t* counts_dev,
                             float min_strength, float* cents_dev, float* strength_dev, void* workspace, size_t workspace_bytes,
                             ake_stream_t stream);
+/* The tuning track: the same estimate over sliding windows of frames, for recordings whose tuning drifts (a tape that changes speed),
+ * and the curve that ake_retune_curve_f32 follows.  mel_dev, frames_major, counts_dev and pitches as above; window_frames >= 1,
+ * stride_frames >= 1.  Recording i with T_i frames has W_i = 1 + (T_i - window_frames) / stride_frames windows when T_i >= window_frames,
+ * one window over all its frames when 0 < T_i < window_frames, none when T_i = 0; window w covers the frames
+ * [w stride_frames, min(w stride_frames + window_frames, T_i)).  Every output row has W = ake_tuning_track_windows(frames, window_frames,
+ * stride_frames) columns, the count of a recording of `frames` frames (-1 for a bad geometry), so a caller sizes them without a read-back.
+ *   cents_raw_dev, strength_dev float32 [batch][W]: the formulas above on each window's three sums, which are added in double in ascending
+ *     frame order; min_strength is not applied to them; columns >= W_i hold 0.
+ *   curve_dev float32 [batch][W], per recording in window order: a window with strength < min_strength takes the value of the nearest
+ *     earlier window that is not (the leading ones that of the first such window; 0 everywhere when there is none); then +-100 is added
+ *     so that each value lies within 50 of the unwrapped value before it (v + 100 floor((before - v) / 100 + 0.5)); then the value is
+ *     clamped to +-50 -- a drift that leaves the semitone saturates, it does not jump; columns >= W_i repeat the last valid value.  The
+ *     decisions are made on the doubles.
+ *   window_counts_dev int32 [batch]: W_i.
+ * Three launches: every frame's three sums once (not once per overlapping window), a thread per window, a thread per recording.  No
+ * floating-point atomics: two runs give the same bits.  The workspace (8-byte aligned) holds the per-frame sums and the windows'
+ * doubles.  Refusals as ake_tuning_estimate_f32's, and AKE_ERR_INVALID for a bad geometry; nothing is launched after any of them.
+ * Host model: metrics.tuning_track. */
+int ake_tuning_track_windows(int frames, int window_frames, int stride_frames);
+size_t ake_tuning_track_workspace_bytes(int batch, int frames, int window_frames, int stride_frames);
+int ake_tuning_track_f32(const float* mel_dev, int frames_major, int batch, int pitches, int frames, const int32_t* counts_dev,
+                         int window_frames, int stride_frames, float min_strength, float* cents_raw_dev, float* strength_dev,
+                         float* curve_dev, int32_t* window_counts_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream);
 /* Retuning: row i is resampled by rho_i = 2^(cents_dev[i] / 1200), which undoes a detuning of cents_dev[i] (float32 [batch]; NaN is read
  * as 0, values beyond +-50 as +-50).  in_dev [batch][in_stride], row i holds lengths_dev[i] samples (int64, clamped to 0..n_max; NULL:
  * n_max).  n_out_i = floor(n_i * rho_i), written to lengths_out_dev (int64 [batch], nullable), and
@@ -792,6 +815,35 @@ int ake_retune_f32(const float* in_dev, int batch, int64_t n_max, int64_t in_str
                    float* out_dev, int64_t out_stride, int64_t* lengths_out_dev, ake_stream_t stream);
 int ake_retune_pcm16_f32(const int16_t* in_dev, int batch, int64_t n_max, int64_t in_stride, const int64_t* lengths_dev,
                          const float* cents_dev, float* out_dev, int64_t out_stride, int64_t* lengths_out_dev, ake_stream_t stream);
+/* Retuning along a curve: ake_retune_f32 with a ratio that is piecewise linear in the input position (host models
+ * metrics.retune_curve_reference, retune_curve_forward, retune_curve_positions).  cents_dev float32 [batch][cents_stride], `knots` >= 1
+ * values a row (ake_tuning_track_f32's curve goes straight in); knot i sits at input sample p_i = knot_first + i knot_step (knot_first
+ * >= 0, knot_step >= 64) and carries rho_i = 2^(cents_i / 1200), read as ake_retune_f32 reads its cents.  rho is rho_0 in front of the
+ * first knot, rho_{knots-1} behind the last, linear in p between two.  The output index of input position p is
+ *   K(p) = rho_0 p in front of the first knot;  K_0 = rho_0 p_0,  K_{i+1} = K_i + knot_step (rho_i + rho_{i+1}) / 2  (double, ascending i)
+ *   K(p) = K_i + rho_i u + (rho_{i+1} - rho_i) u^2 / (2 knot_step),  u = p - p_i, inside segment i
+ * n_out_i = floor(K(n_i)) < ake_retune_out_len(n_max), the buffer's width as before.  Output k reads the position K^{-1}(k): with s the
+ * last segment with K_s <= k, c = k - K_s and a = (rho_{s+1} - rho_s) / (2 knot_step), u = 2 c / (rho_s + sqrt(rho_s^2 + 4 a c)); k / rho_0 in
+ * front of the first knot, c / rho_{knots-1} behind the last.  The position is kept as the integer p_s + floor(u) and the fraction
+ * u - floor(u); only the fraction is rounded to float32.  Taps, table, blend and sum order are ake_retune_f32's own code.  A row whose
+ * clamped cents are all exactly 0 is copied bit for bit.  The PCM form gives the float form's results bit for bit.
+ * Two launches: a prefix launch writes rho_i, K_i, n_out_i and the copy flag into the workspace (ake_retune_curve_workspace_bytes(batch,
+ * knots), 8-byte aligned; 0 for a batch outside 1..65535 or knots outside 1..2^22), then the resampling launch.
+ * ake_retune_curve_positions: positions_dev double [batch][m] = K^{-1}(out_index_dev[batch][m]) by the device function the resampler
+ * uses (the prefix launch, then a thread per index).
+ * AKE_ERR_INVALID: a null argument (lengths_dev and lengths_out_dev may be null), a bad batch or n_max, knots < 1, knot_step outside
+ * 64..2^32, knot_first outside 0..2^40, in_stride < n_max, out_stride < the width, cents_stride < knots, m < 1, a misaligned workspace;
+ * AKE_ERR_WORKSPACE: workspace_bytes below the query.  Nothing is launched after any of them. */
+size_t ake_retune_curve_workspace_bytes(int batch, int knots);
+int ake_retune_curve_f32(const float* in_dev, int batch, int64_t n_max, int64_t in_stride, const int64_t* lengths_dev, const float* cents_dev,
+                         int knots, int64_t cents_stride, int64_t knot_first, int64_t knot_step, float* out_dev, int64_t out_stride,
+                         int64_t* lengths_out_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream);
+int ake_retune_curve_pcm16_f32(const int16_t* in_dev, int batch, int64_t n_max, int64_t in_stride, const int64_t* lengths_dev,
+                               const float* cents_dev, int knots, int64_t cents_stride, int64_t knot_first, int64_t knot_step, float* out_dev,
+                               int64_t out_stride, int64_t* lengths_out_dev, void* workspace, size_t workspace_bytes, ake_stream_t stream);
+int ake_retune_curve_positions(const float* cents_dev, int batch, int knots, int64_t cents_stride, int64_t knot_first, int64_t knot_step,
+                               const int64_t* out_index_dev, int64_t m, double* positions_dev, void* workspace, size_t workspace_bytes,
+                               ake_stream_t stream);
 
 /* The retuner on audio that arrives in chunks, all recordings in lockstep (KeyEstimator.stream(retune_cents=...), ake_amd.StreamRetuner;
  * host model metrics.stream_retune).  Z, the table, beta and the cutoff are ake_retune_f32's.

@@ -11,6 +11,9 @@ recordings -> profiles/tuning.md.
   accuracy  : KeyTrack.score (smoothed path) on 24 modulating recordings of 5 min whose partials are scaled by 2^(c / 1200),
               c = -45 .. 45, with tuning=None and tuning="auto", on a net trained as tools/track_accuracy.py trains its own
 
+  follow    : the tuning track and the curve retuner (tuning="follow") -> profiles/tuning_follow.md holds its figures: the drift table
+              (ramp, sine, constant) on the device, and the new launches' times at 256 x 15 s and 8 x 10 min beside retune_kernel's
+
 Every step runs in a child process of its own under its own time limit; the first step that fails or runs out of time ends the run,
 and the report says "Not measured" for every step without a result (--json keeps results between runs).     python3 tools/tuning_bench.py [--markdown profiles/tuning.md]
 """
@@ -26,7 +29,7 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 SR, DEV, HOP = 22050, "cuda:0", 4410
-STEPS = (("errors", 300), ("timings", 420), ("accuracy", 900))             # name, time limit in seconds
+STEPS = (("errors", 300), ("timings", 420), ("accuracy", 900), ("follow", 420))             # name, time limit in seconds
 DETUNINGS = (-45.0, -30.0, -15.0, 0.0, 15.0, 30.0, 45.0)
 
 
@@ -253,6 +256,79 @@ def step_accuracy(args):
     return {"training": training, "recordings": R, "rows": rows}
 
 
+# ---- step: follow ----
+
+def drifting_clip(seed, cents_fn, seconds):
+    """tests/test_tuning_follow_host.py's clip: harmonic_clip's notes, every frequency times 2 ** (c(t) / 1200), the phase the running sum."""
+    import numpy as np
+    n = seconds * SR
+    rng = np.random.default_rng(9000 + seed)
+    notes = int(rng.integers(8, 11))
+    midi = rng.integers(40, 85, size=notes)
+    phase = rng.uniform(0.0, 2 * np.pi, size=(notes, 5))
+    scale = 2.0 ** (cents_fn(np.arange(n, dtype=np.float64) / SR) / 1200.0)
+    warped = (np.cumsum(scale) - scale[0]) / SR
+    y, total = np.zeros(n), 0.0
+    for i in range(notes):
+        f0 = 440.0 * 2.0 ** ((midi[i] - 69) / 12.0)
+        for h in range(1, 6):
+            y += np.sin(2 * np.pi * f0 * h * warped + phase[i, h - 1]) / h
+            total += 1.0 / h
+    return y / (0.5 * total)
+
+
+def step_follow(args):
+    import numpy as np
+    import torch
+    import ake_amd
+    from ake_amd import synthetic
+    est = ake_amd.KeyEstimator(None, SR, 5, device=DEV)
+    wf, sf = 25, 5
+    first, step = (wf - 1) // 2 * HOP, sf * HOP
+    drifts = (("ramp -35 .. +35", lambda t: -35.0 + 70.0 * t / 40.0), ("25 sin(2 pi t / 30 s) + 5", lambda t: 25.0 * np.sin(2 * np.pi * t / 30.0) + 5.0),
+              ("constant +20", lambda t: np.full_like(t, 20.0)))
+    audio = torch.from_numpy(np.stack([drifting_clip(i, fn, 40) for i, (_, fn) in enumerate(drifts)]).astype(np.float32)).to(DEV)
+    whole_c, whole_s = est.estimate_tuning(audio)
+    raw, strength, curve, n_win = est.tuning_track(audio)
+    centres = (np.arange(raw.shape[1]) * sf + (wf - 1) / 2) * HOP / SR
+    followed, len_f = ake_amd.retune_curve(audio, curve, first, step)
+    one, len_o = ake_amd.retune(audio, whole_c)
+    left_f = est.tuning_track(followed, len_f)
+    left_o = est.tuning_track(one, len_o)
+    after_c, after_s = est.estimate_tuning(followed, len_f)
+    table = []
+    for i, (name, fn) in enumerate(drifts):
+        live = lambda t, i=i: t[0][i, :int(t[3][i])].abs().max()
+        table.append({"drift": name, "whole": [round(float(whole_c[i]), 2), round(float(whole_s[i]), 2)],
+                      "window_error": round(float(np.abs(raw[i].cpu().double().numpy() - fn(centres)).max()), 2),
+                      "left_one_number": round(float(live(left_o)), 2), "left_follow": round(float(live(left_f)), 2),
+                      "strength_after": round(float(after_s[i]), 2)})
+    out = {"device": torch.cuda.get_device_name(0), "table": table}
+    clips = synthetic.make_batch_device(range(256), torch.device(DEV))[0]
+    recs = torch.cat([clips[:160].reshape(8, -1)] * 2, dim=1).contiguous()                # 8 x 10 min
+    for name, x in (("256 x 15 s", clips), ("8 x 10 min", recs)):
+        B, n = x.shape
+        mel = est.plan.logmag(x)
+        cv = ake_amd.tuning_track(mel, wf, sf)[2]
+        g = torch.Generator(device=DEV).manual_seed(1)
+        cv = (torch.rand(cv.shape, device=DEV, generator=g) * 90.0 - 45.0)
+        cents = cv[:, 0].contiguous()
+        idx = torch.arange(0, n, 1000, device=DEV)[None].expand(B, -1).contiguous()
+        ake_amd._lib.prof_enable("", True)
+        for _ in range(args.reps):
+            ake_amd.tuning_track(mel, wf, sf); ake_amd.retune_curve(x, cv, first, step); ake_amd.retune(x, cents)
+            ake_amd.retune_curve_positions(idx, cv, first, step)
+        kernels = {k: round(v[0] / v[1], 4) for k, v in ake_amd._lib.prof_results().items()}
+        ake_amd._lib.prof_enable("", False)
+        out[name] = {"frames": int(mel.shape[2]), "samples": int(n), "knots": int(cv.shape[1]), "kernel_mean_ms": kernels,
+                     "tuning_track_ms": timed(lambda: ake_amd.tuning_track(mel, wf, sf), args.reps),
+                     "estimate_ms": timed(lambda: ake_amd.estimate_tuning(mel), args.reps),
+                     "retune_curve_ms": timed(lambda: ake_amd.retune_curve(x, cv, first, step), args.reps),
+                     "retune_ms": timed(lambda: ake_amd.retune(x, cents), args.reps),
+                     "positions_ms": timed(lambda: ake_amd.retune_curve_positions(idx, cv, first, step), args.reps)}
+    return out
+
+
 # ---- report ----
 
 def report(res):
@@ -310,6 +386,8 @@ def report(res):
         md += [""]
     else:
         md += ["## Key tracks of detuned recordings", "", "Not measured.", ""]
+    if "follow" in res:
+        md += ["## A tuning that drifts (profiles/tuning_follow.md)", "", "```json", json.dumps(res["follow"], indent=1), "```", ""]
     return "\n".join(md)
 
 
@@ -326,7 +404,7 @@ def main():
     if args.step:
         import torch
         assert torch.cuda.is_available(), "tuning_bench needs the GPU"
-        res = {"errors": step_errors, "timings": step_timings, "accuracy": step_accuracy}[args.step](args)
+        res = {"errors": step_errors, "timings": step_timings, "accuracy": step_accuracy, "follow": step_follow}[args.step](args)
         torch.cuda.synchronize()
         print("RESULT " + json.dumps(res))
         return
