@@ -145,6 +145,8 @@ SYMBOLS = {
     "ake_profile_workspace_bytes": (_SZ, [_I, _I]),
     "ake_profile_windows": (_I, [_I, _I, _I]),
     "ake_profile_emissions_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _I, C.c_float, _P, _P, _P, _P, _P, _SZ, _P]),
+    "ake_profile_tuned_workspace_bytes": (_SZ, [_I, _I]),
+    "ake_profile_emissions_tuned_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _I, C.c_float, _P, _I64, _I64, _P, _P, _P, _P, _P, _SZ, _P]),
     "ake_key_changes_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
     "ake_stream_key_changes_state_bytes": (_SZ, [_I, _I]),
     "ake_stream_key_changes_f32": (_I, [_P, _SZ, _I, _I, _I64, _P, _I, _I64, _I, _I, _I, _I, _P, _P, _SZ, _I, _I64, _I, _P, _P, _P, _P]),

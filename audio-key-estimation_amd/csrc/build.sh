@@ -9,7 +9,7 @@ BUILD=build
 mkdir -p $BUILD
 HEADERS="common.h bf16_split.h philox.h keys.h cqt_stream.h profile.h changes.h pcnet_kernels.h pcnet_bwd_kernels.h pcnet_net.h pcnet_plan.h pcnet_forward.h pcnet_backward.h ../../include/ake_hip.h"
 pids=()
-for f in common.cpp cqt.hip pcnet.hip pipeline.hip optim.hip audio.hip loss.hip track.hip smooth.hip synth.hip tuning.hip profile.hip stream.hip stream_profile.hip changes.hip stream_changes.hip; do
+for f in common.cpp cqt.hip pcnet.hip pipeline.hip optim.hip audio.hip loss.hip track.hip smooth.hip synth.hip tuning.hip profile.hip profile_tuned.hip stream.hip stream_profile.hip changes.hip stream_changes.hip; do
   obj=$BUILD/${f%.*}.o
   stale=0
   [ -f "$obj" ] || stale=1
@@ -24,5 +24,5 @@ for f in common.cpp cqt.hip pcnet.hip pipeline.hip optim.hip audio.hip loss.hip 
   fi
 done
 for p in "${pids[@]:-}"; do [ -n "$p" ] && wait "$p"; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC $BUILD/common.o $BUILD/cqt.o $BUILD/pcnet.o $BUILD/pipeline.o $BUILD/optim.o $BUILD/audio.o $BUILD/loss.o $BUILD/track.o $BUILD/smooth.o $BUILD/synth.o $BUILD/tuning.o $BUILD/profile.o $BUILD/stream.o $BUILD/stream_profile.o $BUILD/changes.o $BUILD/stream_changes.o -o $OUT
+$HIPCC --offload-arch=gfx950 -shared -fPIC $BUILD/common.o $BUILD/cqt.o $BUILD/pcnet.o $BUILD/pipeline.o $BUILD/optim.o $BUILD/audio.o $BUILD/loss.o $BUILD/track.o $BUILD/smooth.o $BUILD/synth.o $BUILD/tuning.o $BUILD/profile.o $BUILD/profile_tuned.o $BUILD/stream.o $BUILD/stream_profile.o $BUILD/changes.o $BUILD/stream_changes.o -o $OUT
 echo "built $(realpath $OUT)"

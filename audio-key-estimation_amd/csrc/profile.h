@@ -148,4 +148,56 @@ __device__ __forceinline__ int prof_score_block(ProfScoreLds& s, bool live, Fram
     return k;
 }
 
+// ---- the tuned chroma (profile_tuned.hip): 36 octave-folded sums per frame, cut into 12 classes at boundaries that follow the tuning ----
+
+constexpr int kProfFolded = 36;      // folded positions: bin k sits at k % 36
+constexpr int kProfFoldBatch = 12;   // octaves whose loads go out together (12 octaves from C1 lie beyond any audio rate's range)
+
+// The sum of v over the bins p, p + 36, ... below pitches, in ascending octave.  load(k) gives L[k] of the frame; the loads of
+// kProfFoldBatch octaves are issued before the first is used.
+template <typename Load>
+__device__ __forceinline__ double prof_fold_sum(int p, int pitches, int compression, Load load) {
+    double s = 0.0;
+    for (int k = p; k < pitches; k += kProfFolded * kProfFoldBatch) {
+        float L[kProfFoldBatch];
+#pragma unroll
+        for (int q = 0; q < kProfFoldBatch; ++q) L[q] = k + kProfFolded * q < pitches ? load(k + kProfFolded * q) : 0.f;
+#pragma unroll
+        for (int q = 0; q < kProfFoldBatch; ++q)
+            if (k + kProfFolded * q < pitches) s = prof_add(s, L[q], compression);
+    }
+    return s;
+}
+
+// Where a window's cents put the class boundaries: class j holds the folded bins 3 j + n .. 3 j + n + 3 (mod 36), the first weighted
+// by w0 = 1 - g, the last by w3 = g, the two between whole.  cents as the kernel receives it: NaN reads as 0, beyond +-50 as +-50.
+struct ProfTunedCut {
+    int n;                      // -3 .. 0
+    double w0, w3;              // w0 in (0, 1], w3 in [0, 1)
+};
+
+__device__ __forceinline__ ProfTunedCut prof_tuned_cut(float cents) {
+#pragma clang fp contract(off)
+    double c = cents != cents ? 0.0 : static_cast<double>(cents);
+    c = c < -50.0 ? -50.0 : (c > 50.0 ? 50.0 : c);
+    const double u = 3.0 * c / 100.0 - 1.0;                       // delta - 1, in [-2.5, 0.5]
+    const double fl = floor(u);
+    const double g = u - fl;                                      // exact
+    return ProfTunedCut{static_cast<int>(fl), 1.0 - g, g};
+}
+
+// x_j = ((w0 FW[b0] + FW[b1]) + FW[b2]) + w3 FW[b3], every product rounded before it is added; a term of weight 0 is not added.
+__device__ __forceinline__ double prof_tuned_class(int j, const ProfTunedCut& cut, const double* fw) {
+#pragma clang fp contract(off)
+    const int b = 3 * j + cut.n + kProfFolded;                    // >= 33: the remainders below are those of a positive number
+    const double head = cut.w0 * fw[b % kProfFolded];
+    double x = head + fw[(b + 1) % kProfFolded];
+    x = x + fw[(b + 2) % kProfFolded];
+    if (cut.w3 != 0.0) {
+        const double tail = cut.w3 * fw[(b + 3) % kProfFolded];
+        x = x + tail;
+    }
+    return x;
+}
+
 }  // namespace ake_profile

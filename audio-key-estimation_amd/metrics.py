@@ -1481,7 +1481,7 @@ def profile_window_counts(frame_counts, window_frames, stride_frames):
     return torch.where(n < int(window_frames), torch.zeros_like(w), w)
 
 
-def profile_emissions(logmag, window_frames, stride_frames, counts=None, profiles="krumhansl", compression="log", sharpness=10.0):
+def profile_emissions(logmag, window_frames, stride_frames, counts=None, profiles="krumhansl", compression="log", sharpness=10.0, cents=None):
     """Key emissions without a net (Krumhansl-Schmuckler): every window's chroma correlated with the 24 rotations of a minor and a major
     key profile -> ``(chroma (R, W, 12), emissions (R, W, 24), key_id int32 (R, W), confidence (R, W))``, float64: the float64 model of
     ``ake_profile_emissions_f32``.
@@ -1507,10 +1507,24 @@ def profile_emissions(logmag, window_frames, stride_frames, counts=None, profile
 
     ``profiles``: a name of ``KEY_PROFILES`` or a (2, 12) tensor (``key_profile_table``).  ``sharpness = 10.0`` and
     ``compression = "log"`` are starting values that nobody has measured against annotated music; ``tools/profile_baseline.py`` scores
-    them and their neighbours on synthesised recordings (``profiles/key_profiles.md``)."""
+    them and their neighbours on synthesised recordings (``profiles/key_profiles.md``).
+
+    ``cents`` (default None: all of the above, untouched) is the tuned chroma, the float64 model of ``ake_profile_emissions_tuned_f32``:
+    the chroma of a recording that sits ``cents`` off A4 = 440 Hz, from its own transform, without retuning it.  One value, (R,) or
+    (R, W), rounded to float32 as the kernel receives it, NaN read as 0 and clamped to +-50 (``retune_reference``'s rule).  ``n_bins``
+    must then be a multiple of 36.  With ``F[r, t, p]`` the octave-folded sums (``folded_chroma``) and ``FW[p]`` their sum over a
+    window's frames in ascending t::
+
+        delta = 3.0 * c / 100.0,    n = floor(delta - 1.0) in {-3 .. 0},    g = delta - 1.0 - n in [0, 1)
+        x[r, w, j] = (((1 - g) * FW[b0] + FW[b1]) + FW[b2]) + g * FW[b3],    b_i = (3 j + n + i) % 36
+
+    with a term of weight 0 left out: the class boundaries move by ``delta`` bins and split the one bin each crosses.  At ``c = 0`` that
+    is ``FW[3j-1] + FW[3j] + FW[3j+1]``, the classes above; everything behind ``x`` is the same."""
     L = torch.as_tensor(logmag).detach().to(device="cpu", dtype=torch.float64)
     if L.dim() != 3 or L.shape[1] % TUNING_BINS_PER_SEMITONE != 0:
         raise ValueError(f"profile_emissions: logmag must be (R, n_bins, T) with n_bins a multiple of 3, got {tuple(L.shape)}")
+    if cents is not None and L.shape[1] % FOLDED_BINS != 0:
+        raise ValueError(f"profile_emissions: the tuned chroma (cents) needs n_bins a multiple of 36 (whole octaves), got {L.shape[1]}")
     mode = _profile_compression(compression)
     prof = key_profile_table(profiles)
     sharpness = float(sharpness)
@@ -1523,16 +1537,81 @@ def profile_emissions(logmag, window_frames, stride_frames, counts=None, profile
     n = torch.full((R,), T, dtype=torch.int64) if counts is None else torch.as_tensor(counts).detach().cpu().to(torch.int64).reshape(R).clamp(0, T)
     W = int(profile_window_counts(torch.tensor(T), wf, sf))
     n_win = profile_window_counts(n, wf, sf)
-    c = _profile_frame_chroma(L, mode)
+    c = _profile_frame_chroma(L, mode) if cents is None else _folded_frames(L, mode)
     c = torch.where((torch.arange(T)[None, :] < n[:, None])[:, :, None], c, torch.zeros_like(c))
-    x = torch.zeros((R, W, 12), dtype=torch.float64)
+    x = torch.zeros((R, W, c.shape[2]), dtype=torch.float64)
     if W > 0:
         start = torch.arange(W) * sf
         for i in range(T if wf == 0 else wf):                                                # ascending t (behind counts[r]: zeros)
             x += c[:, start + i, :]
+    if cents is not None:
+        x = tuned_class_sums(x, _tuned_cents(cents, R, W))
     live = torch.arange(W)[None, :] < n_win[:, None]                                         # (R, W)
     x = torch.where(live[:, :, None], x, torch.zeros_like(x))
     return _profile_score(x, live, prof, sharpness)
+
+
+FOLDED_BINS = 36                        # folded positions of the tuned chroma: bin k sits at k % 36
+
+
+def _folded_frames(L, mode):
+    """(R, n_bins, T) float64 log-CQT, n_bins a multiple of 36 -> F (R, T, 36): the bins of every folded position added in ascending
+    octave."""
+    R, P, T = L.shape
+    v = L if mode == 0 else torch.expm1(L) if mode == 1 else torch.expm1(L) ** 2
+    F = torch.zeros((R, T, FOLDED_BINS), dtype=torch.float64)
+    for k in range(P):                                                                       # ascending k: ascending octave at every p
+        F[:, :, k % FOLDED_BINS] += v[:, k, :]
+    return F
+
+
+def folded_chroma(logmag, counts=None, compression="log"):
+    """The 36 octave-folded sums of every frame -> (R, T, 36) float64: ``F[r, t, p]`` is the sum of ``v[r, p + 36 o, t]`` over the
+    octaves o in ascending order, ``v`` as in ``profile_emissions``; zeros in the frames at or behind ``counts[r]`` (default T).  What
+    the tuned chroma (``profile_emissions(cents=...)``) is cut from, and what ``profile_fold_kernel`` writes.  ``logmag`` (R, n_bins, T)
+    with ``n_bins`` a multiple of 36, else ``ValueError``."""
+    L = torch.as_tensor(logmag).detach().to(device="cpu", dtype=torch.float64)
+    if L.dim() != 3 or L.shape[1] % FOLDED_BINS != 0:
+        raise ValueError(f"folded_chroma: logmag must be (R, n_bins, T) with n_bins a multiple of 36, got {tuple(L.shape)}")
+    R, P, T = L.shape
+    F = _folded_frames(L, _profile_compression(compression))
+    if counts is not None:
+        n = torch.as_tensor(counts).detach().cpu().to(torch.int64).reshape(R).clamp(0, T)
+        F = torch.where((torch.arange(T)[None, :] < n[:, None])[:, :, None], F, torch.zeros_like(F))
+    return F
+
+
+def _tuned_cents(cents, R, W):
+    """``cents`` of the tuned chroma (one value, (R,) or (R, W)) -> float64 (R, W) as the kernel reads it: rounded to float32, NaN as
+    0, clamped to +-50."""
+    c = torch.as_tensor(cents).detach().to(device="cpu", dtype=torch.float32).to(torch.float64)
+    if c.dim() == 0:
+        c = c.expand(R, W)
+    elif c.dim() == 1 and c.shape[0] == R:
+        c = c[:, None].expand(R, W)
+    elif tuple(c.shape) != (R, W):
+        raise ValueError(f"profile_emissions: cents must be one value, ({R},) or ({R}, {W}), got {tuple(c.shape)}")
+    return torch.nan_to_num(c, nan=0.0).clamp(-RETUNE_MAX_CENTS, RETUNE_MAX_CENTS)
+
+
+def tuned_cut(cents):
+    """Where ``cents`` (float64, within +-50) put the class boundaries -> ``(n, g)``: class j holds the folded bins ``3 j + n ..
+    3 j + n + 3`` (mod 36), the first weighted ``1 - g``, the last ``g``."""
+    u = 3.0 * cents / 100.0 - 1.0
+    n = torch.floor(u)
+    return n.to(torch.int64), u - n
+
+
+def tuned_class_sums(FW, cents):
+    """Folded window sums FW (..., 36) float64 and their windows' cents (...) float64, as ``_tuned_cents`` returns them -> the twelve
+    class sums (..., 12), in the order of addition the kernel uses."""
+    n, g = tuned_cut(cents)
+    b = 3 * torch.arange(12) + n[..., None] + FOLDED_BINS                                      # >= 33
+    take = lambda i: torch.gather(FW, -1, (b + i) % FOLDED_BINS)
+    w0, w3 = (1.0 - g)[..., None], g[..., None]
+    x = w0 * take(0) + take(1)                                                               # (a product and a sum: two roundings)
+    x = x + take(2)
+    return torch.where(w3 != 0.0, x + w3 * take(3), x)
 
 
 def _profile_frame_chroma(L, mode):

@@ -187,7 +187,13 @@ class KeyTrack:
     frame from which the key of window w + 1 holds, where ``refined_source`` (``"smooth_key_id"`` or ``"key_id"``, the labels that were
     refined) names two different keys at the windows w and w + 1, else -1; ``change_gain`` and ``change_contrast`` (R, W - 1): what the
     frames' own scores gain over the grid's placement, and the mean per-frame advantage of each side's own key (near 0 or below: the
-    labels do not fit the frames).  All four are None otherwise.  ``segments``, ``change_points`` and ``boundary_score`` read them."""
+    labels do not fit the frames).  All four are None otherwise.  ``segments``, ``change_points`` and ``boundary_score`` read them.
+
+    ``track(method="profile", tuning=..., tuned_chroma=True)`` sets ``tuned_chroma``: the recordings were not retuned, the class
+    boundaries of the chroma were moved instead (``metrics.profile_emissions(cents=...)``).  ``tuning_cents`` then holds the cents
+    every window's chroma was cut by, (R,) float32, or (R, W) with ``tuning="follow"`` (the tuning track's curve on the key track's
+    windows), and ``tuning_strength`` the strength of the measurement in the same shape (None with given cents).  ``times``, the
+    geometry and every boundary are in the recording's own time: nothing is translated."""
     key: torch.Tensor
     tonic: torch.Tensor
     genre: torch.Tensor | None
@@ -218,6 +224,13 @@ class KeyTrack:
     change_gain: torch.Tensor | None = None
     change_contrast: torch.Tensor | None = None
     refined_source: str | None = None
+    tuned_chroma: bool = False
+
+    @property
+    def _stretch_cents(self):
+        """The cents the track's time axis is stretched by: ``tuning_cents``, but None on a tuned-chroma track, whose audio nobody
+        resampled."""
+        return None if self.tuned_chroma else self.tuning_cents
 
     def _tensors(self):
         """Every device tensor of the track; the two of a smooth track, the three of its posteriors, the two of a retuned track and
@@ -251,7 +264,7 @@ class KeyTrack:
                 return []
             k = torch.tensor(seconds, dtype=torch.float64) * self.sample_rate
             return (self._curve_positions(k, recording).cpu() / self.sample_rate).tolist()
-        rho = 1.0 if self.tuning_cents is None else 2.0 ** (float(self.tuning_cents[recording]) / 1200.0)
+        rho = 1.0 if self._stretch_cents is None else 2.0 ** (float(self._stretch_cents[recording]) / 1200.0)
         return [t / rho for t in seconds]
 
     def _source(self, what, smoothed, refined):
@@ -300,7 +313,7 @@ class KeyTrack:
         if self.tuning_curve is not None:                            # a followed track: the boundaries go through the curve, all at once
             rho = 1.0
         else:
-            rho = 1.0 if self.tuning_cents is None else 2.0 ** (float(self.tuning_cents[recording]) / 1200.0)
+            rho = 1.0 if self._stretch_cents is None else 2.0 ** (float(self._stretch_cents[recording]) / 1200.0)
         out, a = [], 0
         for b in range(n):
             if b + 1 < n and ids[b + 1] == ids[a]:
@@ -332,7 +345,7 @@ class KeyTrack:
             at = [w for w in range(n - 1) if frame[w] >= 0]
             own = self._own_seconds(recording, [frame[w] * self.hop / self.sample_rate for w in at])
             return [(t, ids[w], ids[w + 1], gain[w], contrast[w]) for t, w in zip(own, at)]
-        rho = 1.0 if self.tuning_cents is None else 2.0 ** (float(self.tuning_cents[recording]) / 1200.0)
+        rho = 1.0 if self._stretch_cents is None else 2.0 ** (float(self._stretch_cents[recording]) / 1200.0)
         return [(frame[w] * self.hop / self.sample_rate / rho, ids[w], ids[w + 1], gain[w], contrast[w]) for w in range(n - 1) if frame[w] >= 0]
 
     def boundary_score(self, annotations: KeyAnnotations, refined: bool | None = None, tolerance_seconds: float = 1.0):
@@ -358,9 +371,9 @@ class KeyTrack:
             raise ValueError(f"boundary_score: the track has {R} recordings, the annotations {annotations.seg_start.shape[0]}")
         start = annotations.seg_start.to(device=dev, dtype=torch.int64)
         rho = torch.ones((R, 1), dtype=torch.float64, device=dev)
-        if self.tuning_cents is not None:
-            start = metrics.scale_boundaries(start, self.tuning_cents)
-            rho = metrics.tuning_ratio(self.tuning_cents.to(dev)).reshape(R, 1)
+        if self._stretch_cents is not None:
+            start = metrics.scale_boundaries(start, self._stretch_cents)
+            rho = metrics.tuning_ratio(self._stretch_cents.to(dev)).reshape(R, 1)
         key = annotations.seg_key.to(device=dev, dtype=torch.int64)
         S = start.shape[1]
         count = annotations.seg_count.to(dev).to(torch.int64).reshape(R, 1).clamp(0, S)
@@ -410,8 +423,8 @@ class KeyTrack:
             tally.zero_(); changes.zero_()
             return TrackScore(truth, category, tally, changes)
         start = annotations.seg_start.to(device=dev, dtype=torch.int64)
-        if self.tuning_cents is not None:
-            start = metrics.scale_boundaries(start, self.tuning_cents)
+        if self._stretch_cents is not None:
+            start = metrics.scale_boundaries(start, self._stretch_cents)
         if self.tuning_curve is not None:
             start = metrics.curve_boundaries(start, self.tuning_curve, self.tuning_knot_first, self.tuning_knot_step)
         start = start.contiguous()
@@ -460,6 +473,9 @@ class KeyEstimator:
     ``min_strength`` hold the last strong value), then a resampler whose ratio is linear in the input position between the window
     centres (``ake_amd.retune_curve``, two launches), then the call on the retuned audio as with "auto".  Nothing is read back.
     Refused with a ``ValueError`` on ``frames=0`` estimators, which have a hop per clip.
+
+    ``tuned_chroma=True`` (``track(method="profile")`` and ``profile_key``, with any ``tuning``) retunes nothing: the profile method only
+    sums bins, so the one transform's chroma is cut at class boundaries moved by the cents (``track`` has the details).
 
     ``KeyEstimator(None, device=..., pitches=288)``: an estimator without a net, for the calls that need none --
     ``track(method="profile")``, ``stream(method="profile")``, ``profile_key`` and ``fit_key_profiles`` (and ``estimate_tuning``).
@@ -535,10 +551,11 @@ class KeyEstimator:
         cents = self._given_tuning(tuning, audio.shape[0], tuning_window_seconds, tuning_stride_seconds)
         return self._issue(lambda slot, a, l: self._run_wrapped(slot, *self._retuned(slot, a, l, cents, min_strength)[:2]), audio, lengths)
 
-    def _given_tuning(self, tuning, B, window_seconds=5.0, stride_seconds=1.0):
+    def _given_tuning(self, tuning, B, window_seconds=5.0, stride_seconds=1.0, retunes=True):
         """``tuning`` of ``__call__`` / ``track`` / ``profile_key`` checked -> None for "auto", the ``_Follow`` geometry for "follow",
-        else the (B,) float32 cents on the device."""
-        self._refuse_unretunable("tuning")
+        else the (B,) float32 cents on the device.  ``retunes=False``: for the tuned chroma, which resamples nothing."""
+        if retunes:
+            self._refuse_unretunable("tuning")
         if isinstance(tuning, str):
             if tuning == "follow":
                 return self._follow_geometry('tuning="follow"', window_seconds, stride_seconds)
@@ -684,7 +701,7 @@ class KeyEstimator:
               transition: torch.Tensor | None = None, signature_weight: float = 1.0, posteriors: bool = False,
               tuning=None, min_strength: float = 0.0, method: str = "net", profiles="krumhansl", compression: str = "log",
               profile_sharpness: float = 10.0, refine: bool = False, refine_slack_seconds: float | None = None,
-              tuning_window_seconds: float = 5.0, tuning_stride_seconds: float = 1.0) -> KeyTrack:
+              tuning_window_seconds: float = 5.0, tuning_stride_seconds: float = 1.0, tuned_chroma: bool = False) -> KeyTrack:
         """The key of long recordings over time: audio (R, n) or (R, C, n) float32 on the GPU -> ``KeyTrack``.  int16 audio is 16-bit
         PCM, as in ``__call__``.
 
@@ -736,13 +753,28 @@ class KeyEstimator:
         ``KeyTrack.segments``, ``change_points`` and ``boundary_score`` read; nothing else of the track changes with it.  The profile
         method reads the log-CQT it already holds.  The net method transforms the audio once more for it: the fused track call keeps
         its own transform inside its workspace and does not expose it.  How far the boundaries then lie from the
-        truth on synthesised recordings is in ``profiles/track_refine.md``."""
+        truth on synthesised recordings is in ``profiles/track_refine.md``.
+
+        ``tuned_chroma=True`` (``method="profile"`` with a ``tuning``; default False: everything above, same launches, same bits) meets
+        the detuning without retuning the audio: ONE transform, then the chroma's class boundaries are moved by the cents and split
+        the bin each crosses (``ake_amd.profile_emissions(cents=...)``; ``metrics.profile_emissions`` is the definition) -- no resampling
+        pass, no second transform, and every time of the track stays in the recording's own clock.  ``tuning="auto"``:
+        ``ake_amd.estimate_tuning`` on that transform (``min_strength`` as above), one value per recording.  A number or a (R,) tensor of
+        cents: used as given.  ``tuning="follow"``: ``ake_amd.tuning_track`` on the key track's own windows (``window_frames``,
+        ``stride_frames``), whose ``curve`` row gives every window its cents, held weak windows, unwrap and clamp included;
+        ``tuning_window_seconds`` and ``tuning_stride_seconds`` are not read in this mode.  ``KeyTrack.tuning_cents`` and
+        ``tuning_strength`` are filled and ``KeyTrack.tuned_chroma`` is set.  The smoother, the posteriors, ``score`` and
+        ``fit_key_transition`` take the emissions as before.  Refused with a ``ValueError``: ``method="net"`` (the net needs retuned
+        audio), ``tuning=None``, ``refine=True`` (the change-point kernel reads the uniform per-frame chroma) and a plan whose bins are
+        not a multiple of 36.  The estimator's top bin may lie anywhere: nothing is resampled."""
         if posteriors and not smooth:
             raise ValueError("track(posteriors=True) needs smooth=True: the posteriors belong to the smoothed track's emissions and transition")
+        if tuned_chroma and method == "net":
+            raise ValueError('track(tuned_chroma=True): only method="profile" sums bins; the net needs retuned audio (leave tuned_chroma at False)')
         if method == "profile":
             return self._track_profile(audio, lengths, rate, channel, window_seconds, stride_seconds, smooth, mean_key_seconds, transition,
                                        signature_weight, posteriors, tuning, min_strength, profiles, compression, profile_sharpness,
-                                       refine, refine_slack_seconds, tuning_window_seconds, tuning_stride_seconds)
+                                       refine, refine_slack_seconds, tuning_window_seconds, tuning_stride_seconds, bool(tuned_chroma))
         if method != "net":
             raise ValueError('track: method must be "net" or "profile"')
         self._need_net('KeyEstimator.track(method="net")')
@@ -1093,6 +1125,26 @@ class KeyEstimator:
         if self.net is not None and getattr(self.net, "local", False):
             raise ValueError(f"{what}: the profile method is not offered on an estimator of a --local net; build one with KeyEstimator(None, ...)")
 
+    def _refuse_untunable_chroma(self, what, tuning):
+        if tuning is None:
+            raise ValueError(f'{what} needs a tuning ("auto", "follow", a number of cents or a (B,) tensor of cents): it is the cents that '
+                             f'move the chroma\'s class boundaries')
+        if self.plan.n_bins % metrics.FOLDED_BINS != 0:
+            raise ValueError(f"{what}: the tuned chroma folds whole octaves, and this estimator's {self.plan.n_bins} bins are no multiple of 36")
+
+    def _tuned_cents(self, mel, frames, tuned, ws):
+        """The cents of the tuned chroma, measured on the transform the chroma is cut from -> ``(cents, strength)``: (R,) twice for
+        ``tuning="auto"`` (``ake_amd.estimate_tuning``; the ragged transform's zeros behind a row's frames add nothing, so no counts),
+        the tuning track's ``curve`` and ``strength`` (R, W) for a ``_Follow``, on its windows; given cents as they are, with no
+        strength."""
+        cents, min_strength = tuned
+        if isinstance(cents, _Follow):
+            _, strength, curve, _ = _tuning.tuning_track(mel, cents.window_frames, cents.stride_frames, frames, min_strength, workspace=ws)
+            return curve, strength
+        if cents is None:
+            return _tuning.estimate_tuning(mel, None, min_strength, workspace=ws)
+        return cents, None
+
     def _resampled(self, audio, lengths, rate, channel):
         if audio.dim() == 3 or (rate is not None and int(rate) != self.sample_rate):
             rs = get_resampler(self.sample_rate if rate is None else int(rate), self.sample_rate, self.device)
@@ -1102,8 +1154,13 @@ class KeyEstimator:
 
     def _track_profile(self, audio, lengths, rate, channel, window_seconds, stride_seconds, smooth, mean_key_seconds, transition,
                        signature_weight, posteriors, tuning, min_strength, profiles, compression, sharpness, refine=False,
-                       refine_slack_seconds=None, tuning_window_seconds=5.0, tuning_stride_seconds=1.0):
+                       refine_slack_seconds=None, tuning_window_seconds=5.0, tuning_stride_seconds=1.0, tuned_chroma=False):
         self._refuse_unprofilable('track(method="profile")')
+        if tuned_chroma:
+            self._refuse_untunable_chroma('track(tuned_chroma=True)', tuning)
+            if refine:
+                raise ValueError("track(tuned_chroma=True): refine=True is not offered with it; the change-point kernel reads the uniform "
+                                 "per-frame chroma")
         if float(signature_weight) != 1.0:
             raise ValueError('track(method="profile"): signature_weight weighs the net\'s key head, which this method does not run; leave it at 1')
         mode = metrics._profile_compression(compression)
@@ -1115,13 +1172,19 @@ class KeyEstimator:
         wf = track_window_frames(int(round(window_seconds * self.sample_rate)), self.plan.hop_length)
         sf = track_stride_frames(stride_seconds, self.frames)
         smoothing = (self._transition(sf, mean_key_seconds, transition), bool(posteriors)) if smooth else None
-        cents = None if tuning is None else self._given_tuning(tuning, audio.shape[0], tuning_window_seconds, tuning_stride_seconds)
+        if tuned_chroma and isinstance(tuning, str) and tuning == "follow":
+            cents = _Follow(wf, sf)                                  # the tuning track runs on the key track's own windows
+        else:
+            cents = None if tuning is None else self._given_tuning(tuning, audio.shape[0], tuning_window_seconds, tuning_stride_seconds,
+                                                                   retunes=not tuned_chroma)
         refining = (self._refining(sf, refine_slack_seconds, profiles, compression)[0], prof, mode) if refine else None
 
         def run(slot, a, l):
             used = strength = None
             if self.streams > 1:                                     # (a user's table is a fresh tensor of the caller's stream)
                 prof.record_stream(torch.cuda.current_stream(self.device))
+            if tuned_chroma:                                         # one transform; nothing is retuned
+                return self._run_profile_track(slot, a, l, wf, sf, smoothing, prof, mode, sharpness, tuned=(cents, float(min_strength)))
             if tuning is not None:
                 a, l, used, strength = self._retuned(slot, a, l, cents, min_strength)
             track = self._run_profile_track(slot, a, l, wf, sf, smoothing, prof, mode, sharpness, refining)
@@ -1147,6 +1210,14 @@ class KeyEstimator:
             frames = (1 + lengths.clamp(0, n) // self.plan.hop_length).clamp(max=T).to(torch.int32)
         return self.plan.logmag(audio, lengths=lengths, workspace=ws), frames, ws
 
+    def _tuned_bytes(self, R, T, wf, sf):
+        """Workspace of the tuned chroma's launches on (R, T) frames: the tuning measurement's and ``ake_profile_emissions_tuned_f32``'s."""
+        L = _lib.lib()
+        nbytes = int(L.ake_profile_tuned_workspace_bytes(R, T))
+        if nbytes == 0:
+            _lib.check(-1, "ake_profile_tuned_workspace_bytes")
+        return max(nbytes, int(L.ake_tuning_workspace_bytes(R, T)), int(L.ake_tuning_track_workspace_bytes(R, T, wf, sf)) if wf > 0 else 0)
+
     _sig_tables = {}
 
     @classmethod
@@ -1158,7 +1229,7 @@ class KeyEstimator:
             cls._sig_tables[key] = torch.tensor([rows.index(m) for m in metrics.KEY_MAJOR_TONIC], dtype=torch.int32, device=device)
         return cls._sig_tables[key]
 
-    def _run_profile_track(self, slot, audio, lengths, wf, sf, smoothing, prof, mode, sharpness, refining=None):
+    def _run_profile_track(self, slot, audio, lengths, wf, sf, smoothing, prof, mode, sharpness, refining=None, tuned=None):
         dev = self.device
         R, n = audio.shape
         hop = self.plan.hop_length
@@ -1171,8 +1242,13 @@ class KeyEstimator:
                              wf * hop / self.sample_rate, sf * hop / self.sample_rate, emissions=f32(R, 0, 24))
         else:
             sbytes = 0 if smoothing is None else self._smooth_workspace_bytes(R, W, smoothing[1])
-            mel, frames, ws = self._profile_logmag(slot, audio, lengths, sbytes)
-            chroma, emissions, key_id, conf = _keyprofile._launch(mel, False, frames, wf, sf, W, prof, mode, sharpness, ws)
+            if tuned is None:
+                mel, frames, ws = self._profile_logmag(slot, audio, lengths, sbytes)
+                chroma, emissions, key_id, conf = _keyprofile._launch(mel, False, frames, wf, sf, W, prof, mode, sharpness, ws)
+            else:                                                    # the tuned chroma: the cents from this transform, then the cut
+                mel, frames, ws = self._profile_logmag(slot, audio, lengths, max(sbytes, self._tuned_bytes(R, self.plan.num_frames(n), wf, sf)))
+                cents, strength = self._tuned_cents(mel, frames, tuned, ws)
+                chroma, emissions, key_id, conf = _keyprofile._launch(mel, False, frames, wf, sf, W, prof, mode, sharpness, ws, cents)
             counts = torch.full((R,), W, dtype=torch.int32, device=dev) if frames is None else \
                 track_counts(frames.to(torch.int64), wf, sf).to(torch.int32)
             tonic = torch.maximum(emissions[..., :12], emissions[..., 12:])
@@ -1183,6 +1259,12 @@ class KeyEstimator:
             track = KeyTrack(chroma, tonic, None, key_id, sig, tonic_id, conf, counts, times, wf * hop / self.sample_rate,
                              sf * hop / self.sample_rate, emissions=emissions)
         track.hop, track.window_frames, track.stride_frames, track.sample_rate = int(hop), int(wf), int(sf), self.sample_rate
+        if tuned is not None:
+            track.tuned_chroma = True
+            if W == 0:                                               # no window, no transform: given cents stay, nothing was measured
+                cents, strength = (tuned[0], None) if isinstance(tuned[0], torch.Tensor) else \
+                    (f32(R, 0), f32(R, 0)) if isinstance(tuned[0], _Follow) else (f32(R).zero_(), f32(R).zero_())
+            track.tuning_cents, track.tuning_strength = cents, strength
         if smoothing is not None:
             track.smooth_key_id = i32(R, W)
             if smoothing[1]:
@@ -1200,25 +1282,42 @@ class KeyEstimator:
     @torch.no_grad()
     def profile_key(self, audio: torch.Tensor, lengths: torch.Tensor | None = None, rate: int | None = None, channel: int = 0,
                     tuning=None, min_strength: float = 0.0, profiles="krumhansl", compression: str = "log", sharpness: float = 10.0,
-                    tuning_window_seconds: float = 5.0, tuning_stride_seconds: float = 1.0):
+                    tuning_window_seconds: float = 5.0, tuning_stride_seconds: float = 1.0, tuned_chroma: bool = False):
         """One key per clip without a net -> ``(key_id int32 (B,), confidence (B,), chroma (B, 12), emissions (B, 24))`` on the device:
         one transform at the estimator's plan, then ``ake_amd.profile_emissions`` in its whole-clip mode (``window_frames=0``: every
         clip's chroma over its own ``1 + lengths[i] // hop`` frames; ``metrics.profile_emissions`` is the definition).  ``audio``,
         ``lengths``, ``rate``, ``channel``, ``tuning``, ``min_strength``, ``streams`` > 1 and ``join()`` as in ``__call__``; ``profiles``,
         ``compression`` and ``sharpness`` as in ``ake_amd.profile_emissions``.  ``key_id`` is -1 for a silent clip.  Refused with a
-        ``ValueError`` on ``frames=0`` estimators."""
+        ``ValueError`` on ``frames=0`` estimators.
+
+        ``tuned_chroma=True`` (with a ``tuning``, else ``ValueError``; bins that are no multiple of 36 likewise): the clip is not
+        retuned; one transform, then ``ake_amd.profile_emissions(cents=...)`` cuts the chroma by the cents (``track`` has the details).
+        ``"auto"`` and ``"follow"`` both use the whole-clip estimate (``ake_amd.estimate_tuning`` with ``min_strength``), a number or a
+        (B,) tensor is used as given; ``tuning_window_seconds`` and ``tuning_stride_seconds`` are not read."""
         self._refuse_unprofilable("profile_key")
+        if tuned_chroma:
+            self._refuse_untunable_chroma("profile_key(tuned_chroma=True)", tuning)
         mode = metrics._profile_compression(compression)
         sharpness = float(sharpness)
         if not sharpness > 0.0:
             raise ValueError("profile_key: sharpness must be positive")
         prof = _keyprofile.device_profiles(profiles, self.device)
         audio, lengths = self._resampled(audio, lengths, rate, channel)
-        cents = None if tuning is None else self._given_tuning(tuning, audio.shape[0], tuning_window_seconds, tuning_stride_seconds)
+        if tuned_chroma and isinstance(tuning, str) and tuning == "follow":
+            cents = None                                             # one window, the clip: the whole-clip estimate, as "auto"
+        else:
+            cents = None if tuning is None else self._given_tuning(tuning, audio.shape[0], tuning_window_seconds, tuning_stride_seconds,
+                                                                   retunes=not tuned_chroma)
 
         def run(slot, a, l):
             if self.streams > 1:
                 prof.record_stream(torch.cuda.current_stream(self.device))
+            if tuned_chroma:                                         # one transform; nothing is retuned
+                R, n = a.shape
+                mel, frames, ws = self._profile_logmag(slot, a, l, self._tuned_bytes(R, self.plan.num_frames(n), 0, 1))
+                used = self._tuned_cents(mel, frames, (cents, float(min_strength)), ws)[0]
+                chroma, emissions, key_id, conf = _keyprofile._launch(mel, False, frames, 0, 1, 1, prof, mode, sharpness, ws, used)
+                return key_id[:, 0], conf[:, 0], chroma[:, 0], emissions[:, 0]
             if tuning is not None:
                 a, l = self._retuned(slot, a, l, cents, min_strength)[:2]
             mel, frames, ws = self._profile_logmag(slot, a, l)

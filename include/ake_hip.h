@@ -918,6 +918,31 @@ int ake_profile_emissions_f32(const float* mel_dev, int frames_major, int record
                               float sharpness, float* chroma_out, float* emissions_out, int32_t* key_id_out, float* confidence_out,
                               void* workspace, size_t workspace_bytes, ake_stream_t stream);
 
+/* Tuned chroma (csrc/profile_tuned.hip): ake_profile_emissions_f32 on a detuned recording without retuning it.  The class boundaries
+ * move by the detuning and split the one bin each crosses.  Host model: metrics.profile_emissions(cents=...).  Every argument of
+ * ake_profile_emissions_f32 means what it means there, with the same refusals and outputs, except that pitches must be a multiple of 36
+ * (whole octaves; AKE_ERR_UNSUPPORTED otherwise).  Window (r, w) reads its detuning from
+ * cents_dev[r * cents_rec_stride + w * cents_win_stride] (float32 cents; NaN reads as 0, beyond +-50 as +-50; strides in elements, not
+ * negative; a window stride of 0 gives one value per recording); only windows in front of a recording's count are read.  A null
+ * cents_dev is AKE_ERR_UNSUPPORTED.  With p = k % 36 the folded position of bin k:
+ *   F[r][t][p]  = sum of v[r][p + 36 o][t] over the octaves o, ascending
+ *   FW[p]       = sum of F[r][t][p] over the window's frames, ascending t
+ *   delta = 3.0 * c / 100.0,  n = floor(delta - 1.0) in {-3 .. 0},  g = delta - 1.0 - n in [0, 1)
+ *   x[r][w][j]  = (((1 - g) FW[b0] + FW[b1]) + FW[b2]) + g FW[b3],   b_i = (3 j + n + i) % 36
+ * in double, every product rounded before it is added, a term of weight 0 left out.  At c = 0 that is FW[3j-1] + FW[3j] + FW[3j+1],
+ * ake_profile_emissions_f32's classes (in another order of addition).  Everything behind x is that entry's scoring.
+ * Two launches: blocks of (64 frames, one recording) write F in double into the workspace (zeros for frames at or behind n_r, so what
+ * the workspace held never matters), then one block per (window, recording) adds its frames, cuts the classes and scores them.  No
+ * atomics: two runs on the same input are bit-identical, and so are the two layouts.  The workspace (8-byte aligned) holds F:
+ * ake_profile_tuned_workspace_bytes (0 for recordings outside 1..65535 or frames < 1); too small or null: AKE_ERR_WORKSPACE.  A refused
+ * call launches nothing. */
+size_t ake_profile_tuned_workspace_bytes(int recordings, int frames);
+int ake_profile_emissions_tuned_f32(const float* mel_dev, int frames_major, int recordings, int pitches, int frames, const int32_t* counts_dev,
+                                    int window_frames, int stride_frames, int windows, const float* profiles_dev /* [2][12] */,
+                                    int compression, float sharpness, const float* cents_dev, int64_t cents_rec_stride,
+                                    int64_t cents_win_stride, float* chroma_out, float* emissions_out, int32_t* key_id_out,
+                                    float* confidence_out, void* workspace, size_t workspace_bytes, ake_stream_t stream);
+
 /* The profile method and a tuning meter on a stream of audio in lockstep (csrc/stream_profile.hip; KeyEstimator.stream(method="profile",
  * tuning_meter=True)).  Host models: metrics.stream_profile and metrics.stream_tuning.
  * state_dev holds, per recording, a ring of per-frame chroma, double [recordings][ring_frames][12] with the stream's frame t in row
